@@ -20,13 +20,21 @@ max-over-ranks of the timing / the status histogram).  Default = the north-star 
 ("a batch of 4096 hunter instances at 1/2/4/8 MI355X": 4096 split into contiguous shards, 512 per GPU at 8 —
 configs[3]'s shape); `--weak` keeps `--batch` instances on every GPU instead (4096 x N in total).  `--gather` additionally
 times an RCCL all-gather of the status words and the solution trajectories after the timed region and reports the
-throughput with it included.  Prints ONE JSON line on rank 0 (with `roofline` and `cpu_baseline` at any world size).
+throughput with it included.  Prints ONE JSON line on rank 0.
+
+A plain run does only what the headline needs: set-up, warm-up, the timed steps and the line (`metric`, `value`, `unit`,
+`higher_is_better`, `dtype`, `ms_per_step`, ...).  `--full` adds everything else the line used to carry, at any world size:
+per-kernel phase times and `roofline` (extra un-timed steps on one stream), `halves`, `solver_state` (WBC optimality, status
+histograms), the secondary figures (configs[3] / configs[4] shares, full tick, backtracking, standing batch, config-1 latency;
+`--no-extras` drops them) and `cpu_baseline` (`--no-cpu-baseline` drops it).  `--dump-outputs DIR` writes what the timed path
+computed in its last step as DIR/<name>.npy (float64; a fixed, seeded sample of instances where the whole would exceed 32 MiB).
 """
 from __future__ import annotations
 
 import argparse
 import json
 import os
+import subprocess
 import sys
 import time
 from pathlib import Path
@@ -379,11 +387,43 @@ def source_fingerprint():
     return h.hexdigest()
 
 
+DUMP_BYTES = 32 << 20   # --dump-outputs: above this the instances are sampled (the files stay far below 64 MiB in all)
+DUMP_SEED = 20240611
+
+
+def timed_path_outputs(s):
+    """What a caller of hb_step_resident receives after a step, one row per instance: the MPC iterate (x, u), the WBC solution and
+    status, the MPC status and the performance record (cost, dynamics SSE, equality SSE, step size)."""
+    x, u = s.get_solution()
+    sol, wbc_status = s.get_wbc_solution()
+    return {"mpc_x": x, "mpc_u": u, "wbc_solution": sol, "wbc_status": wbc_status, "mpc_status": s.mpc_status(),
+            "mpc_performance": s.get_performance()}
+
+
+def dump_outputs(outputs, out_dir, suffix=""):
+    """Writes the arrays of timed_path_outputs as out_dir/<name><suffix>.npy in float64.  Where all instances together would pass
+    DUMP_BYTES, the same fixed, seeded sample of instances is taken from every array; `instances` names the rows written.
+    -> {name: shape}"""
+    arrays = {k: np.asarray(v, dtype=np.float64) for k, v in outputs.items()}
+    B = next(iter(arrays.values())).shape[0]
+    row_bytes = 8 * (1 + sum(a[0].size for a in arrays.values()))
+    n = max(1, min(B, DUMP_BYTES // row_bytes))
+    idx = np.arange(B) if n == B else np.sort(np.random.default_rng(DUMP_SEED).choice(B, n, replace=False))
+    arrays = {k: a[idx] for k, a in arrays.items()}
+    arrays["instances"] = idx.astype(np.float64)
+    out = Path(out_dir)
+    out.mkdir(parents=True, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(out / f"{k}{suffix}.npy", np.ascontiguousarray(a))
+    return {k: list(a.shape) for k, a in arrays.items()}
+
+
 def launch_ranks_if_needed(args):
     """`--gpus N` is the number of ranks of the job (one process per GPU).  Under `torch.distributed.run` (the
-    driver's launch line) WORLD_SIZE must equal it; started bare with N > 1, this process replaces itself by
-    `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 bench.py <same arguments>`, after
-    checking that the node has N GPUs.  It never prints an n_gpus = 1 line for a request of N."""
+    driver's launch line) WORLD_SIZE must equal it; started bare with N > 1, this process starts
+    `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 bench.py <same arguments>` as a child,
+    after checking that the node has N GPUs, and exits with its status (a fresh process: this one has already opened the HIP
+    runtime to count the devices).  It never prints an n_gpus = 1 line for a request of N."""
     if args.gpus < 1:
         raise SystemExit("bench.py: --gpus must be >= 1")
     ws = os.environ.get("WORLD_SIZE")
@@ -405,7 +445,7 @@ def launch_ranks_if_needed(args):
     env = dict(os.environ)
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")   # dmabuf IPC: RCCL between the ranks' processes needs it on this stack
     sys.stdout.flush()
-    os.execvpe(cmd[0], cmd, env)
+    raise SystemExit(subprocess.call(cmd, env=env))
 
 
 def main():
@@ -423,8 +463,14 @@ def main():
     ap.add_argument("--random-cmd", action="store_true", help="configs[3]: per-instance cmd_vel, gait from walkGait")
     ap.add_argument("--hierarchical", action="store_true", help="configs[4]: HierarchicalWbc (3-priority HoQp cascade) instead of WeightedWbc")
     ap.add_argument("--gather", action="store_true", help="time an RCCL all-gather of status + trajectories (multi-GPU)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the full-tick figure and the config-1 latency block")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything besides the headline: phase times + roofline, halves, solver_state, the "
+                         "secondary figures and the CPU baseline (a plain run: set-up, warm-up, the timed steps, the line)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the secondary figures (shares, full tick, backtracking, "
+                                                               "standing batch, config-1 latency)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last step as DIR/<name>.npy (float64)")
     args = ap.parse_args()
     launch_ranks_if_needed(args)
 
@@ -488,57 +534,63 @@ def main():
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     chunk_counters = s.chunk_counters()
+    # what the timed path computed in its last step, read before anything else runs on the solver
+    dumped = None
+    if args.dump_outputs:
+        dumped = dump_outputs(timed_path_outputs(s), args.dump_outputs, f"_rank{rank}" if world > 1 else "")
     elapsed = sharding.max_over_ranks(elapsed, dist, device="cuda")
     # who took part: an RCCL SUM all-reduce of 1 and the gathered device identities (no derived figure: facts the launch can be checked against)
     rccl_ranks, devices = sharding.participants(sharding.device_identity(local_rank), dist, device="cuda")
     ms_per_step = 1e3 * elapsed / args.steps
     value = total_instances * args.steps / elapsed
 
-    # per-kernel device time: HIP events recorded on the library's own MPC / WBC streams (hb_get_stats), averaged
-    # over extra un-timed steps with a sync after each so the events are complete.
-    s.set_chunks(1)  # phase times are recorded on one stream
-    phases = {"k_lq": 0.0, "k_ric_bwd": 0.0, "k_ric_fwd": 0.0, "linesearch": 0.0, "k_wbc": 0.0, "mpc_total": 0.0}
-    n_prof = 10
-    for _ in range(n_prof):
-        s.step_resident()
-        st = s.stats()
-        phases["k_lq"] += st["ms_lq"] / n_prof
-        phases["k_ric_bwd"] += st["ms_riccati_bwd"] / n_prof
-        phases["k_ric_fwd"] += st["ms_riccati_fwd"] / n_prof
-        phases["linesearch"] += st["ms_linesearch"] / n_prof
-        phases["k_wbc"] += st["ms_wbc"] / n_prof
-        phases["mpc_total"] += st["ms_mpc_total"] / n_prof
-    perf = s.get_performance()
-    sol, status = s.get_wbc_solution()
-    mpc_status = s.mpc_status()
-    n_nodes = s.get_references()["n_nodes"]
-    # Optimality of the WBC solutions of the last update, from the product's own rigid-body terms (hb_eval_rbd) — SURVEY.md 8d: the
-    # equation of motion M a + nle = S' tau + J' F is the equality block of the QP; torque limits and the friction pyramid its inequalities.
-    # (stationarity needs the multipliers, which stay on the device: that half of the KKT conditions is held by the oracle tests)
-    Mq, nle, Jc, _ = s.eval_rbd(w["rbd"])
-    acc, Fc, tau = sol[:, :16], sol[:, 16:28], sol[:, 28:38]
-    eom = np.einsum("bij,bj->bi", Mq, acc) + nle - np.einsum("bki,bk->bi", Jc, Fc)
-    eom[:, 6:] -= tau
-    wbc_eom_res = float(np.abs(eom).max())
-    tl = np.asarray(params["config"]["torque_limits"], dtype=float)
-    wbc_tau_viol = float(max(0.0, (np.abs(tau) - np.tile(tl, 2)[None, :]).max()))
-    mu = float(params["config"]["wbc_friction_mu"])
-    F3 = Fc.reshape(-1, 4, 3)
-    wbc_cone_viol = float(max(0.0, np.maximum.reduce([np.abs(F3[..., 0]) - mu * F3[..., 2], np.abs(F3[..., 1]) - mu * F3[..., 2], -F3[..., 2]]).max()))
-    wbc_eom_res, wbc_tau_viol, wbc_cone_viol = (float(v) for v in sharding.max_vector_over_ranks([wbc_eom_res, wbc_tau_viol, wbc_cone_viol], dist, device="cuda"))
-    hist = sharding.sum_over_ranks([int((status == k).sum()) for k in range(4)], dist, device="cuda")
-    mpc_hist = sharding.sum_over_ranks([int((mpc_status == k).sum()) for k in range(4)], dist, device="cuda")
-    wbc_iters = s.get_wbc_iterations()            # active-set iterations of the last WBC solve (nWSR of the reference)
-    it_edges = [0, 16, 20, 24, 28, 32, 40, 64, 1 << 30]
-    it_hist = sharding.sum_over_ranks([int(((wbc_iters >= lo) & (wbc_iters < hi)).sum()) for lo, hi in zip(it_edges, it_edges[1:])],
-                                      dist, device="cuda")
-    step_hist = sharding.sum_over_ranks([int((perf[:, 3] == 1.0).sum()), int(((perf[:, 3] < 1.0) & (perf[:, 3] > 0.0)).sum()),
-                                         int((perf[:, 3] == 0.0).sum())], dist, device="cuda")
+    if args.full:
+        # per-kernel device time: HIP events recorded on the library's own MPC / WBC streams (hb_get_stats), averaged
+        # over extra un-timed steps with a sync after each so the events are complete.
+        s.set_chunks(1)  # phase times are recorded on one stream
+        phases = {"k_lq": 0.0, "k_ric_bwd": 0.0, "k_ric_fwd": 0.0, "linesearch": 0.0, "k_wbc": 0.0, "mpc_total": 0.0}
+        n_prof = 10
+        for _ in range(n_prof):
+            s.step_resident()
+            st = s.stats()
+            phases["k_lq"] += st["ms_lq"] / n_prof
+            phases["k_ric_bwd"] += st["ms_riccati_bwd"] / n_prof
+            phases["k_ric_fwd"] += st["ms_riccati_fwd"] / n_prof
+            phases["linesearch"] += st["ms_linesearch"] / n_prof
+            phases["k_wbc"] += st["ms_wbc"] / n_prof
+            phases["mpc_total"] += st["ms_mpc_total"] / n_prof
+        perf = s.get_performance()
+        sol, status = s.get_wbc_solution()
+        mpc_status = s.mpc_status()
+        n_nodes = s.get_references()["n_nodes"]
+        # Optimality of the WBC solutions of the last update, from the product's own rigid-body terms (hb_eval_rbd) — SURVEY.md 8d: the
+        # equation of motion M a + nle = S' tau + J' F is the equality block of the QP; torque limits and the friction pyramid its inequalities.
+        # (stationarity needs the multipliers, which stay on the device: that half of the KKT conditions is held by the oracle tests)
+        Mq, nle, Jc, _ = s.eval_rbd(w["rbd"])
+        acc, Fc, tau = sol[:, :16], sol[:, 16:28], sol[:, 28:38]
+        eom = np.einsum("bij,bj->bi", Mq, acc) + nle - np.einsum("bki,bk->bi", Jc, Fc)
+        eom[:, 6:] -= tau
+        wbc_eom_res = float(np.abs(eom).max())
+        tl = np.asarray(params["config"]["torque_limits"], dtype=float)
+        wbc_tau_viol = float(max(0.0, (np.abs(tau) - np.tile(tl, 2)[None, :]).max()))
+        mu = float(params["config"]["wbc_friction_mu"])
+        F3 = Fc.reshape(-1, 4, 3)
+        wbc_cone_viol = float(max(0.0, np.maximum.reduce([np.abs(F3[..., 0]) - mu * F3[..., 2], np.abs(F3[..., 1]) - mu * F3[..., 2], -F3[..., 2]]).max()))
+        wbc_eom_res, wbc_tau_viol, wbc_cone_viol = (float(v) for v in sharding.max_vector_over_ranks([wbc_eom_res, wbc_tau_viol, wbc_cone_viol], dist, device="cuda"))
+        hist = sharding.sum_over_ranks([int((status == k).sum()) for k in range(4)], dist, device="cuda")
+        mpc_hist = sharding.sum_over_ranks([int((mpc_status == k).sum()) for k in range(4)], dist, device="cuda")
+        wbc_iters = s.get_wbc_iterations()            # active-set iterations of the last WBC solve (nWSR of the reference)
+        it_edges = [0, 16, 20, 24, 28, 32, 40, 64, 1 << 30]
+        it_hist = sharding.sum_over_ranks([int(((wbc_iters >= lo) & (wbc_iters < hi)).sum()) for lo, hi in zip(it_edges, it_edges[1:])],
+                                          dist, device="cuda")
+        step_hist = sharding.sum_over_ranks([int((perf[:, 3] == 1.0).sum()), int(((perf[:, 3] < 1.0) & (perf[:, 3] > 0.0)).sum()),
+                                             int((perf[:, 3] == 0.0).sum())], dist, device="cuda")
 
     # optional: what a gather of the per-instance outputs over xGMI would add
     gather = None
     if args.gather and dist is not None:
         xs, us = s.get_solution()
+        _, status = s.get_wbc_solution()
         payload = torch.from_numpy(np.concatenate([xs.ravel(), us.ravel()])).cuda()
         st_t = torch.from_numpy(status.astype(np.int32)).cuda()
         out_p = torch.empty(world * payload.numel(), dtype=payload.dtype, device="cuda")
@@ -561,7 +613,7 @@ def main():
 
     extras = {}
     s.close()
-    if rank == 0 and world == 1 and not args.no_extras:
+    if args.full and rank == 0 and world == 1 and not args.no_extras:
         for key, kw in (("with_configs3_share", dict(B=512, N=100, random_cmd=True, hierarchical=False)),
                         ("with_configs4_share", dict(B=1024, N=200, random_cmd=False, hierarchical=True))):
             try:
@@ -592,41 +644,6 @@ def main():
             extras["config1_latency_ms"] = {"error": repr(e)}
 
     if rank == 0:
-        dom = max(("k_lq", "k_ric_bwd", "k_ric_fwd"), key=lambda k: phases[k])
-        alg_bytes = BYTES_PER_NODE[dom] * int(n_nodes.sum())
-        achieved = alg_bytes / (phases[dom] * 1e-3) / 1e9
-        traffic, traffic_source = None, None
-        pmc = ROOT / "profiles" / "pmc_latest.json"
-        if pmc.exists() and B == 4096 and N == 100 and not args.random_cmd and not args.hierarchical:
-            try:
-                pj = json.loads(pmc.read_text())
-                stamp = f"tag {pj.get('tag')}, commit {pj.get('git_head')}, kernel sources sha256 {str(pj.get('source_sha256'))[:12]}"
-                # (the counter file names kernels as the profiler does: the LQ approximation runs as k_lq_trip since round 6)
-                if "k_lq_trip" in pj:
-                    pj["k_lq"] = pj["k_lq_trip"]
-                if pj.get("source_sha256") == source_fingerprint():
-                    traffic = pj.get(dom, {}).get("hbm_bytes_per_launch")
-                    traffic_source = (f"profiles/pmc_latest.json ({stamp} = the running tree's kernel sources): rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE "
-                                      "passes over this workload, collected in a separate run (counters cannot be read inside the timed process), "
-                                      "NOT measured in this run")
-                else:   # a counter file collected on other kernel sources says nothing about this run
-                    traffic_source = (f"profiles/pmc_latest.json ({stamp}) was collected on DIFFERENT kernel sources than the running tree "
-                                      f"(sha256 {source_fingerprint()[:12]}): traffic dropped")
-            except Exception:
-                traffic = None
-        per_kernel = {k: {"ms": phases[k], "algorithmic_GBs": BYTES_PER_NODE[k] * int(n_nodes.sum()) / (phases[k] * 1e-3) / 1e9,
-                          "frac_of_hbm_peak": BYTES_PER_NODE[k] * int(n_nodes.sum()) / (phases[k] * 1e-3) / 1e9 / HBM_PEAK_GBS}
-                      for k in ("k_lq", "k_ric_bwd", "k_ric_fwd")}
-        # what each kernel REALLY moves (FETCH_SIZE / WRITE_SIZE counter passes, same source and caveat as roofline.traffic) over
-        # this run's launch time: k_ric_fwd is the kernel that is HBM bound, on 2 x the bytes the 8d formula grants it
-        if traffic is not None:
-            for k, v in per_kernel.items():
-                cb = pj.get(k, {}).get("hbm_bytes_per_launch")
-                if cb:
-                    v["counter_bytes_per_launch"] = cb
-                    v["counter_GBs"] = cb / (phases[k] * 1e-3) / 1e9
-                    v["counter_frac_of_hbm_peak"] = v["counter_GBs"] / HBM_PEAK_GBS
-                    v["counter_over_algorithmic"] = cb / (BYTES_PER_NODE[k] * int(n_nodes.sum()))
         out = {
             "metric": metric_string(strong, total_instances, B, world, N),
             "value": value, "value_per_gpu": value / world, "unit": "updates/s", "n_gpus": world, "rccl_ranks": rccl_ranks, "devices": devices,
@@ -649,29 +666,69 @@ def main():
                                        f"weak scaling: {B} instances per rank x {world}") +
                                       f", no data-path collective; {n_chunks} instance range(s) per GPU, each free-running on its own HIP stream (steps replayed as hipGraphs)"
                                       + ("; all-gather of outputs timed separately" if gather else "")},
-            "roofline": {"bound": "hbm", "kernel": dom, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_source,
-                         "algorithmic_bytes_per_launch": alg_bytes, "launch_ms": phases[dom],
-                         "whole_update_frac_of_hbm_roofline": (BYTES_PER_UPDATE(N) * value / world) / (HBM_PEAK_GBS * 1e9),
-                         "per_kernel": per_kernel},
-            "phase_ms": phases,
-            "phase_ms_note": "HIP-event times of the kernels with the whole batch on ONE stream (no chunk overlap), taken after the timed region; "
-                             "the headline runs the same kernels per instance range on " + str(n_chunks) + " concurrent stream(s)",
-            "halves": {"mpc_solves_per_s_per_gpu": B / (phases["mpc_total"] * 1e-3), "wbc_solves_per_s_per_gpu": B / (phases["k_wbc"] * 1e-3),
-                       "note": "device time of each half alone (HIP events); the reference runs them 1:5 (100 Hz MPC, 500 Hz WBC)"},
-            "solver_state": {"max_dyn_sse": float(perf[:, 1].max()), "max_eq_sse": float(perf[:, 2].max()),
-                             "wbc_eom_residual_max": wbc_eom_res, "wbc_torque_limit_violation_max": wbc_tau_viol,
-                             "wbc_friction_pyramid_violation_max": wbc_cone_viol,
-                             "wbc_optimality_note": "max over the batch of |M a + nle - S' tau - J' F| (N, N m), of |tau| - limit and of the friction-pyramid "
-                                                    "rows, from hb_eval_rbd on the rbd states of the last update; dual residuals: tests/test_oracle_qp.py",
-                             "wbc_status_histogram_all_ranks": hist, "mpc_status_histogram_all_ranks": mpc_hist,
-                             "wbc_active_set_iterations_histogram_all_ranks": {f"{lo}..{hi - 1}" if hi < (1 << 30) else f">={lo}": n
-                                                                               for lo, hi, n in zip(it_edges, it_edges[1:], it_hist)},
-                             "wbc_active_set_iterations_min_max_rank0": [int(wbc_iters.min()), int(wbc_iters.max())],
-                             "line_search_step_histogram_all_ranks": {"full": step_hist[0], "backtracked": step_hist[1], "no_step": step_hist[2]},
-                             "nodes_per_instance_min_max": [int(n_nodes.min()), int(n_nodes.max())],
-                             "chunk_step_counters_rank0": chunk_counters},
         }
+        if dumped is not None:
+            out["dumped_outputs"] = {"dir": str(args.dump_outputs), "arrays": dumped}
+        if args.full:
+            dom = max(("k_lq", "k_ric_bwd", "k_ric_fwd"), key=lambda k: phases[k])
+            alg_bytes = BYTES_PER_NODE[dom] * int(n_nodes.sum())
+            achieved = alg_bytes / (phases[dom] * 1e-3) / 1e9
+            traffic, traffic_source = None, None
+            pmc = ROOT / "profiles" / "pmc_latest.json"
+            if pmc.exists() and B == 4096 and N == 100 and not args.random_cmd and not args.hierarchical:
+                try:
+                    pj = json.loads(pmc.read_text())
+                    stamp = f"tag {pj.get('tag')}, commit {pj.get('git_head')}, kernel sources sha256 {str(pj.get('source_sha256'))[:12]}"
+                    # (the counter file names kernels as the profiler does: the LQ approximation runs as k_lq_trip since round 6)
+                    if "k_lq_trip" in pj:
+                        pj["k_lq"] = pj["k_lq_trip"]
+                    if pj.get("source_sha256") == source_fingerprint():
+                        traffic = pj.get(dom, {}).get("hbm_bytes_per_launch")
+                        traffic_source = (f"profiles/pmc_latest.json ({stamp} = the running tree's kernel sources): rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE "
+                                          "passes over this workload, collected in a separate run (counters cannot be read inside the timed process), "
+                                          "NOT measured in this run")
+                    else:   # a counter file collected on other kernel sources says nothing about this run
+                        traffic_source = (f"profiles/pmc_latest.json ({stamp}) was collected on DIFFERENT kernel sources than the running tree "
+                                          f"(sha256 {source_fingerprint()[:12]}): traffic dropped")
+                except Exception:
+                    traffic = None
+            per_kernel = {k: {"ms": phases[k], "algorithmic_GBs": BYTES_PER_NODE[k] * int(n_nodes.sum()) / (phases[k] * 1e-3) / 1e9,
+                              "frac_of_hbm_peak": BYTES_PER_NODE[k] * int(n_nodes.sum()) / (phases[k] * 1e-3) / 1e9 / HBM_PEAK_GBS}
+                          for k in ("k_lq", "k_ric_bwd", "k_ric_fwd")}
+            # what each kernel REALLY moves (FETCH_SIZE / WRITE_SIZE counter passes, same source and caveat as roofline.traffic) over
+            # this run's launch time: k_ric_fwd is the kernel that is HBM bound, on 2 x the bytes the 8d formula grants it
+            if traffic is not None:
+                for k, v in per_kernel.items():
+                    cb = pj.get(k, {}).get("hbm_bytes_per_launch")
+                    if cb:
+                        v["counter_bytes_per_launch"] = cb
+                        v["counter_GBs"] = cb / (phases[k] * 1e-3) / 1e9
+                        v["counter_frac_of_hbm_peak"] = v["counter_GBs"] / HBM_PEAK_GBS
+                        v["counter_over_algorithmic"] = cb / (BYTES_PER_NODE[k] * int(n_nodes.sum()))
+            out.update({
+                "roofline": {"bound": "hbm", "kernel": dom, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                             "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_source,
+                             "algorithmic_bytes_per_launch": alg_bytes, "launch_ms": phases[dom],
+                             "whole_update_frac_of_hbm_roofline": (BYTES_PER_UPDATE(N) * value / world) / (HBM_PEAK_GBS * 1e9),
+                             "per_kernel": per_kernel},
+                "phase_ms": phases,
+                "phase_ms_note": "HIP-event times of the kernels with the whole batch on ONE stream (no chunk overlap), taken after the timed region; "
+                                 "the headline runs the same kernels per instance range on " + str(n_chunks) + " concurrent stream(s)",
+                "halves": {"mpc_solves_per_s_per_gpu": B / (phases["mpc_total"] * 1e-3), "wbc_solves_per_s_per_gpu": B / (phases["k_wbc"] * 1e-3),
+                           "note": "device time of each half alone (HIP events); the reference runs them 1:5 (100 Hz MPC, 500 Hz WBC)"},
+                "solver_state": {"max_dyn_sse": float(perf[:, 1].max()), "max_eq_sse": float(perf[:, 2].max()),
+                                 "wbc_eom_residual_max": wbc_eom_res, "wbc_torque_limit_violation_max": wbc_tau_viol,
+                                 "wbc_friction_pyramid_violation_max": wbc_cone_viol,
+                                 "wbc_optimality_note": "max over the batch of |M a + nle - S' tau - J' F| (N, N m), of |tau| - limit and of the friction-pyramid "
+                                                        "rows, from hb_eval_rbd on the rbd states of the last update; dual residuals: tests/test_oracle_qp.py",
+                                 "wbc_status_histogram_all_ranks": hist, "mpc_status_histogram_all_ranks": mpc_hist,
+                                 "wbc_active_set_iterations_histogram_all_ranks": {f"{lo}..{hi - 1}" if hi < (1 << 30) else f">={lo}": n
+                                                                                   for lo, hi, n in zip(it_edges, it_edges[1:], it_hist)},
+                                 "wbc_active_set_iterations_min_max_rank0": [int(wbc_iters.min()), int(wbc_iters.max())],
+                                 "line_search_step_histogram_all_ranks": {"full": step_hist[0], "backtracked": step_hist[1], "no_step": step_hist[2]},
+                                 "nodes_per_instance_min_max": [int(n_nodes.min()), int(n_nodes.max())],
+                                 "chunk_step_counters_rank0": chunk_counters},
+            })
         if gather:
             out["gather"] = gather
         out.update(extras)
@@ -680,7 +737,7 @@ def main():
         dist.destroy_process_group()
     if rank == 0:
         # the CPU leg runs on rank 0's host cores AFTER the final barrier (the other ranks are gone: nothing of it overlaps the timed region)
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(params, N)
         print(json.dumps(out))
 

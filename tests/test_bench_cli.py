@@ -6,6 +6,8 @@ import subprocess
 import sys
 from pathlib import Path
 
+import pytest
+
 ROOT = Path(__file__).resolve().parents[1]
 
 
@@ -16,9 +18,14 @@ def _run(extra_env, *argv):
 
 
 def test_bare_multi_gpu_request_without_gpus_refuses():
-    r = _run({}, "--gpus", "2", "--steps", "1", "--warmup", "0")
+    # one GPU more than this node shows (at least 2: --gpus 1 starts no ranks), counted in a child as bench.py counts them
+    c = subprocess.run([sys.executable, "-c", "import torch; print(torch.cuda.device_count() if torch.cuda.is_available() else 0)"],
+                       capture_output=True, text=True, timeout=300)
+    have = int(c.stdout.strip().splitlines()[-1])
+    want = max(2, have + 1)
+    r = _run({}, "--gpus", str(want), "--steps", "1", "--warmup", "0")
     assert r.returncode != 0
-    assert "--gpus 2 needs 2 MI355X" in r.stderr and "found 0" in r.stderr
+    assert f"--gpus {want} needs {want} MI355X" in r.stderr and f"found {have}" in r.stderr
     assert '"n_gpus"' not in r.stdout
 
 
@@ -29,7 +36,8 @@ def test_world_size_mismatch_refuses():
 
 
 def test_launcher_command_line(monkeypatch):
-    """With enough devices the bare process replaces itself by torch.distributed.run with one rank per GPU on 127.0.0.1."""
+    """With enough devices the bare process starts torch.distributed.run with one rank per GPU on 127.0.0.1 as a fresh child
+    process and exits with its status."""
     import importlib.util
     import types
     spec = importlib.util.spec_from_file_location("bench_under_test", ROOT / "bench.py")
@@ -41,16 +49,15 @@ def test_launcher_command_line(monkeypatch):
     monkeypatch.delenv("WORLD_SIZE", raising=False)
     seen = {}
 
-    def fake_exec(file, argv, env):
+    def fake_call(argv, env):
         seen["argv"], seen["env"] = argv, env
-        raise SystemExit(0)
+        return 3
 
-    monkeypatch.setattr(os, "execvpe", fake_exec)
+    monkeypatch.setattr(bench.subprocess, "call", fake_call)
     monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "4", "--steps", "7"])
-    try:
+    with pytest.raises(SystemExit) as e:
         bench.launch_ranks_if_needed(types.SimpleNamespace(gpus=4))
-    except SystemExit:
-        pass
+    assert e.value.code == 3          # the child's exit status is this process's
     a = seen["argv"]
     assert a[1:3] == ["-m", "torch.distributed.run"] and "--nproc-per-node=4" in a and "--nnodes=1" in a
     assert a[a.index("--master-addr") + 1] == "127.0.0.1"
@@ -101,9 +108,6 @@ def test_counter_file_is_tied_to_the_kernel_sources():
     assert "source_sha256" in pj and "git_head" in pj and "tag" in pj
 
 
-import pytest
-
-
 @pytest.mark.gpu
 def test_bench_under_the_launcher_goes_through_rccl_even_with_one_rank():
     """The driver's multi-GPU launch line with ONE rank on the one GPU of this box: process group on the nccl (= RCCL) backend,
@@ -114,7 +118,7 @@ def test_bench_under_the_launcher_goes_through_rccl_even_with_one_rank():
     env["HSA_ENABLE_IPC_MODE_LEGACY"] = "0"
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
                         "--master-port", "29533", str(ROOT / "bench.py"), "--gpus", "1", "--total-batch", "96", "--nodes", "24", "--steps", "4",
-                        "--warmup", "1", "--random-cmd", "--gather", "--no-cpu-baseline", "--no-extras"], env=env, capture_output=True, text=True,
+                        "--warmup", "1", "--random-cmd", "--gather", "--full", "--no-cpu-baseline", "--no-extras"], env=env, capture_output=True, text=True,
                        timeout=600)
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert r.returncode == 0 and lines, r.stdout[-2000:] + r.stderr[-2000:]
@@ -130,16 +134,73 @@ def test_bench_under_the_launcher_goes_through_rccl_even_with_one_rank():
 
 @pytest.mark.gpu
 def test_bench_line_under_the_launcher_keeps_roofline_and_cpu_baseline():
-    """rank 0 prints `roofline` and `cpu_baseline` at ANY world size (the CPU leg runs after the final barrier)."""
+    """With --full, rank 0 prints `roofline` and `cpu_baseline` at ANY world size (the CPU leg runs after the final barrier)."""
     import json
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env["HSA_ENABLE_IPC_MODE_LEGACY"] = "0"
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
                         "--master-port", "29534", str(ROOT / "bench.py"), "--gpus", "1", "--batch", "64", "--nodes", "24", "--steps", "3",
-                        "--warmup", "1", "--no-extras"], env=env, capture_output=True, text=True, timeout=600)
+                        "--warmup", "1", "--full", "--no-extras"], env=env, capture_output=True, text=True, timeout=600)
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert r.returncode == 0 and lines, r.stdout[-2000:] + r.stderr[-2000:]
     j = json.loads(lines[-1])
     assert j["scaling"] == "strong" and j["config"]["total_instances"] == 64
     assert j["cpu_baseline"]["value"] > 0 and j["cpu_baseline"]["kind"] == "port" and j["roofline"]["kernel"] in ("k_lq", "k_ric_bwd", "k_ric_fwd")
     assert sum(j["solver_state"]["mpc_status_histogram_all_ranks"]) == 64
+
+
+def test_dumped_outputs_are_float64_within_budget_on_a_fixed_sample(tmp_path):
+    """--dump-outputs: every array of the timed path as <name>.npy in float64, under 64 MiB in all; a batch too large for the budget
+    is cut to the same seeded sample of instances in every array and in every run, and `instances` names the rows kept."""
+    import numpy as np
+    bench = _bench_module()
+    rng = np.random.default_rng(0)
+    B, N = 4096, 100
+    outputs = {"mpc_x": rng.standard_normal((B, N + 1, 22)), "mpc_u": rng.standard_normal((B, N, 22)),
+               "wbc_solution": rng.standard_normal((B, 38)), "wbc_status": np.zeros(B, dtype=np.int32),
+               "mpc_status": rng.integers(0, 4, B).astype(np.int32), "mpc_performance": rng.standard_normal((B, 4))}
+    shapes = bench.dump_outputs(outputs, tmp_path / "a")
+    bench.dump_outputs(outputs, tmp_path / "b")
+    files = sorted((tmp_path / "a").glob("*.npy"))
+    assert sorted(f.stem for f in files) == sorted(list(outputs) + ["instances"]) == sorted(shapes)
+    assert sum(f.stat().st_size for f in files) <= 64 << 20
+    idx = np.load(tmp_path / "a" / "instances.npy")
+    assert idx.dtype == np.float64 and 0 < len(idx) < B and np.all(np.diff(idx) > 0) and idx[-1] < B
+    for f in files:
+        a = np.load(f)
+        assert a.dtype == np.float64 and np.array_equal(a, np.load(tmp_path / "b" / f.name))
+        if f.stem != "instances":
+            assert np.array_equal(a, outputs[f.stem][idx.astype(np.int64)].astype(np.float64))
+    # a batch within the budget is written whole, in instance order; several ranks write side by side
+    small = {k: v[:8] for k, v in outputs.items()}
+    bench.dump_outputs(small, tmp_path / "c", "_rank1")
+    assert np.array_equal(np.load(tmp_path / "c" / "instances_rank1.npy"), np.arange(8))
+    assert np.array_equal(np.load(tmp_path / "c" / "mpc_u_rank1.npy"), small["mpc_u"])
+
+
+@pytest.mark.gpu
+def test_plain_bench_line_is_the_headline_and_dumps_the_same_outputs_every_run(tmp_path):
+    """A plain run prints the headline line only (the rest is behind --full), takes --steps timed steps, and --dump-outputs writes
+    what the timed path computed in its last step: the same arrays, bit for bit, in two runs with the same arguments."""
+    import json
+    import numpy as np
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    lines = []
+    for d in ("a", "b"):
+        r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--batch", "256", "--nodes", "24", "--steps", "5",
+                            "--warmup", "2", "--dump-outputs", str(tmp_path / d)], env=env, capture_output=True, text=True, timeout=600)
+        out = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert r.returncode == 0 and out, r.stdout[-2000:] + r.stderr[-2000:]
+        lines.append(json.loads(out[-1]))
+    j = lines[0]
+    assert j["unit"] == "updates/s" and j["higher_is_better"] is True and j["dtype"] == "f64" and j["steps"] == 5
+    assert j["metric"] == "MPC+WBC updates/sec (batch=256, N=24, 12-DoF)" and j["ms_per_step"] > 0
+    assert abs(j["value"] - 256 / (j["ms_per_step"] * 1e-3)) < 1e-6 * j["value"]
+    assert not {"roofline", "phase_ms", "halves", "solver_state", "cpu_baseline", "config1_latency_ms"} & set(j)
+    names = sorted(f.name for f in (tmp_path / "a").glob("*.npy"))
+    assert names == sorted(f"{k}.npy" for k in ("mpc_x", "mpc_u", "wbc_solution", "wbc_status", "mpc_status", "mpc_performance", "instances"))
+    assert sorted(j["dumped_outputs"]["arrays"]) == sorted(n[:-4] for n in names)
+    for n in names:
+        a, b = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert a.dtype == np.float64 and a.shape[0] == 256 and np.array_equal(a, b), n
+    assert np.isfinite(np.load(tmp_path / "a" / "mpc_x.npy")).all() and np.load(tmp_path / "a" / "wbc_status.npy").max() == 0

@@ -13,9 +13,9 @@ from hunter_bipedal_control_amd import abi, ingest
 
 ROOT = Path(__file__).resolve().parents[1]
 PARAMS_BIN = ROOT / "hunter_bipedal_control_amd" / "data" / "hunter_params.bin"
-REF = Path("/root/reference")
-CFG = REF / "legged_controllers/config/hunter"
-URDF = REF / "legged_examples/legged_hunter/legged_hunter_description/urdf/hunter.urdf"
+# the reference's task.info / reference.info / gait.info and hunter.urdf, stored as test inputs
+CFG = ROOT / "tests" / "golden" / "reference_input"
+URDF = CFG / "hunter.urdf"
 
 
 @pytest.fixture(scope="module")
@@ -64,7 +64,6 @@ def test_cpp_loader_errors_like_the_reference(exe, tmp_path):
     assert r.returncode == 1 and "does not match this ABI" in r.stderr
 
 
-@pytest.mark.skipif(not REF.exists(), reason="needs the reference's config files (build container only)")
 def test_cpp_ingest_of_the_reference_files_reproduces_the_packaged_blob(exe, tmp_path):
     """task.info + hunter.urdf + reference.info + gait.info read by the C++ header == the packaged image, byte for byte; and the
     Python ingest of the same files == the packaged JSON values."""

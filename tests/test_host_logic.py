@@ -8,7 +8,8 @@ import pytest
 from hunter_bipedal_control_amd import abi, ingest
 from oracle import refgen, workloads
 
-REF = Path("/root/reference")
+# the reference's task.info / reference.info / gait.info and hunter.urdf, stored as test inputs
+REF_INPUT = Path(__file__).resolve().parent / "golden" / "reference_input"
 
 
 def test_info_parser_semantics():
@@ -45,10 +46,9 @@ def test_packaged_params_and_struct_layout(params):
     assert mdl.gravity == 9.81 and abs(mdl.q_upper[3] - 1.5) < 1e-12
 
 
-@pytest.mark.skipif(not REF.exists(), reason="reference tree only exists in the build container")
 def test_packaged_params_equal_fresh_ingest_of_the_reference_files(params):
-    cfgdir = REF / "legged_controllers/config/hunter"
-    model = ingest.read_urdf(REF / "legged_examples/legged_hunter/legged_hunter_description/urdf/hunter.urdf")
+    cfgdir = REF_INPUT
+    model = ingest.read_urdf(REF_INPUT / "hunter.urdf")
     cfg = ingest.read_config(cfgdir / "task.info", cfgdir / "reference.info", cfgdir / "gait.info")
     assert model == params["model"] and cfg == params["config"]
 

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Everything DESIGN.md / README quote for a round, collected on ONE GPU box in one call and written under gpurun_out/<tag>/final/ with
 # the names profiles/ uses (copy them there and commit):   gpurun --timeout 2400 -- 'bash tools/evidence.sh r04'
-#   <tag>_bench.json                        python bench.py --steps 200 --warmup 5 (the driver's line incl. extras and cpu_baseline)
+#   <tag>_bench.json                        python bench.py --steps 200 --warmup 5 --full (the line incl. extras and cpu_baseline)
 #   <tag>_kernel_stats.{txt,json}           rocprofv3 --kernel-trace --stats, bench --chunks 1 (single stream: true kernel durations)
 #   <tag>_kernel_stats_chunked.{txt,json}   the same with the headline's four instance ranges (durations under overlap; launch counts)
 #   <tag>_kernel_stats_b512.{txt,json}      the same at 512 instances (k_ric_bwd4 row)
@@ -22,17 +22,17 @@ prof() {  # name, command...
   [ -n "$db" ] && python tools/rocprof_summary.py $db $out/${tag}_kernel_stats$([ $name = main ] || echo _$name).txt > /dev/null 2>&1
   rm -rf $out/prof_$name
 }
-(timeout 900 python bench.py --steps 200 --warmup 5 > $out/${tag}_bench.json) 2> $out/bench.err
-prof main python $R/bench.py --steps 20 --warmup 3 --chunks 1 --no-extras --no-cpu-baseline
-prof chunked python $R/bench.py --steps 20 --warmup 3 --no-extras --no-cpu-baseline
-prof b512 python $R/bench.py --batch 512 --steps 40 --warmup 3 --chunks 1 --no-extras --no-cpu-baseline
+(timeout 900 python bench.py --steps 200 --warmup 5 --full > $out/${tag}_bench.json) 2> $out/bench.err
+prof main python $R/bench.py --steps 20 --warmup 3 --chunks 1 --full --no-extras --no-cpu-baseline
+prof chunked python $R/bench.py --steps 20 --warmup 3 --full --no-extras --no-cpu-baseline
+prof b512 python $R/bench.py --batch 512 --steps 40 --warmup 3 --chunks 1 --full --no-extras --no-cpu-baseline
 prof full_tick python $R/tools/bench_tick.py --steps 10
 # timeline of configs[3]'s per-GPU share (512 instances, per-instance commands, two free-running ranges): which kernels are co-resident
 (cd /tmp && timeout 600 rocprofv3 --kernel-trace -d $out/prof_tl512 -o run -- python $R/bench.py --batch 512 --random-cmd --steps 60 --warmup 5 --no-extras --no-cpu-baseline > $out/prof_tl512.log 2>&1)
 db=$(find $out/prof_tl512 -name "*results.db" | head -1)
 [ -n "$db" ] && python tools/rocprof_timeline.py $db "" 8.0 > $out/${tag}_timeline_b512.txt 2>> $out/prof_tl512.log
 rm -rf $out/prof_tl512
-prof config4_share python $R/bench.py --hierarchical --batch 1024 --nodes 200 --steps 20 --warmup 3 --chunks 1 --no-extras --no-cpu-baseline
+prof config4_share python $R/bench.py --hierarchical --batch 1024 --nodes 200 --steps 20 --warmup 3 --chunks 1 --full --no-extras --no-cpu-baseline
 prof rollout python $R/tools/bench_rollout.py
 (timeout 600 python tools/bench_tick.py > $out/${tag}_full_tick_breakdown.json) 2> $out/tick.err
 (timeout 900 python tools/occupancy_sweep.py > $out/${tag}_occupancy_sweep.json) 2> $out/sweep.err

@@ -13,8 +13,8 @@ ROOT = Path(__file__).resolve().parents[1]
 rows = []
 for B in (512, 1024, 2048, 4096):
     steps = max(50, 200 * 512 // B)
-    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--batch", str(B), "--steps", str(steps), "--warmup", "5", "--no-cpu-baseline",
-                        "--no-extras"], capture_output=True, text=True)
+    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--batch", str(B), "--steps", str(steps), "--warmup", "5", "--full",
+                        "--no-cpu-baseline", "--no-extras"], capture_output=True, text=True)
     line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     if r.returncode != 0 or not line:
         rows.append({"batch": B, "error": (r.stderr or r.stdout)[-400:]})
@@ -34,7 +34,7 @@ if full and "updates_per_s" in rows[0]:
 # one GPU's share of BASELINE configs[4]: 8192 instances x N = 200 over 8 GPUs = 1024 per GPU, HierarchicalWbc
 c4 = None
 r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--batch", "1024", "--nodes", "200", "--hierarchical", "--steps", "60", "--warmup", "5",
-                    "--no-cpu-baseline", "--no-extras"], capture_output=True, text=True)
+                    "--full", "--no-cpu-baseline", "--no-extras"], capture_output=True, text=True)
 line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
 if r.returncode == 0 and line:
     j = json.loads(line[-1])
@@ -47,7 +47,7 @@ else:
 rc = []
 for B in (512, 4096):
     r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--batch", str(B), "--random-cmd", "--steps", str(max(50, 200 * 512 // B)), "--warmup", "5",
-                        "--no-cpu-baseline", "--no-extras"], capture_output=True, text=True)
+                        "--full", "--no-cpu-baseline", "--no-extras"], capture_output=True, text=True)
     line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     if r.returncode != 0 or not line:
         rc.append({"batch": B, "error": (r.stderr or r.stdout)[-400:]})
