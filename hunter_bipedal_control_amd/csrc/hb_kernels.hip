@@ -1237,6 +1237,11 @@ struct hb_ctx {
   EstBatch est{};
   hb_estimator_config est_cfg{};
   bool est_ready = false;
+  // KKT certificate of the WeightedWbc QP (hb_wbc_set_certificate): allocated on the first enable; cert_last tells whether the last
+  // WBC call ran the certificate kernel
+  bool wbc_cert = false, cert_last = false;
+  double* cert_buf = nullptr;  // [B][HB_WBC_CERT_SIZE]
+  double* dual_buf = nullptr;  // [B][HB_WBC_NCONS_MAX]
 };
 
 static thread_local std::string g_create_error;
@@ -1265,7 +1270,7 @@ static hipError_t dalloc(hb_ctx* ctx, T** p, size_t n) {
 
 extern "C" {
 
-int32_t hb_version(void) { return 100; }
+int32_t hb_version(void) { return 101; }
 
 const char* hb_last_error(const hb_ctx* ctx) { return ctx ? ctx->err.c_str() : g_create_error.c_str(); }
 
@@ -2343,11 +2348,14 @@ static int32_t wbc_launch(hb_ctx* ctx, bool from_policy, double dt) {
   }
   if (ctx->config.wbc_type == 1)
     hipLaunchKernelGGL(k_hwbc, dim3(ctx->B), dim3(64), HoLdsDev::total * sizeof(double), s, w, ctx->dmodel, ctx->dconfig);
+  else if (ctx->wbc_cert)
+    hipLaunchKernelGGL(k_wbc_cert, dim3(ctx->B), dim3(64), 0, s, w, ctx->dmodel, ctx->dconfig, ctx->cert_buf, ctx->dual_buf);
   else
     hipLaunchKernelGGL(k_wbc, dim3(ctx->B), dim3(64), 0, s, w, ctx->dmodel, ctx->dconfig);
   HB_HIP(hipEventRecord(ctx->ev[6], s));
   HB_HIP(hipGetLastError());
   ctx->stats.n_wbc_solves += ctx->B;
+  ctx->cert_last = ctx->wbc_cert;
   return HB_OK;
 }
 
@@ -2448,6 +2456,9 @@ static int32_t range_publish_policy_wbc(hb_ctx* ctx, int i0, int cnt, hipStream_
   hipLaunchKernelGGL(k_policy_eval, dim3((cnt + 63) / 64), dim3(64), 0, s, w, ctx->Nmax, ctx->dconfig);
   if (ctx->config.wbc_type == 1)
     hipLaunchKernelGGL(k_hwbc, dim3(cnt), dim3(64), HoLdsDev::total * sizeof(double), s, w, ctx->dmodel, ctx->dconfig);
+  else if (ctx->wbc_cert)  // (chosen when a range graph is captured: hb_wbc_set_certificate re-captures them)
+    hipLaunchKernelGGL(k_wbc_cert, dim3(cnt), dim3(64), 0, s, w, ctx->dmodel, ctx->dconfig, ctx->cert_buf + size_t(i0) * HB_WBC_CERT_SIZE,
+                       ctx->dual_buf + size_t(i0) * HB_WBC_NCONS_MAX);
   else
     hipLaunchKernelGGL(k_wbc, dim3(cnt), dim3(64), 0, s, w, ctx->dmodel, ctx->dconfig);
   return HB_OK;
@@ -2573,6 +2584,7 @@ int32_t hb_step_resident(hb_ctx* ctx, double dt) {
     ctx->w.policy_valid = true;
     ctx->policy_read_pending = false;  // the lazy join orders the next policy write (by another entry point) after these readers
     ctx->stats.n_wbc_solves += ctx->B;
+    ctx->cert_last = ctx->wbc_cert;
   }
   return HB_OK;
 }
@@ -2708,6 +2720,7 @@ int32_t hb_tick_resident(hb_ctx* ctx, double dt_est, const double* quat, const d
     ctx->w.policy_valid = true;
     ctx->policy_read_pending = false;
     ctx->stats.n_wbc_solves += ctx->B;
+    ctx->cert_last = ctx->wbc_cert;
   }
   return HB_OK;
 }
@@ -2743,6 +2756,42 @@ int32_t hb_get_wbc_solution(hb_ctx* ctx, double* sol, int32_t* status) {
   HB_HIP(hipStreamSynchronize(ctx->s_wbc));
   if (sol) HB_HIP(hipMemcpy(sol, ctx->w.sol, B * HB_NWBC * 8, hipMemcpyDeviceToHost));
   if (status) HB_HIP(hipMemcpy(status, ctx->w.status, B * sizeof(int), hipMemcpyDeviceToHost));
+  return HB_OK;
+}
+
+int32_t hb_wbc_set_certificate(hb_ctx* ctx, int32_t enable) {
+  if (ctx) lazy_join(ctx);
+  if (!ctx || enable < 0 || enable > 1) return HB_ERR_ARG;
+  if (enable && ctx->config.wbc_type != 0) {
+    ctx->err = "hb_wbc_set_certificate: the KKT certificate is defined for WeightedWbc only, not for HierarchicalWbc (wbc_type = 1)";
+    return HB_ERR_ARG;
+  }
+  if (bool(enable) == ctx->wbc_cert) return HB_OK;
+  HB_HIP(hipSetDevice(ctx->device));
+  int32_t rc = hb_sync(ctx);
+  if (rc != HB_OK) return rc;
+  if (enable && !ctx->cert_buf) {
+    HB_HIP(dalloc(ctx, &ctx->cert_buf, size_t(ctx->B) * HB_WBC_CERT_SIZE));
+    HB_HIP(dalloc(ctx, &ctx->dual_buf, size_t(ctx->B) * HB_WBC_NCONS_MAX));
+  }
+  ctx->wbc_cert = enable != 0;
+  ++ctx->graph_epoch;  // captured range graphs hold the other WBC kernel
+  return HB_OK;
+}
+
+int32_t hb_wbc_get_certificate(hb_ctx* ctx, int32_t inst_begin, int32_t inst_count, double* cert, double* dual) {
+  if (ctx) lazy_join(ctx);
+  if (!ctx || inst_begin < 0 || inst_count < 0 || inst_begin > ctx->B || inst_count > ctx->B - inst_begin) return HB_ERR_ARG;
+  if (!ctx->cert_last) {
+    ctx->err = "hb_wbc_get_certificate: certificates were off at the last WBC call (hb_wbc_set_certificate)";
+    return HB_ERR_STATE;
+  }
+  HB_HIP(hipSetDevice(ctx->device));
+  HB_HIP(hipStreamSynchronize(ctx->s_wbc));
+  if (cert && inst_count)
+    HB_HIP(hipMemcpy(cert, ctx->cert_buf + size_t(inst_begin) * HB_WBC_CERT_SIZE, size_t(inst_count) * HB_WBC_CERT_SIZE * 8, hipMemcpyDeviceToHost));
+  if (dual && inst_count)
+    HB_HIP(hipMemcpy(dual, ctx->dual_buf + size_t(inst_begin) * HB_WBC_NCONS_MAX, size_t(inst_count) * HB_WBC_NCONS_MAX * 8, hipMemcpyDeviceToHost));
   return HB_OK;
 }
 

@@ -517,16 +517,184 @@ HB_HD void wbc_phase_a(const Ctx& cx, const DevModel& M, const DevConfig& C, con
   cx.sync();
 }
 
-// One WBC solve.  xdes/udes/rbd: this instance's inputs; sol in/out (kept when the QP fails).
+// Coefficient of variable i in constraint row cid (dense EoM rows from LDS, sparse rows from their (index, coefficient) pairs).
+HB_HD double wbc_cons_coeff(const WbcCons& wc, const DevConfig& C, const double* Ee, int cid, int i) {
+  if (cid < 16) return Ee[cid * NW + i];
+  int idx[3];
+  double cf[3], rhs;
+  const int nn = sparse_row(wc, C, cid, idx, cf, &rhs);
+  double a = 0.0;
+  for (int t = 0; t < nn; ++t) a += idx[t] == i ? cf[t] : 0.0;
+  return a;
+}
+
+// KKT certificate of the WeightedWbc QP at the returned solution (hb_wbc_set_certificate; layout HB_WBC_CERT_* of hunter_hip.h).
+// Runs at the end of the certificate instantiation of wbc_solve, while the rows, the point and the working set are in LDS; the J / R
+// buffers are free by then.  The cost is the UNREGULARISED one, H = A_w' A_w, g = -A_w' b_w, and the point is the returned `sol`
+// (the previous solution when the solve failed).  The multipliers are the least-squares solution on the final working set W
+// (equalities always in): y_W = argmin |H x + g - A_W' y_W|_2 by Householder QR of A_W' (38 x |W|, never the normal equations).
+// Sign convention: H x + g - A'y = 0, y <= 0 on active upper-bounded rows.
+template <class Ctx>
+HB_HD void wbc_certificate(const Ctx& cx, const DevConfig& C, const WbcCons& wc, const double* udes, bool stance_mode, int n_aw,
+                           double eps, int status, double* lds, const double* sol, double* cert, double* dual) {
+  const double* Ee = lds + WbcLds::Eeom;
+  const double* Aw = lds + WbcLds::Aw;
+  const double* bw = lds + WbcLds::bw;
+  const double* beom = lds + WbcLds::beom;
+  const double* x = lds + WbcLds::x;
+  const int* is_active = reinterpret_cast<const int*>(lds + WbcLds::iact) + 40;
+  double* red = lds + WbcLds::red;
+  double* At = lds + WbcLds::J;       // A_W' row-major (row = variable, column = member of W), reduced to R in place
+  double* wk = lds + WbcLds::R;
+  double* xe = wk;                    // 38 evaluation point
+  double* gs = wk + 40;               // 38 H xe + g
+  double* c = wk + 80;                // 38 Q' (H xe + g)
+  double* rd = wk + 120;              // 38 diagonal of R
+  double* y = wk + 160;               // 64 multipliers by constraint id
+  double* ax = wk + 224;              // 18 dense cost rows at xe
+  int* wid = reinterpret_cast<int*>(wk + 248);  // 40 ints: ids of W
+  double* part = wk + 272;            // 5 x 64 lane partial maxima
+  const int n_cons = wc.n_eq + wc.n_in;
+  for (int i = cx.lane; i < 64; i += cx.nlanes) {
+    y[i] = 0.0;
+    if (i < NW) xe[i] = status == 0 ? x[i] : sol[i];
+  }
+  cx.sync();
+  for (int k = cx.lane; k < n_aw; k += cx.nlanes) {
+    double s = 0.0;
+    for (int j = 0; j < 16; ++j) s += Aw[k * 16 + j] * xe[j];
+    ax[k] = s;
+  }
+  cx.sync();
+  // gradient H xe + g = A_w'(A_w xe - b_w) (formed as one product: no cancellation between H xe and g), and the scale max(1, |g|, |H xe|)
+  const double wf2 = stance_mode ? 0.0 : C.w_force * C.w_force;
+  double pm = 0.0;
+  for (int i = cx.lane; i < NW; i += cx.nlanes) {
+    double hx = 0.0, g = 0.0, gr = 0.0;
+    if (i < 16) {
+      for (int k = 0; k < n_aw; ++k) {
+        hx += Aw[k * 16 + i] * ax[k];
+        g -= Aw[k * 16 + i] * bw[k];
+        gr += Aw[k * 16 + i] * (ax[k] - bw[k]);
+      }
+    } else if (i < 28) {
+      hx = wf2 * xe[i];
+      g = -wf2 * udes[i - 16];
+      gr = wf2 * (xe[i] - udes[i - 16]);
+    }
+    gs[i] = gr;
+    c[i] = gr;
+    pm = fmax(pm, fmax(fabs(hx), fabs(g)));
+  }
+  red[cx.lane] = pm;
+  // working set: every equality, then the active inequalities in id order (each lane walks the same list: m is uniform)
+  int m = 0;
+  for (int cid = 0; cid < n_cons; ++cid)
+    if ((cid < wc.n_eq || is_active[cid]) && m < NW) {
+      if (cx.lane == 0) wid[m] = cid;
+      ++m;
+    }
+  cx.sync();
+  double scale = 1.0;
+  for (int l = 0; l < cx.nlanes; ++l) scale = fmax(scale, red[l]);
+  for (int idx = cx.lane; idx < NW * NW; idx += cx.nlanes) {
+    const int i = idx / NW, j = idx - NW * i;
+    At[idx] = j < m ? wbc_cons_coeff(wc, C, Ee, wid[j], i) : 0.0;
+  }
+  cx.sync();
+  // Householder QR of A_W', the right-hand side carried along as column m; lane j owns column j of a step.  (Rolled loops from k: the
+  // fixed 38-row form with masks, as in the solve, measured 30 % slower here.)
+  for (int k = 0; k < m; ++k) {
+    double nrm2 = 0.0;
+    for (int i = k; i < NW; ++i) nrm2 += At[i * NW + k] * At[i * NW + k];
+    const double akk = At[k * NW + k];
+    const double alpha = akk > 0.0 ? -sqrt(nrm2) : sqrt(nrm2);
+    const double v0 = akk - alpha;
+    const double vtv = nrm2 - akk * akk + v0 * v0;
+    if (vtv > 0.0) {
+      const double beta = 2.0 / vtv;
+      for (int j = k + 1 + cx.lane; j <= m; j += cx.nlanes) {
+        double* col = j < m ? At + j : c;
+        const int st = j < m ? NW : 1;
+        double s = v0 * col[k * st];
+        for (int i = k + 1; i < NW; ++i) s += At[i * NW + k] * col[i * st];
+        s *= beta;
+        col[k * st] -= s * v0;
+        for (int i = k + 1; i < NW; ++i) col[i * st] -= s * At[i * NW + k];
+      }
+    }
+    cx.sync();
+    if (cx.lane == 0) rd[k] = alpha;
+  }
+  cx.sync();
+  // R y_W = (Q' gs)[0:m], column-oriented back substitution
+  for (int k = m - 1; k >= 0; --k) {
+    const double yk = rd[k] != 0.0 ? c[k] / rd[k] : 0.0;
+    cx.sync();
+    for (int i = cx.lane; i < k; i += cx.nlanes) c[i] -= At[i * NW + k] * yk;
+    if (cx.lane == 0) y[wid[k]] = yk;
+    cx.sync();
+  }
+  // residuals: lane-partial maxima of r_eq, r_in, r_dual, r_comp (rows) and r_stat (variables)
+  double p_eq = 0.0, p_in = 0.0, p_du = 0.0, p_co = 0.0, p_st = 0.0;
+  for (int cid = cx.lane; cid < n_cons; cid += cx.nlanes) {
+    double s;
+    if (cid < 16) {
+      s = -beom[cid];
+      for (int i = 0; i < NW; ++i) s += Ee[cid * NW + i] * xe[i];
+    } else {
+      int idx[3];
+      double cf[3], rhs;
+      const int nn = sparse_row(wc, C, cid, idx, cf, &rhs);
+      s = -rhs;
+      for (int t = 0; t < nn; ++t) s += cf[t] * xe[idx[t]];
+    }
+    if (cid < wc.n_eq) {
+      p_eq = fmax(p_eq, fabs(s));
+    } else {
+      p_in = fmax(p_in, s);
+      p_du = fmax(p_du, y[cid]);
+      p_co = fmax(p_co, fabs(y[cid] * s));
+    }
+  }
+  for (int i = cx.lane; i < NW; i += cx.nlanes) {
+    double s = gs[i];
+    for (int j = 0; j < m; ++j) s -= wbc_cons_coeff(wc, C, Ee, wid[j], i) * y[wid[j]];
+    p_st = fmax(p_st, fabs(s));
+  }
+  part[cx.lane] = p_eq;
+  part[64 + cx.lane] = p_in;
+  part[128 + cx.lane] = p_st;
+  part[192 + cx.lane] = p_du;
+  part[256 + cx.lane] = p_co;
+  cx.sync();
+  if (cx.lane == 0) {
+    double r[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+    for (int l = 0; l < cx.nlanes; ++l)
+      for (int t = 0; t < 5; ++t) r[t] = fmax(r[t], part[64 * t + l]);
+    cert[HB_WBC_CERT_R_EQ] = r[0];
+    cert[HB_WBC_CERT_R_IN] = r[1];
+    cert[HB_WBC_CERT_R_STAT] = r[2];
+    cert[HB_WBC_CERT_R_DUAL] = r[3];
+    cert[HB_WBC_CERT_R_COMP] = r[4];
+    cert[HB_WBC_CERT_N_ACTIVE] = double(m);
+    cert[HB_WBC_CERT_EPS] = eps;
+    cert[HB_WBC_CERT_SCALE] = scale;
+  }
+  for (int i = cx.lane; i < HB_WBC_NCONS_MAX; i += cx.nlanes) dual[i] = y[i];
+}
+
+// One WBC solve.  xdes/udes/rbd: this instance's inputs; sol in/out (kept when the QP fails).  The kCert instantiation also writes
+// the KKT certificate (cert [HB_WBC_CERT_SIZE]) and the dual solution (dual [HB_WBC_NCONS_MAX]) of this instance.
 #if defined(HB_ABLATE) && defined(__HIP_DEVICE_COMPILE__)
 #define HB_WBC_MARK(i) if (C.debug_stop == 198 && blockIdx.x == 5) wt_[i] = __builtin_readcyclecounter();
 #else
 #define HB_WBC_MARK(i)
 #endif
-template <class Ctx>
+template <class Ctx, bool kCert = false>
 HB_HD void wbc_solve(const Ctx& cx, const DevModel& M, const DevConfig& C, const double* xdes, const double* udes,
                      const double* rbd, int mode, bool stance_mode, double* lds, double* sol, int* status_out,
-                     int* iters_out) {
+                     int* iters_out, double* cert = nullptr, double* dual = nullptr) {
 #if defined(HB_ABLATE) && defined(__HIP_DEVICE_COMPILE__)
   long long wt_[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 #endif
@@ -1078,6 +1246,7 @@ HB_HD void wbc_solve(const Ctx& cx, const DevModel& M, const DevConfig& C, const
     *status_out = status;
     *iters_out = iter;
   }
+  if constexpr (kCert) wbc_certificate(cx, C, wc, udes, stance_mode, n_aw, eps, status, lds, sol, cert, dual);
 }
 
 // MPC_MRT_Interface::evaluatePolicy with a feed-forward controller: linear interpolation of the state and
@@ -1133,6 +1302,19 @@ __global__ __launch_bounds__(64) void k_wbc(WbcBatch w, const DevModel* __restri
   __shared__ double lds[WbcLds::total];
   wbc_solve(WbcDeviceCtx(), *M, *C, w.xdes + size_t(inst) * HB_NX, w.udes + size_t(inst) * HB_NU, w.rbd + size_t(inst) * HB_NRBD,
             w.mode[inst], w.stance[inst] != 0, lds, w.sol + size_t(inst) * NW, w.status + inst, w.iters + inst);
+}
+
+// k_wbc with the KKT certificate (hb_wbc_set_certificate): the same solve, then the certificate and the dual solution of the
+// instance (cert [B][HB_WBC_CERT_SIZE], dual [B][HB_WBC_NCONS_MAX], both already offset to the launch's first instance)
+__global__ __launch_bounds__(64) void k_wbc_cert(WbcBatch w, const DevModel* __restrict__ M, const DevConfig* __restrict__ C,
+                                                 double* cert, double* dual) {
+  __builtin_amdgcn_s_setprio(3);
+  const int inst = blockIdx.x;
+  __shared__ double lds[WbcLds::total];
+  wbc_solve<WbcDeviceCtx, true>(WbcDeviceCtx(), *M, *C, w.xdes + size_t(inst) * HB_NX, w.udes + size_t(inst) * HB_NU,
+                                w.rbd + size_t(inst) * HB_NRBD, w.mode[inst], w.stance[inst] != 0, lds, w.sol + size_t(inst) * NW,
+                                w.status + inst, w.iters + inst, cert + size_t(inst) * HB_WBC_CERT_SIZE,
+                                dual + size_t(inst) * HB_WBC_NCONS_MAX);
 }
 
 __global__ void k_rbd(int n, const DevModel* __restrict__ M, const double* rbd, double* Mo, double* nle, double* J, double* dJv) {

@@ -28,6 +28,7 @@ ABI_SYMBOLS = [
     "hb_refgen_reset", "hb_refgen_set_schedule", "hb_refgen_update", "hb_mpc_get_references", "hb_joint_command", "hb_centroidal_state_from_rbd", "hb_plant_reset", "hb_plant_step",
     "hb_plant_get_state", "hb_hoqp_solve", "hb_mpc_reset_masked", "hb_mpc_get_status", "hb_joint_set_flags",
     "hb_joint_get_emergency_stop", "hb_set_resident_time", "hb_get_wbc_iterations", "hb_ik_solve", "hb_debug_chunk_counters", "hb_debug_graph_state", "hb_refgen_get_status", "hb_tick_resident",
+    "hb_wbc_set_certificate", "hb_wbc_get_certificate",
 ]
 # include/hunter_lcm.h
 LCM_SYMBOLS = ["hb_lcm_fingerprint", "hb_lcm_encoded_size", "hb_lcm_field_count", "hb_lcm_encode", "hb_lcm_decode", "hb_lcm_frame", "hb_lcm_unframe",
@@ -287,6 +288,25 @@ class HunterSolver:
         it = np.zeros(self.B, dtype=np.int32)
         self._check(self.lib.hb_get_wbc_iterations(self.ctx, _p(it)), "hb_get_wbc_iterations")
         return it
+
+    # field order of hunter_hip.h's HB_WBC_CERT_* (the certificate of one instance)
+    WBC_CERT_FIELDS = ("r_eq", "r_in", "r_stat", "r_dual", "r_comp", "n_active", "eps", "scale")
+
+    def wbc_set_certificate(self, enable: bool = True):
+        """KKT certificate + dual solution of the WeightedWbc QP on every later WBC call (hb_wbc_set_certificate)."""
+        self._check(self.lib.hb_wbc_set_certificate(self.ctx, C.c_int32(1 if enable else 0)), "hb_wbc_set_certificate")
+
+    def wbc_certificate(self, inst_begin: int = 0, count: int | None = None) -> dict:
+        """Certificates of instances [inst_begin, inst_begin + count) from the last WBC call: the named fields of hunter_hip.h
+        (r_eq, r_in, r_stat, r_dual, r_comp, n_active, eps, scale; [count] each, n_active as int) and dual [count][60]."""
+        count = self.B - inst_begin if count is None else int(count)
+        cert, dual = np.zeros((max(count, 0), 8)), np.zeros((max(count, 0), 60))
+        self._check(self.lib.hb_wbc_get_certificate(self.ctx, C.c_int32(inst_begin), C.c_int32(count), _p(cert), _p(dual)),
+                    "hb_wbc_get_certificate")
+        out = {name: cert[:, k].copy() for k, name in enumerate(self.WBC_CERT_FIELDS)}
+        out["n_active"] = out["n_active"].astype(np.int32)
+        out["dual"] = dual
+        return out
 
     def sync(self):
         self._check(self.lib.hb_sync(self.ctx), "hb_sync")

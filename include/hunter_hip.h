@@ -280,6 +280,35 @@ int32_t hb_get_wbc_solution(hb_ctx* ctx, double* sol /*[batch][38]*/, int32_t* s
 /* Active-set iterations of the last WBC solve of every instance (constraint additions + drops of the dual active-set
  * method; the role of nWSR at WeightedWbc.cpp:51-55).  iters: [batch]. */
 int32_t hb_get_wbc_iterations(hb_ctx* ctx, int32_t* iters /*[batch]*/);
+/* KKT certificate and dual solution of the WeightedWbc QP (hb_config.wbc_type = 0), per instance, computed inside the WBC kernel
+ * right after the solve.  The QP is the reference's (legged_wbc/src/WeightedWbc.cpp:24-41) WITHOUT the Tikhonov term:
+ *   min 1/2 x'H x + g'x,  H = A_w'A_w, g = -A_w'b_w (every weighted task incl. the contact forces; the stance task in stance mode),
+ *   rows A = [EoM 16 ; zero force 3 n_sw ; torque limits 20 ; friction pyramid 5 n_c ; 3 n_sw all-zero rows] in the order qpOASES
+ *   receives them (56 / 58 / 60 rows), each an equality or "<= f",
+ * evaluated at the sol the call returned (the previous solution when the solve failed).  The multipliers y are the least-squares
+ * solution  argmin |Hx + g - A_W'y_W|_2  on the solver's final working set W (equalities always in W).
+ * Sign convention: Hx + g - A'y = 0, y_i <= 0 on active upper-bounded rows (qpOASES getDualSolution's convention as far as known;
+ * the reference never reads the dual).  dual[HB_WBC_NCONS_MAX] holds y in the row order above; rows outside W, the all-zero rows
+ * and the padding are zero.
+ * hb_wbc_set_certificate: 0 (default) / 1.  Every later WBC launch (hb_wbc_update, hb_wbc_update_direct, hb_step_resident,
+ * hb_tick_resident, with or without hb_set_chunks) runs the certificate kernel; sol / status / iterations are bit-identical either
+ * way.  Switching re-captures the range graphs.  HB_ERR_ARG when enabling on a HierarchicalWbc context (wbc_type = 1).
+ * hb_wbc_get_certificate: the certificates of instances [inst_begin, inst_begin + inst_count) from the last WBC call (synchronises
+ * the WBC stream); cert [count][HB_WBC_CERT_SIZE], dual [count][HB_WBC_NCONS_MAX], either may be NULL.  HB_ERR_STATE if certificates
+ * were off at that call (or no WBC call ran since they were enabled). */
+#define HB_WBC_CERT_R_EQ 0      /* max |A_E x - b_E| over the EoM and zero-force rows */
+#define HB_WBC_CERT_R_IN 1      /* max(0, max(D x - f)) */
+#define HB_WBC_CERT_R_STAT 2    /* |H x + g - A'y|_inf */
+#define HB_WBC_CERT_R_DUAL 3    /* max(0, max y_i) over the inequality rows (sign violation) */
+#define HB_WBC_CERT_R_COMP 4    /* max |y_i (D x - f)_i| over the inequality rows */
+#define HB_WBC_CERT_N_ACTIVE 5  /* size of the final working set, equalities included */
+#define HB_WBC_CERT_EPS 6       /* the Tikhonov term the problem was solved with (wbc_eps_reg, or the norm-scaled value) */
+#define HB_WBC_CERT_SCALE 7     /* max(1, |g|_inf, |H x|_inf): relative figures are r / scale */
+#define HB_WBC_CERT_SIZE 8
+#define HB_WBC_NCONS_MAX 60
+int32_t hb_wbc_set_certificate(hb_ctx* ctx, int32_t enable);
+int32_t hb_wbc_get_certificate(hb_ctx* ctx, int32_t inst_begin, int32_t inst_count, double* cert /*[count][8]*/,
+                               double* dual /*[count][60]*/);
 /* Pipelining of hb_step_resident: the batch is cut into n_chunks (1..8) instance ranges, each a linear
  * MPC -> publish -> WBC sequence on its own HIP stream so that the per-instance sweeps of one range overlap the
  * per-node kernels of another.  Results are identical for every n_chunks; hb_get_stats phase times are only

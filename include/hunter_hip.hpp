@@ -208,6 +208,21 @@ class Wbc {
   const std::vector<int32_t>& status() const { return status_; }
   const Context& context() const { return ctx_; }
 
+  // KKT certificate of the WeightedWbc QP (hunter_hip.h, hb_wbc_set_certificate): computed by every update from the next one on
+  void enableCertificate(bool on) { ctx_.check(hb_wbc_set_certificate(ctx_.get(), on ? 1 : 0), "hb_wbc_set_certificate"); }
+  // certificates of the last update, [batch][HB_WBC_CERT_SIZE] (indices HB_WBC_CERT_*)
+  const vector_t& certificate() {
+    cert_.resize(size_t(ctx_.batch()) * HB_WBC_CERT_SIZE);
+    ctx_.check(hb_wbc_get_certificate(ctx_.get(), 0, ctx_.batch(), cert_.data(), nullptr), "hb_wbc_get_certificate");
+    return cert_;
+  }
+  // dual solution of instance i in the last update, [HB_WBC_NCONS_MAX] in qpOASES row order (the counterpart of getDualSolution)
+  vector_t dualSolution(size_t i) const {
+    vector_t y(HB_WBC_NCONS_MAX, 0.0);
+    ctx_.check(hb_wbc_get_certificate(ctx_.get(), int32_t(i), 1, nullptr, y.data()), "hb_wbc_get_certificate");
+    return y;
+  }
+
  protected:
   void reportUnsolved() const {
     // instances that hit the iteration limit keep their previous solution on the device (WeightedWbc.cpp:57-65)
@@ -218,7 +233,7 @@ class Wbc {
       }
   }
   Context ctx_;
-  vector_t last_;
+  vector_t last_, cert_;
   std::vector<int32_t> status_, stance_;
 };
 
