@@ -1160,6 +1160,14 @@ struct ErrSlot {
   const char* c_str() const { return tl().c_str(); }
 };
 
+// Slots of hb_ctx::ev: timing points of the MPC phases (iteration 0 of a whole-batch solve) and of the WBC, then the policy
+// hand-over: published, and consumed by the last policy evaluation.
+enum EvSlot { EV_LQ_BEGIN, EV_LQ_END, EV_RIC_BWD_END, EV_RIC_FWD_END, EV_LS_END, EV_WBC_BEGIN, EV_WBC_END, EV_PUBLISHED, EV_POLICY_READ, EV_COUNT };
+constexpr int kMaxRanges = 8;  // instance ranges (hb_set_chunks), each on a stream of its own
+// Slots of hb_ctx::ev_sync, cross-stream ordering points that are NOT timing events: a resident-input writer (plant, estimator) waits
+// for the MPC stream / the MPC stream for it; fork of the range streams from the MPC / WBC streams; SYNC_JOIN + c: join of range c.
+enum SyncSlot { SYNC_BEFORE_WRITER, SYNC_AFTER_WRITER, SYNC_FORK_MPC, SYNC_FORK_WBC, SYNC_JOIN, SYNC_COUNT = SYNC_JOIN + kMaxRanges };
+
 struct hb_ctx {
   int device = 0, B = 0, Nmax = 0, n_cu = 256;
   // Guards the host-side state both threads touch while ENQUEUEING work (policy hand-over flags, counters); never held across
@@ -1173,10 +1181,8 @@ struct hb_ctx {
   DevConfig* dconfig = nullptr;
   Batch b{};
   hipStream_t s_mpc = nullptr, s_wbc = nullptr;
-  hipEvent_t ev[9]{};  // 0..4 MPC phases, 5/6 WBC begin/end, 7 publish, 8 policy buffers consumed by the last policy evaluation
-  // cross-stream ordering points that are NOT timing events: 0 / 1 resident-input writers (plant, estimator) wait for the MPC
-  // stream / the MPC stream waits for them; 2 / 3 fork of the chunk streams from the MPC / WBC streams; 4.. join of chunk c
-  hipEvent_t ev_sync[4 + 8]{};
+  hipEvent_t ev[EV_COUNT]{};
+  hipEvent_t ev_sync[SYNC_COUNT]{};
   // Pinned staging for the asynchronous forms of hb_set_resident_time / hb_estimator_update / hb_refgen_update: a caller-owned host
   // array is copied into a library-owned pinned slot and uploaded from there, so the call returns without a device
   // synchronisation and the caller's array is free again.  STAGE_DEPTH slots per array, each guarded by the event of its last upload:
@@ -1189,7 +1195,7 @@ struct hb_ctx {
   // the next tick's upload only has to wait for that early point), the upload stream and its events
   struct TickUpload { double *quat = nullptr, *w = nullptr, *a = nullptr, *qj = nullptr, *qdj = nullptr, *tnow = nullptr, *t0 = nullptr, *cmd = nullptr; int* contact = nullptr; } up;
   hipStream_t s_up = nullptr;
-  hipEvent_t ev_up = nullptr, ev_consumed[8]{};
+  hipEvent_t ev_up = nullptr, ev_consumed[kMaxRanges]{};
   int consumed_pending = 0;
   bool grid_saved = false;  // tp / modep / np_nodes hold the grid the iterate lives on; the tables have changed since
   bool policy_read_pending = false;
@@ -1203,14 +1209,14 @@ struct hb_ctx {
   // instance chunks pipelined on their own streams by hb_step_resident (independent instances: the latency-bound
   // per-instance sweeps of one chunk overlap the per-node kernels of another)
   int n_chunks = 1;
-  hipStream_t s_chunk[8]{};
+  hipStream_t s_chunk[kMaxRanges]{};
   // hipGraphs of one chunk's whole step (x0 -> SQP iteration -> publish -> policy -> WBC), one per (chunk, x0-sequence slot): at
   // small batch sizes the step is launch bound — ~25 enqueues per chunk and step against kernels of 100..900 us — and the
   // chunk streams only overlap if the host keeps them fed.  Graphs captured in epoch e are stale once a device pointer they
   // hold changes (the iterate / previous-iterate swap of the warm start, a new x0 sequence, a new chunk count).
   static constexpr int GRAPH_SLOTS = 16;
-  hipGraphExec_t chunk_graph[8][GRAPH_SLOTS]{};
-  uint64_t chunk_graph_epoch[8][GRAPH_SLOTS]{};
+  hipGraphExec_t chunk_graph[kMaxRanges][GRAPH_SLOTS]{};
+  uint64_t chunk_graph_epoch[kMaxRanges][GRAPH_SLOTS]{};
   uint64_t graph_epoch = 1;
   int64_t dbg_graph_launches = 0, dbg_direct = 0, dbg_forks = 0, dbg_captures = 0, dbg_capture_failures = 0;
   bool graph_disabled = false;   // a capture / instantiation failed once: direct launches from then on (until hb_set_chunks)
@@ -1254,6 +1260,29 @@ static thread_local std::string g_create_error;
       return HB_ERR_DEVICE;                                                                \
     }                                                                                      \
   } while (0)
+
+// passes on the failure of a call that returns an hb status (its error text is already set)
+#define HB_TRY(expr)                \
+  do {                              \
+    const int32_t rc_ = (expr);     \
+    if (rc_ != HB_OK) return rc_;   \
+  } while (0)
+
+// Device scratch of one call of a unit-level entry point, freed on every return path.
+template <class T>
+struct DevBuf {
+  T* p = nullptr;
+  DevBuf() = default;
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+  ~DevBuf() { if (p) (void)hipFree(p); }
+  // n elements, filled from the host array `from` when one is given
+  hipError_t alloc(size_t n, const T* from = nullptr) {
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&p), n * sizeof(T));
+    if (e == hipSuccess && from) e = hipMemcpy(p, from, n * sizeof(T), hipMemcpyHostToDevice);
+    return e;
+  }
+};
 
 template <class T>
 static hipError_t dalloc(hb_ctx* ctx, T** p, size_t n) {
@@ -1435,6 +1464,19 @@ static int32_t stage_upload(hb_ctx* ctx, int id, void* dst, const void* src, siz
   return HB_OK;
 }
 
+// The six sensor arrays of an estimator update (quaternion, angular velocity, linear acceleration, joint positions, joint
+// velocities, contact flags: staging ids ST_QUAT .. ST_CONTACT) into dst[0..5] on s, through pinned staging when `staged`.
+static int32_t upload_sensors(hb_ctx* ctx, const void* const dst[6], const void* const src[6], bool staged, hipStream_t s) {
+  static constexpr size_t bytes_per_instance[6] = {4 * 8, 3 * 8, 3 * 8, 10 * 8, 10 * 8, 4 * sizeof(int)};
+  for (int k = 0; k < 6; ++k) {
+    void* d = const_cast<void*>(dst[k]);
+    const size_t bytes = size_t(ctx->B) * bytes_per_instance[k];
+    if (staged) HB_TRY(stage_upload(ctx, ST_QUAT + k, d, src[k], bytes, s));
+    else HB_HIP(hipMemcpyAsync(d, src[k], bytes, hipMemcpyHostToDevice, s));
+  }
+  return HB_OK;
+}
+
 // Chunked hb_step_resident calls free-run: every chunk of instances is its own stream that goes from one step straight into the
 // next (instances are independent), without a per-step join.  The join into the two library streams happens here, lazily, at
 // the start of every OTHER entry point — the getters, the table updates, the joint command, hb_sync ... only know s_mpc / s_wbc —
@@ -1442,12 +1484,31 @@ static int32_t stage_upload(hb_ctx* ctx, int id, void* dst, const void* src, siz
 static void lazy_join(hb_ctx* ctx) {
   if (ctx->chunks_pending == 0 && ctx->fork_needed) return;  // nothing in flight (always, without chunks): no state is touched
   for (int c = 0; c < ctx->chunks_pending; ++c) {
-    (void)hipStreamWaitEvent(ctx->s_mpc, ctx->ev_sync[4 + c], 0);
-    (void)hipStreamWaitEvent(ctx->s_wbc, ctx->ev_sync[4 + c], 0);
+    (void)hipStreamWaitEvent(ctx->s_mpc, ctx->ev_sync[SYNC_JOIN + c], 0);
+    (void)hipStreamWaitEvent(ctx->s_wbc, ctx->ev_sync[SYNC_JOIN + c], 0);
   }
   ctx->chunks_pending = 0;
   ctx->fork_needed = true;
 }
+
+extern "C++" {  // (templates cannot have C linkage)
+// Enqueues a writer of the resident observation on s (launch()); with `fence`, between two ordering points: it starts after the work
+// queued so far on the MPC stream, and the MPC stream's later work after it (the observation feeds the next solve there).
+template <class F>
+static int32_t resident_write(hb_ctx* ctx, hipStream_t s, bool fence, F&& launch) {
+  if (fence) {
+    HB_HIP(hipEventRecord(ctx->ev_sync[SYNC_BEFORE_WRITER], ctx->s_mpc));
+    HB_HIP(hipStreamWaitEvent(s, ctx->ev_sync[SYNC_BEFORE_WRITER], 0));
+  }
+  launch();
+  HB_HIP(hipGetLastError());
+  if (fence) {
+    HB_HIP(hipEventRecord(ctx->ev_sync[SYNC_AFTER_WRITER], s));
+    HB_HIP(hipStreamWaitEvent(ctx->s_mpc, ctx->ev_sync[SYNC_AFTER_WRITER], 0));
+  }
+  return HB_OK;
+}
+}  // extern "C++"
 
 // joint command outputs and the per-instance controller flags (allocated on first use; loaded = 1, no emergency stop)
 static int32_t joint_state_alloc(hb_ctx* ctx) {
@@ -1465,8 +1526,7 @@ int32_t hb_joint_set_flags(hb_ctx* ctx, const int32_t* controller_loaded, const 
   if (ctx) lazy_join(ctx);
   if (!ctx) return HB_ERR_ARG;
   HB_HIP(hipSetDevice(ctx->device));
-  int32_t rc = joint_state_alloc(ctx);
-  if (rc != HB_OK) return rc;
+  HB_TRY(joint_state_alloc(ctx));
   HB_HIP(hipStreamSynchronize(ctx->s_wbc));
   if (controller_loaded) HB_HIP(hipMemcpy(ctx->jc_loaded, controller_loaded, size_t(ctx->B) * sizeof(int), hipMemcpyHostToDevice));
   if (emergency_stop) HB_HIP(hipMemcpy(ctx->jc_estop, emergency_stop, size_t(ctx->B) * sizeof(int), hipMemcpyHostToDevice));
@@ -1477,8 +1537,7 @@ int32_t hb_joint_get_emergency_stop(hb_ctx* ctx, int32_t* emergency_stop) {
   if (ctx) lazy_join(ctx);
   if (!ctx || !emergency_stop) return HB_ERR_ARG;
   HB_HIP(hipSetDevice(ctx->device));
-  int32_t rc = joint_state_alloc(ctx);
-  if (rc != HB_OK) return rc;
+  HB_TRY(joint_state_alloc(ctx));
   HB_HIP(hipStreamSynchronize(ctx->s_wbc));
   HB_HIP(hipMemcpy(emergency_stop, ctx->jc_estop, size_t(ctx->B) * sizeof(int), hipMemcpyDeviceToHost));
   return HB_OK;
@@ -1494,8 +1553,7 @@ int32_t hb_joint_command(hb_ctx* ctx, const hb_joint_gains* gains, double dt, do
   }
   HB_HIP(hipSetDevice(ctx->device));
   const size_t n = size_t(ctx->B) * HB_NJ;
-  int32_t rc_ = joint_state_alloc(ctx);
-  if (rc_ != HB_OK) return rc_;
+  HB_TRY(joint_state_alloc(ctx));
   hipStream_t s = ctx->s_wbc;
   hipLaunchKernelGGL(k_joint_command, dim3((ctx->B + 63) / 64), dim3(64), 0, s, ctx->w, ctx->dmodel, *gains, dt, ctx->jc_estop, ctx->jc_loaded,
                      ctx->jc_out);
@@ -1556,19 +1614,11 @@ int32_t hb_plant_step(hb_ctx* ctx, const double* tau, const int32_t* contact, do
   if (tau) HB_HIP(hipMemcpyAsync(p.tau, tau, B * 10 * 8, hipMemcpyHostToDevice, s));
   if (contact) HB_HIP(hipMemcpyAsync(p.contact, contact, B * 4 * sizeof(int), hipMemcpyHostToDevice, s));
   const double* dtau = tau ? p.tau : ctx->jc_out + 5 * B * HB_NJ;
-  if (to_resident) {
-    // the resident observation feeds the next hb_mpc_solve(NULL) / hb_refgen_update(NULL) on the MPC stream
-    HB_HIP(hipEventRecord(ctx->ev_sync[0], ctx->s_mpc));
-    HB_HIP(hipStreamWaitEvent(s, ctx->ev_sync[0], 0));
-  }
-  hipLaunchKernelGGL(k_plant, dim3(ctx->B), dim3(64), 0, s, p, ctx->dmodel, dtau, contact ? p.contact : nullptr, ctx->w.mode, dt, substeps,
-                     to_resident ? ctx->w.rbd : nullptr, to_resident ? ctx->b.x0 : nullptr, to_resident ? ctx->w.t_now : nullptr);
-  HB_HIP(hipGetLastError());
-  if (to_resident) {
-    HB_HIP(hipEventRecord(ctx->ev_sync[1], s));
-    HB_HIP(hipStreamWaitEvent(ctx->s_mpc, ctx->ev_sync[1], 0));
-  }
-  return HB_OK;
+  // the resident observation feeds the next hb_mpc_solve(NULL) / hb_refgen_update(NULL) on the MPC stream
+  return resident_write(ctx, s, to_resident, [&] {
+    hipLaunchKernelGGL(k_plant, dim3(ctx->B), dim3(64), 0, s, p, ctx->dmodel, dtau, contact ? p.contact : nullptr, ctx->w.mode, dt, substeps,
+                       to_resident ? ctx->w.rbd : nullptr, to_resident ? ctx->b.x0 : nullptr, to_resident ? ctx->w.t_now : nullptr);
+  });
 }
 
 int32_t hb_plant_get_state(hb_ctx* ctx, double* q, double* v, double* rbd, double* lambda, double* vdot) {
@@ -1648,20 +1698,84 @@ int32_t hb_refgen_set_schedule(hb_ctx* ctx, int32_t i0, int32_t cnt, const int32
   return HB_OK;
 }
 
-// Called (on the MPC stream) before node tables are overwritten while an iterate exists: keeps the grid that iterate lives on,
-// so that the next solve can bring it onto the new tables (k_warm_shift).  Instances [i0, i0 + cnt) are marked dirty.
-static int32_t save_grid_before_table_update(hb_ctx* ctx, int i0, int cnt) {
-  if (!ctx->traj_set) return HB_OK;
-  Batch& b = ctx->b;
-  const size_t B = ctx->B, N = ctx->Nmax;
-  hipStream_t s = ctx->s_mpc;
-  if (!ctx->grid_saved) {
+// ---- instance-range views and the launchers shared by the whole-batch entry points and the instance ranges ----------------------
+// Views: sub-batch [i0, i0 + cnt) of a batch, same layout, offset base pointers.
+static Batch batch_view(const Batch& b, int i0, int cnt) {
+  Batch v = b;
+  const size_t N = b.Nmax, o = i0;
+  v.B = cnt;
+  v.n_nodes += o; v.t += o * (N + 1); v.mode += o * N; v.xref += o * N * HB_NX; v.swing += o * N * 24;
+  v.x += o * (N + 1) * HB_NX; v.u += o * N * HB_NU; v.x0 += o * HB_NX; v.recs += o * N * REC_SIZE; v.gains += o * N * GAIN_SIZE;
+  v.dx += o * (N + 1) * HB_NX; v.du += o * N * HB_NU; v.acc += o * 4; v.partial += o * N * 3; v.ls_tail += o * LS_TAIL_MAX * N * 3; v.ls_norm += o * 2; v.accepted += o; v.perf += o * 4;
+  v.ric_fail += o; v.mpc_status += o; v.xp += o * (N + 1) * HB_NX; v.up += o * N * HB_NU; v.tp += o * (N + 1); v.modep += o * N;
+  v.np_nodes += o; v.grid_dirty += o; v.lqpark += o * (N + LqPark::trip_max) * LqPark::size;
+  return v;
+}
+static WbcBatch wbc_view(const WbcBatch& w, int Nmax, int i0, int cnt) {
+  WbcBatch v = w;
+  const size_t N = Nmax, o = i0;
+  v.B = cnt;
+  v.t_now += o; v.rbd += o * HB_NRBD; v.walk += o; v.xdes += o * HB_NX; v.udes += o * HB_NU; v.mode += o; v.stance += o;
+  v.sol += o * HB_NWBC; v.status += o; v.iters += o;
+  v.px += o * (N + 1) * HB_NX; v.pu += o * N * HB_NU; v.pt += o * (N + 1); v.pmode += o * N; v.pn += o;
+  return v;
+}
+// (what k_estimator reads and writes; the resident outputs res_* are the caller's, the contact-force observer is not viewed)
+static EstBatch est_view(const EstBatch& e, int i0, int cnt) {
+  EstBatch v = e;
+  const size_t o = i0;
+  v.B = cnt;
+  v.xhat += o * 18; v.P += o * 324; v.yaw_last += o; v.rbd += o * HB_NRBD; v.x += o * HB_NX;
+  v.quat += o * 4; v.w_local += o * 3; v.a_local += o * 3; v.qj += o * 10; v.qdj += o * 10; v.contact += o * 4;
+  return v;
+}
+static RefgenBatch refgen_view(const RefgenBatch& r, int i0, int cnt) {
+  RefgenBatch v = r;
+  const size_t o = i0;
+  v.B = cnt;
+  v.n_ev += o; v.ev += o * HB_MAX_EVENTS; v.modes += o * (HB_MAX_EVENTS + 1); v.stance += o * 12;
+  v.phases += o * 4 * (HB_MAX_EVENTS + 1) * RG_PHASE; v.t0 += o; v.cmd += o * 4; v.status += o; v.n_knots += o;
+  v.knot_t += o * RG_MAX_KNOTS; v.knot_x += o * RG_MAX_KNOTS * HB_NX;
+  return v;
+}
+
+// Before the node tables of b are overwritten while an iterate exists: keeps the grid that iterate lives on (`copy`; tp / modep /
+// np_nodes) and marks instances [i0, i0 + cnt) of b dirty, so that the next solve brings them onto the new tables (k_warm_shift).
+static int32_t launch_grid_save(hb_ctx* ctx, const Batch& b, bool copy, int i0, int cnt, hipStream_t s) {
+  const size_t B = b.B, N = b.Nmax;
+  if (copy) {
     HB_HIP(hipMemcpyAsync(b.tp, b.t, B * (N + 1) * 8, hipMemcpyDeviceToDevice, s));
     HB_HIP(hipMemcpyAsync(b.modep, b.mode, B * N * sizeof(int), hipMemcpyDeviceToDevice, s));
     HB_HIP(hipMemcpyAsync(b.np_nodes, b.n_nodes, B * sizeof(int), hipMemcpyDeviceToDevice, s));
-    ctx->grid_saved = true;
   }
   HB_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(b.grid_dirty + i0), 1, size_t(cnt), s));
+  return HB_OK;
+}
+
+// The iterate of b brought onto the current node tables (the previous iterate xp / up is the source).
+static void launch_warm_start(const hb_ctx* ctx, const Batch& b, hipStream_t s) {
+  hipLaunchKernelGGL(k_warm_shift, dim3(((ctx->Nmax + 1) * HB_NX + kWarmShiftThreads - 1) / kWarmShiftThreads, b.B), dim3(kWarmShiftThreads), 0, s, b,
+                     ctx->dmodel);
+  hipLaunchKernelGGL(k_grid_clean, dim3((b.B + 255) / 256), dim3(256), 0, s, b);
+}
+
+// Reference generation of the instances of b / r: planner, joint IK (when configured), node tables.
+static void launch_refgen(const hb_ctx* ctx, const Batch& b, const RefgenBatch& r, double horizon, hipStream_t s) {
+  hipLaunchKernelGGL(k_refgen, dim3((4 * b.B + 63) / 64), dim3(64), 0, s, b, r, ctx->dmodel, ctx->rg_cfg, horizon);
+  if (ctx->rg_cfg.joint_ik)
+    hipLaunchKernelGGL(k_refgen_ik, dim3((2 * b.B + 7) / 8), dim3(64), 0, s, b, r, ctx->dmodel, ctx->rg_cfg, horizon);
+  hipLaunchKernelGGL(k_refgen_nodes, dim3((b.B * ctx->Nmax + 63) / 64), dim3(64), 0, s, b, r, ctx->rg_cfg);
+}
+
+static void launch_estimator(const hb_ctx* ctx, const EstBatch& e, double dt, hipStream_t s) {
+  hipLaunchKernelGGL(k_estimator, dim3(e.B), dim3(64), 0, s, e, ctx->dmodel, ctx->est_cfg, dt);
+}
+
+// Called (on the MPC stream) before the whole batch's node tables are written: see launch_grid_save.
+static int32_t save_grid_before_table_update(hb_ctx* ctx, int i0, int cnt) {
+  if (!ctx->traj_set) return HB_OK;
+  HB_TRY(launch_grid_save(ctx, ctx->b, !ctx->grid_saved, i0, cnt, ctx->s_mpc));
+  ctx->grid_saved = true;
   return HB_OK;
 }
 
@@ -1681,24 +1795,17 @@ int32_t hb_refgen_update(hb_ctx* ctx, const double* t0, double horizon, const do
   const size_t B = ctx->B;
   RefgenBatch& r = ctx->rg;
   hipStream_t s = ctx->s_mpc;  // the tables belong to the MPC side
-  {
-    int32_t rc = save_grid_before_table_update(ctx, 0, ctx->B);
-    if (rc != HB_OK) return rc;
-  }
+  HB_TRY(save_grid_before_table_update(ctx, 0, ctx->B));
   if (status) {
     HB_HIP(hipMemcpyAsync(r.t0, t0, B * 8, hipMemcpyHostToDevice, s));
     HB_HIP(hipMemcpyAsync(r.cmd, cmd_vel, B * 4 * 8, hipMemcpyHostToDevice, s));
     if (x_now) HB_HIP(hipMemcpyAsync(ctx->b.x0, x_now, B * HB_NX * 8, hipMemcpyHostToDevice, s));
   } else {  // enqueue-only form (status through hb_refgen_get_status)
-    int32_t rc;
-    if ((rc = stage_upload(ctx, ST_T0, r.t0, t0, B * 8, s)) != HB_OK) return rc;
-    if ((rc = stage_upload(ctx, ST_CMD, r.cmd, cmd_vel, B * 4 * 8, s)) != HB_OK) return rc;
-    if (x_now && (rc = stage_upload(ctx, ST_X0, ctx->b.x0, x_now, B * HB_NX * 8, s)) != HB_OK) return rc;
+    HB_TRY(stage_upload(ctx, ST_T0, r.t0, t0, B * 8, s));
+    HB_TRY(stage_upload(ctx, ST_CMD, r.cmd, cmd_vel, B * 4 * 8, s));
+    if (x_now) HB_TRY(stage_upload(ctx, ST_X0, ctx->b.x0, x_now, B * HB_NX * 8, s));
   }
-  hipLaunchKernelGGL(k_refgen, dim3((4 * ctx->B + 63) / 64), dim3(64), 0, s, ctx->b, r, ctx->dmodel, ctx->rg_cfg, horizon);
-  if (ctx->rg_cfg.joint_ik)
-    hipLaunchKernelGGL(k_refgen_ik, dim3((2 * ctx->B + 7) / 8), dim3(64), 0, s, ctx->b, r, ctx->dmodel, ctx->rg_cfg, horizon);
-  hipLaunchKernelGGL(k_refgen_nodes, dim3((ctx->B * ctx->Nmax + 63) / 64), dim3(64), 0, s, ctx->b, r, ctx->rg_cfg);
+  launch_refgen(ctx, ctx->b, r, horizon, s);
   HB_HIP(hipGetLastError());
   r.init_stance = 0;
   if (status) {
@@ -1821,16 +1928,7 @@ static int32_t estimator_run(hb_ctx* ctx, double dt, int32_t to_resident, double
   hipStream_t s = ctx->s_wbc;
   e.res_rbd = to_resident ? ctx->w.rbd : nullptr;
   e.res_x0 = to_resident ? ctx->b.x0 : nullptr;
-  if (to_resident) {  // the resident observation feeds the MPC stream: write it between two ordering points (as hb_plant_step does)
-    HB_HIP(hipEventRecord(ctx->ev_sync[0], ctx->s_mpc));
-    HB_HIP(hipStreamWaitEvent(s, ctx->ev_sync[0], 0));
-  }
-  hipLaunchKernelGGL(k_estimator, dim3(ctx->B), dim3(64), 0, s, e, ctx->dmodel, ctx->est_cfg, dt);
-  HB_HIP(hipGetLastError());
-  if (to_resident) {
-    HB_HIP(hipEventRecord(ctx->ev_sync[1], s));
-    HB_HIP(hipStreamWaitEvent(ctx->s_mpc, ctx->ev_sync[1], 0));
-  }
+  HB_TRY(resident_write(ctx, s, to_resident, [&] { launch_estimator(ctx, e, dt, s); }));
   if (rbd) HB_HIP(hipMemcpyAsync(rbd, e.rbd, B * HB_NRBD * 8, hipMemcpyDeviceToHost, s));
   if (x_state) HB_HIP(hipMemcpyAsync(x_state, e.x, B * HB_NX * 8, hipMemcpyDeviceToHost, s));
   if (rbd || x_state) HB_HIP(hipStreamSynchronize(s));  // without host outputs the call is enqueue-only
@@ -1847,25 +1945,11 @@ int32_t hb_estimator_update(hb_ctx* ctx, double dt, const double* quat, const do
     return HB_ERR_STATE;
   }
   HB_HIP(hipSetDevice(ctx->device));
-  const size_t B = ctx->B;
-  EstBatch e = ctx->est;
-  hipStream_t s = ctx->s_wbc;  // the estimator belongs to the control-thread side (LeggedController::update)
-  if (rbd || x_state) {
-    HB_HIP(hipMemcpyAsync(const_cast<double*>(e.quat), quat, B * 4 * 8, hipMemcpyHostToDevice, s));
-    HB_HIP(hipMemcpyAsync(const_cast<double*>(e.w_local), ang_vel_local, B * 3 * 8, hipMemcpyHostToDevice, s));
-    HB_HIP(hipMemcpyAsync(const_cast<double*>(e.a_local), lin_acc_local, B * 3 * 8, hipMemcpyHostToDevice, s));
-    HB_HIP(hipMemcpyAsync(const_cast<double*>(e.qj), joint_pos, B * 10 * 8, hipMemcpyHostToDevice, s));
-    HB_HIP(hipMemcpyAsync(const_cast<double*>(e.qdj), joint_vel, B * 10 * 8, hipMemcpyHostToDevice, s));
-    HB_HIP(hipMemcpyAsync(const_cast<int*>(e.contact), contact_flag, B * 4 * sizeof(int), hipMemcpyHostToDevice, s));
-  } else {  // enqueue-only form: the sensor arrays go through pinned staging and are the caller's again on return
-    int32_t rc;
-    if ((rc = stage_upload(ctx, ST_QUAT, const_cast<double*>(e.quat), quat, B * 4 * 8, s)) != HB_OK) return rc;
-    if ((rc = stage_upload(ctx, ST_W, const_cast<double*>(e.w_local), ang_vel_local, B * 3 * 8, s)) != HB_OK) return rc;
-    if ((rc = stage_upload(ctx, ST_A, const_cast<double*>(e.a_local), lin_acc_local, B * 3 * 8, s)) != HB_OK) return rc;
-    if ((rc = stage_upload(ctx, ST_QJ, const_cast<double*>(e.qj), joint_pos, B * 10 * 8, s)) != HB_OK) return rc;
-    if ((rc = stage_upload(ctx, ST_QDJ, const_cast<double*>(e.qdj), joint_vel, B * 10 * 8, s)) != HB_OK) return rc;
-    if ((rc = stage_upload(ctx, ST_CONTACT, const_cast<int*>(e.contact), contact_flag, B * 4 * sizeof(int), s)) != HB_OK) return rc;
-  }
+  const EstBatch& e = ctx->est;
+  const void* const dst[6] = {e.quat, e.w_local, e.a_local, e.qj, e.qdj, e.contact};
+  const void* const src[6] = {quat, ang_vel_local, lin_acc_local, joint_pos, joint_vel, contact_flag};
+  // (enqueue-only form: the sensor arrays go through pinned staging and are the caller's again on return)
+  HB_TRY(upload_sensors(ctx, dst, src, !(rbd || x_state), ctx->s_wbc));  // the estimator belongs to the control-thread side (LeggedController::update)
   return estimator_run(ctx, dt, to_resident, rbd, x_state);
 }
 
@@ -1937,8 +2021,7 @@ int32_t hb_lcm_unframe(const uint8_t* frame, int32_t frame_len, char* channel, i
 int32_t hb_joint_command_lcm(hb_ctx* ctx, const hb_joint_gains* gains, double dt, int64_t timestamp_ns, uint8_t* low_cmd) {
   if (ctx) lazy_join(ctx);
   if (!ctx || !gains || !low_cmd) return HB_ERR_ARG;
-  int32_t rc = hb_joint_command(ctx, gains, dt, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
-  if (rc != HB_OK) return rc;
+  HB_TRY(hb_joint_command(ctx, gains, dt, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr));
   const size_t B = ctx->B, words = B * 62;
   if (!ctx->lcm_cmd) HB_HIP(dalloc(ctx, &ctx->lcm_cmd, words));
   hipStream_t s = ctx->s_wbc;
@@ -2033,10 +2116,7 @@ int32_t hb_mpc_set_references(hb_ctx* ctx, int32_t i0, int32_t cnt, const int32_
   const size_t N = ctx->Nmax;
   Batch& b = ctx->b;
   HB_HIP(hipSetDevice(ctx->device));
-  {
-    int32_t rc = save_grid_before_table_update(ctx, i0, cnt);
-    if (rc != HB_OK) return rc;
-  }
+  HB_TRY(save_grid_before_table_update(ctx, i0, cnt));
   HB_HIP(hipMemcpyAsync(b.n_nodes + i0, n_nodes, cnt * sizeof(int), hipMemcpyHostToDevice, ctx->s_mpc));
   HB_HIP(hipMemcpyAsync(b.t + i0 * (N + 1), t, cnt * (N + 1) * 8, hipMemcpyHostToDevice, ctx->s_mpc));
   HB_HIP(hipMemcpyAsync(b.mode + i0 * N, mode, cnt * N * sizeof(int), hipMemcpyHostToDevice, ctx->s_mpc));
@@ -2115,38 +2195,18 @@ int32_t hb_mpc_set_trajectory(hb_ctx* ctx, const double* x, const double* u) {
   return HB_OK;
 }
 
-// sub-batch [i0, i0 + cnt) of a batch: same layout, offset base pointers
-static Batch batch_view(const Batch& b, int i0, int cnt) {
-  Batch v = b;
-  const size_t N = b.Nmax, o = i0;
-  v.B = cnt;
-  v.n_nodes += o; v.t += o * (N + 1); v.mode += o * N; v.xref += o * N * HB_NX; v.swing += o * N * 24;
-  v.x += o * (N + 1) * HB_NX; v.u += o * N * HB_NU; v.x0 += o * HB_NX; v.recs += o * N * REC_SIZE; v.gains += o * N * GAIN_SIZE;
-  v.dx += o * (N + 1) * HB_NX; v.du += o * N * HB_NU; v.acc += o * 4; v.partial += o * N * 3; v.ls_tail += o * LS_TAIL_MAX * N * 3; v.ls_norm += o * 2; v.accepted += o; v.perf += o * 4;
-  v.ric_fail += o; v.mpc_status += o; v.xp += o * (N + 1) * HB_NX; v.up += o * N * HB_NU; v.tp += o * (N + 1); v.modep += o * N;
-  v.np_nodes += o; v.grid_dirty += o; v.lqpark += o * (N + LqPark::trip_max) * LqPark::size;
-  return v;
-}
-static WbcBatch wbc_view(const WbcBatch& w, int Nmax, int i0, int cnt) {
-  WbcBatch v = w;
-  const size_t N = Nmax, o = i0;
-  v.B = cnt;
-  v.t_now += o; v.rbd += o * HB_NRBD; v.walk += o; v.xdes += o * HB_NX; v.udes += o * HB_NU; v.mode += o; v.stance += o;
-  v.sol += o * HB_NWBC; v.status += o; v.iters += o;
-  v.px += o * (N + 1) * HB_NX; v.pu += o * N * HB_NU; v.pt += o * (N + 1); v.pmode += o * N; v.pn += o;
-  return v;
+// The tables changed: the iterate becomes the previous iterate, the source of the warm start.
+static void swap_iterate(hb_ctx* ctx) {
+  std::swap(ctx->b.x, ctx->b.xp);
+  std::swap(ctx->b.u, ctx->b.up);
+  ++ctx->graph_epoch;  // captured range graphs hold the old pointers
 }
 
 // Brings the iterate onto the current node tables if they changed since it was computed (see k_warm_shift); MPC stream.
 static int32_t warm_start_onto_new_tables(hb_ctx* ctx) {
   if (!ctx->grid_saved) return HB_OK;
-  Batch& b = ctx->b;
-  std::swap(b.x, b.xp);
-  std::swap(b.u, b.up);
-  ++ctx->graph_epoch;  // captured chunk graphs hold the old pointers
-  hipLaunchKernelGGL(k_warm_shift, dim3(((ctx->Nmax + 1) * HB_NX + kWarmShiftThreads - 1) / kWarmShiftThreads, ctx->B), dim3(kWarmShiftThreads), 0, ctx->s_mpc, b,
-                     ctx->dmodel);
-  hipLaunchKernelGGL(k_grid_clean, dim3((ctx->B + 255) / 256), dim3(256), 0, ctx->s_mpc, b);
+  swap_iterate(ctx);
+  launch_warm_start(ctx, ctx->b, ctx->s_mpc);
   HB_HIP(hipGetLastError());
   ctx->grid_saved = false;
   return HB_OK;
@@ -2194,25 +2254,19 @@ static void launch_ric_fwd(hb_ctx* ctx, const Batch& b, int B, int concurrent, h
   else hipLaunchKernelGGL(k_ric_fwd, dim3(B), dim3(64), 0, s, b);
 }
 
-static int32_t mpc_iterations(hb_ctx* ctx, int i0 = 0, int cnt = -1, hipStream_t stream = nullptr) {
-  const bool whole = cnt < 0;
-  if (whole) {
-    int32_t rc = warm_start_onto_new_tables(ctx);
-    if (rc != HB_OK) return rc;
-  }
-  const Batch b = whole ? ctx->b : batch_view(ctx->b, i0, cnt);
-  hipStream_t s = whole ? ctx->s_mpc : stream;
+// The SQP iterations of the instances of b on s; `timed`: iteration 0 records the phase events ev[EV_LQ_BEGIN .. EV_LS_END].
+static int32_t enqueue_sqp(hb_ctx* ctx, const Batch& b, hipStream_t s, bool timed) {
   const int B = b.B, N = ctx->Nmax;
   for (int it = 0; it < ctx->config.sqp_iterations; ++it) {
-    const bool timed = (it == 0) && whole;
+    const bool mark = timed && it == 0;
     hipLaunchKernelGGL(k_set_x0, dim3((B * HB_NX + 255) / 256), dim3(256), 0, s, b);
-    if (timed) HB_HIP(hipEventRecord(ctx->ev[0], s));
+    if (mark) HB_HIP(hipEventRecord(ctx->ev[EV_LQ_BEGIN], s));
     launch_lq(ctx, b, B, ctx->B, s);
-    if (timed) HB_HIP(hipEventRecord(ctx->ev[1], s));
+    if (mark) HB_HIP(hipEventRecord(ctx->ev[EV_LQ_END], s));
     launch_ric_bwd(ctx, b, B, ctx->B, s);
-    if (timed) HB_HIP(hipEventRecord(ctx->ev[2], s));
+    if (mark) HB_HIP(hipEventRecord(ctx->ev[EV_RIC_BWD_END], s));
     launch_ric_fwd(ctx, b, B, ctx->B, s);
-    if (timed) HB_HIP(hipEventRecord(ctx->ev[3], s));
+    if (mark) HB_HIP(hipEventRecord(ctx->ev[EV_RIC_FWD_END], s));
     // filter line search: the full step for every instance, node-parallel; then the backtracking tail in one launch
     hipLaunchKernelGGL(k_ls_eval, dim3((B * N + 63) / 64), dim3(64), 0, s, b, ctx->dmodel, ctx->dconfig, 1.0);
     hipLaunchKernelGGL(k_ls_decide, dim3(B), dim3(64), 0, s, b, ctx->dconfig, 1.0);
@@ -2233,16 +2287,21 @@ static int32_t mpc_iterations(hb_ctx* ctx, int i0 = 0, int cnt = -1, hipStream_t
         a_win = a;
       }
     }
-    if (timed) HB_HIP(hipEventRecord(ctx->ev[4], s));
+    if (mark) HB_HIP(hipEventRecord(ctx->ev[EV_LS_END], s));
     // evaluated per iteration: ric_fail / accepted are overwritten by the next one
     hipLaunchKernelGGL(k_mpc_status, dim3((B + 255) / 256), dim3(256), 0, s, b, it == 0 ? 1 : 0);
   }
   HB_HIP(hipGetLastError());
-  {
-    std::lock_guard<std::mutex> lk(ctx->mtx);
-    if (whole) ctx->timed = true;
-    ctx->stats.n_mpc_solves += B;
-  }
+  return HB_OK;
+}
+
+// MPC solve of the whole batch on the MPC stream: warm start onto new tables, the timed SQP iterations, the solve counted.
+static int32_t mpc_solve_batch(hb_ctx* ctx) {
+  HB_TRY(warm_start_onto_new_tables(ctx));
+  HB_TRY(enqueue_sqp(ctx, ctx->b, ctx->s_mpc, true));
+  std::lock_guard<std::mutex> lk(ctx->mtx);
+  ctx->timed = true;
+  ctx->stats.n_mpc_solves += ctx->B;
   return HB_OK;
 }
 
@@ -2258,7 +2317,7 @@ int32_t hb_mpc_solve(hb_ctx* ctx, const double* x0) {
     HB_HIP(hipMemcpyAsync(ctx->b.x0, x0, size_t(ctx->B) * HB_NX * 8, hipMemcpyHostToDevice, ctx->s_mpc));
     HB_HIP(hipStreamSynchronize(ctx->s_mpc));
   }
-  return mpc_iterations(ctx);
+  return mpc_solve_batch(ctx);
 }
 
 int32_t hb_mpc_get_solution(hb_ctx* ctx, int32_t i0, int32_t cnt, double* x, double* u) {
@@ -2307,7 +2366,8 @@ __global__ __launch_bounds__(256) void k_publish(const double* __restrict__ x, c
     else pn[e - nx - nu - nt - nm] = n_nodes[e - nx - nu - nt - nm];
   }
 }
-static void launch_publish(const Batch& b, const WbcBatch& w, size_t cnt, size_t N, hipStream_t s) {
+static void launch_publish(const Batch& b, const WbcBatch& w, hipStream_t s) {
+  const size_t cnt = b.B, N = b.Nmax;
   const size_t nx = cnt * (N + 1) * HB_NX, nu = cnt * N * HB_NU, nt = cnt * (N + 1), nm = cnt * N, nn = cnt;
   const size_t total = nx + nu + nt + nm + nn;
   const unsigned blocks = unsigned(std::min<size_t>((total + 256 * 4 - 1) / (256 * 4), 8192));   // four elements per thread, grid-stride beyond
@@ -2317,7 +2377,6 @@ static void launch_publish(const Batch& b, const WbcBatch& w, size_t cnt, size_t
 int32_t hb_mpc_publish(hb_ctx* ctx) {
   if (ctx) lazy_join(ctx);
   if (!ctx) return HB_ERR_ARG;
-  const size_t B = ctx->B, N = ctx->Nmax;
   HB_HIP(hipSetDevice(ctx->device));
   // device-to-device copy of the solution into the policy buffers read by the WBC stream
   hipStream_t s = ctx->s_mpc;
@@ -2325,34 +2384,41 @@ int32_t hb_mpc_publish(hb_ctx* ctx) {
   // only the copies below touch the policy buffers: they wait for the last policy evaluation on the WBC stream, the SQP
   // kernels of the next solve do not (so a WBC solve overlaps the next LQ approximation)
   if (ctx->policy_read_pending) {
-    HB_HIP(hipStreamWaitEvent(s, ctx->ev[8], 0));
+    HB_HIP(hipStreamWaitEvent(s, ctx->ev[EV_POLICY_READ], 0));
     ctx->policy_read_pending = false;
   }
-  launch_publish(ctx->b, ctx->w, B, N, s);
-  HB_HIP(hipEventRecord(ctx->ev[7], s));
-  HB_HIP(hipStreamWaitEvent(ctx->s_wbc, ctx->ev[7], 0));
+  launch_publish(ctx->b, ctx->w, s);
+  HB_HIP(hipEventRecord(ctx->ev[EV_PUBLISHED], s));
+  HB_HIP(hipStreamWaitEvent(ctx->s_wbc, ctx->ev[EV_PUBLISHED], 0));
   ctx->w.policy_valid = true;
   return HB_OK;
 }
 
-static int32_t wbc_launch(hb_ctx* ctx, bool from_policy, double dt) {
-  (void)dt;
-  WbcBatch& w = ctx->w;
-  hipStream_t s = ctx->s_wbc;
-  std::lock_guard<std::mutex> lk(ctx->mtx);  // enqueue only (pairs with hb_mpc_publish on the MPC thread)
-  HB_HIP(hipEventRecord(ctx->ev[5], s));
+// Policy evaluation (`from_policy`; then policy_read records when the policy buffers are free again) and WBC of the instances of w,
+// instances [i0, i0 + w.B) of the batch, on s: the WBC kernel of the configuration and of the certificate switch.
+static int32_t launch_policy_wbc(hb_ctx* ctx, const WbcBatch& w, int i0, bool from_policy, hipEvent_t policy_read, hipStream_t s) {
   if (from_policy) {
-    hipLaunchKernelGGL(k_policy_eval, dim3((ctx->B + 63) / 64), dim3(64), 0, s, w, ctx->Nmax, ctx->dconfig);
-    HB_HIP(hipEventRecord(ctx->ev[8], s));  // the policy buffers are free again once this has run
-    ctx->policy_read_pending = true;
+    hipLaunchKernelGGL(k_policy_eval, dim3((w.B + 63) / 64), dim3(64), 0, s, w, ctx->Nmax, ctx->dconfig);
+    if (policy_read) HB_HIP(hipEventRecord(policy_read, s));
   }
   if (ctx->config.wbc_type == 1)
-    hipLaunchKernelGGL(k_hwbc, dim3(ctx->B), dim3(64), HoLdsDev::total * sizeof(double), s, w, ctx->dmodel, ctx->dconfig);
-  else if (ctx->wbc_cert)
-    hipLaunchKernelGGL(k_wbc_cert, dim3(ctx->B), dim3(64), 0, s, w, ctx->dmodel, ctx->dconfig, ctx->cert_buf, ctx->dual_buf);
+    hipLaunchKernelGGL(k_hwbc, dim3(w.B), dim3(64), HoLdsDev::total * sizeof(double), s, w, ctx->dmodel, ctx->dconfig);
+  else if (ctx->wbc_cert)  // (in a range graph: chosen at capture, hb_wbc_set_certificate re-captures)
+    hipLaunchKernelGGL(k_wbc_cert, dim3(w.B), dim3(64), 0, s, w, ctx->dmodel, ctx->dconfig, ctx->cert_buf + size_t(i0) * HB_WBC_CERT_SIZE,
+                       ctx->dual_buf + size_t(i0) * HB_WBC_NCONS_MAX);
   else
-    hipLaunchKernelGGL(k_wbc, dim3(ctx->B), dim3(64), 0, s, w, ctx->dmodel, ctx->dconfig);
-  HB_HIP(hipEventRecord(ctx->ev[6], s));
+    hipLaunchKernelGGL(k_wbc, dim3(w.B), dim3(64), 0, s, w, ctx->dmodel, ctx->dconfig);
+  return HB_OK;
+}
+
+// WBC of the whole batch on the WBC stream, timed (ev[EV_WBC_BEGIN .. EV_WBC_END]) and counted
+static int32_t wbc_launch(hb_ctx* ctx, bool from_policy) {
+  hipStream_t s = ctx->s_wbc;
+  std::lock_guard<std::mutex> lk(ctx->mtx);  // enqueue only (pairs with hb_mpc_publish on the MPC thread)
+  HB_HIP(hipEventRecord(ctx->ev[EV_WBC_BEGIN], s));
+  HB_TRY(launch_policy_wbc(ctx, ctx->w, 0, from_policy, ctx->ev[EV_POLICY_READ], s));
+  if (from_policy) ctx->policy_read_pending = true;
+  HB_HIP(hipEventRecord(ctx->ev[EV_WBC_END], s));
   HB_HIP(hipGetLastError());
   ctx->stats.n_wbc_solves += ctx->B;
   ctx->cert_last = ctx->wbc_cert;
@@ -2376,8 +2442,7 @@ int32_t hb_wbc_update(hb_ctx* ctx, const double* t_now, const double* rbd, const
     HB_HIP(hipMemcpyAsync(w.rbd, rbd, B * HB_NRBD * 8, hipMemcpyHostToDevice, s));
   }
   if (walk_flag) HB_HIP(hipMemcpyAsync(w.walk, walk_flag, B * sizeof(int), hipMemcpyHostToDevice, s));
-  int32_t rc = wbc_launch(ctx, true, dt);
-  if (rc != HB_OK) return rc;
+  HB_TRY(wbc_launch(ctx, true));
   if (sol) HB_HIP(hipMemcpyAsync(sol, w.sol, B * HB_NWBC * 8, hipMemcpyDeviceToHost, s));
   if (x_des) HB_HIP(hipMemcpyAsync(x_des, w.xdes, B * HB_NX * 8, hipMemcpyDeviceToHost, s));
   if (u_des) HB_HIP(hipMemcpyAsync(u_des, w.udes, B * HB_NU * 8, hipMemcpyDeviceToHost, s));
@@ -2401,8 +2466,7 @@ int32_t hb_wbc_update_direct(hb_ctx* ctx, const double* x_des, const double* u_d
   HB_HIP(hipMemcpyAsync(w.mode, mode, B * sizeof(int), hipMemcpyHostToDevice, s));
   if (stance_flag) HB_HIP(hipMemcpyAsync(w.stance, stance_flag, B * sizeof(int), hipMemcpyHostToDevice, s));
   else HB_HIP(hipMemsetAsync(w.stance, 0, B * sizeof(int), s));
-  int32_t rc = wbc_launch(ctx, false, dt);
-  if (rc != HB_OK) return rc;
+  HB_TRY(wbc_launch(ctx, false));
   if (sol) HB_HIP(hipMemcpyAsync(sol, w.sol, B * HB_NWBC * 8, hipMemcpyDeviceToHost, s));
   if (status) HB_HIP(hipMemcpyAsync(status, w.status, B * sizeof(int), hipMemcpyDeviceToHost, s));
   HB_HIP(hipStreamSynchronize(s));
@@ -2447,21 +2511,105 @@ int32_t hb_set_resident_x0_sequence(hb_ctx* ctx, int32_t n_seq, const double* x0
   return HB_OK;
 }
 
-// Publish + policy evaluation + WBC of the instance range [i0, i0 + cnt) on stream s: the tail of one range's step / tick.
-static int32_t range_publish_policy_wbc(hb_ctx* ctx, int i0, int cnt, hipStream_t s) {
-  const size_t N = ctx->Nmax;
+// ---- instance ranges (hb_set_chunks > 1) --------------------------------------------------------------------------------------
+// A chunked hb_step_resident / hb_tick_resident runs every range of instances on a stream of its own, which goes from one call straight
+// into the next (instances are independent) without a per-call join (lazy_join).
+
+// SQP iterations, publish, policy evaluation and WBC of the instance range [i0, i0 + cnt) on s: the tail of a range's step and tick.
+static int32_t enqueue_range_update(hb_ctx* ctx, int i0, int cnt, hipStream_t s) {
   const Batch b = batch_view(ctx->b, i0, cnt);
   const WbcBatch w = wbc_view(ctx->w, ctx->Nmax, i0, cnt);
-  launch_publish(b, w, size_t(cnt), N, s);
-  hipLaunchKernelGGL(k_policy_eval, dim3((cnt + 63) / 64), dim3(64), 0, s, w, ctx->Nmax, ctx->dconfig);
-  if (ctx->config.wbc_type == 1)
-    hipLaunchKernelGGL(k_hwbc, dim3(cnt), dim3(64), HoLdsDev::total * sizeof(double), s, w, ctx->dmodel, ctx->dconfig);
-  else if (ctx->wbc_cert)  // (chosen when a range graph is captured: hb_wbc_set_certificate re-captures them)
-    hipLaunchKernelGGL(k_wbc_cert, dim3(cnt), dim3(64), 0, s, w, ctx->dmodel, ctx->dconfig, ctx->cert_buf + size_t(i0) * HB_WBC_CERT_SIZE,
-                       ctx->dual_buf + size_t(i0) * HB_WBC_NCONS_MAX);
-  else
-    hipLaunchKernelGGL(k_wbc, dim3(cnt), dim3(64), 0, s, w, ctx->dmodel, ctx->dconfig);
+  HB_TRY(enqueue_sqp(ctx, b, s, false));
+  launch_publish(b, w, s);
+  return launch_policy_wbc(ctx, w, i0, true, nullptr, s);
+}
+
+// Fork, only when another entry point ran since the last chunked call, the tables changed or the range count did (`fork` tells): the
+// range streams start after everything queued so far on the MPC stream (table updates, warm start, resident-input writers ordered
+// into it) and on the WBC stream (resident rbd / time writers, the last reader of the policy buffers).
+static int32_t fork_ranges(hb_ctx* ctx, bool& fork) {
+  fork = ctx->fork_needed || ctx->grid_saved || ctx->chunks_pending != ctx->n_chunks;
+  if (!fork) return HB_OK;
+  ++ctx->dbg_forks;
+  lazy_join(ctx);
+  HB_TRY(warm_start_onto_new_tables(ctx));
+  HB_HIP(hipEventRecord(ctx->ev_sync[SYNC_FORK_MPC], ctx->s_mpc));
+  HB_HIP(hipEventRecord(ctx->ev_sync[SYNC_FORK_WBC], ctx->s_wbc));
   return HB_OK;
+}
+
+extern "C++" {
+// body(c, i0, cnt, s) enqueues range c, instances [i0, i0 + cnt), on its stream s: behind the fork points when `fork`, ahead of the
+// range's join point.
+template <class F>
+static int32_t for_each_range(hb_ctx* ctx, bool fork, F&& body) {
+  const int per = (ctx->B + ctx->n_chunks - 1) / ctx->n_chunks;
+  int used = 0;
+  for (int c = 0; c < ctx->n_chunks; ++c) {
+    const int i0 = c * per, cnt = std::min(per, ctx->B - i0);
+    if (cnt <= 0) break;
+    hipStream_t s = ctx->s_chunk[c];
+    if (fork) {
+      HB_HIP(hipStreamWaitEvent(s, ctx->ev_sync[SYNC_FORK_MPC], 0));
+      HB_HIP(hipStreamWaitEvent(s, ctx->ev_sync[SYNC_FORK_WBC], 0));
+    }
+    HB_TRY(body(c, i0, cnt, s));
+    HB_HIP(hipGetLastError());
+    HB_HIP(hipEventRecord(ctx->ev_sync[SYNC_JOIN + c], s));
+    used = c + 1;
+  }
+  ctx->chunks_pending = used;
+  return HB_OK;
+}
+
+// The step of range c, enqueue() on s: with `graphable`, one launch of a hipGraph of it (captured on first use in the graph epoch, kept
+// in `slot`), else direct launches.
+template <class F>
+static int32_t enqueue_range_step(hb_ctx* ctx, int c, int slot, bool graphable, hipStream_t s, F&& enqueue) {
+  if (graphable) {
+    hipGraphExec_t& ge = ctx->chunk_graph[c][slot];
+    if (ge && ctx->chunk_graph_epoch[c][slot] != ctx->graph_epoch) { (void)hipGraphExecDestroy(ge); ge = nullptr; }
+    if (!ge && !ctx->graph_disabled) {
+      hipGraph_t g = nullptr;
+      bool ok = false;
+      if (hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal) == hipSuccess) {
+        const int32_t rc = enqueue();
+        const hipError_t ce = hipStreamEndCapture(s, &g);
+        ++ctx->dbg_captures;
+        ok = rc == HB_OK && ce == hipSuccess && g && hipGraphInstantiate(&ge, g, nullptr, nullptr, 0) == hipSuccess;
+        if (g) (void)hipGraphDestroy(g);
+      }
+      if (ok) {
+        ctx->chunk_graph_epoch[c][slot] = ctx->graph_epoch;
+      } else {
+        // a capture / instantiation that fails once is not retried on every step (it would double the host cost for good):
+        // this context steps its ranges with direct launches from now on; hb_debug_chunk_counters reports the failure
+        ge = nullptr;
+        ctx->graph_disabled = true;
+        ++ctx->dbg_capture_failures;
+      }
+      (void)hipGetLastError();
+    }
+    if (ge && hipGraphLaunch(ge, s) == hipSuccess) {
+      ++ctx->dbg_graph_launches;
+      return HB_OK;
+    }
+  }
+  ++ctx->dbg_direct;
+  return enqueue();
+}
+}  // extern "C++"
+
+// End of a chunked step / tick: every range has solved, published and read its policy.  `steady`: the call did not fork.
+static void finish_ranges(hb_ctx* ctx, bool steady) {
+  ctx->fork_needed = false;
+  ctx->steady_chunked_steps = steady ? ctx->steady_chunked_steps + 1 : 0;
+  std::lock_guard<std::mutex> lk(ctx->mtx);
+  ctx->w.policy_valid = true;
+  ctx->policy_read_pending = false;  // the lazy join orders the next policy write (by another entry point) after these readers
+  ctx->stats.n_mpc_solves += ctx->B;
+  ctx->stats.n_wbc_solves += ctx->B;
+  ctx->cert_last = ctx->wbc_cert;
 }
 
 int32_t hb_step_resident(hb_ctx* ctx, double dt) {
@@ -2480,112 +2628,33 @@ int32_t hb_step_resident(hb_ctx* ctx, double dt) {
   if (ctx->n_chunks <= 1) {
     lazy_join(ctx);
     if (x0_next) HB_HIP(hipMemcpyAsync(ctx->b.x0, x0_next, size_t(ctx->B) * HB_NX * 8, hipMemcpyDeviceToDevice, ctx->s_mpc));
-    int32_t rc = mpc_iterations(ctx);
-    if (rc != HB_OK) return rc;
-    rc = hb_mpc_publish(ctx);
-    if (rc != HB_OK) return rc;
-    rc = wbc_launch(ctx, true, dt);
-    if (rc != HB_OK) return rc;
+    HB_TRY(mpc_solve_batch(ctx));
+    HB_TRY(hb_mpc_publish(ctx));
+    HB_TRY(wbc_launch(ctx, true));
     // hb_mpc_publish already orders the next policy write after this step's policy evaluation.  The next step's SQP
     // kernels are additionally held back until this WBC has finished: letting them time-slice the CUs with the WBC
     // cost throughput (re-measured in round 2 with the lighter WBC: 367 k -> 357 k updates/s; the LQ kernel fills every
     // CU's LDS) and blurred the per-kernel timings.
-    HB_HIP(hipStreamWaitEvent(ctx->s_mpc, ctx->ev[6], 0));
+    HB_HIP(hipStreamWaitEvent(ctx->s_mpc, ctx->ev[EV_WBC_END], 0));
     return HB_OK;
   }
-  // pipelined: every chunk of instances is a linear sequence x0 -> MPC -> publish -> policy evaluation -> WBC on its own stream,
-  // and consecutive steps of one chunk follow each other on that stream without waiting for the other chunks (lazy_join): the
-  // per-instance sweeps of one chunk (k_ric_bwd: a serial chain over the horizon that leaves most SIMDs idle at small batch
-  // sizes) overlap the LQ kernel of the others, across step boundaries.
-  // Fork (only when another entry point ran since the last chunked step, or the tables changed): the chunk streams start after
-  // everything queued so far on the MPC stream (table updates, warm start, resident-input writers ordered into it) and on the
-  // WBC stream (resident rbd / time writers, the last reader of the policy buffers).
-  const bool fork = ctx->fork_needed || ctx->grid_saved || ctx->chunks_pending != ctx->n_chunks;
-  if (fork) {
-    ++ctx->dbg_forks;
-    lazy_join(ctx);
-    int32_t rc = warm_start_onto_new_tables(ctx);
-    if (rc != HB_OK) return rc;
-    HB_HIP(hipEventRecord(ctx->ev_sync[2], ctx->s_mpc));
-    HB_HIP(hipEventRecord(ctx->ev_sync[3], ctx->s_wbc));
-  }
-  const int per = (ctx->B + ctx->n_chunks - 1) / ctx->n_chunks;
-  const size_t N = ctx->Nmax;
-  int used = 0;
-  for (int c = 0; c < ctx->n_chunks; ++c) {
-    const int i0 = c * per, cnt = std::min(per, ctx->B - i0);
-    if (cnt <= 0) break;
-    hipStream_t s = ctx->s_chunk[c];
-    if (fork) {
-      HB_HIP(hipStreamWaitEvent(s, ctx->ev_sync[2], 0));
-      HB_HIP(hipStreamWaitEvent(s, ctx->ev_sync[3], 0));
-    }
-    auto enqueue = [&]() -> int32_t {
+  // pipelined: every range of instances is a linear sequence x0 -> MPC -> publish -> policy evaluation -> WBC on its own stream, and
+  // consecutive steps of one range follow each other on that stream without waiting for the other ranges: the per-instance sweeps of
+  // one range (k_ric_bwd: a serial chain over the horizon that leaves most SIMDs idle at small batch sizes) overlap the LQ kernel of
+  // the others, across step boundaries.
+  bool fork;
+  HB_TRY(fork_ranges(ctx, fork));
+  // steady state (no fork for a few steps, the x0 slot fits): the step of a range is replayed as one graph launch
+  const int slot = ctx->n_seq > 0 ? seq_slot : 0;
+  const bool graphable = !fork && ctx->steady_chunked_steps >= 2 && slot < hb_ctx::GRAPH_SLOTS && ctx->n_seq <= hb_ctx::GRAPH_SLOTS;
+  HB_TRY(for_each_range(ctx, fork, [&](int c, int i0, int cnt, hipStream_t s) {
+    return enqueue_range_step(ctx, c, slot, graphable, s, [&]() -> int32_t {
       if (x0_next)
         HB_HIP(hipMemcpyAsync(ctx->b.x0 + size_t(i0) * HB_NX, x0_next + size_t(i0) * HB_NX, size_t(cnt) * HB_NX * 8, hipMemcpyDeviceToDevice, s));
-      int32_t rc = mpc_iterations(ctx, i0, cnt, s);
-      if (rc != HB_OK) return rc;
-      return range_publish_policy_wbc(ctx, i0, cnt, s);
-    };
-    // steady state (no fork for a few steps, the x0 slot fits): replay the step as one graph launch
-    const int slot = ctx->n_seq > 0 ? seq_slot : 0;
-    const bool graphable = !fork && ctx->steady_chunked_steps >= 2 && slot < hb_ctx::GRAPH_SLOTS && ctx->n_seq <= hb_ctx::GRAPH_SLOTS;
-    bool launched = false;
-    if (graphable) {
-      hipGraphExec_t& ge = ctx->chunk_graph[c][slot];
-      if (ge && ctx->chunk_graph_epoch[c][slot] != ctx->graph_epoch) { (void)hipGraphExecDestroy(ge); ge = nullptr; }
-      if (!ge && !ctx->graph_disabled) {
-        hipGraph_t g = nullptr;
-        const hipError_t be = hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal);
-        bool ok = false;
-        if (be == hipSuccess) {
-          const int32_t rc = enqueue();
-          const hipError_t ce = hipStreamEndCapture(s, &g);
-          ++ctx->dbg_captures;
-          if (rc == HB_OK) {  // the capture pass counted a solve that was never enqueued: the launch / direct pass below counts the real one
-            std::lock_guard<std::mutex> lk(ctx->mtx);
-            ctx->stats.n_mpc_solves -= cnt;
-          }
-          ok = rc == HB_OK && ce == hipSuccess && g && hipGraphInstantiate(&ge, g, nullptr, nullptr, 0) == hipSuccess;
-          if (g) (void)hipGraphDestroy(g);
-        }
-        if (ok) {
-          ctx->chunk_graph_epoch[c][slot] = ctx->graph_epoch;
-        } else {
-          // a capture / instantiation that fails once is not retried on every step (it would double the host cost for good):
-          // this context steps its ranges with direct launches from now on; hb_debug_chunk_counters reports the failure
-          ge = nullptr;
-          ctx->graph_disabled = true;
-          ++ctx->dbg_capture_failures;
-        }
-        (void)hipGetLastError();
-      }
-      if (ge && hipGraphLaunch(ge, s) == hipSuccess) {
-        launched = true;
-        ++ctx->dbg_graph_launches;
-        std::lock_guard<std::mutex> lk(ctx->mtx);
-        ctx->stats.n_mpc_solves += cnt;
-      }
-    }
-    if (!launched) {
-      ++ctx->dbg_direct;
-      const int32_t rc = enqueue();
-      if (rc != HB_OK) return rc;
-    }
-    HB_HIP(hipGetLastError());
-    HB_HIP(hipEventRecord(ctx->ev_sync[4 + c], s));
-    used = c + 1;
-  }
-  ctx->chunks_pending = used;
-  ctx->fork_needed = false;
-  ctx->steady_chunked_steps = fork ? 0 : ctx->steady_chunked_steps + 1;
-  {
-    std::lock_guard<std::mutex> lk(ctx->mtx);
-    ctx->w.policy_valid = true;
-    ctx->policy_read_pending = false;  // the lazy join orders the next policy write (by another entry point) after these readers
-    ctx->stats.n_wbc_solves += ctx->B;
-    ctx->cert_last = ctx->wbc_cert;
-  }
+      return enqueue_range_update(ctx, i0, cnt, s);
+    });
+  }));
+  finish_ranges(ctx, !fork);
   return HB_OK;
 }
 
@@ -2603,11 +2672,10 @@ int32_t hb_tick_resident(hb_ctx* ctx, double dt_est, const double* quat, const d
       !(horizon > 0.0))
     return HB_ERR_ARG;
   if (ctx->n_chunks <= 1) {  // one stream: the four calls themselves (enqueue-only forms)
-    int32_t rc = hb_set_resident_time(ctx, t_now);
-    if (rc == HB_OK) rc = hb_estimator_update(ctx, dt_est, quat, ang_vel_local, lin_acc_local, joint_pos, joint_vel, contact_flag, 1, nullptr, nullptr);
-    if (rc == HB_OK) rc = hb_refgen_update(ctx, t_now, horizon, nullptr, cmd_vel, nullptr);
-    if (rc == HB_OK) rc = hb_step_resident(ctx, dt_wbc);
-    return rc;
+    HB_TRY(hb_set_resident_time(ctx, t_now));
+    HB_TRY(hb_estimator_update(ctx, dt_est, quat, ang_vel_local, lin_acc_local, joint_pos, joint_vel, contact_flag, 1, nullptr, nullptr));
+    HB_TRY(hb_refgen_update(ctx, t_now, horizon, nullptr, cmd_vel, nullptr));
+    return hb_step_resident(ctx, dt_wbc);
   }
   if (!ctx->est_ready || !ctx->rg_ready || !ctx->refs_set || !ctx->traj_set) {
     ctx->err = "hb_tick_resident: estimator / reference generation / references / trajectory not initialised";
@@ -2619,109 +2687,57 @@ int32_t hb_tick_resident(hb_ctx* ctx, double dt_est, const double* quat, const d
       return HB_ERR_STATE;
     }
   HB_HIP(hipSetDevice(ctx->device));
-  const size_t B = ctx->B, N = ctx->Nmax;
+  const size_t B = ctx->B;
+  hb_ctx::TickUpload& up = ctx->up;
   if (!ctx->s_up) {
     HB_HIP(hipStreamCreateWithFlags(&ctx->s_up, hipStreamNonBlocking));
     HB_HIP(hipEventCreateWithFlags(&ctx->ev_up, hipEventDisableTiming));
     for (auto& ev : ctx->ev_consumed) HB_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-    HB_HIP(dalloc(ctx, &ctx->up.quat, B * 4)); HB_HIP(dalloc(ctx, &ctx->up.w, B * 3)); HB_HIP(dalloc(ctx, &ctx->up.a, B * 3));
-    HB_HIP(dalloc(ctx, &ctx->up.qj, B * 10)); HB_HIP(dalloc(ctx, &ctx->up.qdj, B * 10)); HB_HIP(dalloc(ctx, &ctx->up.contact, B * 4));
-    HB_HIP(dalloc(ctx, &ctx->up.tnow, B)); HB_HIP(dalloc(ctx, &ctx->up.t0, B)); HB_HIP(dalloc(ctx, &ctx->up.cmd, B * 4));
+    HB_HIP(dalloc(ctx, &up.quat, B * 4)); HB_HIP(dalloc(ctx, &up.w, B * 3)); HB_HIP(dalloc(ctx, &up.a, B * 3));
+    HB_HIP(dalloc(ctx, &up.qj, B * 10)); HB_HIP(dalloc(ctx, &up.qdj, B * 10)); HB_HIP(dalloc(ctx, &up.contact, B * 4));
+    HB_HIP(dalloc(ctx, &up.tnow, B)); HB_HIP(dalloc(ctx, &up.t0, B)); HB_HIP(dalloc(ctx, &up.cmd, B * 4));
   }
-  // fork from the library streams when another entry point ran since the last tick (or this is the first one)
-  const bool fork = ctx->fork_needed || ctx->grid_saved || ctx->chunks_pending != ctx->n_chunks;
-  if (fork) {
-    ++ctx->dbg_forks;
-    lazy_join(ctx);
-    int32_t rc = warm_start_onto_new_tables(ctx);
-    if (rc != HB_OK) return rc;
-    HB_HIP(hipEventRecord(ctx->ev_sync[2], ctx->s_mpc));
-    HB_HIP(hipEventRecord(ctx->ev_sync[3], ctx->s_wbc));
-  }
+  bool fork;
+  HB_TRY(fork_ranges(ctx, fork));
   // this tick's host inputs: one upload, after every range has read the previous tick's
-  {
-    hipStream_t su = ctx->s_up;
-    for (int c = 0; c < ctx->consumed_pending; ++c) HB_HIP(hipStreamWaitEvent(su, ctx->ev_consumed[c], 0));
-    int32_t rc;
-    if ((rc = stage_upload(ctx, ST_QUAT, ctx->up.quat, quat, B * 4 * 8, su)) != HB_OK) return rc;
-    if ((rc = stage_upload(ctx, ST_W, ctx->up.w, ang_vel_local, B * 3 * 8, su)) != HB_OK) return rc;
-    if ((rc = stage_upload(ctx, ST_A, ctx->up.a, lin_acc_local, B * 3 * 8, su)) != HB_OK) return rc;
-    if ((rc = stage_upload(ctx, ST_QJ, ctx->up.qj, joint_pos, B * 10 * 8, su)) != HB_OK) return rc;
-    if ((rc = stage_upload(ctx, ST_QDJ, ctx->up.qdj, joint_vel, B * 10 * 8, su)) != HB_OK) return rc;
-    if ((rc = stage_upload(ctx, ST_CONTACT, ctx->up.contact, contact_flag, B * 4 * sizeof(int), su)) != HB_OK) return rc;
-    if ((rc = stage_upload(ctx, ST_TNOW, ctx->up.tnow, t_now, B * 8, su)) != HB_OK) return rc;
-    if ((rc = stage_upload(ctx, ST_T0, ctx->up.t0, t_now, B * 8, su)) != HB_OK) return rc;
-    if ((rc = stage_upload(ctx, ST_CMD, ctx->up.cmd, cmd_vel, B * 4 * 8, su)) != HB_OK) return rc;
-    HB_HIP(hipEventRecord(ctx->ev_up, su));
-  }
+  hipStream_t su = ctx->s_up;
+  for (int c = 0; c < ctx->consumed_pending; ++c) HB_HIP(hipStreamWaitEvent(su, ctx->ev_consumed[c], 0));
+  const void* const dst[6] = {up.quat, up.w, up.a, up.qj, up.qdj, up.contact};
+  const void* const src[6] = {quat, ang_vel_local, lin_acc_local, joint_pos, joint_vel, contact_flag};
+  HB_TRY(upload_sensors(ctx, dst, src, true, su));
+  HB_TRY(stage_upload(ctx, ST_TNOW, up.tnow, t_now, B * 8, su));
+  HB_TRY(stage_upload(ctx, ST_T0, up.t0, t_now, B * 8, su));
+  HB_TRY(stage_upload(ctx, ST_CMD, up.cmd, cmd_vel, B * 4 * 8, su));
+  HB_HIP(hipEventRecord(ctx->ev_up, su));
   // the tables change for every instance: the previous iterate becomes the source of the warm start (as warm_start_onto_new_tables)
-  std::swap(ctx->b.x, ctx->b.xp);
-  std::swap(ctx->b.u, ctx->b.up);
-  ++ctx->graph_epoch;
-  const int per = (ctx->B + ctx->n_chunks - 1) / ctx->n_chunks;
-  int used = 0;
-  for (int c = 0; c < ctx->n_chunks; ++c) {
-    const int i0 = c * per, cnt = std::min(per, ctx->B - i0);
-    if (cnt <= 0) break;
-    hipStream_t s = ctx->s_chunk[c];
-    const size_t o = size_t(i0);
-    if (fork) {
-      HB_HIP(hipStreamWaitEvent(s, ctx->ev_sync[2], 0));
-      HB_HIP(hipStreamWaitEvent(s, ctx->ev_sync[3], 0));
-    }
+  swap_iterate(ctx);
+  // the estimator and the reference generation read this tick's uploads
+  EstBatch est = ctx->est;
+  est.quat = up.quat; est.w_local = up.w; est.a_local = up.a; est.qj = up.qj; est.qdj = up.qdj; est.contact = up.contact;
+  RefgenBatch rg = ctx->rg;
+  rg.t0 = up.t0;
+  rg.cmd = up.cmd;
+  HB_TRY(for_each_range(ctx, fork, [&](int c, int i0, int cnt, hipStream_t s) -> int32_t {
     HB_HIP(hipStreamWaitEvent(s, ctx->ev_up, 0));
     const Batch b = batch_view(ctx->b, i0, cnt);
     const WbcBatch w = wbc_view(ctx->w, ctx->Nmax, i0, cnt);
     // controller time + estimator -> resident rbd state and observation of the range
-    HB_HIP(hipMemcpyAsync(w.t_now, ctx->up.tnow + o, size_t(cnt) * 8, hipMemcpyDeviceToDevice, s));
-    EstBatch e = ctx->est;
-    e.B = cnt;
-    e.xhat += o * 18; e.P += o * 324; e.yaw_last += o; e.rbd += o * HB_NRBD; e.x += o * HB_NX;
-    e.quat = ctx->up.quat + o * 4; e.w_local = ctx->up.w + o * 3; e.a_local = ctx->up.a + o * 3;
-    e.qj = ctx->up.qj + o * 10; e.qdj = ctx->up.qdj + o * 10; e.contact = ctx->up.contact + o * 4;
+    HB_HIP(hipMemcpyAsync(w.t_now, up.tnow + i0, size_t(cnt) * 8, hipMemcpyDeviceToDevice, s));
+    EstBatch e = est_view(est, i0, cnt);
     e.res_rbd = w.rbd;
     e.res_x0 = b.x0;
-    hipLaunchKernelGGL(k_estimator, dim3(cnt), dim3(64), 0, s, e, ctx->dmodel, ctx->est_cfg, dt_est);
+    launch_estimator(ctx, e, dt_est, s);
     // reference generation at the new time (the grid that is about to be replaced is kept for the warm start)
-    HB_HIP(hipMemcpyAsync(b.tp, b.t, size_t(cnt) * (N + 1) * 8, hipMemcpyDeviceToDevice, s));
-    HB_HIP(hipMemcpyAsync(b.modep, b.mode, size_t(cnt) * N * sizeof(int), hipMemcpyDeviceToDevice, s));
-    HB_HIP(hipMemcpyAsync(b.np_nodes, b.n_nodes, size_t(cnt) * sizeof(int), hipMemcpyDeviceToDevice, s));
-    HB_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(b.grid_dirty), 1, size_t(cnt), s));
-    RefgenBatch r = ctx->rg;
-    r.B = cnt;
-    r.n_ev += o; r.ev += o * HB_MAX_EVENTS; r.modes += o * (HB_MAX_EVENTS + 1); r.stance += o * 12;
-    r.phases += o * 4 * (HB_MAX_EVENTS + 1) * RG_PHASE; r.status += o; r.n_knots += o; r.knot_t += o * RG_MAX_KNOTS;
-    r.knot_x += o * RG_MAX_KNOTS * HB_NX;
-    r.t0 = ctx->up.t0 + o;
-    r.cmd = ctx->up.cmd + o * 4;
-    hipLaunchKernelGGL(k_refgen, dim3((4 * cnt + 63) / 64), dim3(64), 0, s, b, r, ctx->dmodel, ctx->rg_cfg, horizon);
-    if (ctx->rg_cfg.joint_ik)
-      hipLaunchKernelGGL(k_refgen_ik, dim3((2 * cnt + 7) / 8), dim3(64), 0, s, b, r, ctx->dmodel, ctx->rg_cfg, horizon);
-    hipLaunchKernelGGL(k_refgen_nodes, dim3((cnt * ctx->Nmax + 63) / 64), dim3(64), 0, s, b, r, ctx->rg_cfg);
+    HB_TRY(launch_grid_save(ctx, b, true, 0, cnt, s));
+    launch_refgen(ctx, b, refgen_view(rg, i0, cnt), horizon, s);
     HB_HIP(hipEventRecord(ctx->ev_consumed[c], s));  // the upload buffers are free for the next tick
     // warm start onto the new tables, MPC iteration, publish, policy evaluation, WBC
-    hipLaunchKernelGGL(k_warm_shift, dim3(((ctx->Nmax + 1) * HB_NX + kWarmShiftThreads - 1) / kWarmShiftThreads, cnt), dim3(kWarmShiftThreads), 0, s, b, ctx->dmodel);
-    hipLaunchKernelGGL(k_grid_clean, dim3((cnt + 255) / 256), dim3(256), 0, s, b);
-    int32_t rc = mpc_iterations(ctx, i0, cnt, s);
-    if (rc != HB_OK) return rc;
-    rc = range_publish_policy_wbc(ctx, i0, cnt, s);
-    if (rc != HB_OK) return rc;
-    HB_HIP(hipGetLastError());
-    HB_HIP(hipEventRecord(ctx->ev_sync[4 + c], s));
-    used = c + 1;
-  }
+    launch_warm_start(ctx, b, s);
+    return enqueue_range_update(ctx, i0, cnt, s);
+  }));
   ctx->rg.init_stance = 0;
-  ctx->chunks_pending = used;
-  ctx->consumed_pending = used;
-  ctx->fork_needed = false;
-  ctx->steady_chunked_steps = 0;
-  {
-    std::lock_guard<std::mutex> lk(ctx->mtx);
-    ctx->w.policy_valid = true;
-    ctx->policy_read_pending = false;
-    ctx->stats.n_wbc_solves += ctx->B;
-    ctx->cert_last = ctx->wbc_cert;
-  }
+  ctx->consumed_pending = ctx->chunks_pending;
+  finish_ranges(ctx, false);
   return HB_OK;
 }
 
@@ -2739,9 +2755,8 @@ int32_t hb_debug_graph_state(hb_ctx* ctx, int64_t* out2) {
 
 int32_t hb_set_chunks(hb_ctx* ctx, int32_t n_chunks) {
   if (ctx) lazy_join(ctx);
-  if (!ctx || n_chunks < 1 || n_chunks > 8) return HB_ERR_ARG;
-  int32_t rc = hb_sync(ctx);
-  if (rc != HB_OK) return rc;
+  if (!ctx || n_chunks < 1 || n_chunks > kMaxRanges) return HB_ERR_ARG;
+  HB_TRY(hb_sync(ctx));
   ctx->n_chunks = n_chunks;
   ctx->graph_disabled = false;  // a new set of ranges gets a new chance to capture
   ++ctx->graph_epoch;
@@ -2768,8 +2783,7 @@ int32_t hb_wbc_set_certificate(hb_ctx* ctx, int32_t enable) {
   }
   if (bool(enable) == ctx->wbc_cert) return HB_OK;
   HB_HIP(hipSetDevice(ctx->device));
-  int32_t rc = hb_sync(ctx);
-  if (rc != HB_OK) return rc;
+  HB_TRY(hb_sync(ctx));
   if (enable && !ctx->cert_buf) {
     HB_HIP(dalloc(ctx, &ctx->cert_buf, size_t(ctx->B) * HB_WBC_CERT_SIZE));
     HB_HIP(dalloc(ctx, &ctx->dual_buf, size_t(ctx->B) * HB_WBC_NCONS_MAX));
@@ -2812,13 +2826,13 @@ int32_t hb_get_stats(hb_ctx* ctx, hb_stats* out) {
   HB_HIP(hipStreamSynchronize(ctx->s_wbc));
   float ms = 0;
   if (ctx->timed) {
-    if (hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]) == hipSuccess) ctx->stats.ms_lq = ms;
-    if (hipEventElapsedTime(&ms, ctx->ev[1], ctx->ev[2]) == hipSuccess) ctx->stats.ms_riccati_bwd = ms;
-    if (hipEventElapsedTime(&ms, ctx->ev[2], ctx->ev[3]) == hipSuccess) ctx->stats.ms_riccati_fwd = ms;
-    if (hipEventElapsedTime(&ms, ctx->ev[3], ctx->ev[4]) == hipSuccess) ctx->stats.ms_linesearch = ms;
-    if (hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[4]) == hipSuccess) ctx->stats.ms_mpc_total = ms;
+    if (hipEventElapsedTime(&ms, ctx->ev[EV_LQ_BEGIN], ctx->ev[EV_LQ_END]) == hipSuccess) ctx->stats.ms_lq = ms;
+    if (hipEventElapsedTime(&ms, ctx->ev[EV_LQ_END], ctx->ev[EV_RIC_BWD_END]) == hipSuccess) ctx->stats.ms_riccati_bwd = ms;
+    if (hipEventElapsedTime(&ms, ctx->ev[EV_RIC_BWD_END], ctx->ev[EV_RIC_FWD_END]) == hipSuccess) ctx->stats.ms_riccati_fwd = ms;
+    if (hipEventElapsedTime(&ms, ctx->ev[EV_RIC_FWD_END], ctx->ev[EV_LS_END]) == hipSuccess) ctx->stats.ms_linesearch = ms;
+    if (hipEventElapsedTime(&ms, ctx->ev[EV_LQ_BEGIN], ctx->ev[EV_LS_END]) == hipSuccess) ctx->stats.ms_mpc_total = ms;
   }
-  if (ctx->stats.n_wbc_solves > 0 && hipEventElapsedTime(&ms, ctx->ev[5], ctx->ev[6]) == hipSuccess) ctx->stats.ms_wbc = ms;
+  if (ctx->stats.n_wbc_solves > 0 && hipEventElapsedTime(&ms, ctx->ev[EV_WBC_BEGIN], ctx->ev[EV_WBC_END]) == hipSuccess) ctx->stats.ms_wbc = ms;
   if (ctx->stats.n_wbc_solves > 0) {
     std::vector<int> st(ctx->B);
     HB_HIP(hipMemcpy(st.data(), ctx->w.status, size_t(ctx->B) * sizeof(int), hipMemcpyDeviceToHost));
@@ -2835,25 +2849,21 @@ int32_t hb_eval_flow_map(hb_ctx* ctx, int32_t n, const double* x, const double* 
   if (ctx) lazy_join(ctx);
   if (!ctx || n <= 0 || !x || !u || !f) return HB_ERR_ARG;
   HB_HIP(hipSetDevice(ctx->device));
-  double *dx_, *du_, *df_, *dA = nullptr, *dB = nullptr;
-  HB_HIP(hipMalloc(&dx_, size_t(n) * HB_NX * 8));
-  HB_HIP(hipMalloc(&du_, size_t(n) * HB_NU * 8));
-  HB_HIP(hipMalloc(&df_, size_t(n) * HB_NX * 8));
-  HB_HIP(hipMemcpy(dx_, x, size_t(n) * HB_NX * 8, hipMemcpyHostToDevice));
-  HB_HIP(hipMemcpy(du_, u, size_t(n) * HB_NU * 8, hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(k_flow_map, dim3((n + 63) / 64), dim3(64), 0, ctx->s_mpc, n, ctx->dmodel, dx_, du_, df_, (double*)nullptr, (double*)nullptr);
+  const size_t m = n;
+  DevBuf<double> dx_, du_, df_, dA, dB;
+  HB_HIP(dx_.alloc(m * HB_NX, x));
+  HB_HIP(du_.alloc(m * HB_NU, u));
+  HB_HIP(df_.alloc(m * HB_NX));
+  hipLaunchKernelGGL(k_flow_map, dim3((n + 63) / 64), dim3(64), 0, ctx->s_mpc, n, ctx->dmodel, dx_.p, du_.p, df_.p, (double*)nullptr, (double*)nullptr);
   if (dfdx || dfdu) {
-    HB_HIP(hipMalloc(&dA, size_t(n) * 484 * 8));
-    HB_HIP(hipMalloc(&dB, size_t(n) * 484 * 8));
-    hipLaunchKernelGGL(k_flow_jac, dim3(n), dim3(64), 0, ctx->s_mpc, ctx->dmodel, dx_, du_, dA, dB);
+    HB_HIP(dA.alloc(m * 484));
+    HB_HIP(dB.alloc(m * 484));
+    hipLaunchKernelGGL(k_flow_jac, dim3(n), dim3(64), 0, ctx->s_mpc, ctx->dmodel, dx_.p, du_.p, dA.p, dB.p);
   }
   HB_HIP(hipStreamSynchronize(ctx->s_mpc));
-  HB_HIP(hipMemcpy(f, df_, size_t(n) * HB_NX * 8, hipMemcpyDeviceToHost));
-  if (dfdx) HB_HIP(hipMemcpy(dfdx, dA, size_t(n) * 484 * 8, hipMemcpyDeviceToHost));
-  if (dfdu) HB_HIP(hipMemcpy(dfdu, dB, size_t(n) * 484 * 8, hipMemcpyDeviceToHost));
-  (void)hipFree(dx_); (void)hipFree(du_); (void)hipFree(df_);
-  if (dA) (void)hipFree(dA);
-  if (dB) (void)hipFree(dB);
+  HB_HIP(hipMemcpy(f, df_.p, m * HB_NX * 8, hipMemcpyDeviceToHost));
+  if (dfdx) HB_HIP(hipMemcpy(dfdx, dA.p, m * 484 * 8, hipMemcpyDeviceToHost));
+  if (dfdu) HB_HIP(hipMemcpy(dfdu, dB.p, m * 484 * 8, hipMemcpyDeviceToHost));
   return HB_OK;
 }
 
@@ -2861,18 +2871,16 @@ int32_t hb_eval_foot_kinematics(hb_ctx* ctx, int32_t n, const double* x, const d
   if (ctx) lazy_join(ctx);
   if (!ctx || n <= 0 || !x || !u || !pos || !vel) return HB_ERR_ARG;
   HB_HIP(hipSetDevice(ctx->device));
-  double *dx_, *du_, *dp, *dv;
-  HB_HIP(hipMalloc(&dx_, size_t(n) * HB_NX * 8));
-  HB_HIP(hipMalloc(&du_, size_t(n) * HB_NU * 8));
-  HB_HIP(hipMalloc(&dp, size_t(n) * 12 * 8));
-  HB_HIP(hipMalloc(&dv, size_t(n) * 12 * 8));
-  HB_HIP(hipMemcpy(dx_, x, size_t(n) * HB_NX * 8, hipMemcpyHostToDevice));
-  HB_HIP(hipMemcpy(du_, u, size_t(n) * HB_NU * 8, hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(k_flow_map, dim3((n + 63) / 64), dim3(64), 0, ctx->s_mpc, n, ctx->dmodel, dx_, du_, (double*)nullptr, dp, dv);
+  const size_t m = n;
+  DevBuf<double> dx_, du_, dp, dv;
+  HB_HIP(dx_.alloc(m * HB_NX, x));
+  HB_HIP(du_.alloc(m * HB_NU, u));
+  HB_HIP(dp.alloc(m * 12));
+  HB_HIP(dv.alloc(m * 12));
+  hipLaunchKernelGGL(k_flow_map, dim3((n + 63) / 64), dim3(64), 0, ctx->s_mpc, n, ctx->dmodel, dx_.p, du_.p, (double*)nullptr, dp.p, dv.p);
   HB_HIP(hipStreamSynchronize(ctx->s_mpc));
-  HB_HIP(hipMemcpy(pos, dp, size_t(n) * 12 * 8, hipMemcpyDeviceToHost));
-  HB_HIP(hipMemcpy(vel, dv, size_t(n) * 12 * 8, hipMemcpyDeviceToHost));
-  (void)hipFree(dx_); (void)hipFree(du_); (void)hipFree(dp); (void)hipFree(dv);
+  HB_HIP(hipMemcpy(pos, dp.p, m * 12 * 8, hipMemcpyDeviceToHost));
+  HB_HIP(hipMemcpy(vel, dv.p, m * 12 * 8, hipMemcpyDeviceToHost));
   return HB_OK;
 }
 
@@ -2880,20 +2888,19 @@ int32_t hb_eval_rbd(hb_ctx* ctx, int32_t n, const double* rbd, double* Mo, doubl
   if (ctx) lazy_join(ctx);
   if (!ctx || n <= 0 || !rbd) return HB_ERR_ARG;
   HB_HIP(hipSetDevice(ctx->device));
-  double *dr, *dM, *dn, *dJ, *dd;
-  HB_HIP(hipMalloc(&dr, size_t(n) * HB_NRBD * 8));
-  HB_HIP(hipMalloc(&dM, size_t(n) * 256 * 8));
-  HB_HIP(hipMalloc(&dn, size_t(n) * 16 * 8));
-  HB_HIP(hipMalloc(&dJ, size_t(n) * 192 * 8));
-  HB_HIP(hipMalloc(&dd, size_t(n) * 12 * 8));
-  HB_HIP(hipMemcpy(dr, rbd, size_t(n) * HB_NRBD * 8, hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(k_rbd, dim3((n + 63) / 64), dim3(64), 0, ctx->s_wbc, n, ctx->dmodel, dr, dM, dn, dJ, dd);
+  const size_t m = n;
+  DevBuf<double> dr, dM, dn, dJ, dd;
+  HB_HIP(dr.alloc(m * HB_NRBD, rbd));
+  HB_HIP(dM.alloc(m * 256));
+  HB_HIP(dn.alloc(m * 16));
+  HB_HIP(dJ.alloc(m * 192));
+  HB_HIP(dd.alloc(m * 12));
+  hipLaunchKernelGGL(k_rbd, dim3((n + 63) / 64), dim3(64), 0, ctx->s_wbc, n, ctx->dmodel, dr.p, dM.p, dn.p, dJ.p, dd.p);
   HB_HIP(hipStreamSynchronize(ctx->s_wbc));
-  if (Mo) HB_HIP(hipMemcpy(Mo, dM, size_t(n) * 256 * 8, hipMemcpyDeviceToHost));
-  if (nle) HB_HIP(hipMemcpy(nle, dn, size_t(n) * 16 * 8, hipMemcpyDeviceToHost));
-  if (J) HB_HIP(hipMemcpy(J, dJ, size_t(n) * 192 * 8, hipMemcpyDeviceToHost));
-  if (dJv) HB_HIP(hipMemcpy(dJv, dd, size_t(n) * 12 * 8, hipMemcpyDeviceToHost));
-  (void)hipFree(dr); (void)hipFree(dM); (void)hipFree(dn); (void)hipFree(dJ); (void)hipFree(dd);
+  if (Mo) HB_HIP(hipMemcpy(Mo, dM.p, m * 256 * 8, hipMemcpyDeviceToHost));
+  if (nle) HB_HIP(hipMemcpy(nle, dn.p, m * 16 * 8, hipMemcpyDeviceToHost));
+  if (J) HB_HIP(hipMemcpy(J, dJ.p, m * 192 * 8, hipMemcpyDeviceToHost));
+  if (dJv) HB_HIP(hipMemcpy(dJv, dd.p, m * 12 * 8, hipMemcpyDeviceToHost));
   return HB_OK;
 }
 
@@ -2901,22 +2908,18 @@ int32_t hb_ik_solve(hb_ctx* ctx, int32_t n, const double* q16, const int32_t* le
   if (ctx) lazy_join(ctx);
   if (!ctx || n <= 0 || !q16 || !leg || !des_pos || !R_des || !out5) return HB_ERR_ARG;
   HB_HIP(hipSetDevice(ctx->device));
-  double *dq = nullptr, *dd = nullptr, *dR = nullptr, *dout = nullptr;
-  int* dl = nullptr;
-  HB_HIP(hipMalloc(&dq, size_t(n) * HB_NV * 8));
-  HB_HIP(hipMalloc(&dd, size_t(n) * 3 * 8));
-  HB_HIP(hipMalloc(&dR, size_t(n) * 9 * 8));
-  HB_HIP(hipMalloc(&dout, size_t(n) * 5 * 8));
-  HB_HIP(hipMalloc(&dl, size_t(n) * sizeof(int)));
-  HB_HIP(hipMemcpy(dq, q16, size_t(n) * HB_NV * 8, hipMemcpyHostToDevice));
-  HB_HIP(hipMemcpy(dd, des_pos, size_t(n) * 3 * 8, hipMemcpyHostToDevice));
-  HB_HIP(hipMemcpy(dR, R_des, size_t(n) * 9 * 8, hipMemcpyHostToDevice));
-  HB_HIP(hipMemcpy(dl, leg, size_t(n) * sizeof(int), hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(k_ik_solve, dim3((n + 7) / 8), dim3(64), 0, ctx->s_mpc, n, ctx->dmodel, dq, dl, dd, dR, dout);
+  const size_t m = n;
+  DevBuf<double> dq, dd, dR, dout;
+  DevBuf<int> dl;
+  HB_HIP(dq.alloc(m * HB_NV, q16));
+  HB_HIP(dd.alloc(m * 3, des_pos));
+  HB_HIP(dR.alloc(m * 9, R_des));
+  HB_HIP(dout.alloc(m * 5));
+  HB_HIP(dl.alloc(m, leg));
+  hipLaunchKernelGGL(k_ik_solve, dim3((n + 7) / 8), dim3(64), 0, ctx->s_mpc, n, ctx->dmodel, dq.p, dl.p, dd.p, dR.p, dout.p);
   HB_HIP(hipGetLastError());
   HB_HIP(hipStreamSynchronize(ctx->s_mpc));
-  HB_HIP(hipMemcpy(out5, dout, size_t(n) * 5 * 8, hipMemcpyDeviceToHost));
-  hipFree(dq); hipFree(dd); hipFree(dR); hipFree(dout); hipFree(dl);
+  HB_HIP(hipMemcpy(out5, dout.p, m * 5 * 8, hipMemcpyDeviceToHost));
   return HB_OK;
 }
 
@@ -2933,32 +2936,28 @@ int32_t hb_hoqp_solve(hb_ctx* ctx, int32_t n_problems, int32_t n_vars, int32_t n
     }
   HB_HIP(hipSetDevice(ctx->device));
   const size_t P = size_t(n_problems), nm = P * HQ_L * HQ_M * HQ_N, nv = P * HQ_L * HQ_M, nx = P * HQ_L * HQ_N;
-  double *dA = nullptr, *dD = nullptr, *db = nullptr, *df = nullptr, *dx = nullptr, *ds = nullptr;
-  int *dma = nullptr, *dmd = nullptr, *dst = nullptr;
-  hipError_t e = hipSuccess;
-  auto al = [&](void** p, size_t bytes) { if (e == hipSuccess) e = hipMalloc(p, bytes); };
-  al(reinterpret_cast<void**>(&dA), nm * 8); al(reinterpret_cast<void**>(&dD), nm * 8); al(reinterpret_cast<void**>(&db), nv * 8);
-  al(reinterpret_cast<void**>(&df), nv * 8); al(reinterpret_cast<void**>(&dx), nx * 8); al(reinterpret_cast<void**>(&ds), nv * 8);
-  al(reinterpret_cast<void**>(&dma), HQ_L * sizeof(int)); al(reinterpret_cast<void**>(&dmd), HQ_L * sizeof(int));
-  al(reinterpret_cast<void**>(&dst), P * sizeof(int));
-  auto cp = [&](void* d, const void* h, size_t bytes) { if (e == hipSuccess) e = hipMemcpy(d, h, bytes, hipMemcpyHostToDevice); };
-  cp(dA, A, nm * 8); cp(dD, D, nm * 8); cp(db, b, nv * 8); cp(df, f, nv * 8);
-  cp(dma, m_eq, size_t(n_levels) * sizeof(int)); cp(dmd, m_in, size_t(n_levels) * sizeof(int));
-  if (e == hipSuccess) e = hipMemset(dx, 0, nx * 8);
-  if (e == hipSuccess) e = hipMemset(ds, 0, nv * 8);
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL(k_hoqp_generic, dim3(n_problems), dim3(64), 0, ctx->s_wbc, n_vars, n_levels, dma, dmd, dA, db, dD, df, ctx->hconfig.wbc_eps,
-                       4 * ctx->hconfig.wbc_max_iter, dx, ds, dst, ctx->hconfig.wbc_reg_steps);
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess) e = hipStreamSynchronize(ctx->s_wbc);
-  if (e == hipSuccess) e = hipMemcpy(x, dx, nx * 8, hipMemcpyDeviceToHost);
-  if (e == hipSuccess) e = hipMemcpy(slack, ds, nv * 8, hipMemcpyDeviceToHost);
-  if (e == hipSuccess) e = hipMemcpy(status, dst, P * sizeof(int), hipMemcpyDeviceToHost);
-  for (void* p : {static_cast<void*>(dA), static_cast<void*>(dD), static_cast<void*>(db), static_cast<void*>(df), static_cast<void*>(dx),
-                  static_cast<void*>(ds), static_cast<void*>(dma), static_cast<void*>(dmd), static_cast<void*>(dst)})
-    if (p) (void)hipFree(p);
-  if (e != hipSuccess) { ctx->err = std::string("hb_hoqp_solve: ") + hipGetErrorString(e); return HB_ERR_DEVICE; }
+  DevBuf<double> dA, dD, db, df, dx, ds;
+  DevBuf<int> dma, dmd, dst;
+  HB_HIP(dA.alloc(nm, A));
+  HB_HIP(dD.alloc(nm, D));
+  HB_HIP(db.alloc(nv, b));
+  HB_HIP(df.alloc(nv, f));
+  HB_HIP(dx.alloc(nx));
+  HB_HIP(ds.alloc(nv));
+  HB_HIP(dma.alloc(HQ_L));
+  HB_HIP(dmd.alloc(HQ_L));
+  HB_HIP(dst.alloc(P));
+  HB_HIP(hipMemcpy(dma.p, m_eq, size_t(n_levels) * sizeof(int), hipMemcpyHostToDevice));
+  HB_HIP(hipMemcpy(dmd.p, m_in, size_t(n_levels) * sizeof(int), hipMemcpyHostToDevice));
+  HB_HIP(hipMemset(dx.p, 0, nx * 8));
+  HB_HIP(hipMemset(ds.p, 0, nv * 8));
+  hipLaunchKernelGGL(k_hoqp_generic, dim3(n_problems), dim3(64), 0, ctx->s_wbc, n_vars, n_levels, dma.p, dmd.p, dA.p, db.p, dD.p, df.p,
+                     ctx->hconfig.wbc_eps, 4 * ctx->hconfig.wbc_max_iter, dx.p, ds.p, dst.p, ctx->hconfig.wbc_reg_steps);
+  HB_HIP(hipGetLastError());
+  HB_HIP(hipStreamSynchronize(ctx->s_wbc));
+  HB_HIP(hipMemcpy(x, dx.p, nx * 8, hipMemcpyDeviceToHost));
+  HB_HIP(hipMemcpy(slack, ds.p, nv * 8, hipMemcpyDeviceToHost));
+  HB_HIP(hipMemcpy(status, dst.p, P * sizeof(int), hipMemcpyDeviceToHost));
   return HB_OK;
 }
 
@@ -2966,19 +2965,12 @@ int32_t hb_centroidal_state_from_rbd(hb_ctx* ctx, int32_t n, const double* rbd, 
   if (ctx) lazy_join(ctx);
   if (!ctx || !rbd || !x || n <= 0) return HB_ERR_ARG;
   HB_HIP(hipSetDevice(ctx->device));
-  double *drbd = nullptr, *dx = nullptr;
-  HB_HIP(hipMalloc(reinterpret_cast<void**>(&drbd), size_t(n) * HB_NRBD * 8));
-  hipError_t e = hipMalloc(reinterpret_cast<void**>(&dx), size_t(n) * HB_NX * 8);
-  if (e != hipSuccess) { (void)hipFree(drbd); ctx->err = "hb_centroidal_state_from_rbd: hipMalloc failed"; return HB_ERR_DEVICE; }
-  e = hipMemcpy(drbd, rbd, size_t(n) * HB_NRBD * 8, hipMemcpyHostToDevice);
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL(k_centroidal_state, dim3((n + 63) / 64), dim3(64), 0, ctx->s_wbc, n, ctx->dmodel, drbd, dx);
-    e = hipStreamSynchronize(ctx->s_wbc);
-  }
-  if (e == hipSuccess) e = hipMemcpy(x, dx, size_t(n) * HB_NX * 8, hipMemcpyDeviceToHost);
-  (void)hipFree(drbd);
-  (void)hipFree(dx);
-  if (e != hipSuccess) { ctx->err = std::string("hb_centroidal_state_from_rbd: ") + hipGetErrorString(e); return HB_ERR_DEVICE; }
+  DevBuf<double> drbd, dx;
+  HB_HIP(drbd.alloc(size_t(n) * HB_NRBD, rbd));
+  HB_HIP(dx.alloc(size_t(n) * HB_NX));
+  hipLaunchKernelGGL(k_centroidal_state, dim3((n + 63) / 64), dim3(64), 0, ctx->s_wbc, n, ctx->dmodel, drbd.p, dx.p);
+  HB_HIP(hipStreamSynchronize(ctx->s_wbc));
+  HB_HIP(hipMemcpy(x, dx.p, size_t(n) * HB_NX * 8, hipMemcpyDeviceToHost));
   return HB_OK;
 }
 

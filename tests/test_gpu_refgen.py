@@ -202,20 +202,25 @@ def test_enqueue_only_tick_equals_the_synchronous_calls(params):
     assert np.array_equal(wa[0], wb[0]) and np.array_equal(wa[1], wb[1]) and np.array_equal(ma, mb)
 
 
-def test_tick_resident_on_instance_ranges_equals_the_four_calls(params):
+@pytest.mark.parametrize("wbc", ["weighted", "hierarchical", "weighted_cert"])
+def test_tick_resident_on_instance_ranges_equals_the_four_calls(params, wbc):
     """hb_tick_resident with three instance ranges (every range runs its slice of time + estimator + references + warm start +
     MPC + WBC on its own stream, ranges up to a tick apart) against hb_set_resident_time / hb_estimator_update / hb_refgen_update /
     hb_step_resident on one stream: identical tables, iterate, WBC solution, filter state and status words after seven ticks with
-    changing sensors and commands; the caller's arrays are overwritten right after every call."""
+    changing sensors and commands; the caller's arrays are overwritten right after every call.  For each WBC kernel the ranges
+    launch: WeightedWbc, HierarchicalWbc (wbc_type = 1), and WeightedWbc with the KKT certificate, whose fields and dual solution
+    must match too."""
     from hunter_bipedal_control_amd.solver import HunterSolver
     B, N = 50, 40
     c = params["config"]
     horizon = N * c["dt"]
     rng = np.random.default_rng(12)
-    out = []
+    out, certs = [], []
     for ranges in (1, 3):
-        s = HunterSolver(params, batch=B, max_nodes=N + 6)
+        s = HunterSolver(params, batch=B, max_nodes=N + 6, wbc_type=1 if wbc == "hierarchical" else 0)
         try:
+            if wbc == "weighted_cert":
+                s.wbc_set_certificate(True)
             w = workload.device_trot_batch(s, params, n_intervals=N)
             s.set_resident_inputs(w["x0"], w["t_now"], w["rbd"])
             s.set_chunks(ranges)
@@ -244,6 +249,8 @@ def test_tick_resident_on_instance_ranges_equals_the_four_calls(params):
                     contact[...] = 0
             assert s.refgen_status().max() == 0
             out.append((s.get_references(), s.get_solution(), s.get_wbc_solution(), s.mpc_status(), s.estimator_filter()))
+            if wbc == "weighted_cert":
+                certs.append(s.wbc_certificate())
         finally:
             s.close()
     (ra, sa, wa, ma, ea), (rb, sb, wb, mb, eb) = out
@@ -251,3 +258,8 @@ def test_tick_resident_on_instance_ranges_equals_the_four_calls(params):
     assert np.array_equal(sa[0], sb[0]) and np.array_equal(sa[1], sb[1])
     assert np.array_equal(wa[0], wb[0]) and np.array_equal(wa[1], wb[1]) and np.array_equal(ma, mb)
     assert np.array_equal(ea[0], eb[0]) and np.array_equal(ea[1], eb[1])
+    if wbc == "weighted_cert":
+        ca, cb = certs
+        assert set(ca) == set(cb) == set(HunterSolver.WBC_CERT_FIELDS) | {"dual"}
+        for k in ca:
+            assert np.array_equal(ca[k], cb[k]), k
