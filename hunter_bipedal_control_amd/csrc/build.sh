@@ -4,14 +4,14 @@
 # s_waitcnt vmcnt(0), which drains the software-pipelined record prefetch of the sweeps.
 set -e
 cd "$(dirname "$0")"
-HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}
+. ./hipcc_flags.sh
 OUT=../libhunter_hip.so
 # --ablate: the profiling variant with the phase-by-phase exits compiled in (tools/perf_quick.py --lib variants/libhunter_hip_ablate.so --ablate-lq)
 # (the profiling variant may spill: its phase exits change the register allocation; scratch there is reported, not fatal)
 ABLATE=0
 if [ "$1" = "--ablate" ]; then shift; mkdir -p ../../variants; OUT=../../variants/libhunter_hip_ablate.so; ABLATE=1; set -- -DHB_ABLATE "$@"; fi
 LOG=$(mktemp)
-$HIPCC --offload-arch=gfx950 -O3 -std=c++17 -mllvm -disable-machine-licm -fPIC -shared -Rpass-analysis=kernel-resource-usage -o $OUT hb_kernels.hip "$@" 2> "$LOG" || { cat "$LOG" >&2; rm -f "$LOG"; exit 1; }
+$HIPCC $HB_HIPCC_FLAGS -shared -Rpass-analysis=kernel-resource-usage -o $OUT hb_kernels.hip "$@" 2> "$LOG" || { cat "$LOG" >&2; rm -f "$LOG"; exit 1; }
 grep -E "error|warning:" "$LOG" | grep -v "Wcomment" >&2 || true
 python3 - "$LOG" "$ABLATE" <<'PY'
 import re, sys

@@ -170,79 +170,10 @@ HB_HD int small_lsqp(const Ctx& cx, int n, int mA, const double* A, const double
   int* act = reinterpret_cast<int*>(g + 12);  // 12 ints
   int* is_act = act + 12;                     // mD <= 40 ints
   double* viol = g + 12 + 26;                 // 40: violation of the inactive constraints (host reduction only)
-  // R~ by Givens row insertion into sqrt(eps) I (stored in R), then J = R~^-1
-  const double se_tail = sqrt(eps), se_head = sqrt(eps + shift);
-#if defined(__HIP_DEVICE_COMPILE__)
-  // Device: n structured Householder reflectors on lane-owned columns (registers, wave-uniform broadcasts) instead of mA x n
-  // Givens rotations with two ordering points each — see the level-0 factorisation in hwbc_solve.
-  {
-    constexpr int MA = 24;  // level 1: 6 rows, level 2: 12 + 3 n_sw <= 24
-    const int j = cx.lane;
-    double acol[MA];
-    double gj = 0.0;
-#pragma unroll
-    for (int rr = 0; rr < MA; ++rr) {
-      acol[rr] = (j < n && rr < mA) ? A[rr * LD + j] : 0.0;
-      gj += acol[rr] * (rr < mA ? b[rr] : 0.0);
-    }
-    if (j < n) g[j] = gj;
-#pragma unroll 1
-    for (int k = 0; k < n; ++k) {
-      double dot = 0.0;
-      double ck[MA];
-#pragma unroll
-      for (int rr = 0; rr < MA; ++rr) {
-        ck[rr] = wave_bcast_f64(acol[rr], k);
-        dot += ck[rr] * acol[rr];
-      }
-      const double se = k < n_shift ? se_head : se_tail;
-      const double sig2 = se * se + wave_bcast_f64(dot, k);
-      const double alpha = -sqrt(sig2);
-      const double v0 = se - alpha;
-      const double beta = 2.0 * rcp_t(sig2 - se * se + v0 * v0);
-      const double w = beta * (dot + (j == k ? v0 * se : 0.0));
-      const bool live = j > k && j < n;
-#pragma unroll
-      for (int rr = 0; rr < MA; ++rr) acol[rr] = live ? acol[rr] - w * ck[rr] : (j == k ? 0.0 : acol[rr]);
-      if (j < LD) R[k * LD + j] = (j < k || j >= n) ? 0.0 : (j == k ? alpha : -w * v0);
-    }
-    cx.sync();
-  }
-  for (int rw = 0; rw < 0; ++rw) {
-#else
-  for (int idx = cx.lane; idx < n * LD; idx += cx.nlanes) R[idx] = (idx / LD == idx % LD) ? (idx / LD < n_shift ? se_head : se_tail) : 0.0;
-  for (int i = cx.lane; i < n; i += cx.nlanes) g[i] = 0.0;
-  cx.sync();
-  for (int rw = 0; rw < mA; ++rw) {
-#endif
-    for (int j = cx.lane; j < n; j += cx.nlanes) {
-      np[j] = A[rw * LD + j];
-      g[j] += A[rw * LD + j] * b[rw];
-    }
-    cx.sync();
-    for (int k = 0; k < n; ++k) {
-      const double a = R[k * LD + k], bb = np[k];
-      cx.sync();
-      if (bb != 0.0) {
-        const double rh = rsqrt_t(a * a + bb * bb), cc = a * rh, ss = bb * rh;
-        for (int j = k + cx.lane; j < n; j += cx.nlanes) {
-          const double t1 = R[k * LD + j], t2 = np[j];
-          R[k * LD + j] = cc * t1 + ss * t2;
-          np[j] = -ss * t1 + cc * t2;
-        }
-      }
-      cx.sync();
-    }
-  }
-  for (int col = cx.lane; col < n; col += cx.nlanes) {
-    for (int i = n - 1; i > col; --i) J[i * LD + col] = 0.0;
-    for (int i = col; i >= 0; --i) {
-      double s = (i == col) ? 1.0 : 0.0;
-      for (int k = i + 1; k <= col; ++k) s -= R[i * LD + k] * J[k * LD + col];
-      J[i * LD + col] = s * rcp_t(R[i * LD + i]);
-    }
-  }
-  cx.sync();
+  // R~, the factor of [diag(sqrt(eps + shift) | sqrt(eps)) ; A] (stored in R), g = A'b, then J = R~^-1
+  constexpr int MA = 24;  // level 1: 6 rows, level 2: 12 + 3 n_sw <= 24
+  regularised_factor<MA, true>(cx, n, mA, A, LD, b, g, HeadTailDiag{sqrt(eps + shift), sqrt(eps), n_shift}, R, LD, LD, np);
+  invert_upper(cx, R, LD, n, J);
   for (int k = cx.lane; k < n; k += cx.nlanes) {
     double s = 0.0;
     for (int i = 0; i < n; ++i) s += J[i * LD + k] * g[i];
@@ -386,36 +317,7 @@ HB_HD int small_lsqp(const Ctx& cx, int n, int mA, const double* A, const double
         break;
       }
       // partial / dual-only step: drop active constraint l
-      if (cx.lane == 0) is_act[act[l]] = 0;
-      cx.sync();
-      for (int j = l; j < q - 1; ++j) {
-        for (int i = cx.lane; i <= j + 1; i += cx.nlanes) R[i * LD + j] = R[i * LD + j + 1];
-        if (cx.lane == 0) { act[j] = act[j + 1]; lam[j] = lam[j + 1]; }
-        cx.sync();
-      }
-      for (int i = cx.lane; i < q; i += cx.nlanes) R[i * LD + q - 1] = 0.0;
-      --q;
-      cx.sync();
-      for (int j = l; j < q; ++j) {
-        const double a = R[j * LD + j], bb = R[(j + 1) * LD + j];
-        cx.sync();
-        if (bb != 0.0) {
-          const double rh = rsqrt_t(a * a + bb * bb), cc = a * rh, ss = bb * rh;
-          for (int k = cx.lane; k < n; k += cx.nlanes) {
-            if (k >= j && k < q) {
-              const double t1j = R[j * LD + k], t2j = R[(j + 1) * LD + k];
-              R[j * LD + k] = cc * t1j + ss * t2j;
-              R[(j + 1) * LD + k] = -ss * t1j + cc * t2j;
-            }
-            const double u1 = J[k * LD + j], u2 = J[k * LD + j + 1];
-            J[k * LD + j] = cc * u1 + ss * u2;
-            J[k * LD + j + 1] = -ss * u1 + cc * u2;
-          }
-        }
-        cx.sync();
-        if (cx.lane == 0) R[(j + 1) * LD + j] = 0.0;
-        cx.sync();
-      }
+      drop_constraint(cx, n, LD, R, J, act, lam, is_act, l, q);
     }
   }
 }
@@ -655,59 +557,31 @@ static_assert(HoLdsDev::LU + 28 * NW <= HoLdsDev::late_end && HoLdsDev::LU >= Ho
               "the LU work matrix of the level-0 kernel must not reach Z1 / Z2 / AZ (Z1 is its output)");
 static_assert(HoLdsDev::total * 8 <= 40960, "k_hwbc: 4 instances per CU");
 
-template <class Ctx>
-HB_HD void hwbc_solve(const Ctx& cx, const DevModel& M, const DevConfig& C, const double* xdes, const double* udes,
-                      const double* rbd, int mode, double* lds, double* sol, int* status_out, int max_level = 3) {
 #if defined(__HIP_DEVICE_COMPILE__)
-  using L = HoLdsDev;
+using HoL = HoLdsDev;
 #else
-  using L = HoLds;
+using HoL = HoLds;
 #endif
-  double* Jm = lds + L::J;
-  double* Rm = lds + L::R;
-  double* Tm = lds + L::T;
-  double* Q2 = lds + L::Q2;
-  double* Ee = lds + L::Ee;
-  double* Jc = lds + L::Jc;
-  double* dJv = lds + L::dJv;
-  double* Aw = lds + L::Aw;
-  double* bw = lds + L::bw;
-  double* beom = lds + L::beom;
-  double* x = lds + L::x;
-  double* g = lds + L::g;
-  double* z = lds + L::z;
-  double* np = lds + L::np;
-  double* v0 = lds + L::v0;
-  double* Z1 = lds + L::Z1;
-  double* Z2 = lds + L::Z2;
-  double* AZ = lds + L::AZ;
-  double* rhs = lds + L::rhs;
-  double* DZ = lds + L::DZ;
-  double* ft = lds + L::ft;
-  double* zs = lds + L::zs;
-  double* qpw = lds + L::qpw;
-  double* work = lds + L::work;
-  int* viol = reinterpret_cast<int*>(lds + L::ints);  // [40] current violated set, [40..] misc
-  int* imisc = viol + 48;
+// the LDS work area of the cascade as pointers (layout HoL)
+struct HwbcWork {
+  double *J, *R, *T, *Q2, *LU, *Ee, *Jc, *dJv, *Aw, *bw, *beom, *x, *g, *z, *np, *v0, *Z1, *Z2, *AZ, *rhs, *DZ, *ft, *zs, *qpw, *work;
+  double *xprev, *ls, *xc;
+  int *viol, *imisc;   // [40] current violated set of level 0, misc
+  HB_HD explicit HwbcWork(double* lds)
+      : J(lds + HoL::J), R(lds + HoL::R), T(lds + HoL::T), Q2(lds + HoL::Q2), LU(lds + HoL::LU), Ee(lds + HoL::Ee), Jc(lds + HoL::Jc),
+        dJv(lds + HoL::dJv), Aw(lds + HoL::Aw), bw(lds + HoL::bw), beom(lds + HoL::beom), x(lds + HoL::x), g(lds + HoL::g),
+        z(lds + HoL::z), np(lds + HoL::np), v0(lds + HoL::v0), Z1(lds + HoL::Z1), Z2(lds + HoL::Z2), AZ(lds + HoL::AZ),
+        rhs(lds + HoL::rhs), DZ(lds + HoL::DZ), ft(lds + HoL::ft), zs(lds + HoL::zs), qpw(lds + HoL::qpw), work(lds + HoL::work),
+        xprev(lds + HoL::xprev), ls(lds + HoL::ls), xc(lds + HoL::xc), viol(reinterpret_cast<int*>(lds + HoL::ints)), imisc(viol + 48) {}
+};
 
-  bool cf[HB_NC];
-  mode_flags(mode, cf);
+// The rows of the cascade: the dense equality-type task of level 0, A0 z = b0 (equation of motion, zero swing force, no contact
+// motion), and the sparse inequality rows (torque limits, friction pyramid) every level carries.
+struct HwbcRows {
   WbcCons wc;
-  wc.n_sw = 0;
-  wc.n_c = 0;
-  for (int i = 0; i < HB_NC; ++i) {
-    if (cf[i]) wc.add_contact(i);
-    else wc.add_swing(i);
-  }
-  wc.n_eq = 16 + 3 * wc.n_sw;
-  wc.n_in = 20 + 5 * wc.n_c;
-  const int mA0 = 16 + 3 * wc.n_sw + 3 * wc.n_c;  // always 28
-  wbc_phase_a(cx, M, C, xdes, udes, rbd, wc, false, 1.0, 1.0, Rm, Ee, beom, Aw, bw, Jc, dJv, Jm);
-  for (int c = cx.lane; c < 40; c += cx.nlanes) viol[c] = 0;
-  cx.sync();
-
-  // dense row r of the level-0 equality-type task and its right-hand side
-  auto a0_row = [&](int r, int col) -> double {
+  const double *Ee, *beom, *Jc, *dJv;
+  HB_HD int mA0() const { return 16 + 3 * wc.n_sw + 3 * wc.n_c; }  // always 28
+  HB_HD double a0(int r, int col) const {
     if (r < 16) return Ee[r * NW + col];
     if (r < 16 + 3 * wc.n_sw) {
       const int s = r - 16;
@@ -716,14 +590,15 @@ HB_HD void hwbc_solve(const Ctx& cx, const DevModel& M, const DevConfig& C, cons
     const int s = r - 16 - 3 * wc.n_sw;
     const int foot = wc.contact_foot(s / 3);
     return col < 16 ? Jc[(3 * foot + s % 3) * 16 + col] : 0.0;
-  };
-  auto a0_rhs = [&](int r) -> double {
+  }
+  HB_HD double b0(int r) const {
     if (r < 16) return beom[r];
     if (r < 16 + 3 * wc.n_sw) return 0.0;
     const int s = r - 16 - 3 * wc.n_sw;
     return -dJv[3 * wc.contact_foot(s / 3) + s % 3];
-  };
-  auto ineq_row = [&](int c, int col, double* rhs_out) -> double {
+  }
+  // coefficient of variable col in inequality row c; its right-hand side where asked for
+  HB_HD double ineq(const DevConfig& C, int c, int col, double* rhs_out) const {
     int idx[3];
     double cfv[3], rh;
     const int nn = sparse_row(wc, C, wc.n_eq + c, idx, cfv, &rh);
@@ -732,465 +607,474 @@ HB_HD void hwbc_solve(const Ctx& cx, const DevModel& M, const DevConfig& C, cons
     for (int t = 0; t < nn; ++t)
       if (idx[t] == col) vv = cfv[t];
     return vv;
-  };
+  }
+};
 
-  // ------------------------------------------------------------------ level 0
+// R^-1 R^-T v by two substitutions (no inverse).
+#if defined(__HIP_DEVICE_COMPILE__)
+// Lane j carries v_j, then y_j, and returns x_j; rinv: 1 / R_jj.
+__device__ __forceinline__ double hwbc_rtr_solve_lane(const double* Rm, double rinv, int j, double vj) {
+#pragma unroll 1
+  for (int k = 0; k < NW; ++k) {
+    const double yk = wave_bcast_f64(vj * rinv, k);
+    if (j == k) vj = yk;
+    if (j > k && j < NW) vj -= Rm[k * NW + j] * yk;
+  }
+#pragma unroll 1
+  for (int k = NW - 1; k >= 0; --k) {
+    const double xk = wave_bcast_f64(vj * rinv, k);
+    if (j == k) vj = xk;
+    if (j < k) vj -= Rm[j * NW + k] * xk;
+  }
+  return vj;
+}
+#else
+// Host twin: in place on v, one lane.
+template <class Ctx>
+HB_HD void hwbc_rtr_solve(const Ctx& cx, const double* Rm, double* v) {
+  for (int l0 = cx.lane; l0 < 1; l0 += cx.nlanes) {
+    for (int k = 0; k < NW; ++k) {
+      const double yk = v[k] / Rm[k * NW + k];
+      v[k] = yk;
+      for (int jj = k + 1; jj < NW; ++jj) v[jj] -= Rm[k * NW + jj] * yk;
+    }
+    for (int k = NW - 1; k >= 0; --k) {
+      const double xk = v[k] / Rm[k * NW + k];
+      v[k] = xk;
+      for (int jj = 0; jj < k; ++jj) v[jj] -= Rm[jj * NW + k] * xk;
+    }
+  }
+  cx.sync();
+}
+#endif
+
+// Level 0, first pass (no violated inequality rows yet — in normal operation the only pass): the triangular factor of
+// [sqrt(eps) I ; A0] by 38 structured Householder reflectors instead of 28 x 38 Givens rotations, and x = R^-1 R^-T A0'b0.
+// rinv (device): 1 / R_jj of that factor on lane j, for the regularisation steps that reuse it.
+template <class Ctx>
+HB_HD void hwbc_l0_first_pass(const Ctx& cx, const HwbcRows& rows, const HwbcWork& W, double se, double& rinv) {
+  constexpr int MA = 28;
+#if defined(__HIP_DEVICE_COMPILE__)
+  // lane j owns column j of A0 (28 registers)
+  const int j = cx.lane;
+  double acol[MA];
+  double gj = 0.0;
+#pragma unroll
+  for (int r = 0; r < MA; ++r) {
+    acol[r] = j < NW ? rows.a0(r, j) : 0.0;
+    gj += acol[r] * rows.b0(r);
+  }
+  const double diag = householder_factor<MA>(acol, j, NW, NW, UniformDiag(se), W.R, NW);
+  rinv = j < NW ? rcp_t(diag) : 0.0;
+  cx.sync();
+  gj = hwbc_rtr_solve_lane(W.R, rinv, j, gj);
+  if (j < NW) W.x[j] = gj;
+  cx.sync();
+#else
+  // Host twin: the same reflectors on a copy of A0 in the (not yet used) T buffer, one column per loop trip
+  double* Tm = W.T;
+  double* np = W.np;
+  for (int idx = cx.lane; idx < MA * NW; idx += cx.nlanes) Tm[idx] = rows.a0(idx / NW, idx % NW);
+  cx.sync();
+  for (int jj = cx.lane; jj < NW; jj += cx.nlanes) {
+    double sacc = 0.0;
+    for (int r = 0; r < MA; ++r) sacc += Tm[r * NW + jj] * rows.b0(r);
+    W.g[jj] = sacc;
+  }
+  cx.sync();
+  for (int k = 0; k < NW; ++k) {
+    for (int jj = cx.lane; jj < NW; jj += cx.nlanes) {
+      double dot = 0.0;
+      for (int r = 0; r < MA; ++r) dot += Tm[r * NW + k] * Tm[r * NW + jj];
+      np[jj] = dot;
+    }
+    cx.sync();
+    const double sig2 = se * se + np[k];
+    const double alpha = -sqrt(sig2);
+    const double v0 = se - alpha;
+    const double beta = 2.0 * rcp_t(sig2 - se * se + v0 * v0);
+    for (int jj = cx.lane; jj < NW; jj += cx.nlanes) {
+      const double w = beta * (np[jj] + (jj == k ? v0 * se : 0.0));
+      if (jj > k)
+        for (int r = 0; r < MA; ++r) Tm[r * NW + jj] -= w * Tm[r * NW + k];
+      W.R[k * NW + jj] = jj < k ? 0.0 : (jj == k ? alpha : -w * v0);
+    }
+    cx.sync();
+    for (int r = cx.lane; r < MA; r += cx.nlanes) Tm[r * NW + k] = 0.0;
+    cx.sync();
+  }
+  hwbc_rtr_solve(cx, W.R, W.g);
+  for (int k = cx.lane; k < NW; k += cx.nlanes) W.x[k] = W.g[k];
+  cx.sync();
+  (void)rinv;
+#endif
+}
+
+// Level 0, regularisation step while no inequality row has been violated: the first pass's factor serves,
+// x += eps R^-1 R^-T (x_k - x_{k-1}), the difference in np.
+template <class Ctx>
+HB_HD void hwbc_l0_reg_step(const Ctx& cx, const DevConfig& C, const HwbcWork& W, double rinv) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  const int j = cx.lane;
+  const double dj = hwbc_rtr_solve_lane(W.R, rinv, j, j < NW ? W.np[j] : 0.0);
+  if (j < NW) W.x[j] += C.wbc_eps * dj;
+#else
+  hwbc_rtr_solve(cx, W.R, W.np);
+  for (int k = cx.lane; k < NW; k += cx.nlanes) W.x[k] += C.wbc_eps * W.np[k];
+  (void)rinv;
+#endif
+  cx.sync();
+}
+
+// Level 0, pass with violated inequality rows: the minimiser of the quadratic piece of the current violated set,
+// by Givens insertion of A0's and the violated rows into sqrt(eps0) I.  xprev <- the point before.
+template <class Ctx>
+HB_HD void hwbc_l0_refactor(const Ctx& cx, const DevConfig& C, const HwbcRows& rows, const HwbcWork& W, double se) {
+  double* g = W.g;
+  for (int i = cx.lane; i < NW; i += cx.nlanes) W.xprev[i] = W.x[i];
+  for (int idx = cx.lane; idx < NW * NW; idx += cx.nlanes) W.R[idx] = (idx / NW == idx % NW) ? se : 0.0;
+  for (int i = cx.lane; i < NW; i += cx.nlanes) g[i] = C.wbc_eps * W.xc[i];   // the proximal term's share of the gradient (0 in phase 0)
+  cx.sync();
+  const int mA0 = rows.mA0(), n_rows = mA0 + rows.wc.n_in;
+  for (int rw = 0; rw < n_rows; ++rw) {
+    const bool is_a = rw < mA0;
+    if (!is_a && !W.viol[rw - mA0]) continue;
+    double rh = 0.0;
+    if (is_a) rh = rows.b0(rw);
+    else rows.ineq(C, rw - mA0, 0, &rh);
+    for (int i = cx.lane; i < NW; i += cx.nlanes) {
+      const double a = is_a ? rows.a0(rw, i) : rows.ineq(C, rw - mA0, i, nullptr);
+      W.np[i] = a;
+      g[i] += a * rh;
+    }
+    cx.sync();
+    givens_insert_row(cx, W.R, NW, NW, W.np);
+  }
+  invert_upper(cx, W.R, NW, NW, W.J);
+  for (int k = cx.lane; k < NW; k += cx.nlanes) {
+    double s = 0.0;
+    for (int i = 0; i < NW; ++i) s += W.J[i * NW + k] * g[i];
+    W.z[k] = s;
+  }
+  cx.sync();
+  for (int i = cx.lane; i < NW; i += cx.nlanes) {
+    double s = 0.0;
+    for (int k = 0; k < NW; ++k) s += W.J[i * NW + k] * W.z[k];
+    W.x[i] = s;
+  }
+  cx.sync();
+}
+
+// Level 0, after hwbc_l0_refactor: x is the minimiser of the quadratic piece of the previous point's violated set: a descent
+// direction d = x - xprev of phi from xprev, but the full step may overshoot into other pieces and the passes can cycle (joint rates
+// of several rad/s; with the small eps of the qpOASES rule the pieces are nearly flat in the ten directions no level-0 row sees, and
+// a plain or crudely damped iteration no longer settles).  EXACT line search instead: along d, phi'(t) = s1 + t s2 + sum_c (a_c + t b_c)_+ b_c
+// is piecewise linear and increasing (a = D xprev - f, b = D d; s1, s2 from the smooth part); one lane per breakpoint
+// t_c = -a_c / b_c evaluates phi' there, the root lies between the last negative and the first non-negative one, where phi'
+// is linear.  A semismooth Newton step with exact line search on a strictly convex piecewise quadratic terminates finitely.
+// Returns whether the full step was taken (if not, the point is not the minimiser of its piece: another pass follows whatever the
+// violated set does).
+template <class Ctx>
+HB_HD bool hwbc_l0_line_search(const Ctx& cx, const DevConfig& C, const HwbcRows& rows, const HwbcWork& W, double eps0) {
+  const WbcCons& wc = rows.wc;
+  const double* xprev = W.xprev;
+  double* x = W.x;
+  double* z = W.z;
+  double* la = W.ls;               // a_c, then phi'(t_c)
+  double* lb = la + 40;            // b_c
+  for (int i = cx.lane; i < NW; i += cx.nlanes) z[i] = x[i] - xprev[i];   // d
+  cx.sync();
+  const int mA0 = rows.mA0();
+  double p1 = 0.0, p2 = 0.0;
+  for (int rw = cx.lane; rw < mA0 + NW; rw += cx.nlanes) {
+    if (rw < mA0) {
+      double rr = -rows.b0(rw), ad = 0.0;
+      for (int i = 0; i < NW; ++i) { const double a = rows.a0(rw, i); rr += a * xprev[i]; ad += a * z[i]; }
+      p1 += rr * ad;
+      p2 += ad * ad;
+    } else {
+      const int i = rw - mA0;
+      p1 += (eps0 * xprev[i] - C.wbc_eps * W.xc[i]) * z[i];
+      p2 += eps0 * z[i] * z[i];
+    }
+  }
+  for (int c = cx.lane; c < wc.n_in; c += cx.nlanes) {
+    int idx[3];
+    double cfv[3], rh;
+    const int nn = sparse_row(wc, C, wc.n_eq + c, idx, cfv, &rh);
+    double a = -rh, bb = 0.0;
+    for (int t = 0; t < nn; ++t) { a += cfv[t] * xprev[idx[t]]; bb += cfv[t] * z[idx[t]]; }
+    la[c] = a;
+    lb[c] = bb;
+  }
+  W.work[cx.lane] = p1;
+  cx.sync();
+  double s1 = 0.0;
+  for (int l = 0; l < cx.nlanes; ++l) s1 += W.work[l];
+  cx.sync();
+  W.work[cx.lane] = p2;
+  cx.sync();
+  double s2 = 0.0;
+  for (int l = 0; l < cx.nlanes; ++l) s2 += W.work[l];
+  cx.sync();
+  auto dphi = [&](double t) -> double {
+    double v = s1 + t * s2;
+    for (int c = 0; c < wc.n_in; ++c) {
+      const double r = la[c] + t * lb[c];
+      v += r > 0.0 ? r * lb[c] : 0.0;
+    }
+    return v;
+  };
+  // bracket of the root among the breakpoints (every lane scans the <= 40 candidates its neighbours evaluated)
+  double* tc = W.g;                // g | z | np are contiguous (38 each): t_c in g[0..39], phi'(t_c) behind them (z is dead now)
+  double* dp = W.g + 40;
+  cx.sync();
+  for (int c = cx.lane; c < wc.n_in; c += cx.nlanes) {
+    const double t = lb[c] != 0.0 ? -la[c] / lb[c] : -1.0;
+    tc[c] = t;
+    dp[c] = t > 0.0 ? dphi(t) : 0.0;
+  }
+  cx.sync();
+  double t_lo = 0.0, t_hi = 1e300;
+  for (int c = 0; c < wc.n_in; ++c) {
+    const double t = tc[c];
+    if (!(t > 0.0)) continue;
+    if (dp[c] < 0.0) { if (t > t_lo) t_lo = t; }
+    else if (t < t_hi) t_hi = t;
+  }
+  const double p_lo = dphi(t_lo);
+  const double t_mid = t_hi < 1e300 ? 0.5 * (t_lo + t_hi) : t_lo + 1.0;
+  double slope = s2;
+  for (int c = 0; c < wc.n_in; ++c)
+    if (la[c] + t_mid * lb[c] > 0.0) slope += lb[c] * lb[c];
+  double t_star = (p_lo < 0.0 && slope > 0.0) ? t_lo - p_lo / slope : t_lo;
+  if (t_star > t_hi) t_star = t_hi;
+  cx.sync();
+  const bool full_step = !(fabs(t_star - 1.0) > 1e-9);
+  if (!full_step)
+    for (int i = cx.lane; i < NW; i += cx.nlanes) x[i] = xprev[i] + t_star * (x[i] - xprev[i]);
+  cx.sync();
+  return full_step;
+}
+
+// Level 0: violated set and slack v0 = (D x - f)_+ of the new point; returns whether the set changed.
+template <class Ctx>
+HB_HD bool hwbc_l0_violated_set(const Ctx& cx, const DevConfig& C, const HwbcRows& rows, const HwbcWork& W) {
+  if (cx.lane == 0) W.imisc[0] = 0;
+  cx.sync();
+  for (int c = cx.lane; c < rows.wc.n_in; c += cx.nlanes) {
+    double rh;
+    int idx[3];
+    double cfv[3];
+    const int nn = sparse_row(rows.wc, C, rows.wc.n_eq + c, idx, cfv, &rh);
+    double s = -rh;
+    for (int t = 0; t < nn; ++t) s += cfv[t] * W.x[idx[t]];
+    const int nv = (s > 1e-10 * fmax(1.0, fabs(rh))) ? 1 : 0;
+    W.v0[c] = s > 0.0 ? s : 0.0;
+    if (nv != W.viol[c]) { W.viol[c] = nv; W.imisc[0] = 1; }
+  }
+  cx.sync();
+  return W.imisc[0] != 0;
+}
+
+// Level 0: EoM + zero swing force + no contact motion with the inequalities slacked.  Returns the instance status.
+// phi(p) = 1/2 |A0 p - b0|^2 + 1/2 |(D p - f)_+|^2 + eps0/2 |p|^2 is the convex piecewise quadratic that level 0 minimises.
+// Phase 0 minimises phi; every further phase is one REGULARISATION STEP (see wbc_solve): the proximal problem around the point x_k
+// just found, phi(p) - eps x_k'p (up to a constant: the solver's eps/2 |p|^2 recentred on x_k), minimised by the same passes.
+// While no inequality row is violated the factor R of [sqrt(eps0) I; A0] of the first pass serves every phase:
+// x_{k+1} = x_k + eps R^-1 R^-T (x_k - x_{k-1}), x_{-1} = 0 — two more substitutions; the residual gradient is never formed.
+template <class Ctx>
+HB_HD int hwbc_level0(const Ctx& cx, const DevConfig& C, const HwbcRows& rows, const HwbcWork& W) {
   int status = 0;
   // level 0 has equality rows: its Hessian block is A0'A0 + 1e-12 I in the reference (HoQp.cpp:74-78), on top of the
   // regularised-minimiser rule's eps
   const double eps0 = C.wbc_eps + kHoqpHessianShift;
   const double se = sqrt(eps0);
-  // phi(p) = 1/2 |A0 p - b0|^2 + 1/2 |(D p - f)_+|^2 + eps0/2 |p|^2 is the convex piecewise quadratic that level 0 minimises.
-  // Phase 0 minimises phi; every further phase is one REGULARISATION STEP (see wbc_solve): the proximal problem around the point x_k
-  // just found, phi(p) - eps x_k'p (up to a constant: the solver's eps/2 |p|^2 recentred on x_k), minimised by the same passes.
-  // While no inequality row is violated the factor R of [sqrt(eps0) I; A0] of the first pass serves every phase:
-  // x_{k+1} = x_k + eps R^-1 R^-T (x_k - x_{k-1}), x_{-1} = 0 — two more substitutions; the residual gradient is never formed.
-  double* xprev = lds + L::xprev;
-  double* xc = lds + L::xc;
+  double* x = W.x;
+  double* xc = W.xc;
   for (int i = cx.lane; i < NW; i += cx.nlanes) xc[i] = 0.0;
   cx.sync();
   constexpr int kMaxPass = 30;
-  bool fast_ok = false;   // Rm holds the factor of [sqrt(eps0) I; A0] and no inequality row is violated
-#if defined(__HIP_DEVICE_COMPILE__)
-  double rinv = 0.0;      // 1 / R_jj of that factor (lane j)
-#endif
+  bool fast_ok = false;   // R holds the factor of [sqrt(eps0) I; A0] and no inequality row is violated
+  double rinv = 0.0;
   const int n_reg = C.wbc_reg_steps > 0 ? C.wbc_reg_steps : 0;   // (phase 0 — the solve with every constraint — runs whatever the field holds)
   for (int phase = 0; phase <= n_reg && status == 0; ++phase) {
-  if (phase > 0) {
-    for (int i = cx.lane; i < NW; i += cx.nlanes) { np[i] = x[i] - xc[i]; xc[i] = x[i]; }   // x_k - x_{k-1}; the new centre
-    cx.sync();
+    if (phase > 0) {
+      for (int i = cx.lane; i < NW; i += cx.nlanes) { W.np[i] = x[i] - xc[i]; xc[i] = x[i]; }   // x_k - x_{k-1}; the new centre
+      cx.sync();
+    }
+    for (int it = 0; it < kMaxPass; ++it) {
+      bool full_step = true;
+      if (it == 0 && phase == 0) {
+        fast_ok = true;
+        hwbc_l0_first_pass(cx, rows, W, se, rinv);
+      } else if (it == 0 && fast_ok) {
+        hwbc_l0_reg_step(cx, C, W, rinv);
+      } else {
+        fast_ok = false;
+        hwbc_l0_refactor(cx, C, rows, W, se);
+        full_step = hwbc_l0_line_search(cx, C, rows, W, eps0);
+      }
+      if (!hwbc_l0_violated_set(cx, C, rows, W) && full_step) break;
+      // A row that sits ON its bound at the minimiser ((D x - f) = 0 to rounding) flickers in and out of the violated set for ever
+      // while the point no longer moves — the pieces on both sides of the kink share the minimiser.  (Seen with the small eps of the
+      // qpOASES rule, where the rounding noise of x exceeds the 1e-10 of the set test.)  A full step that leaves the point where
+      // it was is convergence as well — and so is a line-searched step of length zero.
+      if (it > 0) {
+        for (int i = cx.lane; i < NW; i += cx.nlanes) { W.z[i] = fabs(x[i] - W.xprev[i]); W.g[i] = fabs(x[i]); }
+        cx.sync();
+        double dmax = 0.0, xmax = 1.0;
+        for (int i = 0; i < NW; ++i) { dmax = fmax(dmax, W.z[i]); xmax = fmax(xmax, W.g[i]); }
+        cx.sync();
+        if (dmax <= 1e-9 * xmax) break;
+      }
+      if (it == kMaxPass - 1) status = HB_INST_MAXITER;
+    }
   }
-  for (int it = 0; it < kMaxPass; ++it) {
-    bool full_step = true;
-    if (it == 0 && phase == 0) {
-      fast_ok = true;
-      // First pass (no violated inequality rows yet — in normal operation the only pass): the triangular factor of
-      // [sqrt(eps) I ; A0] by 38 structured Householder reflectors instead of 28 x 38 Givens rotations.  Reflector k has
-      // its support on row k of the identity block and on the 28 rows of A0, so row k of the factor is final after step k
-      // and the identity block never has to be stored.  x = R^-1 R^-T A0'b0 by two substitutions (no inverse).
-#if defined(__HIP_DEVICE_COMPILE__)
-      {
-        // lane j owns column j of A0 (28 registers); column k reaches the other lanes as wave-uniform values (v_readlane)
-        constexpr int MA = 28;
-        const int j = cx.lane;
-        double acol[MA];
-        double gj = 0.0;
-#pragma unroll
-        for (int r = 0; r < MA; ++r) {
-          acol[r] = j < NW ? a0_row(r, j) : 0.0;
-          gj += acol[r] * a0_rhs(r);
-        }
-#pragma unroll 1
-        for (int k = 0; k < NW; ++k) {
-          double dot = 0.0;
-          double ck[MA];
-#pragma unroll
-          for (int r = 0; r < MA; ++r) {
-            ck[r] = wave_bcast_f64(acol[r], k);
-            dot += ck[r] * acol[r];
-          }
-          const double sig2 = se * se + wave_bcast_f64(dot, k);
-          const double alpha = -sqrt(sig2);
-          const double v0 = se - alpha;
-          const double beta = 2.0 * rcp_t(sig2 - se * se + v0 * v0);
-          const double w = beta * (dot + (j == k ? v0 * se : 0.0));
-          const bool live = j > k && j < NW;
-#pragma unroll
-          for (int r = 0; r < MA; ++r) acol[r] = live ? acol[r] - w * ck[r] : (j == k ? 0.0 : acol[r]);
-          if (j < NW) Rm[k * NW + j] = j < k ? 0.0 : (j == k ? alpha : -w * v0);
-          if (j == k) rinv = rcp_t(alpha);
-        }
-        cx.sync();
-        // R'y = g (lane j carries g_j, then y_j), R x = y
-#pragma unroll 1
-        for (int k = 0; k < NW; ++k) {
-          const double yk = wave_bcast_f64(gj * rinv, k);
-          if (j == k) gj = yk;
-          if (j > k && j < NW) gj -= Rm[k * NW + j] * yk;
-        }
-#pragma unroll 1
-        for (int k = NW - 1; k >= 0; --k) {
-          const double xk = wave_bcast_f64(gj * rinv, k);
-          if (j == k) gj = xk;
-          if (j < k) gj -= Rm[j * NW + k] * xk;
-        }
-        if (j < NW) x[j] = gj;
-        cx.sync();
-      }
-#else
-      {
-        // same algorithm, A0 in the (not yet used) T buffer, one column per loop trip
-        constexpr int MA = 28;
-        for (int idx = cx.lane; idx < MA * NW; idx += cx.nlanes) Tm[idx] = a0_row(idx / NW, idx % NW);
-        cx.sync();
-        for (int jj = cx.lane; jj < NW; jj += cx.nlanes) {
-          double sacc = 0.0;
-          for (int r = 0; r < MA; ++r) sacc += Tm[r * NW + jj] * a0_rhs(r);
-          g[jj] = sacc;
-        }
-        cx.sync();
-        for (int k = 0; k < NW; ++k) {
-          for (int jj = cx.lane; jj < NW; jj += cx.nlanes) {
-            double dot = 0.0;
-            for (int r = 0; r < MA; ++r) dot += Tm[r * NW + k] * Tm[r * NW + jj];
-            np[jj] = dot;
-          }
-          cx.sync();
-          const double sig2 = se * se + np[k];
-          const double alpha = -sqrt(sig2);
-          const double v0 = se - alpha;
-          const double beta = 2.0 * rcp_t(sig2 - se * se + v0 * v0);
-          for (int jj = cx.lane; jj < NW; jj += cx.nlanes) {
-            const double w = beta * (np[jj] + (jj == k ? v0 * se : 0.0));
-            if (jj > k)
-              for (int r = 0; r < MA; ++r) Tm[r * NW + jj] -= w * Tm[r * NW + k];
-            Rm[k * NW + jj] = jj < k ? 0.0 : (jj == k ? alpha : -w * v0);
-          }
-          cx.sync();
-          for (int r = cx.lane; r < MA; r += cx.nlanes) Tm[r * NW + k] = 0.0;
-          cx.sync();
-        }
-        for (int l0 = cx.lane; l0 < 1; l0 += cx.nlanes) {
-          for (int k = 0; k < NW; ++k) {
-            const double yk = g[k] / Rm[k * NW + k];
-            g[k] = yk;
-            for (int jj = k + 1; jj < NW; ++jj) g[jj] -= Rm[k * NW + jj] * yk;
-          }
-          for (int k = NW - 1; k >= 0; --k) {
-            const double xk = g[k] / Rm[k * NW + k];
-            g[k] = xk;
-            for (int jj = 0; jj < k; ++jj) g[jj] -= Rm[jj * NW + k] * xk;
-          }
-          for (int k = 0; k < NW; ++k) x[k] = g[k];
-        }
-        cx.sync();
-      }
-#endif
-    } else if (it == 0 && fast_ok) {
-      // regularisation step on the first pass's factor (no violated row so far): x += eps R^-1 R^-T (x_k - x_{k-1}), the difference in np
-#if defined(__HIP_DEVICE_COMPILE__)
-      {
-        const int j = cx.lane;
-        double dj = j < NW ? np[j] : 0.0;
-#pragma unroll 1
-        for (int k = 0; k < NW; ++k) {
-          const double yk = wave_bcast_f64(dj * rinv, k);
-          if (j == k) dj = yk;
-          if (j > k && j < NW) dj -= Rm[k * NW + j] * yk;
-        }
-#pragma unroll 1
-        for (int k = NW - 1; k >= 0; --k) {
-          const double xk = wave_bcast_f64(dj * rinv, k);
-          if (j == k) dj = xk;
-          if (j < k) dj -= Rm[j * NW + k] * xk;
-        }
-        if (j < NW) x[j] += C.wbc_eps * dj;
-        cx.sync();
-      }
-#else
-      for (int l0 = cx.lane; l0 < 1; l0 += cx.nlanes) {
-        for (int k = 0; k < NW; ++k) {
-          const double yk = np[k] / Rm[k * NW + k];
-          np[k] = yk;
-          for (int jj = k + 1; jj < NW; ++jj) np[jj] -= Rm[k * NW + jj] * yk;
-        }
-        for (int k = NW - 1; k >= 0; --k) {
-          const double xk = np[k] / Rm[k * NW + k];
-          np[k] = xk;
-          for (int jj = 0; jj < k; ++jj) np[jj] -= Rm[jj * NW + k] * xk;
-        }
-        for (int k = 0; k < NW; ++k) x[k] += C.wbc_eps * np[k];
-      }
-      cx.sync();
-#endif
-    } else {
-    fast_ok = false;
-    for (int i = cx.lane; i < NW; i += cx.nlanes) xprev[i] = x[i];
-    for (int idx = cx.lane; idx < NW * NW; idx += cx.nlanes) Rm[idx] = (idx / NW == idx % NW) ? se : 0.0;
-    for (int i = cx.lane; i < NW; i += cx.nlanes) g[i] = C.wbc_eps * xc[i];   // the proximal term's share of the gradient (0 in phase 0)
-    cx.sync();
-    const int n_rows = mA0 + wc.n_in;
-    for (int rw = 0; rw < n_rows; ++rw) {
-      const bool is_a = rw < mA0;
-      if (!is_a && !viol[rw - mA0]) continue;
-      double rh = 0.0;
-      if (is_a) rh = a0_rhs(rw);
-      else ineq_row(rw - mA0, 0, &rh);
-      for (int i = cx.lane; i < NW; i += cx.nlanes) {
-        const double a = is_a ? a0_row(rw, i) : ineq_row(rw - mA0, i, nullptr);
-        np[i] = a;
-        g[i] += a * rh;
-      }
-      cx.sync();
-      for (int k = 0; k < NW; ++k) {
-        const double a = Rm[k * NW + k], b = np[k];
-        cx.sync();
-        if (b != 0.0) {
-          const double rh2 = rsqrt_t(a * a + b * b), cc = a * rh2, ss = b * rh2;
-          for (int j = k + cx.lane; j < NW; j += cx.nlanes) {
-            const double t1 = Rm[k * NW + j], t2 = np[j];
-            Rm[k * NW + j] = cc * t1 + ss * t2;
-            np[j] = -ss * t1 + cc * t2;
-          }
-        }
-        cx.sync();
-      }
-    }
-    for (int col = cx.lane; col < NW; col += cx.nlanes) {
-      for (int i = NW - 1; i > col; --i) Jm[i * NW + col] = 0.0;
-      for (int i = col; i >= 0; --i) {
-        double s = (i == col) ? 1.0 : 0.0;
-        for (int k = i + 1; k <= col; ++k) s -= Rm[i * NW + k] * Jm[k * NW + col];
-        Jm[i * NW + col] = s * rcp_t(Rm[i * NW + i]);
-      }
-    }
-    cx.sync();
-    for (int k = cx.lane; k < NW; k += cx.nlanes) {
-      double s = 0.0;
-      for (int i = 0; i < NW; ++i) s += Jm[i * NW + k] * g[i];
-      z[k] = s;
-    }
-    cx.sync();
-    for (int i = cx.lane; i < NW; i += cx.nlanes) {
-      double s = 0.0;
-      for (int k = 0; k < NW; ++k) s += Jm[i * NW + k] * z[k];
-      x[i] = s;
-    }
-    cx.sync();
-    // x is the minimiser of the quadratic piece of the previous point's violated set: a descent direction d = x - xprev of phi
-    // from xprev, but the full step may overshoot into other pieces and the passes can cycle (joint rates of several rad/s; with
-    // the small eps of the qpOASES rule the pieces are nearly flat in the ten directions no level-0 row sees, and a plain or
-    // crudely damped iteration no longer settles).  EXACT line search instead: along d, phi'(t) = s1 + t s2 + sum_c (a_c + t b_c)_+ b_c
-    // is piecewise linear and increasing (a = D xprev - f, b = D d; s1, s2 from the smooth part); one lane per breakpoint
-    // t_c = -a_c / b_c evaluates phi' there, the root lies between the last negative and the first non-negative one, where phi'
-    // is linear.  A semismooth Newton step with exact line search on a strictly convex piecewise quadratic terminates finitely.
-    {
-      double* la = lds + L::ls;        // a_c, then phi'(t_c)
-      double* lb = la + 40;            // b_c
-      for (int i = cx.lane; i < NW; i += cx.nlanes) z[i] = x[i] - xprev[i];   // d
-      cx.sync();
-      double p1 = 0.0, p2 = 0.0;
-      for (int rw = cx.lane; rw < mA0 + NW; rw += cx.nlanes) {
-        if (rw < mA0) {
-          double rr = -a0_rhs(rw), ad = 0.0;
-          for (int i = 0; i < NW; ++i) { const double a = a0_row(rw, i); rr += a * xprev[i]; ad += a * z[i]; }
-          p1 += rr * ad;
-          p2 += ad * ad;
-        } else {
-          const int i = rw - mA0;
-          p1 += (eps0 * xprev[i] - C.wbc_eps * xc[i]) * z[i];
-          p2 += eps0 * z[i] * z[i];
-        }
-      }
-      for (int c = cx.lane; c < wc.n_in; c += cx.nlanes) {
-        int idx[3];
-        double cfv[3], rh;
-        const int nn = sparse_row(wc, C, wc.n_eq + c, idx, cfv, &rh);
-        double a = -rh, bb = 0.0;
-        for (int t = 0; t < nn; ++t) { a += cfv[t] * xprev[idx[t]]; bb += cfv[t] * z[idx[t]]; }
-        la[c] = a;
-        lb[c] = bb;
-      }
-      work[cx.lane] = p1;
-      cx.sync();
-      double s1 = 0.0;
-      for (int l = 0; l < cx.nlanes; ++l) s1 += work[l];
-      cx.sync();
-      work[cx.lane] = p2;
-      cx.sync();
-      double s2 = 0.0;
-      for (int l = 0; l < cx.nlanes; ++l) s2 += work[l];
-      cx.sync();
-      auto dphi = [&](double t) -> double {
-        double v = s1 + t * s2;
-        for (int c = 0; c < wc.n_in; ++c) {
-          const double r = la[c] + t * lb[c];
-          v += r > 0.0 ? r * lb[c] : 0.0;
-        }
-        return v;
-      };
-      // bracket of the root among the breakpoints (every lane scans the <= 40 candidates its neighbours evaluated)
-      double* tc = g;                  // g | z | np are contiguous (38 each): t_c in g[0..39], phi'(t_c) behind them (z is dead now)
-      double* dp = g + 40;
-      cx.sync();
-      for (int c = cx.lane; c < wc.n_in; c += cx.nlanes) {
-        const double t = lb[c] != 0.0 ? -la[c] / lb[c] : -1.0;
-        tc[c] = t;
-        dp[c] = t > 0.0 ? dphi(t) : 0.0;
-      }
-      cx.sync();
-      double t_lo = 0.0, t_hi = 1e300;
-      for (int c = 0; c < wc.n_in; ++c) {
-        const double t = tc[c];
-        if (!(t > 0.0)) continue;
-        if (dp[c] < 0.0) { if (t > t_lo) t_lo = t; }
-        else if (t < t_hi) t_hi = t;
-      }
-      const double p_lo = dphi(t_lo);
-      const double t_mid = t_hi < 1e300 ? 0.5 * (t_lo + t_hi) : t_lo + 1.0;
-      double slope = s2;
-      for (int c = 0; c < wc.n_in; ++c)
-        if (la[c] + t_mid * lb[c] > 0.0) slope += lb[c] * lb[c];
-      double t_star = (p_lo < 0.0 && slope > 0.0) ? t_lo - p_lo / slope : t_lo;
-      if (t_star > t_hi) t_star = t_hi;
-      cx.sync();
-      if (fabs(t_star - 1.0) > 1e-9) {
-        full_step = false;  // (the point is then not the minimiser of its piece: another pass follows whatever the set does)
-        for (int i = cx.lane; i < NW; i += cx.nlanes) x[i] = xprev[i] + t_star * (x[i] - xprev[i]);
-      }
-      cx.sync();
-    }
-    }
-    // violated set of the new point
-    if (cx.lane == 0) imisc[0] = 0;
-    cx.sync();
-    for (int c = cx.lane; c < wc.n_in; c += cx.nlanes) {
-      double rh;
-      int idx[3];
-      double cfv[3];
-      const int nn = sparse_row(wc, C, wc.n_eq + c, idx, cfv, &rh);
-      double s = -rh;
-      for (int t = 0; t < nn; ++t) s += cfv[t] * x[idx[t]];
-      const int nv = (s > 1e-10 * fmax(1.0, fabs(rh))) ? 1 : 0;
-      v0[c] = s > 0.0 ? s : 0.0;
-      if (nv != viol[c]) { viol[c] = nv; imisc[0] = 1; }
-    }
-    cx.sync();
-    if (!imisc[0] && full_step) break;
-    // A row that sits ON its bound at the minimiser ((D x - f) = 0 to rounding) flickers in and out of the violated set for ever
-    // while the point no longer moves — the pieces on both sides of the kink share the minimiser.  (Seen with the small eps of the
-    // qpOASES rule, where the rounding noise of x exceeds the 1e-10 of the set test.)  A full step that leaves the point where
-    // it was is convergence as well — and so is a line-searched step of length zero.
-    if (it > 0) {
-      for (int i = cx.lane; i < NW; i += cx.nlanes) { z[i] = fabs(x[i] - xprev[i]); g[i] = fabs(x[i]); }
-      cx.sync();
-      double dmax = 0.0, xmax = 1.0;
-      for (int i = 0; i < NW; ++i) { dmax = fmax(dmax, z[i]); xmax = fmax(xmax, g[i]); }
-      cx.sync();
-      if (dmax <= 1e-9 * xmax) break;
-    }
-    if (it == kMaxPass - 1) status = HB_INST_MAXITER;
-  }
-  }  // phase
-  if (max_level <= 1) {
-    for (int i = cx.lane; i < NW; i += cx.nlanes) sol[i] = x[i];
-    if (cx.lane == 0) *status_out = status;
-    return;
-  }
-  // ------------------------------------------------------------------ kernel of the level-0 task: Z1 = kernel(A0)
-  // Eigen's FullPivLU::kernel() of the 28 x 38 task matrix (HoQp.cpp:162), one column per lane; the work matrix lies over buffers
-  // that are written only after Z1 exists (device layout).  rank(A0) = 26 (double support: two rigid feet, rank 5 each) .. 28,
-  // so the basis has 10 .. 12 columns; a stance leg in a kinematic singularity would leave more — the solve is then given up
-  // (previous solution kept, WeightedWbc.cpp:57-65 semantics) instead of overrunning the 12-column buffers.
-  double* LU = lds + L::LU;
-  for (int idx = cx.lane; idx < 28 * NW; idx += cx.nlanes) LU[idx] = a0_row(idx / NW, idx % NW);
-  for (int idx = cx.lane; idx < NW * 12; idx += cx.nlanes) Z1[idx] = 0.0;
-  cx.sync();
-  const int n1 = fullpivlu_kernel(cx, LU, mA0, NW, NW, Z1, 12, 12, work);  // 10..12
-  if (n1 < 0) {
-    if (cx.lane == 0) *status_out = HB_INST_MAXITER;
-    return;
-  }
-  HB_ABLATE_STOP(C.debug_stop == 43);  // profiling ablation: level 0 + kernel basis
-  // ------------------------------------------------------------------ level 1: base acceleration
-  const double* A1 = Aw + 3 * wc.n_sw * 16;
-  const double* b1 = bw + 3 * wc.n_sw;
-  for (int idx = cx.lane; idx < 6 * 12; idx += cx.nlanes) {
-    const int i = idx / 12, j = idx % 12;
-    double s = 0.0;
-    for (int c = 0; c < 16; ++c) s += A1[i * 16 + c] * Z1[c * 12 + j];
-    AZ[idx] = s;
-  }
-  for (int i = cx.lane; i < 6; i += cx.nlanes) {
-    double s = b1[i];
-    for (int c = 0; c < 16; ++c) s -= A1[i * 16 + c] * x[c];
-    rhs[i] = s;
-  }
-  for (int idx = cx.lane; idx < wc.n_in * 12; idx += cx.nlanes) {
+  return status;
+}
+
+// Inequality rows of a later level in the coordinates of its basis Z (38 x nz, ld 12): D Z z <= f - D x + v0.
+template <class Ctx>
+HB_HD void hwbc_project_inequalities(const Ctx& cx, const DevConfig& C, const HwbcRows& rows, const HwbcWork& W, const double* Z) {
+  for (int idx = cx.lane; idx < rows.wc.n_in * 12; idx += cx.nlanes) {
     const int c = idx / 12, j = idx % 12;
     int ix[3];
     double cfv[3], rh;
-    const int nn = sparse_row(wc, C, wc.n_eq + c, ix, cfv, &rh);
+    const int nn = sparse_row(rows.wc, C, rows.wc.n_eq + c, ix, cfv, &rh);
     double s = 0.0, dx = 0.0;
-    for (int t = 0; t < nn; ++t) { s += cfv[t] * Z1[ix[t] * 12 + j]; dx += cfv[t] * x[ix[t]]; }
-    DZ[idx] = s;
-    if (j == 0) ft[c] = fmax(0.0, rh - dx + v0[c]);   // (z = 0 is feasible by construction: see hoqp_generic)
+    for (int t = 0; t < nn; ++t) { s += cfv[t] * Z[ix[t] * 12 + j]; dx += cfv[t] * W.x[ix[t]]; }
+    W.DZ[idx] = s;
+    if (j == 0) W.ft[c] = fmax(0.0, rh - dx + W.v0[c]);   // (z = 0 is feasible by construction: see hoqp_generic)
   }
   cx.sync();
-  {
-    const int rc1 = small_lsqp(cx, n1, 6, AZ, rhs, C.wbc_eps, wc.n_in, DZ, ft, 4 * C.wbc_max_iter, zs, qpw, n1, kHoqpHessianShift, C.wbc_reg_steps);
-    cx.sync();
-    if (rc1 > status) status = rc1;
-  }
+}
+
+// The level QP on (AZ, rhs, DZ, ft) over nz coordinates, then x += Z zs.  Returns the QP's code.
+template <class Ctx>
+HB_HD int hwbc_level_qp(const Ctx& cx, const DevConfig& C, const HwbcRows& rows, const HwbcWork& W, const double* Z, int nz, int m) {
+  const int rc = small_lsqp(cx, nz, m, W.AZ, W.rhs, C.wbc_eps, rows.wc.n_in, W.DZ, W.ft, 4 * C.wbc_max_iter, W.zs, W.qpw, nz, kHoqpHessianShift,
+                            C.wbc_reg_steps);
+  cx.sync();
   for (int i = cx.lane; i < NW; i += cx.nlanes) {
-    double s = x[i];
-    for (int j = 0; j < n1; ++j) s += Z1[i * 12 + j] * zs[j];
-    g[i] = s;  // x2
+    double s = W.x[i];
+    for (int j = 0; j < nz; ++j) s += Z[i * 12 + j] * W.zs[j];
+    W.g[i] = s;
   }
   cx.sync();
-  for (int i = cx.lane; i < NW; i += cx.nlanes) x[i] = g[i];
-  HB_ABLATE_STOP(C.debug_stop == 44);  // profiling ablation: ... + level-1 QP
-  // kernel of A1 Z1 (6 x n1), again as the reference takes it; Z2 = Z1 kernel(A1 Z1)
-  for (int idx = cx.lane; idx < 6 * n1; idx += cx.nlanes) Tm[idx] = AZ[(idx / n1) * 12 + idx % n1];
-  for (int idx = cx.lane; idx < 144; idx += cx.nlanes) Q2[idx] = 0.0;
+  for (int i = cx.lane; i < NW; i += cx.nlanes) W.x[i] = W.g[i];
+  return rc;
+}
+
+// Z1 = kernel(A0): Eigen's FullPivLU::kernel() of the 28 x 38 task matrix (HoQp.cpp:162), one column per lane; the work matrix lies
+// over buffers that are written only after Z1 exists (device layout).  rank(A0) = 26 (double support: two rigid feet, rank 5 each)
+// .. 28, so the basis has 10 .. 12 columns; a stance leg in a kinematic singularity would leave more — the solve is then given up
+// (previous solution kept, WeightedWbc.cpp:57-65 semantics) instead of overrunning the 12-column buffers.  Returns the number of
+// columns, or -1.
+template <class Ctx>
+HB_HD int hwbc_level0_kernel(const Ctx& cx, const HwbcRows& rows, const HwbcWork& W) {
+  for (int idx = cx.lane; idx < 28 * NW; idx += cx.nlanes) W.LU[idx] = rows.a0(idx / NW, idx % NW);
+  for (int idx = cx.lane; idx < NW * 12; idx += cx.nlanes) W.Z1[idx] = 0.0;
   cx.sync();
-  const int n2 = fullpivlu_kernel(cx, Tm, 6, n1, n1, Q2, 12, 12, work);
-  if (n2 < 0) {
-    if (cx.lane == 0) *status_out = HB_INST_MAXITER;
-    return;
+  return fullpivlu_kernel(cx, W.LU, rows.mA0(), NW, NW, W.Z1, 12, 12, W.work);  // 10..12
+}
+
+// Level 1: base acceleration, over x + Z1 z.
+template <class Ctx>
+HB_HD int hwbc_level1(const Ctx& cx, const DevConfig& C, const HwbcRows& rows, const HwbcWork& W, int n1) {
+  const double* A1 = W.Aw + 3 * rows.wc.n_sw * 16;
+  const double* b1 = W.bw + 3 * rows.wc.n_sw;
+  for (int idx = cx.lane; idx < 6 * 12; idx += cx.nlanes) {
+    const int i = idx / 12, j = idx % 12;
+    double s = 0.0;
+    for (int c = 0; c < 16; ++c) s += A1[i * 16 + c] * W.Z1[c * 12 + j];
+    W.AZ[idx] = s;
   }
+  for (int i = cx.lane; i < 6; i += cx.nlanes) {
+    double s = b1[i];
+    for (int c = 0; c < 16; ++c) s -= A1[i * 16 + c] * W.x[c];
+    W.rhs[i] = s;
+  }
+  hwbc_project_inequalities(cx, C, rows, W, W.Z1);
+  return hwbc_level_qp(cx, C, rows, W, W.Z1, n1, 6);
+}
+
+// Z2 = Z1 kernel(A1 Z1) (6 x n1), again as the reference takes it.  Returns the number of columns, or -1.
+template <class Ctx>
+HB_HD int hwbc_level1_kernel(const Ctx& cx, const HwbcWork& W, int n1) {
+  for (int idx = cx.lane; idx < 6 * n1; idx += cx.nlanes) W.T[idx] = W.AZ[(idx / n1) * 12 + idx % n1];
+  for (int idx = cx.lane; idx < 144; idx += cx.nlanes) W.Q2[idx] = 0.0;
+  cx.sync();
+  const int n2 = fullpivlu_kernel(cx, W.T, 6, n1, n1, W.Q2, 12, 12, W.work);
+  if (n2 < 0) return n2;
   for (int idx = cx.lane; idx < NW * 12; idx += cx.nlanes) {
     const int i = idx / 12, j = idx % 12;
     double s = 0.0;
     if (j < n2)
-      for (int k = 0; k < n1; ++k) s += Z1[i * 12 + k] * Q2[k * 12 + j];
-    Z2[idx] = s;
+      for (int k = 0; k < n1; ++k) s += W.Z1[i * 12 + k] * W.Q2[k * 12 + j];
+    W.Z2[idx] = s;
   }
   cx.sync();
-  // ------------------------------------------------------------------ level 2: 0.1 * contact force + swing legs
-  if (n2 > 0 && max_level >= 3) {
-    const int m2 = 12 + 3 * wc.n_sw;
-    for (int idx = cx.lane; idx < m2 * 12; idx += cx.nlanes) {
-      const int i = idx / 12, j = idx % 12;
-      double s = 0.0;
-      if (i < 12) s = 0.1 * Z2[(16 + i) * 12 + j];
-      else
-        for (int c = 0; c < 16; ++c) s += Aw[(i - 12) * 16 + c] * Z2[c * 12 + j];
-      AZ[idx] = s;
-    }
-    for (int i = cx.lane; i < m2; i += cx.nlanes) {
-      double s;
-      if (i < 12) s = 0.1 * (udes[i] - x[16 + i]);
-      else {
-        s = bw[i - 12];
-        for (int c = 0; c < 16; ++c) s -= Aw[(i - 12) * 16 + c] * x[c];
-      }
-      rhs[i] = s;
-    }
-    for (int idx = cx.lane; idx < wc.n_in * 12; idx += cx.nlanes) {
-      const int c = idx / 12, j = idx % 12;
-      int ix[3];
-      double cfv[3], rh;
-      const int nn = sparse_row(wc, C, wc.n_eq + c, ix, cfv, &rh);
-      double s = 0.0, dx = 0.0;
-      for (int t = 0; t < nn; ++t) { s += cfv[t] * Z2[ix[t] * 12 + j]; dx += cfv[t] * x[ix[t]]; }
-      DZ[idx] = s;
-      if (j == 0) ft[c] = fmax(0.0, rh - dx + v0[c]);   // (z = 0 is feasible by construction: see hoqp_generic)
-    }
-    cx.sync();
-    const int rc2 = small_lsqp(cx, n2, m2, AZ, rhs, C.wbc_eps, wc.n_in, DZ, ft, 4 * C.wbc_max_iter, zs, qpw, n2, kHoqpHessianShift, C.wbc_reg_steps);
-    cx.sync();
-    if (rc2 > status) status = rc2;
-    for (int i = cx.lane; i < NW; i += cx.nlanes) {
-      double s = x[i];
-      for (int j = 0; j < n2; ++j) s += Z2[i * 12 + j] * zs[j];
-      g[i] = s;
-    }
-    cx.sync();
-    for (int i = cx.lane; i < NW; i += cx.nlanes) x[i] = g[i];
-    cx.sync();
+  return n2;
+}
+
+// Level 2: 0.1 * contact force + swing legs, over x + Z2 z.
+template <class Ctx>
+HB_HD int hwbc_level2(const Ctx& cx, const DevConfig& C, const HwbcRows& rows, const HwbcWork& W, const double* udes, int n2) {
+  const int m2 = 12 + 3 * rows.wc.n_sw;
+  for (int idx = cx.lane; idx < m2 * 12; idx += cx.nlanes) {
+    const int i = idx / 12, j = idx % 12;
+    double s = 0.0;
+    if (i < 12) s = 0.1 * W.Z2[(16 + i) * 12 + j];
+    else
+      for (int c = 0; c < 16; ++c) s += W.Aw[(i - 12) * 16 + c] * W.Z2[c * 12 + j];
+    W.AZ[idx] = s;
   }
-  for (int i = cx.lane; i < NW; i += cx.nlanes) sol[i] = x[i];
+  for (int i = cx.lane; i < m2; i += cx.nlanes) {
+    double s;
+    if (i < 12) s = 0.1 * (udes[i] - W.x[16 + i]);
+    else {
+      s = W.bw[i - 12];
+      for (int c = 0; c < 16; ++c) s -= W.Aw[(i - 12) * 16 + c] * W.x[c];
+    }
+    W.rhs[i] = s;
+  }
+  hwbc_project_inequalities(cx, C, rows, W, W.Z2);
+  const int rc = hwbc_level_qp(cx, C, rows, W, W.Z2, n2, m2);
+  cx.sync();
+  return rc;
+}
+
+template <class Ctx>
+HB_HD void hwbc_solve(const Ctx& cx, const DevModel& M, const DevConfig& C, const double* xdes, const double* udes,
+                      const double* rbd, int mode, double* lds, double* sol, int* status_out, int max_level = 3) {
+  const HwbcWork W(lds);
+  const HwbcRows rows{wbc_cons_of_mode(mode), W.Ee, W.beom, W.Jc, W.dJv};
+  wbc_phase_a(cx, M, C, xdes, udes, rbd, rows.wc, false, 1.0, 1.0, W.R, W.Ee, W.beom, W.Aw, W.bw, W.Jc, W.dJv, W.J);
+  for (int c = cx.lane; c < 40; c += cx.nlanes) W.viol[c] = 0;
+  cx.sync();
+  int status = hwbc_level0(cx, C, rows, W);
+  if (max_level > 1) {
+    const int n1 = hwbc_level0_kernel(cx, rows, W);
+    if (n1 < 0) {
+      if (cx.lane == 0) *status_out = HB_INST_MAXITER;
+      return;
+    }
+    HB_ABLATE_STOP(C.debug_stop == 43);  // profiling ablation: level 0 + kernel basis
+    const int rc1 = hwbc_level1(cx, C, rows, W, n1);
+    if (rc1 > status) status = rc1;
+    HB_ABLATE_STOP(C.debug_stop == 44);  // profiling ablation: ... + level-1 QP
+    const int n2 = hwbc_level1_kernel(cx, W, n1);
+    if (n2 < 0) {
+      if (cx.lane == 0) *status_out = HB_INST_MAXITER;
+      return;
+    }
+    if (n2 > 0 && max_level >= 3) {
+      const int rc2 = hwbc_level2(cx, C, rows, W, udes, n2);
+      if (rc2 > status) status = rc2;
+    }
+  }
+  for (int i = cx.lane; i < NW; i += cx.nlanes) sol[i] = W.x[i];
   if (cx.lane == 0) *status_out = status;
 }
 
@@ -1207,7 +1091,9 @@ __global__ __launch_bounds__(64) void k_hoqp_generic(int n, int n_levels, const 
                               x_levels + o * HQ_N, slack + o * HQ_M, lds, reg_steps);
   if (cx.lane == 0) status[p] = rc;
 }
-__global__ __launch_bounds__(64) void k_hwbc(WbcBatch w, const DevModel* __restrict__ M, const DevConfig* __restrict__ C) {
+// One wavefront per SIMD: two instances on one SIMD while another idles cost 5 % of the kernel's time (measured).  The register count
+// used to enforce this by being above 256; it is stated here so that it no longer depends on the register allocator.
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) void k_hwbc(WbcBatch w, const DevModel* __restrict__ M, const DevConfig* __restrict__ C) {
   __builtin_amdgcn_s_setprio(3);  // per-instance serial solve: latency critical next to another chunk's LQ kernel (see k_ric_bwd)
   const int inst = blockIdx.x;
   extern __shared__ __attribute__((aligned(16))) double lds_h[];

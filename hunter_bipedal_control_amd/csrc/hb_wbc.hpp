@@ -8,6 +8,7 @@
 //     sqrt(eps) I (never from H) — the role of qpOASES::QProblem::init at WeightedWbc.cpp:44-55.
 #pragma once
 #include "hb_lq.hpp"
+#include "hb_qpfactor.hpp"
 
 namespace hb {
 
@@ -302,6 +303,17 @@ struct WbcLds {
   static constexpr int total = xb + NW;
 };
 
+// the LDS work area of one WBC solve as pointers (layout WbcLds)
+struct WbcWork {
+  double *J, *R, *Ee, *Aw, *bw, *beom, *x, *np, *d, *z, *r, *lam, *red, *misc, *xb;
+  int *act, *is_active;
+  HB_HD explicit WbcWork(double* lds)
+      : J(lds + WbcLds::J), R(lds + WbcLds::R), Ee(lds + WbcLds::Eeom), Aw(lds + WbcLds::Aw), bw(lds + WbcLds::bw),
+        beom(lds + WbcLds::beom), x(lds + WbcLds::x), np(lds + WbcLds::np), d(lds + WbcLds::d), z(lds + WbcLds::z),
+        r(lds + WbcLds::r), lam(lds + WbcLds::lam), red(lds + WbcLds::red), misc(lds + WbcLds::misc), xb(lds + WbcLds::xb),
+        act(reinterpret_cast<int*>(lds + WbcLds::iact)), is_active(act + 40) {}
+};
+
 // constraint ids: [0,16) EoM rows, [16,16+3 nsw) zero force on swing feet, then inequalities:
 //   torque limits 20 rows (+tau_j <= lim, -tau_j <= lim), friction pyramid 5 rows per contact foot.
 struct WbcCons {
@@ -314,6 +326,19 @@ struct WbcCons {
   HB_HD void add_swing(int i) { sw_pack |= i << (2 * n_sw); ++n_sw; }
   HB_HD void add_contact(int i) { c_pack |= i << (2 * n_c); ++n_c; }
 };
+// the rows of contact mode `mode` (bit per foot: in contact)
+HB_HD WbcCons wbc_cons_of_mode(int mode) {
+  bool cf[HB_NC];
+  mode_flags(mode, cf);
+  WbcCons wc;
+  for (int i = 0; i < HB_NC; ++i) {
+    if (cf[i]) wc.add_contact(i);
+    else wc.add_swing(i);
+  }
+  wc.n_eq = 16 + 3 * wc.n_sw;
+  wc.n_in = 20 + 5 * wc.n_c;
+  return wc;
+}
 
 // sparse inequality / selector rows: returns up to 3 (index, coeff) pairs and the right-hand side
 HB_HD int sparse_row(const WbcCons& wc, const DevConfig& C, int cid, int* idx, double* cf, double* rhs) {
@@ -536,16 +561,12 @@ HB_HD double wbc_cons_coeff(const WbcCons& wc, const DevConfig& C, const double*
 // Sign convention: H x + g - A'y = 0, y <= 0 on active upper-bounded rows.
 template <class Ctx>
 HB_HD void wbc_certificate(const Ctx& cx, const DevConfig& C, const WbcCons& wc, const double* udes, bool stance_mode, int n_aw,
-                           double eps, int status, double* lds, const double* sol, double* cert, double* dual) {
-  const double* Ee = lds + WbcLds::Eeom;
-  const double* Aw = lds + WbcLds::Aw;
-  const double* bw = lds + WbcLds::bw;
-  const double* beom = lds + WbcLds::beom;
-  const double* x = lds + WbcLds::x;
-  const int* is_active = reinterpret_cast<const int*>(lds + WbcLds::iact) + 40;
-  double* red = lds + WbcLds::red;
-  double* At = lds + WbcLds::J;       // A_W' row-major (row = variable, column = member of W), reduced to R in place
-  double* wk = lds + WbcLds::R;
+                           double eps, int status, const WbcWork& W, const double* sol, double* cert, double* dual) {
+  const double *Ee = W.Ee, *Aw = W.Aw, *bw = W.bw, *beom = W.beom, *x = W.x;
+  const int* is_active = W.is_active;
+  double* red = W.red;
+  double* At = W.J;                   // A_W' row-major (row = variable, column = member of W), reduced to R in place
+  double* wk = W.R;
   double* xe = wk;                    // 38 evaluation point
   double* gs = wk + 40;               // 38 H xe + g
   double* c = wk + 80;                // 38 Q' (H xe + g)
@@ -684,483 +705,394 @@ HB_HD void wbc_certificate(const Ctx& cx, const DevConfig& C, const WbcCons& wc,
   for (int i = cx.lane; i < HB_WBC_NCONS_MAX; i += cx.nlanes) dual[i] = y[i];
 }
 
-// One WBC solve.  xdes/udes/rbd: this instance's inputs; sol in/out (kept when the QP fails).  The kCert instantiation also writes
-// the KKT certificate (cert [HB_WBC_CERT_SIZE]) and the dual solution (dual [HB_WBC_NCONS_MAX]) of this instance.
+// State of one WBC solve that the phases hand on: the problem (rows, eps) and the working set (J'N = [R; 0], q active rows, the
+// equalities first).
+struct WbcState {
+  WbcCons wc;
+  int n_aw;              // dense cost rows: stance mode 6 (qdd_base = 0), else 3 * n_sw swing + 6 base
+  bool stance_mode;
+  double eps;
+  int q = 0, iter = 0, status = 0;
+  int n_eq_active = 0;   // equalities in the active set (positions 0 .. n_eq_active - 1, never dropped)
+#if defined(__HIP_DEVICE_COMPILE__)
+  // lane i keeps row i of J in registers for the whole active-set loop: z = J2 d2 and the reflector update work on it without LDS
+  // reads (the LDS copy stays current for the column accesses of d = J'n and is what a constraint drop works on)
+  double jrow[NW];
+#if defined(HB_ABLATE)
+  long long wt_[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+#endif
+#endif
+};
 #if defined(HB_ABLATE) && defined(__HIP_DEVICE_COMPILE__)
-#define HB_WBC_MARK(i) if (C.debug_stop == 198 && blockIdx.x == 5) wt_[i] = __builtin_readcyclecounter();
+#define HB_WBC_MARK(i) if (C.debug_stop == 198 && blockIdx.x == 5) st.wt_[i] = __builtin_readcyclecounter();
 #else
 #define HB_WBC_MARK(i)
 #endif
-template <class Ctx, bool kCert = false>
-HB_HD void wbc_solve(const Ctx& cx, const DevModel& M, const DevConfig& C, const double* xdes, const double* udes,
-                     const double* rbd, int mode, bool stance_mode, double* lds, double* sol, int* status_out,
-                     int* iters_out, double* cert = nullptr, double* dual = nullptr) {
-#if defined(HB_ABLATE) && defined(__HIP_DEVICE_COMPILE__)
-  long long wt_[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-#endif
-  HB_WBC_MARK(0)
-  double* Jm = lds + WbcLds::J;
-  double* Rm = lds + WbcLds::R;
-  double* Ee = lds + WbcLds::Eeom;
-  double* Aw = lds + WbcLds::Aw;
-  double* bw = lds + WbcLds::bw;
-  double* beom = lds + WbcLds::beom;
-  double* x = lds + WbcLds::x;
-  double* np = lds + WbcLds::np;
-  double* d = lds + WbcLds::d;
-  double* z = lds + WbcLds::z;
-  double* r = lds + WbcLds::r;
-  double* lam = lds + WbcLds::lam;
-  double* red = lds + WbcLds::red;
-  double* misc = lds + WbcLds::misc;
-  int* act = reinterpret_cast<int*>(lds + WbcLds::iact);
-  int* is_active = act + 40;
-  double* xb = lds + WbcLds::xb;
 
-  bool cf[HB_NC];
-  mode_flags(mode, cf);
-  WbcCons wc;
-  wc.n_sw = 0;
-  wc.n_c = 0;
-  for (int i = 0; i < HB_NC; ++i) {
-    if (cf[i]) wc.add_contact(i);
-    else wc.add_swing(i);
+// The Tikhonov term of this problem (hb_config.wbc_eps_mode): the configured constant, or what qpOASES 3.2's regulariseHessian adds to
+// the diagonal, |H|_F * epsRegularisation with epsRegularisation = 1e3 * EPS (Options::setToMPC; WeightedWbc.cpp:44-55 passes
+// H = A_w' A_w [qpOASES-knowledge]).  A_w = [Aw (n_aw x 16) | w_force I (12, walking) | 0], so |H|_F^2 = |Aw' Aw|_F^2 + 12 w_force^4.
+template <class Ctx>
+HB_HD double wbc_eps(const Ctx& cx, const DevConfig& C, const WbcWork& W, const WbcState& st) {
+  if (C.wbc_eps_mode != 1) return C.wbc_eps;
+  double part = 0.0;
+  for (int e = cx.lane; e < 256; e += cx.nlanes) {
+    const int i = e >> 4, j = e & 15;
+    double g = 0.0;
+    for (int rw = 0; rw < st.n_aw; ++rw) g += W.Aw[rw * 16 + i] * W.Aw[rw * 16 + j];
+    part += g * g;
   }
-  wc.n_eq = 16 + 3 * wc.n_sw;
-  wc.n_in = 20 + 5 * wc.n_c;
-  // number of dense cost rows: stance mode 6 (qdd_base = 0), else 3*n_sw swing + 6 base
-  const int n_aw = stance_mode ? 6 : 3 * wc.n_sw + 6;
+  W.red[cx.lane] = part;
+  cx.sync();
+  double h2 = st.stance_mode ? 0.0 : 12.0 * (C.w_force * C.w_force) * (C.w_force * C.w_force);
+  for (int l = 0; l < cx.nlanes; ++l) h2 += W.red[l];   // (every lane, same order: a uniform value)
+  cx.sync();
+  const double e1 = sqrt(h2) * (1.0e3 * 2.220446049250313e-16);
+  return e1 > 0.0 ? e1 : C.wbc_eps;
+}
 
-  // ------------------------------------------------------------------ phase A: rigid-body quantities
-  static_assert(PHASE_A_WORK_DOUBLES <= NW * NW, "phase-A workspace must fit the J buffer");
-  wbc_phase_a(cx, M, C, xdes, udes, rbd, wc, stance_mode, C.w_swing, C.w_base, Rm, Ee, beom, Aw, bw, nullptr, nullptr, Jm);
-  if (cx.lane == 0) misc[0] = 0.0;  // status
-  cx.sync();
-  HB_WBC_MARK(1)
-
-  HB_ABLATE_STOP(C.debug_stop == 11 || (C.debug_stop >= 13 && C.debug_stop <= 15));
-  // The Tikhonov term of this problem (hb_config.wbc_eps_mode): the configured constant, or what qpOASES 3.2's regulariseHessian adds to
-  // the diagonal, |H|_F * epsRegularisation with epsRegularisation = 1e3 * EPS (Options::setToMPC; WeightedWbc.cpp:44-55 passes
-  // H = A_w' A_w [qpOASES-knowledge]).  A_w = [Aw (n_aw x 16) | w_force I (12, walking) | 0], so |H|_F^2 = |Aw' Aw|_F^2 + 12 w_force^4.
-  double eps = C.wbc_eps;
-  if (C.wbc_eps_mode == 1) {
-    double part = 0.0;
-    for (int e = cx.lane; e < 256; e += cx.nlanes) {
-      const int i = e >> 4, j = e & 15;
-      double g = 0.0;
-      for (int rw = 0; rw < n_aw; ++rw) g += Aw[rw * 16 + i] * Aw[rw * 16 + j];
-      part += g * g;
-    }
-    red[cx.lane] = part;
-    cx.sync();
-    double h2 = stance_mode ? 0.0 : 12.0 * (C.w_force * C.w_force) * (C.w_force * C.w_force);
-    for (int l = 0; l < cx.nlanes; ++l) h2 += red[l];   // (every lane, same order: a uniform value)
-    cx.sync();
-    const double e1 = sqrt(h2) * (1.0e3 * 2.220446049250313e-16);
-    eps = e1 > 0.0 ? e1 : C.wbc_eps;
-  }
-  // ------------------------------------------------------------------ phase B: R~ by Givens row insertion
-  const double se = sqrt(eps);
-  for (int idx = cx.lane; idx < NW * NW; idx += cx.nlanes) Rm[idx] = (idx / NW == idx % NW) ? se : 0.0;
-  cx.sync();
-  // contact-force cost rows (weight w_force, WbcBase.cpp:325-338) are diagonal: fold into the diagonal start
-  if (!stance_mode && C.w_force != 0.0) {
-    for (int i = cx.lane; i < 12; i += cx.nlanes) Rm[(16 + i) * NW + 16 + i] = sqrt(eps + C.w_force * C.w_force);
-    cx.sync();
-  }
-  // right-hand side g = A_w' b_w accumulates in d (dense over 38)
-  for (int i = cx.lane; i < NW; i += cx.nlanes) {
-    double s = 0.0;
-    if (i < 16)
-      for (int rw = 0; rw < n_aw; ++rw) s += Aw[rw * 16 + i] * bw[rw];
-    else if (i < 28 && !stance_mode)
-      s = C.w_force * C.w_force * udes[i - 16];
-    d[i] = s;
-  }
-#if defined(__HIP_DEVICE_COMPILE__)
-  // Device: the 16 x 16 triangle of [sqrt(eps) I ; A_w] by 16 structured Householder reflectors (support: row k of the identity
-  // block + the dense cost rows), lane j owning column j of A_w in registers and column k reaching the other lanes as
-  // wave-uniform values — no LDS traffic and no ordering point inside the factorisation (see k_hwbc level 0, hb_hoqp.hpp).
-  {
-    constexpr int MA = 18;
-    const int j = cx.lane;
-    double acol[MA];
-#pragma unroll
-    for (int r = 0; r < MA; ++r) acol[r] = (j < 16 && r < n_aw) ? Aw[r * 16 + j] : 0.0;
-#pragma unroll 1
-    for (int k = 0; k < 16; ++k) {
-      double dot = 0.0;
-      double ck[MA];
-#pragma unroll
-      for (int r = 0; r < MA; ++r) {
-        ck[r] = wave_bcast_f64(acol[r], k);
-        dot += ck[r] * acol[r];
-      }
-      const double sig2 = se * se + wave_bcast_f64(dot, k);
-      const double alpha = -sqrt(sig2);
-      const double v0 = se - alpha;
-      const double beta = 2.0 * rcp_t(sig2 - se * se + v0 * v0);
-      const double w = beta * (dot + (j == k ? v0 * se : 0.0));
-      const bool live = j > k && j < 16;
-#pragma unroll
-      for (int r = 0; r < MA; ++r) acol[r] = live ? acol[r] - w * ck[r] : (j == k ? 0.0 : acol[r]);
-      if (j < 16) Rm[k * NW + j] = j < k ? 0.0 : (j == k ? alpha : -w * v0);
-    }
-    cx.sync();
-  }
-  HB_WBC_MARK(2)
-#else
-  for (int rw = 0; rw < n_aw; ++rw) {
-    for (int i = cx.lane; i < NW; i += cx.nlanes) np[i] = (i < 16) ? Aw[rw * 16 + i] : 0.0;
-    cx.sync();
-    for (int k = 0; k < 16; ++k) {  // the row is zero beyond column 15 and stays so
-      const double a = Rm[k * NW + k], b = np[k];
-      cx.sync();
-      if (b != 0.0) {
-        const double rh = rsqrt_t(a * a + b * b), cc = a * rh, ss = b * rh;
-        for (int j = cx.lane; j < 16; j += cx.nlanes) {  // the row and the rows of R~ it meets are zero beyond column 15
-          if (j >= k) {
-            const double t1 = Rm[k * NW + j], t2 = np[j];
-            Rm[k * NW + j] = cc * t1 + ss * t2;
-            np[j] = -ss * t1 + cc * t2;
-          }
-        }
-      }
-      cx.sync();
-    }
-  }
-#endif
-  // J = R~^-1 (upper triangular inverse), one column per lane.  R~ is a dense 16 x 16 triangle (the cost rows only
-  // involve the accelerations) followed by a diagonal: columns >= 16 of the inverse are the reciprocal diagonal.
-  for (int idx = cx.lane; idx < NW * NW; idx += cx.nlanes) Jm[idx] = 0.0;
-  cx.sync();
+// J = R~^-1.  R~ is a dense 16 x 16 triangle (the cost rows only involve the accelerations) followed by a diagonal: columns >= 16 of
+// the inverse are the reciprocal diagonal.  J is zero on entry.
+template <class Ctx>
+HB_HD void wbc_invert_cost_factor(const Ctx& cx, const WbcWork& W) {
 #if defined(__HIP_DEVICE_COMPILE__)
   // Device: a lane keeps ITS column of the inverse in registers (fixed 16-step loops, entries beyond the column masked to zero) and
   // writes it once — in place every term was an LDS round trip behind the store of the row before it (17 k cycles of a 290 k solve)
   if (cx.lane < NW) {
     const int col = cx.lane;
     if (col >= 16) {
-      Jm[col * NW + col] = rcp_t(Rm[col * NW + col]);
+      W.J[col * NW + col] = rcp_t(W.R[col * NW + col]);
     } else {
       double xc[16];
 #pragma unroll
       for (int i = 15; i >= 0; --i) {
         double s = (i == col) ? 1.0 : 0.0;
 #pragma unroll
-        for (int k = i + 1; k < 16; ++k) s -= Rm[i * NW + k] * (k <= col ? xc[k] : 0.0);
-        xc[i] = i <= col ? s * rcp_t(Rm[i * NW + i]) : 0.0;
+        for (int k = i + 1; k < 16; ++k) s -= W.R[i * NW + k] * (k <= col ? xc[k] : 0.0);
+        xc[i] = i <= col ? s * rcp_t(W.R[i * NW + i]) : 0.0;
       }
 #pragma unroll
       for (int i = 0; i < 16; ++i)
-        if (i <= col) Jm[i * NW + col] = xc[i];
+        if (i <= col) W.J[i * NW + col] = xc[i];
     }
   }
 #else
-  for (int col = cx.lane; col < NW; col += cx.nlanes) {
-    if (col >= 16) {
-      Jm[col * NW + col] = rcp_t(Rm[col * NW + col]);
-    } else {
-      for (int i = col; i >= 0; --i) {
-        double s = (i == col) ? 1.0 : 0.0;
-        for (int k = i + 1; k <= col; ++k) s -= Rm[i * NW + k] * Jm[k * NW + col];
-        Jm[i * NW + col] = s * rcp_t(Rm[i * NW + i]);
-      }
-    }
-  }
+  invert_upper(cx, W.R, NW, 16, W.J);
+  for (int col = 16 + cx.lane; col < NW; col += cx.nlanes) W.J[col * NW + col] = rcp_t(W.R[col * NW + col]);
 #endif
   cx.sync();
-  // unconstrained minimiser x = J J' g
-  for (int k = cx.lane; k < NW; k += cx.nlanes) {
-    double sa[4] = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-    for (int i = 0; i < NW; ++i) sa[i & 3] += Jm[i * NW + k] * d[i];
-    z[k] = (sa[0] + sa[1]) + (sa[2] + sa[3]);
-  }
+}
+
+// Phase B: the factor R~ of H + eps I = [sqrt(eps) I ; A_w]'[sqrt(eps) I ; A_w] (never formed from H), J = R~^-1 and the
+// unconstrained minimiser x = J J' A_w' b_w.  Leaves R zero (from here on it is the factor of the working set) and no row active.
+template <class Ctx>
+HB_HD void wbc_cost_factor(const Ctx& cx, const DevConfig& C, const double* udes, const WbcWork& W, WbcState& st) {
+  const double se = sqrt(st.eps);
+  for (int idx = cx.lane; idx < NW * NW; idx += cx.nlanes) W.R[idx] = (idx / NW == idx % NW) ? se : 0.0;
   cx.sync();
-  for (int i = cx.lane; i < NW; i += cx.nlanes) {
-    double sa[4] = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-    for (int k = 0; k < NW; ++k) sa[k & 3] += Jm[i * NW + k] * z[k];
-    x[i] = (sa[0] + sa[1]) + (sa[2] + sa[3]);
+  // contact-force cost rows (weight w_force, WbcBase.cpp:325-338) are diagonal: fold into the diagonal start
+  if (!st.stance_mode && C.w_force != 0.0) {
+    for (int i = cx.lane; i < 12; i += cx.nlanes) W.R[(16 + i) * NW + 16 + i] = sqrt(st.eps + C.w_force * C.w_force);
+    cx.sync();
   }
-  for (int idx = cx.lane; idx < NW * NW; idx += cx.nlanes) Rm[idx] = 0.0;
-  for (int i = cx.lane; i < 64; i += cx.nlanes) is_active[i] = 0;
+  // right-hand side g = A_w' b_w accumulates in d (dense over 38)
+  for (int i = cx.lane; i < NW; i += cx.nlanes) {
+    double s = 0.0;
+    if (i < 16)
+      for (int rw = 0; rw < st.n_aw; ++rw) s += W.Aw[rw * 16 + i] * W.bw[rw];
+    else if (i < 28 && !st.stance_mode)
+      s = C.w_force * C.w_force * udes[i - 16];
+    W.d[i] = s;
+  }
+  // the 16 x 16 triangle of [sqrt(eps) I ; A_w]: the dense cost rows only involve the accelerations
+  regularised_factor<18, false>(cx, 16, st.n_aw, W.Aw, 16, nullptr, nullptr, UniformDiag(se), W.R, NW, 16, W.np);
+  HB_WBC_MARK(2)
+  for (int idx = cx.lane; idx < NW * NW; idx += cx.nlanes) W.J[idx] = 0.0;
+  cx.sync();
+  wbc_invert_cost_factor(cx, W);
+  // unconstrained minimiser x = J J' g
+  for (int k = cx.lane; k < NW; k += cx.nlanes) W.z[k] = dot4<NW>(W.J + k, NW, W.d, 1);
+  cx.sync();
+  for (int i = cx.lane; i < NW; i += cx.nlanes) W.x[i] = dot4<NW>(W.J + i * NW, 1, W.z, 1);
+  for (int idx = cx.lane; idx < NW * NW; idx += cx.nlanes) W.R[idx] = 0.0;
+  for (int i = cx.lane; i < 64; i += cx.nlanes) W.is_active[i] = 0;
   cx.sync();
   HB_WBC_MARK(3)
+}
 
-  HB_ABLATE_STOP(C.debug_stop == 12);
-  // ------------------------------------------------------------------ phase C: Goldfarb–Idnani iterations
+// (Device) the lane's register copy of its row of J, from the LDS copy.
+template <class Ctx>
+HB_HD void wbc_load_jrow(const Ctx& cx, const WbcWork& W, WbcState& st) {
 #if defined(__HIP_DEVICE_COMPILE__)
-  // lane i keeps row i of J in registers for the whole active-set loop: z = J2 d2 and the reflector update work on it
-  // without LDS reads (the LDS copy stays current for the column accesses of d = J'n and is what a constraint drop works on)
-  double jrow[NW];
 #pragma unroll
-  for (int j = 0; j < NW; ++j) jrow[j] = cx.lane < NW ? Jm[cx.lane * NW + j] : 0.0;
+  for (int j = 0; j < NW; ++j) st.jrow[j] = cx.lane < NW ? W.J[cx.lane * NW + j] : 0.0;
 #endif
-  // One Householder reflector H maps d2 = d[q:] onto (alpha, 0, ...); the trailing columns of J are updated as J2 <- J2 H,
-  // each lane owning a row of J (one barrier instead of one per rotation).  Leaves d = (d1, alpha, 0, ...).
-  auto reflect = [&](int q) {
-    double nrm2 = 0.0;
+}
+
+// (J2 d2)_i with J2 = J(:, q:), d2 = d[q:].  Fixed trip count with a uniform mask instead of a loop from q: the compiler unrolls it
+// and batches the LDS reads; the rolled loop paid one LDS round trip per term on a wave that has its SIMD to itself.
+HB_HD double wbc_j2d2(const WbcWork& W, const WbcState& st, int i) {
+  double sa[4] = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+  for (int j = 0; j < NW; ++j) {
 #if defined(__HIP_DEVICE_COMPILE__)
-    {
-      const double dj = (cx.lane >= q && cx.lane < NW) ? d[cx.lane] : 0.0;
-      nrm2 = wave_sum_f64(dj * dj);
-    }
+    const double jij = st.jrow[j];  // i == lane
 #else
-    for (int j = q; j < NW; ++j) nrm2 += d[j] * d[j];
+    const double jij = W.J[i * NW + j];
 #endif
-    const double dq = d[q];
-    const double alpha = dq > 0.0 ? -sqrt(nrm2) : sqrt(nrm2);
-    const double v0 = dq - alpha;
-    const double vtv = nrm2 - dq * dq + v0 * v0;
-    if (vtv > 0.0 && nrm2 > 0.0) {
-      const double beta = 2.0 * rcp_t(vtv);
-      // reflector vector hv = (0, ..., 0, v0, d[q+1], ..., d[NW-1]); each lane holds its row of J in registers:
-      // two fixed-length passes (unrolled, batched LDS traffic) instead of two rolled loops from q + 1
-      for (int k = cx.lane; k < NW; k += cx.nlanes) {
+    sa[j & 3] += jij * (j >= st.q ? W.d[j] : 0.0);
+  }
+  return (sa[0] + sa[1]) + (sa[2] + sa[3]);
+}
+
+// One Householder reflector H maps d2 = d[q:] onto (alpha, 0, ...); the trailing columns of J are updated as J2 <- J2 H,
+// each lane owning a row of J (one barrier instead of one per rotation).  Leaves d = (d1, alpha, 0, ...).
+template <class Ctx>
+HB_HD void wbc_reflect(const Ctx& cx, const WbcWork& W, WbcState& st, int q) {
+  double* d = W.d;
+  double nrm2 = 0.0;
 #if defined(__HIP_DEVICE_COMPILE__)
-        double* row = jrow;  // k == lane
+  {
+    const double dj = (cx.lane >= q && cx.lane < NW) ? d[cx.lane] : 0.0;
+    nrm2 = wave_sum_f64(dj * dj);
+  }
 #else
-        double row[NW];
-#pragma unroll
-        for (int j = 0; j < NW; ++j) row[j] = Jm[k * NW + j];
+  for (int j = q; j < NW; ++j) nrm2 += d[j] * d[j];
 #endif
-        double sa[4] = {0.0, 0.0, 0.0, 0.0};
+  const double dq = d[q];
+  const double alpha = dq > 0.0 ? -sqrt(nrm2) : sqrt(nrm2);
+  const double v0 = dq - alpha;
+  const double vtv = nrm2 - dq * dq + v0 * v0;
+  if (vtv > 0.0 && nrm2 > 0.0) {
+    const double beta = 2.0 * rcp_t(vtv);
+    // reflector vector hv = (0, ..., 0, v0, d[q+1], ..., d[NW-1]); each lane holds its row of J in registers:
+    // two fixed-length passes (unrolled, batched LDS traffic) instead of two rolled loops from q + 1
+    for (int k = cx.lane; k < NW; k += cx.nlanes) {
+#if defined(__HIP_DEVICE_COMPILE__)
+      double* row = st.jrow;  // k == lane
+#else
+      double row[NW];
 #pragma unroll
-        for (int j = 0; j < NW; ++j) sa[j & 3] += row[j] * (j < q ? 0.0 : (j == q ? v0 : d[j]));
-        const double sacc = ((sa[0] + sa[1]) + (sa[2] + sa[3])) * beta;
+      for (int j = 0; j < NW; ++j) row[j] = W.J[k * NW + j];
+#endif
+      double sa[4] = {0.0, 0.0, 0.0, 0.0};
 #pragma unroll
-        for (int j = 0; j < NW; ++j) {
-          row[j] = row[j] - sacc * (j < q ? 0.0 : (j == q ? v0 : d[j]));
-          Jm[k * NW + j] = row[j];
-        }
+      for (int j = 0; j < NW; ++j) sa[j & 3] += row[j] * (j < q ? 0.0 : (j == q ? v0 : d[j]));
+      const double sacc = ((sa[0] + sa[1]) + (sa[2] + sa[3])) * beta;
+#pragma unroll
+      for (int j = 0; j < NW; ++j) {
+        row[j] = row[j] - sacc * (j < q ? 0.0 : (j == q ? v0 : d[j]));
+        W.J[k * NW + j] = row[j];
       }
     }
-    cx.sync();
-    for (int j = q + cx.lane; j < NW; j += cx.nlanes) d[j] = (j == q) ? alpha : 0.0;
-    cx.sync();
-  };
-  int q = 0, iter = 0, status = 0;
-  // ---- the equalities (16 equation-of-motion rows + 3 zero-force rows per swing foot) enter the active set as a block:
-  // they are never dropped and no inequality is active yet, so the dual method's step-length logic is idle for them —
-  // each addition is the full primal step.  Per row only d = J'n, the reflector and the new column of R are formed; the
-  // primal point after the block is  x - J1 R^-T (N'x - b)  in one go (forward substitution through lane registers).
-  if (wc.n_eq > C.wbc_max_iter) status = HB_INST_MAXITER;  // every addition counts as one iteration (nWSR)
+  }
+  cx.sync();
+  for (int j = q + cx.lane; j < NW; j += cx.nlanes) d[j] = (j == q) ? alpha : 0.0;
+  cx.sync();
+}
+
+// Appends row p, whose d = J'n wbc_reflect has just reduced, to the working set with multiplier lam_p — unless it depends on the
+// rows already there (returns false).
+template <class Ctx>
+HB_HD bool wbc_append_row(const Ctx& cx, const WbcWork& W, WbcState& st, int p, double lam_p) {
+  if (!(fabs(W.d[st.q]) > 1e-13 * fmax(1.0, fabs(W.R[0])))) return false;
+  for (int i = cx.lane; i <= st.q; i += cx.nlanes) W.R[i * NW + st.q] = W.d[i];
+  if (cx.lane == 0) { W.act[st.q] = p; W.lam[st.q] = lam_p; W.is_active[p] = 1; }
+  ++st.q;
+  return true;
+}
+
+// The equalities (16 equation-of-motion rows + 3 zero-force rows per swing foot) enter the active set as a block:
+// they are never dropped and no inequality is active yet, so the dual method's step-length logic is idle for them —
+// each addition is the full primal step.  Per row only d = J'n, the reflector and the new column of R are formed; the
+// primal point after the block is  x - J1 R^-T (N'x - b)  in one go (forward substitution through lane registers).
+template <class Ctx>
+HB_HD void wbc_equality_block(const Ctx& cx, const DevConfig& C, const WbcWork& W, WbcState& st) {
+  const WbcCons& wc = st.wc;
+  if (wc.n_eq > C.wbc_max_iter) st.status = HB_INST_MAXITER;  // every addition counts as one iteration (nWSR)
 #if defined(__HIP_DEVICE_COMPILE__)
 #pragma unroll
 #endif
-  for (int p = 0; p < 16 + 3 * HB_NC; ++p) {  // (fixed trip count: unrolled on the device, q = p is then a constant in `reflect`)
-    if (p >= wc.n_eq || status != 0) break;
+  for (int p = 0; p < 16 + 3 * HB_NC; ++p) {  // (fixed trip count: unrolled on the device, q = p is then a constant in wbc_reflect)
+    if (p >= wc.n_eq || st.status != 0) break;
     if (p == 5) { HB_WBC_MARK(7) }
     if (p < 16) {
-      for (int k = cx.lane; k < NW; k += cx.nlanes) {
-        double sa[4] = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-        for (int i = 0; i < NW; ++i) sa[i & 3] += Jm[i * NW + k] * Ee[p * NW + i];
-        d[k] = (sa[0] + sa[1]) + (sa[2] + sa[3]);
-      }
+      for (int k = cx.lane; k < NW; k += cx.nlanes) W.d[k] = dot4<NW>(W.J + k, NW, W.Ee + p * NW, 1);
     } else {
       const int sidx = 16 + 3 * wc.swing_foot((p - 16) / 3) + (p - 16) % 3;  // unit normal: a row of J
-      for (int k = cx.lane; k < NW; k += cx.nlanes) d[k] = Jm[sidx * NW + k];
+      for (int k = cx.lane; k < NW; k += cx.nlanes) W.d[k] = W.J[sidx * NW + k];
     }
     cx.sync();
     if (p == 5) { HB_WBC_MARK(8) }
-    reflect(q);
+    wbc_reflect(cx, W, st, st.q);
     if (p == 5) { HB_WBC_MARK(9) }
-    if (!(fabs(d[q]) > 1e-13 * fmax(1.0, fabs(Rm[0])))) { status = HB_INST_INFEASIBLE; break; }  // dependent equality rows
-    for (int i = cx.lane; i <= q; i += cx.nlanes) Rm[i * NW + q] = d[i];
-    if (cx.lane == 0) { act[q] = p; lam[q] = 0.0; is_active[p] = 1; }
-    ++q;
-    ++iter;
+    if (!wbc_append_row(cx, W, st, p, 0.0)) { st.status = HB_INST_INFEASIBLE; break; }  // dependent equality rows
+    ++st.iter;
     cx.sync();
   }
   HB_WBC_MARK(4)
-  if (status == 0 && q > 0) {
+  const int q = st.q;
+  if (st.status == 0 && q > 0) {
     // residuals s_p = n_p'x - b_p (lane p), then R'y = s by substitution, then x -= J1 y
     for (int pp = cx.lane; pp < NW; pp += cx.nlanes) {
       double sres = 0.0;
       if (pp < q) {
-        if (pp < 16) {
-          double sa[4] = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-          for (int i = 0; i < NW; ++i) sa[i & 3] += Ee[pp * NW + i] * x[i];
-          sres = (sa[0] + sa[1]) + (sa[2] + sa[3]) - beom[pp];
-        } else {
-          sres = x[16 + 3 * wc.swing_foot((pp - 16) / 3) + (pp - 16) % 3];
-        }
+        if (pp < 16) sres = dot4<NW>(W.Ee + pp * NW, 1, W.x, 1) - W.beom[pp];
+        else sres = W.x[16 + 3 * wc.swing_foot((pp - 16) / 3) + (pp - 16) % 3];
       }
-      r[pp] = sres;
+      W.r[pp] = sres;
     }
     cx.sync();
 #if defined(__HIP_DEVICE_COMPILE__)
     {
-      double sres = cx.lane < NW ? r[cx.lane] : 0.0;
-      const double rdiag = rcp_t(cx.lane < q ? Rm[cx.lane * NW + cx.lane] : 1.0);
+      double sres = cx.lane < NW ? W.r[cx.lane] : 0.0;
+      const double rdiag = rcp_t(cx.lane < q ? W.R[cx.lane * NW + cx.lane] : 1.0);
       double xacc = 0.0;
       for (int i = 0; i < q; ++i) {  // y_i = s_i / R_ii (uniform), s_p -= R_ip y_i on the lanes p > i, x -= J(:, i) y_i
         const double yi = wave_bcast_f64(sres * rdiag, i);
-        if (cx.lane > i && cx.lane < q) sres -= Rm[i * NW + cx.lane] * yi;
-        xacc += (cx.lane < NW ? Jm[cx.lane * NW + i] : 0.0) * yi;
+        if (cx.lane > i && cx.lane < q) sres -= W.R[i * NW + cx.lane] * yi;
+        xacc += (cx.lane < NW ? W.J[cx.lane * NW + i] : 0.0) * yi;
       }
-      if (cx.lane < NW) x[cx.lane] -= xacc;
+      if (cx.lane < NW) W.x[cx.lane] -= xacc;
     }
 #else
     for (int l0 = cx.lane; l0 < 1; l0 += cx.nlanes) {
       for (int i = 0; i < q; ++i) {
-        const double yi = r[i] / Rm[i * NW + i];
-        for (int pp = i + 1; pp < q; ++pp) r[pp] -= Rm[i * NW + pp] * yi;
-        r[i] = yi;
+        const double yi = W.r[i] / W.R[i * NW + i];
+        for (int pp = i + 1; pp < q; ++pp) W.r[pp] -= W.R[i * NW + pp] * yi;
+        W.r[i] = yi;
       }
       for (int k = 0; k < NW; ++k) {
         double acc = 0.0;
-        for (int i = 0; i < q; ++i) acc += Jm[k * NW + i] * r[i];
-        x[k] -= acc;
+        for (int i = 0; i < q; ++i) acc += W.J[k * NW + i] * W.r[i];
+        W.x[k] -= acc;
       }
     }
 #endif
     cx.sync();
   }
   HB_WBC_MARK(5)
-  const int next_eq_active = q;  // equalities in the active set (never dropped)
-  const int n_cons = wc.n_eq + wc.n_in;
-  const double inf = 1e300;
-  // Phase 0 is the eps-regularised problem; every further phase is one REGULARISATION STEP (qpOASES numRegularisationSteps, setToMPC: 1 —
-  // WeightedWbc.cpp:47-48): the proximal-point problem  argmin f + eps/2 |x - x_k|^2  with the same constraints.  With J J' = (H + eps I)^-1,
-  // J'N = [R; 0] and J2 = J(:, q:), its solution on the current working set is  x_{k+1} = x_k + eps J2 J2'(x_k - x_{k-1}),  x_{-1} = 0,  with
-  // multipliers  lam + eps R^-1 J1'(x_k - x_{k-1})  — and that pair is what the dual method iterates on, so the same loop goes on from it
-  // (normally one scan that finds nothing violated).  The residual gradient is never formed (J2 J2' would amplify its rounding noise by
-  // 1 / eps in the directions no cost row sees).  One step moves the point from first to second order in eps / lambda away from the
-  // eps -> 0 limit, the minimum-norm minimiser.
-  for (int i = cx.lane; i < NW; i += cx.nlanes) xb[i] = 0.0;
-  cx.sync();
-  const int n_reg = C.wbc_reg_steps > 0 ? C.wbc_reg_steps : 0;   // (phase 0 — the solve with every constraint — runs whatever the field holds)
-  for (int phase = 0; phase <= n_reg && status == 0; ++phase) {
-  if (phase > 0) {
-    for (int i = cx.lane; i < NW; i += cx.nlanes) { np[i] = x[i] - xb[i]; xb[i] = x[i]; }
+  st.n_eq_active = q;
+}
+
+// r[n_eq_active .. q-1] <- the entries of R^-1 r that belong to the active INEQUALITIES.  The equalities hold positions
+// 0 .. n_eq_active - 1 of the active set for good and R is upper triangular, so the back substitution from the bottom reaches the
+// inequalities first and stops there: q - n_eq steps (0 .. 3 typically) instead of q (22 +), two ordering points each.  `visit(i, ri)`
+// runs on lane 0 for every entry.
+template <class Ctx, class Visit>
+HB_HD void wbc_backsolve_inequalities(const Ctx& cx, const WbcWork& W, const WbcState& st, Visit visit) {
+  for (int i = st.q - 1; i >= st.n_eq_active; --i) {
+    const double ri = W.r[i] / W.R[i * NW + i];
     cx.sync();
-    for (int k = cx.lane; k < NW; k += cx.nlanes) {   // d = J'(x_k - x_{k-1})
-      double sa[4] = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-      for (int i = 0; i < NW; ++i) sa[i & 3] += Jm[i * NW + k] * np[i];
-      d[k] = (sa[0] + sa[1]) + (sa[2] + sa[3]);
-    }
+    for (int k = st.n_eq_active + cx.lane; k < i; k += cx.nlanes) W.r[k] -= W.R[k * NW + i] * ri;
+    if (cx.lane == 0) visit(i, ri);
     cx.sync();
-    for (int i = cx.lane; i < NW; i += cx.nlanes) {   // x += eps J2 d2
-      double sa[4] = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-      for (int j = 0; j < NW; ++j) {
-#if defined(__HIP_DEVICE_COMPILE__)
-        const double jij = jrow[j];
-#else
-        const double jij = Jm[i * NW + j];
-#endif
-        sa[j & 3] += jij * (j >= q ? d[j] : 0.0);
-      }
-      x[i] += eps * ((sa[0] + sa[1]) + (sa[2] + sa[3]));
-      if (i < q) r[i] = d[i];
-    }
-    cx.sync();
-    // multipliers of the active INEQUALITIES (positions next_eq_active .. q - 1): R is upper triangular, so the back substitution of
-    // R dl = d1 from the bottom reaches them first and stops there
-    for (int i = q - 1; i >= next_eq_active; --i) {
-      const double ri = r[i] / Rm[i * NW + i];
-      cx.sync();
-      for (int k = next_eq_active + cx.lane; k < i; k += cx.nlanes) r[k] -= Rm[k * NW + i] * ri;
-      if (cx.lane == 0) lam[i] = fmax(0.0, lam[i] + eps * ri);   // (a multiplier that sat at zero: the row stays, at multiplier zero)
-      cx.sync();
-    }
   }
-  while (status == 0) {
-    int p = -1;
-    double sp = 0.0;
-    {
-      // most violated inequality (lane-parallel scan + reduction through LDS)
-      double best = 0.0;
-      int bi = -1;
-      for (int c = wc.n_eq + cx.lane; c < n_cons; c += cx.nlanes) {
-        if (is_active[c]) continue;
-        int idx[3];
-        double cfv[3], rhs;
-        const int nn = sparse_row(wc, C, c, idx, cfv, &rhs);
-        double s = -rhs;
-        for (int t = 0; t < nn; ++t) s += cfv[t] * x[idx[t]];
-        if (s > 1e-9 * fmax(1.0, fabs(rhs)) && s > best) { best = s; bi = c; }
-      }
+}
+
+// One REGULARISATION STEP (qpOASES numRegularisationSteps, setToMPC: 1 — WeightedWbc.cpp:47-48): the proximal-point problem
+// argmin f + eps/2 |x - x_k|^2  with the same constraints.  With J J' = (H + eps I)^-1, J'N = [R; 0] and J2 = J(:, q:), its solution on
+// the current working set is  x_{k+1} = x_k + eps J2 J2'(x_k - x_{k-1}),  x_{-1} = 0,  with multipliers  lam + eps R^-1 J1'(x_k - x_{k-1})
+// — and that pair is what the dual method iterates on, so the inequality loop goes on from it (normally one scan that finds nothing
+// violated).  The residual gradient is never formed (J2 J2' would amplify its rounding noise by 1 / eps in the directions no cost
+// row sees).  One step moves the point from first to second order in eps / lambda away from the eps -> 0 limit, the minimum-norm
+// minimiser.
+template <class Ctx>
+HB_HD void wbc_regularisation_step(const Ctx& cx, const WbcWork& W, WbcState& st) {
+  for (int i = cx.lane; i < NW; i += cx.nlanes) { W.np[i] = W.x[i] - W.xb[i]; W.xb[i] = W.x[i]; }
+  cx.sync();
+  for (int k = cx.lane; k < NW; k += cx.nlanes) W.d[k] = dot4<NW>(W.J + k, NW, W.np, 1);   // d = J'(x_k - x_{k-1})
+  cx.sync();
+  for (int i = cx.lane; i < NW; i += cx.nlanes) {   // x += eps J2 d2
+    W.x[i] += st.eps * wbc_j2d2(W, st, i);
+    if (i < st.q) W.r[i] = W.d[i];
+  }
+  cx.sync();
+  // (a multiplier that sat at zero: the row stays, at multiplier zero)
+  wbc_backsolve_inequalities(cx, W, st, [&](int i, double ri) { W.lam[i] = fmax(0.0, W.lam[i] + st.eps * ri); });
+}
+
+// Most violated inactive inequality at x (lane-parallel scan + reduction), or -1: optimal.
+template <class Ctx>
+HB_HD int wbc_most_violated(const Ctx& cx, const DevConfig& C, const WbcWork& W, const WbcState& st) {
+  double best = 0.0;
+  int bi = -1;
+  for (int c = st.wc.n_eq + cx.lane; c < st.wc.n_eq + st.wc.n_in; c += cx.nlanes) {
+    if (W.is_active[c]) continue;
+    int idx[3];
+    double cfv[3], rhs;
+    const int nn = sparse_row(st.wc, C, c, idx, cfv, &rhs);
+    double s = -rhs;
+    for (int t = 0; t < nn; ++t) s += cfv[t] * W.x[idx[t]];
+    if (s > 1e-9 * fmax(1.0, fabs(rhs)) && s > best) { best = s; bi = c; }
+  }
 #if defined(__HIP_DEVICE_COMPILE__)
-      // wave arg-max (DPP maximum + ballot, lowest lane on ties like the serial scan of the host version)
-      const double gb = wave_max_f64(best);
-      if (!(gb > 0.0)) break;  // optimal
-      p = __builtin_amdgcn_readlane(bi, __ffsll(__ballot(best == gb)) - 1);
+  // wave arg-max (DPP maximum + ballot, lowest lane on ties like the serial scan of the host version)
+  const double gb = wave_max_f64(best);
+  if (!(gb > 0.0)) return -1;
+  return __builtin_amdgcn_readlane(bi, __ffsll(__ballot(best == gb)) - 1);
 #else
-      red[cx.lane] = best;
-      cx.sync();
-      // serial arg-max over lane partials (nlanes <= 64)
-      double gb = 0.0;
-      int gl = -1;
-      for (int l = 0; l < cx.nlanes; ++l)
-        if (red[l] > gb) { gb = red[l]; gl = l; }
-      cx.sync();
-      if (gl < 0) break;  // optimal
-      if (cx.lane == gl) misc[1] = double(bi);
-      cx.sync();
-      p = int(misc[1]);
-      cx.sync();
+  W.red[cx.lane] = best;
+  cx.sync();
+  // serial arg-max over lane partials (nlanes <= 64)
+  double gb = 0.0;
+  int gl = -1;
+  for (int l = 0; l < cx.nlanes; ++l)
+    if (W.red[l] > gb) { gb = W.red[l]; gl = l; }
+  cx.sync();
+  if (gl < 0) return -1;
+  if (cx.lane == gl) W.misc[1] = double(bi);
+  cx.sync();
+  const int p = int(W.misc[1]);
+  cx.sync();
+  return p;
 #endif
-    }
+}
+
+// Phase C: Goldfarb–Idnani iterations over the inequalities, from the current point and working set, until none is violated.
+template <class Ctx>
+HB_HD void wbc_inequalities(const Ctx& cx, const DevConfig& C, const WbcWork& W, WbcState& st) {
+  const double inf = 1e300;
+  double* x = W.x;
+  double* d = W.d;
+  double* z = W.z;
+  double* r = W.r;
+  double* lam = W.lam;
+  while (st.status == 0) {
+    const int p = wbc_most_violated(cx, C, W, st);
+    if (p < 0) break;  // optimal
     // normal of p — an inequality (the equalities are all in): at most two non-zeros, kept as (index, coefficient) pairs;
     // every product with it (n'x, J'n, z'n, n'n) is one or two terms instead of a 38-term sum or a wave reduction
     double prhs;
     int pidx[3] = {0, 0, 0};
     double pcf[3] = {0.0, 0.0, 0.0};
-    const int pnn = sparse_row(wc, C, p, pidx, pcf, &prhs);
+    const int pnn = sparse_row(st.wc, C, p, pidx, pcf, &prhs);
     const int pi0 = pidx[0], pi1 = pnn > 1 ? pidx[1] : pidx[0];
     const double pc0 = pcf[0], pc1 = pnn > 1 ? pcf[1] : 0.0;
     double lam_p = 0.0;
     bool done_p = false;
     while (!done_p) {
-      if (++iter > C.wbc_max_iter) { status = HB_INST_MAXITER; break; }
+      if (++st.iter > C.wbc_max_iter) { st.status = HB_INST_MAXITER; break; }
       // sp = n'x - rhs ; d = J' n
-      // (four interleaved partial sums per dot product: a single f64 FMA chain leaves most issue slots empty on a wave
-      // that has its SIMD to itself)
-      for (int k = cx.lane; k < NW; k += cx.nlanes) d[k] = pc0 * Jm[pi0 * NW + k] + pc1 * Jm[pi1 * NW + k];
+      for (int k = cx.lane; k < NW; k += cx.nlanes) d[k] = pc0 * W.J[pi0 * NW + k] + pc1 * W.J[pi1 * NW + k];
       cx.sync();
-      sp = pc0 * x[pi0] + pc1 * x[pi1] - prhs;
+      const double sp = pc0 * x[pi0] + pc1 * x[pi1] - prhs;
       // z = J2 d2 ; r = R^-1 d1 (column-oriented back substitution on a copy)
-      // (fixed trip count with a uniform mask instead of a loop from q: the compiler unrolls it and batches the LDS
-      // reads; the rolled loop paid one LDS round trip per term on a wave that has its SIMD to itself)
       for (int i = cx.lane; i < NW; i += cx.nlanes) {
-        double sa[4] = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-        for (int j = 0; j < NW; ++j) {
-#if defined(__HIP_DEVICE_COMPILE__)
-          const double jij = jrow[j];
-#else
-          const double jij = Jm[i * NW + j];
-#endif
-          sa[j & 3] += jij * (j >= q ? d[j] : 0.0);
-        }
-        z[i] = (sa[0] + sa[1]) + (sa[2] + sa[3]);
-        if (i < q) r[i] = d[i];
+        z[i] = wbc_j2d2(W, st, i);
+        if (i < st.q) r[i] = d[i];
       }
       cx.sync();
-      // the dual step direction r = R^-1 d1 only matters for active INEQUALITIES (their multipliers must stay >= 0).  The
-      // equalities hold positions 0 .. next_eq_active - 1 of the active set for good and R is upper triangular, so the back
-      // substitution stops there: q - n_eq steps (0 .. 3 typically) instead of q (22 +), two ordering points each
-      const bool need_r = q > next_eq_active;
-      if (need_r)
-        for (int i = q - 1; i >= next_eq_active; --i) {
-          const double ri = r[i] / Rm[i * NW + i];
-          cx.sync();
-          for (int k = next_eq_active + cx.lane; k < i; k += cx.nlanes) r[k] -= Rm[k * NW + i] * ri;
-          if (cx.lane == 0) r[i] = ri;
-          cx.sync();
-        }
+      // the dual step direction r = R^-1 d1 only matters for active INEQUALITIES (their multipliers must stay >= 0)
+      const int q = st.q, n_eq_active = st.n_eq_active;
+      const bool need_r = q > n_eq_active;
+      if (need_r) wbc_backsolve_inequalities(cx, W, st, [&](int i, double ri) { r[i] = ri; });
       const double zn = pc0 * z[pi0] + pc1 * z[pi1], nn2 = pc0 * pc0 + pc1 * pc1;
       const double t2 = (zn > 1e-14 * (1.0 + nn2)) ? sp * rcp_t(zn) : inf;
       const double dir = 1.0;
       double t1 = inf;
       int l = -1;
-      for (int j = next_eq_active; j < q && need_r; ++j) {
+      for (int j = n_eq_active; j < q && need_r; ++j) {
         const double rj = dir * r[j];
         if (rj > 0.0) {
           const double tj = lam[j] / rj;
@@ -1169,84 +1101,83 @@ HB_HD void wbc_solve(const Ctx& cx, const DevModel& M, const DevConfig& C, const
       }
       const double t2abs = fabs(t2);
       const double t = fmin(t1, t2abs);
-      if (t >= inf) { status = HB_INST_INFEASIBLE; break; }
+      if (t >= inf) { st.status = HB_INST_INFEASIBLE; break; }
       cx.sync();
       if (t2 >= inf) {
         if (need_r)
-          for (int j = next_eq_active + cx.lane; j < q; j += cx.nlanes) lam[j] -= t * dir * r[j];
+          for (int j = n_eq_active + cx.lane; j < q; j += cx.nlanes) lam[j] -= t * dir * r[j];
         lam_p += t;
       } else {
         for (int k = cx.lane; k < NW; k += cx.nlanes) x[k] -= dir * t * z[k];
         if (need_r)
-          for (int j = next_eq_active + cx.lane; j < q; j += cx.nlanes) lam[j] -= t * dir * r[j];
+          for (int j = n_eq_active + cx.lane; j < q; j += cx.nlanes) lam[j] -= t * dir * r[j];
         lam_p += t;
       }
       cx.sync();
       if (t2 < inf && t == t2abs) {
         // full step: add constraint p
-        reflect(q);
-        if (fabs(d[q]) > 1e-13 * fmax(1.0, fabs(Rm[0]))) {
-          for (int i = cx.lane; i <= q; i += cx.nlanes) Rm[i * NW + q] = d[i];
-          if (cx.lane == 0) { act[q] = p; lam[q] = lam_p; is_active[p] = 1; }
-          ++q;
-        }
+        wbc_reflect(cx, W, st, q);
+        wbc_append_row(cx, W, st, p, lam_p);
         cx.sync();
         done_p = true;
       } else {
         // partial (or dual-only) step: drop active constraint l
-        if (cx.lane == 0) is_active[act[l]] = 0;
-        cx.sync();
-        for (int j = l; j < q - 1; ++j) {
-          for (int i = cx.lane; i <= j + 1; i += cx.nlanes) Rm[i * NW + j] = Rm[i * NW + j + 1];
-          if (cx.lane == 0) { act[j] = act[j + 1]; lam[j] = lam[j + 1]; }
-          cx.sync();
-        }
-        for (int i = cx.lane; i < q; i += cx.nlanes) Rm[i * NW + q - 1] = 0.0;
-        --q;
-        cx.sync();
-        for (int j = l; j < q; ++j) {
-          const double a = Rm[j * NW + j], b = Rm[(j + 1) * NW + j];
-          cx.sync();
-          if (b != 0.0) {
-            const double rh = rsqrt_t(a * a + b * b), cc = a * rh, ss = b * rh;
-            for (int k = cx.lane; k < NW; k += cx.nlanes) {
-              if (k >= j && k < q) {
-                const double t1j = Rm[j * NW + k], t2j = Rm[(j + 1) * NW + k];
-                Rm[j * NW + k] = cc * t1j + ss * t2j;
-                Rm[(j + 1) * NW + k] = -ss * t1j + cc * t2j;
-              }
-              const double u1 = Jm[k * NW + j], u2 = Jm[k * NW + j + 1];
-              Jm[k * NW + j] = cc * u1 + ss * u2;
-              Jm[k * NW + j + 1] = -ss * u1 + cc * u2;
-            }
-          }
-          cx.sync();
-          if (cx.lane == 0) Rm[(j + 1) * NW + j] = 0.0;
-          cx.sync();
-        }
-#if defined(__HIP_DEVICE_COMPILE__)
-#pragma unroll
-        for (int j = 0; j < NW; ++j) jrow[j] = cx.lane < NW ? Jm[cx.lane * NW + j] : 0.0;  // the rotations worked on the LDS copy
-#endif
+        drop_constraint(cx, NW, NW, W.R, W.J, W.act, lam, W.is_active, l, st.q);
+        wbc_load_jrow(cx, W, st);  // the rotations worked on the LDS copy
       }
     }
-    if (status != 0) break;
   }
-  }  // phase
+}
+
+// One WBC solve.  xdes/udes/rbd: this instance's inputs; sol in/out (kept when the QP fails).  The kCert instantiation also writes
+// the KKT certificate (cert [HB_WBC_CERT_SIZE]) and the dual solution (dual [HB_WBC_NCONS_MAX]) of this instance.
+template <class Ctx, bool kCert = false>
+HB_HD void wbc_solve(const Ctx& cx, const DevModel& M, const DevConfig& C, const double* xdes, const double* udes,
+                     const double* rbd, int mode, bool stance_mode, double* lds, double* sol, int* status_out,
+                     int* iters_out, double* cert = nullptr, double* dual = nullptr) {
+  const WbcWork W(lds);
+  WbcState st;
+  HB_WBC_MARK(0)
+  st.wc = wbc_cons_of_mode(mode);
+  st.stance_mode = stance_mode;
+  st.n_aw = stance_mode ? 6 : 3 * st.wc.n_sw + 6;
+  // ------------------------------------------------------------------ phase A: rigid-body quantities
+  static_assert(PHASE_A_WORK_DOUBLES <= NW * NW, "phase-A workspace must fit the J buffer");
+  wbc_phase_a(cx, M, C, xdes, udes, rbd, st.wc, stance_mode, C.w_swing, C.w_base, W.R, W.Ee, W.beom, W.Aw, W.bw, nullptr, nullptr, W.J);
+  if (cx.lane == 0) W.misc[0] = 0.0;  // status
+  cx.sync();
+  HB_WBC_MARK(1)
+  HB_ABLATE_STOP(C.debug_stop == 11 || (C.debug_stop >= 13 && C.debug_stop <= 15));
+  st.eps = wbc_eps(cx, C, W, st);
+  // ------------------------------------------------------------------ phase B: cost factor, unconstrained minimiser
+  wbc_cost_factor(cx, C, udes, W, st);
+  HB_ABLATE_STOP(C.debug_stop == 12);
+  // ------------------------------------------------------------------ phase C: Goldfarb–Idnani iterations
+  wbc_load_jrow(cx, W, st);
+  wbc_equality_block(cx, C, W, st);
+  // Phase 0 is the eps-regularised problem; every further phase is one regularisation step, after which the same loop goes on
+  for (int i = cx.lane; i < NW; i += cx.nlanes) W.xb[i] = 0.0;   // prox centre of the regularisation step before (x_{-1} = 0)
+  cx.sync();
+  const int n_reg = C.wbc_reg_steps > 0 ? C.wbc_reg_steps : 0;   // (phase 0 — the solve with every constraint — runs whatever the field holds)
+  for (int phase = 0; phase <= n_reg && st.status == 0; ++phase) {
+    if (phase > 0) wbc_regularisation_step(cx, W, st);
+    wbc_inequalities(cx, C, W, st);
+  }
   cx.sync();
   HB_WBC_MARK(6)
 #if defined(HB_ABLATE) && defined(__HIP_DEVICE_COMPILE__)
   if (C.debug_stop == 198 && blockIdx.x == 5 && cx.lane == 0)
     printf("wbc trace: phase A %lld | Householder of A_w %lld | J = R^-1, x0 %lld | equality block (%d rows) %lld | primal update %lld | inequalities (%d iterations) %lld | row 5: d = J'n %lld, reflector %lld  (cycles)\n",
-           wt_[1] - wt_[0], wt_[2] - wt_[1], wt_[3] - wt_[2], next_eq_active, wt_[4] - wt_[3], wt_[5] - wt_[4], iter - next_eq_active, wt_[6] - wt_[5], wt_[8] - wt_[7], wt_[9] - wt_[8]);
+           st.wt_[1] - st.wt_[0], st.wt_[2] - st.wt_[1], st.wt_[3] - st.wt_[2], st.n_eq_active, st.wt_[4] - st.wt_[3], st.wt_[5] - st.wt_[4], st.iter - st.n_eq_active, st.wt_[6] - st.wt_[5], st.wt_[8] - st.wt_[7], st.wt_[9] - st.wt_[8]);
 #endif
-  if (status == 0)
-    for (int i = cx.lane; i < NW; i += cx.nlanes) sol[i] = x[i];
+  // ------------------------------------------------------------------ write-out (the certificate while rows, point and working set are in LDS)
+  if (st.status == 0)
+    for (int i = cx.lane; i < NW; i += cx.nlanes) sol[i] = W.x[i];
   if (cx.lane == 0) {
-    *status_out = status;
-    *iters_out = iter;
+    *status_out = st.status;
+    *iters_out = st.iter;
   }
-  if constexpr (kCert) wbc_certificate(cx, C, wc, udes, stance_mode, n_aw, eps, status, lds, sol, cert, dual);
+  if constexpr (kCert) wbc_certificate(cx, C, st.wc, udes, stance_mode, st.n_aw, st.eps, st.status, W, sol, cert, dual);
 }
 
 // MPC_MRT_Interface::evaluatePolicy with a feed-forward controller: linear interpolation of the state and

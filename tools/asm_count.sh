@@ -3,8 +3,9 @@
 #   tools/asm_count.sh            whole kernel
 #   tools/asm_count.sh --phases   per phase (between the ordering points HB_ABLATE_STOP leaves; -DHB_PHASE_MARK names them by source line)
 cd "$(dirname "$0")/../hunter_bipedal_control_amd/csrc"
+. ./hipcc_flags.sh
 if [ "$1" = "--phases" ]; then shift; set -- -DHB_PHASE_MARK "$@"; fi
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -S --cuda-device-only -o /tmp/hb_k.s hb_kernels.hip "$@" 2>/dev/null
+$HIPCC $HB_HIPCC_FLAGS -S --cuda-device-only -o /tmp/hb_k.s hb_kernels.hip "$@" 2>/dev/null
 L=$(grep -n "^_ZN12_GLOBAL__N_14k_lqE" /tmp/hb_k.s | cut -d: -f1)
 sed -n "${L},\$p" /tmp/hb_k.s | awk '
 function flush(name) { printf "%-28s valu %5d salu %5d lds %4d vmem %4d mfma %3d\n", name, v, s, d, g, m; tv+=v; ts+=s; td+=d; tg+=g; tm+=m; v=s=d=g=m=0 }

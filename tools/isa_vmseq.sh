@@ -7,7 +7,9 @@
 set -e
 k=${1:?kernel name (substring of the mangled symbol)}
 d=$(mktemp -d)
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -mllvm -disable-machine-licm -fPIC -S --cuda-device-only -o $d/hb.s "$(dirname "$0")/../hunter_bipedal_control_amd/csrc/hb_kernels.hip" 2>/dev/null
+csrc="$(dirname "$0")/../hunter_bipedal_control_amd/csrc"
+. "$csrc/hipcc_flags.sh"
+$HIPCC $HB_HIPCC_FLAGS -S --cuda-device-only -o $d/hb.s "$csrc/hb_kernels.hip" 2>/dev/null
 python3 - "$d/hb.s" "$k" <<'P'
 import re, sys
 src, key = open(sys.argv[1]).read().split("\n"), sys.argv[2]
