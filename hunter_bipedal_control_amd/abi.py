@@ -216,3 +216,35 @@ def write_params_blob(params: dict, path) -> None:
         f.write(struct.pack(f"<{len(modes)}i", *modes))
         f.write(struct.pack(f"<{len(tt)}d", *tt))
         f.write(struct.pack(f"<{len(tm)}i", *tm))
+
+
+HB_GAIT_MAX_INIT_EVENTS, HB_GAIT_MAX_PHASES = 8, 8
+
+
+class HbGaitConfig(C.Structure):
+    """hb_gait_config (include/hunter_hip.h): the device-resident gait manager."""
+    _fields_ = [("phase_transition_stance_time", C.c_double), ("init_event_times", C.c_double * HB_GAIT_MAX_INIT_EVENTS),
+                ("template_switching_times", C.c_double * (HB_GAIT_MAX_PHASES + 1)), ("n_init_events", C.c_int32),
+                ("init_modes", C.c_int32 * (HB_GAIT_MAX_INIT_EVENTS + 1)), ("n_template_phases", C.c_int32),
+                ("template_modes", C.c_int32 * HB_GAIT_MAX_PHASES), ("filter_cmd", C.c_int32), ("reserved", C.c_int32)]
+
+
+def make_gait_config(params: dict, filter_cmd: bool = False) -> HbGaitConfig:
+    """initialModeSchedule / defaultModeSequenceTemplate / phaseTransitionStanceTime as ingest.read_config gives them.
+    filter_cmd: cmd_vel arguments are raw requests, rate-limited on the device once per pass."""
+    c = params["config"]
+    ev, modes = c["initial_mode_schedule"]["event_times"], c["initial_mode_schedule"]["modes"]
+    tt, tm = c["default_mode_template"]["switching_times"], c["default_mode_template"]["modes"]
+    if not (1 <= len(ev) <= HB_GAIT_MAX_INIT_EVENTS and len(modes) == len(ev) + 1):
+        raise ValueError("initial mode schedule: 1..8 event times and one more mode")
+    if not (1 <= len(tm) <= HB_GAIT_MAX_PHASES and len(tt) == len(tm) + 1):
+        raise ValueError("default mode-sequence template: 1..8 phases and one more switching time")
+    out = HbGaitConfig()
+    out.phase_transition_stance_time = c["phase_transition_stance_time"]
+    out.n_init_events, out.n_template_phases = len(ev), len(tm)
+    _fill(out.init_event_times, ev)
+    _fill(out.init_modes, modes)
+    _fill(out.template_switching_times, tt)
+    _fill(out.template_modes, tm)
+    out.filter_cmd = 1 if filter_cmd else 0
+    return out

@@ -17,6 +17,7 @@
 #include "hb_hoqp.hpp"
 #include "hb_estimator.hpp"
 #include "hb_refgen.hpp"
+#include "hb_gait.hpp"
 #include "hb_plant.hpp"
 
 using namespace hb;
@@ -1014,6 +1015,27 @@ struct RefgenBatch {
   int init_stance;  // take the current feet as latest stance positions (first update after a reset without state)
 };
 
+// gait manager (hb_gait.hpp), ahead of k_refgen when it is enabled: one thread per instance.  Reads the observation, the time and the
+// uploaded command of the pass; writes the window into the planner's schedule rows and the filtered command into the gait state.
+__global__ __launch_bounds__(64) void k_gait(Batch b, RefgenBatch r, GaitBatch g, hb_gait_config K, double horizon) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= g.B) return;
+  gait_pass(g, i, K, r.t0[i], horizon, b.x0 + size_t(i) * HB_NX, r.cmd + size_t(i) * 4, r.n_ev + i, r.ev + size_t(i) * HB_MAX_EVENTS,
+            r.modes + size_t(i) * (HB_MAX_EVENTS + 1));
+}
+__global__ __launch_bounds__(64) void k_gait_reset(GaitBatch g, hb_gait_config K, const unsigned char* __restrict__ mask) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= g.B || (mask && !mask[i])) return;
+  gait_reset_instance(g, i, K);
+}
+// hb_gait_insert_template: g is the view of the addressed instances
+__global__ __launch_bounds__(64) void k_gait_insert(GaitBatch g, double pts, int n_switch, const double* __restrict__ sw, const int* __restrict__ modes,
+                                                    const double* __restrict__ start, const double* __restrict__ final_time) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= g.B) return;
+  gait_insert_template(g, i, pts, n_switch, sw, modes, start[i], final_time[i]);
+}
+
 // planner step: FOUR lanes per instance, one per foot (refgen_plan: the four planner loops and the leg evaluations side by side; the lane
 // of foot 0 finishes with the shooting grid and the knots) — thread-per-instance the kernel was a 0.26 ms chain on 64 wavefronts
 __global__ __launch_bounds__(64) void k_refgen(Batch b, RefgenBatch r, const DevModel* __restrict__ M, hb_refgen_config K, double horizon) {
@@ -1239,6 +1261,10 @@ struct hb_ctx {
   hb_refgen_config rg_cfg{};
   bool rg_ready = false;
   std::vector<int> rg_have_schedule;
+  // device gait manager (allocated on the first hb_gait_reset); while gait_on, k_gait writes the schedule windows
+  GaitBatch gait{};
+  hb_gait_config gait_cfg{};
+  bool gait_on = false;
   // state estimator (allocated on the first hb_estimator_reset)
   EstBatch est{};
   hb_estimator_config est_cfg{};
@@ -1299,7 +1325,7 @@ static hipError_t dalloc(hb_ctx* ctx, T** p, size_t n) {
 
 extern "C" {
 
-int32_t hb_version(void) { return 101; }
+int32_t hb_version(void) { return 200; }
 
 const char* hb_last_error(const hb_ctx* ctx) { return ctx ? ctx->err.c_str() : g_create_error.c_str(); }
 
@@ -1676,6 +1702,10 @@ int32_t hb_refgen_set_schedule(hb_ctx* ctx, int32_t i0, int32_t cnt, const int32
     ctx->err = "hb_refgen_set_schedule: call hb_refgen_reset first";
     return HB_ERR_STATE;
   }
+  if (ctx->gait_on) {
+    ctx->err = "hb_refgen_set_schedule: the device gait manager writes the schedules (hb_gait_reset); call hb_gait_disable to supply them from the host";
+    return HB_ERR_STATE;
+  }
   for (int i = 0; i < cnt; ++i) {
     if (n_events[i] < 0 || n_events[i] > HB_MAX_EVENTS) {
       ctx->err = "hb_refgen_set_schedule: n_events out of range";
@@ -1738,6 +1768,14 @@ static RefgenBatch refgen_view(const RefgenBatch& r, int i0, int cnt) {
   v.knot_t += o * RG_MAX_KNOTS; v.knot_x += o * RG_MAX_KNOTS * HB_NX;
   return v;
 }
+static GaitBatch gait_view(const GaitBatch& g, int i0, int cnt) {
+  GaitBatch v = g;   // (slot-major arrays: the pitch stays the whole batch)
+  const size_t o = i0;
+  v.B = cnt;
+  v.n_ev += o; v.ev += o; v.modes += o; v.tpl_n += o; v.tpl_sw += o; v.tpl_modes += o; v.last_vel += o; v.cmd += o * 4; v.hist += o;
+  v.hist_n += o; v.hist_head += o; v.level += o; v.vel_abs += o; v.vel_avg += o; v.status += o;
+  return v;
+}
 
 // Before the node tables of b are overwritten while an iterate exists: keeps the grid that iterate lives on (`copy`; tp / modep /
 // np_nodes) and marks instances [i0, i0 + cnt) of b dirty, so that the next solve brings them onto the new tables (k_warm_shift).
@@ -1759,8 +1797,15 @@ static void launch_warm_start(const hb_ctx* ctx, const Batch& b, hipStream_t s) 
   hipLaunchKernelGGL(k_grid_clean, dim3((b.B + 255) / 256), dim3(256), 0, s, b);
 }
 
-// Reference generation of the instances of b / r: planner, joint IK (when configured), node tables.
-static void launch_refgen(const hb_ctx* ctx, const Batch& b, const RefgenBatch& r, double horizon, hipStream_t s) {
+// Reference generation of the instances of b / r (instances [i0, i0 + b.B) of the context): planner, joint IK (when configured), node
+// tables.  With the gait manager on, k_gait first: it writes the schedule window the planner reads, and the three kernels take the
+// filtered command of the gait state instead of the uploaded one.
+static void launch_refgen(const hb_ctx* ctx, const Batch& b, RefgenBatch r, int i0, double horizon, hipStream_t s) {
+  if (ctx->gait_on) {
+    const GaitBatch g = gait_view(ctx->gait, i0, b.B);
+    hipLaunchKernelGGL(k_gait, dim3((b.B + 63) / 64), dim3(64), 0, s, b, r, g, ctx->gait_cfg, horizon);
+    r.cmd = g.cmd;
+  }
   hipLaunchKernelGGL(k_refgen, dim3((4 * b.B + 63) / 64), dim3(64), 0, s, b, r, ctx->dmodel, ctx->rg_cfg, horizon);
   if (ctx->rg_cfg.joint_ik)
     hipLaunchKernelGGL(k_refgen_ik, dim3((2 * b.B + 7) / 8), dim3(64), 0, s, b, r, ctx->dmodel, ctx->rg_cfg, horizon);
@@ -1787,7 +1832,7 @@ int32_t hb_refgen_update(hb_ctx* ctx, const double* t0, double horizon, const do
     return HB_ERR_STATE;
   }
   for (int v : ctx->rg_have_schedule)
-    if (!v) {
+    if (!v && !ctx->gait_on) {
       ctx->err = "hb_refgen_update: an instance has no mode schedule (hb_refgen_set_schedule)";
       return HB_ERR_STATE;
     }
@@ -1805,7 +1850,7 @@ int32_t hb_refgen_update(hb_ctx* ctx, const double* t0, double horizon, const do
     HB_TRY(stage_upload(ctx, ST_CMD, r.cmd, cmd_vel, B * 4 * 8, s));
     if (x_now) HB_TRY(stage_upload(ctx, ST_X0, ctx->b.x0, x_now, B * HB_NX * 8, s));
   }
-  launch_refgen(ctx, ctx->b, r, horizon, s);
+  launch_refgen(ctx, ctx->b, r, 0, horizon, s);
   HB_HIP(hipGetLastError());
   r.init_stance = 0;
   if (status) {
@@ -1826,6 +1871,153 @@ int32_t hb_refgen_get_status(hb_ctx* ctx, int32_t* status) {
   HB_HIP(hipSetDevice(ctx->device));
   HB_HIP(hipMemcpyAsync(status, ctx->rg.status, size_t(ctx->B) * sizeof(int), hipMemcpyDeviceToHost, ctx->s_mpc));
   HB_HIP(hipStreamSynchronize(ctx->s_mpc));
+  return HB_OK;
+}
+
+int32_t hb_refgen_get_schedule(hb_ctx* ctx, int32_t i0, int32_t cnt, int32_t* n_events, double* event_times, int32_t* modes) {
+  if (ctx) lazy_join(ctx);
+  if (!ctx || i0 < 0 || cnt <= 0 || i0 > ctx->B || cnt > ctx->B - i0) return HB_ERR_ARG;
+  if (!ctx->rg_ready) {
+    ctx->err = "hb_refgen_get_schedule: call hb_refgen_reset first";
+    return HB_ERR_STATE;
+  }
+  HB_HIP(hipSetDevice(ctx->device));
+  HB_HIP(hipStreamSynchronize(ctx->s_mpc));
+  const RefgenBatch& r = ctx->rg;
+  const size_t o = i0, n = cnt;
+  if (n_events) HB_HIP(hipMemcpy(n_events, r.n_ev + o, n * sizeof(int), hipMemcpyDeviceToHost));
+  if (event_times) HB_HIP(hipMemcpy(event_times, r.ev + o * HB_MAX_EVENTS, n * HB_MAX_EVENTS * 8, hipMemcpyDeviceToHost));
+  if (modes) HB_HIP(hipMemcpy(modes, r.modes + o * (HB_MAX_EVENTS + 1), n * (HB_MAX_EVENTS + 1) * sizeof(int), hipMemcpyDeviceToHost));
+  return HB_OK;
+}
+
+// ---- device gait manager ------------------------------------------------------------------------------------------------------
+int32_t hb_gait_reset(hb_ctx* ctx, const hb_gait_config* cfg, const uint8_t* mask) {
+  if (ctx) lazy_join(ctx);
+  if (!ctx || !cfg) return HB_ERR_ARG;
+  bool ok = cfg->n_init_events >= 1 && cfg->n_init_events <= HB_GAIT_MAX_INIT_EVENTS && cfg->n_template_phases >= 1 &&
+            cfg->n_template_phases <= HB_GAIT_MAX_PHASES && cfg->phase_transition_stance_time >= 0.0 && (cfg->filter_cmd == 0 || cfg->filter_cmd == 1) &&
+            cfg->reserved == 0;
+  for (int k = 0; ok && k <= cfg->n_init_events; ++k) ok = cfg->init_modes[k] >= 0 && cfg->init_modes[k] <= 3;
+  for (int k = 0; ok && k + 1 < cfg->n_init_events; ++k) ok = cfg->init_event_times[k] < cfg->init_event_times[k + 1];
+  for (int k = 0; ok && k < cfg->n_template_phases; ++k)
+    ok = cfg->template_modes[k] >= 0 && cfg->template_modes[k] <= 3 && cfg->template_switching_times[k] < cfg->template_switching_times[k + 1];
+  if (!ok) {
+    ctx->err = "hb_gait_reset: hb_gait_config wants 1..8 strictly increasing initial events, a template of 1..8 phases with strictly increasing "
+               "switching times, modes in 0..3, phase_transition_stance_time >= 0, filter_cmd 0 / 1 and reserved = 0";
+    return HB_ERR_ARG;
+  }
+  if (!ctx->rg_ready) {
+    ctx->err = "hb_gait_reset: call hb_refgen_reset first";
+    return HB_ERR_STATE;
+  }
+  HB_HIP(hipSetDevice(ctx->device));
+  HB_TRY(hb_sync(ctx));
+  const size_t B = ctx->B;
+  GaitBatch& g = ctx->gait;
+  if (!g.n_ev) {
+    HB_HIP(dalloc(ctx, &g.n_ev, B));
+    HB_HIP(dalloc(ctx, &g.ev, B * HB_MAX_EVENTS));
+    HB_HIP(dalloc(ctx, &g.modes, B * (HB_MAX_EVENTS + 1)));
+    HB_HIP(dalloc(ctx, &g.tpl_n, B));
+    HB_HIP(dalloc(ctx, &g.tpl_sw, B * (HB_GAIT_MAX_PHASES + 1)));
+    HB_HIP(dalloc(ctx, &g.tpl_modes, B * HB_GAIT_MAX_PHASES));
+    HB_HIP(dalloc(ctx, &g.last_vel, B * 4));
+    HB_HIP(dalloc(ctx, &g.cmd, B * 4));
+    HB_HIP(dalloc(ctx, &g.hist, B * GAIT_HIST));
+    HB_HIP(dalloc(ctx, &g.hist_n, B));
+    HB_HIP(dalloc(ctx, &g.hist_head, B));
+    HB_HIP(dalloc(ctx, &g.level, B));
+    HB_HIP(dalloc(ctx, &g.vel_abs, B));
+    HB_HIP(dalloc(ctx, &g.vel_avg, B));
+    HB_HIP(dalloc(ctx, &g.status, B));
+    g.B = g.stride = ctx->B;
+    mask = nullptr;   // first use: every instance starts as a fresh object
+  }
+  DevBuf<unsigned char> dmask;
+  if (mask) HB_HIP(dmask.alloc(B, mask));
+  hipLaunchKernelGGL(k_gait_reset, dim3((ctx->B + 63) / 64), dim3(64), 0, ctx->s_mpc, g, *cfg, dmask.p);
+  HB_HIP(hipGetLastError());
+  HB_HIP(hipStreamSynchronize(ctx->s_mpc));
+  ctx->gait_cfg = *cfg;
+  if (!ctx->gait_on) {
+    ctx->gait_on = true;
+    ++ctx->graph_epoch;  // (as hb_wbc_set_certificate: what a range enqueues has changed)
+  }
+  return HB_OK;
+}
+
+int32_t hb_gait_disable(hb_ctx* ctx) {
+  if (ctx) lazy_join(ctx);
+  if (!ctx) return HB_ERR_ARG;
+  if (!ctx->gait_on) return HB_OK;
+  HB_HIP(hipSetDevice(ctx->device));
+  HB_TRY(hb_sync(ctx));
+  ctx->gait_on = false;
+  ++ctx->graph_epoch;
+  return HB_OK;
+}
+
+int32_t hb_gait_insert_template(hb_ctx* ctx, int32_t i0, int32_t cnt, int32_t n_switch, const double* switching_times, const int32_t* modes,
+                                const double* start, const double* final_time) {
+  if (ctx) lazy_join(ctx);
+  if (!ctx || !switching_times || !modes || !start || !final_time || i0 < 0 || cnt <= 0 || i0 > ctx->B || cnt > ctx->B - i0) return HB_ERR_ARG;
+  bool ok = n_switch >= 2 && n_switch <= HB_GAIT_MAX_PHASES + 1;
+  for (int k = 0; ok && k + 1 < n_switch; ++k) ok = modes[k] >= 0 && modes[k] <= 3 && switching_times[k] < switching_times[k + 1];
+  if (!ok) {
+    ctx->err = "hb_gait_insert_template: 2..9 strictly increasing switching times and modes in 0..3";
+    return HB_ERR_ARG;
+  }
+  if (!ctx->gait_on) {
+    ctx->err = "hb_gait_insert_template: the device gait manager is not enabled (hb_gait_reset)";
+    return HB_ERR_STATE;
+  }
+  HB_HIP(hipSetDevice(ctx->device));
+  HB_TRY(hb_sync(ctx));
+  DevBuf<double> dsw, dstart, dfinal;
+  DevBuf<int> dmodes;
+  HB_HIP(dsw.alloc(n_switch, switching_times));
+  HB_HIP(dmodes.alloc(n_switch - 1, modes));
+  HB_HIP(dstart.alloc(cnt, start));
+  HB_HIP(dfinal.alloc(cnt, final_time));
+  hipLaunchKernelGGL(k_gait_insert, dim3((cnt + 63) / 64), dim3(64), 0, ctx->s_mpc, gait_view(ctx->gait, i0, cnt), ctx->gait_cfg.phase_transition_stance_time,
+                     n_switch, dsw.p, dmodes.p, dstart.p, dfinal.p);
+  HB_HIP(hipGetLastError());
+  HB_HIP(hipStreamSynchronize(ctx->s_mpc));
+  return HB_OK;
+}
+
+int32_t hb_gait_get_state(hb_ctx* ctx, int32_t i0, int32_t cnt, int32_t* level, double* vel_abs, double* vel_avg, double* cmd, int32_t* n_events,
+                          double* event_times, int32_t* modes, int32_t* status) {
+  if (ctx) lazy_join(ctx);
+  if (!ctx || i0 < 0 || cnt <= 0 || i0 > ctx->B || cnt > ctx->B - i0) return HB_ERR_ARG;
+  if (!ctx->gait.n_ev) {
+    ctx->err = "hb_gait_get_state: call hb_gait_reset first";
+    return HB_ERR_STATE;
+  }
+  HB_HIP(hipSetDevice(ctx->device));
+  HB_HIP(hipStreamSynchronize(ctx->s_mpc));
+  const GaitBatch& g = ctx->gait;
+  const size_t o = i0, n = cnt, B = ctx->B;
+  if (level) HB_HIP(hipMemcpy(level, g.level + o, n * sizeof(int), hipMemcpyDeviceToHost));
+  if (vel_abs) HB_HIP(hipMemcpy(vel_abs, g.vel_abs + o, n * 8, hipMemcpyDeviceToHost));
+  if (vel_avg) HB_HIP(hipMemcpy(vel_avg, g.vel_avg + o, n * 8, hipMemcpyDeviceToHost));
+  if (cmd) HB_HIP(hipMemcpy(cmd, g.cmd + o * 4, n * 4 * 8, hipMemcpyDeviceToHost));
+  if (n_events) HB_HIP(hipMemcpy(n_events, g.n_ev + o, n * sizeof(int), hipMemcpyDeviceToHost));
+  if (status) HB_HIP(hipMemcpy(status, g.status + o, n * sizeof(int), hipMemcpyDeviceToHost));
+  // the schedule is slot-major on the device: rows of the addressed instances, slot by slot, transposed on the host
+  if (event_times) {
+    std::vector<double> tmp(size_t(HB_MAX_EVENTS) * n);
+    HB_HIP(hipMemcpy2D(tmp.data(), n * 8, g.ev + o, B * 8, n * 8, HB_MAX_EVENTS, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < n; ++i)
+      for (size_t k = 0; k < HB_MAX_EVENTS; ++k) event_times[i * HB_MAX_EVENTS + k] = tmp[k * n + i];
+  }
+  if (modes) {
+    std::vector<int> tmp(size_t(HB_MAX_EVENTS + 1) * n);
+    HB_HIP(hipMemcpy2D(tmp.data(), n * sizeof(int), g.modes + o, B * sizeof(int), n * sizeof(int), HB_MAX_EVENTS + 1, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < n; ++i)
+      for (size_t k = 0; k <= HB_MAX_EVENTS; ++k) modes[i * (HB_MAX_EVENTS + 1) + k] = tmp[k * n + i];
+  }
   return HB_OK;
 }
 
@@ -2682,7 +2874,7 @@ int32_t hb_tick_resident(hb_ctx* ctx, double dt_est, const double* quat, const d
     return HB_ERR_STATE;
   }
   for (int v : ctx->rg_have_schedule)
-    if (!v) {
+    if (!v && !ctx->gait_on) {
       ctx->err = "hb_tick_resident: an instance has no mode schedule (hb_refgen_set_schedule)";
       return HB_ERR_STATE;
     }
@@ -2729,7 +2921,7 @@ int32_t hb_tick_resident(hb_ctx* ctx, double dt_est, const double* quat, const d
     launch_estimator(ctx, e, dt_est, s);
     // reference generation at the new time (the grid that is about to be replaced is kept for the warm start)
     HB_TRY(launch_grid_save(ctx, b, true, 0, cnt, s));
-    launch_refgen(ctx, b, refgen_view(rg, i0, cnt), horizon, s);
+    launch_refgen(ctx, b, refgen_view(rg, i0, cnt), i0, horizon, s);
     HB_HIP(hipEventRecord(ctx->ev_consumed[c], s));  // the upload buffers are free for the next tick
     // warm start onto the new tables, MPC iteration, publish, policy evaluation, WBC
     launch_warm_start(ctx, b, s);

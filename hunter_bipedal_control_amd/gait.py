@@ -1,6 +1,7 @@
 """Host-side gait logic of the reference manager (row a20 of SURVEY.md §8 and the command / gait-selection state of a3):
-a few integers and event times per robot instance, kept on the host by design — its output, the mode schedule, is what
-``hb_refgen_set_schedule`` hands to the device.  Python mirror of the classes in ``include/hunter_hip.hpp``.
+a few integers and event times per robot instance — its output, the mode schedule, is what ``hb_refgen_set_schedule`` hands to
+the device.  Python mirror of the classes in ``include/hunter_hip.hpp``, and the host twin the device-resident gait manager
+(``hb_gait_reset``, csrc/hb_gait.hpp) is held to.
 
   * ``GaitSchedule``      legged_interface/src/gait/GaitSchedule.cpp:57-161 (insert / get / tile a mode-sequence template)
   * ``CmdVelFilter``      the per-callback rate limiter of the cmd_vel subscriber,

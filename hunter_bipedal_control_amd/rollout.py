@@ -120,12 +120,17 @@ class DeviceLoop:
 
 class ResidentLoop:
     """The same loop with the plant stub on the device too (hb_plant_step): nothing but the reference-generation time
-    stamps, the commands and the mode-schedule windows crosses PCIe."""
+    stamps, the commands and the mode-schedule windows crosses PCIe — and with device_gait not even the windows: the gait
+    scheduler and the command-driven gait selection (walkGait) run per instance on the device (hb_gait_reset)."""
 
     def __init__(self, solver, params: dict, gaits, cmd_vel, n_intervals: int = 100, mpc_every: int = 8, dt: float = 0.002,
-                 t_gait_start: float = 0.3, joint_ik: bool = True, substeps: int = 4, static_schedule_until: float = 0.0):
+                 t_gait_start: float = 0.3, joint_ik: bool = True, substeps: int = 4, static_schedule_until: float = 0.0,
+                 device_gait: bool = False):
         """static_schedule_until > 0: the mode schedules are uploaded once for [-1, static_schedule_until] (at most
-        HB_MAX_EVENTS events) instead of a sliding window per MPC call — no per-call host work for large batches."""
+        HB_MAX_EVENTS events) instead of a sliding window per MPC call — no per-call host work for large batches.
+        device_gait: the device gait manager produces the windows; step() builds no per-instance list and uploads no schedule, and
+        the gait of every instance follows its command as in the reference (set_cmd replaces the commands between steps).  `gaits`
+        other than the default "stance" go in once, at t_gait_start, through hb_gait_insert_template."""
         self.s, self.params, self.B = solver, params, solver.B
         self.horizon = n_intervals * params["config"]["dt"]
         self.dt, self.mpc_every, self.substeps = dt, mpc_every, substeps
@@ -133,7 +138,25 @@ class ResidentLoop:
         self.gains = abi.make_joint_gains()
         self.t, self.tick = 0.0, 0
         solver.refgen_reset(abi.make_refgen_config(params, joint_ik=joint_ik))
-        self.schedules = [gait.gait_schedule(params, g, t_gait_start, 1.0e3 if g == "stance" else 60.0) for g in gaits]
+        self.device_gait = device_gait
+        if device_gait:
+            if static_schedule_until > 0.0:
+                raise ValueError("static_schedule_until is a host-schedule option")
+            solver.gait_reset(abi.make_gait_config(params))
+            gaits, named = list(gaits), params["config"]["gaits"]
+            i = 0
+            while i < self.B:                                  # one call per run of instances with the same named gait
+                j = i
+                while j < self.B and gaits[j] == gaits[i]:
+                    j += 1
+                if gaits[i] != "stance":
+                    g = named[gaits[i]]
+                    solver.gait_insert_template(g["switching_times"], g["modes"], np.full(j - i, t_gait_start),
+                                                t_gait_start + self.horizon, inst_begin=i)
+                i = j
+            self.schedules = None
+        else:
+            self.schedules = [gait.gait_schedule(params, g, t_gait_start, 1.0e3 if g == "stance" else 60.0) for g in gaits]
         q0 = standing_configuration(params, self.B, solver)
         solver.plant_reset(q0)
         # resident observation of the initial state
@@ -145,11 +168,21 @@ class ResidentLoop:
         if self.static:
             solver.refgen_set_schedule([schedule_window(ms, -1.0, static_schedule_until) for ms in self.schedules])
 
-    def step(self):
+    def _windows(self):
+        """Host schedule path: the mode-schedule window of every instance for this MPC call."""
+        return [schedule_window(ms, self.t - 1.0, self.t + self.horizon + 1.5) for ms in self.schedules]
+
+    def set_cmd(self, cmd_vel):
+        """Replace the velocity commands [B][4] = (vx, vy, vz, yaw rate); they take effect at the next MPC call."""
+        self.cmd = np.ascontiguousarray(cmd_vel, dtype=float).reshape(self.B, 4)
+
+    def step(self, want_outputs: bool = False):
+        """want_outputs: the WBC result and the joint command of the tick come back to the host (self.last = dict(out, cmd), as
+        DeviceLoop keeps them) instead of staying on the device; the loop itself is the same."""
         s = self.s
         if self.tick % self.mpc_every == 0:
-            if not self.static:
-                s.refgen_set_schedule([schedule_window(ms, self.t - 1.0, self.t + self.horizon + 1.5) for ms in self.schedules])
+            if not self.static and not self.device_gait:
+                s.refgen_set_schedule(self._windows())
             status = s.refgen_update(np.full(self.B, self.t), self.horizon, None, self.cmd)
             if status.max() != 0:
                 raise RuntimeError(f"reference generation failed: {status}")
@@ -158,8 +191,11 @@ class ResidentLoop:
                 self.started = True
             s.mpc_solve(None)
             s.publish()
-        s.wbc_update_resident(self.dt)
-        s.joint_command_resident(self.gains, self.dt)
+        if want_outputs:
+            self.last = dict(out=s.wbc_update(None, None, dt=self.dt), cmd=s.joint_command(self.gains, self.dt))
+        else:
+            s.wbc_update_resident(self.dt)
+            s.joint_command_resident(self.gains, self.dt)
         s.plant_step(None, None, self.dt, self.substeps, to_resident=True)
         self.t += self.dt
         self.tick += 1

@@ -29,6 +29,7 @@ ABI_SYMBOLS = [
     "hb_plant_get_state", "hb_hoqp_solve", "hb_mpc_reset_masked", "hb_mpc_get_status", "hb_joint_set_flags",
     "hb_joint_get_emergency_stop", "hb_set_resident_time", "hb_get_wbc_iterations", "hb_ik_solve", "hb_debug_chunk_counters", "hb_debug_graph_state", "hb_refgen_get_status", "hb_tick_resident",
     "hb_wbc_set_certificate", "hb_wbc_get_certificate",
+    "hb_refgen_get_schedule", "hb_gait_reset", "hb_gait_disable", "hb_gait_insert_template", "hb_gait_get_state",
 ]
 # include/hunter_lcm.h
 LCM_SYMBOLS = ["hb_lcm_fingerprint", "hb_lcm_encoded_size", "hb_lcm_field_count", "hb_lcm_encode", "hb_lcm_decode", "hb_lcm_frame", "hb_lcm_unframe",
@@ -352,6 +353,44 @@ class HunterSolver:
         status = np.zeros(self.B, dtype=np.int32)
         self._check(self.lib.hb_refgen_get_status(self.ctx, _p(status)), "hb_refgen_get_status")
         return status
+
+    def refgen_schedule(self, inst_begin: int = 0, count: int | None = None):
+        """The mode-schedule windows the last reference-generation pass read (hb_refgen_get_schedule) -> list of gait.ModeSchedule."""
+        from .gait import ModeSchedule
+        count = self.B - inst_begin if count is None else int(count)
+        n = np.zeros(count, dtype=np.int32)
+        ev, modes = np.zeros((count, abi.HB_MAX_EVENTS)), np.zeros((count, abi.HB_MAX_EVENTS + 1), dtype=np.int32)
+        self._check(self.lib.hb_refgen_get_schedule(self.ctx, C.c_int32(inst_begin), C.c_int32(count), _p(n), _p(ev), _p(modes)), "hb_refgen_get_schedule")
+        return [ModeSchedule(ev[i, :n[i]].tolist(), modes[i, :n[i] + 1].tolist()) for i in range(count)]
+
+    # ---- device-resident gait manager (GaitSchedule + walkGait + the cmd_vel rate limiter per instance) -----------------
+    def gait_reset(self, gait_cfg: "abi.HbGaitConfig", mask=None):
+        """Enable the device gait manager and (re)initialise every instance, or those with mask[i] != 0 (hb_gait_reset)."""
+        m = None if mask is None else np.ascontiguousarray(np.asarray(mask) != 0, dtype=np.uint8).reshape(self.B)
+        self._check(self.lib.hb_gait_reset(self.ctx, C.byref(gait_cfg), _p(m)), "hb_gait_reset")
+
+    def gait_disable(self):
+        self._check(self.lib.hb_gait_disable(self.ctx), "hb_gait_disable")
+
+    def gait_insert_template(self, switching_times, modes, start, final, inst_begin: int = 0):
+        """insertModeSequenceTemplate(template, start[i], final[i]) for instances [inst_begin, inst_begin + len(start))."""
+        sw, md = _f64(switching_times), _i32(modes)
+        assert sw.ndim == 1 and md.shape == (sw.shape[0] - 1,)
+        start = _f64(np.atleast_1d(start))
+        final = _f64(np.broadcast_to(np.asarray(final, dtype=np.float64), start.shape))
+        self._check(self.lib.hb_gait_insert_template(self.ctx, C.c_int32(inst_begin), C.c_int32(start.shape[0]), C.c_int32(sw.shape[0]), _p(sw), _p(md),
+                                                     _p(start), _p(final)), "hb_gait_insert_template")
+
+    def gait_state(self, inst_begin: int = 0, count: int | None = None) -> dict:
+        """hb_gait_get_state: level, vel_abs, vel_avg, cmd [count][4] (filtered), the persistent schedule (n_events, event_times, modes) and
+        status, per instance."""
+        n = self.B - inst_begin if count is None else int(count)
+        out = dict(level=np.zeros(n, dtype=np.int32), vel_abs=np.zeros(n), vel_avg=np.zeros(n), cmd=np.zeros((n, 4)),
+                   n_events=np.zeros(n, dtype=np.int32), event_times=np.zeros((n, abi.HB_MAX_EVENTS)),
+                   modes=np.zeros((n, abi.HB_MAX_EVENTS + 1), dtype=np.int32), status=np.zeros(n, dtype=np.int32))
+        self._check(self.lib.hb_gait_get_state(self.ctx, C.c_int32(inst_begin), C.c_int32(n), *[_p(out[k]) for k in (
+            "level", "vel_abs", "vel_avg", "cmd", "n_events", "event_times", "modes", "status")]), "hb_gait_get_state")
+        return out
 
     def get_references(self):
         n = np.zeros(self.B, dtype=np.int32)

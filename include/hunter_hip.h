@@ -366,7 +366,8 @@ int32_t hb_estimator_get_filter(hb_ctx* ctx, double* x_hat, double* P);
  * 2-knot target from cmd_vel (TargetTrajectoriesPublisher.h:101-131), event-clipped shooting grid, swing planner
  * (footholds: SwingTrajectoryPlanner::calNextFootPos; x/y/z multi-node cubic splines: genSwingTrajs,
  * SwingTrajectoryPlanner.cpp:164-358).  The gait scheduler (GaitSchedule.cpp:57-161, a few integers and event times per
- * instance) stays on the host: its output, the mode schedule, is an input.  With joint_ik the targets are resampled
+ * instance) runs on the host by default — its output, the mode schedule, is an input (hb_refgen_set_schedule) — or on the device
+ * (hb_gait_reset, below).  With joint_ik the targets are resampled
  * every 0.15 s and their joint part replaced by the inverse kinematics of the planned foot positions
  * (calculateJointRef), warm-started knot to knot. */
 #define HB_MAX_EVENTS 64
@@ -395,6 +396,64 @@ int32_t hb_refgen_update(hb_ctx* ctx, const double* t0, double horizon, const do
                          int32_t* status);
 /* Status words of the last hb_refgen_update (synchronises). */
 int32_t hb_refgen_get_status(hb_ctx* ctx, int32_t* status /*[batch]*/);
+/* The mode-schedule window the last reference-generation pass read, for instances [inst_begin, inst_begin + inst_count): what
+ * hb_refgen_set_schedule uploaded, or, with the device gait manager on, what it wrote.  n_events [count], event_times
+ * [count][HB_MAX_EVENTS], modes [count][HB_MAX_EVENTS + 1]; any pointer may be NULL.  Synchronises. */
+int32_t hb_refgen_get_schedule(hb_ctx* ctx, int32_t inst_begin, int32_t inst_count, int32_t* n_events, double* event_times,
+                               int32_t* modes);
+
+/* ---- device-resident gait manager ---------------------------------------------------------------------------------
+ * The gait scheduler and the command-driven gait selection of the reference manager, per instance, on the device: GaitSchedule::
+ * {insertModeSequenceTemplate, getModeSchedule, tileModeSequenceTemplate} (legged_interface/src/gait/GaitSchedule.cpp:57-161),
+ * SwitchedModelReferenceManager::{calculateVelAbs, walkGait, findInsertModeSequenceTemplateTimer}
+ * (legged_interface/src/SwitchedModelReferenceManager.cpp:173-249, gaitType_ == 0) and the cmd_vel rate limiter
+ * (legged_controllers/include/legged_controllers/TargetTrajectoriesPublisher.h:97-129).  While it is enabled, every reference-generation
+ * pass (hb_refgen_update, hb_tick_resident) first runs one more kernel that, per instance and in the reference's order
+ * (SwitchedModelReferenceManager.cpp:145-158):
+ *   1. rate-limits the incoming request (filter_cmd = 1; limits 0.1, 0.05, -, 0.3 per pass, linear z forced to 0),
+ *   2. takes the window getModeSchedule(t0 - T, t0 + 2 T) of the instance's persistent schedule (T = horizon) — this is the mode
+ *      schedule the planner of the same pass reads,
+ *   3. evaluates calculateVelAbs on the first target state built from the observation and the filtered command, and the 50-sample
+ *      average velAvg_,
+ *   4. applies the walkGait thresholds (<= 0.02 level 0, (0.03, 0.4) level 1, >= 0.4 level 3),
+ *   5. on a level change to 0 / 1 inserts the stance / trot template at the first window event >= t0, up to t0 + T; it takes
+ *      effect from the next pass.  Level 3 inserts nothing; without a window event >= t0 the level changes and nothing is inserted.
+ * The reference-generation kernels then read the FILTERED command.  Event times are bit-identical to the host classes of
+ * hunter_hip.hpp / gait.py.  A schedule that would exceed HB_MAX_EVENTS events sets the instance's gait status to 1: its window stays
+ * as the previous pass wrote it and its gait state stops advancing until hb_gait_reset; other instances are unaffected.
+ * Not part of it: gaitType_ == 2 (trotGait), the /gait_type topic and the early / late-contact buffers. */
+#define HB_GAIT_MAX_INIT_EVENTS 8
+#define HB_GAIT_MAX_PHASES 8
+typedef struct hb_gait_config {
+  double phase_transition_stance_time;                      /* gait.info / task.info phaseTransitionStanceTime: one value per context */
+  double init_event_times[HB_GAIT_MAX_INIT_EVENTS];         /* initialModeSchedule: 1 <= n_init_events <= 8 strictly increasing times */
+  double template_switching_times[HB_GAIT_MAX_PHASES + 1];  /* defaultModeSequenceTemplate: n_template_phases + 1 increasing times */
+  int32_t n_init_events;
+  int32_t init_modes[HB_GAIT_MAX_INIT_EVENTS + 1];          /* n_init_events + 1 modes */
+  int32_t n_template_phases;                                /* 1..8 */
+  int32_t template_modes[HB_GAIT_MAX_PHASES];
+  int32_t filter_cmd;              /* 1: cmd_vel arguments are raw requests, rate-limited on the device once per pass; 0: already filtered */
+  int32_t reserved;                /* 0 */
+} hb_gait_config;
+/* Allocates on first use (that call initialises every instance), (re)initialises every instance — or, with mask [batch] != NULL, the
+ * instances with mask[i] != 0 — to a fresh
+ * reference object (the initial schedule and default template of cfg, gait level 0, empty velocity history, lastVel_ = 0, status 0) and
+ * enables the manager.  cfg's context-wide values (phase_transition_stance_time, filter_cmd) always take effect.  HB_ERR_STATE before
+ * hb_refgen_reset.  Enabling re-captures the range graphs. */
+int32_t hb_gait_reset(hb_ctx* ctx, const hb_gait_config* cfg, const uint8_t* mask);
+/* Back to host-supplied schedules (hb_refgen_set_schedule; the window of the last pass stays in place until then).  While the manager
+ * is enabled hb_refgen_set_schedule returns HB_ERR_STATE. */
+int32_t hb_gait_disable(hb_ctx* ctx);
+/* The direct form of insertModeSequenceTemplate(template, start[i], final[i]) for instances [inst_begin, inst_begin + inst_count):
+ * n_switch switching times (2..9) and n_switch - 1 modes — e.g. a named gait of gait.info.  The template becomes the instance's tiling
+ * template; the gait level is not touched.  Synchronises. */
+int32_t hb_gait_insert_template(hb_ctx* ctx, int32_t inst_begin, int32_t inst_count, int32_t n_switch, const double* switching_times,
+                                const int32_t* modes, const double* start /*[count]*/, const double* final_time /*[count]*/);
+/* Gait state of instances [inst_begin, inst_begin + inst_count) (any pointer may be NULL): level [count] (gaitLevel_), vel_abs / vel_avg
+ * [count], cmd [count][4] (the filtered command), the persistent schedule n_events [count], event_times [count][HB_MAX_EVENTS], modes
+ * [count][HB_MAX_EVENTS + 1], status [count] (0, or 1 after an overflow).  Synchronises. */
+int32_t hb_gait_get_state(hb_ctx* ctx, int32_t inst_begin, int32_t inst_count, int32_t* level, double* vel_abs, double* vel_avg,
+                          double* cmd, int32_t* n_events, double* event_times, int32_t* modes, int32_t* status);
 /* Node tables back to the host (any pointer may be NULL); layouts as in hb_mpc_set_references. */
 int32_t hb_mpc_get_references(hb_ctx* ctx, int32_t inst_begin, int32_t inst_count, int32_t* n_nodes, double* t,
                               int32_t* mode, double* x_ref, double* swing_ref);

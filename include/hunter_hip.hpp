@@ -95,11 +95,55 @@ class Context {
     check(hb_get_stats(ctx_.get(), &st), "hb_get_stats");
     return st;
   }
+  // device-resident gait manager (hunter_hip.h, hb_gait_reset): the per-instance GaitSchedule / walkGait / cmd_vel limiter on the device
+  void gaitReset(const hb_gait_config& cfg, const std::vector<uint8_t>* mask = nullptr) const {
+    if (mask && mask->size() != size_t(batch_)) throw std::invalid_argument("[hunter_hip] Context::gaitReset: one mask byte per instance");
+    check(hb_gait_reset(ctx_.get(), &cfg, mask ? mask->data() : nullptr), "hb_gait_reset");
+  }
+  void gaitDisable() const { check(hb_gait_disable(ctx_.get()), "hb_gait_disable"); }
+  // insertModeSequenceTemplate(switchingTimes / modes, start[i], final[i]) for instances [instBegin, instBegin + start.size())
+  void gaitInsertTemplate(int instBegin, const std::vector<double>& switchingTimes, const std::vector<int32_t>& modes, const std::vector<double>& start,
+                          const std::vector<double>& finalTime) const {
+    if (modes.size() + 1 != switchingTimes.size() || start.size() != finalTime.size())
+      throw std::invalid_argument("[hunter_hip] Context::gaitInsertTemplate: wrong vector size");
+    check(hb_gait_insert_template(ctx_.get(), instBegin, int32_t(start.size()), int32_t(switchingTimes.size()), switchingTimes.data(), modes.data(),
+                                  start.data(), finalTime.data()),
+          "hb_gait_insert_template");
+  }
+  std::vector<int32_t> gaitLevels() const {
+    std::vector<int32_t> level(static_cast<size_t>(batch_), 0);
+    check(hb_gait_get_state(ctx_.get(), 0, batch_, level.data(), nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr), "hb_gait_get_state");
+    return level;
+  }
+  std::vector<int32_t> gaitStatus() const {
+    std::vector<int32_t> st(static_cast<size_t>(batch_), 0);
+    check(hb_gait_get_state(ctx_.get(), 0, batch_, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, st.data()), "hb_gait_get_state");
+    return st;
+  }
 
  private:
   std::shared_ptr<hb_ctx> ctx_;
   int batch_, maxNodes_;
 };
+
+// hb_gait_config of the device gait manager from the ingested files: initialModeSchedule, defaultModeSequenceTemplate and
+// phaseTransitionStanceTime.  filterCmd: the cmd_vel arguments are raw requests, rate-limited on the device once per pass.
+inline hb_gait_config makeGaitConfig(const Parameters& p, bool filterCmd) {
+  if (p.initialEventTimes.empty() || p.initialEventTimes.size() > size_t(HB_GAIT_MAX_INIT_EVENTS) || p.initialModes.size() != p.initialEventTimes.size() + 1 ||
+      p.defaultTemplate.modes.empty() || p.defaultTemplate.modes.size() > size_t(HB_GAIT_MAX_PHASES) ||
+      p.defaultTemplate.switchingTimes.size() != p.defaultTemplate.modes.size() + 1)
+    throw std::invalid_argument("[hunter_hip] makeGaitConfig: 1..8 initial events and a default template of 1..8 phases expected");
+  hb_gait_config g{};
+  g.phase_transition_stance_time = p.phaseTransitionStanceTime;
+  g.n_init_events = int32_t(p.initialEventTimes.size());
+  for (size_t k = 0; k < p.initialEventTimes.size(); ++k) g.init_event_times[k] = p.initialEventTimes[k];
+  for (size_t k = 0; k < p.initialModes.size(); ++k) g.init_modes[k] = p.initialModes[k];
+  g.n_template_phases = int32_t(p.defaultTemplate.modes.size());
+  for (size_t k = 0; k < p.defaultTemplate.switchingTimes.size(); ++k) g.template_switching_times[k] = p.defaultTemplate.switchingTimes[k];
+  for (size_t k = 0; k < p.defaultTemplate.modes.size(); ++k) g.template_modes[k] = p.defaultTemplate.modes[k];
+  g.filter_cmd = filterCmd ? 1 : 0;
+  return g;
+}
 
 // ---- MPC side: the calls LeggedController makes on ocs2::MPC_MRT_Interface --------------------------------------
 class MpcMrtInterface {
@@ -409,6 +453,12 @@ class ReferenceManager {
     if (int(gaits_.size()) != ctx_.batch()) throw std::invalid_argument("[hunter_hip] one GaitSchedule per instance expected");
     ctx_.check(hb_refgen_reset(ctx_.get(), &settings, nullptr), "hb_refgen_reset");
   }
+  // The gait scheduler and the walk-gait selection on the device (hb_gait_reset): preSolverRun then does no per-instance host work and
+  // uploads no schedule; with cfg.filter_cmd = 1 its cmdVel are raw requests.  gaitSchedule() / gaitSelector() are not available.
+  ReferenceManager(Context ctx, const hb_refgen_config& settings, const hb_gait_config& gaitConfig) : ctx_(std::move(ctx)), deviceGait_(true) {
+    ctx_.check(hb_refgen_reset(ctx_.get(), &settings, nullptr), "hb_refgen_reset");
+    ctx_.gaitReset(gaitConfig);
+  }
   GaitSchedule& gaitSchedule(int instance) { return gaits_.at(size_t(instance)); }
   GaitSelector& gaitSelector(int instance) { return selectors_.at(size_t(instance)); }
   // gaitType_ == 0 of the reference (the default, /gait_type topic): the gait of every instance follows its averaged command
@@ -419,6 +469,7 @@ class ReferenceManager {
     const size_t B = size_t(ctx_.batch());
     if (initTime.size() != B || cmdVel.size() != B * 4 || (observation && observation->size() != B * HB_NX))
       throw std::invalid_argument("[hunter_hip] ReferenceManager::preSolverRun: wrong vector size");
+    if (deviceGait_) return refgenUpdate(initTime, timeHorizon, cmdVel, observation);
     std::vector<int32_t> nEvents(B), modes(B * (HB_MAX_EVENTS + 1), 3);
     vector_t events(B * HB_MAX_EVENTS, 0.0);
     for (size_t i = 0; i < B; ++i) {
@@ -434,6 +485,12 @@ class ReferenceManager {
       for (size_t e = 0; e < ms.modeSequence.size(); ++e) modes[i * (HB_MAX_EVENTS + 1) + e] = ms.modeSequence[e];
     }
     ctx_.check(hb_refgen_set_schedule(ctx_.get(), 0, ctx_.batch(), nEvents.data(), events.data(), modes.data()), "hb_refgen_set_schedule");
+    refgenUpdate(initTime, timeHorizon, cmdVel, observation);
+  }
+
+ private:
+  void refgenUpdate(const vector_t& initTime, scalar_t timeHorizon, const vector_t& cmdVel, const vector_t* observation) {
+    const size_t B = size_t(ctx_.batch());
     status_.resize(B);
     ctx_.check(hb_refgen_update(ctx_.get(), initTime.data(), timeHorizon, observation ? observation->data() : nullptr, cmdVel.data(),
                                 status_.data()),
@@ -442,8 +499,8 @@ class ReferenceManager {
       if (status_[i] != 0) throw std::runtime_error("[hunter_hip] reference generation failed for instance " + std::to_string(i));
   }
 
- private:
   Context ctx_;
+  bool deviceGait_ = false;
   std::vector<GaitSchedule> gaits_;
   std::vector<GaitSelector> selectors_;
   bool walkGait_ = false;
@@ -618,6 +675,29 @@ class ShardedSolver {
       for (size_t i = 0; i < n; ++i) obs[i].state.assign(states.begin() + (b + i) * HB_NX, states.begin() + (b + i + 1) * HB_NX);
       mpc_[size_t(g)].setCurrentObservation(obs);
     });
+  }
+  // device gait manager of every shard (Context::gaitReset & co. with the instance slicing); hb_refgen_reset per shard comes first
+  void gaitReset(const hb_gait_config& cfg) {
+    forEachShard([&](int g, size_t, size_t) { mpc_[size_t(g)].context().gaitReset(cfg); });
+  }
+  void gaitDisable() {
+    forEachShard([&](int g, size_t, size_t) { mpc_[size_t(g)].context().gaitDisable(); });
+  }
+  // start / finalTime [batch]
+  void gaitInsertTemplate(const std::vector<double>& switchingTimes, const std::vector<int32_t>& modes, const vector_t& start, const vector_t& finalTime) {
+    requireSize(start, size_t(batch_), "gaitInsertTemplate");
+    requireSize(finalTime, size_t(batch_), "gaitInsertTemplate");
+    forEachShard([&](int g, size_t b, size_t n) {
+      mpc_[size_t(g)].context().gaitInsertTemplate(0, switchingTimes, modes, slice(start, b, n, 1), slice(finalTime, b, n, 1));
+    });
+  }
+  std::vector<int32_t> gaitLevels() {
+    std::vector<int32_t> level(size_t(batch_), 0);
+    forEachShard([&](int g, size_t b, size_t) {
+      const std::vector<int32_t> l = mpc_[size_t(g)].context().gaitLevels();
+      std::copy(l.begin(), l.end(), level.begin() + b);
+    });
+    return level;
   }
   // MPC_MRT_Interface::advanceMpc on every device at once; returns the per-instance status words in instance order
   const std::vector<int32_t>& advanceMpc() {
