@@ -1045,15 +1045,327 @@ HB_HD int hwbc_level2(const Ctx& cx, const DevConfig& C, const HwbcRows& rows, c
   return rc;
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// Per-level optimality certificate of the cascade (hb_hwbc_set_certificate; layout HB_HWBC_CERT_* of hunter_hip.h).
+// The certificate instantiation of hwbc_solve keeps what the plain solve overwrites — the points after levels 0 and 1 and the final
+// working sets of the two small QPs — in a work area BEHIND the cascade's own LDS (layout HoCertLds, offsets from HoL::total), and
+// evaluates the certificate at the end of the solve, while the task rows, v0 and the kernel bases Z1 / Z2 are still in LDS.
+// The final working-set flags of small_lsqp, by inequality row, in its workspace ws (valid until the workspace is reused).
+HB_HD const int* small_lsqp_active_flags(const double* ws) { return reinterpret_cast<const int*>(ws + 360) + 12; }
+
+#if defined(__HIP_DEVICE_COMPILE__)
+#define HB_CERT_ROLLED _Pragma("unroll 1")   // the certificate is not time critical; unrolled, its loops over the task rows spill
+#else
+#define HB_CERT_ROLLED
+#endif
+struct HoCertLds {
+  static constexpr int xl = 0;               // 3 x 38: the solution after each level
+  static constexpr int act = xl + 3 * NW;    // 2 x 40 ints: working-set flags of levels 1 and 2
+  static constexpr int Q = act + 40;         // 38 x 12: orthonormal basis of the level's search space
+  static constexpr int g = Q + NW * 12;      // 38: A_k'(A_k x_k - b_k)
+  static constexpr int h = g + 40;           // 38: g - D'y
+  static constexpr int y = h + 40;           // 40: multipliers by inequality row
+  static constexpr int s = y + 40;           // 40: D x_k - f - v0
+  static constexpr int ro = s + 40;          // 28: A_k x_k - b_k
+  static constexpr int ax = ro + 28;         // 28: A_k x_k
+  static constexpr int M = ax + 28;          // 12 x 12: Q'D_W', reduced to its triangular factor in place
+  static constexpr int c = M + 144;          // 12: Q'g
+  static constexpr int rd = c + 12;          // 12: diagonal of the factor
+  static constexpr int rowc = rd + 12;       // 40 x 3: coefficients of the inequality rows
+  static constexpr int rowf = rowc + 120;    // 40: their right-hand sides
+  static constexpr int rowi = rowf + 40;     // 40 x 4 ints: their column indices and their count
+  static constexpr int wid = rowi + 80;      // 12 ints: rows of the working set
+  static constexpr int part = wid + 8;       // 64: lane partials of a reduction
+  static constexpr int total = part + 64;
+};
+static_assert((HoLdsDev::total + HoCertLds::total) * 8 <= 65536, "k_hwbc_cert: dynamic LDS without a function attribute");
+
+// `reached`: number of levels the cascade ran (3 unless a kernel basis was given up); n1 / n2: columns of Z1 / Z2 (where reached).
+// A level that was not reached is judged at the returned sol with no multipliers and the unprojected gradient.
+// Everything is evaluated without the Tikhonov terms and without the 1e-12 Hessian shift: the reference's problem, not ours.
 template <class Ctx>
-HB_HD void hwbc_solve(const Ctx& cx, const DevModel& M, const DevConfig& C, const double* xdes, const double* udes,
-                      const double* rbd, int mode, double* lds, double* sol, int* status_out, int max_level = 3) {
-  const HwbcWork W(lds);
-  const HwbcRows rows{wbc_cons_of_mode(mode), W.Ee, W.beom, W.Jc, W.dJv};
+HB_HD void hwbc_certificate(const Ctx& cx, const DevConfig& C, const HwbcRows& rows, const HwbcWork& W, const double* udes, const double* sol,
+                            int reached, int n1, int n2, double* E, double* cert, double* x_levels, double* slack0, double* dual) {
+  double* xl = E + HoCertLds::xl;
+  const int* act = reinterpret_cast<const int*>(E + HoCertLds::act);
+  double* Q = E + HoCertLds::Q;
+  double* g = E + HoCertLds::g;
+  double* h = E + HoCertLds::h;
+  double* y = E + HoCertLds::y;
+  double* sr = E + HoCertLds::s;
+  double* ro = E + HoCertLds::ro;
+  double* ax = E + HoCertLds::ax;
+  double* Mq = E + HoCertLds::M;
+  double* cq = E + HoCertLds::c;
+  double* rd = E + HoCertLds::rd;
+  double* rowc = E + HoCertLds::rowc;
+  double* rowf = E + HoCertLds::rowf;
+  int* rowi = reinterpret_cast<int*>(E + HoCertLds::rowi);
+  int* wid = reinterpret_cast<int*>(E + HoCertLds::wid);
+  double* part = E + HoCertLds::part;
+  const WbcCons& wc = rows.wc;
+  const int n_in = wc.n_in, n_sw = wc.n_sw;
+  const double* A1 = W.Aw + 3 * n_sw * 16;
+  const double* b1 = W.bw + 3 * n_sw;
+  // rows of the tasks (HierarchicalWbc.cpp:23-27): level 0 through HwbcRows, level 1 the base acceleration, level 2 0.1 * contact
+  // force + swing legs
+  auto a_of = [&](int k, int r, int col) -> double {
+    if (k == 0) return rows.a0(r, col);
+    if (k == 1) return col < 16 ? A1[r * 16 + col] : 0.0;
+    if (r < 12) return col == 16 + r ? 0.1 : 0.0;
+    return col < 16 ? W.Aw[(r - 12) * 16 + col] : 0.0;
+  };
+  auto b_of = [&](int k, int r) -> double {
+    if (k == 0) return rows.b0(r);
+    if (k == 1) return b1[r];
+    return r < 12 ? 0.1 * udes[r] : W.bw[r - 12];
+  };
+  auto sum_of = [&](double v) -> double {
+    cx.sync();
+    part[cx.lane] = v;
+    cx.sync();
+    double t = 0.0;
+    HB_CERT_ROLLED
+    for (int l = 0; l < cx.nlanes; ++l) t += part[l];
+    return t;
+  };
+  auto max_of = [&](double v) -> double {
+    cx.sync();
+    part[cx.lane] = v;
+    cx.sync();
+    double t = part[0];
+    HB_CERT_ROLLED
+    for (int l = 1; l < cx.nlanes; ++l) t = fmax(t, part[l]);
+    return t;
+  };
+  // the points of the levels that were not reached, and the inequality rows as (index, coefficient) lists
+  for (int idx = cx.lane; idx < 3 * NW; idx += cx.nlanes) {
+    const int k = idx / NW, i = idx - NW * k;
+    if (k >= reached) xl[idx] = sol[i];
+    else if (k == 2) xl[idx] = W.x[i];
+  }
+  for (int c = cx.lane; c < n_in; c += cx.nlanes) {
+    int ix[3];
+    double cfv[3], rh;
+    const int nn = sparse_row(wc, C, wc.n_eq + c, ix, cfv, &rh);
+    for (int t = 0; t < 3; ++t) { rowi[4 * c + t] = t < nn ? ix[t] : 0; rowc[3 * c + t] = t < nn ? cfv[t] : 0.0; }
+    rowi[4 * c + 3] = nn;
+    rowf[c] = rh;
+  }
+  cx.sync();
+  const double* x2 = xl + 2 * NW;
+  HB_CERT_ROLLED
+  for (int k = 0; k < HB_HWBC_LEVELS; ++k) {
+    const double* xk = xl + k * NW;
+    const bool run = k < reached;
+    const int nk = k == 0 ? NW : (run ? (k == 1 ? n1 : n2) : 0);
+    const int mk = k == 0 ? rows.mA0() : (k == 1 ? 6 : 12 + 3 * n_sw);
+    // residual of the task at its own optimum and at the returned solution
+    double p_own = 0.0, p_fin = 0.0;
+    for (int r = cx.lane; r < mk; r += cx.nlanes) {
+      double s1 = 0.0, s2 = 0.0;
+      HB_CERT_ROLLED
+      for (int i = 0; i < NW; ++i) { const double a = a_of(k, r, i); s1 += a * xk[i]; s2 += a * x2[i]; }
+      const double b = b_of(k, r);
+      ax[r] = s1;
+      ro[r] = s1 - b;
+      p_own += (s1 - b) * (s1 - b);
+      p_fin += (s2 - b) * (s2 - b);
+    }
+    const double res_own = sqrt(sum_of(p_own)), res_fin = sqrt(sum_of(p_fin));
+    // gradient (formed from the residual: no cancellation between A'A x and A'b) and scale
+    double p_sc = 1.0;
+    for (int i = cx.lane; i < NW; i += cx.nlanes) {
+      double gi = 0.0, atb = 0.0, atax = 0.0;
+      HB_CERT_ROLLED
+      for (int r = 0; r < mk; ++r) { const double a = a_of(k, r, i); gi += a * ro[r]; atb += a * b_of(k, r); atax += a * ax[r]; }
+      g[i] = gi;
+      p_sc = fmax(p_sc, fmax(fabs(atb), fabs(atax)));
+    }
+    const double scale = max_of(p_sc);
+    // inequality rows against the frozen level-0 slack; multipliers of level 0: the slack itself
+    double p_in = 0.0, p_cnt = 0.0;
+    for (int c = cx.lane; c < HB_HWBC_NINEQ_MAX; c += cx.nlanes) {
+      double s = 0.0, yc = 0.0;
+      if (c < n_in) {
+        s = -rowf[c] - W.v0[c];
+        HB_CERT_ROLLED
+        for (int t = 0; t < rowi[4 * c + 3]; ++t) s += rowc[3 * c + t] * xk[rowi[4 * c + t]];
+        if (k == 0) { yc = -W.v0[c]; p_cnt += W.v0[c] > 0.0 ? 1.0 : 0.0; }
+        p_in = fmax(p_in, s);
+      }
+      sr[c] = s;
+      y[c] = yc;
+    }
+    const double r_in = max_of(p_in);
+    int m = 0;
+    if (k == 0) m = int(sum_of(p_cnt));
+    cx.sync();
+    if (k > 0 && run && nk > 0) {
+      // Q: thin QR of the kernel basis by modified Gram–Schmidt, twice; one column per lane in the projections
+      const double* Z = k == 1 ? W.Z1 : W.Z2;
+      for (int idx = cx.lane; idx < NW * 12; idx += cx.nlanes) Q[idx] = Z[idx];
+      cx.sync();
+      for (int pass = 0; pass < 2; ++pass)
+        for (int j = 0; j < nk; ++j) {
+          double nn = 0.0;
+          HB_CERT_ROLLED
+          for (int i = 0; i < NW; ++i) nn += Q[i * 12 + j] * Q[i * 12 + j];
+          const double rn = nn > 0.0 ? 1.0 / sqrt(nn) : 0.0;
+          cx.sync();
+          for (int i = cx.lane; i < NW; i += cx.nlanes) Q[i * 12 + j] *= rn;
+          cx.sync();
+          for (int c = j + 1 + cx.lane; c < nk; c += cx.nlanes) {
+            double dot = 0.0;
+            HB_CERT_ROLLED
+            for (int i = 0; i < NW; ++i) dot += Q[i * 12 + j] * Q[i * 12 + c];
+            HB_CERT_ROLLED
+            for (int i = 0; i < NW; ++i) Q[i * 12 + c] -= dot * Q[i * 12 + j];
+          }
+          cx.sync();
+        }
+      // working set in row order (every lane walks the same flags: m is uniform)
+      const int* fl = act + 40 * (k - 1);
+      HB_CERT_ROLLED
+      for (int c = 0; c < n_in; ++c)
+        if (fl[c] && m < nk) {
+          if (cx.lane == 0) wid[m] = c;
+          ++m;
+        }
+      cx.sync();
+      // y_W = argmin |Q'(g - D_W'y_W)|_2 by Householder QR of Q'D_W' (nk x m), the right-hand side carried along as column m
+      for (int idx = cx.lane; idx < nk * 12; idx += cx.nlanes) {
+        const int j = idx / 12, w = idx - 12 * j;
+        double s = 0.0;
+        if (w < m) {
+          const int c = wid[w];
+          HB_CERT_ROLLED
+          for (int t = 0; t < rowi[4 * c + 3]; ++t) s += rowc[3 * c + t] * Q[rowi[4 * c + t] * 12 + j];
+        }
+        Mq[idx] = s;
+      }
+      for (int j = cx.lane; j < nk; j += cx.nlanes) {
+        double s = 0.0;
+        HB_CERT_ROLLED
+        for (int i = 0; i < NW; ++i) s += Q[i * 12 + j] * g[i];
+        cq[j] = s;
+      }
+      cx.sync();
+      for (int kk = 0; kk < m; ++kk) {
+        double nrm2 = 0.0;
+        HB_CERT_ROLLED
+        for (int i = kk; i < nk; ++i) nrm2 += Mq[i * 12 + kk] * Mq[i * 12 + kk];
+        const double akk = Mq[kk * 12 + kk];
+        const double alpha = akk > 0.0 ? -sqrt(nrm2) : sqrt(nrm2);
+        const double v0 = akk - alpha;
+        const double vtv = nrm2 - akk * akk + v0 * v0;
+        if (vtv > 0.0) {
+          const double beta = 2.0 / vtv;
+          for (int j = kk + 1 + cx.lane; j <= m; j += cx.nlanes) {
+            double* col = j < m ? Mq + j : cq;
+            const int st = j < m ? 12 : 1;
+            double s = v0 * col[kk * st];
+            HB_CERT_ROLLED
+            for (int i = kk + 1; i < nk; ++i) s += Mq[i * 12 + kk] * col[i * st];
+            s *= beta;
+            col[kk * st] -= s * v0;
+            HB_CERT_ROLLED
+            for (int i = kk + 1; i < nk; ++i) col[i * st] -= s * Mq[i * 12 + kk];
+          }
+        }
+        cx.sync();
+        if (cx.lane == 0) rd[kk] = alpha;
+      }
+      cx.sync();
+      for (int kk = m - 1; kk >= 0; --kk) {
+        const double yk = rd[kk] != 0.0 ? cq[kk] / rd[kk] : 0.0;
+        cx.sync();
+        for (int i = cx.lane; i < kk; i += cx.nlanes) cq[i] -= Mq[i * 12 + kk] * yk;
+        if (cx.lane == 0) y[wid[kk]] = yk;
+        cx.sync();
+      }
+    }
+    // stationarity in the level's search space, sign and complementarity of the multipliers
+    for (int i = cx.lane; i < NW; i += cx.nlanes) {
+      double s = g[i];
+      HB_CERT_ROLLED
+      for (int c = 0; c < n_in; ++c)
+        if (y[c] != 0.0)
+          HB_CERT_ROLLED
+          for (int t = 0; t < rowi[4 * c + 3]; ++t)
+            if (rowi[4 * c + t] == i) s -= rowc[3 * c + t] * y[c];
+      h[i] = s;
+    }
+    cx.sync();
+    double p_st = 0.0;
+    if (k == 0 || !run) {
+      for (int i = cx.lane; i < NW; i += cx.nlanes) p_st += h[i] * h[i];
+    } else {
+      for (int j = cx.lane; j < nk; j += cx.nlanes) {
+        double s = 0.0;
+        HB_CERT_ROLLED
+        for (int i = 0; i < NW; ++i) s += Q[i * 12 + j] * h[i];
+        p_st += s * s;
+      }
+    }
+    const double r_stat = sqrt(sum_of(p_st));
+    double p_du = 0.0, p_co = 0.0;
+    for (int c = cx.lane; c < n_in; c += cx.nlanes) {
+      p_du = fmax(p_du, y[c]);
+      p_co = fmax(p_co, fabs(y[c] * sr[c]));
+    }
+    const double r_dual = max_of(p_du), r_comp = max_of(p_co);
+    // the step of this level seen by every higher task
+    double p_hi = 0.0;
+    if (k > 0) {
+      const double* xp = xl + (k - 1) * NW;
+      for (int r = cx.lane; r < rows.mA0() + (k == 2 ? 6 : 0); r += cx.nlanes) {
+        const int kj = r < rows.mA0() ? 0 : 1, rr = kj == 0 ? r : r - rows.mA0();
+        double s = 0.0;
+        HB_CERT_ROLLED
+        for (int i = 0; i < NW; ++i) s += a_of(kj, rr, i) * (xk[i] - xp[i]);
+        p_hi = fmax(p_hi, fabs(s));
+      }
+    }
+    const double r_hier = max_of(p_hi);
+    if (cx.lane == 0) {
+      double* ck = cert + k * HB_HWBC_CERT_SIZE;
+      ck[HB_HWBC_CERT_RES_OWN] = res_own;
+      ck[HB_HWBC_CERT_RES_FINAL] = res_fin;
+      ck[HB_HWBC_CERT_R_HIER] = r_hier;
+      ck[HB_HWBC_CERT_R_IN] = r_in;
+      ck[HB_HWBC_CERT_R_STAT] = r_stat;
+      ck[HB_HWBC_CERT_R_DUAL] = r_dual;
+      ck[HB_HWBC_CERT_R_COMP] = r_comp;
+      ck[HB_HWBC_CERT_N_FREE] = double(nk);
+      ck[HB_HWBC_CERT_N_ACTIVE] = double(m);
+      ck[HB_HWBC_CERT_SCALE] = scale;
+    }
+    for (int c = cx.lane; c < HB_HWBC_NINEQ_MAX; c += cx.nlanes) dual[k * HB_HWBC_NINEQ_MAX + c] = y[c];
+    for (int i = cx.lane; i < NW; i += cx.nlanes) x_levels[k * NW + i] = xk[i];
+    cx.sync();
+  }
+  for (int c = cx.lane; c < HB_HWBC_NINEQ_MAX; c += cx.nlanes) slack0[c] = c < n_in ? W.v0[c] : 0.0;
+}
+
+// One cascade solve.  sol in/out (kept when a kernel basis is given up).  The kCert instantiation also keeps, in the certificate's work
+// area E, the points after levels 0 and 1 and the working sets of the QPs of levels 1 and 2, and reports how far the cascade came
+// (reached: levels run; n1c / n2c: columns of Z1 / Z2).
+template <class Ctx, bool kCert>
+HB_HD void hwbc_cascade(const Ctx& cx, const DevModel& M, const DevConfig& C, const double* xdes, const double* udes, const double* rbd,
+                        const HwbcRows& rows, const HwbcWork& W, double* sol, int* status_out, int max_level, double* E, int& reached,
+                        int& n1c, int& n2c) {
   wbc_phase_a(cx, M, C, xdes, udes, rbd, rows.wc, false, 1.0, 1.0, W.R, W.Ee, W.beom, W.Aw, W.bw, W.Jc, W.dJv, W.J);
   for (int c = cx.lane; c < 40; c += cx.nlanes) W.viol[c] = 0;
   cx.sync();
   int status = hwbc_level0(cx, C, rows, W);
+  int* act = reinterpret_cast<int*>(E + HoCertLds::act);
+  if constexpr (kCert) {
+    for (int i = cx.lane; i < NW; i += cx.nlanes) E[HoCertLds::xl + i] = W.x[i];
+    for (int c = cx.lane; c < 80; c += cx.nlanes) act[c] = 0;
+    cx.sync();
+    reached = 1;
+  }
   if (max_level > 1) {
     const int n1 = hwbc_level0_kernel(cx, rows, W);
     if (n1 < 0) {
@@ -1063,6 +1375,15 @@ HB_HD void hwbc_solve(const Ctx& cx, const DevModel& M, const DevConfig& C, cons
     HB_ABLATE_STOP(C.debug_stop == 43);  // profiling ablation: level 0 + kernel basis
     const int rc1 = hwbc_level1(cx, C, rows, W, n1);
     if (rc1 > status) status = rc1;
+    if constexpr (kCert) {
+      // the point after level 1 and the working set of its QP, before level 2 reuses the workspace
+      cx.sync();
+      for (int i = cx.lane; i < NW; i += cx.nlanes) E[HoCertLds::xl + NW + i] = W.x[i];
+      for (int c = cx.lane; c < rows.wc.n_in; c += cx.nlanes) act[c] = small_lsqp_active_flags(W.qpw)[c];
+      cx.sync();
+      reached = 2;
+      n1c = n1;
+    }
     HB_ABLATE_STOP(C.debug_stop == 44);  // profiling ablation: ... + level-1 QP
     const int n2 = hwbc_level1_kernel(cx, W, n1);
     if (n2 < 0) {
@@ -1072,10 +1393,34 @@ HB_HD void hwbc_solve(const Ctx& cx, const DevModel& M, const DevConfig& C, cons
     if (n2 > 0 && max_level >= 3) {
       const int rc2 = hwbc_level2(cx, C, rows, W, udes, n2);
       if (rc2 > status) status = rc2;
+      if constexpr (kCert) {
+        for (int c = cx.lane; c < rows.wc.n_in; c += cx.nlanes) act[40 + c] = small_lsqp_active_flags(W.qpw)[c];
+        cx.sync();
+        n2c = n2;
+      }
     }
   }
   for (int i = cx.lane; i < NW; i += cx.nlanes) sol[i] = W.x[i];
   if (cx.lane == 0) *status_out = status;
+  if constexpr (kCert) reached = 3;
+}
+
+// The kCert instantiation also writes the per-level certificate (cert [3][HB_HWBC_CERT_SIZE]), the solution after each level
+// (x_levels [3][38]), the level-0 slack (slack0 [40]) and the multipliers (dual [3][40]) of this instance; its LDS is
+// HoL::total + HoCertLds::total doubles.
+template <class Ctx, bool kCert = false>
+HB_HD void hwbc_solve(const Ctx& cx, const DevModel& M, const DevConfig& C, const double* xdes, const double* udes,
+                      const double* rbd, int mode, double* lds, double* sol, int* status_out, int max_level = 3, double* cert = nullptr,
+                      double* x_levels = nullptr, double* slack0 = nullptr, double* dual = nullptr) {
+  const HwbcWork W(lds);
+  const HwbcRows rows{wbc_cons_of_mode(mode), W.Ee, W.beom, W.Jc, W.dJv};
+  double* E = lds + HoL::total;   // (certificate instantiation only: its work area lies behind the cascade's)
+  int reached = 0, n1 = 0, n2 = 0;
+  hwbc_cascade<Ctx, kCert>(cx, M, C, xdes, udes, rbd, rows, W, sol, status_out, max_level, E, reached, n1, n2);
+  if constexpr (kCert) {
+    cx.sync();
+    hwbc_certificate(cx, C, rows, W, udes, sol, reached, n1, n2, E, cert, x_levels, slack0, dual);
+  }
 }
 
 #if defined(__HIPCC__)
@@ -1100,6 +1445,20 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) void
   // hb_config.reserved = 41 / 42 stops the cascade after level 0 / 1 (profiling ablation only)
   hwbc_solve(WbcDeviceCtx(), *M, *C, w.xdes + size_t(inst) * HB_NX, w.udes + size_t(inst) * HB_NU, w.rbd + size_t(inst) * HB_NRBD,
              w.mode[inst], lds_h, w.sol + size_t(inst) * NW, w.status + inst, (HB_ABLATE_ON && C->debug_stop == 41) ? 1 : ((HB_ABLATE_ON && C->debug_stop == 42) ? 2 : 3));
+  if (threadIdx.x == 0) w.iters[inst] = 0;
+}
+// k_hwbc with the per-level certificate (hb_hwbc_set_certificate): the same solve, then the certificate, the per-level solutions, the
+// level-0 slack and the multipliers of the instance (all already offset to the launch's first instance).  Dynamic LDS:
+// (HoLdsDev::total + HoCertLds::total) doubles.
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) void k_hwbc_cert(WbcBatch w, const DevModel* __restrict__ M, const DevConfig* __restrict__ C,
+                                                                                              double* cert, double* x_levels, double* slack0, double* dual) {
+  __builtin_amdgcn_s_setprio(3);
+  const int inst = blockIdx.x;
+  extern __shared__ __attribute__((aligned(16))) double lds_h[];
+  hwbc_solve<WbcDeviceCtx, true>(WbcDeviceCtx(), *M, *C, w.xdes + size_t(inst) * HB_NX, w.udes + size_t(inst) * HB_NU, w.rbd + size_t(inst) * HB_NRBD,
+                                 w.mode[inst], lds_h, w.sol + size_t(inst) * NW, w.status + inst, 3,
+                                 cert + size_t(inst) * HB_HWBC_LEVELS * HB_HWBC_CERT_SIZE, x_levels + size_t(inst) * HB_HWBC_LEVELS * NW,
+                                 slack0 + size_t(inst) * HB_HWBC_NINEQ_MAX, dual + size_t(inst) * HB_HWBC_LEVELS * HB_HWBC_NINEQ_MAX);
   if (threadIdx.x == 0) w.iters[inst] = 0;
 }
 #endif

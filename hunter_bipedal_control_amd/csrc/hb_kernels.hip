@@ -1274,6 +1274,12 @@ struct hb_ctx {
   bool wbc_cert = false, cert_last = false;
   double* cert_buf = nullptr;  // [B][HB_WBC_CERT_SIZE]
   double* dual_buf = nullptr;  // [B][HB_WBC_NCONS_MAX]
+  // per-level certificate of the HierarchicalWbc cascade (hb_hwbc_set_certificate): the same switch (wbc_cert / cert_last) on a
+  // wbc_type = 1 context, its own buffers
+  double* hcert_buf = nullptr;    // [B][HB_HWBC_LEVELS][HB_HWBC_CERT_SIZE]
+  double* hxlev_buf = nullptr;    // [B][HB_HWBC_LEVELS][38]
+  double* hslack_buf = nullptr;   // [B][HB_HWBC_NINEQ_MAX]
+  double* hdual_buf = nullptr;    // [B][HB_HWBC_LEVELS][HB_HWBC_NINEQ_MAX]
 };
 
 static thread_local std::string g_create_error;
@@ -2593,7 +2599,11 @@ static int32_t launch_policy_wbc(hb_ctx* ctx, const WbcBatch& w, int i0, bool fr
     hipLaunchKernelGGL(k_policy_eval, dim3((w.B + 63) / 64), dim3(64), 0, s, w, ctx->Nmax, ctx->dconfig);
     if (policy_read) HB_HIP(hipEventRecord(policy_read, s));
   }
-  if (ctx->config.wbc_type == 1)
+  if (ctx->config.wbc_type == 1 && ctx->wbc_cert)  // (in a range graph: chosen at capture, hb_hwbc_set_certificate re-captures)
+    hipLaunchKernelGGL(k_hwbc_cert, dim3(w.B), dim3(64), (HoLdsDev::total + HoCertLds::total) * sizeof(double), s, w, ctx->dmodel, ctx->dconfig,
+                       ctx->hcert_buf + size_t(i0) * HB_HWBC_LEVELS * HB_HWBC_CERT_SIZE, ctx->hxlev_buf + size_t(i0) * HB_HWBC_LEVELS * HB_NWBC,
+                       ctx->hslack_buf + size_t(i0) * HB_HWBC_NINEQ_MAX, ctx->hdual_buf + size_t(i0) * HB_HWBC_LEVELS * HB_HWBC_NINEQ_MAX);
+  else if (ctx->config.wbc_type == 1)
     hipLaunchKernelGGL(k_hwbc, dim3(w.B), dim3(64), HoLdsDev::total * sizeof(double), s, w, ctx->dmodel, ctx->dconfig);
   else if (ctx->wbc_cert)  // (in a range graph: chosen at capture, hb_wbc_set_certificate re-captures)
     hipLaunchKernelGGL(k_wbc_cert, dim3(w.B), dim3(64), 0, s, w, ctx->dmodel, ctx->dconfig, ctx->cert_buf + size_t(i0) * HB_WBC_CERT_SIZE,
@@ -2988,7 +2998,7 @@ int32_t hb_wbc_set_certificate(hb_ctx* ctx, int32_t enable) {
 int32_t hb_wbc_get_certificate(hb_ctx* ctx, int32_t inst_begin, int32_t inst_count, double* cert, double* dual) {
   if (ctx) lazy_join(ctx);
   if (!ctx || inst_begin < 0 || inst_count < 0 || inst_begin > ctx->B || inst_count > ctx->B - inst_begin) return HB_ERR_ARG;
-  if (!ctx->cert_last) {
+  if (!ctx->cert_last || ctx->config.wbc_type != 0) {  // (a HierarchicalWbc context keeps its certificates elsewhere: hb_hwbc_get_certificate)
     ctx->err = "hb_wbc_get_certificate: certificates were off at the last WBC call (hb_wbc_set_certificate)";
     return HB_ERR_STATE;
   }
@@ -2998,6 +3008,46 @@ int32_t hb_wbc_get_certificate(hb_ctx* ctx, int32_t inst_begin, int32_t inst_cou
     HB_HIP(hipMemcpy(cert, ctx->cert_buf + size_t(inst_begin) * HB_WBC_CERT_SIZE, size_t(inst_count) * HB_WBC_CERT_SIZE * 8, hipMemcpyDeviceToHost));
   if (dual && inst_count)
     HB_HIP(hipMemcpy(dual, ctx->dual_buf + size_t(inst_begin) * HB_WBC_NCONS_MAX, size_t(inst_count) * HB_WBC_NCONS_MAX * 8, hipMemcpyDeviceToHost));
+  return HB_OK;
+}
+
+int32_t hb_hwbc_set_certificate(hb_ctx* ctx, int32_t enable) {
+  if (ctx) lazy_join(ctx);
+  if (!ctx || enable < 0 || enable > 1) return HB_ERR_ARG;
+  if (ctx->config.wbc_type != 1) {
+    ctx->err = "hb_hwbc_set_certificate: the per-level certificate is defined for HierarchicalWbc (wbc_type = 1) only; WeightedWbc has hb_wbc_set_certificate";
+    return HB_ERR_ARG;
+  }
+  if (bool(enable) == ctx->wbc_cert) return HB_OK;
+  HB_HIP(hipSetDevice(ctx->device));
+  HB_TRY(hb_sync(ctx));
+  if (enable && !ctx->hcert_buf) {
+    HB_HIP(dalloc(ctx, &ctx->hcert_buf, size_t(ctx->B) * HB_HWBC_LEVELS * HB_HWBC_CERT_SIZE));
+    HB_HIP(dalloc(ctx, &ctx->hxlev_buf, size_t(ctx->B) * HB_HWBC_LEVELS * HB_NWBC));
+    HB_HIP(dalloc(ctx, &ctx->hslack_buf, size_t(ctx->B) * HB_HWBC_NINEQ_MAX));
+    HB_HIP(dalloc(ctx, &ctx->hdual_buf, size_t(ctx->B) * HB_HWBC_LEVELS * HB_HWBC_NINEQ_MAX));
+  }
+  ctx->wbc_cert = enable != 0;
+  ++ctx->graph_epoch;  // captured range graphs hold the other WBC kernel
+  return HB_OK;
+}
+
+int32_t hb_hwbc_get_certificate(hb_ctx* ctx, int32_t inst_begin, int32_t inst_count, double* cert, double* x_levels, double* slack0,
+                                double* dual) {
+  if (ctx) lazy_join(ctx);
+  if (!ctx || inst_begin < 0 || inst_count < 0 || inst_begin > ctx->B || inst_count > ctx->B - inst_begin) return HB_ERR_ARG;
+  if (ctx->config.wbc_type != 1 || !ctx->cert_last) {
+    ctx->err = "hb_hwbc_get_certificate: certificates were off at the last WBC call (hb_hwbc_set_certificate)";
+    return HB_ERR_STATE;
+  }
+  HB_HIP(hipSetDevice(ctx->device));
+  HB_HIP(hipStreamSynchronize(ctx->s_wbc));
+  const size_t i0 = size_t(inst_begin), n = size_t(inst_count);
+  const size_t nc = HB_HWBC_LEVELS * HB_HWBC_CERT_SIZE, nx = HB_HWBC_LEVELS * HB_NWBC, nd = HB_HWBC_LEVELS * HB_HWBC_NINEQ_MAX;
+  if (cert && n) HB_HIP(hipMemcpy(cert, ctx->hcert_buf + i0 * nc, n * nc * 8, hipMemcpyDeviceToHost));
+  if (x_levels && n) HB_HIP(hipMemcpy(x_levels, ctx->hxlev_buf + i0 * nx, n * nx * 8, hipMemcpyDeviceToHost));
+  if (slack0 && n) HB_HIP(hipMemcpy(slack0, ctx->hslack_buf + i0 * HB_HWBC_NINEQ_MAX, n * HB_HWBC_NINEQ_MAX * 8, hipMemcpyDeviceToHost));
+  if (dual && n) HB_HIP(hipMemcpy(dual, ctx->hdual_buf + i0 * nd, n * nd * 8, hipMemcpyDeviceToHost));
   return HB_OK;
 }
 

@@ -28,7 +28,7 @@ ABI_SYMBOLS = [
     "hb_refgen_reset", "hb_refgen_set_schedule", "hb_refgen_update", "hb_mpc_get_references", "hb_joint_command", "hb_centroidal_state_from_rbd", "hb_plant_reset", "hb_plant_step",
     "hb_plant_get_state", "hb_hoqp_solve", "hb_mpc_reset_masked", "hb_mpc_get_status", "hb_joint_set_flags",
     "hb_joint_get_emergency_stop", "hb_set_resident_time", "hb_get_wbc_iterations", "hb_ik_solve", "hb_debug_chunk_counters", "hb_debug_graph_state", "hb_refgen_get_status", "hb_tick_resident",
-    "hb_wbc_set_certificate", "hb_wbc_get_certificate",
+    "hb_wbc_set_certificate", "hb_wbc_get_certificate", "hb_hwbc_set_certificate", "hb_hwbc_get_certificate",
     "hb_refgen_get_schedule", "hb_gait_reset", "hb_gait_disable", "hb_gait_insert_template", "hb_gait_get_state",
 ]
 # include/hunter_lcm.h
@@ -307,6 +307,27 @@ class HunterSolver:
         out = {name: cert[:, k].copy() for k, name in enumerate(self.WBC_CERT_FIELDS)}
         out["n_active"] = out["n_active"].astype(np.int32)
         out["dual"] = dual
+        return out
+
+    # field order of hunter_hip.h's HB_HWBC_CERT_* (the certificate of one level of one instance)
+    HWBC_CERT_FIELDS = ("res_own", "res_final", "r_hier", "r_in", "r_stat", "r_dual", "r_comp", "n_free", "n_active", "scale")
+
+    def hwbc_set_certificate(self, enable: bool = True):
+        """Per-level certificate of the HierarchicalWbc cascade on every later WBC call (hb_hwbc_set_certificate)."""
+        self._check(self.lib.hb_hwbc_set_certificate(self.ctx, C.c_int32(1 if enable else 0)), "hb_hwbc_set_certificate")
+
+    def hwbc_certificate(self, inst_begin: int = 0, count: int | None = None) -> dict:
+        """Per-level certificates of instances [inst_begin, inst_begin + count) from the last WBC call: the named fields of hunter_hip.h
+        (res_own, res_final, r_hier, r_in, r_stat, r_dual, r_comp, n_free, n_active, scale; [count][3] each, the two counts as int),
+        cert [count][3][10] (the same, as one array), x_levels [count][3][38], slack0 [count][40] and dual [count][3][40]."""
+        count = self.B - inst_begin if count is None else int(count)
+        n = max(count, 0)
+        cert, xl, s0, dual = np.zeros((n, 3, 10)), np.zeros((n, 3, 38)), np.zeros((n, 40)), np.zeros((n, 3, 40))
+        self._check(self.lib.hb_hwbc_get_certificate(self.ctx, C.c_int32(inst_begin), C.c_int32(count), _p(cert), _p(xl), _p(s0), _p(dual)),
+                    "hb_hwbc_get_certificate")
+        out = {name: cert[:, :, k].copy() for k, name in enumerate(self.HWBC_CERT_FIELDS)}
+        out["n_free"], out["n_active"] = out["n_free"].astype(np.int32), out["n_active"].astype(np.int32)
+        out.update(cert=cert, x_levels=xl, slack0=s0, dual=dual)
         return out
 
     def sync(self):

@@ -309,6 +309,40 @@ int32_t hb_get_wbc_iterations(hb_ctx* ctx, int32_t* iters /*[batch]*/);
 int32_t hb_wbc_set_certificate(hb_ctx* ctx, int32_t enable);
 int32_t hb_wbc_get_certificate(hb_ctx* ctx, int32_t inst_begin, int32_t inst_count, double* cert /*[count][8]*/,
                                double* dual /*[count][60]*/);
+/* Per-level optimality certificate of the HierarchicalWbc cascade (hb_config.wbc_type = 1), per instance, computed inside the WBC kernel
+ * right after the solve.  Levels k = 0, 1, 2 with the tasks A_k x = b_k of HierarchicalWbc.cpp:23-27 and the shared
+ * inequality rows D x <= f of level 0 (torque limits 20, friction pyramid 5 n_c; n_in <= HB_HWBC_NINEQ_MAX), WITHOUT the Tikhonov terms
+ * and without the 1e-12 Hessian shift:
+ *   x_k       the solution after level k (x_2 = the returned sol);  v0 = (D x_0 - f)_+ the level-0 slack;  g_k = A_k'(A_k x_k - b_k);
+ *   Q_k       an ORTHONORMAL basis of the level's search space: Q_0 = I, Q_1 spans kernel(A_0), Q_2 spans kernel([A_0; A_1]) (thin QR of
+ *             the kernel bases the cascade holds), so no figure depends on the basis the solver happened to use;
+ *   y_k       the multipliers of the inequality rows, g - D'y = 0, y <= 0 on active rows: y_0 = -v0 (the slacked rows' multipliers are
+ *             the slack), y_k = argmin |Q_k'(g_k - D_W'y_W)|_2 on the final working set W of the level's QP for k >= 1, zero outside W.
+ * A level the cascade did not reach (a kernel basis was given up: status != 0, previous solution kept) is judged at the returned sol
+ * with N_FREE = N_ACTIVE = 0, y = 0 and the UNPROJECTED |g_k|_2 as R_STAT, so it never looks certified; every field stays finite.
+ * hb_hwbc_set_certificate: 0 (default) / 1.  Every later WBC launch (hb_wbc_update, hb_wbc_update_direct, hb_step_resident,
+ * hb_tick_resident, with or without hb_set_chunks) runs the certificate kernel; sol / status and the resident outputs are bit-identical
+ * either way.  Switching re-captures the range graphs.  HB_ERR_ARG on a WeightedWbc context (wbc_type = 0: hb_wbc_set_certificate).
+ * hb_hwbc_get_certificate: instances [inst_begin, inst_begin + inst_count) of the last WBC call (synchronises the WBC stream);
+ * cert [count][3][HB_HWBC_CERT_SIZE], x_levels [count][3][38], slack0 [count][40] (v0), dual [count][3][40] (y_k by inequality row),
+ * any may be NULL; rows >= n_in are zero.  HB_ERR_STATE if certificates were off at that call (or no WBC call ran since they were
+ * enabled), HB_ERR_ARG for a bad range. */
+#define HB_HWBC_LEVELS 3
+#define HB_HWBC_NINEQ_MAX 40
+#define HB_HWBC_CERT_RES_OWN 0    /* |A_k x_k - b_k|_2: the optimum of this priority */
+#define HB_HWBC_CERT_RES_FINAL 1  /* |A_k x_2 - b_k|_2: what the returned solution achieves */
+#define HB_HWBC_CERT_R_HIER 2     /* max_{j<k} |A_j (x_k - x_{k-1})|_inf: the step of this level seen by every higher task; 0 for k = 0 */
+#define HB_HWBC_CERT_R_IN 3       /* max(0, max(D x_k - f - v0)) */
+#define HB_HWBC_CERT_R_STAT 4     /* |Q_k'(g_k - D'y_k)|_2 */
+#define HB_HWBC_CERT_R_DUAL 5     /* max(0, max y_k) (sign violation) */
+#define HB_HWBC_CERT_R_COMP 6     /* max |y_k o (D x_k - f - v0)| */
+#define HB_HWBC_CERT_N_FREE 7     /* columns of Q_k (38, 10..12, <= 6) */
+#define HB_HWBC_CERT_N_ACTIVE 8   /* |W| (level 0: rows with v0 > 0) */
+#define HB_HWBC_CERT_SCALE 9      /* max(1, |A_k'b_k|_inf, |A_k'A_k x_k|_inf): R_STAT, R_DUAL, R_COMP are read relative to it */
+#define HB_HWBC_CERT_SIZE 10
+int32_t hb_hwbc_set_certificate(hb_ctx* ctx, int32_t enable);
+int32_t hb_hwbc_get_certificate(hb_ctx* ctx, int32_t inst_begin, int32_t inst_count, double* cert /*[count][3][10]*/,
+                                double* x_levels /*[count][3][38]*/, double* slack0 /*[count][40]*/, double* dual /*[count][3][40]*/);
 /* Pipelining of hb_step_resident: the batch is cut into n_chunks (1..8) instance ranges, each a linear
  * MPC -> publish -> WBC sequence on its own HIP stream so that the per-instance sweeps of one range overlap the
  * per-node kernels of another.  Results are identical for every n_chunks; hb_get_stats phase times are only

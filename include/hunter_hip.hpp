@@ -267,6 +267,28 @@ class Wbc {
     return y;
   }
 
+  // Per-level certificate of the HierarchicalWbc cascade (hunter_hip.h, hb_hwbc_set_certificate; a wbc_type = 1 context): computed by
+  // every update from the next one on
+  void enableLevelCertificate(bool on) { ctx_.check(hb_hwbc_set_certificate(ctx_.get(), on ? 1 : 0), "hb_hwbc_set_certificate"); }
+  struct LevelCertificate {
+    vector_t cert;     // [batch][HB_HWBC_LEVELS][HB_HWBC_CERT_SIZE] (indices HB_HWBC_CERT_*)
+    vector_t xLevels;  // [batch][HB_HWBC_LEVELS][38]: the solution after each level (HoQp::getSolutions)
+    vector_t slack0;   // [batch][HB_HWBC_NINEQ_MAX]: the level-0 slack
+    vector_t dual;     // [batch][HB_HWBC_LEVELS][HB_HWBC_NINEQ_MAX]: the multipliers of the inequality rows
+  };
+  // certificates of the last update
+  const LevelCertificate& levelCertificate() {
+    const size_t B = size_t(ctx_.batch());
+    lcert_.cert.resize(B * HB_HWBC_LEVELS * HB_HWBC_CERT_SIZE);
+    lcert_.xLevels.resize(B * HB_HWBC_LEVELS * HB_NWBC);
+    lcert_.slack0.resize(B * HB_HWBC_NINEQ_MAX);
+    lcert_.dual.resize(B * HB_HWBC_LEVELS * HB_HWBC_NINEQ_MAX);
+    ctx_.check(hb_hwbc_get_certificate(ctx_.get(), 0, ctx_.batch(), lcert_.cert.data(), lcert_.xLevels.data(), lcert_.slack0.data(),
+                                       lcert_.dual.data()),
+               "hb_hwbc_get_certificate");
+    return lcert_;
+  }
+
  protected:
   void reportUnsolved() const {
     // instances that hit the iteration limit keep their previous solution on the device (WeightedWbc.cpp:57-65)
@@ -278,6 +300,7 @@ class Wbc {
   }
   Context ctx_;
   vector_t last_, cert_;
+  LevelCertificate lcert_;
   std::vector<int32_t> status_, stance_;
 };
 
