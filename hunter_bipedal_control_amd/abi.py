@@ -164,6 +164,8 @@ def make_joint_gains(**overrides) -> HbJointGains:
 
 
 HB_MAX_EVENTS = 64
+# field order of hunter_hip.h's HB_MPC_CERT_* (HunterSolver.mpc_certificate)
+MPC_CERT_FIELDS = ("r_dyn", "r_stat", "obj", "step_max", "u_max", "lambda_max", "scale", "n_nodes")
 # hb_status / per-instance status words (include/hunter_hip.h)
 HB_OK, HB_ERR_ARG, HB_ERR_DEVICE, HB_ERR_STATE, HB_ERR_NO_GPU = 0, -1, -2, -3, -4
 HB_INST_OK, HB_INST_MAXITER, HB_INST_INFEASIBLE, HB_INST_NAN = 0, 1, 2, 3

@@ -12,6 +12,7 @@
 
 #include "hb_host.hpp"
 #include "hb_riccati.hpp"
+#include "hb_mpccert.hpp"
 #include "hb_lcm.hpp"
 #include "hb_wbc.hpp"
 #include "hb_hoqp.hpp"
@@ -695,6 +696,94 @@ __global__ __launch_bounds__(64) void k_ric_fwd(Batch b) { ric_fwd_body<false>(b
 __global__ __launch_bounds__(64) void k_ric_fwd_w(Batch b) { ric_fwd_body<true>(b); }
 constexpr int kRicFwdWaveMaxBatch = 512;
 
+// ---- KKT certificate of the stage QP (hb_mpccert.hpp), on demand: hb_mpc_get_certificate.  Work buffers of the instances of `b`.
+struct MpcCertBuf {
+  double* node;     // [B][Nmax][CertNode::size]
+  double* costate;  // [B][Nmax+1][22]
+  double* cert;     // [B][MPC_CERT_SIZE]
+  double* util;     // [B][Nmax][12]: u~ as hb_mpc_get_certificate returns it
+};
+// One wavefront per (instance, node), grid as k_lq.  The Riccati part of the record and the gains are staged with 16-byte loads, every
+// load of a lane requested before the first is stored (the record is the LDS image: straight copies).  A node behind the horizon, and
+// every node of an instance whose MPC call ended HB_INST_NAN, only zeroes its u~ row.
+__global__ __launch_bounds__(64) void k_mpc_cert_nodes(Batch b, MpcCertBuf cb) {
+  const int k = blockIdx.x, inst = blockIdx.y;
+  __shared__ double lds[CertLds::total];
+  const WaveCtx cx;
+  const int l = cx.lane;
+  const size_t nd = size_t(inst) * b.Nmax + k;
+  double* out = cb.node + nd * CertNode::size;
+  if (k >= b.n_nodes[inst] || b.mpc_status[inst] == HB_INST_NAN) {
+    if (l < 12) cb.util[nd * 12 + l] = 0.0;
+    return;
+  }
+  constexpr int P_REC = CERT_REC_LEN / 2, P_G = GAIN_SIZE / 2, N_REC = (P_REC + 63) / 64, N_G = (P_G + 63) / 64;   // 750, 144 pairs: 12, 3 loads per lane
+  typedef double d2 __attribute__((ext_vector_type(2)));
+  d2 brec[N_REC], bg[N_G];
+  const d2* prec = reinterpret_cast<const d2*>(b.recs + nd * REC_SIZE) + l;
+  const d2* pg = reinterpret_cast<const d2*>(b.gains + nd * GAIN_SIZE) + l;
+#pragma unroll
+  for (int r = 0; r < N_REC; ++r) brec[r] = (64 * r + 63 < P_REC || l + 64 * r < P_REC) ? prec[64 * r] : d2{0.0, 0.0};
+#pragma unroll
+  for (int r = 0; r < N_G; ++r) bg[r] = (64 * r + 63 < P_G || l + 64 * r < P_G) ? pg[64 * r] : d2{0.0, 0.0};
+  const double dxv = l < 44 ? b.dx[(size_t(inst) * (b.Nmax + 1) + k) * HB_NX + l] : 0.0;   // dx_k, dx_(k+1): 44 consecutive doubles
+  {
+    d2* srec = reinterpret_cast<d2*>(lds + CertLds::rec) + l;
+    d2* sg = reinterpret_cast<d2*>(lds + CertLds::G) + l;
+#pragma unroll
+    for (int r = 0; r < N_REC; ++r) if (64 * r + 63 < P_REC || l + 64 * r < P_REC) srec[64 * r] = brec[r];
+#pragma unroll
+    for (int r = 0; r < N_G; ++r) if (64 * r + 63 < P_G || l + 64 * r < P_G) sg[64 * r] = bg[r];
+    if (l < 44) lds[l < 22 ? CertLds::dx + l : CertLds::dxn + l - 22] = dxv;
+  }
+  cx.sync();
+  mpc_cert_node(cx, lds, k == 0, out);
+  if (l < 12) cb.util[nd * 12 + l] = lds[CertLds::ut + l];
+}
+
+// One wavefront per instance, backward over the stages: per stage the 22 rows of [A~ b~ B~ .] (396 pairs, 16-byte loads) and the lane's
+// entry of c_k / d_k, requested one stage ahead (WaveCtx::sync does not drain them).  Rows behind the horizon of the costate output
+// are zeroed; an HB_INST_NAN instance gets a zero costate and NaN fields.
+__global__ __launch_bounds__(64) void k_mpc_cert_sweep(Batch b, MpcCertBuf cb) {
+  const int inst = blockIdx.x;
+  __shared__ double lds[CertSweepLds::total];
+  const WaveCtx cx;
+  const int l = cx.lane;
+  const int n = b.n_nodes[inst];
+  const bool certified = b.mpc_status[inst] != HB_INST_NAN;
+  double* costate = cb.costate + size_t(inst) * (b.Nmax + 1) * HB_NX;
+  const double* nodes = cb.node + size_t(inst) * b.Nmax * CertNode::size;
+  mpc_cert_sweep_init(cx, lds);
+  for (int e = (certified ? n * HB_NX : 0) + l; e < (b.Nmax + 1) * HB_NX; e += 64) costate[e] = 0.0;   // lambda_n = 0 and the rows behind it
+  if (certified) {
+    constexpr int P_AB = REC_PR / 2, N_AB = (P_AB + 63) / 64;   // 396 pairs: 7 loads per lane
+    typedef double d2 __attribute__((ext_vector_type(2)));
+    d2 bab[N_AB];
+    double cdv = 0.0;
+    const int cd_off = l < 22 ? CertNode::c + l : (l >= REC_CU && l < REC_CU + 12) ? CertNode::d + l - REC_CU : -1;
+#define HB_CERT_FETCH(kk)                                                                                                         \
+  {                                                                                                                               \
+    const d2* pab_ = reinterpret_cast<const d2*>(b.recs + (size_t(inst) * b.Nmax + (kk)) * REC_SIZE + REC_AB) + l;                \
+    _Pragma("unroll") for (int r = 0; r < N_AB; ++r) bab[r] = (64 * r + 63 < P_AB || l + 64 * r < P_AB) ? pab_[64 * r] : d2{0.0, 0.0}; \
+    cdv = cd_off >= 0 ? nodes[size_t(kk) * CertNode::size + cd_off] : 0.0;                                                       \
+  }
+    if (n > 0) HB_CERT_FETCH(n - 1);
+    for (int k = n - 1; k >= 0; --k) {
+      {
+        d2* sab = reinterpret_cast<d2*>(lds + CertSweepLds::AB) + l;
+#pragma unroll
+        for (int r = 0; r < N_AB; ++r) if (64 * r + 63 < P_AB || l + 64 * r < P_AB) sab[64 * r] = bab[r];
+      }
+      const double cdk = cdv;
+      cx.sync();
+      if (k > 0) HB_CERT_FETCH(k - 1);
+      mpc_cert_sweep_stage(cx, lds, [cdk](int) { return cdk; }, costate + size_t(k) * HB_NX);
+    }
+#undef HB_CERT_FETCH
+  }
+  mpc_cert_finish(cx, lds, nodes, certified ? n : 0, certified, cb.cert + size_t(inst) * MPC_CERT_SIZE);
+}
+
 // line search: value of trial point (x + alpha dx, u + alpha du), one thread per node
 __global__ __launch_bounds__(64) void k_ls_eval(Batch b, const DevModel* __restrict__ M, const DevConfig* __restrict__ C,
                                                 double alpha) {
@@ -1280,6 +1369,12 @@ struct hb_ctx {
   double* hxlev_buf = nullptr;    // [B][HB_HWBC_LEVELS][38]
   double* hslack_buf = nullptr;   // [B][HB_HWBC_NINEQ_MAX]
   double* hdual_buf = nullptr;    // [B][HB_HWBC_LEVELS][HB_HWBC_NINEQ_MAX]
+  // KKT certificate of the MPC's stage QP (hb_mpc_get_certificate): work buffers allocated on the first call.  The records, gains and
+  // step of a solve belong to the node tables and the iterate it ran on: mpc_tables_epoch counts their replacements by the host
+  // (hb_mpc_set_references, hb_refgen_update, hb_mpc_reset*, hb_mpc_set_trajectory), mpc_solved_epoch is its value at the last MPC call
+  // (0: none yet).
+  MpcCertBuf mcert{};
+  uint64_t mpc_tables_epoch = 1, mpc_solved_epoch = 0;
 };
 
 static thread_local std::string g_create_error;
@@ -1331,7 +1426,7 @@ static hipError_t dalloc(hb_ctx* ctx, T** p, size_t n) {
 
 extern "C" {
 
-int32_t hb_version(void) { return 200; }
+int32_t hb_version(void) { return 201; }
 
 const char* hb_last_error(const hb_ctx* ctx) { return ctx ? ctx->err.c_str() : g_create_error.c_str(); }
 
@@ -1859,6 +1954,7 @@ int32_t hb_refgen_update(hb_ctx* ctx, const double* t0, double horizon, const do
   launch_refgen(ctx, ctx->b, r, 0, horizon, s);
   HB_HIP(hipGetLastError());
   r.init_stance = 0;
+  ++ctx->mpc_tables_epoch;
   if (status) {
     HB_HIP(hipMemcpyAsync(status, r.status, B * sizeof(int), hipMemcpyDeviceToHost, s));
     HB_HIP(hipStreamSynchronize(s));
@@ -2322,6 +2418,7 @@ int32_t hb_mpc_set_references(hb_ctx* ctx, int32_t i0, int32_t cnt, const int32_
   HB_HIP(hipMemcpyAsync(b.swing + i0 * N * 24, swing_ref, cnt * N * 24 * 8, hipMemcpyHostToDevice, ctx->s_mpc));
   HB_HIP(hipStreamSynchronize(ctx->s_mpc));  // host buffers are caller-owned: safe to reuse on return
   ctx->refs_set = true;
+  ++ctx->mpc_tables_epoch;
   return HB_OK;
 }
 
@@ -2350,6 +2447,7 @@ static int32_t mpc_cold_start(hb_ctx* ctx, const double* x0, const uint8_t* mask
         if (mask[i]) HB_HIP(hipMemcpyAsync(ctx->b.x0 + i * HB_NX, x0 + i * HB_NX, HB_NX * 8, hipMemcpyHostToDevice, ctx->s_mpc));
     }
   }
+  ++ctx->mpc_tables_epoch;
   hipLaunchKernelGGL(k_cold_start, dim3(ctx->Nmax + 1, ctx->B), dim3(64), 0, ctx->s_mpc, ctx->b, ctx->dmodel, dmask);
   HB_HIP(hipGetLastError());
   HB_HIP(hipStreamSynchronize(ctx->s_mpc));
@@ -2384,6 +2482,7 @@ int32_t hb_mpc_set_trajectory(hb_ctx* ctx, const double* x, const double* u) {
   if (!ctx || !x || !u) return HB_ERR_ARG;
   const size_t B = ctx->B, N = ctx->Nmax;
   HB_HIP(hipSetDevice(ctx->device));
+  ++ctx->mpc_tables_epoch;
   HB_HIP(hipMemcpyAsync(ctx->b.x, x, B * (N + 1) * HB_NX * 8, hipMemcpyHostToDevice, ctx->s_mpc));
   HB_HIP(hipMemcpyAsync(ctx->b.u, u, B * N * HB_NU * 8, hipMemcpyHostToDevice, ctx->s_mpc));
   hipLaunchKernelGGL(k_grid_clean, dim3((ctx->B + 255) / 256), dim3(256), 0, ctx->s_mpc, ctx->b);  // given on the current tables
@@ -2500,6 +2599,7 @@ static int32_t mpc_solve_batch(hb_ctx* ctx) {
   std::lock_guard<std::mutex> lk(ctx->mtx);
   ctx->timed = true;
   ctx->stats.n_mpc_solves += ctx->B;
+  ctx->mpc_solved_epoch = ctx->mpc_tables_epoch;
   return HB_OK;
 }
 
@@ -2812,6 +2912,7 @@ static void finish_ranges(hb_ctx* ctx, bool steady) {
   ctx->stats.n_mpc_solves += ctx->B;
   ctx->stats.n_wbc_solves += ctx->B;
   ctx->cert_last = ctx->wbc_cert;
+  ctx->mpc_solved_epoch = ctx->mpc_tables_epoch;
 }
 
 int32_t hb_step_resident(hb_ctx* ctx, double dt) {
@@ -3048,6 +3149,80 @@ int32_t hb_hwbc_get_certificate(hb_ctx* ctx, int32_t inst_begin, int32_t inst_co
   if (x_levels && n) HB_HIP(hipMemcpy(x_levels, ctx->hxlev_buf + i0 * nx, n * nx * 8, hipMemcpyDeviceToHost));
   if (slack0 && n) HB_HIP(hipMemcpy(slack0, ctx->hslack_buf + i0 * HB_HWBC_NINEQ_MAX, n * HB_HWBC_NINEQ_MAX * 8, hipMemcpyDeviceToHost));
   if (dual && n) HB_HIP(hipMemcpy(dual, ctx->hdual_buf + i0 * nd, n * nd * 8, hipMemcpyDeviceToHost));
+  return HB_OK;
+}
+
+// The records, gains and step on the device are those of the last MPC call, on the tables and the iterate it ran on
+static int32_t mpc_records_current(hb_ctx* ctx, const char* who) {
+  if (ctx->mpc_solved_epoch == 0) {
+    ctx->err = std::string(who) + ": no MPC call has completed on this context (hb_mpc_solve, hb_step_resident, hb_tick_resident)";
+    return HB_ERR_STATE;
+  }
+  if (ctx->mpc_solved_epoch != ctx->mpc_tables_epoch) {
+    ctx->err = std::string(who) + ": the node tables or the iterate were replaced since the last MPC call (hb_mpc_set_references, "
+               "hb_refgen_update, hb_mpc_reset, hb_mpc_reset_masked, hb_mpc_set_trajectory): solve again first";
+    return HB_ERR_STATE;
+  }
+  return HB_OK;
+}
+
+int32_t hb_mpc_get_certificate(hb_ctx* ctx, int32_t inst_begin, int32_t inst_count, double* cert, double* costate, double* u_til) {
+  if (ctx) lazy_join(ctx);
+  if (!ctx) return HB_ERR_ARG;
+  if (inst_begin < 0 || inst_count <= 0 || inst_begin > ctx->B || inst_count > ctx->B - inst_begin) {
+    ctx->err = "hb_mpc_get_certificate: instance range outside the batch";
+    return HB_ERR_ARG;
+  }
+  HB_TRY(mpc_records_current(ctx, "hb_mpc_get_certificate"));
+  HB_HIP(hipSetDevice(ctx->device));
+  const size_t B = ctx->B, N = ctx->Nmax, i0 = size_t(inst_begin), cnt = size_t(inst_count);
+  MpcCertBuf& m = ctx->mcert;
+  if (!m.node) {
+    HB_HIP(dalloc(ctx, &m.node, B * N * CertNode::size));
+    HB_HIP(dalloc(ctx, &m.costate, B * (N + 1) * HB_NX));
+    HB_HIP(dalloc(ctx, &m.cert, B * MPC_CERT_SIZE));
+    HB_HIP(dalloc(ctx, &m.util, B * N * 12));
+  }
+  const Batch b = batch_view(ctx->b, inst_begin, inst_count);
+  const MpcCertBuf v{m.node + i0 * N * CertNode::size, m.costate + i0 * (N + 1) * HB_NX, m.cert + i0 * MPC_CERT_SIZE, m.util + i0 * N * 12};
+  hipStream_t s = ctx->s_mpc;
+  hipLaunchKernelGGL(k_mpc_cert_nodes, dim3(ctx->Nmax, inst_count), dim3(64), 0, s, b, v);
+  hipLaunchKernelGGL(k_mpc_cert_sweep, dim3(inst_count), dim3(64), 0, s, b, v);
+  HB_HIP(hipGetLastError());
+  if (cert) HB_HIP(hipMemcpyAsync(cert, v.cert, cnt * MPC_CERT_SIZE * 8, hipMemcpyDeviceToHost, s));
+  if (costate) HB_HIP(hipMemcpyAsync(costate, v.costate, cnt * (N + 1) * HB_NX * 8, hipMemcpyDeviceToHost, s));
+  if (u_til) HB_HIP(hipMemcpyAsync(u_til, v.util, cnt * N * 12 * 8, hipMemcpyDeviceToHost, s));
+  HB_HIP(hipStreamSynchronize(s));
+  return HB_OK;
+}
+
+int32_t hb_mpc_get_lq(hb_ctx* ctx, int32_t inst, double* A, double* B, double* b, double* Q, double* P, double* R, double* q, double* r,
+                      int32_t* n_til) {
+  if (ctx) lazy_join(ctx);
+  if (!ctx) return HB_ERR_ARG;
+  if (inst < 0 || inst >= ctx->B) {
+    ctx->err = "hb_mpc_get_lq: instance outside the batch";
+    return HB_ERR_ARG;
+  }
+  HB_TRY(mpc_records_current(ctx, "hb_mpc_get_lq"));
+  HB_HIP(hipSetDevice(ctx->device));
+  const size_t N = ctx->Nmax;
+  std::vector<double> recs(N * REC_SIZE);
+  int n = 0;
+  HB_HIP(hipMemcpyAsync(&n, ctx->b.n_nodes + inst, sizeof(int), hipMemcpyDeviceToHost, ctx->s_mpc));
+  HB_HIP(hipMemcpyAsync(recs.data(), ctx->b.recs + size_t(inst) * N * REC_SIZE, recs.size() * 8, hipMemcpyDeviceToHost, ctx->s_mpc));
+  HB_HIP(hipStreamSynchronize(ctx->s_mpc));
+  n = std::max(0, std::min(n, ctx->Nmax));
+  const auto zero = [N](double* p, size_t per) { if (p) std::memset(p, 0, N * per * 8); };   // rows k >= n stay zero
+  zero(A, 22 * 22); zero(B, 22 * NU_T); zero(b, 22); zero(Q, 22 * 22); zero(P, NU_T * 22); zero(R, NU_T * NU_T); zero(q, 22); zero(r, NU_T);
+  if (n_til) std::memset(n_til, 0, N * sizeof(int32_t));
+  for (size_t k = 0; k < size_t(n); ++k) {
+    int nt = 0;
+    rec_unpack(recs.data() + k * REC_SIZE, A ? A + k * 484 : nullptr, B ? B + k * 264 : nullptr, b ? b + k * 22 : nullptr,
+               Q ? Q + k * 484 : nullptr, P ? P + k * 264 : nullptr, R ? R + k * 144 : nullptr, q ? q + k * 22 : nullptr,
+               r ? r + k * 12 : nullptr, &nt);
+    if (n_til) n_til[k] = nt;
+  }
   return HB_OK;
 }
 

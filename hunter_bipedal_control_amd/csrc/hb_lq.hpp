@@ -71,6 +71,29 @@ HB_HD constexpr int rec_b(int i) { return REC_AB + i * REC_LD + REC_CV; }       
 HB_HD constexpr int rec_P(int a, int c) { return REC_PR + a * REC_LD + c; }            // P~(a, c)
 HB_HD constexpr int rec_R(int a, int c) { return REC_PR + a * REC_LD + REC_CU + c; }   // R~(a, c)
 HB_HD constexpr int rec_r(int a) { return REC_PR + a * REC_LD + REC_CV; }              // r~(a)
+// The stage QP of one record as dense row-major arrays, the OCP-QP layout (A, B, b, Q, S = P, R, q, r): A [22][22], B [22][12], b [22],
+// Q [22][22] (full, symmetric), P [12][22], R [12][12], q [22], r [12]; n_til = n_f + n_z projected inputs (the columns behind them are
+// the padding: R~ = I, zero elsewhere).  Any pointer may be null.  The one unpack routine: hb_mpc_get_lq and the host harness use it.
+inline void rec_unpack(const double* rec, double* A, double* B, double* b, double* Q, double* P, double* R, double* q, double* r, int* n_til) {
+  for (int i = 0; i < 22; ++i) {
+    for (int c = 0; c < 22; ++c) {
+      if (A) A[i * 22 + c] = rec[rec_A(i, c)];
+      if (Q) Q[i * 22 + c] = rec[REC_QT + (i <= c ? rec_Qidx(i, c) : rec_Qidx(c, i))];
+    }
+    for (int a = 0; a < NU_T; ++a)
+      if (B) B[i * NU_T + a] = rec[rec_B(i, a)];
+    if (b) b[i] = rec[rec_b(i)];
+    if (q) q[i] = rec[REC_qT + i];
+  }
+  for (int a = 0; a < NU_T; ++a) {
+    for (int c = 0; c < 22; ++c)
+      if (P) P[a * 22 + c] = rec[rec_P(a, c)];
+    for (int c = 0; c < NU_T; ++c)
+      if (R) R[a * NU_T + c] = rec[rec_R(a, c)];
+    if (r) r[a] = rec[rec_r(a)];
+  }
+  if (n_til) *n_til = int(rec[REC_META]) + int(rec[REC_META + 1]);
+}
 
 struct RelaxedBarrierD {
   double mu, delta;

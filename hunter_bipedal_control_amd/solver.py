@@ -29,6 +29,7 @@ ABI_SYMBOLS = [
     "hb_plant_get_state", "hb_hoqp_solve", "hb_mpc_reset_masked", "hb_mpc_get_status", "hb_joint_set_flags",
     "hb_joint_get_emergency_stop", "hb_set_resident_time", "hb_get_wbc_iterations", "hb_ik_solve", "hb_debug_chunk_counters", "hb_debug_graph_state", "hb_refgen_get_status", "hb_tick_resident",
     "hb_wbc_set_certificate", "hb_wbc_get_certificate", "hb_hwbc_set_certificate", "hb_hwbc_get_certificate",
+    "hb_mpc_get_certificate", "hb_mpc_get_lq",
     "hb_refgen_get_schedule", "hb_gait_reset", "hb_gait_disable", "hb_gait_insert_template", "hb_gait_get_state",
 ]
 # include/hunter_lcm.h
@@ -329,6 +330,36 @@ class HunterSolver:
         out["n_free"], out["n_active"] = out["n_free"].astype(np.int32), out["n_active"].astype(np.int32)
         out.update(cert=cert, x_levels=xl, slack0=s0, dual=dual)
         return out
+
+    # field order of hunter_hip.h's HB_MPC_CERT_* (the certificate of one instance's stage QP)
+    MPC_CERT_FIELDS = abi.MPC_CERT_FIELDS
+
+    def mpc_certificate(self, inst_begin: int = 0, count: int | None = None) -> dict:
+        """KKT certificate of the stage QP of the last MPC call for instances [inst_begin, inst_begin + count), computed on demand
+        (hb_mpc_get_certificate): the named fields of hunter_hip.h (r_dyn, r_stat, obj, step_max, u_max, lambda_max, scale, n_nodes;
+        [count] each, n_nodes as int; r_stat is read relative to scale), cert [count][8] (the same, as one array),
+        costate [count][max_nodes+1][22] and u_til [count][max_nodes][12]."""
+        count = self.B - inst_begin if count is None else int(count)
+        n = max(count, 0)
+        cert, costate, u_til = np.zeros((n, 8)), np.zeros((n, self.N + 1, 22)), np.zeros((n, self.N, 12))
+        self._check(self.lib.hb_mpc_get_certificate(self.ctx, C.c_int32(inst_begin), C.c_int32(count), _p(cert), _p(costate), _p(u_til)),
+                    "hb_mpc_get_certificate")
+        out = {name: cert[:, k].copy() for k, name in enumerate(self.MPC_CERT_FIELDS)}
+        out["n_nodes"] = out["n_nodes"].astype(np.int32)
+        out.update(cert=cert, costate=costate, u_til=u_til)
+        return out
+
+    def mpc_lq(self, inst: int) -> dict:
+        """The stage QP of instance `inst` as the last MPC call left it (hb_mpc_get_lq), dense and trimmed to its n intervals, in the
+        OCP-QP layout: A [n][22][22], B [n][22][12], b [n][22], Q [n][22][22], P [n][12][22] (the cross term S), R [n][12][12],
+        q [n][22], r [n][12], n_til [n] (projected inputs per stage; the columns behind them are padding)."""
+        N = self.N
+        out = dict(A=np.zeros((N, 22, 22)), B=np.zeros((N, 22, 12)), b=np.zeros((N, 22)), Q=np.zeros((N, 22, 22)), P=np.zeros((N, 12, 22)),
+                   R=np.zeros((N, 12, 12)), q=np.zeros((N, 22)), r=np.zeros((N, 12)), n_til=np.zeros(N, dtype=np.int32))
+        self._check(self.lib.hb_mpc_get_lq(self.ctx, C.c_int32(inst), *[_p(out[k]) for k in ("A", "B", "b", "Q", "P", "R", "q", "r", "n_til")]),
+                    "hb_mpc_get_lq")
+        n = int(np.count_nonzero(out["n_til"]))   # every stage has at least the six kernel coordinates
+        return {k: v[:n].copy() for k, v in out.items()}
 
     def sync(self):
         self._check(self.lib.hb_sync(self.ctx), "hb_sync")

@@ -343,6 +343,49 @@ int32_t hb_wbc_get_certificate(hb_ctx* ctx, int32_t inst_begin, int32_t inst_cou
 int32_t hb_hwbc_set_certificate(hb_ctx* ctx, int32_t enable);
 int32_t hb_hwbc_get_certificate(hb_ctx* ctx, int32_t inst_begin, int32_t inst_count, double* cert /*[count][3][10]*/,
                                 double* x_levels /*[count][3][38]*/, double* slack0 /*[count][40]*/, double* dual /*[count][3][40]*/);
+/* KKT certificate, costates and stage-QP export of the MPC's Riccati solve, per instance, ON DEMAND: there is no switch, and
+ * hb_mpc_solve / hb_step_resident / hb_tick_resident enqueue nothing for it; the two certificate kernels run inside
+ * hb_mpc_get_certificate on what a solve leaves on the device (the projected stage records, the gains, the step).
+ *
+ * The certificate covers one instance with n intervals.  The data are those of the LAST SQP iteration of the last MPC call, as
+ * stored in the records.  Padded input columns are included: R~ = I, zero elsewhere, so they contribute exactly zero.  The start
+ * state is dx_0 as stored (the solve makes it 0).
+ *   u~_k = K~_k dx_k + k~_k, 12 entries, recomputed from the gains and dx: what the forward sweep applied.
+ *   Costates, backward over the stages:  lambda_n = 0 (there is no terminal cost: the backward sweep starts from S = 0),
+ *       lambda_k = q~_k + Q~_k dx_k + P~_k' u~_k + A~_k' lambda_(k+1),
+ *   the multiplier of dx_(k+1) = A~_k dx_k + B~_k u~_k + b~_k in the Lagrangian
+ *       cost + sum lambda_(k+1)' (A~ dx + B~ u~ + b~ - dx_(k+1));    lambda_0 = dV/dx_0.
+ *   R_DYN uses all 22 rows of the record; the forward sweep forms the joint rows 12..21 in closed form, so this residual is the
+ *   cross-check between the two forms the two sweeps use.  R_STAT is the input stationarity; state stationarity holds by
+ *   construction of lambda.  OBJ is the QP objective at the step; it has no sign guarantee (b~ != 0).  SCALE has NO floor at 1: the
+ *   stage costs carry a factor dt, so a floor would hide 300 x on a standing robot; R_STAT is read relative to SCALE.
+ * An instance whose status word of that MPC call is HB_INST_NAN is not certified: N_NODES = 0, fields 0-6 NaN, its costate and u~
+ * rows zero.  HB_INST_MAXITER is certified as usual (the line search rejected the step, but the QP solution is what it is).
+ * Out of scope: the unprojected problem and the multipliers of the equality constraints (C, D, e are not in the record), the
+ * nonlinear problem's KKT, the WBC (hb_wbc_set_certificate / hb_hwbc_set_certificate).
+ *
+ * hb_mpc_get_certificate: joins the instance-range streams as the other getters do, runs the certificate kernels for
+ * [inst_begin, inst_begin + inst_count) on the MPC stream, synchronises it and copies.  cert [count][HB_MPC_CERT_SIZE],
+ * costate [count][max_nodes+1][22] (lambda_0 .. lambda_n), u_til [count][max_nodes][12]; any may be NULL; rows k >= n_i (costate: k > n_i)
+ * are zero.  The work buffers are allocated on the first call.
+ * hb_mpc_get_lq: the stage QP of one instance, unpacked on the host into dense row-major arrays in the standard OCP-QP layout
+ * (A, B, b, Q, S = P, R, q, r: what HPIPM takes), n_til = projected inputs per stage; any pointer may be NULL; rows k >= n are zero.
+ * Both: HB_ERR_STATE when no MPC call has completed, or when the node tables or the iterate were replaced since the last one
+ * (hb_mpc_set_references, hb_refgen_update, hb_mpc_reset, hb_mpc_reset_masked, hb_mpc_set_trajectory); HB_ERR_ARG on a bad range. */
+#define HB_MPC_CERT_R_DYN 0       /* max(|dx_0|_inf, max_k |dx_(k+1) - (A~_k dx_k + B~_k u~_k + b~_k)|_inf) */
+#define HB_MPC_CERT_R_STAT 1      /* max_k |r~_k + P~_k dx_k + R~_k u~_k + B~_k' lambda_(k+1)|_inf */
+#define HB_MPC_CERT_OBJ 2         /* sum_k q~'dx + r~'u~ + 1/2 dx'Q~dx + u~'P~dx + 1/2 u~'R~u~ */
+#define HB_MPC_CERT_STEP_MAX 3    /* max_k |dx_k|_inf */
+#define HB_MPC_CERT_U_MAX 4       /* max_k |u~_k|_inf */
+#define HB_MPC_CERT_LAMBDA_MAX 5  /* max_k |lambda_k|_inf */
+#define HB_MPC_CERT_SCALE 6       /* max_k max(|r~_k|_inf, |P~_k dx_k|_inf, |R~_k u~_k|_inf, |B~_k' lambda_(k+1)|_inf) */
+#define HB_MPC_CERT_N_NODES 7     /* the n covered; 0 = not certified */
+#define HB_MPC_CERT_SIZE 8
+int32_t hb_mpc_get_certificate(hb_ctx* ctx, int32_t inst_begin, int32_t inst_count, double* cert /*[count][8]*/,
+                               double* costate /*[count][max_nodes+1][22] or NULL*/, double* u_til /*[count][max_nodes][12] or NULL*/);
+int32_t hb_mpc_get_lq(hb_ctx* ctx, int32_t inst, double* A /*[max_nodes][22][22]*/, double* B /*[..][22][12]*/, double* b /*[..][22]*/,
+                      double* Q /*[..][22][22], full symmetric*/, double* P /*[..][12][22]*/, double* R /*[..][12][12]*/,
+                      double* q /*[..][22]*/, double* r /*[..][12]*/, int32_t* n_til /*[max_nodes]*/);
 /* Pipelining of hb_step_resident: the batch is cut into n_chunks (1..8) instance ranges, each a linear
  * MPC -> publish -> WBC sequence on its own HIP stream so that the per-instance sweeps of one range overlap the
  * per-node kernels of another.  Results are identical for every n_chunks; hb_get_stats phase times are only

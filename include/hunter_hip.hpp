@@ -18,6 +18,7 @@
 // One Context = one GPU = `batch` independent robot instances.  batch == 1 reproduces the reference's shapes.
 #pragma once
 
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -207,6 +208,41 @@ class MpcMrtInterface {
     vector_t perf(size_t(ctx_.batch()) * 4, 0.0);
     ctx_.check(hb_mpc_get_performance(ctx_.get(), perf.data()), "hb_mpc_get_performance");
     return perf;
+  }
+  // KKT certificate of the stage QP of the last advanceMpc, computed on demand (hunter_hip.h, hb_mpc_get_certificate): instances
+  // [instBegin, instBegin + count), count < 0: to the end of the batch.  R_STAT is read relative to SCALE; an instance with
+  // N_NODES = 0 (status HB_INST_NAN) is not certified.
+  struct Certificate {
+    vector_t cert;     // [count][HB_MPC_CERT_SIZE] (indices HB_MPC_CERT_*)
+    vector_t costate;  // [count][maxNodes + 1][22]: lambda_0 .. lambda_n, zero behind
+    vector_t uTil;     // [count][maxNodes][12]: the projected inputs the forward sweep applied
+  };
+  Certificate certificate(int instBegin = 0, int count = -1) const {
+    if (count < 0) count = ctx_.batch() - instBegin;
+    const size_t n = size_t(std::max(count, 0)), N = size_t(ctx_.maxNodes());
+    Certificate c;
+    c.cert.assign(n * HB_MPC_CERT_SIZE, 0.0);
+    c.costate.assign(n * (N + 1) * HB_NX, 0.0);
+    c.uTil.assign(n * N * 12, 0.0);
+    ctx_.check(hb_mpc_get_certificate(ctx_.get(), instBegin, count, c.cert.data(), c.costate.data(), c.uTil.data()), "hb_mpc_get_certificate");
+    return c;
+  }
+  // The stage QP of one instance as the last advanceMpc left it (hb_mpc_get_lq), dense, [maxNodes] stages each, rows behind the
+  // instance's horizon zero: the OCP-QP layout A, B, b, Q, S = P, R, q, r.
+  struct StageQp {
+    vector_t A, B, b, Q, P, R, q, r;   // [maxNodes] x (22x22, 22x12, 22, 22x22, 12x22, 12x12, 22, 12)
+    std::vector<int32_t> nTil;         // [maxNodes]: projected inputs per stage (0 behind the horizon)
+  };
+  StageQp stageQp(int inst) const {
+    const size_t N = size_t(ctx_.maxNodes());
+    StageQp s;
+    s.A.assign(N * 484, 0.0); s.B.assign(N * 264, 0.0); s.b.assign(N * 22, 0.0); s.Q.assign(N * 484, 0.0);
+    s.P.assign(N * 264, 0.0); s.R.assign(N * 144, 0.0); s.q.assign(N * 22, 0.0); s.r.assign(N * 12, 0.0);
+    s.nTil.assign(N, 0);
+    ctx_.check(hb_mpc_get_lq(ctx_.get(), inst, s.A.data(), s.B.data(), s.b.data(), s.Q.data(), s.P.data(), s.R.data(), s.q.data(), s.r.data(),
+                             s.nTil.data()),
+               "hb_mpc_get_lq");
+    return s;
   }
   const Context& context() const { return ctx_; }
 
@@ -750,6 +786,28 @@ class ShardedSolver {
       std::copy(p.begin(), p.end(), perf.begin() + b * 4);
     });
     return perf;
+  }
+  // MpcMrtInterface::certificate for the whole batch, in instance order
+  MpcMrtInterface::Certificate certificate() {
+    const size_t N = size_t(maxNodes_);
+    MpcMrtInterface::Certificate c;
+    c.cert.assign(size_t(batch_) * HB_MPC_CERT_SIZE, 0.0);
+    c.costate.assign(size_t(batch_) * (N + 1) * HB_NX, 0.0);
+    c.uTil.assign(size_t(batch_) * N * 12, 0.0);
+    forEachShard([&](int g, size_t b, size_t) {
+      const MpcMrtInterface::Certificate s = mpc_[size_t(g)].certificate();
+      std::copy(s.cert.begin(), s.cert.end(), c.cert.begin() + b * HB_MPC_CERT_SIZE);
+      std::copy(s.costate.begin(), s.costate.end(), c.costate.begin() + b * (N + 1) * HB_NX);
+      std::copy(s.uTil.begin(), s.uTil.end(), c.uTil.begin() + b * N * 12);
+    });
+    return c;
+  }
+  // MpcMrtInterface::stageQp of instance `inst` of the whole batch: forwarded to its shard with the shard's instance offset
+  MpcMrtInterface::StageQp stageQp(int inst) {
+    if (inst < 0 || inst >= batch_) throw std::invalid_argument("[hunter_hip] ShardedSolver::stageQp: instance outside the batch");
+    size_t g = 0;
+    while (begin_[g + 1] <= inst) ++g;
+    return mpc_[g].stageQp(inst - begin_[g]);
   }
   // the hot part of LeggedController::update for the whole batch (controllerUpdate per shard); outputs in instance order
   void controllerUpdate(const vector_t& time, const vector_t& rbdStateMeasured, const std::vector<int32_t>* walkFlag, scalar_t period,

@@ -1,0 +1,95 @@
+// TEST HARNESS: one SQP iteration's LQ approximation and Riccati sweeps of one instance (as hostemu.cpp's emu_sqp_iteration) followed by
+// the certificate of the stage QP (hb_mpccert.hpp) and the stage-QP export (hb_lq.hpp rec_unpack), compiled for the host with one
+// emulated lane, for tests/test_mpc_certificate_host.py.  Not part of the product; the product path runs k_mpc_cert_nodes /
+// k_mpc_cert_sweep.
+#include <cmath>
+#include <cstring>
+#include <vector>
+#include "../../hunter_bipedal_control_amd/csrc/hb_host.hpp"
+#include "../../hunter_bipedal_control_amd/csrc/hb_mpccert.hpp"
+
+using namespace hb;
+namespace {
+struct HostCtx {
+  int lane = 0, nlanes = 1;
+  void sync() const {}
+};
+}  // namespace
+
+extern "C" {
+// x [N+1][22], u [N][22]: the iterate the problem is linearised at (x[0] is replaced by x0).  perturb_stage >= 0: rel (1 + |k~_0|) is
+// added to k~_0 of that stage before the forward sweep.  Outputs: dx [N+1][22], cert [8], costate [N+1][22], u_til [N][12] and the
+// stage QP A [N][22][22], B [N][22][12], b [N][22], Q [N][22][22], P [N][12][22], R [N][12][12], q [N][22], r [N][12], n_til [N].
+void emu_mpc_certificate(const hb_model* m, const hb_config* c, int N, const double* t, const int* mode, const double* xref,
+                         const double* swing, const double* x0, double* x, const double* u, int perturb_stage, double perturb_rel,
+                         double* dx_out, double* cert, double* costate, double* u_til, double* A, double* B, double* b, double* Q,
+                         double* P, double* R, double* q, double* r, int* n_til) {
+  DevModel d = make_dev_model(*m);
+  DevConfig dc = make_dev_config(*c, d);
+  HostCtx cx;
+  std::vector<double> recs(size_t(N) * REC_SIZE), gains(size_t(N) * GAIN_SIZE);
+  std::vector<double> lds(LqLds::total, 0.0);
+  for (int i = 0; i < 22; ++i) x[i] = x0[i];
+  for (int k = 0; k < N; ++k) {
+    NodeIn in{x + k * 22, u + k * 22, x + (k + 1) * 22, xref + k * 22, swing + k * 24, t[k + 1] - t[k], mode[k]};
+    lq_node(cx, d, dc, in, lds.data(), recs.data() + size_t(k) * REC_SIZE);
+  }
+  std::vector<double> rl(RicLds::total, 0.0);
+  for (int k = N - 1; k >= 0; --k) {
+    ric_stage(cx, rl.data(), recs.data() + size_t(k) * REC_SIZE);
+    riccati_bwd_node(cx, rl.data(), recs.data() + size_t(k) * REC_SIZE, gains.data() + size_t(k) * GAIN_SIZE);
+  }
+  if (perturb_stage >= 0 && perturb_stage < N) {
+    double& k0 = gains[size_t(perturb_stage) * GAIN_SIZE + 264];
+    k0 += perturb_rel * (1.0 + std::fabs(k0));
+  }
+  std::vector<double> fl(FwdLds::total, 0.0);
+  std::vector<double> dx(size_t(N + 1) * 22), du(size_t(N) * 22);
+  for (int k = 0; k < N; ++k)
+    riccati_fwd_node(cx, fl.data(), recs.data() + size_t(k) * REC_SIZE + REC_AB, recs.data() + size_t(k) * REC_SIZE + REC_KX,
+                     gains.data() + size_t(k) * GAIN_SIZE, dx.data() + k * 22, du.data() + k * 22);
+  for (int i = 0; i < 22; ++i) dx[size_t(N) * 22 + i] = fl[FwdLds::dx + i];
+  std::memcpy(dx_out, dx.data(), dx.size() * 8);
+  // the certificate: nodes, then the backward pass
+  std::vector<double> nodes(size_t(N) * CertNode::size, 0.0), cl(CertLds::total, 0.0), sl(CertSweepLds::total, 0.0);
+  for (int k = 0; k < N; ++k) {
+    mpc_cert_stage(cx, cl.data(), recs.data() + size_t(k) * REC_SIZE, gains.data() + size_t(k) * GAIN_SIZE, dx.data() + k * 22);
+    mpc_cert_node(cx, cl.data(), k == 0, nodes.data() + size_t(k) * CertNode::size);
+    for (int a = 0; a < 12; ++a) u_til[k * 12 + a] = nodes[size_t(k) * CertNode::size + CertNode::ut + a];
+  }
+  mpc_cert_sweep_init(cx, sl.data());
+  for (int i = 0; i < 22; ++i) costate[size_t(N) * 22 + i] = 0.0;
+  for (int k = N - 1; k >= 0; --k) {
+    for (int e = 0; e < REC_PR; ++e) sl[CertSweepLds::AB + e] = recs[size_t(k) * REC_SIZE + REC_AB + e];
+    const double* nd = nodes.data() + size_t(k) * CertNode::size;
+    mpc_cert_sweep_stage(cx, sl.data(), [nd](int col) { return col < 22 ? nd[CertNode::c + col] : nd[CertNode::d + col - REC_CU]; },
+                         costate + size_t(k) * 22);
+  }
+  mpc_cert_finish(cx, sl.data(), nodes.data(), N, true, cert);
+  for (int k = 0; k < N; ++k)
+    rec_unpack(recs.data() + size_t(k) * REC_SIZE, A + k * 484, B + k * 264, b + k * 22, Q + k * 484, P + k * 264, R + k * 144, q + k * 22,
+               r + k * 12, n_til + k);
+}
+// rec_unpack of one record of REC_SIZE doubles (the arrays of one stage)
+void emu_rec_unpack(const double* rec, double* A, double* B, double* b, double* Q, double* P, double* R, double* q, double* r, int* n_til) {
+  rec_unpack(rec, A, B, b, Q, P, R, q, r, n_til);
+}
+// the record index the accessors of hb_lq.hpp give: which = 0 rec_A(i, j), 1 rec_B, 2 rec_b(i), 3 rec_P, 4 rec_R, 5 rec_r(i),
+// 6 Q~(i, j) for i <= j (packed upper triangle), 7 q~(i), 8 n_f, 9 n_z; -1 otherwise
+int emu_rec_index(int which, int i, int j) {
+  switch (which) {
+    case 0: return rec_A(i, j);
+    case 1: return rec_B(i, j);
+    case 2: return rec_b(i);
+    case 3: return rec_P(i, j);
+    case 4: return rec_R(i, j);
+    case 5: return rec_r(i);
+    case 6: return REC_QT + rec_Qidx(i, j);
+    case 7: return REC_qT + i;
+    case 8: return REC_META;
+    case 9: return REC_META + 1;
+  }
+  return -1;
+}
+int emu_rec_size() { return REC_SIZE; }
+}
