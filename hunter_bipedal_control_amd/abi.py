@@ -147,6 +147,26 @@ def make_estimator_config(params: dict, **overrides) -> HbEstimatorConfig:
     return out
 
 
+class HbSensorConfig(C.Structure):
+    """hb_sensor_config (include/hunter_hip.h): noise of the plant's sensor model, hb_plant_set_sensor_model."""
+    _fields_ = [(k, C.c_double) for k in ("orientation_noise", "gyro_noise", "accel_noise", "joint_pos_noise", "joint_vel_noise",
+                                          "joint_torque_noise")] + [("seed", C.c_uint64), ("instance_offset", C.c_uint32),
+                                                                    ("reserved", C.c_int32)]
+
+
+def make_sensor_config(seed: int = 0, instance_offset: int = 0, **sigmas) -> HbSensorConfig:
+    """Standard deviations by channel name (orientation_noise [rad], gyro_noise, accel_noise, joint_pos_noise, joint_vel_noise,
+    joint_torque_noise; default 0 = ideal channel), the 64-bit seed and the global index of the context's instance 0."""
+    out = HbSensorConfig()
+    names = [k for k, _ in HbSensorConfig._fields_[:6]]
+    for k, v in sigmas.items():
+        if k not in names:
+            raise TypeError(f"make_sensor_config: unknown channel {k!r} (one of {names})")
+        setattr(out, k, float(v))
+    out.seed, out.instance_offset, out.reserved = int(seed) & 0xFFFFFFFFFFFFFFFF, int(instance_offset), 0
+    return out
+
+
 class HbJointGains(C.Structure):
     _fields_ = [(k, C.c_double) for k in ("kp_big_stance", "kp_big_swing", "kd_big", "kp_small_stance", "kp_small_swing", "kd_small",
                                           "kd_feet", "kp_position", "kd_position")]

@@ -20,6 +20,7 @@
 #include "hb_refgen.hpp"
 #include "hb_gait.hpp"
 #include "hb_plant.hpp"
+#include "hb_sensors.hpp"
 
 using namespace hb;
 
@@ -997,6 +998,13 @@ struct PlantBatch {
   int* contact;            // [B][4] staging of host contact flags
   double* rbd;             // [B][32] repacked state
   double baum, eps;
+  // what the last step applied (hb_plant_sense reads them; zero torque / all flags 1 before the first step)
+  double* tau_last;        // [B][10]
+  int* contact_last;       // [B][4]
+  // sensor arrays of hb_plant_sense: quat, gyro, accel, joint pos / vel / torque [B][4|3|3|10|10|10], contact flags [B][4]
+  double *s_quat, *s_gyro, *s_accel, *s_jp, *s_jv, *s_jt;
+  int* s_contact;
+  double *gyro_bias, *accel_bias;  // [B][3] each, or null (hb_plant_set_sensor_model)
 };
 
 __global__ __launch_bounds__(64) void k_plant(PlantBatch p, const DevModel* __restrict__ M, const double* tau, const int* contact,
@@ -1011,6 +1019,8 @@ __global__ __launch_bounds__(64) void k_plant(PlantBatch p, const DevModel* __re
     else { bool cf[HB_NC]; mode_flags(mode[i], cf); cflag[cx.lane] = cf[cx.lane] ? 1 : 0; }
   }
   __syncthreads();
+  if (cx.lane < HB_NJ) p.tau_last[10 * i + cx.lane] = tau[10 * i + cx.lane];
+  if (cx.lane < HB_NC) p.contact_last[4 * i + cx.lane] = cflag[cx.lane];
   plant_step(cx, *M, p.q + 16 * i, p.v + 16 * i, p.anchor + 12 * i, p.pinned + 4 * i, tau + 10 * i, cflag, p.baum, p.eps, dt, substeps, lds,
              p.lambda + 12 * i, p.vdot + 16 * i);
   if (cx.lane == 0) {
@@ -1037,7 +1047,56 @@ __global__ void k_plant_reset(PlantBatch p, const DevModel* __restrict__ M) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= p.B) return;
   plant_feet(*M, p.q + 16 * i, p.anchor + 12 * i);
-  for (int c = 0; c < HB_NC; ++c) p.pinned[4 * i + c] = 0;
+  for (int c = 0; c < HB_NC; ++c) { p.pinned[4 * i + c] = 0; p.contact_last[4 * i + c] = 1; }
+  for (int a = 0; a < 16; ++a) p.vdot[16 * i + a] = 0.0;
+  for (int a = 0; a < 12; ++a) p.lambda[12 * i + a] = 0.0;
+  for (int j = 0; j < HB_NJ; ++j) p.tau_last[10 * i + j] = 0.0;
+}
+
+// ---- sensors from the plant: one thread per instance, 64 instances per workgroup ---------------------------------------------------
+// The per-instance routine (hb_sensors.hpp plant_sense) reads and writes LDS rows; the workgroup moves its 64 instances' inputs and
+// outputs between LDS and global memory array by array, consecutive lanes on consecutive words (the arrays are instance-major, so a
+// workgroup's slice of each is one contiguous run) — a thread storing its own 10 doubles would stride the lanes 80 bytes apart.
+constexpr int kSenseThreads = 64;
+constexpr int kSenseIn = 16 + 16 + 3 + 10 + 3 + 3;   // q | v | vdot[0:3] | tau | gyro bias | accel bias
+constexpr int kSenseOut = 4 + 3 + 3 + 10 + 10 + 10;  // quat | gyro | accel | joint pos | vel | torque
+constexpr int kSenseRow = kSenseIn + kSenseOut;      // 91 doubles: an odd row length, the lanes' rows start in different LDS banks
+static_assert(kSenseRow % 2 == 1, "keep the LDS row length odd");
+__global__ __launch_bounds__(kSenseThreads) void k_plant_sense(PlantBatch p, const DevModel* __restrict__ M, hb_sensor_config K, int noisy,
+                                                               unsigned long long count) {
+  __shared__ double row[kSenseThreads * kSenseRow];
+  __shared__ int cfl[kSenseThreads * HB_NC];
+  const int i0 = blockIdx.x * kSenseThreads, n = min(kSenseThreads, p.B - i0), lane = threadIdx.x;
+  // per-instance width w of a global array at `src`, to / from LDS column `col`
+  auto load = [&](const double* src, int w, int col) {
+    for (int e = lane; e < n * w; e += kSenseThreads) row[(e / w) * kSenseRow + col + e % w] = src[size_t(i0) * w + e];
+  };
+  auto store = [&](double* dst, int w, int col) {
+    for (int e = lane; e < n * w; e += kSenseThreads) dst[size_t(i0) * w + e] = row[(e / w) * kSenseRow + col + e % w];
+  };
+  load(p.q, 16, 0);
+  load(p.v, 16, 16);
+  for (int e = lane; e < n * 3; e += kSenseThreads) row[(e / 3) * kSenseRow + 32 + e % 3] = p.vdot[size_t(i0 + e / 3) * 16 + e % 3];
+  load(p.tau_last, 10, 35);
+  if (p.gyro_bias) load(p.gyro_bias, 3, 45);
+  if (p.accel_bias) load(p.accel_bias, 3, 48);
+  for (int e = lane; e < n * HB_NC; e += kSenseThreads) cfl[e] = p.contact_last[size_t(i0) * HB_NC + e];
+  __syncthreads();
+  if (lane < n) {
+    double* r = row + lane * kSenseRow;
+    double* o = r + kSenseIn;
+    const SenseOut out{o, o + 4, o + 7, o + 10, o + 20, o + 30, cfl + lane * HB_NC};  // (the flags pass through in place)
+    plant_sense(M->gravity, r, r + 16, r + 32, r + 35, cfl + lane * HB_NC, K, noisy != 0, p.gyro_bias ? r + 45 : nullptr,
+                p.accel_bias ? r + 48 : nullptr, K.instance_offset + uint32_t(i0 + lane), count, out);
+  }
+  __syncthreads();
+  store(p.s_quat, 4, kSenseIn);
+  store(p.s_gyro, 3, kSenseIn + 4);
+  store(p.s_accel, 3, kSenseIn + 7);
+  store(p.s_jp, 10, kSenseIn + 10);
+  store(p.s_jv, 10, kSenseIn + 20);
+  store(p.s_jt, 10, kSenseIn + 30);
+  for (int e = lane; e < n * HB_NC; e += kSenseThreads) p.s_contact[size_t(i0) * HB_NC + e] = cfl[e];
 }
 
 // ---- joint command law: one thread per instance, joints in the reference's order -----------------------------------
@@ -1345,6 +1404,13 @@ struct hb_ctx {
   int* lcm_bad = nullptr;
   PlantBatch plant{};
   bool plant_ready = false;
+  // sensor model of the plant (hb_plant_set_sensor_model): sens_noisy = a configuration with at least one sigma > 0 is in force;
+  // sense_count = hb_plant_sense calls since the model was set (the noise counter); sensed = the sensor arrays hold a reading of this
+  // plant (cleared by hb_plant_reset)
+  hb_sensor_config sens_cfg{};
+  bool sens_noisy = false, sensed = false;
+  uint64_t sense_count = 0;
+  double *sens_gyro_bias_buf = nullptr, *sens_accel_bias_buf = nullptr;  // [B][3] each, allocated on the first non-null bias
   // reference generation (allocated on the first hb_refgen_reset)
   RefgenBatch rg{};
   hb_refgen_config rg_cfg{};
@@ -1426,7 +1492,7 @@ static hipError_t dalloc(hb_ctx* ctx, T** p, size_t n) {
 
 extern "C" {
 
-int32_t hb_version(void) { return 201; }
+int32_t hb_version(void) { return 202; }
 
 const char* hb_last_error(const hb_ctx* ctx) { return ctx ? ctx->err.c_str() : g_create_error.c_str(); }
 
@@ -1709,8 +1775,18 @@ int32_t hb_plant_reset(hb_ctx* ctx, const double* q0, const double* v0, double b
     HB_HIP(dalloc(ctx, &p.tau, B * 10));
     HB_HIP(dalloc(ctx, &p.contact, B * 4));
     HB_HIP(dalloc(ctx, &p.rbd, B * HB_NRBD));
+    HB_HIP(dalloc(ctx, &p.tau_last, B * 10));
+    HB_HIP(dalloc(ctx, &p.contact_last, B * 4));
+    HB_HIP(dalloc(ctx, &p.s_quat, B * 4));
+    HB_HIP(dalloc(ctx, &p.s_gyro, B * 3));
+    HB_HIP(dalloc(ctx, &p.s_accel, B * 3));
+    HB_HIP(dalloc(ctx, &p.s_jp, B * 10));
+    HB_HIP(dalloc(ctx, &p.s_jv, B * 10));
+    HB_HIP(dalloc(ctx, &p.s_jt, B * 10));
+    HB_HIP(dalloc(ctx, &p.s_contact, B * 4));
     p.B = ctx->B;
   }
+  ctx->sensed = false;
   p.baum = baumgarte;
   p.eps = eps;
   HB_HIP(hipMemcpy(p.q, q0, B * 16 * 8, hipMemcpyHostToDevice));
@@ -1764,6 +1840,70 @@ int32_t hb_plant_get_state(hb_ctx* ctx, double* q, double* v, double* rbd, doubl
   if (rbd) HB_HIP(hipMemcpy(rbd, p.rbd, B * HB_NRBD * 8, hipMemcpyDeviceToHost));
   if (lambda) HB_HIP(hipMemcpy(lambda, p.lambda, B * 12 * 8, hipMemcpyDeviceToHost));
   if (vdot) HB_HIP(hipMemcpy(vdot, p.vdot, B * 16 * 8, hipMemcpyDeviceToHost));
+  return HB_OK;
+}
+
+int32_t hb_plant_set_sensor_model(hb_ctx* ctx, const hb_sensor_config* cfg, const double* gyro_bias, const double* accel_bias) {
+  if (ctx) lazy_join(ctx);
+  if (!ctx) return HB_ERR_ARG;
+  if (!ctx->plant_ready) {
+    ctx->err = "hb_plant_set_sensor_model: call hb_plant_reset first (the sensor arrays belong to the plant)";
+    return HB_ERR_STATE;
+  }
+  if (cfg && !sensor_config_valid(*cfg)) {
+    ctx->err = "hb_plant_set_sensor_model: every noise standard deviation must be finite and >= 0, and `reserved` 0";
+    return HB_ERR_ARG;
+  }
+  HB_HIP(hipSetDevice(ctx->device));
+  const size_t B = ctx->B;
+  PlantBatch& p = ctx->plant;
+  HB_HIP(hipStreamSynchronize(ctx->s_wbc));  // (an earlier reading may still be using the biases)
+  // the bias arrays are kept once allocated; a null pointer in the batch means "no bias"
+  const double* src[2] = {gyro_bias, accel_bias};
+  double** dst[2] = {&p.gyro_bias, &p.accel_bias};
+  double** store[2] = {&ctx->sens_gyro_bias_buf, &ctx->sens_accel_bias_buf};
+  for (int k = 0; k < 2; ++k) {
+    if (src[k]) {
+      if (!*store[k]) HB_HIP(dalloc(ctx, store[k], B * 3));
+      HB_HIP(hipMemcpy(*store[k], src[k], B * 3 * 8, hipMemcpyHostToDevice));
+    }
+    *dst[k] = src[k] ? *store[k] : nullptr;
+  }
+  ctx->sens_cfg = cfg ? *cfg : hb_sensor_config{};
+  ctx->sens_noisy = cfg && (cfg->orientation_noise > 0.0 || cfg->gyro_noise > 0.0 || cfg->accel_noise > 0.0 || cfg->joint_pos_noise > 0.0 ||
+                            cfg->joint_vel_noise > 0.0 || cfg->joint_torque_noise > 0.0);
+  ctx->sense_count = 0;
+  return HB_OK;
+}
+
+int32_t hb_plant_sense(hb_ctx* ctx, double* quat, double* ang_vel_local, double* lin_acc_local, double* joint_pos, double* joint_vel,
+                       double* joint_torque, int32_t* contact_flag) {
+  if (ctx) lazy_join(ctx);
+  if (!ctx) return HB_ERR_ARG;
+  if (!ctx->plant_ready) {
+    ctx->err = "hb_plant_sense: call hb_plant_reset first";
+    return HB_ERR_STATE;
+  }
+  HB_HIP(hipSetDevice(ctx->device));
+  const size_t B = ctx->B;
+  const PlantBatch& p = ctx->plant;
+  hipStream_t s = ctx->s_wbc;  // behind the plant step, in front of the estimator
+  hipLaunchKernelGGL(k_plant_sense, dim3((ctx->B + kSenseThreads - 1) / kSenseThreads), dim3(kSenseThreads), 0, s, p, ctx->dmodel, ctx->sens_cfg,
+                     ctx->sens_noisy ? 1 : 0, static_cast<unsigned long long>(ctx->sense_count));
+  HB_HIP(hipGetLastError());
+  ++ctx->sense_count;
+  ctx->sensed = true;
+  double* const outs[6] = {quat, ang_vel_local, lin_acc_local, joint_pos, joint_vel, joint_torque};
+  const double* const dev[6] = {p.s_quat, p.s_gyro, p.s_accel, p.s_jp, p.s_jv, p.s_jt};
+  const size_t width[6] = {4, 3, 3, 10, 10, 10};
+  bool any = contact_flag != nullptr;
+  for (int k = 0; k < 6; ++k)
+    if (outs[k]) {
+      HB_HIP(hipMemcpyAsync(outs[k], dev[k], B * width[k] * 8, hipMemcpyDeviceToHost, s));
+      any = true;
+    }
+  if (contact_flag) HB_HIP(hipMemcpyAsync(contact_flag, p.s_contact, B * 4 * sizeof(int), hipMemcpyDeviceToHost, s));
+  if (any) HB_HIP(hipStreamSynchronize(s));  // without host outputs the call is enqueue-only
   return HB_OK;
 }
 
@@ -2186,6 +2326,12 @@ int32_t hb_estimator_reset(hb_ctx* ctx, const hb_estimator_config* cfg, const do
   return HB_OK;
 }
 
+static void launch_contact_force(const hb_ctx* ctx, double gama, double beta, const double* rbd_dev, const double* tau_dev, hipStream_t s) {
+  const EstBatch& e = ctx->est;
+  hipLaunchKernelGGL(k_contact_force, dim3((ctx->B + kCfThreads - 1) / kCfThreads), dim3(kCfThreads), 0, s, ctx->B, ctx->dmodel, gama, beta, rbd_dev,
+                     tau_dev, e.cf_z, e.cf_dist, e.cf_out);
+}
+
 int32_t hb_estimator_contact_force(hb_ctx* ctx, double dt, const double* rbd, const double* joint_torque, double* est_disturbance_torque,
                                    double* est_contact_force) {
   if (ctx) lazy_join(ctx);
@@ -2206,8 +2352,7 @@ int32_t hb_estimator_contact_force(hb_ctx* ctx, double dt, const double* rbd, co
     HB_HIP(hipMemcpyAsync(e.cf_rbd, rbd, B * HB_NRBD * 8, hipMemcpyHostToDevice, s));
     rbd_dev = e.cf_rbd;
   }
-  hipLaunchKernelGGL(k_contact_force, dim3((ctx->B + kCfThreads - 1) / kCfThreads), dim3(kCfThreads), 0, s, ctx->B, ctx->dmodel, gama, beta, rbd_dev,
-                     e.cf_tau, e.cf_z, e.cf_dist, e.cf_out);
+  launch_contact_force(ctx, gama, beta, rbd_dev, e.cf_tau, s);
   HB_HIP(hipGetLastError());
   if (est_disturbance_torque) HB_HIP(hipMemcpyAsync(est_disturbance_torque, e.cf_dist, B * HB_NV * 8, hipMemcpyDeviceToHost, s));
   if (est_contact_force) HB_HIP(hipMemcpyAsync(est_contact_force, e.cf_out, B * 16 * 8, hipMemcpyDeviceToHost, s));
@@ -2215,10 +2360,9 @@ int32_t hb_estimator_contact_force(hb_ctx* ctx, double dt, const double* rbd, co
   return HB_OK;
 }
 
-// filter step on the inputs already in ctx->est (device), outputs as in hb_estimator_update
-static int32_t estimator_run(hb_ctx* ctx, double dt, int32_t to_resident, double* rbd, double* x_state) {
+// filter step on the inputs e points to (device; ctx->est: its own upload buffers), outputs as in hb_estimator_update
+static int32_t estimator_run(hb_ctx* ctx, EstBatch e, double dt, int32_t to_resident, double* rbd, double* x_state) {
   const size_t B = ctx->B;
-  EstBatch e = ctx->est;
   hipStream_t s = ctx->s_wbc;
   e.res_rbd = to_resident ? ctx->w.rbd : nullptr;
   e.res_x0 = to_resident ? ctx->b.x0 : nullptr;
@@ -2244,7 +2388,47 @@ int32_t hb_estimator_update(hb_ctx* ctx, double dt, const double* quat, const do
   const void* const src[6] = {quat, ang_vel_local, lin_acc_local, joint_pos, joint_vel, contact_flag};
   // (enqueue-only form: the sensor arrays go through pinned staging and are the caller's again on return)
   HB_TRY(upload_sensors(ctx, dst, src, !(rbd || x_state), ctx->s_wbc));  // the estimator belongs to the control-thread side (LeggedController::update)
-  return estimator_run(ctx, dt, to_resident, rbd, x_state);
+  return estimator_run(ctx, ctx->est, dt, to_resident, rbd, x_state);
+}
+
+// The two estimator calls on the sensor arrays hb_plant_sense left on the device.
+static int32_t sensed_ready(hb_ctx* ctx, const char* who) {
+  const char* why = !ctx->plant_ready ? "call hb_plant_reset first"
+                    : !ctx->est_ready ? "call hb_estimator_reset first"
+                    : !ctx->sensed    ? "no sensor reading on the device yet (hb_plant_sense after hb_plant_reset)"
+                                      : nullptr;
+  if (!why) return HB_OK;
+  ctx->err = std::string(who) + ": " + why;
+  return HB_ERR_STATE;
+}
+
+int32_t hb_estimator_update_resident(hb_ctx* ctx, double dt, int32_t to_resident, double* rbd, double* x_state) {
+  if (ctx) lazy_join(ctx);
+  if (!ctx || !(dt > 0.0)) return HB_ERR_ARG;
+  HB_TRY(sensed_ready(ctx, "hb_estimator_update_resident"));
+  HB_HIP(hipSetDevice(ctx->device));
+  const PlantBatch& p = ctx->plant;
+  EstBatch e = ctx->est;  // the same kernel with its input pointers aimed at the plant's sensor arrays: nothing is copied
+  e.quat = p.s_quat; e.w_local = p.s_gyro; e.a_local = p.s_accel; e.qj = p.s_jp; e.qdj = p.s_jv; e.contact = p.s_contact;
+  return estimator_run(ctx, e, dt, to_resident, rbd, x_state);
+}
+
+int32_t hb_estimator_contact_force_resident(hb_ctx* ctx, double dt, double* est_disturbance_torque, double* est_contact_force) {
+  if (ctx) lazy_join(ctx);
+  if (!ctx || !(dt > 0.0)) return HB_ERR_ARG;
+  HB_TRY(sensed_ready(ctx, "hb_estimator_contact_force_resident"));
+  HB_HIP(hipSetDevice(ctx->device));
+  const size_t B = ctx->B;
+  const EstBatch& e = ctx->est;
+  hipStream_t s = ctx->s_wbc;
+  if (dt > 1.0) dt = 0.002;     // (StateEstimateBase.cpp:133-134)
+  const double gama = std::exp(-ctx->est_cfg.contact_force_cutoff_frequency * dt), beta = (1.0 - gama) / (gama * dt);
+  launch_contact_force(ctx, gama, beta, e.rbd, ctx->plant.s_jt, s);
+  HB_HIP(hipGetLastError());
+  if (est_disturbance_torque) HB_HIP(hipMemcpyAsync(est_disturbance_torque, e.cf_dist, B * HB_NV * 8, hipMemcpyDeviceToHost, s));
+  if (est_contact_force) HB_HIP(hipMemcpyAsync(est_contact_force, e.cf_out, B * 16 * 8, hipMemcpyDeviceToHost, s));
+  if (est_disturbance_torque || est_contact_force) HB_HIP(hipStreamSynchronize(s));  // without host outputs the call is enqueue-only
+  return HB_OK;
 }
 
 // ---- LCM wire format (include/hunter_lcm.h) -----------------------------------------------------------------------
@@ -2359,7 +2543,7 @@ int32_t hb_estimator_update_lcm(hb_ctx* ctx, double dt, const uint8_t* low_state
     return HB_ERR_ARG;
   }
   if (timestamp) HB_HIP(hipMemcpy(timestamp, ctx->lcm_ts, B * 8, hipMemcpyDeviceToHost));
-  return estimator_run(ctx, dt, to_resident, rbd, x_state);
+  return estimator_run(ctx, ctx->est, dt, to_resident, rbd, x_state);
 }
 
 int32_t hb_estimator_get_filter(hb_ctx* ctx, double* x_hat, double* P) {

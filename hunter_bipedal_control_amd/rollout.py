@@ -5,7 +5,9 @@ policy -> WBC -> joint command -> plant, the loop of LeggedController::update (l
 Everything between the plant's state and the joint torque runs on the device (reference generation, SQP, policy
 evaluation, WBC, joint command law); the plant stub integrates either on the device (ResidentLoop, hb_plant_step) or on the host (DeviceLoop, with a plant object the
 caller injects — the tests pass the numpy twin oracle/plant.py)  with the device's rigid-body
-terms.  The observation is the plant's true state (no estimator noise); `hb_estimator_update` can be put in its place.
+terms.  The observation is the plant's true state by default; with use_estimator it is the state estimator's output on the plant's
+sensors — host arrays in DeviceLoop (ideal sensors), device arrays in ResidentLoop (hb_plant_sense + hb_estimator_update_resident: no
+sensor crosses PCIe; optional biases and seeded noise, hb_plant_set_sensor_model).
 """
 from __future__ import annotations
 
@@ -121,11 +123,16 @@ class DeviceLoop:
 class ResidentLoop:
     """The same loop with the plant stub on the device too (hb_plant_step): nothing but the reference-generation time
     stamps, the commands and the mode-schedule windows crosses PCIe — and with device_gait not even the windows: the gait
-    scheduler and the command-driven gait selection (walkGait) run per instance on the device (hb_gait_reset)."""
+    scheduler and the command-driven gait selection (walkGait) run per instance on the device (hb_gait_reset).
+
+    use_estimator closes the loop through the state estimator on the device as well: per tick hb_plant_sense turns the plant's state into
+    IMU, encoder, effort and contact-flag arrays, hb_estimator_update_resident filters them into the resident observation, then MPC (every
+    mpc_every ticks), WBC, joint command and the plant step follow as before.  sensor_config (abi.make_sensor_config) adds seeded noise,
+    sensor_bias = (gyro_bias, accel_bias) [B][3] constant biases; both None: ideal sensors."""
 
     def __init__(self, solver, params: dict, gaits, cmd_vel, n_intervals: int = 100, mpc_every: int = 8, dt: float = 0.002,
                  t_gait_start: float = 0.3, joint_ik: bool = True, substeps: int = 4, static_schedule_until: float = 0.0,
-                 device_gait: bool = False):
+                 device_gait: bool = False, use_estimator: bool = False, sensor_config=None, sensor_bias=None):
         """static_schedule_until > 0: the mode schedules are uploaded once for [-1, static_schedule_until] (at most
         HB_MAX_EVENTS events) instead of a sliding window per MPC call — no per-call host work for large batches.
         device_gait: the device gait manager produces the windows; step() builds no per-instance list and uploads no schedule, and
@@ -164,6 +171,19 @@ class ResidentLoop:
         rbd[:, 0:3], rbd[:, 3:6], rbd[:, 6:16] = q0[:, 3:6], q0[:, 0:3], q0[:, 6:]
         solver.set_resident_inputs(solver.centroidal_state_from_rbd(rbd), np.zeros(self.B), rbd)
         self.started = False
+        self.use_estimator = use_estimator
+        if use_estimator:
+            # the filter starts where DeviceLoop starts it: base position and the four contact points of q0
+            x = np.zeros((self.B, 22))
+            x[:, 6:9], x[:, 9:12], x[:, 12:] = q0[:, 0:3], q0[:, 3:6], q0[:, 6:]
+            xh0 = np.zeros((self.B, 18))
+            xh0[:, 0:3] = q0[:, 0:3]
+            xh0[:, 6:18] = np.asarray(solver.eval_foot_kinematics(x, np.zeros((self.B, 22)))[0]).reshape(self.B, 12)
+            solver.estimator_reset(abi.make_estimator_config(params), xh0)
+            gyro_bias, accel_bias = sensor_bias if sensor_bias is not None else (None, None)
+            solver.plant_set_sensor_model(sensor_config, gyro_bias, accel_bias)
+        elif sensor_config is not None or sensor_bias is not None:
+            raise ValueError("sensor_config / sensor_bias belong to use_estimator=True")
         self.static = static_schedule_until > 0.0
         if self.static:
             solver.refgen_set_schedule([schedule_window(ms, -1.0, static_schedule_until) for ms in self.schedules])
@@ -180,6 +200,10 @@ class ResidentLoop:
         """want_outputs: the WBC result and the joint command of the tick come back to the host (self.last = dict(out, cmd), as
         DeviceLoop keeps them) instead of staying on the device; the loop itself is the same."""
         s = self.s
+        if self.use_estimator:
+            s.plant_sense()
+            s.estimator_update_resident(self.dt, to_resident=True)
+            s.set_resident_time(np.full(self.B, self.t))       # (the estimator knows no clock; the plant step below leaves it alone)
         if self.tick % self.mpc_every == 0:
             if not self.static and not self.device_gait:
                 s.refgen_set_schedule(self._windows())
@@ -196,6 +220,6 @@ class ResidentLoop:
         else:
             s.wbc_update_resident(self.dt)
             s.joint_command_resident(self.gains, self.dt)
-        s.plant_step(None, None, self.dt, self.substeps, to_resident=True)
+        s.plant_step(None, None, self.dt, self.substeps, to_resident=not self.use_estimator)
         self.t += self.dt
         self.tick += 1

@@ -31,6 +31,7 @@ ABI_SYMBOLS = [
     "hb_wbc_set_certificate", "hb_wbc_get_certificate", "hb_hwbc_set_certificate", "hb_hwbc_get_certificate",
     "hb_mpc_get_certificate", "hb_mpc_get_lq",
     "hb_refgen_get_schedule", "hb_gait_reset", "hb_gait_disable", "hb_gait_insert_template", "hb_gait_get_state",
+    "hb_plant_set_sensor_model", "hb_plant_sense", "hb_estimator_update_resident", "hb_estimator_contact_force_resident",
 ]
 # include/hunter_lcm.h
 LCM_SYMBOLS = ["hb_lcm_fingerprint", "hb_lcm_encoded_size", "hb_lcm_field_count", "hb_lcm_encode", "hb_lcm_decode", "hb_lcm_frame", "hb_lcm_unframe",
@@ -248,6 +249,42 @@ class HunterSolver:
         self._check(self.lib.hb_plant_get_state(self.ctx, _p(out["q"]), _p(out["v"]), _p(out["rbd"]), _p(out["lam"]), _p(out["vdot"])),
                     "hb_plant_get_state")
         return out
+
+    # ---- sensors from the plant (hb_plant_sense) and the estimator on them ------------------------------------------------
+    def plant_set_sensor_model(self, sensor_cfg: "abi.HbSensorConfig" = None, gyro_bias=None, accel_bias=None):
+        """sensor_cfg None: ideal sensors; gyro_bias / accel_bias [B][3] or None (zero).  Restarts the noise counter."""
+        gb = None if gyro_bias is None else _f64(gyro_bias, (self.B, 3))
+        ab = None if accel_bias is None else _f64(accel_bias, (self.B, 3))
+        self._check(self.lib.hb_plant_set_sensor_model(self.ctx, None if sensor_cfg is None else C.byref(sensor_cfg), _p(gb), _p(ab)),
+                    "hb_plant_set_sensor_model")
+
+    def plant_sense(self, want_outputs=False):
+        """One sensor reading of every instance, left on the device for estimator_update_resident.  want_outputs: -> dict(quat[B][4],
+        ang_vel_local[B][3], lin_acc_local[B][3], joint_pos / joint_vel / joint_torque [B][10], contact_flag[B][4] int32); otherwise
+        the call is enqueue-only and returns None."""
+        out = None
+        if want_outputs:
+            out = dict(quat=np.zeros((self.B, 4)), ang_vel_local=np.zeros((self.B, 3)), lin_acc_local=np.zeros((self.B, 3)),
+                       joint_pos=np.zeros((self.B, 10)), joint_vel=np.zeros((self.B, 10)), joint_torque=np.zeros((self.B, 10)),
+                       contact_flag=np.zeros((self.B, 4), dtype=np.int32))
+        ptrs = [None] * 7 if out is None else [_p(a) for a in out.values()]
+        self._check(self.lib.hb_plant_sense(self.ctx, *ptrs), "hb_plant_sense")
+        return out
+
+    def estimator_update_resident(self, dt, to_resident=False, want_outputs=False):
+        """hb_estimator_update on the arrays the last plant_sense left on the device -> (rbd[B][32], x_state[B][22]), or (None, None)
+        for the enqueue-only form."""
+        rbd, x = (np.zeros((self.B, 32)), np.zeros((self.B, 22))) if want_outputs else (None, None)
+        self._check(self.lib.hb_estimator_update_resident(self.ctx, C.c_double(dt), C.c_int32(1 if to_resident else 0), _p(rbd), _p(x)),
+                    "hb_estimator_update_resident")
+        return rbd, x
+
+    def estimator_contact_force_resident(self, dt, want_outputs=True):
+        """hb_estimator_contact_force(rbd = None) on the sensed joint torque -> (estDisturbancetorque_ [B][16], estContactforce_ [B][16])."""
+        dist, cf = (np.zeros((self.B, 16)), np.zeros((self.B, 16))) if want_outputs else (None, None)
+        self._check(self.lib.hb_estimator_contact_force_resident(self.ctx, C.c_double(dt), _p(dist), _p(cf)),
+                    "hb_estimator_contact_force_resident")
+        return dist, cf
 
     # ---- device-resident stepping -----------------------------------------------------------------
     def set_resident_inputs(self, x0, t_now, rbd, walk_flag=None):

@@ -250,8 +250,46 @@ int32_t hb_plant_reset(hb_ctx* ctx, const double* q0 /*[batch][16]*/, const doub
 int32_t hb_plant_step(hb_ctx* ctx, const double* tau, const int32_t* contact, double dt, int32_t substeps,
                       int32_t to_resident);
 /* State to the host (any may be NULL): q[batch][16], v[batch][16], rbd[batch][32], lambda[batch][12] (last contact
- * forces), vdot[batch][16] (last acceleration). */
+ * forces), vdot[batch][16] (last acceleration); lambda and vdot are zero between hb_plant_reset and the first step. */
 int32_t hb_plant_get_state(hb_ctx* ctx, double* q, double* v, double* rbd, double* lambda, double* vdot);
+
+/* ---- sensors from the plant: what LeggedController::updateStateEstimation reads, computed on the device -----------
+ * hb_plant_sense turns the plant's state into the sensor arrays of hb_estimator_update and leaves them on the device
+ * (plant-owned arrays [batch][4|3|3|10|10|10] and int [batch][4]); hb_estimator_update_resident /
+ * hb_estimator_contact_force_resident consume them where they lie, so that plant -> sensors -> estimator -> MPC -> WBC -> joint
+ * command -> plant never crosses PCIe.  Per instance, from q, v, the last acceleration vdot, and the torque and contact flags the last
+ * hb_plant_step applied (before the first step after hb_plant_reset: vdot = 0, torque = 0, all four flags 1):
+ *   quat[4] (x y z w) of the base from the ZYX half angles (c. / s. = cos / sin of yaw/2, pitch/2, roll/2):
+ *       x = cz cy sx - sz sy cx,  y = cz sy cx + sz cy sx,  z = sz cy cx - cz sy sx,  w = cz cy cx + sz sy sx,  negated if w < 0;
+ *   ang_vel_local[3] = R' E(zyx) v[3:6];   lin_acc_local[3] = R' (vdot[0:3] + g e_z) with g = hb_model.gravity (specific force);
+ *   joint_pos[10] = q[6:];  joint_vel[10] = v[6:];  joint_torque[10] = the torque the last hb_plant_step integrated (the host tau or the
+ *   hb_joint_command torque);  contact_flag[4] = the flags that step applied.
+ * Imperfections (hb_plant_set_sensor_model): constant per-instance biases on the gyroscope and the accelerometer, added first, then
+ * zero-mean Gaussian noise.  The generator is Philox4x32-10, counter based, without state on the device:
+ *   key = (seed low 32, seed high 32);  counter = (instance_offset + i, sense_count low 32, sense_count high 32, block), where
+ *   sense_count is the number of hb_plant_sense calls of this context since hb_plant_set_sensor_model (a 64-bit host count).
+ *   A block of four words gives four standard normals by Box-Muller with u = (word + 0.5) 2^-32:
+ *   (w0, w1) -> r cos(2 pi u1), r sin(2 pi u1), r = sqrt(-2 ln u0); (w2, w3) likewise.  Normal n is lane n % 4 of block n / 4:
+ *   orientation 0-2, gyro 3-5, accel 6-8, joint_pos 9-18, joint_vel 19-28, joint_torque 29-38.
+ * A channel with sigma = 0 is the ideal value bit for bit whatever the other channels are set to; blocks no channel needs are not
+ * generated.  Contact flags are never corrupted.  A seed of 0 is valid.  Same seed, same instance_offset + i, same sense_count: same
+ * bits, so a shard (instance_offset = global index of its instance 0) reproduces its slice of the unsharded batch. */
+typedef struct hb_sensor_config {
+  double orientation_noise;   /* rad: rotation vector delta = sigma * z (3 normals), quat <- quat (x) [delta/|delta| sin(|delta|/2), cos(|delta|/2)], w >= 0 */
+  double gyro_noise, accel_noise, joint_pos_noise, joint_vel_noise, joint_torque_noise;   /* standard deviations, additive */
+  uint64_t seed;
+  uint32_t instance_offset;   /* global index of instance 0 of this context: a shard reproduces the unsharded batch */
+  int32_t reserved;           /* 0 */
+} hb_sensor_config;
+/* cfg NULL: ideal sensors (no noise).  gyro_bias / accel_bias [batch][3], either may be NULL = zero.  Restarts sense_count at 0.
+ * The model survives hb_plant_reset.  HB_ERR_STATE before hb_plant_reset; HB_ERR_ARG for a negative or non-finite sigma or a nonzero
+ * `reserved` (the model in force is kept). */
+int32_t hb_plant_set_sensor_model(hb_ctx* ctx, const hb_sensor_config* cfg, const double* gyro_bias, const double* accel_bias);
+/* One reading of every instance on the WBC stream, left on the device; host out (any may be NULL): quat[batch][4],
+ * ang_vel_local[batch][3], lin_acc_local[batch][3], joint_pos / joint_vel / joint_torque [batch][10], contact_flag[batch][4].  With every
+ * pointer NULL the call is enqueue-only.  HB_ERR_STATE before hb_plant_reset. */
+int32_t hb_plant_sense(hb_ctx* ctx, double* quat, double* ang_vel_local, double* lin_acc_local, double* joint_pos, double* joint_vel,
+                       double* joint_torque, int32_t* contact_flag);
 
 /* ---- device-resident stepping (bench / rollouts; inputs already in HBM) ------------------------
  * hb_step_resident runs hb_mpc_solve(NULL) + hb_mpc_publish + WBC on device-resident t_now/rbd that
@@ -434,6 +472,13 @@ int32_t hb_estimator_update(hb_ctx* ctx, double dt, const double* quat, const do
  * never called); they are provided for the same diagnostics. */
 int32_t hb_estimator_contact_force(hb_ctx* ctx, double dt, const double* rbd, const double* joint_torque,
                                    double* est_disturbance_torque, double* est_contact_force);
+/* The two calls above on the arrays the last hb_plant_sense left on the device — no sensor crosses PCIe, nothing is copied: the same
+ * filter kernel reads the plant's sensor arrays in place.  hb_estimator_update_resident is hb_estimator_update (rbd / x_state /
+ * to_resident as there; without host outputs enqueue-only); hb_estimator_contact_force_resident is
+ * hb_estimator_contact_force(rbd = NULL) on the sensed joint torque (without host outputs enqueue-only).  Both run on the WBC
+ * stream.  HB_ERR_STATE before hb_plant_reset, before hb_estimator_reset, or before the first hb_plant_sense after hb_plant_reset. */
+int32_t hb_estimator_update_resident(hb_ctx* ctx, double dt, int32_t to_resident, double* rbd, double* x_state);
+int32_t hb_estimator_contact_force_resident(hb_ctx* ctx, double dt, double* est_disturbance_torque, double* est_contact_force);
 /* Filter state to the host (either may be NULL): x_hat[batch][18], P[batch][18][18]. */
 int32_t hb_estimator_get_filter(hb_ctx* ctx, double* x_hat, double* P);
 
