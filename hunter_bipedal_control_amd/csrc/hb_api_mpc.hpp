@@ -1,0 +1,337 @@
+// Host side, part 2: the MPC — node tables, cold and warm start, the SQP iteration and its launchers, read-back of the iterate,
+// KKT certificate and stage-QP export.
+#pragma once
+
+extern "C" {
+
+// Before the node tables of b are overwritten while an iterate exists: keeps the grid that iterate lives on (`copy`; tp / modep /
+// np_nodes) and marks instances [i0, i0 + cnt) of b dirty, so that the next solve brings them onto the new tables (k_warm_shift).
+static int32_t launch_grid_save(hb_ctx* ctx, Batch b, bool copy, int i0, int cnt, hipStream_t s) {
+  if (copy) {
+    const Range all{0, b.B};
+    HB_TRY(copy_field(ctx, hipMemcpyDeviceToDevice, b.t, b, b.tp, all, &s));
+    HB_TRY(copy_field(ctx, hipMemcpyDeviceToDevice, b.mode, b, b.modep, all, &s));
+    HB_TRY(copy_field(ctx, hipMemcpyDeviceToDevice, b.n_nodes, b, b.np_nodes, all, &s));
+  }
+  HB_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(b.grid_dirty + i0), 1, size_t(cnt), s));
+  return HB_OK;
+}
+
+// The iterate of b brought onto the current node tables (the previous iterate xp / up is the source).
+static void launch_warm_start(const hb_ctx* ctx, const Batch& b, hipStream_t s) {
+  hipLaunchKernelGGL(k_warm_shift, dim3(((ctx->Nmax + 1) * HB_NX + kWarmShiftThreads - 1) / kWarmShiftThreads, b.B), dim3(kWarmShiftThreads), 0, s, b,
+                     ctx->dmodel);
+  hipLaunchKernelGGL(k_grid_clean, dim3((b.B + 255) / 256), dim3(256), 0, s, b);
+}
+
+// Called (on the MPC stream) before the whole batch's node tables are written: see launch_grid_save.
+static int32_t save_grid_before_table_update(hb_ctx* ctx, int i0, int cnt) {
+  if (!ctx->traj_set) return HB_OK;
+  HB_TRY(launch_grid_save(ctx, ctx->b, !ctx->grid_saved, i0, cnt, ctx->s_mpc));
+  ctx->grid_saved = true;
+  return HB_OK;
+}
+
+int32_t hb_mpc_set_references(hb_ctx* ctx, int32_t i0, int32_t cnt, const int32_t* n_nodes, const double* t,
+                              const int32_t* mode, const double* x_ref, const double* swing_ref) {
+  HB_ENTER_ARGS(false);
+  HB_FAIL_IF(!n_nodes || !t || !mode || !x_ref || !swing_ref || !range_ok(ctx, i0, cnt, 1), HB_ERR_ARG, "hb_mpc_set_references: bad argument");
+  for (int i = 0; i < cnt; ++i)
+    HB_FAIL_IF(n_nodes[i] < 1 || n_nodes[i] > ctx->Nmax, HB_ERR_ARG, "hb_mpc_set_references: n_nodes out of range");
+  Batch& b = ctx->b;
+  const Range r{i0, cnt};
+  HB_ENTER_DEVICE();
+  HB_TRY(save_grid_before_table_update(ctx, i0, cnt));
+  HB_TRY(push(ctx, n_nodes, b, b.n_nodes, r, &ctx->s_mpc));
+  HB_TRY(push(ctx, t, b, b.t, r, &ctx->s_mpc));
+  HB_TRY(push(ctx, mode, b, b.mode, r, &ctx->s_mpc));
+  HB_TRY(push(ctx, x_ref, b, b.xref, r, &ctx->s_mpc));
+  HB_TRY(push(ctx, swing_ref, b, b.swing, r, &ctx->s_mpc));
+  HB_HIP(hipStreamSynchronize(ctx->s_mpc));  // host buffers are caller-owned: safe to reuse on return
+  ctx->refs_set = true;
+  ++ctx->mpc_tables_epoch;
+  return HB_OK;
+}
+
+static int32_t mpc_cold_start(hb_ctx* ctx, const double* x0, const uint8_t* mask) {
+  HB_FAIL_IF(!ctx->refs_set, HB_ERR_STATE, "hb_mpc_reset: references not set");
+  HB_ENTER_DEVICE();
+  const size_t B = ctx->B;
+  unsigned char* dmask = nullptr;
+  if (mask) {
+    HB_FAIL_IF(!ctx->traj_set, HB_ERR_STATE, "hb_mpc_reset_masked: no iterate yet (hb_mpc_reset first)");
+    if (!ctx->reset_mask) HB_HIP(dalloc(ctx, &ctx->reset_mask, B));
+    dmask = ctx->reset_mask;
+    HB_HIP(hipMemcpyAsync(dmask, mask, B, hipMemcpyHostToDevice, ctx->s_mpc));
+  }
+  if (x0) {
+    if (!mask) {
+      HB_TRY(push(ctx, x0, ctx->b, ctx->b.x0, whole(ctx), &ctx->s_mpc));
+    } else {  // only the masked rows of the observation are replaced
+      const size_t nx = extent_of(ctx->b, ctx->Nmax, ctx->b.x0).n;
+      for (size_t i = 0; i < B; ++i)
+        if (mask[i]) HB_TRY(push(ctx, x0 + i * nx, ctx->b, ctx->b.x0, Range{int(i), 1}, &ctx->s_mpc));
+    }
+  }
+  ++ctx->mpc_tables_epoch;
+  hipLaunchKernelGGL(k_cold_start, dim3(ctx->Nmax + 1, ctx->B), dim3(64), 0, ctx->s_mpc, ctx->b, ctx->dmodel, dmask);
+  HB_HIP(hipGetLastError());
+  HB_HIP(hipStreamSynchronize(ctx->s_mpc));
+  if (!mask) ctx->grid_saved = false;  // every instance sits on the current tables
+  ctx->traj_set = true;
+  return HB_OK;
+}
+
+int32_t hb_mpc_reset(hb_ctx* ctx, const double* x0) {
+  HB_ENTER_ARGS(false);
+  return mpc_cold_start(ctx, x0, nullptr);
+}
+
+int32_t hb_mpc_reset_masked(hb_ctx* ctx, const uint8_t* mask, const double* x0) {
+  HB_ENTER_ARGS(!mask);
+  return mpc_cold_start(ctx, x0, mask);
+}
+
+int32_t hb_mpc_get_status(hb_ctx* ctx, int32_t* status) {
+  HB_ENTER(!status);
+  HB_TRY(pull(ctx, status, ctx->b, ctx->b.mpc_status, whole(ctx), &ctx->s_mpc));
+  HB_HIP(hipStreamSynchronize(ctx->s_mpc));
+  return HB_OK;
+}
+
+int32_t hb_mpc_set_trajectory(hb_ctx* ctx, const double* x, const double* u) {
+  HB_ENTER_ARGS(!x || !u);
+  HB_ENTER_DEVICE();
+  ++ctx->mpc_tables_epoch;
+  HB_TRY(push(ctx, x, ctx->b, ctx->b.x, whole(ctx), &ctx->s_mpc));
+  HB_TRY(push(ctx, u, ctx->b, ctx->b.u, whole(ctx), &ctx->s_mpc));
+  hipLaunchKernelGGL(k_grid_clean, dim3((ctx->B + 255) / 256), dim3(256), 0, ctx->s_mpc, ctx->b);  // given on the current tables
+  HB_HIP(hipStreamSynchronize(ctx->s_mpc));
+  ctx->grid_saved = false;
+  ctx->traj_set = true;
+  return HB_OK;
+}
+
+// The tables changed: the iterate becomes the previous iterate, the source of the warm start.
+static void swap_iterate(hb_ctx* ctx) {
+  std::swap(ctx->b.x, ctx->b.xp);
+  std::swap(ctx->b.u, ctx->b.up);
+  ++ctx->graph_epoch;  // captured range graphs hold the old pointers
+}
+
+// Brings the iterate onto the current node tables if they changed since it was computed (see k_warm_shift); MPC stream.
+static int32_t warm_start_onto_new_tables(hb_ctx* ctx) {
+  if (!ctx->grid_saved) return HB_OK;
+  swap_iterate(ctx);
+  launch_warm_start(ctx, ctx->b, ctx->s_mpc);
+  HB_HIP(hipGetLastError());
+  ctx->grid_saved = false;
+  return HB_OK;
+}
+
+// Backward sweep of `B` instances: small launches take four wavefronts per instance (k_ric_bwd4), large ones the one-wavefront form
+// (eight sweeps per CU are then the better use of the chip).  hb_config.reserved = 101 / 104 forces one / four (tests, tuning).
+// `concurrent` = instances whose sweeps may be in flight at the same time (the whole batch when its instance ranges free-run on their
+// own streams): what decides is how many sweeps share the chip, not the size of this launch.
+static void launch_ric_bwd(hb_ctx* ctx, const Batch& b, int B, int concurrent, hipStream_t s) {
+  const int sel = ctx->hconfig.debug_stop;
+  const bool four = sel == 104 || (HB_ABLATE_ON && ((sel >= 24 && sel <= 27) || sel == 199)) || (sel != 101 && !(HB_ABLATE_ON && sel != 0 && sel != 198) && concurrent <= kRicBwd4MaxBatch);
+  if (four) hipLaunchKernelGGL(k_ric_bwd4, dim3(B), dim3(256), 0, s, b, sel);
+  else hipLaunchKernelGGL(k_ric_bwd, dim3(B), dim3(64), 0, s, b, sel);
+}
+
+// LQ approximation: trips of tlen nodes per wavefront (k_lq_trip).  Longer trips fill the lanes of the value phase better (16 nodes:
+// all 64), shorter ones keep small batches spread over the chip and balance them finer: the longest trip
+// that still gives every wavefront slot of the chip (12 per CU) four trips of the CONCURRENT batch — 16 nodes from 2048 instances up, 8 at
+// 1024, 4 at 512 (512 x 108 on two ranges, updates/s: one-node kernel 329.7 k, 4 nodes 325.0 k, 8: 316.9 k, 16: 305.2 k).  The result does not depend on the
+// choice.  hb_config.reserved = 120 + s forces 2^s, 130 + L any length L <= 16 (lengths that are no power of two measured within the
+// noise of the powers of two at 512, 1024 and 4096 instances); 129 the one-node-per-wavefront kernel of rounds 1-5 (k_lq: cooperative leg
+// pass; A / B only, differs from the trips by rounding).
+constexpr int kLqTripsPerSlot = 4;
+static int lq_trip_len(const hb_ctx* ctx, int concurrent) {
+  const int sel = ctx->hconfig.debug_stop;
+  if (sel >= 120 && sel <= 124) return 1 << (sel - 120);
+  if (sel >= 131 && sel <= 146) return sel - 130;   // any trip length 1..16 (launch-geometry sweeps)
+  const long slots = 12L * ctx->n_cu;
+  for (int sh = 4; sh > 0; --sh)
+    if (long(concurrent) * ((ctx->Nmax + (1 << sh) - 1) >> sh) >= kLqTripsPerSlot * slots) return 1 << sh;
+  return 1;
+}
+static void launch_lq(hb_ctx* ctx, const Batch& b, int B, int concurrent, hipStream_t s) {
+  if (ctx->hconfig.debug_stop == 129) { hipLaunchKernelGGL(k_lq, dim3(ctx->Nmax, B), dim3(64), 0, s, b, ctx->dmodel, ctx->dconfig); return; }
+  const int len = lq_trip_len(ctx, concurrent);
+  const int ntrip = (ctx->Nmax + len - 1) / len;
+  hipLaunchKernelGGL(k_lq_trip, dim3(unsigned(ntrip) * B), dim3(64), 0, s, b, ctx->dmodel, ctx->dconfig, len);
+}
+
+// Forward sweep: the wave form while the batch leaves a SIMD one wavefront (hb_config.reserved = 111 / 114 force the row / the wave form)
+static void launch_ric_fwd(hb_ctx* ctx, const Batch& b, int B, int concurrent, hipStream_t s) {
+  const int sel = ctx->hconfig.debug_stop;
+  if (sel == 114 || (sel != 111 && concurrent <= kRicFwdWaveMaxBatch)) hipLaunchKernelGGL(k_ric_fwd_w, dim3(B), dim3(64), 0, s, b);
+  else hipLaunchKernelGGL(k_ric_fwd, dim3(B), dim3(64), 0, s, b);
+}
+
+// The SQP iterations of the instances of b on s; `timed`: iteration 0 records the phase events ev[EV_LQ_BEGIN .. EV_LS_END].
+static int32_t enqueue_sqp(hb_ctx* ctx, const Batch& b, hipStream_t s, bool timed) {
+  const int B = b.B, N = ctx->Nmax;
+  for (int it = 0; it < ctx->config.sqp_iterations; ++it) {
+    const bool mark = timed && it == 0;
+    hipLaunchKernelGGL(k_set_x0, dim3((B * HB_NX + 255) / 256), dim3(256), 0, s, b);
+    if (mark) HB_HIP(hipEventRecord(ctx->ev[EV_LQ_BEGIN], s));
+    launch_lq(ctx, b, B, ctx->B, s);
+    if (mark) HB_HIP(hipEventRecord(ctx->ev[EV_LQ_END], s));
+    launch_ric_bwd(ctx, b, B, ctx->B, s);
+    if (mark) HB_HIP(hipEventRecord(ctx->ev[EV_RIC_BWD_END], s));
+    launch_ric_fwd(ctx, b, B, ctx->B, s);
+    if (mark) HB_HIP(hipEventRecord(ctx->ev[EV_RIC_FWD_END], s));
+    // filter line search: the full step for every instance, node-parallel; then the backtracking tail in one launch
+    hipLaunchKernelGGL(k_ls_eval, dim3((B * N + 63) / 64), dim3(64), 0, s, b, ctx->dmodel, ctx->dconfig, 1.0);
+    hipLaunchKernelGGL(k_ls_decide, dim3(B), dim3(64), 0, s, b, ctx->dconfig, 1.0);
+    if (ctx->config.alpha_decay > 0.0 && ctx->config.alpha_decay < 1.0 && ctx->config.alpha_decay >= ctx->config.alpha_min) {
+      // step sizes alpha_decay^1, ^2, ... >= alpha_min, in windows of LS_TAIL_MAX = 16 evaluated side by side (the shipped 0.5 / 1e-4
+      // makes 13: one window).  A slower decay (0.9 / 1e-4: 88 step sizes) walks on window after window down to alpha_min as OCS2's
+      // FilterLinesearch does; an instance that has accepted or given up makes the later windows return at once.  The window's first
+      // step size is the running product the sequential search would hold there (same rounding as the kernels' own products).
+      double a_win = ctx->config.alpha_decay;
+      while (a_win >= ctx->config.alpha_min) {
+        int n_alpha = 0;
+        double a = a_win;
+        for (; a >= ctx->config.alpha_min && n_alpha < LS_TAIL_MAX; a *= ctx->config.alpha_decay) ++n_alpha;
+        hipLaunchKernelGGL(k_ls_tail_eval, dim3((B * N + 63) / 64, n_alpha), dim3(64), 0, s, b, ctx->dmodel, ctx->dconfig, a_win,
+                           ctx->config.alpha_decay, ctx->config.alpha_min);
+        hipLaunchKernelGGL(k_ls_tail_decide, dim3(B), dim3(64), 0, s, b, ctx->dconfig, a_win, ctx->config.alpha_decay,
+                           ctx->config.alpha_min, n_alpha);
+        a_win = a;
+      }
+    }
+    if (mark) HB_HIP(hipEventRecord(ctx->ev[EV_LS_END], s));
+    // evaluated per iteration: ric_fail / accepted are overwritten by the next one
+    hipLaunchKernelGGL(k_mpc_status, dim3((B + 255) / 256), dim3(256), 0, s, b, it == 0 ? 1 : 0);
+  }
+  HB_HIP(hipGetLastError());
+  return HB_OK;
+}
+
+// MPC solve of the whole batch on the MPC stream: warm start onto new tables, the timed SQP iterations, the solve counted.
+static int32_t mpc_solve_batch(hb_ctx* ctx) {
+  HB_TRY(warm_start_onto_new_tables(ctx));
+  HB_TRY(enqueue_sqp(ctx, ctx->b, ctx->s_mpc, true));
+  std::lock_guard<std::mutex> lk(ctx->mtx);
+  ctx->timed = true;
+  ctx->stats.n_mpc_solves += ctx->B;
+  ctx->mpc_solved_epoch = ctx->mpc_tables_epoch;
+  return HB_OK;
+}
+
+int32_t hb_mpc_solve(hb_ctx* ctx, const double* x0) {
+  HB_ENTER_ARGS(false);
+  HB_FAIL_IF(!ctx->refs_set || !ctx->traj_set, HB_ERR_STATE, "hb_mpc_solve: call hb_mpc_set_references and hb_mpc_reset/hb_mpc_set_trajectory first");
+  HB_ENTER_DEVICE();
+  if (x0) {
+    HB_TRY(push(ctx, x0, ctx->b, ctx->b.x0, whole(ctx), &ctx->s_mpc));
+    HB_HIP(hipStreamSynchronize(ctx->s_mpc));
+  }
+  return mpc_solve_batch(ctx);
+}
+
+int32_t hb_mpc_get_solution(hb_ctx* ctx, int32_t i0, int32_t cnt, double* x, double* u) {
+  HB_ENTER(!range_ok(ctx, i0, cnt, 1));
+  HB_TRY(pull(ctx, x, ctx->b, ctx->b.x, Range{i0, cnt}, &ctx->s_mpc));
+  HB_TRY(pull(ctx, u, ctx->b, ctx->b.u, Range{i0, cnt}, &ctx->s_mpc));
+  HB_HIP(hipStreamSynchronize(ctx->s_mpc));
+  return HB_OK;
+}
+
+int32_t hb_mpc_get_step(hb_ctx* ctx, double* dx, double* du) {
+  HB_ENTER(false);
+  HB_TRY(pull(ctx, dx, ctx->b, ctx->b.dx, whole(ctx), &ctx->s_mpc));
+  HB_TRY(pull(ctx, du, ctx->b, ctx->b.du, whole(ctx), &ctx->s_mpc));
+  HB_HIP(hipStreamSynchronize(ctx->s_mpc));
+  return HB_OK;
+}
+
+int32_t hb_mpc_get_performance(hb_ctx* ctx, double* perf) {
+  HB_ENTER(!perf);
+  HB_TRY(pull(ctx, perf, ctx->b, ctx->b.perf, whole(ctx), &ctx->s_mpc));
+  HB_HIP(hipStreamSynchronize(ctx->s_mpc));
+  return HB_OK;
+}
+
+int32_t hb_mpc_get_references(hb_ctx* ctx, int32_t i0, int32_t cnt, int32_t* n_nodes, double* t, int32_t* mode, double* x_ref,
+                              double* swing_ref) {
+  HB_ENTER_ARGS(!range_ok(ctx, i0, cnt, 1));
+  HB_FAIL_IF(!ctx->refs_set, HB_ERR_STATE, "hb_mpc_get_references: references not set");
+  HB_ENTER_DEVICE();
+  HB_HIP(hipStreamSynchronize(ctx->s_mpc));
+  Batch& b = ctx->b;
+  const Range r{i0, cnt};
+  HB_TRY(pull(ctx, n_nodes, b, b.n_nodes, r));
+  HB_TRY(pull(ctx, t, b, b.t, r));
+  HB_TRY(pull(ctx, mode, b, b.mode, r));
+  HB_TRY(pull(ctx, x_ref, b, b.xref, r));
+  HB_TRY(pull(ctx, swing_ref, b, b.swing, r));
+  return HB_OK;
+}
+
+// The records, gains and step on the device are those of the last MPC call, on the tables and the iterate it ran on
+static int32_t mpc_records_current(hb_ctx* ctx, const char* who) {
+  if (ctx->mpc_solved_epoch == 0) {
+    ctx->err = std::string(who) + ": no MPC call has completed on this context (hb_mpc_solve, hb_step_resident, hb_tick_resident)";
+    return HB_ERR_STATE;
+  }
+  if (ctx->mpc_solved_epoch != ctx->mpc_tables_epoch) {
+    ctx->err = std::string(who) + ": the node tables or the iterate were replaced since the last MPC call (hb_mpc_set_references, "
+               "hb_refgen_update, hb_mpc_reset, hb_mpc_reset_masked, hb_mpc_set_trajectory): solve again first";
+    return HB_ERR_STATE;
+  }
+  return HB_OK;
+}
+
+int32_t hb_mpc_get_certificate(hb_ctx* ctx, int32_t inst_begin, int32_t inst_count, double* cert, double* costate, double* u_til) {
+  HB_ENTER_ARGS(false);
+  HB_FAIL_IF(!range_ok(ctx, inst_begin, inst_count, 1), HB_ERR_ARG, "hb_mpc_get_certificate: instance range outside the batch");
+  HB_TRY(mpc_records_current(ctx, "hb_mpc_get_certificate"));
+  HB_ENTER_DEVICE();
+  MpcCertBuf& m = ctx->mcert;
+  if (!m.node) HB_HIP(alloc_fields(ctx, m));
+  const Range r{inst_begin, inst_count};
+  const Batch b = view(ctx->b, ctx->Nmax, inst_begin, inst_count);
+  const MpcCertBuf v = from_instance(m, ctx->Nmax, inst_begin);
+  hipStream_t s = ctx->s_mpc;
+  hipLaunchKernelGGL(k_mpc_cert_nodes, dim3(ctx->Nmax, inst_count), dim3(64), 0, s, b, v);
+  hipLaunchKernelGGL(k_mpc_cert_sweep, dim3(inst_count), dim3(64), 0, s, b, v);
+  HB_HIP(hipGetLastError());
+  HB_TRY(pull(ctx, cert, m, m.cert, r, &s));
+  HB_TRY(pull(ctx, costate, m, m.costate, r, &s));
+  HB_TRY(pull(ctx, u_til, m, m.util, r, &s));
+  HB_HIP(hipStreamSynchronize(s));
+  return HB_OK;
+}
+
+int32_t hb_mpc_get_lq(hb_ctx* ctx, int32_t inst, double* A, double* B, double* b, double* Q, double* P, double* R, double* q, double* r,
+                      int32_t* n_til) {
+  HB_ENTER_ARGS(false);
+  HB_FAIL_IF(inst < 0 || inst >= ctx->B, HB_ERR_ARG, "hb_mpc_get_lq: instance outside the batch");
+  HB_TRY(mpc_records_current(ctx, "hb_mpc_get_lq"));
+  HB_ENTER_DEVICE();
+  const size_t N = ctx->Nmax;
+  std::vector<double> recs(extent_of(ctx->b, N, ctx->b.recs).n);
+  int n = 0;
+  HB_TRY(pull(ctx, &n, ctx->b, ctx->b.n_nodes, Range{inst, 1}, &ctx->s_mpc));
+  HB_TRY(pull(ctx, recs.data(), ctx->b, ctx->b.recs, Range{inst, 1}, &ctx->s_mpc));
+  HB_HIP(hipStreamSynchronize(ctx->s_mpc));
+  n = std::max(0, std::min(n, ctx->Nmax));
+  const auto zero = [N](double* p, size_t per) { if (p) std::memset(p, 0, N * per * 8); };   // rows k >= n stay zero
+  zero(A, 22 * 22); zero(B, 22 * NU_T); zero(b, 22); zero(Q, 22 * 22); zero(P, NU_T * 22); zero(R, NU_T * NU_T); zero(q, 22); zero(r, NU_T);
+  if (n_til) std::memset(n_til, 0, N * sizeof(int32_t));
+  for (size_t k = 0; k < size_t(n); ++k) {
+    int nt = 0;
+    rec_unpack(recs.data() + k * REC_SIZE, A ? A + k * 484 : nullptr, B ? B + k * 264 : nullptr, b ? b + k * 22 : nullptr,
+               Q ? Q + k * 484 : nullptr, P ? P + k * 264 : nullptr, R ? R + k * 144 : nullptr, q ? q + k * 22 : nullptr,
+               r ? r + k * 12 : nullptr, &nt);
+    if (n_til) n_til[k] = nt;
+  }
+  return HB_OK;
+}
+
+}  // extern "C"

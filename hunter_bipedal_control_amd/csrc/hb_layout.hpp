@@ -1,0 +1,259 @@
+// The device-resident arrays of a batch: the structs the kernels take by value and, per struct, ONE description of its arrays —
+// fields(s, N, f) calls f(name, member, extent) for every device array in allocation order.  Allocation, instance-range views and
+// host <-> device copies of instance ranges are derived from the description (below and hb_api_ctx.hpp); nothing else restates how
+// many elements an instance owns.  Host code only, and plain C++: tests/host_emu/layoutemu.cpp compiles this header with g++.
+#pragma once
+#include <cstddef>
+
+#include "hb_host.hpp"
+#include "hb_mpccert.hpp"
+#include "hb_wbc.hpp"
+#include "hb_refgen.hpp"
+#include "hb_gait.hpp"
+
+namespace {
+using namespace hb;
+
+// Elements of an array that belong to one instance (n: the allocation is B * n) and the distance from one instance's data to the next
+// (step: the view of the instances from i0 on starts i0 * step further).  Instance-major arrays [B][n]: step = n.
+struct Extent {
+  size_t n, step;
+  constexpr Extent(size_t n_) : n(n_), step(n_) {}
+  constexpr Extent(size_t n_, size_t step_) : n(n_), step(step_) {}
+};
+// [slots][B]: the pitch of a slot row is the whole batch in every view (GaitBatch::stride), consecutive instances are neighbours
+constexpr Extent slot_major(size_t slots) { return Extent(slots, 1); }
+
+#define HB_FIELD(member, ...) f(#member, member, Extent(__VA_ARGS__))
+
+// ---------------------------------------------------------------------------------------------------------
+// device-resident problem data of a batch
+constexpr int LS_TAIL_MAX = 16;   // step sizes the backtracking tail evaluates side by side (decay 0.5, alpha_min 1e-4: 13 of them)
+struct Batch {
+  int B, Nmax;
+  int* n_nodes;
+  double* t;
+  int* mode;
+  double* xref;
+  double* swing;
+  double* x;
+  double* u;
+  double* x0;
+  double* recs;
+  double* gains;
+  double* dx;
+  double* du;
+  double* acc;      // armijo, base merit, base dyn, base eq
+  double* partial;
+  double* ls_norm;  // |dx|, |du| (l2, whole trajectory) of the instances whose full step was refused (k_ls_decide)
+  double* ls_tail;  // [LS_TAIL_MAX][Nmax][3] per instance: per-node line-search partials of the backtracking step sizes, evaluated side by side
+  int* accepted;
+  double* perf;     // merit dyn eq step
+  int* ric_fail;
+  int* mpc_status;  // hb_inst_status of the last MPC call
+  // iterate of the previous MPC call on ITS time grid (warm start across calls, k_warm_shift); x / u and xp / up swap roles
+  double* xp;
+  double* up;
+  double* tp;
+  int* modep;
+  int* np_nodes;
+  int* grid_dirty;  // the node tables changed since the iterate was last brought onto them
+  double* lqpark;   // phase-1 images of the nodes, parked by the value phase of k_lq_trip
+};
+template <class F>
+constexpr void fields(Batch& b, size_t N, F&& f) {
+  HB_FIELD(b.n_nodes, 1); HB_FIELD(b.t, N + 1); HB_FIELD(b.mode, N); HB_FIELD(b.xref, N * HB_NX); HB_FIELD(b.swing, N * 24);
+  HB_FIELD(b.x, (N + 1) * HB_NX); HB_FIELD(b.u, N * HB_NU); HB_FIELD(b.x0, HB_NX); HB_FIELD(b.recs, N * REC_SIZE); HB_FIELD(b.gains, N * GAIN_SIZE);
+  HB_FIELD(b.dx, (N + 1) * HB_NX); HB_FIELD(b.du, N * HB_NU); HB_FIELD(b.acc, 4); HB_FIELD(b.partial, N * 3);
+  HB_FIELD(b.ls_tail, LS_TAIL_MAX * N * 3); HB_FIELD(b.ls_norm, 2); HB_FIELD(b.accepted, 1); HB_FIELD(b.perf, 4); HB_FIELD(b.ric_fail, 1);
+  HB_FIELD(b.mpc_status, 1); HB_FIELD(b.xp, (N + 1) * HB_NX); HB_FIELD(b.up, N * HB_NU); HB_FIELD(b.tp, N + 1); HB_FIELD(b.modep, N);
+  HB_FIELD(b.np_nodes, 1); HB_FIELD(b.grid_dirty, 1); HB_FIELD(b.lqpark, (N + LqPark::trip_max) * LqPark::size);
+}
+
+// KKT certificate of the MPC's stage QP (hb_mpccert.hpp), on demand: work buffers of hb_mpc_get_certificate
+struct MpcCertBuf {
+  double* node;
+  double* costate;
+  double* cert;
+  double* util;     // u~ as hb_mpc_get_certificate returns it
+};
+template <class F>
+constexpr void fields(MpcCertBuf& m, size_t N, F&& f) {
+  HB_FIELD(m.node, N * CertNode::size); HB_FIELD(m.costate, (N + 1) * HB_NX); HB_FIELD(m.cert, MPC_CERT_SIZE); HB_FIELD(m.util, N * 12);
+}
+
+// WbcBatch (hb_wbc.hpp): inputs and outputs of the WBC, and the published policy (PrimalSolution) its stream reads
+template <class F>
+constexpr void fields(WbcBatch& w, size_t N, F&& f) {
+  HB_FIELD(w.t_now, 1); HB_FIELD(w.rbd, HB_NRBD); HB_FIELD(w.walk, 1); HB_FIELD(w.xdes, HB_NX); HB_FIELD(w.udes, HB_NU); HB_FIELD(w.mode, 1);
+  HB_FIELD(w.stance, 1); HB_FIELD(w.sol, HB_NWBC); HB_FIELD(w.status, 1); HB_FIELD(w.iters, 1); HB_FIELD(w.px, (N + 1) * HB_NX);
+  HB_FIELD(w.pu, N * HB_NU); HB_FIELD(w.pt, N + 1); HB_FIELD(w.pmode, N); HB_FIELD(w.pn, 1);
+}
+
+// KKT certificate of the WeightedWbc QP (hb_wbc_set_certificate) and per-level certificate of the HierarchicalWbc cascade
+// (hb_hwbc_set_certificate): outputs of k_wbc_cert / k_hwbc_cert, allocated on the first enable
+struct WbcCertBuf {
+  double *cert, *dual;
+};
+template <class F>
+constexpr void fields(WbcCertBuf& c, size_t, F&& f) {
+  HB_FIELD(c.cert, HB_WBC_CERT_SIZE); HB_FIELD(c.dual, HB_WBC_NCONS_MAX);
+}
+struct HwbcCertBuf {
+  double *cert, *xlev, *slack, *dual;   // per level | the solution after each level | the level-0 slack | multipliers of the inequality rows per level
+};
+template <class F>
+constexpr void fields(HwbcCertBuf& c, size_t, F&& f) {
+  HB_FIELD(c.cert, HB_HWBC_LEVELS * HB_HWBC_CERT_SIZE); HB_FIELD(c.xlev, HB_HWBC_LEVELS * HB_NWBC); HB_FIELD(c.slack, HB_HWBC_NINEQ_MAX);
+  HB_FIELD(c.dual, HB_HWBC_LEVELS * HB_HWBC_NINEQ_MAX);
+}
+
+// ---- plant stub ------------------------------------------------------------------------------------------------------
+struct PlantBatch {
+  int B;
+  double *q, *v, *anchor;
+  int* pinned;
+  double *lambda, *vdot;
+  double* tau;             // staging of host torques
+  int* contact;            // staging of host contact flags
+  double* rbd;             // repacked state
+  double baum, eps;
+  // what the last step applied (hb_plant_sense reads them; zero torque / all flags 1 before the first step)
+  double* tau_last;
+  int* contact_last;
+  // sensor arrays of hb_plant_sense: quat, gyro, accel, joint pos / vel / torque, contact flags
+  double *s_quat, *s_gyro, *s_accel, *s_jp, *s_jv, *s_jt;
+  int* s_contact;
+  double *gyro_bias, *accel_bias;  // [B][3] each, or null: not described, hb_plant_set_sensor_model aims them at buffers of its own
+};
+template <class F>
+constexpr void fields(PlantBatch& p, size_t, F&& f) {
+  HB_FIELD(p.q, 16); HB_FIELD(p.v, 16); HB_FIELD(p.anchor, 12); HB_FIELD(p.pinned, 4); HB_FIELD(p.lambda, 12); HB_FIELD(p.vdot, 16);
+  HB_FIELD(p.tau, 10); HB_FIELD(p.contact, 4); HB_FIELD(p.rbd, HB_NRBD); HB_FIELD(p.tau_last, 10); HB_FIELD(p.contact_last, 4); HB_FIELD(p.s_quat, 4);
+  HB_FIELD(p.s_gyro, 3); HB_FIELD(p.s_accel, 3); HB_FIELD(p.s_jp, 10); HB_FIELD(p.s_jv, 10); HB_FIELD(p.s_jt, 10); HB_FIELD(p.s_contact, 4);
+}
+
+// ---- reference generation ----------------------------------------------------------------------------------------------
+struct RefgenBatch {
+  int B;
+  int* n_ev;
+  double* ev;
+  int* modes;
+  double* stance;   // [4][3] per instance
+  double* phases;   // [4][HB_MAX_EVENTS + 1][RG_PHASE] per instance
+  double* t0;
+  double* cmd;
+  int* status;
+  int* n_knots;
+  double* knot_t;
+  double* knot_x;
+  int init_stance;  // take the current feet as latest stance positions (first update after a reset without state)
+};
+template <class F>
+constexpr void fields(RefgenBatch& r, size_t, F&& f) {
+  HB_FIELD(r.n_ev, 1); HB_FIELD(r.ev, HB_MAX_EVENTS); HB_FIELD(r.modes, HB_MAX_EVENTS + 1); HB_FIELD(r.stance, 12);
+  HB_FIELD(r.phases, 4 * (HB_MAX_EVENTS + 1) * RG_PHASE); HB_FIELD(r.t0, 1); HB_FIELD(r.cmd, 4); HB_FIELD(r.status, 1); HB_FIELD(r.n_knots, 1);
+  HB_FIELD(r.knot_t, RG_MAX_KNOTS); HB_FIELD(r.knot_x, RG_MAX_KNOTS * HB_NX);
+}
+
+// GaitBatch (hb_gait.hpp): the schedule, the template, the rate limiter and the velocity history are slot-major
+template <class F>
+constexpr void fields(GaitBatch& g, size_t, F&& f) {
+  HB_FIELD(g.n_ev, 1); HB_FIELD(g.ev, slot_major(HB_MAX_EVENTS)); HB_FIELD(g.modes, slot_major(HB_MAX_EVENTS + 1)); HB_FIELD(g.tpl_n, 1);
+  HB_FIELD(g.tpl_sw, slot_major(HB_GAIT_MAX_PHASES + 1)); HB_FIELD(g.tpl_modes, slot_major(HB_GAIT_MAX_PHASES)); HB_FIELD(g.last_vel, slot_major(4));
+  HB_FIELD(g.cmd, 4); HB_FIELD(g.hist, slot_major(GAIT_HIST)); HB_FIELD(g.hist_n, 1); HB_FIELD(g.hist_head, 1); HB_FIELD(g.level, 1);
+  HB_FIELD(g.vel_abs, 1); HB_FIELD(g.vel_avg, 1); HB_FIELD(g.status, 1);
+}
+
+// ---- state estimator -------------------------------------------------------------------------------------------------------
+struct EstBatch {
+  int B;
+  double *xhat, *P, *yaw_last;                        // filter state
+  const double *quat, *w_local, *a_local, *qj, *qdj;  // inputs: the estimator's own upload buffers, or aimed at another struct's arrays
+  const int* contact;
+  double *rbd, *x;                                    // outputs
+  double *res_rbd, *res_x0;                           // resident inputs of hb_step_resident (or null): the caller's, not described
+  // hb_estimator_contact_force: low-pass state pSCgZinvlast_, joint efforts, the two outputs, a host-given rbd
+  double *cf_z, *cf_tau, *cf_dist, *cf_out, *cf_rbd;
+};
+// what k_estimator reads and writes: the part an instance range views
+template <class F>
+constexpr void filter_fields(EstBatch& e, F&& f) {
+  HB_FIELD(e.xhat, 18); HB_FIELD(e.P, 324); HB_FIELD(e.yaw_last, 1); HB_FIELD(e.quat, 4); HB_FIELD(e.w_local, 3); HB_FIELD(e.a_local, 3);
+  HB_FIELD(e.qj, 10); HB_FIELD(e.qdj, 10); HB_FIELD(e.contact, 4); HB_FIELD(e.rbd, HB_NRBD); HB_FIELD(e.x, HB_NX);
+}
+template <class F>
+constexpr void fields(EstBatch& e, size_t, F&& f) {
+  filter_fields(e, f);
+  HB_FIELD(e.cf_z, HB_NV);   // (the contact-force observer runs on the whole batch only)
+  HB_FIELD(e.cf_tau, HB_NJ); HB_FIELD(e.cf_dist, HB_NV); HB_FIELD(e.cf_out, 16); HB_FIELD(e.cf_rbd, HB_NRBD);
+}
+
+// hb_tick_resident: device-side upload targets of one tick's host inputs (read early in every instance range's tick, so that the
+// next tick's upload only has to wait for that early point)
+struct TickUpload {
+  double *quat, *w, *a, *qj, *qdj;
+  int* contact;
+  double *tnow, *t0, *cmd;
+};
+template <class F>
+constexpr void fields(TickUpload& up, size_t, F&& f) {
+  HB_FIELD(up.quat, 4); HB_FIELD(up.w, 3); HB_FIELD(up.a, 3); HB_FIELD(up.qj, 10); HB_FIELD(up.qdj, 10); HB_FIELD(up.contact, 4);
+  HB_FIELD(up.tnow, 1); HB_FIELD(up.t0, 1); HB_FIELD(up.cmd, 4);
+}
+#undef HB_FIELD
+
+// ---- what is derived from a description ------------------------------------------------------------------------------------
+template <class S>
+constexpr int n_fields() {
+  S s{};
+  int n = 0;
+  fields(s, 1, [&n](const char*, auto*&, Extent) { ++n; });
+  return n;
+}
+// A member the description forgets would be allocated by nobody and left at instance 0 by every view: the struct is its scalars plus
+// exactly the described pointers (plus the pointers named here, which are aimed at other structs' arrays).
+constexpr size_t kPtr = sizeof(void*);
+static_assert(sizeof(Batch) == 2 * sizeof(int) + n_fields<Batch>() * kPtr, "describe every array of Batch in fields()");
+static_assert(sizeof(MpcCertBuf) == n_fields<MpcCertBuf>() * kPtr, "describe every array of MpcCertBuf in fields()");
+static_assert(sizeof(WbcBatch) == kPtr /*B*/ + n_fields<WbcBatch>() * kPtr + kPtr /*policy_valid*/, "describe every array of WbcBatch in fields()");
+static_assert(sizeof(WbcCertBuf) == n_fields<WbcCertBuf>() * kPtr && sizeof(HwbcCertBuf) == n_fields<HwbcCertBuf>() * kPtr, "certificate buffers");
+static_assert(sizeof(PlantBatch) == kPtr /*B*/ + 2 * sizeof(double) + (n_fields<PlantBatch>() + 2 /*gyro_bias, accel_bias*/) * kPtr,
+              "describe every array of PlantBatch in fields()");
+static_assert(sizeof(RefgenBatch) == kPtr /*B*/ + n_fields<RefgenBatch>() * kPtr + kPtr /*init_stance*/, "describe every array of RefgenBatch in fields()");
+static_assert(sizeof(GaitBatch) == 2 * sizeof(int) + n_fields<GaitBatch>() * kPtr, "describe every array of GaitBatch in fields()");
+static_assert(sizeof(EstBatch) == kPtr /*B*/ + (n_fields<EstBatch>() + 2 /*res_rbd, res_x0*/) * kPtr, "describe every array of EstBatch in fields()");
+static_assert(sizeof(TickUpload) == n_fields<TickUpload>() * kPtr, "describe every array of TickUpload in fields()");
+
+// The same struct with every described array starting at instance i0.
+template <class S>
+S from_instance(const S& s, size_t N, int i0) {
+  S v = s;
+  fields(v, N, [i0](const char*, auto*& p, Extent e) { p += size_t(i0) * e.step; });
+  return v;
+}
+// Sub-batch [i0, i0 + cnt) of a batch: same layout, offset base pointers.
+template <class S>
+S view(const S& s, size_t N, int i0, int cnt) {
+  S v = from_instance(s, N, i0);
+  v.B = cnt;
+  return v;
+}
+// (what k_estimator reads and writes; the resident outputs res_* are the caller's, the contact-force observer is not viewed)
+inline EstBatch view(const EstBatch& e, size_t, int i0, int cnt) {
+  EstBatch v = e;
+  filter_fields(v, [i0](const char*, auto*& p, Extent x) { p += size_t(i0) * x.step; });
+  v.B = cnt;
+  return v;
+}
+// Extent of the array `member` of s (n = 0: s does not describe it).
+template <class S, class T>
+Extent extent_of(S& s, size_t N, T* const& member) {
+  Extent found(0);
+  fields(s, N, [&](const char*, auto*& p, Extent e) {
+    if (static_cast<const void*>(&p) == static_cast<const void*>(&member)) found = e;
+  });
+  return found;
+}
+
+}  // namespace

@@ -45,6 +45,7 @@ typedef enum hb_status {
   HB_ERR_STATE = -3,     /* call order (e.g. solve before references were set) */
   HB_ERR_NO_GPU = -4     /* no gfx950 device visible: the product path never falls back to a CPU */
 } hb_status;
+/* An instance range [inst_begin, inst_begin + inst_count) that leaves the batch is HB_ERR_ARG in every entry, also where the sum overflows int32. */
 
 /* Per-instance solver status words written by the device (SURVEY.md §5 "failure detection"). */
 #define HB_INST_OK 0
