@@ -2,6 +2,7 @@
 from __future__ import annotations
 
 import ctypes as C
+from types import SimpleNamespace
 
 import numpy as np
 
@@ -55,6 +56,22 @@ class HbConfig(C.Structure):
         ("delta_tol", C.c_double),
         ("wbc_reg_steps", C.c_int32), ("wbc_eps_mode", C.c_int32),
     ]
+
+
+# Values of hb_config.reserved: hand-written mirror of csrc/hb_forms.hpp (there and in DESIGN.md 3.0: the meaning of every code; held together by
+# tests/test_forms_host.py).  The stops of a kernel (profiling build) stand in code order, as the tools walk them: each includes the phases before it.
+_LQ = dict(LQ_LOADS=10, LQ_LEG_VALUES=6, LQ_VALUE_PREPASS=7, LQ_DIRECTIONS=9, LQ_COMPOSE=1, LQ_FACTOR=2, LQ_SOLVES=3, LQ_DEFECT=30,
+           LQ_B_COLUMNS=31, LQ_COST=4, LQ_SOFT_ROWS=5, LQ_Q=32, LQ_P=33, LQ_R=34)
+_WBC = dict(WBC_A_BASE=13, WBC_A_LEGS=14, WBC_A_FINISH=15, WBC_A=11, WBC_B=12)
+_RIC1 = dict(RIC1_STAGING=20, RIC1_GEMM1=21, RIC1_GEMM2=22, RIC1_FACTOR=23)    # k_ric_bwd
+_RIC4 = dict(RIC4_STAGING=24, RIC4_GEMM1=25, RIC4_GEMM2=26, RIC4_FACTOR=27)    # k_ric_bwd4
+_HWBC = dict(HWBC_LEVEL0=41, HWBC_KERNEL0=43, HWBC_QP1=44, HWBC_LEVEL1=42)
+FORMS = dict(NONE=0, **_LQ, **_WBC, **_RIC1, **_RIC4, **_HWBC, RIC_BWD_ONE=101, RIC_BWD_FOUR=104, RIC_FWD_ROW=111, RIC_FWD_WAVE=114,
+             LQT_ONE_RECORD=117, LQT_TRACE=118, LQT_PARK_NOTHING=119, LQT_VALUES_ONCE=125, LQT_VALUES=126, LQT_VALUES_FWD=127,
+             LQT_VALUES_LEGS=128, LQ_ONE_NODE=129, RIC1_TRACE=197, WBC_TRACE=198, RIC4_TRACE=199)
+FORM_RANGES = dict(LQ_TRIP_POW2=(120, 124), LQ_TRIP_LEN=(131, 146))   # LQ trips of 2^(value - first) / of value - first + 1 nodes
+FORM = SimpleNamespace(**FORMS)
+LQ_STOPS, WBC_STOPS, RIC1_STOPS, RIC4_STOPS, HWBC_STOPS = (tuple(d.values()) for d in (_LQ, _WBC, _RIC1, _RIC4, _HWBC))
 
 
 class HbStats(C.Structure):

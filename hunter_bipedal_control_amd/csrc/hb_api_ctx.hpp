@@ -29,6 +29,7 @@ struct hb_ctx {
   hb_config config;
   DevModel hmodel;
   DevConfig hconfig;
+  KernelForms forms;   // decoded once from config.reserved (hb_forms.hpp): which form of the LQ kernel and the sweeps is launched
   DevModel* dmodel = nullptr;
   DevConfig* dconfig = nullptr;
   Batch b{};
@@ -358,6 +359,7 @@ int32_t hb_create(const hb_model* model, const hb_config* config, int32_t batch,
   ctx->config = *config;
   ctx->hmodel = make_dev_model(*model);
   ctx->hconfig = make_dev_config(*config, ctx->hmodel);
+  ctx->forms = decode_forms(config->reserved, HB_ABLATE_ON);
 
   auto fail = [&](const char* what, hipError_t e) {
     g_create_error = std::string("hb_create: ") + what + ": " + hipGetErrorString(e);

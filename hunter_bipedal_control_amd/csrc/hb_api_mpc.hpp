@@ -129,45 +129,23 @@ static int32_t warm_start_onto_new_tables(hb_ctx* ctx) {
   return HB_OK;
 }
 
-// Backward sweep of `B` instances: small launches take four wavefronts per instance (k_ric_bwd4), large ones the one-wavefront form
-// (eight sweeps per CU are then the better use of the chip).  hb_config.reserved = 101 / 104 forces one / four (tests, tuning).
-// `concurrent` = instances whose sweeps may be in flight at the same time (the whole batch when its instance ranges free-run on their
-// own streams): what decides is how many sweeps share the chip, not the size of this launch.
+// The three launchers pick the kernel form by ctx->forms and `concurrent` = the instances whose kernels may be in flight at the same time (hb_forms.hpp:
+// use_ric_bwd4, lq_trip_len, use_ric_fwd_wave); the forms agree bit for bit.  `dbg`: the sweeps take hb_config.reserved as an argument (profiling stops).
 static void launch_ric_bwd(hb_ctx* ctx, const Batch& b, int B, int concurrent, hipStream_t s) {
-  const int sel = ctx->hconfig.debug_stop;
-  const bool four = sel == 104 || (HB_ABLATE_ON && ((sel >= 24 && sel <= 27) || sel == 199)) || (sel != 101 && !(HB_ABLATE_ON && sel != 0 && sel != 198) && concurrent <= kRicBwd4MaxBatch);
-  if (four) hipLaunchKernelGGL(k_ric_bwd4, dim3(B), dim3(256), 0, s, b, sel);
-  else hipLaunchKernelGGL(k_ric_bwd, dim3(B), dim3(64), 0, s, b, sel);
+  const int dbg = ctx->hconfig.debug_stop;
+  if (use_ric_bwd4(ctx->forms, concurrent)) hipLaunchKernelGGL(k_ric_bwd4, dim3(B), dim3(256), 0, s, b, dbg);
+  else hipLaunchKernelGGL(k_ric_bwd, dim3(B), dim3(64), 0, s, b, dbg);
 }
 
-// LQ approximation: trips of tlen nodes per wavefront (k_lq_trip).  Longer trips fill the lanes of the value phase better (16 nodes:
-// all 64), shorter ones keep small batches spread over the chip and balance them finer: the longest trip
-// that still gives every wavefront slot of the chip (12 per CU) four trips of the CONCURRENT batch — 16 nodes from 2048 instances up, 8 at
-// 1024, 4 at 512 (512 x 108 on two ranges, updates/s: one-node kernel 329.7 k, 4 nodes 325.0 k, 8: 316.9 k, 16: 305.2 k).  The result does not depend on the
-// choice.  hb_config.reserved = 120 + s forces 2^s, 130 + L any length L <= 16 (lengths that are no power of two measured within the
-// noise of the powers of two at 512, 1024 and 4096 instances); 129 the one-node-per-wavefront kernel of rounds 1-5 (k_lq: cooperative leg
-// pass; A / B only, differs from the trips by rounding).
-constexpr int kLqTripsPerSlot = 4;
-static int lq_trip_len(const hb_ctx* ctx, int concurrent) {
-  const int sel = ctx->hconfig.debug_stop;
-  if (sel >= 120 && sel <= 124) return 1 << (sel - 120);
-  if (sel >= 131 && sel <= 146) return sel - 130;   // any trip length 1..16 (launch-geometry sweeps)
-  const long slots = 12L * ctx->n_cu;
-  for (int sh = 4; sh > 0; --sh)
-    if (long(concurrent) * ((ctx->Nmax + (1 << sh) - 1) >> sh) >= kLqTripsPerSlot * slots) return 1 << sh;
-  return 1;
-}
 static void launch_lq(hb_ctx* ctx, const Batch& b, int B, int concurrent, hipStream_t s) {
-  if (ctx->hconfig.debug_stop == 129) { hipLaunchKernelGGL(k_lq, dim3(ctx->Nmax, B), dim3(64), 0, s, b, ctx->dmodel, ctx->dconfig); return; }
-  const int len = lq_trip_len(ctx, concurrent);
+  if (ctx->forms.lq == KernelForms::Lq::OneNode) { hipLaunchKernelGGL(k_lq, dim3(ctx->Nmax, B), dim3(64), 0, s, b, ctx->dmodel, ctx->dconfig); return; }
+  const int len = lq_trip_len(ctx->forms, concurrent, ctx->Nmax, ctx->n_cu);
   const int ntrip = (ctx->Nmax + len - 1) / len;
   hipLaunchKernelGGL(k_lq_trip, dim3(unsigned(ntrip) * B), dim3(64), 0, s, b, ctx->dmodel, ctx->dconfig, len);
 }
 
-// Forward sweep: the wave form while the batch leaves a SIMD one wavefront (hb_config.reserved = 111 / 114 force the row / the wave form)
 static void launch_ric_fwd(hb_ctx* ctx, const Batch& b, int B, int concurrent, hipStream_t s) {
-  const int sel = ctx->hconfig.debug_stop;
-  if (sel == 114 || (sel != 111 && concurrent <= kRicFwdWaveMaxBatch)) hipLaunchKernelGGL(k_ric_fwd_w, dim3(B), dim3(64), 0, s, b);
+  if (use_ric_fwd_wave(ctx->forms, concurrent)) hipLaunchKernelGGL(k_ric_fwd_w, dim3(B), dim3(64), 0, s, b);
   else hipLaunchKernelGGL(k_ric_fwd, dim3(B), dim3(64), 0, s, b);
 }
 

@@ -1372,7 +1372,7 @@ HB_HD void hwbc_cascade(const Ctx& cx, const DevModel& M, const DevConfig& C, co
       if (cx.lane == 0) *status_out = HB_INST_MAXITER;
       return;
     }
-    HB_ABLATE_STOP(C.debug_stop == 43);  // profiling ablation: level 0 + kernel basis
+    HB_ABLATE_STOP(C.debug_stop == form::HWBC_KERNEL0);  // profiling ablation: level 0 + kernel basis
     const int rc1 = hwbc_level1(cx, C, rows, W, n1);
     if (rc1 > status) status = rc1;
     if constexpr (kCert) {
@@ -1384,7 +1384,7 @@ HB_HD void hwbc_cascade(const Ctx& cx, const DevModel& M, const DevConfig& C, co
       reached = 2;
       n1c = n1;
     }
-    HB_ABLATE_STOP(C.debug_stop == 44);  // profiling ablation: ... + level-1 QP
+    HB_ABLATE_STOP(C.debug_stop == form::HWBC_QP1);  // profiling ablation: ... + level-1 QP
     const int n2 = hwbc_level1_kernel(cx, W, n1);
     if (n2 < 0) {
       if (cx.lane == 0) *status_out = HB_INST_MAXITER;
@@ -1442,9 +1442,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) void
   __builtin_amdgcn_s_setprio(3);  // per-instance serial solve: latency critical next to another chunk's LQ kernel (see k_ric_bwd)
   const int inst = blockIdx.x;
   extern __shared__ __attribute__((aligned(16))) double lds_h[];
-  // hb_config.reserved = 41 / 42 stops the cascade after level 0 / 1 (profiling ablation only)
+  // HWBC_LEVEL0 / HWBC_LEVEL1 stop the cascade after level 0 / 1 (profiling build only)
   hwbc_solve(WbcDeviceCtx(), *M, *C, w.xdes + size_t(inst) * HB_NX, w.udes + size_t(inst) * HB_NU, w.rbd + size_t(inst) * HB_NRBD,
-             w.mode[inst], lds_h, w.sol + size_t(inst) * NW, w.status + inst, (HB_ABLATE_ON && C->debug_stop == 41) ? 1 : ((HB_ABLATE_ON && C->debug_stop == 42) ? 2 : 3));
+             w.mode[inst], lds_h, w.sol + size_t(inst) * NW, w.status + inst, (HB_ABLATE_ON && C->debug_stop == form::HWBC_LEVEL0) ? 1 : ((HB_ABLATE_ON && C->debug_stop == form::HWBC_LEVEL1) ? 2 : 3));
   if (threadIdx.x == 0) w.iters[inst] = 0;
 }
 // k_hwbc with the per-level certificate (hb_hwbc_set_certificate): the same solve, then the certificate, the per-level solutions, the

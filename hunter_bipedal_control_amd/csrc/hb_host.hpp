@@ -91,7 +91,7 @@ inline DevConfig make_dev_config(const hb_config& c, const DevModel& M) {
   d.wbc_reg_steps = c.wbc_reg_steps;
   d.wbc_eps_mode = c.wbc_eps_mode;
   for (int i = 0; i < HB_NJ; ++i) d.default_joint_state[i] = c.default_joint_state[i];
-  d.debug_stop = c.reserved;  // hb_config.reserved doubles as the profiling ablation switch
+  d.debug_stop = c.reserved;  // hb_config.reserved: every value the kernels read is named in hb_forms.hpp
   return d;
 }
 

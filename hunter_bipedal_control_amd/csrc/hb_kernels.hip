@@ -241,8 +241,8 @@ __global__ __launch_bounds__(64, 3) void k_lq_trip(Batch b, const DevModel* __re
   double* park = b.lqpark + (size_t(inst) * (b.Nmax + LqPark::trip_max) + k0) * LqPark::size;   // the trip's parked data (LqPark)
   lq_trip_stage_constants(*M, lds, threadIdx.x);
   WaveCtx().sync();
-  // (profiling build, 125: the value phase runs once per trip, later launches re-use what it parked — the dense part alone on valid data)
-  if (!(HB_ABLATE_ON && C->debug_stop == 125 && park[size_t(LqPark::n_feet / 4 * tlen) * 16] != 0.0)) {
+  // (profiling build, LQT_VALUES_ONCE: the value phase runs once per trip, later launches re-use what it parked — the dense part alone on valid data)
+  if (!(HB_ABLATE_ON && C->debug_stop == form::LQT_VALUES_ONCE && park[size_t(LqPark::n_feet / 4 * tlen) * 16] != 0.0)) {
     // (every lane runs the phase: lanes beyond the trip's last node repeat it and park nothing.  Raising the wavefront's priority for
     // this one long dependent chain was tried — s_setprio 3: 515 k against 525 k updates/s — and dropped)
     lq_trip_values(LqTrip{lds, park, tlen, nt, int(threadIdx.x), HB_ABLATE_ON ? C->debug_stop : 0}, *M, *C, b.x + size_t(inst) * (b.Nmax + 1) * HB_NX, b.u + size_t(inst) * b.Nmax * HB_NU,
@@ -253,16 +253,16 @@ __global__ __launch_bounds__(64, 3) void k_lq_trip(Batch b, const DevModel* __re
   __builtin_amdgcn_s_waitcnt(0);
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
 #if defined(HB_ABLATE) && defined(HB_LQV_TRACE)
-  if (C->debug_stop == 118 && blockIdx.x == 1000 && threadIdx.x == 0) {
+  if (C->debug_stop == form::LQT_TRACE && blockIdx.x == 1000 && threadIdx.x == 0) {
     const long long* m = reinterpret_cast<const long long*>(lds + LqLds::total - 24);
     const long long t12 = __builtin_readcyclecounter();
     printf("lq value-phase trace (cycles): loads %lld | fwd sweep %lld | feet %lld | bwd joints %lld %lld %lld %lld %lld | stash %lld | wait %lld | value pass 0 %lld | 1 %lld | drain %lld\n",
            m[1] - m[0], m[2] - m[1], 0LL, m[3] - m[2], m[4] - m[3], m[5] - m[4], m[6] - m[5], m[7] - m[6], m[8] - m[7], m[9] - m[8], m[10] - m[9], m[11] - m[10], t12 - m[11]);
     printf("   value pass 1: stash reads %lld | point values %lld | contact point, sums %lld | hand-out %lld | park %lld\n", m[12] - m[10], m[13] - m[12], m[14] - m[13], m[15] - m[14], m[11] - m[15]);
   }
-  if (C->debug_stop == 118) return;
+  if (C->debug_stop == form::LQT_TRACE) return;
 #endif
-  if (HB_ABLATE_ON && C->debug_stop >= 126 && C->debug_stop <= 128) return;   // profiling build: the value phase alone (127 / 128: parts of it)
+  if (HB_ABLATE_ON && C->debug_stop >= form::LQT_VALUES && C->debug_stop <= form::LQT_VALUES_LEGS) return;   // profiling build: the value phase alone, or parts of it
   // the lane's entry of the table the cost phase reads per lane, for all the trip's nodes (NodeIn::consts)
   const double c_tab = lq_lane_constants(*M, *C, threadIdx.x);
   for (int t = 0; t < nt; ++t) {
@@ -296,15 +296,14 @@ __global__ __launch_bounds__(64, 3) void k_lq_trip(Batch b, const DevModel* __re
     cx.sync();
     const double* park_lds = lds + LqLds::park;
     const double* xnext_lds = lds + LqLds::xnext_park;
-    // (profiling build, 117: every node of a workgroup writes ONE record slot — the stores are issued, their lines stay in the L2)
-    double* recp = b.recs + ((HB_ABLATE_ON && C->debug_stop == 117) ? size_t(blockIdx.x & 4095) : nd) * REC_SIZE;
+    // (profiling build, LQT_ONE_RECORD: every node of a workgroup writes ONE record slot — the stores are issued, their lines stay in the L2)
+    double* recp = b.recs + ((HB_ABLATE_ON && C->debug_stop == form::LQT_ONE_RECORD) ? size_t(blockIdx.x & 4095) : nd) * REC_SIZE;
     lq_node_dense(cx, *M, *C, in, lds, recp, [park_lds](int i) { return park_lds[i]; }, [xnext_lds](int i) { return xnext_lds[i]; });
     cx.sync();
   }
 #endif
 }
 
-constexpr int kRicBwd4MaxBatch = 512;    // instances per launch up to which the four-wavefront backward sweep is taken (measured)
 __global__ __launch_bounds__(64, 2) void k_ric_bwd(Batch b, int dbg) {
   // per-instance serial chain: when this kernel shares SIMDs with the node-parallel LQ kernel of another chunk stream (chunked
   // hb_step_resident), it is the latency-critical one — ask the arbiter to issue it first
@@ -345,9 +344,9 @@ __global__ __launch_bounds__(64, 2) void k_ric_bwd(Batch b, int dbg) {
     meta_nz = meta[1];
   }
 #if defined(HB_ABLATE)
-  // cycle-counter trace of one stage (tools/perf_quick.py --stop 197): the marks live in the slack words behind RicLds::flag, not in registers
+  // cycle-counter trace of one stage (tools/perf_quick.py --stop with RIC1_TRACE): the marks live in the slack words behind RicLds::flag, not in registers
   long long* t1_ = reinterpret_cast<long long*>(lds + RicLds::flag + 8);
-#define HB_RIC1_MARK(i) if (dbg == 197 && blockIdx.x == 9 && k == 50 && cx.lane == 0) t1_[i] = __builtin_readcyclecounter();
+#define HB_RIC1_MARK(i) if (dbg == form::RIC1_TRACE && blockIdx.x == 9 && k == 50 && cx.lane == 0) t1_[i] = __builtin_readcyclecounter();
 #else
 #define HB_RIC1_MARK(i)
 #endif
@@ -372,7 +371,7 @@ __global__ __launch_bounds__(64, 2) void k_ric_bwd(Batch b, int dbg) {
       }
     }
     cx.sync();
-    if (HB_ABLATE_ON && dbg == 20) { if (k > 0) HB_RIC_FETCH(k - 1, l); continue; }  // profiling ablation: staging only
+    if (HB_ABLATE_ON && dbg == form::RIC1_STAGING) { if (k > 0) HB_RIC_FETCH(k - 1, l); continue; }  // profiling ablation: staging only
     // n_til: number of projected inputs of this stage (uniform; requested one stage ahead with the prefetch)
     const int n_til = int(meta_nf) + int(meta_nz);
     HB_RIC1_MARK(1)
@@ -393,7 +392,7 @@ __global__ __launch_bounds__(64, 2) void k_ric_bwd(Batch b, int dbg) {
       meta_nf = meta[0];
       meta_nz = meta[1];
     }
-    if (HB_ABLATE_ON && (dbg == 21 || dbg == 22 || dbg == 23)) continue;
+    if (HB_ABLATE_ON && (dbg == form::RIC1_GEMM1 || dbg == form::RIC1_GEMM2 || dbg == form::RIC1_FACTOR)) continue;
     RicT3 t;
     HB_RIC1_MARK(3)
     ric_phase3_mma(cxk, lds, t, m1);
@@ -407,7 +406,7 @@ __global__ __launch_bounds__(64, 2) void k_ric_bwd(Batch b, int dbg) {
     ric_phase3_finish(cxk, lds, t);
     HB_RIC1_MARK(5)
 #if defined(HB_ABLATE)
-    if (dbg == 197 && blockIdx.x == 9 && k == 50 && cx.lane == 0)
+    if (dbg == form::RIC1_TRACE && blockIdx.x == 9 && k == 50 && cx.lane == 0)
       printf("ric1 trace: stage-in %lld | GEMM 1 + GEMM 2 + factor + solves %lld | fetch %lld | GEMM 3 %lld | Q~ + store %lld  (cycles)\n", t1_[1] - t1_[0], t1_[2] - t1_[1],
              t1_[3] - t1_[2], t1_[4] - t1_[3], t1_[5] - t1_[4]);
 #endif
@@ -471,7 +470,7 @@ __global__ __launch_bounds__(256, 2) void k_ric_bwd4(Batch b, int dbg) {
   double* Qs = lds + L::Qs;
 #if defined(HB_ABLATE)
   long long tr_[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-#define HB_RIC4_MARK(i) if (dbg == 199 && blockIdx.x == 7 && k == 50) tr_[i] = __builtin_readcyclecounter();
+#define HB_RIC4_MARK(i) if (dbg == form::RIC4_TRACE && blockIdx.x == 7 && k == 50) tr_[i] = __builtin_readcyclecounter();
 #else
 #define HB_RIC4_MARK(i)
 #endif
@@ -504,7 +503,7 @@ __global__ __launch_bounds__(256, 2) void k_ric_bwd4(Batch b, int dbg) {
     }
     block_sync_lds();
     HB_RIC4_MARK(1)
-    if (HB_ABLATE_ON && dbg == 24) continue;   // profiling ablation: staging only
+    if (HB_ABLATE_ON && dbg == form::RIC4_STAGING) continue;   // profiling ablation: staging only
     double* gains = b.gains + (size_t(inst) * b.Nmax + k) * GAIN_SIZE;
     const bool wide = n_til > 9;   // 12 projected inputs (double support): three 16-column tiles, 12 x 12 factor
     // ---- GEMM 1: M1 = S [A~ b~ B~ .] (+ s in the vector column)
@@ -531,7 +530,7 @@ __global__ __launch_bounds__(256, 2) void k_ric_bwd4(Batch b, int dbg) {
     }
     block_sync_lds();
     HB_RIC4_MARK(2)
-    if (HB_ABLATE_ON && dbg == 25) continue;   // ... + GEMM 1
+    if (HB_ABLATE_ON && dbg == form::RIC4_GEMM1) continue;   // ... + GEMM 1
     // ---- GEMM 2: Hu = B~' M1 + [P~ r~ R~ .]  (every element of [P~ r~ R~] is read and replaced by the lane that owns it)
     if (w < (wide ? 3 : 2)) {
       const int NC = wide ? L::LDW : 32, c0 = 16 * w;
@@ -542,7 +541,7 @@ __global__ __launch_bounds__(256, 2) void k_ric_bwd4(Batch b, int dbg) {
     }
     block_sync_lds();
     HB_RIC4_MARK(3)
-    if (HB_ABLATE_ON && dbg == 26) continue;   // ... + GEMM 2
+    if (HB_ABLATE_ON && dbg == form::RIC4_GEMM2) continue;   // ... + GEMM 2
     // ---- factor + solves on wavefront 0.  Meanwhile wavefronts 1..3 start GEMM 3, T = Q~ + A~' M1 + Hux' K~ on its upper block
     // triangle (tiles (0,0) / (0,1) / (1,1), one each): the A~' M1 part does not need the gains — six of a tile's nine matrix
     // instructions run under the factorisation, in the same accumulator and the same order as in the one-wavefront form
@@ -560,7 +559,7 @@ __global__ __launch_bounds__(256, 2) void k_ric_bwd4(Batch b, int dbg) {
     HB_RIC4_MARK(4)
     block_sync_lds();
     HB_RIC4_MARK(5)
-    if (HB_ABLATE_ON && dbg == 27) continue;   // ... + factor, solves | first part of GEMM 3
+    if (HB_ABLATE_ON && dbg == form::RIC4_FACTOR) continue;   // ... + factor, solves | first part of GEMM 3
     // ---- rest of GEMM 3: + Hux' K~, + Q~, new S | s (mirrored)
     if (w != 0) {
       tile_mma<NU_T, L::LDW, true, L::LDN, false, NU_T, true>(cx, t3, Hu + r0, Kk + c0, Mr, Nr);
@@ -571,7 +570,7 @@ __global__ __launch_bounds__(256, 2) void k_ric_bwd4(Batch b, int dbg) {
     block_sync_lds();
     HB_RIC4_MARK(7)
 #if defined(HB_ABLATE)
-    if (dbg == 199 && blockIdx.x == 7 && k == 50 && (tid & 63) == 0)
+    if (dbg == form::RIC4_TRACE && blockIdx.x == 7 && k == 50 && (tid & 63) == 0)
       printf("ric4 trace role %d: stage-in %lld gemm1 %lld (init %lld mma %lld store %lld barrier %lld) gemm2 %lld | own work %lld wait %lld | gemm3b %lld (mma %lld) wait %lld  (cycles)\n", w,
              tr_[1] - tr_[0], tr_[2] - tr_[1], tr_[8] - tr_[1], tr_[9] - tr_[8], tr_[10] - tr_[9], tr_[2] - tr_[10], tr_[3] - tr_[2], tr_[4] - tr_[3], tr_[5] - tr_[4],
              tr_[6] - tr_[5], tr_[11] - tr_[5], tr_[7] - tr_[6]);
@@ -662,7 +661,6 @@ __device__ __forceinline__ void ric_fwd_body(const Batch& b) {
 }
 __global__ __launch_bounds__(64) void k_ric_fwd(Batch b) { ric_fwd_body<false>(b); }
 __global__ __launch_bounds__(64) void k_ric_fwd_w(Batch b) { ric_fwd_body<true>(b); }
-constexpr int kRicFwdWaveMaxBatch = 512;
 
 // ---- KKT certificate of the stage QP (hb_mpccert.hpp), on demand: hb_mpc_get_certificate.  Work buffers of the instances of `b`.
 // One wavefront per (instance, node), grid as k_lq.  The Riccati part of the record and the gains are staged with 16-byte loads, every

@@ -34,7 +34,7 @@ struct DevConfig {
   double wbc_mu, swing_kp, swing_kd, bh_kp, bh_kd, ba_kp, ba_kd, w_swing, w_base, w_force, wbc_eps;
   int wbc_max_iter, wbc_type;
   double default_joint_state[HB_NJ];
-  int debug_stop;  // >0: lq_node returns after that phase (profiling ablation only)
+  int debug_stop;  // hb_config.reserved: a code of hb_forms.hpp (stops and traces: profiling build only)
   int wbc_reg_steps;
   int wbc_eps_mode;   // 0 fixed wbc_eps, 1 |H|_F * 1e3 EPS per problem (WeightedWbc)
 };
@@ -589,7 +589,7 @@ HB_HD void lq_tail(const Ctx& cx, const DevModel& M, const DevConfig& C, const N
 #if defined(__HIP_DEVICE_COMPILE__)
   if (cx.lane < 22) { lds[LqLds::park + cx.lane] = xref_reg; lds[LqLds::xnext_park + cx.lane] = xnext_reg; }  // (ordered by the barriers of the projection)
 #endif
-  HB_ABLATE_STOP(C.debug_stop == 1);
+  HB_ABLATE_STOP(C.debug_stop == form::LQ_COMPOSE);
   // slot classification (uniform): contact foot = 3 equality rows (zero velocity), swing foot = 1 equality row (normal velocity,
   // slot 3i) + 2 soft rows (xy reference, slots 3i+1, 3i+2)
   int n_f = 0;
@@ -711,7 +711,7 @@ HB_HD void lq_tail(const Ctx& cx, const DevModel& M, const DevConfig& C, const N
       if (!((donemask >> i) & 1)) perm[w++] = i;
   }
   cx.sync();
-  HB_ABLATE_STOP(C.debug_stop == 2);
+  HB_ABLATE_STOP(C.debug_stop == form::LQ_FACTOR);
   const int rank = rank_l;
   const int nz = 10 - rank;
   // Solve A11 Y = -W1 (23 right-hand sides) and, in the same instruction stream, the kernel basis
@@ -786,7 +786,7 @@ HB_HD void lq_tail(const Ctx& cx, const DevModel& M, const DevConfig& C, const N
 #endif
   }
 
-  HB_ABLATE_STOP(C.debug_stop == 3);
+  HB_ABLATE_STOP(C.debug_stop == form::LQ_SOLVES);
 #if defined(__HIP_DEVICE_COMPILE__)
   // the per-role constants of the cost phase (lane = role): weight and the two limits of the role's relaxed barrier.  With the lane's table
   // entries in registers (NodeIn::consts) they are gathered from the other lanes in the cost phase itself; otherwise requested HERE — behind
@@ -857,7 +857,7 @@ HB_HD void lq_tail(const Ctx& cx, const DevModel& M, const DevConfig& C, const N
     }
   }
   cx.sync();
-  HB_ABLATE_STOP(C.debug_stop == 30);
+  HB_ABLATE_STOP(C.debug_stop == form::LQ_DEFECT);
   // B~ columns: contact forces (foot order) first, zero padding after the kernel directions; one column per (uniform)
   // step, one row per lane (the kernel columns of rows 0..11 came from the tile above)
   for (int row = cx.lane; row < 22; row += cx.nlanes) {
@@ -884,7 +884,7 @@ HB_HD void lq_tail(const Ctx& cx, const DevModel& M, const DevConfig& C, const N
     }
     rec[rec_b(row)] = s;
   }
-  HB_ABLATE_STOP(C.debug_stop == 31);
+  HB_ABLATE_STOP(C.debug_stop == form::LQ_B_COLUMNS);
   // -------------------------------------------------------------- phase 4: cost pieces, one "role" per lane; then the cost part of the record
   // roles 0..21 state entries, 22..43 input entries, 44..55 constraint slots, 56..59 friction barrier values.
   // Partial sums (cost, defect^2, equality^2) are reduced through LDS (scratch aliases Mm, not live yet).
@@ -1081,7 +1081,7 @@ HB_HD void lq_tail(const Ctx& cx, const DevModel& M, const DevConfig& C, const N
   }
   cx.sync();
 #endif
-  HB_ABLATE_STOP(C.debug_stop == 4);
+  HB_ABLATE_STOP(C.debug_stop == form::LQ_COST);
   // soft rows: gradients and the dense pieces P_j, R_jj
   for (int c = cx.lane; c < 32; c += cx.nlanes) {  // rows 0..21: state directions -> q_x; rows 22..31: joint-rate directions -> r_u
     double s = 0;
@@ -1126,7 +1126,7 @@ HB_HD void lq_tail(const Ctx& cx, const DevModel& M, const DevConfig& C, const N
   }
   cx.sync();
 
-  HB_ABLATE_STOP(C.debug_stop == 5);
+  HB_ABLATE_STOP(C.debug_stop == form::LQ_SOFT_ROWS);
   // Q~ = Q + Kx' M + P_j' Kx ,  Q = diag(Qd) + w sum_soft c c'      (three accumulating GEMMs on the matrix cores)
   // Q~ is symmetric up to rounding: only its upper block triangle is formed — tiles (0,0), (0,1) and (1,1), 27 MFMAs
   // instead of 36 — and the off-diagonal tile is stored twice (k_ric_bwd mirrors the upper triangle anyway).
@@ -1158,7 +1158,7 @@ HB_HD void lq_tail(const Ctx& cx, const DevModel& M, const DevConfig& C, const N
       if (a <= b) *dst = dt * v;
     });
   }
-  HB_ABLATE_STOP(C.debug_stop == 32);
+  HB_ABLATE_STOP(C.debug_stop == form::LQ_Q);
   for (int a = cx.lane; a < 22; a += cx.nlanes) {
     rec[REC_QF + a] = dt * qx[a];
     rec[REC_RF + a] = dt * ru[a];
@@ -1177,7 +1177,7 @@ HB_HD void lq_tail(const Ctx& cx, const DevModel& M, const DevConfig& C, const N
     for (int a = 0; a < NU_T; ++a)
       if (a < n_f || a >= ntil) rec[rec_P(a, c)] = 0.0;
   }
-  HB_ABLATE_STOP(C.debug_stop == 33);
+  HB_ABLATE_STOP(C.debug_stop == form::LQ_P);
   // R~ (12x12): contact-force blocks, Z' R_jj Z, identity on the padding
   for (int idx = cx.lane; idx < NU_T * NU_T; idx += cx.nlanes) {
     const int ca = idx / NU_T, cb = idx % NU_T;
@@ -1206,7 +1206,7 @@ HB_HD void lq_tail(const Ctx& cx, const DevModel& M, const DevConfig& C, const N
     }
     rec[rec_r(col)] = dt * s;
   }
-  HB_ABLATE_STOP(C.debug_stop == 34);
+  HB_ABLATE_STOP(C.debug_stop == form::LQ_R);
   // recovery data
   for (int k = cx.lane; k < 10; k += cx.nlanes) rec[REC_KE + k] = Kx[k * LDK + 22];
   for (int idx = cx.lane; idx < 60; idx += cx.nlanes) rec[REC_Z + idx] = idx % 6 < nz ? Z[(idx / 6) * LDK + idx % 6] : 0.0;  // (zero-padded: the forward sweep runs six terms)
@@ -1242,7 +1242,7 @@ HB_HD void lq_node_dense(const Ctx& cx, const DevModel& M, const DevConfig& C, c
   }
   cx.sync();
 #endif
-  HB_ABLATE_STOP(C.debug_stop == 9);
+  HB_ABLATE_STOP(C.debug_stop == form::LQ_DIRECTIONS);
   // constraint rows of the base-position directions (closed form)
   for (int task = cx.lane; task < 3; task += cx.nlanes) lq_closed_task(C, lds, in.mode, task);
   cx.sync();
@@ -1317,12 +1317,12 @@ struct LqTrip {   // what the value phase's helpers share
   double* lds;
   double* park;   // the trip's parked data
   int tlen, nt, lane;   // lines of a node lie tlen lines apart (the trip's nominal length, 1..16), nt <= tlen nodes exist
-  int dbg;        // profiling build: 127 / 128 leave the value phase behind the forward sweep / the leg pass
+  int dbg;        // profiling build: LQT_VALUES_FWD / LQT_VALUES_LEGS leave the value phase behind the forward sweep / the leg pass
 };
 #if defined(HB_ABLATE) && defined(HB_LQV_TRACE)
-// cycle-counter trace of ONE wavefront's value phase (build.sh --ablate -DHB_LQV_TRACE, tools/perf_quick.py --stop 118): marks in the last
+// cycle-counter trace of ONE wavefront's value phase (build.sh --ablate -DHB_LQV_TRACE, tools/perf_quick.py --stop with LQT_TRACE): marks in the last
 // words of the node's LDS.  The compiler moves arithmetic across the marks: good for the sweeps and the waits, coarse inside the value passes.
-#define HB_LQV_MARK(tr, i) if ((tr).dbg == 118 && blockIdx.x == 1000 && (tr).lane == 0) reinterpret_cast<long long*>((tr).lds + LqLds::total - 24)[i] = __builtin_readcyclecounter();
+#define HB_LQV_MARK(tr, i) if ((tr).dbg == form::LQT_TRACE && blockIdx.x == 1000 && (tr).lane == 0) reinterpret_cast<long long*>((tr).lds + LqLds::total - 24)[i] = __builtin_readcyclecounter();
 #else
 #define HB_LQV_MARK(tr, i)
 #endif
@@ -1337,7 +1337,7 @@ __device__ __forceinline__ void lq_park_out(const LqTrip& tr, int n0, const doub
   asm volatile("" : "+v"(lane));   // (addresses rebuilt per call: kept across the calls of a whole phase they were spilled)
   lane &= 63;
   const int t = lane >> 2, e = lane & 3;
-  if (t < tr.nt && !(HB_ABLATE_ON && tr.dbg == 119)) {   // (profiling build, 119: the value phase computes but parks nothing — stale data is read back)
+  if (t < tr.nt && !(HB_ABLATE_ON && tr.dbg == form::LQT_PARK_NOTHING)) {   // (profiling build: the value phase computes but parks nothing — stale data is read back)
     double* line = tr.park + (size_t(n0 >> 2) * tr.tlen + t) * 16 + 2 * e;
 #pragma unroll
     for (int i = 0; i < 8; i += 2) {
@@ -1388,7 +1388,7 @@ __device__ __forceinline__ void lq_trip_leg_pass(const LqTrip& tr, const DevMode
     R = R * axis_rot_sc<double>(ax, sk, ck);
     op = o;
   }
-  if (HB_ABLATE_ON && tr.dbg == 127) return;
+  if (HB_ABLATE_ON && tr.dbg == form::LQT_VALUES_FWD) return;
   HB_LQV_MARK(tr, 2)
 #pragma unroll
   for (int f = 0; f < 2; ++f) {
@@ -1468,7 +1468,7 @@ __device__ __forceinline__ void lq_trip_values(const LqTrip& tr, const DevModel&
     double val[27];
     lq_trip_leg_pass(tr, M, leg, pt_own ? dt : 0.0, xk, uk, val);
     HB_LQV_MARK(tr, 8)
-    if (HB_ABLATE_ON && (tr.dbg == 127 || tr.dbg == 128)) return;
+    if (HB_ABLATE_ON && (tr.dbg == form::LQT_VALUES_FWD || tr.dbg == form::LQT_VALUES_LEGS)) return;
     // its contact points, and the head of their joint-induced velocities: entries 200..207
 #pragma unroll
     for (int n = 0; n < 8; ++n) tail[n] = val[15 + n];
@@ -1686,7 +1686,7 @@ HB_HD void lq_node(const Ctx& cx, const DevModel& M, const DevConfig& C, const N
   // composites per joint, staged in LDS); the direction lanes of stage 2 then
   // evaluate the closed-form tangents of the 27 leg outputs (rigid rotation of the outboard composite about the seeded
   // joint axis).
-  HB_ABLATE_STOP(C.debug_stop == 10);
+  HB_ABLATE_STOP(C.debug_stop == form::LQ_LOADS);
   double* LJ_all = lds + LqLds::LJ;  // 4 x LEGJ_SIZE; its head is overwritten by ABt in the final compose
   leg_value_pass_coop(cx, M, 4, [](int g) { return g & 1; },
                       [xs, us, dt](int g, int j) { return xs[12 + j] + ((g >> 1) ? dt : 0.0) * us[12 + j]; },
@@ -1695,7 +1695,7 @@ HB_HD void lq_node(const Ctx& cx, const DevModel& M, const DevConfig& C, const N
                       , &jc_pre
 #endif
                       );
-  HB_ABLATE_STOP(C.debug_stop == 6);
+  HB_ABLATE_STOP(C.debug_stop == form::LQ_LEG_VALUES);
   // ---- values of BOTH RK2 points (plain doubles), one after the other: flow map, constraint-row values of the first point, and the
   // uniform values the direction lanes multiply their tangents with (lq_point_values / lq_store_point_values).  The second point
   // x + dt f(x, u) needs the first one's flow map.  Device: four lanes run the (identical) whole-body part and take one contact
@@ -1779,7 +1779,7 @@ HB_HD void lq_node(const Ctx& cx, const DevModel& M, const DevConfig& C, const N
     cx.sync();
   }
 #endif
-  HB_ABLATE_STOP(C.debug_stop == 7);
+  HB_ABLATE_STOP(C.debug_stop == form::LQ_VALUE_PREPASS);
   lq_node_dense(cx, M, C, in, lds, rec, xref_at, xnext_at);
 }
 

@@ -11,8 +11,10 @@
 #define HB_HD inline
 #endif
 
-// Profiling ablation exits (tools/perf_quick.py --ablate-*): compiled in only with -DHB_ABLATE (csrc/build.sh --ablate builds the
-// variant library variants/libhunter_hip_ablate.so); the release kernels carry none of them.
+#include "hb_forms.hpp"  // the codes the exits below compare DevConfig::debug_stop with
+
+// Profiling ablation exits (tools/perf_quick.py --ablate-*): exits only with -DHB_ABLATE (csrc/build.sh --ablate: variants/libhunter_hip_ablate.so).
+// In the release kernels HB_ABLATE_STOP is a compiler-only ordering point (see below) and HB_ABLATE_ON folds every other profiling condition away.
 #if defined(HB_ABLATE)
 #define HB_ABLATE_STOP(cond) do { if (cond) return; } while (0)
 #define HB_ABLATE_ON 1

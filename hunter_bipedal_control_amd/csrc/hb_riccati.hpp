@@ -306,16 +306,16 @@ HB_HD void ric_phase12(const Ctx& cx, double* lds, double* gains, int n_til, Wav
   static_assert(RicLds::CU + 9 <= 32, "x block, vector and 9 inputs must fit two tiles");
   if (n_til <= 9) {
     ric_phase1<2>(cx, lds, m1);
-    HB_ABLATE_STOP(dbg == 21);
+    HB_ABLATE_STOP(dbg == form::RIC1_GEMM1);
     ric_phase2_gemm<2>(cx, lds, m1);
-    HB_ABLATE_STOP(dbg == 22);
+    HB_ABLATE_STOP(dbg == form::RIC1_GEMM2);
     ric_factor_solve<9>(cx, lds + RicLds::Hu, lds + RicLds::Kk, lds + RicLds::flag, gains);
   } else {
     WaveTile<2, 3> m1w;
     ric_phase1<3>(cx, lds, m1w);
-    HB_ABLATE_STOP(dbg == 21);
+    HB_ABLATE_STOP(dbg == form::RIC1_GEMM1);
     ric_phase2_gemm<3>(cx, lds, m1w);
-    HB_ABLATE_STOP(dbg == 22);
+    HB_ABLATE_STOP(dbg == form::RIC1_GEMM2);
 #if defined(__HIP_DEVICE_COMPILE__)
 #pragma unroll
     for (int tm = 0; tm < 2; ++tm)
@@ -423,7 +423,7 @@ template <class Ctx>
 HB_HD void riccati_bwd_node(const Ctx& cx, double* lds, const double* rec, double* gains, int dbg = 0) {
   WaveTile<2, 2> m1;
   ric_phase12(cx, lds, gains, int(rec[REC_META]) + int(rec[REC_META + 1]), m1, dbg);
-  HB_ABLATE_STOP(dbg == 21 || dbg == 22 || dbg == 23);  // profiling ablation markers (hb_config.reserved)
+  HB_ABLATE_STOP(dbg == form::RIC1_GEMM1 || dbg == form::RIC1_GEMM2 || dbg == form::RIC1_FACTOR);  // profiling stops (hb_forms.hpp)
   RicT3 t;
   ric_phase3_mma(cx, lds, t, m1);
   double* Qs = lds + RicLds::Qs;

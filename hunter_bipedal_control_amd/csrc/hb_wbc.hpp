@@ -445,13 +445,13 @@ HB_HD void wbc_phase_a(const Ctx& cx, const DevModel& M, const DevConfig& C, con
   for (int task = cx.lane; task < (stance_mode ? 1 : 2); task += cx.nlanes)
     body_pass_base(M, task ? K.qd : q, task ? K.vd : v, task ? D : P, K.BA[task]);
   cx.sync();
-  HB_ABLATE_STOP(C.debug_stop == 13);  // profiling ablation markers 13..16 (hb_config.reserved): phase A step by step
+  HB_ABLATE_STOP(C.debug_stop == form::WBC_A_BASE);  // profiling stops WBC_A_BASE .. WBC_A_FINISH (hb_forms.hpp): phase A step by step
   for (int task = cx.lane; task < (stance_mode ? 2 : 4); task += cx.nlanes) {
     const int pass = task >> 1, leg = task & 1;
     body_pass_leg(M, pass ? K.qd : q, pass ? K.vd : v, pass ? D : P, K.W[task], leg, K.LA[task]);
   }
   cx.sync();
-  HB_ABLATE_STOP(C.debug_stop == 14);
+  HB_ABLATE_STOP(C.debug_stop == form::WBC_A_LEGS);
   for (int task = cx.lane; task < (stance_mode ? 1 : 2); task += cx.nlanes)
     body_pass_finish(task ? D : P, K.BA[task], K.LA[2 * task], K.LA[2 * task + 1]);
   for (int task = cx.lane; task < 2; task += cx.nlanes) {
@@ -479,7 +479,7 @@ HB_HD void wbc_phase_a(const Ctx& cx, const DevModel& M, const DevConfig& C, con
     }
   }
   cx.sync();
-  HB_ABLATE_STOP(C.debug_stop == 15);
+  HB_ABLATE_STOP(C.debug_stop == form::WBC_A_FINISH);
   // ---- step 2: fills shared by the wave.  EoM rows: [M, -J', -S'] x = -nle   (WbcBase.cpp:138-149)
   for (int idx = cx.lane; idx < 16 * NW; idx += cx.nlanes) {
     const int i = idx / NW, j = idx - NW * i;
@@ -724,7 +724,7 @@ struct WbcState {
 #endif
 };
 #if defined(HB_ABLATE) && defined(__HIP_DEVICE_COMPILE__)
-#define HB_WBC_MARK(i) if (C.debug_stop == 198 && blockIdx.x == 5) st.wt_[i] = __builtin_readcyclecounter();
+#define HB_WBC_MARK(i) if (C.debug_stop == form::WBC_TRACE && blockIdx.x == 5) st.wt_[i] = __builtin_readcyclecounter();
 #else
 #define HB_WBC_MARK(i)
 #endif
@@ -1147,11 +1147,11 @@ HB_HD void wbc_solve(const Ctx& cx, const DevModel& M, const DevConfig& C, const
   if (cx.lane == 0) W.misc[0] = 0.0;  // status
   cx.sync();
   HB_WBC_MARK(1)
-  HB_ABLATE_STOP(C.debug_stop == 11 || (C.debug_stop >= 13 && C.debug_stop <= 15));
+  HB_ABLATE_STOP(C.debug_stop == form::WBC_A || (C.debug_stop >= form::WBC_A_BASE && C.debug_stop <= form::WBC_A_FINISH));
   st.eps = wbc_eps(cx, C, W, st);
   // ------------------------------------------------------------------ phase B: cost factor, unconstrained minimiser
   wbc_cost_factor(cx, C, udes, W, st);
-  HB_ABLATE_STOP(C.debug_stop == 12);
+  HB_ABLATE_STOP(C.debug_stop == form::WBC_B);
   // ------------------------------------------------------------------ phase C: Goldfarb–Idnani iterations
   wbc_load_jrow(cx, W, st);
   wbc_equality_block(cx, C, W, st);
@@ -1166,7 +1166,7 @@ HB_HD void wbc_solve(const Ctx& cx, const DevModel& M, const DevConfig& C, const
   cx.sync();
   HB_WBC_MARK(6)
 #if defined(HB_ABLATE) && defined(__HIP_DEVICE_COMPILE__)
-  if (C.debug_stop == 198 && blockIdx.x == 5 && cx.lane == 0)
+  if (C.debug_stop == form::WBC_TRACE && blockIdx.x == 5 && cx.lane == 0)
     printf("wbc trace: phase A %lld | Householder of A_w %lld | J = R^-1, x0 %lld | equality block (%d rows) %lld | primal update %lld | inequalities (%d iterations) %lld | row 5: d = J'n %lld, reflector %lld  (cycles)\n",
            st.wt_[1] - st.wt_[0], st.wt_[2] - st.wt_[1], st.wt_[3] - st.wt_[2], st.n_eq_active, st.wt_[4] - st.wt_[3], st.wt_[5] - st.wt_[4], st.iter - st.n_eq_active, st.wt_[6] - st.wt_[5], st.wt_[8] - st.wt_[7], st.wt_[9] - st.wt_[8]);
 #endif

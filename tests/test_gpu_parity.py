@@ -995,7 +995,7 @@ def test_randomised_command_workload_parity_two_iterations(params, oracle):
 
 @pytest.mark.parametrize("nu", [9, 12, 6])
 def test_riccati_one_and_four_wavefront_sweeps(params, oracle, nu):
-    """Both forms of the backward sweep (hb_config.reserved = 101: one wavefront per instance, k_ric_bwd; 104: four, k_ric_bwd4 —
+    """Both forms of the backward sweep (hb_config.reserved = RIC_BWD_ONE: one wavefront per instance, k_ric_bwd; RIC_BWD_FOUR: four, k_ric_bwd4 —
     the product picks by batch size) on the unit problem of test_riccati: each against the oracle at 1e-9, and BIT-IDENTICAL to
     each other (the four-wavefront form cuts the stage by output tiles; every tile is accumulated exactly as before)."""
     from hunter_bipedal_control_amd.solver import HunterSolver
@@ -1012,7 +1012,8 @@ def test_riccati_one_and_four_wavefront_sweeps(params, oracle, nu):
     q, r = rng.standard_normal((n, N, 22)), rng.standard_normal((n, N, nu))
     dx0 = 0.1 * rng.standard_normal((n, 22))
     out = {}
-    for variant in (101, 104):
+    one, four = abi.FORM.RIC_BWD_ONE, abi.FORM.RIC_BWD_FOUR
+    for variant in (one, four):
         s = HunterSolver(params, batch=8, max_nodes=N, reserved=variant)
         try:
             out[variant] = s.riccati_solve(A, Bm, b, Q, R, P, q, r, dx0)
@@ -1021,15 +1022,15 @@ def test_riccati_one_and_four_wavefront_sweeps(params, oracle, nu):
     for i in range(n):
         dxo, duo = oracle.riccati(A[i], Bm[i], b[i], Q[i], R[i], P[i], q[i], r[i], dx0[i])
         scale = max(1.0, np.abs(dxo).max())
-        for variant in (101, 104):
+        for variant in (one, four):
             assert np.abs(out[variant][0][i] - dxo).max() < 1e-9 * scale and np.abs(out[variant][1][i] - duo).max() < 1e-9 * scale
-    assert np.array_equal(out[101][0], out[104][0]) and np.array_equal(out[101][1], out[104][1])
+    assert np.array_equal(out[one][0], out[four][0]) and np.array_equal(out[one][1], out[four][1])
 
 
 @pytest.mark.parametrize("gait", ["trot", "stance", "ragged"])
 def test_sqp_step_identical_with_either_form_of_the_sweeps(params, gait):
-    """Three SQP iterations + WBC of a whole batch with the one- and the four-wavefront backward sweep (hb_config.reserved = 101 / 104)
-    and with the row and the wave form of the forward sweep (111 / 114; the product picks each by batch size): bit-identical iterate,
+    """Three SQP iterations + WBC of a whole batch with the one- and the four-wavefront backward sweep (hb_config.reserved = RIC_BWD_ONE / RIC_BWD_FOUR)
+    and with the row and the wave form of the forward sweep (RIC_FWD_ROW / RIC_FWD_WAVE; the product picks each by batch size): bit-identical iterate,
     step, performance index and WBC solution — trot (9-wide stages), a standing batch (12-wide stages: three tiles, 12 x 12 factor)
     and ragged horizons with all four modes (incl. a single interval and the 6-wide flight stages)."""
     from hunter_bipedal_control_amd.solver import HunterSolver
@@ -1051,7 +1052,8 @@ def test_sqp_step_identical_with_either_form_of_the_sweeps(params, gait):
         t_now = refs["t"][:, 0] + 0.004
     B = x0.shape[0]
     res = {}
-    for variant in (101, 104, 111, 114):
+    base, others = abi.FORM.RIC_BWD_ONE, (abi.FORM.RIC_BWD_FOUR, abi.FORM.RIC_FWD_ROW, abi.FORM.RIC_FWD_WAVE)
+    for variant in (base,) + others:
         s = HunterSolver(params, batch=B, max_nodes=44, reserved=variant)
         try:
             s.set_references(refs)
@@ -1065,18 +1067,18 @@ def test_sqp_step_identical_with_either_form_of_the_sweeps(params, gait):
             res[variant] = (xs_, us_, dx_, du_, s.get_performance(), sol_, st_, s.mpc_status())
         finally:
             s.close()
-    for variant in (104, 111, 114):
-        for k, (p, q) in enumerate(zip(res[101], res[variant])):
+    for variant in others:
+        for k, (p, q) in enumerate(zip(res[base], res[variant])):
             assert np.array_equal(p, q), (gait, variant, k)
-    assert res[101][7].max() == 0 and np.isfinite(res[101][0]).all()
+    assert res[base][7].max() == 0 and np.isfinite(res[base][0]).all()
 
 
 @pytest.mark.parametrize("gait", ["trot", "ragged"])
 def test_lq_trip_lengths_agree_bit_for_bit_and_with_the_one_node_kernel(params, gait):
-    """k_lq_trip: a wavefront takes a trip of L <= 16 consecutive nodes of an instance (hb_config.reserved = 120 + s: L = 2^s, 130 + L:
-    any length; the product picks a power of two by the number of instances in flight).  A node's arithmetic does not depend on the trip
+    """k_lq_trip: a wavefront takes a trip of L <= 16 consecutive nodes of an instance (hb_config.reserved = first of LQ_TRIP_POW2 + s: L = 2^s,
+    first of LQ_TRIP_LEN + L - 1: any length; the product picks a power of two by the number of instances in flight).  A node's arithmetic does not depend on the trip
     length — every L gives the same bits, ragged
-    horizons and trips cut short by the horizon's end included —, and the one-node-per-wavefront kernel of rounds 1-5 (129: cooperative
+    horizons and trips cut short by the horizon's end included —, and the one-node-per-wavefront kernel of rounds 1-5 (LQ_ONE_NODE: cooperative
     leg pass with cross-lane scans) differs from the trips by rounding only (serial leg pass, peeled frames): 1e-9 relative on the
     iterate after three SQP iterations, identical accepted step sizes and status words."""
     from hunter_bipedal_control_amd.solver import HunterSolver
@@ -1095,7 +1097,9 @@ def test_lq_trip_lengths_agree_bit_for_bit_and_with_the_one_node_kernel(params, 
         t_now = refs["t"][:, 0] + 0.004
     B = x0.shape[0]
     res = {}
-    for variant in (120, 121, 122, 123, 124, 133, 137, 143, 129):
+    pow2, length = abi.FORM_RANGES["LQ_TRIP_POW2"][0], abi.FORM_RANGES["LQ_TRIP_LEN"][0] - 1
+    trips = [pow2 + s for s in range(5)] + [length + L for L in (3, 7, 13)]
+    for variant in trips + [abi.FORM.LQ_ONE_NODE]:
         s = HunterSolver(params, batch=B, max_nodes=44, reserved=variant)
         try:
             s.set_references(refs)
@@ -1109,13 +1113,14 @@ def test_lq_trip_lengths_agree_bit_for_bit_and_with_the_one_node_kernel(params, 
             res[variant] = (xs_, us_, dx_, du_, s.get_performance(), sol_, st_, s.mpc_status())
         finally:
             s.close()
-    for variant in (121, 122, 123, 124, 133, 137, 143):
-        for k, (p, q) in enumerate(zip(res[120], res[variant])):
+    for variant in trips[1:]:
+        for k, (p, q) in enumerate(zip(res[trips[0]], res[variant])):
             assert np.array_equal(p, q), (gait, variant, k)
-    assert res[124][7].max() == 0 and np.isfinite(res[124][0]).all()
-    one = res[129]
-    assert np.array_equal(one[7], res[124][7]) and np.array_equal(one[6], res[124][6])
-    assert np.array_equal(one[4][:, 3], res[124][4][:, 3])                       # accepted step sizes
+    ref = res[trips[4]]   # (trips of 16 nodes)
+    assert ref[7].max() == 0 and np.isfinite(ref[0]).all()
+    one = res[abi.FORM.LQ_ONE_NODE]
+    assert np.array_equal(one[7], ref[7]) and np.array_equal(one[6], ref[6])
+    assert np.array_equal(one[4][:, 3], ref[4][:, 3])                       # accepted step sizes
     for k in (0, 1):
         scale = max(1.0, np.abs(one[k]).max())
-        assert np.abs(one[k] - res[124][k]).max() < 1e-9 * scale, (gait, k, np.abs(one[k] - res[124][k]).max())
+        assert np.abs(one[k] - ref[k]).max() < 1e-9 * scale, (gait, k, np.abs(one[k] - ref[k]).max())

@@ -9,7 +9,7 @@ import bench
 ap = argparse.ArgumentParser()
 ap.add_argument("--batch", type=int, default=4096)
 ap.add_argument("--lib", default=None, help="variant library (variants/libhunter_hip_ablate.so)")
-ap.add_argument("--stop", type=int, default=0, help="ablation stop of the backward sweep (20..23, HB_ABLATE build)")
+ap.add_argument("--stop", type=int, default=0, help="ablation stop of the backward sweep (a value of abi.RIC1_STOPS, HB_ABLATE build)")
 args = ap.parse_args()
 if args.lib:
     from pathlib import Path

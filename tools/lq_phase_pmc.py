@@ -2,17 +2,17 @@
 """Summary of tools/lq_phase_pmc.sh: per ablation stop the k_lq counters per wavefront (= per node), and the increments phase by phase."""
 import sys
 from pathlib import Path
-sys.path.insert(0, str(Path(__file__).resolve().parent))
+sys.path[:0] = [str(Path(__file__).resolve().parent), str(Path(__file__).resolve().parents[1])]
 from pmc_summary import per_kernel
+from hunter_bipedal_control_amd import abi
 
-ORDER = [(10, "loads"), (6, "leg value pass"), (7, "value pre-pass"), (9, "direction pass"), (1, "compose"), (2, "Gram + pivoted Cholesky"),
-         (3, "solves"), (30, "defect, A~ B~ tiles"), (31, "B~ columns, b~"), (4, "cost"), (5, "soft rows, Pj, M"), (32, "Q~ q~"), (33, "P~ r~"),
-         (34, "R~"), (0, "recovery data, end")]   # (code order: A~ / B~ / b~ are formed right behind the projection)
+NAME = {v: k for k, v in abi.FORMS.items()}
+ORDER = [(sp, NAME[sp]) for sp in abi.LQ_STOPS + (abi.FORM.NONE,)]   # (code order: A~ / B~ / b~ are formed right behind the projection)
 root = Path(sys.argv[1])
 KERNEL, PER = "k_lq", 1.0
 if len(sys.argv) > 2 and sys.argv[2] == "--trip":   # k_lq_trip: a wavefront walks a trip of nodes; counters are shown per NODE (100 nodes = 7 trips of <= 16)
     KERNEL, PER = "k_lq_trip", 100.0 / 7.0
-    ORDER = [(126, "value phase (trip)")] + [(sp, ("read-back + " if sp == 9 else "") + nm) for sp, nm in ORDER if sp not in (10, 6, 7)]
+    ORDER = [(abi.FORM.LQT_VALUES, NAME[abi.FORM.LQT_VALUES])] + ORDER[3:]   # (the three stops of lq_node's own value phase are not in the trip kernel)
 prev = None
 print(f"{'phase':26s} {'us':>8s} {'VALU':>7s} {'SALU':>7s} {'LDS':>6s} {'kcyc/wave':>10s} {'stall%':>7s} {'wait%':>6s}   (increments; counters per wavefront)")
 for stop, name in ORDER:

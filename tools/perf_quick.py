@@ -14,11 +14,11 @@ ap.add_argument("--batch", type=int, default=4096)
 ap.add_argument("--chunks", type=int, default=1)
 ap.add_argument("--no-tail", action="store_true", help="A/B: alpha_decay = 0, i.e. no backtracking-tail launches")
 ap.add_argument("--standing", action="store_true", help="every instance stands (mode STANCE at every node: the 12-wide stages of the sweeps)")
-ap.add_argument("--reserved", type=int, default=0, help="hb_config.reserved of the timed run (e.g. 120 + s: LQ trips of 2^s nodes; 129: the one-node kernel)")
+ap.add_argument("--reserved", type=int, default=0, help="hb_config.reserved of the timed run: a value of abi.FORMS / abi.FORM_RANGES (csrc/hb_forms.hpp), e.g. 120 + s = LQ_TRIP_POW2: trips of 2^s nodes")
 ap.add_argument("--stop", type=int, default=None, help="run ONLY this ablation stop (HB_ABLATE build), few steps: for counter passes")
 args = ap.parse_args()
 from pathlib import Path
-from hunter_bipedal_control_amd import ingest, workload, solver as _solver_mod
+from hunter_bipedal_control_amd import abi, ingest, workload, solver as _solver_mod
 if args.lib:  # a variant build (tools only; the product loader has no override)
     _solver_mod._LIB_PATH = Path(args.lib).resolve()
 from hunter_bipedal_control_amd.solver import HunterSolver
@@ -30,7 +30,7 @@ B, N = args.batch, 100
 def run(reserved=0, steps=args.steps):
     s = HunterSolver(P, batch=B, max_nodes=N + (8 if args.standing else 0), reserved=reserved, **({"alpha_decay": 0.0} if args.no_tail else {}))
     if args.standing:
-        from hunter_bipedal_control_amd import abi, gait
+        from hunter_bipedal_control_amd import gait
         hor = N * P["config"]["dt"]
         x0, rbd, cmd = workload.batch_inputs(P, B, 0, (0.0, 0.0, 0.0, 0.0), False)
         sched = gait.schedule_window(gait.gait_schedule(P, "stance", 0.1, 0.1 + 2 * hor + 2.0), 0.1 - hor - 1.0, 1e9)
@@ -75,13 +75,13 @@ if args.chunks > 1:
     run(steps=3)  # throwaway context: the first context of a process overlaps its chunk streams worse
 print(json.dumps(dict(lib=args.lib or "default", **run(args.reserved, steps=max(args.steps, 30 * 4096 // B)))))
 if args.ablate_lq:
-    for stop in (10, 6, 7, 9, 1, 2, 3, 30, 31, 4, 5, 32, 33, 34):  # (code order)
+    for stop in abi.LQ_STOPS:  # (code order)
         r = run(stop, steps=5)
         print(json.dumps(dict(stop=stop, ms_lq=r["ms_lq"])))
 if args.ablate_ric:
-    for stop in (24, 25, 26, 27, 104):   # four-wavefront sweep (k_ric_bwd4): staging / + GEMM 1 / + GEMM 2 / + factor, solves / whole
+    for stop in abi.RIC4_STOPS + (abi.FORM.RIC_BWD_FOUR,):   # four-wavefront sweep (k_ric_bwd4): staging / + GEMM 1 / + GEMM 2 / + factor, solves / whole
         r = run(stop, steps=5)
         print(json.dumps(dict(stop=stop, ms_ric_bwd4=r["ms_riccati_bwd"])))
-    for stop in (20, 21, 22, 23):
+    for stop in abi.RIC1_STOPS:
         r = run(stop, steps=5)
         print(json.dumps(dict(stop=stop, ms_ric_bwd=r["ms_riccati_bwd"])))

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """A / B of bench.py's configs[3] share (512 instances, per-instance commands, two instance ranges) over hb_config.reserved values / variant
-libraries:  python tools/share_ab.py [--lib variants/x.so] --reserved 0 129 123"""
+libraries:  python tools/share_ab.py [--lib variants/x.so] --reserved 0 129 123   (abi.FORMS / abi.FORM_RANGES: NONE, LQ_ONE_NODE, LQ_TRIP_POW2 + 3)"""
 import argparse, json, os, sys, time
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 ap = argparse.ArgumentParser()
