@@ -32,3 +32,10 @@ elif bad:
     sys.exit("build.sh: scratch memory in hot kernel(s): " + ", ".join(bad))
 PY
 rm -f "$LOG"
+# The device unit wrappers of the test suite (tests/gpu_unit/primitives.hip: one kernel per device-only primitive of hb_math.hpp /
+# hb_tile.hpp / hb_qpfactor.hpp), same flags; built with the product so that it travels with the tree.  Not part of libhunter_hip.so.
+if [ "$ABLATE" = "0" ] && [ -f ../../tests/gpu_unit/primitives.hip ]; then
+  TMP=../../tests/gpu_unit/libhb_primitives.$$.so
+  $HIPCC $HB_HIPCC_FLAGS -shared -o $TMP ../../tests/gpu_unit/primitives.hip || { rm -f $TMP; exit 1; }
+  mv -f $TMP ../../tests/gpu_unit/libhb_primitives.so
+fi

@@ -22,32 +22,11 @@
 #include "hb_plant.hpp"
 #include "hb_sensors.hpp"
 #include "hb_layout.hpp"
+#include "hb_wavectx.hpp"
 
 using namespace hb;
 
 namespace {
-
-struct DeviceCtx {
-  int lane, nlanes;
-  __device__ DeviceCtx() : lane(threadIdx.x), nlanes(blockDim.x) {}
-  __device__ void sync() const { __syncthreads(); }
-};
-// Context of the kernels whose workgroup is exactly one wavefront and whose lanes exchange data through LDS only.  The
-// LDS unit executes the DS instructions of one wave in order, so "every lane's earlier LDS writes are visible to every
-// lane's later LDS reads" needs no hardware barrier and, unlike __syncthreads() (a workgroup-scope fence: s_waitcnt
-// vmcnt(0)), does not drain the global loads / stores in flight — software-pipelined prefetches stay in flight across
-// the phases of a stage.  What remains is a compiler-level ordering point.
-struct WaveCtx {
-  int lane;
-  static constexpr int nlanes = 64;
-  __device__ WaveCtx() : lane(threadIdx.x) {}
-  __device__ explicit WaveCtx(int l) : lane(l) {}
-  __device__ void sync() const {
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-  }
-};
-
 
 __global__ void k_set_x0(Batch b) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;

@@ -200,11 +200,13 @@ __device__ __forceinline__ double wave_max_f64(double v) {
 #undef HB_DPP_MAX
   return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), 63), __builtin_amdgcn_readlane(__double2loint(v), 63));
 }
-// max(0, maximum over the 64 lanes), returned uniformly: the same ladder for values whose maximum only matters when it is positive
-// (the pivot search of the rank-revealing Cholesky).  Lanes without a source read zero (bound_ctrl) instead of keeping a copy of
+// The same ladder for values whose maximum only matters when it is positive (the pivot search of the rank-revealing Cholesky): the
+// maximum over the 64 lanes when that is positive, otherwise SOME value that is not positive (the maximum itself, as it happens: lane
+// 63, the lane read back, has a source in every step, so none of the zeros below reaches it) — enough for a caller that only compares
+// the result with a threshold >= 0.  Returned uniformly.  Lanes without a source read zero (bound_ctrl) instead of keeping a copy of
 // their own value, and the maximum is the bare v_max_f64 (fmax() canonicalises both operands first): 22 VALU instructions
 // instead of 38.
-__device__ __forceinline__ double wave_max_nonneg_f64(double v) {
+__device__ __forceinline__ double wave_max_pos_f64(double v) {
 #define HB_DPP_MAX0(ctrl, rmask)                                                                            \
   {                                                                                                         \
     const int lo2_ = __builtin_amdgcn_update_dpp(0, __double2loint(v), ctrl, rmask, 0xf, true);             \
@@ -226,6 +228,14 @@ __device__ __forceinline__ double wave_max_nonneg_f64(double v) {
   HB_DPP_MAX0(0x143, 0xc)
 #undef HB_DPP_MAX0
   return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), 63), __builtin_amdgcn_readlane(__double2loint(v), 63));
+}
+// max(0, maximum over the 64 lanes), returned uniformly: the ladder above with the 0 applied to the value read back, on the scalar
+// unit — a maximum with the sign bit set (negative, or -0.0) becomes +0.0.  (Two scalar selects behind the read-back: on the
+// dependency chain of a caller that loops on the result they cost what they look like, see wave_max_pos_f64.)
+__device__ __forceinline__ double wave_max_nonneg_f64(double v) {
+  const double m = wave_max_pos_f64(v);
+  const int hi = __double2hiint(m), lo = __double2loint(m);
+  return __hiloint2double(hi < 0 ? 0 : hi, hi < 0 ? 0 : lo);
 }
 // Sum over the 64 lanes of a wavefront, returned uniformly (same DPP ladder; lanes without a source add zero).
 __device__ __forceinline__ double wave_sum_f64(double v) {
@@ -489,6 +499,14 @@ __device__ __forceinline__ void seg8_prefix_mat3(Mat3<double>& P) {
 #pragma unroll
   for (int e = 0; e < 9; ++e) S.m[e] = seg8_shift_entry<CTRL, BANK>(P.m[e], e, carrier);
   P = S * P;
+}
+// Inclusive prefix product over each group of eight lanes: lane k < 5 <- M_0 M_1 ... M_k (in that order) of the matrices the lanes of
+// its group came in with.  Distances 1, 2, 4; the last step only has a partner for lane 4 of a group.  (Lanes 5..7 must hold the
+// identity or are not read afterwards.)
+__device__ __forceinline__ void seg8_prefix_product(Mat3<double>& P) {
+  seg8_prefix_mat3<0x111, 0xf>(P);   // row_shr:1
+  seg8_prefix_mat3<0x112, 0xf>(P);   // row_shr:2
+  seg8_prefix_mat3<0x114, 0xa>(P);   // row_shr:4: only lane 4 of a group has a partner
 }
 #endif
 

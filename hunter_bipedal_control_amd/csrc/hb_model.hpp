@@ -304,9 +304,7 @@ HB_HD void leg_value_pass_coop(const Ctx& cx, const DevModel& M, int ngroups, LE
     if (!dvalid) E = Mat3<double>::identity();
     // frames: inclusive prefix product P_k = E_0 ... E_k, then R_k^- = P_{k-1} (identity in front of the first joint)
     Mat3<double> P = E;
-    seg8_prefix_mat3<0x111, 0xf>(P);   // row_shr:1
-    seg8_prefix_mat3<0x112, 0xf>(P);   // row_shr:2
-    seg8_prefix_mat3<0x114, 0xa>(P);   // row_shr:4: only lane 4 of a group has a partner
+    seg8_prefix_product(P);
     Mat3<double> Rm;
 #pragma unroll
     for (int e = 0; e < 9; ++e) {

@@ -383,9 +383,7 @@ __device__ __forceinline__ void ik_kin(const IkLane& L, const Mat3<double>& R0, 
   Mat3<double> E = axis_rot_sc<double>(L.ax, sv, cv);
   if (!L.joint) E = Mat3<double>::identity();
   Mat3<double> P = E;
-  seg8_prefix_mat3<0x111, 0xf>(P);
-  seg8_prefix_mat3<0x112, 0xf>(P);
-  seg8_prefix_mat3<0x114, 0xa>(P);
+  seg8_prefix_product(P);
   Mat3<double> Pex;
 #pragma unroll
   for (int e = 0; e < 9; ++e) {

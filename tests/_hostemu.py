@@ -12,7 +12,7 @@ CSRC = Path(__file__).resolve().parents[1] / "hunter_bipedal_control_amd" / "csr
 
 def build() -> Path:
     so = HERE / "libhostemu.so"
-    deps = [HERE / "hostemu.cpp", *CSRC.glob("*.hpp")]
+    deps = [HERE / "hostemu.cpp", HERE.parent / "gpu_unit" / "prim_cases.hpp", *CSRC.glob("*.hpp")]
     with open(HERE / ".hostemu.lock", "w") as lock:
         fcntl.flock(lock, fcntl.LOCK_EX)
         if not so.exists() or so.stat().st_mtime < max(d.stat().st_mtime for d in deps):

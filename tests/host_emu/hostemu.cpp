@@ -264,3 +264,89 @@ void emu_plant_step(const hb_model* m, double* q, double* v, double* anchor, int
   plant_step(cx, d, q, v, anchor, pinned, tau, contact, baum, eps, dt, substeps, lds.data(), lambda, vdot);
 }
 }
+
+// The host twin of the device unit wrappers (tests/gpu_unit/primitives.hip): the same cases (tests/gpu_unit/prim_cases.hpp) through the
+// host branches of the product headers, with the arguments of the hbp_* entries.  tests/test_primitives_host.py feeds them the vectors
+// and the assertion helpers of the GPU tests; tests/test_gpu_primitives_qpfactor.py measures the device against them.
+#include "../gpu_unit/prim_cases.hpp"
+extern "C" {
+int32_t emu_prim_math(int32_t op, const double* x, int32_t n, double* y) {
+  if (n <= 0) return -1;
+#define HBP_MATH_CASE(OP) case hbp::OP: for (int i = 0; i < n; ++i) hbp::math_point<hbp::OP>(x, n, i, y); break;
+  switch (op) {
+    HBP_MATH_OPS(HBP_MATH_CASE)
+    default: return -1;
+  }
+#undef HBP_MATH_CASE
+  return 0;
+}
+int32_t emu_prim_tile_desc(int32_t id, int32_t* d) { return hbp::tile_desc(id, d); }
+int32_t emu_prim_sizes(int32_t* s) {
+  const int32_t v[8] = {hbp::N_TILE_SPECS, hbp::TILE_LDS, hbp::TILE_DST, hbp::RT_LD, hbp::RT_LDD, hbp::RT_WORDS, hbp::QF_A, hbp::QF_R};
+  std::memcpy(s, v, sizeof(v));
+  return 0;
+}
+int32_t emu_prim_tile_mma(int32_t id, int32_t ncases, const double* img, const int32_t* par, double sw, double* dst) {
+  using namespace hbp;   // (the names inside HBP_TILE_SPECS)
+  if (ncases <= 0) return -1;
+  for (int c = 0; c < ncases; ++c)
+    if (!hbp::tile_par_ok(par + 8 * c)) return -1;
+  // (the image gets a margin: where the device reads mapped words behind an operand, the host loops stay inside Mr x Nr x KR anyway)
+  std::vector<double> lds(2 * hbp::TILE_LDS, 0.0);
+#define HBP_TILE_CASE(ID, ...)                                                                                                  \
+  case ID: {                                                                                                                    \
+    typedef __VA_ARGS__ S;                                                                                                      \
+    for (int c = 0; c < ncases; ++c) {                                                                                          \
+      std::memcpy(lds.data(), img + size_t(c) * hbp::TILE_LDS, hbp::TILE_LDS * 8);                                              \
+      hbp::tile_mma_case<S>(HostCtx{}, lds.data(), par + 8 * c, sw, dst + size_t(c) * hbp::TILE_DST);                           \
+    }                                                                                                                           \
+    break;                                                                                                                      \
+  }
+  switch (id) {
+    HBP_TILE_SPECS(HBP_TILE_CASE)
+    default: return -1;
+  }
+#undef HBP_TILE_CASE
+  return 0;
+}
+int32_t emu_prim_tile_roundtrip(int32_t ncases, const double* a, const double* b, const int32_t* par, double scale, double* dst, int32_t* flag) {
+  if (ncases <= 0) return -1;
+  for (int c = 0; c < ncases; ++c)
+    if (!hbp::roundtrip_par_ok(par + 8 * c)) return -1;
+  for (int c = 0; c < ncases; ++c) {
+    flag[c] = 0;
+    hbp::tile_roundtrip_case(HostCtx{}, a + size_t(c) * hbp::RT_WORDS, b + size_t(c) * hbp::RT_WORDS, par + 8 * c, scale,
+                             dst + size_t(c) * hbp::RT_WORDS, flag + c);
+  }
+  return 0;
+}
+// (diag: the diagonal of R for lanes j < n, zero behind — the host form has no per-lane return value)
+int32_t emu_prim_regularised_factor(int32_t which, int32_t ncases, const double* A, const double* b, const int32_t* par, const double* dpar,
+                                    double* R, double* J, double* g, double* diag) {
+  if (ncases <= 0 || which < 0 || which > 1) return -1;
+  for (int c = 0; c < ncases; ++c)
+    if (!hbp::regfac_par_ok(par + 8 * c, which == 0 ? 18 : 24)) return -1;
+  for (int c = 0; c < ncases; ++c) {
+    double np[64] = {0.0};
+    const int32_t* p = par + 8 * c;
+    double* Rc = R + size_t(c) * hbp::QF_R;
+    if (which == 0)
+      hbp::regularised_factor_case<18, false, false>(HostCtx{}, p, dpar + 2 * c, A + size_t(c) * hbp::QF_A, b + 32 * c, Rc, J + size_t(c) * hbp::QF_R,
+                                                     g + 16 * c, np);
+    else
+      hbp::regularised_factor_case<24, true, true>(HostCtx{}, p, dpar + 2 * c, A + size_t(c) * hbp::QF_A, b + 32 * c, Rc, J + size_t(c) * hbp::QF_R,
+                                                   g + 16 * c, np);
+    for (int j = 0; j < 64; ++j) diag[64 * c + j] = j < p[0] ? Rc[j * p[3] + j] : 0.0;
+  }
+  return 0;
+}
+int32_t emu_prim_givens(int32_t ncases, int32_t* par, double* R, double* J, double* np, int32_t* act, int32_t* is_active, double* lam) {
+  if (ncases <= 0) return -1;
+  for (int c = 0; c < ncases; ++c)
+    if (!hbp::givens_par_ok(par + 8 * c, act + 64 * c)) return -1;
+  for (int c = 0; c < ncases; ++c)
+    hbp::givens_case(HostCtx{}, par + 8 * c, R + size_t(c) * hbp::QF_R, J + size_t(c) * hbp::QF_R, np + 64 * c, act + 64 * c, is_active + 64 * c,
+                     lam + 64 * c);
+  return 0;
+}
+}
