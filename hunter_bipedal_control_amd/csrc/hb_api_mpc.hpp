@@ -1,5 +1,5 @@
 // Host side, part 2: the MPC — node tables, cold and warm start, the SQP iteration and its launchers, read-back of the iterate,
-// KKT certificate and stage-QP export.
+// KKT certificate, stage-QP export and the export of the records' recovery data.
 #pragma once
 
 extern "C" {
@@ -286,19 +286,31 @@ int32_t hb_mpc_get_certificate(hb_ctx* ctx, int32_t inst_begin, int32_t inst_cou
   return HB_OK;
 }
 
-int32_t hb_mpc_get_lq(hb_ctx* ctx, int32_t inst, double* A, double* B, double* b, double* Q, double* P, double* R, double* q, double* r,
-                      int32_t* n_til) {
-  HB_ENTER_ARGS(false);
-  HB_FAIL_IF(inst < 0 || inst >= ctx->B, HB_ERR_ARG, "hb_mpc_get_lq: instance outside the batch");
-  HB_TRY(mpc_records_current(ctx, "hb_mpc_get_lq"));
+// What hb_mpc_get_lq and hb_mpc_get_recovery share: the checks, the node count n of instance `inst` (clamped to [0, max_nodes]) and its
+// records, pulled on the MPC stream and synchronised.
+static int32_t pull_instance_records(hb_ctx* ctx, const char* who, int32_t inst, std::vector<double>& recs, int& n) {
+  if (inst < 0 || inst >= ctx->B) {
+    ctx->err = std::string(who) + ": instance outside the batch";
+    return HB_ERR_ARG;
+  }
+  HB_TRY(mpc_records_current(ctx, who));
   HB_ENTER_DEVICE();
-  const size_t N = ctx->Nmax;
-  std::vector<double> recs(extent_of(ctx->b, N, ctx->b.recs).n);
-  int n = 0;
+  recs.resize(extent_of(ctx->b, ctx->Nmax, ctx->b.recs).n);
+  n = 0;
   HB_TRY(pull(ctx, &n, ctx->b, ctx->b.n_nodes, Range{inst, 1}, &ctx->s_mpc));
   HB_TRY(pull(ctx, recs.data(), ctx->b, ctx->b.recs, Range{inst, 1}, &ctx->s_mpc));
   HB_HIP(hipStreamSynchronize(ctx->s_mpc));
   n = std::max(0, std::min(n, ctx->Nmax));
+  return HB_OK;
+}
+
+int32_t hb_mpc_get_lq(hb_ctx* ctx, int32_t inst, double* A, double* B, double* b, double* Q, double* P, double* R, double* q, double* r,
+                      int32_t* n_til) {
+  HB_ENTER_ARGS(false);
+  std::vector<double> recs;
+  int n = 0;
+  HB_TRY(pull_instance_records(ctx, "hb_mpc_get_lq", inst, recs, n));
+  const size_t N = ctx->Nmax;
   const auto zero = [N](double* p, size_t per) { if (p) std::memset(p, 0, N * per * 8); };   // rows k >= n stay zero
   zero(A, 22 * 22); zero(B, 22 * NU_T); zero(b, 22); zero(Q, 22 * 22); zero(P, NU_T * 22); zero(R, NU_T * NU_T); zero(q, 22); zero(r, NU_T);
   if (n_til) std::memset(n_til, 0, N * sizeof(int32_t));
@@ -309,6 +321,22 @@ int32_t hb_mpc_get_lq(hb_ctx* ctx, int32_t inst, double* A, double* B, double* b
                r ? r + k * 12 : nullptr, &nt);
     if (n_til) n_til[k] = nt;
   }
+  return HB_OK;
+}
+
+int32_t hb_mpc_get_recovery(hb_ctx* ctx, int32_t inst, double* Kx, double* ke, double* Z, double* dF, double* qf, double* rf, double* meta,
+                            double* dt, double* dq) {
+  HB_ENTER_ARGS(false);
+  std::vector<double> recs;
+  int n = 0;
+  HB_TRY(pull_instance_records(ctx, "hb_mpc_get_recovery", inst, recs, n));
+  const size_t N = ctx->Nmax;
+  const auto zero = [N](double* p, size_t per) { if (p) std::memset(p, 0, N * per * 8); };   // rows k >= n stay zero
+  zero(Kx, 220); zero(ke, 10); zero(Z, 60); zero(dF, 12); zero(qf, 22); zero(rf, 22); zero(meta, 6); zero(dt, 1); zero(dq, 10);
+  const auto at = [](double* p, size_t k, size_t per) { return p ? p + k * per : nullptr; };
+  for (size_t k = 0; k < size_t(n); ++k)
+    rec_unpack_recovery(recs.data() + k * REC_SIZE, at(Kx, k, 220), at(ke, k, 10), at(Z, k, 60), at(dF, k, 12), at(qf, k, 22), at(rf, k, 22),
+                        at(meta, k, 6), at(dt, k, 1), at(dq, k, 10));
   return HB_OK;
 }
 

@@ -94,6 +94,18 @@ inline void rec_unpack(const double* rec, double* A, double* B, double* b, doubl
   }
   if (n_til) *n_til = int(rec[REC_META]) + int(rec[REC_META + 1]);
 }
+// The rest of the record, what recovers the full input step from the projected one (du = T u~ + K dx + k, hunter_hip.h) and what the
+// line search reads: Kx [10][22], ke [10], Z [10][6], dF [12], qf [22], rf [22], meta [6] (n_f, n_z, mode, cost dt, dyn_sse dt,
+// eq_sse dt), dt [1], dq [10].  Straight copies, nothing is recomputed.  Any pointer may be null.
+HB_HD void rec_unpack_recovery(const double* rec, double* Kx, double* ke, double* Z, double* dF, double* qf, double* rf, double* meta,
+                               double* dt, double* dq) {
+  const auto copy = [rec](double* dst, int at, int n) {
+    if (dst)
+      for (int i = 0; i < n; ++i) dst[i] = rec[at + i];
+  };
+  copy(Kx, REC_KX, 220); copy(ke, REC_KE, 10); copy(Z, REC_Z, 60); copy(dF, REC_DF, 12); copy(qf, REC_QF, 22); copy(rf, REC_RF, 22);
+  copy(meta, REC_META, 6); copy(dt, REC_DT, 1); copy(dq, REC_DQ, 10);
+}
 
 struct RelaxedBarrierD {
   double mu, delta;

@@ -29,7 +29,7 @@ ABI_SYMBOLS = [
     "hb_plant_get_state", "hb_hoqp_solve", "hb_mpc_reset_masked", "hb_mpc_get_status", "hb_joint_set_flags",
     "hb_joint_get_emergency_stop", "hb_set_resident_time", "hb_get_wbc_iterations", "hb_ik_solve", "hb_debug_chunk_counters", "hb_debug_graph_state", "hb_refgen_get_status", "hb_tick_resident",
     "hb_wbc_set_certificate", "hb_wbc_get_certificate", "hb_hwbc_set_certificate", "hb_hwbc_get_certificate",
-    "hb_mpc_get_certificate", "hb_mpc_get_lq",
+    "hb_mpc_get_certificate", "hb_mpc_get_lq", "hb_mpc_get_recovery",
     "hb_refgen_get_schedule", "hb_gait_reset", "hb_gait_disable", "hb_gait_insert_template", "hb_gait_get_state",
     "hb_plant_set_sensor_model", "hb_plant_sense", "hb_estimator_update_resident", "hb_estimator_contact_force_resident",
 ]
@@ -396,6 +396,19 @@ class HunterSolver:
         self._check(self.lib.hb_mpc_get_lq(self.ctx, C.c_int32(inst), *[_p(out[k]) for k in ("A", "B", "b", "Q", "P", "R", "q", "r", "n_til")]),
                     "hb_mpc_get_lq")
         n = int(np.count_nonzero(out["n_til"]))   # every stage has at least the six kernel coordinates
+        return {k: v[:n].copy() for k, v in out.items()}
+
+    RECOVERY_KEYS = ("Kx", "ke", "Z", "dF", "qf", "rf", "meta", "dt", "dq")
+
+    def mpc_recovery(self, inst: int) -> dict:
+        """The rest of the records of instance `inst` (hb_mpc_get_recovery), trimmed to its n intervals: what recovers the full input
+        step du = T u~ + K dx + k (hunter_hip.h) and what the line search reads.  Kx [n][10][22], ke [n][10], Z [n][10][6], dF [n][12],
+        qf [n][22], rf [n][22], meta [n][6] (n_f, n_z, mode, cost dt, dyn_sse dt, eq_sse dt), dt [n], dq [n][10]."""
+        N = self.N
+        out = dict(Kx=np.zeros((N, 10, 22)), ke=np.zeros((N, 10)), Z=np.zeros((N, 10, 6)), dF=np.zeros((N, 12)), qf=np.zeros((N, 22)),
+                   rf=np.zeros((N, 22)), meta=np.zeros((N, 6)), dt=np.zeros(N), dq=np.zeros((N, 10)))
+        self._check(self.lib.hb_mpc_get_recovery(self.ctx, C.c_int32(inst), *[_p(out[k]) for k in self.RECOVERY_KEYS]), "hb_mpc_get_recovery")
+        n = int(np.count_nonzero(out["meta"][:, 0] + out["meta"][:, 1]))   # every stage has at least the six kernel coordinates
         return {k: v[:n].copy() for k, v in out.items()}
 
     def sync(self):

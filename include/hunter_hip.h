@@ -407,7 +407,21 @@ int32_t hb_hwbc_get_certificate(hb_ctx* ctx, int32_t inst_begin, int32_t inst_co
  * are zero.  The work buffers are allocated on the first call.
  * hb_mpc_get_lq: the stage QP of one instance, unpacked on the host into dense row-major arrays in the standard OCP-QP layout
  * (A, B, b, Q, S = P, R, q, r: what HPIPM takes), n_til = projected inputs per stage; any pointer may be NULL; rows k >= n are zero.
- * Both: HB_ERR_STATE when no MPC call has completed, or when the node tables or the iterate were replaced since the last one
+ * hb_mpc_get_recovery: the rest of the same instance's records, copied as stored: what turns the projected input u~ of the stage QP back
+ * into the full input step, and what the line search reads.  The stage QP above is the unprojected node LQ (dynamics A, B, b; cost
+ * Q, P, R, q, r, scaled by dt; equality constraints C dx + D du + e = 0) after the change of input variables
+ *       du = T u~ + K dx + k      (du [22]: 12 contact forces, foot by foot, then 10 joint rates)
+ *   T [22][12]: column a < n_f is the unit vector of the a-th force row of the contact feet, taken in foot order (3 rows per contact
+ *       foot of the mode); column n_f + b, b < n_z, holds Z[:, b] under the joint-rate rows 12..21; the columns behind n_f + n_z are zero.
+ *       The columns of T span the null space of D.
+ *   K [22][22] = [0 ; Kx] and k [22] = [dF ; ke]: dF = -F on the swing feet (their force is constrained to zero) and 0 on the contact
+ *       feet; (Kx, ke) is the basic least-squares solution of the velocity rows of the constraints for the joint rates.
+ *   Hence A~ = A + B K, B~ = B T, b~ = b + B k, R~ = T'RT (+ I on the padding), P~ = T'(P + R K), Q~ = Q + K'P + P'K + K'RK,
+ *   r~ = T'(r + R k), q~ = q + K'r + (P' + K'R) k.
+ *   Kx [max_nodes][10][22], ke [..][10], Z [..][10][6] (columns >= n_z zero), dF [..][12], qf [..][22] and rf [..][22] (the unprojected
+ *   cost gradients q and r, scaled by dt), meta [..][6] (n_f, n_z, mode, cost dt, dyn_sse dt = dt |b|^2, eq_sse dt = dt |e|^2),
+ *   dt [max_nodes] (interval length), dq [..][10] (the joint rows of b); any pointer may be NULL; rows k >= n are zero.
+ * All three: HB_ERR_STATE when no MPC call has completed, or when the node tables or the iterate were replaced since the last one
  * (hb_mpc_set_references, hb_refgen_update, hb_mpc_reset, hb_mpc_reset_masked, hb_mpc_set_trajectory); HB_ERR_ARG on a bad range. */
 #define HB_MPC_CERT_R_DYN 0       /* max(|dx_0|_inf, max_k |dx_(k+1) - (A~_k dx_k + B~_k u~_k + b~_k)|_inf) */
 #define HB_MPC_CERT_R_STAT 1      /* max_k |r~_k + P~_k dx_k + R~_k u~_k + B~_k' lambda_(k+1)|_inf */
@@ -423,6 +437,9 @@ int32_t hb_mpc_get_certificate(hb_ctx* ctx, int32_t inst_begin, int32_t inst_cou
 int32_t hb_mpc_get_lq(hb_ctx* ctx, int32_t inst, double* A /*[max_nodes][22][22]*/, double* B /*[..][22][12]*/, double* b /*[..][22]*/,
                       double* Q /*[..][22][22], full symmetric*/, double* P /*[..][12][22]*/, double* R /*[..][12][12]*/,
                       double* q /*[..][22]*/, double* r /*[..][12]*/, int32_t* n_til /*[max_nodes]*/);
+int32_t hb_mpc_get_recovery(hb_ctx* ctx, int32_t inst, double* Kx /*[max_nodes][10][22]*/, double* ke /*[..][10]*/, double* Z /*[..][10][6]*/,
+                            double* dF /*[..][12]*/, double* qf /*[..][22]*/, double* rf /*[..][22]*/, double* meta /*[..][6]*/,
+                            double* dt /*[max_nodes]*/, double* dq /*[..][10]*/);
 /* Pipelining of hb_step_resident: the batch is cut into n_chunks (1..8) instance ranges, each a linear
  * MPC -> publish -> WBC sequence on its own HIP stream so that the per-instance sweeps of one range overlap the
  * per-node kernels of another.  Results are identical for every n_chunks; hb_get_stats phase times are only

@@ -244,6 +244,21 @@ class MpcMrtInterface {
                "hb_mpc_get_lq");
     return s;
   }
+  // The rest of the same records (hb_mpc_get_recovery): what recovers the full input step du = T u~ + K dx + k (hunter_hip.h) and what
+  // the line search reads, [maxNodes] stages each, rows behind the instance's horizon zero.
+  struct Recovery {
+    vector_t Kx, ke, Z, dF, qf, rf, meta, dt, dq;   // [maxNodes] x (10x22, 10, 10x6, 12, 22, 22, 6, 1, 10)
+  };
+  Recovery recovery(int inst) const {
+    const size_t N = size_t(ctx_.maxNodes());
+    Recovery r;
+    r.Kx.assign(N * 220, 0.0); r.ke.assign(N * 10, 0.0); r.Z.assign(N * 60, 0.0); r.dF.assign(N * 12, 0.0); r.qf.assign(N * 22, 0.0);
+    r.rf.assign(N * 22, 0.0); r.meta.assign(N * 6, 0.0); r.dt.assign(N, 0.0); r.dq.assign(N * 10, 0.0);
+    ctx_.check(hb_mpc_get_recovery(ctx_.get(), inst, r.Kx.data(), r.ke.data(), r.Z.data(), r.dF.data(), r.qf.data(), r.rf.data(), r.meta.data(),
+                                   r.dt.data(), r.dq.data()),
+               "hb_mpc_get_recovery");
+    return r;
+  }
   const Context& context() const { return ctx_; }
 
  private:

@@ -1,7 +1,8 @@
 // TEST HARNESS: one SQP iteration's LQ approximation and Riccati sweeps of one instance (as hostemu.cpp's emu_sqp_iteration) followed by
-// the certificate of the stage QP (hb_mpccert.hpp) and the stage-QP export (hb_lq.hpp rec_unpack), compiled for the host with one
-// emulated lane, for tests/test_mpc_certificate_host.py.  Not part of the product; the product path runs k_mpc_cert_nodes /
+// the certificate of the stage QP (hb_mpccert.hpp) and the stage-QP export (hb_lq.hpp rec_unpack, rec_unpack_recovery), compiled for the host with one
+// emulated lane, for tests/test_mpc_certificate_host.py and tests/test_lq_record_host.py.  Not part of the product; the product path runs k_mpc_cert_nodes /
 // k_mpc_cert_sweep.
+#include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <vector>
@@ -69,6 +70,25 @@ void emu_mpc_certificate(const hb_model* m, const hb_config* c, int N, const dou
   for (int k = 0; k < N; ++k)
     rec_unpack(recs.data() + size_t(k) * REC_SIZE, A + k * 484, B + k * 264, b + k * 22, Q + k * 484, P + k * 264, R + k * 144, q + k * 22,
                r + k * 12, n_til + k);
+}
+// The stage records of one horizon of the host twin, node by node, at a caller-given linearisation point: lq_node on x [N+1][22]
+// (x[k+1] is node k's x_next; x[0] is taken as given), u [N][22], t [N+1], mode [N], xref [N][22], swing [N][24].  Outputs: the stage QP
+// as emu_mpc_certificate returns it and the rest of each record (rec_unpack_recovery): Kx [N][10][22], ke [N][10], Z [N][10][6], dF [N][12],
+// qf [N][22], rf [N][22], meta [N][6], dt [N], dq [N][10].
+void emu_lq_records(const hb_model* m, const hb_config* c, int N, const double* t, const int* mode, const double* xref, const double* swing,
+                    const double* x, const double* u, double* A, double* B, double* b, double* Q, double* P, double* R, double* q, double* r,
+                    int* n_til, double* Kx, double* ke, double* Z, double* dF, double* qf, double* rf, double* meta, double* dt, double* dq) {
+  DevModel d = make_dev_model(*m);
+  DevConfig dc = make_dev_config(*c, d);
+  HostCtx cx;
+  std::vector<double> rec(REC_SIZE), lds(LqLds::total, 0.0);
+  for (int k = 0; k < N; ++k) {
+    NodeIn in{x + k * 22, u + k * 22, x + (k + 1) * 22, xref + k * 22, swing + k * 24, t[k + 1] - t[k], mode[k]};
+    std::fill(rec.begin(), rec.end(), 0.0);   // (the device's allocation is zeroed once: the unused column of the rows stays 0)
+    lq_node(cx, d, dc, in, lds.data(), rec.data());
+    rec_unpack(rec.data(), A + k * 484, B + k * 264, b + k * 22, Q + k * 484, P + k * 264, R + k * 144, q + k * 22, r + k * 12, n_til + k);
+    rec_unpack_recovery(rec.data(), Kx + k * 220, ke + k * 10, Z + k * 60, dF + k * 12, qf + k * 22, rf + k * 22, meta + k * 6, dt + k, dq + k * 10);
+  }
 }
 // rec_unpack of one record of REC_SIZE doubles (the arrays of one stage)
 void emu_rec_unpack(const double* rec, double* A, double* B, double* b, double* Q, double* P, double* R, double* q, double* r, int* n_til) {
