@@ -184,6 +184,35 @@ def make_sensor_config(seed: int = 0, instance_offset: int = 0, **sigmas) -> HbS
     return out
 
 
+class HbContactConfig(C.Structure):
+    """hb_contact_config (include/hunter_hip.h): contact model of the plant, hb_plant_set_contact_model."""
+    _fields_ = [("mode", C.c_int32), ("sweeps", C.c_int32), ("mu", C.c_double), ("ground_z", C.c_double), ("erp", C.c_double),
+                ("tol", C.c_double), ("fall_height", C.c_double), ("reserved", C.c_int32 * 2)]
+
+
+HB_CONTACT_NONFINITE, HB_CONTACT_FALLEN, HB_CONTACT_UNCONVERGED = 1, 2, 4
+# Default sweep count of make_contact_config, from the residual decay of the numpy twin of the definition (DESIGN.md 5 item 17, with
+# the table): standing levels off at 1e-8 m/s by 20 sweeps, landing by 30, a tilted start under random torques reaches 1e-8 at 30; a foot
+# sliding under a push is still at 5e-6 there and decays slowly.  Convergence is NOT promised: HB_CONTACT_UNCONVERGED reports the
+# residual of every step against `tol`.
+CONTACT_DEFAULT_SWEEPS = 30
+
+
+def make_contact_config(params: dict, **overrides) -> HbContactConfig:
+    """The ground-contact model (mode 1) with mu = frictionCoefficient of the task file, ground at z = 0, erp 0.2, 30 sweeps, residual
+    tolerance 1e-3 m/s and no fall detection; any field by name overrides."""
+    d = dict(mode=1, sweeps=CONTACT_DEFAULT_SWEEPS, mu=params["config"]["friction_mu"], ground_z=0.0, erp=0.2, tol=1e-3, fall_height=0.0)
+    for k in overrides:
+        if k not in d:
+            raise TypeError(f"make_contact_config: unknown field {k!r} (one of {sorted(d)})")
+    d.update(overrides)
+    out = HbContactConfig()
+    out.mode, out.sweeps = int(d["mode"]), int(d["sweeps"])
+    for k in ("mu", "ground_z", "erp", "tol", "fall_height"):
+        setattr(out, k, float(d[k]))
+    return out
+
+
 class HbJointGains(C.Structure):
     _fields_ = [(k, C.c_double) for k in ("kp_big_stance", "kp_big_swing", "kd_big", "kp_small_stance", "kp_small_swing", "kd_small",
                                           "kd_feet", "kp_position", "kd_position")]

@@ -93,6 +93,10 @@ struct hb_ctx {
   bool sens_noisy = false, sensed = false;
   uint64_t sense_count = 0;
   double *sens_gyro_bias_buf = nullptr, *sens_accel_bias_buf = nullptr;  // [B][3] each, allocated on the first non-null bias
+  // contact model of the plant (hb_plant_set_contact_model): contact_cfg.mode = 1 while the ground model is in force; the arrays are
+  // allocated by the first call that selects it.  Model and wrench survive hb_plant_reset.
+  ContactBatch contact{};
+  hb_contact_config contact_cfg{};
   // reference generation (allocated on the first hb_refgen_reset)
   RefgenBatch rg{};
   hb_refgen_config rg_cfg{};

@@ -1,4 +1,4 @@
-// Host side, part 5: joint command, plant stub and its sensor model, state estimator and contact-force observer.
+// Host side, part 5: joint command, plant (pinned stub and ground-contact model) and its sensor model, state estimator and contact-force observer.
 #pragma once
 
 extern "C" {
@@ -51,6 +51,18 @@ int32_t hb_joint_command(hb_ctx* ctx, const hb_joint_gains* gains, double dt, do
   return HB_OK;
 }
 
+// impulses, outputs and status of the ground-contact model back to zero (the wrench stays)
+static int32_t contact_clear(hb_ctx* ctx, hipStream_t s) {
+  ContactBatch& c = ctx->contact;
+  HB_HIP(hipMemsetAsync(c.imp, 0, field_count(ctx, c, c.imp) * 8, s));
+  HB_HIP(hipMemsetAsync(c.gap, 0, field_count(ctx, c, c.gap) * 8, s));
+  HB_HIP(hipMemsetAsync(c.pvel, 0, field_count(ctx, c, c.pvel) * 8, s));
+  HB_HIP(hipMemsetAsync(c.res, 0, field_count(ctx, c, c.res) * 8, s));
+  HB_HIP(hipMemsetAsync(c.touching, 0, field_count(ctx, c, c.touching) * sizeof(int), s));
+  HB_HIP(hipMemsetAsync(c.status, 0, field_count(ctx, c, c.status) * sizeof(int), s));
+  return HB_OK;
+}
+
 int32_t hb_plant_reset(hb_ctx* ctx, const double* q0, const double* v0, double baumgarte, double eps) {
   HB_ENTER(!q0 || !(baumgarte >= 0.0) || !(eps >= 0.0));
   PlantBatch& p = ctx->plant;
@@ -66,6 +78,7 @@ int32_t hb_plant_reset(hb_ctx* ctx, const double* q0, const double* v0, double b
   else HB_HIP(hipMemset(p.v, 0, field_count(ctx, p, p.v) * 8));
   hipLaunchKernelGGL(k_plant_reset, dim3((ctx->B + 63) / 64), dim3(64), 0, ctx->s_wbc, p, ctx->dmodel);
   HB_HIP(hipGetLastError());
+  if (ctx->contact.wrench) HB_TRY(contact_clear(ctx, ctx->s_wbc));
   HB_HIP(hipStreamSynchronize(ctx->s_wbc));
   ctx->plant_ready = true;
   return HB_OK;
@@ -83,6 +96,12 @@ int32_t hb_plant_step(hb_ctx* ctx, const double* tau, const int32_t* contact, do
   HB_TRY(push(ctx, contact, p, p.contact, whole(ctx), &s));
   const double* dtau = tau ? p.tau : ctx->jc_out + 5 * B * HB_NJ;
   // the resident observation feeds the next hb_mpc_solve(NULL) / hb_refgen_update(NULL) on the MPC stream
+  if (ctx->contact_cfg.mode == 1)
+    return resident_write(ctx, s, to_resident, [&] {
+      hipLaunchKernelGGL(k_plant_contact, dim3(ctx->B), dim3(64), 0, s, p, ctx->contact, ctx->contact_cfg, ctx->dmodel, dtau, contact ? p.contact : nullptr,
+                         ctx->w.mode, dt, substeps, to_resident ? ctx->w.rbd : nullptr, to_resident ? ctx->b.x0 : nullptr,
+                         to_resident ? ctx->w.t_now : nullptr);
+    });
   return resident_write(ctx, s, to_resident, [&] {
     hipLaunchKernelGGL(k_plant, dim3(ctx->B), dim3(64), 0, s, p, ctx->dmodel, dtau, contact ? p.contact : nullptr, ctx->w.mode, dt, substeps,
                        to_resident ? ctx->w.rbd : nullptr, to_resident ? ctx->b.x0 : nullptr, to_resident ? ctx->w.t_now : nullptr);
@@ -100,6 +119,62 @@ int32_t hb_plant_get_state(hb_ctx* ctx, double* q, double* v, double* rbd, doubl
   HB_TRY(pull(ctx, rbd, p, p.rbd, whole(ctx)));
   HB_TRY(pull(ctx, lambda, p, p.lambda, whole(ctx)));
   HB_TRY(pull(ctx, vdot, p, p.vdot, whole(ctx)));
+  return HB_OK;
+}
+
+int32_t hb_plant_set_contact_model(hb_ctx* ctx, const hb_contact_config* cfg) {
+  HB_ENTER_ARGS(false);
+  HB_FAIL_IF(!ctx->plant_ready, HB_ERR_STATE, "hb_plant_set_contact_model: call hb_plant_reset first");
+  HB_FAIL_IF(cfg && !contact_config_valid(*cfg), HB_ERR_ARG, "hb_plant_set_contact_model: mode 0 / 1, sweeps 1 .. 10000, mu >= 0, erp in [0, 1], tol >= 0, fall_height >= 0, every field finite and `reserved` 0");
+  HB_ENTER_DEVICE();
+  HB_HIP(hipStreamSynchronize(ctx->s_wbc));  // (a step in flight still runs under the model it was launched with)
+  const bool ground = cfg && cfg->mode == 1;
+  if (ground && !ctx->contact.wrench) {  // (wrench: the last array of the description, so an allocation that failed half way is repeated)
+    HB_HIP(alloc_fields(ctx, ctx->contact));
+    ctx->contact.B = ctx->B;
+  } else if (ground && ctx->contact_cfg.mode != 1) {
+    HB_TRY(contact_clear(ctx, ctx->s_wbc));  // back from the pinned stub: no warm start from before it
+  }
+  if (!ground && ctx->contact_cfg.mode == 1) {
+    // the ground model moved the feet without touching the stub's anchors: no point counts as pinned, so the next step of the stub
+    // anchors every commanded contact where the foot is now
+    PlantBatch& p = ctx->plant;
+    HB_HIP(hipMemsetAsync(p.pinned, 0, field_count(ctx, p, p.pinned) * sizeof(int), ctx->s_wbc));
+  }
+  ctx->contact_cfg = ground ? *cfg : hb_contact_config{};
+  return HB_OK;
+}
+
+// the two entry points that only exist in the ground model
+static int32_t contact_ready(hb_ctx* ctx, const char* who) {
+  const char* why = !ctx->plant_ready ? "call hb_plant_reset first" : ctx->contact_cfg.mode != 1 ? "the ground-contact model is not in force (hb_plant_set_contact_model, mode 1)" : nullptr;
+  if (!why) return HB_OK;
+  ctx->err = std::string(who) + ": " + why;
+  return HB_ERR_STATE;
+}
+
+int32_t hb_plant_set_external_wrench(hb_ctx* ctx, const double* wrench) {
+  HB_ENTER_ARGS(false);
+  HB_TRY(contact_ready(ctx, "hb_plant_set_external_wrench"));
+  HB_ENTER_DEVICE();
+  ContactBatch& c = ctx->contact;
+  HB_HIP(hipStreamSynchronize(ctx->s_wbc));  // (an earlier step may still be reading the wrench)
+  HB_TRY(push(ctx, wrench, c, c.wrench, whole(ctx)));
+  c.use_wrench = wrench ? 1 : 0;
+  return HB_OK;
+}
+
+int32_t hb_plant_get_contact(hb_ctx* ctx, double* gap, double* point_vel, double* residual, int32_t* touching, int32_t* status) {
+  HB_ENTER_ARGS(false);
+  HB_TRY(contact_ready(ctx, "hb_plant_get_contact"));
+  HB_ENTER_DEVICE();
+  HB_HIP(hipStreamSynchronize(ctx->s_wbc));
+  ContactBatch& c = ctx->contact;
+  HB_TRY(pull(ctx, gap, c, c.gap, whole(ctx)));
+  HB_TRY(pull(ctx, point_vel, c, c.pvel, whole(ctx)));
+  HB_TRY(pull(ctx, residual, c, c.res, whole(ctx)));
+  HB_TRY(pull(ctx, touching, c, c.touching, whole(ctx)));
+  HB_TRY(pull(ctx, status, c, c.status, whole(ctx)));
   return HB_OK;
 }
 

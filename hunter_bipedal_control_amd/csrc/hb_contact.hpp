@@ -1,0 +1,214 @@
+// Plant with unilateral frictional ground contact (contact model 1 of include/hunter_hip.h, "ground"), one 64-lane workgroup per robot.
+// A velocity-level time stepper: per substep the rigid-body terms, the Cholesky factor of M, M^-1 [rhs | J'] and J M^-1 J' are the front
+// half of the pinned stub's substep with every contact point switched on (hb_plant.hpp plant_substep<TERMS_ONLY>); the contact impulses then come
+// from projected Gauss-Seidel sweeps over the four points (normal first, then the tangential pair projected onto the friction disc),
+// warm-started from the previous substep.  Contact is decided by geometry (the gap to the plane z = ground_z), never by the schedule.
+//
+// The sweep is lane-cooperative on the device: lane r < 12 keeps row r of W, g_r and p_r in registers; a point's three (g, p) pairs
+// reach every lane by cross-lane reads, every lane computes the point's update redundantly and applies its own three
+// g_r += W[r][j] dp_j.  No LDS traffic and no barrier inside a sweep.  The host build (one emulated lane) runs the same update
+// routines (pgs_normal / pgs_tangent) over arrays.
+#pragma once
+#include "../../include/hunter_hip.h"
+#include "hb_plant.hpp"
+
+namespace hb {
+
+struct ContactLds {
+  static constexpr int q = PlantLds::total;   // 16
+  static constexpr int v = q + 16;            // 16
+  static constexpr int wgen = v + 16;         // 16 : generalised force of the external base wrench
+  static constexpr int imp = wgen + 16;       // 12 : impulses (warm start, then the substep's result)
+  static constexpr int res = imp + 12;        // 1  : residual of the last sweep
+  static constexpr int total = res + 2;
+};
+constexpr int CONTACT_LDS_TOTAL = ContactLds::total;
+constexpr int HB_CONTACT_SWEEPS_MAX = 10000;   // (a runtime loop count that comes from the caller is range-checked)
+
+inline bool contact_config_valid(const hb_contact_config& K) {
+  if (K.reserved[0] != 0 || K.reserved[1] != 0 || K.mode < 0 || K.mode > 1) return false;
+  if (K.mode == 0) return true;
+  const double big = 1.7976931348623157e308;
+  return K.sweeps >= 1 && K.sweeps <= HB_CONTACT_SWEEPS_MAX && K.mu >= 0.0 && K.mu <= big && K.ground_z >= -big && K.ground_z <= big && K.erp >= 0.0 &&
+         K.erp <= 1.0 && K.tol >= 0.0 && K.tol <= big && K.fall_height >= 0.0 && K.fall_height <= big;
+}
+
+// Normal update of a point: p_n <- max(0, p_n - g_n / W_nn).
+HB_HD double pgs_normal(double gn, double pn, double Wnn) { return fmax(0.0, pn - gn / Wnn); }
+// Tangential update of a point: both entries from the g of before either changes, then projected onto the disc of radius mu p_n.
+HB_HD void pgs_tangent(double ga, double gb, double pa, double pb, double Waa, double Wbb, double mu, double pn, double& ta, double& tb) {
+  ta = pa - ga / Waa;
+  tb = pb - gb / Wbb;
+  const double lim = mu * pn, nrm = sqrt(ta * ta + tb * tb);
+  if (nrm > lim) {
+    const double sc = pn > 0.0 ? lim / nrm : 0.0;
+    ta *= sc;
+    tb *= sc;
+  }
+}
+
+// What a step leaves behind per instance (global memory; hb_plant_get_contact).
+struct ContactOut {
+  double *gap, *pvel, *res;
+  int *touching, *status;
+};
+
+// One substep of length h.  q[16], v[16] in / out (LDS); imp[12] (LDS behind `lds`) in / out; wrench[6] = world force and world moment at
+// the base origin, or null; all_on[4] = {1, 1, 1, 1} in memory every lane can read.
+template <class Ctx>
+HB_HD void contact_substep(const Ctx& cx, const DevModel& Mdl, double* q, double* v, const double* tau, const double* wrench, const int* all_on,
+                           const hb_contact_config& K, double eps, double h, double* lds, double* vdot_out) {
+  double* Jc = lds + PlantLds::Jc;
+  double* X = lds + PlantLds::X;
+  double* A = lds + PlantLds::A;
+  double* feet = lds + PlantLds::feet;
+  double* wgen = lds + ContactLds::wgen;
+  double* imp = lds + ContactLds::imp;
+  if (cx.lane == 0 && wrench) {   // w = [F, E(zyx)' m, 0]: the power of the moment is m . E rates
+    double sz, cz, sy, cy;
+    sincos_t(q[3], sz, cz);
+    sincos_t(q[4], sy, cy);
+    for (int a = 0; a < 3; ++a) wgen[a] = wrench[a];
+    wgen[3] = wrench[5];
+    wgen[4] = -sz * wrench[3] + cz * wrench[4];
+    wgen[5] = cy * cz * wrench[3] + cy * sz * wrench[4] - sy * wrench[5];
+    for (int a = 6; a < 16; ++a) wgen[a] = 0.0;
+  }
+  // the front half of the pinned stub's substep with every point on (its first barrier publishes wgen)
+  plant_substep<true>(cx, Mdl, q, v, tau, all_on, nullptr, 0.0, 0.0, h, lds, nullptr, nullptr, wrench ? wgen : nullptr);
+  double tr = 0.0;
+  for (int i = 0; i < 12; ++i) tr += A[i * 13];
+  const double reg = eps * tr, mu = K.mu;
+#if defined(__HIP_DEVICE_COMPILE__)
+  {
+    const int r = cx.lane < 12 ? cx.lane : 0;   // (lanes 12.. shadow lane 0: nothing reads them)
+    double W[12], D[12];
+    for (int j = 0; j < 12; ++j) {
+      W[j] = A[r * 12 + j] + (j == r ? reg : 0.0);
+      D[j] = A[j * 13] + reg;
+    }
+    double g = 0.0;
+    for (int k = 0; k < 16; ++k) g += Jc[r * 16 + k] * (v[k] + h * X[k * 13]);
+    if (r % 3 == 2) {
+      const double phi = feet[r] - K.ground_z;
+      g += (fmax(phi, 0.0) + K.erp * fmin(phi, 0.0)) / h;
+    }
+    for (int j = 0; j < 12; ++j) g += W[j] * imp[j];
+    double p = imp[r], res = 0.0;
+    for (int s = 0; s < K.sweeps; ++s) {
+      res = 0.0;
+#pragma unroll
+      for (int pt = 0; pt < 4; ++pt) {
+        const int a = 3 * pt, b = a + 1, n = a + 2;
+        const double pn0 = wave_bcast_f64(p, n), pn = pgs_normal(wave_bcast_f64(g, n), pn0, D[n]), dn = pn - pn0;
+        g += W[n] * dn;
+        p = cx.lane == n ? pn : p;
+        res = fmax(res, fabs(D[n] * dn));
+        const double pa0 = wave_bcast_f64(p, a), pb0 = wave_bcast_f64(p, b);
+        double ta, tb;
+        pgs_tangent(wave_bcast_f64(g, a), wave_bcast_f64(g, b), pa0, pb0, D[a], D[b], mu, pn, ta, tb);
+        const double da = ta - pa0, db = tb - pb0;
+        g += W[a] * da;
+        g += W[b] * db;
+        p = cx.lane == a ? ta : (cx.lane == b ? tb : p);
+        res = fmax(res, fmax(fabs(D[a] * da), fabs(D[b] * db)));
+      }
+    }
+    cx.sync();   // (every lane has read the warm start)
+    if (cx.lane < 12) imp[cx.lane] = p;
+    if (cx.lane == 0) lds[ContactLds::res] = res;
+  }
+#else
+  {
+    double W[144], g[12], p[12], res = 0.0;
+    for (int r = 0; r < 12; ++r) {
+      for (int j = 0; j < 12; ++j) W[r * 12 + j] = A[r * 12 + j] + (j == r ? reg : 0.0);
+      double s = 0.0;
+      for (int k = 0; k < 16; ++k) s += Jc[r * 16 + k] * (v[k] + h * X[k * 13]);
+      if (r % 3 == 2) {
+        const double phi = feet[r] - K.ground_z;
+        s += (fmax(phi, 0.0) + K.erp * fmin(phi, 0.0)) / h;
+      }
+      for (int j = 0; j < 12; ++j) s += W[r * 12 + j] * imp[j];
+      g[r] = s;
+      p[r] = imp[r];
+    }
+    for (int s = 0; s < K.sweeps; ++s) {
+      res = 0.0;
+      for (int pt = 0; pt < 4; ++pt) {
+        const int a = 3 * pt, b = a + 1, n = a + 2;
+        const double pn = pgs_normal(g[n], p[n], W[n * 13]), dn = pn - p[n];
+        for (int r = 0; r < 12; ++r) g[r] += W[r * 12 + n] * dn;
+        p[n] = pn;
+        res = fmax(res, fabs(W[n * 13] * dn));
+        double ta, tb;
+        pgs_tangent(g[a], g[b], p[a], p[b], W[a * 13], W[b * 13], mu, pn, ta, tb);
+        const double da = ta - p[a], db = tb - p[b];
+        for (int r = 0; r < 12; ++r) { g[r] += W[r * 12 + a] * da; g[r] += W[r * 12 + b] * db; }
+        p[a] = ta;
+        p[b] = tb;
+        res = fmax(res, fmax(fabs(W[a * 13] * da), fabs(W[b * 13] * db)));
+      }
+    }
+    for (int r = 0; r < 12; ++r) imp[r] = p[r];
+    lds[ContactLds::res] = res;
+  }
+#endif
+  cx.sync();
+  // ---- v+ = v_f + M^-1 J' p,  q+ = q + h v+
+  for (int i = cx.lane; i < 16; i += cx.nlanes) {
+    double vn = v[i] + h * X[i * 13];
+    for (int j = 0; j < 12; ++j) vn += X[i * 13 + 1 + j] * imp[j];
+    if (vdot_out) vdot_out[i] = (vn - v[i]) / h;
+    v[i] = vn;
+    q[i] = q[i] + h * vn;
+  }
+  cx.sync();
+}
+
+// One plant tick of one instance in contact model 1: `substeps` substeps of dt / substeps, then the outputs of the step.  State (q, v,
+// impulses, status) lives in global memory and is staged in LDS behind `lds` (CONTACT_LDS_TOTAL doubles).
+template <class Ctx>
+HB_HD void contact_step(const Ctx& cx, const DevModel& Mdl, double* q_g, double* v_g, double* imp_g, const double* tau, const double* wrench,
+                        const int* all_on, const hb_contact_config& K, double eps, double dt, int substeps, double* lds, double* lambda_out,
+                        double* vdot_out, const ContactOut& out) {
+  double* q = lds + ContactLds::q;
+  double* v = lds + ContactLds::v;
+  double* imp = lds + ContactLds::imp;
+  for (int i = cx.lane; i < 16; i += cx.nlanes) { q[i] = q_g[i]; v[i] = v_g[i]; }
+  for (int i = cx.lane; i < 12; i += cx.nlanes) imp[i] = imp_g[i];
+  cx.sync();
+  const double h = dt / substeps;
+  for (int s = 0; s < substeps; ++s) contact_substep(cx, Mdl, q, v, tau, wrench, all_on, K, eps, h, lds, vdot_out);
+  // ---- outputs: world forces, touching flags and point velocities J v+ of the last substep; gaps at q+
+  const double* Jc = lds + PlantLds::Jc;
+  double* feet = lds + PlantLds::feet;
+  if (cx.lane == 0) plant_feet(Mdl, q, feet);
+  for (int i = cx.lane; i < 16; i += cx.nlanes) { q_g[i] = q[i]; v_g[i] = v[i]; }
+  for (int i = cx.lane; i < 12; i += cx.nlanes) {
+    imp_g[i] = imp[i];
+    lambda_out[i] = imp[i] / h;
+    double s = 0.0;
+    for (int k = 0; k < 16; ++k) s += Jc[i * 16 + k] * v[k];
+    out.pvel[i] = s;
+  }
+  cx.sync();
+  for (int c = cx.lane; c < HB_NC; c += cx.nlanes) {
+    out.gap[c] = feet[3 * c + 2] - K.ground_z;
+    out.touching[c] = imp[3 * c + 2] > 0.0 ? 1 : 0;
+  }
+  if (cx.lane == 0) {
+    const double res = lds[ContactLds::res];
+    bool finite = true;
+    for (int i = 0; i < 16; ++i) finite = finite && fabs(q[i]) <= 1.7976931348623157e308 && fabs(v[i]) <= 1.7976931348623157e308;
+    int st = out.status[0] & HB_CONTACT_FALLEN;   // (latched until hb_plant_reset)
+    if (!finite) st |= HB_CONTACT_NONFINITE;
+    if (K.fall_height > 0.0 && q[2] - K.ground_z < K.fall_height) st |= HB_CONTACT_FALLEN;
+    if (!(res <= K.tol)) st |= HB_CONTACT_UNCONVERGED;
+    out.res[0] = res;
+    out.status[0] = st;
+  }
+  cx.sync();
+}
+
+}  // namespace hb

@@ -20,6 +20,7 @@
 #include "hb_refgen.hpp"
 #include "hb_gait.hpp"
 #include "hb_plant.hpp"
+#include "hb_contact.hpp"
 #include "hb_sensors.hpp"
 #include "hb_layout.hpp"
 #include "hb_wavectx.hpp"
@@ -926,7 +927,30 @@ __global__ void k_centroidal_state(int n, const DevModel* __restrict__ M, const 
   if (i < n) centroidal_state_from_rbd(*M, rbd + size_t(i) * HB_NRBD, x + size_t(i) * HB_NX);
 }
 
-// ---- plant stub: one wave per instance -----------------------------------------------------------------------------
+// ---- plant: one wave per instance --------------------------------------------------------------------------------------
+// What a plant kernel's lane 0 does after its step: the new state repacked as rbd, and with res_rbd the resident rbd state, the
+// resident MPC observation and the resident time advanced by dt.
+__device__ __forceinline__ void plant_publish(const PlantBatch& p, const DevModel* __restrict__ M, int i, double dt, double* res_rbd,
+                                              double* res_x0, double* res_t) {
+  const double* q = p.q + 16 * i;
+  const double* v = p.v + 16 * i;
+  double* rbd = p.rbd + HB_NRBD * i;
+  double sz, cz, sy, cy;
+  sincos_t(q[3], sz, cz);
+  sincos_t(q[4], sy, cy);
+  for (int a = 0; a < 3; ++a) { rbd[a] = q[3 + a]; rbd[3 + a] = q[a]; rbd[HB_NV + 3 + a] = v[a]; }
+  for (int j = 0; j < HB_NJ; ++j) { rbd[6 + j] = q[6 + j]; rbd[6 + HB_NV + j] = v[6 + j]; }
+  // omega_world = E(zyx) rates
+  rbd[HB_NV + 0] = -sz * v[4] + cy * cz * v[5];
+  rbd[HB_NV + 1] = cz * v[4] + cy * sz * v[5];
+  rbd[HB_NV + 2] = v[3] - sy * v[5];
+  if (res_rbd) {
+    for (int c = 0; c < HB_NRBD; ++c) res_rbd[HB_NRBD * i + c] = rbd[c];
+    centroidal_state_from_rbd(*M, rbd, res_x0 + HB_NX * i);
+    res_t[i] += dt;
+  }
+}
+// the pinned stub
 __global__ __launch_bounds__(64) void k_plant(PlantBatch p, const DevModel* __restrict__ M, const double* tau, const int* contact,
                                                const int* mode, double dt, int substeps, double* res_rbd, double* res_x0,
                                                double* res_t) {
@@ -943,25 +967,29 @@ __global__ __launch_bounds__(64) void k_plant(PlantBatch p, const DevModel* __re
   if (cx.lane < HB_NC) p.contact_last[4 * i + cx.lane] = cflag[cx.lane];
   plant_step(cx, *M, p.q + 16 * i, p.v + 16 * i, p.anchor + 12 * i, p.pinned + 4 * i, tau + 10 * i, cflag, p.baum, p.eps, dt, substeps, lds,
              p.lambda + 12 * i, p.vdot + 16 * i);
-  if (cx.lane == 0) {
-    const double* q = p.q + 16 * i;
-    const double* v = p.v + 16 * i;
-    double* rbd = p.rbd + HB_NRBD * i;
-    double sz, cz, sy, cy;
-    sincos_t(q[3], sz, cz);
-    sincos_t(q[4], sy, cy);
-    for (int a = 0; a < 3; ++a) { rbd[a] = q[3 + a]; rbd[3 + a] = q[a]; rbd[HB_NV + 3 + a] = v[a]; }
-    for (int j = 0; j < HB_NJ; ++j) { rbd[6 + j] = q[6 + j]; rbd[6 + HB_NV + j] = v[6 + j]; }
-    // omega_world = E(zyx) rates
-    rbd[HB_NV + 0] = -sz * v[4] + cy * cz * v[5];
-    rbd[HB_NV + 1] = cz * v[4] + cy * sz * v[5];
-    rbd[HB_NV + 2] = v[3] - sy * v[5];
-    if (res_rbd) {
-      for (int c = 0; c < HB_NRBD; ++c) res_rbd[HB_NRBD * i + c] = rbd[c];
-      centroidal_state_from_rbd(*M, rbd, res_x0 + HB_NX * i);
-      res_t[i] += dt;
-    }
+  if (cx.lane == 0) plant_publish(p, M, i, dt, res_rbd, res_x0, res_t);
+}
+// Contact model 1 (hb_contact.hpp): the commanded flags are recorded for hb_plant_sense and play no part in the dynamics.
+__global__ __launch_bounds__(64) void k_plant_contact(PlantBatch p, ContactBatch cb, hb_contact_config K, const DevModel* __restrict__ M,
+                                                      const double* tau, const int* contact, const int* mode, double dt, int substeps,
+                                                      double* res_rbd, double* res_x0, double* res_t) {
+  const int i = blockIdx.x;
+  __shared__ double lds[CONTACT_LDS_TOTAL];
+  __shared__ int all_on[HB_NC];
+  const DeviceCtx cx;
+  if (cx.lane < HB_NC) {
+    int flag;
+    if (contact) flag = contact[4 * i + cx.lane];
+    else { bool cf[HB_NC]; mode_flags(mode[i], cf); flag = cf[cx.lane] ? 1 : 0; }
+    p.contact_last[4 * i + cx.lane] = flag;
+    all_on[cx.lane] = 1;
   }
+  if (cx.lane < HB_NJ) p.tau_last[10 * i + cx.lane] = tau[10 * i + cx.lane];
+  __syncthreads();
+  const ContactOut out{cb.gap + 4 * i, cb.pvel + 12 * i, cb.res + i, cb.touching + 4 * i, cb.status + i};
+  contact_step(cx, *M, p.q + 16 * i, p.v + 16 * i, cb.imp + 12 * i, tau + 10 * i, cb.use_wrench ? cb.wrench + 6 * i : nullptr, all_on, K, p.eps, dt,
+               substeps, lds, p.lambda + 12 * i, p.vdot + 16 * i, out);
+  if (cx.lane == 0) plant_publish(p, M, i, dt, res_rbd, res_x0, res_t);
 }
 __global__ void k_plant_reset(PlantBatch p, const DevModel* __restrict__ M) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;

@@ -133,6 +133,20 @@ constexpr void fields(PlantBatch& p, size_t, F&& f) {
   HB_FIELD(p.s_gyro, 3); HB_FIELD(p.s_accel, 3); HB_FIELD(p.s_jp, 10); HB_FIELD(p.s_jv, 10); HB_FIELD(p.s_jt, 10); HB_FIELD(p.s_contact, 4);
 }
 
+// ground-contact model of the plant (hb_contact.hpp), allocated by the first hb_plant_set_contact_model that selects it: impulses of
+// the last substep (the warm start), the outputs of hb_plant_get_contact, the external base wrench
+struct ContactBatch {
+  int B;
+  int use_wrench;   // hb_plant_set_external_wrench has given one
+  double *imp, *gap, *pvel, *res;
+  int *touching, *status;
+  double* wrench;
+};
+template <class F>
+constexpr void fields(ContactBatch& c, size_t, F&& f) {
+  HB_FIELD(c.imp, 12); HB_FIELD(c.gap, 4); HB_FIELD(c.pvel, 12); HB_FIELD(c.res, 1); HB_FIELD(c.touching, 4); HB_FIELD(c.status, 1); HB_FIELD(c.wrench, 6);
+}
+
 // ---- reference generation ----------------------------------------------------------------------------------------------
 struct RefgenBatch {
   int B;
@@ -220,6 +234,7 @@ static_assert(sizeof(WbcBatch) == kPtr /*B*/ + n_fields<WbcBatch>() * kPtr + kPt
 static_assert(sizeof(WbcCertBuf) == n_fields<WbcCertBuf>() * kPtr && sizeof(HwbcCertBuf) == n_fields<HwbcCertBuf>() * kPtr, "certificate buffers");
 static_assert(sizeof(PlantBatch) == kPtr /*B*/ + 2 * sizeof(double) + (n_fields<PlantBatch>() + 2 /*gyro_bias, accel_bias*/) * kPtr,
               "describe every array of PlantBatch in fields()");
+static_assert(sizeof(ContactBatch) == 2 * sizeof(int) + n_fields<ContactBatch>() * kPtr, "describe every array of ContactBatch in fields()");
 static_assert(sizeof(RefgenBatch) == kPtr /*B*/ + n_fields<RefgenBatch>() * kPtr + kPtr /*init_stance*/, "describe every array of RefgenBatch in fields()");
 static_assert(sizeof(GaitBatch) == 2 * sizeof(int) + n_fields<GaitBatch>() * kPtr, "describe every array of GaitBatch in fields()");
 static_assert(sizeof(EstBatch) == kPtr /*B*/ + (n_fields<EstBatch>() + 2 /*res_rbd, res_x0*/) * kPtr, "describe every array of EstBatch in fields()");

@@ -4,7 +4,7 @@
 // with lambda from the damped normal equations (Jc M^-1 Jc' + eps tr(.) I) lambda = rhs (a foot's two contact points
 // give a rank-5 Jacobian), semi-implicit Euler.  The reference closes its loop through Gazebo / MuJoCo
 // (legged_gazebo/src/LeggedHWSim.cpp:166-192, mujoco/src/main.cc:247); this stub replaces them for regression rollouts
-// and does NOT enforce unilateral contact or friction limits.
+// and does NOT enforce unilateral contact or friction limits (contact model 1, hb_contact.hpp, does).
 // Coordinates: q = [pos, zyx, joints], v = [v_lin (world), ZYX rates, joint rates] (pinocchio's, WbcBase.cpp:72-79).
 #pragma once
 #include "hb_wbc.hpp"
@@ -24,9 +24,12 @@ struct PlantLds {
 };
 
 // One substep of length h.  q[16], v[16], anchor[12] in/out (global or LDS); rows[12] = 1 for pinned contact rows.
-template <class Ctx>
+// TERMS_ONLY: the front half alone, for the ground-contact model (hb_contact.hpp) — the rigid-body terms at (q, v), the Cholesky factor
+// of M, X = M^-1 [rhs | Jc'] with rhs = S' tau - nle (+ wext[16], a generalised force, when one is given) and Jc M^-1 Jc' are left in LDS
+// (PlantLds: M, Jc, X, A, nle, dJv, feet); nothing behind `contact` in the argument list is used except lds and wext.
+template <bool TERMS_ONLY = false, class Ctx>
 HB_HD void plant_substep(const Ctx& cx, const DevModel& Mdl, double* q, double* v, const double* tau, const int* contact, const double* anchor,
-                         double baum, double eps, double h, double* lds, double* lambda_out, double* vdot_out) {
+                         double baum, double eps, double h, double* lds, double* lambda_out, double* vdot_out, const double* wext = nullptr) {
   double* Mm = lds + PlantLds::M;
   double* Jc = lds + PlantLds::Jc;
   double* X = lds + PlantLds::X;
@@ -71,6 +74,7 @@ HB_HD void plant_substep(const Ctx& cx, const DevModel& Mdl, double* q, double* 
     double y[16];
     for (int i = 0; i < 16; ++i) {
       double s = (c == 0) ? ((i >= 6 ? tau[i - 6] : 0.0) - nle[i]) : Jc[(c - 1) * 16 + i];
+      if constexpr (TERMS_ONLY) { if (c == 0 && wext) s += wext[i]; }
       for (int k = 0; k < i; ++k) s -= Mm[i * 16 + k] * y[k];
       y[i] = s / Mm[i * 17];
     }
@@ -90,6 +94,7 @@ HB_HD void plant_substep(const Ctx& cx, const DevModel& Mdl, double* q, double* 
     A[idx] = s;
   }
   cx.sync();
+  if constexpr (TERMS_ONLY) return;
   double tr = 0.0;
   for (int i = 0; i < 12; ++i) tr += A[i * 13];
   tr = fmax(tr, 1e-12);

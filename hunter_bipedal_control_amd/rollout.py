@@ -29,6 +29,14 @@ def standing_configuration(params: dict, batch: int, solver) -> np.ndarray:
     return q
 
 
+def lowest_contact_point(solver, q) -> float:
+    """Height of the lowest contact point over the batch q[B][16] (device kinematics): the ground of a rollout that starts there."""
+    x = np.zeros((q.shape[0], 22))
+    x[:, 6:9], x[:, 9:12], x[:, 12:] = q[:, 0:3], q[:, 3:6], q[:, 6:]
+    feet = np.asarray(solver.eval_foot_kinematics(x, np.zeros((q.shape[0], 22)))[0]).reshape(q.shape[0], 4, 3)
+    return float(feet[:, :, 2].min())
+
+
 class DeviceLoop:
     """One HunterSolver driven in closed loop.  `gait` per instance (names of gait.info), `cmd_vel` [B][4]."""
 
@@ -132,12 +140,15 @@ class ResidentLoop:
 
     def __init__(self, solver, params: dict, gaits, cmd_vel, n_intervals: int = 100, mpc_every: int = 8, dt: float = 0.002,
                  t_gait_start: float = 0.3, joint_ik: bool = True, substeps: int = 4, static_schedule_until: float = 0.0,
-                 device_gait: bool = False, use_estimator: bool = False, sensor_config=None, sensor_bias=None):
+                 device_gait: bool = False, use_estimator: bool = False, sensor_config=None, sensor_bias=None, contact_config=None):
         """static_schedule_until > 0: the mode schedules are uploaded once for [-1, static_schedule_until] (at most
         HB_MAX_EVENTS events) instead of a sliding window per MPC call — no per-call host work for large batches.
         device_gait: the device gait manager produces the windows; step() builds no per-instance list and uploads no schedule, and
         the gait of every instance follows its command as in the reference (set_cmd replaces the commands between steps).  `gaits`
-        other than the default "stance" go in once, at t_gait_start, through hb_gait_insert_template."""
+        other than the default "stance" go in once, at t_gait_start, through hb_gait_insert_template.
+        contact_config: the plant's contact model — None: the pinned stub; a dict of abi.make_contact_config fields ({} = the defaults):
+        ground with unilateral frictional contact, the plane under the lowest contact point of the start unless ground_z is among them;
+        an abi.HbContactConfig is taken as it is."""
         self.s, self.params, self.B = solver, params, solver.B
         self.horizon = n_intervals * params["config"]["dt"]
         self.dt, self.mpc_every, self.substeps = dt, mpc_every, substeps
@@ -166,6 +177,12 @@ class ResidentLoop:
             self.schedules = [gait.gait_schedule(params, g, t_gait_start, 1.0e3 if g == "stance" else 60.0) for g in gaits]
         q0 = standing_configuration(params, self.B, solver)
         solver.plant_reset(q0)
+        if contact_config is not None:
+            if isinstance(contact_config, dict):   # fields of abi.make_contact_config; the plane goes under the start unless given
+                fields = dict(contact_config)
+                fields.setdefault("ground_z", lowest_contact_point(solver, q0))
+                contact_config = abi.make_contact_config(params, **fields)
+            solver.plant_set_contact_model(contact_config)
         # resident observation of the initial state
         rbd = np.zeros((self.B, 32))
         rbd[:, 0:3], rbd[:, 3:6], rbd[:, 6:16] = q0[:, 3:6], q0[:, 0:3], q0[:, 6:]

@@ -32,6 +32,7 @@ ABI_SYMBOLS = [
     "hb_mpc_get_certificate", "hb_mpc_get_lq", "hb_mpc_get_recovery",
     "hb_refgen_get_schedule", "hb_gait_reset", "hb_gait_disable", "hb_gait_insert_template", "hb_gait_get_state",
     "hb_plant_set_sensor_model", "hb_plant_sense", "hb_estimator_update_resident", "hb_estimator_contact_force_resident",
+    "hb_plant_set_contact_model", "hb_plant_set_external_wrench", "hb_plant_get_contact",
 ]
 # include/hunter_lcm.h
 LCM_SYMBOLS = ["hb_lcm_fingerprint", "hb_lcm_encoded_size", "hb_lcm_field_count", "hb_lcm_encode", "hb_lcm_decode", "hb_lcm_frame", "hb_lcm_unframe",
@@ -248,6 +249,25 @@ class HunterSolver:
                    vdot=np.zeros((self.B, 16)))
         self._check(self.lib.hb_plant_get_state(self.ctx, _p(out["q"]), _p(out["v"]), _p(out["rbd"]), _p(out["lam"]), _p(out["vdot"])),
                     "hb_plant_get_state")
+        return out
+
+    # ---- contact model of the plant (hb_plant_set_contact_model) ---------------------------------------------------------------
+    def plant_set_contact_model(self, contact_cfg: "abi.HbContactConfig" = None):
+        """contact_cfg None: the pinned stub (model 0); abi.make_contact_config(params, ...): ground with unilateral frictional contact."""
+        self._check(self.lib.hb_plant_set_contact_model(self.ctx, None if contact_cfg is None else C.byref(contact_cfg)),
+                    "hb_plant_set_contact_model")
+
+    def plant_set_external_wrench(self, wrench=None):
+        """wrench [B][6] = world force, world moment at the base origin, applied by every later step of the ground model; None clears."""
+        w = None if wrench is None else _f64(wrench, (self.B, 6))
+        self._check(self.lib.hb_plant_set_external_wrench(self.ctx, _p(w)), "hb_plant_set_external_wrench")
+
+    def plant_contact(self):
+        """Contact outputs of the last step of the ground model -> dict(gap[B][4], point_vel[B][4][3], residual[B], touching[B][4] int32,
+        status[B] int32: bits abi.HB_CONTACT_*)."""
+        out = dict(gap=np.zeros((self.B, 4)), point_vel=np.zeros((self.B, 4, 3)), residual=np.zeros(self.B),
+                   touching=np.zeros((self.B, 4), dtype=np.int32), status=np.zeros(self.B, dtype=np.int32))
+        self._check(self.lib.hb_plant_get_contact(self.ctx, *[_p(a) for a in out.values()]), "hb_plant_get_contact")
         return out
 
     # ---- sensors from the plant (hb_plant_sense) and the estimator on them ------------------------------------------------

@@ -237,7 +237,7 @@ int32_t hb_joint_command(hb_ctx* ctx, const hb_joint_gains* gains, double dt, do
  * The reference closes its loop through Gazebo / MuJoCo (legged_gazebo/src/LeggedHWSim.cpp:166-192,
  * mujoco/src/main.cc:247).  This stub integrates M(q) vdot + nle = S' tau + Jc' lambda with the contact points of the
  * commanded mode pinned by acceleration-level constraints (Baumgarte gain `baumgarte`, damped normal equations with
- * relative damping `eps`), semi-implicit Euler; it does NOT enforce unilateral contact or friction limits.
+ * relative damping `eps`), semi-implicit Euler; it does NOT enforce unilateral contact or friction limits (contact model 1 below does).
  * Coordinates: q = [pos, zyx, joints], v = [v_lin (world), ZYX rates, joint rates]. */
 int32_t hb_plant_reset(hb_ctx* ctx, const double* q0 /*[batch][16]*/, const double* v0 /*[batch][16] or NULL*/,
                        double baumgarte, double eps);
@@ -251,6 +251,57 @@ int32_t hb_plant_step(hb_ctx* ctx, const double* tau, const int32_t* contact, do
 /* State to the host (any may be NULL): q[batch][16], v[batch][16], rbd[batch][32], lambda[batch][12] (last contact
  * forces), vdot[batch][16] (last acceleration); lambda and vdot are zero between hb_plant_reset and the first step. */
 int32_t hb_plant_get_state(hb_ctx* ctx, double* q, double* v, double* rbd, double* lambda, double* vdot);
+
+/* ---- contact model of the plant: 0 = the pinned stub above (default), 1 = "ground" ------------------------------------------------
+ * Model 1 has a flat ground z = ground_z, unilateral normal forces and Coulomb friction at the model's four contact points; contact is
+ * decided by geometry, not by the schedule.  Per substep of length h = dt / substeps, with q, v in the plant's coordinates, all four
+ * contact points always in the problem, world axes with z up:
+ *  1. Rigid-body terms as in the pinned stub: M, nle, the UNMASKED 12 x 16 contact Jacobian J (rows 3c .. 3c+2 = x, y, z of point c) and
+ *     the contact point positions; the gap is phi_c = z_c - ground_z.
+ *  2. Free velocity v_f = v + h M^-1 (S' tau - nle + w), w = generalised force of the optional external base wrench: rows 0..2 = world
+ *     force at the base origin, rows 3..5 = E(zyx)' (world moment), zero elsewhere (E: world angular velocity = E ZYX rates).
+ *  3. W = J M^-1 J' + eps tr(J M^-1 J') I with eps of hb_plant_reset;  c = J v_f + b, b = 0 on tangential rows and
+ *     (max(phi_c, 0) + erp min(phi_c, 0)) / h on normal rows.
+ *  4. Impulses p[12], warm-started from the previous substep (zero after hb_plant_reset), by `sweeps` sweeps of projected Gauss-Seidel
+ *     over the points 0, 1, 2, 3.  Within a point, with g = W p + c kept current after every change of an entry of p:
+ *       normal first:     p_n <- max(0, p_n - g_n / W_nn);
+ *       tangential pair:  t_a = p_a - g_a / W_aa for a = x, y (both g_a read before either entry changes); if |t| > mu p_n then
+ *                         t <- t (mu p_n / |t|), zero if p_n = 0;  p_x, p_y <- t.
+ *     The residual of the last sweep is max |W_ii dp_i| over its twelve updates [m/s].
+ *  5. v+ = v_f + M^-1 J' p,  q+ = q + h v+.
+ *  6. Outputs of a step: lambda = p / h (world forces, last substep); vdot = (v+ - v) / h (last substep: what the accelerometer of
+ *     hb_plant_sense sees, impacts included); the last substep's residual; touching_c = (p_n > 0); the world velocity J v+ of every
+ *     point (J of the last substep) and the gap of every point at the new q.
+ * The contact flags given to hb_plant_step (host array or planned mode) play no part in the dynamics of model 1; they are still
+ * recorded and handed to the estimator by hb_plant_sense as the commanded flags, which is what the reference feeds its filter
+ * (LeggedController.cpp:224, 329: updateContact(cmdContactFlag)).
+ * Status word per instance: HB_CONTACT_NONFINITE = non-finite state; HB_CONTACT_FALLEN = base z - ground_z < fall_height (latched until
+ * hb_plant_reset; the instance goes on integrating); HB_CONTACT_UNCONVERGED = residual of the last substep > tol.
+ * The model and the wrench survive hb_plant_reset, which clears impulses, outputs and status.  After a NULL model (or with the model
+ * never set) hb_plant_step launches the pinned stub's kernel exactly as before; going back from model 1 to model 0 without a
+ * hb_plant_reset un-pins every point, so the stub's next step anchors each commanded contact where the foot is then. */
+#define HB_CONTACT_NONFINITE 1
+#define HB_CONTACT_FALLEN 2
+#define HB_CONTACT_UNCONVERGED 4
+typedef struct hb_contact_config {
+  int32_t mode;        /* 0: pinned stub (default); 1: ground */
+  int32_t sweeps;      /* 1 .. 10000 */
+  double mu;           /* Coulomb friction coefficient, >= 0 */
+  double ground_z;     /* height of the plane */
+  double erp;          /* share of a penetration removed per substep, [0, 1] */
+  double tol;          /* m/s, >= 0: residual above which HB_CONTACT_UNCONVERGED is raised */
+  double fall_height;  /* >= 0; 0: no fall detection */
+  int32_t reserved[2]; /* 0 */
+} hb_contact_config;
+/* cfg NULL = model 0 (with mode 0 the other fields but `reserved` are ignored).  HB_ERR_STATE before hb_plant_reset; HB_ERR_ARG for a
+ * non-finite or out-of-range field or a nonzero `reserved` (the model in force is kept). */
+int32_t hb_plant_set_contact_model(hb_ctx* ctx, const hb_contact_config* cfg);
+/* wrench[batch][6] = world force, world moment at the base origin, applied by every later step of model 1; NULL clears it.
+ * HB_ERR_STATE before hb_plant_reset or in model 0. */
+int32_t hb_plant_set_external_wrench(hb_ctx* ctx, const double* wrench);
+/* Contact outputs of the last step of model 1 (any may be NULL; zero between hb_plant_reset and the first step): gap[batch][4],
+ * point_vel[batch][12], residual[batch], touching[batch][4], status[batch].  HB_ERR_STATE before hb_plant_reset or in model 0. */
+int32_t hb_plant_get_contact(hb_ctx* ctx, double* gap, double* point_vel, double* residual, int32_t* touching, int32_t* status);
 
 /* ---- sensors from the plant: what LeggedController::updateStateEstimation reads, computed on the device -----------
  * hb_plant_sense turns the plant's state into the sensor arrays of hb_estimator_update and leaves them on the device
