@@ -213,6 +213,38 @@ def make_contact_config(params: dict, **overrides) -> HbContactConfig:
     return out
 
 
+class HbJointModel(C.Structure):
+    """hb_joint_model (include/hunter_hip.h): joint model of the ground-contact plant, hb_plant_set_joint_model."""
+    _fields_ = [(k, C.c_double * NJ) for k in ("armature", "damping", "frictionloss", "lower", "upper", "torque_limit")] + [
+        ("limit_erp", C.c_double), ("tol", C.c_double), ("limits", C.c_int32), ("reserved", C.c_int32)]
+
+
+HB_JOINT_UNCONVERGED = 1 << 30
+
+
+def make_joint_model(params: dict, **overrides) -> HbJointModel:
+    """The joints of the reference's MuJoCo model: armature 0.1 kg m^2 and damping 1 N m s/rad (mujoco/model/hunter/hunter.xml:6),
+    frictionloss 0.2 N m and the ranges (hunter.xml:59-124; the ranges are params["model"]["q_lower"] / ["q_upper"], the same numbers
+    as hunter.urdf:93-556), torque limit 100 N m (ctrlrange of every motor, hunter.xml:25), stops on (limits = 1), limit_erp 0.2,
+    joint-residual tolerance 1e-3 rad/s.  Any field by name overrides; a per-joint field takes a scalar or ten values.
+
+    The URDF's `effort` of 23.7 N m (params["model"]["effort"]) is NOT the default: it lies below the WBC's own torque rows of 28 / 60
+    N m (task.info torqueLimitsTask), so a plant saturating there clips torques the controller considers admissible.  It is a choice by
+    override: make_joint_model(params, torque_limit=params["model"]["effort"])."""
+    m = params["model"]
+    d = dict(armature=0.1, damping=1.0, frictionloss=0.2, lower=m["q_lower"], upper=m["q_upper"], torque_limit=100.0, limit_erp=0.2,
+             tol=1e-3, limits=1)
+    for k in overrides:
+        if k not in d:
+            raise TypeError(f"make_joint_model: unknown field {k!r} (one of {sorted(d)})")
+    d.update(overrides)
+    out = HbJointModel()
+    for k in ("armature", "damping", "frictionloss", "lower", "upper", "torque_limit"):
+        _fill(getattr(out, k), np.broadcast_to(np.asarray(d[k], dtype=float), (NJ,)))
+    out.limit_erp, out.tol, out.limits, out.reserved = float(d["limit_erp"]), float(d["tol"]), int(d["limits"]), 0
+    return out
+
+
 class HbJointGains(C.Structure):
     _fields_ = [(k, C.c_double) for k in ("kp_big_stance", "kp_big_swing", "kd_big", "kp_small_stance", "kp_small_swing", "kd_small",
                                           "kd_feet", "kp_position", "kd_position")]

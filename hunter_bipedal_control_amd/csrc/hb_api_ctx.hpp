@@ -97,6 +97,10 @@ struct hb_ctx {
   // allocated by the first call that selects it.  Model and wrench survive hb_plant_reset.
   ContactBatch contact{};
   hb_contact_config contact_cfg{};
+  // joint model of contact model 1 (hb_plant_set_joint_model): joints_on while one is in force; the arrays are allocated on first use
+  JointBatch joints{};
+  hb_joint_model joint_model{};
+  bool joints_on = false;
   // reference generation (allocated on the first hb_refgen_reset)
   RefgenBatch rg{};
   hb_refgen_config rg_cfg{};

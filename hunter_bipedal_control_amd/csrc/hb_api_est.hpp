@@ -63,6 +63,18 @@ static int32_t contact_clear(hb_ctx* ctx, hipStream_t s) {
   return HB_OK;
 }
 
+// friction and stop impulses, outputs and status of the joint model back to zero
+static int32_t joints_clear(hb_ctx* ctx, hipStream_t s) {
+  JointBatch& j = ctx->joints;
+  HB_HIP(hipMemsetAsync(j.imp, 0, field_count(ctx, j, j.imp) * 8, s));
+  HB_HIP(hipMemsetAsync(j.tau_applied, 0, field_count(ctx, j, j.tau_applied) * 8, s));
+  HB_HIP(hipMemsetAsync(j.friction_torque, 0, field_count(ctx, j, j.friction_torque) * 8, s));
+  HB_HIP(hipMemsetAsync(j.limit_torque, 0, field_count(ctx, j, j.limit_torque) * 8, s));
+  HB_HIP(hipMemsetAsync(j.res, 0, field_count(ctx, j, j.res) * 8, s));
+  HB_HIP(hipMemsetAsync(j.status, 0, field_count(ctx, j, j.status) * sizeof(int), s));
+  return HB_OK;
+}
+
 int32_t hb_plant_reset(hb_ctx* ctx, const double* q0, const double* v0, double baumgarte, double eps) {
   HB_ENTER(!q0 || !(baumgarte >= 0.0) || !(eps >= 0.0));
   PlantBatch& p = ctx->plant;
@@ -79,6 +91,7 @@ int32_t hb_plant_reset(hb_ctx* ctx, const double* q0, const double* v0, double b
   hipLaunchKernelGGL(k_plant_reset, dim3((ctx->B + 63) / 64), dim3(64), 0, ctx->s_wbc, p, ctx->dmodel);
   HB_HIP(hipGetLastError());
   if (ctx->contact.wrench) HB_TRY(contact_clear(ctx, ctx->s_wbc));
+  if (ctx->joints.status) HB_TRY(joints_clear(ctx, ctx->s_wbc));
   HB_HIP(hipStreamSynchronize(ctx->s_wbc));
   ctx->plant_ready = true;
   return HB_OK;
@@ -96,6 +109,12 @@ int32_t hb_plant_step(hb_ctx* ctx, const double* tau, const int32_t* contact, do
   HB_TRY(push(ctx, contact, p, p.contact, whole(ctx), &s));
   const double* dtau = tau ? p.tau : ctx->jc_out + 5 * B * HB_NJ;
   // the resident observation feeds the next hb_mpc_solve(NULL) / hb_refgen_update(NULL) on the MPC stream
+  if (ctx->contact_cfg.mode == 1 && ctx->joints_on)
+    return resident_write(ctx, s, to_resident, [&] {
+      hipLaunchKernelGGL(k_plant_joints, dim3(ctx->B), dim3(64), 0, s, p, ctx->contact, ctx->joints, ctx->contact_cfg, ctx->joint_model, ctx->dmodel, dtau,
+                         contact ? p.contact : nullptr, ctx->w.mode, dt, substeps, to_resident ? ctx->w.rbd : nullptr,
+                         to_resident ? ctx->b.x0 : nullptr, to_resident ? ctx->w.t_now : nullptr);
+    });
   if (ctx->contact_cfg.mode == 1)
     return resident_write(ctx, s, to_resident, [&] {
       hipLaunchKernelGGL(k_plant_contact, dim3(ctx->B), dim3(64), 0, s, p, ctx->contact, ctx->contact_cfg, ctx->dmodel, dtau, contact ? p.contact : nullptr,
@@ -142,6 +161,10 @@ int32_t hb_plant_set_contact_model(hb_ctx* ctx, const hb_contact_config* cfg) {
     HB_HIP(hipMemsetAsync(p.pinned, 0, field_count(ctx, p, p.pinned) * sizeof(int), ctx->s_wbc));
   }
   ctx->contact_cfg = ground ? *cfg : hb_contact_config{};
+  if (!ground && ctx->joints_on) {   // the joint model belongs to contact model 1
+    ctx->joints_on = false;
+    HB_TRY(joints_clear(ctx, ctx->s_wbc));
+  }
   return HB_OK;
 }
 
@@ -175,6 +198,47 @@ int32_t hb_plant_get_contact(hb_ctx* ctx, double* gap, double* point_vel, double
   HB_TRY(pull(ctx, residual, c, c.res, whole(ctx)));
   HB_TRY(pull(ctx, touching, c, c.touching, whole(ctx)));
   HB_TRY(pull(ctx, status, c, c.status, whole(ctx)));
+  return HB_OK;
+}
+
+int32_t hb_plant_set_joint_model(hb_ctx* ctx, const hb_joint_model* model) {
+  HB_ENTER_ARGS(false);
+  HB_TRY(contact_ready(ctx, "hb_plant_set_joint_model"));
+  HB_FAIL_IF(model && !joint_model_valid(*model), HB_ERR_ARG, "hb_plant_set_joint_model: armature, damping, frictionloss >= 0, lower < upper, torque_limit > 0 (+inf allowed), limit_erp in [0, 1], tol >= 0, limits 0 / 1, every other field finite and `reserved` 0");
+  HB_ENTER_DEVICE();
+  HB_HIP(hipStreamSynchronize(ctx->s_wbc));  // (a step in flight still runs under the model it was launched with)
+  if (model && !ctx->joints.status) {  // (status: the last array of the description, so an allocation that failed half way is repeated)
+    HB_HIP(alloc_fields(ctx, ctx->joints));
+    ctx->joints.B = ctx->B;
+  } else if (model && !ctx->joints_on) {
+    HB_TRY(joints_clear(ctx, ctx->s_wbc));  // back from ideal joints: no warm start from before them
+  }
+  if (!model && ctx->joints_on) HB_TRY(joints_clear(ctx, ctx->s_wbc));  // ideal joints again: the outputs read zero
+  if (model) ctx->joint_model = *model;
+  ctx->joints_on = model != nullptr;
+  return HB_OK;
+}
+
+int32_t hb_plant_get_joints(hb_ctx* ctx, double* tau_applied, double* friction_torque, double* limit_torque, double* residual, int32_t* status) {
+  HB_ENTER_ARGS(false);
+  HB_TRY(contact_ready(ctx, "hb_plant_get_joints"));
+  HB_ENTER_DEVICE();
+  HB_HIP(hipStreamSynchronize(ctx->s_wbc));
+  JointBatch& j = ctx->joints;
+  if (!j.status) {  // no joint model was ever set: the outputs are zero
+    const size_t B = ctx->B;
+    double* const outs[3] = {tau_applied, friction_torque, limit_torque};
+    for (double* o : outs)
+      if (o) std::memset(o, 0, B * HB_NJ * 8);
+    if (residual) std::memset(residual, 0, B * 8);
+    if (status) std::memset(status, 0, B * sizeof(int32_t));
+    return HB_OK;
+  }
+  HB_TRY(pull(ctx, tau_applied, j, j.tau_applied, whole(ctx)));
+  HB_TRY(pull(ctx, friction_torque, j, j.friction_torque, whole(ctx)));
+  HB_TRY(pull(ctx, limit_torque, j, j.limit_torque, whole(ctx)));
+  HB_TRY(pull(ctx, residual, j, j.res, whole(ctx)));
+  HB_TRY(pull(ctx, status, j, j.status, whole(ctx)));
   return HB_OK;
 }
 

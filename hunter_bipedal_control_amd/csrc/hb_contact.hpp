@@ -1,6 +1,6 @@
 // Plant with unilateral frictional ground contact (contact model 1 of include/hunter_hip.h, "ground"), one 64-lane workgroup per robot.
 // A velocity-level time stepper: per substep the rigid-body terms, the Cholesky factor of M, M^-1 [rhs | J'] and J M^-1 J' are the front
-// half of the pinned stub's substep with every contact point switched on (hb_plant.hpp plant_substep<TERMS_ONLY>); the contact impulses then come
+// half of the pinned stub's substep with every contact point switched on (hb_plant.hpp plant_substep<1>); the contact impulses then come
 // from projected Gauss-Seidel sweeps over the four points (normal first, then the tangential pair projected onto the friction disc),
 // warm-started from the previous substep.  Contact is decided by geometry (the gap to the plane z = ground_z), never by the schedule.
 //
@@ -75,7 +75,7 @@ HB_HD void contact_substep(const Ctx& cx, const DevModel& Mdl, double* q, double
     for (int a = 6; a < 16; ++a) wgen[a] = 0.0;
   }
   // the front half of the pinned stub's substep with every point on (its first barrier publishes wgen)
-  plant_substep<true>(cx, Mdl, q, v, tau, all_on, nullptr, 0.0, 0.0, h, lds, nullptr, nullptr, wrench ? wgen : nullptr);
+  plant_substep<1>(cx, Mdl, q, v, tau, all_on, nullptr, 0.0, 0.0, h, lds, nullptr, nullptr, wrench ? wgen : nullptr);
   double tr = 0.0;
   for (int i = 0; i < 12; ++i) tr += A[i * 13];
   const double reg = eps * tr, mu = K.mu;

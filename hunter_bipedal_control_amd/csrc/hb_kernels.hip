@@ -21,6 +21,7 @@
 #include "hb_gait.hpp"
 #include "hb_plant.hpp"
 #include "hb_contact.hpp"
+#include "hb_joints.hpp"
 #include "hb_sensors.hpp"
 #include "hb_layout.hpp"
 #include "hb_wavectx.hpp"
@@ -989,6 +990,28 @@ __global__ __launch_bounds__(64) void k_plant_contact(PlantBatch p, ContactBatch
   const ContactOut out{cb.gap + 4 * i, cb.pvel + 12 * i, cb.res + i, cb.touching + 4 * i, cb.status + i};
   contact_step(cx, *M, p.q + 16 * i, p.v + 16 * i, cb.imp + 12 * i, tau + 10 * i, cb.use_wrench ? cb.wrench + 6 * i : nullptr, all_on, K, p.eps, dt,
                substeps, lds, p.lambda + 12 * i, p.vdot + 16 * i, out);
+  if (cx.lane == 0) plant_publish(p, M, i, dt, res_rbd, res_x0, res_t);
+}
+// Contact model 1 with the joint model (hb_joints.hpp); tau_last takes the saturated torque, the one the step integrates.
+__global__ __launch_bounds__(64) void k_plant_joints(PlantBatch p, ContactBatch cb, JointBatch jb, hb_contact_config K, hb_joint_model J,
+                                                     const DevModel* __restrict__ M, const double* tau, const int* contact, const int* mode,
+                                                     double dt, int substeps, double* res_rbd, double* res_x0, double* res_t) {
+  const int i = blockIdx.x;
+  __shared__ double lds[JOINT_LDS_TOTAL];
+  __shared__ int all_on[HB_NC];
+  const DeviceCtx cx;
+  if (cx.lane < HB_NC) {
+    int flag;
+    if (contact) flag = contact[4 * i + cx.lane];
+    else { bool cf[HB_NC]; mode_flags(mode[i], cf); flag = cf[cx.lane] ? 1 : 0; }
+    p.contact_last[4 * i + cx.lane] = flag;
+    all_on[cx.lane] = 1;
+  }
+  __syncthreads();
+  const ContactOut out{cb.gap + 4 * i, cb.pvel + 12 * i, cb.res + i, cb.touching + 4 * i, cb.status + i};
+  const JointOut jout{jb.tau_applied + 10 * i, jb.friction_torque + 10 * i, jb.limit_torque + 10 * i, jb.res + i, jb.status + i};
+  joints_step(cx, *M, p.q + 16 * i, p.v + 16 * i, cb.imp + 12 * i, jb.imp + 20 * i, tau + 10 * i, cb.use_wrench ? cb.wrench + 6 * i : nullptr,
+              all_on, K, J, p.eps, dt, substeps, lds, p.lambda + 12 * i, p.vdot + 16 * i, p.tau_last + 10 * i, out, jout);
   if (cx.lane == 0) plant_publish(p, M, i, dt, res_rbd, res_x0, res_t);
 }
 __global__ void k_plant_reset(PlantBatch p, const DevModel* __restrict__ M) {

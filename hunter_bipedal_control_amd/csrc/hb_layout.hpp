@@ -147,6 +147,19 @@ constexpr void fields(ContactBatch& c, size_t, F&& f) {
   HB_FIELD(c.imp, 12); HB_FIELD(c.gap, 4); HB_FIELD(c.pvel, 12); HB_FIELD(c.res, 1); HB_FIELD(c.touching, 4); HB_FIELD(c.status, 1); HB_FIELD(c.wrench, 6);
 }
 
+// joint model of the ground-contact plant (hb_joints.hpp), allocated by the first hb_plant_set_joint_model that gives one: friction
+// impulses and signed stop impulses of the last substep (the warm start) and the outputs of hb_plant_get_joints
+struct JointBatch {
+  int B;
+  double *imp, *tau_applied, *friction_torque, *limit_torque, *res;
+  int* status;
+};
+template <class F>
+constexpr void fields(JointBatch& j, size_t, F&& f) {
+  HB_FIELD(j.imp, 20); HB_FIELD(j.tau_applied, 10); HB_FIELD(j.friction_torque, 10); HB_FIELD(j.limit_torque, 10); HB_FIELD(j.res, 1);
+  HB_FIELD(j.status, 1);
+}
+
 // ---- reference generation ----------------------------------------------------------------------------------------------
 struct RefgenBatch {
   int B;
@@ -235,6 +248,7 @@ static_assert(sizeof(WbcCertBuf) == n_fields<WbcCertBuf>() * kPtr && sizeof(Hwbc
 static_assert(sizeof(PlantBatch) == kPtr /*B*/ + 2 * sizeof(double) + (n_fields<PlantBatch>() + 2 /*gyro_bias, accel_bias*/) * kPtr,
               "describe every array of PlantBatch in fields()");
 static_assert(sizeof(ContactBatch) == 2 * sizeof(int) + n_fields<ContactBatch>() * kPtr, "describe every array of ContactBatch in fields()");
+static_assert(sizeof(JointBatch) == kPtr /*B*/ + n_fields<JointBatch>() * kPtr, "describe every array of JointBatch in fields()");
 static_assert(sizeof(RefgenBatch) == kPtr /*B*/ + n_fields<RefgenBatch>() * kPtr + kPtr /*init_stance*/, "describe every array of RefgenBatch in fields()");
 static_assert(sizeof(GaitBatch) == 2 * sizeof(int) + n_fields<GaitBatch>() * kPtr, "describe every array of GaitBatch in fields()");
 static_assert(sizeof(EstBatch) == kPtr /*B*/ + (n_fields<EstBatch>() + 2 /*res_rbd, res_x0*/) * kPtr, "describe every array of EstBatch in fields()");

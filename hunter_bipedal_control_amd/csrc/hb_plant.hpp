@@ -21,30 +21,52 @@ struct PlantLds {
   static constexpr int dJv = nle + 16;   // 12
   static constexpr int feet = dJv + 12;  // 12
   static constexpr int total = feet + 12;
+  static constexpr int xs = 13;          // columns of X
 };
+// The same with X = M^-1 [rhs | Jc' | e_6 .. e_15] (16 x 23) for the joint model of contact model 1 (hb_joints.hpp)
+struct PlantJointLds {
+  static constexpr int M = 0;
+  static constexpr int Jc = M + 256;
+  static constexpr int X = Jc + 192;     // 16 x 23
+  static constexpr int A = X + 368;
+  static constexpr int b = A + 144;
+  static constexpr int nle = b + 12;
+  static constexpr int dJv = nle + 16;
+  static constexpr int feet = dJv + 12;
+  static constexpr int total = feet + 12;
+  static constexpr int xs = 23;
+};
+template <int FRONT> struct PlantLdsOf { using type = PlantLds; };
+template <> struct PlantLdsOf<2> { using type = PlantJointLds; };
 
 // One substep of length h.  q[16], v[16], anchor[12] in/out (global or LDS); rows[12] = 1 for pinned contact rows.
-// TERMS_ONLY: the front half alone, for the ground-contact model (hb_contact.hpp) — the rigid-body terms at (q, v), the Cholesky factor
+// FRONT = 1: the front half alone, for the ground-contact model (hb_contact.hpp) — the rigid-body terms at (q, v), the Cholesky factor
 // of M, X = M^-1 [rhs | Jc'] with rhs = S' tau - nle (+ wext[16], a generalised force, when one is given) and Jc M^-1 Jc' are left in LDS
 // (PlantLds: M, Jc, X, A, nle, dJv, feet); nothing behind `contact` in the argument list is used except lds and wext.
-template <bool TERMS_ONLY = false, class Ctx>
+// FRONT = 2: the same for the joint model of that contact model (hb_joints.hpp), on the layout PlantJointLds: mdiag[10] is added to the
+// joint diagonal of M before it is factored, and X carries the ten more columns M^-1 [e_6 .. e_15].
+template <int FRONT = 0, class Ctx>
 HB_HD void plant_substep(const Ctx& cx, const DevModel& Mdl, double* q, double* v, const double* tau, const int* contact, const double* anchor,
-                         double baum, double eps, double h, double* lds, double* lambda_out, double* vdot_out, const double* wext = nullptr) {
-  double* Mm = lds + PlantLds::M;
-  double* Jc = lds + PlantLds::Jc;
-  double* X = lds + PlantLds::X;
-  double* A = lds + PlantLds::A;
-  double* b = lds + PlantLds::b;
-  double* nle = lds + PlantLds::nle;
-  double* dJv = lds + PlantLds::dJv;
-  double* feet = lds + PlantLds::feet;
+                         double baum, double eps, double h, double* lds, double* lambda_out, double* vdot_out, const double* wext = nullptr,
+                         const double* mdiag = nullptr) {
+  using L = typename PlantLdsOf<FRONT>::type;
+  constexpr int XS = L::xs;
+  double* Mm = lds + L::M;
+  double* Jc = lds + L::Jc;
+  double* X = lds + L::X;
+  double* A = lds + L::A;
+  double* b = lds + L::b;
+  double* nle = lds + L::nle;
+  double* dJv = lds + L::dJv;
+  double* feet = lds + L::feet;
   // ---- rigid-body terms (lane 0)
   if (cx.lane == 0) {
     // results and work arrays in LDS (the X / A buffers are not live yet): thread-private they would sit in scratch
-    static_assert((sizeof(BodyPass) + sizeof(BodyWork) + 7) / 8 <= 208 + 144 + 12, "rigid-body workspace must fit X | A | b");
+    static_assert((sizeof(BodyPass) + sizeof(BodyWork) + 7) / 8 <= L::b + 12 - L::X, "rigid-body workspace must fit X | A | b");
     BodyPass& P = *reinterpret_cast<BodyPass*>(X);
     body_pass(Mdl, q, v, P, *reinterpret_cast<BodyWork*>(X + (sizeof(BodyPass) + 7) / 8));
     mass_matrix(P, Mm);
+    if constexpr (FRONT == 2) { for (int j = 0; j < 10; ++j) Mm[(6 + j) * 17] += mdiag[j]; }
     for (int a = 0; a < 16; ++a) nle[a] = P.nle[a];
     for (int ci = 0; ci < HB_NC; ++ci) {
       const double on = contact[ci] ? 1.0 : 0.0;
@@ -70,11 +92,18 @@ HB_HD void plant_substep(const Ctx& cx, const DevModel& Mdl, double* q, double* 
     cx.sync();
   }
   // ---- X = M^-1 [rhs | Jc'],  rhs = S' tau - nle   (one right-hand side per lane)
-  for (int c = cx.lane; c < 13; c += cx.nlanes) {
+  for (int c = cx.lane; c < XS; c += cx.nlanes) {
     double y[16];
     for (int i = 0; i < 16; ++i) {
-      double s = (c == 0) ? ((i >= 6 ? tau[i - 6] : 0.0) - nle[i]) : Jc[(c - 1) * 16 + i];
-      if constexpr (TERMS_ONLY) { if (c == 0 && wext) s += wext[i]; }
+      double s;
+      if constexpr (FRONT == 2) {   // (the unit columns load nothing: Jc has twelve rows)
+        if (c == 0) s = (i >= 6 ? tau[i - 6] : 0.0) - nle[i];
+        else if (c < 13) s = Jc[(c - 1) * 16 + i];
+        else s = (i == c - 7) ? 1.0 : 0.0;
+      } else {
+        s = (c == 0) ? ((i >= 6 ? tau[i - 6] : 0.0) - nle[i]) : Jc[(c - 1) * 16 + i];
+      }
+      if constexpr (FRONT != 0) { if (c == 0 && wext) s += wext[i]; }
       for (int k = 0; k < i; ++k) s -= Mm[i * 16 + k] * y[k];
       y[i] = s / Mm[i * 17];
     }
@@ -83,18 +112,18 @@ HB_HD void plant_substep(const Ctx& cx, const DevModel& Mdl, double* q, double* 
       for (int k = i + 1; k < 16; ++k) s -= Mm[k * 16 + i] * y[k];
       y[i] = s / Mm[i * 17];
     }
-    for (int i = 0; i < 16; ++i) X[i * 13 + c] = y[i];
+    for (int i = 0; i < 16; ++i) X[i * XS + c] = y[i];
   }
   cx.sync();
   // ---- A = Jc M^-1 Jc' (+ damping, + identity on the free rows), b
   for (int idx = cx.lane; idx < 144; idx += cx.nlanes) {
     const int i = idx / 12, j = idx - 12 * i;
     double s = 0.0;
-    for (int k = 0; k < 16; ++k) s += Jc[i * 16 + k] * X[k * 13 + 1 + j];
+    for (int k = 0; k < 16; ++k) s += Jc[i * 16 + k] * X[k * XS + 1 + j];
     A[idx] = s;
   }
   cx.sync();
-  if constexpr (TERMS_ONLY) return;
+  if constexpr (FRONT != 0) return;
   double tr = 0.0;
   for (int i = 0; i < 12; ++i) tr += A[i * 13];
   tr = fmax(tr, 1e-12);

@@ -140,7 +140,8 @@ class ResidentLoop:
 
     def __init__(self, solver, params: dict, gaits, cmd_vel, n_intervals: int = 100, mpc_every: int = 8, dt: float = 0.002,
                  t_gait_start: float = 0.3, joint_ik: bool = True, substeps: int = 4, static_schedule_until: float = 0.0,
-                 device_gait: bool = False, use_estimator: bool = False, sensor_config=None, sensor_bias=None, contact_config=None):
+                 device_gait: bool = False, use_estimator: bool = False, sensor_config=None, sensor_bias=None, contact_config=None,
+                 joint_model=None):
         """static_schedule_until > 0: the mode schedules are uploaded once for [-1, static_schedule_until] (at most
         HB_MAX_EVENTS events) instead of a sliding window per MPC call — no per-call host work for large batches.
         device_gait: the device gait manager produces the windows; step() builds no per-instance list and uploads no schedule, and
@@ -148,7 +149,11 @@ class ResidentLoop:
         other than the default "stance" go in once, at t_gait_start, through hb_gait_insert_template.
         contact_config: the plant's contact model — None: the pinned stub; a dict of abi.make_contact_config fields ({} = the defaults):
         ground with unilateral frictional contact, the plane under the lowest contact point of the start unless ground_z is among them;
-        an abi.HbContactConfig is taken as it is."""
+        an abi.HbContactConfig is taken as it is.
+        joint_model: the joint model of the ground-contact plant — None: ideal joints; a dict of abi.make_joint_model fields ({} = the
+        joints of the reference's MuJoCo model); an abi.HbJointModel is taken as it is.  Needs contact_config."""
+        if joint_model is not None and contact_config is None:
+            raise ValueError("joint_model belongs to the ground-contact plant: give contact_config as well")
         self.s, self.params, self.B = solver, params, solver.B
         self.horizon = n_intervals * params["config"]["dt"]
         self.dt, self.mpc_every, self.substeps = dt, mpc_every, substeps
@@ -183,6 +188,8 @@ class ResidentLoop:
                 fields.setdefault("ground_z", lowest_contact_point(solver, q0))
                 contact_config = abi.make_contact_config(params, **fields)
             solver.plant_set_contact_model(contact_config)
+            if joint_model is not None:
+                solver.plant_set_joint_model(abi.make_joint_model(params, **joint_model) if isinstance(joint_model, dict) else joint_model)
         # resident observation of the initial state
         rbd = np.zeros((self.B, 32))
         rbd[:, 0:3], rbd[:, 3:6], rbd[:, 6:16] = q0[:, 3:6], q0[:, 0:3], q0[:, 6:]

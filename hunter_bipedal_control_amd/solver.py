@@ -33,6 +33,7 @@ ABI_SYMBOLS = [
     "hb_refgen_get_schedule", "hb_gait_reset", "hb_gait_disable", "hb_gait_insert_template", "hb_gait_get_state",
     "hb_plant_set_sensor_model", "hb_plant_sense", "hb_estimator_update_resident", "hb_estimator_contact_force_resident",
     "hb_plant_set_contact_model", "hb_plant_set_external_wrench", "hb_plant_get_contact",
+    "hb_plant_set_joint_model", "hb_plant_get_joints",
 ]
 # include/hunter_lcm.h
 LCM_SYMBOLS = ["hb_lcm_fingerprint", "hb_lcm_encoded_size", "hb_lcm_field_count", "hb_lcm_encode", "hb_lcm_decode", "hb_lcm_frame", "hb_lcm_unframe",
@@ -268,6 +269,21 @@ class HunterSolver:
         out = dict(gap=np.zeros((self.B, 4)), point_vel=np.zeros((self.B, 4, 3)), residual=np.zeros(self.B),
                    touching=np.zeros((self.B, 4), dtype=np.int32), status=np.zeros(self.B, dtype=np.int32))
         self._check(self.lib.hb_plant_get_contact(self.ctx, *[_p(a) for a in out.values()]), "hb_plant_get_contact")
+        return out
+
+    # ---- joint model of the ground-contact plant (hb_plant_set_joint_model) ---------------------------------------------------
+    def plant_set_joint_model(self, joint_model: "abi.HbJointModel" = None):
+        """joint_model None: ideal joints; abi.make_joint_model(params, ...): rotor inertia, damping, dry friction, stops and torque
+        saturation in the ground-contact model (plant_set_contact_model first)."""
+        self._check(self.lib.hb_plant_set_joint_model(self.ctx, None if joint_model is None else C.byref(joint_model)),
+                    "hb_plant_set_joint_model")
+
+    def plant_get_joints(self):
+        """Joint outputs of the last step under the joint model -> dict(tau_applied[B][10], friction_torque[B][10], limit_torque[B][10],
+        residual[B], status[B] int32: bit j = stop of joint j active, bit 10 + j = torque of joint j saturated, abi.HB_JOINT_UNCONVERGED)."""
+        out = dict(tau_applied=np.zeros((self.B, 10)), friction_torque=np.zeros((self.B, 10)), limit_torque=np.zeros((self.B, 10)),
+                   residual=np.zeros(self.B), status=np.zeros(self.B, dtype=np.int32))
+        self._check(self.lib.hb_plant_get_joints(self.ctx, *[_p(a) for a in out.values()]), "hb_plant_get_joints")
         return out
 
     # ---- sensors from the plant (hb_plant_sense) and the estimator on them ------------------------------------------------

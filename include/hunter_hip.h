@@ -303,6 +303,53 @@ int32_t hb_plant_set_external_wrench(hb_ctx* ctx, const double* wrench);
  * point_vel[batch][12], residual[batch], touching[batch][4], status[batch].  HB_ERR_STATE before hb_plant_reset or in model 0. */
 int32_t hb_plant_get_contact(hb_ctx* ctx, double* gap, double* point_vel, double* residual, int32_t* touching, int32_t* status);
 
+/* ---- joint model of contact model 1: rotor inertia, viscous damping, dry friction, joint stops, torque saturation ------------------
+ * One context-wide setting, off by default.  The reference's MuJoCo model gives every leg joint armature 0.1 and damping 1
+ * (mujoco/model/hunter/hunter.xml:6), frictionloss 0.2 and a range (:59-124) and every motor ctrlrange +-100 (:25).  With a model in
+ * force the steps 1 - 6 of contact model 1 above become, per substep of length h:
+ *  1. Mh = M + diag(0_6, armature + h damping).  Every M^-1 of model 1 becomes Mh^-1.
+ *  2. tau_a = clamp(tau, -torque_limit, +torque_limit);  v_f = v + h Mh^-1 (S' tau_a - nle - damping o v_joint + w).  With step 1 this
+ *     is backward Euler in the damping term.
+ *  3. 32 rows: 0-11 the contact rows as above; row 12 + j the friction row of joint j, Jacobian row e_{6+j}; row 22 + j the stop of joint
+ *     j, Jacobian row s_j e_{6+j}, with s_j = +1, phi_j = q_j - lower_j if q_j - lower_j <= upper_j - q_j at the start of the substep,
+ *     otherwise s_j = -1, phi_j = upper_j - q_j.  W = Jh Mh^-1 Jh'; the twelve contact diagonals get eps tr(contact block) as above,
+ *     joint rows get no regularisation (their diagonal (Mh^-1)_jj is positive).  c = Jh v_f + b with, on stop rows,
+ *     b = (max(phi, 0) + limit_erp min(phi, 0)) / h and b = 0 on friction rows.
+ *  4. A sweep does the four contact points as above, then the friction rows j = 0..9: p <- clamp(p - g / W_rr, -frictionloss_j h,
+ *     +frictionloss_j h), then (if `limits`) the stop rows j = 0..9: p <- max(0, p - g / W_rr); g = W p + c is kept current after every
+ *     change.  Warm start of a friction row: the previous substep's p.  Of a stop row: the stored value is u_j = s_j p_j, signed in joint
+ *     coordinates, and the substep starts from p_j = max(0, s_j u_j), so a change of side starts from zero.  Both are zero after
+ *     hb_plant_reset.  The residual of hb_plant_get_contact keeps its meaning (the twelve contact updates, m/s); the joint residual is
+ *     max |W_rr dp_r| over the joint updates of the last sweep [rad/s].
+ *  5. v+ = v_f + Mh^-1 Jh' p,  q+ = q + h v+.
+ *  6. Outputs per instance (hb_plant_get_joints): tau_applied[10] = tau_a; friction_torque[10] = p / h; limit_torque[10] = u / h (joint
+ *     coordinates: >= 0 at a lower stop, <= 0 at an upper one); the joint residual; a status word: bit j = the stop impulse of joint j in
+ *     the last substep is > 0, bit 10 + j = tau_a[j] != tau[j], HB_JOINT_UNCONVERGED = joint residual > tol.  The joint_torque of
+ *     hb_plant_sense becomes tau_a, the torque the step integrated.
+ * The commanded torque stays held over a tick (the reference's simulator evaluates its PD law per simulator step, mujoco/src/main.cc:247). */
+#define HB_JOINT_UNCONVERGED (1 << 30)
+typedef struct hb_joint_model {
+  double armature[10];      /* kg m^2, >= 0: added to the joint diagonal of M */
+  double damping[10];       /* N m s/rad, >= 0: viscous, implicit */
+  double frictionloss[10];  /* N m, >= 0: bound of the dry-friction torque */
+  double lower[10], upper[10];  /* rad, lower < upper */
+  double torque_limit[10];  /* N m, > 0, +inf allowed: actuator saturation */
+  double limit_erp;         /* [0, 1]: share of a limit violation removed per substep */
+  double tol;               /* rad/s, >= 0: joint residual above which HB_JOINT_UNCONVERGED is raised */
+  int32_t limits;           /* 0 / 1: joint stops off / on */
+  int32_t reserved;         /* 0 */
+} hb_joint_model;
+/* model NULL switches the joint model off (hb_plant_step then launches the kernel of contact model 1 exactly as without one).
+ * HB_ERR_STATE before hb_plant_reset or outside contact model 1; HB_ERR_ARG for a violated range, a non-finite field other than a +inf
+ * torque limit, or a nonzero `reserved` (the model in force is kept).  The model survives hb_plant_reset, which clears its impulses,
+ * outputs and status; leaving contact model 1 switches it off. */
+int32_t hb_plant_set_joint_model(hb_ctx* ctx, const hb_joint_model* model);
+/* Joint outputs of the last step under the joint model (any may be NULL; zero between hb_plant_reset and the first step, and without a
+ * joint model): tau_applied / friction_torque / limit_torque [batch][10], residual[batch], status[batch].  HB_ERR_STATE before
+ * hb_plant_reset or outside contact model 1. */
+int32_t hb_plant_get_joints(hb_ctx* ctx, double* tau_applied, double* friction_torque, double* limit_torque, double* residual,
+                            int32_t* status);
+
 /* ---- sensors from the plant: what LeggedController::updateStateEstimation reads, computed on the device -----------
  * hb_plant_sense turns the plant's state into the sensor arrays of hb_estimator_update and leaves them on the device
  * (plant-owned arrays [batch][4|3|3|10|10|10] and int [batch][4]); hb_estimator_update_resident /
