@@ -261,6 +261,18 @@ def make_joint_gains(**overrides) -> HbJointGains:
     return out
 
 
+def hybrid_gains(gains: HbJointGains, stance=(True, True)):
+    """-> (kp[10], kd[10]) by joint, as k_joint_command assigns them with the controller loaded (LeggedController.cpp:222-244): joints 0, 1
+    and 4 of a leg take the small gains (4: kd_feet), 2 and 3 the big ones; stance[leg] selects the stance or the swing kp."""
+    kp, kd = np.zeros(NJ), np.zeros(NJ)
+    for j in range(NJ):
+        k, on = j % 5, bool(stance[j // 5])
+        small = k in (0, 1, 4)
+        kp[j] = (gains.kp_small_stance if on else gains.kp_small_swing) if small else (gains.kp_big_stance if on else gains.kp_big_swing)
+        kd[j] = gains.kd_feet if k == 4 else (gains.kd_small if small else gains.kd_big)
+    return kp, kd
+
+
 HB_MAX_EVENTS = 64
 # field order of hunter_hip.h's HB_MPC_CERT_* (HunterSolver.mpc_certificate)
 MPC_CERT_FIELDS = ("r_dyn", "r_stat", "obj", "step_max", "u_max", "lambda_max", "scale", "n_nodes")

@@ -101,6 +101,8 @@ struct hb_ctx {
   JointBatch joints{};
   hb_joint_model joint_model{};
   bool joints_on = false;
+  // actuator loop per substep and the simulator end of the LCM link (hb_plant_step_hybrid / _lcm, hb_plant_sense_lcm): allocated on first use
+  ActuatorBatch act{};
   // reference generation (allocated on the first hb_refgen_reset)
   RefgenBatch rg{};
   hb_refgen_config rg_cfg{};

@@ -75,6 +75,25 @@ static int32_t joints_clear(hb_ctx* ctx, hipStream_t s) {
   return HB_OK;
 }
 
+// arrays of the actuator loop and of the simulator end of the LCM link (zero-filled: no hybrid step, zero command, zero timestamps)
+static int32_t actuator_alloc(hb_ctx* ctx) {
+  ActuatorBatch& a = ctx->act;
+  if (a.wire_full) return HB_OK;  // (wire_full: the last array of the description, so an allocation that failed half way is repeated)
+  HB_HIP(alloc_fields(ctx, a));
+  a.B = ctx->B;
+  return HB_OK;
+}
+
+// record of the last hybrid step, received command and timestamps back to zero (hb_plant_reset)
+static int32_t actuator_clear(hb_ctx* ctx, hipStream_t s) {
+  ActuatorBatch& a = ctx->act;
+  HB_HIP(hipMemsetAsync(a.tau_first, 0, field_count(ctx, a, a.tau_first) * 8, s));
+  HB_HIP(hipMemsetAsync(a.tau_mean, 0, field_count(ctx, a, a.tau_mean) * 8, s));
+  for (int k = 0; k < 5; ++k) HB_HIP(hipMemsetAsync(a.rcmd[k], 0, field_count(ctx, a, a.rcmd[k]) * 8, s));
+  HB_HIP(hipMemsetAsync(a.last_ts, 0, field_count(ctx, a, a.last_ts) * 8, s));
+  return HB_OK;
+}
+
 int32_t hb_plant_reset(hb_ctx* ctx, const double* q0, const double* v0, double baumgarte, double eps) {
   HB_ENTER(!q0 || !(baumgarte >= 0.0) || !(eps >= 0.0));
   PlantBatch& p = ctx->plant;
@@ -92,6 +111,7 @@ int32_t hb_plant_reset(hb_ctx* ctx, const double* q0, const double* v0, double b
   HB_HIP(hipGetLastError());
   if (ctx->contact.wrench) HB_TRY(contact_clear(ctx, ctx->s_wbc));
   if (ctx->joints.status) HB_TRY(joints_clear(ctx, ctx->s_wbc));
+  if (ctx->act.wire_full) HB_TRY(actuator_clear(ctx, ctx->s_wbc));
   HB_HIP(hipStreamSynchronize(ctx->s_wbc));
   ctx->plant_ready = true;
   return HB_OK;
@@ -125,6 +145,75 @@ int32_t hb_plant_step(hb_ctx* ctx, const double* tau, const int32_t* contact, do
     hipLaunchKernelGGL(k_plant, dim3(ctx->B), dim3(64), 0, s, p, ctx->dmodel, dtau, contact ? p.contact : nullptr, ctx->w.mode, dt, substeps,
                        to_resident ? ctx->w.rbd : nullptr, to_resident ? ctx->b.x0 : nullptr, to_resident ? ctx->w.t_now : nullptr);
   });
+}
+
+// what the step calls check before anything changes; `who` names the entry point
+static int32_t plant_step_ready(hb_ctx* ctx, const char* who, bool need_jc, bool need_mode) {
+  const char* why = !ctx->plant_ready ? "call hb_plant_reset first"
+                    : need_jc && !ctx->jc_computed ? "no device-resident joint command yet (hb_joint_command after a WBC call)"
+                    : need_mode && ctx->stats.n_wbc_solves == 0 ? "no device-resident contact flags yet (a WBC call)"
+                                                                : nullptr;
+  if (!why) return HB_OK;
+  ctx->err = std::string(who) + ": " + why;
+  return HB_ERR_STATE;
+}
+
+// A hybrid step of the plant form in force on the five device arrays cmd (pos_des vel_des kp kd ff, [B][10] each); contact: host flags or null.
+static int32_t plant_launch_hybrid(hb_ctx* ctx, const double* const cmd[5], const int32_t* contact, double dt, int32_t substeps, int32_t to_resident) {
+  PlantBatch& p = ctx->plant;
+  hipStream_t s = ctx->s_wbc;  // the plant follows the control thread
+  HB_TRY(push(ctx, contact, p, p.contact, whole(ctx), &s));
+  const ActuatorCmd c{{cmd[0], cmd[1], cmd[2], cmd[3], cmd[4]}};
+  const int* dcontact = contact ? p.contact : nullptr;
+  double* rr = to_resident ? ctx->w.rbd : nullptr;
+  double* rx = to_resident ? ctx->b.x0 : nullptr;
+  double* rt = to_resident ? ctx->w.t_now : nullptr;
+  if (ctx->contact_cfg.mode == 1 && ctx->joints_on)
+    return resident_write(ctx, s, to_resident, [&] {
+      hipLaunchKernelGGL(k_plant_joints_hybrid, dim3(ctx->B), dim3(64), 0, s, p, ctx->contact, ctx->joints, ctx->act, c, ctx->contact_cfg, ctx->joint_model,
+                         ctx->dmodel, dcontact, ctx->w.mode, dt, substeps, rr, rx, rt);
+    });
+  if (ctx->contact_cfg.mode == 1)
+    return resident_write(ctx, s, to_resident, [&] {
+      hipLaunchKernelGGL(k_plant_contact_hybrid, dim3(ctx->B), dim3(64), 0, s, p, ctx->contact, ctx->act, c, ctx->contact_cfg, ctx->dmodel, dcontact,
+                         ctx->w.mode, dt, substeps, rr, rx, rt);
+    });
+  return resident_write(ctx, s, to_resident, [&] {
+    hipLaunchKernelGGL(k_plant_hybrid, dim3(ctx->B), dim3(64), 0, s, p, ctx->act, c, ctx->dmodel, dcontact, ctx->w.mode, dt, substeps, rr, rx, rt);
+  });
+}
+
+int32_t hb_plant_step_hybrid(hb_ctx* ctx, const double* pos_des, const double* vel_des, const double* kp, const double* kd, const double* tau_ff,
+                             const int32_t* contact, double dt, int32_t substeps, int32_t to_resident) {
+  const double* const host[5] = {pos_des, vel_des, kp, kd, tau_ff};
+  int given = 0;
+  for (const double* h : host) given += h ? 1 : 0;
+  HB_ENTER_ARGS(!(dt > 0.0) || substeps < 1);
+  HB_FAIL_IF(given != 0 && given != 5, HB_ERR_ARG, "hb_plant_step_hybrid: give all five command arrays, or none for the device-resident command of hb_joint_command");
+  HB_TRY(plant_step_ready(ctx, "hb_plant_step_hybrid", given == 0, !contact));
+  HB_ENTER_DEVICE();
+  HB_TRY(actuator_alloc(ctx));
+  ActuatorBatch& a = ctx->act;
+  const size_t n = size_t(ctx->B) * HB_NJ;
+  const double* cmd[5];
+  for (int k = 0; k < 5; ++k) {
+    HB_TRY(push(ctx, host[k], a, a.cmd[k], whole(ctx), &ctx->s_wbc));
+    cmd[k] = given ? a.cmd[k] : ctx->jc_out + k * n;   // planes 0-4 of the joint command: posDes velDes kp kd ff
+  }
+  return plant_launch_hybrid(ctx, cmd, contact, dt, substeps, to_resident);
+}
+
+int32_t hb_plant_get_actuator(hb_ctx* ctx, double* tau_first, double* tau_mean, int64_t* last_timestamp) {
+  HB_ENTER_ARGS(false);
+  HB_FAIL_IF(!ctx->plant_ready, HB_ERR_STATE, "hb_plant_get_actuator: call hb_plant_reset first");
+  HB_ENTER_DEVICE();
+  HB_TRY(actuator_alloc(ctx));
+  HB_HIP(hipStreamSynchronize(ctx->s_wbc));
+  ActuatorBatch& a = ctx->act;
+  HB_TRY(pull(ctx, tau_first, a, a.tau_first, whole(ctx)));
+  HB_TRY(pull(ctx, tau_mean, a, a.tau_mean, whole(ctx)));
+  HB_TRY(pull(ctx, last_timestamp, a, a.last_ts, whole(ctx)));
+  return HB_OK;
 }
 
 int32_t hb_plant_get_state(hb_ctx* ctx, double* q, double* v, double* rbd, double* lambda, double* vdot) {

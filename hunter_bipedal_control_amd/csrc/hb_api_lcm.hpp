@@ -1,4 +1,4 @@
-// Host side, part 6: the LCM wire format (include/hunter_lcm.h) and the two entry points that speak it.
+// Host side, part 6: the LCM wire format (include/hunter_lcm.h) and the entry points that speak it: the controller end and the simulator end.
 #pragma once
 
 extern "C" {
@@ -108,6 +108,56 @@ int32_t hb_estimator_update_lcm(hb_ctx* ctx, double dt, const uint8_t* low_state
   HB_FAIL_IF(bad, HB_ERR_ARG, "hb_estimator_update_lcm: a message does not carry the low_state_t fingerprint");
   if (timestamp) HB_HIP(hipMemcpy(timestamp, ctx->lcm_ts, B * 8, hipMemcpyDeviceToHost));
   return estimator_run(ctx, ctx->est, dt, to_resident, rbd, x_state);
+}
+
+// ---- the simulator end of the link ---------------------------------------------------------------------------------------------------
+int32_t hb_plant_step_lcm(hb_ctx* ctx, const uint8_t* low_cmd, const int32_t* contact, double dt, int32_t substeps, int32_t to_resident,
+                          int32_t* accepted) {
+  HB_ENTER_ARGS(!low_cmd || !(dt > 0.0) || substeps < 1);
+  HB_TRY(plant_step_ready(ctx, "hb_plant_step_lcm", false, !contact));
+  // the fingerprints are looked at here, where the bytes still are: nothing has changed when one is foreign
+  const uint64_t fp = lcm_fingerprint(HB_LCM_LOW_CMD);
+  for (int i = 0; i < ctx->B; ++i)
+    HB_FAIL_IF(lcm_get64(low_cmd + size_t(i) * HB_LCM_LOW_CMD_BYTES) != fp, HB_ERR_ARG, "hb_plant_step_lcm: a message does not carry the low_cmd_t fingerprint");
+  HB_ENTER_DEVICE();
+  HB_TRY(actuator_alloc(ctx));
+  ActuatorBatch& a = ctx->act;
+  hipStream_t s = ctx->s_wbc;
+  HB_HIP(hipMemcpyAsync(a.wire_cmd, low_cmd, field_count(ctx, a, a.wire_cmd) * 8, hipMemcpyHostToDevice, s));
+  hipLaunchKernelGGL(k_lcm_unpack_cmd, dim3((ctx->B + 63) / 64), dim3(64), 0, s, ctx->B, a.wire_cmd, a.rcmd[0], a.rcmd[1], a.rcmd[2], a.rcmd[3], a.rcmd[4],
+                     a.last_ts, a.accepted);
+  HB_HIP(hipGetLastError());
+  HB_TRY(pull(ctx, accepted, a, a.accepted, whole(ctx), &s));
+  HB_TRY(plant_launch_hybrid(ctx, a.rcmd, contact, dt, substeps, to_resident));
+  if (accepted) HB_HIP(hipStreamSynchronize(s));
+  return HB_OK;
+}
+
+int32_t hb_plant_sense_lcm(hb_ctx* ctx, int64_t timestamp_ns, uint8_t* low_state, uint8_t* full_state) {
+  HB_ENTER_ARGS(false);
+  HB_FAIL_IF(!low_state && !full_state, HB_ERR_ARG, "hb_plant_sense_lcm: give low_state, full_state or both");
+  HB_FAIL_IF(!ctx->plant_ready, HB_ERR_STATE, "hb_plant_sense_lcm: call hb_plant_reset first");
+  HB_ENTER_DEVICE();
+  HB_TRY(actuator_alloc(ctx));
+  HB_TRY(hb_plant_sense(ctx, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr));   // (enqueue-only: the arrays stay on the device)
+  ActuatorBatch& a = ctx->act;
+  const PlantBatch& p = ctx->plant;
+  hipStream_t s = ctx->s_wbc;
+  const unsigned B = unsigned(ctx->B);
+  if (low_state) {
+    hipLaunchKernelGGL(k_lcm_pack_state, dim3((B * 42 + 255) / 256), dim3(256), 0, s, ctx->B, p.s_quat, p.s_gyro, p.s_accel, p.s_jp, p.s_jv, p.s_jt,
+                       lcm_fingerprint(HB_LCM_LOW_STATE), timestamp_ns, a.wire_low);
+    HB_HIP(hipGetLastError());
+    HB_TRY(pull(ctx, low_state, a, a.wire_low, whole(ctx), &s));
+  }
+  if (full_state) {
+    hipLaunchKernelGGL(k_lcm_pack_full, dim3((B + 63) / 64), dim3(64), 0, s, ctx->B, ctx->hmodel.gravity, p.q, p.v, p.tau_last,
+                       lcm_fingerprint(HB_LCM_FULL_STATE), timestamp_ns, a.wire_full);
+    HB_HIP(hipGetLastError());
+    HB_TRY(pull(ctx, full_state, a, a.wire_full, whole(ctx), &s));
+  }
+  HB_HIP(hipStreamSynchronize(s));
+  return HB_OK;
 }
 
 }  // extern "C"

@@ -168,10 +168,10 @@ HB_HD void contact_substep(const Ctx& cx, const DevModel& Mdl, double* q, double
 
 // One plant tick of one instance in contact model 1: `substeps` substeps of dt / substeps, then the outputs of the step.  State (q, v,
 // impulses, status) lives in global memory and is staged in LDS behind `lds` (CONTACT_LDS_TOTAL doubles).
-template <class Ctx>
+template <bool HYBRID = false, class Ctx>
 HB_HD void contact_step(const Ctx& cx, const DevModel& Mdl, double* q_g, double* v_g, double* imp_g, const double* tau, const double* wrench,
                         const int* all_on, const hb_contact_config& K, double eps, double dt, int substeps, double* lds, double* lambda_out,
-                        double* vdot_out, const ContactOut& out) {
+                        double* vdot_out, const ContactOut& out, const HybridActuator* actuator = nullptr) {
   double* q = lds + ContactLds::q;
   double* v = lds + ContactLds::v;
   double* imp = lds + ContactLds::imp;
@@ -179,7 +179,17 @@ HB_HD void contact_step(const Ctx& cx, const DevModel& Mdl, double* q_g, double*
   for (int i = cx.lane; i < 12; i += cx.nlanes) imp[i] = imp_g[i];
   cx.sync();
   const double h = dt / substeps;
-  for (int s = 0; s < substeps; ++s) contact_substep(cx, Mdl, q, v, tau, wrench, all_on, K, eps, h, lds, vdot_out);
+  if constexpr (HYBRID) {   // (hb_plant.hpp: the law before every substep; `tau` is not read)
+    const HybridActuator& act = *actuator;
+    ActuatorAcc acc;
+    for (int s = 0; s < substeps; ++s) {
+      actuator_eval(cx, act, q, v, s, act.tau, acc, [](int, double ts) { return ts; });
+      contact_substep(cx, Mdl, q, v, act.tau, wrench, all_on, K, eps, h, lds, vdot_out);
+    }
+    actuator_finish(cx, act, substeps, acc, false);
+  } else {
+    for (int s = 0; s < substeps; ++s) contact_substep(cx, Mdl, q, v, tau, wrench, all_on, K, eps, h, lds, vdot_out);
+  }
   // ---- outputs: world forces, touching flags and point velocities J v+ of the last substep; gaps at q+
   const double* Jc = lds + PlantLds::Jc;
   double* feet = lds + PlantLds::feet;

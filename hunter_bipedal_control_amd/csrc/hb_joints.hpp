@@ -240,12 +240,14 @@ HB_HD void joints_substep(const Ctx& cx, const DevModel& Mdl, double* q, double*
 
 // One plant tick of one instance in contact model 1 with the joint model: `substeps` substeps of dt / substeps, then the outputs of the
 // step.  imp_g[12] the contact impulses, jimp_g[20] the friction impulses and the signed stop impulses; tau_last_g[10] takes the
-// saturated torque (what hb_plant_sense reports as the joint torque).
-template <class Ctx>
+// saturated torque (what hb_plant_sense reports as the joint torque).  HYBRID (hb_plant.hpp): `tau` is not read; the law is
+// evaluated and saturated into taua before every substep, tau_last / tau_applied are the last substep's and saturation bit 10 + j is set
+// if joint j was saturated in any substep.
+template <bool HYBRID = false, class Ctx>
 HB_HD void joints_step(const Ctx& cx, const DevModel& Mdl, double* q_g, double* v_g, double* imp_g, double* jimp_g, const double* tau,
                        const double* wrench, const int* all_on, const hb_contact_config& K, const hb_joint_model& Jm, double eps, double dt,
                        int substeps, double* lds, double* lambda_out, double* vdot_out, double* tau_last_g, const ContactOut& out,
-                       const JointOut& jout) {
+                       const JointOut& jout, const HybridActuator* actuator = nullptr) {
   double* q = lds + JointLds::q;
   double* v = lds + JointLds::v;
   double* imp = lds + JointLds::imp;
@@ -253,13 +255,25 @@ HB_HD void joints_step(const Ctx& cx, const DevModel& Mdl, double* q_g, double* 
   for (int i = cx.lane; i < 16; i += cx.nlanes) { q[i] = q_g[i]; v[i] = v_g[i]; }
   for (int i = cx.lane; i < 12; i += cx.nlanes) imp[i] = imp_g[i];
   for (int i = cx.lane; i < 20; i += cx.nlanes) imp[12 + i] = jimp_g[i];
-  if (cx.lane == 0) {
+  if constexpr (!HYBRID) {
+    if (cx.lane == 0) {
 #pragma unroll
-    for (int j = 0; j < HB_NJ; ++j) taua[j] = joint_saturate(tau[j], Jm.torque_limit[j]);
+      for (int j = 0; j < HB_NJ; ++j) taua[j] = joint_saturate(tau[j], Jm.torque_limit[j]);
+    }
   }
   cx.sync();
   const double h = dt / substeps;
-  for (int s = 0; s < substeps; ++s) joints_substep(cx, Mdl, q, v, wrench, all_on, K, Jm, eps, h, lds, vdot_out);
+  if constexpr (HYBRID) {
+    const HybridActuator& act = *actuator;
+    ActuatorAcc acc;
+    for (int s = 0; s < substeps; ++s) {
+      actuator_eval(cx, act, q, v, s, taua, acc, [&](int j, double ts) { return joint_saturate(ts, actuator_pick(Jm.torque_limit, j)); });
+      joints_substep(cx, Mdl, q, v, wrench, all_on, K, Jm, eps, h, lds, vdot_out);
+    }
+    actuator_finish(cx, act, substeps, acc, true);
+  } else {
+    for (int s = 0; s < substeps; ++s) joints_substep(cx, Mdl, q, v, wrench, all_on, K, Jm, eps, h, lds, vdot_out);
+  }
   // ---- outputs: as contact_step, then the joint arrays
   const double* Jc = lds + PlantJointLds::Jc;
   double* feet = lds + PlantJointLds::feet;
@@ -297,7 +311,8 @@ HB_HD void joints_step(const Ctx& cx, const DevModel& Mdl, double* q_g, double* 
     int js = 0;
     for (int j = 0; j < HB_NJ; ++j) {
       if (imp[22 + j] != 0.0) js |= 1 << j;              // (u = s p with p >= 0: nonzero exactly where the stop impulse is > 0)
-      if (taua[j] != tau[j]) js |= 1 << (10 + j);
+      if constexpr (HYBRID) { if (actuator->sat[j] != 0.0) js |= 1 << (10 + j); }
+      else { if (taua[j] != tau[j]) js |= 1 << (10 + j); }
     }
     if (!(jres <= Jm.tol)) js |= HB_JOINT_UNCONVERGED;
     jout.res[0] = jres;

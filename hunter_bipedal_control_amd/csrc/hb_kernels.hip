@@ -1014,6 +1014,83 @@ __global__ __launch_bounds__(64) void k_plant_joints(PlantBatch p, ContactBatch 
               all_on, K, J, p.eps, dt, substeps, lds, p.lambda + 12 * i, p.vdot + 16 * i, p.tau_last + 10 * i, out, jout);
   if (cx.lane == 0) plant_publish(p, M, i, dt, res_rbd, res_x0, res_t);
 }
+// ---- the hybrid forms of the three plant kernels (hb_plant_step_hybrid / hb_plant_step_lcm): the command's law per substep --------------
+// c: the five command arrays pos_des vel_des kp kd ff, [B][10] each; a: the record of the step.  tau_last takes the last substep's torque.
+struct ActuatorCmd {
+  const double* a[5];
+};
+// The lane context of the hybrid kernels: DeviceCtx under a name of its own, so that they instantiate plant_substep / contact_substep /
+// joints_substep for themselves.  A second caller of the instantiations the held-torque kernels use changes the code generated for
+// THOSE kernels (the inliner moves the body of a function into its only caller and clones it for several: other value order, other
+// register allocation — k_plant came out 800 instructions shorter), and their ISA is to stay what it is.
+struct ActuatorCtx : DeviceCtx {};
+__device__ __forceinline__ HybridActuator actuator_of(const ActuatorCmd& c, const ActuatorBatch& a, int i, double* lds_act) {
+  return HybridActuator{c.a[0] + 10 * i, c.a[1] + 10 * i, c.a[2] + 10 * i, c.a[3] + 10 * i, c.a[4] + 10 * i, a.tau_first + 10 * i, a.tau_mean + 10 * i,
+                        lds_act, lds_act + HB_NJ};
+}
+__global__ __launch_bounds__(64) void k_plant_hybrid(PlantBatch p, ActuatorBatch a, ActuatorCmd c, const DevModel* __restrict__ M, const int* contact,
+                                                      const int* mode, double dt, int substeps, double* res_rbd, double* res_x0, double* res_t) {
+  const int i = blockIdx.x;
+  __shared__ double lds[PLANT_LDS_TOTAL + ACT_LDS];
+  __shared__ int cflag[HB_NC];
+  const ActuatorCtx cx;
+  if (cx.lane < HB_NC) {
+    if (contact) cflag[cx.lane] = contact[4 * i + cx.lane];
+    else { bool cf[HB_NC]; mode_flags(mode[i], cf); cflag[cx.lane] = cf[cx.lane] ? 1 : 0; }
+  }
+  __syncthreads();
+  if (cx.lane < HB_NC) p.contact_last[4 * i + cx.lane] = cflag[cx.lane];
+  const HybridActuator act = actuator_of(c, a, i, lds + PLANT_LDS_TOTAL);
+  plant_step<true>(cx, *M, p.q + 16 * i, p.v + 16 * i, p.anchor + 12 * i, p.pinned + 4 * i, nullptr, cflag, p.baum, p.eps, dt, substeps, lds,
+                   p.lambda + 12 * i, p.vdot + 16 * i, &act);
+  if (cx.lane < HB_NJ) p.tau_last[10 * i + cx.lane] = act.tau[cx.lane];   // (the lane's own entry)
+  if (cx.lane == 0) plant_publish(p, M, i, dt, res_rbd, res_x0, res_t);
+}
+__global__ __launch_bounds__(64) void k_plant_contact_hybrid(PlantBatch p, ContactBatch cb, ActuatorBatch a, ActuatorCmd c, hb_contact_config K,
+                                                              const DevModel* __restrict__ M, const int* contact, const int* mode, double dt,
+                                                              int substeps, double* res_rbd, double* res_x0, double* res_t) {
+  const int i = blockIdx.x;
+  __shared__ double lds[CONTACT_LDS_TOTAL + ACT_LDS];
+  __shared__ int all_on[HB_NC];
+  const ActuatorCtx cx;
+  if (cx.lane < HB_NC) {
+    int flag;
+    if (contact) flag = contact[4 * i + cx.lane];
+    else { bool cf[HB_NC]; mode_flags(mode[i], cf); flag = cf[cx.lane] ? 1 : 0; }
+    p.contact_last[4 * i + cx.lane] = flag;
+    all_on[cx.lane] = 1;
+  }
+  __syncthreads();
+  const ContactOut out{cb.gap + 4 * i, cb.pvel + 12 * i, cb.res + i, cb.touching + 4 * i, cb.status + i};
+  const HybridActuator act = actuator_of(c, a, i, lds + CONTACT_LDS_TOTAL);
+  contact_step<true>(cx, *M, p.q + 16 * i, p.v + 16 * i, cb.imp + 12 * i, nullptr, cb.use_wrench ? cb.wrench + 6 * i : nullptr, all_on, K, p.eps, dt,
+                     substeps, lds, p.lambda + 12 * i, p.vdot + 16 * i, out, &act);
+  if (cx.lane < HB_NJ) p.tau_last[10 * i + cx.lane] = act.tau[cx.lane];   // (the lane's own entry)
+  if (cx.lane == 0) plant_publish(p, M, i, dt, res_rbd, res_x0, res_t);
+}
+__global__ __launch_bounds__(64) void k_plant_joints_hybrid(PlantBatch p, ContactBatch cb, JointBatch jb, ActuatorBatch a, ActuatorCmd c,
+                                                             hb_contact_config K, hb_joint_model J, const DevModel* __restrict__ M, const int* contact,
+                                                             const int* mode, double dt, int substeps, double* res_rbd, double* res_x0,
+                                                             double* res_t) {
+  const int i = blockIdx.x;
+  __shared__ double lds[JOINT_LDS_TOTAL + ACT_LDS];
+  __shared__ int all_on[HB_NC];
+  const ActuatorCtx cx;
+  if (cx.lane < HB_NC) {
+    int flag;
+    if (contact) flag = contact[4 * i + cx.lane];
+    else { bool cf[HB_NC]; mode_flags(mode[i], cf); flag = cf[cx.lane] ? 1 : 0; }
+    p.contact_last[4 * i + cx.lane] = flag;
+    all_on[cx.lane] = 1;
+  }
+  __syncthreads();
+  const ContactOut out{cb.gap + 4 * i, cb.pvel + 12 * i, cb.res + i, cb.touching + 4 * i, cb.status + i};
+  const JointOut jout{jb.tau_applied + 10 * i, jb.friction_torque + 10 * i, jb.limit_torque + 10 * i, jb.res + i, jb.status + i};
+  const HybridActuator act = actuator_of(c, a, i, lds + JOINT_LDS_TOTAL);
+  joints_step<true>(cx, *M, p.q + 16 * i, p.v + 16 * i, cb.imp + 12 * i, jb.imp + 20 * i, nullptr, cb.use_wrench ? cb.wrench + 6 * i : nullptr, all_on, K,
+                    J, p.eps, dt, substeps, lds, p.lambda + 12 * i, p.vdot + 16 * i, p.tau_last + 10 * i, out, jout, &act);
+  if (cx.lane == 0) plant_publish(p, M, i, dt, res_rbd, res_x0, res_t);
+}
 __global__ void k_plant_reset(PlantBatch p, const DevModel* __restrict__ M) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= p.B) return;

@@ -160,6 +160,25 @@ constexpr void fields(JointBatch& j, size_t, F&& f) {
   HB_FIELD(j.status, 1);
 }
 
+// actuator loop of the plant and the simulator end of the LCM link (hb_plant_step_hybrid, hb_plant_step_lcm, hb_plant_sense_lcm),
+// allocated on the first call that needs them — the held-torque path needs none: the record of the last hybrid step, the staging of a
+// host command and the received command (pos_des vel_des kp kd ff, one array each), the timestamp filter, the wire images
+struct ActuatorBatch {
+  int B;
+  double *tau_first, *tau_mean;
+  double *cmd[5], *rcmd[5];
+  uint64_t* last_ts;
+  int* accepted;
+  uint64_t *wire_cmd, *wire_low, *wire_full;   // low_cmd_t in, low_state_t / full_state_t out, 8-byte words
+};
+template <class F>
+constexpr void fields(ActuatorBatch& a, size_t, F&& f) {
+  HB_FIELD(a.tau_first, 10); HB_FIELD(a.tau_mean, 10);
+  HB_FIELD(a.cmd[0], 10); HB_FIELD(a.cmd[1], 10); HB_FIELD(a.cmd[2], 10); HB_FIELD(a.cmd[3], 10); HB_FIELD(a.cmd[4], 10);
+  HB_FIELD(a.rcmd[0], 10); HB_FIELD(a.rcmd[1], 10); HB_FIELD(a.rcmd[2], 10); HB_FIELD(a.rcmd[3], 10); HB_FIELD(a.rcmd[4], 10);
+  HB_FIELD(a.last_ts, 1); HB_FIELD(a.accepted, 1); HB_FIELD(a.wire_cmd, 62); HB_FIELD(a.wire_low, 42); HB_FIELD(a.wire_full, 58);
+}
+
 // ---- reference generation ----------------------------------------------------------------------------------------------
 struct RefgenBatch {
   int B;
@@ -249,6 +268,7 @@ static_assert(sizeof(PlantBatch) == kPtr /*B*/ + 2 * sizeof(double) + (n_fields<
               "describe every array of PlantBatch in fields()");
 static_assert(sizeof(ContactBatch) == 2 * sizeof(int) + n_fields<ContactBatch>() * kPtr, "describe every array of ContactBatch in fields()");
 static_assert(sizeof(JointBatch) == kPtr /*B*/ + n_fields<JointBatch>() * kPtr, "describe every array of JointBatch in fields()");
+static_assert(sizeof(ActuatorBatch) == kPtr /*B*/ + n_fields<ActuatorBatch>() * kPtr, "describe every array of ActuatorBatch in fields()");
 static_assert(sizeof(RefgenBatch) == kPtr /*B*/ + n_fields<RefgenBatch>() * kPtr + kPtr /*init_stance*/, "describe every array of RefgenBatch in fields()");
 static_assert(sizeof(GaitBatch) == 2 * sizeof(int) + n_fields<GaitBatch>() * kPtr, "describe every array of GaitBatch in fields()");
 static_assert(sizeof(EstBatch) == kPtr /*B*/ + (n_fields<EstBatch>() + 2 /*res_rbd, res_x0*/) * kPtr, "describe every array of EstBatch in fields()");

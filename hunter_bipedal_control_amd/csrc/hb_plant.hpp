@@ -39,6 +39,73 @@ struct PlantJointLds {
 template <int FRONT> struct PlantLdsOf { using type = PlantLds; };
 template <> struct PlantLdsOf<2> { using type = PlantJointLds; };
 
+// ---- the actuator of a step: a compile-time switch of plant_step / contact_step (hb_contact.hpp) / joints_step (hb_joints.hpp) ---------
+// HYBRID = false: the caller's torque, held over every substep (hb_plant_step).  HYBRID = true: `actuator` is the instance's hybrid command; the law
+//     tau_s[j] = ff[j] + kp[j] (pos[j] - q_s[6 + j]) + kd[j] (vel[j] - v_s[6 + j])        (operand order of k_joint_command)
+// is evaluated before every substep from the staged (q, v) by the lanes j < 10 into tau[10] (LDS), which the substep routine takes as
+// its torque (hb_plant_step_hybrid; the reference's simulator does the same per simulator step, mujoco/src/main.cc:243-249).  The five
+// command values are re-read from global memory per substep, not kept live across the sweeps.
+struct HybridActuator {
+  const double *pos, *vel, *kp, *kd, *ff;   // [10] each, of the instance (global)
+  double *tau_first, *tau_mean;             // [10] each, of the instance (global): tau_0 before saturation | mean of the torque integrated
+  double* tau;                              // [10] LDS: tau_s
+  double* sat;                              // [10] LDS (joint model only): != 0 where the joint was saturated in any substep
+};
+constexpr int ACT_LDS = 20;                 // tau | sat, behind a form's own LDS
+// A lane's record of a hybrid step: lane j < 10 owns joint j; the one emulated lane of the host build owns all ten.
+#if defined(__HIP_DEVICE_COMPILE__)
+constexpr int ACT_SLOTS = 1;
+#else
+constexpr int ACT_SLOTS = HB_NJ;
+#endif
+struct ActuatorAcc {
+  double sum[ACT_SLOTS];
+  bool sat[ACT_SLOTS];
+};
+// f(joint, slot) for the joints the lane owns
+template <class Ctx, class F>
+HB_HD void actuator_joints(const Ctx& cx, F&& f) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  if (cx.lane < HB_NJ) f(cx.lane, 0);
+#else
+  (void)cx;
+  for (int j = 0; j < HB_NJ; ++j) f(j, j);
+#endif
+}
+// a[j] of a ten-entry array that lives in registers (a kernel argument): selected, never indexed by the lane
+HB_HD double actuator_pick(const double (&a)[HB_NJ], int j) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  double x = a[0];
+#pragma unroll
+  for (int k = 1; k < HB_NJ; ++k) x = j == k ? a[k] : x;
+  return x;
+#else
+  return a[j];
+#endif
+}
+// Before substep s: the law into out[10] (LDS; a.tau, or the joint model's saturated torque) through saturate(joint, tau_s) -> the torque
+// the substep integrates.  The substep's first barrier publishes it.
+template <class Ctx, class Sat>
+HB_HD void actuator_eval(const Ctx& cx, const HybridActuator& a, const double* q, const double* v, int s, double* out, ActuatorAcc& acc,
+                         Sat&& saturate) {
+  actuator_joints(cx, [&](int j, int k) {
+    const double ts = a.ff[j] + a.kp[j] * (a.pos[j] - q[6 + j]) + a.kd[j] * (a.vel[j] - v[6 + j]);
+    const double ti = saturate(j, ts);
+    if (s == 0) a.tau_first[j] = ts;
+    acc.sum[k] = s == 0 ? ti : acc.sum[k] + ti;
+    acc.sat[k] = (s != 0 && acc.sat[k]) || ti != ts;
+    out[j] = ti;
+  });
+}
+// After the last substep: the mean, and the saturation record where the form keeps one (a barrier of the caller publishes it).
+template <class Ctx>
+HB_HD void actuator_finish(const Ctx& cx, const HybridActuator& a, int substeps, const ActuatorAcc& acc, bool record_sat) {
+  actuator_joints(cx, [&](int j, int k) {
+    a.tau_mean[j] = acc.sum[k] / substeps;
+    if (record_sat) a.sat[j] = acc.sat[k] ? 1.0 : 0.0;
+  });
+}
+
 // One substep of length h.  q[16], v[16], anchor[12] in/out (global or LDS); rows[12] = 1 for pinned contact rows.
 // FRONT = 1: the front half alone, for the ground-contact model (hb_contact.hpp) — the rigid-body terms at (q, v), the Cholesky factor
 // of M, X = M^-1 [rhs | Jc'] with rhs = S' tau - nle (+ wext[16], a generalised force, when one is given) and Jc M^-1 Jc' are left in LDS
@@ -200,10 +267,11 @@ HB_HD void plant_feet(const DevModel& Mdl, const double* q, double* feet12) {
 
 // One plant tick of one instance: re-anchor the feet whose contact phase starts, `substeps` substeps of dt / substeps.
 // State (q, v, anchor, pinned) lives in global memory; q / v are staged in LDS behind `lds`.
-template <class Ctx>
+// HYBRID: `tau` is not read; the law's torque of every substep is (see above).
+template <bool HYBRID = false, class Ctx>
 HB_HD void plant_step(const Ctx& cx, const DevModel& Mdl, double* q_g, double* v_g, double* anchor_g, int* pinned_g, const double* tau,
                       const int* contact, double baum, double eps, double dt, int substeps, double* lds, double* lambda_out,
-                      double* vdot_out) {
+                      double* vdot_out, const HybridActuator* actuator = nullptr) {
   double* q = lds + PlantLds::total;
   double* v = q + 16;
   double* anchor = v + 16;
@@ -221,7 +289,17 @@ HB_HD void plant_step(const Ctx& cx, const DevModel& Mdl, double* q_g, double* v
   }
   cx.sync();
   const double h = dt / substeps;
-  for (int s = 0; s < substeps; ++s) plant_substep(cx, Mdl, q, v, tau, contact, anchor, baum, eps, h, lds, lambda_out, vdot_out);
+  if constexpr (HYBRID) {
+    const HybridActuator& act = *actuator;
+    ActuatorAcc acc;
+    for (int s = 0; s < substeps; ++s) {
+      actuator_eval(cx, act, q, v, s, act.tau, acc, [](int, double ts) { return ts; });
+      plant_substep(cx, Mdl, q, v, act.tau, contact, anchor, baum, eps, h, lds, lambda_out, vdot_out);
+    }
+    actuator_finish(cx, act, substeps, acc, false);
+  } else {
+    for (int s = 0; s < substeps; ++s) plant_substep(cx, Mdl, q, v, tau, contact, anchor, baum, eps, h, lds, lambda_out, vdot_out);
+  }
   for (int i = cx.lane; i < 16; i += cx.nlanes) { q_g[i] = q[i]; v_g[i] = v[i]; }
   for (int i = cx.lane; i < 12; i += cx.nlanes) anchor_g[i] = anchor[i];
   cx.sync();

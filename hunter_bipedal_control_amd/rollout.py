@@ -141,7 +141,7 @@ class ResidentLoop:
     def __init__(self, solver, params: dict, gaits, cmd_vel, n_intervals: int = 100, mpc_every: int = 8, dt: float = 0.002,
                  t_gait_start: float = 0.3, joint_ik: bool = True, substeps: int = 4, static_schedule_until: float = 0.0,
                  device_gait: bool = False, use_estimator: bool = False, sensor_config=None, sensor_bias=None, contact_config=None,
-                 joint_model=None):
+                 joint_model=None, actuator: str = "held"):
         """static_schedule_until > 0: the mode schedules are uploaded once for [-1, static_schedule_until] (at most
         HB_MAX_EVENTS events) instead of a sliding window per MPC call — no per-call host work for large batches.
         device_gait: the device gait manager produces the windows; step() builds no per-instance list and uploads no schedule, and
@@ -151,7 +151,13 @@ class ResidentLoop:
         ground with unilateral frictional contact, the plane under the lowest contact point of the start unless ground_z is among them;
         an abi.HbContactConfig is taken as it is.
         joint_model: the joint model of the ground-contact plant — None: ideal joints; a dict of abi.make_joint_model fields ({} = the
-        joints of the reference's MuJoCo model); an abi.HbJointModel is taken as it is.  Needs contact_config."""
+        joints of the reference's MuJoCo model); an abi.HbJointModel is taken as it is.  Needs contact_config.
+        actuator: "held" — the torque of the joint command is held over the tick (hb_plant_step); "substep" — the plant evaluates the
+        command's law ff + kp (pos_des - q) + kd (vel_des - qd) before every substep from its own state (hb_plant_step_hybrid on the
+        device-resident command), as the reference's simulator does per simulator step (mujoco/src/main.cc:243-249)."""
+        if actuator not in ("held", "substep"):
+            raise ValueError('actuator is "held" or "substep"')
+        self.actuator = actuator
         if joint_model is not None and contact_config is None:
             raise ValueError("joint_model belongs to the ground-contact plant: give contact_config as well")
         self.s, self.params, self.B = solver, params, solver.B
@@ -244,6 +250,9 @@ class ResidentLoop:
         else:
             s.wbc_update_resident(self.dt)
             s.joint_command_resident(self.gains, self.dt)
-        s.plant_step(None, None, self.dt, self.substeps, to_resident=not self.use_estimator)
+        if self.actuator == "substep":
+            s.plant_step_hybrid(None, None, self.dt, self.substeps, to_resident=not self.use_estimator)
+        else:
+            s.plant_step(None, None, self.dt, self.substeps, to_resident=not self.use_estimator)
         self.t += self.dt
         self.tick += 1

@@ -33,11 +33,11 @@ ABI_SYMBOLS = [
     "hb_refgen_get_schedule", "hb_gait_reset", "hb_gait_disable", "hb_gait_insert_template", "hb_gait_get_state",
     "hb_plant_set_sensor_model", "hb_plant_sense", "hb_estimator_update_resident", "hb_estimator_contact_force_resident",
     "hb_plant_set_contact_model", "hb_plant_set_external_wrench", "hb_plant_get_contact",
-    "hb_plant_set_joint_model", "hb_plant_get_joints",
+    "hb_plant_set_joint_model", "hb_plant_get_joints", "hb_plant_step_hybrid", "hb_plant_get_actuator",
 ]
 # include/hunter_lcm.h
 LCM_SYMBOLS = ["hb_lcm_fingerprint", "hb_lcm_encoded_size", "hb_lcm_field_count", "hb_lcm_encode", "hb_lcm_decode", "hb_lcm_frame", "hb_lcm_unframe",
-               "hb_joint_command_lcm", "hb_estimator_update_lcm"]
+               "hb_joint_command_lcm", "hb_estimator_update_lcm", "hb_plant_step_lcm", "hb_plant_sense_lcm"]
 
 
 LCM_LOW_CMD, LCM_LOW_STATE, LCM_FULL_STATE = 0, 1, 2
@@ -244,6 +244,43 @@ class HunterSolver:
         contact = None if contact is None else _i32(contact, (self.B, 4))
         self._check(self.lib.hb_plant_step(self.ctx, _p(tau), _p(contact), C.c_double(dt), C.c_int32(substeps), C.c_int32(1 if to_resident else 0)),
                     "hb_plant_step")
+
+    # ---- actuator loop per substep (hb_plant_step_hybrid) and the simulator end of the LCM link ---------------------------------
+    def plant_step_hybrid(self, command=None, contact=None, dt=0.002, substeps=4, to_resident=False):
+        """A hybrid step: the law ff + kp (pos_des - q) + kd (vel_des - qd) evaluated before every substep from the plant's own state.
+        command: dict(pos_des, vel_des, kp, kd, tau_ff) of [B][10] arrays (what joint_command returns), or None for the command the
+        last joint_command left on the device.  A missing key is passed as NULL (the library refuses a partly given command)."""
+        keys = ("pos_des", "vel_des", "kp", "kd", "tau_ff")
+        arrs = [None] * 5 if command is None else [None if command.get(k) is None else _f64(command[k], (self.B, 10)) for k in keys]
+        contact = None if contact is None else _i32(contact, (self.B, 4))
+        self._check(self.lib.hb_plant_step_hybrid(self.ctx, *[_p(a) for a in arrs], _p(contact), C.c_double(dt), C.c_int32(substeps),
+                                                  C.c_int32(1 if to_resident else 0)), "hb_plant_step_hybrid")
+
+    def plant_step_lcm(self, low_cmd, contact=None, dt=0.002, substeps=4, to_resident=False):
+        """hb_plant_step_lcm: low_cmd[B][496] wire images of low_cmd_t through the simulator's timestamp filter, then a hybrid step on the
+        received commands -> accepted[B] int32."""
+        wire = np.ascontiguousarray(low_cmd, dtype=np.uint8)
+        assert wire.shape == (self.B, 496)
+        contact = None if contact is None else _i32(contact, (self.B, 4))
+        accepted = np.zeros(self.B, dtype=np.int32)
+        self._check(self.lib.hb_plant_step_lcm(self.ctx, _p(wire), _p(contact), C.c_double(dt), C.c_int32(substeps),
+                                               C.c_int32(1 if to_resident else 0), _p(accepted)), "hb_plant_step_lcm")
+        return accepted
+
+    def plant_sense_lcm(self, timestamp_ns: int, low_state=True, full_state=True):
+        """hb_plant_sense_lcm: one plant_sense, packed on the device -> (low_state_t wire images [B][336] or None, full_state_t [B][464] or
+        None)."""
+        low = np.zeros((self.B, 336), dtype=np.uint8) if low_state else None
+        full = np.zeros((self.B, 464), dtype=np.uint8) if full_state else None
+        self._check(self.lib.hb_plant_sense_lcm(self.ctx, C.c_int64(timestamp_ns), _p(low), _p(full)), "hb_plant_sense_lcm")
+        return low, full
+
+    def plant_get_actuator(self):
+        """-> dict(tau_first[B][10], tau_mean[B][10] of the last hybrid step, last_timestamp[B] int64: the stored bits of the timestamp
+        filter of plant_step_lcm)."""
+        out = dict(tau_first=np.zeros((self.B, 10)), tau_mean=np.zeros((self.B, 10)), last_timestamp=np.zeros(self.B, dtype=np.int64))
+        self._check(self.lib.hb_plant_get_actuator(self.ctx, *[_p(a) for a in out.values()]), "hb_plant_get_actuator")
+        return out
 
     def plant_state(self):
         out = dict(q=np.zeros((self.B, 16)), v=np.zeros((self.B, 16)), rbd=np.zeros((self.B, 32)), lam=np.zeros((self.B, 12)),

@@ -326,7 +326,8 @@ int32_t hb_plant_get_contact(hb_ctx* ctx, double* gap, double* point_vel, double
  *     coordinates: >= 0 at a lower stop, <= 0 at an upper one); the joint residual; a status word: bit j = the stop impulse of joint j in
  *     the last substep is > 0, bit 10 + j = tau_a[j] != tau[j], HB_JOINT_UNCONVERGED = joint residual > tol.  The joint_torque of
  *     hb_plant_sense becomes tau_a, the torque the step integrated.
- * The commanded torque stays held over a tick (the reference's simulator evaluates its PD law per simulator step, mujoco/src/main.cc:247). */
+ * hb_plant_step holds the commanded torque over the tick; hb_plant_step_hybrid (below) evaluates the hybrid command's law per substep,
+ * as the reference's simulator does per simulator step (mujoco/src/main.cc:243-249). */
 #define HB_JOINT_UNCONVERGED (1 << 30)
 typedef struct hb_joint_model {
   double armature[10];      /* kg m^2, >= 0: added to the joint diagonal of M */
@@ -349,6 +350,29 @@ int32_t hb_plant_set_joint_model(hb_ctx* ctx, const hb_joint_model* model);
  * hb_plant_reset or outside contact model 1. */
 int32_t hb_plant_get_joints(hb_ctx* ctx, double* tau_applied, double* friction_torque, double* limit_torque, double* residual,
                             int32_t* status);
+
+/* ---- hybrid step: the actuator loop per substep --------------------------------------------------------------------------------
+ * The reference's controller does not send a torque but the hybrid command (joint_pos, joint_vel, kp, kd, ff_tau), and its simulator turns
+ * it into a torque inside every simulator step from the simulator's own joint state (mujoco/src/main.cc:243-249).  An instance has a
+ * hybrid command (pos_des, vel_des, kp, kd, ff)[10].  A hybrid step of `substeps` substeps of length h = dt / substeps evaluates
+ *     tau_s[j] = ff[j] + kp[j] (pos_des[j] - q_s[6 + j]) + kd[j] (vel_des[j] - v_s[6 + j])
+ * at the start of every substep s from the plant's own (q_s, v_s) (operand order of hb_joint_command's torque), and tau_s is used
+ * wherever that substep of hb_plant_step uses tau: the right-hand side S' tau_s - nle (+ w) of the pinned stub and of contact model 1;
+ * with the joint model tau_a = clamp(tau_s, +-torque_limit) is taken every substep.  The law is explicit (MuJoCo's Euler integrator is
+ * implicit in the joint damping only, not in actuator terms; hunter.xml sets neither timestep nor integrator, so the reference runs the
+ * law once per 2 ms simulator step: substeps = 1, dt = 0.002 is that rate, more substeps are finer).  Contact flags as in hb_plant_step.
+ * Outputs: the torque hb_plant_sense reports and tau_applied of hb_plant_get_joints are those of the LAST substep (saturated under the
+ * joint model); bit 10 + j of the joint status word is set if joint j was saturated in ANY substep of the step; tau_first[batch][10] =
+ * tau_0 before saturation and tau_mean[batch][10] = the mean over the substeps of the torque integrated (tau_a with the joint model,
+ * else tau_s) describe the last hybrid step: zero after hb_plant_reset, untouched by hb_plant_step.
+ * The five arrays are host [batch][10].  All five NULL: the command of the last hb_joint_command is used where it lies on the device
+ * (HB_ERR_STATE if there is none); some but not all NULL: HB_ERR_ARG.  contact / dt / substeps / to_resident and the state checks as for
+ * hb_plant_step.  Runs on whichever plant form is in force.  Does not touch the received LCM command (hunter_lcm.h) or its timestamps. */
+int32_t hb_plant_step_hybrid(hb_ctx* ctx, const double* pos_des, const double* vel_des, const double* kp, const double* kd,
+                             const double* tau_ff, const int32_t* contact, double dt, int32_t substeps, int32_t to_resident);
+/* tau_first / tau_mean [batch][10] of the last hybrid step and last_timestamp[batch] = the stored bits of the simulator end's timestamp
+ * filter (hunter_lcm.h hb_plant_step_lcm); any may be NULL.  HB_ERR_STATE before hb_plant_reset. */
+int32_t hb_plant_get_actuator(hb_ctx* ctx, double* tau_first, double* tau_mean, int64_t* last_timestamp);
 
 /* ---- sensors from the plant: what LeggedController::updateStateEstimation reads, computed on the device -----------
  * hb_plant_sense turns the plant's state into the sensor arrays of hb_estimator_update and leaves them on the device

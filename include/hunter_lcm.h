@@ -63,6 +63,30 @@ int32_t hb_joint_command_lcm(hb_ctx* ctx, const hb_joint_gains* gains, double dt
 int32_t hb_estimator_update_lcm(hb_ctx* ctx, double dt, const uint8_t* low_state, const int32_t* contact_flag,
                                 int32_t to_resident, double* rbd, double* x_state, int64_t* timestamp);
 
+/* ---- the simulator end of the link: the batched plant in the role of the reference's MuJoCo node -----------------------------------
+ * Per instance the plant keeps a received command and a uint64 last_timestamp, both zero after hb_plant_reset: init_cmd,
+ * mujoco/src/main.cc:251-260, and mujoco/include/lcm_interface/LcmInterface.h:24.
+ * hb_plant_step_lcm = MujocoLcm::HandleLowCmd (LcmInterface.cpp:23-33) followed by a hybrid step (hunter_hip.h hb_plant_step_hybrid:
+ * mycontroller, main.cc:243-249, per substep) on the received commands.  low_cmd[batch][496] (host) is unpacked on the device; a message
+ * replaces its instance's command if and only if (uint64) timestamp > last_timestamp — the unsigned comparison of LcmInterface.cpp:27,
+ * so a negative stamp is accepted — and last_timestamp takes its stamp; otherwise the instance keeps the command it has.  The message's
+ * joint_torque member is ignored, as the reference's callback ignores it.  accepted[batch] (optional) receives 1 / 0 per instance.
+ * contact / dt / substeps / to_resident and the state checks as for hb_plant_step.  A foreign fingerprint in any message returns
+ * HB_ERR_ARG and nothing changes: no command, no timestamp, no step. */
+int32_t hb_plant_step_lcm(hb_ctx* ctx, const uint8_t* low_cmd, const int32_t* contact, double dt, int32_t substeps, int32_t to_resident,
+                          int32_t* accepted);
+/* hb_plant_sense_lcm = exactly one hb_plant_sense — sensor model and noise as configured, sense_count advances once, the sensor arrays
+ * stay on the device for hb_estimator_update_resident — followed by the packing of MujocoLcm::SetSend (LcmInterface.cpp:45-104) on the
+ * device; low_state[batch][336] / full_state[batch][464] (host), either may be NULL, not both (HB_ERR_ARG).  Both timestamps are
+ * timestamp_ns.
+ *   low_state_t (:52-71), from the SENSED values: quaternion (w x y z), accelerometer, gyroscope, joint_pos, joint_vel, and
+ *     joint_torque = the sensed joint torque.  This is the one deliberate difference: the reference sends qfrc_applied[0..9], which is
+ *     zero in its runs, and LeggedMujocoSim::read never reads the member.
+ *   full_state_t (:78-100), ground truth without noise or bias: quaternion (w x y z), gyroscope = base angular velocity in the base
+ *     frame, position = q[0:3], velocity = v[0:3], joint_pos / joint_vel / joint_torque [12] with entries 0-9 filled (joint_torque = the
+ *     torque the last step integrated) and 10-11 zero; accelerometer and foot_force zero (the reference never assigns them). */
+int32_t hb_plant_sense_lcm(hb_ctx* ctx, int64_t timestamp_ns, uint8_t* low_state, uint8_t* full_state);
+
 #ifdef __cplusplus
 }
 #endif
