@@ -101,6 +101,11 @@ struct hb_ctx {
   JointBatch joints{};
   hb_joint_model joint_model{};
   bool joints_on = false;
+  // per-instance terrain of contact model 1 (hb_plant_set_terrain): terrain_on while one is in force (the step calls then launch the
+  // terrain kernels); the array is allocated on first use, terrain_host is its host image ([B][Terrain::size], what hb_plant_get_terrain reports)
+  TerrainBatch terrain{};
+  std::vector<double> terrain_host;
+  bool terrain_on = false;
   // actuator loop per substep and the simulator end of the LCM link (hb_plant_step_hybrid / _lcm, hb_plant_sense_lcm): allocated on first use
   ActuatorBatch act{};
   // reference generation (allocated on the first hb_refgen_reset)

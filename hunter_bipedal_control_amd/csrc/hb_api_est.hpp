@@ -129,6 +129,18 @@ int32_t hb_plant_step(hb_ctx* ctx, const double* tau, const int32_t* contact, do
   HB_TRY(push(ctx, contact, p, p.contact, whole(ctx), &s));
   const double* dtau = tau ? p.tau : ctx->jc_out + 5 * B * HB_NJ;
   // the resident observation feeds the next hb_mpc_solve(NULL) / hb_refgen_update(NULL) on the MPC stream
+  if (ctx->contact_cfg.mode == 1 && ctx->terrain_on && ctx->joints_on)
+    return resident_write(ctx, s, to_resident, [&] {
+      hipLaunchKernelGGL(k_plant_terrain_joints, dim3(ctx->B), dim3(64), 0, s, p, ctx->contact, ctx->joints, ctx->terrain.ter, ctx->contact_cfg,
+                         ctx->joint_model, ctx->dmodel, dtau, contact ? p.contact : nullptr, ctx->w.mode, dt, substeps,
+                         to_resident ? ctx->w.rbd : nullptr, to_resident ? ctx->b.x0 : nullptr, to_resident ? ctx->w.t_now : nullptr);
+    });
+  if (ctx->contact_cfg.mode == 1 && ctx->terrain_on)
+    return resident_write(ctx, s, to_resident, [&] {
+      hipLaunchKernelGGL(k_plant_terrain, dim3(ctx->B), dim3(64), 0, s, p, ctx->contact, ctx->terrain.ter, ctx->contact_cfg, ctx->dmodel, dtau,
+                         contact ? p.contact : nullptr, ctx->w.mode, dt, substeps, to_resident ? ctx->w.rbd : nullptr,
+                         to_resident ? ctx->b.x0 : nullptr, to_resident ? ctx->w.t_now : nullptr);
+    });
   if (ctx->contact_cfg.mode == 1 && ctx->joints_on)
     return resident_write(ctx, s, to_resident, [&] {
       hipLaunchKernelGGL(k_plant_joints, dim3(ctx->B), dim3(64), 0, s, p, ctx->contact, ctx->joints, ctx->contact_cfg, ctx->joint_model, ctx->dmodel, dtau,
@@ -168,6 +180,16 @@ static int32_t plant_launch_hybrid(hb_ctx* ctx, const double* const cmd[5], cons
   double* rr = to_resident ? ctx->w.rbd : nullptr;
   double* rx = to_resident ? ctx->b.x0 : nullptr;
   double* rt = to_resident ? ctx->w.t_now : nullptr;
+  if (ctx->contact_cfg.mode == 1 && ctx->terrain_on && ctx->joints_on)
+    return resident_write(ctx, s, to_resident, [&] {
+      hipLaunchKernelGGL(k_plant_terrain_joints_hybrid, dim3(ctx->B), dim3(64), 0, s, p, ctx->contact, ctx->joints, ctx->terrain.ter, ctx->act, c,
+                         ctx->contact_cfg, ctx->joint_model, ctx->dmodel, dcontact, ctx->w.mode, dt, substeps, rr, rx, rt);
+    });
+  if (ctx->contact_cfg.mode == 1 && ctx->terrain_on)
+    return resident_write(ctx, s, to_resident, [&] {
+      hipLaunchKernelGGL(k_plant_terrain_hybrid, dim3(ctx->B), dim3(64), 0, s, p, ctx->contact, ctx->terrain.ter, ctx->act, c, ctx->contact_cfg,
+                         ctx->dmodel, dcontact, ctx->w.mode, dt, substeps, rr, rx, rt);
+    });
   if (ctx->contact_cfg.mode == 1 && ctx->joints_on)
     return resident_write(ctx, s, to_resident, [&] {
       hipLaunchKernelGGL(k_plant_joints_hybrid, dim3(ctx->B), dim3(64), 0, s, p, ctx->contact, ctx->joints, ctx->act, c, ctx->contact_cfg, ctx->joint_model,
@@ -250,6 +272,7 @@ int32_t hb_plant_set_contact_model(hb_ctx* ctx, const hb_contact_config* cfg) {
     HB_HIP(hipMemsetAsync(p.pinned, 0, field_count(ctx, p, p.pinned) * sizeof(int), ctx->s_wbc));
   }
   ctx->contact_cfg = ground ? *cfg : hb_contact_config{};
+  if (!ground) ctx->terrain_on = false;   // the terrain belongs to contact model 1
   if (!ground && ctx->joints_on) {   // the joint model belongs to contact model 1
     ctx->joints_on = false;
     HB_TRY(joints_clear(ctx, ctx->s_wbc));
@@ -328,6 +351,79 @@ int32_t hb_plant_get_joints(hb_ctx* ctx, double* tau_applied, double* friction_t
   HB_TRY(pull(ctx, limit_torque, j, j.limit_torque, whole(ctx)));
   HB_TRY(pull(ctx, residual, j, j.res, whole(ctx)));
   HB_TRY(pull(ctx, status, j, j.status, whole(ctx)));
+  return HB_OK;
+}
+
+// ---- per-instance terrain of contact model 1 (include/hunter_hip.h above hb_plant_set_terrain) ----------------------------------------
+// The frame of a unit normal n: t1 = (e_x - n_x n) / |e_x - n_x n|, t2 = n x t1, T = [t1 t2 n] row-major; the identity exactly for n = e_z.
+static void terrain_frame(const double n[3], double* T) {
+  double t1[3] = {1.0 - n[0] * n[0], -n[0] * n[1], -n[0] * n[2]};
+  const double l = std::sqrt(t1[0] * t1[0] + t1[1] * t1[1] + t1[2] * t1[2]);
+  for (double& x : t1) x /= l;
+  const double t2[3] = {n[1] * t1[2] - n[2] * t1[1], n[2] * t1[0] - n[0] * t1[2], n[0] * t1[1] - n[1] * t1[0]};
+  for (int a = 0; a < 3; ++a) { T[3 * a] = t1[a]; T[3 * a + 1] = t2[a]; T[3 * a + 2] = n[a]; }
+}
+
+int32_t hb_plant_set_terrain(hb_ctx* ctx, const double* plane, const double* mu) {
+  HB_ENTER_ARGS(false);
+  HB_TRY(contact_ready(ctx, "hb_plant_set_terrain"));
+  const size_t B = ctx->B;
+  std::vector<double> rec(B * Terrain::size);
+  for (size_t i = 0; i < B && (plane || mu); ++i) {
+    double* r = rec.data() + i * Terrain::size;
+    double n[3] = {0.0, 0.0, 1.0}, d = ctx->contact_cfg.ground_z;
+    const char* why = nullptr;
+    if (plane) {
+      const double* pl = plane + 4 * i;
+      const double len = std::sqrt(pl[0] * pl[0] + pl[1] * pl[1] + pl[2] * pl[2]);
+      if (!(std::isfinite(pl[0]) && std::isfinite(pl[1]) && std::isfinite(pl[2]) && std::isfinite(pl[3]))) why = "a non-finite plane entry";
+      else if (!(std::fabs(len - 1.0) <= 1e-9)) why = "a normal that is not of unit length (| |n| - 1 | > 1e-9)";
+      else if (!(pl[2] / len >= 0.5)) why = "n_z < 0.5";
+      for (int a = 0; a < 3; ++a) n[a] = pl[a] / len;
+      d = pl[3];
+    }
+    for (int c = 0; c < HB_NC && !why; ++c) {
+      const double m = mu ? mu[4 * i + c] : ctx->contact_cfg.mu;
+      if (!(std::isfinite(m) && m >= 0.0)) why = "a friction coefficient that is negative or not finite";
+      r[Terrain::mu + c] = m;
+    }
+    if (why) {
+      ctx->err = "hb_plant_set_terrain: instance " + std::to_string(i) + " has " + why + " (the terrain in force is kept)";
+      return HB_ERR_ARG;
+    }
+    terrain_frame(n, r + Terrain::T);
+    r[Terrain::d] = d;
+  }
+  HB_ENTER_DEVICE();
+  HB_HIP(hipStreamSynchronize(ctx->s_wbc));  // (a step in flight still runs on the terrain it was launched with)
+  ContactBatch& c = ctx->contact;
+  if (plane || mu) {
+    TerrainBatch& t = ctx->terrain;
+    if (!t.ter) {
+      HB_HIP(alloc_fields(ctx, t));
+      t.B = ctx->B;
+    }
+    HB_TRY(push(ctx, rec.data(), t, t.ter, whole(ctx)));
+    ctx->terrain_host = std::move(rec);
+  }
+  ctx->terrain_on = plane || mu;
+  // the warm start is expressed in the frame of before
+  HB_HIP(hipMemsetAsync(c.imp, 0, field_count(ctx, c, c.imp) * 8, ctx->s_wbc));
+  HB_HIP(hipStreamSynchronize(ctx->s_wbc));
+  return HB_OK;
+}
+
+int32_t hb_plant_get_terrain(hb_ctx* ctx, double* plane, double* mu, double* frame) {
+  HB_ENTER_ARGS(false);
+  HB_TRY(contact_ready(ctx, "hb_plant_get_terrain"));
+  for (size_t i = 0; i < size_t(ctx->B); ++i) {
+    double r[Terrain::size] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0, ctx->contact_cfg.ground_z, ctx->contact_cfg.mu, ctx->contact_cfg.mu,
+                               ctx->contact_cfg.mu, ctx->contact_cfg.mu};
+    if (ctx->terrain_on) std::memcpy(r, ctx->terrain_host.data() + i * Terrain::size, sizeof r);
+    if (plane) { for (int a = 0; a < 3; ++a) plane[4 * i + a] = r[Terrain::T + 3 * a + 2]; plane[4 * i + 3] = r[Terrain::d]; }
+    if (mu) std::memcpy(mu + 4 * i, r + Terrain::mu, 4 * sizeof(double));
+    if (frame) std::memcpy(frame + 9 * i, r + Terrain::T, 9 * sizeof(double));
+  }
   return HB_OK;
 }
 

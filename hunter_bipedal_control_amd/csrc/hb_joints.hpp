@@ -84,9 +84,11 @@ HB_HD void joint_row(int r, const double* A, const double* X, const double* Jc, 
 }
 
 // One substep of length h.  q[16], v[16] in / out (LDS); imp[32] (LDS behind `lds`) in / out; taua[10] (LDS) the saturated torque.
-template <class Ctx>
+// TERRAIN (hb_contact.hpp): rows 0-11 are those of the plane's frame, through A, the contact columns of X and Jc; the joint rows are unchanged.
+template <bool TERRAIN = false, class Ctx>
 HB_HD void joints_substep(const Ctx& cx, const DevModel& Mdl, double* q, double* v, const double* wrench, const int* all_on,
-                          const hb_contact_config& K, const hb_joint_model& Jm, double eps, double h, double* lds, double* vdot_out) {
+                          const hb_contact_config& K, const hb_joint_model& Jm, double eps, double h, double* lds, double* vdot_out,
+                          const double* ter = nullptr) {
   double* Jc = lds + PlantJointLds::Jc;
   double* X = lds + PlantJointLds::X;
   double* A = lds + PlantJointLds::A;
@@ -125,10 +127,19 @@ HB_HD void joints_substep(const Ctx& cx, const DevModel& Mdl, double* q, double*
   // the front half of the pinned stub's substep with every point on (its first barrier publishes what lane 0 wrote above)
   plant_substep<2>(cx, Mdl, q, v, taua, all_on, nullptr, 0.0, 0.0, h, lds, nullptr, nullptr, wgen, mdiag);
   for (int i = cx.lane; i < 16; i += cx.nlanes) vf[i] = v[i] + h * X[i * XJ];
-  cx.sync();
+  double ground_z;
+  if constexpr (TERRAIN) {
+    terrain_rotate<XJ>(cx, ter + Terrain::T, Jc, X, A, feet);   // (its barriers publish vf)
+    ground_z = ter[Terrain::d];
+  } else {
+    cx.sync();
+    ground_z = K.ground_z;
+  }
   double tr = 0.0;
   for (int i = 0; i < 12; ++i) tr += A[i * 13];
   const double reg = eps * tr, mu = K.mu;
+  double mup[HB_NC];
+  point_mu<TERRAIN>(ter, mu, mup);
   const bool stops = Jm.limits != 0;
   double D[12], Dj[HB_NJ], lim[HB_NJ], sj[HB_NJ];
   for (int k = 0; k < 12; ++k) D[k] = A[k * 13] + reg;
@@ -141,7 +152,7 @@ HB_HD void joints_substep(const Ctx& cx, const DevModel& Mdl, double* q, double*
   {
     const int r = cx.lane < 32 ? cx.lane : 0;   // (lanes 32.. shadow lane 0: nothing reads them)
     double W[22], g, p, res = 0.0, jres = 0.0;
-    joint_row(r, A, X, Jc, vf, feet, K.ground_z, K.erp, h, sgn, bstop, imp, reg, W, g, p);
+    joint_row(r, A, X, Jc, vf, feet, ground_z, K.erp, h, sgn, bstop, imp, reg, W, g, p);
     for (int s = 0; s < K.sweeps; ++s) {
       res = 0.0;
       jres = 0.0;
@@ -154,7 +165,7 @@ HB_HD void joints_substep(const Ctx& cx, const DevModel& Mdl, double* q, double*
         res = fmax(res, fabs(D[n] * dn));
         const double pa0 = wave_bcast_f64(p, a), pb0 = wave_bcast_f64(p, b);
         double ta, tb;
-        pgs_tangent(wave_bcast_f64(g, a), wave_bcast_f64(g, b), pa0, pb0, D[a], D[b], mu, pn, ta, tb);
+        pgs_tangent(wave_bcast_f64(g, a), wave_bcast_f64(g, b), pa0, pb0, D[a], D[b], mup[pt], pn, ta, tb);
         const double da = ta - pa0, db = tb - pb0;
         g += W[a] * da;
         g += W[b] * db;
@@ -186,7 +197,7 @@ HB_HD void joints_substep(const Ctx& cx, const DevModel& Mdl, double* q, double*
 #else
   {
     double W[32 * 22], g[32], p[32], res = 0.0, jres = 0.0;
-    for (int r = 0; r < 32; ++r) joint_row(r, A, X, Jc, vf, feet, K.ground_z, K.erp, h, sgn, bstop, imp, reg, W + 22 * r, g[r], p[r]);
+    for (int r = 0; r < 32; ++r) joint_row(r, A, X, Jc, vf, feet, ground_z, K.erp, h, sgn, bstop, imp, reg, W + 22 * r, g[r], p[r]);
     auto col = [&](int k, double d) { for (int r = 0; r < 32; ++r) g[r] += W[22 * r + k] * d; };
     for (int s = 0; s < K.sweeps; ++s) {
       res = 0.0;
@@ -198,7 +209,7 @@ HB_HD void joints_substep(const Ctx& cx, const DevModel& Mdl, double* q, double*
         p[n] = pn;
         res = fmax(res, fabs(D[n] * dn));
         double ta, tb;
-        pgs_tangent(g[a], g[b], p[a], p[b], D[a], D[b], mu, pn, ta, tb);
+        pgs_tangent(g[a], g[b], p[a], p[b], D[a], D[b], mup[pt], pn, ta, tb);
         const double da = ta - p[a], db = tb - p[b];
         for (int r = 0; r < 32; ++r) { g[r] += W[22 * r + a] * da; g[r] += W[22 * r + b] * db; }
         p[a] = ta;
@@ -243,11 +254,11 @@ HB_HD void joints_substep(const Ctx& cx, const DevModel& Mdl, double* q, double*
 // saturated torque (what hb_plant_sense reports as the joint torque).  HYBRID (hb_plant.hpp): `tau` is not read; the law is
 // evaluated and saturated into taua before every substep, tau_last / tau_applied are the last substep's and saturation bit 10 + j is set
 // if joint j was saturated in any substep.
-template <bool HYBRID = false, class Ctx>
+template <bool HYBRID = false, bool TERRAIN = false, class Ctx>
 HB_HD void joints_step(const Ctx& cx, const DevModel& Mdl, double* q_g, double* v_g, double* imp_g, double* jimp_g, const double* tau,
                        const double* wrench, const int* all_on, const hb_contact_config& K, const hb_joint_model& Jm, double eps, double dt,
                        int substeps, double* lds, double* lambda_out, double* vdot_out, double* tau_last_g, const ContactOut& out,
-                       const JointOut& jout, const HybridActuator* actuator = nullptr) {
+                       const JointOut& jout, const HybridActuator* actuator = nullptr, const double* ter = nullptr) {
   double* q = lds + JointLds::q;
   double* v = lds + JointLds::v;
   double* imp = lds + JointLds::imp;
@@ -268,11 +279,11 @@ HB_HD void joints_step(const Ctx& cx, const DevModel& Mdl, double* q_g, double* 
     ActuatorAcc acc;
     for (int s = 0; s < substeps; ++s) {
       actuator_eval(cx, act, q, v, s, taua, acc, [&](int j, double ts) { return joint_saturate(ts, actuator_pick(Jm.torque_limit, j)); });
-      joints_substep(cx, Mdl, q, v, wrench, all_on, K, Jm, eps, h, lds, vdot_out);
+      joints_substep<TERRAIN>(cx, Mdl, q, v, wrench, all_on, K, Jm, eps, h, lds, vdot_out, ter);
     }
     actuator_finish(cx, act, substeps, acc, true);
   } else {
-    for (int s = 0; s < substeps; ++s) joints_substep(cx, Mdl, q, v, wrench, all_on, K, Jm, eps, h, lds, vdot_out);
+    for (int s = 0; s < substeps; ++s) joints_substep<TERRAIN>(cx, Mdl, q, v, wrench, all_on, K, Jm, eps, h, lds, vdot_out, ter);
   }
   // ---- outputs: as contact_step, then the joint arrays
   const double* Jc = lds + PlantJointLds::Jc;
@@ -281,10 +292,14 @@ HB_HD void joints_step(const Ctx& cx, const DevModel& Mdl, double* q_g, double* 
   for (int i = cx.lane; i < 16; i += cx.nlanes) { q_g[i] = q[i]; v_g[i] = v[i]; }
   for (int i = cx.lane; i < 12; i += cx.nlanes) {
     imp_g[i] = imp[i];
-    lambda_out[i] = imp[i] / h;
-    double s = 0.0;
-    for (int k = 0; k < 16; ++k) s += Jc[i * 16 + k] * v[k];
-    out.pvel[i] = s;
+    if constexpr (TERRAIN) {
+      contact_outputs_terrain(ter, i, Jc, v, imp, h, lambda_out, out.pvel);
+    } else {
+      lambda_out[i] = imp[i] / h;
+      double s = 0.0;
+      for (int k = 0; k < 16; ++k) s += Jc[i * 16 + k] * v[k];
+      out.pvel[i] = s;
+    }
   }
   for (int i = cx.lane; i < 20; i += cx.nlanes) jimp_g[i] = imp[12 + i];
   for (int j = cx.lane; j < HB_NJ; j += cx.nlanes) {
@@ -295,7 +310,8 @@ HB_HD void joints_step(const Ctx& cx, const DevModel& Mdl, double* q_g, double* 
   }
   cx.sync();
   for (int c = cx.lane; c < HB_NC; c += cx.nlanes) {
-    out.gap[c] = feet[3 * c + 2] - K.ground_z;
+    if constexpr (TERRAIN) out.gap[c] = terrain_height(ter, feet + 3 * c);
+    else out.gap[c] = feet[3 * c + 2] - K.ground_z;
     out.touching[c] = imp[3 * c + 2] > 0.0 ? 1 : 0;
   }
   if (cx.lane == 0) {
@@ -304,7 +320,10 @@ HB_HD void joints_step(const Ctx& cx, const DevModel& Mdl, double* q_g, double* 
     for (int i = 0; i < 16; ++i) finite = finite && fabs(q[i]) <= 1.7976931348623157e308 && fabs(v[i]) <= 1.7976931348623157e308;
     int st = out.status[0] & HB_CONTACT_FALLEN;   // (latched until hb_plant_reset)
     if (!finite) st |= HB_CONTACT_NONFINITE;
-    if (K.fall_height > 0.0 && q[2] - K.ground_z < K.fall_height) st |= HB_CONTACT_FALLEN;
+    double height;
+    if constexpr (TERRAIN) height = terrain_height(ter, q);
+    else height = q[2] - K.ground_z;
+    if (K.fall_height > 0.0 && height < K.fall_height) st |= HB_CONTACT_FALLEN;
     if (!(res <= K.tol)) st |= HB_CONTACT_UNCONVERGED;
     out.res[0] = res;
     out.status[0] = st;

@@ -10,6 +10,7 @@
 #include "hb_wbc.hpp"
 #include "hb_refgen.hpp"
 #include "hb_gait.hpp"
+#include "hb_contact.hpp"
 
 namespace {
 using namespace hb;
@@ -160,6 +161,17 @@ constexpr void fields(JointBatch& j, size_t, F&& f) {
   HB_FIELD(j.status, 1);
 }
 
+// per-instance terrain of the ground-contact plant (hb_plant_set_terrain), allocated by the first call that gives one: the record the
+// terrain kernels stage per instance (hb_contact.hpp Terrain: frame T row-major | d | mu of the four points)
+struct TerrainBatch {
+  int B;
+  double* ter;
+};
+template <class F>
+constexpr void fields(TerrainBatch& t, size_t, F&& f) {
+  HB_FIELD(t.ter, Terrain::size);
+}
+
 // actuator loop of the plant and the simulator end of the LCM link (hb_plant_step_hybrid, hb_plant_step_lcm, hb_plant_sense_lcm),
 // allocated on the first call that needs them — the held-torque path needs none: the record of the last hybrid step, the staging of a
 // host command and the received command (pos_des vel_des kp kd ff, one array each), the timestamp filter, the wire images
@@ -268,6 +280,7 @@ static_assert(sizeof(PlantBatch) == kPtr /*B*/ + 2 * sizeof(double) + (n_fields<
               "describe every array of PlantBatch in fields()");
 static_assert(sizeof(ContactBatch) == 2 * sizeof(int) + n_fields<ContactBatch>() * kPtr, "describe every array of ContactBatch in fields()");
 static_assert(sizeof(JointBatch) == kPtr /*B*/ + n_fields<JointBatch>() * kPtr, "describe every array of JointBatch in fields()");
+static_assert(sizeof(TerrainBatch) == kPtr /*B*/ + n_fields<TerrainBatch>() * kPtr, "describe every array of TerrainBatch in fields()");
 static_assert(sizeof(ActuatorBatch) == kPtr /*B*/ + n_fields<ActuatorBatch>() * kPtr, "describe every array of ActuatorBatch in fields()");
 static_assert(sizeof(RefgenBatch) == kPtr /*B*/ + n_fields<RefgenBatch>() * kPtr + kPtr /*init_stance*/, "describe every array of RefgenBatch in fields()");
 static_assert(sizeof(GaitBatch) == 2 * sizeof(int) + n_fields<GaitBatch>() * kPtr, "describe every array of GaitBatch in fields()");

@@ -37,6 +37,19 @@ def lowest_contact_point(solver, q) -> float:
     return float(feet[:, :, 2].min())
 
 
+def plane_under_contact_points(solver, q, normals) -> np.ndarray:
+    """d[B] that puts the plane n_i . x = d_i under the lowest contact point of q[i] (device kinematics), normals[B][3] (any length;
+    measured along the unit normal): the terrain of a rollout that starts there.  With normals (0, 0, 1) it is the height of each
+    instance's lowest contact point (lowest_contact_point is its minimum over the batch)."""
+    q = np.atleast_2d(np.asarray(q, dtype=float))
+    n = np.broadcast_to(np.asarray(normals, dtype=float), (q.shape[0], 3))
+    n = n / np.linalg.norm(n, axis=1, keepdims=True)
+    x = np.zeros((q.shape[0], 22))
+    x[:, 6:9], x[:, 9:12], x[:, 12:] = q[:, 0:3], q[:, 3:6], q[:, 6:]
+    feet = np.asarray(solver.eval_foot_kinematics(x, np.zeros((q.shape[0], 22)))[0]).reshape(q.shape[0], 4, 3)
+    return np.einsum("bcx,bx->bc", feet, n).min(axis=1)
+
+
 class DeviceLoop:
     """One HunterSolver driven in closed loop.  `gait` per instance (names of gait.info), `cmd_vel` [B][4]."""
 
@@ -141,7 +154,7 @@ class ResidentLoop:
     def __init__(self, solver, params: dict, gaits, cmd_vel, n_intervals: int = 100, mpc_every: int = 8, dt: float = 0.002,
                  t_gait_start: float = 0.3, joint_ik: bool = True, substeps: int = 4, static_schedule_until: float = 0.0,
                  device_gait: bool = False, use_estimator: bool = False, sensor_config=None, sensor_bias=None, contact_config=None,
-                 joint_model=None, actuator: str = "held"):
+                 joint_model=None, actuator: str = "held", terrain=None):
         """static_schedule_until > 0: the mode schedules are uploaded once for [-1, static_schedule_until] (at most
         HB_MAX_EVENTS events) instead of a sliding window per MPC call — no per-call host work for large batches.
         device_gait: the device gait manager produces the windows; step() builds no per-instance list and uploads no schedule, and
@@ -154,7 +167,13 @@ class ResidentLoop:
         joints of the reference's MuJoCo model); an abi.HbJointModel is taken as it is.  Needs contact_config.
         actuator: "held" — the torque of the joint command is held over the tick (hb_plant_step); "substep" — the plant evaluates the
         command's law ff + kp (pos_des - q) + kd (vel_des - qd) before every substep from its own state (hb_plant_step_hybrid on the
-        device-resident command), as the reference's simulator does per simulator step (mujoco/src/main.cc:243-249)."""
+        device-resident command), as the reference's simulator does per simulator step (mujoco/src/main.cc:243-249).
+        terrain: per-instance ground of the ground-contact plant — None: the contact model's own plane and mu; dict(plane=[B][4] = unit
+        normal and offset d, or [B][3] = normals alone, the plane then goes under the lowest contact point of each instance's start
+        (plane_under_contact_points); mu=[B][4] per contact point), either may be missing (hb_plant_set_terrain).  Needs contact_config; set
+        after the contact model.  The controller, estimator and swing planner assume level ground."""
+        if terrain is not None and contact_config is None:
+            raise ValueError("terrain belongs to the ground-contact plant: give contact_config as well")
         if actuator not in ("held", "substep"):
             raise ValueError('actuator is "held" or "substep"')
         self.actuator = actuator
@@ -196,6 +215,14 @@ class ResidentLoop:
             solver.plant_set_contact_model(contact_config)
             if joint_model is not None:
                 solver.plant_set_joint_model(abi.make_joint_model(params, **joint_model) if isinstance(joint_model, dict) else joint_model)
+            if terrain is not None:
+                plane = terrain.get("plane")
+                if plane is not None:
+                    plane = np.asarray(plane, dtype=float).reshape(self.B, -1)
+                    if plane.shape[1] == 3:
+                        n = plane / np.linalg.norm(plane, axis=1, keepdims=True)
+                        plane = np.concatenate([n, plane_under_contact_points(solver, q0, n)[:, None]], axis=1)
+                solver.plant_set_terrain(plane, terrain.get("mu"))
         # resident observation of the initial state
         rbd = np.zeros((self.B, 32))
         rbd[:, 0:3], rbd[:, 3:6], rbd[:, 6:16] = q0[:, 3:6], q0[:, 0:3], q0[:, 6:]

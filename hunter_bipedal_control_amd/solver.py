@@ -34,6 +34,7 @@ ABI_SYMBOLS = [
     "hb_plant_set_sensor_model", "hb_plant_sense", "hb_estimator_update_resident", "hb_estimator_contact_force_resident",
     "hb_plant_set_contact_model", "hb_plant_set_external_wrench", "hb_plant_get_contact",
     "hb_plant_set_joint_model", "hb_plant_get_joints", "hb_plant_step_hybrid", "hb_plant_get_actuator",
+    "hb_plant_set_terrain", "hb_plant_get_terrain",
 ]
 # include/hunter_lcm.h
 LCM_SYMBOLS = ["hb_lcm_fingerprint", "hb_lcm_encoded_size", "hb_lcm_field_count", "hb_lcm_encode", "hb_lcm_decode", "hb_lcm_frame", "hb_lcm_unframe",
@@ -321,6 +322,21 @@ class HunterSolver:
         out = dict(tau_applied=np.zeros((self.B, 10)), friction_torque=np.zeros((self.B, 10)), limit_torque=np.zeros((self.B, 10)),
                    residual=np.zeros(self.B), status=np.zeros(self.B, dtype=np.int32))
         self._check(self.lib.hb_plant_get_joints(self.ctx, *[_p(a) for a in out.values()]), "hb_plant_get_joints")
+        return out
+
+    # ---- per-instance terrain of the ground-contact plant (hb_plant_set_terrain) ---------------------------------------------------
+    def plant_set_terrain(self, plane=None, mu=None):
+        """plane [B][4] = unit normal and offset of the instance's ground plane n . x = d (None: (0, 0, 1, ground_z)); mu [B][4] = friction
+        coefficient per contact point (None: the contact model's mu).  Both None: no terrain.  Clears the contact impulses."""
+        pl = None if plane is None else _f64(plane, (self.B, 4))
+        m = None if mu is None else _f64(mu, (self.B, 4))
+        self._check(self.lib.hb_plant_set_terrain(self.ctx, _p(pl), _p(m)), "hb_plant_set_terrain")
+
+    def plant_get_terrain(self):
+        """-> dict(plane[B][4], mu[B][4], frame[B][3][3] = T = [t1 t2 n] with the axes in columns) of the terrain in force; without one,
+        what the contact model amounts to."""
+        out = dict(plane=np.zeros((self.B, 4)), mu=np.zeros((self.B, 4)), frame=np.zeros((self.B, 3, 3)))
+        self._check(self.lib.hb_plant_get_terrain(self.ctx, *[_p(a) for a in out.values()]), "hb_plant_get_terrain")
         return out
 
     # ---- sensors from the plant (hb_plant_sense) and the estimator on them ------------------------------------------------

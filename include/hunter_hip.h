@@ -351,6 +351,34 @@ int32_t hb_plant_set_joint_model(hb_ctx* ctx, const hb_joint_model* model);
 int32_t hb_plant_get_joints(hb_ctx* ctx, double* tau_applied, double* friction_torque, double* limit_torque, double* residual,
                             int32_t* status);
 
+/* ---- per-instance terrain of contact model 1: an inclined plane per robot, a friction coefficient per contact point -----------------
+ * Instance i has a plane {x : n . x = d} with unit normal n, n_z >= 0.5, and a friction coefficient mu_c >= 0 for each contact point
+ * c = 0..3.  The contact frame is T = [t1 t2 n] (columns), built once by hb_plant_set_terrain on the host:
+ *     t1 = (e_x - n_x n) / |e_x - n_x n|,     t2 = n x t1;      for n = e_z this is the identity exactly.
+ * With a terrain in force, steps 1 - 6 of contact model 1 read as follows; everything not named stays as written there.
+ *  1. J~ = blockdiag(T') J: rows 3c, 3c + 1, 3c + 2 are the t1, t2, n components of point c.  The gap is phi_c = n . x_c - d.
+ *  3. W = J~ M^-1 J~' + eps tr(J~ M^-1 J~') I,  c = J~ v_f + b, b on the normal rows, from phi_c as today.
+ *  4. Unchanged, with mu_c of the point in place of mu.  The impulses p are components in (t1, t2, n).
+ *  5. v+ = v_f + M^-1 J~' p.
+ *  6. lambda_c = T p_c / h (world forces, as today); point_vel stays the world velocity J v+; gap_c = n . x_c - d at the new q;
+ *     touching_c = (p_n > 0); HB_CONTACT_FALLEN is raised when n . q[0:3] - d < fall_height.
+ * Joint model: rows 0 - 11 of its 32-row problem take the same substitution, through A, the contact columns of X and Jc; the joint
+ * rows are unchanged.  Arithmetic order: every product with T is the sum over the world axes in the order x, y, z (T p over t1, t2, n);
+ * with T = I it returns its operand, so a terrain (0, 0, 1, ground_z) with mu = cfg.mu gives the step without a terrain, value for value.
+ *
+ * plane: [batch][4] = n_x n_y n_z d, or NULL for (0, 0, 1, ground_z) for every instance; mu: [batch][4], or NULL for cfg.mu for every
+ * point; both defaults are snapshots of the configuration in force at the call.  Both NULL switches the terrain off: the step then
+ * launches the kernels it launches without one.  n is normalised on the host before it is stored.  HB_ERR_ARG for a non-finite entry,
+ * | |n| - 1 | > 1e-9, n_z < 0.5 or mu < 0 (the message names the first offending instance; the terrain in force is kept); HB_ERR_STATE
+ * before hb_plant_reset or outside contact model 1.  The call clears the contact impulses (the warm start is expressed in the frame of
+ * before) and nothing else.  The terrain survives hb_plant_reset and a second hb_plant_set_contact_model with mode 1; leaving model 1
+ * switches it off.  cfg.mu and cfg.ground_z are not read by a step while a terrain is in force. */
+int32_t hb_plant_set_terrain(hb_ctx* ctx, const double* plane /*[batch][4] or NULL*/, const double* mu /*[batch][4] or NULL*/);
+/* The terrain in force (any pointer may be NULL): plane[batch][4] with the stored unit normal, mu[batch][4], frame[batch][9] = T
+ * row-major.  Without a terrain: what the model in force amounts to, (0, 0, 1, ground_z), cfg.mu and the identity.  HB_ERR_STATE before
+ * hb_plant_reset or outside contact model 1. */
+int32_t hb_plant_get_terrain(hb_ctx* ctx, double* plane, double* mu, double* frame);
+
 /* ---- hybrid step: the actuator loop per substep --------------------------------------------------------------------------------
  * The reference's controller does not send a torque but the hybrid command (joint_pos, joint_vel, kp, kd, ff_tau), and its simulator turns
  * it into a torque inside every simulator step from the simulator's own joint state (mujoco/src/main.cc:243-249).  An instance has a

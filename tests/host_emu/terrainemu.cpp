@@ -1,0 +1,91 @@
+// TEST HARNESS: the terrain forms of the ground-contact step routines (hb_contact.hpp contact_step, hb_joints.hpp joints_step with TERRAIN:
+// the routines k_plant_terrain / k_plant_terrain_joints and their hybrid forms run per instance) compiled for the host with one emulated
+// lane, for tests/test_terrain_plant_host.py.  ter = the instance's Terrain record (T row-major | d | mu of the four points), or null for
+// the routines without a terrain.  Not part of the product; the product path always runs the kernels.
+#include <cstddef>
+#include <cstdint>
+#include <vector>
+#include "../../hunter_bipedal_control_amd/csrc/hb_host.hpp"
+#include "../../hunter_bipedal_control_amd/csrc/hb_joints.hpp"
+
+using namespace hb;
+namespace {
+struct HostCtx {
+  int lane = 0, nlanes = 1;
+  void sync() const {}
+};
+HybridActuator actuator(const double* cmd, double* tau_first, double* tau_mean, double* act) {
+  return HybridActuator{cmd, cmd + 10, cmd + 20, cmd + 30, cmd + 40, tau_first, tau_mean, act, act + HB_NJ};
+}
+// the record where the kernels keep it: behind the form's own arrays
+double* staged(std::vector<double>& lds, int at, const double* ter) {
+  if (!ter) return nullptr;
+  for (int k = 0; k < TER_LDS; ++k) lds[at + k] = ter[k];
+  return lds.data() + at;
+}
+}  // namespace
+
+extern "C" {
+int te_record_size() { return Terrain::size; }
+// The arguments of ce_step (contactemu.cpp) and the record.
+void te_step(const hb_model* m, const hb_contact_config* K, const double* ter, double* q, double* v, double* imp, const double* tau,
+             const double* wrench, double eps, double dt, int substeps, double* lambda, double* vdot, double* gap, double* pvel, double* res,
+             int* touching, int* status) {
+  const DevModel d = make_dev_model(*m);
+  const int all_on[4] = {1, 1, 1, 1};
+  std::vector<double> lds(CONTACT_LDS_TOTAL + TER_LDS, 0.0);
+  const ContactOut out{gap, pvel, res, touching, status};
+  const double* t = staged(lds, CONTACT_LDS_TOTAL, ter);
+  if (t) contact_step<false, true>(HostCtx{}, d, q, v, imp, tau, wrench, all_on, *K, eps, dt, substeps, lds.data(), lambda, vdot, out, nullptr, t);
+  else contact_step(HostCtx{}, d, q, v, imp, tau, wrench, all_on, *K, eps, dt, substeps, lds.data(), lambda, vdot, out);
+}
+// The arguments of je_step (jointemu.cpp) and the record.
+void te_joints_step(const hb_model* m, const hb_contact_config* K, const hb_joint_model* J, const double* ter, double* q, double* v, double* imp,
+                    double* jimp, const double* tau, const double* wrench, double eps, double dt, int substeps, double* lambda, double* vdot,
+                    double* gap, double* pvel, double* res, int* touching, int* status, double* tau_applied, double* friction_torque,
+                    double* limit_torque, double* jres, int* jstatus, double* tau_last) {
+  const DevModel d = make_dev_model(*m);
+  const int all_on[4] = {1, 1, 1, 1};
+  std::vector<double> lds(JOINT_LDS_TOTAL + TER_LDS, 0.0);
+  const ContactOut out{gap, pvel, res, touching, status};
+  const JointOut jout{tau_applied, friction_torque, limit_torque, jres, jstatus};
+  const double* t = staged(lds, JOINT_LDS_TOTAL, ter);
+  if (t)
+    joints_step<false, true>(HostCtx{}, d, q, v, imp, jimp, tau, wrench, all_on, *K, *J, eps, dt, substeps, lds.data(), lambda, vdot, tau_last, out,
+                             jout, nullptr, t);
+  else joints_step(HostCtx{}, d, q, v, imp, jimp, tau, wrench, all_on, *K, *J, eps, dt, substeps, lds.data(), lambda, vdot, tau_last, out, jout);
+}
+// The hybrid forms: the arguments of ae_contact_step / ae_joints_step (actemu.cpp) and the record; cmd[5][10] = pos_des vel_des kp kd ff.
+void te_step_hybrid(const hb_model* m, const hb_contact_config* K, const double* ter, double* q, double* v, double* imp, const double* cmd,
+                    const double* wrench, double eps, double dt, int substeps, double* lambda, double* vdot, double* gap, double* pvel, double* res,
+                    int* touching, int* status, double* tau_first, double* tau_mean, double* tau_last) {
+  const DevModel d = make_dev_model(*m);
+  const int all_on[4] = {1, 1, 1, 1};
+  std::vector<double> lds(CONTACT_LDS_TOTAL + ACT_LDS + TER_LDS, 0.0);
+  const ContactOut out{gap, pvel, res, touching, status};
+  const HybridActuator act = actuator(cmd, tau_first, tau_mean, lds.data() + CONTACT_LDS_TOTAL);
+  const double* t = staged(lds, CONTACT_LDS_TOTAL + ACT_LDS, ter);
+  if (t) contact_step<true, true>(HostCtx{}, d, q, v, imp, nullptr, wrench, all_on, *K, eps, dt, substeps, lds.data(), lambda, vdot, out, &act, t);
+  else contact_step<true>(HostCtx{}, d, q, v, imp, nullptr, wrench, all_on, *K, eps, dt, substeps, lds.data(), lambda, vdot, out, &act);
+  for (int j = 0; j < HB_NJ; ++j) tau_last[j] = act.tau[j];
+}
+void te_joints_step_hybrid(const hb_model* m, const hb_contact_config* K, const hb_joint_model* J, const double* ter, double* q, double* v,
+                           double* imp, double* jimp, const double* cmd, const double* wrench, double eps, double dt, int substeps, double* lambda,
+                           double* vdot, double* gap, double* pvel, double* res, int* touching, int* status, double* tau_applied,
+                           double* friction_torque, double* limit_torque, double* jres, int* jstatus, double* tau_last, double* tau_first,
+                           double* tau_mean) {
+  const DevModel d = make_dev_model(*m);
+  const int all_on[4] = {1, 1, 1, 1};
+  std::vector<double> lds(JOINT_LDS_TOTAL + ACT_LDS + TER_LDS, 0.0);
+  const ContactOut out{gap, pvel, res, touching, status};
+  const JointOut jout{tau_applied, friction_torque, limit_torque, jres, jstatus};
+  const HybridActuator act = actuator(cmd, tau_first, tau_mean, lds.data() + JOINT_LDS_TOTAL);
+  const double* t = staged(lds, JOINT_LDS_TOTAL + ACT_LDS, ter);
+  if (t)
+    joints_step<true, true>(HostCtx{}, d, q, v, imp, jimp, nullptr, wrench, all_on, *K, *J, eps, dt, substeps, lds.data(), lambda, vdot, tau_last, out,
+                            jout, &act, t);
+  else
+    joints_step<true>(HostCtx{}, d, q, v, imp, jimp, nullptr, wrench, all_on, *K, *J, eps, dt, substeps, lds.data(), lambda, vdot, tau_last, out, jout,
+                      &act);
+}
+}
