@@ -245,6 +245,49 @@ def make_joint_model(params: dict, **overrides) -> HbJointModel:
     return out
 
 
+class HbEpisodeConfig(C.Structure):
+    """hb_episode_config (include/hunter_hip.h): per-instance episode record of the plant and stop-on-fall, hb_plant_set_episode."""
+    _fields_ = [("slip_speed", C.c_double), ("tilt_limit", C.c_double), ("stop_on_fall", C.c_int32), ("trace_every", C.c_int32),
+                ("trace_capacity", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
+HB_EP_RUNNING, HB_EP_FALLEN, HB_EP_NONFINITE = 0, 1, 2
+HB_EP_TRACE_W, HB_EP_TRACE_MAX = 8, 4096
+# The fields of the two records, (name, first index, length), in the order of the HB_EP_I_* / HB_EP_D_* indices of the header; the trace
+# sample's columns.
+EPISODE_INT_FIELDS = (("STEPS", 0, 1), ("TICKS", 1, 1), ("END_TICK", 2, 1), ("END_CAUSE", 3, 1), ("FIRST_NONFINITE", 4, 1), ("N_TRACE", 5, 1),
+                      ("WBC_STATUS_OR", 6, 1), ("WBC_FAIL_TICKS", 7, 1), ("FIRST_WBC_FAIL", 8, 1), ("CONTACT_TICKS", 9, 4), ("TOUCHDOWNS", 13, 4),
+                      ("PREV_TOUCHING", 17, 4), ("SLIP_TICKS", 21, 1), ("FIRST_SLIP", 22, 1), ("UNCONVERGED_TICKS", 23, 1),
+                      ("CONTACT_STATUS_OR", 24, 1), ("JOINT_STATUS_OR", 25, 1), ("CLAMP_TICKS", 26, 1), ("STOP_TICKS", 27, 1))
+EPISODE_DOUBLE_FIELDS = (("START_POS", 0, 3), ("LAST_BASE", 3, 6), ("HEIGHT_LAST", 9, 1), ("HEIGHT_MIN", 10, 1), ("HEIGHT_MAX", 11, 1),
+                         ("TILT_MAX", 12, 1), ("TAU_MAX", 13, 10), ("WORK_ABS", 23, 1), ("WORK_NET", 24, 1), ("GAP_MIN", 25, 1), ("FN_MAX", 26, 4),
+                         ("SLIP_SPEED_MAX", 30, 1), ("RES_MAX", 31, 1), ("JRES_MAX", 32, 1))
+HB_EP_NI, HB_EP_ND = 28, 33
+EPISODE_TRACE_COLUMNS = ("tick", "x", "y", "height", "yaw", "pitch", "roll", "n_touching")
+
+
+def make_episode_config(**fields) -> HbEpisodeConfig:
+    """slip_speed 0.05 m/s, no tilt limit, no stop on a fall, no trace; any field by name overrides."""
+    d = dict(slip_speed=0.05, tilt_limit=0.0, stop_on_fall=0, trace_every=0, trace_capacity=0)
+    for k in fields:
+        if k not in d:
+            raise TypeError(f"make_episode_config: unknown field {k!r} (one of {sorted(d)})")
+    d.update(fields)
+    out = HbEpisodeConfig()
+    out.slip_speed, out.tilt_limit = float(d["slip_speed"]), float(d["tilt_limit"])
+    out.stop_on_fall, out.trace_every, out.trace_capacity = int(d["stop_on_fall"]), int(d["trace_every"]), int(d["trace_capacity"])
+    return out
+
+
+def split_episode_record(irec, drec) -> dict:
+    """irec[B][HB_EP_NI], drec[B][HB_EP_ND] -> dict of named arrays ([B] for a scalar field, [B][n] otherwise)."""
+    out = {}
+    for table, rec in ((EPISODE_INT_FIELDS, irec), (EPISODE_DOUBLE_FIELDS, drec)):
+        for name, at, n in table:
+            out[name] = rec[:, at].copy() if n == 1 else rec[:, at:at + n].copy()
+    return out
+
+
 class HbJointGains(C.Structure):
     _fields_ = [(k, C.c_double) for k in ("kp_big_stance", "kp_big_swing", "kd_big", "kp_small_stance", "kp_small_swing", "kd_small",
                                           "kd_feet", "kp_position", "kd_position")]

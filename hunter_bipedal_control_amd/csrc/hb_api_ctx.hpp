@@ -108,6 +108,11 @@ struct hb_ctx {
   bool terrain_on = false;
   // actuator loop per substep and the simulator end of the LCM link (hb_plant_step_hybrid / _lcm, hb_plant_sense_lcm): allocated on first use
   ActuatorBatch act{};
+  // per-instance episode record (hb_plant_set_episode): episode_on while one is in force (every plant step is then followed by
+  // k_plant_episode); the records are allocated by the first call that gives a configuration.  The configuration survives hb_plant_reset.
+  EpisodeBatch episode{};
+  hb_episode_config episode_cfg{};
+  bool episode_on = false;
   // reference generation (allocated on the first hb_refgen_reset)
   RefgenBatch rg{};
   hb_refgen_config rg_cfg{};

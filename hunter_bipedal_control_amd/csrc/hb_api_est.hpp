@@ -1,6 +1,40 @@
 // Host side, part 5: joint command, plant (pinned stub and ground-contact model) and its sensor model, state estimator and contact-force observer.
 #pragma once
 
+// ---- per-instance episode record (include/hunter_hip.h above hb_plant_set_episode) -------------------------------------------------
+// The plane the record measures heights from: the terrain records if a terrain is in force, else e_z . x = *d0 (ground_z in model 1, 0 in model 0).
+static const double* episode_plane(const hb_ctx* ctx, double* d0) {
+  *d0 = ctx->contact_cfg.mode == 1 ? ctx->contact_cfg.ground_z : 0.0;
+  return ctx->contact_cfg.mode == 1 && ctx->terrain_on ? ctx->terrain.ter : nullptr;
+}
+
+// the record of every instance from the plant's present state, on s
+static int32_t episode_start(hb_ctx* ctx, hipStream_t s) {
+  EpisodeBatch& e = ctx->episode;
+  double d0;
+  const double* ter = episode_plane(ctx, &d0);
+  if (e.trace) HB_HIP(hipMemsetAsync(e.trace, 0, size_t(ctx->B) * e.trace_cap * HB_EP_TRACE_W * 8, s));
+  hipLaunchKernelGGL(k_plant_episode_init, dim3((ctx->B + 63) / 64), dim3(64), 0, s, e, ctx->plant, ter, d0);
+  HB_HIP(hipGetLastError());
+  return HB_OK;
+}
+
+// Enqueues a plant step of length dt on s (launch(): a writer of the resident observation, resident_write) and, with an episode in force,
+// the update of the record behind it: the one place every step entry point and every plant form goes through.
+template <class F>
+static int32_t plant_write(hb_ctx* ctx, hipStream_t s, bool fence, double dt, F&& launch) {
+  HB_TRY(resident_write(ctx, s, fence, launch));
+  if (!ctx->episode_on) return HB_OK;
+  double d0;
+  const double* ter = episode_plane(ctx, &d0);
+  const int ground = ctx->contact_cfg.mode == 1 ? 1 : 0;
+  hipLaunchKernelGGL(k_plant_episode, dim3((ctx->B + 63) / 64), dim3(64), 0, s, ctx->episode, ctx->episode_cfg, ctx->plant, ctx->contact, ctx->joints, ter,
+                     d0, ground, ground && ctx->joints_on ? 1 : 0, ctx->stats.n_wbc_solves > 0 ? ctx->w.status : nullptr,
+                     ctx->episode_cfg.stop_on_fall ? ctx->jc_estop : nullptr, dt);
+  HB_HIP(hipGetLastError());
+  return HB_OK;
+}
+
 extern "C" {
 
 // joint command outputs and the per-instance controller flags (allocated on first use; loaded = 1, no emergency stop)
@@ -94,6 +128,55 @@ static int32_t actuator_clear(hb_ctx* ctx, hipStream_t s) {
   return HB_OK;
 }
 
+int32_t hb_plant_set_episode(hb_ctx* ctx, const hb_episode_config* cfg) {
+  HB_ENTER_ARGS(false);
+  HB_FAIL_IF(!ctx->plant_ready, HB_ERR_STATE, "hb_plant_set_episode: call hb_plant_reset first");
+  HB_FAIL_IF(cfg && !episode_config_valid(*cfg), HB_ERR_ARG, "hb_plant_set_episode: slip_speed, tilt_limit >= 0 and finite, stop_on_fall 0 / 1, trace_every >= 0, trace_capacity 0 .. 4096 and `reserved` 0 (the episode in force is kept)");
+  HB_ENTER_DEVICE();
+  HB_HIP(hipStreamSynchronize(ctx->s_wbc));  // (a step in flight still updates the record it was launched with)
+  if (!cfg) {
+    ctx->episode_on = false;
+    return HB_OK;
+  }
+  EpisodeBatch& e = ctx->episode;
+  if (!e.drec) {  // (drec: the last array of the description, so an allocation that failed half way is repeated)
+    HB_HIP(alloc_fields(ctx, e));
+    e.B = ctx->B;
+  }
+  if (cfg->trace_capacity > e.trace_cap) {  // the trace grows to the largest capacity asked for
+    if (e.trace) {
+      ctx->allocs.erase(std::remove(ctx->allocs.begin(), ctx->allocs.end(), static_cast<void*>(e.trace)), ctx->allocs.end());
+      HB_HIP(hipFree(e.trace));
+      e.trace = nullptr;
+      e.trace_cap = 0;
+    }
+    HB_HIP(dalloc(ctx, &e.trace, size_t(ctx->B) * cfg->trace_capacity * HB_EP_TRACE_W));
+    e.trace_cap = cfg->trace_capacity;
+  }
+  if (cfg->stop_on_fall) HB_TRY(joint_state_alloc(ctx));
+  ctx->episode_cfg = *cfg;
+  ctx->episode_on = true;
+  HB_TRY(episode_start(ctx, ctx->s_wbc));
+  HB_HIP(hipStreamSynchronize(ctx->s_wbc));
+  return HB_OK;
+}
+
+int32_t hb_plant_get_episode(hb_ctx* ctx, int32_t* irec, double* drec, double* trace) {
+  HB_ENTER_ARGS(false);
+  HB_FAIL_IF(!ctx->plant_ready, HB_ERR_STATE, "hb_plant_get_episode: call hb_plant_reset first");
+  HB_FAIL_IF(!ctx->episode_on, HB_ERR_STATE, "hb_plant_get_episode: no episode in force (hb_plant_set_episode)");
+  HB_ENTER_DEVICE();
+  HB_HIP(hipStreamSynchronize(ctx->s_wbc));
+  EpisodeBatch& e = ctx->episode;
+  HB_TRY(pull(ctx, irec, e, e.irec, whole(ctx)));
+  HB_TRY(pull(ctx, drec, e, e.drec, whole(ctx)));
+  // (the device rows have the pitch of the largest capacity set so far; the caller's have the pitch of the one in force)
+  const size_t row = size_t(ctx->episode_cfg.trace_capacity) * HB_EP_TRACE_W * 8;
+  if (trace && row)
+    HB_HIP(hipMemcpy2D(trace, row, e.trace, size_t(e.trace_cap) * HB_EP_TRACE_W * 8, row, size_t(ctx->B), hipMemcpyDeviceToHost));
+  return HB_OK;
+}
+
 int32_t hb_plant_reset(hb_ctx* ctx, const double* q0, const double* v0, double baumgarte, double eps) {
   HB_ENTER(!q0 || !(baumgarte >= 0.0) || !(eps >= 0.0));
   PlantBatch& p = ctx->plant;
@@ -112,6 +195,7 @@ int32_t hb_plant_reset(hb_ctx* ctx, const double* q0, const double* v0, double b
   if (ctx->contact.wrench) HB_TRY(contact_clear(ctx, ctx->s_wbc));
   if (ctx->joints.status) HB_TRY(joints_clear(ctx, ctx->s_wbc));
   if (ctx->act.wire_full) HB_TRY(actuator_clear(ctx, ctx->s_wbc));
+  if (ctx->episode_on) HB_TRY(episode_start(ctx, ctx->s_wbc));   // the record restarts from the reset state
   HB_HIP(hipStreamSynchronize(ctx->s_wbc));
   ctx->plant_ready = true;
   return HB_OK;
@@ -130,30 +214,30 @@ int32_t hb_plant_step(hb_ctx* ctx, const double* tau, const int32_t* contact, do
   const double* dtau = tau ? p.tau : ctx->jc_out + 5 * B * HB_NJ;
   // the resident observation feeds the next hb_mpc_solve(NULL) / hb_refgen_update(NULL) on the MPC stream
   if (ctx->contact_cfg.mode == 1 && ctx->terrain_on && ctx->joints_on)
-    return resident_write(ctx, s, to_resident, [&] {
+    return plant_write(ctx, s, to_resident, dt, [&] {
       hipLaunchKernelGGL(k_plant_terrain_joints, dim3(ctx->B), dim3(64), 0, s, p, ctx->contact, ctx->joints, ctx->terrain.ter, ctx->contact_cfg,
                          ctx->joint_model, ctx->dmodel, dtau, contact ? p.contact : nullptr, ctx->w.mode, dt, substeps,
                          to_resident ? ctx->w.rbd : nullptr, to_resident ? ctx->b.x0 : nullptr, to_resident ? ctx->w.t_now : nullptr);
     });
   if (ctx->contact_cfg.mode == 1 && ctx->terrain_on)
-    return resident_write(ctx, s, to_resident, [&] {
+    return plant_write(ctx, s, to_resident, dt, [&] {
       hipLaunchKernelGGL(k_plant_terrain, dim3(ctx->B), dim3(64), 0, s, p, ctx->contact, ctx->terrain.ter, ctx->contact_cfg, ctx->dmodel, dtau,
                          contact ? p.contact : nullptr, ctx->w.mode, dt, substeps, to_resident ? ctx->w.rbd : nullptr,
                          to_resident ? ctx->b.x0 : nullptr, to_resident ? ctx->w.t_now : nullptr);
     });
   if (ctx->contact_cfg.mode == 1 && ctx->joints_on)
-    return resident_write(ctx, s, to_resident, [&] {
+    return plant_write(ctx, s, to_resident, dt, [&] {
       hipLaunchKernelGGL(k_plant_joints, dim3(ctx->B), dim3(64), 0, s, p, ctx->contact, ctx->joints, ctx->contact_cfg, ctx->joint_model, ctx->dmodel, dtau,
                          contact ? p.contact : nullptr, ctx->w.mode, dt, substeps, to_resident ? ctx->w.rbd : nullptr,
                          to_resident ? ctx->b.x0 : nullptr, to_resident ? ctx->w.t_now : nullptr);
     });
   if (ctx->contact_cfg.mode == 1)
-    return resident_write(ctx, s, to_resident, [&] {
+    return plant_write(ctx, s, to_resident, dt, [&] {
       hipLaunchKernelGGL(k_plant_contact, dim3(ctx->B), dim3(64), 0, s, p, ctx->contact, ctx->contact_cfg, ctx->dmodel, dtau, contact ? p.contact : nullptr,
                          ctx->w.mode, dt, substeps, to_resident ? ctx->w.rbd : nullptr, to_resident ? ctx->b.x0 : nullptr,
                          to_resident ? ctx->w.t_now : nullptr);
     });
-  return resident_write(ctx, s, to_resident, [&] {
+  return plant_write(ctx, s, to_resident, dt, [&] {
     hipLaunchKernelGGL(k_plant, dim3(ctx->B), dim3(64), 0, s, p, ctx->dmodel, dtau, contact ? p.contact : nullptr, ctx->w.mode, dt, substeps,
                        to_resident ? ctx->w.rbd : nullptr, to_resident ? ctx->b.x0 : nullptr, to_resident ? ctx->w.t_now : nullptr);
   });
@@ -181,26 +265,26 @@ static int32_t plant_launch_hybrid(hb_ctx* ctx, const double* const cmd[5], cons
   double* rx = to_resident ? ctx->b.x0 : nullptr;
   double* rt = to_resident ? ctx->w.t_now : nullptr;
   if (ctx->contact_cfg.mode == 1 && ctx->terrain_on && ctx->joints_on)
-    return resident_write(ctx, s, to_resident, [&] {
+    return plant_write(ctx, s, to_resident, dt, [&] {
       hipLaunchKernelGGL(k_plant_terrain_joints_hybrid, dim3(ctx->B), dim3(64), 0, s, p, ctx->contact, ctx->joints, ctx->terrain.ter, ctx->act, c,
                          ctx->contact_cfg, ctx->joint_model, ctx->dmodel, dcontact, ctx->w.mode, dt, substeps, rr, rx, rt);
     });
   if (ctx->contact_cfg.mode == 1 && ctx->terrain_on)
-    return resident_write(ctx, s, to_resident, [&] {
+    return plant_write(ctx, s, to_resident, dt, [&] {
       hipLaunchKernelGGL(k_plant_terrain_hybrid, dim3(ctx->B), dim3(64), 0, s, p, ctx->contact, ctx->terrain.ter, ctx->act, c, ctx->contact_cfg,
                          ctx->dmodel, dcontact, ctx->w.mode, dt, substeps, rr, rx, rt);
     });
   if (ctx->contact_cfg.mode == 1 && ctx->joints_on)
-    return resident_write(ctx, s, to_resident, [&] {
+    return plant_write(ctx, s, to_resident, dt, [&] {
       hipLaunchKernelGGL(k_plant_joints_hybrid, dim3(ctx->B), dim3(64), 0, s, p, ctx->contact, ctx->joints, ctx->act, c, ctx->contact_cfg, ctx->joint_model,
                          ctx->dmodel, dcontact, ctx->w.mode, dt, substeps, rr, rx, rt);
     });
   if (ctx->contact_cfg.mode == 1)
-    return resident_write(ctx, s, to_resident, [&] {
+    return plant_write(ctx, s, to_resident, dt, [&] {
       hipLaunchKernelGGL(k_plant_contact_hybrid, dim3(ctx->B), dim3(64), 0, s, p, ctx->contact, ctx->act, c, ctx->contact_cfg, ctx->dmodel, dcontact,
                          ctx->w.mode, dt, substeps, rr, rx, rt);
     });
-  return resident_write(ctx, s, to_resident, [&] {
+  return plant_write(ctx, s, to_resident, dt, [&] {
     hipLaunchKernelGGL(k_plant_hybrid, dim3(ctx->B), dim3(64), 0, s, p, ctx->act, c, ctx->dmodel, dcontact, ctx->w.mode, dt, substeps, rr, rx, rt);
   });
 }

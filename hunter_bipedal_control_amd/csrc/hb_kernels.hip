@@ -1201,6 +1201,45 @@ __global__ void k_plant_reset(PlantBatch p, const DevModel* __restrict__ M) {
   for (int j = 0; j < HB_NJ; ++j) p.tau_last[10 * i + j] = 0.0;
 }
 
+// ---- episode record (hb_plant_set_episode, hb_episode.hpp): one thread per instance, behind every plant step --------------------------
+// What the plant form in force left for instance i.  ter: the terrain records or null (then the plane is e_z . x = d0); cb / jb are read
+// only with `ground` / `joints`; wbc_status is null before the first WBC call.
+__device__ __forceinline__ EpisodeIn episode_in(const PlantBatch& p, const ContactBatch& cb, const JointBatch& jb, const double* ter, double d0,
+                                                int ground, int joints, const int* wbc_status, int i) {
+  EpisodeIn in{};
+  in.q = p.q + 16 * i;
+  in.v = p.v + 16 * i;
+  in.tau_last = p.tau_last + 10 * i;
+  in.n[0] = 0.0; in.n[1] = 0.0; in.n[2] = 1.0;
+  in.d = d0;
+  if (ter) {
+    const double* r = ter + size_t(Terrain::size) * i;
+    for (int a = 0; a < 3; ++a) in.n[a] = r[Terrain::T + 3 * a + 2];
+    in.d = r[Terrain::d];
+  }
+  if (wbc_status) in.wbc_status = wbc_status + i;
+  if (ground) {
+    in.gap = cb.gap + 4 * i; in.lambda = p.lambda + 12 * i; in.pvel = cb.pvel + 12 * i; in.res = cb.res + i;
+    in.touching = cb.touching + 4 * i; in.cstatus = cb.status + i;
+  }
+  if (joints) { in.jres = jb.res + i; in.jstatus = jb.status + i; }
+  return in;
+}
+__global__ __launch_bounds__(64) void k_plant_episode_init(EpisodeBatch e, PlantBatch p, const double* __restrict__ ter, double d0) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= e.B) return;
+  const EpisodeIn in = episode_in(p, ContactBatch{}, JointBatch{}, ter, d0, 0, 0, nullptr, i);
+  episode_init(in, e.irec + HB_EP_NI * i, e.drec + HB_EP_ND * i);
+}
+__global__ __launch_bounds__(64) void k_plant_episode(EpisodeBatch e, hb_episode_config K, PlantBatch p, ContactBatch cb, JointBatch jb,
+                                                      const double* __restrict__ ter, double d0, int ground, int joints, const int* wbc_status,
+                                                      int* estop, double dt) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= e.B) return;
+  const EpisodeIn in = episode_in(p, cb, jb, ter, d0, ground, joints, wbc_status, i);
+  episode_update(K, in, dt, e.irec + HB_EP_NI * i, e.drec + HB_EP_ND * i, e.trace + size_t(i) * e.trace_cap * HB_EP_TRACE_W, estop ? estop + i : nullptr);
+}
+
 // ---- sensors from the plant: one thread per instance, 64 instances per workgroup ---------------------------------------------------
 // The per-instance routine (hb_sensors.hpp plant_sense) reads and writes LDS rows; the workgroup moves its 64 instances' inputs and
 // outputs between LDS and global memory array by array, consecutive lanes on consecutive words (the arrays are instance-major, so a

@@ -11,6 +11,7 @@
 #include "hb_refgen.hpp"
 #include "hb_gait.hpp"
 #include "hb_contact.hpp"
+#include "hb_episode.hpp"
 
 namespace {
 using namespace hb;
@@ -172,6 +173,21 @@ constexpr void fields(TerrainBatch& t, size_t, F&& f) {
   HB_FIELD(t.ter, Terrain::size);
 }
 
+// per-instance episode record of the plant (hb_plant_set_episode, hb_episode.hpp), allocated by the first call that gives a
+// configuration: the integer and the double record of every instance.  The trace is [B][trace_cap][HB_EP_TRACE_W] with trace_cap the
+// largest trace_capacity set so far: a run-time extent, so the set call allocates it and the description does not name it.
+struct EpisodeBatch {
+  int B;
+  int trace_cap;
+  int* irec;
+  double* drec;
+  double* trace;
+};
+template <class F>
+constexpr void fields(EpisodeBatch& e, size_t, F&& f) {
+  HB_FIELD(e.irec, HB_EP_NI); HB_FIELD(e.drec, HB_EP_ND);
+}
+
 // actuator loop of the plant and the simulator end of the LCM link (hb_plant_step_hybrid, hb_plant_step_lcm, hb_plant_sense_lcm),
 // allocated on the first call that needs them — the held-torque path needs none: the record of the last hybrid step, the staging of a
 // host command and the received command (pos_des vel_des kp kd ff, one array each), the timestamp filter, the wire images
@@ -281,6 +297,7 @@ static_assert(sizeof(PlantBatch) == kPtr /*B*/ + 2 * sizeof(double) + (n_fields<
 static_assert(sizeof(ContactBatch) == 2 * sizeof(int) + n_fields<ContactBatch>() * kPtr, "describe every array of ContactBatch in fields()");
 static_assert(sizeof(JointBatch) == kPtr /*B*/ + n_fields<JointBatch>() * kPtr, "describe every array of JointBatch in fields()");
 static_assert(sizeof(TerrainBatch) == kPtr /*B*/ + n_fields<TerrainBatch>() * kPtr, "describe every array of TerrainBatch in fields()");
+static_assert(sizeof(EpisodeBatch) == 2 * sizeof(int) + (n_fields<EpisodeBatch>() + 1 /*trace*/) * kPtr, "describe every array of EpisodeBatch in fields()");
 static_assert(sizeof(ActuatorBatch) == kPtr /*B*/ + n_fields<ActuatorBatch>() * kPtr, "describe every array of ActuatorBatch in fields()");
 static_assert(sizeof(RefgenBatch) == kPtr /*B*/ + n_fields<RefgenBatch>() * kPtr + kPtr /*init_stance*/, "describe every array of RefgenBatch in fields()");
 static_assert(sizeof(GaitBatch) == 2 * sizeof(int) + n_fields<GaitBatch>() * kPtr, "describe every array of GaitBatch in fields()");

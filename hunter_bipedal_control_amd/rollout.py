@@ -154,7 +154,7 @@ class ResidentLoop:
     def __init__(self, solver, params: dict, gaits, cmd_vel, n_intervals: int = 100, mpc_every: int = 8, dt: float = 0.002,
                  t_gait_start: float = 0.3, joint_ik: bool = True, substeps: int = 4, static_schedule_until: float = 0.0,
                  device_gait: bool = False, use_estimator: bool = False, sensor_config=None, sensor_bias=None, contact_config=None,
-                 joint_model=None, actuator: str = "held", terrain=None):
+                 joint_model=None, actuator: str = "held", terrain=None, episode=None):
         """static_schedule_until > 0: the mode schedules are uploaded once for [-1, static_schedule_until] (at most
         HB_MAX_EVENTS events) instead of a sliding window per MPC call — no per-call host work for large batches.
         device_gait: the device gait manager produces the windows; step() builds no per-instance list and uploads no schedule, and
@@ -171,7 +171,10 @@ class ResidentLoop:
         terrain: per-instance ground of the ground-contact plant — None: the contact model's own plane and mu; dict(plane=[B][4] = unit
         normal and offset d, or [B][3] = normals alone, the plane then goes under the lowest contact point of each instance's start
         (plane_under_contact_points); mu=[B][4] per contact point), either may be missing (hb_plant_set_terrain).  Needs contact_config; set
-        after the contact model.  The controller, estimator and swing planner assume level ground."""
+        after the contact model.  The controller, estimator and swing planner assume level ground.
+        episode: the per-instance episode record of the plant (hb_plant_set_episode) — None: none; a dict of abi.make_episode_config
+        fields ({} = the defaults); an abi.HbEpisodeConfig is taken as it is.  Set after the models and the terrain, so the record starts
+        from the start state over the ground of the run; episode() reads it, run(n) advances n ticks without a read-back."""
         if terrain is not None and contact_config is None:
             raise ValueError("terrain belongs to the ground-contact plant: give contact_config as well")
         if actuator not in ("held", "substep"):
@@ -223,6 +226,9 @@ class ResidentLoop:
                         n = plane / np.linalg.norm(plane, axis=1, keepdims=True)
                         plane = np.concatenate([n, plane_under_contact_points(solver, q0, n)[:, None]], axis=1)
                 solver.plant_set_terrain(plane, terrain.get("mu"))
+        if episode is not None:
+            solver.plant_set_episode(abi.make_episode_config(**episode) if isinstance(episode, dict) else episode)
+        self.has_episode = episode is not None
         # resident observation of the initial state
         rbd = np.zeros((self.B, 32))
         rbd[:, 0:3], rbd[:, 3:6], rbd[:, 6:16] = q0[:, 3:6], q0[:, 0:3], q0[:, 6:]
@@ -253,9 +259,10 @@ class ResidentLoop:
         """Replace the velocity commands [B][4] = (vx, vy, vz, yaw rate); they take effect at the next MPC call."""
         self.cmd = np.ascontiguousarray(cmd_vel, dtype=float).reshape(self.B, 4)
 
-    def step(self, want_outputs: bool = False):
+    def step(self, want_outputs: bool = False, check_refgen: bool = True):
         """want_outputs: the WBC result and the joint command of the tick come back to the host (self.last = dict(out, cmd), as
-        DeviceLoop keeps them) instead of staying on the device; the loop itself is the same."""
+        DeviceLoop keeps them) instead of staying on the device; the loop itself is the same.  check_refgen False: the status of the
+        reference generation is not read back (run)."""
         s = self.s
         if self.use_estimator:
             s.plant_sense()
@@ -264,8 +271,8 @@ class ResidentLoop:
         if self.tick % self.mpc_every == 0:
             if not self.static and not self.device_gait:
                 s.refgen_set_schedule(self._windows())
-            status = s.refgen_update(np.full(self.B, self.t), self.horizon, None, self.cmd)
-            if status.max() != 0:
+            status = s.refgen_update(np.full(self.B, self.t), self.horizon, None, self.cmd, want_status=check_refgen)
+            if check_refgen and status.max() != 0:
                 raise RuntimeError(f"reference generation failed: {status}")
             if not self.started:
                 s.reset_resident()
@@ -283,3 +290,33 @@ class ResidentLoop:
             s.plant_step(None, None, self.dt, self.substeps, to_resident=not self.use_estimator)
         self.t += self.dt
         self.tick += 1
+
+    def run(self, n: int):
+        """n ticks of step() with no read-back: every call of a tick is enqueue-only (the status of the reference generation is looked at
+        once, after the last tick).  What happened is in the episode record (episode())."""
+        for _ in range(int(n)):
+            self.step(check_refgen=False)
+        status = self.s.refgen_status()
+        if status.max() != 0:
+            raise RuntimeError(f"reference generation failed: {status}")
+
+    def episode(self, want_trace: bool = False) -> dict:
+        """The episode records of the run so far (HunterSolver.plant_episode)."""
+        if not self.has_episode:
+            raise ValueError("ResidentLoop was built without episode=")
+        return self.s.plant_episode(want_trace)
+
+
+def episode_summary(record: dict, start=None, dt: float = 0.002) -> dict:
+    """Per instance, from the episode record alone (HunterSolver.plant_episode): survived (no end so far), end_tick and end_cause (-1 and
+    abi.HB_EP_RUNNING while it runs), distance_x / distance_y travelled from `start` ([B][3] or None: the record's START_POS) to the last
+    upright tick, mean_speed = horizontal distance / (TICKS dt), slip_share = SLIP_TICKS / TICKS, duty_factor[B][4] = CONTACT_TICKS / TICKS
+    (ratios are 0 for an instance with no upright tick)."""
+    ticks = np.asarray(record["TICKS"], dtype=float)
+    start = np.asarray(record["START_POS"] if start is None else start, dtype=float).reshape(len(ticks), 3)
+    dx, dy = record["LAST_BASE"][:, 0] - start[:, 0], record["LAST_BASE"][:, 1] - start[:, 1]
+    per_tick = np.where(ticks > 0, 1.0 / np.maximum(ticks, 1.0), 0.0)
+    return dict(survived=np.asarray(record["END_TICK"]) < 0, end_tick=np.asarray(record["END_TICK"]).copy(),
+                end_cause=np.asarray(record["END_CAUSE"]).copy(), distance_x=dx, distance_y=dy,
+                mean_speed=np.hypot(dx, dy) * per_tick / dt, slip_share=record["SLIP_TICKS"] * per_tick,
+                duty_factor=record["CONTACT_TICKS"] * per_tick[:, None])

@@ -35,6 +35,7 @@ ABI_SYMBOLS = [
     "hb_plant_set_contact_model", "hb_plant_set_external_wrench", "hb_plant_get_contact",
     "hb_plant_set_joint_model", "hb_plant_get_joints", "hb_plant_step_hybrid", "hb_plant_get_actuator",
     "hb_plant_set_terrain", "hb_plant_get_terrain",
+    "hb_plant_set_episode", "hb_plant_get_episode",
 ]
 # include/hunter_lcm.h
 LCM_SYMBOLS = ["hb_lcm_fingerprint", "hb_lcm_encoded_size", "hb_lcm_field_count", "hb_lcm_encode", "hb_lcm_decode", "hb_lcm_frame", "hb_lcm_unframe",
@@ -337,6 +338,25 @@ class HunterSolver:
         what the contact model amounts to."""
         out = dict(plane=np.zeros((self.B, 4)), mu=np.zeros((self.B, 4)), frame=np.zeros((self.B, 3, 3)))
         self._check(self.lib.hb_plant_get_terrain(self.ctx, *[_p(a) for a in out.values()]), "hb_plant_get_terrain")
+        return out
+
+    # ---- per-instance episode record and stop-on-fall (hb_plant_set_episode) -----------------------------------------------------
+    def plant_set_episode(self, cfg: "abi.HbEpisodeConfig" = None):
+        """cfg None: no episode; abi.make_episode_config(...): the record of every instance (re)starts from the plant's present state and
+        is updated on the device after every plant step."""
+        self._check(self.lib.hb_plant_set_episode(self.ctx, None if cfg is None else C.byref(cfg)), "hb_plant_set_episode")
+        self._episode_capacity = 0 if cfg is None else int(cfg.trace_capacity)
+
+    def plant_episode(self, want_trace=False):
+        """The episode records -> dict of named arrays (abi.EPISODE_INT_FIELDS / EPISODE_DOUBLE_FIELDS: [B] or [B][n]); want_trace adds
+        trace[B][trace_capacity][8] (columns abi.EPISODE_TRACE_COLUMNS; the first N_TRACE samples of an instance are valid)."""
+        irec, drec = np.zeros((self.B, abi.HB_EP_NI), dtype=np.int32), np.zeros((self.B, abi.HB_EP_ND))
+        cap = getattr(self, "_episode_capacity", 0)
+        trace = np.zeros((self.B, cap, abi.HB_EP_TRACE_W)) if want_trace else None
+        self._check(self.lib.hb_plant_get_episode(self.ctx, _p(irec), _p(drec), _p(trace) if cap else None), "hb_plant_get_episode")
+        out = abi.split_episode_record(irec, drec)
+        if want_trace:
+            out["trace"] = trace
         return out
 
     # ---- sensors from the plant (hb_plant_sense) and the estimator on them ------------------------------------------------

@@ -402,6 +402,82 @@ int32_t hb_plant_step_hybrid(hb_ctx* ctx, const double* pos_des, const double* v
  * filter (hunter_lcm.h hb_plant_step_lcm); any may be NULL.  HB_ERR_STATE before hb_plant_reset. */
 int32_t hb_plant_get_actuator(hb_ctx* ctx, double* tau_first, double* tau_mean, int64_t* last_timestamp);
 
+/* ---- per-instance episode record and stop-on-fall ---------------------------------------------------------------------------------
+ * What a rollout produced, reduced per instance on the device, so that a batch of scenarios runs thousands of ticks without a read-back
+ * per tick.  Off by default.  With an episode in force the record is updated once after EVERY plant step, whatever the entry point
+ * (hb_plant_step, hb_plant_step_hybrid, hb_plant_step_lcm), the plant form and to_resident, by a kernel of its own (k_plant_episode)
+ * enqueued behind the plant kernel on the same stream; the plant kernels do not know of it.  An instance has an integer record
+ * irec[HB_EP_NI] and a double record drec[HB_EP_ND] (fields HB_EP_I_* / HB_EP_D_* below) and up to trace_capacity trace samples.
+ *
+ * The update of one instance after a step of length dt; k = number of steps the record has seen before this one:
+ *  1. STEPS = k + 1.  If any of q[16], v[16] is non-finite and FIRST_NONFINITE < 0: FIRST_NONFINITE = k.
+ *  2. If END_TICK >= 0 the record is frozen: return.
+ *  3. If the state is non-finite: END_TICK = k, END_CAUSE = HB_EP_NONFINITE, return (the tick contributes nothing).
+ *  4. (n, d) = the instance's plane: the terrain's if one is in force, else (e_z, ground_z) in contact model 1, else (e_z, 0).
+ *     height = n . q[0:3] - d, summed in the order x, y, z;  tilt = max(|q[4]|, |q[5]|) (pitch, roll).
+ *     fallen = contact model 1 has HB_CONTACT_FALLEN in its status word, or tilt_limit > 0 and tilt > tilt_limit.
+ *  5. If fallen: END_TICK = k, END_CAUSE = HB_EP_FALLEN; with stop_on_fall the instance's emergency-stop latch becomes 1; return.  The
+ *     record then holds the last upright tick.
+ *  6. Otherwise the tick is accumulated:  TICKS += 1;  LAST_BASE[6] = q[0:6];  HEIGHT_LAST = height, HEIGHT_MIN / HEIGHT_MAX;  TILT_MAX;
+ *     TAU_MAX[j] = max |tau_last[j]| with tau_last the torque the step applied (the saturated one under the joint model, the last
+ *     substep's in the hybrid forms: what hb_plant_sense reports);  WORK_ABS += dt (sum_j |tau_last[j] v[6 + j]|),  WORK_NET += dt (sum_j
+ *     tau_last[j] v[6 + j]), j upwards, dt multiplied after the sum;  once a WBC call has run, with st = the WBC status word:
+ *     WBC_STATUS_OR |= st, and if st != 0: WBC_FAIL_TICKS += 1 and FIRST_WBC_FAIL = k if it was < 0.
+ *     Contact model 1 only, per point c:  GAP_MIN = min gap_c (one value over the four points);  FN_MAX[c] = max n . lambda_c;
+ *     CONTACT_TICKS[c] += touching_c;  TOUCHDOWNS[c] counts the 0 -> 1 transitions of touching_c (the previous flags are kept in the record,
+ *     PREV_TOUCHING, "not touching" at the start);  for touching points only the tangential speed |pv_c - (n . pv_c) n| of the point
+ *     velocity pv_c feeds SLIP_SPEED_MAX, and a tick with any touching point faster than slip_speed: SLIP_TICKS += 1, FIRST_SLIP = k if it was
+ *     < 0.  Per instance: RES_MAX = max residual;  UNCONVERGED_TICKS counts HB_CONTACT_UNCONVERGED;  CONTACT_STATUS_OR.
+ *     Joint model only:  JRES_MAX,  JOINT_STATUS_OR,  CLAMP_TICKS = ticks with any of the bits 10..19 of the joint status word (a torque
+ *     saturated),  STOP_TICKS = ticks with any of the bits 0..9 (a stop active).
+ *     A field whose source is absent keeps its initial value.  No product is fused with a sum: the record equals the same reduction of
+ *     the per-tick outputs of hb_plant_get_state / _get_contact / _get_joints value for value.
+ *  7. Trace: if trace_every > 0, k % trace_every == 0 and N_TRACE < trace_capacity, one sample of HB_EP_TRACE_W doubles is appended:
+ *     (k, q[0], q[1], height, q[3], q[4], q[5], number of touching points).
+ * Initial values, from the plant's present state: START_POS[3] = q[0:3], LAST_BASE = q[0:6], HEIGHT_LAST = its height; HEIGHT_MIN and
+ * GAP_MIN +inf, HEIGHT_MAX -inf; the other maxima 0 (they are of non-negative quantities); counts, ORs and PREV_TOUCHING 0; END_CAUSE
+ * HB_EP_RUNNING; END_TICK and every FIRST_* -1.
+ * The MPC status word is not in the record: it lives on the MPC stream, and reading it here would order the two streams.
+ *
+ * stop_on_fall: the latch is the emergencyStopFlag_ mirror of hb_joint_set_flags.  From the next hb_joint_command on the instance's
+ * command is setCommand(0, 0, 0, 1, 0) (LeggedController.cpp:245-248) until the caller clears the latch with hb_joint_set_flags.
+ * Nothing else about the instance changes: the plant goes on integrating it, MPC and WBC go on running on it. */
+#define HB_EP_RUNNING 0
+#define HB_EP_FALLEN 1
+#define HB_EP_NONFINITE 2
+#define HB_EP_TRACE_W 8
+#define HB_EP_TRACE_MAX 4096
+#define HB_EP_JOINT_STOP_BITS 0x3ff
+#define HB_EP_JOINT_CLAMP_BITS 0xffc00
+enum {   /* irec */
+  HB_EP_I_STEPS = 0, HB_EP_I_TICKS = 1, HB_EP_I_END_TICK = 2, HB_EP_I_END_CAUSE = 3, HB_EP_I_FIRST_NONFINITE = 4, HB_EP_I_N_TRACE = 5,
+  HB_EP_I_WBC_STATUS_OR = 6, HB_EP_I_WBC_FAIL_TICKS = 7, HB_EP_I_FIRST_WBC_FAIL = 8, HB_EP_I_CONTACT_TICKS = 9 /* [4] */,
+  HB_EP_I_TOUCHDOWNS = 13 /* [4] */, HB_EP_I_PREV_TOUCHING = 17 /* [4] */, HB_EP_I_SLIP_TICKS = 21, HB_EP_I_FIRST_SLIP = 22,
+  HB_EP_I_UNCONVERGED_TICKS = 23, HB_EP_I_CONTACT_STATUS_OR = 24, HB_EP_I_JOINT_STATUS_OR = 25, HB_EP_I_CLAMP_TICKS = 26,
+  HB_EP_I_STOP_TICKS = 27, HB_EP_NI = 28
+};
+enum {   /* drec */
+  HB_EP_D_START_POS = 0 /* [3] */, HB_EP_D_LAST_BASE = 3 /* [6] */, HB_EP_D_HEIGHT_LAST = 9, HB_EP_D_HEIGHT_MIN = 10, HB_EP_D_HEIGHT_MAX = 11,
+  HB_EP_D_TILT_MAX = 12, HB_EP_D_TAU_MAX = 13 /* [10] */, HB_EP_D_WORK_ABS = 23, HB_EP_D_WORK_NET = 24, HB_EP_D_GAP_MIN = 25,
+  HB_EP_D_FN_MAX = 26 /* [4] */, HB_EP_D_SLIP_SPEED_MAX = 30, HB_EP_D_RES_MAX = 31, HB_EP_D_JRES_MAX = 32, HB_EP_ND = 33
+};
+typedef struct hb_episode_config {
+  double slip_speed;      /* m/s, >= 0: a touching point faster than this along the ground counts as slipping */
+  double tilt_limit;      /* rad, >= 0; 0: none.  max(|pitch|, |roll|) above it counts as fallen (works in contact model 0 too) */
+  int32_t stop_on_fall;   /* 0 / 1: the tick an instance is found fallen, its emergency-stop latch (hb_joint_set_flags) is set */
+  int32_t trace_every;    /* 0: no trace; n > 0: one trace sample every n-th tick while the instance is up */
+  int32_t trace_capacity; /* 0 .. HB_EP_TRACE_MAX samples per instance */
+  int32_t reserved[3];    /* 0 */
+} hb_episode_config;
+/* cfg NULL: off.  Otherwise (re)starts the record from the plant's present state.  The configuration survives hb_plant_reset, which
+ * restarts the record from the reset state; a change of contact model, joint model or terrain does not restart it.  With stop_on_fall the
+ * latch array is allocated as hb_joint_set_flags allocates it.  HB_ERR_STATE before hb_plant_reset; HB_ERR_ARG for a non-finite or
+ * out-of-range field or a nonzero `reserved` (the episode in force is kept). */
+int32_t hb_plant_set_episode(hb_ctx* ctx, const hb_episode_config* cfg);
+/* The records (any pointer may be NULL): irec[batch][HB_EP_NI], drec[batch][HB_EP_ND], trace[batch][trace_capacity][HB_EP_TRACE_W] (the
+ * first N_TRACE samples of an instance are valid, the rest zero).  HB_ERR_STATE before hb_plant_reset or with no episode in force. */
+int32_t hb_plant_get_episode(hb_ctx* ctx, int32_t* irec, double* drec, double* trace);
+
 /* ---- sensors from the plant: what LeggedController::updateStateEstimation reads, computed on the device -----------
  * hb_plant_sense turns the plant's state into the sensor arrays of hb_estimator_update and leaves them on the device
  * (plant-owned arrays [batch][4|3|3|10|10|10] and int [batch][4]); hb_estimator_update_resident /

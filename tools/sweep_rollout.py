@@ -1,0 +1,134 @@
+#!/usr/bin/env python3
+"""Scenario sweeps of the closed loop on the device plant, one batch each, read from the per-instance episode record alone
+(hb_plant_set_episode): no getter is called between the first tick and the last.
+
+    python tools/sweep_rollout.py                       the friction sweep (B = 8) and the slope sweep (B = 4) of DESIGN.md 5 item 20, 600 ticks
+    python tools/sweep_rollout.py --grid 64 64 --ticks 5000   friction x slope on a grid, one scenario per instance (4096), static schedules
+    python tools/sweep_rollout.py --readback            the two sweeps once more with the per-tick read-back loop the findings of items 17 - 20
+                                                        were made with, for the wall time per tick of both
+
+Every robot trots at (0.2, 0) m/s; fall_height 0.3 m, slip = tangential speed of a touching point above 0.05 m/s.  Ticks are counted
+from 0: "end 263" is the 264th step."""
+import argparse
+import sys
+import time
+from pathlib import Path
+
+import numpy as np
+
+sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
+from hunter_bipedal_control_amd import abi, ingest  # noqa: E402
+from hunter_bipedal_control_amd.rollout import ResidentLoop, episode_summary  # noqa: E402
+from hunter_bipedal_control_amd.solver import HunterSolver  # noqa: E402
+
+FRICTION = [0.7, 0.5, 0.4, 0.3, 0.2, 0.15, 0.1, 0.05]
+SLOPES = [0.0, 0.05, 0.1, 0.2]
+CAUSE = {abi.HB_EP_RUNNING: "-", abi.HB_EP_FALLEN: "fallen", abi.HB_EP_NONFINITE: "non-finite"}
+
+
+def normals_of(pitch):
+    """Unit normals of pitch slopes, downhill along +x."""
+    pitch = np.asarray(pitch, dtype=float)
+    return np.stack([np.sin(pitch), np.zeros_like(pitch), np.cos(pitch)], axis=1)
+
+
+def make_loop(params, mu, pitch, ticks, static, joint_model):
+    """One batch: instance i trots on a plane of pitch[i] with friction mu[i] under all four points."""
+    B = len(mu)
+    s = HunterSolver(params, batch=B, max_nodes=108)
+    cmd = np.tile([0.2, 0.0, 0.0, 0.0], (B, 1))
+    horizon = 100 * params["config"]["dt"]
+    loop = ResidentLoop(s, params, ["trot"] * B, cmd, contact_config=dict(fall_height=0.3), joint_model=joint_model,
+                        terrain=dict(plane=normals_of(pitch), mu=np.repeat(np.asarray(mu, dtype=float)[:, None], 4, axis=1)),
+                        static_schedule_until=(ticks * 0.002 + horizon + 1.5) if static else 0.0, episode=dict(slip_speed=0.05))
+    return s, loop
+
+
+def run_record(params, mu, pitch, ticks, static=False, joint_model=None):
+    """-> (episode record, wall seconds of the ticks)."""
+    s, loop = make_loop(params, mu, pitch, ticks, static, joint_model)
+    try:
+        s.sync()
+        t0 = time.perf_counter()
+        loop.run(ticks)
+        rec = loop.episode()
+        return rec, time.perf_counter() - t0
+    finally:
+        s.close()
+
+
+def run_readback(params, mu, pitch, ticks, joint_model=None):
+    """The loop of the earlier findings: three synchronising getters after every tick, reduced in numpy -> (figures, wall seconds)."""
+    s, loop = make_loop(params, mu, pitch, ticks, False, joint_model)
+    try:
+        plane = s.plant_get_terrain()["plane"]
+        B = len(mu)
+        slip_ticks, first_slip, fall = np.zeros(B, dtype=int), np.full(B, -1), np.full(B, -1)
+        s.sync()
+        t0 = time.perf_counter()
+        for tick in range(ticks):
+            loop.step()
+            st, con, _ = s.plant_state(), s.plant_contact(), s.plant_get_joints()
+            pv = con["point_vel"]
+            vn = np.einsum("bcx,bx->bc", pv, plane[:, :3])
+            with np.errstate(over="ignore", invalid="ignore"):
+                speed = np.linalg.norm(pv - vn[:, :, None] * plane[:, None, :3], axis=2)
+            slipping = ((speed > 0.05) & (con["touching"] != 0)).any(axis=1) & (fall < 0)
+            slip_ticks += slipping
+            first_slip = np.where((first_slip < 0) & slipping, tick, first_slip)
+            fall = np.where((fall < 0) & ((con["status"] & abi.HB_CONTACT_FALLEN) != 0), tick, fall)
+        wall = time.perf_counter() - t0
+        return dict(slip_ticks=slip_ticks, first_slip=first_slip, fall=fall, z=st["q"][:, 2]), wall
+    finally:
+        s.close()
+
+
+def table(label, values, rec, dt=0.002):
+    """One row per instance; %g columns, since a robot that is lost can leave very large values at its last finite tick."""
+    summ = episode_summary(rec, dt=dt)
+    heads = (label, "end", "cause", "nonfin", "z", "height", "tilt", "tiltmax", "dist_x", "speed", "slipT", "first", "slipmax", "wbcF", "first", "taumax", "duty")
+    print(" ".join(f"{h:>10}" for h in heads))
+    for i, val in enumerate(values):
+        base = rec["LAST_BASE"][i]
+        row = (val, int(rec["END_TICK"][i]), CAUSE[int(rec["END_CAUSE"][i])], int(rec["FIRST_NONFINITE"][i]), base[2], rec["HEIGHT_LAST"][i],
+               max(abs(base[4]), abs(base[5])), rec["TILT_MAX"][i], summ["distance_x"][i], summ["mean_speed"][i], int(rec["SLIP_TICKS"][i]),
+               int(rec["FIRST_SLIP"][i]), rec["SLIP_SPEED_MAX"][i], int(rec["WBC_FAIL_TICKS"][i]), int(rec["FIRST_WBC_FAIL"][i]), rec["TAU_MAX"][i].max(),
+               summ["duty_factor"][i].mean())
+        print(" ".join(f"{x:>10}" if isinstance(x, (str, int)) else f"{x:10.4g}" for x in row))
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--ticks", type=int, default=600)
+    ap.add_argument("--grid", type=int, nargs=2, metavar=("N_MU", "N_SLOPE"), help="friction 0.05 .. 0.7 x pitch 0 .. 0.1 rad, one instance per pair")
+    ap.add_argument("--joint-model", action="store_true", help="the joints of the reference's MuJoCo model instead of ideal joints")
+    ap.add_argument("--readback", action="store_true", help="also time the per-tick read-back loop on the two sweeps")
+    args = ap.parse_args()
+    params = ingest.load_packaged()
+    jm = {} if args.joint_model else None
+    if args.grid:
+        n_mu, n_sl = args.grid
+        mus, slopes = np.linspace(0.05, 0.7, n_mu), np.linspace(0.0, 0.1, n_sl)
+        mu, pitch = np.repeat(mus, n_sl), np.tile(slopes, n_mu)
+        rec, wall = run_record(params, mu, pitch, args.ticks, static=True, joint_model=jm)
+        up = (rec["END_TICK"] < 0).reshape(n_mu, n_sl)
+        end = np.where(rec["END_TICK"] < 0, args.ticks, rec["END_TICK"]).reshape(n_mu, n_sl)
+        print(f"grid {n_mu} x {n_sl} = {len(mu)} instances, {args.ticks} ticks: {wall:.2f} s wall, {1e3 * wall / args.ticks:.3f} ms per tick; "
+              f"{int(up.sum())} instances up at the end, {int((rec['FIRST_NONFINITE'] >= 0).sum())} went non-finite")
+        print("survivors per slope column (of", n_mu, "friction values):", up.sum(axis=0).tolist())
+        print("survivors per friction row (of", n_sl, "slopes):", up.sum(axis=1).tolist())
+        print("median end tick per slope column:", np.median(end, axis=0).astype(int).tolist())
+        print("median end tick per friction row:", np.median(end, axis=1).astype(int).tolist())
+        return
+    for name, mu, pitch, values in (("friction", FRICTION, [0.0] * len(FRICTION), FRICTION), ("slope", [0.7] * len(SLOPES), SLOPES, SLOPES)):
+        rec, wall = run_record(params, mu, pitch, args.ticks, joint_model=jm)
+        print(f"-- {name} sweep, B = {len(mu)}, {args.ticks} ticks, run(): {1e3 * wall / args.ticks:.3f} ms per tick")
+        table("mu" if name == "friction" else "pitch", values, rec)
+        if args.readback:
+            fig, wall_rb = run_readback(params, mu, pitch, args.ticks, joint_model=jm)
+            print(f"   per-tick read-back loop: {1e3 * wall_rb / args.ticks:.3f} ms per tick; slip ticks {fig['slip_ticks'].tolist()} first {fig['first_slip'].tolist()} "
+                  f"fall {fig['fall'].tolist()}")
+
+
+if __name__ == "__main__":
+    main()
