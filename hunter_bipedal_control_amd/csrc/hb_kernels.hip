@@ -24,6 +24,7 @@
 #include "hb_joints.hpp"
 #include "hb_sensors.hpp"
 #include "hb_layout.hpp"
+#include "hb_iterate.hpp"
 #include "hb_wavectx.hpp"
 
 using namespace hb;
@@ -37,108 +38,30 @@ __global__ void k_set_x0(Batch b) {
   b.x[size_t(inst) * (b.Nmax + 1) * HB_NX + c] = b.x0[i];
 }
 
-// cold start: x_k = x0, u_k = weight compensation of mode_k (LeggedRobotInitializer.cpp:67-77)
+// cold start of the instances the mask selects (all without one): hb_iterate.hpp cold_start_entry per (node, lane)
 __global__ void k_cold_start(Batch b, const DevModel* __restrict__ M, const unsigned char* mask) {
   const int k = blockIdx.x, inst = blockIdx.y;
   const int lane = threadIdx.x;
   if (mask && !mask[inst]) return;
   if (k == 0 && lane == 0) { b.grid_dirty[inst] = 0; b.mpc_status[inst] = HB_INST_OK; }
-  if (k > b.n_nodes[inst]) return;
-  double* xk = b.x + (size_t(inst) * (b.Nmax + 1) + k) * HB_NX;
-  if (lane < HB_NX) xk[lane] = b.x0[inst * HB_NX + lane];
-  if (k < b.n_nodes[inst] && lane < HB_NU) {
-    bool cf[HB_NC];
-    mode_flags(b.mode[size_t(inst) * b.Nmax + k], cf);
-    int nc = 0;
-    for (int i = 0; i < HB_NC; ++i) nc += cf[i];
-    double v = 0.0;
-    if (lane < 12 && lane % 3 == 2 && cf[lane / 3]) v = M->total_mass * M->gravity / nc;
-    b.u[(size_t(inst) * b.Nmax + k) * HB_NU + lane] = v;
-  }
+  cold_start_entry(*M, b.n_nodes + inst, b.mode + size_t(inst) * b.Nmax, b.x0 + inst * HB_NX, k, lane, b.x + size_t(inst) * (b.Nmax + 1) * HB_NX,
+                   b.u + size_t(inst) * b.Nmax * HB_NU);
 }
 
-// Warm start across MPC calls: the previous call's iterate (xp, up on the grid tp / modep / np_nodes) is brought onto the new node
-// tables — OCS2 SqpSolver::initializeStateInputTrajectories [OCS2-knowledge]: inside the previous horizon the state at every
-// new node time and the input at the start of every new interval are interpolated linearly from the previous solution; beyond
-// it the initializer takes over (LeggedRobotInitializer.cpp:67-77: the state is carried on, the input is the weight
-// compensation of the interval's mode).  Defined here: an input is HELD instead of interpolated across a mode
-// switch of the previous solution (the neighbouring node belongs to another contact configuration), and the last previous
-// interval holds its input.  One thread per (instance, node); instances whose tables did not change are left alone.
+// Warm start across MPC calls (hb_iterate.hpp warm_shift_entry): the previous call's iterate (xp, up on the grid tp / modep / np_nodes)
+// is brought onto the new node tables; instances whose tables did not change are copied.
 constexpr int kWarmShiftThreads = 256;
 __global__ __launch_bounds__(kWarmShiftThreads) void k_warm_shift(Batch b, const DevModel* __restrict__ M) {
-  // one thread per (node, entry index) of an instance: it moves state entry e AND input entry e of its node (the interval lookup is the
-  // same for both), consecutive threads = consecutive entries, every lane of a wavefront has work (one block per node used 44 of 64
-  // lanes; the kernel is a chain of three dependent round trips per thread, so what it costs is wavefronts / resident wavefronts).
-  // Instances whose tables did
-  // not change keep their iterate (plain copy from the previous buffers: the host swapped them); the others are interpolated
-  // from the previous solution on ITS time grid.  The old interval that contains the node time is found by bisection (a
-  // linear scan was a chain of up to N dependent loads per block: 0.51 ms per 4096 x 100 launch, 0.06 ms of it memory traffic).
+  // one thread per (node, entry index) of an instance, consecutive threads = consecutive entries, every lane of a wavefront has work (one
+  // block per node used 44 of 64 lanes; the kernel is a chain of three dependent round trips per thread, so what it costs is wavefronts /
+  // resident wavefronts).
   const int flat = blockIdx.x * kWarmShiftThreads + threadIdx.x, inst = blockIdx.y;
-  static_assert(HB_NX == HB_NU, "one thread moves entry e of the state and of the input");
   const int k = flat / HB_NX, e = flat - k * HB_NX;
   const size_t N = b.Nmax;
-  if (k > int(N)) return;
-  constexpr bool is_x = true, is_u = true;
-  const double* xp = b.xp + size_t(inst) * (N + 1) * HB_NX;
-  const double* up = b.up + size_t(inst) * N * HB_NU;
-  double* xk = b.x + (size_t(inst) * (N + 1) + k) * HB_NX;
-  double* uk = b.u + (size_t(inst) * N + k) * HB_NU;
-  if (!b.grid_dirty[inst]) {
-    if (is_x) xk[e] = xp[size_t(k) * HB_NX + e];
-    if (is_u && k < int(N)) uk[e] = up[size_t(k) * HB_NU + e];
-    return;
-  }
-  const int n = b.n_nodes[inst], np = b.np_nodes[inst];
-  if (k > n) return;
-  const double* tp = b.tp + size_t(inst) * (N + 1);
-  const int* mp = b.modep + size_t(inst) * N;
-  const double t = b.t[size_t(inst) * (N + 1) + k];
-  // old interval that contains t: the largest i in [0, np - 1] with tp[i] <= t (0 if there is none)
-  // Between two MPC calls the grid moves by a fraction of an interval, so the answer is k, k + 1 or k - 1 almost always: those three
-  // candidates are tested first with loads that do not depend on one another (one round trip); the bisection (up to seven dependent
-  // loads per block) is the fallback.  tp is non-decreasing: i is the answer iff tp[i] <= t and (i is the last or tp[i + 1] > t).
-  int lo = 0, hi = np > 0 ? np - 1 : 0;
-  {
-    const int last = hi;
-    const int c0 = min(max(k - 1, 0), last);
-    const double t0 = tp[c0], t1 = tp[min(c0 + 1, last)], t2 = tp[min(c0 + 2, last)], t3 = tp[min(c0 + 3, last)];
-    const double tc[4] = {t0, t1, t2, t3};
-    for (int d = 0; d < 3; ++d) {
-      const int c = c0 + d;
-      if (c <= last && tc[d] <= t && (c == last || tc[d + 1] > t)) { lo = hi = c; break; }
-    }
-  }
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (tp[mid] <= t) lo = mid; else hi = mid - 1;
-  }
-  const int i = lo;
-  const bool beyond = np <= 0 || t >= tp[np], before = !beyond && t <= tp[0];
-  const double a = (beyond || before) ? 0.0 : (t - tp[i]) / (tp[i + 1] - tp[i]);
-  if (is_x) {
-    double v;
-    if (beyond) v = xp[size_t(np > 0 ? np : 0) * HB_NX + e];
-    else if (before) v = xp[e];
-    else v = (1.0 - a) * xp[size_t(i) * HB_NX + e] + a * xp[size_t(i + 1) * HB_NX + e];
-    xk[e] = v;
-  }
-  if (is_u && k < n) {
-    double v;
-    if (beyond) {  // beyond the previous horizon: weight compensation of this interval's mode
-      bool cf[HB_NC];
-      mode_flags(b.mode[size_t(inst) * N + k], cf);
-      int nc = 0;
-      for (int c = 0; c < HB_NC; ++c) nc += cf[c];
-      v = (e < 12 && e % 3 == 2 && cf[e / 3]) ? M->total_mass * M->gravity / nc : 0.0;
-    } else if (before) {
-      v = up[e];
-    } else if (i + 1 >= np || mp[i + 1] != mp[i]) {
-      v = up[size_t(i) * HB_NU + e];
-    } else {
-      v = (1.0 - a) * up[size_t(i) * HB_NU + e] + a * up[size_t(i + 1) * HB_NU + e];
-    }
-    uk[e] = v;
-  }
+  const WarmShiftInst w{b.Nmax, b.grid_dirty + inst, b.n_nodes + inst, b.t + size_t(inst) * (N + 1), b.mode + size_t(inst) * N, b.np_nodes + inst,
+                        b.tp + size_t(inst) * (N + 1), b.modep + size_t(inst) * N, b.xp + size_t(inst) * (N + 1) * HB_NX, b.up + size_t(inst) * N * HB_NU,
+                        b.x + size_t(inst) * (N + 1) * HB_NX, b.u + size_t(inst) * N * HB_NU};
+  warm_shift_entry(*M, w, k, e);
 }
 __global__ void k_grid_clean(Batch b) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;

@@ -567,20 +567,11 @@ def test_hierarchical_wbc_with_violated_level0_rows_matches_oracle(params, oracl
 
 
 def _oracle_policy(refs, t_now, xo, uo):
-    """Linear interpolation of the published solution at t_now and the planned mode (MPC_MRT evaluatePolicy)."""
-    B = xo.shape[0]
-    xd, ud, md = np.zeros((B, 22)), np.zeros((B, 22)), np.zeros(B, dtype=np.int32)
-    for i in range(B):
-        t = refs["t"][i]
-        n = refs["n_nodes"][i]
-        k = 0
-        while k < n - 1 and t_now[i] >= t[k + 1]:
-            k += 1
-        a = (t_now[i] - t[k]) / (t[k + 1] - t[k])
-        xd[i] = (1 - a) * xo[i, k] + a * xo[i, k + 1]
-        ud[i] = (1 - a) * uo[i, k] + a * uo[i, min(k + 1, n - 1)]
-        md[i] = refs["mode"][i, k]
-    return xd, ud, md
+    """Linear interpolation of the published solution at t_now and the planned mode (MPC_MRT evaluatePolicy): the twin of
+    tests/_iterate_twin.py, which clamps the weight to [0, 1] as the device does."""
+    from _iterate_twin import policy
+    p = policy(refs, xo, uo, t_now, None, np.ones(xo.shape[0], dtype=np.int32), None)
+    return p["x_des"], p["u_des"], p["mode"]
 
 
 @pytest.mark.parametrize("reg", [0, 2])
