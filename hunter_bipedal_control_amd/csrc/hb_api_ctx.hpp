@@ -106,6 +106,12 @@ struct hb_ctx {
   TerrainBatch terrain{};
   std::vector<double> terrain_host;
   bool terrain_on = false;
+  // per-instance model variation of contact model 1 (hb_plant_set_model_variation): modelvar_on while one is in force (the step calls then
+  // launch the varied kernels); the records are allocated on first use, modelvar_host is their host image (what hb_plant_get_model_variation
+  // reports).  Without a terrain the varied kernels read the level record of the configuration in force out of `terrain` (modelvar_level).
+  ModelVarBatch modelvar{};
+  std::vector<DevModel> modelvar_host;
+  bool modelvar_on = false;
   // actuator loop per substep and the simulator end of the LCM link (hb_plant_step_hybrid / _lcm, hb_plant_sense_lcm): allocated on first use
   ActuatorBatch act{};
   // per-instance episode record (hb_plant_set_episode): episode_on while one is in force (every plant step is then followed by

@@ -213,6 +213,18 @@ int32_t hb_plant_step(hb_ctx* ctx, const double* tau, const int32_t* contact, do
   HB_TRY(push(ctx, contact, p, p.contact, whole(ctx), &s));
   const double* dtau = tau ? p.tau : ctx->jc_out + 5 * B * HB_NJ;
   // the resident observation feeds the next hb_mpc_solve(NULL) / hb_refgen_update(NULL) on the MPC stream
+  if (ctx->contact_cfg.mode == 1 && ctx->modelvar_on && ctx->joints_on)
+    return plant_write(ctx, s, to_resident, dt, [&] {
+      hipLaunchKernelGGL(k_plant_varied_joints, dim3(ctx->B), dim3(64), 0, s, p, ctx->contact, ctx->joints, ctx->terrain.ter, ctx->contact_cfg,
+                         ctx->joint_model, ctx->dmodel, ctx->modelvar.mdl, dtau, contact ? p.contact : nullptr, ctx->w.mode, dt, substeps,
+                         to_resident ? ctx->w.rbd : nullptr, to_resident ? ctx->b.x0 : nullptr, to_resident ? ctx->w.t_now : nullptr);
+    });
+  if (ctx->contact_cfg.mode == 1 && ctx->modelvar_on)
+    return plant_write(ctx, s, to_resident, dt, [&] {
+      hipLaunchKernelGGL(k_plant_varied, dim3(ctx->B), dim3(64), 0, s, p, ctx->contact, ctx->terrain.ter, ctx->contact_cfg, ctx->dmodel,
+                         ctx->modelvar.mdl, dtau, contact ? p.contact : nullptr, ctx->w.mode, dt, substeps, to_resident ? ctx->w.rbd : nullptr,
+                         to_resident ? ctx->b.x0 : nullptr, to_resident ? ctx->w.t_now : nullptr);
+    });
   if (ctx->contact_cfg.mode == 1 && ctx->terrain_on && ctx->joints_on)
     return plant_write(ctx, s, to_resident, dt, [&] {
       hipLaunchKernelGGL(k_plant_terrain_joints, dim3(ctx->B), dim3(64), 0, s, p, ctx->contact, ctx->joints, ctx->terrain.ter, ctx->contact_cfg,
@@ -264,6 +276,16 @@ static int32_t plant_launch_hybrid(hb_ctx* ctx, const double* const cmd[5], cons
   double* rr = to_resident ? ctx->w.rbd : nullptr;
   double* rx = to_resident ? ctx->b.x0 : nullptr;
   double* rt = to_resident ? ctx->w.t_now : nullptr;
+  if (ctx->contact_cfg.mode == 1 && ctx->modelvar_on && ctx->joints_on)
+    return plant_write(ctx, s, to_resident, dt, [&] {
+      hipLaunchKernelGGL(k_plant_varied_joints_hybrid, dim3(ctx->B), dim3(64), 0, s, p, ctx->contact, ctx->joints, ctx->terrain.ter, ctx->act, c,
+                         ctx->contact_cfg, ctx->joint_model, ctx->dmodel, ctx->modelvar.mdl, dcontact, ctx->w.mode, dt, substeps, rr, rx, rt);
+    });
+  if (ctx->contact_cfg.mode == 1 && ctx->modelvar_on)
+    return plant_write(ctx, s, to_resident, dt, [&] {
+      hipLaunchKernelGGL(k_plant_varied_hybrid, dim3(ctx->B), dim3(64), 0, s, p, ctx->contact, ctx->terrain.ter, ctx->act, c, ctx->contact_cfg,
+                         ctx->dmodel, ctx->modelvar.mdl, dcontact, ctx->w.mode, dt, substeps, rr, rx, rt);
+    });
   if (ctx->contact_cfg.mode == 1 && ctx->terrain_on && ctx->joints_on)
     return plant_write(ctx, s, to_resident, dt, [&] {
       hipLaunchKernelGGL(k_plant_terrain_joints_hybrid, dim3(ctx->B), dim3(64), 0, s, p, ctx->contact, ctx->joints, ctx->terrain.ter, ctx->act, c,
@@ -336,6 +358,24 @@ int32_t hb_plant_get_state(hb_ctx* ctx, double* q, double* v, double* rbd, doubl
   return HB_OK;
 }
 
+// While a model variation is in force without a terrain, the varied kernels (the terrain forms) read the level record of the contact
+// configuration in force out of the terrain array: (0, 0, 1, ground_z), cfg.mu, T = I for every instance — the step without a terrain,
+// value for value.  Called wherever the variation, the terrain or the configuration changes; on ctx->s_wbc, after its earlier work.
+static int32_t modelvar_level(hb_ctx* ctx) {
+  if (!ctx->modelvar_on || ctx->terrain_on) return HB_OK;
+  TerrainBatch& t = ctx->terrain;
+  if (!t.ter) {
+    HB_HIP(alloc_fields(ctx, t));
+    t.B = ctx->B;
+  }
+  const hb_contact_config& K = ctx->contact_cfg;
+  const double level[Terrain::size] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0, K.ground_z, K.mu, K.mu, K.mu, K.mu};
+  std::vector<double> rec(size_t(ctx->B) * Terrain::size);
+  for (size_t i = 0; i < size_t(ctx->B); ++i) std::memcpy(rec.data() + i * Terrain::size, level, sizeof level);
+  HB_HIP(hipStreamSynchronize(ctx->s_wbc));
+  return push(ctx, rec.data(), t, t.ter, whole(ctx));
+}
+
 int32_t hb_plant_set_contact_model(hb_ctx* ctx, const hb_contact_config* cfg) {
   HB_ENTER_ARGS(false);
   HB_FAIL_IF(!ctx->plant_ready, HB_ERR_STATE, "hb_plant_set_contact_model: call hb_plant_reset first");
@@ -357,6 +397,8 @@ int32_t hb_plant_set_contact_model(hb_ctx* ctx, const hb_contact_config* cfg) {
   }
   ctx->contact_cfg = ground ? *cfg : hb_contact_config{};
   if (!ground) ctx->terrain_on = false;   // the terrain belongs to contact model 1
+  if (!ground) ctx->modelvar_on = false;  // ... and so does the model variation
+  HB_TRY(modelvar_level(ctx));            // (the level record follows the configuration)
   if (!ground && ctx->joints_on) {   // the joint model belongs to contact model 1
     ctx->joints_on = false;
     HB_TRY(joints_clear(ctx, ctx->s_wbc));
@@ -491,6 +533,7 @@ int32_t hb_plant_set_terrain(hb_ctx* ctx, const double* plane, const double* mu)
     ctx->terrain_host = std::move(rec);
   }
   ctx->terrain_on = plane || mu;
+  HB_TRY(modelvar_level(ctx));
   // the warm start is expressed in the frame of before
   HB_HIP(hipMemsetAsync(c.imp, 0, field_count(ctx, c, c.imp) * 8, ctx->s_wbc));
   HB_HIP(hipStreamSynchronize(ctx->s_wbc));
@@ -507,6 +550,46 @@ int32_t hb_plant_get_terrain(hb_ctx* ctx, double* plane, double* mu, double* fra
     if (plane) { for (int a = 0; a < 3; ++a) plane[4 * i + a] = r[Terrain::T + 3 * a + 2]; plane[4 * i + 3] = r[Terrain::d]; }
     if (mu) std::memcpy(mu + 4 * i, r + Terrain::mu, 4 * sizeof(double));
     if (frame) std::memcpy(frame + 9 * i, r + Terrain::T, 9 * sizeof(double));
+  }
+  return HB_OK;
+}
+
+// ---- per-instance model variation of contact model 1 (include/hunter_hip.h above hb_plant_set_model_variation) --------------------------
+int32_t hb_plant_set_model_variation(hb_ctx* ctx, const double* mass_scale, const double* payload) {
+  HB_ENTER_ARGS(false);
+  HB_TRY(contact_ready(ctx, "hb_plant_set_model_variation"));
+  const size_t B = ctx->B;
+  const bool on = mass_scale || payload;
+  std::vector<DevModel> img(on ? B : 0);
+  int bad = 0;
+  if (const char* why = on ? modelvar_compose_batch(ctx->hmodel, int(B), mass_scale, payload, img.data(), &bad) : nullptr) {
+    ctx->err = "hb_plant_set_model_variation: instance " + std::to_string(bad) + " has " + why + " (the variation in force is kept)";
+    return HB_ERR_ARG;
+  }
+  HB_ENTER_DEVICE();
+  HB_HIP(hipStreamSynchronize(ctx->s_wbc));  // (a step in flight still runs on the models it was launched with)
+  if (on) {
+    ModelVarBatch& m = ctx->modelvar;
+    if (!m.mdl) {
+      HB_HIP(alloc_fields(ctx, m));
+      m.B = ctx->B;
+    }
+    HB_TRY(push(ctx, img.data(), m, m.mdl, whole(ctx)));
+    ctx->modelvar_host = std::move(img);
+  }
+  ctx->modelvar_on = on;
+  return modelvar_level(ctx);
+}
+
+int32_t hb_plant_get_model_variation(hb_ctx* ctx, double* mass, double* com, double* inertia, double* total_mass) {
+  HB_ENTER_ARGS(false);
+  HB_TRY(contact_ready(ctx, "hb_plant_get_model_variation"));
+  for (size_t i = 0; i < size_t(ctx->B); ++i) {
+    const DevModel& d = ctx->modelvar_on ? ctx->modelvar_host[i] : ctx->hmodel;
+    if (mass) std::memcpy(mass + HB_NBODY * i, d.mass, sizeof d.mass);
+    if (com) std::memcpy(com + 3 * HB_NBODY * i, d.com, sizeof d.com);
+    if (inertia) std::memcpy(inertia + 6 * HB_NBODY * i, d.inertia, sizeof d.inertia);
+    if (total_mass) total_mass[i] = d.total_mass;
   }
   return HB_OK;
 }

@@ -1114,6 +1114,107 @@ __global__ __launch_bounds__(64) void k_plant_terrain_joints_hybrid(PlantBatch p
                           lds + JOINT_LDS_TOTAL + ACT_LDS);
   if (cx.lane == 0) plant_publish(p, M, i, dt, res_rbd, res_x0, res_t);
 }
+// ---- the varied forms of the four terrain kernels (hb_plant_set_model_variation): the step runs on the instance's own DevModel -----------
+// Mvar: [B] records (hb_layout.hpp ModelVarBatch); the instance's is uniform over the workgroup, so its constants stay scalar loads.  The
+// step routines take Mvar[i]; plant_publish keeps the nominal M, the controller's view.  ter: as above — without a terrain in force the host
+// keeps the level record of the configuration there.  Lane contexts of their own for the reason above ActuatorCtx.
+struct VariedCtx : DeviceCtx {};
+struct VariedActuatorCtx : DeviceCtx {};
+__global__ __launch_bounds__(64) void k_plant_varied(PlantBatch p, ContactBatch cb, const double* __restrict__ ter, hb_contact_config K,
+                                                     const DevModel* __restrict__ M, const DevModel* __restrict__ Mvar, const double* tau, const int* contact,
+                                                     const int* mode, double dt, int substeps, double* res_rbd, double* res_x0, double* res_t) {
+  const int i = blockIdx.x;
+  __shared__ double lds[CONTACT_LDS_TOTAL + TER_LDS];
+  __shared__ int all_on[HB_NC];
+  const VariedCtx cx;
+  if (cx.lane < HB_NC) {
+    int flag;
+    if (contact) flag = contact[4 * i + cx.lane];
+    else { bool cf[HB_NC]; mode_flags(mode[i], cf); flag = cf[cx.lane] ? 1 : 0; }
+    p.contact_last[4 * i + cx.lane] = flag;
+    all_on[cx.lane] = 1;
+  }
+  if (cx.lane < HB_NJ) p.tau_last[10 * i + cx.lane] = tau[10 * i + cx.lane];
+  if (cx.lane < TER_LDS) lds[CONTACT_LDS_TOTAL + cx.lane] = ter[TER_LDS * i + cx.lane];
+  __syncthreads();
+  const ContactOut out{cb.gap + 4 * i, cb.pvel + 12 * i, cb.res + i, cb.touching + 4 * i, cb.status + i};
+  contact_step<false, true>(cx, Mvar[i], p.q + 16 * i, p.v + 16 * i, cb.imp + 12 * i, tau + 10 * i, cb.use_wrench ? cb.wrench + 6 * i : nullptr, all_on, K,
+                            p.eps, dt, substeps, lds, p.lambda + 12 * i, p.vdot + 16 * i, out, nullptr, lds + CONTACT_LDS_TOTAL);
+  if (cx.lane == 0) plant_publish(p, M, i, dt, res_rbd, res_x0, res_t);
+}
+__global__ __launch_bounds__(64) void k_plant_varied_joints(PlantBatch p, ContactBatch cb, JointBatch jb, const double* __restrict__ ter, hb_contact_config K,
+                                                            hb_joint_model J, const DevModel* __restrict__ M, const DevModel* __restrict__ Mvar,
+                                                            const double* tau, const int* contact, const int* mode, double dt, int substeps, double* res_rbd,
+                                                            double* res_x0, double* res_t) {
+  const int i = blockIdx.x;
+  __shared__ double lds[JOINT_LDS_TOTAL + TER_LDS];
+  __shared__ int all_on[HB_NC];
+  const VariedCtx cx;
+  if (cx.lane < HB_NC) {
+    int flag;
+    if (contact) flag = contact[4 * i + cx.lane];
+    else { bool cf[HB_NC]; mode_flags(mode[i], cf); flag = cf[cx.lane] ? 1 : 0; }
+    p.contact_last[4 * i + cx.lane] = flag;
+    all_on[cx.lane] = 1;
+  }
+  if (cx.lane < TER_LDS) lds[JOINT_LDS_TOTAL + cx.lane] = ter[TER_LDS * i + cx.lane];
+  __syncthreads();
+  const ContactOut out{cb.gap + 4 * i, cb.pvel + 12 * i, cb.res + i, cb.touching + 4 * i, cb.status + i};
+  const JointOut jout{jb.tau_applied + 10 * i, jb.friction_torque + 10 * i, jb.limit_torque + 10 * i, jb.res + i, jb.status + i};
+  joints_step<false, true>(cx, Mvar[i], p.q + 16 * i, p.v + 16 * i, cb.imp + 12 * i, jb.imp + 20 * i, tau + 10 * i, cb.use_wrench ? cb.wrench + 6 * i : nullptr,
+                           all_on, K, J, p.eps, dt, substeps, lds, p.lambda + 12 * i, p.vdot + 16 * i, p.tau_last + 10 * i, out, jout, nullptr,
+                           lds + JOINT_LDS_TOTAL);
+  if (cx.lane == 0) plant_publish(p, M, i, dt, res_rbd, res_x0, res_t);
+}
+__global__ __launch_bounds__(64) void k_plant_varied_hybrid(PlantBatch p, ContactBatch cb, const double* __restrict__ ter, ActuatorBatch a, ActuatorCmd c,
+                                                            hb_contact_config K, const DevModel* __restrict__ M, const DevModel* __restrict__ Mvar,
+                                                            const int* contact, const int* mode, double dt, int substeps, double* res_rbd, double* res_x0,
+                                                            double* res_t) {
+  const int i = blockIdx.x;
+  __shared__ double lds[CONTACT_LDS_TOTAL + ACT_LDS + TER_LDS];
+  __shared__ int all_on[HB_NC];
+  const VariedActuatorCtx cx;
+  if (cx.lane < HB_NC) {
+    int flag;
+    if (contact) flag = contact[4 * i + cx.lane];
+    else { bool cf[HB_NC]; mode_flags(mode[i], cf); flag = cf[cx.lane] ? 1 : 0; }
+    p.contact_last[4 * i + cx.lane] = flag;
+    all_on[cx.lane] = 1;
+  }
+  if (cx.lane < TER_LDS) lds[CONTACT_LDS_TOTAL + ACT_LDS + cx.lane] = ter[TER_LDS * i + cx.lane];
+  __syncthreads();
+  const ContactOut out{cb.gap + 4 * i, cb.pvel + 12 * i, cb.res + i, cb.touching + 4 * i, cb.status + i};
+  const HybridActuator act = actuator_of(c, a, i, lds + CONTACT_LDS_TOTAL);
+  contact_step<true, true>(cx, Mvar[i], p.q + 16 * i, p.v + 16 * i, cb.imp + 12 * i, nullptr, cb.use_wrench ? cb.wrench + 6 * i : nullptr, all_on, K, p.eps,
+                           dt, substeps, lds, p.lambda + 12 * i, p.vdot + 16 * i, out, &act, lds + CONTACT_LDS_TOTAL + ACT_LDS);
+  if (cx.lane < HB_NJ) p.tau_last[10 * i + cx.lane] = act.tau[cx.lane];   // (the lane's own entry)
+  if (cx.lane == 0) plant_publish(p, M, i, dt, res_rbd, res_x0, res_t);
+}
+__global__ __launch_bounds__(64) void k_plant_varied_joints_hybrid(PlantBatch p, ContactBatch cb, JointBatch jb, const double* __restrict__ ter,
+                                                                   ActuatorBatch a, ActuatorCmd c, hb_contact_config K, hb_joint_model J,
+                                                                   const DevModel* __restrict__ M, const DevModel* __restrict__ Mvar, const int* contact,
+                                                                   const int* mode, double dt, int substeps, double* res_rbd, double* res_x0, double* res_t) {
+  const int i = blockIdx.x;
+  __shared__ double lds[JOINT_LDS_TOTAL + ACT_LDS + TER_LDS];
+  __shared__ int all_on[HB_NC];
+  const VariedActuatorCtx cx;
+  if (cx.lane < HB_NC) {
+    int flag;
+    if (contact) flag = contact[4 * i + cx.lane];
+    else { bool cf[HB_NC]; mode_flags(mode[i], cf); flag = cf[cx.lane] ? 1 : 0; }
+    p.contact_last[4 * i + cx.lane] = flag;
+    all_on[cx.lane] = 1;
+  }
+  if (cx.lane < TER_LDS) lds[JOINT_LDS_TOTAL + ACT_LDS + cx.lane] = ter[TER_LDS * i + cx.lane];
+  __syncthreads();
+  const ContactOut out{cb.gap + 4 * i, cb.pvel + 12 * i, cb.res + i, cb.touching + 4 * i, cb.status + i};
+  const JointOut jout{jb.tau_applied + 10 * i, jb.friction_torque + 10 * i, jb.limit_torque + 10 * i, jb.res + i, jb.status + i};
+  const HybridActuator act = actuator_of(c, a, i, lds + JOINT_LDS_TOTAL);
+  joints_step<true, true>(cx, Mvar[i], p.q + 16 * i, p.v + 16 * i, cb.imp + 12 * i, jb.imp + 20 * i, nullptr, cb.use_wrench ? cb.wrench + 6 * i : nullptr, all_on,
+                          K, J, p.eps, dt, substeps, lds, p.lambda + 12 * i, p.vdot + 16 * i, p.tau_last + 10 * i, out, jout, &act,
+                          lds + JOINT_LDS_TOTAL + ACT_LDS);
+  if (cx.lane == 0) plant_publish(p, M, i, dt, res_rbd, res_x0, res_t);
+}
 __global__ void k_plant_reset(PlantBatch p, const DevModel* __restrict__ M) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= p.B) return;

@@ -12,6 +12,7 @@
 #include "hb_gait.hpp"
 #include "hb_contact.hpp"
 #include "hb_episode.hpp"
+#include "hb_modelvar.hpp"
 
 namespace {
 using namespace hb;
@@ -173,6 +174,17 @@ constexpr void fields(TerrainBatch& t, size_t, F&& f) {
   HB_FIELD(t.ter, Terrain::size);
 }
 
+// per-instance model variation of the ground-contact plant (hb_plant_set_model_variation, hb_modelvar.hpp), allocated by the first call
+// that gives one: the DevModel record each instance steps on, [B] records of sizeof(DevModel) (about 1.7 KB)
+struct ModelVarBatch {
+  int B;
+  DevModel* mdl;
+};
+template <class F>
+constexpr void fields(ModelVarBatch& m, size_t, F&& f) {
+  HB_FIELD(m.mdl, 1);
+}
+
 // per-instance episode record of the plant (hb_plant_set_episode, hb_episode.hpp), allocated by the first call that gives a
 // configuration: the integer and the double record of every instance.  The trace is [B][trace_cap][HB_EP_TRACE_W] with trace_cap the
 // largest trace_capacity set so far: a run-time extent, so the set call allocates it and the description does not name it.
@@ -297,6 +309,7 @@ static_assert(sizeof(PlantBatch) == kPtr /*B*/ + 2 * sizeof(double) + (n_fields<
 static_assert(sizeof(ContactBatch) == 2 * sizeof(int) + n_fields<ContactBatch>() * kPtr, "describe every array of ContactBatch in fields()");
 static_assert(sizeof(JointBatch) == kPtr /*B*/ + n_fields<JointBatch>() * kPtr, "describe every array of JointBatch in fields()");
 static_assert(sizeof(TerrainBatch) == kPtr /*B*/ + n_fields<TerrainBatch>() * kPtr, "describe every array of TerrainBatch in fields()");
+static_assert(sizeof(ModelVarBatch) == kPtr /*B*/ + n_fields<ModelVarBatch>() * kPtr, "describe every array of ModelVarBatch in fields()");
 static_assert(sizeof(EpisodeBatch) == 2 * sizeof(int) + (n_fields<EpisodeBatch>() + 1 /*trace*/) * kPtr, "describe every array of EpisodeBatch in fields()");
 static_assert(sizeof(ActuatorBatch) == kPtr /*B*/ + n_fields<ActuatorBatch>() * kPtr, "describe every array of ActuatorBatch in fields()");
 static_assert(sizeof(RefgenBatch) == kPtr /*B*/ + n_fields<RefgenBatch>() * kPtr + kPtr /*init_stance*/, "describe every array of RefgenBatch in fields()");

@@ -50,6 +50,19 @@ def plane_under_contact_points(solver, q, normals) -> np.ndarray:
     return np.einsum("bcx,bx->bc", feet, n).min(axis=1)
 
 
+def payload_on_base(mass, pos, inertia=None) -> np.ndarray:
+    """The [B][10] payload array of hb_plant_set_model_variation: mass[B] (or a scalar) [kg], pos[B][3] (or [3]) = the payload's centre of
+    mass in the base frame from the base origin [m], inertia[B][6] (or [6]) = xx xy xz yy yz zz about that centre in base axes (None: a
+    point mass)."""
+    mass = np.atleast_1d(np.asarray(mass, dtype=float))
+    out = np.zeros((mass.shape[0], abi.HB_PAYLOAD_SIZE))
+    out[:, 0] = mass
+    out[:, 1:4] = np.broadcast_to(np.asarray(pos, dtype=float), (mass.shape[0], 3))
+    if inertia is not None:
+        out[:, 4:10] = np.broadcast_to(np.asarray(inertia, dtype=float), (mass.shape[0], 6))
+    return out
+
+
 class DeviceLoop:
     """One HunterSolver driven in closed loop.  `gait` per instance (names of gait.info), `cmd_vel` [B][4]."""
 
@@ -154,7 +167,7 @@ class ResidentLoop:
     def __init__(self, solver, params: dict, gaits, cmd_vel, n_intervals: int = 100, mpc_every: int = 8, dt: float = 0.002,
                  t_gait_start: float = 0.3, joint_ik: bool = True, substeps: int = 4, static_schedule_until: float = 0.0,
                  device_gait: bool = False, use_estimator: bool = False, sensor_config=None, sensor_bias=None, contact_config=None,
-                 joint_model=None, actuator: str = "held", terrain=None, episode=None):
+                 joint_model=None, actuator: str = "held", terrain=None, episode=None, model_variation=None):
         """static_schedule_until > 0: the mode schedules are uploaded once for [-1, static_schedule_until] (at most
         HB_MAX_EVENTS events) instead of a sliding window per MPC call — no per-call host work for large batches.
         device_gait: the device gait manager produces the windows; step() builds no per-instance list and uploads no schedule, and
@@ -172,9 +185,14 @@ class ResidentLoop:
         normal and offset d, or [B][3] = normals alone, the plane then goes under the lowest contact point of each instance's start
         (plane_under_contact_points); mu=[B][4] per contact point), either may be missing (hb_plant_set_terrain).  Needs contact_config; set
         after the contact model.  The controller, estimator and swing planner assume level ground.
+        model_variation: per-instance inertial parameters of the ground-contact plant — None: the nominal robot; dict(mass_scale=[B][11],
+        payload=[B][10] (payload_on_base)), either may be missing (hb_plant_set_model_variation).  Needs contact_config; set after the
+        contact model, the joint model and the terrain and before the episode.  The controller keeps the nominal model.
         episode: the per-instance episode record of the plant (hb_plant_set_episode) — None: none; a dict of abi.make_episode_config
         fields ({} = the defaults); an abi.HbEpisodeConfig is taken as it is.  Set after the models and the terrain, so the record starts
         from the start state over the ground of the run; episode() reads it, run(n) advances n ticks without a read-back."""
+        if model_variation is not None and contact_config is None:
+            raise ValueError("model_variation belongs to the ground-contact plant: give contact_config as well")
         if terrain is not None and contact_config is None:
             raise ValueError("terrain belongs to the ground-contact plant: give contact_config as well")
         if actuator not in ("held", "substep"):
@@ -226,6 +244,8 @@ class ResidentLoop:
                         n = plane / np.linalg.norm(plane, axis=1, keepdims=True)
                         plane = np.concatenate([n, plane_under_contact_points(solver, q0, n)[:, None]], axis=1)
                 solver.plant_set_terrain(plane, terrain.get("mu"))
+        if model_variation is not None:
+            solver.plant_set_model_variation(model_variation.get("mass_scale"), model_variation.get("payload"))
         if episode is not None:
             solver.plant_set_episode(abi.make_episode_config(**episode) if isinstance(episode, dict) else episode)
         self.has_episode = episode is not None

@@ -35,6 +35,7 @@ ABI_SYMBOLS = [
     "hb_plant_set_contact_model", "hb_plant_set_external_wrench", "hb_plant_get_contact",
     "hb_plant_set_joint_model", "hb_plant_get_joints", "hb_plant_step_hybrid", "hb_plant_get_actuator",
     "hb_plant_set_terrain", "hb_plant_get_terrain",
+    "hb_plant_set_model_variation", "hb_plant_get_model_variation",
     "hb_plant_set_episode", "hb_plant_get_episode",
 ]
 # include/hunter_lcm.h
@@ -338,6 +339,23 @@ class HunterSolver:
         what the contact model amounts to."""
         out = dict(plane=np.zeros((self.B, 4)), mu=np.zeros((self.B, 4)), frame=np.zeros((self.B, 3, 3)))
         self._check(self.lib.hb_plant_get_terrain(self.ctx, *[_p(a) for a in out.values()]), "hb_plant_get_terrain")
+        return out
+
+    # ---- per-instance model variation of the ground-contact plant (hb_plant_set_model_variation) -------------------------------------
+    def plant_set_model_variation(self, mass_scale=None, payload=None):
+        """mass_scale [B][11] = a scale of mass and inertia per body (None: 1); payload [B][10] = mass, position[3] in the base frame,
+        inertia[6] = xx xy xz yy yz zz about its own centre of mass, of a payload on the base (None: none; rollout.payload_on_base packs
+        it).  Both None: no variation.  The plant steps on the varied model, the controller keeps the nominal one."""
+        sc = None if mass_scale is None else _f64(mass_scale, (self.B, abi.NBODY))
+        pl = None if payload is None else _f64(payload, (self.B, abi.HB_PAYLOAD_SIZE))
+        self._check(self.lib.hb_plant_set_model_variation(self.ctx, _p(sc), _p(pl)), "hb_plant_set_model_variation")
+
+    def plant_model_variation(self):
+        """-> dict(mass[B][11], com[B][11][3], inertia[B][11][6], total_mass[B]) of the model every instance steps on; without a
+        variation the nominal model repeated."""
+        out = dict(mass=np.zeros((self.B, abi.NBODY)), com=np.zeros((self.B, abi.NBODY, 3)), inertia=np.zeros((self.B, abi.NBODY, 6)),
+                   total_mass=np.zeros(self.B))
+        self._check(self.lib.hb_plant_get_model_variation(self.ctx, *[_p(a) for a in out.values()]), "hb_plant_get_model_variation")
         return out
 
     # ---- per-instance episode record and stop-on-fall (hb_plant_set_episode) -----------------------------------------------------

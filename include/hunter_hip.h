@@ -379,6 +379,49 @@ int32_t hb_plant_set_terrain(hb_ctx* ctx, const double* plane /*[batch][4] or NU
  * hb_plant_reset or outside contact model 1. */
 int32_t hb_plant_get_terrain(hb_ctx* ctx, double* plane, double* mu, double* frame);
 
+/* ---- per-instance model variation of contact model 1: a mass scale per body and a payload on the base ---------------------------------
+ * Instance i steps on inertial parameters of its own; everything on the controller's side keeps the nominal model of hb_create.  The
+ * nominal body b has mass m_b, centre of mass c_b in its link frame and inertia I_b about c_b (xx xy xz yy yz zz, link axes).  A
+ * variation gives instance i a scale s_b > 0 per body (mass_scale, 1 if NULL) and a payload on the base, body 0 (payload, nothing if
+ * NULL): mass m_p >= 0, position r of its centre of mass in the base frame, measured from the base origin, and inertia I_p about the
+ * payload's own centre of mass in base axes (xx xy xz yy yz zz, positive semidefinite).
+ *
+ * Composition (csrc/hb_modelvar.hpp; every operation is an IEEE double operation in the order written, brackets first):
+ *   links b >= 1:  m_b' = s_b m_b;   I_b'[k] = s_b I_b[k], k = 0..5;   c_b' = c_b   (a density scale)
+ *   base:          ms = s_0 m_0;     m_0' = ms + m_p;     c_0'[a] = (ms c_0[a] + m_p r[a]) / m_0',  a = x, y, z
+ *                  d1 = c_0 - c_0',  d2 = r - c_0'
+ *                  I_0'[k] = ((s_0 I_0[k] + P(ms, d1)[k]) + I_p[k]) + P(m_p, d2)[k]
+ *                  P(m, d) = m (|d|^2 1 - d d'):  |d|^2 = (d_x d_x + d_y d_y) + d_z d_z;  diagonal entry aa = m (|d|^2 - d_a d_a);
+ *                  off-diagonal entry ab = m (0 - d_a d_b)
+ *   total_mass' = ((0 + m_0') + m_1') + ... + m_10', in body order
+ *   gravity, joint origins and axes, joint limits and contact offsets: the nominal values.
+ * The unvaried instance — m_p == 0 and every s_b == 1.0 — gets a byte copy of the nominal device record instead; its total_mass is not
+ * summed again.  So "no variation" is an == statement: such a context computes what the context without a variation computes.
+ *
+ * What uses which model.  The varied model enters the step routines of contact model 1 only (contact_step / joints_step, held and hybrid
+ * form): the mass matrix, nle, X = Mh^-1 [...], W and through them every output of the step.  The repacking of the new state and the
+ * resident MPC observation a step writes (centroidal_state_from_rbd), hb_plant_sense (it reads gravity), hb_plant_reset (kinematics), the
+ * episode record and everything of the controller (estimator, reference generation, MPC, WBC, hb_joint_command) keep the nominal model.
+ * The steps run the terrain form of the kernels (above): without a terrain on the record (0, 0, 1, ground_z), cfg.mu, T = I of the
+ * configuration in force, which is the step without a terrain value for value.
+ *
+ * mass_scale: [batch][HB_NBODY] or NULL; payload: [batch][HB_PAYLOAD_SIZE] = m_p, r[3], I_p[6], or NULL.  Both NULL switches the variation
+ * off: the step then launches the kernels it launches without one.  HB_ERR_ARG (the message names the first offending instance; the
+ * variation in force is kept) for a non-finite value, s_b <= 0, m_p < 0, m_p == 0 with a nonzero I_p, or an I_p that is not positive
+ * semidefinite: with a = the largest |entry| of I_p, a diagonal entry < 0, a 2 x 2 principal minor (I_aa I_bb - I_ab I_ab) < -4 eps a^2
+ * or the determinant ((xx yy zz + xy yz xz) + xz xy yz) - ((xz yy xz + xy xy zz) + xx yz yz) < -64 eps a^3, eps = 2^-52 (the slack covers
+ * the roundings of these expressions on entries up to a).  HB_ERR_STATE before hb_plant_reset or outside contact model 1 (the pinned stub
+ * has no varied form).  The call changes the model and nothing else: the stored impulses stay a warm start, outputs and status stay, an
+ * episode record is not restarted.  The variation survives hb_plant_reset and a second hb_plant_set_contact_model with mode 1; leaving
+ * model 1 switches it off.  The first call allocates [batch] device records of about 1.7 KB. */
+#define HB_PAYLOAD_SIZE 10 /* m_p, r[3] (base frame, from the base origin), I_p[6] = xx xy xz yy yz zz about the payload's own COM, base axes */
+int32_t hb_plant_set_model_variation(hb_ctx* ctx, const double* mass_scale /*[batch][HB_NBODY] or NULL*/,
+                                     const double* payload /*[batch][HB_PAYLOAD_SIZE] or NULL*/);
+/* The model every instance steps on (any pointer may be NULL): mass[batch][HB_NBODY], com[batch][HB_NBODY][3],
+ * inertia[batch][HB_NBODY][6], total_mass[batch], from the host's copy of the uploaded image.  Without a variation: the nominal model
+ * repeated per instance.  HB_ERR_STATE before hb_plant_reset or outside contact model 1. */
+int32_t hb_plant_get_model_variation(hb_ctx* ctx, double* mass, double* com, double* inertia, double* total_mass);
+
 /* ---- hybrid step: the actuator loop per substep --------------------------------------------------------------------------------
  * The reference's controller does not send a torque but the hybrid command (joint_pos, joint_vel, kp, kd, ff_tau), and its simulator turns
  * it into a torque inside every simulator step from the simulator's own joint state (mujoco/src/main.cc:243-249).  An instance has a

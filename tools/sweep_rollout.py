@@ -4,6 +4,8 @@
 
     python tools/sweep_rollout.py                       the friction sweep (B = 8) and the slope sweep (B = 4) of DESIGN.md 5 item 20, 600 ticks
     python tools/sweep_rollout.py --grid 64 64 --ticks 5000   friction x slope on a grid, one scenario per instance (4096), static schedules
+    python tools/sweep_rollout.py --payload 8 5 --ticks 5000  payload mass 0 .. 15 kg x fore-aft offset -0.1 .. 0.1 m, 0.15 m above the base origin, on
+                                                        level ground with mu 0.7, one pair per instance (hb_plant_set_model_variation)
     python tools/sweep_rollout.py --readback            the two sweeps once more with the per-tick read-back loop the findings of items 17 - 20
                                                         were made with, for the wall time per tick of both
 
@@ -18,7 +20,7 @@ import numpy as np
 
 sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
 from hunter_bipedal_control_amd import abi, ingest  # noqa: E402
-from hunter_bipedal_control_amd.rollout import ResidentLoop, episode_summary  # noqa: E402
+from hunter_bipedal_control_amd.rollout import ResidentLoop, episode_summary, payload_on_base  # noqa: E402
 from hunter_bipedal_control_amd.solver import HunterSolver  # noqa: E402
 
 FRICTION = [0.7, 0.5, 0.4, 0.3, 0.2, 0.15, 0.1, 0.05]
@@ -32,21 +34,22 @@ def normals_of(pitch):
     return np.stack([np.sin(pitch), np.zeros_like(pitch), np.cos(pitch)], axis=1)
 
 
-def make_loop(params, mu, pitch, ticks, static, joint_model):
-    """One batch: instance i trots on a plane of pitch[i] with friction mu[i] under all four points."""
+def make_loop(params, mu, pitch, ticks, static, joint_model, payload=None):
+    """One batch: instance i trots on a plane of pitch[i] with friction mu[i] under all four points, carrying payload[i] ([B][10]) if given."""
     B = len(mu)
     s = HunterSolver(params, batch=B, max_nodes=108)
     cmd = np.tile([0.2, 0.0, 0.0, 0.0], (B, 1))
     horizon = 100 * params["config"]["dt"]
     loop = ResidentLoop(s, params, ["trot"] * B, cmd, contact_config=dict(fall_height=0.3), joint_model=joint_model,
                         terrain=dict(plane=normals_of(pitch), mu=np.repeat(np.asarray(mu, dtype=float)[:, None], 4, axis=1)),
-                        static_schedule_until=(ticks * 0.002 + horizon + 1.5) if static else 0.0, episode=dict(slip_speed=0.05))
+                        static_schedule_until=(ticks * 0.002 + horizon + 1.5) if static else 0.0, episode=dict(slip_speed=0.05),
+                        model_variation=None if payload is None else dict(payload=payload))
     return s, loop
 
 
-def run_record(params, mu, pitch, ticks, static=False, joint_model=None):
+def run_record(params, mu, pitch, ticks, static=False, joint_model=None, payload=None):
     """-> (episode record, wall seconds of the ticks)."""
-    s, loop = make_loop(params, mu, pitch, ticks, static, joint_model)
+    s, loop = make_loop(params, mu, pitch, ticks, static, joint_model, payload)
     try:
         s.sync()
         t0 = time.perf_counter()
@@ -101,11 +104,37 @@ def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--ticks", type=int, default=600)
     ap.add_argument("--grid", type=int, nargs=2, metavar=("N_MU", "N_SLOPE"), help="friction 0.05 .. 0.7 x pitch 0 .. 0.1 rad, one instance per pair")
+    ap.add_argument("--payload", type=int, nargs=2, metavar=("N_MASS", "N_OFFSET"),
+                    help="payload mass 0 .. 15 kg x fore-aft offset -0.1 .. 0.1 m at 0.15 m above the base origin, one instance per pair")
     ap.add_argument("--joint-model", action="store_true", help="the joints of the reference's MuJoCo model instead of ideal joints")
     ap.add_argument("--readback", action="store_true", help="also time the per-tick read-back loop on the two sweeps")
     args = ap.parse_args()
     params = ingest.load_packaged()
     jm = {} if args.joint_model else None
+    if args.payload:
+        n_m, n_x = args.payload
+        masses, offsets = np.linspace(0.0, 15.0, n_m), np.linspace(-0.1, 0.1, n_x)
+        mass, off = np.repeat(masses, n_x), np.tile(offsets, n_m)
+        B = len(mass)
+        pos = np.stack([off, np.zeros(B), np.full(B, 0.15)], axis=1)
+        rec, wall = run_record(params, [0.7] * B, [0.0] * B, args.ticks, static=True, joint_model=jm, payload=payload_on_base(mass, pos))
+        up = (rec["END_TICK"] < 0).reshape(n_m, n_x)
+        print(f"payload {n_m} x {n_x} = {B} instances, {args.ticks} ticks: {wall:.2f} s wall, {1e3 * wall / args.ticks:.3f} ms per tick; "
+              f"{int(up.sum())} instances up at the end, {int((rec['FIRST_NONFINITE'] >= 0).sum())} went non-finite")
+        print("survivors per offset column", np.round(offsets, 3).tolist(), "(of", n_m, "masses):", up.sum(axis=0).tolist())
+        print("survivors per mass row", np.round(masses, 2).tolist(), "(of", n_x, "offsets):", up.sum(axis=1).tolist())
+        if B <= 64:
+            table("mass/off", [f"{m:.3g}/{x:+.2g}" for m, x in zip(mass, off)], rec)
+        else:   # per mass row: the figures of the instances still up, else of all
+            heads = ("mass", "up", "height", "tiltmax", "taumax", "wbcF")
+            print(" ".join(f"{h:>10}" for h in heads))
+            for k, m in enumerate(masses):
+                sel = np.arange(k * n_x, (k + 1) * n_x)
+                sel = sel[up[k]] if up[k].any() else sel
+                row = (m, int(up[k].sum()), np.median(rec["HEIGHT_LAST"][sel]), rec["TILT_MAX"][sel].max(), rec["TAU_MAX"][sel].max(),
+                       int(rec["WBC_FAIL_TICKS"][sel].max()))
+                print(" ".join(f"{x:>10}" if isinstance(x, int) else f"{x:10.4g}" for x in row))
+        return
     if args.grid:
         n_mu, n_sl = args.grid
         mus, slopes = np.linspace(0.05, 0.7, n_mu), np.linspace(0.0, 0.1, n_sl)
