@@ -340,4 +340,24 @@ int32_t hb_mpc_get_recovery(hb_ctx* ctx, int32_t inst, double* Kx, double* ke, d
   return HB_OK;
 }
 
+// The line-search state of the last SQP iteration of the last MPC call, as the kernels left it (Batch fields of the same names): copies only.
+int32_t hb_mpc_get_linesearch(hb_ctx* ctx, int32_t inst_begin, int32_t inst_count, double* acc, double* partial, double* ls_tail, double* ls_norm,
+                              int32_t* accepted, int32_t* ric_fail) {
+  HB_ENTER_ARGS(false);
+  HB_FAIL_IF(!range_ok(ctx, inst_begin, inst_count, 1), HB_ERR_ARG, "hb_mpc_get_linesearch: instance range outside the batch");
+  HB_TRY(mpc_records_current(ctx, "hb_mpc_get_linesearch"));
+  HB_ENTER_DEVICE();
+  const Range r{inst_begin, inst_count};
+  Batch& b = ctx->b;
+  hipStream_t s = ctx->s_mpc;
+  HB_TRY(pull(ctx, acc, b, b.acc, r, &s));
+  HB_TRY(pull(ctx, partial, b, b.partial, r, &s));
+  HB_TRY(pull(ctx, ls_tail, b, b.ls_tail, r, &s));
+  HB_TRY(pull(ctx, ls_norm, b, b.ls_norm, r, &s));
+  HB_TRY(pull(ctx, accepted, b, b.accepted, r, &s));
+  HB_TRY(pull(ctx, ric_fail, b, b.ric_fail, r, &s));
+  HB_HIP(hipStreamSynchronize(s));
+  return HB_OK;
+}
+
 }  // extern "C"

@@ -31,7 +31,7 @@ constexpr Extent slot_major(size_t slots) { return Extent(slots, 1); }
 
 // ---------------------------------------------------------------------------------------------------------
 // device-resident problem data of a batch
-constexpr int LS_TAIL_MAX = 16;   // step sizes the backtracking tail evaluates side by side (decay 0.5, alpha_min 1e-4: 13 of them)
+constexpr int LS_TAIL_MAX = HB_LS_TAIL_MAX;   // 16: step sizes the backtracking tail evaluates side by side (decay 0.5, alpha_min 1e-4: 13 of them)
 struct Batch {
   int B, Nmax;
   int* n_nodes;

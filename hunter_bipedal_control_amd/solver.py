@@ -29,7 +29,7 @@ ABI_SYMBOLS = [
     "hb_plant_get_state", "hb_hoqp_solve", "hb_mpc_reset_masked", "hb_mpc_get_status", "hb_joint_set_flags",
     "hb_joint_get_emergency_stop", "hb_set_resident_time", "hb_get_wbc_iterations", "hb_ik_solve", "hb_debug_chunk_counters", "hb_debug_graph_state", "hb_refgen_get_status", "hb_tick_resident",
     "hb_wbc_set_certificate", "hb_wbc_get_certificate", "hb_hwbc_set_certificate", "hb_hwbc_get_certificate",
-    "hb_mpc_get_certificate", "hb_mpc_get_lq", "hb_mpc_get_recovery",
+    "hb_mpc_get_certificate", "hb_mpc_get_lq", "hb_mpc_get_recovery", "hb_mpc_get_linesearch",
     "hb_refgen_get_schedule", "hb_gait_reset", "hb_gait_disable", "hb_gait_insert_template", "hb_gait_get_state",
     "hb_plant_set_sensor_model", "hb_plant_sense", "hb_estimator_update_resident", "hb_estimator_contact_force_resident",
     "hb_plant_set_contact_model", "hb_plant_set_external_wrench", "hb_plant_get_contact",
@@ -537,6 +537,21 @@ class HunterSolver:
         self._check(self.lib.hb_mpc_get_recovery(self.ctx, C.c_int32(inst), *[_p(out[k]) for k in self.RECOVERY_KEYS]), "hb_mpc_get_recovery")
         n = int(np.count_nonzero(out["meta"][:, 0] + out["meta"][:, 1]))   # every stage has at least the six kernel coordinates
         return {k: v[:n].copy() for k, v in out.items()}
+
+    LINESEARCH_KEYS = ("acc", "partial", "ls_tail", "ls_norm", "accepted", "ric_fail")
+
+    def mpc_linesearch(self, inst_begin: int = 0, count: int | None = None) -> dict:
+        """The state of the filter line search of the last SQP iteration of the last MPC call (hb_mpc_get_linesearch), read only, as the
+        kernels left it: acc [count][4] (Armijo term, baseline merit, dyn_sse, eq_sse), partial [count][max_nodes][3] (per-node values at
+        step size 1), ls_tail [count][16][max_nodes][3] (the same for the last evaluated window of the backtracking tail; hunter_hip.h says
+        which rows are stale), ls_norm [count][2] (|dx|, |du|), accepted [count] (0 / 1 / 2 = stopped on deltaTol), ric_fail [count]."""
+        count = self.B - inst_begin if count is None else int(count)
+        n = max(count, 0)
+        out = dict(acc=np.zeros((n, 4)), partial=np.zeros((n, self.N, 3)), ls_tail=np.zeros((n, abi.HB_LS_TAIL_MAX, self.N, 3)),
+                   ls_norm=np.zeros((n, 2)), accepted=np.zeros(n, dtype=np.int32), ric_fail=np.zeros(n, dtype=np.int32))
+        self._check(self.lib.hb_mpc_get_linesearch(self.ctx, C.c_int32(inst_begin), C.c_int32(count), *[_p(out[k]) for k in self.LINESEARCH_KEYS]),
+                    "hb_mpc_get_linesearch")
+        return out
 
     def sync(self):
         self._check(self.lib.hb_sync(self.ctx), "hb_sync")

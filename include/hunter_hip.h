@@ -690,8 +690,24 @@ int32_t hb_hwbc_get_certificate(hb_ctx* ctx, int32_t inst_begin, int32_t inst_co
  *   Kx [max_nodes][10][22], ke [..][10], Z [..][10][6] (columns >= n_z zero), dF [..][12], qf [..][22] and rf [..][22] (the unprojected
  *   cost gradients q and r, scaled by dt), meta [..][6] (n_f, n_z, mode, cost dt, dyn_sse dt = dt |b|^2, eq_sse dt = dt |e|^2),
  *   dt [max_nodes] (interval length), dq [..][10] (the joint rows of b); any pointer may be NULL; rows k >= n are zero.
- * All three: HB_ERR_STATE when no MPC call has completed, or when the node tables or the iterate were replaced since the last one
+ * hb_mpc_get_linesearch: the state of the filter line search of the LAST SQP iteration of the last MPC call for the instances
+ * [inst_begin, inst_begin + inst_count), copied as the kernels left it (read only: nothing is launched and nothing changes):
+ *   acc [count][4]: the Armijo directional derivative sum_k qf_k'dx_k + rf_k'du_k, then the baseline merit, dyn_sse, eq_sse (each a sum
+ *       of the records' meta[3..5] in node order) -- what the filter compares every trial with;
+ *   partial [count][max_nodes][3]: per node (dt cost, dt |defect|^2, dt |eq|^2) at the trial point x + dx, u + du (step size 1);
+ *   ls_tail [count][HB_LS_TAIL_MAX][max_nodes][3]: the same at the step sizes of the LAST window of the backtracking tail that
+ *       evaluated the instance: row j of window w holds step size alpha_decay^(16 w + j + 1) (running product).  A window evaluates
+ *       at most HB_LS_TAIL_MAX step sizes >= alpha_min and none below the deltaTol stop; the rows behind them, the rows of nodes
+ *       k >= n and every row of an instance that accepted earlier keep what an earlier window, iteration or call wrote (stale);
+ *   ls_norm [count][2]: |dx|_2 over (n + 1) 22 entries and |du|_2 over n 22 entries, written when the full step is refused (stale
+ *       for an instance that accepted it);
+ *   accepted [count]: 0 = no step size accepted (alpha_min reached, or Riccati failure), 1 = step taken, 2 = stopped on deltaTol;
+ *   ric_fail [count]: 1 = the backward sweep met a non-positive pivot.
+ *   Any pointer may be NULL.  The sums the decisions were taken on are per lane l the sum over nodes l, l + 64, ... followed by the
+ *   wave reduction v[l] += v[l + off], off = 32 .. 1; hb_mpc_get_performance returns them for the accepted step size.
+ * All four: HB_ERR_STATE when no MPC call has completed, or when the node tables or the iterate were replaced since the last one
  * (hb_mpc_set_references, hb_refgen_update, hb_mpc_reset, hb_mpc_reset_masked, hb_mpc_set_trajectory); HB_ERR_ARG on a bad range. */
+#define HB_LS_TAIL_MAX 16         /* step sizes one window of the backtracking tail evaluates side by side */
 #define HB_MPC_CERT_R_DYN 0       /* max(|dx_0|_inf, max_k |dx_(k+1) - (A~_k dx_k + B~_k u~_k + b~_k)|_inf) */
 #define HB_MPC_CERT_R_STAT 1      /* max_k |r~_k + P~_k dx_k + R~_k u~_k + B~_k' lambda_(k+1)|_inf */
 #define HB_MPC_CERT_OBJ 2         /* sum_k q~'dx + r~'u~ + 1/2 dx'Q~dx + u~'P~dx + 1/2 u~'R~u~ */
@@ -709,6 +725,9 @@ int32_t hb_mpc_get_lq(hb_ctx* ctx, int32_t inst, double* A /*[max_nodes][22][22]
 int32_t hb_mpc_get_recovery(hb_ctx* ctx, int32_t inst, double* Kx /*[max_nodes][10][22]*/, double* ke /*[..][10]*/, double* Z /*[..][10][6]*/,
                             double* dF /*[..][12]*/, double* qf /*[..][22]*/, double* rf /*[..][22]*/, double* meta /*[..][6]*/,
                             double* dt /*[max_nodes]*/, double* dq /*[..][10]*/);
+int32_t hb_mpc_get_linesearch(hb_ctx* ctx, int32_t inst_begin, int32_t inst_count, double* acc /*[count][4]*/,
+                              double* partial /*[count][max_nodes][3]*/, double* ls_tail /*[count][16][max_nodes][3]*/,
+                              double* ls_norm /*[count][2]*/, int32_t* accepted /*[count]*/, int32_t* ric_fail /*[count]*/);
 /* Pipelining of hb_step_resident: the batch is cut into n_chunks (1..8) instance ranges, each a linear
  * MPC -> publish -> WBC sequence on its own HIP stream so that the per-instance sweeps of one range overlap the
  * per-node kernels of another.  Results are identical for every n_chunks; hb_get_stats phase times are only

@@ -106,6 +106,23 @@ double emu_sqp_iteration(const hb_model* m, const hb_config* c, int N, const dou
   }
   return 0.0;
 }
+// node_value (hb_riccati.hpp: what k_ls_eval / k_ls_tail_eval call per thread) of the n nodes of one instance at the trial point
+// (x + alpha dx, u + alpha du), formed as the kernels form it; x, dx [n + 1][22], u, du [n][22] -> out [n][3]
+void emu_node_value(const hb_model* m, const hb_config* c, int n, const double* t, const int* mode, const double* xref, const double* swing,
+                    const double* x, const double* u, const double* dx, const double* du, double alpha, double* out) {
+  DevModel d = make_dev_model(*m);
+  DevConfig dc = make_dev_config(*c, d);
+  for (int k = 0; k < n; ++k) {
+    double xt[HB_NX], ut[HB_NU];
+    for (int i = 0; i < HB_NX; ++i) {
+      xt[i] = x[k * HB_NX + i] + alpha * dx[k * HB_NX + i];
+      ut[i] = u[k * HB_NU + i] + alpha * du[k * HB_NU + i];
+    }
+    const double *xn0 = x + (k + 1) * HB_NX, *dxn = dx + (k + 1) * HB_NX;
+    node_value(d, dc, xt, ut, [xn0, dxn, alpha](int i) { return xn0[i] + alpha * dxn[i]; }, xref + k * HB_NX, swing + k * 24, t[k + 1] - t[k],
+               mode[k], out + 3 * k);
+  }
+}
 }
 
 #include "../../hunter_bipedal_control_amd/csrc/hb_wbc.hpp"

@@ -27,6 +27,20 @@ def test_header_and_library_symbols_agree():
         assert hasattr(lib, name), f"libhunter_hip.so does not export {name}"
 
 
+def test_linesearch_getter_is_declared_bound_and_sized_alike():
+    """hb_mpc_get_linesearch: declared once with its nine arguments, bound by the Python wrapper key for key, and the window length the
+    header, the layout description and abi.py name is one number."""
+    header = (ROOT / "include" / "hunter_hip.h").read_text()
+    decl = re.findall(r"int32_t hb_mpc_get_linesearch\(([^;]*)\);", header)
+    assert len(decl) == 1
+    args = [re.sub(r"/\*.*?\*/", "", a).split()[-1].lstrip("*") for a in decl[0].replace("\n", " ").split(",")]
+    assert args == ["ctx", "inst_begin", "inst_count"] + list(solver.HunterSolver.LINESEARCH_KEYS)
+    assert int(re.search(r"#define HB_LS_TAIL_MAX (\d+)", header).group(1)) == abi.HB_LS_TAIL_MAX == 16
+    layout = (ROOT / "hunter_bipedal_control_amd" / "csrc" / "hb_layout.hpp").read_text()
+    assert "constexpr int LS_TAIL_MAX = HB_LS_TAIL_MAX;" in layout
+    assert "hb_mpc_get_linesearch" in solver.ABI_SYMBOLS and hasattr(solver.load_library(), "hb_mpc_get_linesearch")
+
+
 def test_struct_sizes_match_the_header():
     # hb_model: 10 i32 + (30+30+40) f64 + 11 + 33 + 66 f64 + 4 i32 + 12 f64 + 1 f64
     assert C.sizeof(abi.HbModel) == 40 + 8 * (30 + 30 + 40 + 11 + 33 + 66) + 16 + 8 * 13

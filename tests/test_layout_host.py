@@ -95,6 +95,16 @@ def test_allocation_requests_every_array_in_order_with_its_size(layout, struct):
     assert layout["bytes"][struct] == TOTAL_BYTES[struct] == sum(n * size for _, n, size in want)
 
 
+def test_linesearch_arrays_have_the_extents_the_getter_documents(layout):
+    """hb_mpc_get_linesearch copies acc [4], partial [N][3], ls_tail [HB_LS_TAIL_MAX][N][3], ls_norm [2], accepted, ric_fail per instance:
+    the extents of the description (the copy is sized by them) are the shapes hunter_hip.h and HunterSolver.mpc_linesearch give."""
+    from hunter_bipedal_control_amd import abi
+    want = {"acc": (4, D), "partial": (N * 3, D), "ls_tail": (abi.HB_LS_TAIL_MAX * N * 3, D), "ls_norm": (2, D), "accepted": (1, I), "ric_fail": (1, I)}
+    alloc = {name: (n, size) for name, n, size in layout["alloc"]}
+    for member, (extent, size) in want.items():
+        assert alloc[f"Batch.{member}"] == (B * extent, size) and layout["view"][f"Batch.{member}"] == I0 * extent, member
+
+
 def test_view_sets_the_instance_count_and_keeps_the_other_scalars(layout):
     # (B of the view, the remaining scalar unchanged: Nmax, policy_valid, init_stance, and the pitch of the slot-major gait arrays)
     assert layout["scalars"] == {s: (CNT, 1) for s in ("Batch", "WbcBatch", "EstBatch", "RefgenBatch", "GaitBatch")}
