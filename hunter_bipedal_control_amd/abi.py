@@ -289,6 +289,44 @@ def split_episode_record(irec, drec) -> dict:
     return out
 
 
+class HbRespawnConfig(C.Structure):
+    """hb_respawn_config (include/hunter_hip.h): respawn of ended instances, hb_plant_set_respawn."""
+    _fields_ = [("clearance", C.c_double), ("yaw_range", C.c_double), ("joint_pos_sigma", C.c_double), ("base_vel_sigma", C.c_double),
+                ("seed", C.c_uint64), ("instance_offset", C.c_uint32), ("hold_ticks", C.c_int32), ("max_ticks", C.c_int32),
+                ("place", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
+HB_RS_TIMEOUT, HB_RS_STREAM = 3, 0x52535031
+# The totals, (name, index), in the order of the HB_RS_I_* / HB_RS_D_* indices of the header.
+RESPAWN_INT_FIELDS = ("EPISODES", "N_FALLEN", "N_NONFINITE", "N_TIMEOUT", "TICKS_SUM", "TICKS_MIN", "TICKS_MAX", "SLIP_TICKS_SUM",
+                      "WBC_FAIL_TICKS_SUM", "LAST_CAUSE", "LAST_TICKS", "EPISODE_INDEX", "STEPS_SUM")
+RESPAWN_DOUBLE_FIELDS = ("DIST_X_SUM", "DIST_Y_SUM", "WORK_ABS_SUM", "TILT_MAX", "TAU_MAX")
+HB_RS_NI, HB_RS_ND = len(RESPAWN_INT_FIELDS), len(RESPAWN_DOUBLE_FIELDS)
+
+
+def make_respawn_config(**fields) -> HbRespawnConfig:
+    """No hold, no time-out, no placement, no perturbation, seed 0; any field by name overrides."""
+    d = dict(clearance=0.0, yaw_range=0.0, joint_pos_sigma=0.0, base_vel_sigma=0.0, seed=0, instance_offset=0, hold_ticks=0, max_ticks=0,
+             place=0)
+    for k in fields:
+        if k not in d:
+            raise TypeError(f"make_respawn_config: unknown field {k!r} (one of {sorted(d)})")
+    d.update(fields)
+    out = HbRespawnConfig()
+    for k in ("clearance", "yaw_range", "joint_pos_sigma", "base_vel_sigma"):
+        setattr(out, k, float(d[k]))
+    for k in ("seed", "instance_offset", "hold_ticks", "max_ticks", "place"):
+        setattr(out, k, int(d[k]))
+    return out
+
+
+def split_respawn_totals(itot, dtot) -> dict:
+    """itot[B][HB_RS_NI], dtot[B][HB_RS_ND] -> dict of [B] arrays keyed by field name."""
+    out = {name: itot[:, k].copy() for k, name in enumerate(RESPAWN_INT_FIELDS)}
+    out.update({name: dtot[:, k].copy() for k, name in enumerate(RESPAWN_DOUBLE_FIELDS)})
+    return out
+
+
 class HbJointGains(C.Structure):
     _fields_ = [(k, C.c_double) for k in ("kp_big_stance", "kp_big_swing", "kd_big", "kp_small_stance", "kp_small_swing", "kd_small",
                                           "kd_feet", "kp_position", "kd_position")]

@@ -119,6 +119,12 @@ struct hb_ctx {
   EpisodeBatch episode{};
   hb_episode_config episode_cfg{};
   bool episode_on = false;
+  // respawn of ended instances (hb_plant_set_respawn): respawn_on while a configuration is in force; the arrays are allocated by the first
+  // call that gives one.  rs_rg_due / rs_mpc_due (under mtx): a respawn has been enqueued since the last hb_refgen_update / MPC solve, which
+  // then consume the device's pending flags.  The configuration survives hb_plant_reset.
+  RespawnBatch respawn{};
+  hb_respawn_config respawn_cfg{};
+  bool respawn_on = false, rs_rg_due = false, rs_mpc_due = false;
   // reference generation (allocated on the first hb_refgen_reset)
   RefgenBatch rg{};
   hb_refgen_config rg_cfg{};

@@ -37,6 +37,8 @@ static int32_t plant_write(hb_ctx* ctx, hipStream_t s, bool fence, double dt, F&
 
 extern "C" {
 
+static int32_t respawn_totals_start(hb_ctx* ctx, hipStream_t s);   // (below, with the respawn entry points)
+
 // joint command outputs and the per-instance controller flags (allocated on first use; loaded = 1, no emergency stop)
 static int32_t joint_state_alloc(hb_ctx* ctx) {
   if (ctx->jc_out) return HB_OK;
@@ -136,6 +138,7 @@ int32_t hb_plant_set_episode(hb_ctx* ctx, const hb_episode_config* cfg) {
   HB_HIP(hipStreamSynchronize(ctx->s_wbc));  // (a step in flight still updates the record it was launched with)
   if (!cfg) {
     ctx->episode_on = false;
+    ctx->respawn_on = false;   // the respawn reads its decision from the record
     return HB_OK;
   }
   EpisodeBatch& e = ctx->episode;
@@ -157,6 +160,7 @@ int32_t hb_plant_set_episode(hb_ctx* ctx, const hb_episode_config* cfg) {
   ctx->episode_cfg = *cfg;
   ctx->episode_on = true;
   HB_TRY(episode_start(ctx, ctx->s_wbc));
+  if (ctx->respawn_on) HB_TRY(respawn_totals_start(ctx, ctx->s_wbc));   // (the totals account for the steps of the records they folded)
   HB_HIP(hipStreamSynchronize(ctx->s_wbc));
   return HB_OK;
 }
@@ -174,6 +178,88 @@ int32_t hb_plant_get_episode(hb_ctx* ctx, int32_t* irec, double* drec, double* t
   const size_t row = size_t(ctx->episode_cfg.trace_capacity) * HB_EP_TRACE_W * 8;
   if (trace && row)
     HB_HIP(hipMemcpy2D(trace, row, e.trace, size_t(e.trace_cap) * HB_EP_TRACE_W * 8, row, size_t(ctx->B), hipMemcpyDeviceToHost));
+  return HB_OK;
+}
+
+// ---- respawn of ended instances (include/hunter_hip.h above hb_plant_set_respawn) ------------------------------------------------------
+// the totals back to their initial values (all zero), no flag pending, "last spawned state" = the given spawn state; on s
+static int32_t respawn_totals_start(hb_ctx* ctx, hipStream_t s) {
+  RespawnBatch& r = ctx->respawn;
+  HB_HIP(hipMemsetAsync(r.itot, 0, field_count(ctx, r, r.itot) * sizeof(int), s));
+  HB_HIP(hipMemsetAsync(r.dtot, 0, field_count(ctx, r, r.dtot) * 8, s));
+  HB_HIP(hipMemsetAsync(r.rg_pending, 0, field_count(ctx, r, r.rg_pending) * sizeof(int), s));
+  HB_HIP(hipMemsetAsync(r.mpc_pending, 0, field_count(ctx, r, r.mpc_pending), s));
+  HB_TRY(copy_field(ctx, hipMemcpyDeviceToDevice, r.q_spawn, r, r.q_last, whole(ctx), &s));
+  HB_TRY(copy_field(ctx, hipMemcpyDeviceToDevice, r.v_spawn, r, r.v_last, whole(ctx), &s));
+  std::lock_guard<std::mutex> lk(ctx->mtx);
+  ctx->rs_rg_due = ctx->rs_mpc_due = false;
+  return HB_OK;
+}
+
+int32_t hb_plant_set_respawn(hb_ctx* ctx, const hb_respawn_config* cfg, const double* q_spawn, const double* v_spawn) {
+  HB_ENTER_ARGS(false);
+  HB_FAIL_IF(!ctx->plant_ready, HB_ERR_STATE, "hb_plant_set_respawn: call hb_plant_reset first");
+  HB_FAIL_IF(!ctx->episode_on, HB_ERR_STATE, "hb_plant_set_respawn: no episode in force (hb_plant_set_episode): the decision is read from the episode record");
+  if (const char* why = cfg ? respawn_config_refusal(*cfg) : nullptr) {
+    ctx->err = std::string("hb_plant_set_respawn: ") + why + " (the configuration in force is kept)";
+    return HB_ERR_ARG;
+  }
+  HB_FAIL_IF(cfg && !q_spawn, HB_ERR_ARG, "hb_plant_set_respawn: q_spawn is required with a configuration (the configuration in force is kept)");
+  HB_ENTER_DEVICE();
+  HB_HIP(hipStreamSynchronize(ctx->s_wbc));  // (a respawn in flight still runs under the configuration it was launched with)
+  if (!cfg) {
+    std::lock_guard<std::mutex> lk(ctx->mtx);
+    ctx->respawn_on = false;
+    ctx->rs_rg_due = ctx->rs_mpc_due = false;   // (flags still pending are dropped: the next configuration starts with none)
+    return HB_OK;
+  }
+  RespawnBatch& r = ctx->respawn;
+  if (!r.mpc_pending) {  // (mpc_pending: the last array of the description, so an allocation that failed half way is repeated)
+    HB_HIP(alloc_fields(ctx, r));
+    r.B = ctx->B;
+  }
+  HB_TRY(push(ctx, q_spawn, r, r.q_spawn, whole(ctx)));
+  if (v_spawn) HB_TRY(push(ctx, v_spawn, r, r.v_spawn, whole(ctx)));
+  else HB_HIP(hipMemset(r.v_spawn, 0, field_count(ctx, r, r.v_spawn) * 8));
+  ctx->respawn_cfg = *cfg;
+  ctx->respawn_on = true;
+  HB_TRY(respawn_totals_start(ctx, ctx->s_wbc));
+  HB_HIP(hipStreamSynchronize(ctx->s_wbc));
+  return HB_OK;
+}
+
+int32_t hb_plant_respawn(hb_ctx* ctx) {
+  HB_ENTER_ARGS(false);
+  HB_FAIL_IF(!ctx->respawn_on, HB_ERR_STATE, "hb_plant_respawn: no respawn configuration in force (hb_plant_set_respawn)");
+  HB_ENTER_DEVICE();
+  double d0;
+  const double* ter = episode_plane(ctx, &d0);
+  hipStream_t s = ctx->s_wbc;  // behind the plant step and the update of the record
+  const ContactBatch cb = ctx->contact.wrench ? ctx->contact : ContactBatch{};
+  const JointBatch jb = ctx->joints.status ? ctx->joints : JointBatch{};
+  const ActuatorBatch ab = ctx->act.wire_full ? ctx->act : ActuatorBatch{};
+  const EstBatch est = ctx->est_ready ? ctx->est : EstBatch{};
+  // a writer of the resident observation, and of the pending flags and the gait state the MPC stream reads: always between the two
+  // ordering points
+  HB_TRY(resident_write(ctx, s, true, [&] {
+    hipLaunchKernelGGL(k_plant_respawn, dim3(ctx->B), dim3(64), 0, s, ctx->respawn, ctx->respawn_cfg, ctx->episode, ctx->plant, cb, jb, ab, est,
+                       ctx->gait, ctx->gait_cfg, ctx->gait_on ? 1 : 0, ter, d0, ctx->dmodel, ctx->jc_estop, ctx->w.rbd, ctx->b.x0);
+  }));
+  std::lock_guard<std::mutex> lk(ctx->mtx);
+  ctx->rs_rg_due = ctx->rs_mpc_due = true;
+  return HB_OK;
+}
+
+int32_t hb_plant_get_respawn(hb_ctx* ctx, int32_t* itot, double* dtot, double* q_last, double* v_last) {
+  HB_ENTER_ARGS(false);
+  HB_FAIL_IF(!ctx->respawn_on, HB_ERR_STATE, "hb_plant_get_respawn: no respawn configuration in force (hb_plant_set_respawn)");
+  HB_ENTER_DEVICE();
+  HB_HIP(hipStreamSynchronize(ctx->s_wbc));
+  RespawnBatch& r = ctx->respawn;
+  HB_TRY(pull(ctx, itot, r, r.itot, whole(ctx)));
+  HB_TRY(pull(ctx, dtot, r, r.dtot, whole(ctx)));
+  HB_TRY(pull(ctx, q_last, r, r.q_last, whole(ctx)));
+  HB_TRY(pull(ctx, v_last, r, r.v_last, whole(ctx)));
   return HB_OK;
 }
 
@@ -196,6 +282,7 @@ int32_t hb_plant_reset(hb_ctx* ctx, const double* q0, const double* v0, double b
   if (ctx->joints.status) HB_TRY(joints_clear(ctx, ctx->s_wbc));
   if (ctx->act.wire_full) HB_TRY(actuator_clear(ctx, ctx->s_wbc));
   if (ctx->episode_on) HB_TRY(episode_start(ctx, ctx->s_wbc));   // the record restarts from the reset state
+  if (ctx->respawn_on) HB_TRY(respawn_totals_start(ctx, ctx->s_wbc));   // ... and so do the totals of the respawn
   HB_HIP(hipStreamSynchronize(ctx->s_wbc));
   ctx->plant_ready = true;
   return HB_OK;

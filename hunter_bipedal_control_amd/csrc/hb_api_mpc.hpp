@@ -193,6 +193,18 @@ static int32_t enqueue_sqp(hb_ctx* ctx, const Batch& b, hipStream_t s, bool time
 // MPC solve of the whole batch on the MPC stream: warm start onto new tables, the timed SQP iterations, the solve counted.
 static int32_t mpc_solve_batch(hb_ctx* ctx) {
   HB_TRY(warm_start_onto_new_tables(ctx));
+  // a respawn enqueued since the last solve: its instances start cold from this call's observation, once (hb_mpc_reset_masked semantics)
+  bool respawned = false;
+  {
+    std::lock_guard<std::mutex> lk(ctx->mtx);
+    respawned = ctx->respawn_on && ctx->rs_mpc_due;
+    ctx->rs_mpc_due = false;
+  }
+  if (respawned) {
+    hipLaunchKernelGGL(k_cold_start, dim3(ctx->Nmax + 1, ctx->B), dim3(64), 0, ctx->s_mpc, ctx->b, ctx->dmodel, ctx->respawn.mpc_pending);
+    HB_HIP(hipGetLastError());
+    HB_HIP(hipMemsetAsync(ctx->respawn.mpc_pending, 0, size_t(ctx->B), ctx->s_mpc));
+  }
   HB_TRY(enqueue_sqp(ctx, ctx->b, ctx->s_mpc, true));
   std::lock_guard<std::mutex> lk(ctx->mtx);
   ctx->timed = true;

@@ -42,13 +42,14 @@ int32_t hb_refgen_set_schedule(hb_ctx* ctx, int32_t i0, int32_t cnt, const int32
 // Reference generation of the instances of b / r (instances [i0, i0 + b.B) of the context): planner, joint IK (when configured), node
 // tables.  With the gait manager on, k_gait first: it writes the schedule window the planner reads, and the three kernels take the
 // filtered command of the gait state instead of the uploaded one.
-static void launch_refgen(const hb_ctx* ctx, const Batch& b, RefgenBatch r, int i0, double horizon, hipStream_t s) {
+// init_flag: the respawn's pending flags of these instances, or null (hb_refgen_update alone consumes them).
+static void launch_refgen(const hb_ctx* ctx, const Batch& b, RefgenBatch r, int i0, double horizon, hipStream_t s, const int* init_flag = nullptr) {
   if (ctx->gait_on) {
     const GaitBatch g = view(ctx->gait, ctx->Nmax, i0, b.B);
     hipLaunchKernelGGL(k_gait, dim3((b.B + 63) / 64), dim3(64), 0, s, b, r, g, ctx->gait_cfg, horizon);
     r.cmd = g.cmd;
   }
-  hipLaunchKernelGGL(k_refgen, dim3((4 * b.B + 63) / 64), dim3(64), 0, s, b, r, ctx->dmodel, ctx->rg_cfg, horizon);
+  hipLaunchKernelGGL(k_refgen, dim3((4 * b.B + 63) / 64), dim3(64), 0, s, b, r, ctx->dmodel, ctx->rg_cfg, horizon, init_flag);
   if (ctx->rg_cfg.joint_ik)
     hipLaunchKernelGGL(k_refgen_ik, dim3((2 * b.B + 7) / 8), dim3(64), 0, s, b, r, ctx->dmodel, ctx->rg_cfg, horizon);
   hipLaunchKernelGGL(k_refgen_nodes, dim3((b.B * ctx->Nmax + 63) / 64), dim3(64), 0, s, b, r, ctx->rg_cfg);
@@ -72,8 +73,16 @@ int32_t hb_refgen_update(hb_ctx* ctx, const double* t0, double horizon, const do
     HB_TRY(stage_upload(ctx, ST_CMD, r, r.cmd, cmd_vel, s));
     if (x_now) HB_TRY(stage_upload(ctx, ST_X0, ctx->b, ctx->b.x0, x_now, s));
   }
-  launch_refgen(ctx, ctx->b, r, 0, horizon, s);
+  // a respawn enqueued since the last update: its instances take their latest stance positions from this call's observation, once
+  bool respawned = false;
+  {
+    std::lock_guard<std::mutex> lk(ctx->mtx);
+    respawned = ctx->respawn_on && ctx->rs_rg_due;
+    ctx->rs_rg_due = false;
+  }
+  launch_refgen(ctx, ctx->b, r, 0, horizon, s, respawned ? ctx->respawn.rg_pending : nullptr);
   HB_HIP(hipGetLastError());
+  if (respawned) HB_HIP(hipMemsetAsync(ctx->respawn.rg_pending, 0, size_t(ctx->B) * sizeof(int), s));
   r.init_stance = 0;
   ++ctx->mpc_tables_epoch;
   if (status) {

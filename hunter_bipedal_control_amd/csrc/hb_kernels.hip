@@ -23,6 +23,7 @@
 #include "hb_contact.hpp"
 #include "hb_joints.hpp"
 #include "hb_sensors.hpp"
+#include "hb_respawn.hpp"
 #include "hb_layout.hpp"
 #include "hb_iterate.hpp"
 #include "hb_wavectx.hpp"
@@ -859,15 +860,7 @@ __device__ __forceinline__ void plant_publish(const PlantBatch& p, const DevMode
   const double* q = p.q + 16 * i;
   const double* v = p.v + 16 * i;
   double* rbd = p.rbd + HB_NRBD * i;
-  double sz, cz, sy, cy;
-  sincos_t(q[3], sz, cz);
-  sincos_t(q[4], sy, cy);
-  for (int a = 0; a < 3; ++a) { rbd[a] = q[3 + a]; rbd[3 + a] = q[a]; rbd[HB_NV + 3 + a] = v[a]; }
-  for (int j = 0; j < HB_NJ; ++j) { rbd[6 + j] = q[6 + j]; rbd[6 + HB_NV + j] = v[6 + j]; }
-  // omega_world = E(zyx) rates
-  rbd[HB_NV + 0] = -sz * v[4] + cy * cz * v[5];
-  rbd[HB_NV + 1] = cz * v[4] + cy * sz * v[5];
-  rbd[HB_NV + 2] = v[3] - sy * v[5];
+  plant_rbd_from_state(q, v, rbd);
   if (res_rbd) {
     for (int c = 0; c < HB_NRBD; ++c) res_rbd[HB_NRBD * i + c] = rbd[c];
     centroidal_state_from_rbd(*M, rbd, res_x0 + HB_NX * i);
@@ -1264,6 +1257,76 @@ __global__ __launch_bounds__(64) void k_plant_episode(EpisodeBatch e, hb_episode
   episode_update(K, in, dt, e.irec + HB_EP_NI * i, e.drec + HB_EP_ND * i, e.trace + size_t(i) * e.trace_cap * HB_EP_TRACE_W, estop ? estop + i : nullptr);
 }
 
+// ---- respawn of ended instances (hb_plant_respawn, hb_respawn.hpp): one wavefront per instance -----------------------------------------
+// Every lane reads the decision from the instance's record (the same words: wave-uniform), and a wavefront whose instance stays leaves
+// after those loads.  A respawning wavefront draws its Philox blocks one per lane into LDS, lane 0 folds the record, composes and places
+// the spawn state (the one sequential piece: the leg kinematics, as in k_plant_reset) and resets the gait object; then all lanes write the
+// rows, consecutive lanes on consecutive words.  cb / jb / ab / est / estop / e.trace: null arrays where the subsystem has none.
+__global__ __launch_bounds__(64) void k_plant_respawn(RespawnBatch rs, hb_respawn_config K, EpisodeBatch e, PlantBatch p, ContactBatch cb, JointBatch jb,
+                                                      ActuatorBatch ab, EstBatch est, GaitBatch g, hb_gait_config GK, int gait_on,
+                                                      const double* __restrict__ ter, double d0, const DevModel* __restrict__ M, int* estop,
+                                                      double* res_rbd, double* res_x0) {
+  const int i = blockIdx.x;
+  const DeviceCtx cx;
+  int* irec = e.irec + HB_EP_NI * i;
+  const int cause = respawn_decide(K, irec);
+  if (cause == 0) return;
+  __shared__ double sh[RS_DRAW + 16 + 16 + 12 + HB_NRBD + HB_NX + 4];
+  double* draw = sh;
+  double* q = draw + RS_DRAW;
+  double* v = q + 16;
+  double* feet = v + 16;
+  double* rbd = feet + 12;
+  double* x0 = rbd + HB_NRBD;
+  double* plane = x0 + HB_NX;
+  int* itot = rs.itot + HB_RS_NI * i;
+  double* drec = e.drec + HB_EP_ND * i;
+  if (cx.lane < RS_BLOCKS && respawn_block_needed(K, cx.lane))
+    respawn_draw_block(K, K.instance_offset + uint32_t(i), uint32_t(itot[HB_RS_I_EPISODE_INDEX] + 1), cx.lane, draw, nullptr);
+  __syncthreads();
+  if (cx.lane == 0) {
+    respawn_fold(cause, irec, drec, itot, rs.dtot + HB_RS_ND * i);
+    itot[HB_RS_I_EPISODE_INDEX] += 1;
+    plane[0] = 0.0; plane[1] = 0.0; plane[2] = 1.0; plane[3] = d0;
+    if (ter) {
+      const double* r = ter + size_t(Terrain::size) * i;
+      for (int a = 0; a < 3; ++a) plane[a] = r[Terrain::T + 3 * a + 2];
+      plane[3] = r[Terrain::d];
+    }
+    respawn_perturb(K, rs.q_spawn + 16 * i, rs.v_spawn + 16 * i, draw, q, v);
+    plant_feet(*M, q, feet);
+    respawn_place(*M, K, plane, q, feet);
+    plant_rbd_from_state(q, v, rbd);
+    centroidal_state_from_rbd(*M, rbd, x0);
+    if (gait_on) gait_reset_instance(g, i, GK);
+  }
+  __syncthreads();
+  RespawnRows r{};
+  r.q = p.q + 16 * i; r.v = p.v + 16 * i; r.anchor = p.anchor + 12 * i; r.lambda = p.lambda + 12 * i; r.vdot = p.vdot + 16 * i;
+  r.tau_last = p.tau_last + 10 * i; r.rbd = p.rbd + HB_NRBD * i; r.pinned = p.pinned + 4 * i; r.contact_last = p.contact_last + 4 * i;
+  r.q_last = rs.q_last + 16 * i; r.v_last = rs.v_last + 16 * i;
+  if (cb.imp) {
+    r.c_imp = cb.imp + 12 * i; r.c_gap = cb.gap + 4 * i; r.c_pvel = cb.pvel + 12 * i; r.c_res = cb.res + i; r.c_touching = cb.touching + 4 * i;
+    r.c_status = cb.status + i;
+  }
+  if (jb.imp) {
+    r.j_imp = jb.imp + 20 * i; r.j_tau_applied = jb.tau_applied + 10 * i; r.j_friction = jb.friction_torque + 10 * i;
+    r.j_limit = jb.limit_torque + 10 * i; r.j_res = jb.res + i; r.j_status = jb.status + i;
+  }
+  if (ab.tau_first) {
+    r.a_tau_first = ab.tau_first + 10 * i; r.a_tau_mean = ab.tau_mean + 10 * i; r.a_last_ts = ab.last_ts + i;
+    for (int k = 0; k < 5; ++k) r.a_rcmd[k] = ab.rcmd[k] + 10 * i;
+  }
+  r.estop = estop ? estop + i : nullptr;
+  r.irec = irec; r.drec = drec;
+  r.trace = e.trace ? e.trace + size_t(i) * e.trace_cap * HB_EP_TRACE_W : nullptr;
+  r.trace_cap = e.trace_cap;
+  if (est.xhat) { r.xhat = est.xhat + 18 * i; r.P = est.P + 324 * size_t(i); r.yaw_last = est.yaw_last + i; r.cf_z = est.cf_z + HB_NV * i; }
+  r.res_rbd = res_rbd + HB_NRBD * i; r.res_x0 = res_x0 + HB_NX * i;
+  r.rg_pending = rs.rg_pending + i; r.mpc_pending = rs.mpc_pending + i;
+  respawn_write(cx, r, q, v, feet, rbd, x0, plane);
+}
+
 // ---- sensors from the plant: one thread per instance, 64 instances per workgroup ---------------------------------------------------
 // The per-instance routine (hb_sensors.hpp plant_sense) reads and writes LDS rows; the workgroup moves its 64 instances' inputs and
 // outputs between LDS and global memory array by array, consecutive lanes on consecutive words (the arrays are instance-major, so a
@@ -1381,13 +1444,15 @@ __global__ __launch_bounds__(64) void k_gait_insert(GaitBatch g, double pts, int
 
 // planner step: FOUR lanes per instance, one per foot (refgen_plan: the four planner loops and the leg evaluations side by side; the lane
 // of foot 0 finishes with the shooting grid and the knots) — thread-per-instance the kernel was a 0.26 ms chain on 64 wavefronts
-__global__ __launch_bounds__(64) void k_refgen(Batch b, RefgenBatch r, const DevModel* __restrict__ M, hb_refgen_config K, double horizon) {
+// init_flag (or null): per-instance "take the latest stance positions from the observation", the pending flag of a respawn
+__global__ __launch_bounds__(64) void k_refgen(Batch b, RefgenBatch r, const DevModel* __restrict__ M, hb_refgen_config K, double horizon,
+                                               const int* __restrict__ init_flag) {
   const int gid = blockIdx.x * blockDim.x + threadIdx.x;
   const int i = gid >> 2, foot = gid & 3;
   if (i >= b.B) return;   // (a whole group of four leaves together)
   const double* x_now = b.x0 + size_t(i) * HB_NX;
   double* stance = r.stance + size_t(i) * 12;
-  if (r.init_stance) {
+  if (r.init_stance || (init_flag && init_flag[i])) {
     const Mat3<double> R0 = rg_rot_zyx(x_now + 9);
     const Vec3<double> p0(x_now[6], x_now[7], x_now[8]);
     const double* qj = x_now + 12;

@@ -200,6 +200,23 @@ constexpr void fields(EpisodeBatch& e, size_t, F&& f) {
   HB_FIELD(e.irec, HB_EP_NI); HB_FIELD(e.drec, HB_EP_ND);
 }
 
+// respawn of ended instances (hb_plant_set_respawn, hb_respawn.hpp), allocated by the first call that gives a configuration: the totals of
+// the finished episodes (itot, dtot), the spawn state the caller gave (q_spawn, v_spawn) and the last one drawn from it (q_last, v_last),
+// and the two pending flags the MPC side consumes: rg_pending (k_refgen takes the latest stance positions from the observation) and
+// mpc_pending (the mask of k_cold_start in the next solve).
+struct RespawnBatch {
+  int B;
+  int* itot;
+  double *dtot, *q_spawn, *v_spawn, *q_last, *v_last;
+  int* rg_pending;
+  unsigned char* mpc_pending;
+};
+template <class F>
+constexpr void fields(RespawnBatch& r, size_t, F&& f) {
+  HB_FIELD(r.itot, HB_RS_NI); HB_FIELD(r.dtot, HB_RS_ND); HB_FIELD(r.q_spawn, 16); HB_FIELD(r.v_spawn, 16); HB_FIELD(r.q_last, 16);
+  HB_FIELD(r.v_last, 16); HB_FIELD(r.rg_pending, 1); HB_FIELD(r.mpc_pending, 1);
+}
+
 // actuator loop of the plant and the simulator end of the LCM link (hb_plant_step_hybrid, hb_plant_step_lcm, hb_plant_sense_lcm),
 // allocated on the first call that needs them — the held-torque path needs none: the record of the last hybrid step, the staging of a
 // host command and the received command (pos_des vel_des kp kd ff, one array each), the timestamp filter, the wire images
@@ -311,6 +328,7 @@ static_assert(sizeof(JointBatch) == kPtr /*B*/ + n_fields<JointBatch>() * kPtr, 
 static_assert(sizeof(TerrainBatch) == kPtr /*B*/ + n_fields<TerrainBatch>() * kPtr, "describe every array of TerrainBatch in fields()");
 static_assert(sizeof(ModelVarBatch) == kPtr /*B*/ + n_fields<ModelVarBatch>() * kPtr, "describe every array of ModelVarBatch in fields()");
 static_assert(sizeof(EpisodeBatch) == 2 * sizeof(int) + (n_fields<EpisodeBatch>() + 1 /*trace*/) * kPtr, "describe every array of EpisodeBatch in fields()");
+static_assert(sizeof(RespawnBatch) == kPtr /*B*/ + n_fields<RespawnBatch>() * kPtr, "describe every array of RespawnBatch in fields()");
 static_assert(sizeof(ActuatorBatch) == kPtr /*B*/ + n_fields<ActuatorBatch>() * kPtr, "describe every array of ActuatorBatch in fields()");
 static_assert(sizeof(RefgenBatch) == kPtr /*B*/ + n_fields<RefgenBatch>() * kPtr + kPtr /*init_stance*/, "describe every array of RefgenBatch in fields()");
 static_assert(sizeof(GaitBatch) == 2 * sizeof(int) + n_fields<GaitBatch>() * kPtr, "describe every array of GaitBatch in fields()");

@@ -265,6 +265,19 @@ HB_HD void plant_feet(const DevModel& Mdl, const double* q, double* feet12) {
   }
 }
 
+// The plant's state (q, v) repacked as the rbd state a plant step publishes: euler zyx | position | joints | omega_world = E(zyx) rates |
+// linear velocity | joint rates.
+HB_HD void plant_rbd_from_state(const double* q, const double* v, double* rbd) {
+  double sz, cz, sy, cy;
+  sincos_t(q[3], sz, cz);
+  sincos_t(q[4], sy, cy);
+  for (int a = 0; a < 3; ++a) { rbd[a] = q[3 + a]; rbd[3 + a] = q[a]; rbd[HB_NV + 3 + a] = v[a]; }
+  for (int j = 0; j < HB_NJ; ++j) { rbd[6 + j] = q[6 + j]; rbd[6 + HB_NV + j] = v[6 + j]; }
+  rbd[HB_NV + 0] = -sz * v[4] + cy * cz * v[5];
+  rbd[HB_NV + 1] = cz * v[4] + cy * sz * v[5];
+  rbd[HB_NV + 2] = v[3] - sy * v[5];
+}
+
 // One plant tick of one instance: re-anchor the feet whose contact phase starts, `substeps` substeps of dt / substeps.
 // State (q, v, anchor, pinned) lives in global memory; q / v are staged in LDS behind `lds`.
 // HYBRID: `tau` is not read; the law's torque of every substep is (see above).

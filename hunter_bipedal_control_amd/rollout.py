@@ -167,7 +167,7 @@ class ResidentLoop:
     def __init__(self, solver, params: dict, gaits, cmd_vel, n_intervals: int = 100, mpc_every: int = 8, dt: float = 0.002,
                  t_gait_start: float = 0.3, joint_ik: bool = True, substeps: int = 4, static_schedule_until: float = 0.0,
                  device_gait: bool = False, use_estimator: bool = False, sensor_config=None, sensor_bias=None, contact_config=None,
-                 joint_model=None, actuator: str = "held", terrain=None, episode=None, model_variation=None):
+                 joint_model=None, actuator: str = "held", terrain=None, episode=None, model_variation=None, respawn=None):
         """static_schedule_until > 0: the mode schedules are uploaded once for [-1, static_schedule_until] (at most
         HB_MAX_EVENTS events) instead of a sliding window per MPC call — no per-call host work for large batches.
         device_gait: the device gait manager produces the windows; step() builds no per-instance list and uploads no schedule, and
@@ -190,7 +190,13 @@ class ResidentLoop:
         contact model, the joint model and the terrain and before the episode.  The controller keeps the nominal model.
         episode: the per-instance episode record of the plant (hb_plant_set_episode) — None: none; a dict of abi.make_episode_config
         fields ({} = the defaults); an abi.HbEpisodeConfig is taken as it is.  Set after the models and the terrain, so the record starts
-        from the start state over the ground of the run; episode() reads it, run(n) advances n ticks without a read-back."""
+        from the start state over the ground of the run; episode() reads it, run(n) advances n ticks without a read-back.
+        respawn: repeated episodes per instance (hb_plant_set_respawn) — None: a fallen robot stays fallen; a dict of
+        abi.make_respawn_config fields plus, optionally, q_spawn / v_spawn [B][16] (default: the start configuration, at rest).  Needs
+        episode= and is set after it.  step() / run() then call plant_respawn() after the plant step of every tick whose successor is an
+        MPC tick, so that the policy a respawned instance is driven by is always one of its own episode; respawn_totals() reads the totals."""
+        if respawn is not None and episode is None:
+            raise ValueError("respawn reads its decision from the episode record: give episode= as well")
         if model_variation is not None and contact_config is None:
             raise ValueError("model_variation belongs to the ground-contact plant: give contact_config as well")
         if terrain is not None and contact_config is None:
@@ -249,6 +255,11 @@ class ResidentLoop:
         if episode is not None:
             solver.plant_set_episode(abi.make_episode_config(**episode) if isinstance(episode, dict) else episode)
         self.has_episode = episode is not None
+        self.has_respawn = respawn is not None
+        if respawn is not None:
+            fields = dict(respawn)
+            q_spawn, v_spawn = fields.pop("q_spawn", q0), fields.pop("v_spawn", None)
+            solver.plant_set_respawn(abi.make_respawn_config(**fields), q_spawn, v_spawn)
         # resident observation of the initial state
         rbd = np.zeros((self.B, 32))
         rbd[:, 0:3], rbd[:, 3:6], rbd[:, 6:16] = q0[:, 3:6], q0[:, 0:3], q0[:, 6:]
@@ -310,6 +321,8 @@ class ResidentLoop:
             s.plant_step(None, None, self.dt, self.substeps, to_resident=not self.use_estimator)
         self.t += self.dt
         self.tick += 1
+        if self.has_respawn and self.tick % self.mpc_every == 0:   # the next tick is an MPC tick
+            s.plant_respawn()
 
     def run(self, n: int):
         """n ticks of step() with no read-back: every call of a tick is enqueue-only (the status of the reference generation is looked at
@@ -325,6 +338,24 @@ class ResidentLoop:
         if not self.has_episode:
             raise ValueError("ResidentLoop was built without episode=")
         return self.s.plant_episode(want_trace)
+
+    def respawn_totals(self, want_state: bool = False) -> dict:
+        """The totals of the finished episodes (HunterSolver.plant_respawn_totals)."""
+        if not self.has_respawn:
+            raise ValueError("ResidentLoop was built without respawn=")
+        return self.s.plant_respawn_totals(want_state)
+
+
+def respawn_summary(totals: dict, dt: float = 0.002) -> dict:
+    """Per instance, from the totals alone (HunterSolver.plant_respawn_totals): episodes finished, survival_rate = share of them that ended
+    by time-out (neither fallen nor non-finite), fall_rate, mean_ticks and mean_time = mean_ticks dt of an episode, mean_distance_x /
+    mean_distance_y per episode (ratios are 0 for an instance with no finished episode)."""
+    n = np.asarray(totals["EPISODES"], dtype=float)
+    per = np.where(n > 0, 1.0 / np.maximum(n, 1.0), 0.0)
+    mean_ticks = totals["TICKS_SUM"] * per
+    return dict(episodes=np.asarray(totals["EPISODES"]).copy(), survival_rate=totals["N_TIMEOUT"] * per, fall_rate=totals["N_FALLEN"] * per,
+                mean_ticks=mean_ticks, mean_time=mean_ticks * dt, mean_distance_x=totals["DIST_X_SUM"] * per,
+                mean_distance_y=totals["DIST_Y_SUM"] * per)
 
 
 def episode_summary(record: dict, start=None, dt: float = 0.002) -> dict:

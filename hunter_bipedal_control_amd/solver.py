@@ -37,6 +37,7 @@ ABI_SYMBOLS = [
     "hb_plant_set_terrain", "hb_plant_get_terrain",
     "hb_plant_set_model_variation", "hb_plant_get_model_variation",
     "hb_plant_set_episode", "hb_plant_get_episode",
+    "hb_plant_set_respawn", "hb_plant_respawn", "hb_plant_get_respawn",
 ]
 # include/hunter_lcm.h
 LCM_SYMBOLS = ["hb_lcm_fingerprint", "hb_lcm_encoded_size", "hb_lcm_field_count", "hb_lcm_encode", "hb_lcm_decode", "hb_lcm_frame", "hb_lcm_unframe",
@@ -375,6 +376,29 @@ class HunterSolver:
         out = abi.split_episode_record(irec, drec)
         if want_trace:
             out["trace"] = trace
+        return out
+
+    # ---- respawn of ended instances (hb_plant_set_respawn) ---------------------------------------------------------------------------
+    def plant_set_respawn(self, cfg: "abi.HbRespawnConfig" = None, q_spawn=None, v_spawn=None):
+        """cfg None: off; abi.make_respawn_config(...) with q_spawn[B][16] (v_spawn[B][16] or None = zero): plant_respawn() puts every
+        instance whose episode is over back to a state drawn from it.  Needs plant_set_episode; starts the totals."""
+        q = None if q_spawn is None else _f64(q_spawn, (self.B, 16))
+        v = None if v_spawn is None else _f64(v_spawn, (self.B, 16))
+        self._check(self.lib.hb_plant_set_respawn(self.ctx, None if cfg is None else C.byref(cfg), _p(q), _p(v)), "hb_plant_set_respawn")
+
+    def plant_respawn(self):
+        """Enqueue-only: the device respawns the instances whose episode record says so (hb_plant_respawn)."""
+        self._check(self.lib.hb_plant_respawn(self.ctx), "hb_plant_respawn")
+
+    def plant_respawn_totals(self, want_state=False):
+        """The totals of the finished episodes -> dict of [B] arrays keyed by field name (abi.RESPAWN_INT_FIELDS / RESPAWN_DOUBLE_FIELDS);
+        want_state adds q_last / v_last [B][16], the last spawned state."""
+        itot, dtot = np.zeros((self.B, abi.HB_RS_NI), dtype=np.int32), np.zeros((self.B, abi.HB_RS_ND))
+        q, v = (np.zeros((self.B, 16)), np.zeros((self.B, 16))) if want_state else (None, None)
+        self._check(self.lib.hb_plant_get_respawn(self.ctx, _p(itot), _p(dtot), _p(q), _p(v)), "hb_plant_get_respawn")
+        out = abi.split_respawn_totals(itot, dtot)
+        if want_state:
+            out["q_last"], out["v_last"] = q, v
         return out
 
     # ---- sensors from the plant (hb_plant_sense) and the estimator on them ------------------------------------------------

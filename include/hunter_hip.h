@@ -521,6 +521,95 @@ int32_t hb_plant_set_episode(hb_ctx* ctx, const hb_episode_config* cfg);
  * first N_TRACE samples of an instance are valid, the rest zero).  HB_ERR_STATE before hb_plant_reset or with no episode in force. */
 int32_t hb_plant_get_episode(hb_ctx* ctx, int32_t* irec, double* drec, double* trace);
 
+/* ---- respawn of ended instances: episode after episode on the device ------------------------------------------------------------------
+ * With an episode in force, hb_plant_respawn puts every instance whose episode is over back to a spawn state, in one enqueue-only launch
+ * (k_plant_respawn) on the plant's stream, ordered against the MPC stream like a plant step that writes the resident observation.  The
+ * device decides WHO is put back, from the instance's episode record; the host decides WHEN, by calling.  Off by default.
+ *
+ * Decision for one instance (irec = its episode record):
+ *   if END_TICK >= 0:  cause = END_CAUSE;  respawn iff  STEPS - (END_TICK + 1) >= hold_ticks  (the steps the record has seen after the
+ *                      end step);
+ *   else if max_ticks > 0 and TICKS >= max_ticks:  cause = HB_RS_TIMEOUT;  respawn (no hold);
+ *   else the instance stays and NOT ONE BYTE of any of its arrays is written.
+ * An instance that has ended is never a time-out, however many ticks it has.
+ *
+ * For a respawned instance, in this order:
+ *  1. Fold of the finished record into the totals itot[HB_RS_NI] / dtot[HB_RS_ND] (HB_RS_I_* / HB_RS_D_* below):
+ *       N_FALLEN / N_NONFINITE / N_TIMEOUT += 1 by cause;  TICKS_SUM += TICKS;  TICKS_MIN = TICKS if EPISODES == 0, else min;  TICKS_MAX =
+ *       max;  SLIP_TICKS_SUM += SLIP_TICKS;  WBC_FAIL_TICKS_SUM += WBC_FAIL_TICKS;  STEPS_SUM += STEPS;  LAST_CAUSE = cause;  LAST_TICKS =
+ *       TICKS;  EPISODES += 1;   DIST_X_SUM += LAST_BASE[0] - START_POS[0];  DIST_Y_SUM += LAST_BASE[1] - START_POS[1];  WORK_ABS_SUM +=
+ *       WORK_ABS;  TILT_MAX = max(TILT_MAX, record TILT_MAX);  TAU_MAX = max over the record's TAU_MAX[0..9] and itself.
+ *     Every difference and sum is rounded on its own.  Initial values (hb_plant_set_respawn with a configuration, hb_plant_reset): every
+ *     total 0, TICKS_MIN included (it is the first folded TICKS from the first fold on), LAST_CAUSE HB_EP_RUNNING.
+ *     Identity: for every instance, at any time,  STEPS_SUM + (STEPS of its current record) = the plant steps enqueued since the totals
+ *     were last started; and EPISODE_INDEX == EPISODES, N_FALLEN + N_NONFINITE + N_TIMEOUT == EPISODES.
+ *  2. Draw of the spawn state.  e = EPISODE_INDEX + 1, the index of the episode that starts (the state of hb_plant_reset is episode 0 and is
+ *     never drawn).  Philox4x32-10 and Box-Muller as for hb_plant_sense (above), u = (word + 0.5) 2^-32:
+ *       key = (seed low 32, seed high 32);  counter = (instance_offset + i, e, HB_RS_STREAM, block).
+ *       block 0, word 0: the uniform u of the yaw offset;  q[3] = q_spawn[3] + yaw_range (2 u - 1)       (words 1-3 unused)
+ *       normal n is lane n % 4 of block 1 + n / 4:  n = 0..9: q[6 + n] = q_spawn[6 + n] + joint_pos_sigma z_n   (blocks 1, 2, 3)
+ *                                                   n = 12..14: v[n - 12] = v_spawn[n - 12] + base_vel_sigma z_n  (block 4)
+ *     Everything else of q[16], v[16] is q_spawn / v_spawn (v_spawn NULL: zero).  A channel with range / sigma 0 leaves the given value bit
+ *     for bit and its blocks are not generated.  Same seed, same instance_offset + i, same e: same bits (a shard reproduces its slice).
+ *  3. Placement (place = 1): (n, d) the instance's plane by the rule of step 4 of the episode record; g = min over the four contact points
+ *     c of n . p_c - d (summed x, y, z, unfused), p_c the contact points at q;  q[0:3] += (clearance - g) n.  The result is the "last
+ *     spawned state" hb_plant_get_respawn returns.
+ *  4. Plant: q, v;  anchor = the contact points at q, pinned 0, contact_last 1, lambda, vdot, tau_last 0 (what hb_plant_reset leaves).  Zeroed
+ *     where the arrays exist: the contact model's impulses, outputs and status word (HB_CONTACT_FALLEN with it; the external wrench stays);
+ *     the joint model's impulses, outputs and status; the actuator record (tau_first, tau_mean, the received command, the timestamp filter);
+ *     the emergency-stop latch.  Terrain and model variation stay: they belong to the instance.
+ *  5. Episode: the record restarts from the new state (initial values above hb_plant_set_episode), its trace rows are zeroed, EPISODE_INDEX
+ *     += 1.
+ *  6. Estimator, if hb_estimator_reset has run: x_hat = (q[0:3], 0 0 0, the four contact points at q), P = 100 I (what hb_estimator_reset
+ *     leaves), yaw_last = 0, low-pass state of hb_estimator_contact_force = 0.
+ *  7. The plant's rbd, the resident rbd and the resident MPC observation are repacked from (q, v) as a plant step with to_resident does; the
+ *     resident time is left alone.
+ *  8. Two pending flags for the MPC side, each consumed once, by the next hb_refgen_update and the next hb_mpc_solve on the MPC stream:
+ *     the reference generation takes the flagged instance's latest stance positions from the observation of THAT call (as for the whole
+ *     batch after hb_refgen_reset(..., NULL)); the solve cold-starts the flagged instances after the warm start onto the new tables
+ *     (hb_mpc_reset_masked semantics: iterate, grid_dirty, status word).
+ *  9. Device gait manager, if enabled: the instance becomes a fresh object (hb_gait_reset with a mask).  Host-supplied schedules are the
+ *     caller's and are left alone.
+ *
+ * Limits.  With a respawn configuration in force hb_step_resident and hb_tick_resident return HB_ERR_STATE (the instance-range / graph
+ * paths do not consume the pending flags).  The policy published before a respawn belongs to the old episode: call hb_plant_respawn so
+ * that the next tick is an MPC tick (reference generation, solve, publish), as ResidentLoop does.  With respawn off every call enqueues
+ * exactly what it enqueued before. */
+#define HB_RS_TIMEOUT 3          /* cause of an episode ended by max_ticks (beside HB_EP_FALLEN / HB_EP_NONFINITE) */
+#define HB_RS_STREAM 0x52535031u /* third counter word of the respawn stream */
+enum {   /* itot */
+  HB_RS_I_EPISODES = 0, HB_RS_I_N_FALLEN = 1, HB_RS_I_N_NONFINITE = 2, HB_RS_I_N_TIMEOUT = 3, HB_RS_I_TICKS_SUM = 4, HB_RS_I_TICKS_MIN = 5,
+  HB_RS_I_TICKS_MAX = 6, HB_RS_I_SLIP_TICKS_SUM = 7, HB_RS_I_WBC_FAIL_TICKS_SUM = 8, HB_RS_I_LAST_CAUSE = 9, HB_RS_I_LAST_TICKS = 10,
+  HB_RS_I_EPISODE_INDEX = 11, HB_RS_I_STEPS_SUM = 12, HB_RS_NI = 13
+};
+enum {   /* dtot */
+  HB_RS_D_DIST_X_SUM = 0, HB_RS_D_DIST_Y_SUM = 1, HB_RS_D_WORK_ABS_SUM = 2, HB_RS_D_TILT_MAX = 3, HB_RS_D_TAU_MAX = 4, HB_RS_ND = 5
+};
+typedef struct hb_respawn_config {
+  double clearance;        /* m, >= 0: gap of the lowest contact point after placement */
+  double yaw_range;        /* rad, >= 0: uniform yaw offset in [-yaw_range, yaw_range] */
+  double joint_pos_sigma;  /* rad, >= 0: Gaussian perturbation of the 10 joint angles */
+  double base_vel_sigma;   /* m/s, >= 0: Gaussian perturbation of the 3 linear base velocities */
+  uint64_t seed;
+  uint32_t instance_offset; /* global index of instance 0 of this context */
+  int32_t hold_ticks;      /* >= 0: plant steps an ended instance waits after its end step */
+  int32_t max_ticks;       /* >= 0; 0: none.  An instance still up with TICKS >= max_ticks is respawned as timed out */
+  int32_t place;           /* 0 / 1 */
+  int32_t reserved[2];     /* 0 */
+} hb_respawn_config;
+/* cfg NULL: off.  q_spawn[batch][16] (required with cfg), v_spawn[batch][16] or NULL = zero.  Starts the totals (initial values above);
+ * "last spawned state" starts as (q_spawn, v_spawn).  The configuration survives hb_plant_reset, which restarts the totals (as does
+ * hb_plant_set_episode with a configuration: the totals account for the steps of the records they folded); turning the episode off turns
+ * respawn off.  HB_ERR_STATE before hb_plant_reset or with no episode in force; HB_ERR_ARG (the configuration in force
+ * is kept) for a negative or non-finite clearance / yaw_range / joint_pos_sigma / base_vel_sigma, hold_ticks < 0, max_ticks < 0, place not
+ * 0 / 1, a nonzero `reserved`, or cfg without q_spawn. */
+int32_t hb_plant_set_respawn(hb_ctx* ctx, const hb_respawn_config* cfg, const double* q_spawn, const double* v_spawn);
+/* Enqueue-only.  HB_ERR_STATE without a respawn configuration in force. */
+int32_t hb_plant_respawn(hb_ctx* ctx);
+/* itot[batch][HB_RS_NI], dtot[batch][HB_RS_ND], q_last / v_last [batch][16] = the last spawned state; any may be NULL.  Synchronises like
+ * hb_plant_get_episode.  HB_ERR_STATE without a respawn configuration in force. */
+int32_t hb_plant_get_respawn(hb_ctx* ctx, int32_t* itot, double* dtot, double* q_last, double* v_last);
+
 /* ---- sensors from the plant: what LeggedController::updateStateEstimation reads, computed on the device -----------
  * hb_plant_sense turns the plant's state into the sensor arrays of hb_estimator_update and leaves them on the device
  * (plant-owned arrays [batch][4|3|3|10|10|10] and int [batch][4]); hb_estimator_update_resident /

@@ -6,6 +6,8 @@
     python tools/sweep_rollout.py --grid 64 64 --ticks 5000   friction x slope on a grid, one scenario per instance (4096), static schedules
     python tools/sweep_rollout.py --payload 8 5 --ticks 5000  payload mass 0 .. 15 kg x fore-aft offset -0.1 .. 0.1 m, 0.15 m above the base origin, on
                                                         level ground with mu 0.7, one pair per instance (hb_plant_set_model_variation)
+    python tools/sweep_rollout.py --respawn 250 --ticks 2000  the friction sweep as repeated episodes of at most 250 ticks per instance (hb_plant_set_respawn:
+                                                        a fallen robot is put back at the next MPC boundary), read from the respawn totals alone
     python tools/sweep_rollout.py --readback            the two sweeps once more with the per-tick read-back loop the findings of items 17 - 20
                                                         were made with, for the wall time per tick of both
 
@@ -20,7 +22,7 @@ import numpy as np
 
 sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
 from hunter_bipedal_control_amd import abi, ingest  # noqa: E402
-from hunter_bipedal_control_amd.rollout import ResidentLoop, episode_summary, payload_on_base  # noqa: E402
+from hunter_bipedal_control_amd.rollout import ResidentLoop, episode_summary, payload_on_base, respawn_summary  # noqa: E402
 from hunter_bipedal_control_amd.solver import HunterSolver  # noqa: E402
 
 FRICTION = [0.7, 0.5, 0.4, 0.3, 0.2, 0.15, 0.1, 0.05]
@@ -34,7 +36,7 @@ def normals_of(pitch):
     return np.stack([np.sin(pitch), np.zeros_like(pitch), np.cos(pitch)], axis=1)
 
 
-def make_loop(params, mu, pitch, ticks, static, joint_model, payload=None):
+def make_loop(params, mu, pitch, ticks, static, joint_model, payload=None, respawn=None):
     """One batch: instance i trots on a plane of pitch[i] with friction mu[i] under all four points, carrying payload[i] ([B][10]) if given."""
     B = len(mu)
     s = HunterSolver(params, batch=B, max_nodes=108)
@@ -43,8 +45,22 @@ def make_loop(params, mu, pitch, ticks, static, joint_model, payload=None):
     loop = ResidentLoop(s, params, ["trot"] * B, cmd, contact_config=dict(fall_height=0.3), joint_model=joint_model,
                         terrain=dict(plane=normals_of(pitch), mu=np.repeat(np.asarray(mu, dtype=float)[:, None], 4, axis=1)),
                         static_schedule_until=(ticks * 0.002 + horizon + 1.5) if static else 0.0, episode=dict(slip_speed=0.05),
-                        model_variation=None if payload is None else dict(payload=payload))
+                        model_variation=None if payload is None else dict(payload=payload), respawn=respawn)
     return s, loop
+
+
+def run_respawn(params, mu, ticks, max_ticks, joint_model=None):
+    """The friction sweep as repeated episodes -> (respawn totals, wall seconds of the ticks)."""
+    s, loop = make_loop(params, mu, [0.0] * len(mu), ticks, False, joint_model,
+                        respawn=dict(max_ticks=max_ticks, hold_ticks=0, place=1, clearance=0.0, yaw_range=0.1, joint_pos_sigma=0.005, seed=1))
+    try:
+        s.sync()
+        t0 = time.perf_counter()
+        loop.run(ticks)
+        tot = loop.respawn_totals()
+        return tot, time.perf_counter() - t0
+    finally:
+        s.close()
 
 
 def run_record(params, mu, pitch, ticks, static=False, joint_model=None, payload=None):
@@ -107,10 +123,23 @@ def main():
     ap.add_argument("--payload", type=int, nargs=2, metavar=("N_MASS", "N_OFFSET"),
                     help="payload mass 0 .. 15 kg x fore-aft offset -0.1 .. 0.1 m at 0.15 m above the base origin, one instance per pair")
     ap.add_argument("--joint-model", action="store_true", help="the joints of the reference's MuJoCo model instead of ideal joints")
+    ap.add_argument("--respawn", type=int, metavar="N_TICKS", help="the friction sweep as repeated episodes of at most N_TICKS ticks, from the respawn totals")
     ap.add_argument("--readback", action="store_true", help="also time the per-tick read-back loop on the two sweeps")
     args = ap.parse_args()
     params = ingest.load_packaged()
     jm = {} if args.joint_model else None
+    if args.respawn:
+        tot, wall = run_respawn(params, FRICTION, args.ticks, args.respawn, joint_model=jm)
+        summ = respawn_summary(tot, dt=0.002)
+        print(f"-- friction sweep as repeated episodes of at most {args.respawn} ticks, B = {len(FRICTION)}, {args.ticks} ticks, run(): "
+              f"{1e3 * wall / args.ticks:.3f} ms per tick")
+        heads = ("mu", "episodes", "fallen", "nonfin", "timeout", "fall_rate", "mean_ticks", "mean_s", "dist_x", "tiltmax", "taumax")
+        print(" ".join(f"{h:>10}" for h in heads))
+        for i, m in enumerate(FRICTION):
+            row = (m, int(tot["EPISODES"][i]), int(tot["N_FALLEN"][i]), int(tot["N_NONFINITE"][i]), int(tot["N_TIMEOUT"][i]), summ["fall_rate"][i],
+                   summ["mean_ticks"][i], summ["mean_time"][i], summ["mean_distance_x"][i], tot["TILT_MAX"][i], tot["TAU_MAX"][i])
+            print(" ".join(f"{x:>10}" if isinstance(x, int) else f"{x:10.4g}" for x in row))
+        return
     if args.payload:
         n_m, n_x = args.payload
         masses, offsets = np.linspace(0.0, 15.0, n_m), np.linspace(-0.1, 0.1, n_x)
