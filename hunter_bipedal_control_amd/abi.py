@@ -327,6 +327,52 @@ def split_respawn_totals(itot, dtot) -> dict:
     return out
 
 
+class HbScenarioConfig(C.Structure):
+    """hb_scenario_config (include/hunter_hip.h): scenario draw at respawn, hb_plant_set_scenario."""
+    _fields_ = [("seed", C.c_uint64), ("channels", C.c_int32), ("mu_per_point", C.c_int32), ("grade_max", C.c_double), ("mu_lo", C.c_double),
+                ("mu_hi", C.c_double), ("payload_mass_max", C.c_double), ("payload_center", C.c_double * 3),
+                ("payload_half_extent", C.c_double * 3), ("mass_scale_range", C.c_double), ("push_force_max", C.c_double),
+                ("push_start_lo", C.c_int32), ("push_start_hi", C.c_int32), ("push_ticks", C.c_int32), ("log_capacity", C.c_int32),
+                ("reserved", C.c_int32 * 2)]
+
+
+HB_SC_STREAM = 0x53434E31
+HB_SC_SLOPE, HB_SC_MU, HB_SC_PAYLOAD, HB_SC_MASS, HB_SC_PUSH = 1, 2, 4, 8, 16
+HB_SC_ALL = HB_SC_SLOPE | HB_SC_MU | HB_SC_PAYLOAD | HB_SC_MASS | HB_SC_PUSH
+# scen[HB_SC_N], (name, first index, count), in the order of the HB_SC_* indices of the header.
+SCENARIO_FIELDS = (("GRADE", 0, 2), ("MUS", 2, 4), ("PAYLOAD_M", 6, 1), ("PAYLOAD_R", 7, 3), ("SCALE", 10, 11), ("PUSH_START", 21, 1), ("PUSH_F", 22, 2))
+HB_SC_N = 24
+# a log row: these six, then the HB_SC_N parameters
+SCENARIO_LOG_HEAD = ("EPISODE", "CAUSE", "TICKS", "DIST_X", "DIST_Y", "TILT_MAX")
+HB_SC_LOG_W, HB_SC_LOG_MAX = len(SCENARIO_LOG_HEAD) + HB_SC_N, 1024
+
+
+def make_scenario_config(**fields) -> HbScenarioConfig:
+    """No channel, no log, seed 0, mu in [0, 0], push_ticks 0; any field by name overrides (payload_center / payload_half_extent: 3 values)."""
+    d = dict(seed=0, channels=0, mu_per_point=0, grade_max=0.0, mu_lo=0.0, mu_hi=0.0, payload_mass_max=0.0, payload_center=(0.0, 0.0, 0.0),
+             payload_half_extent=(0.0, 0.0, 0.0), mass_scale_range=0.0, push_force_max=0.0, push_start_lo=0, push_start_hi=0, push_ticks=0,
+             log_capacity=0)
+    for k in fields:
+        if k not in d:
+            raise TypeError(f"make_scenario_config: unknown field {k!r} (one of {sorted(d)})")
+    d.update(fields)
+    out = HbScenarioConfig()
+    for k in ("grade_max", "mu_lo", "mu_hi", "payload_mass_max", "mass_scale_range", "push_force_max"):
+        setattr(out, k, float(d[k]))
+    for k in ("seed", "channels", "mu_per_point", "push_start_lo", "push_start_hi", "push_ticks", "log_capacity"):
+        setattr(out, k, int(d[k]))
+    for k in ("payload_center", "payload_half_extent"):
+        for a in range(3):
+            getattr(out, k)[a] = float(d[k][a])
+    return out
+
+
+def split_scenario(scen) -> dict:
+    """scen[...][HB_SC_N] -> dict of [...] / [...][n] arrays keyed by field name."""
+    scen = np.asarray(scen)
+    return {name: (scen[..., at].copy() if n == 1 else scen[..., at:at + n].copy()) for name, at, n in SCENARIO_FIELDS}
+
+
 class HbJointGains(C.Structure):
     _fields_ = [(k, C.c_double) for k in ("kp_big_stance", "kp_big_swing", "kd_big", "kp_small_stance", "kp_small_swing", "kd_small",
                                           "kd_feet", "kp_position", "kd_position")]

@@ -125,6 +125,12 @@ struct hb_ctx {
   RespawnBatch respawn{};
   hb_respawn_config respawn_cfg{};
   bool respawn_on = false, rs_rg_due = false, rs_mpc_due = false;
+  // scenario draw at respawn (hb_plant_set_scenario): scenario_on while a configuration is in force; the arrays are allocated by the first
+  // call that gives one.  While it is on the device owns the terrain and model records (terrain_host / modelvar_host are stale and the
+  // getters read the device) and, with HB_SC_PUSH, the external wrench.
+  ScenarioBatch scenario{};
+  hb_scenario_config scenario_cfg{};
+  bool scenario_on = false;
   // reference generation (allocated on the first hb_refgen_reset)
   RefgenBatch rg{};
   hb_refgen_config rg_cfg{};

@@ -23,7 +23,14 @@ static int32_t episode_start(hb_ctx* ctx, hipStream_t s) {
 // the update of the record behind it: the one place every step entry point and every plant form goes through.
 template <class F>
 static int32_t plant_write(hb_ctx* ctx, hipStream_t s, bool fence, double dt, F&& launch) {
-  HB_TRY(resident_write(ctx, s, fence, launch));
+  if (ctx->scenario_on && (ctx->scenario_cfg.channels & HB_SC_PUSH)) {   // the scenario's push: the wrench of this step, ahead of the plant kernel
+    HB_TRY(resident_write(ctx, s, fence, [&] {
+      hipLaunchKernelGGL(k_plant_push, dim3((ctx->B + 63) / 64), dim3(64), 0, s, ctx->scenario, ctx->scenario_cfg, ctx->episode, ctx->contact.wrench);
+      launch();
+    }));
+  } else {
+    HB_TRY(resident_write(ctx, s, fence, launch));
+  }
   if (!ctx->episode_on) return HB_OK;
   double d0;
   const double* ter = episode_plane(ctx, &d0);
@@ -38,6 +45,8 @@ static int32_t plant_write(hb_ctx* ctx, hipStream_t s, bool fence, double dt, F&
 extern "C" {
 
 static int32_t respawn_totals_start(hb_ctx* ctx, hipStream_t s);   // (below, with the respawn entry points)
+static int32_t scenario_off(hb_ctx* ctx);                           // (below, with the scenario entry points)
+static int32_t scenario_start(hb_ctx* ctx, bool rows);
 
 // joint command outputs and the per-instance controller flags (allocated on first use; loaded = 1, no emergency stop)
 static int32_t joint_state_alloc(hb_ctx* ctx) {
@@ -139,7 +148,7 @@ int32_t hb_plant_set_episode(hb_ctx* ctx, const hb_episode_config* cfg) {
   if (!cfg) {
     ctx->episode_on = false;
     ctx->respawn_on = false;   // the respawn reads its decision from the record
-    return HB_OK;
+    return scenario_off(ctx);  // ... and the scenario is drawn at respawn
   }
   EpisodeBatch& e = ctx->episode;
   if (!e.drec) {  // (drec: the last array of the description, so an allocation that failed half way is repeated)
@@ -208,10 +217,12 @@ int32_t hb_plant_set_respawn(hb_ctx* ctx, const hb_respawn_config* cfg, const do
   HB_ENTER_DEVICE();
   HB_HIP(hipStreamSynchronize(ctx->s_wbc));  // (a respawn in flight still runs under the configuration it was launched with)
   if (!cfg) {
-    std::lock_guard<std::mutex> lk(ctx->mtx);
-    ctx->respawn_on = false;
-    ctx->rs_rg_due = ctx->rs_mpc_due = false;   // (flags still pending are dropped: the next configuration starts with none)
-    return HB_OK;
+    {
+      std::lock_guard<std::mutex> lk(ctx->mtx);
+      ctx->respawn_on = false;
+      ctx->rs_rg_due = ctx->rs_mpc_due = false;   // (flags still pending are dropped: the next configuration starts with none)
+    }
+    return scenario_off(ctx);   // the scenario is drawn at respawn
   }
   RespawnBatch& r = ctx->respawn;
   if (!r.mpc_pending) {  // (mpc_pending: the last array of the description, so an allocation that failed half way is repeated)
@@ -242,6 +253,12 @@ int32_t hb_plant_respawn(hb_ctx* ctx) {
   // a writer of the resident observation, and of the pending flags and the gait state the MPC stream reads: always between the two
   // ordering points
   HB_TRY(resident_write(ctx, s, true, [&] {
+    if (ctx->scenario_on) {   // the scenario of the episode that starts, drawn ahead of the respawn from the same decision
+      const int ch = ctx->scenario_cfg.channels;
+      hipLaunchKernelGGL(k_plant_scenario, dim3(ctx->B), dim3(64), 0, s, ctx->scenario, ctx->scenario_cfg, ctx->respawn_cfg, ctx->respawn, ctx->episode,
+                         (ch & (HB_SC_SLOPE | HB_SC_MU)) ? ctx->terrain.ter : nullptr, (ch & (HB_SC_PAYLOAD | HB_SC_MASS)) ? ctx->modelvar.mdl : nullptr,
+                         ctx->dmodel, ctx->contact_cfg.ground_z);
+    }
     hipLaunchKernelGGL(k_plant_respawn, dim3(ctx->B), dim3(64), 0, s, ctx->respawn, ctx->respawn_cfg, ctx->episode, ctx->plant, cb, jb, ab, est,
                        ctx->gait, ctx->gait_cfg, ctx->gait_on ? 1 : 0, ter, d0, ctx->dmodel, ctx->jc_estop, ctx->w.rbd, ctx->b.x0);
   }));
@@ -260,6 +277,138 @@ int32_t hb_plant_get_respawn(hb_ctx* ctx, int32_t* itot, double* dtot, double* q
   HB_TRY(pull(ctx, dtot, r, r.dtot, whole(ctx)));
   HB_TRY(pull(ctx, q_last, r, r.q_last, whole(ctx)));
   HB_TRY(pull(ctx, v_last, r, r.v_last, whole(ctx)));
+  return HB_OK;
+}
+
+// ---- scenario draw at respawn (include/hunter_hip.h above hb_plant_set_scenario) --------------------------------------------------------
+static int32_t modelvar_level(hb_ctx* ctx);   // (below, with the model variation)
+static int32_t contact_ready(hb_ctx* ctx, const char* who);
+
+// the level record of the configuration in force, for every instance
+static std::vector<double> terrain_level_image(const hb_ctx* ctx) {
+  const hb_contact_config& K = ctx->contact_cfg;
+  const double level[Terrain::size] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0, K.ground_z, K.mu, K.mu, K.mu, K.mu};
+  std::vector<double> rec(size_t(ctx->B) * Terrain::size);
+  for (size_t i = 0; i < size_t(ctx->B); ++i) std::memcpy(rec.data() + i * Terrain::size, level, sizeof level);
+  return rec;
+}
+
+// No finished episode logged and no push in every instance; with `rows`, scen back to "before the first draw" too.  Synchronous; the
+// caller has drained ctx->s_wbc.
+static int32_t scenario_start(hb_ctx* ctx, bool rows) {
+  ScenarioBatch& c = ctx->scenario;
+  const size_t B = ctx->B;
+  std::vector<double> scen(B * HB_SC_N), psh(B * SC_PUSH);
+  for (size_t i = 0; i < B; ++i) scenario_row_init(scen.data() + HB_SC_N * i, psh.data() + SC_PUSH * i);
+  if (rows) HB_TRY(push(ctx, scen.data(), c, c.scen, whole(ctx)));
+  HB_TRY(push(ctx, psh.data(), c, c.push, whole(ctx)));
+  HB_HIP(hipMemset(c.count, 0, field_count(ctx, c, c.count) * sizeof(int)));
+  if (c.log) HB_HIP(hipMemset(c.log, 0, B * c.log_cap * HB_SC_LOG_W * 8));
+  return HB_OK;
+}
+
+// The host images of the records the device has been drawing, from the device.  The caller has drained ctx->s_wbc.
+static int32_t scenario_refresh_host(hb_ctx* ctx) {
+  if (!ctx->scenario_on) return HB_OK;
+  const int ch = ctx->scenario_cfg.channels;
+  if ((ch & (HB_SC_SLOPE | HB_SC_MU)) && ctx->terrain_on) HB_TRY(pull(ctx, ctx->terrain_host.data(), ctx->terrain, ctx->terrain.ter, whole(ctx)));
+  if ((ch & (HB_SC_PAYLOAD | HB_SC_MASS)) && ctx->modelvar_on) HB_TRY(pull(ctx, ctx->modelvar_host.data(), ctx->modelvar, ctx->modelvar.mdl, whole(ctx)));
+  return HB_OK;
+}
+
+// Scenario off: terrain and variation stay in force as last drawn (the host images follow the device), the wrench the scenario owned is
+// cleared.  The caller has drained ctx->s_wbc.
+static int32_t scenario_off(hb_ctx* ctx) {
+  if (!ctx->scenario_on) return HB_OK;
+  HB_TRY(scenario_refresh_host(ctx));
+  ctx->scenario_on = false;
+  if (ctx->scenario_cfg.channels & HB_SC_PUSH) {
+    ContactBatch& c = ctx->contact;
+    HB_HIP(hipMemset(c.wrench, 0, field_count(ctx, c, c.wrench) * 8));
+    c.use_wrench = 0;
+  }
+  return HB_OK;
+}
+
+int32_t hb_plant_set_scenario(hb_ctx* ctx, const hb_scenario_config* cfg) {
+  HB_ENTER_ARGS(false);
+  if (!cfg && !ctx->scenario_on) return HB_OK;
+  HB_TRY(contact_ready(ctx, "hb_plant_set_scenario"));
+  HB_FAIL_IF(cfg && !ctx->respawn_on, HB_ERR_STATE, "hb_plant_set_scenario: no respawn configuration in force (hb_plant_set_respawn): the scenario is drawn at respawn");
+  if (const char* why = cfg ? scenario_config_refusal(*cfg) : nullptr) {
+    ctx->err = std::string("hb_plant_set_scenario: ") + why + " (the configuration in force is kept)";
+    return HB_ERR_ARG;
+  }
+  HB_ENTER_DEVICE();
+  HB_HIP(hipStreamSynchronize(ctx->s_wbc));  // (a respawn or a step in flight still runs under the configuration it was launched with)
+  HB_TRY(scenario_off(ctx));   // (a configuration in force hands its records and its wrench back first; a failure below leaves it off)
+  if (!cfg) return HB_OK;
+  ScenarioBatch& c = ctx->scenario;
+  if (!c.count) {  // (count: the last array of the description, so an allocation that failed half way is repeated)
+    HB_HIP(alloc_fields(ctx, c));
+    c.B = ctx->B;
+  }
+  if (cfg->log_capacity > c.log_cap) {  // the log grows to the largest capacity asked for
+    if (c.log) {
+      ctx->allocs.erase(std::remove(ctx->allocs.begin(), ctx->allocs.end(), static_cast<void*>(c.log)), ctx->allocs.end());
+      HB_HIP(hipFree(c.log));
+      c.log = nullptr;
+      c.log_cap = 0;
+    }
+    HB_HIP(dalloc(ctx, &c.log, size_t(ctx->B) * cfg->log_capacity * HB_SC_LOG_W));
+    c.log_cap = cfg->log_capacity;
+  }
+  if ((cfg->channels & (HB_SC_SLOPE | HB_SC_MU)) && !ctx->terrain_on) {   // the level record: the step without a terrain, value for value
+    TerrainBatch& t = ctx->terrain;
+    if (!t.ter) {
+      HB_HIP(alloc_fields(ctx, t));
+      t.B = ctx->B;
+    }
+    std::vector<double> rec = terrain_level_image(ctx);
+    HB_TRY(push(ctx, rec.data(), t, t.ter, whole(ctx)));
+    ctx->terrain_host = std::move(rec);
+    ctx->terrain_on = true;
+  }
+  if ((cfg->channels & (HB_SC_PAYLOAD | HB_SC_MASS)) && !ctx->modelvar_on) {   // nominal copies
+    ModelVarBatch& m = ctx->modelvar;
+    if (!m.mdl) {
+      HB_HIP(alloc_fields(ctx, m));
+      m.B = ctx->B;
+    }
+    std::vector<DevModel> img(size_t(ctx->B), ctx->hmodel);
+    HB_TRY(push(ctx, img.data(), m, m.mdl, whole(ctx)));
+    ctx->modelvar_host = std::move(img);
+    ctx->modelvar_on = true;
+    HB_TRY(modelvar_level(ctx));
+  }
+  if (cfg->channels & HB_SC_PUSH) {   // the scenario owns the wrench
+    ContactBatch& cb = ctx->contact;
+    HB_HIP(hipMemset(cb.wrench, 0, field_count(ctx, cb, cb.wrench) * 8));
+    cb.use_wrench = 1;
+  }
+  ctx->scenario_cfg = *cfg;
+  ctx->scenario_on = true;
+  return scenario_start(ctx, true);
+}
+
+int32_t hb_plant_get_scenario(hb_ctx* ctx, double* scen) {
+  HB_ENTER_ARGS(false);
+  HB_FAIL_IF(!ctx->scenario_on, HB_ERR_STATE, "hb_plant_get_scenario: no scenario in force (hb_plant_set_scenario)");
+  HB_ENTER_DEVICE();
+  HB_HIP(hipStreamSynchronize(ctx->s_wbc));
+  return pull(ctx, scen, ctx->scenario, ctx->scenario.scen, whole(ctx));
+}
+
+int32_t hb_plant_get_scenario_log(hb_ctx* ctx, int32_t* count, double* log) {
+  HB_ENTER_ARGS(false);
+  HB_FAIL_IF(!ctx->scenario_on, HB_ERR_STATE, "hb_plant_get_scenario_log: no scenario in force (hb_plant_set_scenario)");
+  HB_ENTER_DEVICE();
+  HB_HIP(hipStreamSynchronize(ctx->s_wbc));
+  ScenarioBatch& c = ctx->scenario;
+  HB_TRY(pull(ctx, count, c, c.count, whole(ctx)));
+  // (the device rows have the pitch of the largest capacity set so far; the caller's have the pitch of the one in force)
+  const size_t row = size_t(ctx->scenario_cfg.log_capacity) * HB_SC_LOG_W * 8;
+  if (log && row) HB_HIP(hipMemcpy2D(log, row, c.log, size_t(c.log_cap) * HB_SC_LOG_W * 8, row, size_t(ctx->B), hipMemcpyDeviceToHost));
   return HB_OK;
 }
 
@@ -284,6 +433,7 @@ int32_t hb_plant_reset(hb_ctx* ctx, const double* q0, const double* v0, double b
   if (ctx->episode_on) HB_TRY(episode_start(ctx, ctx->s_wbc));   // the record restarts from the reset state
   if (ctx->respawn_on) HB_TRY(respawn_totals_start(ctx, ctx->s_wbc));   // ... and so do the totals of the respawn
   HB_HIP(hipStreamSynchronize(ctx->s_wbc));
+  if (ctx->scenario_on) HB_TRY(scenario_start(ctx, false));   // the log is empty, nobody has a push; terrain, models and scen stay as last drawn
   ctx->plant_ready = true;
   return HB_OK;
 }
@@ -455,10 +605,7 @@ static int32_t modelvar_level(hb_ctx* ctx) {
     HB_HIP(alloc_fields(ctx, t));
     t.B = ctx->B;
   }
-  const hb_contact_config& K = ctx->contact_cfg;
-  const double level[Terrain::size] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0, K.ground_z, K.mu, K.mu, K.mu, K.mu};
-  std::vector<double> rec(size_t(ctx->B) * Terrain::size);
-  for (size_t i = 0; i < size_t(ctx->B); ++i) std::memcpy(rec.data() + i * Terrain::size, level, sizeof level);
+  const std::vector<double> rec = terrain_level_image(ctx);
   HB_HIP(hipStreamSynchronize(ctx->s_wbc));
   return push(ctx, rec.data(), t, t.ter, whole(ctx));
 }
@@ -482,6 +629,7 @@ int32_t hb_plant_set_contact_model(hb_ctx* ctx, const hb_contact_config* cfg) {
     PlantBatch& p = ctx->plant;
     HB_HIP(hipMemsetAsync(p.pinned, 0, field_count(ctx, p, p.pinned) * sizeof(int), ctx->s_wbc));
   }
+  if (!ground) HB_TRY(scenario_off(ctx));   // the scenario belongs to contact model 1 (and gives the wrench back)
   ctx->contact_cfg = ground ? *cfg : hb_contact_config{};
   if (!ground) ctx->terrain_on = false;   // the terrain belongs to contact model 1
   if (!ground) ctx->modelvar_on = false;  // ... and so does the model variation
@@ -504,6 +652,7 @@ static int32_t contact_ready(hb_ctx* ctx, const char* who) {
 int32_t hb_plant_set_external_wrench(hb_ctx* ctx, const double* wrench) {
   HB_ENTER_ARGS(false);
   HB_TRY(contact_ready(ctx, "hb_plant_set_external_wrench"));
+  HB_FAIL_IF(ctx->scenario_on && (ctx->scenario_cfg.channels & HB_SC_PUSH), HB_ERR_STATE, "hb_plant_set_external_wrench: the scenario in force owns the wrench (hb_plant_set_scenario with HB_SC_PUSH)");
   HB_ENTER_DEVICE();
   ContactBatch& c = ctx->contact;
   HB_HIP(hipStreamSynchronize(ctx->s_wbc));  // (an earlier step may still be reading the wrench)
@@ -568,18 +717,11 @@ int32_t hb_plant_get_joints(hb_ctx* ctx, double* tau_applied, double* friction_t
 }
 
 // ---- per-instance terrain of contact model 1 (include/hunter_hip.h above hb_plant_set_terrain) ----------------------------------------
-// The frame of a unit normal n: t1 = (e_x - n_x n) / |e_x - n_x n|, t2 = n x t1, T = [t1 t2 n] row-major; the identity exactly for n = e_z.
-static void terrain_frame(const double n[3], double* T) {
-  double t1[3] = {1.0 - n[0] * n[0], -n[0] * n[1], -n[0] * n[2]};
-  const double l = std::sqrt(t1[0] * t1[0] + t1[1] * t1[1] + t1[2] * t1[2]);
-  for (double& x : t1) x /= l;
-  const double t2[3] = {n[1] * t1[2] - n[2] * t1[1], n[2] * t1[0] - n[0] * t1[2], n[0] * t1[1] - n[1] * t1[0]};
-  for (int a = 0; a < 3; ++a) { T[3 * a] = t1[a]; T[3 * a + 1] = t2[a]; T[3 * a + 2] = n[a]; }
-}
-
+// (the stored record of a plane — normalisation and the frame T — is hb_contact.hpp terrain_plane_record, shared with k_plant_scenario)
 int32_t hb_plant_set_terrain(hb_ctx* ctx, const double* plane, const double* mu) {
   HB_ENTER_ARGS(false);
   HB_TRY(contact_ready(ctx, "hb_plant_set_terrain"));
+  HB_FAIL_IF(!plane && !mu && ctx->scenario_on && (ctx->scenario_cfg.channels & (HB_SC_SLOPE | HB_SC_MU)), HB_ERR_STATE, "hb_plant_set_terrain: the scenario in force draws the terrain (hb_plant_set_scenario): turn it off first");
   const size_t B = ctx->B;
   std::vector<double> rec(B * Terrain::size);
   for (size_t i = 0; i < B && (plane || mu); ++i) {
@@ -588,12 +730,14 @@ int32_t hb_plant_set_terrain(hb_ctx* ctx, const double* plane, const double* mu)
     const char* why = nullptr;
     if (plane) {
       const double* pl = plane + 4 * i;
-      const double len = std::sqrt(pl[0] * pl[0] + pl[1] * pl[1] + pl[2] * pl[2]);
+      const double len = terrain_normal_length(pl);
       if (!(std::isfinite(pl[0]) && std::isfinite(pl[1]) && std::isfinite(pl[2]) && std::isfinite(pl[3]))) why = "a non-finite plane entry";
       else if (!(std::fabs(len - 1.0) <= 1e-9)) why = "a normal that is not of unit length (| |n| - 1 | > 1e-9)";
       else if (!(pl[2] / len >= 0.5)) why = "n_z < 0.5";
-      for (int a = 0; a < 3; ++a) n[a] = pl[a] / len;
-      d = pl[3];
+      if (!why) terrain_plane_record(pl, len, r);
+    } else {
+      terrain_frame(n, r + Terrain::T);
+      r[Terrain::d] = d;
     }
     for (int c = 0; c < HB_NC && !why; ++c) {
       const double m = mu ? mu[4 * i + c] : ctx->contact_cfg.mu;
@@ -604,8 +748,6 @@ int32_t hb_plant_set_terrain(hb_ctx* ctx, const double* plane, const double* mu)
       ctx->err = "hb_plant_set_terrain: instance " + std::to_string(i) + " has " + why + " (the terrain in force is kept)";
       return HB_ERR_ARG;
     }
-    terrain_frame(n, r + Terrain::T);
-    r[Terrain::d] = d;
   }
   HB_ENTER_DEVICE();
   HB_HIP(hipStreamSynchronize(ctx->s_wbc));  // (a step in flight still runs on the terrain it was launched with)
@@ -630,6 +772,11 @@ int32_t hb_plant_set_terrain(hb_ctx* ctx, const double* plane, const double* mu)
 int32_t hb_plant_get_terrain(hb_ctx* ctx, double* plane, double* mu, double* frame) {
   HB_ENTER_ARGS(false);
   HB_TRY(contact_ready(ctx, "hb_plant_get_terrain"));
+  if (ctx->scenario_on) {   // the device draws the records: the host image is stale
+    HB_ENTER_DEVICE();
+    HB_HIP(hipStreamSynchronize(ctx->s_wbc));
+    HB_TRY(scenario_refresh_host(ctx));
+  }
   for (size_t i = 0; i < size_t(ctx->B); ++i) {
     double r[Terrain::size] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0, ctx->contact_cfg.ground_z, ctx->contact_cfg.mu, ctx->contact_cfg.mu,
                                ctx->contact_cfg.mu, ctx->contact_cfg.mu};
@@ -645,6 +792,7 @@ int32_t hb_plant_get_terrain(hb_ctx* ctx, double* plane, double* mu, double* fra
 int32_t hb_plant_set_model_variation(hb_ctx* ctx, const double* mass_scale, const double* payload) {
   HB_ENTER_ARGS(false);
   HB_TRY(contact_ready(ctx, "hb_plant_set_model_variation"));
+  HB_FAIL_IF(!mass_scale && !payload && ctx->scenario_on && (ctx->scenario_cfg.channels & (HB_SC_PAYLOAD | HB_SC_MASS)), HB_ERR_STATE, "hb_plant_set_model_variation: the scenario in force draws the variation (hb_plant_set_scenario): turn it off first");
   const size_t B = ctx->B;
   const bool on = mass_scale || payload;
   std::vector<DevModel> img(on ? B : 0);
@@ -671,6 +819,11 @@ int32_t hb_plant_set_model_variation(hb_ctx* ctx, const double* mass_scale, cons
 int32_t hb_plant_get_model_variation(hb_ctx* ctx, double* mass, double* com, double* inertia, double* total_mass) {
   HB_ENTER_ARGS(false);
   HB_TRY(contact_ready(ctx, "hb_plant_get_model_variation"));
+  if (ctx->scenario_on) {   // the device draws the records: the host image is stale
+    HB_ENTER_DEVICE();
+    HB_HIP(hipStreamSynchronize(ctx->s_wbc));
+    HB_TRY(scenario_refresh_host(ctx));
+  }
   for (size_t i = 0; i < size_t(ctx->B); ++i) {
     const DevModel& d = ctx->modelvar_on ? ctx->modelvar_host[i] : ctx->hmodel;
     if (mass) std::memcpy(mass + HB_NBODY * i, d.mass, sizeof d.mass);

@@ -54,6 +54,33 @@ struct Terrain {
   static constexpr int T = 0, d = 9, mu = 10, size = 14;
 };
 constexpr int TER_LDS = Terrain::size;
+// The frame of a unit normal n: t1 = (e_x - n_x n) / |e_x - n_x n|, t2 = n x t1, T = [t1 t2 n] row-major; the identity exactly for n = e_z.
+// Every product, sum and quotient is rounded on its own, so the host setter and the device (k_plant_scenario) store the same bits.
+HB_HD void terrain_frame(const double n[3], double* T) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  double t1[3] = {1.0 - n[0] * n[0], -n[0] * n[1], -n[0] * n[2]};
+  const double l = sqrt(t1[0] * t1[0] + t1[1] * t1[1] + t1[2] * t1[2]);
+  for (int a = 0; a < 3; ++a) t1[a] /= l;
+  const double t2[3] = {n[1] * t1[2] - n[2] * t1[1], n[2] * t1[0] - n[0] * t1[2], n[0] * t1[1] - n[1] * t1[0]};
+  for (int a = 0; a < 3; ++a) { T[3 * a] = t1[a]; T[3 * a + 1] = t2[a]; T[3 * a + 2] = n[a]; }
+}
+// |pl[0:3]| of a plane (n, d), summed x, y, z
+HB_HD double terrain_normal_length(const double* pl) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  return sqrt(pl[0] * pl[0] + pl[1] * pl[1] + pl[2] * pl[2]);
+}
+// T and d of the record r[Terrain::size] of the plane pl[4] = (n, d), len = terrain_normal_length(pl): n is normalised before it is stored.
+// The four friction coefficients are the caller's.
+HB_HD void terrain_plane_record(const double* pl, double len, double* r) {
+  double n[3];
+  for (int a = 0; a < 3; ++a) n[a] = pl[a] / len;
+  terrain_frame(n, r + Terrain::T);
+  r[Terrain::d] = pl[3];
+}
 // (x, y, z) <- T' (x, y, z): world components to (t1, t2, n) components, every sum over the world axes in the order x, y, z.  T = I returns
 // the operand.
 HB_HD void terrain_to_frame(const double* T, double& x, double& y, double& z) {

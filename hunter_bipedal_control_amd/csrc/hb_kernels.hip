@@ -24,6 +24,7 @@
 #include "hb_joints.hpp"
 #include "hb_sensors.hpp"
 #include "hb_respawn.hpp"
+#include "hb_scenario.hpp"
 #include "hb_layout.hpp"
 #include "hb_iterate.hpp"
 #include "hb_wavectx.hpp"
@@ -1325,6 +1326,54 @@ __global__ __launch_bounds__(64) void k_plant_respawn(RespawnBatch rs, hb_respaw
   r.res_rbd = res_rbd + HB_NRBD * i; r.res_x0 = res_x0 + HB_NX * i;
   r.rg_pending = rs.rg_pending + i; r.mpc_pending = rs.mpc_pending + i;
   respawn_write(cx, r, q, v, feet, rbd, x0, plane);
+}
+
+// ---- scenario draw at respawn (hb_plant_set_scenario, hb_scenario.hpp): one wavefront per instance, ahead of k_plant_respawn -------------
+// Every lane reads k_plant_respawn's decision from the instance's still unchanged record (the same words: wave-uniform), and a wavefront
+// whose instance stays leaves after those loads.  A respawning wavefront appends the log row of the finished episode (all lanes, from the
+// scen still in place), draws its Philox blocks one per lane into LDS, stages its terrain record in LDS (all lanes), lets
+// lane 0 compose (the one sequential piece) and then writes terrain record, DevModel record, push record and scen with all lanes,
+// consecutive lanes on consecutive words.  ter / mdl: null where no channel of the pair is on.
+__global__ __launch_bounds__(64) void k_plant_scenario(ScenarioBatch sc, hb_scenario_config K, hb_respawn_config RK, RespawnBatch rs, EpisodeBatch e,
+                                                       double* ter, DevModel* mdl, const DevModel* __restrict__ M, double ground_z) {
+  const int i = blockIdx.x;
+  const DeviceCtx cx;
+  const int* irec = e.irec + HB_EP_NI * i;
+  const int cause = respawn_decide(RK, irec);
+  if (cause == 0) return;
+  __shared__ double sh[SC_DRAW + Terrain::size + SC_MODEL_WORDS + HB_SC_N + SC_PUSH + SC_WORK];
+  double* u = sh;
+  double* ter_s = u + SC_DRAW;
+  double* mdl_s = ter_s + Terrain::size;
+  double* scen_s = mdl_s + SC_MODEL_WORDS;
+  double* push_s = scen_s + HB_SC_N;
+  double* work = push_s + SC_PUSH;
+  const int* itot = rs.itot + HB_RS_NI * i;
+  ScenarioRows r{};
+  r.ter = ter ? ter + size_t(Terrain::size) * i : nullptr;
+  r.mdl = mdl ? reinterpret_cast<double*>(mdl + i) : nullptr;
+  r.push = sc.push + SC_PUSH * i;
+  r.scen = sc.scen + HB_SC_N * i;
+  if (K.log_capacity > 0)
+    scenario_log_append(cx, K.log_capacity, cause, irec, e.drec + HB_EP_ND * i, itot, r.scen, sc.count + i,
+                        sc.log + size_t(i) * sc.log_cap * HB_SC_LOG_W);
+  if (cx.lane < SC_BLOCKS && scenario_block_needed(K, cx.lane))
+    scenario_draw_block(K, RK.instance_offset + uint32_t(i), uint32_t(itot[HB_RS_I_EPISODE_INDEX] + 1), cx.lane, u, nullptr);
+  if (r.ter)
+    for (int a = cx.lane; a < Terrain::size; a += cx.nlanes) ter_s[a] = r.ter[a];
+  __syncthreads();
+  if (cx.lane == 0)   // (modelvar_compose writes the whole staged DevModel: the nominal copy, then the varied entries)
+    scenario_compose(K, u, rs.q_spawn + 16 * i, ground_z, *M, ter_s, reinterpret_cast<DevModel*>(mdl_s), scen_s, push_s, work);
+  __syncthreads();
+  scenario_store(cx, r, ter_s, mdl_s, push_s, scen_s);
+}
+
+// The push of the scenario: one thread per instance, ahead of the plant kernel.  Writes the instance's external wrench for the step that
+// follows from its push record and the STEPS of its current episode record.
+__global__ __launch_bounds__(64) void k_plant_push(ScenarioBatch sc, hb_scenario_config K, EpisodeBatch e, double* wrench) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= sc.B) return;
+  scenario_push_wrench(K, sc.push + SC_PUSH * i, e.irec[HB_EP_NI * i + HB_EP_I_STEPS], wrench + 6 * i);
 }
 
 // ---- sensors from the plant: one thread per instance, 64 instances per workgroup ---------------------------------------------------

@@ -217,6 +217,22 @@ constexpr void fields(RespawnBatch& r, size_t, F&& f) {
   HB_FIELD(r.v_last, 16); HB_FIELD(r.rg_pending, 1); HB_FIELD(r.mpc_pending, 1);
 }
 
+// scenario draw at respawn (hb_plant_set_scenario, hb_scenario.hpp), allocated by the first call that gives a configuration: the parameter
+// row of the current episode (scen), the push record (first pushed step or -1, F_x, F_y) and the number of logged episodes (count).  The
+// log is [B][log_cap][HB_SC_LOG_W] with log_cap the largest log_capacity set so far: a run-time extent, so the set call allocates it and
+// the description does not name it.
+struct ScenarioBatch {
+  int B;
+  int log_cap;
+  double *scen, *push;
+  int* count;
+  double* log;
+};
+template <class F>
+constexpr void fields(ScenarioBatch& c, size_t, F&& f) {
+  HB_FIELD(c.scen, HB_SC_N); HB_FIELD(c.push, 3); HB_FIELD(c.count, 1);
+}
+
 // actuator loop of the plant and the simulator end of the LCM link (hb_plant_step_hybrid, hb_plant_step_lcm, hb_plant_sense_lcm),
 // allocated on the first call that needs them — the held-torque path needs none: the record of the last hybrid step, the staging of a
 // host command and the received command (pos_des vel_des kp kd ff, one array each), the timestamp filter, the wire images
@@ -329,6 +345,7 @@ static_assert(sizeof(TerrainBatch) == kPtr /*B*/ + n_fields<TerrainBatch>() * kP
 static_assert(sizeof(ModelVarBatch) == kPtr /*B*/ + n_fields<ModelVarBatch>() * kPtr, "describe every array of ModelVarBatch in fields()");
 static_assert(sizeof(EpisodeBatch) == 2 * sizeof(int) + (n_fields<EpisodeBatch>() + 1 /*trace*/) * kPtr, "describe every array of EpisodeBatch in fields()");
 static_assert(sizeof(RespawnBatch) == kPtr /*B*/ + n_fields<RespawnBatch>() * kPtr, "describe every array of RespawnBatch in fields()");
+static_assert(sizeof(ScenarioBatch) == 2 * sizeof(int) + (n_fields<ScenarioBatch>() + 1 /*log*/) * kPtr, "describe every array of ScenarioBatch in fields()");
 static_assert(sizeof(ActuatorBatch) == kPtr /*B*/ + n_fields<ActuatorBatch>() * kPtr, "describe every array of ActuatorBatch in fields()");
 static_assert(sizeof(RefgenBatch) == kPtr /*B*/ + n_fields<RefgenBatch>() * kPtr + kPtr /*init_stance*/, "describe every array of RefgenBatch in fields()");
 static_assert(sizeof(GaitBatch) == 2 * sizeof(int) + n_fields<GaitBatch>() * kPtr, "describe every array of GaitBatch in fields()");

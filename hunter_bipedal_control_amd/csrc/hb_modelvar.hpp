@@ -19,6 +19,9 @@ constexpr double MODELVAR_PSD2 = 4.0 * 2.220446049250313e-16, MODELVAR_PSD3 = 64
 
 // P(m, d) = m (|d|^2 1 - d d') as xx xy xz yy yz zz: |d|^2 = (dx dx + dy dy) + dz dz; diagonal m (|d|^2 - da da); off-diagonal m (0 - da db)
 HB_HD void modelvar_shift(double m, const double* d, double* P) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
   const double dd = (d[0] * d[0] + d[1] * d[1]) + d[2] * d[2];
   P[0] = m * (dd - d[0] * d[0]);
   P[1] = m * (0.0 - d[0] * d[1]);
@@ -50,8 +53,12 @@ HB_HD const char* modelvar_refusal(const double* scale, const double* payload) {
   return nullptr;
 }
 
-// The instance's model.  Unvaried (no payload mass, every scale == 1.0): a copy of the nominal record, total_mass included.
+// The instance's model.  Unvaried (no payload mass, every scale == 1.0): a copy of the nominal record, total_mass included.  Nothing is
+// fused (here and in modelvar_shift): the device (k_plant_scenario) composes the bits the host composes.
 HB_HD void modelvar_compose(const DevModel& N, const double* scale, const double* payload, DevModel* out) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
   *out = N;
   const double mp = payload ? payload[Payload::m] : 0.0;
   bool varied = mp != 0.0;

@@ -167,7 +167,7 @@ class ResidentLoop:
     def __init__(self, solver, params: dict, gaits, cmd_vel, n_intervals: int = 100, mpc_every: int = 8, dt: float = 0.002,
                  t_gait_start: float = 0.3, joint_ik: bool = True, substeps: int = 4, static_schedule_until: float = 0.0,
                  device_gait: bool = False, use_estimator: bool = False, sensor_config=None, sensor_bias=None, contact_config=None,
-                 joint_model=None, actuator: str = "held", terrain=None, episode=None, model_variation=None, respawn=None):
+                 joint_model=None, actuator: str = "held", terrain=None, episode=None, model_variation=None, respawn=None, scenario=None):
         """static_schedule_until > 0: the mode schedules are uploaded once for [-1, static_schedule_until] (at most
         HB_MAX_EVENTS events) instead of a sliding window per MPC call — no per-call host work for large batches.
         device_gait: the device gait manager produces the windows; step() builds no per-instance list and uploads no schedule, and
@@ -194,7 +194,12 @@ class ResidentLoop:
         respawn: repeated episodes per instance (hb_plant_set_respawn) — None: a fallen robot stays fallen; a dict of
         abi.make_respawn_config fields plus, optionally, q_spawn / v_spawn [B][16] (default: the start configuration, at rest).  Needs
         episode= and is set after it.  step() / run() then call plant_respawn() after the plant step of every tick whose successor is an
-        MPC tick, so that the policy a respawned instance is driven by is always one of its own episode; respawn_totals() reads the totals."""
+        MPC tick, so that the policy a respawned instance is driven by is always one of its own episode; respawn_totals() reads the totals.
+        scenario: a scenario drawn on the device for every respawned instance (hb_plant_set_scenario) — None: none; a dict of
+        abi.make_scenario_config fields; an abi.HbScenarioConfig is taken as it is.  Needs respawn= (and contact_config=) and is set
+        after it; scenario() / scenario_log() read the current parameters and the log of the finished episodes."""
+        if scenario is not None and (respawn is None or contact_config is None):
+            raise ValueError("the scenario is drawn at respawn, for the ground-contact plant: give respawn= and contact_config= as well")
         if respawn is not None and episode is None:
             raise ValueError("respawn reads its decision from the episode record: give episode= as well")
         if model_variation is not None and contact_config is None:
@@ -260,6 +265,9 @@ class ResidentLoop:
             fields = dict(respawn)
             q_spawn, v_spawn = fields.pop("q_spawn", q0), fields.pop("v_spawn", None)
             solver.plant_set_respawn(abi.make_respawn_config(**fields), q_spawn, v_spawn)
+        self.has_scenario = scenario is not None
+        if scenario is not None:
+            solver.plant_set_scenario(abi.make_scenario_config(**scenario) if isinstance(scenario, dict) else scenario)
         # resident observation of the initial state
         rbd = np.zeros((self.B, 32))
         rbd[:, 0:3], rbd[:, 3:6], rbd[:, 6:16] = q0[:, 3:6], q0[:, 0:3], q0[:, 6:]
@@ -344,6 +352,34 @@ class ResidentLoop:
         if not self.has_respawn:
             raise ValueError("ResidentLoop was built without respawn=")
         return self.s.plant_respawn_totals(want_state)
+
+
+    def scenario(self):
+        """scen[B][HB_SC_N] of the episodes that are running (HunterSolver.plant_scenario)."""
+        if not self.has_scenario:
+            raise ValueError("ResidentLoop was built without scenario=")
+        return self.s.plant_scenario()
+
+    def scenario_log(self) -> dict:
+        """The log of the finished episodes (HunterSolver.plant_scenario_log)."""
+        if not self.has_scenario:
+            raise ValueError("ResidentLoop was built without scenario=")
+        return self.s.plant_scenario_log()
+
+
+def scenario_table(log: dict) -> dict:
+    """The log of HunterSolver.plant_scenario_log as flat arrays over all finished episodes that were logged, instance by instance in the
+    order they finished: INSTANCE, the six abi.SCENARIO_LOG_HEAD fields (EPISODE, CAUSE and TICKS as integers) and the parameters of
+    abi.SCENARIO_FIELDS ([n] or [n][k])."""
+    count, rows = np.asarray(log["count"]), np.asarray(log["log"])
+    inst = np.repeat(np.arange(len(count)), count)
+    flat = np.concatenate([rows[i, :count[i]] for i in range(len(count))], axis=0) if len(count) else np.zeros((0, abi.HB_SC_LOG_W))
+    flat = flat.reshape(-1, abi.HB_SC_LOG_W)
+    out = dict(INSTANCE=inst)
+    for k, name in enumerate(abi.SCENARIO_LOG_HEAD):
+        out[name] = flat[:, k].astype(np.int64) if name in ("EPISODE", "CAUSE", "TICKS") else flat[:, k].copy()
+    out.update(abi.split_scenario(flat[:, len(abi.SCENARIO_LOG_HEAD):]))
+    return out
 
 
 def respawn_summary(totals: dict, dt: float = 0.002) -> dict:

@@ -38,6 +38,7 @@ ABI_SYMBOLS = [
     "hb_plant_set_model_variation", "hb_plant_get_model_variation",
     "hb_plant_set_episode", "hb_plant_get_episode",
     "hb_plant_set_respawn", "hb_plant_respawn", "hb_plant_get_respawn",
+    "hb_plant_set_scenario", "hb_plant_get_scenario", "hb_plant_get_scenario_log",
 ]
 # include/hunter_lcm.h
 LCM_SYMBOLS = ["hb_lcm_fingerprint", "hb_lcm_encoded_size", "hb_lcm_field_count", "hb_lcm_encode", "hb_lcm_decode", "hb_lcm_frame", "hb_lcm_unframe",
@@ -400,6 +401,27 @@ class HunterSolver:
         if want_state:
             out["q_last"], out["v_last"] = q, v
         return out
+
+    # ---- scenario draw at respawn (hb_plant_set_scenario) -----------------------------------------------------------------------------
+    def plant_set_scenario(self, cfg: "abi.HbScenarioConfig" = None):
+        """cfg None: off; abi.make_scenario_config(...): every plant_respawn() draws terrain, friction, payload, link masses and a push
+        (the channels of cfg) for the instances it respawns.  Needs contact model 1 and plant_set_respawn."""
+        self._check(self.lib.hb_plant_set_scenario(self.ctx, None if cfg is None else C.byref(cfg)), "hb_plant_set_scenario")
+        self._scenario_log_capacity = 0 if cfg is None else int(cfg.log_capacity)
+
+    def plant_scenario(self):
+        """-> scen[B][HB_SC_N], the parameters every instance's current episode runs under (abi.split_scenario names them)."""
+        scen = np.zeros((self.B, abi.HB_SC_N))
+        self._check(self.lib.hb_plant_get_scenario(self.ctx, _p(scen)), "hb_plant_get_scenario")
+        return scen
+
+    def plant_scenario_log(self):
+        """-> dict(count[B] int32, log[B][log_capacity][HB_SC_LOG_W]): the finished episodes of every instance in order, each row
+        abi.SCENARIO_LOG_HEAD and then the HB_SC_N parameters it ran under; rows behind count are zero."""
+        cap = getattr(self, "_scenario_log_capacity", 0)
+        count, log = np.zeros(self.B, dtype=np.int32), np.zeros((self.B, cap, abi.HB_SC_LOG_W))
+        self._check(self.lib.hb_plant_get_scenario_log(self.ctx, _p(count), _p(log) if cap else None), "hb_plant_get_scenario_log")
+        return dict(count=count, log=log)
 
     # ---- sensors from the plant (hb_plant_sense) and the estimator on them ------------------------------------------------
     def plant_set_sensor_model(self, sensor_cfg: "abi.HbSensorConfig" = None, gyro_bias=None, accel_bias=None):

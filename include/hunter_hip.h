@@ -557,7 +557,8 @@ int32_t hb_plant_get_episode(hb_ctx* ctx, int32_t* irec, double* drec, double* t
  *  4. Plant: q, v;  anchor = the contact points at q, pinned 0, contact_last 1, lambda, vdot, tau_last 0 (what hb_plant_reset leaves).  Zeroed
  *     where the arrays exist: the contact model's impulses, outputs and status word (HB_CONTACT_FALLEN with it; the external wrench stays);
  *     the joint model's impulses, outputs and status; the actuator record (tau_first, tau_mean, the received command, the timestamp filter);
- *     the emergency-stop latch.  Terrain and model variation stay: they belong to the instance.
+ *     the emergency-stop latch.  Terrain and model variation stay: they belong to the instance (a scenario in
+ *     force, hb_plant_set_scenario below, has drawn them anew before this step).
  *  5. Episode: the record restarts from the new state (initial values above hb_plant_set_episode), its trace rows are zeroed, EPISODE_INDEX
  *     += 1.
  *  6. Estimator, if hb_estimator_reset has run: x_hat = (q[0:3], 0 0 0, the four contact points at q), P = 100 I (what hb_estimator_reset
@@ -609,6 +610,92 @@ int32_t hb_plant_respawn(hb_ctx* ctx);
 /* itot[batch][HB_RS_NI], dtot[batch][HB_RS_ND], q_last / v_last [batch][16] = the last spawned state; any may be NULL.  Synchronises like
  * hb_plant_get_episode.  HB_ERR_STATE without a respawn configuration in force. */
 int32_t hb_plant_get_respawn(hb_ctx* ctx, int32_t* itot, double* dtot, double* q_last, double* v_last);
+
+/* ---- scenario draw at respawn: terrain, friction, payload, link masses and a push per episode, on the device ---------------------------
+ * With a scenario in force, hb_plant_respawn draws a new scenario for every instance it respawns: a kernel of its own (k_plant_scenario)
+ * enqueued ahead of k_plant_respawn in the same call reads the same decision from the still unchanged episode record, and for a
+ * respawning instance, in this order, (a) appends the log row of the finished episode, (b) draws, (c) writes the instance's terrain
+ * record, DevModel record, push record and parameter row scen[HB_SC_N].  k_plant_respawn is unchanged: it places the robot on the plane it
+ * now finds.  An instance that stays costs the decision loads and an exit: NOT ONE BYTE of it is written.  Off by default; without a
+ * scenario every call enqueues exactly what it enqueues without this block.  Episode 0 (the state of hb_plant_reset) is never drawn: it runs
+ * on the terrain and the variation in force at the call.
+ *
+ * The draw.  Philox4x32-10, u_k = (word k + 0.5) 2^-32 as for the spawn state (above):
+ *       key = (seed low 32, seed high 32) of the SCENARIO's seed;  counter = (instance_offset + i, e, HB_SC_STREAM, block),
+ * instance_offset from the respawn configuration in force, e = EPISODE_INDEX + 1 the episode that starts.  Every operation below is an
+ * IEEE double operation of its own in the order written, brackets first, nothing fused; there is no trigonometry, logarithm or
+ * exponential in it.  Blocks are independent; a block whose channel is off is not generated.
+ *   block 0, HB_SC_SLOPE:   g_x = grade_max (2 u_0 - 1),  g_y = grade_max (2 u_1 - 1);   l = sqrt((g_x g_x + g_y g_y) + 1);
+ *                           n0 = ((-g_x) / l, (-g_y) / l, 1 / l);   d = (n0_x s_x + n0_y s_y) + n0_z ground_z,  (s_x, s_y) = q_spawn[0:2] of the
+ *                           respawn configuration: the plane pivots under the spawn point.  The stored record (T, d) is what
+ *                           hb_plant_set_terrain stores for plane = (n0, d), its own normalisation n = n0 / |n0| and the frame T included
+ *                           (one routine, csrc/hb_contact.hpp terrain_plane_record, called by both).  n_z >= 1 / sqrt(3) for grade_max <= 1.
+ *   block 1, HB_SC_MU:      mu_c = mu_lo + (mu_hi - mu_lo) u_c,  c = 0..3;  with mu_per_point = 0 all four points take c = 0's value.
+ *   block 2, HB_SC_PAYLOAD: m_p = payload_mass_max u_0;   r[a] = payload_center[a] + payload_half_extent[a] (2 u_{1+a} - 1);   I_p = 0.
+ *   blocks 3-5, HB_SC_MASS: body b uses word b % 4 of block 3 + b / 4:   s_b = 1 + mass_scale_range (2 u - 1)   (> 0 for a range < 1).
+ *   block 6, HB_SC_PUSH:    start = push_start_lo + int(u_0 (push_start_hi - push_start_lo + 1))  (<= push_start_hi for every word);
+ *                           F_x = push_force_max (2 u_1 - 1),  F_y = push_force_max (2 u_2 - 1).
+ * With HB_SC_PAYLOAD or HB_SC_MASS the instance's DevModel record is the composition of hb_plant_set_model_variation (above,
+ * csrc/hb_modelvar.hpp modelvar_compose) of the nominal model with s (1 for every body if HB_SC_MASS is off) and the payload (none if
+ * HB_SC_PAYLOAD is off), bit for bit what the host setter composes from the same numbers.
+ * A channel that is off leaves its part of the records bit for bit (HB_SC_SLOPE: T and d; HB_SC_MU: the four coefficients; both model
+ * channels off: the DevModel record) and its entries of scen are 0.  Before an instance's first draw scen is zero with PUSH_START = -1.
+ *
+ * scen[HB_SC_N]: GRADE[2] = g_x g_y, MUS[4], PAYLOAD_M, PAYLOAD_R[3], SCALE[HB_NBODY], PUSH_START, PUSH_F[2].
+ * Log: up to log_capacity rows of HB_SC_LOG_W doubles per instance, appended in order until full (count == log_capacity: later episodes
+ * are not logged): the finished episode's index (EPISODE_INDEX before the fold), its cause, TICKS, LAST_BASE[0] - START_POS[0],
+ * LAST_BASE[1] - START_POS[1], TILT_MAX of its record, then the HB_SC_N parameters it ran under (all zero, PUSH_START -1, for episode 0).
+ *
+ * Push.  While HB_SC_PUSH is in force the scenario owns the external wrench of contact model 1: hb_plant_set_scenario zeroes it and
+ * switches it on, hb_plant_set_external_wrench returns HB_ERR_STATE, and turning the scenario off clears the wrench and switches it off.
+ * Ahead of every plant kernel a kernel of its own (k_plant_push, one thread per instance) writes
+ *       wrench_i = (F_x, F_y, 0, 0, 0, 0)  if the instance has a push (start >= 0) and  start <= STEPS < start + push_ticks,  else 0,
+ * STEPS that of the instance's current episode record, so the first pushed step of an episode is its step number `start`.  The plant
+ * kernels do not change.  hb_plant_reset sets every push record to "none" (start = -1).
+ *
+ * State.  HB_ERR_STATE before hb_plant_reset, outside contact model 1 or without a respawn configuration in force; HB_ERR_ARG (the
+ * configuration in force is kept) for a violated range, a non-finite field or a nonzero `reserved`.  HB_SC_SLOPE or HB_SC_MU without a
+ * terrain in force turns the terrain on with the level record ((0, 0, 1, ground_z), cfg.mu, T = I: the step without a terrain, value for
+ * value); HB_SC_PAYLOAD or HB_SC_MASS without a variation turns the variation on with nominal copies.  While a scenario is in force
+ * hb_plant_get_terrain and hb_plant_get_model_variation synchronise and read the device records (the host copies are stale); turning the
+ * scenario off leaves terrain and variation in force as last drawn, and the host copies are refreshed from the device.
+ * hb_plant_set_terrain / hb_plant_set_model_variation with a scenario in force overwrite the records of every instance as always; the next
+ * draw overwrites them again; switching off (both arguments NULL) what the scenario draws returns HB_ERR_STATE.  Turning respawn or the episode off, or leaving model 1, turns the scenario off.  hb_plant_reset empties the
+ * log and sets the push records to "none"; terrain and model records stay as last drawn, scen too.  Every call with a configuration
+ * restarts scen, the push records and the log.
+ * Out of scope: a draw for episode 0, payload inertia or a payload on a link, non-planar terrain, a push with a moment or more than one
+ * push per episode, per-episode joint parameters, the instance-range / graph paths. */
+#define HB_SC_STREAM 0x53434E31u /* third counter word; differs from HB_RS_STREAM, so the spawn-state draws keep their bits */
+enum { HB_SC_SLOPE = 1, HB_SC_MU = 2, HB_SC_PAYLOAD = 4, HB_SC_MASS = 8, HB_SC_PUSH = 16 }; /* channels */
+enum {   /* scen */
+  HB_SC_GRADE = 0 /* [2] */, HB_SC_MUS = 2 /* [4] */, HB_SC_PAYLOAD_M = 6, HB_SC_PAYLOAD_R = 7 /* [3] */, HB_SC_SCALE = 10 /* [HB_NBODY] */,
+  HB_SC_PUSH_START = 21, HB_SC_PUSH_F = 22 /* [2] */, HB_SC_N = 24
+};
+#define HB_SC_LOG_W (6 + HB_SC_N) /* finished episode's index, cause, TICKS, dist_x, dist_y, TILT_MAX, then its HB_SC_N parameters */
+#define HB_SC_LOG_MAX 1024
+typedef struct hb_scenario_config {
+  uint64_t seed;
+  int32_t channels;           /* OR of HB_SC_* */
+  int32_t mu_per_point;       /* 0: one coefficient for the four points; 1: one each */
+  double grade_max;           /* [0, 1]: each of the two ground gradients uniform in [-grade_max, grade_max] */
+  double mu_lo, mu_hi;        /* 0 <= lo <= hi, finite */
+  double payload_mass_max;    /* kg, >= 0 */
+  double payload_center[3], payload_half_extent[3];  /* m, base frame; half extents >= 0 */
+  double mass_scale_range;    /* [0, 1): s_b uniform in [1 - range, 1 + range] */
+  double push_force_max;      /* N, >= 0: each horizontal component uniform in [-max, max] */
+  int32_t push_start_lo, push_start_hi;  /* 0 <= lo <= hi <= 1 << 20: first pushed step of the episode */
+  int32_t push_ticks;         /* >= 1 with HB_SC_PUSH */
+  int32_t log_capacity;       /* 0 .. HB_SC_LOG_MAX finished episodes kept per instance */
+  int32_t reserved[2];        /* 0 */
+} hb_scenario_config;
+/* cfg NULL: off. */
+int32_t hb_plant_set_scenario(hb_ctx* ctx, const hb_scenario_config* cfg);
+/* scen[batch][HB_SC_N]: the parameters every instance's current episode runs under.  Synchronises like hb_plant_get_episode.  HB_ERR_STATE
+ * without a scenario in force. */
+int32_t hb_plant_get_scenario(hb_ctx* ctx, double* scen);
+/* count[batch] = rows logged per instance, log[batch][log_capacity][HB_SC_LOG_W] (rows behind count are zero); either may be NULL.
+ * Synchronises.  HB_ERR_STATE without a scenario in force. */
+int32_t hb_plant_get_scenario_log(hb_ctx* ctx, int32_t* count, double* log);
 
 /* ---- sensors from the plant: what LeggedController::updateStateEstimation reads, computed on the device -----------
  * hb_plant_sense turns the plant's state into the sensor arrays of hb_estimator_update and leaves them on the device

@@ -8,6 +8,11 @@
                                                         level ground with mu 0.7, one pair per instance (hb_plant_set_model_variation)
     python tools/sweep_rollout.py --respawn 250 --ticks 2000  the friction sweep as repeated episodes of at most 250 ticks per instance (hb_plant_set_respawn:
                                                         a fallen robot is put back at the next MPC boundary), read from the respawn totals alone
+    python tools/sweep_rollout.py --randomize 2000 --robots 4096   a robustness sweep in one run(n) and one read-back: every respawn draws slope, friction,
+                                                        payload and a push on the device (hb_plant_set_scenario); survival rate and mean ticks
+                                                        binned by mu, grade and payload mass, from the scenario log alone.  --host-driven: the
+                                                        same sweep with the host calling the setters per respawn round and uploading a wrench
+                                                        per tick, for the wall time of both
     python tools/sweep_rollout.py --readback            the two sweeps once more with the per-tick read-back loop the findings of items 17 - 20
                                                         were made with, for the wall time per tick of both
 
@@ -22,7 +27,7 @@ import numpy as np
 
 sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
 from hunter_bipedal_control_amd import abi, ingest  # noqa: E402
-from hunter_bipedal_control_amd.rollout import ResidentLoop, episode_summary, payload_on_base, respawn_summary  # noqa: E402
+from hunter_bipedal_control_amd.rollout import ResidentLoop, episode_summary, payload_on_base, respawn_summary, scenario_table  # noqa: E402
 from hunter_bipedal_control_amd.solver import HunterSolver  # noqa: E402
 
 FRICTION = [0.7, 0.5, 0.4, 0.3, 0.2, 0.15, 0.1, 0.05]
@@ -61,6 +66,74 @@ def run_respawn(params, mu, ticks, max_ticks, joint_model=None):
         return tot, time.perf_counter() - t0
     finally:
         s.close()
+
+
+RANDOMIZE = dict(grade_max=0.15, mu_lo=0.05, mu_hi=0.8, payload_mass_max=3.0, payload_center=(0.0, 0.0, 0.15), payload_half_extent=(0.1, 0.05, 0.0),
+                 push_force_max=40.0, push_start_lo=50, push_start_hi=150, push_ticks=25)
+RANDOMIZE_RESPAWN = dict(hold_ticks=0, place=1, clearance=0.0, yaw_range=0.1, joint_pos_sigma=0.005, seed=1)
+
+
+def run_randomize(params, robots, ticks, max_ticks, joint_model=None, host_driven=False):
+    """Repeated episodes with a new scenario each -> (scenario log or None, respawn totals, wall seconds of the ticks).  host_driven: the
+    host draws (numpy, not the device's stream) and calls hb_plant_set_terrain / hb_plant_set_model_variation after every respawn round and
+    hb_plant_set_external_wrench before every tick."""
+    channels = abi.HB_SC_SLOPE | abi.HB_SC_MU | abi.HB_SC_PAYLOAD | abi.HB_SC_PUSH
+    log_capacity = min(abi.HB_SC_LOG_MAX, ticks // 8 + 1)
+    scenario = None if host_driven else dict(RANDOMIZE, channels=channels, seed=2, log_capacity=log_capacity)
+    B = robots
+    s = HunterSolver(params, batch=B, max_nodes=108)
+    try:
+        horizon = 100 * params["config"]["dt"]
+        loop = ResidentLoop(s, params, ["trot"] * B, np.tile([0.2, 0.0, 0.0, 0.0], (B, 1)), contact_config=dict(fall_height=0.3), joint_model=joint_model,
+                            static_schedule_until=ticks * 0.002 + horizon + 1.5, episode=dict(slip_speed=0.05),
+                            respawn=dict(RANDOMIZE_RESPAWN, max_ticks=max_ticks), scenario=scenario)
+        rng = np.random.default_rng(2)
+        s.sync()
+        t0 = time.perf_counter()
+        if not host_driven:
+            loop.run(ticks)
+            log = loop.scenario_log()
+        else:
+            R, push, start = RANDOMIZE, np.zeros((B, 6)), np.full(B, -1)
+            for tick in range(ticks):
+                steps = s.plant_episode()["STEPS"]
+                w = np.where(((start >= 0) & (start <= steps) & (steps < start + R["push_ticks"]))[:, None], push, 0.0)
+                s.plant_set_external_wrench(w)
+                loop.step()
+                if loop.tick % loop.mpc_every == 0:   # a respawn round has been enqueued: the host draws for everybody and uploads the batch
+                    g = R["grade_max"] * rng.uniform(-1.0, 1.0, (B, 2))
+                    n = np.concatenate([-g, np.ones((B, 1))], axis=1)
+                    n /= np.linalg.norm(n, axis=1)[:, None]
+                    s.plant_set_terrain(np.concatenate([n, np.zeros((B, 1))], axis=1), np.repeat(rng.uniform(R["mu_lo"], R["mu_hi"], (B, 1)), 4, axis=1))
+                    pl = np.zeros((B, abi.HB_PAYLOAD_SIZE))
+                    pl[:, 0] = R["payload_mass_max"] * rng.uniform(0.0, 1.0, B)
+                    pl[:, 1:4] = np.asarray(R["payload_center"]) + np.asarray(R["payload_half_extent"]) * rng.uniform(-1.0, 1.0, (B, 3))
+                    s.plant_set_model_variation(None, pl)
+                    push[:, 0:2] = R["push_force_max"] * rng.uniform(-1.0, 1.0, (B, 2))
+                    start = rng.integers(R["push_start_lo"], R["push_start_hi"] + 1, B)
+            log = None
+        tot = loop.respawn_totals()
+        return log, tot, time.perf_counter() - t0
+    finally:
+        s.close()
+
+
+def print_randomize(log, bins=4):
+    """Survival rate (episodes that ended by time-out) and mean ticks, binned by mu, |grade| and payload mass, from the log alone."""
+    t = scenario_table(log)
+    drawn = t["EPISODE"] > 0                       # (episode 0 ran on the terrain and the model of the start, not on a draw)
+    n = int(drawn.sum())
+    print(f"   {len(t['EPISODE'])} finished episodes logged, {n} of them on a drawn scenario")
+    survived, ticks = (t["CAUSE"] == abi.HB_RS_TIMEOUT)[drawn], t["TICKS"][drawn]
+    for name, x in (("mu", t["MUS"][drawn, 0]), ("|grade|", np.hypot(t["GRADE"][drawn, 0], t["GRADE"][drawn, 1])), ("payload kg", t["PAYLOAD_M"][drawn])):
+        if n == 0:
+            break
+        edges = np.linspace(x.min(), x.max(), bins + 1)
+        which = np.clip(np.searchsorted(edges, x, side="right") - 1, 0, bins - 1)
+        print(f"   {name:>12} " + " ".join(f"{'[%.3g, %.3g]' % (edges[b], edges[b + 1]):>16}" for b in range(bins)))
+        for label, val in (("episodes", lambda m: f"{int(m.sum())}"), ("survival", lambda m: f"{survived[m].mean():.3f}" if m.any() else "-"),
+                           ("mean ticks", lambda m: f"{ticks[m].mean():.1f}" if m.any() else "-")):
+            print(f"   {label:>12} " + " ".join(f"{val(which == b):>16}" for b in range(bins)))
 
 
 def run_record(params, mu, pitch, ticks, static=False, joint_model=None, payload=None):
@@ -124,10 +197,22 @@ def main():
                     help="payload mass 0 .. 15 kg x fore-aft offset -0.1 .. 0.1 m at 0.15 m above the base origin, one instance per pair")
     ap.add_argument("--joint-model", action="store_true", help="the joints of the reference's MuJoCo model instead of ideal joints")
     ap.add_argument("--respawn", type=int, metavar="N_TICKS", help="the friction sweep as repeated episodes of at most N_TICKS ticks, from the respawn totals")
+    ap.add_argument("--randomize", type=int, metavar="N_TICKS", help="N_TICKS ticks of repeated episodes with slope, friction, payload and a push drawn on the device per episode; one read-back")
+    ap.add_argument("--robots", type=int, default=64, help="batch of --randomize")
+    ap.add_argument("--max-ticks", type=int, default=400, help="time-out of an episode of --randomize")
+    ap.add_argument("--host-driven", action="store_true", help="--randomize with the host calling the setters per respawn round and uploading a wrench per tick")
     ap.add_argument("--readback", action="store_true", help="also time the per-tick read-back loop on the two sweeps")
     args = ap.parse_args()
     params = ingest.load_packaged()
     jm = {} if args.joint_model else None
+    if args.randomize:
+        log, tot, wall = run_randomize(params, args.robots, args.randomize, args.max_ticks, joint_model=jm, host_driven=args.host_driven)
+        print(f"-- randomised scenarios per episode, B = {args.robots}, {args.randomize} ticks, episodes of at most {args.max_ticks} ticks, "
+              f"{'host-driven' if args.host_driven else 'run() and one read-back'}: {wall:.3f} s, {1e3 * wall / args.randomize:.3f} ms per tick")
+        print(f"   episodes {int(tot['EPISODES'].sum())}: fallen {int(tot['N_FALLEN'].sum())}, non-finite {int(tot['N_NONFINITE'].sum())}, timed out {int(tot['N_TIMEOUT'].sum())}")
+        if log is not None:
+            print_randomize(log)
+        return
     if args.respawn:
         tot, wall = run_respawn(params, FRICTION, args.ticks, args.respawn, joint_model=jm)
         summ = respawn_summary(tot, dt=0.002)
