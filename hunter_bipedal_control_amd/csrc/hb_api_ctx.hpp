@@ -106,6 +106,12 @@ struct hb_ctx {
   TerrainBatch terrain{};
   std::vector<double> terrain_host;
   bool terrain_on = false;
+  // per-instance terrain profile of contact model 1 (hb_plant_set_terrain_profile): profile_on while one is in force (the step calls then
+  // launch the profile kernels, and terrain_on is false: one ground at a time); the arrays are allocated on first use, profile_host is the
+  // host image of the stored records ([B][Profile::stored]), profile_knots the knots as given ([B][HB_PROFILE_MAX_KNOTS][2], zero beyond K)
+  ProfileBatch profile{};
+  std::vector<double> profile_host, profile_knots;
+  bool profile_on = false;
   // per-instance model variation of contact model 1 (hb_plant_set_model_variation): modelvar_on while one is in force (the step calls then
   // launch the varied kernels); the records are allocated on first use, modelvar_host is their host image (what hb_plant_get_model_variation
   // reports).  Without a terrain the varied kernels read the level record of the configuration in force out of `terrain` (modelvar_level).

@@ -2,9 +2,11 @@
 #pragma once
 
 // ---- per-instance episode record (include/hunter_hip.h above hb_plant_set_episode) -------------------------------------------------
-// The plane the record measures heights from: the terrain records if a terrain is in force, else e_z . x = *d0 (ground_z in model 1, 0 in model 0).
+// The plane the record measures heights from: the terrain records if a terrain is in force, the records of the facet under each base origin
+// if a profile is (ProfileBatch::base, the Terrain layout), else e_z . x = *d0 (ground_z in model 1, 0 in model 0).
 static const double* episode_plane(const hb_ctx* ctx, double* d0) {
   *d0 = ctx->contact_cfg.mode == 1 ? ctx->contact_cfg.ground_z : 0.0;
+  if (ctx->contact_cfg.mode == 1 && ctx->profile_on) return ctx->profile.base;
   return ctx->contact_cfg.mode == 1 && ctx->terrain_on ? ctx->terrain.ter : nullptr;
 }
 
@@ -213,6 +215,7 @@ int32_t hb_plant_set_respawn(hb_ctx* ctx, const hb_respawn_config* cfg, const do
     ctx->err = std::string("hb_plant_set_respawn: ") + why + " (the configuration in force is kept)";
     return HB_ERR_ARG;
   }
+  HB_FAIL_IF(cfg && ctx->profile_on, HB_ERR_STATE, "hb_plant_set_respawn: a terrain profile is in force (hb_plant_set_terrain_profile): no respawn on a profile, turn it off first");
   HB_FAIL_IF(cfg && !q_spawn, HB_ERR_ARG, "hb_plant_set_respawn: q_spawn is required with a configuration (the configuration in force is kept)");
   HB_ENTER_DEVICE();
   HB_HIP(hipStreamSynchronize(ctx->s_wbc));  // (a respawn in flight still runs under the configuration it was launched with)
@@ -282,6 +285,7 @@ int32_t hb_plant_get_respawn(hb_ctx* ctx, int32_t* itot, double* dtot, double* q
 
 // ---- scenario draw at respawn (include/hunter_hip.h above hb_plant_set_scenario) --------------------------------------------------------
 static int32_t modelvar_level(hb_ctx* ctx);   // (below, with the model variation)
+static int32_t profile_locate(hb_ctx* ctx, const double* q, hipStream_t s);   // (below, with the terrain profile)
 static int32_t contact_ready(hb_ctx* ctx, const char* who);
 
 // the level record of the configuration in force, for every instance
@@ -335,6 +339,7 @@ int32_t hb_plant_set_scenario(hb_ctx* ctx, const hb_scenario_config* cfg) {
   if (!cfg && !ctx->scenario_on) return HB_OK;
   HB_TRY(contact_ready(ctx, "hb_plant_set_scenario"));
   HB_FAIL_IF(cfg && !ctx->respawn_on, HB_ERR_STATE, "hb_plant_set_scenario: no respawn configuration in force (hb_plant_set_respawn): the scenario is drawn at respawn");
+  HB_FAIL_IF(cfg && ctx->profile_on && (cfg->channels & (HB_SC_SLOPE | HB_SC_MU)), HB_ERR_STATE, "hb_plant_set_scenario: a terrain profile is in force (hb_plant_set_terrain_profile): no slope or friction draw on a profile, turn it off first");
   if (const char* why = cfg ? scenario_config_refusal(*cfg) : nullptr) {
     ctx->err = std::string("hb_plant_set_scenario: ") + why + " (the configuration in force is kept)";
     return HB_ERR_ARG;
@@ -430,6 +435,7 @@ int32_t hb_plant_reset(hb_ctx* ctx, const double* q0, const double* v0, double b
   if (ctx->contact.wrench) HB_TRY(contact_clear(ctx, ctx->s_wbc));
   if (ctx->joints.status) HB_TRY(joints_clear(ctx, ctx->s_wbc));
   if (ctx->act.wire_full) HB_TRY(actuator_clear(ctx, ctx->s_wbc));
+  if (ctx->profile_on) HB_TRY(profile_locate(ctx, q0, ctx->s_wbc));   // the facets under the reset state
   if (ctx->episode_on) HB_TRY(episode_start(ctx, ctx->s_wbc));   // the record restarts from the reset state
   if (ctx->respawn_on) HB_TRY(respawn_totals_start(ctx, ctx->s_wbc));   // ... and so do the totals of the respawn
   HB_HIP(hipStreamSynchronize(ctx->s_wbc));
@@ -450,6 +456,19 @@ int32_t hb_plant_step(hb_ctx* ctx, const double* tau, const int32_t* contact, do
   HB_TRY(push(ctx, contact, p, p.contact, whole(ctx), &s));
   const double* dtau = tau ? p.tau : ctx->jc_out + 5 * B * HB_NJ;
   // the resident observation feeds the next hb_mpc_solve(NULL) / hb_refgen_update(NULL) on the MPC stream
+  const DevModel* mvar = ctx->modelvar_on ? ctx->modelvar.mdl : nullptr;   // (the profile forms take the variation by pointer)
+  if (ctx->contact_cfg.mode == 1 && ctx->profile_on && ctx->joints_on)
+    return plant_write(ctx, s, to_resident, dt, [&] {
+      hipLaunchKernelGGL(k_plant_profile_joints, dim3(ctx->B), dim3(64), 0, s, p, ctx->contact, ctx->joints, ctx->profile, ctx->contact_cfg,
+                         ctx->joint_model, ctx->dmodel, mvar, dtau, contact ? p.contact : nullptr, ctx->w.mode, dt, substeps,
+                         to_resident ? ctx->w.rbd : nullptr, to_resident ? ctx->b.x0 : nullptr, to_resident ? ctx->w.t_now : nullptr);
+    });
+  if (ctx->contact_cfg.mode == 1 && ctx->profile_on)
+    return plant_write(ctx, s, to_resident, dt, [&] {
+      hipLaunchKernelGGL(k_plant_profile, dim3(ctx->B), dim3(64), 0, s, p, ctx->contact, ctx->profile, ctx->contact_cfg, ctx->dmodel, mvar, dtau,
+                         contact ? p.contact : nullptr, ctx->w.mode, dt, substeps, to_resident ? ctx->w.rbd : nullptr,
+                         to_resident ? ctx->b.x0 : nullptr, to_resident ? ctx->w.t_now : nullptr);
+    });
   if (ctx->contact_cfg.mode == 1 && ctx->modelvar_on && ctx->joints_on)
     return plant_write(ctx, s, to_resident, dt, [&] {
       hipLaunchKernelGGL(k_plant_varied_joints, dim3(ctx->B), dim3(64), 0, s, p, ctx->contact, ctx->joints, ctx->terrain.ter, ctx->contact_cfg,
@@ -513,6 +532,17 @@ static int32_t plant_launch_hybrid(hb_ctx* ctx, const double* const cmd[5], cons
   double* rr = to_resident ? ctx->w.rbd : nullptr;
   double* rx = to_resident ? ctx->b.x0 : nullptr;
   double* rt = to_resident ? ctx->w.t_now : nullptr;
+  const DevModel* mvar = ctx->modelvar_on ? ctx->modelvar.mdl : nullptr;   // (the profile forms take the variation by pointer)
+  if (ctx->contact_cfg.mode == 1 && ctx->profile_on && ctx->joints_on)
+    return plant_write(ctx, s, to_resident, dt, [&] {
+      hipLaunchKernelGGL(k_plant_profile_joints_hybrid, dim3(ctx->B), dim3(64), 0, s, p, ctx->contact, ctx->joints, ctx->profile, ctx->act, c,
+                         ctx->contact_cfg, ctx->joint_model, ctx->dmodel, mvar, dcontact, ctx->w.mode, dt, substeps, rr, rx, rt);
+    });
+  if (ctx->contact_cfg.mode == 1 && ctx->profile_on)
+    return plant_write(ctx, s, to_resident, dt, [&] {
+      hipLaunchKernelGGL(k_plant_profile_hybrid, dim3(ctx->B), dim3(64), 0, s, p, ctx->contact, ctx->profile, ctx->act, c, ctx->contact_cfg,
+                         ctx->dmodel, mvar, dcontact, ctx->w.mode, dt, substeps, rr, rx, rt);
+    });
   if (ctx->contact_cfg.mode == 1 && ctx->modelvar_on && ctx->joints_on)
     return plant_write(ctx, s, to_resident, dt, [&] {
       hipLaunchKernelGGL(k_plant_varied_joints_hybrid, dim3(ctx->B), dim3(64), 0, s, p, ctx->contact, ctx->joints, ctx->terrain.ter, ctx->act, c,
@@ -632,6 +662,7 @@ int32_t hb_plant_set_contact_model(hb_ctx* ctx, const hb_contact_config* cfg) {
   if (!ground) HB_TRY(scenario_off(ctx));   // the scenario belongs to contact model 1 (and gives the wrench back)
   ctx->contact_cfg = ground ? *cfg : hb_contact_config{};
   if (!ground) ctx->terrain_on = false;   // the terrain belongs to contact model 1
+  if (!ground) ctx->profile_on = false;   // ... and so does the terrain profile
   if (!ground) ctx->modelvar_on = false;  // ... and so does the model variation
   HB_TRY(modelvar_level(ctx));            // (the level record follows the configuration)
   if (!ground && ctx->joints_on) {   // the joint model belongs to contact model 1
@@ -762,6 +793,7 @@ int32_t hb_plant_set_terrain(hb_ctx* ctx, const double* plane, const double* mu)
     ctx->terrain_host = std::move(rec);
   }
   ctx->terrain_on = plane || mu;
+  ctx->profile_on = false;   // one ground at a time: the call replaces a terrain profile
   HB_TRY(modelvar_level(ctx));
   // the warm start is expressed in the frame of before
   HB_HIP(hipMemsetAsync(c.imp, 0, field_count(ctx, c, c.imp) * 8, ctx->s_wbc));
@@ -784,6 +816,93 @@ int32_t hb_plant_get_terrain(hb_ctx* ctx, double* plane, double* mu, double* fra
     if (plane) { for (int a = 0; a < 3; ++a) plane[4 * i + a] = r[Terrain::T + 3 * a + 2]; plane[4 * i + 3] = r[Terrain::d]; }
     if (mu) std::memcpy(mu + 4 * i, r + Terrain::mu, 4 * sizeof(double));
     if (frame) std::memcpy(frame + 9 * i, r + Terrain::T, 9 * sizeof(double));
+  }
+  return HB_OK;
+}
+
+// ---- per-instance terrain profile of contact model 1 (include/hunter_hip.h above hb_plant_set_terrain_profile) ------------------------
+// (the stored record of an instance, validation included, is hb_contact.hpp profile_record)
+// seg and base of every instance from the host state q[B][16]: the segment under the four contact points and the base origin, and the Terrain
+// record of the facet under the base.  On s, behind its earlier work; the caller synchronises.
+static int32_t profile_locate(hb_ctx* ctx, const double* q, hipStream_t s) {
+  const size_t B = ctx->B;
+  std::vector<int> seg(B * (HB_NC + 1));
+  std::vector<double> base(B * Terrain::size);
+  for (size_t i = 0; i < B; ++i) {
+    const double* r = ctx->profile_host.data() + i * Profile::stored;
+    double feet[12];
+    plant_feet(ctx->hmodel, q + 16 * i, feet);
+    for (int c = 0; c < HB_NC + 1; ++c) seg[(HB_NC + 1) * i + c] = profile_segment(r, c < HB_NC ? feet + 3 * c : q + 16 * i);
+    double* b = base.data() + Terrain::size * i;
+    std::memcpy(b, r + Profile::head, Terrain::size * sizeof(double));
+    std::memcpy(b, r + Profile::seg + Profile::rec * seg[(HB_NC + 1) * i + HB_NC], Profile::rec * sizeof(double));
+  }
+  HB_HIP(hipStreamSynchronize(s));
+  ProfileBatch& t = ctx->profile;
+  HB_TRY(push(ctx, seg.data(), t, t.seg, whole(ctx)));
+  return push(ctx, base.data(), t, t.base, whole(ctx));
+}
+
+int32_t hb_plant_set_terrain_profile(hb_ctx* ctx, const int32_t* n_knots, const double* dir, const double* knots, const double* mu) {
+  HB_ENTER_ARGS(false);
+  HB_TRY(contact_ready(ctx, "hb_plant_set_terrain_profile"));
+  const bool on = n_knots || dir || knots;
+  HB_FAIL_IF(on && !(n_knots && dir && knots), HB_ERR_ARG, "hb_plant_set_terrain_profile: give n_knots, dir and knots, or none of them to switch the profile off (the profile in force is kept)");
+  HB_FAIL_IF(!on && mu, HB_ERR_ARG, "hb_plant_set_terrain_profile: friction coefficients without a profile (the profile in force is kept)");
+  HB_FAIL_IF(on && ctx->respawn_on, HB_ERR_STATE, "hb_plant_set_terrain_profile: a respawn configuration is in force (hb_plant_set_respawn): no respawn on a profile, turn it off first");
+  HB_FAIL_IF(on && ctx->scenario_on && (ctx->scenario_cfg.channels & (HB_SC_SLOPE | HB_SC_MU)), HB_ERR_STATE, "hb_plant_set_terrain_profile: the scenario in force draws the terrain (hb_plant_set_scenario): turn it off first");
+  const size_t B = ctx->B;
+  std::vector<double> rec(on ? B * Profile::stored : 0), kn(on ? B * HB_PROFILE_MAX_KNOTS * 2 : 0);
+  for (size_t i = 0; i < B && on; ++i) {
+    const double* k = knots + i * HB_PROFILE_MAX_KNOTS * 2;
+    if (const char* why = profile_record(n_knots[i], dir + 2 * i, k, mu ? mu + 4 * i : nullptr, ctx->contact_cfg.mu, rec.data() + i * Profile::stored)) {
+      ctx->err = "hb_plant_set_terrain_profile: instance " + std::to_string(i) + " has " + why + " (the profile in force is kept)";
+      return HB_ERR_ARG;
+    }
+    std::memcpy(kn.data() + i * HB_PROFILE_MAX_KNOTS * 2, k, size_t(n_knots[i]) * 2 * sizeof(double));
+  }
+  HB_ENTER_DEVICE();
+  HB_HIP(hipStreamSynchronize(ctx->s_wbc));  // (a step in flight still runs on the ground it was launched with)
+  ContactBatch& c = ctx->contact;
+  if (on) {
+    ProfileBatch& t = ctx->profile;
+    if (!t.base) {  // (base: the last array of the description, so an allocation that failed half way is repeated)
+      HB_HIP(alloc_fields(ctx, t));
+      t.B = ctx->B;
+    }
+    HB_TRY(push(ctx, rec.data(), t, t.prof, whole(ctx)));
+    ctx->profile_host = std::move(rec);
+    ctx->profile_knots = std::move(kn);
+    std::vector<double> q(B * 16);
+    HB_TRY(pull(ctx, q.data(), ctx->plant, ctx->plant.q, whole(ctx)));
+    HB_TRY(profile_locate(ctx, q.data(), ctx->s_wbc));
+    ctx->terrain_on = false;   // one ground at a time: the profile replaces a terrain
+  }
+  ctx->profile_on = on;
+  HB_TRY(modelvar_level(ctx));
+  // the warm start is expressed in the frames of before
+  HB_HIP(hipMemsetAsync(c.imp, 0, field_count(ctx, c, c.imp) * 8, ctx->s_wbc));
+  HB_HIP(hipStreamSynchronize(ctx->s_wbc));
+  return HB_OK;
+}
+
+int32_t hb_plant_get_terrain_profile(hb_ctx* ctx, int32_t* n_knots, double* dir, double* knots, double* mu, double* records, int32_t* segment) {
+  HB_ENTER_ARGS(false);
+  HB_TRY(contact_ready(ctx, "hb_plant_get_terrain_profile"));
+  HB_FAIL_IF(!ctx->profile_on, HB_ERR_STATE, "hb_plant_get_terrain_profile: no terrain profile in force (hb_plant_set_terrain_profile)");
+  if (segment) {
+    HB_ENTER_DEVICE();
+    HB_HIP(hipStreamSynchronize(ctx->s_wbc));
+    HB_TRY(pull(ctx, segment, ctx->profile, ctx->profile.seg, whole(ctx)));
+  }
+  constexpr size_t nrec = size_t(Profile::rec) * (HB_PROFILE_MAX_KNOTS - 1);
+  for (size_t i = 0; i < size_t(ctx->B); ++i) {
+    const double* r = ctx->profile_host.data() + i * Profile::stored;
+    if (n_knots) n_knots[i] = int32_t(r[Profile::nseg]) + 1;
+    if (dir) std::memcpy(dir + 2 * i, r + Profile::dir, 2 * sizeof(double));
+    if (knots) std::memcpy(knots + i * HB_PROFILE_MAX_KNOTS * 2, ctx->profile_knots.data() + i * HB_PROFILE_MAX_KNOTS * 2, HB_PROFILE_MAX_KNOTS * 2 * sizeof(double));
+    if (mu) std::memcpy(mu + 4 * i, r + Profile::head + Terrain::mu, 4 * sizeof(double));
+    if (records) std::memcpy(records + i * nrec, r + Profile::seg, nrec * sizeof(double));
   }
   return HB_OK;
 }

@@ -9,6 +9,8 @@
 // g_r += W[r][j] dp_j.  No LDS traffic and no barrier inside a sweep.  The host build (one emulated lane) runs the same update
 // routines (pgs_normal / pgs_tangent) over arrays.
 #pragma once
+#include <cmath>
+#include <cstring>
 #include "../../include/hunter_hip.h"
 #include "hb_plant.hpp"
 
@@ -151,6 +153,139 @@ HB_HD void point_mu(const double* ter, double mu, double* mup) {
   }
 }
 
+// ---- per-instance terrain profile (hb_plant_set_terrain_profile): piecewise-planar ground, a facet per contact point and substep ---------
+// The record of an instance.  [0, stored) is what the host stores per instance and the profile kernels stage once per step in LDS behind the
+// form's own arrays; the rest is working storage of the step.  head: a Terrain record — T, d of the facet under the base origin at q+
+// (written by the outputs) and mu of the four points; dir: a; nseg: K - 1 as a double; brk[k] = s_k (k = 1 .. nseg - 1 are scanned);
+// seg[j] = (T_j row-major, d_j), the first ten entries of the Terrain record of the plane; act[c]: the record of the segment under point c
+// in this substep; sel: the segment under the four points and the base origin at q+ (as doubles).
+struct Profile {
+  static constexpr int rec = 10;
+  static constexpr int head = 0, dir = Terrain::size, nseg = dir + 2, brk = nseg + 1, seg = brk + HB_PROFILE_MAX_KNOTS,
+                       stored = seg + rec * (HB_PROFILE_MAX_KNOTS - 1), act = stored, sel = act + rec * HB_NC, size = sel + HB_NC + 1;
+};
+constexpr int PRO_LDS = Profile::size;
+// What a profile step leaves behind per instance besides ContactOut: seg[5] and the Terrain record of the facet under the base (base[14]:
+// what k_plant_episode measures height and tilt against); pro: the staged record (LDS).
+struct ProfileIo {
+  double* pro;
+  int* seg;
+  double* base;
+};
+// Host: the stored record r[Profile::stored] of one instance from its profile (K knots (s, z), direction, mu[4] or null for cfg_mu), or the
+// reason it is refused.  The segment records come from terrain_plane_record, the routine behind hb_plant_set_terrain: the plane handed to
+// it is the unit normal and d of the segment.
+inline const char* profile_record(int K, const double* dir, const double* knots, const double* mu, double cfg_mu, double* r) {
+  if (K < 2 || K > HB_PROFILE_MAX_KNOTS) return "a number of knots outside 2 .. HB_PROFILE_MAX_KNOTS";
+  if (!(std::isfinite(dir[0]) && std::isfinite(dir[1]))) return "a non-finite direction";
+  const double len = std::sqrt(dir[0] * dir[0] + dir[1] * dir[1]);
+  if (!(len > 0.0) || !std::isfinite(len)) return "a direction of length zero";
+  const double a[2] = {dir[0] / len, dir[1] / len};
+  for (int k = 0; k < 2 * K; ++k)
+    if (!std::isfinite(knots[k])) return "a non-finite knot";
+  for (int k = 0; k < Profile::stored; ++k) r[k] = 0.0;
+  r[Profile::dir] = a[0];
+  r[Profile::dir + 1] = a[1];
+  r[Profile::nseg] = double(K - 1);
+  for (int k = 0; k < K; ++k) r[Profile::brk + k] = knots[2 * k];
+  for (int j = 0; j + 1 < K; ++j) {
+    const double ds = knots[2 * j + 2] - knots[2 * j];
+    if (!(ds > 0.0)) return "knots whose s is not strictly increasing";
+    const double m = (knots[2 * j + 3] - knots[2 * j + 1]) / ds;
+    // (sqrt(3) to rounding: a riser given by its height and width)
+    if (!(std::isfinite(m) && m * m <= 3.0 * (1.0 + 1e-12))) return "a segment steeper than sqrt(3) (n_z < 0.5)";
+    const double w = std::sqrt(1.0 + m * m);
+    double pl[4] = {0.0 - m * a[0] / w, 0.0 - m * a[1] / w, 1.0 / w, 0.0};   // (0 - : no negative zero on level ground)
+    // (normalised until its length rounds to 1, so that hb_plant_set_terrain, which divides by the length once more, stores the same bits)
+    for (int it = 0; it < 4 && terrain_normal_length(pl) != 1.0; ++it) {
+      const double l = terrain_normal_length(pl);
+      for (int x = 0; x < 3; ++x) pl[x] /= l;
+    }
+    pl[3] = pl[0] * (a[0] * knots[2 * j]) + pl[1] * (a[1] * knots[2 * j]) + pl[2] * knots[2 * j + 1];
+    double full[Terrain::size];
+    terrain_plane_record(pl, terrain_normal_length(pl), full);
+    std::memcpy(r + Profile::seg + Profile::rec * j, full, Profile::rec * sizeof(double));
+  }
+  for (int c = 0; c < HB_NC; ++c) {
+    const double m = mu ? mu[c] : cfg_mu;
+    if (!(std::isfinite(m) && m >= 0.0)) return "a friction coefficient that is negative or not finite";
+    r[Profile::head + Terrain::mu + c] = m;
+  }
+  std::memcpy(r + Profile::head, r + Profile::seg, Profile::rec * sizeof(double));   // (until a state is located: segment 0)
+  return nullptr;
+}
+
+// The segment under the world point x[3]: the last j with s_j <= a . x, the end segments open-ended.  A scan over the breakpoints.
+HB_HD int profile_segment(const double* pro, const double* x) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  const double s = pro[Profile::dir] * x[0] + pro[Profile::dir + 1] * x[1];
+  const int nseg = int(pro[Profile::nseg]);
+  int j = 0;
+  for (int k = 1; k < nseg; ++k) j = s >= pro[Profile::brk + k] ? k : j;
+  return j;
+}
+// Point c copies the record of the segment under feet[3 c ..] into its slot of act, one lane per point.
+template <class Ctx>
+HB_HD void profile_select(const Ctx& cx, double* pro, const double* feet) {
+  for (int c = cx.lane; c < HB_NC; c += cx.nlanes) {
+    const double* src = pro + Profile::seg + Profile::rec * profile_segment(pro, feet + 3 * c);
+    double* dst = pro + Profile::act + Profile::rec * c;
+    for (int k = 0; k < Profile::rec; ++k) dst[k] = src[k];
+  }
+  cx.sync();
+}
+// terrain_rotate with the frame of each point: Jc <- blockdiag(T_c') Jc, the contact columns of X take their point's frame, block (c, c') of
+// A <- T_c' A_cc' T_c' (block rows, then block columns), feet_c <- T_c' feet_c.  act: the four active records.
+template <int XS, class Ctx>
+HB_HD void profile_rotate(const Ctx& cx, const double* act, double* Jc, double* X, double* A, double* feet) {
+  for (int e = cx.lane; e < 64; e += cx.nlanes) {
+    const int c = e >> 4, k = e & 15;
+    const double* T = act + Profile::rec * c;
+    double* r = Jc + 48 * c + k;
+    terrain_to_frame(T, r[0], r[16], r[32]);
+    double* x = X + k * XS + 1 + 3 * c;
+    terrain_to_frame(T, x[0], x[1], x[2]);
+  }
+  for (int e = cx.lane; e < 48; e += cx.nlanes) {
+    const int c = e / 12, j = e - 12 * c;
+    double* a = A + 36 * c + j;
+    terrain_to_frame(act + Profile::rec * c, a[0], a[12], a[24]);
+  }
+  for (int c = cx.lane; c < HB_NC; c += cx.nlanes) terrain_to_frame(act + Profile::rec * c, feet[3 * c], feet[3 * c + 1], feet[3 * c + 2]);
+  cx.sync();
+  for (int e = cx.lane; e < 48; e += cx.nlanes) {
+    double* a = A + 3 * e;   // row e / 4, block column e % 4
+    terrain_to_frame(act + Profile::rec * (e & 3), a[0], a[1], a[2]);
+  }
+  cx.sync();
+}
+// d of the facet the normal row r = 3 c + 2 measures its gap from (TERRAIN 2), else the caller's
+template <int TERRAIN>
+HB_HD double row_ground(const double* ter, int r, double ground_z) {
+  if constexpr (TERRAIN == 2) return ter[Profile::act + Profile::rec * (r / 3) + Terrain::d];
+  else return ground_z;
+}
+// The outputs of a profile step at q+ (feet[12] world, q[16]): the segment under the four points and the base origin is selected again, the
+// points' records go to act (gap_c), the base's to head (the fall test, ProfileIo::base).  One lane per point and one for the base.
+template <class Ctx>
+HB_HD void profile_outputs_select(const Ctx& cx, double* pro, const double* feet, const double* q) {
+  for (int c = cx.lane; c < HB_NC + 1; c += cx.nlanes) {
+    const int j = profile_segment(pro, c < HB_NC ? feet + 3 * c : q);
+    const double* src = pro + Profile::seg + Profile::rec * j;
+    double* dst = c < HB_NC ? pro + Profile::act + Profile::rec * c : pro + Profile::head;
+    for (int k = 0; k < Profile::rec; ++k) dst[k] = src[k];
+    pro[Profile::sel + c] = double(j);
+  }
+  cx.sync();
+}
+template <class Ctx>
+HB_HD void profile_publish(const Ctx& cx, const ProfileIo& io) {
+  for (int c = cx.lane; c < HB_NC + 1; c += cx.nlanes) io.seg[c] = int(io.pro[Profile::sel + c]);
+  for (int k = cx.lane; k < Terrain::size; k += cx.nlanes) io.base[k] = io.pro[Profile::head + k];
+}
+
 // What a step leaves behind per instance (global memory; hb_plant_get_contact).
 struct ContactOut {
   double *gap, *pvel, *res;
@@ -159,8 +294,9 @@ struct ContactOut {
 
 // One substep of length h.  q[16], v[16] in / out (LDS); imp[12] (LDS behind `lds`) in / out; wrench[6] = world force and world moment at
 // the base origin, or null; all_on[4] = {1, 1, 1, 1} in memory every lane can read.  TERRAIN: ter = the instance's Terrain record (LDS); W, c,
-// the impulses and the gap are those of the plane's frame, and K.mu / K.ground_z are not read.
-template <bool TERRAIN = false, class Ctx>
+// the impulses and the gap are those of the plane's frame, and K.mu / K.ground_z are not read.  TERRAIN 2: ter = the instance's staged
+// Profile record (LDS, writable: ProfileIo::pro); frame and offset are those of each point's facet, selected here from the substep's start.
+template <int TERRAIN = 0, class Ctx>
 HB_HD void contact_substep(const Ctx& cx, const DevModel& Mdl, double* q, double* v, const double* tau, const double* wrench, const int* all_on,
                            const hb_contact_config& K, double eps, double h, double* lds, double* vdot_out, const double* ter = nullptr) {
   double* Jc = lds + PlantLds::Jc;
@@ -182,7 +318,11 @@ HB_HD void contact_substep(const Ctx& cx, const DevModel& Mdl, double* q, double
   // the front half of the pinned stub's substep with every point on (its first barrier publishes wgen)
   plant_substep<1>(cx, Mdl, q, v, tau, all_on, nullptr, 0.0, 0.0, h, lds, nullptr, nullptr, wrench ? wgen : nullptr);
   double ground_z;
-  if constexpr (TERRAIN) {
+  if constexpr (TERRAIN == 2) {
+    profile_select(cx, const_cast<double*>(ter), feet);
+    profile_rotate<PlantLds::xs>(cx, ter + Profile::act, Jc, X, A, feet);
+    ground_z = row_ground<2>(ter, cx.lane < 12 ? cx.lane : 0, 0.0);   // (the lane's own row)
+  } else if constexpr (TERRAIN) {
     terrain_rotate<PlantLds::xs>(cx, ter + Terrain::T, Jc, X, A, feet);
     ground_z = ter[Terrain::d];
   } else {
@@ -192,7 +332,7 @@ HB_HD void contact_substep(const Ctx& cx, const DevModel& Mdl, double* q, double
   for (int i = 0; i < 12; ++i) tr += A[i * 13];
   const double reg = eps * tr, mu = K.mu;
   double mup[HB_NC];
-  point_mu<TERRAIN>(ter, mu, mup);
+  point_mu<(TERRAIN != 0)>(ter, mu, mup);
 #if defined(__HIP_DEVICE_COMPILE__)
   {
     const int r = cx.lane < 12 ? cx.lane : 0;   // (lanes 12.. shadow lane 0: nothing reads them)
@@ -240,7 +380,7 @@ HB_HD void contact_substep(const Ctx& cx, const DevModel& Mdl, double* q, double
       double s = 0.0;
       for (int k = 0; k < 16; ++k) s += Jc[r * 16 + k] * (v[k] + h * X[k * 13]);
       if (r % 3 == 2) {
-        const double phi = feet[r] - ground_z;
+        const double phi = feet[r] - row_ground<TERRAIN>(ter, r, ground_z);
         s += (fmax(phi, 0.0) + K.erp * fmin(phi, 0.0)) / h;
       }
       for (int j = 0; j < 12; ++j) s += W[r * 12 + j] * imp[j];
@@ -283,11 +423,13 @@ HB_HD void contact_substep(const Ctx& cx, const DevModel& Mdl, double* q, double
 // One plant tick of one instance in contact model 1: `substeps` substeps of dt / substeps, then the outputs of the step.  State (q, v,
 // impulses, status) lives in global memory and is staged in LDS behind `lds` (CONTACT_LDS_TOTAL doubles).
 // TERRAIN: ter = the instance's Terrain record (LDS); lambda is T p / h, the point velocities are brought back to the world, gaps and the
-// fall test are measured along n.
-template <bool HYBRID = false, bool TERRAIN = false, class Ctx>
+// fall test are measured along n.  TERRAIN 2: pio = the instance's profile record and outputs, ter = pio->pro; lambda and the point
+// velocities come back through the frames of the last substep, gaps and the fall test are measured over the facets selected at q+.
+template <bool HYBRID = false, int TERRAIN = 0, class Ctx>
 HB_HD void contact_step(const Ctx& cx, const DevModel& Mdl, double* q_g, double* v_g, double* imp_g, const double* tau, const double* wrench,
                         const int* all_on, const hb_contact_config& K, double eps, double dt, int substeps, double* lds, double* lambda_out,
-                        double* vdot_out, const ContactOut& out, const HybridActuator* actuator = nullptr, const double* ter = nullptr) {
+                        double* vdot_out, const ContactOut& out, const HybridActuator* actuator = nullptr, const double* ter = nullptr,
+                        const ProfileIo* pio = nullptr) {
   double* q = lds + ContactLds::q;
   double* v = lds + ContactLds::v;
   double* imp = lds + ContactLds::imp;
@@ -313,7 +455,9 @@ HB_HD void contact_step(const Ctx& cx, const DevModel& Mdl, double* q_g, double*
   for (int i = cx.lane; i < 16; i += cx.nlanes) { q_g[i] = q[i]; v_g[i] = v[i]; }
   for (int i = cx.lane; i < 12; i += cx.nlanes) {
     imp_g[i] = imp[i];
-    if constexpr (TERRAIN) {
+    if constexpr (TERRAIN == 2) {
+      contact_outputs_terrain(ter + Profile::act + Profile::rec * (i / 3), i, Jc, v, imp, h, lambda_out, out.pvel);
+    } else if constexpr (TERRAIN) {
       contact_outputs_terrain(ter, i, Jc, v, imp, h, lambda_out, out.pvel);
     } else {
       lambda_out[i] = imp[i] / h;
@@ -323,11 +467,14 @@ HB_HD void contact_step(const Ctx& cx, const DevModel& Mdl, double* q_g, double*
     }
   }
   cx.sync();
+  if constexpr (TERRAIN == 2) profile_outputs_select(cx, pio->pro, feet, q);
   for (int c = cx.lane; c < HB_NC; c += cx.nlanes) {
-    if constexpr (TERRAIN) out.gap[c] = terrain_height(ter, feet + 3 * c);
+    if constexpr (TERRAIN == 2) out.gap[c] = terrain_height(ter + Profile::act + Profile::rec * c, feet + 3 * c);
+    else if constexpr (TERRAIN) out.gap[c] = terrain_height(ter, feet + 3 * c);
     else out.gap[c] = feet[3 * c + 2] - K.ground_z;
     out.touching[c] = imp[3 * c + 2] > 0.0 ? 1 : 0;
   }
+  if constexpr (TERRAIN == 2) profile_publish(cx, *pio);
   if (cx.lane == 0) {
     const double res = lds[ContactLds::res];
     bool finite = true;
@@ -335,7 +482,7 @@ HB_HD void contact_step(const Ctx& cx, const DevModel& Mdl, double* q_g, double*
     int st = out.status[0] & HB_CONTACT_FALLEN;   // (latched until hb_plant_reset)
     if (!finite) st |= HB_CONTACT_NONFINITE;
     double height;
-    if constexpr (TERRAIN) height = terrain_height(ter, q);
+    if constexpr (TERRAIN) height = terrain_height(ter, q);   // (TERRAIN 2: the head of the record is the facet under the base)
     else height = q[2] - K.ground_z;
     if (K.fall_height > 0.0 && height < K.fall_height) st |= HB_CONTACT_FALLEN;
     if (!(res <= K.tol)) st |= HB_CONTACT_UNCONVERGED;

@@ -85,7 +85,8 @@ HB_HD void joint_row(int r, const double* A, const double* X, const double* Jc, 
 
 // One substep of length h.  q[16], v[16] in / out (LDS); imp[32] (LDS behind `lds`) in / out; taua[10] (LDS) the saturated torque.
 // TERRAIN (hb_contact.hpp): rows 0-11 are those of the plane's frame, through A, the contact columns of X and Jc; the joint rows are unchanged.
-template <bool TERRAIN = false, class Ctx>
+// TERRAIN 2 (the profile): the same with the frame and offset of each point's facet.
+template <int TERRAIN = 0, class Ctx>
 HB_HD void joints_substep(const Ctx& cx, const DevModel& Mdl, double* q, double* v, const double* wrench, const int* all_on,
                           const hb_contact_config& K, const hb_joint_model& Jm, double eps, double h, double* lds, double* vdot_out,
                           const double* ter = nullptr) {
@@ -128,7 +129,11 @@ HB_HD void joints_substep(const Ctx& cx, const DevModel& Mdl, double* q, double*
   plant_substep<2>(cx, Mdl, q, v, taua, all_on, nullptr, 0.0, 0.0, h, lds, nullptr, nullptr, wgen, mdiag);
   for (int i = cx.lane; i < 16; i += cx.nlanes) vf[i] = v[i] + h * X[i * XJ];
   double ground_z;
-  if constexpr (TERRAIN) {
+  if constexpr (TERRAIN == 2) {
+    profile_select(cx, const_cast<double*>(ter), feet);   // (its barrier publishes vf)
+    profile_rotate<XJ>(cx, ter + Profile::act, Jc, X, A, feet);
+    ground_z = row_ground<2>(ter, cx.lane < 12 ? cx.lane : 0, 0.0);   // (the lane's own row)
+  } else if constexpr (TERRAIN) {
     terrain_rotate<XJ>(cx, ter + Terrain::T, Jc, X, A, feet);   // (its barriers publish vf)
     ground_z = ter[Terrain::d];
   } else {
@@ -139,7 +144,7 @@ HB_HD void joints_substep(const Ctx& cx, const DevModel& Mdl, double* q, double*
   for (int i = 0; i < 12; ++i) tr += A[i * 13];
   const double reg = eps * tr, mu = K.mu;
   double mup[HB_NC];
-  point_mu<TERRAIN>(ter, mu, mup);
+  point_mu<(TERRAIN != 0)>(ter, mu, mup);
   const bool stops = Jm.limits != 0;
   double D[12], Dj[HB_NJ], lim[HB_NJ], sj[HB_NJ];
   for (int k = 0; k < 12; ++k) D[k] = A[k * 13] + reg;
@@ -197,7 +202,8 @@ HB_HD void joints_substep(const Ctx& cx, const DevModel& Mdl, double* q, double*
 #else
   {
     double W[32 * 22], g[32], p[32], res = 0.0, jres = 0.0;
-    for (int r = 0; r < 32; ++r) joint_row(r, A, X, Jc, vf, feet, ground_z, K.erp, h, sgn, bstop, imp, reg, W + 22 * r, g[r], p[r]);
+    for (int r = 0; r < 32; ++r)
+      joint_row(r, A, X, Jc, vf, feet, row_ground<TERRAIN>(ter, r < 12 ? r : 0, ground_z), K.erp, h, sgn, bstop, imp, reg, W + 22 * r, g[r], p[r]);
     auto col = [&](int k, double d) { for (int r = 0; r < 32; ++r) g[r] += W[22 * r + k] * d; };
     for (int s = 0; s < K.sweeps; ++s) {
       res = 0.0;
@@ -254,11 +260,12 @@ HB_HD void joints_substep(const Ctx& cx, const DevModel& Mdl, double* q, double*
 // saturated torque (what hb_plant_sense reports as the joint torque).  HYBRID (hb_plant.hpp): `tau` is not read; the law is
 // evaluated and saturated into taua before every substep, tau_last / tau_applied are the last substep's and saturation bit 10 + j is set
 // if joint j was saturated in any substep.
-template <bool HYBRID = false, bool TERRAIN = false, class Ctx>
+template <bool HYBRID = false, int TERRAIN = 0, class Ctx>
 HB_HD void joints_step(const Ctx& cx, const DevModel& Mdl, double* q_g, double* v_g, double* imp_g, double* jimp_g, const double* tau,
                        const double* wrench, const int* all_on, const hb_contact_config& K, const hb_joint_model& Jm, double eps, double dt,
                        int substeps, double* lds, double* lambda_out, double* vdot_out, double* tau_last_g, const ContactOut& out,
-                       const JointOut& jout, const HybridActuator* actuator = nullptr, const double* ter = nullptr) {
+                       const JointOut& jout, const HybridActuator* actuator = nullptr, const double* ter = nullptr,
+                       const ProfileIo* pio = nullptr) {
   double* q = lds + JointLds::q;
   double* v = lds + JointLds::v;
   double* imp = lds + JointLds::imp;
@@ -292,7 +299,9 @@ HB_HD void joints_step(const Ctx& cx, const DevModel& Mdl, double* q_g, double* 
   for (int i = cx.lane; i < 16; i += cx.nlanes) { q_g[i] = q[i]; v_g[i] = v[i]; }
   for (int i = cx.lane; i < 12; i += cx.nlanes) {
     imp_g[i] = imp[i];
-    if constexpr (TERRAIN) {
+    if constexpr (TERRAIN == 2) {
+      contact_outputs_terrain(ter + Profile::act + Profile::rec * (i / 3), i, Jc, v, imp, h, lambda_out, out.pvel);
+    } else if constexpr (TERRAIN) {
       contact_outputs_terrain(ter, i, Jc, v, imp, h, lambda_out, out.pvel);
     } else {
       lambda_out[i] = imp[i] / h;
@@ -309,11 +318,14 @@ HB_HD void joints_step(const Ctx& cx, const DevModel& Mdl, double* q_g, double* 
     jout.limit_torque[j] = imp[22 + j] / h;
   }
   cx.sync();
+  if constexpr (TERRAIN == 2) profile_outputs_select(cx, pio->pro, feet, q);
   for (int c = cx.lane; c < HB_NC; c += cx.nlanes) {
-    if constexpr (TERRAIN) out.gap[c] = terrain_height(ter, feet + 3 * c);
+    if constexpr (TERRAIN == 2) out.gap[c] = terrain_height(ter + Profile::act + Profile::rec * c, feet + 3 * c);
+    else if constexpr (TERRAIN) out.gap[c] = terrain_height(ter, feet + 3 * c);
     else out.gap[c] = feet[3 * c + 2] - K.ground_z;
     out.touching[c] = imp[3 * c + 2] > 0.0 ? 1 : 0;
   }
+  if constexpr (TERRAIN == 2) profile_publish(cx, *pio);
   if (cx.lane == 0) {
     const double res = lds[JointLds::res], jres = lds[JointLds::res + 1];
     bool finite = true;

@@ -1209,6 +1209,116 @@ __global__ __launch_bounds__(64) void k_plant_varied_joints_hybrid(PlantBatch p,
                           lds + JOINT_LDS_TOTAL + ACT_LDS);
   if (cx.lane == 0) plant_publish(p, M, i, dt, res_rbd, res_x0, res_t);
 }
+// ---- the profile forms of the four ground kernels (hb_plant_set_terrain_profile): piecewise-planar ground, a facet per contact point -------
+// pb: hb_layout.hpp ProfileBatch; the instance's stored record is staged once per step in LDS behind the form's own arrays (and the
+// actuator's), the working part of the record (hb_contact.hpp Profile) follows it there.  Mvar: the [B] records of a model variation in
+// force, or null: the step runs on the instance's own DevModel or on the nominal one, so these four cover what the terrain and the varied
+// forms need eight for.  Lane contexts of their own for the reason above ActuatorCtx.
+struct ProfileCtx : DeviceCtx {};
+struct ProfileActuatorCtx : DeviceCtx {};
+__global__ __launch_bounds__(64) void k_plant_profile(PlantBatch p, ContactBatch cb, ProfileBatch pb, hb_contact_config K, const DevModel* __restrict__ M,
+                                                      const DevModel* __restrict__ Mvar, const double* tau, const int* contact, const int* mode, double dt,
+                                                      int substeps, double* res_rbd, double* res_x0, double* res_t) {
+  const int i = blockIdx.x;
+  __shared__ double lds[CONTACT_LDS_TOTAL + PRO_LDS];
+  __shared__ int all_on[HB_NC];
+  const ProfileCtx cx;
+  if (cx.lane < HB_NC) {
+    int flag;
+    if (contact) flag = contact[4 * i + cx.lane];
+    else { bool cf[HB_NC]; mode_flags(mode[i], cf); flag = cf[cx.lane] ? 1 : 0; }
+    p.contact_last[4 * i + cx.lane] = flag;
+    all_on[cx.lane] = 1;
+  }
+  if (cx.lane < HB_NJ) p.tau_last[10 * i + cx.lane] = tau[10 * i + cx.lane];
+  for (int k = cx.lane; k < Profile::stored; k += cx.nlanes) lds[CONTACT_LDS_TOTAL + k] = pb.prof[size_t(Profile::stored) * i + k];
+  __syncthreads();
+  const ContactOut out{cb.gap + 4 * i, cb.pvel + 12 * i, cb.res + i, cb.touching + 4 * i, cb.status + i};
+  const ProfileIo pio{lds + CONTACT_LDS_TOTAL, pb.seg + 5 * i, pb.base + Terrain::size * i};
+  const DevModel& Ms = Mvar ? Mvar[i] : *M;
+  contact_step<false, 2>(cx, Ms, p.q + 16 * i, p.v + 16 * i, cb.imp + 12 * i, tau + 10 * i, cb.use_wrench ? cb.wrench + 6 * i : nullptr, all_on, K,
+                         p.eps, dt, substeps, lds, p.lambda + 12 * i, p.vdot + 16 * i, out, nullptr, pio.pro, &pio);
+  if (cx.lane == 0) plant_publish(p, M, i, dt, res_rbd, res_x0, res_t);
+}
+__global__ __launch_bounds__(64) void k_plant_profile_joints(PlantBatch p, ContactBatch cb, JointBatch jb, ProfileBatch pb, hb_contact_config K,
+                                                             hb_joint_model J, const DevModel* __restrict__ M, const DevModel* __restrict__ Mvar,
+                                                             const double* tau, const int* contact, const int* mode, double dt, int substeps,
+                                                             double* res_rbd, double* res_x0, double* res_t) {
+  const int i = blockIdx.x;
+  __shared__ double lds[JOINT_LDS_TOTAL + PRO_LDS];
+  __shared__ int all_on[HB_NC];
+  const ProfileCtx cx;
+  if (cx.lane < HB_NC) {
+    int flag;
+    if (contact) flag = contact[4 * i + cx.lane];
+    else { bool cf[HB_NC]; mode_flags(mode[i], cf); flag = cf[cx.lane] ? 1 : 0; }
+    p.contact_last[4 * i + cx.lane] = flag;
+    all_on[cx.lane] = 1;
+  }
+  for (int k = cx.lane; k < Profile::stored; k += cx.nlanes) lds[JOINT_LDS_TOTAL + k] = pb.prof[size_t(Profile::stored) * i + k];
+  __syncthreads();
+  const ContactOut out{cb.gap + 4 * i, cb.pvel + 12 * i, cb.res + i, cb.touching + 4 * i, cb.status + i};
+  const ProfileIo pio{lds + JOINT_LDS_TOTAL, pb.seg + 5 * i, pb.base + Terrain::size * i};
+  const DevModel& Ms = Mvar ? Mvar[i] : *M;
+  const JointOut jout{jb.tau_applied + 10 * i, jb.friction_torque + 10 * i, jb.limit_torque + 10 * i, jb.res + i, jb.status + i};
+  joints_step<false, 2>(cx, Ms, p.q + 16 * i, p.v + 16 * i, cb.imp + 12 * i, jb.imp + 20 * i, tau + 10 * i, cb.use_wrench ? cb.wrench + 6 * i : nullptr,
+                        all_on, K, J, p.eps, dt, substeps, lds, p.lambda + 12 * i, p.vdot + 16 * i, p.tau_last + 10 * i, out, jout, nullptr, pio.pro,
+                        &pio);
+  if (cx.lane == 0) plant_publish(p, M, i, dt, res_rbd, res_x0, res_t);
+}
+__global__ __launch_bounds__(64) void k_plant_profile_hybrid(PlantBatch p, ContactBatch cb, ProfileBatch pb, ActuatorBatch a, ActuatorCmd c,
+                                                             hb_contact_config K, const DevModel* __restrict__ M, const DevModel* __restrict__ Mvar,
+                                                             const int* contact, const int* mode, double dt, int substeps, double* res_rbd,
+                                                             double* res_x0, double* res_t) {
+  const int i = blockIdx.x;
+  __shared__ double lds[CONTACT_LDS_TOTAL + ACT_LDS + PRO_LDS];
+  __shared__ int all_on[HB_NC];
+  const ProfileActuatorCtx cx;
+  if (cx.lane < HB_NC) {
+    int flag;
+    if (contact) flag = contact[4 * i + cx.lane];
+    else { bool cf[HB_NC]; mode_flags(mode[i], cf); flag = cf[cx.lane] ? 1 : 0; }
+    p.contact_last[4 * i + cx.lane] = flag;
+    all_on[cx.lane] = 1;
+  }
+  for (int k = cx.lane; k < Profile::stored; k += cx.nlanes) lds[CONTACT_LDS_TOTAL + ACT_LDS + k] = pb.prof[size_t(Profile::stored) * i + k];
+  __syncthreads();
+  const ContactOut out{cb.gap + 4 * i, cb.pvel + 12 * i, cb.res + i, cb.touching + 4 * i, cb.status + i};
+  const ProfileIo pio{lds + CONTACT_LDS_TOTAL + ACT_LDS, pb.seg + 5 * i, pb.base + Terrain::size * i};
+  const DevModel& Ms = Mvar ? Mvar[i] : *M;
+  const HybridActuator act = actuator_of(c, a, i, lds + CONTACT_LDS_TOTAL);
+  contact_step<true, 2>(cx, Ms, p.q + 16 * i, p.v + 16 * i, cb.imp + 12 * i, nullptr, cb.use_wrench ? cb.wrench + 6 * i : nullptr, all_on, K, p.eps, dt,
+                        substeps, lds, p.lambda + 12 * i, p.vdot + 16 * i, out, &act, pio.pro, &pio);
+  if (cx.lane < HB_NJ) p.tau_last[10 * i + cx.lane] = act.tau[cx.lane];   // (the lane's own entry)
+  if (cx.lane == 0) plant_publish(p, M, i, dt, res_rbd, res_x0, res_t);
+}
+__global__ __launch_bounds__(64) void k_plant_profile_joints_hybrid(PlantBatch p, ContactBatch cb, JointBatch jb, ProfileBatch pb, ActuatorBatch a,
+                                                                    ActuatorCmd c, hb_contact_config K, hb_joint_model J,
+                                                                    const DevModel* __restrict__ M, const DevModel* __restrict__ Mvar,
+                                                                    const int* contact, const int* mode, double dt, int substeps, double* res_rbd,
+                                                                    double* res_x0, double* res_t) {
+  const int i = blockIdx.x;
+  __shared__ double lds[JOINT_LDS_TOTAL + ACT_LDS + PRO_LDS];
+  __shared__ int all_on[HB_NC];
+  const ProfileActuatorCtx cx;
+  if (cx.lane < HB_NC) {
+    int flag;
+    if (contact) flag = contact[4 * i + cx.lane];
+    else { bool cf[HB_NC]; mode_flags(mode[i], cf); flag = cf[cx.lane] ? 1 : 0; }
+    p.contact_last[4 * i + cx.lane] = flag;
+    all_on[cx.lane] = 1;
+  }
+  for (int k = cx.lane; k < Profile::stored; k += cx.nlanes) lds[JOINT_LDS_TOTAL + ACT_LDS + k] = pb.prof[size_t(Profile::stored) * i + k];
+  __syncthreads();
+  const ContactOut out{cb.gap + 4 * i, cb.pvel + 12 * i, cb.res + i, cb.touching + 4 * i, cb.status + i};
+  const ProfileIo pio{lds + JOINT_LDS_TOTAL + ACT_LDS, pb.seg + 5 * i, pb.base + Terrain::size * i};
+  const DevModel& Ms = Mvar ? Mvar[i] : *M;
+  const JointOut jout{jb.tau_applied + 10 * i, jb.friction_torque + 10 * i, jb.limit_torque + 10 * i, jb.res + i, jb.status + i};
+  const HybridActuator act = actuator_of(c, a, i, lds + JOINT_LDS_TOTAL);
+  joints_step<true, 2>(cx, Ms, p.q + 16 * i, p.v + 16 * i, cb.imp + 12 * i, jb.imp + 20 * i, nullptr, cb.use_wrench ? cb.wrench + 6 * i : nullptr, all_on, K,
+                       J, p.eps, dt, substeps, lds, p.lambda + 12 * i, p.vdot + 16 * i, p.tau_last + 10 * i, out, jout, &act, pio.pro, &pio);
+  if (cx.lane == 0) plant_publish(p, M, i, dt, res_rbd, res_x0, res_t);
+}
 __global__ void k_plant_reset(PlantBatch p, const DevModel* __restrict__ M) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= p.B) return;

@@ -174,6 +174,22 @@ constexpr void fields(TerrainBatch& t, size_t, F&& f) {
   HB_FIELD(t.ter, Terrain::size);
 }
 
+// per-instance terrain profile of the ground-contact plant (hb_plant_set_terrain_profile), allocated by the first call that gives one:
+// prof: the stored part of the record the profile kernels stage per instance (hb_contact.hpp Profile: mu of the four points in a Terrain
+// head | direction | number of segments | breakpoints | (T_j, d_j) per segment); seg: the segment under the four contact points and the
+// base origin at the end of the last step; base: the Terrain record of the facet under the base origin there (what k_plant_episode takes
+// in place of the terrain records)
+struct ProfileBatch {
+  int B;
+  double* prof;
+  int* seg;
+  double* base;
+};
+template <class F>
+constexpr void fields(ProfileBatch& t, size_t, F&& f) {
+  HB_FIELD(t.prof, Profile::stored); HB_FIELD(t.seg, HB_NC + 1); HB_FIELD(t.base, Terrain::size);
+}
+
 // per-instance model variation of the ground-contact plant (hb_plant_set_model_variation, hb_modelvar.hpp), allocated by the first call
 // that gives one: the DevModel record each instance steps on, [B] records of sizeof(DevModel) (about 1.7 KB)
 struct ModelVarBatch {
@@ -342,6 +358,7 @@ static_assert(sizeof(PlantBatch) == kPtr /*B*/ + 2 * sizeof(double) + (n_fields<
 static_assert(sizeof(ContactBatch) == 2 * sizeof(int) + n_fields<ContactBatch>() * kPtr, "describe every array of ContactBatch in fields()");
 static_assert(sizeof(JointBatch) == kPtr /*B*/ + n_fields<JointBatch>() * kPtr, "describe every array of JointBatch in fields()");
 static_assert(sizeof(TerrainBatch) == kPtr /*B*/ + n_fields<TerrainBatch>() * kPtr, "describe every array of TerrainBatch in fields()");
+static_assert(sizeof(ProfileBatch) == kPtr /*B*/ + n_fields<ProfileBatch>() * kPtr, "describe every array of ProfileBatch in fields()");
 static_assert(sizeof(ModelVarBatch) == kPtr /*B*/ + n_fields<ModelVarBatch>() * kPtr, "describe every array of ModelVarBatch in fields()");
 static_assert(sizeof(EpisodeBatch) == 2 * sizeof(int) + (n_fields<EpisodeBatch>() + 1 /*trace*/) * kPtr, "describe every array of EpisodeBatch in fields()");
 static_assert(sizeof(RespawnBatch) == kPtr /*B*/ + n_fields<RespawnBatch>() * kPtr, "describe every array of RespawnBatch in fields()");

@@ -50,6 +50,35 @@ def plane_under_contact_points(solver, q, normals) -> np.ndarray:
     return np.einsum("bcx,bx->bc", feet, n).min(axis=1)
 
 
+def curb_profile(height: float, at: float, riser_slope: float = np.sqrt(3.0)) -> np.ndarray:
+    """Knots [4][2] of a curb (height > 0) or a step down (height < 0) whose riser starts at s = `at`: level at 0, a riser of slope
+    riser_slope (the steepest hb_plant_set_terrain_profile takes is sqrt(3)), level at `height`.  height 0: the same four knots, level."""
+    run = max(abs(height) / riser_slope, 1e-3)
+    return np.array([[at - 1.0, 0.0], [at, 0.0], [at + run, height], [at + run + 1.0, height]])
+
+
+def stairs_profile(rise: float, run: float, steps: int, at: float, riser_slope: float = np.sqrt(3.0)) -> np.ndarray:
+    """Knots [2 + 2 steps][2] of a flight of `steps` stairs from s = `at`: treads of length `run` (riser included), risers of height `rise`
+    (negative: down) and slope riser_slope.  2 + 2 steps <= abi.HB_PROFILE_MAX_KNOTS, so at most 7 steps."""
+    w = abs(rise) / riser_slope
+    if steps < 1 or 2 + 2 * steps > abi.HB_PROFILE_MAX_KNOTS or not run > w:
+        raise ValueError("stairs_profile: 1 .. 7 steps, each tread longer than its riser is wide")
+    k = [[at - 1.0, 0.0]]
+    for i in range(steps):
+        k += [[at + i * run, i * rise], [at + i * run + w, (i + 1) * rise]]
+    k.append([at + steps * run + 1.0, steps * rise])
+    return np.array(k)
+
+
+def pack_profiles(profiles):
+    """[B] knot arrays of different lengths -> (n_knots[B], knots[B][HB_PROFILE_MAX_KNOTS][2]) of hb_plant_set_terrain_profile."""
+    n = np.array([len(k) for k in profiles], dtype=np.int32)
+    out = np.zeros((len(profiles), abi.HB_PROFILE_MAX_KNOTS, 2))
+    for i, k in enumerate(profiles):
+        out[i, :len(k)] = k
+    return n, out
+
+
 def payload_on_base(mass, pos, inertia=None) -> np.ndarray:
     """The [B][10] payload array of hb_plant_set_model_variation: mass[B] (or a scalar) [kg], pos[B][3] (or [3]) = the payload's centre of
     mass in the base frame from the base origin [m], inertia[B][6] (or [6]) = xx xy xz yy yz zz about that centre in base axes (None: a
@@ -183,8 +212,11 @@ class ResidentLoop:
         device-resident command), as the reference's simulator does per simulator step (mujoco/src/main.cc:243-249).
         terrain: per-instance ground of the ground-contact plant — None: the contact model's own plane and mu; dict(plane=[B][4] = unit
         normal and offset d, or [B][3] = normals alone, the plane then goes under the lowest contact point of each instance's start
-        (plane_under_contact_points); mu=[B][4] per contact point), either may be missing (hb_plant_set_terrain).  Needs contact_config; set
-        after the contact model.  The controller, estimator and swing planner assume level ground.
+        (plane_under_contact_points); mu=[B][4] per contact point), either may be missing (hb_plant_set_terrain); or dict(profile=dict(dir=
+        [B][2], knots=[B] knot arrays [K_i][2] (curb_profile, stairs_profile) or [B][K][2], mu=[B][4] or missing), relative=True):
+        piecewise-planar ground per instance (hb_plant_set_terrain_profile), `relative` adds the height of the lowest contact point of each
+        instance's start to the knot heights.  Needs contact_config; set after the contact model.  The controller, estimator and swing
+        planner assume level ground.
         model_variation: per-instance inertial parameters of the ground-contact plant — None: the nominal robot; dict(mass_scale=[B][11],
         payload=[B][10] (payload_on_base)), either may be missing (hb_plant_set_model_variation).  Needs contact_config; set after the
         contact model, the joint model and the terrain and before the episode.  The controller keeps the nominal model.
@@ -247,7 +279,17 @@ class ResidentLoop:
             solver.plant_set_contact_model(contact_config)
             if joint_model is not None:
                 solver.plant_set_joint_model(abi.make_joint_model(params, **joint_model) if isinstance(joint_model, dict) else joint_model)
-            if terrain is not None:
+            if terrain is not None and terrain.get("profile") is not None:
+                if terrain.get("plane") is not None or terrain.get("mu") is not None:
+                    raise ValueError("terrain: a profile or a plane, one ground at a time (the profile's mu goes inside profile=)")
+                prof = terrain["profile"]
+                n_knots, knots = pack_profiles([np.asarray(k, dtype=float) for k in prof["knots"]])
+                if terrain.get("relative", True):
+                    z0 = plane_under_contact_points(solver, q0, [0.0, 0.0, 1.0])
+                    for i in range(self.B):
+                        knots[i, :n_knots[i], 1] += z0[i]
+                solver.plant_set_terrain_profile(n_knots, np.asarray(prof["dir"], dtype=float).reshape(self.B, 2), knots, prof.get("mu"))
+            elif terrain is not None:
                 plane = terrain.get("plane")
                 if plane is not None:
                     plane = np.asarray(plane, dtype=float).reshape(self.B, -1)

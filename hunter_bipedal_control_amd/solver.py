@@ -35,6 +35,7 @@ ABI_SYMBOLS = [
     "hb_plant_set_contact_model", "hb_plant_set_external_wrench", "hb_plant_get_contact",
     "hb_plant_set_joint_model", "hb_plant_get_joints", "hb_plant_step_hybrid", "hb_plant_get_actuator",
     "hb_plant_set_terrain", "hb_plant_get_terrain",
+    "hb_plant_set_terrain_profile", "hb_plant_get_terrain_profile",
     "hb_plant_set_model_variation", "hb_plant_get_model_variation",
     "hb_plant_set_episode", "hb_plant_get_episode",
     "hb_plant_set_respawn", "hb_plant_respawn", "hb_plant_get_respawn",
@@ -341,6 +342,32 @@ class HunterSolver:
         what the contact model amounts to."""
         out = dict(plane=np.zeros((self.B, 4)), mu=np.zeros((self.B, 4)), frame=np.zeros((self.B, 3, 3)))
         self._check(self.lib.hb_plant_get_terrain(self.ctx, *[_p(a) for a in out.values()]), "hb_plant_get_terrain")
+        return out
+
+    # ---- per-instance terrain profile of the ground-contact plant (hb_plant_set_terrain_profile) ------------------------------------
+    def plant_set_terrain_profile(self, n_knots=None, direction=None, knots=None, mu=None):
+        """Piecewise-planar ground per instance: n_knots [B]; direction [B][2] = the horizontal direction s is measured along; knots
+        [B][K][2] = (s_k, z_k) with K <= abi.HB_PROFILE_MAX_KNOTS (rows from n_knots[i] on are not read); mu [B][4] per contact point (None:
+        the contact model's mu).  All None: no profile.  Replaces a terrain of plant_set_terrain; clears the contact impulses."""
+        if n_knots is None and direction is None and knots is None and mu is None:
+            self._check(self.lib.hb_plant_set_terrain_profile(self.ctx, None, None, None, None), "hb_plant_set_terrain_profile")
+            return
+        nk = _i32(n_knots, (self.B,))
+        d = _f64(direction, (self.B, 2))
+        k = np.asarray(knots, dtype=np.float64)
+        assert k.ndim == 3 and k.shape[0] == self.B and k.shape[1] <= abi.HB_PROFILE_MAX_KNOTS and k.shape[2] == 2, k.shape
+        kk = np.zeros((self.B, abi.HB_PROFILE_MAX_KNOTS, 2))
+        kk[:, :k.shape[1]] = k
+        m = None if mu is None else _f64(mu, (self.B, 4))
+        self._check(self.lib.hb_plant_set_terrain_profile(self.ctx, _p(nk), _p(d), _p(kk), _p(m)), "hb_plant_set_terrain_profile")
+
+    def plant_get_terrain_profile(self):
+        """-> dict(n_knots[B], dir[B][2], knots[B][16][2], mu[B][4], records[B][15][10] = (T_j row-major, d_j) per segment, segment[B][5] =
+        the segment under the four contact points and under the base origin at the end of the last step) of the profile in force."""
+        K = abi.HB_PROFILE_MAX_KNOTS
+        out = dict(n_knots=np.zeros(self.B, dtype=np.int32), dir=np.zeros((self.B, 2)), knots=np.zeros((self.B, K, 2)), mu=np.zeros((self.B, 4)),
+                   records=np.zeros((self.B, K - 1, abi.HB_PROFILE_RECORD)), segment=np.zeros((self.B, 5), dtype=np.int32))
+        self._check(self.lib.hb_plant_get_terrain_profile(self.ctx, *[_p(a) for a in out.values()]), "hb_plant_get_terrain_profile")
         return out
 
     # ---- per-instance model variation of the ground-contact plant (hb_plant_set_model_variation) -------------------------------------

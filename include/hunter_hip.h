@@ -372,12 +372,48 @@ int32_t hb_plant_get_joints(hb_ctx* ctx, double* tau_applied, double* friction_t
  * | |n| - 1 | > 1e-9, n_z < 0.5 or mu < 0 (the message names the first offending instance; the terrain in force is kept); HB_ERR_STATE
  * before hb_plant_reset or outside contact model 1.  The call clears the contact impulses (the warm start is expressed in the frame of
  * before) and nothing else.  The terrain survives hb_plant_reset and a second hb_plant_set_contact_model with mode 1; leaving model 1
- * switches it off.  cfg.mu and cfg.ground_z are not read by a step while a terrain is in force. */
+ * switches it off.  cfg.mu and cfg.ground_z are not read by a step while a terrain is in force.  One ground at a time: every successful
+ * call, both NULL included, ends a terrain profile in force (hb_plant_set_terrain_profile below). */
 int32_t hb_plant_set_terrain(hb_ctx* ctx, const double* plane /*[batch][4] or NULL*/, const double* mu /*[batch][4] or NULL*/);
 /* The terrain in force (any pointer may be NULL): plane[batch][4] with the stored unit normal, mu[batch][4], frame[batch][9] = T
  * row-major.  Without a terrain: what the model in force amounts to, (0, 0, 1, ground_z), cfg.mu and the identity.  HB_ERR_STATE before
- * hb_plant_reset or outside contact model 1. */
+ * hb_plant_reset or outside contact model 1.  A terrain profile is no terrain of this call: with one in force it reports the level ground. */
 int32_t hb_plant_get_terrain(hb_ctx* ctx, double* plane, double* mu, double* frame);
+
+/* ---- per-instance terrain profile of contact model 1: piecewise-planar ground per robot (ramps, curbs, stairs) ------------------------
+ * Instance i has a horizontal unit direction a = (a_x, a_y), K knots (s_k, z_k), 2 <= K <= HB_PROFILE_MAX_KNOTS, s strictly increasing,
+ * and a friction coefficient mu_c >= 0 per contact point.  The ground is the surface z = z(s), s = a_x x + a_y y, with z(s) linear
+ * between knots and the first and the last segment continued beyond their end knots.  Segment j (knots j, j + 1) has the slope
+ * m_j = (z_{j+1} - z_j) / (s_{j+1} - s_j), the plane n_j = (-m_j a_x, -m_j a_y, 1) / sqrt(1 + m_j^2), d_j = n_j . (a_x s_j, a_y s_j, z_j),
+ * and the 10-double record (T_j, d_j): the frame T_j of n_j exactly as hb_plant_set_terrain builds it for the plane (n_j, d_j), so a
+ * one-segment profile stores, bit for bit, the record of that plane.
+ * Per substep, once the world contact points x_c of the substep's start are known, point c takes the segment j_c with
+ * s_{j_c} <= s(x_c) < s_{j_c + 1} (the end segments open-ended) and with it T_c, d_c.  Steps 1 - 6 of the terrain above then hold with
+ * T_c, d_c of the point in place of T, d: J~ = blockdiag(T_c') J; block (c, c') of A becomes T_c' A_cc' T_c'; the contact columns of X take
+ * their point's frame; phi_c = n_c . x_c - d_c; the impulses p_c are components in the point's own (t1, t2, n); lambda_c = T_c p_c / h and
+ * point_vel stay world quantities (T_c of the last substep); with the joint model rows 0 - 11 take the same substitution.  The outputs
+ * at q+ select again from the new positions: gap_c = n_c . x_c - d_c over the facet under point c, HB_CONTACT_FALLEN over the facet under
+ * the base origin q[0:3].  Arithmetic order: as the terrain's, every product with T_c the sum over the world axes x, y, z.  So a profile
+ * whose segments are all level at ground_z with mu = cfg.mu is the step without a terrain, and a one-segment profile the step of
+ * hb_plant_set_terrain on the same plane, value for value.  With a model variation in force the step runs on the instance's own model.
+ *
+ * n_knots[batch]; dir[batch][2] (|a| > 0, normalised before it is stored); knots[batch][HB_PROFILE_MAX_KNOTS][2] = (s_k, z_k), entries
+ * from n_knots on are not read; mu[batch][4] or NULL for cfg.mu (a snapshot).  n_knots, dir and knots all NULL (and mu NULL) switch the
+ * profile off.  HB_ERR_ARG for K out of range, a non-finite entry, |a| = 0, a knot spacing <= 0, |m_j| > sqrt(3) (n_z < 0.5) or mu < 0 (the
+ * message names the first offending instance; the profile in force is kept).  HB_ERR_STATE before hb_plant_reset, outside contact
+ * model 1, and while a respawn configuration or a scenario with the slope or friction channel is in force (those two calls in turn are
+ * refused while a profile is in force).  One ground at a time: setting a profile replaces a terrain of hb_plant_set_terrain and
+ * hb_plant_set_terrain replaces a profile; both clear the contact impulses and nothing else.  The profile survives hb_plant_reset and a
+ * second hb_plant_set_contact_model with mode 1; leaving model 1 switches it off.  With an episode record in force, height and tilt of
+ * the record are measured against the facet under the base origin. */
+#define HB_PROFILE_MAX_KNOTS 16
+int32_t hb_plant_set_terrain_profile(hb_ctx* ctx, const int32_t* n_knots /*[batch]*/, const double* dir /*[batch][2]*/,
+                                     const double* knots /*[batch][HB_PROFILE_MAX_KNOTS][2]*/, const double* mu /*[batch][4] or NULL*/);
+/* The profile in force (any pointer may be NULL): n_knots[batch], dir[batch][2] as stored, knots[batch][HB_PROFILE_MAX_KNOTS][2] (zero
+ * from n_knots on), mu[batch][4], records[batch][HB_PROFILE_MAX_KNOTS - 1][10] = (T_j row-major, d_j) per segment (zero from n_knots - 1
+ * on), segment[batch][5] = the segment under the four contact points and under the base origin at the end of the last step (at the state
+ * of the last hb_plant_reset or of the set call before a step).  HB_ERR_STATE without a profile in force. */
+int32_t hb_plant_get_terrain_profile(hb_ctx* ctx, int32_t* n_knots, double* dir, double* knots, double* mu, double* records, int32_t* segment);
 
 /* ---- per-instance model variation of contact model 1: a mass scale per body and a payload on the base ---------------------------------
  * Instance i steps on inertial parameters of its own; everything on the controller's side keeps the nominal model of hb_create.  The

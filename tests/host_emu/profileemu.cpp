@@ -1,0 +1,92 @@
+// TEST HARNESS: the profile forms of the ground-contact step routines (hb_contact.hpp contact_step, hb_joints.hpp joints_step with TERRAIN 2:
+// the routines k_plant_profile / k_plant_profile_joints and their hybrid forms run per instance) compiled for the host with one emulated
+// lane, for tests/test_profile_plant_host.py.  pro = the instance's stored Profile record (pe_record builds it with the host setter's
+// routine).  Not part of the product; the product path always runs the kernels.
+#include <cstddef>
+#include <cstdint>
+#include <vector>
+#include "../../hunter_bipedal_control_amd/csrc/hb_host.hpp"
+#include "../../hunter_bipedal_control_amd/csrc/hb_joints.hpp"
+
+using namespace hb;
+namespace {
+struct HostCtx {
+  int lane = 0, nlanes = 1;
+  void sync() const {}
+};
+HybridActuator actuator(const double* cmd, double* tau_first, double* tau_mean, double* act) {
+  return HybridActuator{cmd, cmd + 10, cmd + 20, cmd + 30, cmd + 40, tau_first, tau_mean, act, act + HB_NJ};
+}
+// the record where the kernels keep it: behind the form's own arrays, the working part behind the stored one
+ProfileIo staged(std::vector<double>& lds, int at, const double* pro, int* seg, double* base) {
+  for (int k = 0; k < Profile::stored; ++k) lds[at + k] = pro[k];
+  return ProfileIo{lds.data() + at, seg, base};
+}
+}  // namespace
+
+extern "C" {
+int pe_stored_size() { return Profile::stored; }
+int pe_segments_at() { return Profile::seg; }
+int pe_segment_size() { return Profile::rec; }
+// The stored record of a profile: 0, or -1 with the refusal in why[128].
+int pe_record(int K, const double* dir, const double* knots, const double* mu, double cfg_mu, double* rec, char* why) {
+  const char* w = profile_record(K, dir, knots, mu, cfg_mu, rec);
+  if (!w) return 0;
+  int k = 0;
+  for (; k < 127 && w[k]; ++k) why[k] = w[k];
+  why[k] = 0;
+  return -1;
+}
+int pe_segment(const double* pro, const double* x) { return profile_segment(pro, x); }
+// The arguments of te_step (terrainemu.cpp) with the stored profile record in the terrain record's place, and seg[5], base[14].
+void pe_step(const hb_model* m, const hb_contact_config* K, const double* pro, double* q, double* v, double* imp, const double* tau,
+             const double* wrench, double eps, double dt, int substeps, double* lambda, double* vdot, double* gap, double* pvel, double* res,
+             int* touching, int* status, int* seg, double* base) {
+  const DevModel d = make_dev_model(*m);
+  const int all_on[4] = {1, 1, 1, 1};
+  std::vector<double> lds(CONTACT_LDS_TOTAL + PRO_LDS, 0.0);
+  const ContactOut out{gap, pvel, res, touching, status};
+  const ProfileIo io = staged(lds, CONTACT_LDS_TOTAL, pro, seg, base);
+  contact_step<false, 2>(HostCtx{}, d, q, v, imp, tau, wrench, all_on, *K, eps, dt, substeps, lds.data(), lambda, vdot, out, nullptr, io.pro, &io);
+}
+void pe_joints_step(const hb_model* m, const hb_contact_config* K, const hb_joint_model* J, const double* pro, double* q, double* v, double* imp,
+                    double* jimp, const double* tau, const double* wrench, double eps, double dt, int substeps, double* lambda, double* vdot,
+                    double* gap, double* pvel, double* res, int* touching, int* status, double* tau_applied, double* friction_torque,
+                    double* limit_torque, double* jres, int* jstatus, double* tau_last, int* seg, double* base) {
+  const DevModel d = make_dev_model(*m);
+  const int all_on[4] = {1, 1, 1, 1};
+  std::vector<double> lds(JOINT_LDS_TOTAL + PRO_LDS, 0.0);
+  const ContactOut out{gap, pvel, res, touching, status};
+  const JointOut jout{tau_applied, friction_torque, limit_torque, jres, jstatus};
+  const ProfileIo io = staged(lds, JOINT_LDS_TOTAL, pro, seg, base);
+  joints_step<false, 2>(HostCtx{}, d, q, v, imp, jimp, tau, wrench, all_on, *K, *J, eps, dt, substeps, lds.data(), lambda, vdot, tau_last, out, jout,
+                        nullptr, io.pro, &io);
+}
+void pe_step_hybrid(const hb_model* m, const hb_contact_config* K, const double* pro, double* q, double* v, double* imp, const double* cmd,
+                    const double* wrench, double eps, double dt, int substeps, double* lambda, double* vdot, double* gap, double* pvel, double* res,
+                    int* touching, int* status, double* tau_first, double* tau_mean, double* tau_last, int* seg, double* base) {
+  const DevModel d = make_dev_model(*m);
+  const int all_on[4] = {1, 1, 1, 1};
+  std::vector<double> lds(CONTACT_LDS_TOTAL + ACT_LDS + PRO_LDS, 0.0);
+  const ContactOut out{gap, pvel, res, touching, status};
+  const HybridActuator act = actuator(cmd, tau_first, tau_mean, lds.data() + CONTACT_LDS_TOTAL);
+  const ProfileIo io = staged(lds, CONTACT_LDS_TOTAL + ACT_LDS, pro, seg, base);
+  contact_step<true, 2>(HostCtx{}, d, q, v, imp, nullptr, wrench, all_on, *K, eps, dt, substeps, lds.data(), lambda, vdot, out, &act, io.pro, &io);
+  for (int j = 0; j < HB_NJ; ++j) tau_last[j] = act.tau[j];
+}
+void pe_joints_step_hybrid(const hb_model* m, const hb_contact_config* K, const hb_joint_model* J, const double* pro, double* q, double* v,
+                           double* imp, double* jimp, const double* cmd, const double* wrench, double eps, double dt, int substeps, double* lambda,
+                           double* vdot, double* gap, double* pvel, double* res, int* touching, int* status, double* tau_applied,
+                           double* friction_torque, double* limit_torque, double* jres, int* jstatus, double* tau_last, double* tau_first,
+                           double* tau_mean, int* seg, double* base) {
+  const DevModel d = make_dev_model(*m);
+  const int all_on[4] = {1, 1, 1, 1};
+  std::vector<double> lds(JOINT_LDS_TOTAL + ACT_LDS + PRO_LDS, 0.0);
+  const ContactOut out{gap, pvel, res, touching, status};
+  const JointOut jout{tau_applied, friction_torque, limit_torque, jres, jstatus};
+  const HybridActuator act = actuator(cmd, tau_first, tau_mean, lds.data() + JOINT_LDS_TOTAL);
+  const ProfileIo io = staged(lds, JOINT_LDS_TOTAL + ACT_LDS, pro, seg, base);
+  joints_step<true, 2>(HostCtx{}, d, q, v, imp, jimp, nullptr, wrench, all_on, *K, *J, eps, dt, substeps, lds.data(), lambda, vdot, tau_last, out, jout,
+                       &act, io.pro, &io);
+}
+}

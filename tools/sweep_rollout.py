@@ -13,6 +13,8 @@
                                                         binned by mu, grade and payload mass, from the scenario log alone.  --host-driven: the
                                                         same sweep with the host calling the setters per respawn round and uploading a wrench
                                                         per tick, for the wall time of both
+    python tools/sweep_rollout.py --curb                one curb or step-down height per robot (0 / 1 / 2 / 3 cm down and up, B = 8), the riser --curb-at
+                                                        metres ahead of the base origin, trot across it (hb_plant_set_terrain_profile)
     python tools/sweep_rollout.py --readback            the two sweeps once more with the per-tick read-back loop the findings of items 17 - 20
                                                         were made with, for the wall time per tick of both
 
@@ -27,11 +29,12 @@ import numpy as np
 
 sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
 from hunter_bipedal_control_amd import abi, ingest  # noqa: E402
-from hunter_bipedal_control_amd.rollout import ResidentLoop, episode_summary, payload_on_base, respawn_summary, scenario_table  # noqa: E402
+from hunter_bipedal_control_amd.rollout import ResidentLoop, curb_profile, episode_summary, payload_on_base, respawn_summary, scenario_table  # noqa: E402
 from hunter_bipedal_control_amd.solver import HunterSolver  # noqa: E402
 
 FRICTION = [0.7, 0.5, 0.4, 0.3, 0.2, 0.15, 0.1, 0.05]
 SLOPES = [0.0, 0.05, 0.1, 0.2]
+CURBS = [0.0, -0.01, -0.02, -0.03, 0.0, 0.01, 0.02, 0.03]
 CAUSE = {abi.HB_EP_RUNNING: "-", abi.HB_EP_FALLEN: "fallen", abi.HB_EP_NONFINITE: "non-finite"}
 
 
@@ -52,6 +55,27 @@ def make_loop(params, mu, pitch, ticks, static, joint_model, payload=None, respa
                         static_schedule_until=(ticks * 0.002 + horizon + 1.5) if static else 0.0, episode=dict(slip_speed=0.05),
                         model_variation=None if payload is None else dict(payload=payload), respawn=respawn)
     return s, loop
+
+
+def run_curb(params, heights, at, ticks, joint_model=None, riser_slope=np.sqrt(3.0)):
+    """One batch: instance i trots along +x across a curb (height > 0) or a step down (< 0) of heights[i] whose riser starts `at` ahead of the
+    base origin of the start -> (episode record, segment under the points and the base at the end, wall seconds of the ticks)."""
+    B = len(heights)
+    s = HunterSolver(params, batch=B, max_nodes=108)
+    try:
+        # fall_height 0.2, not the 0.3 of the other sweeps: the fall test is measured along the normal of the facet under the base origin,
+        # and over a riser of slope sqrt(3) (n_z = 0.5) the standing height of 0.62 m reads 0.31 m
+        loop = ResidentLoop(s, params, ["trot"] * B, np.tile([0.2, 0.0, 0.0, 0.0], (B, 1)), contact_config=dict(fall_height=0.2), joint_model=joint_model,
+                            terrain=dict(profile=dict(dir=np.tile([1.0, 0.0], (B, 1)), knots=[curb_profile(h, at, riser_slope) for h in heights]), relative=True),
+                            episode=dict(slip_speed=0.05))
+        s.sync()
+        t0 = time.perf_counter()
+        loop.run(ticks)
+        rec = loop.episode()
+        wall = time.perf_counter() - t0
+        return rec, s.plant_get_terrain_profile()["segment"], wall
+    finally:
+        s.close()
 
 
 def run_respawn(params, mu, ticks, max_ticks, joint_model=None):
@@ -201,10 +225,19 @@ def main():
     ap.add_argument("--robots", type=int, default=64, help="batch of --randomize")
     ap.add_argument("--max-ticks", type=int, default=400, help="time-out of an episode of --randomize")
     ap.add_argument("--host-driven", action="store_true", help="--randomize with the host calling the setters per respawn round and uploading a wrench per tick")
+    ap.add_argument("--curb", action="store_true", help="one curb / step-down height per robot (0, 1, 2, 3 cm down and up), trot across it; from the episode record alone")
+    ap.add_argument("--curb-at", type=float, default=0.08, help="where the riser of --curb starts, metres ahead of the base origin of the start")
+    ap.add_argument("--riser-slope", type=float, default=float(np.sqrt(3.0)), help="slope of the riser of --curb (at most sqrt(3))")
     ap.add_argument("--readback", action="store_true", help="also time the per-tick read-back loop on the two sweeps")
     args = ap.parse_args()
     params = ingest.load_packaged()
     jm = {} if args.joint_model else None
+    if args.curb:
+        rec, seg, wall = run_curb(params, CURBS, args.curb_at, args.ticks, joint_model=jm, riser_slope=args.riser_slope)
+        print(f"-- curb sweep, B = {len(CURBS)}, riser of slope {args.riser_slope:.3g} {args.curb_at} m ahead, {args.ticks} ticks, run(): {1e3 * wall / args.ticks:.3f} ms per tick")
+        table("height", CURBS, rec)
+        print("   segment under the four contact points and the base at the end (0 before the riser, 1 on it, 2 beyond):", seg.tolist())
+        return
     if args.randomize:
         log, tot, wall = run_randomize(params, args.robots, args.randomize, args.max_ticks, joint_model=jm, host_driven=args.host_driven)
         print(f"-- randomised scenarios per episode, B = {args.robots}, {args.randomize} ticks, episodes of at most {args.max_ticks} ticks, "
