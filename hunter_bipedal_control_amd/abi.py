@@ -406,7 +406,8 @@ def hybrid_gains(gains: HbJointGains, stance=(True, True)):
 HB_MAX_EVENTS = 64
 # field order of hunter_hip.h's HB_MPC_CERT_* (HunterSolver.mpc_certificate)
 MPC_CERT_FIELDS = ("r_dyn", "r_stat", "obj", "step_max", "u_max", "lambda_max", "scale", "n_nodes")
-HB_LS_TAIL_MAX = 16   # step sizes one window of the backtracking tail evaluates side by side (hb_mpc_get_linesearch: ls_tail rows)
+RIC_GAINS_SENTINEL_BITS = 0x7ff85e471e100001   # HB_RIC_GAINS_SENTINEL_BITS: what hb_riccati_gains leaves in a gain slot the sweep did not write
+HB_LS_TAIL_MAX = 16  # step sizes one window of the backtracking tail evaluates side by side (hb_mpc_get_linesearch: ls_tail rows)
 # hb_status / per-instance status words (include/hunter_hip.h)
 HB_OK, HB_ERR_ARG, HB_ERR_DEVICE, HB_ERR_STATE, HB_ERR_NO_GPU = 0, -1, -2, -3, -4
 HB_INST_OK, HB_INST_MAXITER, HB_INST_INFEASIBLE, HB_INST_NAN = 0, 1, 2, 3

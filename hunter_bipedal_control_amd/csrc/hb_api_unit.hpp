@@ -128,25 +128,9 @@ int32_t hb_riccati_solve(hb_ctx* ctx, int32_t n, int32_t N, int32_t nu, const do
   std::vector<double> recs(size_t(n) * rec_inst, 0.0);
   for (int i = 0; i < n; ++i)
     for (int k = 0; k < N; ++k) {
-      double* rec = recs.data() + size_t(i) * rec_inst + size_t(k) * REC_SIZE;
       const size_t sk = size_t(i) * N + k;
-      for (int row = 0; row < 22; ++row) std::memcpy(rec + rec_A(row, 0), A + sk * 484 + row * 22, 22 * 8);
-      for (int i = 0; i < 22; ++i)   // the record holds the upper triangle of Q~, packed
-        for (int c = i; c < 22; ++c) rec[REC_QT + rec_Qidx(i, c)] = Q[sk * 484 + i * 22 + c];
-      for (int row = 0; row < 22; ++row) rec[rec_b(row)] = bv[sk * 22 + row];
-      std::memcpy(rec + REC_qT, q + sk * 22, 22 * 8);
-      for (int row = 0; row < 22; ++row)
-        for (int c = 0; c < nu; ++c) rec[rec_B(row, c)] = Bm[(sk * 22 + row) * nu + c];
-      for (int a = 0; a < NU_T; ++a) {
-        for (int c = 0; c < NU_T; ++c)
-          rec[rec_R(a, c)] = (a < nu && c < nu) ? R[(sk * nu + a) * nu + c] : (a == c ? 1.0 : 0.0);
-        if (a < nu) {
-          std::memcpy(rec + rec_P(a, 0), P + (sk * nu + a) * 22, 22 * 8);
-          rec[rec_r(a)] = r[sk * nu + a];
-        }
-      }
-      rec[REC_META + 0] = double(nu);  // number of real inputs (the backward sweep picks its factor width from it)
-      rec[REC_META + 1] = 0.0;
+      rec_pack(recs.data() + size_t(i) * rec_inst + size_t(k) * REC_SIZE, nu, 0, nu, A + sk * 484, Bm + sk * 22 * nu, bv + sk * 22, Q + sk * 484,
+               R + sk * nu * nu, P + sk * nu * 22, q + sk * 22, r + sk * nu);
     }
   // The forward kernel reconstructs du through the projection data; for this unit entry point the reduced input
   // is returned directly, so run backward on the device and the (cheap) forward recursion on the host.
@@ -185,6 +169,54 @@ int32_t hb_riccati_solve(hb_ctx* ctx, int32_t n, int32_t N, int32_t nu, const do
     }
     std::memcpy(dx + (size_t(i) * (N + 1) + N) * 22, xk, 22 * 8);
   }
+  return HB_OK;
+}
+
+int32_t hb_riccati_gains(hb_ctx* ctx, int32_t n, const int32_t* N, const int32_t* n_f, const int32_t* n_z, const double* A, const double* Bm,
+                         const double* bv, const double* Q, const double* R, const double* P, const double* q, const double* r,
+                         double* K, double* kv, int32_t* ric_fail) {
+  HB_ENTER_ARGS(n <= 0 || n > ctx->B || !N || !n_f || !n_z || !A || !Bm || !bv || !Q || !R || !P || !q || !r || !K || !kv || !ric_fail);
+  const size_t Nm = ctx->Nmax;
+  for (int i = 0; i < n; ++i) {
+    HB_FAIL_IF(N[i] < 1 || N[i] > ctx->Nmax, HB_ERR_ARG, "hb_riccati_gains: 1 <= N[i] <= max_nodes");
+    for (int k = 0; k < N[i]; ++k) {
+      const int f = n_f[i * Nm + k], z = n_z[i * Nm + k];
+      HB_FAIL_IF(f < 0 || z < 0 || (f + z != 6 && f + z != 9 && f + z != 12), HB_ERR_ARG, "hb_riccati_gains: n_f + n_z of a stage must be 6, 9 or 12");
+    }
+  }
+  // Records of the real stages exactly as hb_riccati_solve packs them; whatever the sweep has no business reading — the stages behind
+  // an instance's horizon, the instances behind the call's — is a quiet NaN, and the gains start as HB_RIC_GAINS_SENTINEL_BITS everywhere.
+  const size_t rec_inst = extent_of(ctx->b, Nm, ctx->b.recs).n, gain_inst = extent_of(ctx->b, Nm, ctx->b.gains).n;   // doubles per instance
+  std::vector<double> recs(size_t(ctx->B) * rec_inst, __builtin_nan(""));
+  for (int i = 0; i < n; ++i)
+    for (int k = 0; k < N[i]; ++k) {
+      const size_t sk = size_t(i) * Nm + k;
+      rec_pack(recs.data() + size_t(i) * rec_inst + size_t(k) * REC_SIZE, n_f[sk], n_z[sk], NU_T, A + sk * 484, Bm + sk * 22 * NU_T, bv + sk * 22,
+               Q + sk * 484, R + sk * NU_T * NU_T, P + sk * NU_T * 22, q + sk * 22, r + sk * NU_T);
+    }
+  const uint64_t sentinel_bits = HB_RIC_GAINS_SENTINEL_BITS;
+  double sentinel;
+  std::memcpy(&sentinel, &sentinel_bits, 8);
+  std::vector<double> gains(size_t(ctx->B) * gain_inst, sentinel);
+  HB_ENTER_DEVICE();
+  std::vector<int> nn(ctx->B, 1), fail(ctx->B, -1);
+  for (int i = 0; i < n; ++i) nn[i] = N[i];
+  HB_TRY(push(ctx, nn.data(), ctx->b, ctx->b.n_nodes, whole(ctx)));
+  HB_TRY(push(ctx, recs.data(), ctx->b, ctx->b.recs, whole(ctx)));
+  HB_TRY(push(ctx, gains.data(), ctx->b, ctx->b.gains, whole(ctx)));
+  HB_TRY(push(ctx, fail.data(), ctx->b, ctx->b.ric_fail, whole(ctx)));
+  launch_ric_bwd(ctx, ctx->b, n, n, ctx->s_mpc);
+  HB_HIP(hipGetLastError());
+  HB_HIP(hipStreamSynchronize(ctx->s_mpc));
+  HB_TRY(pull(ctx, gains.data(), ctx->b, ctx->b.gains, Range{0, n}));
+  HB_TRY(pull(ctx, ric_fail, ctx->b, ctx->b.ric_fail, Range{0, n}));
+  ctx->refs_set = false;  // the batch buffers were clobbered
+  for (int i = 0; i < n; ++i)
+    for (size_t k = 0; k < Nm; ++k) {
+      const double* g = gains.data() + size_t(i) * gain_inst + k * GAIN_SIZE;
+      std::memcpy(K + (size_t(i) * Nm + k) * NU_T * 22, g, NU_T * 22 * 8);
+      std::memcpy(kv + (size_t(i) * Nm + k) * NU_T, g + NU_T * 22, NU_T * 8);
+    }
   return HB_OK;
 }
 

@@ -94,6 +94,31 @@ inline void rec_unpack(const double* rec, double* A, double* B, double* b, doubl
   }
   if (n_til) *n_til = int(rec[REC_META]) + int(rec[REC_META + 1]);
 }
+// The other direction, for the unit entries that run the sweeps on caller-given stage data (hb_riccati_solve, hb_riccati_gains) and the
+// host harness: the Riccati part of one record from a stage QP with nu = n_f + n_z real inputs.  A [22][22], Q [22][22] (its upper triangle
+// is read), b, q [22]; B [22][ldu], R [.][ldu], r [.] and P [.][22] are read on their leading nu columns / rows.  The whole record is
+// written: R~ = I on the padding rows, zero everywhere else (B~, P~, r~ of the padding, the unused column, the recovery part).
+inline void rec_pack(double* rec, int n_f, int n_z, int ldu, const double* A, const double* B, const double* b, const double* Q, const double* R,
+                     const double* P, const double* q, const double* r) {
+  const int nu = n_f + n_z;
+  for (int e = 0; e < REC_SIZE; ++e) rec[e] = 0.0;
+  for (int i = 0; i < 22; ++i) {
+    for (int c = 0; c < 22; ++c) rec[rec_A(i, c)] = A[i * 22 + c];
+    for (int c = i; c < 22; ++c) rec[REC_QT + rec_Qidx(i, c)] = Q[i * 22 + c];
+    for (int a = 0; a < nu; ++a) rec[rec_B(i, a)] = B[i * ldu + a];
+    rec[rec_b(i)] = b[i];
+    rec[REC_qT + i] = q[i];
+  }
+  for (int a = 0; a < NU_T; ++a) {
+    for (int c = 0; c < NU_T; ++c) rec[rec_R(a, c)] = (a < nu && c < nu) ? R[a * ldu + c] : (a == c ? 1.0 : 0.0);
+    if (a < nu) {
+      for (int c = 0; c < 22; ++c) rec[rec_P(a, c)] = P[a * 22 + c];
+      rec[rec_r(a)] = r[a];
+    }
+  }
+  rec[REC_META + 0] = double(n_f);  // the backward sweep picks its factor width from n_f + n_z
+  rec[REC_META + 1] = double(n_z);
+}
 // The rest of the record, what recovers the full input step from the projected one (du = T u~ + K dx + k, hunter_hip.h) and what the
 // line search reads: Kx [10][22], ke [10], Z [10][6], dF [12], qf [22], rf [22], meta [6] (n_f, n_z, mode, cost dt, dyn_sse dt,
 // eq_sse dt), dt [1], dq [10].  Straight copies, nothing is recomputed.  Any pointer may be null.

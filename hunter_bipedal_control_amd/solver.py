@@ -24,7 +24,7 @@ ABI_SYMBOLS = [
     "hb_wbc_update", "hb_wbc_update_direct", "hb_set_resident_inputs", "hb_step_resident", "hb_set_resident_x0_sequence",
     "hb_get_wbc_solution", "hb_set_chunks",
     "hb_sync", "hb_get_stats", "hb_get_input_cost", "hb_version", "hb_eval_flow_map", "hb_eval_foot_kinematics",
-    "hb_eval_rbd", "hb_riccati_solve", "hb_estimator_reset", "hb_estimator_update", "hb_estimator_get_filter", "hb_estimator_contact_force",
+    "hb_eval_rbd", "hb_riccati_solve", "hb_riccati_gains", "hb_estimator_reset", "hb_estimator_update", "hb_estimator_get_filter", "hb_estimator_contact_force",
     "hb_refgen_reset", "hb_refgen_set_schedule", "hb_refgen_update", "hb_mpc_get_references", "hb_joint_command", "hb_centroidal_state_from_rbd", "hb_plant_reset", "hb_plant_step",
     "hb_plant_get_state", "hb_hoqp_solve", "hb_mpc_reset_masked", "hb_mpc_get_status", "hb_joint_set_flags",
     "hb_joint_get_emergency_stop", "hb_set_resident_time", "hb_get_wbc_iterations", "hb_ik_solve", "hb_debug_chunk_counters", "hb_debug_graph_state", "hb_refgen_get_status", "hb_tick_resident",
@@ -835,3 +835,18 @@ class HunterSolver:
         self._check(self.lib.hb_riccati_solve(self.ctx, C.c_int32(n), C.c_int32(N), C.c_int32(nu), _p(A), _p(Bm), _p(b), _p(Q), _p(R),
                                               _p(P), _p(q), _p(r), _p(dx0), _p(dx), _p(du)), "hb_riccati_solve")
         return dx, du
+
+    def riccati_gains(self, N, n_f, n_z, A, Bm, b, Q, R, P, q, r):
+        """The gains of the backward sweep alone (hb_riccati_gains): N [n] stages per instance, n_f, n_z [n][max_nodes] widths per stage, stage
+        data [n][max_nodes][...] padded to 12 inputs -> K [n][max_nodes][12][22], k [n][max_nodes][12], ric_fail [n].  Slots the sweep did not
+        write hold abi.RIC_GAINS_SENTINEL_BITS."""
+        N = _i32(np.atleast_1d(N))
+        n, M = N.shape[0], self.N
+        n_f, n_z = _i32(n_f, (n, M)), _i32(n_z, (n, M))
+        A, Q = _f64(A, (n, M, 22, 22)), _f64(Q, (n, M, 22, 22))
+        Bm, R, P = _f64(Bm, (n, M, 22, 12)), _f64(R, (n, M, 12, 12)), _f64(P, (n, M, 12, 22))
+        b, q, r = _f64(b, (n, M, 22)), _f64(q, (n, M, 22)), _f64(r, (n, M, 12))
+        K, k, fail = np.zeros((n, M, 12, 22)), np.zeros((n, M, 12)), np.zeros(n, dtype=np.int32)
+        self._check(self.lib.hb_riccati_gains(self.ctx, C.c_int32(n), _p(N), _p(n_f), _p(n_z), _p(A), _p(Bm), _p(b), _p(Q), _p(R), _p(P), _p(q),
+                                              _p(r), _p(K), _p(k), _p(fail)), "hb_riccati_gains")
+        return K, k, fail

@@ -1124,6 +1124,20 @@ int32_t hb_centroidal_state_from_rbd(hb_ctx* ctx, int32_t n, const double* rbd /
 int32_t hb_riccati_solve(hb_ctx* ctx, int32_t n, int32_t N, int32_t nu, const double* A, const double* B,
                          const double* b, const double* Q, const double* R, const double* P, const double* q,
                          const double* r, const double* dx0, double* dx /*[n][N+1][22]*/, double* du /*[n][N][nu]*/);
+/* The gains of the Riccati backward sweep alone, on caller-given stage data with per-stage widths: n <= batch instances, N[i] stages
+ * (1 <= N[i] <= max_nodes), stage k of instance i with n_f[i][k] + n_z[i][k] in {6, 9, 12} real inputs (the two numbers go to the record's
+ * width words as the LQ stage writes them).  Every array is [n][max_nodes][...] with the input index padded to 12: A [..][22][22],
+ * B [..][22][12], b [..][22], Q [..][22][22], R [..][12][12], P [..][12][22], q [..][22], r [..][12]; of B, R, P, r the leading
+ * n_f + n_z columns / rows are read, stages k >= N[i] are not read at all.  Records are packed as hb_riccati_solve packs them (R~ padded
+ * with I, B~, P~, r~ with zeros); the record of every stage k >= N[i] and of every instance n .. batch-1 is filled with quiet NaNs and the
+ * whole gains buffer with the bit pattern HB_RIC_GAINS_SENTINEL_BITS before the launch, so that K, k show which slots the sweep wrote and
+ * whether anything behind a horizon reached its arithmetic.  The sweep is the product's (hb_config.reserved picks its form as everywhere).
+ * Outputs: K [n][max_nodes][12][22], k [n][max_nodes][12] (u~ = k + K dx), ric_fail [n] (1: a pivot of some stage was not positive).
+ * Clobbers the MPC reference tables of the context like hb_riccati_solve. */
+#define HB_RIC_GAINS_SENTINEL_BITS 0x7ff85e471e100001ULL
+int32_t hb_riccati_gains(hb_ctx* ctx, int32_t n, const int32_t* N, const int32_t* n_f, const int32_t* n_z, const double* A,
+                         const double* B, const double* b, const double* Q, const double* R, const double* P, const double* q,
+                         const double* r, double* K, double* k, int32_t* ric_fail);
 /* Generic hierarchical QP cascade on small dense tasks (HoQp.cpp:21-198; HoQp.h:24-89): n_problems independent stacks of
  * n_levels <= 3 tasks {A x = b in the least-squares sense, D x <= f with slack} on n_vars <= 8 variables, m_eq[l] / m_in[l]
  * <= 8 rows per level (the same shape for every problem).  Blocks are padded: A, D [n_problems][3][8][8] row-major, b, f

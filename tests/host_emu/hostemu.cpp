@@ -106,6 +106,48 @@ double emu_sqp_iteration(const hb_model* m, const hb_config* c, int N, const dou
   }
   return 0.0;
 }
+// hb_riccati_gains on the host (include/hunter_hip.h: same arguments behind the context's batch B and Nmax, same record packing, same
+// NaN records behind the horizons and the same sentinel in the gains), the backward sweep being riccati_bwd_node stage by stage.
+int32_t emu_riccati_gains(int32_t B, int32_t Nmax, int32_t n, const int32_t* N, const int32_t* n_f, const int32_t* n_z, const double* A,
+                          const double* Bm, const double* bv, const double* Q, const double* R, const double* P, const double* q, const double* r,
+                          double* K, double* kv, int32_t* ric_fail) {
+  if (n <= 0 || n > B || Nmax <= 0) return -1;
+  const size_t Nm = Nmax;
+  for (int i = 0; i < n; ++i) {
+    if (N[i] < 1 || N[i] > Nmax) return -1;
+    for (int k = 0; k < N[i]; ++k) {
+      const int f = n_f[i * Nm + k], z = n_z[i * Nm + k];
+      if (f < 0 || z < 0 || (f + z != 6 && f + z != 9 && f + z != 12)) return -1;
+    }
+  }
+  std::vector<double> recs(size_t(B) * Nm * REC_SIZE, __builtin_nan(""));
+  for (int i = 0; i < n; ++i)
+    for (int k = 0; k < N[i]; ++k) {
+      const size_t sk = size_t(i) * Nm + k;
+      rec_pack(recs.data() + sk * REC_SIZE, n_f[sk], n_z[sk], NU_T, A + sk * 484, Bm + sk * 22 * NU_T, bv + sk * 22, Q + sk * 484, R + sk * NU_T * NU_T,
+               P + sk * NU_T * 22, q + sk * 22, r + sk * NU_T);
+    }
+  const uint64_t sentinel_bits = HB_RIC_GAINS_SENTINEL_BITS;
+  double sentinel;
+  std::memcpy(&sentinel, &sentinel_bits, 8);
+  std::vector<double> gains(size_t(B) * Nm * GAIN_SIZE, sentinel);
+  HostCtx cx;
+  for (int i = 0; i < n; ++i) {
+    std::vector<double> rl(RicLds::total, 0.0);
+    for (int k = N[i] - 1; k >= 0; --k) {
+      const double* rec = recs.data() + (size_t(i) * Nm + k) * REC_SIZE;
+      ric_stage(cx, rl.data(), rec);
+      riccati_bwd_node(cx, rl.data(), rec, gains.data() + (size_t(i) * Nm + k) * GAIN_SIZE);
+    }
+    ric_fail[i] = rl[RicLds::flag] != 0.0 ? 1 : 0;
+    for (size_t k = 0; k < Nm; ++k) {
+      const double* g = gains.data() + (size_t(i) * Nm + k) * GAIN_SIZE;
+      std::memcpy(K + (size_t(i) * Nm + k) * NU_T * 22, g, NU_T * 22 * 8);
+      std::memcpy(kv + (size_t(i) * Nm + k) * NU_T, g + NU_T * 22, NU_T * 8);
+    }
+  }
+  return 0;
+}
 // node_value (hb_riccati.hpp: what k_ls_eval / k_ls_tail_eval call per thread) of the n nodes of one instance at the trial point
 // (x + alpha dx, u + alpha du), formed as the kernels form it; x, dx [n + 1][22], u, du [n][22] -> out [n][3]
 void emu_node_value(const hb_model* m, const hb_config* c, int n, const double* t, const int* mode, const double* xref, const double* swing,

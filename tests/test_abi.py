@@ -41,6 +41,21 @@ def test_linesearch_getter_is_declared_bound_and_sized_alike():
     assert "hb_mpc_get_linesearch" in solver.ABI_SYMBOLS and hasattr(solver.load_library(), "hb_mpc_get_linesearch")
 
 
+def test_riccati_gains_entry_is_declared_bound_and_its_sentinel_is_one_number():
+    """hb_riccati_gains: declared once, bound by the Python wrapper, and the bit pattern it leaves in gain slots the sweep did not write is
+    the same number in the header, in abi.py and in the twin that looks for it (tests/_rictwin.py)."""
+    import _rictwin
+    header = (ROOT / "include" / "hunter_hip.h").read_text()
+    decl = re.findall(r"int32_t hb_riccati_gains\(([^;]*)\);", header)
+    assert len(decl) == 1
+    args = [a.split()[-1].lstrip("*") for a in decl[0].replace("\n", " ").split(",")]
+    assert args == ["ctx", "n", "N", "n_f", "n_z", "A", "B", "b", "Q", "R", "P", "q", "r", "K", "k", "ric_fail"]
+    bits = int(re.search(r"#define HB_RIC_GAINS_SENTINEL_BITS (0x[0-9a-fA-F]+)ULL", header).group(1), 16)
+    assert bits == abi.RIC_GAINS_SENTINEL_BITS == int(_rictwin.SENTINEL_BITS)
+    assert (bits >> 51) == 0xfff and bits & ((1 << 51) - 1), "a quiet NaN with a payload: arithmetic on it cannot come out finite"
+    assert "hb_riccati_gains" in solver.ABI_SYMBOLS and hasattr(solver.HunterSolver, "riccati_gains")
+
+
 def test_struct_sizes_match_the_header():
     # hb_model: 10 i32 + (30+30+40) f64 + 11 + 33 + 66 f64 + 4 i32 + 12 f64 + 1 f64
     assert C.sizeof(abi.HbModel) == 40 + 8 * (30 + 30 + 40 + 11 + 33 + 66) + 16 + 8 * 13
