@@ -9,7 +9,7 @@ import numpy as np
 NX, NU, NV, NJ, NC, NBODY, NWBC, NRBD, SWING_REF = 22, 22, 16, 10, 4, 11, 38, 32, 6
 FLY, MODE_R, MODE_L, STANCE = 0, 1, 2, 3
 HB_PAYLOAD_SIZE = 10   # hb_plant_set_model_variation: m_p, r[3], I_p[6] = xx xy xz yy yz zz
-HB_PROFILE_MAX_KNOTS = 16   # hb_plant_set_terrain_profile: knots per instance at most
+HB_PROFILE_MAX_KNOTS = 16   # hb_plant_set_terrain_profile, hb_ground_set_profile: knots per instance at most
 HB_PROFILE_RECORD = 10      # hb_plant_get_terrain_profile: doubles per segment record, T row-major | d
 
 

@@ -146,6 +146,12 @@ struct hb_ctx {
   GaitBatch gait{};
   hb_gait_config gait_cfg{};
   bool gait_on = false;
+  // ground map of the controller (hb_ground_set_profile): ground_on while one is in force (the planner and the filter then run in their
+  // ground forms, hb_forms.hpp use_ground_forms); the array is allocated on first use, ground_host is the host image of the stored records
+  // ([B][Ground::size]), ground_knots the knots as given ([B][HB_PROFILE_MAX_KNOTS][2], zero beyond K).  Nothing resets it but its own setter.
+  GroundBatch ground{};
+  std::vector<double> ground_host, ground_knots;
+  bool ground_on = false;
   // state estimator (allocated on the first hb_estimator_reset)
   EstBatch est{};
   hb_estimator_config est_cfg{};
@@ -369,7 +375,7 @@ static int32_t resident_write(hb_ctx* ctx, hipStream_t s, bool fence, F&& launch
 
 extern "C" {
 
-int32_t hb_version(void) { return 202; }
+int32_t hb_version(void) { return 300; }
 
 const char* hb_last_error(const hb_ctx* ctx) { return ctx ? ctx->err.c_str() : g_create_error.c_str(); }
 

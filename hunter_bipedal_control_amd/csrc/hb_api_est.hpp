@@ -1003,8 +1003,12 @@ int32_t hb_plant_sense(hb_ctx* ctx, double* quat, double* ang_vel_local, double*
   return HB_OK;
 }
 
-static void launch_estimator(const hb_ctx* ctx, const EstBatch& e, double dt, hipStream_t s) {
-  hipLaunchKernelGGL(k_estimator, dim3(e.B), dim3(64), 0, s, e, ctx->dmodel, ctx->est_cfg, dt);
+// Filter step of the instances of e (instances [i0, i0 + e.B) of the context); in its ground form while a ground map is in force.
+static void launch_estimator(const hb_ctx* ctx, const EstBatch& e, double dt, hipStream_t s, int i0 = 0) {
+  if (use_ground_forms(ctx->ground_on))
+    hipLaunchKernelGGL(k_estimator_ground, dim3(e.B), dim3(64), 0, s, e, view(ctx->ground, ctx->Nmax, i0, e.B), ctx->dmodel, ctx->est_cfg, dt);
+  else
+    hipLaunchKernelGGL(k_estimator, dim3(e.B), dim3(64), 0, s, e, ctx->dmodel, ctx->est_cfg, dt);
 }
 
 int32_t hb_estimator_reset(hb_ctx* ctx, const hb_estimator_config* cfg, const double* x_hat0) {

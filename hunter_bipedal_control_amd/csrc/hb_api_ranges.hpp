@@ -222,7 +222,7 @@ int32_t hb_tick_resident(hb_ctx* ctx, double dt_est, const double* quat, const d
     EstBatch e = view(est, ctx->Nmax, i0, cnt);
     e.res_rbd = w.rbd;
     e.res_x0 = b.x0;
-    launch_estimator(ctx, e, dt_est, s);
+    launch_estimator(ctx, e, dt_est, s, i0);
     // reference generation at the new time (the grid that is about to be replaced is kept for the warm start)
     HB_TRY(launch_grid_save(ctx, b, true, 0, cnt, s));
     launch_refgen(ctx, b, view(rg, ctx->Nmax, i0, cnt), i0, horizon, s);

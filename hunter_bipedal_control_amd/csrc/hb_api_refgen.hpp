@@ -49,7 +49,11 @@ static void launch_refgen(const hb_ctx* ctx, const Batch& b, RefgenBatch r, int 
     hipLaunchKernelGGL(k_gait, dim3((b.B + 63) / 64), dim3(64), 0, s, b, r, g, ctx->gait_cfg, horizon);
     r.cmd = g.cmd;
   }
-  hipLaunchKernelGGL(k_refgen, dim3((4 * b.B + 63) / 64), dim3(64), 0, s, b, r, ctx->dmodel, ctx->rg_cfg, horizon, init_flag);
+  if (use_ground_forms(ctx->ground_on))   // the planner on the ground map of these instances (hb_ground_set_profile)
+    hipLaunchKernelGGL(k_refgen_ground, dim3((4 * b.B + 63) / 64), dim3(64), 0, s, b, r, view(ctx->ground, ctx->Nmax, i0, b.B), ctx->dmodel, ctx->rg_cfg,
+                       horizon, init_flag);
+  else
+    hipLaunchKernelGGL(k_refgen, dim3((4 * b.B + 63) / 64), dim3(64), 0, s, b, r, ctx->dmodel, ctx->rg_cfg, horizon, init_flag);
   if (ctx->rg_cfg.joint_ik)
     hipLaunchKernelGGL(k_refgen_ik, dim3((2 * b.B + 7) / 8), dim3(64), 0, s, b, r, ctx->dmodel, ctx->rg_cfg, horizon);
   hipLaunchKernelGGL(k_refgen_nodes, dim3((b.B * ctx->Nmax + 63) / 64), dim3(64), 0, s, b, r, ctx->rg_cfg);

@@ -74,6 +74,26 @@ int32_t hb_ik_solve(hb_ctx* ctx, int32_t n, const double* q16, const int32_t* le
   return HB_OK;
 }
 
+int32_t hb_ground_eval(hb_ctx* ctx, int32_t n, const int32_t* inst, const double* xy, double* height, int32_t* segment) {
+  HB_ENTER_ARGS(n <= 0 || !inst || !xy || !(height || segment));
+  HB_FAIL_IF(!ctx->ground_on, HB_ERR_STATE, "hb_ground_eval: no ground map in force (hb_ground_set_profile)");
+  for (int p = 0; p < n; ++p) HB_FAIL_IF(inst[p] < 0 || inst[p] >= ctx->B, HB_ERR_ARG, "hb_ground_eval: instance index outside the batch");
+  HB_ENTER_DEVICE();
+  const size_t m = n;
+  DevBuf<double> dxy, dh;
+  DevBuf<int> di, ds;
+  HB_HIP(dxy.alloc(m * 2, xy));
+  HB_HIP(di.alloc(m, inst));
+  HB_HIP(dh.alloc(m));
+  HB_HIP(ds.alloc(m));
+  hipLaunchKernelGGL(k_ground_eval, dim3((n + 63) / 64), dim3(64), 0, ctx->s_mpc, n, ctx->ground, di.p, dxy.p, dh.p, ds.p);
+  HB_HIP(hipGetLastError());
+  HB_HIP(hipStreamSynchronize(ctx->s_mpc));
+  if (height) HB_HIP(hipMemcpy(height, dh.p, m * 8, hipMemcpyDeviceToHost));
+  if (segment) HB_HIP(hipMemcpy(segment, ds.p, m * 4, hipMemcpyDeviceToHost));
+  return HB_OK;
+}
+
 int32_t hb_hoqp_solve(hb_ctx* ctx, int32_t n_problems, int32_t n_vars, int32_t n_levels, const int32_t* m_eq, const int32_t* m_in,
                       const double* A, const double* b, const double* D, const double* f, double* x, double* slack, int32_t* status) {
   HB_ENTER_ARGS(n_problems <= 0 || n_vars <= 0 || n_vars > HQ_N || n_levels <= 0 || n_levels > HQ_L || !m_eq || !m_in || !A || !b || !D || !f ||

@@ -134,6 +134,10 @@ inline bool use_ric_fwd_wave(const KernelForms& f, int concurrent) {
   return f.fwd == KernelForms::Fwd::Wave || (f.fwd == KernelForms::Fwd::Auto && concurrent <= kRicFwdWaveMaxBatch);
 }
 
+// Planner and filter: the ground forms (k_refgen_ground, k_estimator_ground) while a ground map is in force (hb_ground_set_profile), the
+// base forms otherwise — the base forms never see the map, so a context without one runs what it always ran.
+inline bool use_ground_forms(bool map_in_force) { return map_in_force; }
+
 // LQ approximation: trips of this many nodes per wavefront (k_lq_trip).  Longer trips fill the lanes of the value phase better (16 nodes:
 // all 64), shorter ones keep small batches spread over the chip and balance them finer: the longest trip that still gives every
 // wavefront slot of the chip (12 per CU) four trips of the CONCURRENT batch — 16 nodes from 2048 instances up, 8 at 1024, 4 at 512

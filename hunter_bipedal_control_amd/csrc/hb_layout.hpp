@@ -13,6 +13,7 @@
 #include "hb_contact.hpp"
 #include "hb_episode.hpp"
 #include "hb_modelvar.hpp"
+#include "hb_ground.hpp"
 
 namespace {
 using namespace hb;
@@ -291,6 +292,17 @@ constexpr void fields(RefgenBatch& r, size_t, F&& f) {
   HB_FIELD(r.knot_t, RG_MAX_KNOTS); HB_FIELD(r.knot_x, RG_MAX_KNOTS * HB_NX);
 }
 
+// ground map of the controller (hb_ground_set_profile, hb_ground.hpp), allocated by the first call that gives one: the record the ground
+// forms of k_refgen and k_estimator read per instance (Ground: direction | number of segments | breakpoints | heights | slopes)
+struct GroundBatch {
+  int B;
+  double* map;
+};
+template <class F>
+constexpr void fields(GroundBatch& g, size_t, F&& f) {
+  HB_FIELD(g.map, Ground::size);
+}
+
 // GaitBatch (hb_gait.hpp): the schedule, the template, the rate limiter and the velocity history are slot-major
 template <class F>
 constexpr void fields(GaitBatch& g, size_t, F&& f) {
@@ -365,6 +377,7 @@ static_assert(sizeof(RespawnBatch) == kPtr /*B*/ + n_fields<RespawnBatch>() * kP
 static_assert(sizeof(ScenarioBatch) == 2 * sizeof(int) + (n_fields<ScenarioBatch>() + 1 /*log*/) * kPtr, "describe every array of ScenarioBatch in fields()");
 static_assert(sizeof(ActuatorBatch) == kPtr /*B*/ + n_fields<ActuatorBatch>() * kPtr, "describe every array of ActuatorBatch in fields()");
 static_assert(sizeof(RefgenBatch) == kPtr /*B*/ + n_fields<RefgenBatch>() * kPtr + kPtr /*init_stance*/, "describe every array of RefgenBatch in fields()");
+static_assert(sizeof(GroundBatch) == kPtr /*B*/ + n_fields<GroundBatch>() * kPtr, "describe every array of GroundBatch in fields()");
 static_assert(sizeof(GaitBatch) == 2 * sizeof(int) + n_fields<GaitBatch>() * kPtr, "describe every array of GaitBatch in fields()");
 static_assert(sizeof(EstBatch) == kPtr /*B*/ + (n_fields<EstBatch>() + 2 /*res_rbd, res_x0*/) * kPtr, "describe every array of EstBatch in fields()");
 static_assert(sizeof(TickUpload) == n_fields<TickUpload>() * kPtr, "describe every array of TickUpload in fields()");

@@ -196,7 +196,8 @@ class ResidentLoop:
     def __init__(self, solver, params: dict, gaits, cmd_vel, n_intervals: int = 100, mpc_every: int = 8, dt: float = 0.002,
                  t_gait_start: float = 0.3, joint_ik: bool = True, substeps: int = 4, static_schedule_until: float = 0.0,
                  device_gait: bool = False, use_estimator: bool = False, sensor_config=None, sensor_bias=None, contact_config=None,
-                 joint_model=None, actuator: str = "held", terrain=None, episode=None, model_variation=None, respawn=None, scenario=None):
+                 joint_model=None, actuator: str = "held", terrain=None, episode=None, model_variation=None, respawn=None, scenario=None,
+                 ground_map=None):
         """static_schedule_until > 0: the mode schedules are uploaded once for [-1, static_schedule_until] (at most
         HB_MAX_EVENTS events) instead of a sliding window per MPC call — no per-call host work for large batches.
         device_gait: the device gait manager produces the windows; step() builds no per-instance list and uploads no schedule, and
@@ -216,7 +217,12 @@ class ResidentLoop:
         [B][2], knots=[B] knot arrays [K_i][2] (curb_profile, stairs_profile) or [B][K][2], mu=[B][4] or missing), relative=True):
         piecewise-planar ground per instance (hb_plant_set_terrain_profile), `relative` adds the height of the lowest contact point of each
         instance's start to the knot heights.  Needs contact_config; set after the contact model.  The controller, estimator and swing
-        planner assume level ground.
+        planner assume level ground unless ground_map tells them otherwise.
+        ground_map: the ground the controller's side plans and filters on (hb_ground_set_profile) — None: the level plane; "plant": the
+        plant's terrain profile with the start offset taken out (the knots of terrain["profile"] as given when relative, less the height of
+        the lowest contact point of the start otherwise), so a level relative profile is the zero map; dict(dir=[B][2], knots=[B] knot
+        arrays [K_i][2] or [B][K][2]): a map of the caller's, heights relative to the level ground the controller assumes — independent of
+        the plant's ground, wrong on purpose if wanted.
         model_variation: per-instance inertial parameters of the ground-contact plant — None: the nominal robot; dict(mass_scale=[B][11],
         payload=[B][10] (payload_on_base)), either may be missing (hb_plant_set_model_variation).  Needs contact_config; set after the
         contact model, the joint model and the terrain and before the episode.  The controller keeps the nominal model.
@@ -284,10 +290,13 @@ class ResidentLoop:
                     raise ValueError("terrain: a profile or a plane, one ground at a time (the profile's mu goes inside profile=)")
                 prof = terrain["profile"]
                 n_knots, knots = pack_profiles([np.asarray(k, dtype=float) for k in prof["knots"]])
-                if terrain.get("relative", True):
-                    z0 = plane_under_contact_points(solver, q0, [0.0, 0.0, 1.0])
-                    for i in range(self.B):
+                z0 = plane_under_contact_points(solver, q0, [0.0, 0.0, 1.0])
+                plant_map = dict(n_knots=n_knots, dir=np.asarray(prof["dir"], dtype=float).reshape(self.B, 2), knots=knots.copy())
+                for i in range(self.B):
+                    if terrain.get("relative", True):
                         knots[i, :n_knots[i], 1] += z0[i]
+                    else:
+                        plant_map["knots"][i, :n_knots[i], 1] -= z0[i]
                 solver.plant_set_terrain_profile(n_knots, np.asarray(prof["dir"], dtype=float).reshape(self.B, 2), knots, prof.get("mu"))
             elif terrain is not None:
                 plane = terrain.get("plane")
@@ -297,6 +306,13 @@ class ResidentLoop:
                         n = plane / np.linalg.norm(plane, axis=1, keepdims=True)
                         plane = np.concatenate([n, plane_under_contact_points(solver, q0, n)[:, None]], axis=1)
                 solver.plant_set_terrain(plane, terrain.get("mu"))
+        if isinstance(ground_map, str):
+            if ground_map != "plant" or terrain is None or terrain.get("profile") is None:
+                raise ValueError('ground_map is None, "plant" (with terrain=dict(profile=...)) or dict(dir=..., knots=...)')
+            solver.ground_set_profile(plant_map["n_knots"], plant_map["dir"], plant_map["knots"])
+        elif ground_map is not None:
+            n_knots, knots = pack_profiles([np.asarray(k, dtype=float) for k in ground_map["knots"]])
+            solver.ground_set_profile(n_knots, np.asarray(ground_map["dir"], dtype=float).reshape(self.B, 2), knots)
         if model_variation is not None:
             solver.plant_set_model_variation(model_variation.get("mass_scale"), model_variation.get("payload"))
         if episode is not None:

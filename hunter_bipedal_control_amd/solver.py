@@ -40,6 +40,7 @@ ABI_SYMBOLS = [
     "hb_plant_set_episode", "hb_plant_get_episode",
     "hb_plant_set_respawn", "hb_plant_respawn", "hb_plant_get_respawn",
     "hb_plant_set_scenario", "hb_plant_get_scenario", "hb_plant_get_scenario_log",
+    "hb_ground_set_profile", "hb_ground_get_profile", "hb_ground_eval",
 ]
 # include/hunter_lcm.h
 LCM_SYMBOLS = ["hb_lcm_fingerprint", "hb_lcm_encoded_size", "hb_lcm_field_count", "hb_lcm_encode", "hb_lcm_decode", "hb_lcm_frame", "hb_lcm_unframe",
@@ -369,6 +370,38 @@ class HunterSolver:
                    records=np.zeros((self.B, K - 1, abi.HB_PROFILE_RECORD)), segment=np.zeros((self.B, 5), dtype=np.int32))
         self._check(self.lib.hb_plant_get_terrain_profile(self.ctx, *[_p(a) for a in out.values()]), "hb_plant_get_terrain_profile")
         return out
+
+    # ---- ground map of the controller (hb_ground_set_profile) -----------------------------------------------------------------------
+    def ground_set_profile(self, n_knots=None, direction=None, knots=None):
+        """Height profile the planner, the command target and the filter take for the ground, per instance: n_knots [B]; direction
+        [B][2]; knots [B][K][2] = (s_k, g_k) with K <= abi.HB_PROFILE_MAX_KNOTS (rows from n_knots[i] on are not read), heights relative
+        to the level ground of a controller without a map.  All None: no map.  Independent of the plant's ground."""
+        nk = None if n_knots is None else _i32(n_knots, (self.B,))
+        d = None if direction is None else _f64(direction, (self.B, 2))
+        kk = None
+        if knots is not None:
+            k = np.asarray(knots, dtype=np.float64)
+            assert k.ndim == 3 and k.shape[0] == self.B and k.shape[1] <= abi.HB_PROFILE_MAX_KNOTS and k.shape[2] == 2, k.shape
+            kk = np.zeros((self.B, abi.HB_PROFILE_MAX_KNOTS, 2))
+            kk[:, :k.shape[1]] = k
+        self._check(self.lib.hb_ground_set_profile(self.ctx, _p(nk), _p(d), _p(kk)), "hb_ground_set_profile")
+
+    def ground_get_profile(self):
+        """-> dict(n_knots[B], dir[B][2] as stored, knots[B][16][2], slopes[B][15]) of the map in force."""
+        K = abi.HB_PROFILE_MAX_KNOTS
+        out = dict(n_knots=np.zeros(self.B, dtype=np.int32), dir=np.zeros((self.B, 2)), knots=np.zeros((self.B, K, 2)), slopes=np.zeros((self.B, K - 1)))
+        self._check(self.lib.hb_ground_get_profile(self.ctx, *[_p(a) for a in out.values()]), "hb_ground_get_profile")
+        return out
+
+    def ground_eval(self, inst, xy):
+        """The device height function of the map in force at n points: inst [n] = the instance whose map a point is put to, xy [n][2]
+        -> (height[n], segment[n])."""
+        ii = _i32(inst)
+        n = ii.shape[0]
+        p = _f64(xy, (n, 2))
+        h, seg = np.zeros(n), np.zeros(n, dtype=np.int32)
+        self._check(self.lib.hb_ground_eval(self.ctx, C.c_int32(n), _p(ii), _p(p), _p(h), _p(seg)), "hb_ground_eval")
+        return h, seg
 
     # ---- per-instance model variation of the ground-contact plant (hb_plant_set_model_variation) -------------------------------------
     def plant_set_model_variation(self, mass_scale=None, payload=None):

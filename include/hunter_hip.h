@@ -1092,6 +1092,37 @@ int32_t hb_gait_insert_template(hb_ctx* ctx, int32_t inst_begin, int32_t inst_co
  * [count][HB_MAX_EVENTS + 1], status [count] (0, or 1 after an overflow).  Synchronises. */
 int32_t hb_gait_get_state(hb_ctx* ctx, int32_t inst_begin, int32_t inst_count, int32_t* level, double* vel_abs, double* vel_avg,
                           double* cmd, int32_t* n_events, double* event_times, int32_t* modes, int32_t* status);
+/* ---- ground map of the controller: footholds, command target and filter foot heights on a per-instance height profile ---------------
+ * Without a map the planner, the command target and the filter take the ground for the level plane (heights next_position_z,
+ * com_height and 0).  A map gives instance i a horizontal unit direction a = (a_x, a_y) and K knots (s_k, g_k), 2 <= K <=
+ * HB_PROFILE_MAX_KNOTS, s strictly increasing: the shape of the plant's terrain profile (hb_plant_set_terrain_profile) without its
+ * friction, and under the same checks, so a plant profile is always a valid map.  The heights g are RELATIVE to that level ground: g = 0
+ * everywhere is the world without a map.  The map is independent of the plant's ground (a wrong map can be given on purpose).
+ * Height function  G_i(x, y):  s = a_x x + a_y y (two products, one sum);  j = the last k in 1 .. K - 2 with s >= s_k, else 0 (the end
+ * segments open-ended, the scan of the plant's profile);  G = g_j + m_j (s - s_j)  with  m_j = (g_{j+1} - g_j) / (s_{j+1} - s_j)  computed
+ * once by the set call.  Every operation is rounded on its own (no fused multiply-add): a level segment returns g_j bit for bit, a NaN
+ * argument returns NaN.
+ * While a map is in force the planner step and the filter step run in their ground forms (other kernels; the forms without a map are
+ * untouched), which differ from the level ones in exactly these operands:
+ *   latest stance position of a foot in contact, after its x, y refresh:   z = G(x, y) + next_position_z
+ *   foothold p_n of a swing phase (calNextFootPos):                        z = G(p_n.x, p_n.y) + next_position_z
+ *   centrifugal term of the foothold:                                      sqrt((body.z - G(body.x, body.y)) / 9.81) in place of sqrt(body.z / 9.81)
+ *   first target knot:      x_now[8] moves towards  com_height + G(x_now[6], x_now[7])  by at most 0.04
+ *   second target knot:     tgt[8] = com_height + G(tgt[6], tgt[7])
+ *   filter measurement rows 24 .. 27 (foot heights):  y[24 + f] = G(xh[6 + 3 f], xh[7 + 3 f])  at the PREDICTED state xh, all four feet;
+ *                           the x 100 noise of a foot off the ground and the measurement matrix stay as they are.
+ * The friction cone, the end-effector constraint rows (world z), the joint-reference IK and the node tables take what the planner wrote.
+ *
+ * n_knots[batch]; dir[batch][2] (|a| > 0, normalised before it is stored); knots[batch][HB_PROFILE_MAX_KNOTS][2] = (s_k, g_k), entries
+ * from n_knots on are not read.  All three NULL switch the map off.  HB_ERR_ARG for K out of range, a non-finite entry, |a| = 0, a knot
+ * spacing <= 0 or |m_j| > sqrt(3) (the message names the first offending instance; the map in force is kept).  Legal any time after
+ * hb_create; synchronises, takes effect from the next pass, and switching a map on or off re-captures the range graphs.  The map
+ * survives hb_refgen_reset, hb_estimator_reset, hb_plant_reset and a respawn. */
+int32_t hb_ground_set_profile(hb_ctx* ctx, const int32_t* n_knots /*[batch]*/, const double* dir /*[batch][2]*/,
+                              const double* knots /*[batch][HB_PROFILE_MAX_KNOTS][2]*/);
+/* The map in force (any pointer may be NULL): n_knots[batch], dir[batch][2] as stored, knots[batch][HB_PROFILE_MAX_KNOTS][2] (zero from
+ * n_knots on), slopes[batch][HB_PROFILE_MAX_KNOTS - 1] = m_j (zero from n_knots - 1 on).  HB_ERR_STATE without a map in force. */
+int32_t hb_ground_get_profile(hb_ctx* ctx, int32_t* n_knots, double* dir, double* knots, double* slopes);
 /* Node tables back to the host (any pointer may be NULL); layouts as in hb_mpc_set_references. */
 int32_t hb_mpc_get_references(hb_ctx* ctx, int32_t inst_begin, int32_t inst_count, int32_t* n_nodes, double* t,
                               int32_t* mode, double* x_ref, double* swing_ref);
@@ -1159,6 +1190,10 @@ int32_t hb_debug_graph_state(hb_ctx* ctx, int64_t* out2);
  * out5[n][5] = the leg's joint angles.  Runs the lane-cooperative device routine that hb_refgen_update uses per knot; it is
  * the entry the reference-compiled golden vectors (tests/golden/ref_ik.json) are checked through. */
 int32_t hb_ik_solve(hb_ctx* ctx, int32_t n, const double* q16, const int32_t* leg, const double* des_pos, const double* R_des, double* out5);
+/* The height function of the ground map in force (hb_ground_set_profile) at n points, one kernel launch: point p is put to the map of
+ * instance inst[p] (0 <= inst[p] < batch), xy[n][2]; height[n] = G(x, y), segment[n] = j (either may be NULL, not both).  Runs the device
+ * routine the ground forms of the planner and the filter call.  HB_ERR_STATE without a map in force. */
+int32_t hb_ground_eval(hb_ctx* ctx, int32_t n, const int32_t* inst, const double* xy, double* height, int32_t* segment);
 /* QP step of the last SQP iteration (before the line search scaled it): dx[batch][max_nodes+1][22],
  * du[batch][max_nodes][22]; either may be NULL. */
 int32_t hb_mpc_get_step(hb_ctx* ctx, double* dx, double* du);

@@ -538,6 +538,16 @@ class ReferenceManager {
   // gaitType_ == 0 of the reference (the default, /gait_type topic): the gait of every instance follows its averaged command
   // speed (walkGait).  It needs the observation on the host, i.e. preSolverRun must be given `observation`.
   void setWalkGaitSelection(bool on) { walkGait_ = on; }
+  // The ground map of the controller's side (hb_ground_set_profile; one map per context, so the reference manager and the estimator of a
+  // context share it): nKnots [batch], dir [batch][2], knots [batch][HB_PROFILE_MAX_KNOTS][2] = (s_k, g_k).  All three empty: no map.
+  void setGroundProfile(const std::vector<int32_t>& nKnots, const vector_t& dir, const vector_t& knots) {
+    const size_t B = size_t(ctx_.batch());
+    const bool off = nKnots.empty() && dir.size() == 0 && knots.size() == 0;
+    if (!off && (nKnots.size() != B || size_t(dir.size()) != B * 2 || size_t(knots.size()) != B * HB_PROFILE_MAX_KNOTS * 2))
+      throw std::invalid_argument("[hunter_hip] setGroundProfile: wrong vector size");
+    ctx_.check(hb_ground_set_profile(ctx_.get(), off ? nullptr : nKnots.data(), off ? nullptr : dir.data(), off ? nullptr : knots.data()),
+               "hb_ground_set_profile");
+  }
   // initTime [batch], cmdVel [batch][4] = (vx, vy, vz, yaw rate); observation [batch][22] or nullptr = the resident one
   void preSolverRun(const vector_t& initTime, scalar_t timeHorizon, const vector_t& cmdVel, const vector_t* observation = nullptr) {
     const size_t B = size_t(ctx_.batch());
@@ -608,6 +618,16 @@ class KalmanFilterEstimate {
     return rbdState_;
   }
   const vector_t& observationState() const { return observationState_; }  // currentObservation_.state per instance
+  // The ground map of the controller's side (hb_ground_set_profile; one map per context, so the reference manager and the estimator of a
+  // context share it): nKnots [batch], dir [batch][2], knots [batch][HB_PROFILE_MAX_KNOTS][2] = (s_k, g_k).  All three empty: no map.
+  void setGroundProfile(const std::vector<int32_t>& nKnots, const vector_t& dir, const vector_t& knots) {
+    const size_t B = size_t(ctx_.batch());
+    const bool off = nKnots.empty() && dir.size() == 0 && knots.size() == 0;
+    if (!off && (nKnots.size() != B || size_t(dir.size()) != B * 2 || size_t(knots.size()) != B * HB_PROFILE_MAX_KNOTS * 2))
+      throw std::invalid_argument("[hunter_hip] setGroundProfile: wrong vector size");
+    ctx_.check(hb_ground_set_profile(ctx_.get(), off ? nullptr : nKnots.data(), off ? nullptr : dir.data(), off ? nullptr : knots.data()),
+               "hb_ground_set_profile");
+  }
   // StateEstimateBase::setCmdTorque + estContactForce (StateEstimateBase.cpp:130-206; LeggedController.cpp:344-345): the momentum
   // observer on the rbd state the last update() left on the device.  cmdTorque [batch][10] = the measured joint efforts.
   void estContactForce(scalar_t period, const vector_t& cmdTorque) {

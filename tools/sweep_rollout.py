@@ -14,7 +14,9 @@
                                                         same sweep with the host calling the setters per respawn round and uploading a wrench
                                                         per tick, for the wall time of both
     python tools/sweep_rollout.py --curb                one curb or step-down height per robot (0 / 1 / 2 / 3 cm down and up, B = 8), the riser --curb-at
-                                                        metres ahead of the base origin, trot across it (hb_plant_set_terrain_profile)
+                                                        metres ahead of the base origin, trot across it (hb_plant_set_terrain_profile);
+                                                        --ground-map: the controller plans and filters on the plant's profile
+                                                        (hb_ground_set_profile) instead of on the level plane
     python tools/sweep_rollout.py --readback            the two sweeps once more with the per-tick read-back loop the findings of items 17 - 20
                                                         were made with, for the wall time per tick of both
 
@@ -57,9 +59,9 @@ def make_loop(params, mu, pitch, ticks, static, joint_model, payload=None, respa
     return s, loop
 
 
-def run_curb(params, heights, at, ticks, joint_model=None, riser_slope=np.sqrt(3.0)):
+def run_curb(params, heights, at, ticks, joint_model=None, riser_slope=np.sqrt(3.0), ground_map=False):
     """One batch: instance i trots along +x across a curb (height > 0) or a step down (< 0) of heights[i] whose riser starts `at` ahead of the
-    base origin of the start -> (episode record, segment under the points and the base at the end, wall seconds of the ticks)."""
+    base origin of the start; ground_map: the controller is given the profile too -> (episode record, segment under the points and the base at the end, wall seconds of the ticks)."""
     B = len(heights)
     s = HunterSolver(params, batch=B, max_nodes=108)
     try:
@@ -67,7 +69,7 @@ def run_curb(params, heights, at, ticks, joint_model=None, riser_slope=np.sqrt(3
         # and over a riser of slope sqrt(3) (n_z = 0.5) the standing height of 0.62 m reads 0.31 m
         loop = ResidentLoop(s, params, ["trot"] * B, np.tile([0.2, 0.0, 0.0, 0.0], (B, 1)), contact_config=dict(fall_height=0.2), joint_model=joint_model,
                             terrain=dict(profile=dict(dir=np.tile([1.0, 0.0], (B, 1)), knots=[curb_profile(h, at, riser_slope) for h in heights]), relative=True),
-                            episode=dict(slip_speed=0.05))
+                            episode=dict(slip_speed=0.05), ground_map="plant" if ground_map else None)
         s.sync()
         t0 = time.perf_counter()
         loop.run(ticks)
@@ -226,6 +228,7 @@ def main():
     ap.add_argument("--max-ticks", type=int, default=400, help="time-out of an episode of --randomize")
     ap.add_argument("--host-driven", action="store_true", help="--randomize with the host calling the setters per respawn round and uploading a wrench per tick")
     ap.add_argument("--curb", action="store_true", help="one curb / step-down height per robot (0, 1, 2, 3 cm down and up), trot across it; from the episode record alone")
+    ap.add_argument("--ground-map", action="store_true", help="--curb with the controller's ground map set to the plant's profile (hb_ground_set_profile)")
     ap.add_argument("--curb-at", type=float, default=0.08, help="where the riser of --curb starts, metres ahead of the base origin of the start")
     ap.add_argument("--riser-slope", type=float, default=float(np.sqrt(3.0)), help="slope of the riser of --curb (at most sqrt(3))")
     ap.add_argument("--readback", action="store_true", help="also time the per-tick read-back loop on the two sweeps")
@@ -233,8 +236,8 @@ def main():
     params = ingest.load_packaged()
     jm = {} if args.joint_model else None
     if args.curb:
-        rec, seg, wall = run_curb(params, CURBS, args.curb_at, args.ticks, joint_model=jm, riser_slope=args.riser_slope)
-        print(f"-- curb sweep, B = {len(CURBS)}, riser of slope {args.riser_slope:.3g} {args.curb_at} m ahead, {args.ticks} ticks, run(): {1e3 * wall / args.ticks:.3f} ms per tick")
+        rec, seg, wall = run_curb(params, CURBS, args.curb_at, args.ticks, joint_model=jm, riser_slope=args.riser_slope, ground_map=args.ground_map)
+        print(f"-- curb sweep, {'controller on the ground map' if args.ground_map else 'controller blind'}, B = {len(CURBS)}, riser of slope {args.riser_slope:.3g} {args.curb_at} m ahead, {args.ticks} ticks, run(): {1e3 * wall / args.ticks:.3f} ms per tick")
         table("height", CURBS, rec)
         print("   segment under the four contact points and the base at the end (0 before the riser, 1 on it, 2 beyond):", seg.tolist())
         return
