@@ -444,71 +444,61 @@ int32_t hb_plant_reset(hb_ctx* ctx, const double* q0, const double* v0, double b
   return HB_OK;
 }
 
+// A step of the plant form in force (hb_forms.hpp plant_form), behind plant_write.  The drive is the held device torque dtau, or with cmd
+// the five device arrays of the hybrid actuator (pos_des vel_des kp kd ff, [B][10] each); contact: host flags or null.  Each form's launch
+// names its kernel and the arguments ahead of the tail every step kernel ends with.
+static int32_t plant_launch(hb_ctx* ctx, const double* dtau, const double* const* cmd, const int32_t* contact, double dt, int32_t substeps,
+                            int32_t to_resident) {
+  PlantBatch& p = ctx->plant;
+  hipStream_t s = ctx->s_wbc;  // the plant follows the control thread
+  HB_TRY(push(ctx, contact, p, p.contact, whole(ctx), &s));
+  const ActuatorCmd c = cmd ? ActuatorCmd{{cmd[0], cmd[1], cmd[2], cmd[3], cmd[4]}} : ActuatorCmd{};
+  const int* dcontact = contact ? p.contact : nullptr;
+  // the resident observation feeds the next hb_mpc_solve(NULL) / hb_refgen_update(NULL) on the MPC stream
+  double* rr = to_resident ? ctx->w.rbd : nullptr;
+  double* rx = to_resident ? ctx->b.x0 : nullptr;
+  double* rt = to_resident ? ctx->w.t_now : nullptr;
+  const DevModel* mvar = ctx->modelvar_on ? ctx->modelvar.mdl : nullptr;   // (the profile forms take the variation by pointer)
+  auto go = [&](auto kernel, const auto&... lead) {
+    return plant_write(ctx, s, to_resident, dt, [&] {
+      hipLaunchKernelGGL(kernel, dim3(ctx->B), dim3(64), 0, s, lead..., dcontact, ctx->w.mode, dt, substeps, rr, rx, rt);
+    });
+  };
+  const ContactBatch& cb = ctx->contact;
+  const JointBatch& jb = ctx->joints;
+  const ActuatorBatch& a = ctx->act;
+  const double* ter = ctx->terrain.ter;
+  const hb_contact_config& K = ctx->contact_cfg;
+  const hb_joint_model& J = ctx->joint_model;
+  const DevModel* M = ctx->dmodel;
+  const PlantForm f = plant_form(K.mode, ctx->joints_on, ctx->terrain_on, ctx->modelvar_on, ctx->profile_on, cmd != nullptr);
+  switch (f.ground) {
+    case PlantForm::Ground::Pinned:
+      return f.hybrid ? go(k_plant_hybrid, p, a, c, M) : go(k_plant, p, M, dtau);
+    case PlantForm::Ground::Level:
+      if (f.hybrid) return f.joints ? go(k_plant_joints_hybrid, p, cb, jb, a, c, K, J, M) : go(k_plant_contact_hybrid, p, cb, a, c, K, M);
+      return f.joints ? go(k_plant_joints, p, cb, jb, K, J, M, dtau) : go(k_plant_contact, p, cb, K, M, dtau);
+    case PlantForm::Ground::Terrain:
+      if (f.hybrid) return f.joints ? go(k_plant_terrain_joints_hybrid, p, cb, jb, ter, a, c, K, J, M) : go(k_plant_terrain_hybrid, p, cb, ter, a, c, K, M);
+      return f.joints ? go(k_plant_terrain_joints, p, cb, jb, ter, K, J, M, dtau) : go(k_plant_terrain, p, cb, ter, K, M, dtau);
+    case PlantForm::Ground::Varied:
+      if (f.hybrid) return f.joints ? go(k_plant_varied_joints_hybrid, p, cb, jb, ter, a, c, K, J, M, mvar) : go(k_plant_varied_hybrid, p, cb, ter, a, c, K, M, mvar);
+      return f.joints ? go(k_plant_varied_joints, p, cb, jb, ter, K, J, M, mvar, dtau) : go(k_plant_varied, p, cb, ter, K, M, mvar, dtau);
+    case PlantForm::Ground::Profile:
+      if (f.hybrid) return f.joints ? go(k_plant_profile_joints_hybrid, p, cb, jb, ctx->profile, a, c, K, J, M, mvar) : go(k_plant_profile_hybrid, p, cb, ctx->profile, a, c, K, M, mvar);
+      return f.joints ? go(k_plant_profile_joints, p, cb, jb, ctx->profile, K, J, M, mvar, dtau) : go(k_plant_profile, p, cb, ctx->profile, K, M, mvar, dtau);
+  }
+  return HB_ERR_STATE;   // (not reached: the switch covers PlantForm::Ground)
+}
+
 int32_t hb_plant_step(hb_ctx* ctx, const double* tau, const int32_t* contact, double dt, int32_t substeps, int32_t to_resident) {
   HB_ENTER_ARGS(!(dt > 0.0) || substeps < 1);
   HB_FAIL_IF(!ctx->plant_ready, HB_ERR_STATE, "hb_plant_step: call hb_plant_reset first");
   HB_FAIL_IF((!tau && !ctx->jc_computed) || (!contact && ctx->stats.n_wbc_solves == 0), HB_ERR_STATE, "hb_plant_step: no device-resident torque / contact flags yet (hb_joint_command after a WBC call)");
   HB_ENTER_DEVICE();
-  const size_t B = ctx->B;
   PlantBatch& p = ctx->plant;
-  hipStream_t s = ctx->s_wbc;  // the plant follows the control thread
-  HB_TRY(push(ctx, tau, p, p.tau, whole(ctx), &s));
-  HB_TRY(push(ctx, contact, p, p.contact, whole(ctx), &s));
-  const double* dtau = tau ? p.tau : ctx->jc_out + 5 * B * HB_NJ;
-  // the resident observation feeds the next hb_mpc_solve(NULL) / hb_refgen_update(NULL) on the MPC stream
-  const DevModel* mvar = ctx->modelvar_on ? ctx->modelvar.mdl : nullptr;   // (the profile forms take the variation by pointer)
-  if (ctx->contact_cfg.mode == 1 && ctx->profile_on && ctx->joints_on)
-    return plant_write(ctx, s, to_resident, dt, [&] {
-      hipLaunchKernelGGL(k_plant_profile_joints, dim3(ctx->B), dim3(64), 0, s, p, ctx->contact, ctx->joints, ctx->profile, ctx->contact_cfg,
-                         ctx->joint_model, ctx->dmodel, mvar, dtau, contact ? p.contact : nullptr, ctx->w.mode, dt, substeps,
-                         to_resident ? ctx->w.rbd : nullptr, to_resident ? ctx->b.x0 : nullptr, to_resident ? ctx->w.t_now : nullptr);
-    });
-  if (ctx->contact_cfg.mode == 1 && ctx->profile_on)
-    return plant_write(ctx, s, to_resident, dt, [&] {
-      hipLaunchKernelGGL(k_plant_profile, dim3(ctx->B), dim3(64), 0, s, p, ctx->contact, ctx->profile, ctx->contact_cfg, ctx->dmodel, mvar, dtau,
-                         contact ? p.contact : nullptr, ctx->w.mode, dt, substeps, to_resident ? ctx->w.rbd : nullptr,
-                         to_resident ? ctx->b.x0 : nullptr, to_resident ? ctx->w.t_now : nullptr);
-    });
-  if (ctx->contact_cfg.mode == 1 && ctx->modelvar_on && ctx->joints_on)
-    return plant_write(ctx, s, to_resident, dt, [&] {
-      hipLaunchKernelGGL(k_plant_varied_joints, dim3(ctx->B), dim3(64), 0, s, p, ctx->contact, ctx->joints, ctx->terrain.ter, ctx->contact_cfg,
-                         ctx->joint_model, ctx->dmodel, ctx->modelvar.mdl, dtau, contact ? p.contact : nullptr, ctx->w.mode, dt, substeps,
-                         to_resident ? ctx->w.rbd : nullptr, to_resident ? ctx->b.x0 : nullptr, to_resident ? ctx->w.t_now : nullptr);
-    });
-  if (ctx->contact_cfg.mode == 1 && ctx->modelvar_on)
-    return plant_write(ctx, s, to_resident, dt, [&] {
-      hipLaunchKernelGGL(k_plant_varied, dim3(ctx->B), dim3(64), 0, s, p, ctx->contact, ctx->terrain.ter, ctx->contact_cfg, ctx->dmodel,
-                         ctx->modelvar.mdl, dtau, contact ? p.contact : nullptr, ctx->w.mode, dt, substeps, to_resident ? ctx->w.rbd : nullptr,
-                         to_resident ? ctx->b.x0 : nullptr, to_resident ? ctx->w.t_now : nullptr);
-    });
-  if (ctx->contact_cfg.mode == 1 && ctx->terrain_on && ctx->joints_on)
-    return plant_write(ctx, s, to_resident, dt, [&] {
-      hipLaunchKernelGGL(k_plant_terrain_joints, dim3(ctx->B), dim3(64), 0, s, p, ctx->contact, ctx->joints, ctx->terrain.ter, ctx->contact_cfg,
-                         ctx->joint_model, ctx->dmodel, dtau, contact ? p.contact : nullptr, ctx->w.mode, dt, substeps,
-                         to_resident ? ctx->w.rbd : nullptr, to_resident ? ctx->b.x0 : nullptr, to_resident ? ctx->w.t_now : nullptr);
-    });
-  if (ctx->contact_cfg.mode == 1 && ctx->terrain_on)
-    return plant_write(ctx, s, to_resident, dt, [&] {
-      hipLaunchKernelGGL(k_plant_terrain, dim3(ctx->B), dim3(64), 0, s, p, ctx->contact, ctx->terrain.ter, ctx->contact_cfg, ctx->dmodel, dtau,
-                         contact ? p.contact : nullptr, ctx->w.mode, dt, substeps, to_resident ? ctx->w.rbd : nullptr,
-                         to_resident ? ctx->b.x0 : nullptr, to_resident ? ctx->w.t_now : nullptr);
-    });
-  if (ctx->contact_cfg.mode == 1 && ctx->joints_on)
-    return plant_write(ctx, s, to_resident, dt, [&] {
-      hipLaunchKernelGGL(k_plant_joints, dim3(ctx->B), dim3(64), 0, s, p, ctx->contact, ctx->joints, ctx->contact_cfg, ctx->joint_model, ctx->dmodel, dtau,
-                         contact ? p.contact : nullptr, ctx->w.mode, dt, substeps, to_resident ? ctx->w.rbd : nullptr,
-                         to_resident ? ctx->b.x0 : nullptr, to_resident ? ctx->w.t_now : nullptr);
-    });
-  if (ctx->contact_cfg.mode == 1)
-    return plant_write(ctx, s, to_resident, dt, [&] {
-      hipLaunchKernelGGL(k_plant_contact, dim3(ctx->B), dim3(64), 0, s, p, ctx->contact, ctx->contact_cfg, ctx->dmodel, dtau, contact ? p.contact : nullptr,
-                         ctx->w.mode, dt, substeps, to_resident ? ctx->w.rbd : nullptr, to_resident ? ctx->b.x0 : nullptr,
-                         to_resident ? ctx->w.t_now : nullptr);
-    });
-  return plant_write(ctx, s, to_resident, dt, [&] {
-    hipLaunchKernelGGL(k_plant, dim3(ctx->B), dim3(64), 0, s, p, ctx->dmodel, dtau, contact ? p.contact : nullptr, ctx->w.mode, dt, substeps,
-                       to_resident ? ctx->w.rbd : nullptr, to_resident ? ctx->b.x0 : nullptr, to_resident ? ctx->w.t_now : nullptr);
-  });
+  HB_TRY(push(ctx, tau, p, p.tau, whole(ctx), &ctx->s_wbc));
+  return plant_launch(ctx, tau ? p.tau : ctx->jc_out + 5 * size_t(ctx->B) * HB_NJ, nullptr, contact, dt, substeps, to_resident);
 }
 
 // what the step calls check before anything changes; `who` names the entry point
@@ -520,62 +510,6 @@ static int32_t plant_step_ready(hb_ctx* ctx, const char* who, bool need_jc, bool
   if (!why) return HB_OK;
   ctx->err = std::string(who) + ": " + why;
   return HB_ERR_STATE;
-}
-
-// A hybrid step of the plant form in force on the five device arrays cmd (pos_des vel_des kp kd ff, [B][10] each); contact: host flags or null.
-static int32_t plant_launch_hybrid(hb_ctx* ctx, const double* const cmd[5], const int32_t* contact, double dt, int32_t substeps, int32_t to_resident) {
-  PlantBatch& p = ctx->plant;
-  hipStream_t s = ctx->s_wbc;  // the plant follows the control thread
-  HB_TRY(push(ctx, contact, p, p.contact, whole(ctx), &s));
-  const ActuatorCmd c{{cmd[0], cmd[1], cmd[2], cmd[3], cmd[4]}};
-  const int* dcontact = contact ? p.contact : nullptr;
-  double* rr = to_resident ? ctx->w.rbd : nullptr;
-  double* rx = to_resident ? ctx->b.x0 : nullptr;
-  double* rt = to_resident ? ctx->w.t_now : nullptr;
-  const DevModel* mvar = ctx->modelvar_on ? ctx->modelvar.mdl : nullptr;   // (the profile forms take the variation by pointer)
-  if (ctx->contact_cfg.mode == 1 && ctx->profile_on && ctx->joints_on)
-    return plant_write(ctx, s, to_resident, dt, [&] {
-      hipLaunchKernelGGL(k_plant_profile_joints_hybrid, dim3(ctx->B), dim3(64), 0, s, p, ctx->contact, ctx->joints, ctx->profile, ctx->act, c,
-                         ctx->contact_cfg, ctx->joint_model, ctx->dmodel, mvar, dcontact, ctx->w.mode, dt, substeps, rr, rx, rt);
-    });
-  if (ctx->contact_cfg.mode == 1 && ctx->profile_on)
-    return plant_write(ctx, s, to_resident, dt, [&] {
-      hipLaunchKernelGGL(k_plant_profile_hybrid, dim3(ctx->B), dim3(64), 0, s, p, ctx->contact, ctx->profile, ctx->act, c, ctx->contact_cfg,
-                         ctx->dmodel, mvar, dcontact, ctx->w.mode, dt, substeps, rr, rx, rt);
-    });
-  if (ctx->contact_cfg.mode == 1 && ctx->modelvar_on && ctx->joints_on)
-    return plant_write(ctx, s, to_resident, dt, [&] {
-      hipLaunchKernelGGL(k_plant_varied_joints_hybrid, dim3(ctx->B), dim3(64), 0, s, p, ctx->contact, ctx->joints, ctx->terrain.ter, ctx->act, c,
-                         ctx->contact_cfg, ctx->joint_model, ctx->dmodel, ctx->modelvar.mdl, dcontact, ctx->w.mode, dt, substeps, rr, rx, rt);
-    });
-  if (ctx->contact_cfg.mode == 1 && ctx->modelvar_on)
-    return plant_write(ctx, s, to_resident, dt, [&] {
-      hipLaunchKernelGGL(k_plant_varied_hybrid, dim3(ctx->B), dim3(64), 0, s, p, ctx->contact, ctx->terrain.ter, ctx->act, c, ctx->contact_cfg,
-                         ctx->dmodel, ctx->modelvar.mdl, dcontact, ctx->w.mode, dt, substeps, rr, rx, rt);
-    });
-  if (ctx->contact_cfg.mode == 1 && ctx->terrain_on && ctx->joints_on)
-    return plant_write(ctx, s, to_resident, dt, [&] {
-      hipLaunchKernelGGL(k_plant_terrain_joints_hybrid, dim3(ctx->B), dim3(64), 0, s, p, ctx->contact, ctx->joints, ctx->terrain.ter, ctx->act, c,
-                         ctx->contact_cfg, ctx->joint_model, ctx->dmodel, dcontact, ctx->w.mode, dt, substeps, rr, rx, rt);
-    });
-  if (ctx->contact_cfg.mode == 1 && ctx->terrain_on)
-    return plant_write(ctx, s, to_resident, dt, [&] {
-      hipLaunchKernelGGL(k_plant_terrain_hybrid, dim3(ctx->B), dim3(64), 0, s, p, ctx->contact, ctx->terrain.ter, ctx->act, c, ctx->contact_cfg,
-                         ctx->dmodel, dcontact, ctx->w.mode, dt, substeps, rr, rx, rt);
-    });
-  if (ctx->contact_cfg.mode == 1 && ctx->joints_on)
-    return plant_write(ctx, s, to_resident, dt, [&] {
-      hipLaunchKernelGGL(k_plant_joints_hybrid, dim3(ctx->B), dim3(64), 0, s, p, ctx->contact, ctx->joints, ctx->act, c, ctx->contact_cfg, ctx->joint_model,
-                         ctx->dmodel, dcontact, ctx->w.mode, dt, substeps, rr, rx, rt);
-    });
-  if (ctx->contact_cfg.mode == 1)
-    return plant_write(ctx, s, to_resident, dt, [&] {
-      hipLaunchKernelGGL(k_plant_contact_hybrid, dim3(ctx->B), dim3(64), 0, s, p, ctx->contact, ctx->act, c, ctx->contact_cfg, ctx->dmodel, dcontact,
-                         ctx->w.mode, dt, substeps, rr, rx, rt);
-    });
-  return plant_write(ctx, s, to_resident, dt, [&] {
-    hipLaunchKernelGGL(k_plant_hybrid, dim3(ctx->B), dim3(64), 0, s, p, ctx->act, c, ctx->dmodel, dcontact, ctx->w.mode, dt, substeps, rr, rx, rt);
-  });
 }
 
 int32_t hb_plant_step_hybrid(hb_ctx* ctx, const double* pos_des, const double* vel_des, const double* kp, const double* kd, const double* tau_ff,
@@ -595,7 +529,7 @@ int32_t hb_plant_step_hybrid(hb_ctx* ctx, const double* pos_des, const double* v
     HB_TRY(push(ctx, host[k], a, a.cmd[k], whole(ctx), &ctx->s_wbc));
     cmd[k] = given ? a.cmd[k] : ctx->jc_out + k * n;   // planes 0-4 of the joint command: posDes velDes kp kd ff
   }
-  return plant_launch_hybrid(ctx, cmd, contact, dt, substeps, to_resident);
+  return plant_launch(ctx, nullptr, cmd, contact, dt, substeps, to_resident);
 }
 
 int32_t hb_plant_get_actuator(hb_ctx* ctx, double* tau_first, double* tau_mean, int64_t* last_timestamp) {

@@ -128,7 +128,7 @@ int32_t hb_plant_step_lcm(hb_ctx* ctx, const uint8_t* low_cmd, const int32_t* co
                      a.last_ts, a.accepted);
   HB_HIP(hipGetLastError());
   HB_TRY(pull(ctx, accepted, a, a.accepted, whole(ctx), &s));
-  HB_TRY(plant_launch_hybrid(ctx, a.rcmd, contact, dt, substeps, to_resident));
+  HB_TRY(plant_launch(ctx, nullptr, a.rcmd, contact, dt, substeps, to_resident));
   if (accepted) HB_HIP(hipStreamSynchronize(s));
   return HB_OK;
 }

@@ -887,14 +887,53 @@ __global__ __launch_bounds__(64) void k_plant(PlantBatch p, const DevModel* __re
              p.lambda + 12 * i, p.vdot + 16 * i);
   if (cx.lane == 0) plant_publish(p, M, i, dt, res_rbd, res_x0, res_t);
 }
-// Contact model 1 (hb_contact.hpp): the commanded flags are recorded for hb_plant_sense and play no part in the dynamics.
-__global__ __launch_bounds__(64) void k_plant_contact(PlantBatch p, ContactBatch cb, hb_contact_config K, const DevModel* __restrict__ M,
-                                                      const double* tau, const int* contact, const int* mode, double dt, int substeps,
-                                                      double* res_rbd, double* res_x0, double* res_t) {
+// ---- the hybrid actuator (hb_plant_step_hybrid / hb_plant_step_lcm): the command's law per substep ----------------------------------------
+// c: the five command arrays pos_des vel_des kp kd ff, [B][10] each; a: the record of the step.  tau_last takes the last substep's torque.
+struct ActuatorCmd {
+  const double* a[5];
+};
+__device__ __forceinline__ HybridActuator actuator_of(const ActuatorCmd& c, const ActuatorBatch& a, int i, double* lds_act) {
+  return HybridActuator{c.a[0] + 10 * i, c.a[1] + 10 * i, c.a[2] + 10 * i, c.a[3] + 10 * i, c.a[4] + 10 * i, a.tau_first + 10 * i, a.tau_mean + 10 * i,
+                        lds_act, lds_act + HB_NJ};
+}
+// The lane contexts of the plant kernels: DeviceCtx under a name of its own per family, held and hybrid, so that each pair of kernels
+// instantiates plant_substep / contact_substep / joints_substep for itself.  A second caller of the instantiations another kernel uses
+// changes the code generated for THAT kernel (the inliner moves the body of a function into its only caller and clones it for several:
+// other value order, other register allocation — k_plant came out 800 instructions shorter), and their ISA is to stay what it is.
+// The level kernels and k_plant share DeviceCtx (held) and ActuatorCtx (hybrid).
+struct ActuatorCtx : DeviceCtx {};
+struct TerrainCtx : DeviceCtx {};
+struct TerrainActuatorCtx : DeviceCtx {};
+struct VariedCtx : DeviceCtx {};
+struct VariedActuatorCtx : DeviceCtx {};
+struct ProfileCtx : DeviceCtx {};
+struct ProfileActuatorCtx : DeviceCtx {};
+// ---- contact model 1 (hb_contact.hpp): ONE body for the sixteen kernels that follow; hb_forms.hpp plant_form picks among them ----------------
+// The commanded flags are recorded for hb_plant_sense and play no part in the dynamics.  A kernel passes {} / nullptr for what its form lacks.
+// Five kernels still spell their instantiation out, statement for statement: through the body one lost a load and four measured slower
+// than before; they forward like the others once their forms pass.
+//   GROUND  0: the level ground of K | 1: an inclined plane per instance, a friction coefficient per point (hb_plant_set_terrain; ter:
+//           [B][Terrain::size]) | 2: piecewise-planar ground, a facet per contact point (hb_plant_set_terrain_profile; pb: hb_layout.hpp
+//           ProfileBatch).  The instance's record is staged once per step in LDS behind the form's own arrays (and the actuator's); the
+//           working part of a profile record (hb_contact.hpp Profile) follows it there.
+//   MODEL   the DevModel the step reads.  0: the nominal *M | 1: Mvar[i] (hb_plant_set_model_variation; [B] records, hb_layout.hpp
+//           ModelVarBatch — uniform over the workgroup, so its constants stay scalar loads; without a terrain in force the host keeps the
+//           level record of the configuration in ter) | 2: Mvar ? Mvar[i] : *M, so the four profile kernels cover what the terrain and the
+//           varied kernels need eight for.  plant_publish keeps the nominal M, the controller's view.
+//   JOINTS  the joint model (hb_joints.hpp): joints_step; tau_last takes the saturated torque, the one the step integrates.
+//   HYBRID  the actuator's law per substep (c, a) in place of the held torque tau.
+template <int GROUND, int MODEL, bool JOINTS, bool HYBRID, class Ctx>
+__device__ __forceinline__ void plant_ground_step(const PlantBatch& p, const ContactBatch& cb, const JointBatch& jb, const double* ter,
+                                                  const ProfileBatch& pb, const ActuatorBatch& a, const ActuatorCmd& c, const hb_contact_config& K,
+                                                  const hb_joint_model& J, const DevModel* M, const DevModel* Mvar, const double* tau,
+                                                  const int* contact, const int* mode, double dt, int substeps, double* res_rbd, double* res_x0,
+                                                  double* res_t) {
+  constexpr int ACT = JOINTS ? JOINT_LDS_TOTAL : CONTACT_LDS_TOTAL;   // LDS: the step's arrays | the actuator's | the ground record
+  constexpr int GND = ACT + (HYBRID ? ACT_LDS : 0);
   const int i = blockIdx.x;
-  __shared__ double lds[CONTACT_LDS_TOTAL];
+  __shared__ double lds[GND + (GROUND == 1 ? TER_LDS : GROUND == 2 ? PRO_LDS : 0)];
   __shared__ int all_on[HB_NC];
-  const DeviceCtx cx;
+  const Ctx cx;
   if (cx.lane < HB_NC) {
     int flag;
     if (contact) flag = contact[4 * i + cx.lane];
@@ -902,17 +941,40 @@ __global__ __launch_bounds__(64) void k_plant_contact(PlantBatch p, ContactBatch
     p.contact_last[4 * i + cx.lane] = flag;
     all_on[cx.lane] = 1;
   }
-  if (cx.lane < HB_NJ) p.tau_last[10 * i + cx.lane] = tau[10 * i + cx.lane];
+  if constexpr (!HYBRID && !JOINTS)
+    if (cx.lane < HB_NJ) p.tau_last[10 * i + cx.lane] = tau[10 * i + cx.lane];
+  if constexpr (GROUND == 1)
+    if (cx.lane < TER_LDS) lds[GND + cx.lane] = ter[TER_LDS * i + cx.lane];
+  if constexpr (GROUND == 2)
+    for (int k = cx.lane; k < Profile::stored; k += cx.nlanes) lds[GND + k] = pb.prof[size_t(Profile::stored) * i + k];
   __syncthreads();
   const ContactOut out{cb.gap + 4 * i, cb.pvel + 12 * i, cb.res + i, cb.touching + 4 * i, cb.status + i};
-  contact_step(cx, *M, p.q + 16 * i, p.v + 16 * i, cb.imp + 12 * i, tau + 10 * i, cb.use_wrench ? cb.wrench + 6 * i : nullptr, all_on, K, p.eps, dt,
-               substeps, lds, p.lambda + 12 * i, p.vdot + 16 * i, out);
+  const ProfileIo pio{lds + GND, pb.seg + 5 * i, pb.base + Terrain::size * i};
+  const DevModel& Ms = MODEL == 1 || (MODEL == 2 && Mvar) ? Mvar[i] : *M;
+  const JointOut jout{jb.tau_applied + 10 * i, jb.friction_torque + 10 * i, jb.limit_torque + 10 * i, jb.res + i, jb.status + i};
+  const HybridActuator act = actuator_of(c, a, i, lds + ACT);
+  if constexpr (JOINTS)
+    joints_step<HYBRID, GROUND>(cx, Ms, p.q + 16 * i, p.v + 16 * i, cb.imp + 12 * i, jb.imp + 20 * i, HYBRID ? nullptr : tau + 10 * i,
+                                cb.use_wrench ? cb.wrench + 6 * i : nullptr, all_on, K, J, p.eps, dt, substeps, lds, p.lambda + 12 * i, p.vdot + 16 * i,
+                                p.tau_last + 10 * i, out, jout, HYBRID ? &act : nullptr, GROUND ? lds + GND : nullptr, GROUND == 2 ? &pio : nullptr);
+  else
+    contact_step<HYBRID, GROUND>(cx, Ms, p.q + 16 * i, p.v + 16 * i, cb.imp + 12 * i, HYBRID ? nullptr : tau + 10 * i,
+                                 cb.use_wrench ? cb.wrench + 6 * i : nullptr, all_on, K, p.eps, dt, substeps, lds, p.lambda + 12 * i, p.vdot + 16 * i, out,
+                                 HYBRID ? &act : nullptr, GROUND ? lds + GND : nullptr, GROUND == 2 ? &pio : nullptr);
+  if constexpr (HYBRID && !JOINTS)
+    if (cx.lane < HB_NJ) p.tau_last[10 * i + cx.lane] = act.tau[cx.lane];   // (the lane's own entry)
   if (cx.lane == 0) plant_publish(p, M, i, dt, res_rbd, res_x0, res_t);
 }
-// Contact model 1 with the joint model (hb_joints.hpp); tau_last takes the saturated torque, the one the step integrates.
+__global__ __launch_bounds__(64) void k_plant_contact(PlantBatch p, ContactBatch cb, hb_contact_config K, const DevModel* __restrict__ M,
+                                                      const double* tau, const int* contact, const int* mode, double dt, int substeps,
+                                                      double* res_rbd, double* res_x0, double* res_t) {
+  plant_ground_step<0, 0, false, false, DeviceCtx>(p, cb, {}, nullptr, {}, {}, {}, K, {}, M, nullptr, tau, contact, mode, dt, substeps, res_rbd, res_x0, res_t);
+}
 __global__ __launch_bounds__(64) void k_plant_joints(PlantBatch p, ContactBatch cb, JointBatch jb, hb_contact_config K, hb_joint_model J,
                                                      const DevModel* __restrict__ M, const double* tau, const int* contact, const int* mode,
                                                      double dt, int substeps, double* res_rbd, double* res_x0, double* res_t) {
+  // plant_ground_step<0, 0, true, false, DeviceCtx> written out: through the shared body this one kernel came out with one global load
+  // fewer in plant_publish, and a changed count of memory instructions is where the kernels stay as they were.
   const int i = blockIdx.x;
   __shared__ double lds[JOINT_LDS_TOTAL];
   __shared__ int all_on[HB_NC];
@@ -931,20 +993,7 @@ __global__ __launch_bounds__(64) void k_plant_joints(PlantBatch p, ContactBatch 
               all_on, K, J, p.eps, dt, substeps, lds, p.lambda + 12 * i, p.vdot + 16 * i, p.tau_last + 10 * i, out, jout);
   if (cx.lane == 0) plant_publish(p, M, i, dt, res_rbd, res_x0, res_t);
 }
-// ---- the hybrid forms of the three plant kernels (hb_plant_step_hybrid / hb_plant_step_lcm): the command's law per substep --------------
-// c: the five command arrays pos_des vel_des kp kd ff, [B][10] each; a: the record of the step.  tau_last takes the last substep's torque.
-struct ActuatorCmd {
-  const double* a[5];
-};
-// The lane context of the hybrid kernels: DeviceCtx under a name of its own, so that they instantiate plant_substep / contact_substep /
-// joints_substep for themselves.  A second caller of the instantiations the held-torque kernels use changes the code generated for
-// THOSE kernels (the inliner moves the body of a function into its only caller and clones it for several: other value order, other
-// register allocation — k_plant came out 800 instructions shorter), and their ISA is to stay what it is.
-struct ActuatorCtx : DeviceCtx {};
-__device__ __forceinline__ HybridActuator actuator_of(const ActuatorCmd& c, const ActuatorBatch& a, int i, double* lds_act) {
-  return HybridActuator{c.a[0] + 10 * i, c.a[1] + 10 * i, c.a[2] + 10 * i, c.a[3] + 10 * i, c.a[4] + 10 * i, a.tau_first + 10 * i, a.tau_mean + 10 * i,
-                        lds_act, lds_act + HB_NJ};
-}
+// the pinned stub under the hybrid actuator
 __global__ __launch_bounds__(64) void k_plant_hybrid(PlantBatch p, ActuatorBatch a, ActuatorCmd c, const DevModel* __restrict__ M, const int* contact,
                                                       const int* mode, double dt, int substeps, double* res_rbd, double* res_x0, double* res_t) {
   const int i = blockIdx.x;
@@ -966,6 +1015,7 @@ __global__ __launch_bounds__(64) void k_plant_hybrid(PlantBatch p, ActuatorBatch
 __global__ __launch_bounds__(64) void k_plant_contact_hybrid(PlantBatch p, ContactBatch cb, ActuatorBatch a, ActuatorCmd c, hb_contact_config K,
                                                               const DevModel* __restrict__ M, const int* contact, const int* mode, double dt,
                                                               int substeps, double* res_rbd, double* res_x0, double* res_t) {
+  // plant_ground_step<0, 0, false, true, ActuatorCtx> written out (timing)
   const int i = blockIdx.x;
   __shared__ double lds[CONTACT_LDS_TOTAL + ACT_LDS];
   __shared__ int all_on[HB_NC];
@@ -989,33 +1039,12 @@ __global__ __launch_bounds__(64) void k_plant_joints_hybrid(PlantBatch p, Contac
                                                              hb_contact_config K, hb_joint_model J, const DevModel* __restrict__ M, const int* contact,
                                                              const int* mode, double dt, int substeps, double* res_rbd, double* res_x0,
                                                              double* res_t) {
-  const int i = blockIdx.x;
-  __shared__ double lds[JOINT_LDS_TOTAL + ACT_LDS];
-  __shared__ int all_on[HB_NC];
-  const ActuatorCtx cx;
-  if (cx.lane < HB_NC) {
-    int flag;
-    if (contact) flag = contact[4 * i + cx.lane];
-    else { bool cf[HB_NC]; mode_flags(mode[i], cf); flag = cf[cx.lane] ? 1 : 0; }
-    p.contact_last[4 * i + cx.lane] = flag;
-    all_on[cx.lane] = 1;
-  }
-  __syncthreads();
-  const ContactOut out{cb.gap + 4 * i, cb.pvel + 12 * i, cb.res + i, cb.touching + 4 * i, cb.status + i};
-  const JointOut jout{jb.tau_applied + 10 * i, jb.friction_torque + 10 * i, jb.limit_torque + 10 * i, jb.res + i, jb.status + i};
-  const HybridActuator act = actuator_of(c, a, i, lds + JOINT_LDS_TOTAL);
-  joints_step<true>(cx, *M, p.q + 16 * i, p.v + 16 * i, cb.imp + 12 * i, jb.imp + 20 * i, nullptr, cb.use_wrench ? cb.wrench + 6 * i : nullptr, all_on, K,
-                    J, p.eps, dt, substeps, lds, p.lambda + 12 * i, p.vdot + 16 * i, p.tau_last + 10 * i, out, jout, &act);
-  if (cx.lane == 0) plant_publish(p, M, i, dt, res_rbd, res_x0, res_t);
+  plant_ground_step<0, 0, true, true, ActuatorCtx>(p, cb, jb, nullptr, {}, a, c, K, J, M, nullptr, nullptr, contact, mode, dt, substeps, res_rbd, res_x0, res_t);
 }
-// ---- the terrain forms of the four ground kernels (hb_plant_set_terrain): an inclined plane per instance, a friction coefficient per point ----
-// ter: [B][Terrain::size], the instance's record is staged in LDS behind the form's own arrays (and the actuator's).  Lane contexts of their
-// own for the reason above ActuatorCtx, one for the held forms and one for the hybrid forms.
-struct TerrainCtx : DeviceCtx {};
-struct TerrainActuatorCtx : DeviceCtx {};
 __global__ __launch_bounds__(64) void k_plant_terrain(PlantBatch p, ContactBatch cb, const double* __restrict__ ter, hb_contact_config K,
                                                       const DevModel* __restrict__ M, const double* tau, const int* contact, const int* mode, double dt,
                                                       int substeps, double* res_rbd, double* res_x0, double* res_t) {
+  // plant_ground_step<1, 0, false, false, TerrainCtx> written out (timing)
   const int i = blockIdx.x;
   __shared__ double lds[CONTACT_LDS_TOTAL + TER_LDS];
   __shared__ int all_on[HB_NC];
@@ -1039,30 +1068,13 @@ __global__ __launch_bounds__(64) void k_plant_terrain_joints(PlantBatch p, Conta
                                                              hb_contact_config K, hb_joint_model J, const DevModel* __restrict__ M, const double* tau,
                                                              const int* contact, const int* mode, double dt, int substeps, double* res_rbd,
                                                              double* res_x0, double* res_t) {
-  const int i = blockIdx.x;
-  __shared__ double lds[JOINT_LDS_TOTAL + TER_LDS];
-  __shared__ int all_on[HB_NC];
-  const TerrainCtx cx;
-  if (cx.lane < HB_NC) {
-    int flag;
-    if (contact) flag = contact[4 * i + cx.lane];
-    else { bool cf[HB_NC]; mode_flags(mode[i], cf); flag = cf[cx.lane] ? 1 : 0; }
-    p.contact_last[4 * i + cx.lane] = flag;
-    all_on[cx.lane] = 1;
-  }
-  if (cx.lane < TER_LDS) lds[JOINT_LDS_TOTAL + cx.lane] = ter[TER_LDS * i + cx.lane];
-  __syncthreads();
-  const ContactOut out{cb.gap + 4 * i, cb.pvel + 12 * i, cb.res + i, cb.touching + 4 * i, cb.status + i};
-  const JointOut jout{jb.tau_applied + 10 * i, jb.friction_torque + 10 * i, jb.limit_torque + 10 * i, jb.res + i, jb.status + i};
-  joints_step<false, true>(cx, *M, p.q + 16 * i, p.v + 16 * i, cb.imp + 12 * i, jb.imp + 20 * i, tau + 10 * i, cb.use_wrench ? cb.wrench + 6 * i : nullptr,
-                           all_on, K, J, p.eps, dt, substeps, lds, p.lambda + 12 * i, p.vdot + 16 * i, p.tau_last + 10 * i, out, jout, nullptr,
-                           lds + JOINT_LDS_TOTAL);
-  if (cx.lane == 0) plant_publish(p, M, i, dt, res_rbd, res_x0, res_t);
+  plant_ground_step<1, 0, true, false, TerrainCtx>(p, cb, jb, ter, {}, {}, {}, K, J, M, nullptr, tau, contact, mode, dt, substeps, res_rbd, res_x0, res_t);
 }
 __global__ __launch_bounds__(64) void k_plant_terrain_hybrid(PlantBatch p, ContactBatch cb, const double* __restrict__ ter, ActuatorBatch a,
                                                              ActuatorCmd c, hb_contact_config K, const DevModel* __restrict__ M, const int* contact,
                                                              const int* mode, double dt, int substeps, double* res_rbd, double* res_x0,
                                                              double* res_t) {
+  // plant_ground_step<1, 0, false, true, TerrainActuatorCtx> written out (timing)
   const int i = blockIdx.x;
   __shared__ double lds[CONTACT_LDS_TOTAL + ACT_LDS + TER_LDS];
   __shared__ int all_on[HB_NC];
@@ -1087,216 +1099,54 @@ __global__ __launch_bounds__(64) void k_plant_terrain_joints_hybrid(PlantBatch p
                                                                     ActuatorBatch a, ActuatorCmd c, hb_contact_config K, hb_joint_model J,
                                                                     const DevModel* __restrict__ M, const int* contact, const int* mode, double dt,
                                                                     int substeps, double* res_rbd, double* res_x0, double* res_t) {
-  const int i = blockIdx.x;
-  __shared__ double lds[JOINT_LDS_TOTAL + ACT_LDS + TER_LDS];
-  __shared__ int all_on[HB_NC];
-  const TerrainActuatorCtx cx;
-  if (cx.lane < HB_NC) {
-    int flag;
-    if (contact) flag = contact[4 * i + cx.lane];
-    else { bool cf[HB_NC]; mode_flags(mode[i], cf); flag = cf[cx.lane] ? 1 : 0; }
-    p.contact_last[4 * i + cx.lane] = flag;
-    all_on[cx.lane] = 1;
-  }
-  if (cx.lane < TER_LDS) lds[JOINT_LDS_TOTAL + ACT_LDS + cx.lane] = ter[TER_LDS * i + cx.lane];
-  __syncthreads();
-  const ContactOut out{cb.gap + 4 * i, cb.pvel + 12 * i, cb.res + i, cb.touching + 4 * i, cb.status + i};
-  const JointOut jout{jb.tau_applied + 10 * i, jb.friction_torque + 10 * i, jb.limit_torque + 10 * i, jb.res + i, jb.status + i};
-  const HybridActuator act = actuator_of(c, a, i, lds + JOINT_LDS_TOTAL);
-  joints_step<true, true>(cx, *M, p.q + 16 * i, p.v + 16 * i, cb.imp + 12 * i, jb.imp + 20 * i, nullptr, cb.use_wrench ? cb.wrench + 6 * i : nullptr, all_on,
-                          K, J, p.eps, dt, substeps, lds, p.lambda + 12 * i, p.vdot + 16 * i, p.tau_last + 10 * i, out, jout, &act,
-                          lds + JOINT_LDS_TOTAL + ACT_LDS);
-  if (cx.lane == 0) plant_publish(p, M, i, dt, res_rbd, res_x0, res_t);
+  plant_ground_step<1, 0, true, true, TerrainActuatorCtx>(p, cb, jb, ter, {}, a, c, K, J, M, nullptr, nullptr, contact, mode, dt, substeps, res_rbd, res_x0, res_t);
 }
-// ---- the varied forms of the four terrain kernels (hb_plant_set_model_variation): the step runs on the instance's own DevModel -----------
-// Mvar: [B] records (hb_layout.hpp ModelVarBatch); the instance's is uniform over the workgroup, so its constants stay scalar loads.  The
-// step routines take Mvar[i]; plant_publish keeps the nominal M, the controller's view.  ter: as above — without a terrain in force the host
-// keeps the level record of the configuration there.  Lane contexts of their own for the reason above ActuatorCtx.
-struct VariedCtx : DeviceCtx {};
-struct VariedActuatorCtx : DeviceCtx {};
 __global__ __launch_bounds__(64) void k_plant_varied(PlantBatch p, ContactBatch cb, const double* __restrict__ ter, hb_contact_config K,
                                                      const DevModel* __restrict__ M, const DevModel* __restrict__ Mvar, const double* tau, const int* contact,
                                                      const int* mode, double dt, int substeps, double* res_rbd, double* res_x0, double* res_t) {
-  const int i = blockIdx.x;
-  __shared__ double lds[CONTACT_LDS_TOTAL + TER_LDS];
-  __shared__ int all_on[HB_NC];
-  const VariedCtx cx;
-  if (cx.lane < HB_NC) {
-    int flag;
-    if (contact) flag = contact[4 * i + cx.lane];
-    else { bool cf[HB_NC]; mode_flags(mode[i], cf); flag = cf[cx.lane] ? 1 : 0; }
-    p.contact_last[4 * i + cx.lane] = flag;
-    all_on[cx.lane] = 1;
-  }
-  if (cx.lane < HB_NJ) p.tau_last[10 * i + cx.lane] = tau[10 * i + cx.lane];
-  if (cx.lane < TER_LDS) lds[CONTACT_LDS_TOTAL + cx.lane] = ter[TER_LDS * i + cx.lane];
-  __syncthreads();
-  const ContactOut out{cb.gap + 4 * i, cb.pvel + 12 * i, cb.res + i, cb.touching + 4 * i, cb.status + i};
-  contact_step<false, true>(cx, Mvar[i], p.q + 16 * i, p.v + 16 * i, cb.imp + 12 * i, tau + 10 * i, cb.use_wrench ? cb.wrench + 6 * i : nullptr, all_on, K,
-                            p.eps, dt, substeps, lds, p.lambda + 12 * i, p.vdot + 16 * i, out, nullptr, lds + CONTACT_LDS_TOTAL);
-  if (cx.lane == 0) plant_publish(p, M, i, dt, res_rbd, res_x0, res_t);
+  plant_ground_step<1, 1, false, false, VariedCtx>(p, cb, {}, ter, {}, {}, {}, K, {}, M, Mvar, tau, contact, mode, dt, substeps, res_rbd, res_x0, res_t);
 }
 __global__ __launch_bounds__(64) void k_plant_varied_joints(PlantBatch p, ContactBatch cb, JointBatch jb, const double* __restrict__ ter, hb_contact_config K,
                                                             hb_joint_model J, const DevModel* __restrict__ M, const DevModel* __restrict__ Mvar,
                                                             const double* tau, const int* contact, const int* mode, double dt, int substeps, double* res_rbd,
                                                             double* res_x0, double* res_t) {
-  const int i = blockIdx.x;
-  __shared__ double lds[JOINT_LDS_TOTAL + TER_LDS];
-  __shared__ int all_on[HB_NC];
-  const VariedCtx cx;
-  if (cx.lane < HB_NC) {
-    int flag;
-    if (contact) flag = contact[4 * i + cx.lane];
-    else { bool cf[HB_NC]; mode_flags(mode[i], cf); flag = cf[cx.lane] ? 1 : 0; }
-    p.contact_last[4 * i + cx.lane] = flag;
-    all_on[cx.lane] = 1;
-  }
-  if (cx.lane < TER_LDS) lds[JOINT_LDS_TOTAL + cx.lane] = ter[TER_LDS * i + cx.lane];
-  __syncthreads();
-  const ContactOut out{cb.gap + 4 * i, cb.pvel + 12 * i, cb.res + i, cb.touching + 4 * i, cb.status + i};
-  const JointOut jout{jb.tau_applied + 10 * i, jb.friction_torque + 10 * i, jb.limit_torque + 10 * i, jb.res + i, jb.status + i};
-  joints_step<false, true>(cx, Mvar[i], p.q + 16 * i, p.v + 16 * i, cb.imp + 12 * i, jb.imp + 20 * i, tau + 10 * i, cb.use_wrench ? cb.wrench + 6 * i : nullptr,
-                           all_on, K, J, p.eps, dt, substeps, lds, p.lambda + 12 * i, p.vdot + 16 * i, p.tau_last + 10 * i, out, jout, nullptr,
-                           lds + JOINT_LDS_TOTAL);
-  if (cx.lane == 0) plant_publish(p, M, i, dt, res_rbd, res_x0, res_t);
+  plant_ground_step<1, 1, true, false, VariedCtx>(p, cb, jb, ter, {}, {}, {}, K, J, M, Mvar, tau, contact, mode, dt, substeps, res_rbd, res_x0, res_t);
 }
 __global__ __launch_bounds__(64) void k_plant_varied_hybrid(PlantBatch p, ContactBatch cb, const double* __restrict__ ter, ActuatorBatch a, ActuatorCmd c,
                                                             hb_contact_config K, const DevModel* __restrict__ M, const DevModel* __restrict__ Mvar,
                                                             const int* contact, const int* mode, double dt, int substeps, double* res_rbd, double* res_x0,
                                                             double* res_t) {
-  const int i = blockIdx.x;
-  __shared__ double lds[CONTACT_LDS_TOTAL + ACT_LDS + TER_LDS];
-  __shared__ int all_on[HB_NC];
-  const VariedActuatorCtx cx;
-  if (cx.lane < HB_NC) {
-    int flag;
-    if (contact) flag = contact[4 * i + cx.lane];
-    else { bool cf[HB_NC]; mode_flags(mode[i], cf); flag = cf[cx.lane] ? 1 : 0; }
-    p.contact_last[4 * i + cx.lane] = flag;
-    all_on[cx.lane] = 1;
-  }
-  if (cx.lane < TER_LDS) lds[CONTACT_LDS_TOTAL + ACT_LDS + cx.lane] = ter[TER_LDS * i + cx.lane];
-  __syncthreads();
-  const ContactOut out{cb.gap + 4 * i, cb.pvel + 12 * i, cb.res + i, cb.touching + 4 * i, cb.status + i};
-  const HybridActuator act = actuator_of(c, a, i, lds + CONTACT_LDS_TOTAL);
-  contact_step<true, true>(cx, Mvar[i], p.q + 16 * i, p.v + 16 * i, cb.imp + 12 * i, nullptr, cb.use_wrench ? cb.wrench + 6 * i : nullptr, all_on, K, p.eps,
-                           dt, substeps, lds, p.lambda + 12 * i, p.vdot + 16 * i, out, &act, lds + CONTACT_LDS_TOTAL + ACT_LDS);
-  if (cx.lane < HB_NJ) p.tau_last[10 * i + cx.lane] = act.tau[cx.lane];   // (the lane's own entry)
-  if (cx.lane == 0) plant_publish(p, M, i, dt, res_rbd, res_x0, res_t);
+  plant_ground_step<1, 1, false, true, VariedActuatorCtx>(p, cb, {}, ter, {}, a, c, K, {}, M, Mvar, nullptr, contact, mode, dt, substeps, res_rbd, res_x0, res_t);
 }
 __global__ __launch_bounds__(64) void k_plant_varied_joints_hybrid(PlantBatch p, ContactBatch cb, JointBatch jb, const double* __restrict__ ter,
                                                                    ActuatorBatch a, ActuatorCmd c, hb_contact_config K, hb_joint_model J,
                                                                    const DevModel* __restrict__ M, const DevModel* __restrict__ Mvar, const int* contact,
                                                                    const int* mode, double dt, int substeps, double* res_rbd, double* res_x0, double* res_t) {
-  const int i = blockIdx.x;
-  __shared__ double lds[JOINT_LDS_TOTAL + ACT_LDS + TER_LDS];
-  __shared__ int all_on[HB_NC];
-  const VariedActuatorCtx cx;
-  if (cx.lane < HB_NC) {
-    int flag;
-    if (contact) flag = contact[4 * i + cx.lane];
-    else { bool cf[HB_NC]; mode_flags(mode[i], cf); flag = cf[cx.lane] ? 1 : 0; }
-    p.contact_last[4 * i + cx.lane] = flag;
-    all_on[cx.lane] = 1;
-  }
-  if (cx.lane < TER_LDS) lds[JOINT_LDS_TOTAL + ACT_LDS + cx.lane] = ter[TER_LDS * i + cx.lane];
-  __syncthreads();
-  const ContactOut out{cb.gap + 4 * i, cb.pvel + 12 * i, cb.res + i, cb.touching + 4 * i, cb.status + i};
-  const JointOut jout{jb.tau_applied + 10 * i, jb.friction_torque + 10 * i, jb.limit_torque + 10 * i, jb.res + i, jb.status + i};
-  const HybridActuator act = actuator_of(c, a, i, lds + JOINT_LDS_TOTAL);
-  joints_step<true, true>(cx, Mvar[i], p.q + 16 * i, p.v + 16 * i, cb.imp + 12 * i, jb.imp + 20 * i, nullptr, cb.use_wrench ? cb.wrench + 6 * i : nullptr, all_on,
-                          K, J, p.eps, dt, substeps, lds, p.lambda + 12 * i, p.vdot + 16 * i, p.tau_last + 10 * i, out, jout, &act,
-                          lds + JOINT_LDS_TOTAL + ACT_LDS);
-  if (cx.lane == 0) plant_publish(p, M, i, dt, res_rbd, res_x0, res_t);
+  plant_ground_step<1, 1, true, true, VariedActuatorCtx>(p, cb, jb, ter, {}, a, c, K, J, M, Mvar, nullptr, contact, mode, dt, substeps, res_rbd, res_x0, res_t);
 }
-// ---- the profile forms of the four ground kernels (hb_plant_set_terrain_profile): piecewise-planar ground, a facet per contact point -------
-// pb: hb_layout.hpp ProfileBatch; the instance's stored record is staged once per step in LDS behind the form's own arrays (and the
-// actuator's), the working part of the record (hb_contact.hpp Profile) follows it there.  Mvar: the [B] records of a model variation in
-// force, or null: the step runs on the instance's own DevModel or on the nominal one, so these four cover what the terrain and the varied
-// forms need eight for.  Lane contexts of their own for the reason above ActuatorCtx.
-struct ProfileCtx : DeviceCtx {};
-struct ProfileActuatorCtx : DeviceCtx {};
 __global__ __launch_bounds__(64) void k_plant_profile(PlantBatch p, ContactBatch cb, ProfileBatch pb, hb_contact_config K, const DevModel* __restrict__ M,
                                                       const DevModel* __restrict__ Mvar, const double* tau, const int* contact, const int* mode, double dt,
                                                       int substeps, double* res_rbd, double* res_x0, double* res_t) {
-  const int i = blockIdx.x;
-  __shared__ double lds[CONTACT_LDS_TOTAL + PRO_LDS];
-  __shared__ int all_on[HB_NC];
-  const ProfileCtx cx;
-  if (cx.lane < HB_NC) {
-    int flag;
-    if (contact) flag = contact[4 * i + cx.lane];
-    else { bool cf[HB_NC]; mode_flags(mode[i], cf); flag = cf[cx.lane] ? 1 : 0; }
-    p.contact_last[4 * i + cx.lane] = flag;
-    all_on[cx.lane] = 1;
-  }
-  if (cx.lane < HB_NJ) p.tau_last[10 * i + cx.lane] = tau[10 * i + cx.lane];
-  for (int k = cx.lane; k < Profile::stored; k += cx.nlanes) lds[CONTACT_LDS_TOTAL + k] = pb.prof[size_t(Profile::stored) * i + k];
-  __syncthreads();
-  const ContactOut out{cb.gap + 4 * i, cb.pvel + 12 * i, cb.res + i, cb.touching + 4 * i, cb.status + i};
-  const ProfileIo pio{lds + CONTACT_LDS_TOTAL, pb.seg + 5 * i, pb.base + Terrain::size * i};
-  const DevModel& Ms = Mvar ? Mvar[i] : *M;
-  contact_step<false, 2>(cx, Ms, p.q + 16 * i, p.v + 16 * i, cb.imp + 12 * i, tau + 10 * i, cb.use_wrench ? cb.wrench + 6 * i : nullptr, all_on, K,
-                         p.eps, dt, substeps, lds, p.lambda + 12 * i, p.vdot + 16 * i, out, nullptr, pio.pro, &pio);
-  if (cx.lane == 0) plant_publish(p, M, i, dt, res_rbd, res_x0, res_t);
+  plant_ground_step<2, 2, false, false, ProfileCtx>(p, cb, {}, nullptr, pb, {}, {}, K, {}, M, Mvar, tau, contact, mode, dt, substeps, res_rbd, res_x0, res_t);
 }
 __global__ __launch_bounds__(64) void k_plant_profile_joints(PlantBatch p, ContactBatch cb, JointBatch jb, ProfileBatch pb, hb_contact_config K,
                                                              hb_joint_model J, const DevModel* __restrict__ M, const DevModel* __restrict__ Mvar,
                                                              const double* tau, const int* contact, const int* mode, double dt, int substeps,
                                                              double* res_rbd, double* res_x0, double* res_t) {
-  const int i = blockIdx.x;
-  __shared__ double lds[JOINT_LDS_TOTAL + PRO_LDS];
-  __shared__ int all_on[HB_NC];
-  const ProfileCtx cx;
-  if (cx.lane < HB_NC) {
-    int flag;
-    if (contact) flag = contact[4 * i + cx.lane];
-    else { bool cf[HB_NC]; mode_flags(mode[i], cf); flag = cf[cx.lane] ? 1 : 0; }
-    p.contact_last[4 * i + cx.lane] = flag;
-    all_on[cx.lane] = 1;
-  }
-  for (int k = cx.lane; k < Profile::stored; k += cx.nlanes) lds[JOINT_LDS_TOTAL + k] = pb.prof[size_t(Profile::stored) * i + k];
-  __syncthreads();
-  const ContactOut out{cb.gap + 4 * i, cb.pvel + 12 * i, cb.res + i, cb.touching + 4 * i, cb.status + i};
-  const ProfileIo pio{lds + JOINT_LDS_TOTAL, pb.seg + 5 * i, pb.base + Terrain::size * i};
-  const DevModel& Ms = Mvar ? Mvar[i] : *M;
-  const JointOut jout{jb.tau_applied + 10 * i, jb.friction_torque + 10 * i, jb.limit_torque + 10 * i, jb.res + i, jb.status + i};
-  joints_step<false, 2>(cx, Ms, p.q + 16 * i, p.v + 16 * i, cb.imp + 12 * i, jb.imp + 20 * i, tau + 10 * i, cb.use_wrench ? cb.wrench + 6 * i : nullptr,
-                        all_on, K, J, p.eps, dt, substeps, lds, p.lambda + 12 * i, p.vdot + 16 * i, p.tau_last + 10 * i, out, jout, nullptr, pio.pro,
-                        &pio);
-  if (cx.lane == 0) plant_publish(p, M, i, dt, res_rbd, res_x0, res_t);
+  plant_ground_step<2, 2, true, false, ProfileCtx>(p, cb, jb, nullptr, pb, {}, {}, K, J, M, Mvar, tau, contact, mode, dt, substeps, res_rbd, res_x0, res_t);
 }
 __global__ __launch_bounds__(64) void k_plant_profile_hybrid(PlantBatch p, ContactBatch cb, ProfileBatch pb, ActuatorBatch a, ActuatorCmd c,
                                                              hb_contact_config K, const DevModel* __restrict__ M, const DevModel* __restrict__ Mvar,
                                                              const int* contact, const int* mode, double dt, int substeps, double* res_rbd,
                                                              double* res_x0, double* res_t) {
-  const int i = blockIdx.x;
-  __shared__ double lds[CONTACT_LDS_TOTAL + ACT_LDS + PRO_LDS];
-  __shared__ int all_on[HB_NC];
-  const ProfileActuatorCtx cx;
-  if (cx.lane < HB_NC) {
-    int flag;
-    if (contact) flag = contact[4 * i + cx.lane];
-    else { bool cf[HB_NC]; mode_flags(mode[i], cf); flag = cf[cx.lane] ? 1 : 0; }
-    p.contact_last[4 * i + cx.lane] = flag;
-    all_on[cx.lane] = 1;
-  }
-  for (int k = cx.lane; k < Profile::stored; k += cx.nlanes) lds[CONTACT_LDS_TOTAL + ACT_LDS + k] = pb.prof[size_t(Profile::stored) * i + k];
-  __syncthreads();
-  const ContactOut out{cb.gap + 4 * i, cb.pvel + 12 * i, cb.res + i, cb.touching + 4 * i, cb.status + i};
-  const ProfileIo pio{lds + CONTACT_LDS_TOTAL + ACT_LDS, pb.seg + 5 * i, pb.base + Terrain::size * i};
-  const DevModel& Ms = Mvar ? Mvar[i] : *M;
-  const HybridActuator act = actuator_of(c, a, i, lds + CONTACT_LDS_TOTAL);
-  contact_step<true, 2>(cx, Ms, p.q + 16 * i, p.v + 16 * i, cb.imp + 12 * i, nullptr, cb.use_wrench ? cb.wrench + 6 * i : nullptr, all_on, K, p.eps, dt,
-                        substeps, lds, p.lambda + 12 * i, p.vdot + 16 * i, out, &act, pio.pro, &pio);
-  if (cx.lane < HB_NJ) p.tau_last[10 * i + cx.lane] = act.tau[cx.lane];   // (the lane's own entry)
-  if (cx.lane == 0) plant_publish(p, M, i, dt, res_rbd, res_x0, res_t);
+  plant_ground_step<2, 2, false, true, ProfileActuatorCtx>(p, cb, {}, nullptr, pb, a, c, K, {}, M, Mvar, nullptr, contact, mode, dt, substeps, res_rbd, res_x0, res_t);
 }
 __global__ __launch_bounds__(64) void k_plant_profile_joints_hybrid(PlantBatch p, ContactBatch cb, JointBatch jb, ProfileBatch pb, ActuatorBatch a,
                                                                     ActuatorCmd c, hb_contact_config K, hb_joint_model J,
                                                                     const DevModel* __restrict__ M, const DevModel* __restrict__ Mvar,
                                                                     const int* contact, const int* mode, double dt, int substeps, double* res_rbd,
                                                                     double* res_x0, double* res_t) {
+  // plant_ground_step<2, 2, true, true, ProfileActuatorCtx> written out (timing)
   const int i = blockIdx.x;
   __shared__ double lds[JOINT_LDS_TOTAL + ACT_LDS + PRO_LDS];
   __shared__ int all_on[HB_NC];

@@ -1,5 +1,6 @@
 // TEST HARNESS: the hybrid forms of the three plant step wrappers (hb_plant.hpp plant_step, hb_contact.hpp contact_step, hb_joints.hpp
-// joints_step with the HybridActuator: the routines k_plant_hybrid / k_plant_contact_hybrid / k_plant_joints_hybrid run per instance) and
+// joints_step with the HybridActuator: the routines k_plant_hybrid / k_plant_contact_hybrid / k_plant_joints_hybrid run per instance, the last two as HYBRID forms
+// of the shared body hb_kernels.hip plant_ground_step) and
 // the per-item routines of the three wire kernels of the simulator end (hb_lcm.hpp), compiled for the host with one emulated lane, for
 // tests/test_actuator_plant_host.py.  Not part of the product; the product path always runs the kernels.
 #include <cstddef>

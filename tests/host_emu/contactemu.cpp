@@ -1,4 +1,5 @@
-// TEST HARNESS: the ground-contact model of the plant (hb_contact.hpp: the routine k_plant_contact runs per instance) compiled for the
+// TEST HARNESS: the ground-contact model of the plant (hb_contact.hpp: the routine the kernels of contact model 1 run per instance
+// through their shared body, hb_kernels.hip plant_ground_step; k_plant_contact is the form without ground record or joints) compiled for the
 // host with one emulated lane, for tests/test_contact_plant_host.py.  Not part of the product; the product path always runs the kernel.
 #include <cstddef>
 #include <cstdint>

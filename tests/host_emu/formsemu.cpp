@@ -4,8 +4,12 @@
 //                     before the header existed (copied verbatim below: `sel` is hb_config.reserved, HB_ABLATE_ON the build), for
 //                     both builds, over reserved in -1 .. 260 and a grid of (concurrent, Nmax, n_cu); prints "checked N" and
 //                     "mismatch ..." lines, exit status 1 if any.
+//   formsemu plant    compares plant_form, mapped to a kernel name the way plant_launch's switch does, with the two ladders of
+//                     hb_api_est.hpp it replaces (their conditions copied verbatim below), over contact mode 0 / 1, the sixteen
+//                     combinations of joints / terrain / variation / profile and held / hybrid; same output as check.
 #include <cstdio>
 #include <cstring>
+#include <string>
 #include "../../hunter_bipedal_control_amd/csrc/hb_forms.hpp"
 
 namespace before {   // the thresholds and the expressions as they stood in hb_kernels.hip / hb_api_mpc.hpp
@@ -26,7 +30,43 @@ int lq_trip_len(int sel, int concurrent, int Nmax, int n_cu) {
 }
 bool one_node(int sel) { return sel == 129; }
 bool fwd_wave(int sel, int concurrent) { return sel == 114 || (sel != 111 && concurrent <= kRicFwdWaveMaxBatch); }
+
+// The plant: the conditions of the two ladders hb_plant_step and plant_launch_hybrid held (hb_api_est.hpp), rung by rung in their order;
+// a rung returns the name of the kernel it launched.  `ctx` carries the five words of the context the rungs read.
+struct Ctx { struct { int mode; } contact_cfg; bool joints_on, terrain_on, modelvar_on, profile_on; };
+const char* plant_step(const Ctx* ctx) {
+  if (ctx->contact_cfg.mode == 1 && ctx->profile_on && ctx->joints_on) return "k_plant_profile_joints";
+  if (ctx->contact_cfg.mode == 1 && ctx->profile_on) return "k_plant_profile";
+  if (ctx->contact_cfg.mode == 1 && ctx->modelvar_on && ctx->joints_on) return "k_plant_varied_joints";
+  if (ctx->contact_cfg.mode == 1 && ctx->modelvar_on) return "k_plant_varied";
+  if (ctx->contact_cfg.mode == 1 && ctx->terrain_on && ctx->joints_on) return "k_plant_terrain_joints";
+  if (ctx->contact_cfg.mode == 1 && ctx->terrain_on) return "k_plant_terrain";
+  if (ctx->contact_cfg.mode == 1 && ctx->joints_on) return "k_plant_joints";
+  if (ctx->contact_cfg.mode == 1) return "k_plant_contact";
+  return "k_plant";
+}
+const char* plant_launch_hybrid(const Ctx* ctx) {
+  if (ctx->contact_cfg.mode == 1 && ctx->profile_on && ctx->joints_on) return "k_plant_profile_joints_hybrid";
+  if (ctx->contact_cfg.mode == 1 && ctx->profile_on) return "k_plant_profile_hybrid";
+  if (ctx->contact_cfg.mode == 1 && ctx->modelvar_on && ctx->joints_on) return "k_plant_varied_joints_hybrid";
+  if (ctx->contact_cfg.mode == 1 && ctx->modelvar_on) return "k_plant_varied_hybrid";
+  if (ctx->contact_cfg.mode == 1 && ctx->terrain_on && ctx->joints_on) return "k_plant_terrain_joints_hybrid";
+  if (ctx->contact_cfg.mode == 1 && ctx->terrain_on) return "k_plant_terrain_hybrid";
+  if (ctx->contact_cfg.mode == 1 && ctx->joints_on) return "k_plant_joints_hybrid";
+  if (ctx->contact_cfg.mode == 1) return "k_plant_contact_hybrid";
+  return "k_plant_hybrid";
+}
 }  // namespace before
+
+// The kernel plant_launch (hb_api_est.hpp) launches for a form: its switch, by name.
+static std::string plant_kernel(const hb::PlantForm& f) {
+  using G = hb::PlantForm::Ground;
+  const char* tail = f.hybrid ? "_hybrid" : "";
+  if (f.ground == G::Pinned) return std::string("k_plant") + tail;
+  if (f.ground == G::Level) return std::string(f.joints ? "k_plant_joints" : "k_plant_contact") + tail;
+  const char* family = f.ground == G::Terrain ? "k_plant_terrain" : f.ground == G::Varied ? "k_plant_varied" : "k_plant_profile";
+  return std::string(family) + (f.joints ? "_joints" : "") + tail;
+}
 
 int main(int argc, char** argv) {
   if (argc == 2 && !std::strcmp(argv[1], "table")) {
@@ -35,6 +75,21 @@ int main(int argc, char** argv) {
       else std::printf("range %s %d %d\n", e.name, e.first, e.last);
     }
     return 0;
+  }
+  if (argc == 2 && !std::strcmp(argv[1], "plant")) {
+    long checked = 0, bad = 0;
+    for (int mode = 0; mode <= 1; ++mode)
+      for (int flags = 0; flags < 16; ++flags)
+        for (int hybrid = 0; hybrid <= 1; ++hybrid) {
+          const before::Ctx c{{mode}, (flags & 1) != 0, (flags & 2) != 0, (flags & 4) != 0, (flags & 8) != 0};
+          const std::string was = hybrid ? before::plant_launch_hybrid(&c) : before::plant_step(&c);
+          const std::string is = plant_kernel(hb::plant_form(mode, c.joints_on, c.terrain_on, c.modelvar_on, c.profile_on, hybrid != 0));
+          ++checked;
+          if (was != is && ++bad) std::printf("mismatch mode %d joints %d terrain %d modelvar %d profile %d hybrid %d: %s, was %s\n", mode, c.joints_on,
+                                              c.terrain_on, c.modelvar_on, c.profile_on, hybrid, is.c_str(), was.c_str());
+        }
+    std::printf("checked %ld\n", checked);
+    return bad ? 1 : 0;
   }
   if (argc != 2 || std::strcmp(argv[1], "check")) return 2;
   const int concurrents[] = {1, 511, 512, 513, 1024, 2047, 2048, 4096}, nmaxs[] = {1, 44, 100, 108, 200}, ncus[] = {64, 256};

@@ -1,4 +1,5 @@
-// TEST HARNESS: the joint model of the ground-contact plant (hb_joints.hpp: the routine k_plant_joints runs per instance) compiled for the
+// TEST HARNESS: the joint model of the ground-contact plant (hb_joints.hpp: the routine the JOINTS forms of the shared kernel body run per
+// instance, hb_kernels.hip plant_ground_step; k_plant_joints is the form on level ground) compiled for the
 // host with one emulated lane, for tests/test_joint_plant_host.py.  Not part of the product; the product path always runs the kernel.
 #include <cstddef>
 #include <cstdint>

@@ -1,5 +1,6 @@
 // TEST HARNESS: the profile forms of the ground-contact step routines (hb_contact.hpp contact_step, hb_joints.hpp joints_step with TERRAIN 2:
-// the routines k_plant_profile / k_plant_profile_joints and their hybrid forms run per instance) compiled for the host with one emulated
+// the routines k_plant_profile / k_plant_profile_joints and their hybrid forms run per instance: GROUND 2 of the shared body hb_kernels.hip
+// plant_ground_step) compiled for the host with one emulated
 // lane, for tests/test_profile_plant_host.py.  pro = the instance's stored Profile record (pe_record builds it with the host setter's
 // routine).  Not part of the product; the product path always runs the kernels.
 #include <cstddef>

@@ -1,5 +1,6 @@
 // TEST HARNESS: the terrain forms of the ground-contact step routines (hb_contact.hpp contact_step, hb_joints.hpp joints_step with TERRAIN:
-// the routines k_plant_terrain / k_plant_terrain_joints and their hybrid forms run per instance) compiled for the host with one emulated
+// the routines k_plant_terrain / k_plant_terrain_joints and their hybrid forms run per instance: GROUND 1 of the shared body hb_kernels.hip
+// plant_ground_step) compiled for the host with one emulated
 // lane, for tests/test_terrain_plant_host.py.  ter = the instance's Terrain record (T row-major | d | mu of the four points), or null for
 // the routines without a terrain.  Not part of the product; the product path always runs the kernels.
 #include <cstddef>

@@ -5,6 +5,10 @@ the launchers of hb_api_mpc.hpp held before the header existed (backward-sweep c
 choice), for the release and the profiling build, over every combination of hb_config.reserved in -1 .. 260, concurrent in
 {1, 511, 512, 513, 1024, 2047, 2048, 4096}, Nmax in {1, 44, 100, 108, 200} and n_cu in {64, 256}.
 
+The plant's rule — plant_form, mapped to the kernel plant_launch launches for it — against verbatim copies of the conditions of the two
+nine-rung ladders hb_plant_step and plant_launch_hybrid held, over contact mode 0 / 1, every combination of joints_on, terrain_on,
+modelvar_on and profile_on, and held / hybrid drive.
+
 The table — every code a site of the library reads, the families of selectors by their bounds — against abi.py's hand-written mirror.
 (LQT_VALUES .. LQT_VALUES_LEGS, 126 .. 128, are single codes: the kernels read each of them on its own, and the first and the last
 name the bounds of the one site that reads them as an interval.)"""
@@ -38,6 +42,12 @@ def test_selection_rules_agree_with_the_expressions_they_replace(formsemu):
     r = subprocess.run([str(formsemu), "check"], capture_output=True, text=True)
     assert r.returncode == 0, r.stdout
     assert r.stdout.strip() == f"checked {262 * 2 * 8 * 5 * 2}"
+
+
+def test_plant_form_agrees_with_the_ladders_it_replaces(formsemu):
+    r = subprocess.run([str(formsemu), "plant"], capture_output=True, text=True)
+    assert r.returncode == 0, r.stdout
+    assert r.stdout.strip() == f"checked {2 * 2 ** 4 * 2}"
 
 
 def test_table_equals_the_python_mirror(table):
