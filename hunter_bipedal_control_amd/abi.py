@@ -71,7 +71,7 @@ _RIC4 = dict(RIC4_STAGING=24, RIC4_GEMM1=25, RIC4_GEMM2=26, RIC4_FACTOR=27)    #
 _HWBC = dict(HWBC_LEVEL0=41, HWBC_KERNEL0=43, HWBC_QP1=44, HWBC_LEVEL1=42)
 FORMS = dict(NONE=0, **_LQ, **_WBC, **_RIC1, **_RIC4, **_HWBC, RIC_BWD_ONE=101, RIC_BWD_FOUR=104, RIC_FWD_ROW=111, RIC_FWD_WAVE=114,
              LQT_ONE_RECORD=117, LQT_TRACE=118, LQT_PARK_NOTHING=119, LQT_VALUES_ONCE=125, LQT_VALUES=126, LQT_VALUES_FWD=127,
-             LQT_VALUES_LEGS=128, LQ_ONE_NODE=129, RIC1_TRACE=197, WBC_TRACE=198, RIC4_TRACE=199)
+             LQT_VALUES_LEGS=128, LQ_ONE_NODE=129, LS_EVAL_NODE=151, RIC1_TRACE=197, WBC_TRACE=198, RIC4_TRACE=199)
 FORM_RANGES = dict(LQ_TRIP_POW2=(120, 124), LQ_TRIP_LEN=(131, 146))   # LQ trips of 2^(value - first) / of value - first + 1 nodes
 FORM = SimpleNamespace(**FORMS)
 LQ_STOPS, WBC_STOPS, RIC1_STOPS, RIC4_STOPS, HWBC_STOPS = (tuple(d.values()) for d in (_LQ, _WBC, _RIC1, _RIC4, _HWBC))

@@ -33,6 +33,8 @@ struct hb_ctx {
   DevModel* dmodel = nullptr;
   DevConfig* dconfig = nullptr;
   Batch b{};
+  LsList lslist{};   // the line search's list of refused instances, per instance range (hb_layout.hpp)
+  int ls_per = 0;    // instances per range of the last MPC call (the whole batch on one stream: B): its counters are the slots 0, ls_per, ...
   hipStream_t s_mpc = nullptr, s_wbc = nullptr;
   hipEvent_t ev[EV_COUNT]{};
   hipEvent_t ev_sync[SYNC_COUNT]{};
@@ -440,7 +442,9 @@ int32_t hb_create(const hb_model* model, const hb_config* config, int32_t batch,
   const char* what = "ctx->dmodel";
   if ((e = dalloc(ctx, &ctx->dmodel, 1)) != hipSuccess) return fail(what, e);
   if ((e = dalloc(ctx, &ctx->dconfig, 1)) != hipSuccess) return fail("ctx->dconfig", e);
-  if ((e = alloc_fields(ctx, b, &what)) != hipSuccess || (e = alloc_fields(ctx, w, &what)) != hipSuccess) return fail(what, e);
+  if ((e = alloc_fields(ctx, b, &what)) != hipSuccess || (e = alloc_fields(ctx, w, &what)) != hipSuccess ||
+      (e = alloc_fields(ctx, ctx->lslist, &what)) != hipSuccess)
+    return fail(what, e);
   if ((e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_hwbc), hipFuncAttributeMaxDynamicSharedMemorySize,
                                int(HoLdsDev::total * sizeof(double)))) != hipSuccess)
     return fail("k_hwbc LDS size", e);

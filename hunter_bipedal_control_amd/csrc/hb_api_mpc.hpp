@@ -149,9 +149,14 @@ static void launch_ric_fwd(hb_ctx* ctx, const Batch& b, int B, int concurrent, h
   else hipLaunchKernelGGL(k_ric_fwd, dim3(B), dim3(64), 0, s, b);
 }
 
-// The SQP iterations of the instances of b on s; `timed`: iteration 0 records the phase events ev[EV_LQ_BEGIN .. EV_LS_END].
-static int32_t enqueue_sqp(hb_ctx* ctx, const Batch& b, hipStream_t s, bool timed) {
+// The SQP iterations of the instances of b (the view of the batch from instance i0 on) on s; `timed`: iteration 0 records the phase
+// events ev[EV_LQ_BEGIN .. EV_LS_END].
+static int32_t enqueue_sqp(hb_ctx* ctx, const Batch& b, int i0, hipStream_t s, bool timed) {
   const int B = b.B, N = ctx->Nmax;
+  const LsList ls = from_instance(ctx->lslist, N, i0);
+  const bool ls_node = ctx->forms.ls == KernelForms::Ls::Node;
+  // k_ls_tail_eval walks its work list on a bounded grid: eight workgroups per CU are resident (two wavefronts per SIMD)
+  const unsigned tail_grid = unsigned(std::min<long>(8L * ctx->n_cu, long(B) * ((N + 31) / 32) * LS_TAIL_MAX));
   for (int it = 0; it < ctx->config.sqp_iterations; ++it) {
     const bool mark = timed && it == 0;
     hipLaunchKernelGGL(k_set_x0, dim3((B * HB_NX + 255) / 256), dim3(256), 0, s, b);
@@ -163,8 +168,10 @@ static int32_t enqueue_sqp(hb_ctx* ctx, const Batch& b, hipStream_t s, bool time
     launch_ric_fwd(ctx, b, B, ctx->B, s);
     if (mark) HB_HIP(hipEventRecord(ctx->ev[EV_RIC_FWD_END], s));
     // filter line search: the full step for every instance, node-parallel; then the backtracking tail in one launch
-    hipLaunchKernelGGL(k_ls_eval, dim3((B * N + 63) / 64), dim3(64), 0, s, b, ctx->dmodel, ctx->dconfig, 1.0);
-    hipLaunchKernelGGL(k_ls_decide, dim3(B), dim3(64), 0, s, b, ctx->dconfig, 1.0);
+    // (the refused instances go to the list ls, which the tail walks; the thread-per-node form of the tail does not read it)
+    if (ls_node) hipLaunchKernelGGL(k_ls_eval_node, dim3((B * N + 63) / 64), dim3(64), 0, s, b, ls, ctx->dmodel, ctx->dconfig, 1.0);
+    else hipLaunchKernelGGL(k_ls_eval, dim3((B * N + 31) / 32), dim3(64), 0, s, b, ls, ctx->dmodel, ctx->dconfig, 1.0);
+    hipLaunchKernelGGL(k_ls_decide, dim3(B), dim3(64), 0, s, b, ls, ctx->dconfig, 1.0);
     if (ctx->config.alpha_decay > 0.0 && ctx->config.alpha_decay < 1.0 && ctx->config.alpha_decay >= ctx->config.alpha_min) {
       // step sizes alpha_decay^1, ^2, ... >= alpha_min, in windows of LS_TAIL_MAX = 16 evaluated side by side (the shipped 0.5 / 1e-4
       // makes 13: one window).  A slower decay (0.9 / 1e-4: 88 step sizes) walks on window after window down to alpha_min as OCS2's
@@ -175,8 +182,12 @@ static int32_t enqueue_sqp(hb_ctx* ctx, const Batch& b, hipStream_t s, bool time
         int n_alpha = 0;
         double a = a_win;
         for (; a >= ctx->config.alpha_min && n_alpha < LS_TAIL_MAX; a *= ctx->config.alpha_decay) ++n_alpha;
-        hipLaunchKernelGGL(k_ls_tail_eval, dim3((B * N + 63) / 64, n_alpha), dim3(64), 0, s, b, ctx->dmodel, ctx->dconfig, a_win,
-                           ctx->config.alpha_decay, ctx->config.alpha_min);
+        if (ls_node)
+          hipLaunchKernelGGL(k_ls_tail_eval_node, dim3((B * N + 63) / 64, n_alpha), dim3(64), 0, s, b, ctx->dmodel, ctx->dconfig, a_win,
+                             ctx->config.alpha_decay, ctx->config.alpha_min);
+        else
+          hipLaunchKernelGGL(k_ls_tail_eval, dim3(tail_grid), dim3(64), 0, s, b, ls, ctx->dmodel, ctx->dconfig, a_win, ctx->config.alpha_decay,
+                             ctx->config.alpha_min, n_alpha);
         hipLaunchKernelGGL(k_ls_tail_decide, dim3(B), dim3(64), 0, s, b, ctx->dconfig, a_win, ctx->config.alpha_decay,
                            ctx->config.alpha_min, n_alpha);
         a_win = a;
@@ -205,11 +216,12 @@ static int32_t mpc_solve_batch(hb_ctx* ctx) {
     HB_HIP(hipGetLastError());
     HB_HIP(hipMemsetAsync(ctx->respawn.mpc_pending, 0, size_t(ctx->B), ctx->s_mpc));
   }
-  HB_TRY(enqueue_sqp(ctx, ctx->b, ctx->s_mpc, true));
+  HB_TRY(enqueue_sqp(ctx, ctx->b, 0, ctx->s_mpc, true));
   std::lock_guard<std::mutex> lk(ctx->mtx);
   ctx->timed = true;
   ctx->stats.n_mpc_solves += ctx->B;
   ctx->mpc_solved_epoch = ctx->mpc_tables_epoch;
+  ctx->ls_per = ctx->B;
   return HB_OK;
 }
 
@@ -369,6 +381,20 @@ int32_t hb_mpc_get_linesearch(hb_ctx* ctx, int32_t inst_begin, int32_t inst_coun
   HB_TRY(pull(ctx, accepted, b, b.accepted, r, &s));
   HB_TRY(pull(ctx, ric_fail, b, b.ric_fail, r, &s));
   HB_HIP(hipStreamSynchronize(s));
+  return HB_OK;
+}
+
+// How many instances the last SQP iteration of the last MPC call put on the list of the backtracking tail: the counters of the instance
+// ranges of that call, summed.
+int32_t hb_mpc_get_linesearch_refused(hb_ctx* ctx, int32_t* count) {
+  HB_ENTER_ARGS(!count);
+  HB_TRY(mpc_records_current(ctx, "hb_mpc_get_linesearch_refused"));
+  HB_ENTER_DEVICE();
+  std::vector<int> slots(size_t(ctx->B));
+  HB_TRY(pull(ctx, slots.data(), ctx->lslist, ctx->lslist.count, whole(ctx), &ctx->s_mpc));
+  HB_HIP(hipStreamSynchronize(ctx->s_mpc));
+  *count = 0;
+  for (int i0 = 0; i0 < ctx->B; i0 += ctx->ls_per) *count += slots[size_t(i0)];
   return HB_OK;
 }
 

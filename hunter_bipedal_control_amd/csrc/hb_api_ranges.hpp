@@ -25,7 +25,7 @@ int32_t hb_set_resident_x0_sequence(hb_ctx* ctx, int32_t n_seq, const double* x0
 static int32_t enqueue_range_update(hb_ctx* ctx, int i0, int cnt, hipStream_t s) {
   const Batch b = view(ctx->b, ctx->Nmax, i0, cnt);
   const WbcBatch w = view(ctx->w, ctx->Nmax, i0, cnt);
-  HB_TRY(enqueue_sqp(ctx, b, s, false));
+  HB_TRY(enqueue_sqp(ctx, b, i0, s, false));
   launch_publish(b, w, s);
   return launch_policy_wbc(ctx, w, i0, true, nullptr, s);
 }
@@ -117,6 +117,7 @@ static void finish_ranges(hb_ctx* ctx, bool steady) {
   ctx->stats.n_wbc_solves += ctx->B;
   ctx->cert_last = ctx->wbc_cert;
   ctx->mpc_solved_epoch = ctx->mpc_tables_epoch;
+  ctx->ls_per = (ctx->B + ctx->n_chunks - 1) / ctx->n_chunks;   // (for_each_range)
 }
 
 int32_t hb_step_resident(hb_ctx* ctx, double dt) {

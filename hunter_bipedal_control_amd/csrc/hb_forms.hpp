@@ -67,6 +67,8 @@ namespace form {
   X(LQT_VALUES_FWD, 127, "k_lq_trip, lq_trip_values",     "stop: the value phase up to its forward sweep") \
   X(LQT_VALUES_LEGS, 128, "k_lq_trip, lq_trip_values",    "stop: the value phase up to its leg pass (last of LQT_VALUES ..)") \
   X(LQ_ONE_NODE,    129, "decode_forms",                  "selector: the one-node-per-wavefront kernel k_lq (differs from the trips by rounding)") \
+  /* selector of the line search */ \
+  X(LS_EVAL_NODE,   151, "decode_forms",                  "selector: thread-per-node line-search evaluation (k_ls_eval_node, k_ls_tail_eval_node; differs from the two-lane form by rounding)") \
   /* traces */ \
   X(RIC1_TRACE,     197, "k_ric_bwd",                     "trace: cycle counts of stage 50 of instance 9") \
   X(WBC_TRACE,      198, "wbc_solve, decode_forms",       "trace: cycle counts of the WeightedWbc solve of instance 5 (leaves the sweep's choice alone)") \
@@ -103,6 +105,7 @@ struct KernelForms {
   enum class Bwd { Auto, One, Four } bwd = Bwd::Auto;     // backward sweep: k_ric_bwd / k_ric_bwd4
   enum class Fwd { Auto, Row, Wave } fwd = Fwd::Auto;     // forward sweep: k_ric_fwd / k_ric_fwd_w
   enum class Lq { Trips, OneNode } lq = Lq::Trips;        // LQ approximation: k_lq_trip / k_lq
+  enum class Ls { Pair, Node } ls = Ls::Pair;             // line-search evaluation: k_ls_eval, k_ls_tail_eval / k_ls_eval_node, k_ls_tail_eval_node
   int trip_len = 0;                                       // nodes per trip of k_lq_trip, forced; 0: by the batch
 };
 
@@ -118,6 +121,7 @@ inline KernelForms decode_forms(int reserved, bool ablate) {
   if (reserved == RIC_FWD_WAVE) f.fwd = KernelForms::Fwd::Wave;
   else if (reserved == RIC_FWD_ROW) f.fwd = KernelForms::Fwd::Row;
   if (reserved == LQ_ONE_NODE) f.lq = KernelForms::Lq::OneNode;
+  if (reserved == LS_EVAL_NODE) f.ls = KernelForms::Ls::Node;
   if (reserved >= LQ_TRIP_POW2_FIRST && reserved <= LQ_TRIP_POW2_LAST) f.trip_len = 1 << (reserved - LQ_TRIP_POW2_FIRST);
   if (reserved >= LQ_TRIP_LEN_FIRST && reserved <= LQ_TRIP_LEN_LAST) f.trip_len = reserved - LQ_TRIP_LEN_FIRST + 1;   // (launch-geometry sweeps)
   return f;

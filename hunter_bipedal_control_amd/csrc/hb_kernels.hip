@@ -650,10 +650,61 @@ __global__ __launch_bounds__(64) void k_mpc_cert_sweep(Batch b, MpcCertBuf cb) {
   mpc_cert_finish(cx, lds, nodes, certified ? n : 0, certified, cb.cert + size_t(inst) * MPC_CERT_SIZE);
 }
 
-// line search: value of trial point (x + alpha dx, u + alpha du), one thread per node
-__global__ __launch_bounds__(64) void k_ls_eval(Batch b, const DevModel* __restrict__ M, const DevConfig* __restrict__ C,
+// line search: value of trial point (x + alpha dx, u + alpha du).  Two forms: two lanes per node (the product) and one
+// thread per node (k_ls_eval_node / k_ls_tail_eval_node, hb_config.reserved = LS_EVAL_NODE); they differ by rounding only.
+// The full-step kernels also clear the list of refused instances k_ls_decide fills for the tail.
+//
+// Two lanes per node, 32 nodes per workgroup: what k_ls_eval and k_ls_tail_eval do for the node (inst, k) of the calling pair.  The
+// pair's trial point goes to LDS, every second entry from each lane; the next node's trial state is only read once per entry (defect)
+// and is formed from global memory there.  Both lanes of a pair call this together; lane 0 writes the three values to `out`.
+__device__ __forceinline__ void ls_pair_node(const Batch& b, const DevModel& M, const DevConfig& C, double* lds, int inst, int k, double alpha,
+                                             double* out) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  const int p = threadIdx.x >> 1, h = threadIdx.x & 1;
+  const size_t nd = size_t(inst) * b.Nmax + k;
+  const size_t xo = (size_t(inst) * (b.Nmax + 1) + k) * HB_NX;
+  double* x = lds + p * LS_PAIR_X;
+  double* u = x + HB_NX;
+  const WaveCtx cx;
+  cx.sync();   // (a caller that loops: the partner's reads of the previous point come first)
+#pragma unroll
+  for (int t = 0; t < HB_NX / 2; ++t) {
+    const int i = 2 * t + h;
+    x[i] = b.x[xo + i] + alpha * b.dx[xo + i];
+    u[i] = b.u[nd * HB_NU + i] + alpha * b.du[nd * HB_NU + i];
+  }
+  cx.sync();
+  const double* tt = b.t + size_t(inst) * (b.Nmax + 1);
+  const double* xn0 = b.x + xo + HB_NX;
+  const double* dxn = b.dx + xo + HB_NX;
+  double o3[3];
+  node_value_pair(M, C, x, u, lds + 32 * LS_PAIR_X + threadIdx.x * LS_PAIR_FT, h, [xn0, dxn, alpha](int i) { return xn0[i] + alpha * dxn[i]; },
+                  b.xref + nd * HB_NX, b.swing + nd * 24, tt[k + 1] - tt[k], b.mode[nd], o3);
+  if (h == 0) {
+    out[0] = o3[0];
+    out[1] = o3[1];
+    out[2] = o3[2];
+  }
+#endif
+}
+__global__ __launch_bounds__(64, 2) void k_ls_eval(Batch b, LsList ls, const DevModel* __restrict__ M, const DevConfig* __restrict__ C,
+                                                   double alpha) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  if (blockIdx.x == 0 && threadIdx.x == 0) *ls.count = 0;
+  const int gid = blockIdx.x * 32 + (threadIdx.x >> 1);
+  const int inst = gid / b.Nmax, k = gid % b.Nmax;
+  if (inst >= b.B) return;
+  if (b.accepted[inst] || k >= b.n_nodes[inst]) return;
+  __shared__ double lds[LS_PAIR_LDS];
+  ls_pair_node(b, *M, *C, lds, inst, k, alpha, b.partial + (size_t(inst) * b.Nmax + k) * 3);
+#endif
+}
+
+// one thread per node
+__global__ __launch_bounds__(64) void k_ls_eval_node(Batch b, LsList ls, const DevModel* __restrict__ M, const DevConfig* __restrict__ C,
                                                 double alpha) {
   const int gid = blockIdx.x * blockDim.x + threadIdx.x;
+  if (gid == 0) *ls.count = 0;
   const int inst = gid / b.Nmax, k = gid % b.Nmax;
   if (inst >= b.B) return;
   if (b.accepted[inst] || k >= b.n_nodes[inst]) return;
@@ -687,7 +738,7 @@ __device__ inline double wave_sum(double v) {
   return __shfl(v, 0, 64);
 }
 
-__global__ __launch_bounds__(64) void k_ls_decide(Batch b, const DevConfig* __restrict__ C, double alpha) {
+__global__ __launch_bounds__(64) void k_ls_decide(Batch b, LsList ls, const DevConfig* __restrict__ C, double alpha) {
   const int inst = blockIdx.x, lane = threadIdx.x;
   if (b.accepted[inst]) return;
   const int n = b.n_nodes[inst];
@@ -713,7 +764,11 @@ __global__ __launch_bounds__(64) void k_ls_decide(Batch b, const DevConfig* __re
     for (int i = lane; i < n * HB_NU; i += 64) nu2 += b.du[uo + i] * b.du[uo + i];
     nx2 = wave_sum(nx2);
     nu2 = wave_sum(nu2);
-    if (lane == 0) { b.ls_norm[inst * 2] = sqrt(nx2); b.ls_norm[inst * 2 + 1] = sqrt(nu2); }
+    if (lane == 0) {
+      b.ls_norm[inst * 2] = sqrt(nx2);
+      b.ls_norm[inst * 2 + 1] = sqrt(nu2);
+      ls.inst[atomicAdd(ls.count, 1)] = inst;   // the tail's work list (in no particular order)
+    }
     return;
   }
   // commit the step
@@ -731,15 +786,56 @@ __global__ __launch_bounds__(64) void k_ls_decide(Batch b, const DevConfig* __re
 // Backtracking tail of the filter line search.  An instance that did not accept the full step tries alpha0, alpha0 * decay, ...
 // >= alpha_min in that order and takes the first one the filter accepts (OCS2 FilterLinesearch); before every trial it gives up — no
 // step, converged — once alpha |dx| and alpha |du| are both below sqp.deltaTol.  The trials do not depend on each other, so they are
-// EVALUATED SIDE BY SIDE (k_ls_tail_eval: k_ls_eval once per step size, thread = node, per-node partials; the same node evaluation
-// and the same summation order as k_ls_eval + k_ls_decide) and a second kernel walks the sequence with exactly the sequential rules (k_ls_tail_decide):
+// EVALUATED SIDE BY SIDE (k_ls_tail_eval: k_ls_eval once per step size, per-node partials; the same node evaluation and the same
+// summation order as k_ls_eval + k_ls_decide) and a second kernel walks the sequence with exactly the sequential rules (k_ls_tail_decide):
 // identical decisions, but the launch takes ONE trial's time instead of up to 13 in a row (an instance that walks down to
 // alpha_min used to hold the whole batch back: 2.4 ms of line search per step in the backtracking figure), and without the loop over
-// the step sizes around the node evaluation the kernel no longer spills (the one-launch form carried 476 B / lane of scratch).
-// Instances that accepted alpha = 1 — all of them in steady state — leave at once.
-__global__ __launch_bounds__(64) void k_ls_tail_eval(Batch b, const DevModel* __restrict__ M, const DevConfig* __restrict__ C, double alpha0,
-                                                     double decay, double alpha_min) {
-  // (k_ls_eval with the step size of blockIdx.y; one node per thread and no loop around the node evaluation: no scratch)
+// the step sizes around the node evaluation the thread-per-node kernel does not spill (its one-launch form carried 476 B / lane of scratch).
+// The product's form walks the list of refused instances k_ls_decide left: a bounded grid whose workgroups take the items (list entry,
+// block of 32 nodes of that instance, step size; the step size running fastest) with a grid stride.  A workgroup LOOKS AT 64 of its items
+// at once, one per lane — whether the instance is still searching, the block has nodes, the step size is one the sequential search
+// reaches — and then evaluates the live ones one after the other, all lanes on one item.  A list full of instances that stop on deltaTol
+// at once (a converging batch: thousands of entries, nothing to evaluate) costs a workgroup a round or two of loads instead of one
+// chain of dependent loads per item; with an empty list — every instance accepted the full step: the steady state — a workgroup
+// returns after one load.
+__global__ __launch_bounds__(64, 2) void k_ls_tail_eval(Batch b, LsList ls, const DevModel* __restrict__ M, const DevConfig* __restrict__ C,
+                                                        double alpha0, double decay, double alpha_min, int n_alpha) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  const int n_list = *ls.count;
+  const int nblk = (b.Nmax + 31) / 32;
+  const long items = long(n_list) * nblk * n_alpha, G = gridDim.x;
+  const double delta_tol = C->delta_tol;
+  __shared__ double lds[LS_PAIR_LDS];
+  for (long base = blockIdx.x; base < items; base += 64 * G) {
+    bool live = false;
+    {
+      const long item = base + threadIdx.x * G;
+      if (item < items) {
+        const int ai = int(item % n_alpha), blk = int((item / n_alpha) % nblk), inst = ls.inst[item / n_alpha / nblk];
+        const int n = b.n_nodes[inst], acc = b.accepted[inst];   // (accepted: in an earlier window)
+        const double dx_norm = b.ls_norm[inst * 2], du_norm = b.ls_norm[inst * 2 + 1];
+        double alpha = alpha0;
+        for (int j = 0; j < ai; ++j) alpha *= decay;   // (the sequential search multiplies step by step: the same rounding)
+        // step sizes the sequential search never reaches are not evaluated: it stops (no step) at the first alpha with alpha |dx| and
+        // alpha |du| below deltaTol, and the condition is monotone in alpha — a converged instance evaluates nothing
+        live = !acc && blk * 32 < n && alpha >= alpha_min && !(alpha * du_norm < delta_tol && alpha * dx_norm < delta_tol);
+      }
+    }
+    for (unsigned long long todo = __ballot(live); todo; todo &= todo - 1) {
+      const long item = base + __builtin_ctzll(todo) * G;
+      const int ai = int(item % n_alpha), blk = int((item / n_alpha) % nblk), inst = __builtin_amdgcn_readfirstlane(ls.inst[item / n_alpha / nblk]);
+      double alpha = alpha0;
+      for (int j = 0; j < ai; ++j) alpha *= decay;
+      const int k = blk * 32 + (threadIdx.x >> 1);
+      if (k < b.n_nodes[inst]) ls_pair_node(b, *M, *C, lds, inst, k, alpha, b.ls_tail + ((size_t(inst) * LS_TAIL_MAX + ai) * b.Nmax + k) * 3);
+    }
+  }
+#endif
+}
+// one thread per node, one workgroup row per step size
+__global__ __launch_bounds__(64) void k_ls_tail_eval_node(Batch b, const DevModel* __restrict__ M, const DevConfig* __restrict__ C, double alpha0,
+                                                          double decay, double alpha_min) {
+  // (k_ls_eval_node with the step size of blockIdx.y; one node per thread and no loop around the node evaluation: no scratch)
   const int gid = blockIdx.x * blockDim.x + threadIdx.x, ai = blockIdx.y;
   const int inst = gid / b.Nmax, k = gid % b.Nmax;
   if (inst >= b.B) return;

@@ -74,6 +74,18 @@ constexpr void fields(Batch& b, size_t N, F&& f) {
   HB_FIELD(b.np_nodes, 1); HB_FIELD(b.grid_dirty, 1); HB_FIELD(b.lqpark, (N + LqPark::trip_max) * LqPark::size);
 }
 
+// The instances whose full step the line search refused, for the backtracking tail (k_ls_decide appends, k_ls_tail_eval walks): a counter
+// and the instance ids, numbered within the view.  One slot of each per instance, so that the view of an instance range starts at slots
+// of its own: the range's counter is the first of them, its list can hold the whole range.  The order of the list is not deterministic.
+struct LsList {
+  int* count;
+  int* inst;
+};
+template <class F>
+constexpr void fields(LsList& l, size_t, F&& f) {
+  HB_FIELD(l.count, 1); HB_FIELD(l.inst, 1);
+}
+
 // KKT certificate of the MPC's stage QP (hb_mpccert.hpp), on demand: work buffers of hb_mpc_get_certificate
 struct MpcCertBuf {
   double* node;
@@ -362,6 +374,7 @@ constexpr int n_fields() {
 // exactly the described pointers (plus the pointers named here, which are aimed at other structs' arrays).
 constexpr size_t kPtr = sizeof(void*);
 static_assert(sizeof(Batch) == 2 * sizeof(int) + n_fields<Batch>() * kPtr, "describe every array of Batch in fields()");
+static_assert(sizeof(LsList) == n_fields<LsList>() * kPtr, "describe every array of LsList in fields()");
 static_assert(sizeof(MpcCertBuf) == n_fields<MpcCertBuf>() * kPtr, "describe every array of MpcCertBuf in fields()");
 static_assert(sizeof(WbcBatch) == kPtr /*B*/ + n_fields<WbcBatch>() * kPtr + kPtr /*policy_valid*/, "describe every array of WbcBatch in fields()");
 static_assert(sizeof(WbcCertBuf) == n_fields<WbcCertBuf>() * kPtr && sizeof(HwbcCertBuf) == n_fields<HwbcCertBuf>() * kPtr, "certificate buffers");

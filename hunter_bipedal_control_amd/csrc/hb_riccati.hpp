@@ -802,6 +802,150 @@ HB_HD void node_value(const DevModel& M, const DevConfig& C, const double* x, co
   out3[2] = dt * eq;
 }
 
+#if defined(__HIP_DEVICE_COMPILE__)
+// node_value on TWO LANES: lane parity h = leg.  Each lane runs leg_eval for its own leg at both RK2 points, the fifteen composite sums
+// meet through one DPP exchange each (leg 0 + leg 1 on both lanes: the sum node_value forms), both lanes hold the whole-body core, and
+// each lane takes its leg's two contact points (h, h + 2) and half of the cost roles: its 5 joints' barriers and rows of R_jj, its 6
+// force entries, every second tracking entry and every second entry of the 12 centroidal defects, its 5 joint defects.  x / u: the
+// pair's trial point in LDS (shared by the two lanes); ft: 12 doubles of LDS of THIS lane, where the leg's contact points wait for
+// the rolled loop over them (as thread-private arrays that loop would index them dynamically: scratch).  Nothing of the first point
+// outlives it but f1: the contact-point terms of the cost are taken where the points are formed.  The two lanes of a pair must call
+// this together (every exit ahead of it depends on the node alone); lane 0 and lane 1 return the same three sums.
+constexpr int LS_PAIR_X = 45;    // doubles per pair (odd: conflict-free over the 32 pairs), 44 used
+constexpr int LS_PAIR_FT = 13;   // doubles per lane (odd), 12 used
+constexpr int LS_PAIR_LDS = 32 * LS_PAIR_X + 64 * LS_PAIR_FT;
+__device__ __forceinline__ double pair_sum(double v) { return v + dpp_full_f64<0xB1>(v); }   // quad_perm:[1,0,3,2]
+__device__ __forceinline__ Vec3<double> pair_sum(Vec3<double> v) { return {pair_sum(v.x), pair_sum(v.y), pair_sum(v.z)}; }
+// one RK2 point: the lane's leg, its contact points (base frame) to ft, the core from the pair's sums.  The sines and cosines of the
+// three base angles are computed once per pair: yaw on lane 0, pitch on lane 1, exchanged; roll on both.
+template <class QF, class QDF>
+__device__ __forceinline__ void pair_point(const DevModel& M, int h, QF qj, QDF qdj, double yaw, double pitch, double roll, const double* hn,
+                                           double* ft, CentroidalCore<double>& core) {
+  LegOut<double> L;
+  leg_eval<double>(M, h, qj, qdj, L);
+#pragma unroll
+  for (int f = 0; f < 2; ++f) {
+    st3(ft + 6 * f, L.foot[f]);
+    st3(ft + 6 * f + 3, L.foot_vj[f]);
+  }
+  double s_own, c_own, sc[6];
+  sincos_t(h ? pitch : yaw, s_own, c_own);
+  sincos_t(roll, sc[4], sc[5]);
+  const double s_oth = dpp_full_f64<0xB1>(s_own), c_oth = dpp_full_f64<0xB1>(c_own);
+  sc[0] = h ? s_oth : s_own; sc[1] = h ? c_oth : c_own;
+  sc[2] = h ? s_own : s_oth; sc[3] = h ? c_own : c_oth;
+  Sym3<double> IO;
+  IO.xx = pair_sum(L.IO.xx); IO.xy = pair_sum(L.IO.xy); IO.xz = pair_sum(L.IO.xz);
+  IO.yy = pair_sum(L.IO.yy); IO.yz = pair_sum(L.IO.yz); IO.zz = pair_sum(L.IO.zz);
+  const double zyx[3] = {yaw, pitch, roll};
+  centroidal_core<double>(M, pair_sum(L.mc), IO, pair_sum(L.l_sum), pair_sum(L.L_sum), zyx, hn, core, sc);
+}
+template <class XN>
+__device__ inline void node_value_pair(const DevModel& M, const DevConfig& C, const double* x, const double* u, double* ft, int h, XN xnext,
+                                       const double* xref, const double* swing, double dt, int mode, double* out3) {
+  const int cfm = ((mode == 2 || mode == 3) ? 5 : 0) | ((mode == 1 || mode == 3) ? 10 : 0);   // mode_flags as a mask
+  const int nc = __builtin_popcount(cfm);
+  const double fz_nom = nc > 0 ? M.total_mass * M.gravity / nc : 0.0;
+  const double inv_m = rcp_t(M.total_mass);
+  const RelaxedBarrierD fb{C.fb_mu, C.fb_delta};
+  const RelaxedBarrierD bp{C.pos_b[0], C.pos_b[1]}, bv{C.vel_b[0], C.vel_b[1]}, bf{C.force_b[0], C.force_b[1]};
+  double cost = 0, eq = 0;
+  double f1[12], f2[12];
+  {
+    CentroidalCore<double> c;
+    pair_point(M, h, [x](int j) { return x[12 + j]; }, [u](int j) { return u[12 + j]; }, x[9], x[10], x[11], x, ft, c);
+    Vec3<double> fs, ms;
+#pragma unroll 1
+    for (int f = 0; f < 2; ++f) {
+      const int i = h + 2 * f;
+      Vec3<double> rel, vel;
+      centroidal_foot<double>(c, ld3(ft + 6 * f), ld3(ft + 6 * f + 3), rel, vel);
+      const double Fx = u[3 * i], Fy = u[3 * i + 1], Fz = u[3 * i + 2];
+      const Vec3<double> F(Fx, Fy, Fz);
+      fs = fs + F;
+      ms = ms + cross(rel - c.com_rel, F);
+      // the cost roles of this contact point
+      const bool closed = (cfm >> i) & 1;
+      const double dz = Fz - (closed ? fz_nom : 0.0);
+      cost += 0.5 * C.R_FF_diag[3 * i] * Fx * Fx + 0.5 * C.R_FF_diag[3 * i + 1] * Fy * Fy + 0.5 * C.R_FF_diag[3 * i + 2] * dz * dz;
+      const double pz = x[8] + rel.z;
+      if (closed) {
+        const double hf = C.friction_mu * (Fz + C.friction_gripper) - sqrt(Fx * Fx + Fy * Fy + C.friction_reg);
+        cost += fb.value(hf);
+        const double r2 = vel.z + C.zv_gain * pz + C.zv_off;
+        eq += vel.x * vel.x + vel.y * vel.y + r2 * r2;
+      } else {
+        const double* sw = swing + 6 * i;
+        const double r0 = vel.z + C.kp_normal * pz - (sw[5] + C.kp_normal * sw[2]);
+        const double r1 = C.xy_gain * (x[6] + rel.x) + vel.x - (sw[3] + C.xy_gain * sw[0]);
+        const double r2 = C.xy_gain * (x[7] + rel.y) + vel.y - (sw[4] + C.xy_gain * sw[1]);
+        eq += r0 * r0 + Fx * Fx + Fy * Fy + Fz * Fz;
+        cost += 0.5 * C.soft_w * (r1 * r1 + r2 * r2);
+      }
+      cost += bf.value(Fz - C.force_lim[0]) + bf.value(C.force_lim[1] - Fz);
+    }
+    fs = pair_sum(fs);
+    ms = pair_sum(ms);
+    f1[0] = inv_m * fs.x; f1[1] = inv_m * fs.y; f1[2] = inv_m * fs.z - M.gravity;
+    f1[3] = inv_m * ms.x; f1[4] = inv_m * ms.y; f1[5] = inv_m * ms.z;
+    f1[6] = c.v_lin.x; f1[7] = c.v_lin.y; f1[8] = c.v_lin.z;
+    f1[9] = c.euler_rate.x; f1[10] = c.euler_rate.y; f1[11] = c.euler_rate.z;
+  }
+  {
+    double hn[6], zyx[3];
+#pragma unroll
+    for (int i = 0; i < 6; ++i) hn[i] = x[i] + dt * f1[i];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) zyx[i] = x[9 + i] + dt * f1[9 + i];
+    CentroidalCore<double> c;
+    pair_point(M, h, [x, u, dt](int j) { return x[12 + j] + dt * u[12 + j]; }, [u](int j) { return u[12 + j]; }, zyx[0], zyx[1], zyx[2], hn,
+               ft, c);
+    Vec3<double> ms;
+#pragma unroll 1
+    for (int f = 0; f < 2; ++f) {
+      const int i = h + 2 * f;
+      const Vec3<double> rel = c.R * ld3(ft + 6 * f);
+      ms = ms + cross(rel - c.com_rel, Vec3<double>(u[3 * i], u[3 * i + 1], u[3 * i + 2]));
+    }
+    ms = pair_sum(ms);
+    f2[0] = f1[0]; f2[1] = f1[1]; f2[2] = f1[2];   // (the forces are those of the first point)
+    f2[3] = inv_m * ms.x; f2[4] = inv_m * ms.y; f2[5] = inv_m * ms.z;
+    f2[6] = c.v_lin.x; f2[7] = c.v_lin.y; f2[8] = c.v_lin.z;
+    f2[9] = c.euler_rate.x; f2[10] = c.euler_rate.y; f2[11] = c.euler_rate.z;
+  }
+  double dyn = 0;
+#pragma unroll
+  for (int t = 0; t < 6; ++t) {
+    const int i = 2 * t + h;
+    const double fa = h ? f1[2 * t + 1] : f1[2 * t], fb2 = h ? f2[2 * t + 1] : f2[2 * t];
+    const double d = x[i] + 0.5 * dt * (fa + fb2) - xnext(i);
+    dyn += d * d;
+  }
+#pragma unroll 1
+  for (int t = 0; t < 11; ++t) {
+    const int i = 2 * t + h;
+    const double dx = x[i] - xref[i];
+    cost += 0.5 * C.Q_diag[i] * dx * dx;
+  }
+#pragma unroll 1  // 20 barrier evaluations per lane: rolled, as in node_value
+  for (int t = 0; t < 5; ++t) {
+    const int j = 5 * h + t;
+    const double d = x[12 + j] + dt * u[12 + j] - xnext(12 + j);
+    dyn += d * d;
+    double s = 0;
+#pragma unroll
+    for (int l = 0; l < HB_NJ; ++l) s += C.R_jj[j * 10 + l] * u[12 + l];
+    cost += 0.5 * u[12 + j] * s;
+    cost += bp.value(x[12 + j] - M.q_lower[j]) + bp.value(M.q_upper[j] - x[12 + j]);
+    cost += bv.value(u[12 + j] + M.qd_limit[j]) + bv.value(M.qd_limit[j] - u[12 + j]);
+  }
+  // lane 0 + lane 1
+  out3[0] = dt * pair_sum(cost);
+  out3[1] = dt * pair_sum(dyn);
+  out3[2] = dt * pair_sum(eq);
+}
+#endif
+
 // Filter line-search acceptance (OCS2 FilterLinesearch::acceptStep).
 HB_HD bool filter_accept(const DevConfig& C, double base_merit, double base_viol, double merit, double viol, double alpha,
                          double armijo) {

@@ -29,7 +29,7 @@ ABI_SYMBOLS = [
     "hb_plant_get_state", "hb_hoqp_solve", "hb_mpc_reset_masked", "hb_mpc_get_status", "hb_joint_set_flags",
     "hb_joint_get_emergency_stop", "hb_set_resident_time", "hb_get_wbc_iterations", "hb_ik_solve", "hb_debug_chunk_counters", "hb_debug_graph_state", "hb_refgen_get_status", "hb_tick_resident",
     "hb_wbc_set_certificate", "hb_wbc_get_certificate", "hb_hwbc_set_certificate", "hb_hwbc_get_certificate",
-    "hb_mpc_get_certificate", "hb_mpc_get_lq", "hb_mpc_get_recovery", "hb_mpc_get_linesearch",
+    "hb_mpc_get_certificate", "hb_mpc_get_lq", "hb_mpc_get_recovery", "hb_mpc_get_linesearch", "hb_mpc_get_linesearch_refused",
     "hb_refgen_get_schedule", "hb_gait_reset", "hb_gait_disable", "hb_gait_insert_template", "hb_gait_get_state",
     "hb_plant_set_sensor_model", "hb_plant_sense", "hb_estimator_update_resident", "hb_estimator_contact_force_resident",
     "hb_plant_set_contact_model", "hb_plant_set_external_wrench", "hb_plant_get_contact",
@@ -658,6 +658,12 @@ class HunterSolver:
         self._check(self.lib.hb_mpc_get_linesearch(self.ctx, C.c_int32(inst_begin), C.c_int32(count), *[_p(out[k]) for k in self.LINESEARCH_KEYS]),
                     "hb_mpc_get_linesearch")
         return out
+
+    def mpc_linesearch_refused(self) -> int:
+        """How many instances the last SQP iteration of the last MPC call handed to the backtracking tail (hb_mpc_get_linesearch_refused)."""
+        n = C.c_int32(0)
+        self._check(self.lib.hb_mpc_get_linesearch_refused(self.ctx, C.byref(n)), "hb_mpc_get_linesearch_refused")
+        return int(n.value)
 
     def sync(self):
         self._check(self.lib.hb_sync(self.ctx), "hb_sync")

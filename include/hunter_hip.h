@@ -917,7 +917,9 @@ int32_t hb_hwbc_get_certificate(hb_ctx* ctx, int32_t inst_begin, int32_t inst_co
  *   ric_fail [count]: 1 = the backward sweep met a non-positive pivot.
  *   Any pointer may be NULL.  The sums the decisions were taken on are per lane l the sum over nodes l, l + 64, ... followed by the
  *   wave reduction v[l] += v[l + off], off = 32 .. 1; hb_mpc_get_performance returns them for the accepted step size.
- * All four: HB_ERR_STATE when no MPC call has completed, or when the node tables or the iterate were replaced since the last one
+ * hb_mpc_get_linesearch_refused: *count = how many instances of the batch that iteration refused the full step of and handed to the
+ *   backtracking tail (the length of the tail's work list; Riccati failures included).
+ * All five: HB_ERR_STATE when no MPC call has completed, or when the node tables or the iterate were replaced since the last one
  * (hb_mpc_set_references, hb_refgen_update, hb_mpc_reset, hb_mpc_reset_masked, hb_mpc_set_trajectory); HB_ERR_ARG on a bad range. */
 #define HB_LS_TAIL_MAX 16         /* step sizes one window of the backtracking tail evaluates side by side */
 #define HB_MPC_CERT_R_DYN 0       /* max(|dx_0|_inf, max_k |dx_(k+1) - (A~_k dx_k + B~_k u~_k + b~_k)|_inf) */
@@ -940,6 +942,7 @@ int32_t hb_mpc_get_recovery(hb_ctx* ctx, int32_t inst, double* Kx /*[max_nodes][
 int32_t hb_mpc_get_linesearch(hb_ctx* ctx, int32_t inst_begin, int32_t inst_count, double* acc /*[count][4]*/,
                               double* partial /*[count][max_nodes][3]*/, double* ls_tail /*[count][16][max_nodes][3]*/,
                               double* ls_norm /*[count][2]*/, int32_t* accepted /*[count]*/, int32_t* ric_fail /*[count]*/);
+int32_t hb_mpc_get_linesearch_refused(hb_ctx* ctx, int32_t* count);
 /* Pipelining of hb_step_resident: the batch is cut into n_chunks (1..8) instance ranges, each a linear
  * MPC -> publish -> WBC sequence on its own HIP stream so that the per-instance sweeps of one range overlap the
  * per-node kernels of another.  Results are identical for every n_chunks; hb_get_stats phase times are only
