@@ -375,6 +375,49 @@ def split_scenario(scen) -> dict:
     return {name: (scen[..., at].copy() if n == 1 else scen[..., at:at + n].copy()) for name, at, n in SCENARIO_FIELDS}
 
 
+class HbProfileDrawConfig(C.Structure):
+    """hb_profile_draw_config (include/hunter_hip.h): profile draw at respawn, hb_plant_set_profile_draw."""
+    _fields_ = [("seed", C.c_uint64), ("kinds", C.c_int32), ("mu_per_point", C.c_int32), ("dir", C.c_double * 2), ("height_lo", C.c_double),
+                ("height_hi", C.c_double), ("at_lo", C.c_double), ("at_hi", C.c_double), ("riser_slope", C.c_double), ("steps_lo", C.c_int32),
+                ("steps_hi", C.c_int32), ("run_lo", C.c_double), ("run_hi", C.c_double), ("mu_lo", C.c_double), ("mu_hi", C.c_double),
+                ("follow_map", C.c_int32), ("log_capacity", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
+HB_PD_STREAM = 0x50444431
+HB_PD_FLAT, HB_PD_CURB, HB_PD_STAIRS = 1, 2, 4
+HB_PD_ALL = HB_PD_FLAT | HB_PD_CURB | HB_PD_STAIRS
+# row[HB_PD_N], (name, first index, count), in the order of the HB_PD_* indices of the header.
+PROFILE_DRAW_FIELDS = (("KIND", 0, 1), ("HEIGHT", 1, 1), ("AT", 2, 1), ("STEPS", 3, 1), ("RUN", 4, 1), ("MUS", 5, 4))
+HB_PD_N = 9
+# a log row: these five, then the HB_PD_N parameters
+PROFILE_DRAW_LOG_HEAD = ("EPISODE", "CAUSE", "TICKS", "PROGRESS", "TILT_MAX")
+HB_PD_LOG_W, HB_PD_LOG_MAX = len(PROFILE_DRAW_LOG_HEAD) + HB_PD_N, 1024
+
+
+def make_profile_draw_config(**fields) -> HbProfileDrawConfig:
+    """Level ground only along x, risers of slope 1.7 one metre ahead, one step of run 0.3 m, mu in [0, 0], no map, no log, seed 0; any
+    field by name overrides (dir: 2 values)."""
+    d = dict(seed=0, kinds=HB_PD_FLAT, mu_per_point=0, dir=(1.0, 0.0), height_lo=0.0, height_hi=0.0, at_lo=1.0, at_hi=1.0, riser_slope=1.7,
+             steps_lo=1, steps_hi=1, run_lo=0.3, run_hi=0.3, mu_lo=0.0, mu_hi=0.0, follow_map=0, log_capacity=0)
+    for k in fields:
+        if k not in d:
+            raise TypeError(f"make_profile_draw_config: unknown field {k!r} (one of {sorted(d)})")
+    d.update(fields)
+    out = HbProfileDrawConfig()
+    for k in ("height_lo", "height_hi", "at_lo", "at_hi", "riser_slope", "run_lo", "run_hi", "mu_lo", "mu_hi"):
+        setattr(out, k, float(d[k]))
+    for k in ("seed", "kinds", "mu_per_point", "steps_lo", "steps_hi", "follow_map", "log_capacity"):
+        setattr(out, k, int(d[k]))
+    out.dir[0], out.dir[1] = float(d["dir"][0]), float(d["dir"][1])
+    return out
+
+
+def split_profile_draw(row) -> dict:
+    """row[...][HB_PD_N] -> dict of [...] / [...][n] arrays keyed by field name."""
+    row = np.asarray(row)
+    return {name: (row[..., at].copy() if n == 1 else row[..., at:at + n].copy()) for name, at, n in PROFILE_DRAW_FIELDS}
+
+
 class HbJointGains(C.Structure):
     _fields_ = [(k, C.c_double) for k in ("kp_big_stance", "kp_big_swing", "kd_big", "kp_small_stance", "kp_small_swing", "kd_small",
                                           "kd_feet", "kp_position", "kd_position")]

@@ -139,6 +139,12 @@ struct hb_ctx {
   ScenarioBatch scenario{};
   hb_scenario_config scenario_cfg{};
   bool scenario_on = false;
+  // profile draw at respawn (hb_plant_set_profile_draw): profile_draw_on while a configuration is in force (profile_on is then true as
+  // well, and profile_host / profile_knots / ground_host / ground_knots are stale: profile_draw_refresh_host brings them up to date);
+  // profile_draw_cfg holds the direction already normalised; the arrays are allocated by the first call that gives a configuration
+  ProfileDrawBatch profile_draw{};
+  hb_profile_draw_config profile_draw_cfg{};
+  bool profile_draw_on = false;
   // reference generation (allocated on the first hb_refgen_reset)
   RefgenBatch rg{};
   hb_refgen_config rg_cfg{};

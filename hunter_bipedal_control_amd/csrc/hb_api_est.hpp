@@ -49,6 +49,8 @@ extern "C" {
 static int32_t respawn_totals_start(hb_ctx* ctx, hipStream_t s);   // (below, with the respawn entry points)
 static int32_t scenario_off(hb_ctx* ctx);                           // (below, with the scenario entry points)
 static int32_t scenario_start(hb_ctx* ctx, bool rows);
+static int32_t profile_draw_off(hb_ctx* ctx);                       // (below, with the profile draw entry points)
+static int32_t profile_draw_refresh_host(hb_ctx* ctx);
 
 // joint command outputs and the per-instance controller flags (allocated on first use; loaded = 1, no emergency stop)
 static int32_t joint_state_alloc(hb_ctx* ctx) {
@@ -150,7 +152,8 @@ int32_t hb_plant_set_episode(hb_ctx* ctx, const hb_episode_config* cfg) {
   if (!cfg) {
     ctx->episode_on = false;
     ctx->respawn_on = false;   // the respawn reads its decision from the record
-    return scenario_off(ctx);  // ... and the scenario is drawn at respawn
+    HB_TRY(profile_draw_off(ctx));   // ... and the scenario and the profile are drawn at respawn
+    return scenario_off(ctx);
   }
   EpisodeBatch& e = ctx->episode;
   if (!e.drec) {  // (drec: the last array of the description, so an allocation that failed half way is repeated)
@@ -225,7 +228,8 @@ int32_t hb_plant_set_respawn(hb_ctx* ctx, const hb_respawn_config* cfg, const do
       ctx->respawn_on = false;
       ctx->rs_rg_due = ctx->rs_mpc_due = false;   // (flags still pending are dropped: the next configuration starts with none)
     }
-    return scenario_off(ctx);   // the scenario is drawn at respawn
+    HB_TRY(profile_draw_off(ctx));   // the scenario and the profile are drawn at respawn
+    return scenario_off(ctx);
   }
   RespawnBatch& r = ctx->respawn;
   if (!r.mpc_pending) {  // (mpc_pending: the last array of the description, so an allocation that failed half way is repeated)
@@ -253,6 +257,8 @@ int32_t hb_plant_respawn(hb_ctx* ctx) {
   const JointBatch jb = ctx->joints.status ? ctx->joints : JointBatch{};
   const ActuatorBatch ab = ctx->act.wire_full ? ctx->act : ActuatorBatch{};
   const EstBatch est = ctx->est_ready ? ctx->est : EstBatch{};
+  // (on a profile the kernel takes its plane from the facet it locates and writes ProfileBatch::base: `ter`, which would be that array, is not passed)
+  const bool on_profile = ctx->contact_cfg.mode == 1 && ctx->profile_on;
   // a writer of the resident observation, and of the pending flags and the gait state the MPC stream reads: always between the two
   // ordering points
   HB_TRY(resident_write(ctx, s, true, [&] {
@@ -262,8 +268,13 @@ int32_t hb_plant_respawn(hb_ctx* ctx) {
                          (ch & (HB_SC_SLOPE | HB_SC_MU)) ? ctx->terrain.ter : nullptr, (ch & (HB_SC_PAYLOAD | HB_SC_MASS)) ? ctx->modelvar.mdl : nullptr,
                          ctx->dmodel, ctx->contact_cfg.ground_z);
     }
+    if (ctx->profile_draw_on)   // the ground of the episode that starts, from the same decision (the map follows where asked and in force)
+      hipLaunchKernelGGL(k_plant_profile_draw, dim3(ctx->B), dim3(64), 0, s, ctx->profile_draw, ctx->profile_draw_cfg, ctx->respawn_cfg, ctx->respawn,
+                         ctx->episode, ctx->profile, ctx->profile_draw_cfg.follow_map && ctx->ground_on ? ctx->ground.map : nullptr,
+                         ctx->contact_cfg.ground_z);
     hipLaunchKernelGGL(k_plant_respawn, dim3(ctx->B), dim3(64), 0, s, ctx->respawn, ctx->respawn_cfg, ctx->episode, ctx->plant, cb, jb, ab, est,
-                       ctx->gait, ctx->gait_cfg, ctx->gait_on ? 1 : 0, ter, d0, ctx->dmodel, ctx->jc_estop, ctx->w.rbd, ctx->b.x0);
+                       ctx->gait, ctx->gait_cfg, ctx->gait_on ? 1 : 0, on_profile ? nullptr : ter, d0, ctx->dmodel, ctx->jc_estop, ctx->w.rbd,
+                       ctx->b.x0, on_profile ? ctx->profile : ProfileBatch{});
   }));
   std::lock_guard<std::mutex> lk(ctx->mtx);
   ctx->rs_rg_due = ctx->rs_mpc_due = true;
@@ -417,6 +428,149 @@ int32_t hb_plant_get_scenario_log(hb_ctx* ctx, int32_t* count, double* log) {
   return HB_OK;
 }
 
+// ---- profile draw at respawn (include/hunter_hip.h above hb_plant_set_profile_draw) -----------------------------------------------------
+// No finished episode logged in every instance; with `rows`, the parameter rows back to "before the first draw" (zero) too.  Synchronous;
+// the caller has drained ctx->s_wbc.
+static int32_t profile_draw_start(hb_ctx* ctx, bool rows) {
+  ProfileDrawBatch& d = ctx->profile_draw;
+  if (rows) HB_HIP(hipMemset(d.row, 0, field_count(ctx, d, d.row) * 8));
+  HB_HIP(hipMemset(d.count, 0, field_count(ctx, d, d.count) * sizeof(int)));
+  if (d.log) HB_HIP(hipMemset(d.log, 0, size_t(ctx->B) * d.log_cap * HB_PD_LOG_W * 8));
+  return HB_OK;
+}
+
+// The host images of the records the device has been drawing, from the device: the profile's records and knots and, where the map
+// follows, the map's (its knots as given are its breakpoints and heights).  The caller has drained ctx->s_wbc.
+static int32_t profile_draw_refresh_host(hb_ctx* ctx) {
+  if (!ctx->profile_draw_on) return HB_OK;
+  HB_TRY(pull(ctx, ctx->profile_host.data(), ctx->profile, ctx->profile.prof, whole(ctx)));
+  HB_TRY(pull(ctx, ctx->profile_knots.data(), ctx->profile_draw, ctx->profile_draw.knots, whole(ctx)));
+  if (!(ctx->profile_draw_cfg.follow_map && ctx->ground_on)) return HB_OK;
+  HB_TRY(pull(ctx, ctx->ground_host.data(), ctx->ground, ctx->ground.map, whole(ctx)));
+  for (size_t i = 0; i < size_t(ctx->B); ++i) {
+    const double* r = ctx->ground_host.data() + i * Ground::size;
+    double* k = ctx->ground_knots.data() + i * PD_KNOTS;
+    const int K = int(r[Ground::nseg]) + 1;
+    for (int j = 0; j < HB_PROFILE_MAX_KNOTS; ++j) {
+      k[2 * j] = j < K ? r[Ground::brk + j] : 0.0;
+      k[2 * j + 1] = j < K ? r[Ground::hgt + j] : 0.0;
+    }
+  }
+  return HB_OK;
+}
+
+// Draw off: profile and map stay in force as last drawn (the host images follow the device).  The caller has drained ctx->s_wbc.
+static int32_t profile_draw_off(hb_ctx* ctx) {
+  if (!ctx->profile_draw_on) return HB_OK;
+  HB_TRY(profile_draw_refresh_host(ctx));
+  ctx->profile_draw_on = false;
+  return HB_OK;
+}
+
+int32_t hb_plant_set_profile_draw(hb_ctx* ctx, const hb_profile_draw_config* cfg) {
+  HB_ENTER_ARGS(false);
+  if (!cfg && !ctx->profile_draw_on) return HB_OK;
+  HB_TRY(contact_ready(ctx, "hb_plant_set_profile_draw"));
+  HB_FAIL_IF(cfg && !ctx->respawn_on, HB_ERR_STATE, "hb_plant_set_profile_draw: no respawn configuration in force (hb_plant_set_respawn): the profile is drawn at respawn");
+  HB_FAIL_IF(cfg && ctx->scenario_on && (ctx->scenario_cfg.channels & (HB_SC_SLOPE | HB_SC_MU)), HB_ERR_STATE, "hb_plant_set_profile_draw: the scenario in force draws the terrain (hb_plant_set_scenario with HB_SC_SLOPE or HB_SC_MU): turn it off first");
+  if (const char* why = cfg ? profile_draw_config_refusal(*cfg) : nullptr) {
+    ctx->err = std::string("hb_plant_set_profile_draw: ") + why + " (the configuration in force is kept)";
+    return HB_ERR_ARG;
+  }
+  HB_FAIL_IF(cfg && cfg->follow_map && !ctx->ground_on, HB_ERR_STATE, "hb_plant_set_profile_draw: follow_map without a ground map in force (hb_ground_set_profile): set the zero map first");
+  HB_FAIL_IF(cfg && !(std::fabs(ctx->contact_cfg.ground_z) <= PD_REACH), HB_ERR_STATE, "hb_plant_set_profile_draw: |ground_z| of the contact model above 1e3: the knots are drawn around ground_z");
+  HB_ENTER_DEVICE();
+  HB_HIP(hipStreamSynchronize(ctx->s_wbc));  // (a respawn or a step in flight still runs under the configuration it was launched with)
+  if (!cfg) return profile_draw_off(ctx);
+  const size_t B = ctx->B;
+  hb_profile_draw_config K = *cfg;
+  profile_direction(cfg->dir, K.dir);
+  // the level ground every instance starts on: the FLAT knots around its spawn point
+  std::vector<double> qs(B * 16), rec(B * Profile::stored), kn(B * PD_KNOTS), grel(cfg->follow_map ? B * PD_KNOTS : 0),
+      grec(cfg->follow_map ? B * Ground::size : 0);
+  HB_TRY(pull(ctx, qs.data(), ctx->respawn, ctx->respawn.q_spawn, whole(ctx)));
+  const double mu4[HB_NC] = {ctx->contact_cfg.mu, ctx->contact_cfg.mu, ctx->contact_cfg.mu, ctx->contact_cfg.mu};
+  for (size_t i = 0; i < B; ++i) {
+    const double s0 = profile_draw_s0(K.dir, qs.data() + 16 * i);
+    if (!(std::fabs(s0) <= PD_REACH)) {
+      ctx->err = "hb_plant_set_profile_draw: instance " + std::to_string(i) + " has a spawn point further than 1e3 along dir (the configuration in force is kept)";
+      return HB_ERR_STATE;
+    }
+    double rel[PD_KNOTS];
+    const int nk = profile_draw_flat(s0, ctx->contact_cfg.ground_z, rel, kn.data() + i * PD_KNOTS);
+    profile_compose(OneLane{}, nk, K.dir, kn.data() + i * PD_KNOTS, mu4, rec.data() + i * Profile::stored);
+    if (cfg->follow_map) {   // the map follows from the start: the zero map over the same knots
+      std::memcpy(grel.data() + i * PD_KNOTS, rel, sizeof rel);
+      ground_compose(OneLane{}, nk, K.dir, rel, grec.data() + i * Ground::size);
+    }
+  }
+  HB_TRY(profile_draw_off(ctx));   // (a configuration in force hands its records back first; a failure below leaves it off)
+  ProfileDrawBatch& d = ctx->profile_draw;
+  if (!d.count) {  // (count: the last array of the description, so an allocation that failed half way is repeated)
+    HB_HIP(alloc_fields(ctx, d));
+    d.B = ctx->B;
+  }
+  if (cfg->log_capacity > d.log_cap) {  // the log grows to the largest capacity asked for
+    if (d.log) {
+      ctx->allocs.erase(std::remove(ctx->allocs.begin(), ctx->allocs.end(), static_cast<void*>(d.log)), ctx->allocs.end());
+      HB_HIP(hipFree(d.log));
+      d.log = nullptr;
+      d.log_cap = 0;
+    }
+    HB_HIP(dalloc(ctx, &d.log, B * cfg->log_capacity * HB_PD_LOG_W));
+    d.log_cap = cfg->log_capacity;
+  }
+  ProfileBatch& t = ctx->profile;
+  if (!t.base) {  // (base: the last array of the description, so an allocation that failed half way is repeated)
+    HB_HIP(alloc_fields(ctx, t));
+    t.B = ctx->B;
+  }
+  HB_TRY(push(ctx, rec.data(), t, t.prof, whole(ctx)));
+  HB_TRY(push(ctx, kn.data(), d, d.knots, whole(ctx)));
+  ctx->profile_host = std::move(rec);
+  ctx->profile_knots = std::move(kn);
+  if (cfg->follow_map) {
+    HB_TRY(hb_sync(ctx));   // (a pass in flight on the MPC stream still runs on the map it was launched with)
+    HB_TRY(push(ctx, grec.data(), ctx->ground, ctx->ground.map, whole(ctx)));
+    ctx->ground_host = std::move(grec);
+    ctx->ground_knots = std::move(grel);
+  }
+  std::vector<double> q(B * 16);
+  HB_TRY(pull(ctx, q.data(), ctx->plant, ctx->plant.q, whole(ctx)));
+  HB_TRY(profile_locate(ctx, q.data(), ctx->s_wbc));
+  ctx->terrain_on = false;   // one ground at a time: the level profile replaces a terrain
+  ctx->profile_on = true;
+  HB_TRY(modelvar_level(ctx));
+  // the warm start is expressed in the frames of before
+  ContactBatch& c = ctx->contact;
+  HB_HIP(hipMemsetAsync(c.imp, 0, field_count(ctx, c, c.imp) * 8, ctx->s_wbc));
+  HB_HIP(hipStreamSynchronize(ctx->s_wbc));
+  ctx->profile_draw_cfg = K;
+  ctx->profile_draw_on = true;
+  return profile_draw_start(ctx, true);
+}
+
+int32_t hb_plant_get_profile_draw(hb_ctx* ctx, double* row) {
+  HB_ENTER_ARGS(false);
+  HB_FAIL_IF(!ctx->profile_draw_on, HB_ERR_STATE, "hb_plant_get_profile_draw: no profile draw in force (hb_plant_set_profile_draw)");
+  HB_ENTER_DEVICE();
+  HB_HIP(hipStreamSynchronize(ctx->s_wbc));
+  return pull(ctx, row, ctx->profile_draw, ctx->profile_draw.row, whole(ctx));
+}
+
+int32_t hb_plant_get_profile_draw_log(hb_ctx* ctx, int32_t* count, double* log) {
+  HB_ENTER_ARGS(false);
+  HB_FAIL_IF(!ctx->profile_draw_on, HB_ERR_STATE, "hb_plant_get_profile_draw_log: no profile draw in force (hb_plant_set_profile_draw)");
+  HB_ENTER_DEVICE();
+  HB_HIP(hipStreamSynchronize(ctx->s_wbc));
+  ProfileDrawBatch& d = ctx->profile_draw;
+  HB_TRY(pull(ctx, count, d, d.count, whole(ctx)));
+  // (the device rows have the pitch of the largest capacity set so far; the caller's have the pitch of the one in force)
+  const size_t row = size_t(ctx->profile_draw_cfg.log_capacity) * HB_PD_LOG_W * 8;
+  if (log && row) HB_HIP(hipMemcpy2D(log, row, d.log, size_t(d.log_cap) * HB_PD_LOG_W * 8, row, size_t(ctx->B), hipMemcpyDeviceToHost));
+  return HB_OK;
+}
+
 int32_t hb_plant_reset(hb_ctx* ctx, const double* q0, const double* v0, double baumgarte, double eps) {
   HB_ENTER(!q0 || !(baumgarte >= 0.0) || !(eps >= 0.0));
   PlantBatch& p = ctx->plant;
@@ -435,11 +589,16 @@ int32_t hb_plant_reset(hb_ctx* ctx, const double* q0, const double* v0, double b
   if (ctx->contact.wrench) HB_TRY(contact_clear(ctx, ctx->s_wbc));
   if (ctx->joints.status) HB_TRY(joints_clear(ctx, ctx->s_wbc));
   if (ctx->act.wire_full) HB_TRY(actuator_clear(ctx, ctx->s_wbc));
+  if (ctx->profile_draw_on) {   // the device draws the records: the host image the locate reads is stale
+    HB_HIP(hipStreamSynchronize(ctx->s_wbc));
+    HB_TRY(profile_draw_refresh_host(ctx));
+  }
   if (ctx->profile_on) HB_TRY(profile_locate(ctx, q0, ctx->s_wbc));   // the facets under the reset state
   if (ctx->episode_on) HB_TRY(episode_start(ctx, ctx->s_wbc));   // the record restarts from the reset state
   if (ctx->respawn_on) HB_TRY(respawn_totals_start(ctx, ctx->s_wbc));   // ... and so do the totals of the respawn
   HB_HIP(hipStreamSynchronize(ctx->s_wbc));
   if (ctx->scenario_on) HB_TRY(scenario_start(ctx, false));   // the log is empty, nobody has a push; terrain, models and scen stay as last drawn
+  if (ctx->profile_draw_on) HB_TRY(profile_draw_start(ctx, false));   // the log is empty; profile, map and rows stay as last drawn
   ctx->plant_ready = true;
   return HB_OK;
 }
@@ -578,6 +737,7 @@ int32_t hb_plant_set_contact_model(hb_ctx* ctx, const hb_contact_config* cfg) {
   HB_ENTER_ARGS(false);
   HB_FAIL_IF(!ctx->plant_ready, HB_ERR_STATE, "hb_plant_set_contact_model: call hb_plant_reset first");
   HB_FAIL_IF(cfg && !contact_config_valid(*cfg), HB_ERR_ARG, "hb_plant_set_contact_model: mode 0 / 1, sweeps 1 .. 10000, mu >= 0, erp in [0, 1], tol >= 0, fall_height >= 0, every field finite and `reserved` 0");
+  HB_FAIL_IF(cfg && cfg->mode == 1 && ctx->profile_draw_on && !(std::fabs(cfg->ground_z) <= PD_REACH), HB_ERR_ARG, "hb_plant_set_contact_model: |ground_z| above 1e3 while a profile draw is in force (hb_plant_set_profile_draw): its knots are drawn around ground_z");
   HB_ENTER_DEVICE();
   HB_HIP(hipStreamSynchronize(ctx->s_wbc));  // (a step in flight still runs under the model it was launched with)
   const bool ground = cfg && cfg->mode == 1;
@@ -594,6 +754,7 @@ int32_t hb_plant_set_contact_model(hb_ctx* ctx, const hb_contact_config* cfg) {
     HB_HIP(hipMemsetAsync(p.pinned, 0, field_count(ctx, p, p.pinned) * sizeof(int), ctx->s_wbc));
   }
   if (!ground) HB_TRY(scenario_off(ctx));   // the scenario belongs to contact model 1 (and gives the wrench back)
+  if (!ground) HB_TRY(profile_draw_off(ctx));   // ... and so does the profile draw
   ctx->contact_cfg = ground ? *cfg : hb_contact_config{};
   if (!ground) ctx->terrain_on = false;   // the terrain belongs to contact model 1
   if (!ground) ctx->profile_on = false;   // ... and so does the terrain profile
@@ -687,6 +848,7 @@ int32_t hb_plant_set_terrain(hb_ctx* ctx, const double* plane, const double* mu)
   HB_ENTER_ARGS(false);
   HB_TRY(contact_ready(ctx, "hb_plant_set_terrain"));
   HB_FAIL_IF(!plane && !mu && ctx->scenario_on && (ctx->scenario_cfg.channels & (HB_SC_SLOPE | HB_SC_MU)), HB_ERR_STATE, "hb_plant_set_terrain: the scenario in force draws the terrain (hb_plant_set_scenario): turn it off first");
+  HB_FAIL_IF(ctx->profile_draw_on, HB_ERR_STATE, "hb_plant_set_terrain: the profile draw in force draws the ground (hb_plant_set_profile_draw): turn it off first");
   const size_t B = ctx->B;
   std::vector<double> rec(B * Terrain::size);
   for (size_t i = 0; i < B && (plane || mu); ++i) {
@@ -783,6 +945,7 @@ int32_t hb_plant_set_terrain_profile(hb_ctx* ctx, const int32_t* n_knots, const 
   const bool on = n_knots || dir || knots;
   HB_FAIL_IF(on && !(n_knots && dir && knots), HB_ERR_ARG, "hb_plant_set_terrain_profile: give n_knots, dir and knots, or none of them to switch the profile off (the profile in force is kept)");
   HB_FAIL_IF(!on && mu, HB_ERR_ARG, "hb_plant_set_terrain_profile: friction coefficients without a profile (the profile in force is kept)");
+  HB_FAIL_IF(ctx->profile_draw_on, HB_ERR_STATE, "hb_plant_set_terrain_profile: the profile draw in force draws the ground (hb_plant_set_profile_draw): turn it off first");
   HB_FAIL_IF(on && ctx->respawn_on, HB_ERR_STATE, "hb_plant_set_terrain_profile: a respawn configuration is in force (hb_plant_set_respawn): no respawn on a profile, turn it off first");
   HB_FAIL_IF(on && ctx->scenario_on && (ctx->scenario_cfg.channels & (HB_SC_SLOPE | HB_SC_MU)), HB_ERR_STATE, "hb_plant_set_terrain_profile: the scenario in force draws the terrain (hb_plant_set_scenario): turn it off first");
   const size_t B = ctx->B;
@@ -824,9 +987,10 @@ int32_t hb_plant_get_terrain_profile(hb_ctx* ctx, int32_t* n_knots, double* dir,
   HB_ENTER_ARGS(false);
   HB_TRY(contact_ready(ctx, "hb_plant_get_terrain_profile"));
   HB_FAIL_IF(!ctx->profile_on, HB_ERR_STATE, "hb_plant_get_terrain_profile: no terrain profile in force (hb_plant_set_terrain_profile)");
-  if (segment) {
+  if (segment || ctx->profile_draw_on) {
     HB_ENTER_DEVICE();
     HB_HIP(hipStreamSynchronize(ctx->s_wbc));
+    HB_TRY(profile_draw_refresh_host(ctx));   // (the device draws the records: the host image is stale)
     HB_TRY(pull(ctx, segment, ctx->profile, ctx->profile.seg, whole(ctx)));
   }
   constexpr size_t nrec = size_t(Profile::rec) * (HB_PROFILE_MAX_KNOTS - 1);

@@ -41,6 +41,11 @@ int32_t hb_ground_set_profile(hb_ctx* ctx, const int32_t* n_knots, const double*
 int32_t hb_ground_get_profile(hb_ctx* ctx, int32_t* n_knots, double* dir, double* knots, double* slopes) {
   HB_ENTER_ARGS(false);
   HB_FAIL_IF(!ctx->ground_on, HB_ERR_STATE, "hb_ground_get_profile: no ground map in force (hb_ground_set_profile)");
+  if (ctx->profile_draw_on && ctx->profile_draw_cfg.follow_map) {   // the device draws the records: the host image is stale
+    HB_ENTER_DEVICE();
+    HB_HIP(hipStreamSynchronize(ctx->s_wbc));
+    HB_TRY(profile_draw_refresh_host(ctx));
+  }
   for (size_t i = 0; i < size_t(ctx->B); ++i) {
     const double* r = ctx->ground_host.data() + i * Ground::size;
     if (n_knots) n_knots[i] = int32_t(r[Ground::nseg]) + 1;

@@ -172,46 +172,83 @@ struct ProfileIo {
   int* seg;
   double* base;
 };
+// One lane that owns every element: what the host runs the lane-cooperative composers below with.
+struct OneLane {
+  int lane = 0, nlanes = 1;
+  HB_HD void sync() const {}
+};
+// a[2] = dir / |dir|: the division every stored direction goes through once (profile_record, ground_record, hb_plant_set_profile_draw).
+HB_HD void profile_direction(const double* dir, double* a) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  const double len = sqrt(dir[0] * dir[0] + dir[1] * dir[1]);
+  a[0] = dir[0] / len;
+  a[1] = dir[1] / len;
+}
+// The record rec[Profile::rec] = (T_j, d_j) of segment j of valid knots along the unit direction a.  It comes from terrain_plane_record,
+// the routine behind hb_plant_set_terrain: the plane handed to it is the unit normal and d of the segment.  Every operation is rounded on
+// its own, so the host setter and the device (k_plant_profile_draw) store the same bits.
+HB_HD void profile_segment_record(const double* a, const double* knots, int j, double* rec) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  const double ds = knots[2 * j + 2] - knots[2 * j];
+  const double m = (knots[2 * j + 3] - knots[2 * j + 1]) / ds;
+  const double w = sqrt(1.0 + m * m);
+  double pl[4] = {0.0 - m * a[0] / w, 0.0 - m * a[1] / w, 1.0 / w, 0.0};   // (0 - : no negative zero on level ground)
+  // (normalised until its length rounds to 1, so that hb_plant_set_terrain, which divides by the length once more, stores the same bits)
+  for (int it = 0; it < 4 && terrain_normal_length(pl) != 1.0; ++it) {
+    const double l = terrain_normal_length(pl);
+    for (int x = 0; x < 3; ++x) pl[x] /= l;
+  }
+  pl[3] = pl[0] * (a[0] * knots[2 * j]) + pl[1] * (a[1] * knots[2 * j]) + pl[2] * knots[2 * j + 1];
+  terrain_plane_record(pl, terrain_normal_length(pl), rec);   // (writes T and d: the Profile::rec leading entries of a Terrain record)
+}
+static_assert(Terrain::d + 1 == Profile::rec, "a segment record is T and d of a Terrain record");
+// The stored record r[Profile::stored] of VALID knots (K of them, (s, z), along the unit direction a) and the friction coefficients mu[4]:
+// what profile_record composes once it has accepted them, and what k_plant_profile_draw composes for a drawn profile, one segment per lane.
+// knots, a, mu and r may be LDS or plain memory; r is written whole.
+template <class Ctx>
+HB_HD void profile_compose(const Ctx& cx, int K, const double* a, const double* knots, const double* mu, double* r) {
+  for (int k = cx.lane; k < Profile::stored; k += cx.nlanes) r[k] = 0.0;
+  cx.sync();
+  for (int k = cx.lane; k < K; k += cx.nlanes) r[Profile::brk + k] = knots[2 * k];
+  for (int j = cx.lane; j + 1 < K; j += cx.nlanes) profile_segment_record(a, knots, j, r + Profile::seg + Profile::rec * j);
+  for (int c = cx.lane; c < HB_NC; c += cx.nlanes) r[Profile::head + Terrain::mu + c] = mu[c];
+  if (cx.lane == 0) {
+    r[Profile::dir] = a[0];
+    r[Profile::dir + 1] = a[1];
+    r[Profile::nseg] = double(K - 1);
+  }
+  cx.sync();
+  for (int k = cx.lane; k < Profile::rec; k += cx.nlanes) r[Profile::head + k] = r[Profile::seg + k];   // (until a state is located: segment 0)
+  cx.sync();
+}
 // Host: the stored record r[Profile::stored] of one instance from its profile (K knots (s, z), direction, mu[4] or null for cfg_mu), or the
-// reason it is refused.  The segment records come from terrain_plane_record, the routine behind hb_plant_set_terrain: the plane handed to
-// it is the unit normal and d of the segment.
+// reason it is refused (r is then not written).  The validation; the record of what it accepts is profile_compose's.
 inline const char* profile_record(int K, const double* dir, const double* knots, const double* mu, double cfg_mu, double* r) {
   if (K < 2 || K > HB_PROFILE_MAX_KNOTS) return "a number of knots outside 2 .. HB_PROFILE_MAX_KNOTS";
   if (!(std::isfinite(dir[0]) && std::isfinite(dir[1]))) return "a non-finite direction";
   const double len = std::sqrt(dir[0] * dir[0] + dir[1] * dir[1]);
   if (!(len > 0.0) || !std::isfinite(len)) return "a direction of length zero";
-  const double a[2] = {dir[0] / len, dir[1] / len};
   for (int k = 0; k < 2 * K; ++k)
     if (!std::isfinite(knots[k])) return "a non-finite knot";
-  for (int k = 0; k < Profile::stored; ++k) r[k] = 0.0;
-  r[Profile::dir] = a[0];
-  r[Profile::dir + 1] = a[1];
-  r[Profile::nseg] = double(K - 1);
-  for (int k = 0; k < K; ++k) r[Profile::brk + k] = knots[2 * k];
   for (int j = 0; j + 1 < K; ++j) {
     const double ds = knots[2 * j + 2] - knots[2 * j];
     if (!(ds > 0.0)) return "knots whose s is not strictly increasing";
     const double m = (knots[2 * j + 3] - knots[2 * j + 1]) / ds;
     // (sqrt(3) to rounding: a riser given by its height and width)
     if (!(std::isfinite(m) && m * m <= 3.0 * (1.0 + 1e-12))) return "a segment steeper than sqrt(3) (n_z < 0.5)";
-    const double w = std::sqrt(1.0 + m * m);
-    double pl[4] = {0.0 - m * a[0] / w, 0.0 - m * a[1] / w, 1.0 / w, 0.0};   // (0 - : no negative zero on level ground)
-    // (normalised until its length rounds to 1, so that hb_plant_set_terrain, which divides by the length once more, stores the same bits)
-    for (int it = 0; it < 4 && terrain_normal_length(pl) != 1.0; ++it) {
-      const double l = terrain_normal_length(pl);
-      for (int x = 0; x < 3; ++x) pl[x] /= l;
-    }
-    pl[3] = pl[0] * (a[0] * knots[2 * j]) + pl[1] * (a[1] * knots[2 * j]) + pl[2] * knots[2 * j + 1];
-    double full[Terrain::size];
-    terrain_plane_record(pl, terrain_normal_length(pl), full);
-    std::memcpy(r + Profile::seg + Profile::rec * j, full, Profile::rec * sizeof(double));
   }
+  double mu4[HB_NC];
   for (int c = 0; c < HB_NC; ++c) {
-    const double m = mu ? mu[c] : cfg_mu;
-    if (!(std::isfinite(m) && m >= 0.0)) return "a friction coefficient that is negative or not finite";
-    r[Profile::head + Terrain::mu + c] = m;
+    mu4[c] = mu ? mu[c] : cfg_mu;
+    if (!(std::isfinite(mu4[c]) && mu4[c] >= 0.0)) return "a friction coefficient that is negative or not finite";
   }
-  std::memcpy(r + Profile::head, r + Profile::seg, Profile::rec * sizeof(double));   // (until a state is located: segment 0)
+  double a[2];
+  profile_direction(dir, a);
+  profile_compose(OneLane{}, K, a, knots, mu4, r);
   return nullptr;
 }
 

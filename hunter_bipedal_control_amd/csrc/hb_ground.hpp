@@ -15,21 +15,31 @@ struct Ground {
                        size = slope + HB_PROFILE_MAX_KNOTS - 1;
 };
 
+// The record r[Ground::size] of VALID knots (K of them, (s, g), along the unit direction a): what ground_record composes once it has
+// accepted them, and what k_plant_profile_draw composes for the map that follows a drawn profile, one knot per lane.  r is written whole.
+template <class Ctx>
+HB_HD void ground_compose(const Ctx& cx, int K, const double* a, const double* knots, double* r) {
+  for (int k = cx.lane; k < Ground::size; k += cx.nlanes) r[k] = 0.0;
+  cx.sync();
+  if (cx.lane == 0) {
+    r[Ground::dir] = a[0];
+    r[Ground::dir + 1] = a[1];
+    r[Ground::nseg] = double(K - 1);
+  }
+  for (int k = cx.lane; k < K; k += cx.nlanes) {
+    r[Ground::brk + k] = knots[2 * k];
+    r[Ground::hgt + k] = 0.0 + knots[2 * k + 1];   // (0 + : no negative zero, so that a level segment returns its height bit for bit)
+  }
+  for (int j = cx.lane; j + 1 < K; j += cx.nlanes) r[Ground::slope + j] = (knots[2 * j + 3] - knots[2 * j + 1]) / (knots[2 * j + 2] - knots[2 * j]);
+  cx.sync();
+}
 // Host: the record r[Ground::size] of one instance from its map (K knots (s, g), direction), or the reason it is refused.  The checks
 // are profile_record's (the routine is run on the map, so a plant profile is always a valid map and the two never drift apart); the
 // direction is normalised by the same division.
 inline const char* ground_record(int K, const double* dir, const double* knots, double* r) {
   double pro[Profile::stored];
   if (const char* why = profile_record(K, dir, knots, nullptr, 0.0, pro)) return why;
-  for (int k = 0; k < Ground::size; ++k) r[k] = 0.0;
-  r[Ground::dir] = pro[Profile::dir];
-  r[Ground::dir + 1] = pro[Profile::dir + 1];
-  r[Ground::nseg] = double(K - 1);
-  for (int k = 0; k < K; ++k) {
-    r[Ground::brk + k] = knots[2 * k];
-    r[Ground::hgt + k] = 0.0 + knots[2 * k + 1];   // (0 + : no negative zero, so that a level segment returns its height bit for bit)
-  }
-  for (int j = 0; j + 1 < K; ++j) r[Ground::slope + j] = (knots[2 * j + 3] - knots[2 * j + 1]) / (knots[2 * j + 2] - knots[2 * j]);
+  ground_compose(OneLane{}, K, pro + Profile::dir, knots, r);
   return nullptr;
 }
 

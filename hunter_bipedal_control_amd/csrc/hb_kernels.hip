@@ -25,6 +25,7 @@
 #include "hb_sensors.hpp"
 #include "hb_respawn.hpp"
 #include "hb_scenario.hpp"
+#include "hb_profiledraw.hpp"
 #include "hb_layout.hpp"
 #include "hb_iterate.hpp"
 #include "hb_wavectx.hpp"
@@ -1319,16 +1320,21 @@ __global__ __launch_bounds__(64) void k_plant_episode(EpisodeBatch e, hb_episode
 // after those loads.  A respawning wavefront draws its Philox blocks one per lane into LDS, lane 0 folds the record, composes and places
 // the spawn state (the one sequential piece: the leg kinematics, as in k_plant_reset) and resets the gait object; then all lanes write the
 // rows, consecutive lanes on consecutive words.  cb / jb / ab / est / estop / e.trace: null arrays where the subsystem has none.
+// pb: the terrain profile in force (null prof: none, and nothing below differs from the placement on the plane; with one, ter is null: the
+// host's plane pointer would be pb.base, which this kernel writes): lane 0 places the state
+// vertically on the facets under its contact points and locates it (hb_profiledraw.hpp), the record starts over the facet under the base
+// origin, and seg[5] / base[14] of the instance are written with the rows.
 __global__ __launch_bounds__(64) void k_plant_respawn(RespawnBatch rs, hb_respawn_config K, EpisodeBatch e, PlantBatch p, ContactBatch cb, JointBatch jb,
                                                       ActuatorBatch ab, EstBatch est, GaitBatch g, hb_gait_config GK, int gait_on,
                                                       const double* __restrict__ ter, double d0, const DevModel* __restrict__ M, int* estop,
-                                                      double* res_rbd, double* res_x0) {
+                                                      double* res_rbd, double* res_x0, ProfileBatch pb) {
   const int i = blockIdx.x;
   const DeviceCtx cx;
   int* irec = e.irec + HB_EP_NI * i;
   const int cause = respawn_decide(K, irec);
   if (cause == 0) return;
-  __shared__ double sh[RS_DRAW + 16 + 16 + 12 + HB_NRBD + HB_NX + 4];
+  __shared__ double sh[RS_DRAW + 16 + 16 + 12 + HB_NRBD + HB_NX + 4 + Terrain::size];
+  __shared__ int seg[HB_NC + 1];
   double* draw = sh;
   double* q = draw + RS_DRAW;
   double* v = q + 16;
@@ -1336,6 +1342,7 @@ __global__ __launch_bounds__(64) void k_plant_respawn(RespawnBatch rs, hb_respaw
   double* rbd = feet + 12;
   double* x0 = rbd + HB_NRBD;
   double* plane = x0 + HB_NX;
+  double* base = plane + 4;
   int* itot = rs.itot + HB_RS_NI * i;
   double* drec = e.drec + HB_EP_ND * i;
   if (cx.lane < RS_BLOCKS && respawn_block_needed(K, cx.lane))
@@ -1352,7 +1359,15 @@ __global__ __launch_bounds__(64) void k_plant_respawn(RespawnBatch rs, hb_respaw
     }
     respawn_perturb(K, rs.q_spawn + 16 * i, rs.v_spawn + 16 * i, draw, q, v);
     plant_feet(*M, q, feet);
-    respawn_place(*M, K, plane, q, feet);
+    if (pb.prof) {   // on a profile: vertically onto the facets under the points, then the locate of the placed state
+      const double* pro = pb.prof + size_t(Profile::stored) * i;
+      profile_place(*M, K, pro, q, feet);
+      profile_locate_state(pro, q, feet, seg, base);
+      for (int a = 0; a < 3; ++a) plane[a] = base[Terrain::T + 3 * a + 2];
+      plane[3] = base[Terrain::d];
+    } else {
+      respawn_place(*M, K, plane, q, feet);
+    }
     plant_rbd_from_state(q, v, rbd);
     centroidal_state_from_rbd(*M, rbd, x0);
     if (gait_on) gait_reset_instance(g, i, GK);
@@ -1382,6 +1397,53 @@ __global__ __launch_bounds__(64) void k_plant_respawn(RespawnBatch rs, hb_respaw
   r.res_rbd = res_rbd + HB_NRBD * i; r.res_x0 = res_x0 + HB_NX * i;
   r.rg_pending = rs.rg_pending + i; r.mpc_pending = rs.mpc_pending + i;
   respawn_write(cx, r, q, v, feet, rbd, x0, plane);
+  if (pb.prof) {
+    for (int c = cx.lane; c < HB_NC + 1; c += cx.nlanes) pb.seg[(HB_NC + 1) * i + c] = seg[c];
+    for (int k = cx.lane; k < Terrain::size; k += cx.nlanes) pb.base[size_t(Terrain::size) * i + k] = base[k];
+  }
+}
+
+// ---- profile draw at respawn (hb_plant_set_profile_draw, hb_profiledraw.hpp): one wavefront per instance, ahead of k_plant_respawn --------
+// Every lane reads k_plant_respawn's decision from the instance's still unchanged record (the same words: wave-uniform), and a wavefront
+// whose instance stays leaves after those loads.  A respawning wavefront appends the log row of the finished episode (all lanes, from the
+// row still in place), draws its Philox blocks one per lane into LDS, lets lane 0 compose the knots and the row (the one sequential
+// piece), composes the profile record and, with a map that follows, the map record one segment per lane (profile_compose /
+// ground_compose: the routines of the host setters) and writes records, knots and row with all lanes, consecutive lanes on consecutive
+// words.  gmap: GroundBatch::map, or null where the controller's map does not follow.
+__global__ __launch_bounds__(64) void k_plant_profile_draw(ProfileDrawBatch pd, hb_profile_draw_config K, hb_respawn_config RK, RespawnBatch rs,
+                                                           EpisodeBatch e, ProfileBatch pb, double* gmap, double ground_z) {
+  const int i = blockIdx.x;
+  const DeviceCtx cx;
+  const int* irec = e.irec + HB_EP_NI * i;
+  const int cause = respawn_decide(RK, irec);
+  if (cause == 0) return;
+  __shared__ double sh[PD_DRAW + 2 + 2 * PD_KNOTS + HB_PD_N + Profile::stored + Ground::size];
+  __shared__ int nk;
+  double* u = sh;
+  double* a = u + PD_DRAW;
+  double* rel = a + 2;
+  double* pk = rel + PD_KNOTS;
+  double* row_s = pk + PD_KNOTS;
+  double* pro_s = row_s + HB_PD_N;
+  double* map_s = pro_s + Profile::stored;
+  const int* itot = rs.itot + HB_RS_NI * i;
+  ProfileDrawRows r{};
+  r.prof = pb.prof + size_t(Profile::stored) * i;
+  r.knots = pd.knots + PD_KNOTS * i;
+  r.row = pd.row + HB_PD_N * i;
+  r.map = gmap ? gmap + size_t(Ground::size) * i : nullptr;
+  if (cx.lane < 2) a[cx.lane] = K.dir[cx.lane];
+  __syncthreads();
+  if (K.log_capacity > 0)
+    profile_draw_log_append(cx, K.log_capacity, cause, a, irec, e.drec + HB_EP_ND * i, itot, r.row, pd.count + i,
+                            pd.log + size_t(i) * pd.log_cap * HB_PD_LOG_W);
+  if (cx.lane < PD_BLOCKS) profile_draw_block(K, RK.instance_offset + uint32_t(i), uint32_t(itot[HB_RS_I_EPISODE_INDEX] + 1), cx.lane, u, nullptr);
+  __syncthreads();
+  if (cx.lane == 0) nk = profile_draw_knots(K, u, profile_draw_s0(a, rs.q_spawn + 16 * i), ground_z, rel, pk, row_s);
+  __syncthreads();
+  profile_compose(cx, nk, a, pk, row_s + HB_PD_MUS, pro_s);
+  if (r.map) ground_compose(cx, nk, a, rel, map_s);
+  profile_draw_store(cx, r, pro_s, pk, row_s, map_s);
 }
 
 // ---- scenario draw at respawn (hb_plant_set_scenario, hb_scenario.hpp): one wavefront per instance, ahead of k_plant_respawn -------------

@@ -14,6 +14,7 @@
 #include "hb_episode.hpp"
 #include "hb_modelvar.hpp"
 #include "hb_ground.hpp"
+#include "hb_profiledraw.hpp"
 
 namespace {
 using namespace hb;
@@ -262,6 +263,23 @@ constexpr void fields(ScenarioBatch& c, size_t, F&& f) {
   HB_FIELD(c.scen, HB_SC_N); HB_FIELD(c.push, 3); HB_FIELD(c.count, 1);
 }
 
+// profile draw at respawn (hb_plant_set_profile_draw, hb_profiledraw.hpp), allocated by the first call that gives a configuration: the
+// parameter row of the ground every instance stands on (row), the plant's knots of that ground as (s, z) pairs, zero behind the last
+// (knots: what hb_plant_get_terrain_profile returns while the device draws) and the number of logged episodes (count).  The drawn records
+// themselves go to ProfileBatch::prof and, with follow_map, GroundBatch::map.  The log is [B][log_cap][HB_PD_LOG_W] with log_cap the
+// largest log_capacity set so far: a run-time extent, so the set call allocates it and the description does not name it.
+struct ProfileDrawBatch {
+  int B;
+  int log_cap;
+  double *row, *knots;
+  int* count;
+  double* log;
+};
+template <class F>
+constexpr void fields(ProfileDrawBatch& d, size_t, F&& f) {
+  HB_FIELD(d.row, HB_PD_N); HB_FIELD(d.knots, PD_KNOTS); HB_FIELD(d.count, 1);
+}
+
 // actuator loop of the plant and the simulator end of the LCM link (hb_plant_step_hybrid, hb_plant_step_lcm, hb_plant_sense_lcm),
 // allocated on the first call that needs them — the held-torque path needs none: the record of the last hybrid step, the staging of a
 // host command and the received command (pos_des vel_des kp kd ff, one array each), the timestamp filter, the wire images
@@ -388,6 +406,7 @@ static_assert(sizeof(ModelVarBatch) == kPtr /*B*/ + n_fields<ModelVarBatch>() * 
 static_assert(sizeof(EpisodeBatch) == 2 * sizeof(int) + (n_fields<EpisodeBatch>() + 1 /*trace*/) * kPtr, "describe every array of EpisodeBatch in fields()");
 static_assert(sizeof(RespawnBatch) == kPtr /*B*/ + n_fields<RespawnBatch>() * kPtr, "describe every array of RespawnBatch in fields()");
 static_assert(sizeof(ScenarioBatch) == 2 * sizeof(int) + (n_fields<ScenarioBatch>() + 1 /*log*/) * kPtr, "describe every array of ScenarioBatch in fields()");
+static_assert(sizeof(ProfileDrawBatch) == 2 * sizeof(int) + (n_fields<ProfileDrawBatch>() + 1 /*log*/) * kPtr, "describe every array of ProfileDrawBatch in fields()");
 static_assert(sizeof(ActuatorBatch) == kPtr /*B*/ + n_fields<ActuatorBatch>() * kPtr, "describe every array of ActuatorBatch in fields()");
 static_assert(sizeof(RefgenBatch) == kPtr /*B*/ + n_fields<RefgenBatch>() * kPtr + kPtr /*init_stance*/, "describe every array of RefgenBatch in fields()");
 static_assert(sizeof(GroundBatch) == kPtr /*B*/ + n_fields<GroundBatch>() * kPtr, "describe every array of GroundBatch in fields()");

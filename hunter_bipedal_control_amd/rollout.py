@@ -197,7 +197,7 @@ class ResidentLoop:
                  t_gait_start: float = 0.3, joint_ik: bool = True, substeps: int = 4, static_schedule_until: float = 0.0,
                  device_gait: bool = False, use_estimator: bool = False, sensor_config=None, sensor_bias=None, contact_config=None,
                  joint_model=None, actuator: str = "held", terrain=None, episode=None, model_variation=None, respawn=None, scenario=None,
-                 ground_map=None):
+                 ground_map=None, profile_draw=None):
         """static_schedule_until > 0: the mode schedules are uploaded once for [-1, static_schedule_until] (at most
         HB_MAX_EVENTS events) instead of a sliding window per MPC call — no per-call host work for large batches.
         device_gait: the device gait manager produces the windows; step() builds no per-instance list and uploads no schedule, and
@@ -235,7 +235,18 @@ class ResidentLoop:
         MPC tick, so that the policy a respawned instance is driven by is always one of its own episode; respawn_totals() reads the totals.
         scenario: a scenario drawn on the device for every respawned instance (hb_plant_set_scenario) — None: none; a dict of
         abi.make_scenario_config fields; an abi.HbScenarioConfig is taken as it is.  Needs respawn= (and contact_config=) and is set
-        after it; scenario() / scenario_log() read the current parameters and the log of the finished episodes."""
+        after it; scenario() / scenario_log() read the current parameters and the log of the finished episodes.
+        profile_draw: a piecewise-planar ground (level, a curb or step-down, a flight of stairs) drawn on the device for every respawned
+        instance (hb_plant_set_profile_draw) — None: none; a dict of abi.make_profile_draw_config fields; an abi.HbProfileDrawConfig is
+        taken as it is.  Needs respawn= and contact_config=, excludes terrain= (the draw owns the ground) and is set after the scenario;
+        ground_map="draw" sets the zero map along the draw's direction and follow_map, so the controller's map follows every drawn
+        ground.  profile_draw() / profile_draw_log() read the current parameters and the log of the finished episodes."""
+        if profile_draw is not None and (respawn is None or contact_config is None):
+            raise ValueError("the profile is drawn at respawn, for the ground-contact plant: give respawn= and contact_config= as well")
+        if profile_draw is not None and terrain is not None:
+            raise ValueError("profile_draw draws the ground: no terrain= beside it")
+        if isinstance(ground_map, str) and ground_map == "draw" and profile_draw is None:
+            raise ValueError('ground_map="draw" follows the drawn profile: give profile_draw= as well')
         if scenario is not None and (respawn is None or contact_config is None):
             raise ValueError("the scenario is drawn at respawn, for the ground-contact plant: give respawn= and contact_config= as well")
         if respawn is not None and episode is None:
@@ -306,9 +317,11 @@ class ResidentLoop:
                         n = plane / np.linalg.norm(plane, axis=1, keepdims=True)
                         plane = np.concatenate([n, plane_under_contact_points(solver, q0, n)[:, None]], axis=1)
                 solver.plant_set_terrain(plane, terrain.get("mu"))
-        if isinstance(ground_map, str):
+        if isinstance(ground_map, str) and ground_map == "draw":
+            pass   # (the zero map goes in with the draw, below)
+        elif isinstance(ground_map, str):
             if ground_map != "plant" or terrain is None or terrain.get("profile") is None:
-                raise ValueError('ground_map is None, "plant" (with terrain=dict(profile=...)) or dict(dir=..., knots=...)')
+                raise ValueError('ground_map is None, "plant" (with terrain=dict(profile=...)), "draw" (with profile_draw=) or dict(dir=..., knots=...)')
             solver.ground_set_profile(plant_map["n_knots"], plant_map["dir"], plant_map["knots"])
         elif ground_map is not None:
             n_knots, knots = pack_profiles([np.asarray(k, dtype=float) for k in ground_map["knots"]])
@@ -326,6 +339,20 @@ class ResidentLoop:
         self.has_scenario = scenario is not None
         if scenario is not None:
             solver.plant_set_scenario(abi.make_scenario_config(**scenario) if isinstance(scenario, dict) else scenario)
+        self.has_profile_draw = profile_draw is not None
+        if profile_draw is not None:
+            follow = isinstance(ground_map, str) and ground_map == "draw"
+            if isinstance(profile_draw, dict):
+                fields = dict(profile_draw)
+                if follow:
+                    fields["follow_map"] = 1
+                profile_draw = abi.make_profile_draw_config(**fields)
+            if follow:
+                if not profile_draw.follow_map:
+                    raise ValueError('ground_map="draw" needs follow_map in the configuration given')
+                level = np.tile(np.array([[-1.0, 0.0], [1.0, 0.0]]), (self.B, 1, 1))
+                solver.ground_set_profile(np.full(self.B, 2), np.tile(np.array(profile_draw.dir[:]), (self.B, 1)), level)
+            solver.plant_set_profile_draw(profile_draw)
         # resident observation of the initial state
         rbd = np.zeros((self.B, 32))
         rbd[:, 0:3], rbd[:, 3:6], rbd[:, 6:16] = q0[:, 3:6], q0[:, 0:3], q0[:, 6:]
@@ -423,6 +450,35 @@ class ResidentLoop:
         if not self.has_scenario:
             raise ValueError("ResidentLoop was built without scenario=")
         return self.s.plant_scenario_log()
+
+
+    def profile_draw(self):
+        """row[B][HB_PD_N] of the grounds the running episodes stand on (HunterSolver.plant_profile_draw)."""
+        if not self.has_profile_draw:
+            raise ValueError("ResidentLoop was built without profile_draw=")
+        return self.s.plant_profile_draw()
+
+    def profile_draw_log(self) -> dict:
+        """The log of the finished episodes (HunterSolver.plant_profile_draw_log)."""
+        if not self.has_profile_draw:
+            raise ValueError("ResidentLoop was built without profile_draw=")
+        return self.s.plant_profile_draw_log()
+
+
+def profile_draw_table(log: dict) -> dict:
+    """The log of HunterSolver.plant_profile_draw_log as flat arrays over all finished episodes that were logged, instance by instance in
+    the order they finished: INSTANCE, the five abi.PROFILE_DRAW_LOG_HEAD fields (EPISODE, CAUSE and TICKS as integers) and the parameters
+    of abi.PROFILE_DRAW_FIELDS ([n] or [n][k]; KIND and STEPS as integers)."""
+    count, rows = np.asarray(log["count"]), np.asarray(log["log"])
+    inst = np.repeat(np.arange(len(count)), count)
+    flat = np.concatenate([rows[i, :count[i]] for i in range(len(count))], axis=0) if len(count) else np.zeros((0, abi.HB_PD_LOG_W))
+    flat = flat.reshape(-1, abi.HB_PD_LOG_W)
+    out = dict(INSTANCE=inst)
+    for k, name in enumerate(abi.PROFILE_DRAW_LOG_HEAD):
+        out[name] = flat[:, k].astype(np.int64) if name in ("EPISODE", "CAUSE", "TICKS") else flat[:, k].copy()
+    out.update(abi.split_profile_draw(flat[:, len(abi.PROFILE_DRAW_LOG_HEAD):]))
+    out["KIND"], out["STEPS"] = out["KIND"].astype(np.int64), out["STEPS"].astype(np.int64)
+    return out
 
 
 def scenario_table(log: dict) -> dict:

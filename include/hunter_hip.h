@@ -733,6 +733,109 @@ int32_t hb_plant_get_scenario(hb_ctx* ctx, double* scen);
  * Synchronises.  HB_ERR_STATE without a scenario in force. */
 int32_t hb_plant_get_scenario_log(hb_ctx* ctx, int32_t* count, double* log);
 
+/* ---- profile draw at respawn: level ground, a curb / step-down or a flight of stairs per episode, on the device --------------------------
+ * With a profile draw in force, hb_plant_respawn draws a new piecewise-planar ground (the terrain profile above) for every instance it
+ * respawns: a kernel of its own (k_plant_profile_draw), enqueued ahead of k_plant_respawn (and behind k_plant_scenario if a scenario is
+ * in force too) in the same call, reads the same decision from the still unchanged episode record, and for a respawning instance, in this
+ * order, (a) appends the log row of the finished episode, (b) draws, (c) composes the knots and from them the stored profile record, (d)
+ * writes the profile record, the knot row, the parameter row row[HB_PD_N] and, with follow_map, the record of the controller's ground map.
+ * k_plant_respawn then places the robot on the profile it finds (below).  An instance that stays costs the decision loads and an exit: NOT
+ * ONE BYTE of it is written.  Off by default; without a draw every call enqueues exactly what it enqueues without this block.  Episode 0
+ * (the state of hb_plant_reset) is never drawn.
+ *
+ * The draw.  Philox4x32-10, u_k = (word k + 0.5) 2^-32 as for the scenario (above):
+ *       key = (seed low 32, seed high 32) of THIS configuration's seed;  counter = (instance_offset + i, e, HB_PD_STREAM, block),
+ * instance_offset from the respawn configuration in force, e = EPISODE_INDEX + 1 the episode that starts.  Every operation below is an
+ * IEEE double operation of its own in the order written, brackets first, nothing fused; there is no transcendental function in it.  The
+ * three blocks are independent and always generated.  a = (a_x, a_y) is the stored unit direction (dir / sqrt(dir_x dir_x + dir_y dir_y),
+ * the division of the terrain profile);  s0 = a_x q_spawn[0] + a_y q_spawn[1] of the respawn configuration;  gz = ground_z of the contact
+ * model.
+ *   block 0:  kind = list[int(u_0 n)], list = the enabled kinds in ascending bit order, n their number;
+ *             h = height_lo + (height_hi - height_lo) u_1;
+ *             s_r = s0 + (at_lo + (at_hi - at_lo) u_2);
+ *             steps = steps_lo + int(u_3 (steps_hi - steps_lo + 1))   (<= steps_hi for every word).
+ *   block 1:  r = run_lo + (run_hi - run_lo) u_0.
+ *   block 2:  mu_c = mu_lo + (mu_hi - mu_lo) u_c,  c = 0..3;  with mu_per_point = 0 all four points take c = 0's value.
+ *   w = max(|h| / riser_slope, 1e-3), the width of a riser.
+ * Relative knots (s, g), K of them:
+ *   HB_PD_FLAT    K = 2:           (s0 - 1, 0), (s0 + 1, 0);
+ *   HB_PD_CURB    K = 4:           (s_r - 1, 0), (s_r, 0), (s_r + w, h), ((s_r + w) + 1, h);
+ *   HB_PD_STAIRS  K = 2 + 2 steps: (s_r - 1, 0);  for i = 0 .. steps - 1: (s_r + i r, i h), ((s_r + i r) + w, (i + 1) h);
+ *                                  ((s_r + steps r) + 1, steps h)          (i, i + 1, steps converted to double, then one product).
+ * The plant's knots are (s, 0 + (gz + g)); its stored record is what hb_plant_set_terrain_profile stores for K, dir, these knots and mu,
+ * bit for bit (one routine, csrc/hb_contact.hpp profile_compose, behind both).  With follow_map the controller's map takes the knots
+ * (s, 0 + g) and stores what hb_ground_set_profile stores for them (csrc/hb_ground.hpp ground_compose).
+ *
+ * row[HB_PD_N]: KIND (the bit value), HEIGHT = h (STAIRS: the rise of one step), AT = at_lo + (at_hi - at_lo) u_2 (the bracket of s_r as computed), STEPS,
+ * RUN = r, MUS[4].  Entries a kind does not use are 0 (FLAT: HEIGHT, AT, STEPS, RUN; CURB: STEPS, RUN).  Before an instance's first draw
+ * the row is zero (KIND 0).
+ * Log: up to log_capacity rows of HB_PD_LOG_W doubles per instance, appended in order until full: the finished episode's index
+ * (EPISODE_INDEX before the fold), its cause, TICKS, the progress a_x (LAST_BASE[0] - START_POS[0]) + a_y (LAST_BASE[1] - START_POS[1]),
+ * TILT_MAX of its record, then the HB_PD_N parameters it ran under.
+ *
+ * Placement on a profile (k_plant_respawn, whenever a profile is in force at a respawn).  Step 3 of the respawn becomes vertical: contact
+ * point c at p_c takes the facet j_c under it (the segment rule of the terrain profile) with (n_c, d_c);  gap_c = ((n_x x + n_y y) + n_z
+ * z) - d;  D = max over c of (clearance - gap_c) / n_{c,z};  q[2] += D  (place = 0: no shift).  A vertical shift changes no s, hence no
+ * facet, and the lowest gap_c becomes clearance to rounding.  On a level profile D is the shift of step 3 on the level plane, bit for
+ * bit.  After placement, either way, the kernel writes the segment under the four contact points and the base origin and the Terrain
+ * record of the facet under the base origin (what hb_plant_reset's host locate writes), and the new episode record measures height
+ * against that facet.
+ *
+ * Validity.  The device cannot refuse a draw, so the set call admits only configurations all of whose draws the terrain profile accepts.
+ * With |s0| <= 1e3, |at| <= 1e3, run_hi <= 1e3 and |gz| <= 1e3 every knot has |s| < 1.1e4 and |z| < 1.4e4, so a rounding moves a knot by
+ * at most 2^-39 m.  s is strictly increasing: lead and tail are 1 m long, a riser is w >= 1e-3 wide, and a tread is at least run_lo - w
+ * >= 1e-3 long before rounding (the third refusal below).  Treads and landings have slope exactly 0: both ends carry the same product.
+ * A riser has |m| <= (|h| + 4e-12) / (w - 2e-12) <= riser_slope + 1e-8 whether w is |h| / riser_slope or the floor 1e-3; with riser_slope
+ * <= 1.7, which is 1.8 % under sqrt(3), that is below the profile's limit.  K <= 2 + 2 * 7 = HB_PROFILE_MAX_KNOTS, and mu_c lies in
+ * [mu_lo, mu_hi].
+ * HB_ERR_ARG (the configuration in force is kept) for: a non-finite field; riser_slope outside (0, 1.7];  run_lo - max(max(|height_lo|,
+ * |height_hi|) / riser_slope, 1e-3) < 1e-3;  |at_lo| or |at_hi| above 1e3;  run_hi above 1e3;  lo > hi in any range, steps outside 1 .. 7,
+ * mu_lo < 0;  |dir| = 0;  kinds outside 1 .. 7;  mu_per_point or follow_map not 0 / 1;  log_capacity outside 0 .. HB_PD_LOG_MAX;  a
+ * nonzero `reserved`.
+ *
+ * State.  HB_ERR_STATE before hb_plant_reset, outside contact model 1, without a respawn configuration in force, while a scenario with
+ * HB_SC_SLOPE or HB_SC_MU is in force (the other order is refused by hb_plant_set_scenario: a profile is then in force; PAYLOAD, MASS and
+ * PUSH combine freely with the draw), with follow_map and no ground map in force (set the zero map first), and when |ground_z| or the
+ * |s0| of an instance's q_spawn exceeds 1e3.  Setting the draw puts every instance on the level profile (the FLAT knots around its s0,
+ * cfg.mu) located at the plant's current state, replacing a terrain of hb_plant_set_terrain, clears the contact impulses as
+ * hb_plant_set_terrain_profile does, and restarts the rows and the log; with follow_map the controller's map becomes the zero map over
+ * the same knots, so plant and map start level together, also when the call replaces a draw in force.  A configuration in force is
+ * switched off before the new one's arrays are allocated and written: HB_ERR_ARG and HB_ERR_STATE keep it, HB_ERR_DEVICE leaves the
+ * draw off.  While the draw is in force hb_plant_set_terrain and every hb_plant_set_terrain_profile, the switch-off call included,
+ * return HB_ERR_STATE (hb_plant_set_respawn with a configuration is refused anyway: a profile is in force), hb_plant_set_contact_model refuses a |ground_z| above 1e3 with HB_ERR_ARG, and hb_plant_get_terrain_profile,
+ * hb_ground_get_profile and hb_plant_reset read the device records first (the host copies are stale).  cfg NULL, turning respawn or the
+ * episode off switch the draw off: profile and map stay in force as last drawn, the host copies are refreshed, and respawn, if still on,
+ * keeps placing on the profile.  Leaving model 1 switches draw and profile off.  hb_plant_reset empties the log; records and rows stay.
+ * Out of scope: a draw for episode 0, a direction per episode, two-dimensional ground, the instance-range / graph paths. */
+#define HB_PD_STREAM 0x50444431u /* third counter word; differs from HB_RS_STREAM and HB_SC_STREAM */
+enum { HB_PD_FLAT = 1, HB_PD_CURB = 2, HB_PD_STAIRS = 4 }; /* kinds */
+enum { HB_PD_KIND = 0, HB_PD_HEIGHT = 1, HB_PD_AT = 2, HB_PD_STEPS = 3, HB_PD_RUN = 4, HB_PD_MUS = 5 /* [4] */, HB_PD_N = 9 }; /* row */
+#define HB_PD_LOG_W (5 + HB_PD_N) /* finished episode's index, cause, TICKS, progress, TILT_MAX, then its HB_PD_N parameters */
+#define HB_PD_LOG_MAX 1024
+typedef struct hb_profile_draw_config {
+  uint64_t seed;
+  int32_t kinds;              /* OR of HB_PD_*, at least one */
+  int32_t mu_per_point;       /* 0: one coefficient for the four points; 1: one each */
+  double dir[2];              /* |dir| > 0, normalised as the terrain profile normalises it */
+  double height_lo, height_hi;/* m, signed (negative: down), lo <= hi: curb height / stair rise */
+  double at_lo, at_hi;        /* m along dir from the spawn point to the first riser, lo <= hi, |.| <= 1e3 */
+  double riser_slope;         /* (0, 1.7] */
+  int32_t steps_lo, steps_hi; /* 1 <= lo <= hi <= 7 */
+  double run_lo, run_hi;      /* m, tread length incl. riser, lo <= hi <= 1e3 */
+  double mu_lo, mu_hi;        /* 0 <= lo <= hi */
+  int32_t follow_map;         /* 0 / 1: the controller's ground map follows the drawn profile */
+  int32_t log_capacity;       /* 0 .. HB_PD_LOG_MAX finished episodes kept per instance */
+  int32_t reserved[2];        /* 0 */
+} hb_profile_draw_config;
+/* cfg NULL: off. */
+int32_t hb_plant_set_profile_draw(hb_ctx* ctx, const hb_profile_draw_config* cfg);
+/* row[batch][HB_PD_N]: the parameters every instance's current ground was drawn with.  Synchronises like hb_plant_get_episode.
+ * HB_ERR_STATE without a profile draw in force. */
+int32_t hb_plant_get_profile_draw(hb_ctx* ctx, double* row);
+/* count[batch] = rows logged per instance, log[batch][log_capacity][HB_PD_LOG_W] (rows behind count are zero); either may be NULL.
+ * Synchronises.  HB_ERR_STATE without a profile draw in force. */
+int32_t hb_plant_get_profile_draw_log(hb_ctx* ctx, int32_t* count, double* log);
+
 /* ---- sensors from the plant: what LeggedController::updateStateEstimation reads, computed on the device -----------
  * hb_plant_sense turns the plant's state into the sensor arrays of hb_estimator_update and leaves them on the device
  * (plant-owned arrays [batch][4|3|3|10|10|10] and int [batch][4]); hb_estimator_update_resident /

@@ -17,6 +17,11 @@
                                                         metres ahead of the base origin, trot across it (hb_plant_set_terrain_profile);
                                                         --ground-map: the controller plans and filters on the plant's profile
                                                         (hb_ground_set_profile) instead of on the level plane
+    python tools/sweep_rollout.py --random-curbs 3000 --robots 256 --max-ticks 1000   repeated episodes on a ground drawn on the device per episode: level, a curb
+                                                        or step-down of -3 .. 3 cm, or a flight of 1 .. 4 stairs (hb_plant_set_profile_draw);
+                                                        survival, progress and tilt by kind and height bin, from one run(n) and one
+                                                        read-back of the draw's log.  --ground-map: the controller's map follows every drawn
+                                                        ground; --joint-model as everywhere
     python tools/sweep_rollout.py --readback            the two sweeps once more with the per-tick read-back loop the findings of items 17 - 20
                                                         were made with, for the wall time per tick of both
 
@@ -31,7 +36,8 @@ import numpy as np
 
 sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
 from hunter_bipedal_control_amd import abi, ingest  # noqa: E402
-from hunter_bipedal_control_amd.rollout import ResidentLoop, curb_profile, episode_summary, payload_on_base, respawn_summary, scenario_table  # noqa: E402
+from hunter_bipedal_control_amd.rollout import (ResidentLoop, curb_profile, episode_summary, payload_on_base, profile_draw_table,  # noqa: E402
+                                                respawn_summary, scenario_table)
 from hunter_bipedal_control_amd.solver import HunterSolver  # noqa: E402
 
 FRICTION = [0.7, 0.5, 0.4, 0.3, 0.2, 0.15, 0.1, 0.05]
@@ -144,6 +150,58 @@ def run_randomize(params, robots, ticks, max_ticks, joint_model=None, host_drive
         s.close()
 
 
+RANDOM_CURBS = dict(kinds=abi.HB_PD_ALL, dir=(1.0, 0.0), height_lo=-0.03, height_hi=0.03, at_lo=0.05, at_hi=0.25, riser_slope=1.7, steps_lo=1,
+                    steps_hi=4, run_lo=0.2, run_hi=0.3, mu_lo=0.7, mu_hi=0.7, seed=3)
+
+
+def run_random_curbs(params, robots, ticks, max_ticks, joint_model=None, ground_map=False):
+    """Repeated episodes on a newly drawn ground each -> (log of the draw, respawn totals, wall seconds of the ticks)."""
+    B = robots
+    s = HunterSolver(params, batch=B, max_nodes=108)
+    try:
+        horizon = 100 * params["config"]["dt"]
+        # (fall_height 0.2 as in run_curb: the fall test is measured along the normal of the facet under the base origin)
+        loop = ResidentLoop(s, params, ["trot"] * B, np.tile([0.2, 0.0, 0.0, 0.0], (B, 1)), contact_config=dict(fall_height=0.2), joint_model=joint_model,
+                            static_schedule_until=ticks * 0.002 + horizon + 1.5, episode=dict(slip_speed=0.05),
+                            respawn=dict(RANDOMIZE_RESPAWN, max_ticks=max_ticks),
+                            profile_draw=dict(RANDOM_CURBS, log_capacity=min(abi.HB_PD_LOG_MAX, ticks // 8 + 1)), ground_map="draw" if ground_map else None)
+        s.sync()
+        t0 = time.perf_counter()
+        loop.run(ticks)
+        log = loop.profile_draw_log()
+        return log, loop.respawn_totals(), time.perf_counter() - t0
+    finally:
+        s.close()
+
+
+def print_random_curbs(log, bins=3):
+    """Survival rate (episodes that ended by time-out), median progress along the direction, median of the largest tilt and mean ticks by
+    kind, and for curbs and stairs by height bin, from the log alone."""
+    t = profile_draw_table(log)
+    drawn = t["EPISODE"] > 0                       # (episode 0 ran on the level ground of the start, not on a draw)
+    print(f"   {len(t['EPISODE'])} finished episodes logged, {int(drawn.sum())} of them on a drawn ground")
+    survived = t["CAUSE"] == abi.HB_RS_TIMEOUT
+    heads = ("kind", "height", "episodes", "survival", "progress med", "tiltmax med", "ticks")
+    print("   " + " ".join(f"{h:>16}" for h in heads))
+
+    def row(kind, label, m):
+        # (medians: a robot that is lost can leave very large values at its last finite tick)
+        cells = (kind, label, f"{int(m.sum())}") + ((f"{survived[m].mean():.3f}", f"{np.median(t['PROGRESS'][m]):.4f}", f"{np.median(t['TILT_MAX'][m]):.4f}",
+                                                     f"{t['TICKS'][m].mean():.1f}") if m.any() else ("-",) * 4)
+        print("   " + " ".join(f"{c:>16}" for c in cells))
+
+    row("flat", "0", drawn & (t["KIND"] == abi.HB_PD_FLAT))
+    for name, kind in (("curb", abi.HB_PD_CURB), ("stairs", abi.HB_PD_STAIRS)):
+        of = drawn & (t["KIND"] == kind)
+        if not of.any():
+            row(name, "-", of)
+            continue
+        edges = np.linspace(t["HEIGHT"][of].min(), t["HEIGHT"][of].max(), bins + 1)
+        which = np.clip(np.searchsorted(edges, t["HEIGHT"], side="right") - 1, 0, bins - 1)
+        for b in range(bins):
+            row(name, "[%.3g, %.3g]" % (edges[b], edges[b + 1]), of & (which == b))
+
+
 def print_randomize(log, bins=4):
     """Survival rate (episodes that ended by time-out) and mean ticks, binned by mu, |grade| and payload mass, from the log alone."""
     t = scenario_table(log)
@@ -224,11 +282,12 @@ def main():
     ap.add_argument("--joint-model", action="store_true", help="the joints of the reference's MuJoCo model instead of ideal joints")
     ap.add_argument("--respawn", type=int, metavar="N_TICKS", help="the friction sweep as repeated episodes of at most N_TICKS ticks, from the respawn totals")
     ap.add_argument("--randomize", type=int, metavar="N_TICKS", help="N_TICKS ticks of repeated episodes with slope, friction, payload and a push drawn on the device per episode; one read-back")
-    ap.add_argument("--robots", type=int, default=64, help="batch of --randomize")
-    ap.add_argument("--max-ticks", type=int, default=400, help="time-out of an episode of --randomize")
+    ap.add_argument("--random-curbs", type=int, metavar="N_TICKS", help="N_TICKS ticks of repeated episodes on level ground, a curb / step-down or stairs drawn on the device per episode; one read-back")
+    ap.add_argument("--robots", type=int, default=64, help="batch of --randomize / --random-curbs")
+    ap.add_argument("--max-ticks", type=int, default=400, help="time-out of an episode of --randomize / --random-curbs")
     ap.add_argument("--host-driven", action="store_true", help="--randomize with the host calling the setters per respawn round and uploading a wrench per tick")
     ap.add_argument("--curb", action="store_true", help="one curb / step-down height per robot (0, 1, 2, 3 cm down and up), trot across it; from the episode record alone")
-    ap.add_argument("--ground-map", action="store_true", help="--curb with the controller's ground map set to the plant's profile (hb_ground_set_profile)")
+    ap.add_argument("--ground-map", action="store_true", help="--curb with the controller's ground map set to the plant's profile (hb_ground_set_profile); --random-curbs with the map following every drawn ground")
     ap.add_argument("--curb-at", type=float, default=0.08, help="where the riser of --curb starts, metres ahead of the base origin of the start")
     ap.add_argument("--riser-slope", type=float, default=float(np.sqrt(3.0)), help="slope of the riser of --curb (at most sqrt(3))")
     ap.add_argument("--readback", action="store_true", help="also time the per-tick read-back loop on the two sweeps")
@@ -240,6 +299,14 @@ def main():
         print(f"-- curb sweep, {'controller on the ground map' if args.ground_map else 'controller blind'}, B = {len(CURBS)}, riser of slope {args.riser_slope:.3g} {args.curb_at} m ahead, {args.ticks} ticks, run(): {1e3 * wall / args.ticks:.3f} ms per tick")
         table("height", CURBS, rec)
         print("   segment under the four contact points and the base at the end (0 before the riser, 1 on it, 2 beyond):", seg.tolist())
+        return
+    if args.random_curbs:
+        log, tot, wall = run_random_curbs(params, args.robots, args.random_curbs, args.max_ticks, joint_model=jm, ground_map=args.ground_map)
+        print(f"-- a ground drawn per episode, {'controller on the map that follows' if args.ground_map else 'controller blind'}, "
+              f"{'joint model' if args.joint_model else 'ideal joints'}, B = {args.robots}, {args.random_curbs} ticks, episodes of at most {args.max_ticks} "
+              f"ticks, run() and one read-back: {wall:.3f} s, {1e3 * wall / args.random_curbs:.3f} ms per tick")
+        print(f"   episodes {int(tot['EPISODES'].sum())}: fallen {int(tot['N_FALLEN'].sum())}, non-finite {int(tot['N_NONFINITE'].sum())}, timed out {int(tot['N_TIMEOUT'].sum())}")
+        print_random_curbs(log)
         return
     if args.randomize:
         log, tot, wall = run_randomize(params, args.robots, args.randomize, args.max_ticks, joint_model=jm, host_driven=args.host_driven)
