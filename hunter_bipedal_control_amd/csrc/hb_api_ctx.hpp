@@ -1,6 +1,6 @@
 // Host side of libhunter_hip.so, part 1: the context, the helpers every entry point shares (errors, entry prologue, instance-range
-// check, allocation and copies derived from the layout descriptions of hb_layout.hpp, pinned staging, lazy join) and hb_create /
-// hb_destroy / hb_sync / hb_get_stats.  Included by hb_kernels.hip only.
+// check, allocation on first use, copies and zero fills derived from the layout descriptions of hb_layout.hpp, the growable per-instance
+// logs, the refusal texts, pinned staging, lazy join) and hb_create / hb_destroy / hb_sync / hb_get_stats.  Included by hb_kernels.hip only.
 #pragma once
 
 // Error text of the last failed call, per calling thread (errno-like): the reference drives one solver from two threads
@@ -249,6 +249,29 @@ static hipError_t alloc_fields(hb_ctx* ctx, S& s, const char** failed = nullptr)
   return e;
 }
 
+// Allocate on first use: the arrays of s are there once the LAST one of its description is (alloc_fields goes in that order), so an
+// allocation that failed half way is repeated by the next call.  ensure_fields also sets s.B where s has one; *fresh: this call allocated.
+template <class S>
+static bool has_fields(const hb_ctx* ctx, const S& s) {
+  S v = s;
+  const void* last = nullptr;
+  fields(v, ctx->Nmax, [&](const char*, auto*& p, Extent) { last = p; });
+  return last != nullptr;
+}
+template <class S>
+static auto set_batch_size(S& s, int B, int) -> decltype(void(s.B)) { s.B = B; }
+template <class S>
+static void set_batch_size(S&, int, long) {}
+template <class S>
+static int32_t ensure_fields(hb_ctx* ctx, S& s, bool* fresh = nullptr) {
+  const bool need = !has_fields(ctx, s);
+  if (fresh) *fresh = need;
+  if (!need) return HB_OK;
+  HB_HIP(alloc_fields(ctx, s));
+  set_batch_size(s, ctx->B, 0);
+  return HB_OK;
+}
+
 // Instances [i0, i0 + cnt) of the batch, cnt >= min_cnt, in a form that cannot overflow.
 struct Range { int i0, cnt; };
 static bool range_ok(const hb_ctx* ctx, int32_t i0, int32_t cnt, int32_t min_cnt) {
@@ -296,6 +319,60 @@ static int32_t pull_slot_major(hb_ctx* ctx, T* host, S& batch, T* const& field, 
 // elements of the whole batch's `field`
 template <class S, class T>
 static size_t field_count(hb_ctx* ctx, S& batch, T* const& field) { return size_t(ctx->B) * extent_of(batch, ctx->Nmax, field).n; }
+// the whole batch's `field` back to zero: on *s when a stream is given, blocking otherwise
+template <class S, class T>
+static int32_t zero_field(hb_ctx* ctx, S& batch, T* const& field, const hipStream_t* s = nullptr) {
+  const size_t bytes = field_count(ctx, batch, field) * sizeof(T);
+  if (s) HB_HIP(hipMemsetAsync(field, 0, bytes, *s));
+  else HB_HIP(hipMemset(field, 0, bytes));
+  return HB_OK;
+}
+
+// Per-instance log [B][cap][W] of doubles whose extent is set at run time (episode trace, scenario log, profile-draw log: no description
+// names them).  log_grow: (log, cap) to `want` rows where that is more; the allocation grows to the largest capacity asked for.
+static int32_t log_grow(hb_ctx* ctx, double*& log, int& cap, int want, int W) {
+  if (want <= cap) return HB_OK;
+  if (log) {
+    ctx->allocs.erase(std::remove(ctx->allocs.begin(), ctx->allocs.end(), static_cast<void*>(log)), ctx->allocs.end());
+    HB_HIP(hipFree(log));
+    log = nullptr;
+    cap = 0;
+  }
+  HB_HIP(dalloc(ctx, &log, size_t(ctx->B) * want * W));
+  cap = want;
+  return HB_OK;
+}
+// log_zero: every row back to zero (no log: nothing), on *s when a stream is given, blocking otherwise
+static int32_t log_zero(hb_ctx* ctx, double* log, int cap, int W, const hipStream_t* s = nullptr) {
+  const size_t bytes = size_t(ctx->B) * cap * W * sizeof(double);
+  if (log && s) HB_HIP(hipMemsetAsync(log, 0, bytes, *s));
+  else if (log) HB_HIP(hipMemset(log, 0, bytes));
+  return HB_OK;
+}
+// log_read: host[B][in_force][W] out of the device's [B][cap][W] (the device rows have the pitch of the largest capacity set so far, the
+// caller's the pitch of the one in force); a null host pointer or in_force = 0 is skipped
+static int32_t log_read(hb_ctx* ctx, double* host, const double* log, int cap, int in_force, int W) {
+  const size_t row = size_t(in_force) * W * sizeof(double);
+  if (host && row) HB_HIP(hipMemcpy2D(host, row, log, size_t(cap) * W * sizeof(double), row, size_t(ctx->B), hipMemcpyDeviceToHost));
+  return HB_OK;
+}
+
+// The refusals that name their caller.  refuse_state: "who: why" (HB_ERR_STATE), nothing to refuse when why is null; refuse_config: a
+// configuration's own refusal text (HB_ERR_ARG), likewise; refuse_instance: what instance i brings, with `code`.  `kept`: what stays in force.
+static int32_t refuse_state(hb_ctx* ctx, const char* who, const char* why) {
+  if (!why) return HB_OK;
+  ctx->err = std::string(who) + ": " + why;
+  return HB_ERR_STATE;
+}
+static int32_t refuse_config(hb_ctx* ctx, const char* who, const char* why) {
+  if (!why) return HB_OK;
+  ctx->err = std::string(who) + ": " + why + " (the configuration in force is kept)";
+  return HB_ERR_ARG;
+}
+static int32_t refuse_instance(hb_ctx* ctx, int32_t code, const char* who, size_t i, const char* why, const char* kept) {
+  ctx->err = std::string(who) + ": instance " + std::to_string(i) + " has " + why + " (the " + kept + " in force is kept)";
+  return code;
+}
 
 // Upload of a caller-owned host array through pinned staging (see hb_ctx::stage): returns as soon as the bytes are in the slot.
 // Each array id belongs to one side of the two-thread split (control side: time, sensors; MPC side: t0, cmd, x0; hb_tick_resident,

@@ -1,4 +1,4 @@
-// Host side, part 8: the ground map of the controller (hb_ground_*; include/hunter_hip.h above hb_ground_set_profile).  The stored
+// Host side, part 10: the ground map of the controller (hb_ground_*; include/hunter_hip.h above hb_ground_set_profile).  The stored
 // record of an instance, validation included, is hb_ground.hpp ground_record; the kernels that read it are the ground forms of the
 // planner and the filter (launch_refgen, launch_estimator).
 #pragma once
@@ -13,20 +13,15 @@ int32_t hb_ground_set_profile(hb_ctx* ctx, const int32_t* n_knots, const double*
   std::vector<double> rec(on ? B * Ground::size : 0), kn(on ? B * HB_PROFILE_MAX_KNOTS * 2 : 0);
   for (size_t i = 0; i < B && on; ++i) {
     const double* k = knots + i * HB_PROFILE_MAX_KNOTS * 2;
-    if (const char* why = ground_record(n_knots[i], dir + 2 * i, k, rec.data() + i * Ground::size)) {
-      ctx->err = "hb_ground_set_profile: instance " + std::to_string(i) + " has " + why + " (the map in force is kept)";
-      return HB_ERR_ARG;
-    }
+    if (const char* why = ground_record(n_knots[i], dir + 2 * i, k, rec.data() + i * Ground::size))
+      return refuse_instance(ctx, HB_ERR_ARG, "hb_ground_set_profile", i, why, "map");
     std::memcpy(kn.data() + i * HB_PROFILE_MAX_KNOTS * 2, k, size_t(n_knots[i]) * 2 * sizeof(double));
   }
   HB_ENTER_DEVICE();
   HB_TRY(hb_sync(ctx));   // (a pass in flight still runs on the map it was launched with)
   if (on) {
     GroundBatch& g = ctx->ground;
-    if (!g.map) {
-      HB_HIP(alloc_fields(ctx, g));
-      g.B = ctx->B;
-    }
+    HB_TRY(ensure_fields(ctx, g));
     HB_TRY(push(ctx, rec.data(), g, g.map, whole(ctx)));
     ctx->ground_host = std::move(rec);
     ctx->ground_knots = std::move(kn);

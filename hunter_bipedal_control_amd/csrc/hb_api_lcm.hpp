@@ -1,4 +1,4 @@
-// Host side, part 6: the LCM wire format (include/hunter_lcm.h) and the entry points that speak it: the controller end and the simulator end.
+// Host side, part 8: the LCM wire format (include/hunter_lcm.h) and the entry points that speak it: the controller end and the simulator end.
 #pragma once
 
 extern "C" {
@@ -120,7 +120,7 @@ int32_t hb_plant_step_lcm(hb_ctx* ctx, const uint8_t* low_cmd, const int32_t* co
   for (int i = 0; i < ctx->B; ++i)
     HB_FAIL_IF(lcm_get64(low_cmd + size_t(i) * HB_LCM_LOW_CMD_BYTES) != fp, HB_ERR_ARG, "hb_plant_step_lcm: a message does not carry the low_cmd_t fingerprint");
   HB_ENTER_DEVICE();
-  HB_TRY(actuator_alloc(ctx));
+  HB_TRY(ensure_fields(ctx, ctx->act));
   ActuatorBatch& a = ctx->act;
   hipStream_t s = ctx->s_wbc;
   HB_HIP(hipMemcpyAsync(a.wire_cmd, low_cmd, field_count(ctx, a, a.wire_cmd) * 8, hipMemcpyHostToDevice, s));
@@ -138,7 +138,7 @@ int32_t hb_plant_sense_lcm(hb_ctx* ctx, int64_t timestamp_ns, uint8_t* low_state
   HB_FAIL_IF(!low_state && !full_state, HB_ERR_ARG, "hb_plant_sense_lcm: give low_state, full_state or both");
   HB_FAIL_IF(!ctx->plant_ready, HB_ERR_STATE, "hb_plant_sense_lcm: call hb_plant_reset first");
   HB_ENTER_DEVICE();
-  HB_TRY(actuator_alloc(ctx));
+  HB_TRY(ensure_fields(ctx, ctx->act));
   HB_TRY(hb_plant_sense(ctx, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr));   // (enqueue-only: the arrays stay on the device)
   ActuatorBatch& a = ctx->act;
   const PlantBatch& p = ctx->plant;

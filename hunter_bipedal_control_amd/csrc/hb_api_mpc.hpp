@@ -214,7 +214,7 @@ static int32_t mpc_solve_batch(hb_ctx* ctx) {
   if (respawned) {
     hipLaunchKernelGGL(k_cold_start, dim3(ctx->Nmax + 1, ctx->B), dim3(64), 0, ctx->s_mpc, ctx->b, ctx->dmodel, ctx->respawn.mpc_pending);
     HB_HIP(hipGetLastError());
-    HB_HIP(hipMemsetAsync(ctx->respawn.mpc_pending, 0, size_t(ctx->B), ctx->s_mpc));
+    HB_TRY(zero_field(ctx, ctx->respawn, ctx->respawn.mpc_pending, &ctx->s_mpc));
   }
   HB_TRY(enqueue_sqp(ctx, ctx->b, 0, ctx->s_mpc, true));
   std::lock_guard<std::mutex> lk(ctx->mtx);
@@ -295,7 +295,7 @@ int32_t hb_mpc_get_certificate(hb_ctx* ctx, int32_t inst_begin, int32_t inst_cou
   HB_TRY(mpc_records_current(ctx, "hb_mpc_get_certificate"));
   HB_ENTER_DEVICE();
   MpcCertBuf& m = ctx->mcert;
-  if (!m.node) HB_HIP(alloc_fields(ctx, m));
+  HB_TRY(ensure_fields(ctx, m));
   const Range r{inst_begin, inst_count};
   const Batch b = view(ctx->b, ctx->Nmax, inst_begin, inst_count);
   const MpcCertBuf v = from_instance(m, ctx->Nmax, inst_begin);

@@ -1,4 +1,4 @@
-// Host side, part 7: instance ranges (hb_set_chunks), hb_step_resident, hb_tick_resident and the range graphs.
+// Host side, part 9: instance ranges (hb_set_chunks), hb_step_resident, hb_tick_resident and the range graphs.
 #pragma once
 
 extern "C" {

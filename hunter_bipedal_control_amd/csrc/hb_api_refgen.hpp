@@ -6,11 +6,9 @@ extern "C" {
 int32_t hb_refgen_reset(hb_ctx* ctx, const hb_refgen_config* cfg, const double* latest_stance) {
   HB_ENTER(!cfg || !(cfg->dt > 0.0));
   RefgenBatch& r = ctx->rg;
-  if (!r.n_ev) {
-    HB_HIP(alloc_fields(ctx, r));
-    r.B = ctx->B;
-    ctx->rg_have_schedule.assign(size_t(ctx->B), 0);
-  }
+  bool fresh = false;
+  HB_TRY(ensure_fields(ctx, r, &fresh));
+  if (fresh) ctx->rg_have_schedule.assign(size_t(ctx->B), 0);
   ctx->rg_cfg = *cfg;
   r.init_stance = latest_stance ? 0 : 1;
   HB_TRY(push(ctx, latest_stance, r, r.stance, whole(ctx)));
@@ -86,7 +84,7 @@ int32_t hb_refgen_update(hb_ctx* ctx, const double* t0, double horizon, const do
   }
   launch_refgen(ctx, ctx->b, r, 0, horizon, s, respawned ? ctx->respawn.rg_pending : nullptr);
   HB_HIP(hipGetLastError());
-  if (respawned) HB_HIP(hipMemsetAsync(ctx->respawn.rg_pending, 0, size_t(ctx->B) * sizeof(int), s));
+  if (respawned) HB_TRY(zero_field(ctx, ctx->respawn, ctx->respawn.rg_pending, &s));
   r.init_stance = 0;
   ++ctx->mpc_tables_epoch;
   if (status) {
@@ -137,9 +135,10 @@ int32_t hb_gait_reset(hb_ctx* ctx, const hb_gait_config* cfg, const uint8_t* mas
   HB_ENTER_DEVICE();
   HB_TRY(hb_sync(ctx));
   GaitBatch& g = ctx->gait;
-  if (!g.n_ev) {
-    HB_HIP(alloc_fields(ctx, g));
-    g.B = g.stride = ctx->B;
+  bool fresh = false;
+  HB_TRY(ensure_fields(ctx, g, &fresh));
+  if (fresh) {
+    g.stride = ctx->B;
     mask = nullptr;   // first use: every instance starts as a fresh object
   }
   DevBuf<unsigned char> dmask;
@@ -190,7 +189,7 @@ int32_t hb_gait_insert_template(hb_ctx* ctx, int32_t i0, int32_t cnt, int32_t n_
 int32_t hb_gait_get_state(hb_ctx* ctx, int32_t i0, int32_t cnt, int32_t* level, double* vel_abs, double* vel_avg, double* cmd, int32_t* n_events,
                           double* event_times, int32_t* modes, int32_t* status) {
   HB_ENTER_ARGS(!range_ok(ctx, i0, cnt, 1));
-  HB_FAIL_IF(!ctx->gait.n_ev, HB_ERR_STATE, "hb_gait_get_state: call hb_gait_reset first");
+  HB_FAIL_IF(!has_fields(ctx, ctx->gait), HB_ERR_STATE, "hb_gait_get_state: call hb_gait_reset first");
   HB_ENTER_DEVICE();
   HB_HIP(hipStreamSynchronize(ctx->s_mpc));
   GaitBatch& g = ctx->gait;

@@ -1,4 +1,4 @@
-// Host side, part 8: unit-level entry points (one kernel or one routine on caller-given data, device scratch per call).
+// Host side, part 11: unit-level entry points (one kernel or one routine on caller-given data, device scratch per call).
 #pragma once
 
 extern "C" {

@@ -114,7 +114,7 @@ int32_t hb_wbc_update_direct(hb_ctx* ctx, const double* x_des, const double* u_d
   HB_TRY(push(ctx, rbd, w, w.rbd, all, &s));
   HB_TRY(push(ctx, mode, w, w.mode, all, &s));
   if (stance_flag) HB_TRY(push(ctx, stance_flag, w, w.stance, all, &s));
-  else HB_HIP(hipMemsetAsync(w.stance, 0, field_count(ctx, w, w.stance) * sizeof(int), s));
+  else HB_TRY(zero_field(ctx, w, w.stance, &s));
   HB_TRY(wbc_launch(ctx, false));
   HB_TRY(pull(ctx, sol, w, w.sol, all, &s));
   HB_TRY(pull(ctx, status, w, w.status, all, &s));
@@ -152,7 +152,7 @@ int32_t hb_wbc_set_certificate(hb_ctx* ctx, int32_t enable) {
   if (bool(enable) == ctx->wbc_cert) return HB_OK;
   HB_ENTER_DEVICE();
   HB_TRY(hb_sync(ctx));
-  if (enable && !ctx->wcert.cert) HB_HIP(alloc_fields(ctx, ctx->wcert));
+  if (enable) HB_TRY(ensure_fields(ctx, ctx->wcert));
   ctx->wbc_cert = enable != 0;
   ++ctx->graph_epoch;  // captured range graphs hold the other WBC kernel
   return HB_OK;
@@ -178,7 +178,7 @@ int32_t hb_hwbc_set_certificate(hb_ctx* ctx, int32_t enable) {
   if (bool(enable) == ctx->wbc_cert) return HB_OK;
   HB_ENTER_DEVICE();
   HB_TRY(hb_sync(ctx));
-  if (enable && !ctx->hcert.cert) HB_HIP(alloc_fields(ctx, ctx->hcert));
+  if (enable) HB_TRY(ensure_fields(ctx, ctx->hcert));
   ctx->wbc_cert = enable != 0;
   ++ctx->graph_epoch;  // captured range graphs hold the other WBC kernel
   return HB_OK;

@@ -144,7 +144,7 @@ inline bool use_ric_fwd_wave(const KernelForms& f, int concurrent) {
 // base forms otherwise — the base forms never see the map, so a context without one runs what it always ran.
 inline bool use_ground_forms(bool map_in_force) { return map_in_force; }
 
-// Plant step: which of the eighteen step kernels a launch takes (hb_api_est.hpp plant_launch names them).  Contact mode 0 is the pinned
+// Plant step: which of the eighteen step kernels a launch takes (hb_api_plant.hpp plant_launch names them).  Contact mode 0 is the pinned
 // stub (k_plant / k_plant_hybrid), which knows neither joints nor ground; in contact model 1 a profile goes before a model variation (the
 // profile kernels take the variation by pointer), a variation before a terrain (the varied kernels read the terrain array, where the
 // host keeps the level record while no terrain is in force), a terrain before the level ground.  `joints` and `hybrid` pick the kernel of

@@ -1799,6 +1799,8 @@ __global__ void k_estimator_reset(int B, double* xhat, double* P, double* yaw_la
 #include "hb_api_mpc.hpp"
 #include "hb_api_wbc.hpp"
 #include "hb_api_refgen.hpp"
+#include "hb_api_plant.hpp"
+#include "hb_api_episode.hpp"
 #include "hb_api_est.hpp"
 #include "hb_api_lcm.hpp"
 #include "hb_api_ranges.hpp"

@@ -5,7 +5,7 @@
 //                     both builds, over reserved in -1 .. 260 and a grid of (concurrent, Nmax, n_cu); prints "checked N" and
 //                     "mismatch ..." lines, exit status 1 if any.
 //   formsemu plant    compares plant_form, mapped to a kernel name the way plant_launch's switch does, with the two ladders of
-//                     hb_api_est.hpp it replaces (their conditions copied verbatim below), over contact mode 0 / 1, the sixteen
+//                     hb_api_est.hpp (since then hb_api_plant.hpp) it replaces (their conditions copied verbatim below), over contact mode 0 / 1, the sixteen
 //                     combinations of joints / terrain / variation / profile and held / hybrid; same output as check.
 #include <cstdio>
 #include <cstring>
@@ -31,7 +31,7 @@ int lq_trip_len(int sel, int concurrent, int Nmax, int n_cu) {
 bool one_node(int sel) { return sel == 129; }
 bool fwd_wave(int sel, int concurrent) { return sel == 114 || (sel != 111 && concurrent <= kRicFwdWaveMaxBatch); }
 
-// The plant: the conditions of the two ladders hb_plant_step and plant_launch_hybrid held (hb_api_est.hpp), rung by rung in their order;
+// The plant: the conditions of the two ladders hb_plant_step and plant_launch_hybrid held (then in hb_api_est.hpp), rung by rung in their order;
 // a rung returns the name of the kernel it launched.  `ctx` carries the five words of the context the rungs read.
 struct Ctx { struct { int mode; } contact_cfg; bool joints_on, terrain_on, modelvar_on, profile_on; };
 const char* plant_step(const Ctx* ctx) {
@@ -58,7 +58,7 @@ const char* plant_launch_hybrid(const Ctx* ctx) {
 }
 }  // namespace before
 
-// The kernel plant_launch (hb_api_est.hpp) launches for a form: its switch, by name.
+// The kernel plant_launch (hb_api_plant.hpp) launches for a form: its switch, by name.
 static std::string plant_kernel(const hb::PlantForm& f) {
   using G = hb::PlantForm::Ground;
   const char* tail = f.hybrid ? "_hybrid" : "";

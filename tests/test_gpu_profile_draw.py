@@ -432,6 +432,29 @@ def test_api_behaviour(params):
         s.close()
 
 
+def test_a_smaller_log_in_a_larger_allocation(params):
+    """log_capacity 3 and then 2 in one context (the device rows keep the pitch of 3) against a fresh context with 2 alone: the draw is
+    stateless per seed, instance and episode, so count and log are equal array for array."""
+    draw = pd.CONFIGS["gpu_draw"]
+    logs = []
+    for capacities in ((3, 2), (2,)):
+        s, _ = _open(params, 3, RESPAWN, dict(draw, log_capacity=capacities[0]))
+        try:
+            for cap in capacities[1:]:
+                s.plant_set_profile_draw(abi.make_profile_draw_config(**dict(draw, log_capacity=cap)))
+            tau, flags = np.zeros((3, 10)), np.ones((3, 4), dtype=np.int32)
+            for _ in range(3):                                               # max_ticks = 1: every instance ends an episode with every tick
+                s.plant_step(tau, flags, DT, SUBSTEPS)
+                s.plant_respawn()
+            logs.append(s.plant_profile_draw_log())
+        finally:
+            s.close()
+    grown, fresh = logs
+    assert grown["log"].shape == fresh["log"].shape == (3, 2, abi.HB_PD_LOG_W)
+    assert fresh["count"].tolist() == [2] * 3
+    assert np.array_equal(grown["count"], fresh["count"]) and np.array_equal(grown["log"], fresh["log"])
+
+
 # ---- the closed loop ----------------------------------------------------------------------------------------------------------------------------
 LOOP_B, LOOP_TICKS, EVERY = 4, 30, 6
 

@@ -476,3 +476,27 @@ def test_error_surface(params):
         s.plant_set_external_wrench(np.zeros((2, 6)))                       # the wrench is the caller's again
     finally:
         s.close()
+
+
+# ---- test 9 --------------------------------------------------------------------------------------------------------------------------------
+def test_a_smaller_log_in_a_larger_allocation(params):
+    """log_capacity 3 and then 2 in one context (the device rows keep the pitch of 3) against a fresh context with 2 alone: the draw is
+    stateless per seed, instance and episode, so count and log are equal array for array."""
+    logs = []
+    for capacities in ((3, 2), (2,)):
+        s = _solver(params, 3)
+        try:
+            _minimal(s, params)
+            for cap in capacities:
+                s.plant_set_scenario(abi.make_scenario_config(**dict(SCENARIO, log_capacity=cap)))
+            flags, tau = np.ones((3, 4), dtype=np.int32), np.zeros((3, 10))
+            for _ in range(3):                                              # max_ticks = 1: every instance ends an episode with every tick
+                s.plant_step(tau, flags, 0.002, 4)
+                s.plant_respawn()
+            logs.append(s.plant_scenario_log())
+        finally:
+            s.close()
+    grown, fresh = logs
+    assert grown["log"].shape == fresh["log"].shape == (3, 2, abi.HB_SC_LOG_W)
+    assert fresh["count"].tolist() == [2] * 3 and fresh["log"][:, :, 0].tolist() == [[0.0, 1.0]] * 3
+    assert np.array_equal(grown["count"], fresh["count"]) and np.array_equal(grown["log"], fresh["log"])
