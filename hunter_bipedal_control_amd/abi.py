@@ -11,6 +11,7 @@ FLY, MODE_R, MODE_L, STANCE = 0, 1, 2, 3
 HB_PAYLOAD_SIZE = 10   # hb_plant_set_model_variation: m_p, r[3], I_p[6] = xx xy xz yy yz zz
 HB_PROFILE_MAX_KNOTS = 16   # hb_plant_set_terrain_profile, hb_ground_set_profile: knots per instance at most
 HB_PROFILE_RECORD = 10      # hb_plant_get_terrain_profile: doubles per segment record, T row-major | d
+HB_FIELD_MAX_NODES = 32     # hb_plant_set_terrain_field: nodes per grid axis at most (a facet record has HB_PROFILE_RECORD doubles too)
 
 
 class HbModel(C.Structure):

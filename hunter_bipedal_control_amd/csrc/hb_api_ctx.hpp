@@ -114,6 +114,12 @@ struct hb_ctx {
   ProfileBatch profile{};
   std::vector<double> profile_host, profile_knots;
   bool profile_on = false;
+  // per-instance height field of contact model 1 (hb_plant_set_terrain_field): field_on while one is in force (the step calls then launch
+  // the field kernels, and terrain_on and profile_on are false: one ground at a time); the arrays are allocated on first use, field_hdr_host
+  // is the host image of the stored records ([B][Field::stored]), field_z_host that of the heights ([B][Field::nz], zero beyond (nu, nw))
+  FieldBatch field{};
+  std::vector<double> field_hdr_host, field_z_host;
+  bool field_on = false;
   // per-instance model variation of contact model 1 (hb_plant_set_model_variation): modelvar_on while one is in force (the step calls then
   // launch the varied kernels); the records are allocated on first use, modelvar_host is their host image (what hb_plant_get_model_variation
   // reports).  Without a terrain the varied kernels read the level record of the configuration in force out of `terrain` (modelvar_level).
@@ -460,7 +466,7 @@ static int32_t resident_write(hb_ctx* ctx, hipStream_t s, bool fence, F&& launch
 
 extern "C" {
 
-int32_t hb_version(void) { return 300; }
+int32_t hb_version(void) { return 301; }
 
 const char* hb_last_error(const hb_ctx* ctx) { return ctx ? ctx->err.c_str() : g_create_error.c_str(); }
 

@@ -49,6 +49,7 @@ int32_t hb_plant_set_respawn(hb_ctx* ctx, const hb_respawn_config* cfg, const do
   HB_FAIL_IF(!ctx->plant_ready, HB_ERR_STATE, "hb_plant_set_respawn: call hb_plant_reset first");
   HB_FAIL_IF(!ctx->episode_on, HB_ERR_STATE, "hb_plant_set_respawn: no episode in force (hb_plant_set_episode): the decision is read from the episode record");
   HB_TRY(refuse_config(ctx, "hb_plant_set_respawn", cfg ? respawn_config_refusal(*cfg) : nullptr));
+  HB_FAIL_IF(cfg && ctx->field_on, HB_ERR_STATE, "hb_plant_set_respawn: a height field is in force (hb_plant_set_terrain_field): no respawn on a field, turn it off first");
   HB_FAIL_IF(cfg && ctx->profile_on, HB_ERR_STATE, "hb_plant_set_respawn: a terrain profile is in force (hb_plant_set_terrain_profile): no respawn on a profile, turn it off first");
   HB_FAIL_IF(cfg && !q_spawn, HB_ERR_ARG, "hb_plant_set_respawn: q_spawn is required with a configuration (the configuration in force is kept)");
   HB_ENTER_DEVICE();
@@ -128,6 +129,7 @@ int32_t hb_plant_set_scenario(hb_ctx* ctx, const hb_scenario_config* cfg) {
   if (!cfg && !ctx->scenario_on) return HB_OK;
   HB_TRY(contact_ready(ctx, "hb_plant_set_scenario"));
   HB_FAIL_IF(cfg && !ctx->respawn_on, HB_ERR_STATE, "hb_plant_set_scenario: no respawn configuration in force (hb_plant_set_respawn): the scenario is drawn at respawn");
+  HB_FAIL_IF(cfg && ctx->field_on && (cfg->channels & (HB_SC_SLOPE | HB_SC_MU)), HB_ERR_STATE, "hb_plant_set_scenario: a height field is in force (hb_plant_set_terrain_field): no slope or friction draw on a field, turn it off first");
   HB_FAIL_IF(cfg && ctx->profile_on && (cfg->channels & (HB_SC_SLOPE | HB_SC_MU)), HB_ERR_STATE, "hb_plant_set_scenario: a terrain profile is in force (hb_plant_set_terrain_profile): no slope or friction draw on a profile, turn it off first");
   HB_TRY(refuse_config(ctx, "hb_plant_set_scenario", cfg ? scenario_config_refusal(*cfg) : nullptr));
   HB_ENTER_DEVICE();
@@ -179,6 +181,7 @@ int32_t hb_plant_set_profile_draw(hb_ctx* ctx, const hb_profile_draw_config* cfg
   HB_ENTER_ARGS(false);
   if (!cfg && !ctx->profile_draw_on) return HB_OK;
   HB_TRY(contact_ready(ctx, "hb_plant_set_profile_draw"));
+  HB_FAIL_IF(cfg && ctx->field_on, HB_ERR_STATE, "hb_plant_set_profile_draw: a height field is in force (hb_plant_set_terrain_field): turn it off first");
   HB_FAIL_IF(cfg && !ctx->respawn_on, HB_ERR_STATE, "hb_plant_set_profile_draw: no respawn configuration in force (hb_plant_set_respawn): the profile is drawn at respawn");
   HB_FAIL_IF(cfg && ctx->scenario_on && (ctx->scenario_cfg.channels & (HB_SC_SLOPE | HB_SC_MU)), HB_ERR_STATE, "hb_plant_set_profile_draw: the scenario in force draws the terrain (hb_plant_set_scenario with HB_SC_SLOPE or HB_SC_MU): turn it off first");
   HB_TRY(refuse_config(ctx, "hb_plant_set_profile_draw", cfg ? profile_draw_config_refusal(*cfg) : nullptr));

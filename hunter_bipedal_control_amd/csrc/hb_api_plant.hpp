@@ -1,8 +1,8 @@
 // Host side, part 5: the plant (hb_plant_*; pinned stub and ground-contact model).  First the static helpers the plant entries and the
 // episode layer on top of them (hb_api_episode.hpp) both need, each below what it calls: joint-command state, episode record, clear
-// functions, the refusals of the step and ground-model entries, level terrain, scenario and profile-draw bookkeeping, profile installation.
-// Then the entries: reset, plant_launch and the step calls, state and actuator getters, contact model and wrench, joint model, terrain,
-// terrain profile, model variation, sensor model and hb_plant_sense.
+// functions, the refusals of the step and ground-model entries, level terrain, scenario and profile-draw bookkeeping, the locate of a height
+// field, profile installation.  Then the entries: reset, plant_launch and the step calls, state and actuator getters, contact model and
+// wrench, joint model, terrain, terrain profile, height field, model variation, sensor model and hb_plant_sense.
 #pragma once
 
 // joint command outputs and the per-instance controller flags (allocated on first use; loaded = 1, no emergency stop): the entries of
@@ -20,9 +20,10 @@ static int32_t joint_state_alloc(hb_ctx* ctx) {
 
 // ---- per-instance episode record (include/hunter_hip.h above hb_plant_set_episode) -------------------------------------------------
 // The plane the record measures heights from: the terrain records if a terrain is in force, the records of the facet under each base origin
-// if a profile is (ProfileBatch::base, the Terrain layout), else e_z . x = *d0 (ground_z in model 1, 0 in model 0).
+// if a profile or a height field is (ProfileBatch::base / FieldBatch::base, the Terrain layout), else e_z . x = *d0 (ground_z in model 1, 0 in model 0).
 static const double* episode_plane(const hb_ctx* ctx, double* d0) {
   *d0 = ctx->contact_cfg.mode == 1 ? ctx->contact_cfg.ground_z : 0.0;
+  if (ctx->contact_cfg.mode == 1 && ctx->field_on) return ctx->field.base;
   if (ctx->contact_cfg.mode == 1 && ctx->profile_on) return ctx->profile.base;
   return ctx->contact_cfg.mode == 1 && ctx->terrain_on ? ctx->terrain.ter : nullptr;
 }
@@ -220,6 +221,28 @@ static int32_t profile_locate(hb_ctx* ctx, const double* q, hipStream_t s) {
   return push(ctx, base.data(), t, t.base, whole(ctx));
 }
 
+// ---- height field: what the plant entries share ---------------------------------------------------------------------------------------------
+// sel and base of every instance from the host state q[B][16]: the facet under the four contact points and the base origin, and the Terrain
+// record of the facet under the base.  On s, behind its earlier work; the caller synchronises.
+static int32_t field_locate(hb_ctx* ctx, const double* q, hipStream_t s) {
+  const size_t B = ctx->B;
+  std::vector<int> sel(B * (HB_NC + 1));
+  std::vector<double> base(B * Terrain::size);
+  for (size_t i = 0; i < B; ++i) {
+    const double* r = ctx->field_hdr_host.data() + i * Field::stored;
+    const double* z = ctx->field_z_host.data() + i * Field::nz;
+    double feet[12], rec[Profile::rec];
+    plant_feet(ctx->hmodel, q + 16 * i, feet);
+    double* b = base.data() + Terrain::size * i;
+    std::memcpy(b, r + Field::head, Terrain::size * sizeof(double));
+    for (int c = 0; c < HB_NC + 1; ++c) sel[(HB_NC + 1) * i + c] = field_facet(r, z, c < HB_NC ? feet + 3 * c : q + 16 * i, c < HB_NC ? rec : b);
+  }
+  HB_HIP(hipStreamSynchronize(s));
+  FieldBatch& t = ctx->field;
+  HB_TRY(push(ctx, sel.data(), t, t.sel, whole(ctx)));
+  return push(ctx, base.data(), t, t.base, whole(ctx));
+}
+
 // No finished episode logged in every instance; with `rows`, the parameter rows back to "before the first draw" (zero) too.  Synchronous;
 // the caller has drained ctx->s_wbc.
 static int32_t profile_draw_start(hb_ctx* ctx, bool rows) {
@@ -279,6 +302,7 @@ static int32_t profile_install(hb_ctx* ctx, std::vector<double>& rec, std::vecto
   HB_TRY(pull(ctx, q.data(), ctx->plant, ctx->plant.q, whole(ctx)));
   HB_TRY(profile_locate(ctx, q.data(), ctx->s_wbc));
   ctx->terrain_on = false;
+  ctx->field_on = false;
   ctx->profile_on = true;
   HB_TRY(modelvar_level(ctx));
   return contact_forget_warm_start(ctx);
@@ -306,6 +330,7 @@ int32_t hb_plant_reset(hb_ctx* ctx, const double* q0, const double* v0, double b
     HB_TRY(profile_draw_refresh_host(ctx));
   }
   if (ctx->profile_on) HB_TRY(profile_locate(ctx, q0, ctx->s_wbc));   // the facets under the reset state
+  if (ctx->field_on) HB_TRY(field_locate(ctx, q0, ctx->s_wbc));
   if (ctx->episode_on) HB_TRY(episode_start(ctx, ctx->s_wbc));   // the record restarts from the reset state
   if (ctx->respawn_on) HB_TRY(respawn_totals_start(ctx, ctx->s_wbc));   // ... and so do the totals of the respawn
   HB_HIP(hipStreamSynchronize(ctx->s_wbc));
@@ -342,7 +367,7 @@ static int32_t plant_launch(hb_ctx* ctx, const double* dtau, const double* const
   const hb_contact_config& K = ctx->contact_cfg;
   const hb_joint_model& J = ctx->joint_model;
   const DevModel* M = ctx->dmodel;
-  const PlantForm f = plant_form(K.mode, ctx->joints_on, ctx->terrain_on, ctx->modelvar_on, ctx->profile_on, cmd != nullptr);
+  const PlantForm f = plant_form(K.mode, ctx->joints_on, ctx->terrain_on, ctx->modelvar_on, ctx->profile_on, cmd != nullptr, ctx->field_on);
   switch (f.ground) {
     case PlantForm::Ground::Pinned:
       return f.hybrid ? go(k_plant_hybrid, p, a, c, M) : go(k_plant, p, M, dtau);
@@ -358,6 +383,9 @@ static int32_t plant_launch(hb_ctx* ctx, const double* dtau, const double* const
     case PlantForm::Ground::Profile:
       if (f.hybrid) return f.joints ? go(k_plant_profile_joints_hybrid, p, cb, jb, ctx->profile, a, c, K, J, M, mvar) : go(k_plant_profile_hybrid, p, cb, ctx->profile, a, c, K, M, mvar);
       return f.joints ? go(k_plant_profile_joints, p, cb, jb, ctx->profile, K, J, M, mvar, dtau) : go(k_plant_profile, p, cb, ctx->profile, K, M, mvar, dtau);
+    case PlantForm::Ground::Field:
+      if (f.hybrid) return f.joints ? go(k_plant_field_joints_hybrid, p, cb, jb, ctx->field, a, c, K, J, M, mvar) : go(k_plant_field_hybrid, p, cb, ctx->field, a, c, K, M, mvar);
+      return f.joints ? go(k_plant_field_joints, p, cb, jb, ctx->field, K, J, M, mvar, dtau) : go(k_plant_field, p, cb, ctx->field, K, M, mvar, dtau);
   }
   return HB_ERR_STATE;   // (not reached: the switch covers PlantForm::Ground)
 }
@@ -441,6 +469,7 @@ int32_t hb_plant_set_contact_model(hb_ctx* ctx, const hb_contact_config* cfg) {
   ctx->contact_cfg = ground ? *cfg : hb_contact_config{};
   if (!ground) ctx->terrain_on = false;   // the terrain belongs to contact model 1
   if (!ground) ctx->profile_on = false;   // ... and so does the terrain profile
+  if (!ground) ctx->field_on = false;     // ... and the height field
   if (!ground) ctx->modelvar_on = false;  // ... and so does the model variation
   HB_TRY(modelvar_level(ctx));            // (the level record follows the configuration)
   if (!ground && ctx->joints_on) {   // the joint model belongs to contact model 1
@@ -555,6 +584,7 @@ int32_t hb_plant_set_terrain(hb_ctx* ctx, const double* plane, const double* mu)
   }
   ctx->terrain_on = plane || mu;
   ctx->profile_on = false;   // one ground at a time: the call replaces a terrain profile
+  ctx->field_on = false;     // ... and a height field
   HB_TRY(modelvar_level(ctx));
   return contact_forget_warm_start(ctx);
 }
@@ -624,6 +654,93 @@ int32_t hb_plant_get_terrain_profile(hb_ctx* ctx, int32_t* n_knots, double* dir,
     if (mu) std::memcpy(mu + 4 * i, r + Profile::head + Terrain::mu, 4 * sizeof(double));
     if (records) std::memcpy(records + i * nrec, r + Profile::seg, nrec * sizeof(double));
   }
+  return HB_OK;
+}
+
+// ---- per-instance height field of contact model 1 (include/hunter_hip.h above hb_plant_set_terrain_field) ------------------------------
+// (the stored record of an instance, validation included, is hb_contact.hpp field_record)
+int32_t hb_plant_set_terrain_field(hb_ctx* ctx, const int32_t* n_nodes, const double* dir, const double* origin, const double* spacing,
+                                   const double* heights, const double* mu) {
+  HB_ENTER_ARGS(false);
+  HB_TRY(contact_ready(ctx, "hb_plant_set_terrain_field"));
+  const bool on = n_nodes || dir || origin || spacing || heights;
+  HB_FAIL_IF(on && !(n_nodes && dir && origin && spacing && heights), HB_ERR_ARG, "hb_plant_set_terrain_field: give n_nodes, dir, origin, spacing and heights, or none of them to switch the field off (the ground in force is kept)");
+  HB_FAIL_IF(!on && mu, HB_ERR_ARG, "hb_plant_set_terrain_field: friction coefficients without a field (the ground in force is kept)");
+  HB_FAIL_IF(ctx->profile_draw_on, HB_ERR_STATE, "hb_plant_set_terrain_field: the profile draw in force draws the ground (hb_plant_set_profile_draw): turn it off first");
+  HB_FAIL_IF(on && ctx->respawn_on, HB_ERR_STATE, "hb_plant_set_terrain_field: a respawn configuration is in force (hb_plant_set_respawn): no respawn on a field, turn it off first");
+  HB_FAIL_IF(on && ctx->scenario_on && (ctx->scenario_cfg.channels & (HB_SC_SLOPE | HB_SC_MU)), HB_ERR_STATE, "hb_plant_set_terrain_field: the scenario in force draws the terrain (hb_plant_set_scenario): turn it off first");
+  const size_t B = ctx->B;
+  std::vector<double> hdr(on ? B * Field::stored : 0), z(on ? B * Field::nz : 0);
+  for (size_t i = 0; i < B && on; ++i) {
+    const int n[2] = {n_nodes[2 * i], n_nodes[2 * i + 1]};
+    const double* zi = heights + i * Field::nz;
+    if (n[0] >= 2 && n[0] <= HB_FIELD_MAX_NODES && n[1] >= 2 && n[1] <= HB_FIELD_MAX_NODES)   // (the stored heights: zero beyond (nu, nw))
+      for (int iu = 0; iu < n[0]; ++iu) std::memcpy(z.data() + i * Field::nz + iu * Field::pitch, zi + iu * Field::pitch, size_t(n[1]) * sizeof(double));
+    if (const char* why = field_record(n, dir + 2 * i, origin + 2 * i, spacing + 2 * i, z.data() + i * Field::nz, mu ? mu + 4 * i : nullptr, ctx->contact_cfg.mu,
+                                       hdr.data() + i * Field::stored))
+      return refuse_instance(ctx, HB_ERR_ARG, "hb_plant_set_terrain_field", i, why, "ground");
+  }
+  HB_ENTER_DEVICE();
+  HB_HIP(hipStreamSynchronize(ctx->s_wbc));  // (a step in flight still runs on the ground it was launched with)
+  if (on) {
+    FieldBatch& t = ctx->field;
+    HB_TRY(ensure_fields(ctx, t));
+    HB_TRY(push(ctx, hdr.data(), t, t.hdr, whole(ctx)));
+    HB_TRY(push(ctx, z.data(), t, t.z, whole(ctx)));
+    ctx->field_hdr_host = std::move(hdr);
+    ctx->field_z_host = std::move(z);
+    std::vector<double> q(B * 16);
+    HB_TRY(pull(ctx, q.data(), ctx->plant, ctx->plant.q, whole(ctx)));
+    HB_TRY(field_locate(ctx, q.data(), ctx->s_wbc));
+    ctx->terrain_on = false;   // one ground at a time: the field replaces a terrain and a profile
+    ctx->profile_on = false;
+  }
+  ctx->field_on = on;
+  HB_TRY(modelvar_level(ctx));
+  return contact_forget_warm_start(ctx);
+}
+
+int32_t hb_plant_get_terrain_field(hb_ctx* ctx, int32_t* n_nodes, double* dir, double* origin, double* spacing, double* heights, double* mu,
+                                   int32_t* facet) {
+  HB_ENTER_ARGS(false);
+  HB_TRY(contact_ready(ctx, "hb_plant_get_terrain_field"));
+  HB_FAIL_IF(!ctx->field_on, HB_ERR_STATE, "hb_plant_get_terrain_field: no height field in force (hb_plant_set_terrain_field)");
+  if (facet) {
+    HB_ENTER_DEVICE();
+    HB_HIP(hipStreamSynchronize(ctx->s_wbc));
+    HB_TRY(pull(ctx, facet, ctx->field, ctx->field.sel, whole(ctx)));
+  }
+  for (size_t i = 0; i < size_t(ctx->B); ++i) {
+    const double* r = ctx->field_hdr_host.data() + i * Field::stored;
+    if (n_nodes) { n_nodes[2 * i] = int32_t(r[Field::nu]); n_nodes[2 * i + 1] = int32_t(r[Field::nw]); }
+    if (dir) std::memcpy(dir + 2 * i, r + Field::dir, 2 * sizeof(double));
+    if (origin) std::memcpy(origin + 2 * i, r + Field::org, 2 * sizeof(double));
+    if (spacing) std::memcpy(spacing + 2 * i, r + Field::step, 2 * sizeof(double));
+    if (mu) std::memcpy(mu + 4 * i, r + Field::head + Terrain::mu, 4 * sizeof(double));
+  }
+  if (heights) std::memcpy(heights, ctx->field_z_host.data(), ctx->field_z_host.size() * sizeof(double));
+  return HB_OK;
+}
+
+int32_t hb_plant_field_eval(hb_ctx* ctx, int32_t n_points, const double* xyz, int32_t* facet_id, double* records, double* height) {
+  HB_ENTER_ARGS(n_points <= 0 || !xyz || !(facet_id || records || height));
+  HB_TRY(contact_ready(ctx, "hb_plant_field_eval"));
+  HB_FAIL_IF(!ctx->field_on, HB_ERR_STATE, "hb_plant_field_eval: no height field in force (hb_plant_set_terrain_field)");
+  HB_ENTER_DEVICE();
+  const size_t m = size_t(ctx->B) * size_t(n_points);
+  DevBuf<double> dx, dr, dh;
+  DevBuf<int> df;
+  HB_HIP(dx.alloc(m * 3, xyz));
+  HB_HIP(dr.alloc(m * Profile::rec));
+  HB_HIP(dh.alloc(m));
+  HB_HIP(df.alloc(m));
+  hipStream_t s = ctx->s_wbc;
+  hipLaunchKernelGGL(k_field_eval, dim3(unsigned((m + 63) / 64)), dim3(64), 0, s, ctx->field, n_points, dx.p, df.p, dr.p, dh.p);
+  HB_HIP(hipGetLastError());
+  HB_HIP(hipStreamSynchronize(s));
+  if (facet_id) HB_HIP(hipMemcpy(facet_id, df.p, m * 4, hipMemcpyDeviceToHost));
+  if (records) HB_HIP(hipMemcpy(records, dr.p, m * Profile::rec * 8, hipMemcpyDeviceToHost));
+  if (height) HB_HIP(hipMemcpy(height, dh.p, m * 8, hipMemcpyDeviceToHost));
   return HB_OK;
 }
 

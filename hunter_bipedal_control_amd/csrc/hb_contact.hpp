@@ -298,10 +298,10 @@ HB_HD void profile_rotate(const Ctx& cx, const double* act, double* Jc, double* 
   }
   cx.sync();
 }
-// d of the facet the normal row r = 3 c + 2 measures its gap from (TERRAIN 2), else the caller's
+// d of the facet the normal row r = 3 c + 2 measures its gap from (TERRAIN 2 and 3), else the caller's
 template <int TERRAIN>
 HB_HD double row_ground(const double* ter, int r, double ground_z) {
-  if constexpr (TERRAIN == 2) return ter[Profile::act + Profile::rec * (r / 3) + Terrain::d];
+  if constexpr (TERRAIN >= 2) return ter[Profile::act + Profile::rec * (r / 3) + Terrain::d];
   else return ground_z;
 }
 // The outputs of a profile step at q+ (feet[12] world, q[16]): the segment under the four points and the base origin is selected again, the
@@ -323,6 +323,111 @@ HB_HD void profile_publish(const Ctx& cx, const ProfileIo& io) {
   for (int k = cx.lane; k < Terrain::size; k += cx.nlanes) io.base[k] = io.pro[Profile::head + k];
 }
 
+// ---- per-instance height field (hb_plant_set_terrain_field): triangulated ground over a grid, a facet per contact point and substep --------
+// The record of an instance where the field kernels stage it (TERRAIN 3).  head, act and sel lie where the profile's do, so that
+// profile_rotate, row_ground, profile_publish and the outputs serve both grounds; [0, stored) is what the host stores per instance: head (a
+// Terrain record: T, d of the facet under the base origin at q+, mu of the four points), dir: a, org: (u0, w0), step: (du, dw), nu / nw as
+// doubles.  The heights z[iu * HB_FIELD_MAX_NODES + iw] stay in global memory (FieldBatch::z); a facet's record is computed from the four
+// heights of its cell where it is needed.
+struct Field {
+  static constexpr int head = Profile::head, dir = Profile::dir, org = dir + 2, step = org + 2, nu = step + 2, nw = nu + 1, stored = nw + 1,
+                       act = Profile::act, sel = Profile::sel, size = Profile::size, pitch = HB_FIELD_MAX_NODES,
+                       nz = HB_FIELD_MAX_NODES * HB_FIELD_MAX_NODES;
+};
+static_assert(Field::stored <= Field::act, "the stored part of a field record ends ahead of the working part");
+// The facet under the world point x[3] of the field (hdr: its record, z: its heights): the id 2 (i (nw - 1) + j) + t, and in
+// rec[Profile::rec] the record (T, d) of its plane, which comes from terrain_plane_record as a profile segment's does.  Every operation is
+// rounded on its own: host, host emulation and device return the same bits.  A NaN coordinate gives facet 0 and a NaN record.
+HB_HD int field_facet(const double* hdr, const double* __restrict__ z, const double* x, double* rec) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  const double ax = hdr[Field::dir], ay = hdr[Field::dir + 1], bx = -ay, by = ax;
+  const double u0 = hdr[Field::org], w0 = hdr[Field::org + 1], du = hdr[Field::step], dw = hdr[Field::step + 1];
+  const int nu = int(hdr[Field::nu]), nw = int(hdr[Field::nw]);
+  const double u = (ax * x[0] + ay * x[1]) - u0, w = (bx * x[0] + by * x[1]) - w0;
+  const double su = u / du, sw = w / dw;
+  // clamp(floor(s), 0, n - 2); a NaN fails every comparison and lands in cell 0
+  const int i = su >= 1.0 ? (su < double(nu - 2) ? int(su) : nu - 2) : 0;
+  const int j = sw >= 1.0 ? (sw < double(nw - 2) ? int(sw) : nw - 2) : 0;
+  const double fu = su - double(i), fw = sw - double(j);
+  const int t = fu < fw ? 1 : 0;   // (fu >= fw: the lower triangle)
+  const double* c = z + i * Field::pitch + j;
+  const double z00 = c[0], z01 = c[1], z10 = c[Field::pitch], z11 = c[Field::pitch + 1];
+  const double p = (t ? z11 - z01 : z10 - z00) / du;
+  const double r = (t ? z01 - z00 : z11 - z10) / dw;
+  const double len = sqrt(1.0 + p * p + r * r);
+  double pl[4] = {0.0 - (p * ax + r * bx) / len, 0.0 - (p * ay + r * by) / len, 1.0 / len, 0.0};   // (0 - : no negative zero on level ground)
+  for (int it = 0; it < 4 && terrain_normal_length(pl) != 1.0; ++it) {   // (as profile_segment_record)
+    const double l = terrain_normal_length(pl);
+    for (int k = 0; k < 3; ++k) pl[k] /= l;
+  }
+  const double un = u0 + double(i) * du, wn = w0 + double(j) * dw;
+  pl[3] = pl[0] * (ax * un + bx * wn) + pl[1] * (ay * un + by * wn) + pl[2] * z00;
+  terrain_plane_record(pl, terrain_normal_length(pl), rec);
+  if (u != u || w != w)
+    for (int k = 0; k < Profile::rec; ++k) rec[k] = u + w;
+  return 2 * (i * (nw - 1) + j) + t;
+}
+// Host: the stored record r[Field::stored] of one instance from its field (n[2] node counts, direction, origin, spacing, heights with the
+// pitch HB_FIELD_MAX_NODES, mu[4] or null for cfg_mu), or the reason it is refused (r is then not written).
+inline const char* field_record(const int* n, const double* dir, const double* org, const double* step, const double* z, const double* mu,
+                                double cfg_mu, double* r) {
+  if (n[0] < 2 || n[0] > HB_FIELD_MAX_NODES || n[1] < 2 || n[1] > HB_FIELD_MAX_NODES) return "a number of nodes outside 2 .. HB_FIELD_MAX_NODES";
+  if (!(std::isfinite(dir[0]) && std::isfinite(dir[1]))) return "a non-finite direction";
+  const double len = std::sqrt(dir[0] * dir[0] + dir[1] * dir[1]);
+  if (!(len > 0.0) || !std::isfinite(len)) return "a direction of length zero";
+  if (!(std::isfinite(org[0]) && std::isfinite(org[1]))) return "a non-finite origin";
+  if (!(std::isfinite(step[0]) && std::isfinite(step[1]))) return "a non-finite spacing";
+  if (!(step[0] > 0.0 && step[1] > 0.0)) return "a spacing that is not positive";
+  for (int i = 0; i < n[0]; ++i)
+    for (int j = 0; j < n[1]; ++j)
+      if (!std::isfinite(z[i * Field::pitch + j])) return "a non-finite height";
+  for (int i = 0; i + 1 < n[0]; ++i)
+    for (int j = 0; j + 1 < n[1]; ++j) {
+      const double* c = z + i * Field::pitch + j;
+      const double pr[2][2] = {{(c[Field::pitch] - c[0]) / step[0], (c[Field::pitch + 1] - c[Field::pitch]) / step[1]},
+                               {(c[Field::pitch + 1] - c[1]) / step[0], (c[1] - c[0]) / step[1]}};
+      for (const auto& t : pr) {
+        const double s2 = t[0] * t[0] + t[1] * t[1];
+        if (!(std::isfinite(s2) && s2 <= 3.0 * (1.0 + 1e-12))) return "a triangle steeper than sqrt(3) (n_z < 0.5)";
+      }
+    }
+  double mu4[HB_NC];
+  for (int c = 0; c < HB_NC; ++c) {
+    mu4[c] = mu ? mu[c] : cfg_mu;
+    if (!(std::isfinite(mu4[c]) && mu4[c] >= 0.0)) return "a friction coefficient that is negative or not finite";
+  }
+  for (int k = 0; k < Field::stored; ++k) r[k] = 0.0;
+  profile_direction(dir, r + Field::dir);
+  r[Field::org] = org[0]; r[Field::org + 1] = org[1];
+  r[Field::step] = step[0]; r[Field::step + 1] = step[1];
+  r[Field::nu] = double(n[0]); r[Field::nw] = double(n[1]);
+  for (int c = 0; c < HB_NC; ++c) r[Field::head + Terrain::mu + c] = mu4[c];
+  const double x0[3] = {0.0, 0.0, 0.0};
+  field_facet(r, z, x0, r + Field::head);   // (until a state is located: the facet under the world origin)
+  return nullptr;
+}
+// profile_select for a field: point c takes the record of the facet under feet[3 c ..] into its slot of act, one lane per point.
+template <class Ctx>
+HB_HD void field_select(const Ctx& cx, double* fld, const double* __restrict__ z, const double* feet) {
+  for (int c = cx.lane; c < HB_NC; c += cx.nlanes) field_facet(fld, z, feet + 3 * c, fld + Field::act + Profile::rec * c);
+  cx.sync();
+}
+// profile_outputs_select for a field: the facets under the four points and the base origin at q+; the points' records go to act, the
+// base's to head, the ids to sel.
+template <class Ctx>
+HB_HD void field_outputs_select(const Ctx& cx, double* fld, const double* __restrict__ z, const double* feet, const double* q) {
+  for (int c = cx.lane; c < HB_NC + 1; c += cx.nlanes) {
+    double rec[Profile::rec];
+    const int id = field_facet(fld, z, c < HB_NC ? feet + 3 * c : q, rec);
+    double* dst = c < HB_NC ? fld + Field::act + Profile::rec * c : fld + Field::head;
+    for (int k = 0; k < Profile::rec; ++k) dst[k] = rec[k];
+    fld[Field::sel + c] = double(id);
+  }
+  cx.sync();
+}
+
 // What a step leaves behind per instance (global memory; hb_plant_get_contact).
 struct ContactOut {
   double *gap, *pvel, *res;
@@ -333,9 +438,11 @@ struct ContactOut {
 // the base origin, or null; all_on[4] = {1, 1, 1, 1} in memory every lane can read.  TERRAIN: ter = the instance's Terrain record (LDS); W, c,
 // the impulses and the gap are those of the plane's frame, and K.mu / K.ground_z are not read.  TERRAIN 2: ter = the instance's staged
 // Profile record (LDS, writable: ProfileIo::pro); frame and offset are those of each point's facet, selected here from the substep's start.
+// TERRAIN 3: the same with ter = the instance's staged Field record and hts = its heights (global memory): the facet comes from field_facet.
 template <int TERRAIN = 0, class Ctx>
 HB_HD void contact_substep(const Ctx& cx, const DevModel& Mdl, double* q, double* v, const double* tau, const double* wrench, const int* all_on,
-                           const hb_contact_config& K, double eps, double h, double* lds, double* vdot_out, const double* ter = nullptr) {
+                           const hb_contact_config& K, double eps, double h, double* lds, double* vdot_out, const double* ter = nullptr,
+                           const double* hts = nullptr) {
   double* Jc = lds + PlantLds::Jc;
   double* X = lds + PlantLds::X;
   double* A = lds + PlantLds::A;
@@ -355,10 +462,11 @@ HB_HD void contact_substep(const Ctx& cx, const DevModel& Mdl, double* q, double
   // the front half of the pinned stub's substep with every point on (its first barrier publishes wgen)
   plant_substep<1>(cx, Mdl, q, v, tau, all_on, nullptr, 0.0, 0.0, h, lds, nullptr, nullptr, wrench ? wgen : nullptr);
   double ground_z;
-  if constexpr (TERRAIN == 2) {
-    profile_select(cx, const_cast<double*>(ter), feet);
+  if constexpr (TERRAIN >= 2) {
+    if constexpr (TERRAIN == 3) field_select(cx, const_cast<double*>(ter), hts, feet);
+    else profile_select(cx, const_cast<double*>(ter), feet);
     profile_rotate<PlantLds::xs>(cx, ter + Profile::act, Jc, X, A, feet);
-    ground_z = row_ground<2>(ter, cx.lane < 12 ? cx.lane : 0, 0.0);   // (the lane's own row)
+    ground_z = row_ground<TERRAIN>(ter, cx.lane < 12 ? cx.lane : 0, 0.0);   // (the lane's own row)
   } else if constexpr (TERRAIN) {
     terrain_rotate<PlantLds::xs>(cx, ter + Terrain::T, Jc, X, A, feet);
     ground_z = ter[Terrain::d];
@@ -466,7 +574,7 @@ template <bool HYBRID = false, int TERRAIN = 0, class Ctx>
 HB_HD void contact_step(const Ctx& cx, const DevModel& Mdl, double* q_g, double* v_g, double* imp_g, const double* tau, const double* wrench,
                         const int* all_on, const hb_contact_config& K, double eps, double dt, int substeps, double* lds, double* lambda_out,
                         double* vdot_out, const ContactOut& out, const HybridActuator* actuator = nullptr, const double* ter = nullptr,
-                        const ProfileIo* pio = nullptr) {
+                        const ProfileIo* pio = nullptr, const double* hts = nullptr) {
   double* q = lds + ContactLds::q;
   double* v = lds + ContactLds::v;
   double* imp = lds + ContactLds::imp;
@@ -479,11 +587,11 @@ HB_HD void contact_step(const Ctx& cx, const DevModel& Mdl, double* q_g, double*
     ActuatorAcc acc;
     for (int s = 0; s < substeps; ++s) {
       actuator_eval(cx, act, q, v, s, act.tau, acc, [](int, double ts) { return ts; });
-      contact_substep<TERRAIN>(cx, Mdl, q, v, act.tau, wrench, all_on, K, eps, h, lds, vdot_out, ter);
+      contact_substep<TERRAIN>(cx, Mdl, q, v, act.tau, wrench, all_on, K, eps, h, lds, vdot_out, ter, hts);
     }
     actuator_finish(cx, act, substeps, acc, false);
   } else {
-    for (int s = 0; s < substeps; ++s) contact_substep<TERRAIN>(cx, Mdl, q, v, tau, wrench, all_on, K, eps, h, lds, vdot_out, ter);
+    for (int s = 0; s < substeps; ++s) contact_substep<TERRAIN>(cx, Mdl, q, v, tau, wrench, all_on, K, eps, h, lds, vdot_out, ter, hts);
   }
   // ---- outputs: world forces, touching flags and point velocities J v+ of the last substep; gaps at q+
   const double* Jc = lds + PlantLds::Jc;
@@ -492,7 +600,7 @@ HB_HD void contact_step(const Ctx& cx, const DevModel& Mdl, double* q_g, double*
   for (int i = cx.lane; i < 16; i += cx.nlanes) { q_g[i] = q[i]; v_g[i] = v[i]; }
   for (int i = cx.lane; i < 12; i += cx.nlanes) {
     imp_g[i] = imp[i];
-    if constexpr (TERRAIN == 2) {
+    if constexpr (TERRAIN >= 2) {
       contact_outputs_terrain(ter + Profile::act + Profile::rec * (i / 3), i, Jc, v, imp, h, lambda_out, out.pvel);
     } else if constexpr (TERRAIN) {
       contact_outputs_terrain(ter, i, Jc, v, imp, h, lambda_out, out.pvel);
@@ -504,14 +612,15 @@ HB_HD void contact_step(const Ctx& cx, const DevModel& Mdl, double* q_g, double*
     }
   }
   cx.sync();
-  if constexpr (TERRAIN == 2) profile_outputs_select(cx, pio->pro, feet, q);
+  if constexpr (TERRAIN == 3) field_outputs_select(cx, pio->pro, hts, feet, q);
+  else if constexpr (TERRAIN == 2) profile_outputs_select(cx, pio->pro, feet, q);
   for (int c = cx.lane; c < HB_NC; c += cx.nlanes) {
-    if constexpr (TERRAIN == 2) out.gap[c] = terrain_height(ter + Profile::act + Profile::rec * c, feet + 3 * c);
+    if constexpr (TERRAIN >= 2) out.gap[c] = terrain_height(ter + Profile::act + Profile::rec * c, feet + 3 * c);
     else if constexpr (TERRAIN) out.gap[c] = terrain_height(ter, feet + 3 * c);
     else out.gap[c] = feet[3 * c + 2] - K.ground_z;
     out.touching[c] = imp[3 * c + 2] > 0.0 ? 1 : 0;
   }
-  if constexpr (TERRAIN == 2) profile_publish(cx, *pio);
+  if constexpr (TERRAIN >= 2) profile_publish(cx, *pio);
   if (cx.lane == 0) {
     const double res = lds[ContactLds::res];
     bool finite = true;

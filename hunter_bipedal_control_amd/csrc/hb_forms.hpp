@@ -7,7 +7,7 @@
 //               so that the phases can be timed and counted one by one (each stop includes everything ahead of it in code order);
 //   traces      profiling build: one wavefront prints the cycle counts of its phases.
 // The rules that depend on the state of the context instead (a ground map, the plant's contact model, joints, terrain, variation and
-// profile) stand here too: use_ground_forms, plant_form.
+// profile, height field) stand here too: use_ground_forms, plant_form.
 // Plain C++14, no HIP: tests/host_emu/formsemu.cpp compiles this header with g++.
 #pragma once
 
@@ -144,19 +144,21 @@ inline bool use_ric_fwd_wave(const KernelForms& f, int concurrent) {
 // base forms otherwise — the base forms never see the map, so a context without one runs what it always ran.
 inline bool use_ground_forms(bool map_in_force) { return map_in_force; }
 
-// Plant step: which of the eighteen step kernels a launch takes (hb_api_plant.hpp plant_launch names them).  Contact mode 0 is the pinned
-// stub (k_plant / k_plant_hybrid), which knows neither joints nor ground; in contact model 1 a profile goes before a model variation (the
-// profile kernels take the variation by pointer), a variation before a terrain (the varied kernels read the terrain array, where the
+// Plant step: which of the twenty-two step kernels a launch takes (hb_api_plant.hpp plant_launch names them).  Contact mode 0 is the pinned
+// stub (k_plant / k_plant_hybrid), which knows neither joints nor ground; in contact model 1 a height field or a profile (one ground at a
+// time: the host never has both in force) goes before a model variation (the field and profile kernels take the variation by pointer), a
+// variation before a terrain (the varied kernels read the terrain array, where the
 // host keeps the level record while no terrain is in force), a terrain before the level ground.  `joints` and `hybrid` pick the kernel of
 // the family: joint model on, the command's law per substep instead of a held torque.
 struct PlantForm {
-  enum class Ground { Pinned, Level, Terrain, Varied, Profile } ground;
+  enum class Ground { Pinned, Level, Terrain, Varied, Profile, Field } ground;
   bool joints, hybrid;
 };
-inline PlantForm plant_form(int contact_mode, bool joints_on, bool terrain_on, bool modelvar_on, bool profile_on, bool hybrid) {
+inline PlantForm plant_form(int contact_mode, bool joints_on, bool terrain_on, bool modelvar_on, bool profile_on, bool hybrid,
+                            bool field_on = false) {
   using G = PlantForm::Ground;
   if (contact_mode != 1) return {G::Pinned, false, hybrid};
-  return {profile_on ? G::Profile : modelvar_on ? G::Varied : terrain_on ? G::Terrain : G::Level, joints_on, hybrid};
+  return {field_on ? G::Field : profile_on ? G::Profile : modelvar_on ? G::Varied : terrain_on ? G::Terrain : G::Level, joints_on, hybrid};
 }
 
 // LQ approximation: trips of this many nodes per wavefront (k_lq_trip).  Longer trips fill the lanes of the value phase better (16 nodes:

@@ -85,11 +85,11 @@ HB_HD void joint_row(int r, const double* A, const double* X, const double* Jc, 
 
 // One substep of length h.  q[16], v[16] in / out (LDS); imp[32] (LDS behind `lds`) in / out; taua[10] (LDS) the saturated torque.
 // TERRAIN (hb_contact.hpp): rows 0-11 are those of the plane's frame, through A, the contact columns of X and Jc; the joint rows are unchanged.
-// TERRAIN 2 (the profile): the same with the frame and offset of each point's facet.
+// TERRAIN 2 (the profile) and 3 (the height field, hts = its heights): the same with the frame and offset of each point's facet.
 template <int TERRAIN = 0, class Ctx>
 HB_HD void joints_substep(const Ctx& cx, const DevModel& Mdl, double* q, double* v, const double* wrench, const int* all_on,
                           const hb_contact_config& K, const hb_joint_model& Jm, double eps, double h, double* lds, double* vdot_out,
-                          const double* ter = nullptr) {
+                          const double* ter = nullptr, const double* hts = nullptr) {
   double* Jc = lds + PlantJointLds::Jc;
   double* X = lds + PlantJointLds::X;
   double* A = lds + PlantJointLds::A;
@@ -129,10 +129,11 @@ HB_HD void joints_substep(const Ctx& cx, const DevModel& Mdl, double* q, double*
   plant_substep<2>(cx, Mdl, q, v, taua, all_on, nullptr, 0.0, 0.0, h, lds, nullptr, nullptr, wgen, mdiag);
   for (int i = cx.lane; i < 16; i += cx.nlanes) vf[i] = v[i] + h * X[i * XJ];
   double ground_z;
-  if constexpr (TERRAIN == 2) {
-    profile_select(cx, const_cast<double*>(ter), feet);   // (its barrier publishes vf)
+  if constexpr (TERRAIN >= 2) {
+    if constexpr (TERRAIN == 3) field_select(cx, const_cast<double*>(ter), hts, feet);   // (its barrier publishes vf)
+    else profile_select(cx, const_cast<double*>(ter), feet);   // (its barrier publishes vf)
     profile_rotate<XJ>(cx, ter + Profile::act, Jc, X, A, feet);
-    ground_z = row_ground<2>(ter, cx.lane < 12 ? cx.lane : 0, 0.0);   // (the lane's own row)
+    ground_z = row_ground<TERRAIN>(ter, cx.lane < 12 ? cx.lane : 0, 0.0);   // (the lane's own row)
   } else if constexpr (TERRAIN) {
     terrain_rotate<XJ>(cx, ter + Terrain::T, Jc, X, A, feet);   // (its barriers publish vf)
     ground_z = ter[Terrain::d];
@@ -265,7 +266,7 @@ HB_HD void joints_step(const Ctx& cx, const DevModel& Mdl, double* q_g, double* 
                        const double* wrench, const int* all_on, const hb_contact_config& K, const hb_joint_model& Jm, double eps, double dt,
                        int substeps, double* lds, double* lambda_out, double* vdot_out, double* tau_last_g, const ContactOut& out,
                        const JointOut& jout, const HybridActuator* actuator = nullptr, const double* ter = nullptr,
-                       const ProfileIo* pio = nullptr) {
+                       const ProfileIo* pio = nullptr, const double* hts = nullptr) {
   double* q = lds + JointLds::q;
   double* v = lds + JointLds::v;
   double* imp = lds + JointLds::imp;
@@ -286,11 +287,11 @@ HB_HD void joints_step(const Ctx& cx, const DevModel& Mdl, double* q_g, double* 
     ActuatorAcc acc;
     for (int s = 0; s < substeps; ++s) {
       actuator_eval(cx, act, q, v, s, taua, acc, [&](int j, double ts) { return joint_saturate(ts, actuator_pick(Jm.torque_limit, j)); });
-      joints_substep<TERRAIN>(cx, Mdl, q, v, wrench, all_on, K, Jm, eps, h, lds, vdot_out, ter);
+      joints_substep<TERRAIN>(cx, Mdl, q, v, wrench, all_on, K, Jm, eps, h, lds, vdot_out, ter, hts);
     }
     actuator_finish(cx, act, substeps, acc, true);
   } else {
-    for (int s = 0; s < substeps; ++s) joints_substep<TERRAIN>(cx, Mdl, q, v, wrench, all_on, K, Jm, eps, h, lds, vdot_out, ter);
+    for (int s = 0; s < substeps; ++s) joints_substep<TERRAIN>(cx, Mdl, q, v, wrench, all_on, K, Jm, eps, h, lds, vdot_out, ter, hts);
   }
   // ---- outputs: as contact_step, then the joint arrays
   const double* Jc = lds + PlantJointLds::Jc;
@@ -299,7 +300,7 @@ HB_HD void joints_step(const Ctx& cx, const DevModel& Mdl, double* q_g, double* 
   for (int i = cx.lane; i < 16; i += cx.nlanes) { q_g[i] = q[i]; v_g[i] = v[i]; }
   for (int i = cx.lane; i < 12; i += cx.nlanes) {
     imp_g[i] = imp[i];
-    if constexpr (TERRAIN == 2) {
+    if constexpr (TERRAIN >= 2) {
       contact_outputs_terrain(ter + Profile::act + Profile::rec * (i / 3), i, Jc, v, imp, h, lambda_out, out.pvel);
     } else if constexpr (TERRAIN) {
       contact_outputs_terrain(ter, i, Jc, v, imp, h, lambda_out, out.pvel);
@@ -318,14 +319,15 @@ HB_HD void joints_step(const Ctx& cx, const DevModel& Mdl, double* q_g, double* 
     jout.limit_torque[j] = imp[22 + j] / h;
   }
   cx.sync();
-  if constexpr (TERRAIN == 2) profile_outputs_select(cx, pio->pro, feet, q);
+  if constexpr (TERRAIN == 3) field_outputs_select(cx, pio->pro, hts, feet, q);
+  else if constexpr (TERRAIN == 2) profile_outputs_select(cx, pio->pro, feet, q);
   for (int c = cx.lane; c < HB_NC; c += cx.nlanes) {
-    if constexpr (TERRAIN == 2) out.gap[c] = terrain_height(ter + Profile::act + Profile::rec * c, feet + 3 * c);
+    if constexpr (TERRAIN >= 2) out.gap[c] = terrain_height(ter + Profile::act + Profile::rec * c, feet + 3 * c);
     else if constexpr (TERRAIN) out.gap[c] = terrain_height(ter, feet + 3 * c);
     else out.gap[c] = feet[3 * c + 2] - K.ground_z;
     out.touching[c] = imp[3 * c + 2] > 0.0 ? 1 : 0;
   }
-  if constexpr (TERRAIN == 2) profile_publish(cx, *pio);
+  if constexpr (TERRAIN >= 2) profile_publish(cx, *pio);
   if (cx.lane == 0) {
     const double res = lds[JointLds::res], jres = lds[JointLds::res + 1];
     bool finite = true;

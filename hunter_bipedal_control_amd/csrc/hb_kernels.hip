@@ -1005,17 +1005,21 @@ struct VariedCtx : DeviceCtx {};
 struct VariedActuatorCtx : DeviceCtx {};
 struct ProfileCtx : DeviceCtx {};
 struct ProfileActuatorCtx : DeviceCtx {};
-// ---- contact model 1 (hb_contact.hpp): ONE body for the sixteen kernels that follow; hb_forms.hpp plant_form picks among them ----------------
+struct FieldCtx : DeviceCtx {};
+struct FieldActuatorCtx : DeviceCtx {};
+// ---- contact model 1 (hb_contact.hpp): ONE body for the twenty kernels that follow; hb_forms.hpp plant_form picks among them ----------------
 // The commanded flags are recorded for hb_plant_sense and play no part in the dynamics.  A kernel passes {} / nullptr for what its form lacks.
 // Five kernels still spell their instantiation out, statement for statement: through the body one lost a load and four measured slower
 // than before; they forward like the others once their forms pass.
 //   GROUND  0: the level ground of K | 1: an inclined plane per instance, a friction coefficient per point (hb_plant_set_terrain; ter:
 //           [B][Terrain::size]) | 2: piecewise-planar ground, a facet per contact point (hb_plant_set_terrain_profile; pb: hb_layout.hpp
 //           ProfileBatch).  The instance's record is staged once per step in LDS behind the form's own arrays (and the actuator's); the
-//           working part of a profile record (hb_contact.hpp Profile) follows it there.
+//           working part of a profile record (hb_contact.hpp Profile) follows it there | 3: a height field, a facet per contact point
+//           (hb_plant_set_terrain_field; fb: hb_layout.hpp FieldBatch): its header is staged where the profile's record is and its
+//           working part lies at the profile's offsets; the heights stay in global memory, a point reads the four of its cell per substep.
 //   MODEL   the DevModel the step reads.  0: the nominal *M | 1: Mvar[i] (hb_plant_set_model_variation; [B] records, hb_layout.hpp
 //           ModelVarBatch — uniform over the workgroup, so its constants stay scalar loads; without a terrain in force the host keeps the
-//           level record of the configuration in ter) | 2: Mvar ? Mvar[i] : *M, so the four profile kernels cover what the terrain and the
+//           level record of the configuration in ter) | 2: Mvar ? Mvar[i] : *M, so the four profile (and field) kernels cover what the terrain and the
 //           varied kernels need eight for.  plant_publish keeps the nominal M, the controller's view.
 //   JOINTS  the joint model (hb_joints.hpp): joints_step; tau_last takes the saturated torque, the one the step integrates.
 //   HYBRID  the actuator's law per substep (c, a) in place of the held torque tau.
@@ -1024,11 +1028,11 @@ __device__ __forceinline__ void plant_ground_step(const PlantBatch& p, const Con
                                                   const ProfileBatch& pb, const ActuatorBatch& a, const ActuatorCmd& c, const hb_contact_config& K,
                                                   const hb_joint_model& J, const DevModel* M, const DevModel* Mvar, const double* tau,
                                                   const int* contact, const int* mode, double dt, int substeps, double* res_rbd, double* res_x0,
-                                                  double* res_t) {
+                                                  double* res_t, const FieldBatch& fb = {}) {
   constexpr int ACT = JOINTS ? JOINT_LDS_TOTAL : CONTACT_LDS_TOTAL;   // LDS: the step's arrays | the actuator's | the ground record
   constexpr int GND = ACT + (HYBRID ? ACT_LDS : 0);
   const int i = blockIdx.x;
-  __shared__ double lds[GND + (GROUND == 1 ? TER_LDS : GROUND == 2 ? PRO_LDS : 0)];
+  __shared__ double lds[GND + (GROUND == 1 ? TER_LDS : GROUND >= 2 ? PRO_LDS : 0)];
   __shared__ int all_on[HB_NC];
   const Ctx cx;
   if (cx.lane < HB_NC) {
@@ -1044,20 +1048,24 @@ __device__ __forceinline__ void plant_ground_step(const PlantBatch& p, const Con
     if (cx.lane < TER_LDS) lds[GND + cx.lane] = ter[TER_LDS * i + cx.lane];
   if constexpr (GROUND == 2)
     for (int k = cx.lane; k < Profile::stored; k += cx.nlanes) lds[GND + k] = pb.prof[size_t(Profile::stored) * i + k];
+  if constexpr (GROUND == 3)
+    if (cx.lane < Field::stored) lds[GND + cx.lane] = fb.hdr[Field::stored * i + cx.lane];
   __syncthreads();
   const ContactOut out{cb.gap + 4 * i, cb.pvel + 12 * i, cb.res + i, cb.touching + 4 * i, cb.status + i};
-  const ProfileIo pio{lds + GND, pb.seg + 5 * i, pb.base + Terrain::size * i};
+  const ProfileIo pio = GROUND == 3 ? ProfileIo{lds + GND, fb.sel + 5 * i, fb.base + Terrain::size * i}
+                                    : ProfileIo{lds + GND, pb.seg + 5 * i, pb.base + Terrain::size * i};
+  const double* __restrict__ hts = GROUND == 3 ? fb.z + size_t(Field::nz) * i : nullptr;
   const DevModel& Ms = MODEL == 1 || (MODEL == 2 && Mvar) ? Mvar[i] : *M;
   const JointOut jout{jb.tau_applied + 10 * i, jb.friction_torque + 10 * i, jb.limit_torque + 10 * i, jb.res + i, jb.status + i};
   const HybridActuator act = actuator_of(c, a, i, lds + ACT);
   if constexpr (JOINTS)
     joints_step<HYBRID, GROUND>(cx, Ms, p.q + 16 * i, p.v + 16 * i, cb.imp + 12 * i, jb.imp + 20 * i, HYBRID ? nullptr : tau + 10 * i,
                                 cb.use_wrench ? cb.wrench + 6 * i : nullptr, all_on, K, J, p.eps, dt, substeps, lds, p.lambda + 12 * i, p.vdot + 16 * i,
-                                p.tau_last + 10 * i, out, jout, HYBRID ? &act : nullptr, GROUND ? lds + GND : nullptr, GROUND == 2 ? &pio : nullptr);
+                                p.tau_last + 10 * i, out, jout, HYBRID ? &act : nullptr, GROUND ? lds + GND : nullptr, GROUND >= 2 ? &pio : nullptr, hts);
   else
     contact_step<HYBRID, GROUND>(cx, Ms, p.q + 16 * i, p.v + 16 * i, cb.imp + 12 * i, HYBRID ? nullptr : tau + 10 * i,
                                  cb.use_wrench ? cb.wrench + 6 * i : nullptr, all_on, K, p.eps, dt, substeps, lds, p.lambda + 12 * i, p.vdot + 16 * i, out,
-                                 HYBRID ? &act : nullptr, GROUND ? lds + GND : nullptr, GROUND == 2 ? &pio : nullptr);
+                                 HYBRID ? &act : nullptr, GROUND ? lds + GND : nullptr, GROUND >= 2 ? &pio : nullptr, hts);
   if constexpr (HYBRID && !JOINTS)
     if (cx.lane < HB_NJ) p.tau_last[10 * i + cx.lane] = act.tau[cx.lane];   // (the lane's own entry)
   if (cx.lane == 0) plant_publish(p, M, i, dt, res_rbd, res_x0, res_t);
@@ -1265,6 +1273,42 @@ __global__ __launch_bounds__(64) void k_plant_profile_joints_hybrid(PlantBatch p
   joints_step<true, 2>(cx, Ms, p.q + 16 * i, p.v + 16 * i, cb.imp + 12 * i, jb.imp + 20 * i, nullptr, cb.use_wrench ? cb.wrench + 6 * i : nullptr, all_on, K,
                        J, p.eps, dt, substeps, lds, p.lambda + 12 * i, p.vdot + 16 * i, p.tau_last + 10 * i, out, jout, &act, pio.pro, &pio);
   if (cx.lane == 0) plant_publish(p, M, i, dt, res_rbd, res_x0, res_t);
+}
+// the four forms on a height field (hb_plant_set_terrain_field): GROUND 3 of the shared body
+__global__ __launch_bounds__(64) void k_plant_field(PlantBatch p, ContactBatch cb, FieldBatch fb, hb_contact_config K, const DevModel* __restrict__ M,
+                                                    const DevModel* __restrict__ Mvar, const double* tau, const int* contact, const int* mode, double dt,
+                                                    int substeps, double* res_rbd, double* res_x0, double* res_t) {
+  plant_ground_step<3, 2, false, false, FieldCtx>(p, cb, {}, nullptr, {}, {}, {}, K, {}, M, Mvar, tau, contact, mode, dt, substeps, res_rbd, res_x0, res_t, fb);
+}
+__global__ __launch_bounds__(64) void k_plant_field_joints(PlantBatch p, ContactBatch cb, JointBatch jb, FieldBatch fb, hb_contact_config K,
+                                                           hb_joint_model J, const DevModel* __restrict__ M, const DevModel* __restrict__ Mvar,
+                                                           const double* tau, const int* contact, const int* mode, double dt, int substeps,
+                                                           double* res_rbd, double* res_x0, double* res_t) {
+  plant_ground_step<3, 2, true, false, FieldCtx>(p, cb, jb, nullptr, {}, {}, {}, K, J, M, Mvar, tau, contact, mode, dt, substeps, res_rbd, res_x0, res_t, fb);
+}
+__global__ __launch_bounds__(64) void k_plant_field_hybrid(PlantBatch p, ContactBatch cb, FieldBatch fb, ActuatorBatch a, ActuatorCmd c,
+                                                           hb_contact_config K, const DevModel* __restrict__ M, const DevModel* __restrict__ Mvar,
+                                                           const int* contact, const int* mode, double dt, int substeps, double* res_rbd,
+                                                           double* res_x0, double* res_t) {
+  plant_ground_step<3, 2, false, true, FieldActuatorCtx>(p, cb, {}, nullptr, {}, a, c, K, {}, M, Mvar, nullptr, contact, mode, dt, substeps, res_rbd, res_x0, res_t, fb);
+}
+__global__ __launch_bounds__(64) void k_plant_field_joints_hybrid(PlantBatch p, ContactBatch cb, JointBatch jb, FieldBatch fb, ActuatorBatch a,
+                                                                  ActuatorCmd c, hb_contact_config K, hb_joint_model J,
+                                                                  const DevModel* __restrict__ M, const DevModel* __restrict__ Mvar,
+                                                                  const int* contact, const int* mode, double dt, int substeps, double* res_rbd,
+                                                                  double* res_x0, double* res_t) {
+  plant_ground_step<3, 2, true, true, FieldActuatorCtx>(p, cb, jb, nullptr, {}, a, c, K, J, M, Mvar, nullptr, contact, mode, dt, substeps, res_rbd, res_x0, res_t, fb);
+}
+// hb_plant_field_eval: the facet under n world points per instance of the field in force, one thread per point
+__global__ __launch_bounds__(64) void k_field_eval(FieldBatch fb, int n, const double* __restrict__ xyz, int* __restrict__ facet,
+                                                   double* __restrict__ records, double* __restrict__ height) {
+  const long e = long(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (e >= long(fb.B) * n) return;
+  const long i = e / n;
+  double rec[Terrain::size];
+  facet[e] = field_facet(fb.hdr + Field::stored * i, fb.z + size_t(Field::nz) * i, xyz + 3 * e, rec);
+  for (int k = 0; k < Profile::rec; ++k) records[Profile::rec * e + k] = rec[k];
+  height[e] = terrain_height(rec, xyz + 3 * e);
 }
 __global__ void k_plant_reset(PlantBatch p, const DevModel* __restrict__ M) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;

@@ -204,6 +204,23 @@ constexpr void fields(ProfileBatch& t, size_t, F&& f) {
   HB_FIELD(t.prof, Profile::stored); HB_FIELD(t.seg, HB_NC + 1); HB_FIELD(t.base, Terrain::size);
 }
 
+// per-instance height field of the ground-contact plant (hb_plant_set_terrain_field), allocated by the first call that gives one: hdr: the
+// stored part of the record the field kernels stage per instance (hb_contact.hpp Field: mu of the four points in a Terrain head |
+// direction | origin | spacing | node counts); z: the heights, [HB_FIELD_MAX_NODES][HB_FIELD_MAX_NODES] per instance, read from global
+// memory by the step; sel: the facet id under the four contact points and the base origin at the end of the last step; base: the Terrain
+// record of the facet under the base origin there (what k_plant_episode takes in place of the terrain records)
+struct FieldBatch {
+  int B;
+  double* hdr;
+  double* z;
+  int* sel;
+  double* base;
+};
+template <class F>
+constexpr void fields(FieldBatch& t, size_t, F&& f) {
+  HB_FIELD(t.hdr, Field::stored); HB_FIELD(t.z, Field::nz); HB_FIELD(t.sel, HB_NC + 1); HB_FIELD(t.base, Terrain::size);
+}
+
 // per-instance model variation of the ground-contact plant (hb_plant_set_model_variation, hb_modelvar.hpp), allocated by the first call
 // that gives one: the DevModel record each instance steps on, [B] records of sizeof(DevModel) (about 1.7 KB)
 struct ModelVarBatch {
@@ -402,6 +419,7 @@ static_assert(sizeof(ContactBatch) == 2 * sizeof(int) + n_fields<ContactBatch>()
 static_assert(sizeof(JointBatch) == kPtr /*B*/ + n_fields<JointBatch>() * kPtr, "describe every array of JointBatch in fields()");
 static_assert(sizeof(TerrainBatch) == kPtr /*B*/ + n_fields<TerrainBatch>() * kPtr, "describe every array of TerrainBatch in fields()");
 static_assert(sizeof(ProfileBatch) == kPtr /*B*/ + n_fields<ProfileBatch>() * kPtr, "describe every array of ProfileBatch in fields()");
+static_assert(sizeof(FieldBatch) == kPtr /*B*/ + n_fields<FieldBatch>() * kPtr, "describe every array of FieldBatch in fields()");
 static_assert(sizeof(ModelVarBatch) == kPtr /*B*/ + n_fields<ModelVarBatch>() * kPtr, "describe every array of ModelVarBatch in fields()");
 static_assert(sizeof(EpisodeBatch) == 2 * sizeof(int) + (n_fields<EpisodeBatch>() + 1 /*trace*/) * kPtr, "describe every array of EpisodeBatch in fields()");
 static_assert(sizeof(RespawnBatch) == kPtr /*B*/ + n_fields<RespawnBatch>() * kPtr, "describe every array of RespawnBatch in fields()");

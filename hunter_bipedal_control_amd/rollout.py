@@ -79,6 +79,60 @@ def pack_profiles(profiles):
     return n, out
 
 
+FIELD_SLOPE2_MAX = 3.0   # hb_plant_set_terrain_field refuses a triangle with p^2 + r^2 above 3 (1 + 1e-12): n_z < 0.5
+
+
+def field_slopes2(heights, spacing) -> np.ndarray:
+    """p^2 + r^2 of both triangles of every cell of the height field heights[nu][nw] with node spacing (du, dw): [nu - 1][nw - 1][2]
+    (lower triangle, upper triangle), as hb_plant_set_terrain_field cuts the cells (along the diagonal from node (i, j) to (i + 1, j + 1))."""
+    z = np.asarray(heights, dtype=float)
+    du, dw = float(spacing[0]), float(spacing[1])
+    z00, z10, z01, z11 = z[:-1, :-1], z[1:, :-1], z[:-1, 1:], z[1:, 1:]
+    low = ((z10 - z00) / du) ** 2 + ((z11 - z10) / dw) ** 2
+    up = ((z11 - z01) / du) ** 2 + ((z01 - z00) / dw) ** 2
+    return np.stack([low, up], axis=-1)
+
+
+def field_from_profile(direction, knots, du: float, w0: float = -1.0, dw: float = 2.0, nw: int = 2, mu=None) -> dict:
+    """The height field that is the terrain profile (direction, knots[K][2]) sampled on a grid: the first grid axis is the profile's
+    direction with a node every du from the first knot to the last, every knot on a node (to 1e-9 du, else ValueError), the heights
+    constant along the second axis (nw nodes every dw from w0).  Every cell then lies within one segment, so either triangle carries its
+    segment's plane and the border cells continue the end segments as the profile does.  -> the dict of one instance of
+    ResidentLoop(terrain=dict(field=...)): dir, origin, spacing, heights[nu][nw] (and mu when given)."""
+    k = np.asarray(knots, dtype=float)
+    at = (k[:, 0] - k[0, 0]) / du
+    nu = int(round(at[-1])) + 1
+    if np.abs(at - np.round(at)).max() > 1e-9 or not 2 <= nu <= abi.HB_FIELD_MAX_NODES or not 2 <= nw <= abi.HB_FIELD_MAX_NODES:
+        raise ValueError("field_from_profile: every knot on a node of the grid, 2 .. HB_FIELD_MAX_NODES nodes per axis")
+    z = np.interp(np.round(at[0]) + np.arange(nu), np.round(at), k[:, 1])
+    out = dict(dir=np.asarray(direction, dtype=float), origin=np.array([k[0, 0], w0]), spacing=np.array([du, dw]), heights=np.repeat(z[:, None], nw, axis=1))
+    if mu is not None:
+        out["mu"] = np.asarray(mu, dtype=float)
+    return out
+
+
+def rough_field(seed: int, amplitude: float, spacing, shape=(abi.HB_FIELD_MAX_NODES, abi.HB_FIELD_MAX_NODES)) -> np.ndarray:
+    """Heights [nu][nw] of seeded rough ground: independent bumps uniform in [-amplitude, amplitude] per node (numpy default_rng(seed)),
+    scaled down as a whole where a triangle would break the slope bound of hb_plant_set_terrain_field (p^2 + r^2 <= 0.99 x 3 after it)."""
+    z = amplitude * np.random.default_rng(seed).uniform(-1.0, 1.0, shape)
+    worst = float(field_slopes2(z, spacing).max())
+    if worst > 0.99 * FIELD_SLOPE2_MAX:
+        z *= np.sqrt(0.99 * FIELD_SLOPE2_MAX / worst)
+    return z
+
+
+def pack_fields(fields):
+    """[B] dicts(dir[2], origin[2], spacing[2], heights[nu_i][nw_i], mu[4] or missing) -> the arguments of
+    HunterSolver.plant_set_terrain_field: (dir[B][2], origin[B][2], spacing[B][2], [B] height arrays, mu[B][4] or None).  mu: given by every
+    instance or by none."""
+    with_mu = [f.get("mu") is not None for f in fields]
+    if any(with_mu) and not all(with_mu):
+        raise ValueError("pack_fields: mu for every instance or for none")
+    col = lambda k: np.array([np.asarray(f[k], dtype=float) for f in fields]).reshape(len(fields), 2)  # noqa: E731
+    return (col("dir"), col("origin"), col("spacing"), [np.asarray(f["heights"], dtype=float) for f in fields],
+            np.array([f["mu"] for f in fields], dtype=float) if all(with_mu) and fields else None)
+
+
 def payload_on_base(mass, pos, inertia=None) -> np.ndarray:
     """The [B][10] payload array of hb_plant_set_model_variation: mass[B] (or a scalar) [kg], pos[B][3] (or [3]) = the payload's centre of
     mass in the base frame from the base origin [m], inertia[B][6] (or [6]) = xx xy xz yy yz zz about that centre in base axes (None: a
@@ -217,7 +271,10 @@ class ResidentLoop:
         [B][2], knots=[B] knot arrays [K_i][2] (curb_profile, stairs_profile) or [B][K][2], mu=[B][4] or missing), relative=True):
         piecewise-planar ground per instance (hb_plant_set_terrain_profile), `relative` adds the height of the lowest contact point of each
         instance's start to the knot heights.  Needs contact_config; set after the contact model.  The controller, estimator and swing
-        planner assume level ground unless ground_map tells them otherwise.
+        planner assume level ground unless ground_map tells them otherwise.  Or dict(field=dict(dir=[B][2], origin=[B][2], spacing=[B][2],
+        heights=[B] arrays [nu_i][nw_i] (rough_field, field_from_profile) or [B][nu][nw], mu=[B][4] or missing) or a list of B such dicts of
+        one instance each, relative=True): a triangulated height field per instance (hb_plant_set_terrain_field), `relative` as for the
+        profile.  ground_map="plant" is refused beside a field (the controller's map is one-dimensional), and so is respawn=.
         ground_map: the ground the controller's side plans and filters on (hb_ground_set_profile) — None: the level plane; "plant": the
         plant's terrain profile with the start offset taken out (the knots of terrain["profile"] as given when relative, less the height of
         the lowest contact point of the start otherwise), so a level relative profile is the zero map; dict(dir=[B][2], knots=[B] knot
@@ -255,6 +312,13 @@ class ResidentLoop:
             raise ValueError("model_variation belongs to the ground-contact plant: give contact_config as well")
         if terrain is not None and contact_config is None:
             raise ValueError("terrain belongs to the ground-contact plant: give contact_config as well")
+        if terrain is not None and terrain.get("field") is not None:
+            if terrain.get("plane") is not None or terrain.get("mu") is not None or terrain.get("profile") is not None:
+                raise ValueError("terrain: a field, a profile or a plane, one ground at a time (the field's mu goes inside field=)")
+            if isinstance(ground_map, str) and ground_map == "plant":
+                raise ValueError('ground_map="plant" with a height field: the controller\'s map is one-dimensional (give dict(dir=..., knots=...) or None)')
+            if respawn is not None:
+                raise ValueError("no respawn on a height field")
         if actuator not in ("held", "substep"):
             raise ValueError('actuator is "held" or "substep"')
         self.actuator = actuator
@@ -296,7 +360,15 @@ class ResidentLoop:
             solver.plant_set_contact_model(contact_config)
             if joint_model is not None:
                 solver.plant_set_joint_model(abi.make_joint_model(params, **joint_model) if isinstance(joint_model, dict) else joint_model)
-            if terrain is not None and terrain.get("profile") is not None:
+            if terrain is not None and terrain.get("field") is not None:
+                fld = terrain["field"]
+                flds = fld if isinstance(fld, (list, tuple)) else [{k: v[i] for k, v in fld.items() if v is not None} for i in range(self.B)]
+                d, org, sp, hts, fmu = pack_fields(flds)
+                if terrain.get("relative", True):
+                    z0 = plane_under_contact_points(solver, q0, [0.0, 0.0, 1.0])
+                    hts = [h + z0[i] for i, h in enumerate(hts)]
+                solver.plant_set_terrain_field(d, org, sp, hts, fmu)
+            elif terrain is not None and terrain.get("profile") is not None:
                 if terrain.get("plane") is not None or terrain.get("mu") is not None:
                     raise ValueError("terrain: a profile or a plane, one ground at a time (the profile's mu goes inside profile=)")
                 prof = terrain["profile"]

@@ -36,6 +36,7 @@ ABI_SYMBOLS = [
     "hb_plant_set_joint_model", "hb_plant_get_joints", "hb_plant_step_hybrid", "hb_plant_get_actuator",
     "hb_plant_set_terrain", "hb_plant_get_terrain",
     "hb_plant_set_terrain_profile", "hb_plant_get_terrain_profile",
+    "hb_plant_set_terrain_field", "hb_plant_get_terrain_field", "hb_plant_field_eval",
     "hb_plant_set_model_variation", "hb_plant_get_model_variation",
     "hb_plant_set_episode", "hb_plant_get_episode",
     "hb_plant_set_respawn", "hb_plant_respawn", "hb_plant_get_respawn",
@@ -371,6 +372,46 @@ class HunterSolver:
                    records=np.zeros((self.B, K - 1, abi.HB_PROFILE_RECORD)), segment=np.zeros((self.B, 5), dtype=np.int32))
         self._check(self.lib.hb_plant_get_terrain_profile(self.ctx, *[_p(a) for a in out.values()]), "hb_plant_get_terrain_profile")
         return out
+
+    # ---- per-instance height field of the ground-contact plant (hb_plant_set_terrain_field) ------------------------------------------
+    def plant_set_terrain_field(self, direction=None, origin=None, spacing=None, heights=None, mu=None):
+        """Triangulated height field per instance: direction [B][2] = the first grid axis a (the second is b = (-a_y, a_x)); origin [B][2]
+        = grid coordinates (u0, w0) of node (0, 0); spacing [B][2] = (du, dw); heights = a [B][nu][nw] array, or a list of B arrays
+        [nu_i][nw_i], 2 <= nu, nw <= abi.HB_FIELD_MAX_NODES; mu [B][4] per contact point (None: the contact model's mu).  All None: no
+        field.  Replaces a terrain or a profile; clears the contact impulses."""
+        if direction is None and origin is None and spacing is None and heights is None and mu is None:
+            self._check(self.lib.hb_plant_set_terrain_field(self.ctx, None, None, None, None, None, None), "hb_plant_set_terrain_field")
+            return
+        N = abi.HB_FIELD_MAX_NODES
+        assert len(heights) == self.B, len(heights)
+        n, z = np.zeros((self.B, 2), dtype=np.int32), np.zeros((self.B, N, N))
+        for i, h in enumerate(heights):
+            h = np.asarray(h, dtype=np.float64)
+            assert h.ndim == 2, h.shape
+            n[i] = h.shape
+            z[i, :min(N, h.shape[0]), :min(N, h.shape[1])] = h[:N, :N]
+        m = None if mu is None else _f64(mu, (self.B, 4))
+        self._check(self.lib.hb_plant_set_terrain_field(self.ctx, _p(n), _p(_f64(direction, (self.B, 2))), _p(_f64(origin, (self.B, 2))),
+                                                        _p(_f64(spacing, (self.B, 2))), _p(z), _p(m)), "hb_plant_set_terrain_field")
+
+    def plant_get_terrain_field(self):
+        """-> dict(n_nodes[B][2], dir[B][2] as stored, origin[B][2], spacing[B][2], heights[B][32][32], mu[B][4], facet[B][5] = the facet id
+        under the four contact points and under the base origin at the end of the last step) of the field in force."""
+        N = abi.HB_FIELD_MAX_NODES
+        out = dict(n_nodes=np.zeros((self.B, 2), dtype=np.int32), dir=np.zeros((self.B, 2)), origin=np.zeros((self.B, 2)), spacing=np.zeros((self.B, 2)),
+                   heights=np.zeros((self.B, N, N)), mu=np.zeros((self.B, 4)), facet=np.zeros((self.B, 5), dtype=np.int32))
+        self._check(self.lib.hb_plant_get_terrain_field(self.ctx, *[_p(a) for a in out.values()]), "hb_plant_get_terrain_field")
+        return out
+
+    def plant_field_eval(self, xyz):
+        """The device facet selection of the field in force: xyz [B][n][3] world points per instance -> (facet_id[B][n],
+        records[B][n][10] = (T row-major, d), height[B][n] = n . x - d)."""
+        x = np.ascontiguousarray(xyz, dtype=np.float64)
+        assert x.ndim == 3 and x.shape[0] == self.B and x.shape[2] == 3, x.shape
+        n = x.shape[1]
+        fid, rec, h = np.zeros((self.B, n), dtype=np.int32), np.zeros((self.B, n, abi.HB_PROFILE_RECORD)), np.zeros((self.B, n))
+        self._check(self.lib.hb_plant_field_eval(self.ctx, C.c_int32(n), _p(x), _p(fid), _p(rec), _p(h)), "hb_plant_field_eval")
+        return fid, rec, h
 
     # ---- ground map of the controller (hb_ground_set_profile) -----------------------------------------------------------------------
     def ground_set_profile(self, n_knots=None, direction=None, knots=None):

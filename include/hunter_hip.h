@@ -373,7 +373,8 @@ int32_t hb_plant_get_joints(hb_ctx* ctx, double* tau_applied, double* friction_t
  * before hb_plant_reset or outside contact model 1.  The call clears the contact impulses (the warm start is expressed in the frame of
  * before) and nothing else.  The terrain survives hb_plant_reset and a second hb_plant_set_contact_model with mode 1; leaving model 1
  * switches it off.  cfg.mu and cfg.ground_z are not read by a step while a terrain is in force.  One ground at a time: every successful
- * call, both NULL included, ends a terrain profile in force (hb_plant_set_terrain_profile below). */
+ * call, both NULL included, ends a terrain profile (hb_plant_set_terrain_profile below) or a height field (hb_plant_set_terrain_field)
+ * in force. */
 int32_t hb_plant_set_terrain(hb_ctx* ctx, const double* plane /*[batch][4] or NULL*/, const double* mu /*[batch][4] or NULL*/);
 /* The terrain in force (any pointer may be NULL): plane[batch][4] with the stored unit normal, mu[batch][4], frame[batch][9] = T
  * row-major.  Without a terrain: what the model in force amounts to, (0, 0, 1, ground_z), cfg.mu and the identity.  HB_ERR_STATE before
@@ -402,8 +403,8 @@ int32_t hb_plant_get_terrain(hb_ctx* ctx, double* plane, double* mu, double* fra
  * profile off.  HB_ERR_ARG for K out of range, a non-finite entry, |a| = 0, a knot spacing <= 0, |m_j| > sqrt(3) (n_z < 0.5) or mu < 0 (the
  * message names the first offending instance; the profile in force is kept).  HB_ERR_STATE before hb_plant_reset, outside contact
  * model 1, and while a respawn configuration or a scenario with the slope or friction channel is in force (those two calls in turn are
- * refused while a profile is in force).  One ground at a time: setting a profile replaces a terrain of hb_plant_set_terrain and
- * hb_plant_set_terrain replaces a profile; both clear the contact impulses and nothing else.  The profile survives hb_plant_reset and a
+ * refused while a profile is in force).  One ground at a time: setting a profile replaces a terrain of hb_plant_set_terrain or a height
+ * field of hb_plant_set_terrain_field, and hb_plant_set_terrain replaces a profile; both clear the contact impulses and nothing else.  The profile survives hb_plant_reset and a
  * second hb_plant_set_contact_model with mode 1; leaving model 1 switches it off.  With an episode record in force, height and tilt of
  * the record are measured against the facet under the base origin. */
 #define HB_PROFILE_MAX_KNOTS 16
@@ -414,6 +415,53 @@ int32_t hb_plant_set_terrain_profile(hb_ctx* ctx, const int32_t* n_knots /*[batc
  * on), segment[batch][5] = the segment under the four contact points and under the base origin at the end of the last step (at the state
  * of the last hb_plant_reset or of the set call before a step).  HB_ERR_STATE without a profile in force. */
 int32_t hb_plant_get_terrain_profile(hb_ctx* ctx, int32_t* n_knots, double* dir, double* knots, double* mu, double* records, int32_t* segment);
+
+/* ---- per-instance height field of contact model 1: two-dimensional triangulated ground per robot (cross slopes, bumps, rough ground) ---
+ * Instance i has
+ *   dir      a horizontal direction a = (a_x, a_y), normalised before it is stored; b = (-a_y, a_x) is the second grid axis;
+ *   origin   (u0, w0): the grid coordinates of node (0, 0);
+ *   spacing  (du, dw) > 0: the distance between neighbouring nodes along a and along b;
+ *   n_nodes  (nu, nw), 2 <= nu, nw <= HB_FIELD_MAX_NODES;
+ *   heights  z[iu][iw], the height of node (iu, iw), which lies at the world point a (u0 + iu du) + b (w0 + iw dw);
+ *   mu       a friction coefficient mu_c >= 0 per contact point.
+ * Selection.  A world point x has u = a . (x, y) - u0, w = b . (x, y) - w0, the cell i = clamp(floor(u / du), 0, nu - 2),
+ * j = clamp(floor(w / dw), 0, nw - 2) and the cell coordinates fu = u / du - i, fw = w / dw - j (outside the grid the planes of the border
+ * cell continue, as the end segments of a profile do).  Each cell is cut along the diagonal from node (i, j) to node (i + 1, j + 1): with
+ * fu >= fw the facet is the lower triangle (t = 0), p = (z[i+1][j] - z[i][j]) / du, r = (z[i+1][j+1] - z[i+1][j]) / dw; otherwise the upper
+ * one (t = 1), r = (z[i][j+1] - z[i][j]) / dw, p = (z[i+1][j+1] - z[i][j+1]) / du.  The facet id is 2 (i (nw - 1) + j) + t.  A NaN
+ * coordinate selects facet 0 and yields a NaN record.
+ * Plane.  n = (-(p a_x + r b_x), -(p a_y + r b_y), 1) / sqrt(1 + p^2 + r^2), normalised until its length rounds to 1;
+ * d = n . (a (u0 + i du) + b (w0 + j dw), z[i][j]) (both triangles of a cell pass through node (i, j)); the 10-double record (T, d) is the
+ * frame of n exactly as hb_plant_set_terrain builds it for the plane (n, d).  Every operation is rounded on its own; host and device run
+ * one routine.  The record is computed where it is needed from the four heights of the cell: no table of facets is stored.
+ * Step.  The definition of the terrain profile above holds with this facet in place of the segment: the facet of point c is selected
+ * from the contact points of the substep's start, J~ = blockdiag(T_c') J, the impulses are components in the point's own frame,
+ * lambda_c = T_c p_c / h and point_vel stay world quantities, the outputs select again at q+, and HB_CONTACT_FALLEN as well as height and
+ * tilt of an episode record are measured over the facet under the base origin.  A field level at ground_z with mu = cfg.mu is the step
+ * without a terrain.  With a model variation in force the step runs on the instance's own model.
+ *
+ * n_nodes[batch][2]; dir[batch][2]; origin[batch][2]; spacing[batch][2]; heights[batch][HB_FIELD_MAX_NODES][HB_FIELD_MAX_NODES], entries
+ * beyond (nu, nw) are not read; mu[batch][4] or NULL for cfg.mu (a snapshot).  The five leading pointers all NULL (and mu NULL) switch
+ * the field off.  HB_ERR_ARG for a count out of range, a non-finite entry, |a| = 0, a spacing <= 0, a triangle with
+ * p^2 + r^2 > 3 (1 + 1e-12) (n_z < 0.5) or mu < 0 (the message names the first offending instance; the ground in force is kept).
+ * HB_ERR_STATE before hb_plant_reset, outside contact model 1, and while a respawn configuration, a profile draw or a scenario with the
+ * slope or friction channel is in force (those three calls in turn are refused while a field is in force).  One ground at a time: plane,
+ * profile and field replace one another; setting a field clears the contact impulses and nothing else.  The field survives
+ * hb_plant_reset and a second hb_plant_set_contact_model with mode 1; leaving model 1 switches it off. */
+#define HB_FIELD_MAX_NODES 32
+int32_t hb_plant_set_terrain_field(hb_ctx* ctx, const int32_t* n_nodes /*[batch][2]*/, const double* dir /*[batch][2]*/,
+                                   const double* origin /*[batch][2]*/, const double* spacing /*[batch][2]*/,
+                                   const double* heights /*[batch][HB_FIELD_MAX_NODES][HB_FIELD_MAX_NODES]*/,
+                                   const double* mu /*[batch][4] or NULL*/);
+/* The field in force (any pointer may be NULL): n_nodes, dir (as stored), origin, spacing, heights (zero beyond (nu, nw)) and mu as laid
+ * out above, facet[batch][5] = the facet id under the four contact points and under the base origin at the end of the last step (at the
+ * state of the last hb_plant_reset or of the set call before a step).  HB_ERR_STATE without a field in force. */
+int32_t hb_plant_get_terrain_field(hb_ctx* ctx, int32_t* n_nodes, double* dir, double* origin, double* spacing, double* heights, double* mu,
+                                   int32_t* facet);
+/* Unit entry: the device's facet selection for n_points arbitrary world points per instance of the field in force.  xyz[batch][n_points][3];
+ * facet_id[batch][n_points], records[batch][n_points][10] = (T row-major, d) of the facet, height[batch][n_points] = n . x - d (any output
+ * may be NULL).  HB_ERR_STATE without a field in force. */
+int32_t hb_plant_field_eval(hb_ctx* ctx, int32_t n_points, const double* xyz, int32_t* facet_id, double* records, double* height);
 
 /* ---- per-instance model variation of contact model 1: a mass scale per body and a payload on the base ---------------------------------
  * Instance i steps on inertial parameters of its own; everything on the controller's side keeps the nominal model of hb_create.  The

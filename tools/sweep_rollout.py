@@ -22,6 +22,10 @@
                                                         survival, progress and tilt by kind and height bin, from one run(n) and one
                                                         read-back of the draw's log.  --ground-map: the controller's map follows every drawn
                                                         ground; --joint-model as everywhere
+    python tools/sweep_rollout.py --rough 1500 --robots 64   rough ground: a seeded 32 x 32 height field of 5 cm cells per robot, bump amplitude
+                                                        0 .. --rough-max metres in eight steps over the batch (hb_plant_set_terrain_field), the
+                                                        controller blind; survival, tilt and slip by amplitude from one run(n) and one
+                                                        read-back of the episode record
     python tools/sweep_rollout.py --readback            the two sweeps once more with the per-tick read-back loop the findings of items 17 - 20
                                                         were made with, for the wall time per tick of both
 
@@ -37,7 +41,7 @@ import numpy as np
 sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
 from hunter_bipedal_control_amd import abi, ingest  # noqa: E402
 from hunter_bipedal_control_amd.rollout import (ResidentLoop, curb_profile, episode_summary, payload_on_base, profile_draw_table,  # noqa: E402
-                                                respawn_summary, scenario_table)
+                                                respawn_summary, rough_field, scenario_table)
 from hunter_bipedal_control_amd.solver import HunterSolver  # noqa: E402
 
 FRICTION = [0.7, 0.5, 0.4, 0.3, 0.2, 0.15, 0.1, 0.05]
@@ -84,6 +88,44 @@ def run_curb(params, heights, at, ticks, joint_model=None, riser_slope=np.sqrt(3
         return rec, s.plant_get_terrain_profile()["segment"], wall
     finally:
         s.close()
+
+
+ROUGH_STEPS, ROUGH_CELL = 8, 0.05
+
+
+def run_rough(params, robots, ticks, amp_max, joint_model=None):
+    """One batch: instance i trots along +x over a rough field of its own (seed i) with bump amplitude amp_max * (i % 8) / 7, 32 x 32 nodes of
+    5 cm, from 0.35 m behind the start to 1.2 m ahead of it -> (amplitude per instance, episode record, wall seconds of the ticks)."""
+    B = robots
+    amp = amp_max * (np.arange(B) % ROUGH_STEPS) / (ROUGH_STEPS - 1)
+    fields = [dict(dir=[1.0, 0.0], origin=[-0.35, -0.775], spacing=[ROUGH_CELL, ROUGH_CELL], heights=rough_field(i, amp[i], (ROUGH_CELL, ROUGH_CELL)))
+              for i in range(B)]
+    s = HunterSolver(params, batch=B, max_nodes=108)
+    try:
+        horizon = 100 * params["config"]["dt"]
+        # (fall_height 0.2 as in run_curb: the fall test is measured along the normal of the facet under the base origin)
+        loop = ResidentLoop(s, params, ["trot"] * B, np.tile([0.2, 0.0, 0.0, 0.0], (B, 1)), contact_config=dict(fall_height=0.2), joint_model=joint_model,
+                            terrain=dict(field=fields, relative=True), static_schedule_until=ticks * 0.002 + horizon + 1.5, episode=dict(slip_speed=0.05))
+        s.sync()
+        t0 = time.perf_counter()
+        loop.run(ticks)
+        rec = loop.episode()
+        return amp, rec, time.perf_counter() - t0
+    finally:
+        s.close()
+
+
+def print_rough(amp, rec):
+    """Per amplitude: robots, how many are up at the end, median end tick of those that fell, median of the largest tilt, mean slip ticks."""
+    heads = ("amplitude", "robots", "up", "survival", "end med", "tiltmax med", "slipT mean", "nonfin")
+    print("   " + " ".join(f"{h:>12}" for h in heads))
+    for a in np.unique(amp):
+        m = amp == a
+        up = rec["END_TICK"][m] < 0
+        fell = rec["END_TICK"][m][~up]
+        cells = (f"{a:.4f}", f"{int(m.sum())}", f"{int(up.sum())}", f"{up.mean():.3f}", f"{int(np.median(fell))}" if len(fell) else "-",
+                 f"{np.median(rec['TILT_MAX'][m]):.4g}", f"{rec['SLIP_TICKS'][m].mean():.1f}", f"{int((rec['FIRST_NONFINITE'][m] >= 0).sum())}")
+        print("   " + " ".join(f"{c:>12}" for c in cells))
 
 
 def run_respawn(params, mu, ticks, max_ticks, joint_model=None):
@@ -290,6 +332,8 @@ def main():
     ap.add_argument("--ground-map", action="store_true", help="--curb with the controller's ground map set to the plant's profile (hb_ground_set_profile); --random-curbs with the map following every drawn ground")
     ap.add_argument("--curb-at", type=float, default=0.08, help="where the riser of --curb starts, metres ahead of the base origin of the start")
     ap.add_argument("--riser-slope", type=float, default=float(np.sqrt(3.0)), help="slope of the riser of --curb (at most sqrt(3))")
+    ap.add_argument("--rough", type=int, metavar="N_TICKS", help="N_TICKS ticks on a seeded rough height field per robot, bump amplitude 0 .. --rough-max over the batch (--robots); one read-back")
+    ap.add_argument("--rough-max", type=float, default=0.035, help="largest bump amplitude of --rough, metres")
     ap.add_argument("--readback", action="store_true", help="also time the per-tick read-back loop on the two sweeps")
     args = ap.parse_args()
     params = ingest.load_packaged()
@@ -299,6 +343,12 @@ def main():
         print(f"-- curb sweep, {'controller on the ground map' if args.ground_map else 'controller blind'}, B = {len(CURBS)}, riser of slope {args.riser_slope:.3g} {args.curb_at} m ahead, {args.ticks} ticks, run(): {1e3 * wall / args.ticks:.3f} ms per tick")
         table("height", CURBS, rec)
         print("   segment under the four contact points and the base at the end (0 before the riser, 1 on it, 2 beyond):", seg.tolist())
+        return
+    if args.rough:
+        amp, rec, wall = run_rough(params, args.robots, args.rough, args.rough_max, joint_model=jm)
+        print(f"-- rough ground, controller blind, {'joint model' if args.joint_model else 'ideal joints'}, B = {args.robots}, {args.rough} ticks, "
+              f"run() and one read-back: {wall:.3f} s, {1e3 * wall / args.rough:.3f} ms per tick")
+        print_rough(amp, rec)
         return
     if args.random_curbs:
         log, tot, wall = run_random_curbs(params, args.robots, args.random_curbs, args.max_ticks, joint_model=jm, ground_map=args.ground_map)
