@@ -166,6 +166,12 @@ struct hb_ctx {
   GroundBatch ground{};
   std::vector<double> ground_host, ground_knots;
   bool ground_on = false;
+  // field map of the controller (hb_ground_set_field): gfield_on while one is in force (the field forms then run); one map at a time, so
+  // never together with ground_on.  gfield_hdr_host ([B][GroundField::size]) and gfield_z_host ([B][GroundField::nz], zero beyond
+  // (nu, nw)) are the host images.  Nothing resets it but the two setters.
+  GroundFieldBatch gfield{};
+  std::vector<double> gfield_hdr_host, gfield_z_host;
+  bool gfield_on = false;
   // state estimator (allocated on the first hb_estimator_reset)
   EstBatch est{};
   hb_estimator_config est_cfg{};
@@ -466,7 +472,7 @@ static int32_t resident_write(hb_ctx* ctx, hipStream_t s, bool fence, F&& launch
 
 extern "C" {
 
-int32_t hb_version(void) { return 301; }
+int32_t hb_version(void) { return 302; }
 
 const char* hb_last_error(const hb_ctx* ctx) { return ctx ? ctx->err.c_str() : g_create_error.c_str(); }
 

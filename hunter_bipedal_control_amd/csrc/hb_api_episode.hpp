@@ -185,6 +185,7 @@ int32_t hb_plant_set_profile_draw(hb_ctx* ctx, const hb_profile_draw_config* cfg
   HB_FAIL_IF(cfg && !ctx->respawn_on, HB_ERR_STATE, "hb_plant_set_profile_draw: no respawn configuration in force (hb_plant_set_respawn): the profile is drawn at respawn");
   HB_FAIL_IF(cfg && ctx->scenario_on && (ctx->scenario_cfg.channels & (HB_SC_SLOPE | HB_SC_MU)), HB_ERR_STATE, "hb_plant_set_profile_draw: the scenario in force draws the terrain (hb_plant_set_scenario with HB_SC_SLOPE or HB_SC_MU): turn it off first");
   HB_TRY(refuse_config(ctx, "hb_plant_set_profile_draw", cfg ? profile_draw_config_refusal(*cfg) : nullptr));
+  HB_FAIL_IF(cfg && cfg->follow_map && ctx->gfield_on, HB_ERR_STATE, "hb_plant_set_profile_draw: follow_map while a field map is in force (hb_ground_set_field): the draw writes profile records, turn the field map off first");
   HB_FAIL_IF(cfg && cfg->follow_map && !ctx->ground_on, HB_ERR_STATE, "hb_plant_set_profile_draw: follow_map without a ground map in force (hb_ground_set_profile): set the zero map first");
   HB_FAIL_IF(cfg && !(std::fabs(ctx->contact_cfg.ground_z) <= PD_REACH), HB_ERR_STATE, "hb_plant_set_profile_draw: |ground_z| of the contact model above 1e3: the knots are drawn around ground_z");
   HB_ENTER_DEVICE();

@@ -41,9 +41,12 @@ int32_t hb_joint_command(hb_ctx* ctx, const hb_joint_gains* gains, double dt, do
   return HB_OK;
 }
 
-// Filter step of the instances of e (instances [i0, i0 + e.B) of the context); in its ground form while a ground map is in force.
+// Filter step of the instances of e (instances [i0, i0 + e.B) of the context); in its ground or field form while a map is in force.
 static void launch_estimator(const hb_ctx* ctx, const EstBatch& e, double dt, hipStream_t s, int i0 = 0) {
-  if (use_ground_forms(ctx->ground_on))
+  const GroundForm gf = use_ground_forms(ctx->ground_on, ctx->gfield_on);
+  if (gf == GroundForm::Field)
+    hipLaunchKernelGGL(k_estimator_gfield, dim3(e.B), dim3(64), 0, s, e, view(ctx->gfield, ctx->Nmax, i0, e.B), ctx->dmodel, ctx->est_cfg, dt);
+  else if (gf == GroundForm::Profile)
     hipLaunchKernelGGL(k_estimator_ground, dim3(e.B), dim3(64), 0, s, e, view(ctx->ground, ctx->Nmax, i0, e.B), ctx->dmodel, ctx->est_cfg, dt);
   else
     hipLaunchKernelGGL(k_estimator, dim3(e.B), dim3(64), 0, s, e, ctx->dmodel, ctx->est_cfg, dt);

@@ -1,7 +1,16 @@
-// Host side, part 10: the ground map of the controller (hb_ground_*; include/hunter_hip.h above hb_ground_set_profile).  The stored
-// record of an instance, validation included, is hb_ground.hpp ground_record; the kernels that read it are the ground forms of the
-// planner and the filter (launch_refgen, launch_estimator).
+// Host side, part 10: the ground map of the controller (hb_ground_*; include/hunter_hip.h above hb_ground_set_profile and
+// hb_ground_set_field).  The stored record of an instance, validation included, is hb_ground.hpp ground_record (profile map) or
+// ground_field_record (field map); the kernels that read it are the ground and field forms of the planner and the filter
+// (launch_refgen, launch_estimator).
 #pragma once
+
+// One map at a time: the profile map, the field map or none.  Every change of what a range enqueues (on, off, profile <-> field) bumps
+// graph_epoch, as hb_gait_reset does.
+static void ground_map_select(hb_ctx* ctx, bool profile, bool field) {
+  if (ctx->ground_on != profile || ctx->gfield_on != field) ++ctx->graph_epoch;
+  ctx->ground_on = profile;
+  ctx->gfield_on = field;
+}
 
 extern "C" {
 
@@ -26,15 +35,13 @@ int32_t hb_ground_set_profile(hb_ctx* ctx, const int32_t* n_knots, const double*
     ctx->ground_host = std::move(rec);
     ctx->ground_knots = std::move(kn);
   }
-  if (ctx->ground_on != on) {
-    ctx->ground_on = on;
-    ++ctx->graph_epoch;   // (as hb_gait_reset: what a range enqueues has changed)
-  }
+  ground_map_select(ctx, on, false);
   return HB_OK;
 }
 
 int32_t hb_ground_get_profile(hb_ctx* ctx, int32_t* n_knots, double* dir, double* knots, double* slopes) {
   HB_ENTER_ARGS(false);
+  HB_FAIL_IF(ctx->gfield_on, HB_ERR_STATE, "hb_ground_get_profile: the map in force is a field map (hb_ground_get_field)");
   HB_FAIL_IF(!ctx->ground_on, HB_ERR_STATE, "hb_ground_get_profile: no ground map in force (hb_ground_set_profile)");
   if (ctx->profile_draw_on && ctx->profile_draw_cfg.follow_map) {   // the device draws the records: the host image is stale
     HB_ENTER_DEVICE();
@@ -48,6 +55,54 @@ int32_t hb_ground_get_profile(hb_ctx* ctx, int32_t* n_knots, double* dir, double
     if (knots) std::memcpy(knots + i * HB_PROFILE_MAX_KNOTS * 2, ctx->ground_knots.data() + i * HB_PROFILE_MAX_KNOTS * 2, HB_PROFILE_MAX_KNOTS * 2 * sizeof(double));
     if (slopes) std::memcpy(slopes + i * (HB_PROFILE_MAX_KNOTS - 1), r + Ground::slope, (HB_PROFILE_MAX_KNOTS - 1) * sizeof(double));
   }
+  return HB_OK;
+}
+
+// The field map (include/hunter_hip.h above hb_ground_set_field): the stored header of an instance, validation included, is hb_ground.hpp
+// ground_field_record; the kernels that read it are the field forms of the planner and the filter.
+int32_t hb_ground_set_field(hb_ctx* ctx, const int32_t* n_nodes, const double* dir, const double* origin, const double* spacing, const double* heights) {
+  HB_ENTER_ARGS(false);
+  const bool on = n_nodes || dir || origin || spacing || heights;
+  HB_FAIL_IF(on && !(n_nodes && dir && origin && spacing && heights), HB_ERR_ARG, "hb_ground_set_field: give n_nodes, dir, origin, spacing and heights, or none of them to switch the map off (the map in force is kept)");
+  HB_FAIL_IF(on && ctx->profile_draw_on && ctx->profile_draw_cfg.follow_map, HB_ERR_STATE, "hb_ground_set_field: the profile draw in force writes the profile map (hb_plant_set_profile_draw, follow_map): turn it off first");
+  const size_t B = ctx->B;
+  std::vector<double> hdr(on ? B * GroundField::size : 0), z(on ? B * GroundField::nz : 0);
+  for (size_t i = 0; i < B && on; ++i) {
+    const int n[2] = {n_nodes[2 * i], n_nodes[2 * i + 1]};
+    const double* zi = heights + i * GroundField::nz;
+    double* zo = z.data() + i * GroundField::nz;
+    if (n[0] >= 2 && n[0] <= HB_FIELD_MAX_NODES && n[1] >= 2 && n[1] <= HB_FIELD_MAX_NODES)   // (the stored heights: zero beyond (nu, nw))
+      for (int iu = 0; iu < n[0]; ++iu)
+        for (int iw = 0; iw < n[1]; ++iw) zo[iu * GroundField::pitch + iw] = 0.0 + zi[iu * GroundField::pitch + iw];   // (0 + : no negative zero, as ground_compose)
+    if (const char* why = ground_field_record(n, dir + 2 * i, origin + 2 * i, spacing + 2 * i, zo, hdr.data() + i * GroundField::size))
+      return refuse_instance(ctx, HB_ERR_ARG, "hb_ground_set_field", i, why, "map");
+  }
+  HB_ENTER_DEVICE();
+  HB_TRY(hb_sync(ctx));   // (a pass in flight still runs on the map it was launched with)
+  if (on) {
+    GroundFieldBatch& g = ctx->gfield;
+    HB_TRY(ensure_fields(ctx, g));
+    HB_TRY(push(ctx, hdr.data(), g, g.hdr, whole(ctx)));
+    HB_TRY(push(ctx, z.data(), g, g.z, whole(ctx)));
+    ctx->gfield_hdr_host = std::move(hdr);
+    ctx->gfield_z_host = std::move(z);
+  }
+  ground_map_select(ctx, false, on);
+  return HB_OK;
+}
+
+int32_t hb_ground_get_field(hb_ctx* ctx, int32_t* n_nodes, double* dir, double* origin, double* spacing, double* heights) {
+  HB_ENTER_ARGS(false);
+  HB_FAIL_IF(!ctx->gfield_on, HB_ERR_STATE, ctx->ground_on ? "hb_ground_get_field: the map in force is a profile map (hb_ground_get_profile)"
+                                                            : "hb_ground_get_field: no field map in force (hb_ground_set_field)");
+  for (size_t i = 0; i < size_t(ctx->B); ++i) {
+    const double* h = ctx->gfield_hdr_host.data() + i * GroundField::size;
+    if (n_nodes) { n_nodes[2 * i] = int32_t(h[GroundField::nu]); n_nodes[2 * i + 1] = int32_t(h[GroundField::nw]); }
+    if (dir) std::memcpy(dir + 2 * i, h + GroundField::dir, 2 * sizeof(double));
+    if (origin) std::memcpy(origin + 2 * i, h + GroundField::org, 2 * sizeof(double));
+    if (spacing) std::memcpy(spacing + 2 * i, h + GroundField::step, 2 * sizeof(double));
+  }
+  if (heights) std::memcpy(heights, ctx->gfield_z_host.data(), ctx->gfield_z_host.size() * sizeof(double));
   return HB_OK;
 }
 

@@ -47,7 +47,11 @@ static void launch_refgen(const hb_ctx* ctx, const Batch& b, RefgenBatch r, int 
     hipLaunchKernelGGL(k_gait, dim3((b.B + 63) / 64), dim3(64), 0, s, b, r, g, ctx->gait_cfg, horizon);
     r.cmd = g.cmd;
   }
-  if (use_ground_forms(ctx->ground_on))   // the planner on the ground map of these instances (hb_ground_set_profile)
+  const GroundForm gf = use_ground_forms(ctx->ground_on, ctx->gfield_on);
+  if (gf == GroundForm::Field)   // the planner on the field map of these instances (hb_ground_set_field)
+    hipLaunchKernelGGL(k_refgen_gfield, dim3((4 * b.B + 63) / 64), dim3(64), 0, s, b, r, view(ctx->gfield, ctx->Nmax, i0, b.B), ctx->dmodel, ctx->rg_cfg,
+                       horizon, init_flag);
+  else if (gf == GroundForm::Profile)   // the planner on the ground map of these instances (hb_ground_set_profile)
     hipLaunchKernelGGL(k_refgen_ground, dim3((4 * b.B + 63) / 64), dim3(64), 0, s, b, r, view(ctx->ground, ctx->Nmax, i0, b.B), ctx->dmodel, ctx->rg_cfg,
                        horizon, init_flag);
   else

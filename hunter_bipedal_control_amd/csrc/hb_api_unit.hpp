@@ -76,7 +76,7 @@ int32_t hb_ik_solve(hb_ctx* ctx, int32_t n, const double* q16, const int32_t* le
 
 int32_t hb_ground_eval(hb_ctx* ctx, int32_t n, const int32_t* inst, const double* xy, double* height, int32_t* segment) {
   HB_ENTER_ARGS(n <= 0 || !inst || !xy || !(height || segment));
-  HB_FAIL_IF(!ctx->ground_on, HB_ERR_STATE, "hb_ground_eval: no ground map in force (hb_ground_set_profile)");
+  HB_FAIL_IF(!ctx->ground_on && !ctx->gfield_on, HB_ERR_STATE, "hb_ground_eval: no ground map in force (hb_ground_set_profile)");
   for (int p = 0; p < n; ++p) HB_FAIL_IF(inst[p] < 0 || inst[p] >= ctx->B, HB_ERR_ARG, "hb_ground_eval: instance index outside the batch");
   HB_ENTER_DEVICE();
   const size_t m = n;
@@ -86,7 +86,10 @@ int32_t hb_ground_eval(hb_ctx* ctx, int32_t n, const int32_t* inst, const double
   HB_HIP(di.alloc(m, inst));
   HB_HIP(dh.alloc(m));
   HB_HIP(ds.alloc(m));
-  hipLaunchKernelGGL(k_ground_eval, dim3((n + 63) / 64), dim3(64), 0, ctx->s_mpc, n, ctx->ground, di.p, dxy.p, dh.p, ds.p);
+  if (use_ground_forms(ctx->ground_on, ctx->gfield_on) == GroundForm::Field)   // (segment: the facet id)
+    hipLaunchKernelGGL(k_ground_field_eval, dim3((n + 63) / 64), dim3(64), 0, ctx->s_mpc, n, ctx->gfield, di.p, dxy.p, dh.p, ds.p);
+  else
+    hipLaunchKernelGGL(k_ground_eval, dim3((n + 63) / 64), dim3(64), 0, ctx->s_mpc, n, ctx->ground, di.p, dxy.p, dh.p, ds.p);
   HB_HIP(hipGetLastError());
   HB_HIP(hipStreamSynchronize(ctx->s_mpc));
   if (height) HB_HIP(hipMemcpy(height, dh.p, m * 8, hipMemcpyDeviceToHost));

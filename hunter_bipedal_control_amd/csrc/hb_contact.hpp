@@ -335,6 +335,39 @@ struct Field {
                        nz = HB_FIELD_MAX_NODES * HB_FIELD_MAX_NODES;
 };
 static_assert(Field::stored <= Field::act, "the stored part of a field record ends ahead of the working part");
+// The cell and triangle under the world point x[0], x[1] of a grid whose header is h[8] = direction a | origin (u0, w0) | spacing (du, dw) | nu,
+// nw as doubles (the eight doubles at Field::dir of a field record; the controller's field map, hb_ground.hpp, stores the same eight):
+// u, w along a and b = (-a_y, a_x) from the origin, the cell (i, j) = clamp(floor(u / du), 0, nu - 2), the same for w, the fractions fu, fw
+// within it (beyond the grid: below 0 or above 1, the border cell's planes continue) and t = 0 (fu >= fw: the lower triangle) or 1.
+// ONE routine for the plant's facet and the map's height: they cannot cut a cell differently.
+struct FieldCell {
+  double ax, ay, bx, by, u0, w0, du, dw, u, w, fu, fw;
+  int nw, i, j, t;
+  const double* cell;   // heights of the cell: cell[0], cell[1], cell[pitch], cell[pitch + 1] = z00, z01, z10, z11
+};
+HB_HD FieldCell field_cell(const double* h, const double* __restrict__ z, const double* x) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  FieldCell c;
+  c.ax = h[0]; c.ay = h[1]; c.bx = -c.ay; c.by = c.ax;
+  c.u0 = h[2]; c.w0 = h[3]; c.du = h[4]; c.dw = h[5];
+  const int nu = int(h[6]);
+  c.nw = int(h[7]);
+  c.u = (c.ax * x[0] + c.ay * x[1]) - c.u0;
+  c.w = (c.bx * x[0] + c.by * x[1]) - c.w0;
+  const double su = c.u / c.du, sw = c.w / c.dw;
+  // clamp(floor(s), 0, n - 2); a NaN fails every comparison and lands in cell 0
+  c.i = su >= 1.0 ? (su < double(nu - 2) ? int(su) : nu - 2) : 0;
+  c.j = sw >= 1.0 ? (sw < double(c.nw - 2) ? int(sw) : c.nw - 2) : 0;
+  c.fu = su - double(c.i);
+  c.fw = sw - double(c.j);
+  c.t = c.fu < c.fw ? 1 : 0;   // (fu >= fw: the lower triangle)
+  c.cell = z + c.i * HB_FIELD_MAX_NODES + c.j;
+  return c;
+}
+static_assert(Field::org == Field::dir + 2 && Field::step == Field::dir + 4 && Field::nu == Field::dir + 6 && Field::nw == Field::dir + 7,
+              "field_cell reads the header of a field record as eight consecutive doubles");
 // The facet under the world point x[3] of the field (hdr: its record, z: its heights): the id 2 (i (nw - 1) + j) + t, and in
 // rec[Profile::rec] the record (T, d) of its plane, which comes from terrain_plane_record as a profile segment's does.  Every operation is
 // rounded on its own: host, host emulation and device return the same bits.  A NaN coordinate gives facet 0 and a NaN record.
@@ -342,17 +375,10 @@ HB_HD int field_facet(const double* hdr, const double* __restrict__ z, const dou
 #if defined(__clang__)
 #pragma clang fp contract(off)
 #endif
-  const double ax = hdr[Field::dir], ay = hdr[Field::dir + 1], bx = -ay, by = ax;
-  const double u0 = hdr[Field::org], w0 = hdr[Field::org + 1], du = hdr[Field::step], dw = hdr[Field::step + 1];
-  const int nu = int(hdr[Field::nu]), nw = int(hdr[Field::nw]);
-  const double u = (ax * x[0] + ay * x[1]) - u0, w = (bx * x[0] + by * x[1]) - w0;
-  const double su = u / du, sw = w / dw;
-  // clamp(floor(s), 0, n - 2); a NaN fails every comparison and lands in cell 0
-  const int i = su >= 1.0 ? (su < double(nu - 2) ? int(su) : nu - 2) : 0;
-  const int j = sw >= 1.0 ? (sw < double(nw - 2) ? int(sw) : nw - 2) : 0;
-  const double fu = su - double(i), fw = sw - double(j);
-  const int t = fu < fw ? 1 : 0;   // (fu >= fw: the lower triangle)
-  const double* c = z + i * Field::pitch + j;
+  const FieldCell fc = field_cell(hdr + Field::dir, z, x);
+  const double ax = fc.ax, ay = fc.ay, bx = fc.bx, by = fc.by, u0 = fc.u0, w0 = fc.w0, du = fc.du, dw = fc.dw, u = fc.u, w = fc.w;
+  const int nw = fc.nw, i = fc.i, j = fc.j, t = fc.t;
+  const double* c = fc.cell;
   const double z00 = c[0], z01 = c[1], z10 = c[Field::pitch], z11 = c[Field::pitch + 1];
   const double p = (t ? z11 - z01 : z10 - z00) / du;
   const double r = (t ? z01 - z00 : z11 - z10) / dw;

@@ -91,9 +91,11 @@ struct EstIn {
 
 // GROUND: the ground form — the four foot-height measurements are the map `gnd` of the instance (hb_ground.hpp) under the PREDICTED foot
 // positions, feetHeights_ of the reference's filter (LinearKalmanFilter.cpp:143,227), in place of 0.  No Jacobian term for it.
-template <bool GROUND = false, class Ctx>
+// GROUND 2: the same on the field map (hb_ground_set_field): gnd its header, gz its heights.  estimator_update<true> is GROUND 1.
+template <int GROUND = 0, class Ctx>
 HB_HD void estimator_update(const Ctx& cx, const DevModel& M, const hb_estimator_config& K, double dt, const EstIn& in, double* xhat,
-                            double* Pst, double* yaw_last, double* lds, double* rbd_out, double* x_out, const double* gnd = nullptr) {
+                            double* Pst, double* yaw_last, double* lds, double* rbd_out, double* x_out, const double* gnd = nullptr,
+                            const double* gz = nullptr) {
   double* xh = lds + EstLds::xh;
   double* ey = lds + EstLds::ey;
   double* qd = lds + EstLds::qd;
@@ -192,7 +194,7 @@ HB_HD void estimator_update(const Ctx& cx, const DevModel& M, const hb_estimator
     double yv = 0.0;
     if (i < 12) yv = -feet[i] + ((i - 3 * (i / 3)) == 2 ? K.foot_radius : 0.0);
     else if (i < 24) yv = -feet[i];
-    else if constexpr (GROUND) yv = ground_height(gnd, xh[6 + 3 * (i - 24)], xh[7 + 3 * (i - 24)]);
+    else if constexpr (GROUND != 0) yv = map_height<GROUND>(gnd, gz, xh[6 + 3 * (i - 24)], xh[7 + 3 * (i - 24)]);
     ey[i] = yv - (xh[plus] - (minus >= 0 ? xh[minus] : 0.0));
   }
   // CP = C Pm

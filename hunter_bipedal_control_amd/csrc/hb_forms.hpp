@@ -140,9 +140,14 @@ inline bool use_ric_fwd_wave(const KernelForms& f, int concurrent) {
   return f.fwd == KernelForms::Fwd::Wave || (f.fwd == KernelForms::Fwd::Auto && concurrent <= kRicFwdWaveMaxBatch);
 }
 
-// Planner and filter: the ground forms (k_refgen_ground, k_estimator_ground) while a ground map is in force (hb_ground_set_profile), the
-// base forms otherwise — the base forms never see the map, so a context without one runs what it always ran.
-inline bool use_ground_forms(bool map_in_force) { return map_in_force; }
+// Planner and filter: the ground forms (k_refgen_ground, k_estimator_ground) while a profile map is in force (hb_ground_set_profile), the
+// field forms (k_refgen_gfield, k_estimator_gfield) while a field map is (hb_ground_set_field), the base forms otherwise — the base forms
+// never see a map, so a context without one runs what it always ran.  One map at a time: the host never has both in force, and a field
+// would go first.
+enum class GroundForm { None, Profile, Field };
+inline GroundForm use_ground_forms(bool map_in_force, bool field_map_in_force = false) {
+  return field_map_in_force ? GroundForm::Field : map_in_force ? GroundForm::Profile : GroundForm::None;
+}
 
 // Plant step: which of the twenty-two step kernels a launch takes (hb_api_plant.hpp plant_launch names them).  Contact mode 0 is the pinned
 // stub (k_plant / k_plant_hybrid), which knows neither joints nor ground; in contact model 1 a height field or a profile (one ground at a

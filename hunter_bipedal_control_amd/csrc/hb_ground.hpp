@@ -1,4 +1,4 @@
-// Ground map of the controller (hb_ground_set_profile): per instance a piecewise-linear height over one horizontal direction, what the
+// Ground map of the controller (hb_ground_set_profile; its two-dimensional form, hb_ground_set_field, is the second half of this file): per instance a piecewise-linear height over one horizontal direction, what the
 // swing planner, the command target and the filter's foot-height rows take for the ground in place of the level plane.  The map has the
 // shape of the plant's terrain profile (hb_contact.hpp Profile: direction, knots, open-ended end segments) without its friction, and its
 // heights are RELATIVE to the level ground the controller has always assumed: g = 0 everywhere is the world of the base forms.
@@ -56,6 +56,47 @@ HB_HD double ground_height(const double* g, double x, double y, int* seg = nullp
   for (int k = 1; k < nseg; ++k) j = s >= g[Ground::brk + k] ? k : j;
   if (seg) *seg = j;
   return g[Ground::hgt + j] + g[Ground::slope + j] * (s - g[Ground::brk + j]);
+}
+
+// ---- the field map (hb_ground_set_field): the grid of a plant height field (hb_contact.hpp Field) without its friction ----------------
+// The header of an instance (doubles): direction a (unit) | origin (u0, w0) | spacing (du, dw) | nu, nw as doubles — the eight doubles
+// field_cell reads; the heights g[iu * pitch + iw] stay in global memory, relative to the level ground like a profile map's.
+struct GroundField {
+  static constexpr int dir = 0, org = 2, step = 4, nu = 6, nw = 7, size = 8, pitch = Field::pitch, nz = Field::nz;
+};
+// Host: the header h[GroundField::size] of one instance from its map, or the reason it is refused (h is then not written).  The checks
+// are field_record's, the triangle bound included (the routine is run on the map, so a plant field is always a valid map); the direction
+// is normalised by the same division.
+inline const char* ground_field_record(const int* n, const double* dir, const double* org, const double* step, const double* z, double* h) {
+  double fld[Field::stored];
+  if (const char* why = field_record(n, dir, org, step, z, nullptr, 0.0, fld)) return why;
+  for (int k = 0; k < GroundField::size; ++k) h[k] = fld[Field::dir + k];
+  return nullptr;
+}
+// G(x, y) of the field map (h: its header, z: its heights): the cell (i, j), the fractions and the triangle are field_cell's, the ones
+// the plant's field_facet cuts its cells by; over the lower triangle (t = 0) G = g00 + (g10 - g00) fu + (g11 - g10) fw, over the upper
+// G = g00 + (g01 - g00) fw + (g11 - g01) fu, left to right, every operation rounded on its own: a level cell returns g00 bit for bit.
+// The four loads are issued together.  A NaN coordinate selects facet 0 and returns NaN.  *facet (or null): 2 (i (nw - 1) + j) + t.
+HB_HD double ground_field_height(const double* h, const double* __restrict__ z, double x, double y, int* facet = nullptr) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  const double xy[2] = {x, y};
+  const FieldCell fc = field_cell(h, z, xy);
+  const double* c = fc.cell;
+  const double g00 = c[0], g01 = c[1], g10 = c[GroundField::pitch], g11 = c[GroundField::pitch + 1];
+  if (facet) *facet = 2 * (fc.i * (fc.nw - 1) + fc.j) + fc.t;
+  const double e1 = fc.t ? g01 - g00 : g10 - g00, e2 = fc.t ? g11 - g01 : g11 - g10;
+  const double f1 = fc.t ? fc.fw : fc.fu, f2 = fc.t ? fc.fu : fc.fw;
+  return g00 + e1 * f1 + e2 * f2;
+}
+
+// What the planner, the command target and the filter put their points to.  MAP: 0 no map, 1 the profile map (gnd: its Ground record),
+// 2 the field map (gnd: its header, gz: its heights).
+template <int MAP>
+HB_HD double map_height(const double* gnd, const double* gz, double x, double y) {
+  if constexpr (MAP == 2) return ground_field_height(gnd, gz, x, y);
+  else return ground_height(gnd, x, y);
 }
 
 }  // namespace hb

@@ -1717,6 +1717,42 @@ __global__ __launch_bounds__(64) void k_refgen_ground(Batch b, RefgenBatch r, Gr
   any |= __shfl_xor(any, 2, 64);
   if (foot == 0) r.status[i] = st == 2 ? 2 : any;
 }
+// the field form of k_refgen (hb_ground_set_field; launched only while a field map is in force): the same step with refgen_plan<2> on the
+// field map of the instance, g = the maps of the instances of b (hb_layout.hpp GroundFieldBatch).  The header's eight doubles are read
+// once into registers (field_cell indexes them statically); the heights stay in global memory — 8 KB per instance, sixteen instances per
+// wavefront: staged they would leave a CU one workgroup — and an evaluation issues its four loads together.  k_refgen and
+// k_refgen_ground are left as they were.
+__global__ __launch_bounds__(64) void k_refgen_gfield(Batch b, RefgenBatch r, GroundFieldBatch g, const DevModel* __restrict__ M, hb_refgen_config K,
+                                                      double horizon, const int* __restrict__ init_flag) {
+  const int gid = blockIdx.x * blockDim.x + threadIdx.x;
+  const int i = gid >> 2, foot = gid & 3;
+  if (i >= b.B) return;   // (a whole group of four leaves together)
+  const double* x_now = b.x0 + size_t(i) * HB_NX;
+  double* stance = r.stance + size_t(i) * 12;
+  if (r.init_stance || (init_flag && init_flag[i])) {
+    const Mat3<double> R0 = rg_rot_zyx(x_now + 9);
+    const Vec3<double> p0(x_now[6], x_now[7], x_now[8]);
+    const double* qj = x_now + 12;
+    LegOut<double> L;
+    leg_eval<double>(*M, foot & 1, [qj](int j) { return qj[j]; }, [](int) { return 0.0; }, L);
+    st3(stance + 3 * foot, p0 + R0 * ((foot >> 1) ? L.foot[1] : L.foot[0]));
+  }
+  double hdr[GroundField::size];
+  const double* __restrict__ gh = g.hdr + size_t(i) * GroundField::size;
+#pragma unroll
+  for (int k = 0; k < GroundField::size; ++k) hdr[k] = gh[k];
+  const double* __restrict__ gz = g.z + size_t(i) * GroundField::nz;
+  const size_t N = b.Nmax;
+  const int st = refgen_plan<2>(*M, K, r.n_ev[i], r.ev + size_t(i) * HB_MAX_EVENTS, r.modes + size_t(i) * (HB_MAX_EVENTS + 1), r.t0[i], horizon,
+                                x_now, r.cmd + size_t(i) * 4, stance, r.phases + size_t(i) * 4 * (HB_MAX_EVENTS + 1) * RG_PHASE, b.Nmax,
+                                b.n_nodes + i, b.t + size_t(i) * (N + 1), r.n_knots + i, r.knot_t + size_t(i) * RG_MAX_KNOTS,
+                                r.knot_x + size_t(i) * RG_MAX_KNOTS * HB_NX, foot, 4, hdr, gz);
+  // status of the instance: 2 (grid too long, from the lane of foot 0) wins, else 1 if any foot reported a phase without its events
+  int any = st == 1 ? 1 : 0;
+  any |= __shfl_xor(any, 1, 64);
+  any |= __shfl_xor(any, 2, 64);
+  if (foot == 0) r.status[i] = st == 2 ? 2 : any;
+}
 // joint-reference IK: eight lanes per (instance, leg), eight pairs per wavefront (hb_refgen.hpp refgen_ik_group)
 __global__ __launch_bounds__(64) void k_refgen_ik(Batch b, RefgenBatch r, const DevModel* __restrict__ M, hb_refgen_config K, double horizon) {
 #if defined(__HIP_DEVICE_COMPILE__)  // (the routine is built from cross-lane instructions: device pass only)
@@ -1804,6 +1840,21 @@ __global__ __launch_bounds__(64) void k_estimator_ground(EstBatch e, GroundBatch
     for (int c = cx.lane; c < HB_NX; c += 64) e.res_x0[HB_NX * i + c] = e.x[HB_NX * i + c];
   }
 }
+// the field form of k_estimator (hb_ground_set_field): the same step with estimator_update<2> on the field map of the instance — four
+// evaluations a tick, the header read through the pointer (uniform over the wave), the heights from global memory
+__global__ __launch_bounds__(64) void k_estimator_gfield(EstBatch e, GroundFieldBatch g, const DevModel* __restrict__ M, hb_estimator_config K, double dt) {
+  const int i = blockIdx.x;
+  __shared__ double lds[EstLds::total];
+  const DeviceCtx cx;
+  const EstIn in{e.quat + 4 * i, e.w_local + 3 * i, e.a_local + 3 * i, e.qj + 10 * i, e.qdj + 10 * i, e.contact + 4 * i};
+  estimator_update<2>(cx, *M, K, dt, in, e.xhat + 18 * i, e.P + 324 * size_t(i), e.yaw_last + i, lds, e.rbd + HB_NRBD * i, e.x + HB_NX * i,
+                      g.hdr + size_t(i) * GroundField::size, g.z + size_t(i) * GroundField::nz);
+  if (e.res_rbd) {
+    __syncthreads();  // lane 0 wrote the outputs
+    for (int c = cx.lane; c < HB_NRBD; c += 64) e.res_rbd[HB_NRBD * i + c] = e.rbd[HB_NRBD * i + c];
+    for (int c = cx.lane; c < HB_NX; c += 64) e.res_x0[HB_NX * i + c] = e.x[HB_NX * i + c];
+  }
+}
 // test hook (hb_ground_eval): the height function at n points, one thread each; inst[p] is the instance whose map point p is put to
 __global__ __launch_bounds__(64) void k_ground_eval(int n, GroundBatch g, const int* __restrict__ inst, const double* __restrict__ xy,
                                                     double* __restrict__ height, int* __restrict__ segment) {
@@ -1812,6 +1863,15 @@ __global__ __launch_bounds__(64) void k_ground_eval(int n, GroundBatch g, const 
   int seg = 0;
   height[p] = ground_height(g.map + size_t(inst[p]) * Ground::size, xy[2 * p], xy[2 * p + 1], &seg);
   segment[p] = seg;
+}
+// the same under a field map (hb_ground_set_field): segment[p] is the facet id
+__global__ __launch_bounds__(64) void k_ground_field_eval(int n, GroundFieldBatch g, const int* __restrict__ inst, const double* __restrict__ xy,
+                                                          double* __restrict__ height, int* __restrict__ segment) {
+  const int p = blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= n) return;
+  int facet = 0;
+  height[p] = ground_field_height(g.hdr + size_t(inst[p]) * GroundField::size, g.z + size_t(inst[p]) * GroundField::nz, xy[2 * p], xy[2 * p + 1], &facet);
+  segment[p] = facet;
 }
 // StateEstimateBase::estContactForce for every instance, one thread each (hb_estimator.hpp contact_force_estimate); the per-leg forward
 // data sits in LDS (the joint loops index it dynamically).  Not on the timed path of the update: 4096 instances take ~ 0.1 ms.

@@ -350,6 +350,19 @@ constexpr void fields(GroundBatch& g, size_t, F&& f) {
   HB_FIELD(g.map, Ground::size);
 }
 
+// field map of the controller (hb_ground_set_field, hb_ground.hpp GroundField), allocated by the first call that gives one: hdr: the eight
+// doubles of an instance's header (direction | origin | spacing | node counts), which the field forms of k_refgen and k_estimator keep in
+// registers / LDS; z: the heights, [HB_FIELD_MAX_NODES][HB_FIELD_MAX_NODES] per instance, read from global memory
+struct GroundFieldBatch {
+  int B;
+  double* hdr;
+  double* z;
+};
+template <class F>
+constexpr void fields(GroundFieldBatch& g, size_t, F&& f) {
+  HB_FIELD(g.hdr, GroundField::size); HB_FIELD(g.z, GroundField::nz);
+}
+
 // GaitBatch (hb_gait.hpp): the schedule, the template, the rate limiter and the velocity history are slot-major
 template <class F>
 constexpr void fields(GaitBatch& g, size_t, F&& f) {
@@ -428,6 +441,7 @@ static_assert(sizeof(ProfileDrawBatch) == 2 * sizeof(int) + (n_fields<ProfileDra
 static_assert(sizeof(ActuatorBatch) == kPtr /*B*/ + n_fields<ActuatorBatch>() * kPtr, "describe every array of ActuatorBatch in fields()");
 static_assert(sizeof(RefgenBatch) == kPtr /*B*/ + n_fields<RefgenBatch>() * kPtr + kPtr /*init_stance*/, "describe every array of RefgenBatch in fields()");
 static_assert(sizeof(GroundBatch) == kPtr /*B*/ + n_fields<GroundBatch>() * kPtr, "describe every array of GroundBatch in fields()");
+static_assert(sizeof(GroundFieldBatch) == kPtr /*B*/ + n_fields<GroundFieldBatch>() * kPtr, "describe every array of GroundFieldBatch in fields()");
 static_assert(sizeof(GaitBatch) == 2 * sizeof(int) + n_fields<GaitBatch>() * kPtr, "describe every array of GaitBatch in fields()");
 static_assert(sizeof(EstBatch) == kPtr /*B*/ + (n_fields<EstBatch>() + 2 /*res_rbd, res_x0*/) * kPtr, "describe every array of EstBatch in fields()");
 static_assert(sizeof(TickUpload) == n_fields<TickUpload>() * kPtr, "describe every array of TickUpload in fields()");

@@ -114,9 +114,10 @@ struct RgTarget {
 // (TIME_TO_TARGET = mpc.timeHorizon) at comHeight.
 // GROUND (the ground form, hb_ground.hpp): both knots stand comHeight above the map `gnd` of the instance under their own x, y.
 constexpr double RG_CMD_DEAD_BAND = 0.06, RG_HEIGHT_CHANGE_LIMIT = 0.04;
-template <bool GROUND = false>
+// GROUND 2: the field form — gnd the header, gz the heights of the instance's field map (hb_ground.hpp map_height).
+template <int GROUND = 0>
 HB_HD void rg_make_target(const RefgenConfig& K, double t0, double horizon, const double* x_now, const double* cmd_vel, double* cur,
-                          double* tgt, RgTarget& T, const double* gnd = nullptr) {
+                          double* tgt, RgTarget& T, const double* gnd = nullptr, const double* gz = nullptr) {
   const Mat3<double> Rn = rg_rot_zyx(x_now + 9);
   Vec3<double> vw = Rn * Vec3<double>(cmd_vel[0], cmd_vel[1], cmd_vel[2]);
   if (fabs(vw.x) < RG_CMD_DEAD_BAND) vw.x = 0.0;
@@ -129,14 +130,14 @@ HB_HD void rg_make_target(const RefgenConfig& K, double t0, double horizon, cons
   cur[0] = vw.x; cur[1] = vw.y; cur[2] = vw.z;
   tgt[0] = vw.x; tgt[1] = vw.y; tgt[2] = vw.z;
   double dz = K.com_height - x_now[8];
-  if constexpr (GROUND) dz = K.com_height + ground_height(gnd, x_now[6], x_now[7]) - x_now[8];
+  if constexpr (GROUND != 0) dz = K.com_height + map_height<GROUND>(gnd, gz, x_now[6], x_now[7]) - x_now[8];
   dz = dz > 0.0 ? fmin(dz, RG_HEIGHT_CHANGE_LIMIT) : fmax(dz, -RG_HEIGHT_CHANGE_LIMIT);
   cur[6] = x_now[6]; cur[7] = x_now[7]; cur[8] = x_now[8] + dz;
   cur[9] = x_now[9];
   tgt[6] = x_now[6] + vw.x * horizon;
   tgt[7] = x_now[7] + vw.y * horizon;
   tgt[8] = K.com_height;
-  if constexpr (GROUND) tgt[8] = K.com_height + ground_height(gnd, tgt[6], tgt[7]);
+  if constexpr (GROUND != 0) tgt[8] = K.com_height + map_height<GROUND>(gnd, gz, tgt[6], tgt[7]);
   tgt[9] = x_now[9] + cmd_vel[3] * horizon;
   for (int j = 0; j < HB_NJ; ++j) { cur[12 + j] = K.default_joints[j]; tgt[12 + j] = K.default_joints[j]; }
 }
@@ -682,15 +683,16 @@ __device__ __forceinline__ void refgen_ik_group(const DevModel& M, const RefgenC
 // GROUND: the ground form — with the map `gnd` of the instance (hb_ground.hpp; read through the pointer, from global memory or LDS: a
 // thread-private copy would be indexed dynamically) the latest stance position and every foothold stand next_position_z above the map under their own x, y, the centrifugal
 // term takes the height of the body above the map, and the target knots follow it (rg_make_target).  Nothing else differs.
-template <bool GROUND = false>
+// GROUND 2: the same on the field map (hb_ground_set_field): gnd its header, gz its heights (global memory).  refgen_plan<true> is GROUND 1.
+template <int GROUND = 0>
 HB_HD int refgen_plan(const DevModel& M, const RefgenConfig& K, int n_ev, const double* ev, const int* modes, double t0, double horizon,
                       const double* x_now, const double* cmd_vel, double* latest_stance, double* phases, int max_nodes,
                       int* n_nodes_out, double* t_out, int* n_knots_out, double* knot_t, double* knot_x, int foot0 = 0, int foot_step = 1,
-                      const double* gnd = nullptr) {
+                      const double* gnd = nullptr, const double* gz = nullptr) {
   const int n_ph = n_ev + 1;
   RgTarget T;
   rg_make_target<GROUND>(K, t0, horizon, x_now, cmd_vel, knot_x + size_t(RG_MAX_KNOTS - 2) * HB_NX, knot_x + size_t(RG_MAX_KNOTS - 1) * HB_NX, T,
-                         gnd);
+                         gnd, gz);
   const double tf_h = T.tf;
   // ---- current feet (InverseKinematics::computeFootPos) ------------------------------------------------------------
   // A foot that is in contact now refreshes its latest stance position (SwingTrajectoryPlanner::update).  (Written here, leg by leg:
@@ -728,7 +730,7 @@ HB_HD int refgen_plan(const DevModel& M, const RefgenConfig& K, int n_ev, const 
   for (int j = foot0; j < HB_NC; j += foot_step) {
     double* ls = latest_stance + 3 * j;
     ls[2] = K.next_position_z;
-    if constexpr (GROUND) ls[2] = ground_height(gnd, ls[0], ls[1]) + K.next_position_z;
+    if constexpr (GROUND != 0) ls[2] = map_height<GROUND>(gnd, gz, ls[0], ls[1]) + K.next_position_z;
     double last[3] = {ls[0], ls[1], ls[2]}, nxt[3] = {ls[0], ls[1], ls[2]};
     int last_final = 0;
     double* phj = phases + size_t(j) * (RG_MAX_EVENTS + 1) * RG_PHASE;
@@ -767,11 +769,11 @@ HB_HD int refgen_plan(const DevModel& M, const RefgenConfig& K, int n_ev, const 
           const Vec3<double> p_sh = (tf - t0) * (0.5 * v + 0.5 * cl) + bias;
           const Vec3<double> p_sym = (t_mid - tf) * v + 0.03 * (v - cl);
           double above = body.z;   // height of the body above the ground under it
-          if constexpr (GROUND) above = body.z - ground_height(gnd, body.x, body.y);
+          if constexpr (GROUND != 0) above = body.z - map_height<GROUND>(gnd, gz, body.x, body.y);
           const Vec3<double> p_cent = (0.5 * sqrt(above / 9.81)) * cross(v, ca);
           const Vec3<double> pn = body + p_sh + p_sym + p_cent;
           nxt[0] = pn.x; nxt[1] = pn.y; nxt[2] = K.next_position_z;
-          if constexpr (GROUND) nxt[2] = ground_height(gnd, pn.x, pn.y) + K.next_position_z;
+          if constexpr (GROUND != 0) nxt[2] = map_height<GROUND>(gnd, gz, pn.x, pn.y) + K.next_position_z;
           last_final = f_idx;
         }
         ph[0] = ts; ph[1] = tf;

@@ -274,8 +274,12 @@ class ResidentLoop:
         planner assume level ground unless ground_map tells them otherwise.  Or dict(field=dict(dir=[B][2], origin=[B][2], spacing=[B][2],
         heights=[B] arrays [nu_i][nw_i] (rough_field, field_from_profile) or [B][nu][nw], mu=[B][4] or missing) or a list of B such dicts of
         one instance each, relative=True): a triangulated height field per instance (hb_plant_set_terrain_field), `relative` as for the
-        profile.  ground_map="plant" is refused beside a field (the controller's map is one-dimensional), and so is respawn=.
-        ground_map: the ground the controller's side plans and filters on (hb_ground_set_profile) — None: the level plane; "plant": the
+        profile.  ground_map="plant" is refused beside a field (the profile map is one-dimensional: ground_map="field" hands the field over),
+        and so is respawn=.
+        ground_map: the ground the controller's side plans and filters on (hb_ground_set_profile, hb_ground_set_field) — None: the level
+        plane; "field": the plant field's heights above the level ground of the start, as a field map (needs terrain=dict(field=...));
+        dict(field=dict(dir=, origin=, spacing=, heights=), per instance as terrain's field): a field map of the caller's, beside any plant
+        ground; "plant": the
         plant's terrain profile with the start offset taken out (the knots of terrain["profile"] as given when relative, less the height of
         the lowest contact point of the start otherwise), so a level relative profile is the zero map; dict(dir=[B][2], knots=[B] knot
         arrays [K_i][2] or [B][K][2]): a map of the caller's, heights relative to the level ground the controller assumes — independent of
@@ -364,8 +368,9 @@ class ResidentLoop:
                 fld = terrain["field"]
                 flds = fld if isinstance(fld, (list, tuple)) else [{k: v[i] for k, v in fld.items() if v is not None} for i in range(self.B)]
                 d, org, sp, hts, fmu = pack_fields(flds)
+                z0 = plane_under_contact_points(solver, q0, [0.0, 0.0, 1.0])
+                plant_field = dict(dir=d, origin=org, spacing=sp, heights=hts if terrain.get("relative", True) else [h - z0[i] for i, h in enumerate(hts)])
                 if terrain.get("relative", True):
-                    z0 = plane_under_contact_points(solver, q0, [0.0, 0.0, 1.0])
                     hts = [h + z0[i] for i, h in enumerate(hts)]
                 solver.plant_set_terrain_field(d, org, sp, hts, fmu)
             elif terrain is not None and terrain.get("profile") is not None:
@@ -391,10 +396,19 @@ class ResidentLoop:
                 solver.plant_set_terrain(plane, terrain.get("mu"))
         if isinstance(ground_map, str) and ground_map == "draw":
             pass   # (the zero map goes in with the draw, below)
+        elif isinstance(ground_map, str) and ground_map == "field":   # the plant field's heights above the level ground of the start
+            if terrain is None or terrain.get("field") is None or contact_config is None:
+                raise ValueError('ground_map="field" hands the plant\'s height field to the controller: give terrain=dict(field=...) as well')
+            solver.ground_set_field(plant_field["dir"], plant_field["origin"], plant_field["spacing"], plant_field["heights"])
         elif isinstance(ground_map, str):
             if ground_map != "plant" or terrain is None or terrain.get("profile") is None:
-                raise ValueError('ground_map is None, "plant" (with terrain=dict(profile=...)), "draw" (with profile_draw=) or dict(dir=..., knots=...)')
+                raise ValueError('ground_map is None, "plant" (with terrain=dict(profile=...)), "field" (with terrain=dict(field=...)), "draw" (with profile_draw=), dict(dir=..., knots=...) or dict(field=dict(dir=, origin=, spacing=, heights=))')
             solver.ground_set_profile(plant_map["n_knots"], plant_map["dir"], plant_map["knots"])
+        elif ground_map is not None and ground_map.get("field") is not None:   # a field map of the caller's
+            fld = ground_map["field"]
+            flds = fld if isinstance(fld, (list, tuple)) else [{k: v[i] for k, v in fld.items() if v is not None} for i in range(self.B)]
+            d, org, sp, hts, _ = pack_fields(flds)
+            solver.ground_set_field(d, org, sp, hts)
         elif ground_map is not None:
             n_knots, knots = pack_profiles([np.asarray(k, dtype=float) for k in ground_map["knots"]])
             solver.ground_set_profile(n_knots, np.asarray(ground_map["dir"], dtype=float).reshape(self.B, 2), knots)

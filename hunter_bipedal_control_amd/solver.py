@@ -42,7 +42,7 @@ ABI_SYMBOLS = [
     "hb_plant_set_respawn", "hb_plant_respawn", "hb_plant_get_respawn",
     "hb_plant_set_scenario", "hb_plant_get_scenario", "hb_plant_get_scenario_log",
     "hb_plant_set_profile_draw", "hb_plant_get_profile_draw", "hb_plant_get_profile_draw_log",
-    "hb_ground_set_profile", "hb_ground_get_profile", "hb_ground_eval",
+    "hb_ground_set_profile", "hb_ground_get_profile", "hb_ground_set_field", "hb_ground_get_field", "hb_ground_eval",
 ]
 # include/hunter_lcm.h
 LCM_SYMBOLS = ["hb_lcm_fingerprint", "hb_lcm_encoded_size", "hb_lcm_field_count", "hb_lcm_encode", "hb_lcm_decode", "hb_lcm_frame", "hb_lcm_unframe",
@@ -435,9 +435,36 @@ class HunterSolver:
         self._check(self.lib.hb_ground_get_profile(self.ctx, *[_p(a) for a in out.values()]), "hb_ground_get_profile")
         return out
 
+    def ground_set_field(self, direction=None, origin=None, spacing=None, heights=None):
+        """Two-dimensional height field the planner, the command target and the filter take for the ground, per instance — the grid of
+        plant_set_terrain_field without its friction: direction [B][2] = the first grid axis a (the second is b = (-a_y, a_x)); origin
+        [B][2]; spacing [B][2]; heights = a [B][nu][nw] array or a list of B arrays [nu_i][nw_i], relative to the level ground of a
+        controller without a map.  All None: no map.  Replaces a profile map (ground_set_profile); independent of the plant's ground."""
+        if direction is None and origin is None and spacing is None and heights is None:
+            self._check(self.lib.hb_ground_set_field(self.ctx, None, None, None, None, None), "hb_ground_set_field")
+            return
+        N = abi.HB_FIELD_MAX_NODES
+        assert len(heights) == self.B, len(heights)
+        n, z = np.zeros((self.B, 2), dtype=np.int32), np.zeros((self.B, N, N))
+        for i, h in enumerate(heights):
+            h = np.asarray(h, dtype=np.float64)
+            assert h.ndim == 2, h.shape
+            n[i] = h.shape
+            z[i, :min(N, h.shape[0]), :min(N, h.shape[1])] = h[:N, :N]
+        self._check(self.lib.hb_ground_set_field(self.ctx, _p(n), _p(_f64(direction, (self.B, 2))), _p(_f64(origin, (self.B, 2))),
+                                                 _p(_f64(spacing, (self.B, 2))), _p(z)), "hb_ground_set_field")
+
+    def ground_get_field(self):
+        """-> dict(n_nodes[B][2], dir[B][2] as stored, origin[B][2], spacing[B][2], heights[B][32][32]) of the field map in force."""
+        N = abi.HB_FIELD_MAX_NODES
+        out = dict(n_nodes=np.zeros((self.B, 2), dtype=np.int32), dir=np.zeros((self.B, 2)), origin=np.zeros((self.B, 2)), spacing=np.zeros((self.B, 2)),
+                   heights=np.zeros((self.B, N, N)))
+        self._check(self.lib.hb_ground_get_field(self.ctx, *[_p(a) for a in out.values()]), "hb_ground_get_field")
+        return out
+
     def ground_eval(self, inst, xy):
         """The device height function of the map in force at n points: inst [n] = the instance whose map a point is put to, xy [n][2]
-        -> (height[n], segment[n])."""
+        -> (height[n], segment[n]); under a field map segment is the facet id."""
         ii = _i32(inst)
         n = ii.shape[0]
         p = _f64(xy, (n, 2))

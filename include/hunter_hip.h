@@ -1277,6 +1277,41 @@ int32_t hb_ground_set_profile(hb_ctx* ctx, const int32_t* n_knots /*[batch]*/, c
 /* The map in force (any pointer may be NULL): n_knots[batch], dir[batch][2] as stored, knots[batch][HB_PROFILE_MAX_KNOTS][2] (zero from
  * n_knots on), slopes[batch][HB_PROFILE_MAX_KNOTS - 1] = m_j (zero from n_knots - 1 on).  HB_ERR_STATE without a map in force. */
 int32_t hb_ground_get_profile(hb_ctx* ctx, int32_t* n_knots, double* dir, double* knots, double* slopes);
+/* ---- ground map of the controller as a two-dimensional height field ------------------------------------------------------------------
+ * A field map gives instance i the grid of a plant height field (hb_plant_set_terrain_field) without its friction: a horizontal unit
+ * direction a = (a_x, a_y) with b = (-a_y, a_x), an origin (u0, w0), spacings (du, dw) > 0, node counts 2 <= nu, nw <= HB_FIELD_MAX_NODES
+ * and heights g[iu][iw], under the same checks (the plant's routine is run on the map with no friction, the triangle bound
+ * p^2 + r^2 <= 3 (1 + 1e-12) included), so a plant field is always a valid map.  The heights are RELATIVE to the level ground the
+ * controller has always assumed: g = 0 everywhere is the world without a map.  The map is independent of the plant's ground.
+ * Height function  G_i(x, y),  every operation rounded on its own (no fused multiply-add), the cell and triangle exactly the plant's
+ * (one routine, csrc/hb_contact.hpp field_cell, serves the plant's facet and this function):
+ *   u = (a_x x + a_y y) - u0;   w = (b_x x + b_y y) - w0;   su = u / du;   sw = w / dw
+ *   i = su >= 1 ? (su < nu - 2 ? int(su) : nu - 2) : 0;   j likewise from sw and nw   (a NaN fails every comparison: cell 0)
+ *   fu = su - i;   fw = sw - j;   t = fu < fw ? 1 : 0     (beyond the grid fu, fw leave [0, 1]: the border cell's planes continue)
+ *   g00 = g[i][j], g01 = g[i][j + 1], g10 = g[i + 1][j], g11 = g[i + 1][j + 1]
+ *   t = 0 (fu >= fw, the lower triangle):   G = g00 + (g10 - g00) fu + (g11 - g10) fw      (left to right)
+ *   t = 1 (the upper triangle):             G = g00 + (g01 - g00) fw + (g11 - g01) fu
+ * A level cell returns g00 bit for bit; a NaN coordinate selects facet 0 and returns NaN.  The facet id is the plant's,
+ * 2 (i (nw - 1) + j) + t.
+ * While a field map is in force the planner step and the filter step run in their field forms (k_refgen_gfield, k_estimator_gfield;
+ * the forms without a map and the profile forms are untouched), which differ from the level ones in exactly the six operands listed
+ * above hb_ground_set_profile, with this G in place of the profile's, per contact point.
+ *
+ * n_nodes[batch][2] = (nu, nw); dir[batch][2] (|a| > 0, normalised before it is stored); origin[batch][2]; spacing[batch][2];
+ * heights[batch][HB_FIELD_MAX_NODES][HB_FIELD_MAX_NODES], entries beyond (nu, nw) are not read.  All five NULL switch the map off.
+ * HB_ERR_ARG for a node count out of range, a non-finite entry, |a| = 0, a spacing <= 0 or a triangle steeper than sqrt(3) (the message
+ * names the first offending instance; the map in force is kept).  One map at a time: hb_ground_set_profile and hb_ground_set_field
+ * replace one another (all-NULL in either switches the map in force off), and each getter returns HB_ERR_STATE while the other kind
+ * is in force.  A profile draw with follow_map (hb_plant_set_profile_draw) writes profile records: it and a field map refuse one another
+ * with HB_ERR_STATE, in either order.  Legal any time after hb_create; synchronises, takes effect from the next pass, and every change of
+ * kind (on, off, profile <-> field) re-captures the range graphs.  The map survives hb_refgen_reset, hb_estimator_reset, hb_plant_reset
+ * and a respawn. */
+int32_t hb_ground_set_field(hb_ctx* ctx, const int32_t* n_nodes /*[batch][2]*/, const double* dir /*[batch][2]*/,
+                            const double* origin /*[batch][2]*/, const double* spacing /*[batch][2]*/,
+                            const double* heights /*[batch][HB_FIELD_MAX_NODES][HB_FIELD_MAX_NODES]*/);
+/* The field map in force (any pointer may be NULL): n_nodes[batch][2], dir[batch][2] as stored, origin, spacing [batch][2],
+ * heights[batch][HB_FIELD_MAX_NODES][HB_FIELD_MAX_NODES] (zero beyond (nu, nw)).  HB_ERR_STATE unless a field map is in force. */
+int32_t hb_ground_get_field(hb_ctx* ctx, int32_t* n_nodes, double* dir, double* origin, double* spacing, double* heights);
 /* Node tables back to the host (any pointer may be NULL); layouts as in hb_mpc_set_references. */
 int32_t hb_mpc_get_references(hb_ctx* ctx, int32_t inst_begin, int32_t inst_count, int32_t* n_nodes, double* t,
                               int32_t* mode, double* x_ref, double* swing_ref);

@@ -548,6 +548,19 @@ class ReferenceManager {
     ctx_.check(hb_ground_set_profile(ctx_.get(), off ? nullptr : nKnots.data(), off ? nullptr : dir.data(), off ? nullptr : knots.data()),
                "hb_ground_set_profile");
   }
+  // The same as a two-dimensional height field (hb_ground_set_field; replaces a profile map and is replaced by one): nNodes [batch][2],
+  // dir, origin, spacing [batch][2], heights [batch][HB_FIELD_MAX_NODES][HB_FIELD_MAX_NODES].  All five empty: no map.
+  void setGroundField(const std::vector<int32_t>& nNodes, const vector_t& dir, const vector_t& origin, const vector_t& spacing,
+                      const vector_t& heights) {
+    const size_t B = size_t(ctx_.batch());
+    const bool off = nNodes.empty() && dir.size() == 0 && origin.size() == 0 && spacing.size() == 0 && heights.size() == 0;
+    if (!off && (nNodes.size() != B * 2 || size_t(dir.size()) != B * 2 || size_t(origin.size()) != B * 2 || size_t(spacing.size()) != B * 2 ||
+                 size_t(heights.size()) != B * HB_FIELD_MAX_NODES * HB_FIELD_MAX_NODES))
+      throw std::invalid_argument("[hunter_hip] setGroundField: wrong vector size");
+    ctx_.check(hb_ground_set_field(ctx_.get(), off ? nullptr : nNodes.data(), off ? nullptr : dir.data(), off ? nullptr : origin.data(),
+                                   off ? nullptr : spacing.data(), off ? nullptr : heights.data()),
+               "hb_ground_set_field");
+  }
   // initTime [batch], cmdVel [batch][4] = (vx, vy, vz, yaw rate); observation [batch][22] or nullptr = the resident one
   void preSolverRun(const vector_t& initTime, scalar_t timeHorizon, const vector_t& cmdVel, const vector_t* observation = nullptr) {
     const size_t B = size_t(ctx_.batch());
@@ -627,6 +640,19 @@ class KalmanFilterEstimate {
       throw std::invalid_argument("[hunter_hip] setGroundProfile: wrong vector size");
     ctx_.check(hb_ground_set_profile(ctx_.get(), off ? nullptr : nKnots.data(), off ? nullptr : dir.data(), off ? nullptr : knots.data()),
                "hb_ground_set_profile");
+  }
+  // The same as a two-dimensional height field (hb_ground_set_field; replaces a profile map and is replaced by one): nNodes [batch][2],
+  // dir, origin, spacing [batch][2], heights [batch][HB_FIELD_MAX_NODES][HB_FIELD_MAX_NODES].  All five empty: no map.
+  void setGroundField(const std::vector<int32_t>& nNodes, const vector_t& dir, const vector_t& origin, const vector_t& spacing,
+                      const vector_t& heights) {
+    const size_t B = size_t(ctx_.batch());
+    const bool off = nNodes.empty() && dir.size() == 0 && origin.size() == 0 && spacing.size() == 0 && heights.size() == 0;
+    if (!off && (nNodes.size() != B * 2 || size_t(dir.size()) != B * 2 || size_t(origin.size()) != B * 2 || size_t(spacing.size()) != B * 2 ||
+                 size_t(heights.size()) != B * HB_FIELD_MAX_NODES * HB_FIELD_MAX_NODES))
+      throw std::invalid_argument("[hunter_hip] setGroundField: wrong vector size");
+    ctx_.check(hb_ground_set_field(ctx_.get(), off ? nullptr : nNodes.data(), off ? nullptr : dir.data(), off ? nullptr : origin.data(),
+                                   off ? nullptr : spacing.data(), off ? nullptr : heights.data()),
+               "hb_ground_set_field");
   }
   // StateEstimateBase::setCmdTorque + estContactForce (StateEstimateBase.cpp:130-206; LeggedController.cpp:344-345): the momentum
   // observer on the rbd state the last update() left on the device.  cmdTorque [batch][10] = the measured joint efforts.

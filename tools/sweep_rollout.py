@@ -25,7 +25,8 @@
     python tools/sweep_rollout.py --rough 1500 --robots 64   rough ground: a seeded 32 x 32 height field of 5 cm cells per robot, bump amplitude
                                                         0 .. --rough-max metres in eight steps over the batch (hb_plant_set_terrain_field), the
                                                         controller blind; survival, tilt and slip by amplitude from one run(n) and one
-                                                        read-back of the episode record
+                                                        read-back of the episode record.  --ground-map: the same rows once more with the
+                                                        field as the controller's field map (hb_ground_set_field), next to the blind ones
     python tools/sweep_rollout.py --readback            the two sweeps once more with the per-tick read-back loop the findings of items 17 - 20
                                                         were made with, for the wall time per tick of both
 
@@ -93,9 +94,10 @@ def run_curb(params, heights, at, ticks, joint_model=None, riser_slope=np.sqrt(3
 ROUGH_STEPS, ROUGH_CELL = 8, 0.05
 
 
-def run_rough(params, robots, ticks, amp_max, joint_model=None):
+def run_rough(params, robots, ticks, amp_max, joint_model=None, ground_map=False):
     """One batch: instance i trots along +x over a rough field of its own (seed i) with bump amplitude amp_max * (i % 8) / 7, 32 x 32 nodes of
-    5 cm, from 0.35 m behind the start to 1.2 m ahead of it -> (amplitude per instance, episode record, wall seconds of the ticks)."""
+    5 cm, from 0.35 m behind the start to 1.2 m ahead of it; ground_map: the controller is given the field too (hb_ground_set_field)
+    -> (amplitude per instance, episode record, wall seconds of the ticks)."""
     B = robots
     amp = amp_max * (np.arange(B) % ROUGH_STEPS) / (ROUGH_STEPS - 1)
     fields = [dict(dir=[1.0, 0.0], origin=[-0.35, -0.775], spacing=[ROUGH_CELL, ROUGH_CELL], heights=rough_field(i, amp[i], (ROUGH_CELL, ROUGH_CELL)))
@@ -105,7 +107,8 @@ def run_rough(params, robots, ticks, amp_max, joint_model=None):
         horizon = 100 * params["config"]["dt"]
         # (fall_height 0.2 as in run_curb: the fall test is measured along the normal of the facet under the base origin)
         loop = ResidentLoop(s, params, ["trot"] * B, np.tile([0.2, 0.0, 0.0, 0.0], (B, 1)), contact_config=dict(fall_height=0.2), joint_model=joint_model,
-                            terrain=dict(field=fields, relative=True), static_schedule_until=ticks * 0.002 + horizon + 1.5, episode=dict(slip_speed=0.05))
+                            terrain=dict(field=fields, relative=True), static_schedule_until=ticks * 0.002 + horizon + 1.5, episode=dict(slip_speed=0.05),
+                            ground_map="field" if ground_map else None)
         s.sync()
         t0 = time.perf_counter()
         loop.run(ticks)
@@ -329,7 +332,7 @@ def main():
     ap.add_argument("--max-ticks", type=int, default=400, help="time-out of an episode of --randomize / --random-curbs")
     ap.add_argument("--host-driven", action="store_true", help="--randomize with the host calling the setters per respawn round and uploading a wrench per tick")
     ap.add_argument("--curb", action="store_true", help="one curb / step-down height per robot (0, 1, 2, 3 cm down and up), trot across it; from the episode record alone")
-    ap.add_argument("--ground-map", action="store_true", help="--curb with the controller's ground map set to the plant's profile (hb_ground_set_profile); --random-curbs with the map following every drawn ground")
+    ap.add_argument("--ground-map", action="store_true", help="--curb with the controller's ground map set to the plant's profile (hb_ground_set_profile); --random-curbs with the map following every drawn ground; --rough a second time with the plant's field as the controller's field map (hb_ground_set_field)")
     ap.add_argument("--curb-at", type=float, default=0.08, help="where the riser of --curb starts, metres ahead of the base origin of the start")
     ap.add_argument("--riser-slope", type=float, default=float(np.sqrt(3.0)), help="slope of the riser of --curb (at most sqrt(3))")
     ap.add_argument("--rough", type=int, metavar="N_TICKS", help="N_TICKS ticks on a seeded rough height field per robot, bump amplitude 0 .. --rough-max over the batch (--robots); one read-back")
@@ -344,11 +347,12 @@ def main():
         table("height", CURBS, rec)
         print("   segment under the four contact points and the base at the end (0 before the riser, 1 on it, 2 beyond):", seg.tolist())
         return
-    if args.rough:
-        amp, rec, wall = run_rough(params, args.robots, args.rough, args.rough_max, joint_model=jm)
-        print(f"-- rough ground, controller blind, {'joint model' if args.joint_model else 'ideal joints'}, B = {args.robots}, {args.rough} ticks, "
-              f"run() and one read-back: {wall:.3f} s, {1e3 * wall / args.rough:.3f} ms per tick")
+    for mapped in ([False, True] if args.ground_map else [False]) if args.rough else []:   # (--ground-map: the same rows next to the blind ones)
+        amp, rec, wall = run_rough(params, args.robots, args.rough, args.rough_max, joint_model=jm, ground_map=mapped)
+        print(f"-- rough ground, controller {'on the field map' if mapped else 'blind'}, {'joint model' if args.joint_model else 'ideal joints'}, "
+              f"B = {args.robots}, {args.rough} ticks, run() and one read-back: {wall:.3f} s, {1e3 * wall / args.rough:.3f} ms per tick")
         print_rough(amp, rec)
+    if args.rough:
         return
     if args.random_curbs:
         log, tot, wall = run_random_curbs(params, args.robots, args.random_curbs, args.max_ticks, joint_model=jm, ground_map=args.ground_map)
