@@ -89,10 +89,10 @@ struct EstIn {
   const int* contact;     // 4
 };
 
-// GROUND: the ground form — the four foot-height measurements are the map `gnd` of the instance (hb_ground.hpp) under the PREDICTED foot
+// MAP_PROFILE: the ground form — the four foot-height measurements are the map `gnd` of the instance (hb_ground.hpp) under the PREDICTED foot
 // positions, feetHeights_ of the reference's filter (LinearKalmanFilter.cpp:143,227), in place of 0.  No Jacobian term for it.
-// GROUND 2: the same on the field map (hb_ground_set_field): gnd its header, gz its heights.  estimator_update<true> is GROUND 1.
-template <int GROUND = 0, class Ctx>
+// MAP_FIELD: the same on the field map (hb_ground_set_field): gnd its header, gz its heights.
+template <int MAP = MAP_NONE, class Ctx>
 HB_HD void estimator_update(const Ctx& cx, const DevModel& M, const hb_estimator_config& K, double dt, const EstIn& in, double* xhat,
                             double* Pst, double* yaw_last, double* lds, double* rbd_out, double* x_out, const double* gnd = nullptr,
                             const double* gz = nullptr) {
@@ -194,7 +194,7 @@ HB_HD void estimator_update(const Ctx& cx, const DevModel& M, const hb_estimator
     double yv = 0.0;
     if (i < 12) yv = -feet[i] + ((i - 3 * (i / 3)) == 2 ? K.foot_radius : 0.0);
     else if (i < 24) yv = -feet[i];
-    else if constexpr (GROUND != 0) yv = map_height<GROUND>(gnd, gz, xh[6 + 3 * (i - 24)], xh[7 + 3 * (i - 24)]);
+    else if constexpr (MAP != MAP_NONE) yv = map_height<MAP>(gnd, gz, xh[6 + 3 * (i - 24)], xh[7 + 3 * (i - 24)]);
     ey[i] = yv - (xh[plus] - (minus >= 0 ? xh[minus] : 0.0));
   }
   // CP = C Pm

@@ -144,7 +144,11 @@ inline bool use_ric_fwd_wave(const KernelForms& f, int concurrent) {
 // field forms (k_refgen_gfield, k_estimator_gfield) while a field map is (hb_ground_set_field), the base forms otherwise — the base forms
 // never see a map, so a context without one runs what it always ran.  One map at a time: the host never has both in force, and a field
 // would go first.
-enum class GroundForm { None, Profile, Field };
+// MAP_*: the map kind under its one set of names — the template argument MAP of the device routines that put a point to the map
+// (hb_ground.hpp map_height, refgen_plan, rg_make_target, estimator_update and the kernel bodies) and the values of GroundForm.  They stand
+// here, not in hb_ground.hpp: this header is upstream of it (hb_math.hpp) and is compiled alone as C++14.
+constexpr int MAP_NONE = 0, MAP_PROFILE = 1, MAP_FIELD = 2;
+enum class GroundForm { None = MAP_NONE, Profile = MAP_PROFILE, Field = MAP_FIELD };
 inline GroundForm use_ground_forms(bool map_in_force, bool field_map_in_force = false) {
   return field_map_in_force ? GroundForm::Field : map_in_force ? GroundForm::Profile : GroundForm::None;
 }

@@ -5,6 +5,7 @@
 // Plain C++ apart from HB_HD: tests/host_emu/groundemu.cpp compiles this header with g++.
 #pragma once
 #include "hb_contact.hpp"
+#include "hb_forms.hpp"  // MAP_NONE, MAP_PROFILE, MAP_FIELD
 
 namespace hb {
 
@@ -91,12 +92,12 @@ HB_HD double ground_field_height(const double* h, const double* __restrict__ z, 
   return g00 + e1 * f1 + e2 * f2;
 }
 
-// What the planner, the command target and the filter put their points to.  MAP: 0 no map, 1 the profile map (gnd: its Ground record),
-// 2 the field map (gnd: its header, gz: its heights).
+// What the planner, the command target and the filter put their points to.  MAP (hb_forms.hpp): MAP_NONE no map, MAP_PROFILE the profile
+// map (gnd: its Ground record), MAP_FIELD the field map (gnd: its header, gz: its heights).  *id (or null): the segment or the facet.
 template <int MAP>
-HB_HD double map_height(const double* gnd, const double* gz, double x, double y) {
-  if constexpr (MAP == 2) return ground_field_height(gnd, gz, x, y);
-  else return ground_height(gnd, x, y);
+HB_HD double map_height(const double* gnd, const double* gz, double x, double y, int* id = nullptr) {
+  if constexpr (MAP == MAP_FIELD) return ground_field_height(gnd, gz, x, y, id);
+  else return ground_height(gnd, x, y, id);
 }
 
 }  // namespace hb

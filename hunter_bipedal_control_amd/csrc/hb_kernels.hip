@@ -1653,11 +1653,69 @@ __global__ __launch_bounds__(64) void k_gait_insert(GaitBatch g, double pts, int
   gait_insert_template(g, i, pts, n_switch, sw, modes, start[i], final_time[i]);
 }
 
+// What a base form of the planner or the filter passes its body for the maps of its instances: nothing.  (Both base forms stay written out
+// for now, each under the instantiation it spells)
+struct NoMap {};
+
 // planner step: FOUR lanes per instance, one per foot (refgen_plan: the four planner loops and the leg evaluations side by side; the lane
 // of foot 0 finishes with the shooting grid and the knots) — thread-per-instance the kernel was a 0.26 ms chain on 64 wavefronts
 // init_flag (or null): per-instance "take the latest stance positions from the observation", the pending flag of a respawn
+// ONE body for the three forms that follow; MAP (hb_forms.hpp) is the map the planner puts its points to, g the
+// maps of the instances of b (NoMap, hb_layout.hpp GroundBatch or GroundFieldBatch).  The batches and the config come by reference: by
+// value the inlined body was allocated and scheduled further from the kernels it replaces.
+template <int MAP, class G>
+__device__ __forceinline__ void refgen_step(const Batch& b, const RefgenBatch& r, const G& g, const DevModel* __restrict__ M, const hb_refgen_config& K,
+                                            double horizon, const int* __restrict__ init_flag) {
+  const int gid = blockIdx.x * blockDim.x + threadIdx.x;
+  const int i = gid >> 2, foot = gid & 3;
+  if (i >= b.B) return;   // (a whole group of four leaves together)
+  const double* x_now = b.x0 + size_t(i) * HB_NX;
+  double* stance = r.stance + size_t(i) * 12;
+  if (r.init_stance || (init_flag && init_flag[i])) {
+    const Mat3<double> R0 = rg_rot_zyx(x_now + 9);
+    const Vec3<double> p0(x_now[6], x_now[7], x_now[8]);
+    const double* qj = x_now + 12;
+    LegOut<double> L;
+    leg_eval<double>(*M, foot & 1, [qj](int j) { return qj[j]; }, [](int) { return 0.0; }, L);
+    st3(stance + 3 * foot, p0 + R0 * ((foot >> 1) ? L.foot[1] : L.foot[0]));
+  }
+  const double* gnd = nullptr;
+  const double* __restrict__ gz = nullptr;
+  [[maybe_unused]] double hdr[GroundField::size];
+  if constexpr (MAP == MAP_PROFILE) {
+    // The four lanes of an instance stage its record in LDS first (16 instances x 50 doubles per wavefront): a foot puts some thirty points
+    // to the map one after the other, each a scan whose loads hang on the point before, and from global memory those chains were half the
+    // kernel.
+    __shared__ double maps[16 * Ground::size];
+    double* rec = maps + (threadIdx.x >> 2) * Ground::size;
+    for (int k = foot; k < Ground::size; k += 4) rec[k] = g.map[size_t(i) * Ground::size + k];
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    gnd = rec;
+  } else if constexpr (MAP == MAP_FIELD) {
+    // The header's eight doubles are read once into registers (field_cell indexes them statically); the heights stay in global memory —
+    // 8 KB per instance, sixteen instances per wavefront: staged they would leave a CU one workgroup — and an evaluation issues its four
+    // loads together.
+    const double* __restrict__ gh = g.hdr + size_t(i) * GroundField::size;
+#pragma unroll
+    for (int k = 0; k < GroundField::size; ++k) hdr[k] = gh[k];
+    gnd = hdr;
+    gz = g.z + size_t(i) * GroundField::nz;
+  }
+  const size_t N = b.Nmax;
+  const int st = refgen_plan<MAP>(*M, K, r.n_ev[i], r.ev + size_t(i) * HB_MAX_EVENTS, r.modes + size_t(i) * (HB_MAX_EVENTS + 1), r.t0[i], horizon,
+                                  x_now, r.cmd + size_t(i) * 4, stance, r.phases + size_t(i) * 4 * (HB_MAX_EVENTS + 1) * RG_PHASE, b.Nmax,
+                                  b.n_nodes + i, b.t + size_t(i) * (N + 1), r.n_knots + i, r.knot_t + size_t(i) * RG_MAX_KNOTS,
+                                  r.knot_x + size_t(i) * RG_MAX_KNOTS * HB_NX, foot, 4, gnd, gz);
+  // status of the instance: 2 (grid too long, from the lane of foot 0) wins, else 1 if any foot reported a phase without its events
+  int any = st == 1 ? 1 : 0;
+  any |= __shfl_xor(any, 1, 64);
+  any |= __shfl_xor(any, 2, 64);
+  if (foot == 0) r.status[i] = st == 2 ? 2 : any;
+}
 __global__ __launch_bounds__(64) void k_refgen(Batch b, RefgenBatch r, const DevModel* __restrict__ M, hb_refgen_config K, double horizon,
                                                const int* __restrict__ init_flag) {
+  // refgen_step<MAP_NONE>(b, r, NoMap{}, M, K, horizon, init_flag) written out (timing)
   const int gid = blockIdx.x * blockDim.x + threadIdx.x;
   const int i = gid >> 2, foot = gid & 3;
   if (i >= b.B) return;   // (a whole group of four leaves together)
@@ -1676,82 +1734,20 @@ __global__ __launch_bounds__(64) void k_refgen(Batch b, RefgenBatch r, const Dev
                              r.cmd + size_t(i) * 4, stance, r.phases + size_t(i) * 4 * (HB_MAX_EVENTS + 1) * RG_PHASE, b.Nmax, b.n_nodes + i,
                              b.t + size_t(i) * (N + 1), r.n_knots + i, r.knot_t + size_t(i) * RG_MAX_KNOTS,
                              r.knot_x + size_t(i) * RG_MAX_KNOTS * HB_NX, foot, 4);
-  // status of the instance: 2 (grid too long, from the lane of foot 0) wins, else 1 if any foot reported a phase without its events
   int any = st == 1 ? 1 : 0;
   any |= __shfl_xor(any, 1, 64);
   any |= __shfl_xor(any, 2, 64);
   if (foot == 0) r.status[i] = st == 2 ? 2 : any;
 }
-// the ground form of k_refgen (hb_ground_set_profile; launched only while a map is in force): the same step with refgen_plan<true> on the map
-// record of the instance, g = the maps of the instances of b (hb_layout.hpp GroundBatch).  k_refgen itself is left as it was.
-// The four lanes of an instance stage its record in LDS first (16 instances x 50 doubles per wavefront): a foot puts some thirty points to
-// the map one after the other, each a scan whose loads hang on the point before, and from global memory those chains were half the kernel.
+// the ground form (hb_ground_set_profile; launched only while a profile map is in force)
 __global__ __launch_bounds__(64) void k_refgen_ground(Batch b, RefgenBatch r, GroundBatch g, const DevModel* __restrict__ M, hb_refgen_config K,
                                                       double horizon, const int* __restrict__ init_flag) {
-  const int gid = blockIdx.x * blockDim.x + threadIdx.x;
-  const int i = gid >> 2, foot = gid & 3;
-  if (i >= b.B) return;   // (a whole group of four leaves together)
-  const double* x_now = b.x0 + size_t(i) * HB_NX;
-  double* stance = r.stance + size_t(i) * 12;
-  if (r.init_stance || (init_flag && init_flag[i])) {
-    const Mat3<double> R0 = rg_rot_zyx(x_now + 9);
-    const Vec3<double> p0(x_now[6], x_now[7], x_now[8]);
-    const double* qj = x_now + 12;
-    LegOut<double> L;
-    leg_eval<double>(*M, foot & 1, [qj](int j) { return qj[j]; }, [](int) { return 0.0; }, L);
-    st3(stance + 3 * foot, p0 + R0 * ((foot >> 1) ? L.foot[1] : L.foot[0]));
-  }
-  __shared__ double maps[16 * Ground::size];
-  double* gnd = maps + (threadIdx.x >> 2) * Ground::size;
-  for (int k = foot; k < Ground::size; k += 4) gnd[k] = g.map[size_t(i) * Ground::size + k];
-  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  const size_t N = b.Nmax;
-  const int st = refgen_plan<true>(*M, K, r.n_ev[i], r.ev + size_t(i) * HB_MAX_EVENTS, r.modes + size_t(i) * (HB_MAX_EVENTS + 1), r.t0[i], horizon,
-                                   x_now, r.cmd + size_t(i) * 4, stance, r.phases + size_t(i) * 4 * (HB_MAX_EVENTS + 1) * RG_PHASE, b.Nmax,
-                                   b.n_nodes + i, b.t + size_t(i) * (N + 1), r.n_knots + i, r.knot_t + size_t(i) * RG_MAX_KNOTS,
-                                   r.knot_x + size_t(i) * RG_MAX_KNOTS * HB_NX, foot, 4, gnd);
-  // status of the instance: 2 (grid too long, from the lane of foot 0) wins, else 1 if any foot reported a phase without its events
-  int any = st == 1 ? 1 : 0;
-  any |= __shfl_xor(any, 1, 64);
-  any |= __shfl_xor(any, 2, 64);
-  if (foot == 0) r.status[i] = st == 2 ? 2 : any;
+  refgen_step<MAP_PROFILE>(b, r, g, M, K, horizon, init_flag);
 }
-// the field form of k_refgen (hb_ground_set_field; launched only while a field map is in force): the same step with refgen_plan<2> on the
-// field map of the instance, g = the maps of the instances of b (hb_layout.hpp GroundFieldBatch).  The header's eight doubles are read
-// once into registers (field_cell indexes them statically); the heights stay in global memory — 8 KB per instance, sixteen instances per
-// wavefront: staged they would leave a CU one workgroup — and an evaluation issues its four loads together.  k_refgen and
-// k_refgen_ground are left as they were.
+// the field form (hb_ground_set_field; launched only while a field map is in force)
 __global__ __launch_bounds__(64) void k_refgen_gfield(Batch b, RefgenBatch r, GroundFieldBatch g, const DevModel* __restrict__ M, hb_refgen_config K,
                                                       double horizon, const int* __restrict__ init_flag) {
-  const int gid = blockIdx.x * blockDim.x + threadIdx.x;
-  const int i = gid >> 2, foot = gid & 3;
-  if (i >= b.B) return;   // (a whole group of four leaves together)
-  const double* x_now = b.x0 + size_t(i) * HB_NX;
-  double* stance = r.stance + size_t(i) * 12;
-  if (r.init_stance || (init_flag && init_flag[i])) {
-    const Mat3<double> R0 = rg_rot_zyx(x_now + 9);
-    const Vec3<double> p0(x_now[6], x_now[7], x_now[8]);
-    const double* qj = x_now + 12;
-    LegOut<double> L;
-    leg_eval<double>(*M, foot & 1, [qj](int j) { return qj[j]; }, [](int) { return 0.0; }, L);
-    st3(stance + 3 * foot, p0 + R0 * ((foot >> 1) ? L.foot[1] : L.foot[0]));
-  }
-  double hdr[GroundField::size];
-  const double* __restrict__ gh = g.hdr + size_t(i) * GroundField::size;
-#pragma unroll
-  for (int k = 0; k < GroundField::size; ++k) hdr[k] = gh[k];
-  const double* __restrict__ gz = g.z + size_t(i) * GroundField::nz;
-  const size_t N = b.Nmax;
-  const int st = refgen_plan<2>(*M, K, r.n_ev[i], r.ev + size_t(i) * HB_MAX_EVENTS, r.modes + size_t(i) * (HB_MAX_EVENTS + 1), r.t0[i], horizon,
-                                x_now, r.cmd + size_t(i) * 4, stance, r.phases + size_t(i) * 4 * (HB_MAX_EVENTS + 1) * RG_PHASE, b.Nmax,
-                                b.n_nodes + i, b.t + size_t(i) * (N + 1), r.n_knots + i, r.knot_t + size_t(i) * RG_MAX_KNOTS,
-                                r.knot_x + size_t(i) * RG_MAX_KNOTS * HB_NX, foot, 4, hdr, gz);
-  // status of the instance: 2 (grid too long, from the lane of foot 0) wins, else 1 if any foot reported a phase without its events
-  int any = st == 1 ? 1 : 0;
-  any |= __shfl_xor(any, 1, 64);
-  any |= __shfl_xor(any, 2, 64);
-  if (foot == 0) r.status[i] = st == 2 ? 2 : any;
+  refgen_step<MAP_FIELD>(b, r, g, M, K, horizon, init_flag);
 }
 // joint-reference IK: eight lanes per (instance, leg), eight pairs per wavefront (hb_refgen.hpp refgen_ik_group)
 __global__ __launch_bounds__(64) void k_refgen_ik(Batch b, RefgenBatch r, const DevModel* __restrict__ M, hb_refgen_config K, double horizon) {
@@ -1814,7 +1810,31 @@ __global__ __launch_bounds__(64) void k_refgen_nodes(Batch b, RefgenBatch r, hb_
 }
 
 // ---- state estimator: one wave per instance ----------------------------------------------------------------------
+// ONE body for the three forms that follow: MAP (hb_forms.hpp) is the map whose heights the foot-height rows
+// measure, g the maps of the instances of e.  The profile record is read through the pointer from global memory, and so is the field
+// header (four evaluations a tick, uniform over the wave); the field heights come from global memory.
+template <int MAP, class G>
+__device__ __forceinline__ void estimator_step(const EstBatch& e, const G& g, const DevModel* __restrict__ M, const hb_estimator_config& K, double dt) {
+  const int i = blockIdx.x;
+  __shared__ double lds[EstLds::total];
+  const DeviceCtx cx;
+  const EstIn in{e.quat + 4 * i, e.w_local + 3 * i, e.a_local + 3 * i, e.qj + 10 * i, e.qdj + 10 * i, e.contact + 4 * i};
+  const double *gnd = nullptr, *gz = nullptr;
+  if constexpr (MAP == MAP_PROFILE) {
+    gnd = g.map + size_t(i) * Ground::size;
+  } else if constexpr (MAP == MAP_FIELD) {
+    gnd = g.hdr + size_t(i) * GroundField::size;
+    gz = g.z + size_t(i) * GroundField::nz;
+  }
+  estimator_update<MAP>(cx, *M, K, dt, in, e.xhat + 18 * i, e.P + 324 * size_t(i), e.yaw_last + i, lds, e.rbd + HB_NRBD * i, e.x + HB_NX * i, gnd, gz);
+  if (e.res_rbd) {
+    __syncthreads();  // lane 0 wrote the outputs
+    for (int c = cx.lane; c < HB_NRBD; c += 64) e.res_rbd[HB_NRBD * i + c] = e.rbd[HB_NRBD * i + c];
+    for (int c = cx.lane; c < HB_NX; c += 64) e.res_x0[HB_NX * i + c] = e.x[HB_NX * i + c];
+  }
+}
 __global__ __launch_bounds__(64) void k_estimator(EstBatch e, const DevModel* __restrict__ M, hb_estimator_config K, double dt) {
+  // estimator_step<MAP_NONE>(e, NoMap{}, M, K, dt) written out (timing)
   const int i = blockIdx.x;
   __shared__ double lds[EstLds::total];
   const DeviceCtx cx;
@@ -1826,52 +1846,39 @@ __global__ __launch_bounds__(64) void k_estimator(EstBatch e, const DevModel* __
     for (int c = cx.lane; c < HB_NX; c += 64) e.res_x0[HB_NX * i + c] = e.x[HB_NX * i + c];
   }
 }
-// the ground form of k_estimator (hb_ground_set_profile): the same step with estimator_update<true> on the map record of the instance
+// the ground form (hb_ground_set_profile)
 __global__ __launch_bounds__(64) void k_estimator_ground(EstBatch e, GroundBatch g, const DevModel* __restrict__ M, hb_estimator_config K, double dt) {
-  const int i = blockIdx.x;
-  __shared__ double lds[EstLds::total];
-  const DeviceCtx cx;
-  const EstIn in{e.quat + 4 * i, e.w_local + 3 * i, e.a_local + 3 * i, e.qj + 10 * i, e.qdj + 10 * i, e.contact + 4 * i};
-  estimator_update<true>(cx, *M, K, dt, in, e.xhat + 18 * i, e.P + 324 * size_t(i), e.yaw_last + i, lds, e.rbd + HB_NRBD * i, e.x + HB_NX * i,
-                         g.map + size_t(i) * Ground::size);
-  if (e.res_rbd) {
-    __syncthreads();  // lane 0 wrote the outputs
-    for (int c = cx.lane; c < HB_NRBD; c += 64) e.res_rbd[HB_NRBD * i + c] = e.rbd[HB_NRBD * i + c];
-    for (int c = cx.lane; c < HB_NX; c += 64) e.res_x0[HB_NX * i + c] = e.x[HB_NX * i + c];
-  }
+  estimator_step<MAP_PROFILE>(e, g, M, K, dt);
 }
-// the field form of k_estimator (hb_ground_set_field): the same step with estimator_update<2> on the field map of the instance — four
-// evaluations a tick, the header read through the pointer (uniform over the wave), the heights from global memory
+// the field form (hb_ground_set_field)
 __global__ __launch_bounds__(64) void k_estimator_gfield(EstBatch e, GroundFieldBatch g, const DevModel* __restrict__ M, hb_estimator_config K, double dt) {
-  const int i = blockIdx.x;
-  __shared__ double lds[EstLds::total];
-  const DeviceCtx cx;
-  const EstIn in{e.quat + 4 * i, e.w_local + 3 * i, e.a_local + 3 * i, e.qj + 10 * i, e.qdj + 10 * i, e.contact + 4 * i};
-  estimator_update<2>(cx, *M, K, dt, in, e.xhat + 18 * i, e.P + 324 * size_t(i), e.yaw_last + i, lds, e.rbd + HB_NRBD * i, e.x + HB_NX * i,
-                      g.hdr + size_t(i) * GroundField::size, g.z + size_t(i) * GroundField::nz);
-  if (e.res_rbd) {
-    __syncthreads();  // lane 0 wrote the outputs
-    for (int c = cx.lane; c < HB_NRBD; c += 64) e.res_rbd[HB_NRBD * i + c] = e.rbd[HB_NRBD * i + c];
-    for (int c = cx.lane; c < HB_NX; c += 64) e.res_x0[HB_NX * i + c] = e.x[HB_NX * i + c];
-  }
+  estimator_step<MAP_FIELD>(e, g, M, K, dt);
 }
-// test hook (hb_ground_eval): the height function at n points, one thread each; inst[p] is the instance whose map point p is put to
+// test hook (hb_ground_eval): the height function at n points, one thread each; inst[p] is the instance whose map point p is put to,
+// segment[p] the segment of a profile map or the facet id of a field map
+template <int MAP, class G>
+__device__ __forceinline__ void ground_eval_step(int n, const G& g, const int* __restrict__ inst, const double* __restrict__ xy, double* __restrict__ height,
+                                                 int* __restrict__ segment) {
+  const int p = blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= n) return;
+  const double *gnd, *gz = nullptr;
+  if constexpr (MAP == MAP_FIELD) {
+    gnd = g.hdr + size_t(inst[p]) * GroundField::size;
+    gz = g.z + size_t(inst[p]) * GroundField::nz;
+  } else {
+    gnd = g.map + size_t(inst[p]) * Ground::size;
+  }
+  int id = 0;
+  height[p] = map_height<MAP>(gnd, gz, xy[2 * p], xy[2 * p + 1], &id);
+  segment[p] = id;
+}
 __global__ __launch_bounds__(64) void k_ground_eval(int n, GroundBatch g, const int* __restrict__ inst, const double* __restrict__ xy,
                                                     double* __restrict__ height, int* __restrict__ segment) {
-  const int p = blockIdx.x * blockDim.x + threadIdx.x;
-  if (p >= n) return;
-  int seg = 0;
-  height[p] = ground_height(g.map + size_t(inst[p]) * Ground::size, xy[2 * p], xy[2 * p + 1], &seg);
-  segment[p] = seg;
+  ground_eval_step<MAP_PROFILE>(n, g, inst, xy, height, segment);
 }
-// the same under a field map (hb_ground_set_field): segment[p] is the facet id
 __global__ __launch_bounds__(64) void k_ground_field_eval(int n, GroundFieldBatch g, const int* __restrict__ inst, const double* __restrict__ xy,
                                                           double* __restrict__ height, int* __restrict__ segment) {
-  const int p = blockIdx.x * blockDim.x + threadIdx.x;
-  if (p >= n) return;
-  int facet = 0;
-  height[p] = ground_field_height(g.hdr + size_t(inst[p]) * GroundField::size, g.z + size_t(inst[p]) * GroundField::nz, xy[2 * p], xy[2 * p + 1], &facet);
-  segment[p] = facet;
+  ground_eval_step<MAP_FIELD>(n, g, inst, xy, height, segment);
 }
 // StateEstimateBase::estContactForce for every instance, one thread each (hb_estimator.hpp contact_force_estimate); the per-leg forward
 // data sits in LDS (the joint loops index it dynamically).  Not on the timed path of the update: 4096 instances take ~ 0.1 ms.

@@ -112,10 +112,10 @@ struct RgTarget {
 // 0.06 dead band ELSE its y component; first knot = observed position and yaw (pitch / roll zero) with the height moved towards
 // comHeight by at most changeLimit_[2] = 0.04 (TargetTrajectoriesPublisher.h:97); second knot = the pose reached after `horizon`
 // (TIME_TO_TARGET = mpc.timeHorizon) at comHeight.
-// GROUND (the ground form, hb_ground.hpp): both knots stand comHeight above the map `gnd` of the instance under their own x, y.
+// MAP_PROFILE (the ground form, hb_ground.hpp): both knots stand comHeight above the map `gnd` of the instance under their own x, y.
+// MAP_FIELD: the field form — gnd the header, gz the heights of the instance's field map (hb_ground.hpp map_height).
 constexpr double RG_CMD_DEAD_BAND = 0.06, RG_HEIGHT_CHANGE_LIMIT = 0.04;
-// GROUND 2: the field form — gnd the header, gz the heights of the instance's field map (hb_ground.hpp map_height).
-template <int GROUND = 0>
+template <int MAP = MAP_NONE>
 HB_HD void rg_make_target(const RefgenConfig& K, double t0, double horizon, const double* x_now, const double* cmd_vel, double* cur,
                           double* tgt, RgTarget& T, const double* gnd = nullptr, const double* gz = nullptr) {
   const Mat3<double> Rn = rg_rot_zyx(x_now + 9);
@@ -130,14 +130,14 @@ HB_HD void rg_make_target(const RefgenConfig& K, double t0, double horizon, cons
   cur[0] = vw.x; cur[1] = vw.y; cur[2] = vw.z;
   tgt[0] = vw.x; tgt[1] = vw.y; tgt[2] = vw.z;
   double dz = K.com_height - x_now[8];
-  if constexpr (GROUND != 0) dz = K.com_height + map_height<GROUND>(gnd, gz, x_now[6], x_now[7]) - x_now[8];
+  if constexpr (MAP != MAP_NONE) dz = K.com_height + map_height<MAP>(gnd, gz, x_now[6], x_now[7]) - x_now[8];
   dz = dz > 0.0 ? fmin(dz, RG_HEIGHT_CHANGE_LIMIT) : fmax(dz, -RG_HEIGHT_CHANGE_LIMIT);
   cur[6] = x_now[6]; cur[7] = x_now[7]; cur[8] = x_now[8] + dz;
   cur[9] = x_now[9];
   tgt[6] = x_now[6] + vw.x * horizon;
   tgt[7] = x_now[7] + vw.y * horizon;
   tgt[8] = K.com_height;
-  if constexpr (GROUND != 0) tgt[8] = K.com_height + map_height<GROUND>(gnd, gz, tgt[6], tgt[7]);
+  if constexpr (MAP != MAP_NONE) tgt[8] = K.com_height + map_height<MAP>(gnd, gz, tgt[6], tgt[7]);
   tgt[9] = x_now[9] + cmd_vel[3] * horizon;
   for (int j = 0; j < HB_NJ; ++j) { cur[12 + j] = K.default_joints[j]; tgt[12 + j] = K.default_joints[j]; }
 }
@@ -680,18 +680,18 @@ __device__ __forceinline__ void refgen_ik_group(const DevModel& M, const RefgenC
 // emulator, tests); the device gives every foot of an instance its own lane, (lane, 4): the four planner loops — the bulk of the work —
 // and the leg evaluation behind a foot's current position run side by side, the lane of foot 0 then lays out the shooting grid and the knots.
 // Returns the status of what THIS caller did (k_refgen combines the four).
-// GROUND: the ground form — with the map `gnd` of the instance (hb_ground.hpp; read through the pointer, from global memory or LDS: a
+// MAP_PROFILE: the ground form — with the map `gnd` of the instance (hb_ground.hpp; read through the pointer, from global memory or LDS: a
 // thread-private copy would be indexed dynamically) the latest stance position and every foothold stand next_position_z above the map under their own x, y, the centrifugal
 // term takes the height of the body above the map, and the target knots follow it (rg_make_target).  Nothing else differs.
-// GROUND 2: the same on the field map (hb_ground_set_field): gnd its header, gz its heights (global memory).  refgen_plan<true> is GROUND 1.
-template <int GROUND = 0>
+// MAP_FIELD: the same on the field map (hb_ground_set_field): gnd its header, gz its heights (global memory).
+template <int MAP = MAP_NONE>
 HB_HD int refgen_plan(const DevModel& M, const RefgenConfig& K, int n_ev, const double* ev, const int* modes, double t0, double horizon,
                       const double* x_now, const double* cmd_vel, double* latest_stance, double* phases, int max_nodes,
                       int* n_nodes_out, double* t_out, int* n_knots_out, double* knot_t, double* knot_x, int foot0 = 0, int foot_step = 1,
                       const double* gnd = nullptr, const double* gz = nullptr) {
   const int n_ph = n_ev + 1;
   RgTarget T;
-  rg_make_target<GROUND>(K, t0, horizon, x_now, cmd_vel, knot_x + size_t(RG_MAX_KNOTS - 2) * HB_NX, knot_x + size_t(RG_MAX_KNOTS - 1) * HB_NX, T,
+  rg_make_target<MAP>(K, t0, horizon, x_now, cmd_vel, knot_x + size_t(RG_MAX_KNOTS - 2) * HB_NX, knot_x + size_t(RG_MAX_KNOTS - 1) * HB_NX, T,
                          gnd, gz);
   const double tf_h = T.tf;
   // ---- current feet (InverseKinematics::computeFootPos) ------------------------------------------------------------
@@ -730,7 +730,7 @@ HB_HD int refgen_plan(const DevModel& M, const RefgenConfig& K, int n_ev, const 
   for (int j = foot0; j < HB_NC; j += foot_step) {
     double* ls = latest_stance + 3 * j;
     ls[2] = K.next_position_z;
-    if constexpr (GROUND != 0) ls[2] = map_height<GROUND>(gnd, gz, ls[0], ls[1]) + K.next_position_z;
+    if constexpr (MAP != MAP_NONE) ls[2] = map_height<MAP>(gnd, gz, ls[0], ls[1]) + K.next_position_z;
     double last[3] = {ls[0], ls[1], ls[2]}, nxt[3] = {ls[0], ls[1], ls[2]};
     int last_final = 0;
     double* phj = phases + size_t(j) * (RG_MAX_EVENTS + 1) * RG_PHASE;
@@ -769,11 +769,11 @@ HB_HD int refgen_plan(const DevModel& M, const RefgenConfig& K, int n_ev, const 
           const Vec3<double> p_sh = (tf - t0) * (0.5 * v + 0.5 * cl) + bias;
           const Vec3<double> p_sym = (t_mid - tf) * v + 0.03 * (v - cl);
           double above = body.z;   // height of the body above the ground under it
-          if constexpr (GROUND != 0) above = body.z - map_height<GROUND>(gnd, gz, body.x, body.y);
+          if constexpr (MAP != MAP_NONE) above = body.z - map_height<MAP>(gnd, gz, body.x, body.y);
           const Vec3<double> p_cent = (0.5 * sqrt(above / 9.81)) * cross(v, ca);
           const Vec3<double> pn = body + p_sh + p_sym + p_cent;
           nxt[0] = pn.x; nxt[1] = pn.y; nxt[2] = K.next_position_z;
-          if constexpr (GROUND != 0) nxt[2] = map_height<GROUND>(gnd, gz, pn.x, pn.y) + K.next_position_z;
+          if constexpr (MAP != MAP_NONE) nxt[2] = map_height<MAP>(gnd, gz, pn.x, pn.y) + K.next_position_z;
           last_final = f_idx;
         }
         ph[0] = ts; ph[1] = tf;
@@ -894,8 +894,8 @@ HB_HD int refgen_instance(const DevModel& M, const RefgenConfig& K, int n_ev, co
                           const double* gnd = nullptr) {
   int nk = 0;
   double knot_t[RG_MAX_KNOTS], knot_x[RG_MAX_KNOTS * HB_NX];
-  const int status = gnd ? refgen_plan<true>(M, K, n_ev, ev, modes, t0, horizon, x_now, cmd_vel, latest_stance, phases, max_nodes, n_nodes_out,
-                                             t_out, &nk, knot_t, knot_x, 0, 1, gnd)
+  const int status = gnd ? refgen_plan<MAP_PROFILE>(M, K, n_ev, ev, modes, t0, horizon, x_now, cmd_vel, latest_stance, phases, max_nodes, n_nodes_out,
+                                                    t_out, &nk, knot_t, knot_x, 0, 1, gnd)
                          : refgen_plan(M, K, n_ev, ev, modes, t0, horizon, x_now, cmd_vel, latest_stance, phases, max_nodes, n_nodes_out, t_out,
                                        &nk, knot_t, knot_x);
   RgIkWork work;

@@ -1,4 +1,6 @@
-"""Throughput of hb_refgen_update at the bench batch size (run on the GPU box, optionally under rocprofv3)."""
+"""Throughput of hb_refgen_update at the bench batch size (run on the GPU box, optionally under rocprofv3).
+--ground-map profile | field: with a ground map per instance, so that k_refgen_ground or k_refgen_gfield runs in place of k_refgen."""
+import argparse
 import sys
 import time
 from pathlib import Path
@@ -7,6 +9,11 @@ import numpy as np
 from hunter_bipedal_control_amd import abi, ingest, workload
 from oracle import refgen
 from hunter_bipedal_control_amd.solver import HunterSolver
+import ground_map_arg
+
+ap = argparse.ArgumentParser()
+ground_map_arg.add_argument(ap)
+args = ap.parse_args()
 
 P = ingest.load_packaged()
 B, N = 4096, 100
@@ -16,6 +23,7 @@ cmd = np.tile([0.3, 0.0, 0.0, 0.1], (B, 1))
 s = HunterSolver(P, batch=B, max_nodes=N + 8)
 s.refgen_reset(abi.make_refgen_config(P))
 s.refgen_set_schedule([refgen.gait_schedule(P, "trot", 0.1, 8.0)] * B)
+ground_map_arg.apply(s, args.ground_map)
 for k in range(3):
     s.refgen_update(np.full(B, 0.1 + 0.015 * k), horizon, x0, cmd)
 t = time.perf_counter()
@@ -25,6 +33,6 @@ dt = (time.perf_counter() - t) / 20
 t = time.perf_counter()
 refgen.make_trot_problem(P, 0.1, horizon, x0[0], cmd[0], N, joint_ik=False)
 th = time.perf_counter() - t
-print(f"refgen: batch {B} x N {N}: {dt * 1e3:.3f} ms per call host-side = {B / dt:.0f} reference sets/s; status max {st.max()}; "
+print(f"refgen (ground map {args.ground_map}): batch {B} x N {N}: {dt * 1e3:.3f} ms per call host-side = {B / dt:.0f} reference sets/s; status max {st.max()}; "
       f"host refgen.py {th * 1e3:.1f} ms per instance")
 s.close()
