@@ -173,12 +173,8 @@ def numpy_kf(params, cfg, st, dt, quat, w_local, a_local, qj, qdj, contact, gmap
     R = zyx_to_rotation(zyx)
     w_glob = R @ w_local
     pos = _feet_rel(params, zyx, qj)
-    h = 1e-6
-    def at(s):
-        dR = np.eye(3) + s * np.array([[0, -w_glob[2], w_glob[1]], [w_glob[2], 0, -w_glob[0]], [-w_glob[1], w_glob[0], 0]])
-        pb = (R.T @ _feet_rel(params, zyx, qj + s * qdj).T).T
-        return (dR @ R @ pb.T).T
-    vel = (at(h) - at(-h)) / (2 * h)
+    import _kftwin
+    vel = _kftwin.exact_foot_velocities(params, zyx, w_glob, qj, qdj)      # (the oracle's Jacobians, not a central difference of the FK)
     A = np.eye(18); A[0:3, 3:6] = dt * np.eye(3)
     Bm = np.zeros((18, 3)); Bm[0:3] = 0.5 * dt * dt * np.eye(3); Bm[3:6] = dt * np.eye(3)
     Cm = np.zeros((28, 18))

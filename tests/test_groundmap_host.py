@@ -4,7 +4,7 @@ oracle.refgen's, value for value, and its filter is the oracle's at the toleranc
 
 Tolerances of the parity test are the project's own for these quantities (tests/test_host_emu.py): grid and x_ref 1e-12, swing tables 1e-10
 with an identical NaN pattern, IK knots 1e-8, filter 1e-10 (P: 1e-9 relative).  The filter twin takes the foot velocities of the original
-_numpy_kf (central differences), which costs 4e-11 of the 1e-10.
+_numpy_kf (the oracle's Jacobians; they were central differences once, which cost 4e-11 of the 1e-10).
 
 Shift property (test 4), measured on the twin itself: a map level at h = 0.07 with state and stance memory raised by h reproduces the
 zero-map tables raised by h to TWIN_SHIFT_RESIDUAL, per quantity, the largest over the eight cases and both calls (pytest -s prints them).
