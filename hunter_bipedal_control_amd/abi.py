@@ -419,6 +419,52 @@ def split_profile_draw(row) -> dict:
     return {name: (row[..., at].copy() if n == 1 else row[..., at:at + n].copy()) for name, at, n in PROFILE_DRAW_FIELDS}
 
 
+class HbFieldDrawConfig(C.Structure):
+    """hb_field_draw_config (include/hunter_hip.h): field draw at respawn, hb_plant_set_field_draw."""
+    _fields_ = [("seed", C.c_uint64), ("kinds", C.c_int32), ("mu_per_point", C.c_int32), ("dir", C.c_double * 2), ("n_nodes", C.c_int32 * 2),
+                ("spacing", C.c_double * 2), ("centre", C.c_double * 2), ("calm", C.c_double), ("amp_lo", C.c_double), ("amp_hi", C.c_double),
+                ("slope_u_lo", C.c_double), ("slope_u_hi", C.c_double), ("slope_w_lo", C.c_double), ("slope_w_hi", C.c_double),
+                ("mu_lo", C.c_double), ("mu_hi", C.c_double), ("follow_map", C.c_int32), ("log_capacity", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
+HB_FD_STREAM = 0x46444431
+HB_FD_FLAT, HB_FD_ROUGH, HB_FD_TILT, HB_FD_TILT_ROUGH = 1, 2, 4, 8
+HB_FD_ALL = HB_FD_FLAT | HB_FD_ROUGH | HB_FD_TILT | HB_FD_TILT_ROUGH
+# row[HB_FD_N], (name, first index, count), in the order of the HB_FD_* indices of the header.
+FIELD_DRAW_FIELDS = (("KIND", 0, 1), ("AMPLITUDE", 1, 1), ("SLOPE_U", 2, 1), ("SLOPE_W", 3, 1), ("MUS", 4, 4))
+HB_FD_N = 8
+# a log row: the profile draw's five leading entries, then the HB_FD_N parameters
+FIELD_DRAW_LOG_HEAD = PROFILE_DRAW_LOG_HEAD
+HB_FD_LOG_W, HB_FD_LOG_MAX = len(FIELD_DRAW_LOG_HEAD) + HB_FD_N, 1024
+
+
+def make_field_draw_config(**fields) -> HbFieldDrawConfig:
+    """Level ground only: a 32 x 32 grid along x with 0.1 m spacing and the spawn point at its middle, no bumps, no tilt, mu in [0, 0], no
+    map, no log, seed 0; any field by name overrides (dir, n_nodes, spacing, centre: 2 values each; centre None: the middle of the grid)."""
+    d = dict(seed=0, kinds=HB_FD_FLAT, mu_per_point=0, dir=(1.0, 0.0), n_nodes=(HB_FIELD_MAX_NODES, HB_FIELD_MAX_NODES), spacing=(0.1, 0.1),
+             centre=None, calm=0.0, amp_lo=0.0, amp_hi=0.0, slope_u_lo=0.0, slope_u_hi=0.0, slope_w_lo=0.0, slope_w_hi=0.0, mu_lo=0.0, mu_hi=0.0,
+             follow_map=0, log_capacity=0)
+    for k in fields:
+        if k not in d:
+            raise TypeError(f"make_field_draw_config: unknown field {k!r} (one of {sorted(d)})")
+    d.update(fields)
+    out = HbFieldDrawConfig()
+    for k in ("calm", "amp_lo", "amp_hi", "slope_u_lo", "slope_u_hi", "slope_w_lo", "slope_w_hi", "mu_lo", "mu_hi"):
+        setattr(out, k, float(d[k]))
+    for k in ("seed", "kinds", "mu_per_point", "follow_map", "log_capacity"):
+        setattr(out, k, int(d[k]))
+    for j in (0, 1):
+        out.dir[j], out.n_nodes[j], out.spacing[j] = float(d["dir"][j]), int(d["n_nodes"][j]), float(d["spacing"][j])
+        out.centre[j] = 0.5 * float(out.n_nodes[j] - 1) * out.spacing[j] if d["centre"] is None else float(d["centre"][j])
+    return out
+
+
+def split_field_draw(row) -> dict:
+    """row[...][HB_FD_N] -> dict of [...] / [...][n] arrays keyed by field name."""
+    row = np.asarray(row)
+    return {name: (row[..., at].copy() if n == 1 else row[..., at:at + n].copy()) for name, at, n in FIELD_DRAW_FIELDS}
+
+
 class HbJointGains(C.Structure):
     _fields_ = [(k, C.c_double) for k in ("kp_big_stance", "kp_big_swing", "kd_big", "kp_small_stance", "kp_small_swing", "kd_small",
                                           "kd_feet", "kp_position", "kd_position")]

@@ -151,6 +151,12 @@ struct hb_ctx {
   ProfileDrawBatch profile_draw{};
   hb_profile_draw_config profile_draw_cfg{};
   bool profile_draw_on = false;
+  // field draw at respawn (hb_plant_set_field_draw): field_draw_on while a configuration is in force (field_on is then true as well, and
+  // field_hdr_host / field_z_host / gfield_hdr_host / gfield_z_host are stale: field_draw_refresh_host brings them up to date);
+  // field_draw_cfg holds the direction already normalised; the arrays are allocated by the first call that gives a configuration
+  FieldDrawBatch field_draw{};
+  hb_field_draw_config field_draw_cfg{};
+  bool field_draw_on = false;
   // reference generation (allocated on the first hb_refgen_reset)
   RefgenBatch rg{};
   hb_refgen_config rg_cfg{};
@@ -472,7 +478,7 @@ static int32_t resident_write(hb_ctx* ctx, hipStream_t s, bool fence, F&& launch
 
 extern "C" {
 
-int32_t hb_version(void) { return 302; }
+int32_t hb_version(void) { return 303; }
 
 const char* hb_last_error(const hb_ctx* ctx) { return ctx ? ctx->err.c_str() : g_create_error.c_str(); }
 

@@ -1,7 +1,7 @@
 // Host side, part 6: the episode layer on top of the plant, each entry below the ones it depends on: the per-instance episode record
 // (hb_plant_set / get_episode), the respawn of ended instances (hb_plant_set_respawn, hb_plant_respawn, hb_plant_get_respawn) and what is
-// drawn at respawn: the scenario (hb_plant_set / get_scenario, hb_plant_get_scenario_log) and the profile (hb_plant_set / get_profile_draw,
-// hb_plant_get_profile_draw_log).  The static helpers they share with the plant entries stand at the head of hb_api_plant.hpp.
+// drawn at respawn: the scenario (hb_plant_set / get_scenario, hb_plant_get_scenario_log), the profile (hb_plant_set / get_profile_draw,
+// hb_plant_get_profile_draw_log) and the height field (hb_plant_set / get_field_draw, hb_plant_get_field_draw_log).  The static helpers they share with the plant entries stand at the head of hb_api_plant.hpp.
 #pragma once
 
 extern "C" {
@@ -16,7 +16,8 @@ int32_t hb_plant_set_episode(hb_ctx* ctx, const hb_episode_config* cfg) {
   if (!cfg) {
     ctx->episode_on = false;
     ctx->respawn_on = false;   // the respawn reads its decision from the record
-    HB_TRY(profile_draw_off(ctx));   // ... and the scenario and the profile are drawn at respawn
+    HB_TRY(profile_draw_off(ctx));   // ... and the scenario, the profile and the field are drawn at respawn
+    HB_TRY(field_draw_off(ctx));
     return scenario_off(ctx);
   }
   EpisodeBatch& e = ctx->episode;
@@ -60,7 +61,8 @@ int32_t hb_plant_set_respawn(hb_ctx* ctx, const hb_respawn_config* cfg, const do
       ctx->respawn_on = false;
       ctx->rs_rg_due = ctx->rs_mpc_due = false;   // (flags still pending are dropped: the next configuration starts with none)
     }
-    HB_TRY(profile_draw_off(ctx));   // the scenario and the profile are drawn at respawn
+    HB_TRY(profile_draw_off(ctx));   // the scenario, the profile and the field are drawn at respawn
+    HB_TRY(field_draw_off(ctx));
     return scenario_off(ctx);
   }
   RespawnBatch& r = ctx->respawn;
@@ -88,6 +90,8 @@ int32_t hb_plant_respawn(hb_ctx* ctx) {
   const EstBatch est = ctx->est_ready ? ctx->est : EstBatch{};
   // (on a profile the kernel takes its plane from the facet it locates and writes ProfileBatch::base: `ter`, which would be that array, is not passed)
   const bool on_profile = ctx->contact_cfg.mode == 1 && ctx->profile_on;
+  // (likewise on a height field: the kernel's field form writes FieldBatch::base)
+  const bool on_field = ctx->contact_cfg.mode == 1 && ctx->field_on;
   // a writer of the resident observation, and of the pending flags and the gait state the MPC stream reads: always between the two
   // ordering points
   HB_TRY(resident_write(ctx, s, true, [&] {
@@ -101,9 +105,16 @@ int32_t hb_plant_respawn(hb_ctx* ctx) {
       hipLaunchKernelGGL(k_plant_profile_draw, dim3(ctx->B), dim3(64), 0, s, ctx->profile_draw, ctx->profile_draw_cfg, ctx->respawn_cfg, ctx->respawn,
                          ctx->episode, ctx->profile, ctx->profile_draw_cfg.follow_map && ctx->ground_on ? ctx->ground.map : nullptr,
                          ctx->contact_cfg.ground_z);
-    hipLaunchKernelGGL(k_plant_respawn, dim3(ctx->B), dim3(64), 0, s, ctx->respawn, ctx->respawn_cfg, ctx->episode, ctx->plant, cb, jb, ab, est,
-                       ctx->gait, ctx->gait_cfg, ctx->gait_on ? 1 : 0, on_profile ? nullptr : ter, d0, ctx->dmodel, ctx->jc_estop, ctx->w.rbd,
-                       ctx->b.x0, on_profile ? ctx->profile : ProfileBatch{});
+    if (ctx->field_draw_on)   // the height field of the episode that starts, from the same decision (the field map follows where asked and in force)
+      hipLaunchKernelGGL(k_plant_field_draw, dim3(ctx->B), dim3(64), 0, s, ctx->field_draw, ctx->field_draw_cfg, ctx->respawn_cfg, ctx->respawn,
+                         ctx->episode, ctx->field, field_draw_follows(ctx) ? ctx->gfield : GroundFieldBatch{}, ctx->contact_cfg.ground_z);
+    if (on_field)
+      hipLaunchKernelGGL(k_plant_respawn_field, dim3(ctx->B), dim3(64), 0, s, ctx->respawn, ctx->respawn_cfg, ctx->episode, ctx->plant, cb, jb, ab,
+                         est, ctx->gait, ctx->gait_cfg, ctx->gait_on ? 1 : 0, d0, ctx->dmodel, ctx->jc_estop, ctx->w.rbd, ctx->b.x0, ctx->field);
+    else
+      hipLaunchKernelGGL(k_plant_respawn, dim3(ctx->B), dim3(64), 0, s, ctx->respawn, ctx->respawn_cfg, ctx->episode, ctx->plant, cb, jb, ab, est,
+                         ctx->gait, ctx->gait_cfg, ctx->gait_on ? 1 : 0, on_profile ? nullptr : ter, d0, ctx->dmodel, ctx->jc_estop, ctx->w.rbd,
+                         ctx->b.x0, on_profile ? ctx->profile : ProfileBatch{});
   }));
   std::lock_guard<std::mutex> lk(ctx->mtx);
   ctx->rs_rg_due = ctx->rs_mpc_due = true;
@@ -181,6 +192,7 @@ int32_t hb_plant_set_profile_draw(hb_ctx* ctx, const hb_profile_draw_config* cfg
   HB_ENTER_ARGS(false);
   if (!cfg && !ctx->profile_draw_on) return HB_OK;
   HB_TRY(contact_ready(ctx, "hb_plant_set_profile_draw"));
+  HB_FAIL_IF(cfg && ctx->field_draw_on, HB_ERR_STATE, "hb_plant_set_profile_draw: a field draw is in force (hb_plant_set_field_draw): turn it off first");
   HB_FAIL_IF(cfg && ctx->field_on, HB_ERR_STATE, "hb_plant_set_profile_draw: a height field is in force (hb_plant_set_terrain_field): turn it off first");
   HB_FAIL_IF(cfg && !ctx->respawn_on, HB_ERR_STATE, "hb_plant_set_profile_draw: no respawn configuration in force (hb_plant_set_respawn): the profile is drawn at respawn");
   HB_FAIL_IF(cfg && ctx->scenario_on && (ctx->scenario_cfg.channels & (HB_SC_SLOPE | HB_SC_MU)), HB_ERR_STATE, "hb_plant_set_profile_draw: the scenario in force draws the terrain (hb_plant_set_scenario with HB_SC_SLOPE or HB_SC_MU): turn it off first");
@@ -237,6 +249,66 @@ int32_t hb_plant_get_profile_draw_log(hb_ctx* ctx, int32_t* count, double* log) 
   ProfileDrawBatch& d = ctx->profile_draw;
   HB_TRY(pull(ctx, count, d, d.count, whole(ctx)));
   return log_read(ctx, log, d.log, d.log_cap, ctx->profile_draw_cfg.log_capacity, HB_PD_LOG_W);
+}
+
+// ---- field draw at respawn (include/hunter_hip.h above hb_plant_set_field_draw) -----------------------------------------------------------
+int32_t hb_plant_set_field_draw(hb_ctx* ctx, const hb_field_draw_config* cfg) {
+  HB_ENTER_ARGS(false);
+  if (!cfg && !ctx->field_draw_on) return HB_OK;
+  HB_TRY(contact_ready(ctx, "hb_plant_set_field_draw"));
+  HB_FAIL_IF(cfg && !ctx->respawn_on, HB_ERR_STATE, "hb_plant_set_field_draw: no respawn configuration in force (hb_plant_set_respawn): the field is drawn at respawn");
+  HB_FAIL_IF(cfg && ctx->profile_draw_on, HB_ERR_STATE, "hb_plant_set_field_draw: a profile draw is in force (hb_plant_set_profile_draw): turn it off first");
+  HB_FAIL_IF(cfg && ctx->scenario_on && (ctx->scenario_cfg.channels & (HB_SC_SLOPE | HB_SC_MU)), HB_ERR_STATE, "hb_plant_set_field_draw: the scenario in force draws the terrain (hb_plant_set_scenario with HB_SC_SLOPE or HB_SC_MU): turn it off first");
+  HB_TRY(refuse_config(ctx, "hb_plant_set_field_draw", cfg ? field_draw_config_refusal(*cfg) : nullptr));
+  HB_FAIL_IF(cfg && cfg->follow_map && ctx->ground_on, HB_ERR_STATE, "hb_plant_set_field_draw: follow_map while a profile map is in force (hb_ground_set_profile): the draw writes field maps, set the zero field map first (hb_ground_set_field)");
+  HB_FAIL_IF(cfg && cfg->follow_map && !ctx->gfield_on, HB_ERR_STATE, "hb_plant_set_field_draw: follow_map without a field map in force (hb_ground_set_field): set the zero field map first");
+  HB_FAIL_IF(cfg && !(std::fabs(ctx->contact_cfg.ground_z) <= FD_REACH), HB_ERR_STATE, "hb_plant_set_field_draw: |ground_z| of the contact model above 1e3: the heights are drawn around ground_z");
+  HB_ENTER_DEVICE();
+  HB_HIP(hipStreamSynchronize(ctx->s_wbc));  // (a respawn or a step in flight still runs under the configuration it was launched with)
+  if (!cfg) return field_draw_off(ctx);
+  const size_t B = ctx->B;
+  hb_field_draw_config K = *cfg;
+  profile_direction(cfg->dir, K.dir);
+  // the level ground every instance starts on: the configured grid around its spawn point, at ground_z
+  std::vector<double> qs(B * 16), hdr(B * Field::stored), z(B * Field::nz), ghdr(cfg->follow_map ? B * GroundField::size : 0),
+      gz(cfg->follow_map ? B * GroundField::nz : 0);
+  HB_TRY(pull(ctx, qs.data(), ctx->respawn, ctx->respawn.q_spawn, whole(ctx)));
+  const double mu4[HB_NC] = {ctx->contact_cfg.mu, ctx->contact_cfg.mu, ctx->contact_cfg.mu, ctx->contact_cfg.mu};
+  for (size_t i = 0; i < B; ++i) {
+    double org[2], sq[2];
+    field_draw_origin(K, K.dir, qs.data() + 16 * i, org, sq);
+    if (!(std::fabs(sq[0]) <= FD_REACH && std::fabs(sq[1]) <= FD_REACH))
+      return refuse_instance(ctx, HB_ERR_STATE, "hb_plant_set_field_draw", i, "a spawn point further than 1e3 along or across dir", "configuration");
+    field_draw_flat(K, ctx->contact_cfg.ground_z, z.data() + i * Field::nz, cfg->follow_map ? gz.data() + i * GroundField::nz : nullptr);
+    field_compose(K.n_nodes, K.dir, org, K.spacing, z.data() + i * Field::nz, mu4, hdr.data() + i * Field::stored);
+    if (cfg->follow_map) ground_field_compose(K.n_nodes, K.dir, org, K.spacing, ghdr.data() + i * GroundField::size);
+  }
+  HB_TRY(field_draw_off(ctx));   // (a configuration in force hands its records back first; a failure below leaves it off)
+  FieldDrawBatch& d = ctx->field_draw;
+  HB_TRY(ensure_fields(ctx, d));
+  HB_TRY(log_grow(ctx, d.log, d.log_cap, cfg->log_capacity, HB_FD_LOG_W));
+  HB_TRY(field_install(ctx, hdr, z, cfg->follow_map ? &ghdr : nullptr, &gz));   // the level field replaces a terrain or a profile
+  ctx->field_draw_cfg = K;
+  ctx->field_draw_on = true;
+  return field_draw_start(ctx, true);
+}
+
+int32_t hb_plant_get_field_draw(hb_ctx* ctx, double* row) {
+  HB_ENTER_ARGS(false);
+  HB_FAIL_IF(!ctx->field_draw_on, HB_ERR_STATE, "hb_plant_get_field_draw: no field draw in force (hb_plant_set_field_draw)");
+  HB_ENTER_DEVICE();
+  HB_HIP(hipStreamSynchronize(ctx->s_wbc));
+  return pull(ctx, row, ctx->field_draw, ctx->field_draw.row, whole(ctx));
+}
+
+int32_t hb_plant_get_field_draw_log(hb_ctx* ctx, int32_t* count, double* log) {
+  HB_ENTER_ARGS(false);
+  HB_FAIL_IF(!ctx->field_draw_on, HB_ERR_STATE, "hb_plant_get_field_draw_log: no field draw in force (hb_plant_set_field_draw)");
+  HB_ENTER_DEVICE();
+  HB_HIP(hipStreamSynchronize(ctx->s_wbc));
+  FieldDrawBatch& d = ctx->field_draw;
+  HB_TRY(pull(ctx, count, d, d.count, whole(ctx)));
+  return log_read(ctx, log, d.log, d.log_cap, ctx->field_draw_cfg.log_capacity, HB_FD_LOG_W);
 }
 
 }  // extern "C"

@@ -18,6 +18,7 @@ int32_t hb_ground_set_profile(hb_ctx* ctx, const int32_t* n_knots, const double*
   HB_ENTER_ARGS(false);
   const bool on = n_knots || dir || knots;
   HB_FAIL_IF(on && !(n_knots && dir && knots), HB_ERR_ARG, "hb_ground_set_profile: give n_knots, dir and knots, or none of them to switch the map off (the map in force is kept)");
+  HB_FAIL_IF(on && ctx->field_draw_on && ctx->field_draw_cfg.follow_map, HB_ERR_STATE, "hb_ground_set_profile: the field draw in force writes the field map (hb_plant_set_field_draw, follow_map): turn it off first");
   const size_t B = ctx->B;
   std::vector<double> rec(on ? B * Ground::size : 0), kn(on ? B * HB_PROFILE_MAX_KNOTS * 2 : 0);
   for (size_t i = 0; i < B && on; ++i) {
@@ -95,6 +96,11 @@ int32_t hb_ground_get_field(hb_ctx* ctx, int32_t* n_nodes, double* dir, double* 
   HB_ENTER_ARGS(false);
   HB_FAIL_IF(!ctx->gfield_on, HB_ERR_STATE, ctx->ground_on ? "hb_ground_get_field: the map in force is a profile map (hb_ground_get_profile)"
                                                             : "hb_ground_get_field: no field map in force (hb_ground_set_field)");
+  if (field_draw_follows(ctx)) {   // the device draws the records: the host image is stale
+    HB_ENTER_DEVICE();
+    HB_HIP(hipStreamSynchronize(ctx->s_wbc));
+    HB_TRY(field_draw_refresh_host(ctx));
+  }
   for (size_t i = 0; i < size_t(ctx->B); ++i) {
     const double* h = ctx->gfield_hdr_host.data() + i * GroundField::size;
     if (n_nodes) { n_nodes[2 * i] = int32_t(h[GroundField::nu]); n_nodes[2 * i + 1] = int32_t(h[GroundField::nw]); }

@@ -308,6 +308,67 @@ static int32_t profile_install(hb_ctx* ctx, std::vector<double>& rec, std::vecto
   return contact_forget_warm_start(ctx);
 }
 
+// ---- field draw at respawn: what the plant entries share with hb_plant_set_field_draw ------------------------------------------------------
+// No finished episode logged in every instance; with `rows`, the parameter rows back to "before the first draw" (zero) too.  Synchronous;
+// the caller has drained ctx->s_wbc.
+static int32_t field_draw_start(hb_ctx* ctx, bool rows) {
+  FieldDrawBatch& d = ctx->field_draw;
+  if (rows) HB_TRY(zero_field(ctx, d, d.row));
+  HB_TRY(zero_field(ctx, d, d.count));
+  return log_zero(ctx, d.log, d.log_cap, HB_FD_LOG_W);
+}
+
+// whether the controller's field map follows the draw in force
+static bool field_draw_follows(const hb_ctx* ctx) { return ctx->field_draw_on && ctx->field_draw_cfg.follow_map && ctx->gfield_on; }
+
+// The host images of the records the device has been drawing, from the device: the field's headers and heights and, where the map
+// follows, the map's.  The caller has drained ctx->s_wbc.
+static int32_t field_draw_refresh_host(hb_ctx* ctx) {
+  if (!ctx->field_draw_on) return HB_OK;
+  HB_TRY(pull(ctx, ctx->field_hdr_host.data(), ctx->field, ctx->field.hdr, whole(ctx)));
+  HB_TRY(pull(ctx, ctx->field_z_host.data(), ctx->field, ctx->field.z, whole(ctx)));
+  if (!field_draw_follows(ctx)) return HB_OK;
+  HB_TRY(pull(ctx, ctx->gfield_hdr_host.data(), ctx->gfield, ctx->gfield.hdr, whole(ctx)));
+  return pull(ctx, ctx->gfield_z_host.data(), ctx->gfield, ctx->gfield.z, whole(ctx));
+}
+
+// Draw off: field and map stay in force as last drawn (the host images follow the device).  The caller has drained ctx->s_wbc.
+static int32_t field_draw_off(hb_ctx* ctx) {
+  if (!ctx->field_draw_on) return HB_OK;
+  HB_TRY(field_draw_refresh_host(ctx));
+  ctx->field_draw_on = false;
+  return HB_OK;
+}
+
+// Installs the field records hdr[B][Field::stored] and heights z[B][Field::nz] as the ground in force: records to the device, host images,
+// the facets under the plant's present state, one ground at a time (the field replaces a terrain and a profile), no warm start from the
+// ground of before.  With a map (ghdr, gz) the field map of the controller follows.  The caller has drained ctx->s_wbc; the vectors are
+// moved from.
+static int32_t field_install(hb_ctx* ctx, std::vector<double>& hdr, std::vector<double>& z, std::vector<double>* ghdr = nullptr,
+                             std::vector<double>* gz = nullptr) {
+  FieldBatch& t = ctx->field;
+  HB_TRY(ensure_fields(ctx, t));
+  HB_TRY(push(ctx, hdr.data(), t, t.hdr, whole(ctx)));
+  HB_TRY(push(ctx, z.data(), t, t.z, whole(ctx)));
+  ctx->field_hdr_host = std::move(hdr);
+  ctx->field_z_host = std::move(z);
+  if (ghdr) {
+    HB_TRY(hb_sync(ctx));   // (a pass in flight on the MPC stream still runs on the map it was launched with)
+    HB_TRY(push(ctx, ghdr->data(), ctx->gfield, ctx->gfield.hdr, whole(ctx)));
+    HB_TRY(push(ctx, gz->data(), ctx->gfield, ctx->gfield.z, whole(ctx)));
+    ctx->gfield_hdr_host = std::move(*ghdr);
+    ctx->gfield_z_host = std::move(*gz);
+  }
+  std::vector<double> q(size_t(ctx->B) * 16);
+  HB_TRY(pull(ctx, q.data(), ctx->plant, ctx->plant.q, whole(ctx)));
+  HB_TRY(field_locate(ctx, q.data(), ctx->s_wbc));
+  ctx->terrain_on = false;   // one ground at a time: the field replaces a terrain and a profile
+  ctx->profile_on = false;
+  ctx->field_on = true;
+  HB_TRY(modelvar_level(ctx));
+  return contact_forget_warm_start(ctx);
+}
+
 extern "C" {
 
 int32_t hb_plant_reset(hb_ctx* ctx, const double* q0, const double* v0, double baumgarte, double eps) {
@@ -329,6 +390,10 @@ int32_t hb_plant_reset(hb_ctx* ctx, const double* q0, const double* v0, double b
     HB_HIP(hipStreamSynchronize(ctx->s_wbc));
     HB_TRY(profile_draw_refresh_host(ctx));
   }
+  if (ctx->field_draw_on) {   // likewise the field the device draws
+    HB_HIP(hipStreamSynchronize(ctx->s_wbc));
+    HB_TRY(field_draw_refresh_host(ctx));
+  }
   if (ctx->profile_on) HB_TRY(profile_locate(ctx, q0, ctx->s_wbc));   // the facets under the reset state
   if (ctx->field_on) HB_TRY(field_locate(ctx, q0, ctx->s_wbc));
   if (ctx->episode_on) HB_TRY(episode_start(ctx, ctx->s_wbc));   // the record restarts from the reset state
@@ -336,6 +401,7 @@ int32_t hb_plant_reset(hb_ctx* ctx, const double* q0, const double* v0, double b
   HB_HIP(hipStreamSynchronize(ctx->s_wbc));
   if (ctx->scenario_on) HB_TRY(scenario_start(ctx, false));   // the log is empty, nobody has a push; terrain, models and scen stay as last drawn
   if (ctx->profile_draw_on) HB_TRY(profile_draw_start(ctx, false));   // the log is empty; profile, map and rows stay as last drawn
+  if (ctx->field_draw_on) HB_TRY(field_draw_start(ctx, false));       // ... and so do field, map and rows of a field draw
   ctx->plant_ready = true;
   return HB_OK;
 }
@@ -453,6 +519,7 @@ int32_t hb_plant_set_contact_model(hb_ctx* ctx, const hb_contact_config* cfg) {
   HB_FAIL_IF(!ctx->plant_ready, HB_ERR_STATE, "hb_plant_set_contact_model: call hb_plant_reset first");
   HB_FAIL_IF(cfg && !contact_config_valid(*cfg), HB_ERR_ARG, "hb_plant_set_contact_model: mode 0 / 1, sweeps 1 .. 10000, mu >= 0, erp in [0, 1], tol >= 0, fall_height >= 0, every field finite and `reserved` 0");
   HB_FAIL_IF(cfg && cfg->mode == 1 && ctx->profile_draw_on && !(std::fabs(cfg->ground_z) <= PD_REACH), HB_ERR_ARG, "hb_plant_set_contact_model: |ground_z| above 1e3 while a profile draw is in force (hb_plant_set_profile_draw): its knots are drawn around ground_z");
+  HB_FAIL_IF(cfg && cfg->mode == 1 && ctx->field_draw_on && !(std::fabs(cfg->ground_z) <= FD_REACH), HB_ERR_ARG, "hb_plant_set_contact_model: |ground_z| above 1e3 while a field draw is in force (hb_plant_set_field_draw): its heights are drawn around ground_z");
   HB_ENTER_DEVICE();
   HB_HIP(hipStreamSynchronize(ctx->s_wbc));  // (a step in flight still runs under the model it was launched with)
   const bool ground = cfg && cfg->mode == 1;
@@ -466,6 +533,7 @@ int32_t hb_plant_set_contact_model(hb_ctx* ctx, const hb_contact_config* cfg) {
   }
   if (!ground) HB_TRY(scenario_off(ctx));   // the scenario belongs to contact model 1 (and gives the wrench back)
   if (!ground) HB_TRY(profile_draw_off(ctx));   // ... and so does the profile draw
+  if (!ground) HB_TRY(field_draw_off(ctx));     // ... and the field draw
   ctx->contact_cfg = ground ? *cfg : hb_contact_config{};
   if (!ground) ctx->terrain_on = false;   // the terrain belongs to contact model 1
   if (!ground) ctx->profile_on = false;   // ... and so does the terrain profile
@@ -550,6 +618,7 @@ int32_t hb_plant_set_terrain(hb_ctx* ctx, const double* plane, const double* mu)
   HB_TRY(contact_ready(ctx, "hb_plant_set_terrain"));
   HB_FAIL_IF(!plane && !mu && ctx->scenario_on && (ctx->scenario_cfg.channels & (HB_SC_SLOPE | HB_SC_MU)), HB_ERR_STATE, "hb_plant_set_terrain: the scenario in force draws the terrain (hb_plant_set_scenario): turn it off first");
   HB_FAIL_IF(ctx->profile_draw_on, HB_ERR_STATE, "hb_plant_set_terrain: the profile draw in force draws the ground (hb_plant_set_profile_draw): turn it off first");
+  HB_FAIL_IF(ctx->field_draw_on, HB_ERR_STATE, "hb_plant_set_terrain: the field draw in force draws the ground (hb_plant_set_field_draw): turn it off first");
   const size_t B = ctx->B;
   std::vector<double> rec(B * Terrain::size);
   for (size_t i = 0; i < B && (plane || mu); ++i) {
@@ -617,6 +686,7 @@ int32_t hb_plant_set_terrain_profile(hb_ctx* ctx, const int32_t* n_knots, const 
   HB_FAIL_IF(on && !(n_knots && dir && knots), HB_ERR_ARG, "hb_plant_set_terrain_profile: give n_knots, dir and knots, or none of them to switch the profile off (the profile in force is kept)");
   HB_FAIL_IF(!on && mu, HB_ERR_ARG, "hb_plant_set_terrain_profile: friction coefficients without a profile (the profile in force is kept)");
   HB_FAIL_IF(ctx->profile_draw_on, HB_ERR_STATE, "hb_plant_set_terrain_profile: the profile draw in force draws the ground (hb_plant_set_profile_draw): turn it off first");
+  HB_FAIL_IF(ctx->field_draw_on, HB_ERR_STATE, "hb_plant_set_terrain_profile: the field draw in force draws the ground (hb_plant_set_field_draw): turn it off first");
   HB_FAIL_IF(on && ctx->respawn_on, HB_ERR_STATE, "hb_plant_set_terrain_profile: a respawn configuration is in force (hb_plant_set_respawn): no respawn on a profile, turn it off first");
   HB_FAIL_IF(on && ctx->scenario_on && (ctx->scenario_cfg.channels & (HB_SC_SLOPE | HB_SC_MU)), HB_ERR_STATE, "hb_plant_set_terrain_profile: the scenario in force draws the terrain (hb_plant_set_scenario): turn it off first");
   const size_t B = ctx->B;
@@ -667,6 +737,7 @@ int32_t hb_plant_set_terrain_field(hb_ctx* ctx, const int32_t* n_nodes, const do
   HB_FAIL_IF(on && !(n_nodes && dir && origin && spacing && heights), HB_ERR_ARG, "hb_plant_set_terrain_field: give n_nodes, dir, origin, spacing and heights, or none of them to switch the field off (the ground in force is kept)");
   HB_FAIL_IF(!on && mu, HB_ERR_ARG, "hb_plant_set_terrain_field: friction coefficients without a field (the ground in force is kept)");
   HB_FAIL_IF(ctx->profile_draw_on, HB_ERR_STATE, "hb_plant_set_terrain_field: the profile draw in force draws the ground (hb_plant_set_profile_draw): turn it off first");
+  HB_FAIL_IF(ctx->field_draw_on, HB_ERR_STATE, "hb_plant_set_terrain_field: the field draw in force draws the ground (hb_plant_set_field_draw): turn it off first");
   HB_FAIL_IF(on && ctx->respawn_on, HB_ERR_STATE, "hb_plant_set_terrain_field: a respawn configuration is in force (hb_plant_set_respawn): no respawn on a field, turn it off first");
   HB_FAIL_IF(on && ctx->scenario_on && (ctx->scenario_cfg.channels & (HB_SC_SLOPE | HB_SC_MU)), HB_ERR_STATE, "hb_plant_set_terrain_field: the scenario in force draws the terrain (hb_plant_set_scenario): turn it off first");
   const size_t B = ctx->B;
@@ -682,20 +753,8 @@ int32_t hb_plant_set_terrain_field(hb_ctx* ctx, const int32_t* n_nodes, const do
   }
   HB_ENTER_DEVICE();
   HB_HIP(hipStreamSynchronize(ctx->s_wbc));  // (a step in flight still runs on the ground it was launched with)
-  if (on) {
-    FieldBatch& t = ctx->field;
-    HB_TRY(ensure_fields(ctx, t));
-    HB_TRY(push(ctx, hdr.data(), t, t.hdr, whole(ctx)));
-    HB_TRY(push(ctx, z.data(), t, t.z, whole(ctx)));
-    ctx->field_hdr_host = std::move(hdr);
-    ctx->field_z_host = std::move(z);
-    std::vector<double> q(B * 16);
-    HB_TRY(pull(ctx, q.data(), ctx->plant, ctx->plant.q, whole(ctx)));
-    HB_TRY(field_locate(ctx, q.data(), ctx->s_wbc));
-    ctx->terrain_on = false;   // one ground at a time: the field replaces a terrain and a profile
-    ctx->profile_on = false;
-  }
-  ctx->field_on = on;
+  if (on) return field_install(ctx, hdr, z);
+  ctx->field_on = false;
   HB_TRY(modelvar_level(ctx));
   return contact_forget_warm_start(ctx);
 }
@@ -705,9 +764,10 @@ int32_t hb_plant_get_terrain_field(hb_ctx* ctx, int32_t* n_nodes, double* dir, d
   HB_ENTER_ARGS(false);
   HB_TRY(contact_ready(ctx, "hb_plant_get_terrain_field"));
   HB_FAIL_IF(!ctx->field_on, HB_ERR_STATE, "hb_plant_get_terrain_field: no height field in force (hb_plant_set_terrain_field)");
-  if (facet) {
+  if (facet || ctx->field_draw_on) {
     HB_ENTER_DEVICE();
     HB_HIP(hipStreamSynchronize(ctx->s_wbc));
+    HB_TRY(field_draw_refresh_host(ctx));   // (the device draws the records: the host image is stale)
     HB_TRY(pull(ctx, facet, ctx->field, ctx->field.sel, whole(ctx)));
   }
   for (size_t i = 0; i < size_t(ctx->B); ++i) {

@@ -395,6 +395,21 @@ HB_HD int field_facet(const double* hdr, const double* __restrict__ z, const dou
     for (int k = 0; k < Profile::rec; ++k) rec[k] = u + w;
   return 2 * (i * (nw - 1) + j) + t;
 }
+// The stored record r[Field::stored] of a VALID field (n[2] node counts, the unit direction a, origin, spacing, the stored heights z with
+// the pitch HB_FIELD_MAX_NODES, mu[4]): what field_record composes once it has accepted them, and what k_plant_field_draw composes for a
+// drawn field (one lane: the record is 22 stores and one facet).  r is written whole; its head is the facet under the world origin until
+// a state is located.
+HB_HD void field_compose(const int* n, const double* a, const double* org, const double* step, const double* __restrict__ z, const double* mu,
+                         double* r) {
+  for (int k = 0; k < Field::stored; ++k) r[k] = 0.0;
+  r[Field::dir] = a[0]; r[Field::dir + 1] = a[1];
+  r[Field::org] = org[0]; r[Field::org + 1] = org[1];
+  r[Field::step] = step[0]; r[Field::step + 1] = step[1];
+  r[Field::nu] = double(n[0]); r[Field::nw] = double(n[1]);
+  for (int c = 0; c < HB_NC; ++c) r[Field::head + Terrain::mu + c] = mu[c];
+  const double x0[3] = {0.0, 0.0, 0.0};
+  field_facet(r, z, x0, r + Field::head);   // (until a state is located: the facet under the world origin)
+}
 // Host: the stored record r[Field::stored] of one instance from its field (n[2] node counts, direction, origin, spacing, heights with the
 // pitch HB_FIELD_MAX_NODES, mu[4] or null for cfg_mu), or the reason it is refused (r is then not written).
 inline const char* field_record(const int* n, const double* dir, const double* org, const double* step, const double* z, const double* mu,
@@ -424,14 +439,9 @@ inline const char* field_record(const int* n, const double* dir, const double* o
     mu4[c] = mu ? mu[c] : cfg_mu;
     if (!(std::isfinite(mu4[c]) && mu4[c] >= 0.0)) return "a friction coefficient that is negative or not finite";
   }
-  for (int k = 0; k < Field::stored; ++k) r[k] = 0.0;
-  profile_direction(dir, r + Field::dir);
-  r[Field::org] = org[0]; r[Field::org + 1] = org[1];
-  r[Field::step] = step[0]; r[Field::step + 1] = step[1];
-  r[Field::nu] = double(n[0]); r[Field::nw] = double(n[1]);
-  for (int c = 0; c < HB_NC; ++c) r[Field::head + Terrain::mu + c] = mu4[c];
-  const double x0[3] = {0.0, 0.0, 0.0};
-  field_facet(r, z, x0, r + Field::head);   // (until a state is located: the facet under the world origin)
+  double a[2];
+  profile_direction(dir, a);
+  field_compose(n, a, org, step, z, mu4, r);
   return nullptr;
 }
 // profile_select for a field: point c takes the record of the facet under feet[3 c ..] into its slot of act, one lane per point.

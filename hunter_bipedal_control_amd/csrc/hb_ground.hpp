@@ -65,13 +65,21 @@ HB_HD double ground_height(const double* g, double x, double y, int* seg = nullp
 struct GroundField {
   static constexpr int dir = 0, org = 2, step = 4, nu = 6, nw = 7, size = 8, pitch = Field::pitch, nz = Field::nz;
 };
+// The header h[GroundField::size] of a VALID map (node counts, the unit direction a, origin, spacing): what ground_field_record stores
+// once it has accepted them, and what k_plant_field_draw stores for the map that follows a drawn field.
+HB_HD void ground_field_compose(const int* n, const double* a, const double* org, const double* step, double* h) {
+  h[GroundField::dir] = a[0]; h[GroundField::dir + 1] = a[1];
+  h[GroundField::org] = org[0]; h[GroundField::org + 1] = org[1];
+  h[GroundField::step] = step[0]; h[GroundField::step + 1] = step[1];
+  h[GroundField::nu] = double(n[0]); h[GroundField::nw] = double(n[1]);
+}
 // Host: the header h[GroundField::size] of one instance from its map, or the reason it is refused (h is then not written).  The checks
 // are field_record's, the triangle bound included (the routine is run on the map, so a plant field is always a valid map); the direction
 // is normalised by the same division.
 inline const char* ground_field_record(const int* n, const double* dir, const double* org, const double* step, const double* z, double* h) {
   double fld[Field::stored];
   if (const char* why = field_record(n, dir, org, step, z, nullptr, 0.0, fld)) return why;
-  for (int k = 0; k < GroundField::size; ++k) h[k] = fld[Field::dir + k];
+  ground_field_compose(n, fld + Field::dir, org, step, h);
   return nullptr;
 }
 // G(x, y) of the field map (h: its header, z: its heights): the cell (i, j), the fractions and the triangle are field_cell's, the ones

@@ -26,6 +26,7 @@
 #include "hb_respawn.hpp"
 #include "hb_scenario.hpp"
 #include "hb_profiledraw.hpp"
+#include "hb_fielddraw.hpp"
 #include "hb_layout.hpp"
 #include "hb_iterate.hpp"
 #include "hb_wavectx.hpp"
@@ -1368,10 +1369,15 @@ __global__ __launch_bounds__(64) void k_plant_episode(EpisodeBatch e, hb_episode
 // host's plane pointer would be pb.base, which this kernel writes): lane 0 places the state
 // vertically on the facets under its contact points and locates it (hb_profiledraw.hpp), the record starts over the facet under the base
 // origin, and seg[5] / base[14] of the instance are written with the rows.
-__global__ __launch_bounds__(64) void k_plant_respawn(RespawnBatch rs, hb_respawn_config K, EpisodeBatch e, PlantBatch p, ContactBatch cb, JointBatch jb,
-                                                      ActuatorBatch ab, EstBatch est, GaitBatch g, hb_gait_config GK, int gait_on,
-                                                      const double* __restrict__ ter, double d0, const DevModel* __restrict__ M, int* estop,
-                                                      double* res_rbd, double* res_x0, ProfileBatch pb) {
+// FIELD (k_plant_respawn_field): fb is the height field in force (ter null, pb without a profile): lane 0 places the state vertically on the
+// facets under its contact points and locates it (hb_fielddraw.hpp), the record starts over the facet under the base origin, and sel[5] /
+// base[14] of the instance are written with the rows.  The form without a field compiles nothing of it and stores what it always stored.
+template <bool FIELD>
+__device__ __forceinline__ void plant_respawn(const RespawnBatch& rs, const hb_respawn_config& K, const EpisodeBatch& e, const PlantBatch& p,
+                                              const ContactBatch& cb, const JointBatch& jb, const ActuatorBatch& ab, const EstBatch& est,
+                                              const GaitBatch& g, const hb_gait_config& GK, int gait_on, const double* __restrict__ ter, double d0,
+                                              const DevModel* __restrict__ M, int* estop, double* res_rbd, double* res_x0, const ProfileBatch& pb,
+                                              const FieldBatch& fb) {
   const int i = blockIdx.x;
   const DeviceCtx cx;
   int* irec = e.irec + HB_EP_NI * i;
@@ -1403,7 +1409,14 @@ __global__ __launch_bounds__(64) void k_plant_respawn(RespawnBatch rs, hb_respaw
     }
     respawn_perturb(K, rs.q_spawn + 16 * i, rs.v_spawn + 16 * i, draw, q, v);
     plant_feet(*M, q, feet);
-    if (pb.prof) {   // on a profile: vertically onto the facets under the points, then the locate of the placed state
+    if constexpr (FIELD) {   // on a height field: vertically onto the facets under the points, then the locate of the placed state
+      const double* fld = fb.hdr + size_t(Field::stored) * i;
+      const double* hts = fb.z + size_t(Field::nz) * i;
+      field_place(*M, K, fld, hts, q, feet);
+      field_locate_state(fld, hts, q, feet, seg, base);
+      for (int a = 0; a < 3; ++a) plane[a] = base[Terrain::T + 3 * a + 2];
+      plane[3] = base[Terrain::d];
+    } else if (pb.prof) {   // on a profile: vertically onto the facets under the points, then the locate of the placed state
       const double* pro = pb.prof + size_t(Profile::stored) * i;
       profile_place(*M, K, pro, q, feet);
       profile_locate_state(pro, q, feet, seg, base);
@@ -1441,10 +1454,83 @@ __global__ __launch_bounds__(64) void k_plant_respawn(RespawnBatch rs, hb_respaw
   r.res_rbd = res_rbd + HB_NRBD * i; r.res_x0 = res_x0 + HB_NX * i;
   r.rg_pending = rs.rg_pending + i; r.mpc_pending = rs.mpc_pending + i;
   respawn_write(cx, r, q, v, feet, rbd, x0, plane);
-  if (pb.prof) {
+  if constexpr (FIELD) {
+    for (int c = cx.lane; c < HB_NC + 1; c += cx.nlanes) fb.sel[(HB_NC + 1) * i + c] = seg[c];
+    for (int k = cx.lane; k < Terrain::size; k += cx.nlanes) fb.base[size_t(Terrain::size) * i + k] = base[k];
+  } else if (pb.prof) {
     for (int c = cx.lane; c < HB_NC + 1; c += cx.nlanes) pb.seg[(HB_NC + 1) * i + c] = seg[c];
     for (int k = cx.lane; k < Terrain::size; k += cx.nlanes) pb.base[size_t(Terrain::size) * i + k] = base[k];
   }
+}
+__global__ __launch_bounds__(64) void k_plant_respawn(RespawnBatch rs, hb_respawn_config K, EpisodeBatch e, PlantBatch p, ContactBatch cb, JointBatch jb,
+                                                      ActuatorBatch ab, EstBatch est, GaitBatch g, hb_gait_config GK, int gait_on,
+                                                      const double* __restrict__ ter, double d0, const DevModel* __restrict__ M, int* estop,
+                                                      double* res_rbd, double* res_x0, ProfileBatch pb) {
+  plant_respawn<false>(rs, K, e, p, cb, jb, ab, est, g, GK, gait_on, ter, d0, M, estop, res_rbd, res_x0, pb, FieldBatch{});
+}
+__global__ __launch_bounds__(64) void k_plant_respawn_field(RespawnBatch rs, hb_respawn_config K, EpisodeBatch e, PlantBatch p, ContactBatch cb,
+                                                            JointBatch jb, ActuatorBatch ab, EstBatch est, GaitBatch g, hb_gait_config GK, int gait_on,
+                                                            double d0, const DevModel* __restrict__ M, int* estop, double* res_rbd, double* res_x0,
+                                                            FieldBatch fb) {
+  plant_respawn<true>(rs, K, e, p, cb, jb, ab, est, g, GK, gait_on, nullptr, d0, M, estop, res_rbd, res_x0, ProfileBatch{}, fb);
+}
+
+// ---- field draw at respawn (hb_plant_set_field_draw, hb_fielddraw.hpp): one wavefront per instance, ahead of k_plant_respawn_field ----------
+// Every lane reads k_plant_respawn's decision from the instance's still unchanged record (the same words: wave-uniform), and a wavefront
+// whose instance stays leaves after those loads.  A respawning wavefront appends the log row of the finished episode (all lanes, from the
+// row still in place), draws its two head blocks one per lane into LDS, lets lane 0 turn them into the row and the node parameters, and
+// then generates the 256 node blocks: lane l takes blocks l + 64 m, m = 0 .. 3, four consecutive nodes each, so that a pass of the
+// wavefront stores one contiguous 2 KB run of the plant's heights (and, with a map that follows, of the map's), 32 B per lane.  The heights
+// never sit in LDS.  Behind a workgroup barrier lane 0 composes the stored header (field_compose: the routine of the host setter; it
+// reads the four heights of the cell under the world origin back) and the map's; header, row and map header go out with consecutive
+// lanes on consecutive words.  gf: the controller's field map, or without arrays where it does not follow.
+__global__ __launch_bounds__(64) void k_plant_field_draw(FieldDrawBatch fd, hb_field_draw_config K, hb_respawn_config RK, RespawnBatch rs,
+                                                         EpisodeBatch e, FieldBatch fb, GroundFieldBatch gf, double ground_z) {
+  const int i = blockIdx.x;
+  const DeviceCtx cx;
+  const int* irec = e.irec + HB_EP_NI * i;
+  const int cause = respawn_decide(RK, irec);
+  if (cause == 0) return;
+  __shared__ double sh[FD_HEAD + 2 + HB_FD_N + 3 + Field::stored + GroundField::size];
+  double* u = sh;
+  double* a = u + FD_HEAD;
+  double* row_s = a + 2;
+  double* par_s = row_s + HB_FD_N;
+  double* hdr_s = par_s + 3;
+  double* map_s = hdr_s + Field::stored;
+  const int* itot = rs.itot + HB_RS_NI * i;
+  double* row = fd.row + HB_FD_N * i;
+  double* z = fb.z + size_t(Field::nz) * i;
+  double* gz = gf.z ? gf.z + size_t(GroundField::nz) * i : nullptr;
+  const uint32_t instance = RK.instance_offset + uint32_t(i), episode = uint32_t(itot[HB_RS_I_EPISODE_INDEX] + 1);
+  if (cx.lane < 2) a[cx.lane] = K.dir[cx.lane];
+  __syncthreads();
+  if (K.log_capacity > 0)
+    field_draw_log_append(cx, K.log_capacity, cause, a, irec, e.drec + HB_EP_ND * i, itot, row, fd.count + i,
+                          fd.log + size_t(i) * fd.log_cap * HB_FD_LOG_W);
+  if (cx.lane < FD_HEAD_BLOCKS) field_draw_block(K, instance, episode, cx.lane, u + 4 * cx.lane, nullptr);
+  __syncthreads();
+  if (cx.lane == 0) {
+    const FieldDrawPar par = field_draw_head(K, u, row_s);
+    par_s[0] = par.A; par_s[1] = par.p; par_s[2] = par.r;
+  }
+  __syncthreads();
+  FieldDrawPar par;
+  par.A = par_s[0]; par.p = par_s[1]; par.r = par_s[2];
+#pragma unroll 1
+  for (int m = 0; m < FD_NODE_BLOCKS / 64; ++m) field_draw_nodes(K, par, instance, episode, cx.lane + 64 * m, ground_z, z, gz);
+  __syncthreads();   // (a workgroup-scope fence: the heights lane 0 reads back below are the ones just stored)
+  if (cx.lane == 0) {
+    double org[2];
+    field_draw_origin(K, a, rs.q_spawn + 16 * i, org);
+    field_compose(K.n_nodes, a, org, K.spacing, z, row_s + HB_FD_MUS, hdr_s);
+    ground_field_compose(K.n_nodes, a, org, K.spacing, map_s);
+  }
+  __syncthreads();
+  for (int k = cx.lane; k < Field::stored; k += cx.nlanes) fb.hdr[size_t(Field::stored) * i + k] = hdr_s[k];
+  for (int k = cx.lane; k < HB_FD_N; k += cx.nlanes) row[k] = row_s[k];
+  if (gz)
+    for (int k = cx.lane; k < GroundField::size; k += cx.nlanes) gf.hdr[size_t(GroundField::size) * i + k] = map_s[k];
 }
 
 // ---- profile draw at respawn (hb_plant_set_profile_draw, hb_profiledraw.hpp): one wavefront per instance, ahead of k_plant_respawn --------

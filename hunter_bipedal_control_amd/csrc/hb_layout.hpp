@@ -15,6 +15,7 @@
 #include "hb_modelvar.hpp"
 #include "hb_ground.hpp"
 #include "hb_profiledraw.hpp"
+#include "hb_fielddraw.hpp"
 
 namespace {
 using namespace hb;
@@ -297,6 +298,22 @@ constexpr void fields(ProfileDrawBatch& d, size_t, F&& f) {
   HB_FIELD(d.row, HB_PD_N); HB_FIELD(d.knots, PD_KNOTS); HB_FIELD(d.count, 1);
 }
 
+// field draw at respawn (hb_plant_set_field_draw, hb_fielddraw.hpp), allocated by the first call that gives a configuration: the parameter
+// row of the ground every instance stands on (row) and the number of logged episodes (count).  The drawn fields themselves go to
+// FieldBatch::hdr / z and, with follow_map, GroundFieldBatch::hdr / z.  The log is [B][log_cap][HB_FD_LOG_W] with log_cap the largest
+// log_capacity set so far: a run-time extent, so the set call allocates it and the description does not name it.
+struct FieldDrawBatch {
+  int B;
+  int log_cap;
+  double* row;
+  int* count;
+  double* log;
+};
+template <class F>
+constexpr void fields(FieldDrawBatch& d, size_t, F&& f) {
+  HB_FIELD(d.row, HB_FD_N); HB_FIELD(d.count, 1);
+}
+
 // actuator loop of the plant and the simulator end of the LCM link (hb_plant_step_hybrid, hb_plant_step_lcm, hb_plant_sense_lcm),
 // allocated on the first call that needs them — the held-torque path needs none: the record of the last hybrid step, the staging of a
 // host command and the received command (pos_des vel_des kp kd ff, one array each), the timestamp filter, the wire images
@@ -438,6 +455,7 @@ static_assert(sizeof(EpisodeBatch) == 2 * sizeof(int) + (n_fields<EpisodeBatch>(
 static_assert(sizeof(RespawnBatch) == kPtr /*B*/ + n_fields<RespawnBatch>() * kPtr, "describe every array of RespawnBatch in fields()");
 static_assert(sizeof(ScenarioBatch) == 2 * sizeof(int) + (n_fields<ScenarioBatch>() + 1 /*log*/) * kPtr, "describe every array of ScenarioBatch in fields()");
 static_assert(sizeof(ProfileDrawBatch) == 2 * sizeof(int) + (n_fields<ProfileDrawBatch>() + 1 /*log*/) * kPtr, "describe every array of ProfileDrawBatch in fields()");
+static_assert(sizeof(FieldDrawBatch) == 2 * sizeof(int) + (n_fields<FieldDrawBatch>() + 1 /*log*/) * kPtr, "describe every array of FieldDrawBatch in fields()");
 static_assert(sizeof(ActuatorBatch) == kPtr /*B*/ + n_fields<ActuatorBatch>() * kPtr, "describe every array of ActuatorBatch in fields()");
 static_assert(sizeof(RefgenBatch) == kPtr /*B*/ + n_fields<RefgenBatch>() * kPtr + kPtr /*init_stance*/, "describe every array of RefgenBatch in fields()");
 static_assert(sizeof(GroundBatch) == kPtr /*B*/ + n_fields<GroundBatch>() * kPtr, "describe every array of GroundBatch in fields()");

@@ -251,7 +251,7 @@ class ResidentLoop:
                  t_gait_start: float = 0.3, joint_ik: bool = True, substeps: int = 4, static_schedule_until: float = 0.0,
                  device_gait: bool = False, use_estimator: bool = False, sensor_config=None, sensor_bias=None, contact_config=None,
                  joint_model=None, actuator: str = "held", terrain=None, episode=None, model_variation=None, respawn=None, scenario=None,
-                 ground_map=None, profile_draw=None):
+                 ground_map=None, profile_draw=None, field_draw=None):
         """static_schedule_until > 0: the mode schedules are uploaded once for [-1, static_schedule_until] (at most
         HB_MAX_EVENTS events) instead of a sliding window per MPC call — no per-call host work for large batches.
         device_gait: the device gait manager produces the windows; step() builds no per-instance list and uploads no schedule, and
@@ -301,13 +301,23 @@ class ResidentLoop:
         instance (hb_plant_set_profile_draw) — None: none; a dict of abi.make_profile_draw_config fields; an abi.HbProfileDrawConfig is
         taken as it is.  Needs respawn= and contact_config=, excludes terrain= (the draw owns the ground) and is set after the scenario;
         ground_map="draw" sets the zero map along the draw's direction and follow_map, so the controller's map follows every drawn
-        ground.  profile_draw() / profile_draw_log() read the current parameters and the log of the finished episodes."""
+        ground.  profile_draw() / profile_draw_log() read the current parameters and the log of the finished episodes.
+        field_draw: a height field (level, rough, tilted or both) composed on the device for every respawned instance
+        (hb_plant_set_field_draw) — None: none; a dict of abi.make_field_draw_config fields; an abi.HbFieldDrawConfig is taken as it is.
+        Needs respawn= and contact_config=, excludes terrain= and profile_draw= (one draw owns the ground) and is set after the scenario;
+        ground_map="draw" sets the zero field map over the draw's grid and follow_map, so the controller's map follows every drawn
+        field.  field_draw() / field_draw_log() read the current parameters and the log of the finished episodes.  (A field of the
+        host's, terrain=dict(field=...), stays refused beside respawn=.)"""
+        if field_draw is not None and (respawn is None or contact_config is None):
+            raise ValueError("the field is drawn at respawn, for the ground-contact plant: give respawn= and contact_config= as well")
+        if field_draw is not None and (terrain is not None or profile_draw is not None):
+            raise ValueError("field_draw draws the ground: no terrain= or profile_draw= beside it")
         if profile_draw is not None and (respawn is None or contact_config is None):
             raise ValueError("the profile is drawn at respawn, for the ground-contact plant: give respawn= and contact_config= as well")
         if profile_draw is not None and terrain is not None:
             raise ValueError("profile_draw draws the ground: no terrain= beside it")
-        if isinstance(ground_map, str) and ground_map == "draw" and profile_draw is None:
-            raise ValueError('ground_map="draw" follows the drawn profile: give profile_draw= as well')
+        if isinstance(ground_map, str) and ground_map == "draw" and profile_draw is None and field_draw is None:
+            raise ValueError('ground_map="draw" follows the drawn ground: give profile_draw= or field_draw= as well')
         if scenario is not None and (respawn is None or contact_config is None):
             raise ValueError("the scenario is drawn at respawn, for the ground-contact plant: give respawn= and contact_config= as well")
         if respawn is not None and episode is None:
@@ -439,6 +449,21 @@ class ResidentLoop:
                 level = np.tile(np.array([[-1.0, 0.0], [1.0, 0.0]]), (self.B, 1, 1))
                 solver.ground_set_profile(np.full(self.B, 2), np.tile(np.array(profile_draw.dir[:]), (self.B, 1)), level)
             solver.plant_set_profile_draw(profile_draw)
+        self.has_field_draw = field_draw is not None
+        if field_draw is not None:
+            follow = isinstance(ground_map, str) and ground_map == "draw"
+            if isinstance(field_draw, dict):
+                fields = dict(field_draw)
+                if follow:
+                    fields["follow_map"] = 1
+                field_draw = abi.make_field_draw_config(**fields)
+            if follow:
+                if not field_draw.follow_map:
+                    raise ValueError('ground_map="draw" needs follow_map in the configuration given')
+                nu, nw = field_draw.n_nodes[0], field_draw.n_nodes[1]
+                solver.ground_set_field(np.tile(np.array(field_draw.dir[:]), (self.B, 1)), np.zeros((self.B, 2)),
+                                        np.tile(np.array(field_draw.spacing[:]), (self.B, 1)), np.zeros((self.B, nu, nw)))
+            solver.plant_set_field_draw(field_draw)
         # resident observation of the initial state
         rbd = np.zeros((self.B, 32))
         rbd[:, 0:3], rbd[:, 3:6], rbd[:, 6:16] = q0[:, 3:6], q0[:, 0:3], q0[:, 6:]
@@ -544,11 +569,38 @@ class ResidentLoop:
             raise ValueError("ResidentLoop was built without profile_draw=")
         return self.s.plant_profile_draw()
 
+    def field_draw(self):
+        """row[B][HB_FD_N] of the fields the running episodes stand on (HunterSolver.plant_get_field_draw)."""
+        if not self.has_field_draw:
+            raise ValueError("ResidentLoop was built without field_draw=")
+        return self.s.plant_get_field_draw()
+
+    def field_draw_log(self) -> dict:
+        """The log of the finished episodes (HunterSolver.plant_get_field_draw_log)."""
+        if not self.has_field_draw:
+            raise ValueError("ResidentLoop was built without field_draw=")
+        return self.s.plant_get_field_draw_log()
+
     def profile_draw_log(self) -> dict:
         """The log of the finished episodes (HunterSolver.plant_profile_draw_log)."""
         if not self.has_profile_draw:
             raise ValueError("ResidentLoop was built without profile_draw=")
         return self.s.plant_profile_draw_log()
+
+
+def field_draw_table(log: dict) -> dict:
+    """The log of HunterSolver.plant_get_field_draw_log as flat arrays over all finished episodes that were logged, instance by instance in
+    the order they finished: INSTANCE, the five abi.FIELD_DRAW_LOG_HEAD fields (EPISODE, CAUSE and TICKS as integers) and the parameters
+    of abi.FIELD_DRAW_FIELDS ([n] or [n][4]; KIND as an integer)."""
+    count, rows = np.asarray(log["count"]), np.asarray(log["log"])
+    flat = np.concatenate([rows[i, :count[i]] for i in range(len(count))], axis=0) if len(count) else np.zeros((0, abi.HB_FD_LOG_W))
+    flat = flat.reshape(-1, abi.HB_FD_LOG_W)
+    out = dict(INSTANCE=np.repeat(np.arange(len(count)), count))
+    for k, name in enumerate(abi.FIELD_DRAW_LOG_HEAD):
+        out[name] = flat[:, k].astype(np.int64) if name in ("EPISODE", "CAUSE", "TICKS") else flat[:, k].copy()
+    out.update(abi.split_field_draw(flat[:, len(abi.FIELD_DRAW_LOG_HEAD):]))
+    out["KIND"] = out["KIND"].astype(np.int64)
+    return out
 
 
 def profile_draw_table(log: dict) -> dict:

@@ -42,6 +42,7 @@ ABI_SYMBOLS = [
     "hb_plant_set_respawn", "hb_plant_respawn", "hb_plant_get_respawn",
     "hb_plant_set_scenario", "hb_plant_get_scenario", "hb_plant_get_scenario_log",
     "hb_plant_set_profile_draw", "hb_plant_get_profile_draw", "hb_plant_get_profile_draw_log",
+    "hb_plant_set_field_draw", "hb_plant_get_field_draw", "hb_plant_get_field_draw_log",
     "hb_ground_set_profile", "hb_ground_get_profile", "hb_ground_set_field", "hb_ground_get_field", "hb_ground_eval",
 ]
 # include/hunter_lcm.h
@@ -572,6 +573,28 @@ class HunterSolver:
         cap = getattr(self, "_profile_draw_log_capacity", 0)
         count, log = np.zeros(self.B, dtype=np.int32), np.zeros((self.B, cap, abi.HB_PD_LOG_W))
         self._check(self.lib.hb_plant_get_profile_draw_log(self.ctx, _p(count), _p(log) if cap else None), "hb_plant_get_profile_draw_log")
+        return dict(count=count, log=log)
+
+    # ---- field draw at respawn (hb_plant_set_field_draw) ------------------------------------------------------------------------------
+    def plant_set_field_draw(self, cfg: "abi.HbFieldDrawConfig" = None):
+        """cfg None: off; abi.make_field_draw_config(...): every plant_respawn() composes a height field (level, rough, tilted or both: the
+        kinds of cfg) on the device for the instances it respawns and places them on it.  Needs contact model 1 and plant_set_respawn;
+        with follow_map a field map in force (ground_set_field), which then follows the drawn field."""
+        self._check(self.lib.hb_plant_set_field_draw(self.ctx, None if cfg is None else C.byref(cfg)), "hb_plant_set_field_draw")
+        self._field_draw_log_capacity = 0 if cfg is None else int(cfg.log_capacity)
+
+    def plant_get_field_draw(self):
+        """-> row[B][HB_FD_N], the parameters every instance's current ground was drawn with (abi.split_field_draw names them)."""
+        row = np.zeros((self.B, abi.HB_FD_N))
+        self._check(self.lib.hb_plant_get_field_draw(self.ctx, _p(row)), "hb_plant_get_field_draw")
+        return row
+
+    def plant_get_field_draw_log(self):
+        """-> dict(count[B] int32, log[B][log_capacity][HB_FD_LOG_W]): the finished episodes of every instance in order, each row
+        abi.FIELD_DRAW_LOG_HEAD and then the HB_FD_N parameters it ran under; rows behind count are zero."""
+        cap = getattr(self, "_field_draw_log_capacity", 0)
+        count, log = np.zeros(self.B, dtype=np.int32), np.zeros((self.B, cap, abi.HB_FD_LOG_W))
+        self._check(self.lib.hb_plant_get_field_draw_log(self.ctx, _p(count), _p(log) if cap else None), "hb_plant_get_field_draw_log")
         return dict(count=count, log=log)
 
     # ---- sensors from the plant (hb_plant_sense) and the estimator on them ------------------------------------------------

@@ -854,7 +854,8 @@ int32_t hb_plant_get_scenario_log(hb_ctx* ctx, int32_t* count, double* log);
  * hb_ground_get_profile and hb_plant_reset read the device records first (the host copies are stale).  cfg NULL, turning respawn or the
  * episode off switch the draw off: profile and map stay in force as last drawn, the host copies are refreshed, and respawn, if still on,
  * keeps placing on the profile.  Leaving model 1 switches draw and profile off.  hb_plant_reset empties the log; records and rows stay.
- * Out of scope: a draw for episode 0, a direction per episode, two-dimensional ground, the instance-range / graph paths. */
+ * Out of scope: a draw for episode 0, a direction per episode, the instance-range / graph paths (two-dimensional ground:
+ * hb_plant_set_field_draw below). */
 #define HB_PD_STREAM 0x50444431u /* third counter word; differs from HB_RS_STREAM and HB_SC_STREAM */
 enum { HB_PD_FLAT = 1, HB_PD_CURB = 2, HB_PD_STAIRS = 4 }; /* kinds */
 enum { HB_PD_KIND = 0, HB_PD_HEIGHT = 1, HB_PD_AT = 2, HB_PD_STEPS = 3, HB_PD_RUN = 4, HB_PD_MUS = 5 /* [4] */, HB_PD_N = 9 }; /* row */
@@ -883,6 +884,116 @@ int32_t hb_plant_get_profile_draw(hb_ctx* ctx, double* row);
 /* count[batch] = rows logged per instance, log[batch][log_capacity][HB_PD_LOG_W] (rows behind count are zero); either may be NULL.
  * Synchronises.  HB_ERR_STATE without a profile draw in force. */
 int32_t hb_plant_get_profile_draw_log(hb_ctx* ctx, int32_t* count, double* log);
+
+/* ---- field draw at respawn: a 32 x 32 height field per episode, composed on the device; respawn on it --------------------------------------
+ * With a field draw in force, hb_plant_respawn composes a new height field (hb_plant_set_terrain_field below) for every instance it
+ * respawns: a kernel of its own (k_plant_field_draw, one wavefront per instance), enqueued ahead of k_plant_respawn (and behind
+ * k_plant_scenario if a scenario is in force too) in the same call, reads the same decision from the still unchanged episode record, and
+ * for a respawning instance, in this order, (a) appends the log row of the finished episode, (b) draws, (c) composes the heights and the
+ * stored header, (d) writes heights, header, the parameter row row[HB_FD_N] and, with follow_map, heights and header of the controller's
+ * field map (hb_ground_set_field).  k_plant_respawn then places the robot on the field it finds (below).  An instance that stays costs the
+ * decision loads and an exit: NOT ONE BYTE of it is written.  Nothing crosses the bus.  Off by default; without a draw every call enqueues
+ * exactly what it enqueues without this block.  Episode 0 (the state of hb_plant_reset) is never drawn.
+ *
+ * The draw.  Philox4x32-10, u_k = (word k + 0.5) 2^-32 as for the profile draw (above):
+ *       key = (seed low 32, seed high 32) of THIS configuration's seed;  counter = (instance_offset + i, e, HB_FD_STREAM, block),
+ * instance_offset from the respawn configuration in force, e = EPISODE_INDEX + 1 the episode that starts.  Every operation below is an
+ * IEEE double operation of its own in the order written, brackets first, nothing fused; there is no transcendental function in it.  All
+ * 258 blocks are independent and always generated.
+ *   block 0:      kind = list[int(u_0 n)], list = the enabled kinds in ascending bit order, n their number;
+ *                 A = amp_lo + (amp_hi - amp_lo) u_1;  p = slope_u_lo + (slope_u_hi - slope_u_lo) u_2;
+ *                 r = slope_w_lo + (slope_w_hi - slope_w_lo) u_3.
+ *   block 1:      mu_c = mu_lo + (mu_hi - mu_lo) u_c,  c = 0..3;  with mu_per_point = 0 all four points take c = 0's value.
+ *   block 2 + k,  k = 0 .. 255:  word m is the uniform u_n of node n = 4 k + m in the PITCH numbering n = iu HB_FIELD_MAX_NODES + iw: the
+ *                 draw of a node does not depend on (nu, nw).
+ *   HB_FD_FLAT and HB_FD_TILT take A = 0;  HB_FD_FLAT and HB_FD_ROUGH take p = r = 0.
+ * Composition.  a = (a_x, a_y) is the stored unit direction (dir / sqrt(dir_x dir_x + dir_y dir_y), the division of the terrain profile),
+ * b = (-a_y, a_x), q_s = q_spawn[0:2] of the respawn configuration in force, gz = ground_z of the contact model, (nu, nw) = n_nodes,
+ * (du, dw) = spacing, (cu, cw) = centre: the grid-local coordinates of the spawn point.
+ *   origin:       u0 = (a_x q_s[0] + a_y q_s[1]) - cu;   w0 = ((-a_y) q_s[0] + a_x q_s[1]) - cw;
+ *   node (iu, iw), iu < nu, iw < nw:   un = double(iu) du,  wn = double(iw) dw;
+ *                 c = 0 if |un - cu| <= calm and |wn - cw| <= calm, else 1   (no bumps in the square around the spawn point);
+ *                 g = (p (un - cu) + r (wn - cw)) + (A (2 u_n - 1)) c        (the height relative to the spawn point's level);
+ *   plant:        heights[iu][iw] = 0 + (gz + g);  nodes beyond (nu, nw) store 0;
+ *   map:          with follow_map the controller's field map takes 0 + g (0 beyond (nu, nw)) and the same eight header doubles
+ *                 (a, u0, w0, du, dw, nu, nw).
+ * What is stored — header, the facet under the world origin in its head, friction, heights — is what hb_plant_set_terrain_field stores
+ * for n_nodes, dir, (u0, w0), spacing, these heights and mu, byte for byte (one routine, csrc/hb_contact.hpp field_compose, behind
+ * both), and the map likewise what hb_ground_set_field stores (csrc/hb_ground.hpp ground_field_compose).
+ *
+ * row[HB_FD_N]: KIND (the bit value), AMPLITUDE = A, SLOPE_U = p, SLOPE_W = r, MUS[4].  Entries a kind does not use are 0 (FLAT:
+ * AMPLITUDE, SLOPE_U, SLOPE_W; ROUGH: the slopes; TILT: AMPLITUDE).  Before an instance's first draw the row is zero (KIND 0).
+ * Log: up to log_capacity rows of HB_FD_LOG_W doubles per instance, appended in order until full: the five leading entries of the profile
+ * draw's log row (index, cause, TICKS, progress along a, TILT_MAX), then the HB_FD_N parameters the episode ran under.
+ *
+ * Placement on a field (k_plant_respawn, whenever a field is in force at a respawn): the vertical rule of the profile draw with the
+ * field's facet in the segment's place.  Contact point c at p_c takes the facet under it (the cell and triangle rule of the height
+ * field) with (n_c, d_c);  gap_c = ((n_x x + n_y y) + n_z z) - d;  D = max over c of (clearance - gap_c) / n_{c,z};  q[2] += D
+ * (place = 0: no shift).  A vertical shift changes no (u, w), hence no facet.  On a level field D is the shift of step 3 on the level
+ * plane, bit for bit.  After placement, either way, the kernel writes the facet ids under the four contact points and the base origin and
+ * the Terrain record of the facet under the base origin (what hb_plant_reset's host locate writes), and the new episode record measures
+ * height against that facet.
+ *
+ * Validity.  The device cannot refuse a draw, so the set call admits only configurations all of whose draws the height field accepts.
+ * Let P = max(|slope_u_lo|, |slope_u_hi|), R likewise for w.  Two neighbouring nodes along u differ by p du + A (b' - b) with bump factors
+ * b, b' in (-1, 1), so a triangle's u-slope is at most P + 2 amp_hi / du in magnitude and its w-slope at most R + 2 amp_hi / dw, before
+ * rounding; the set call refuses unless (P + 2 amp_hi / du)^2 + (R + 2 amp_hi / dw)^2 <= 2.9.  Rounding: with spacing in [1e-3, 10], the
+ * centre inside the grid and |gz| <= 1e3, |g| < 2^11 and |gz + g| < 2^12 (the grid spans at most 310 m, the slopes stay below 1.71, amp_hi below 8.6), so the eleven
+ * roundings behind a stored height, each at most half an ulp of a number below 2^12, move it by less than 11 * 2^-42 < 2^-38 m, a
+ * difference of two heights by less than 2^-37 m, a slope (spacing >= 1e-3) by less than 1e-8 and the sum of the two squares by
+ * less than 4 * 1.71 * 1e-8 < 1e-7: far inside the 0.1 the bound 2.9 leaves below the field's limit 3.  The spacing is
+ * positive, origin and heights are finite (|a . q_s|, |b . q_s| <= 1e3), the counts lie in 2 .. HB_FIELD_MAX_NODES, mu_c in [mu_lo, mu_hi].
+ * HB_ERR_ARG (the configuration in force is kept) for: a non-finite field; kinds outside 1 .. 15; mu_per_point or follow_map not 0 / 1;
+ * |dir| = 0; n_nodes outside 2 .. 32; spacing outside [1e-3, 10]; centre outside [0, (n - 1) spacing]; calm < 0; lo > hi in any range;
+ * amp_lo < 0; mu_lo < 0; the slope bound above; log_capacity outside 0 .. HB_FD_LOG_MAX; a nonzero `reserved`.
+ *
+ * State.  HB_ERR_STATE before hb_plant_reset, outside contact model 1, without a respawn configuration in force, while a profile draw is
+ * in force (and hb_plant_set_profile_draw while a field draw is: a height field is then in force), while a scenario with HB_SC_SLOPE or
+ * HB_SC_MU is in force (the other order is refused by hb_plant_set_scenario: a field is then in force; PAYLOAD, MASS and PUSH combine
+ * freely with the draw), with follow_map unless a FIELD map is in force (set the zero field map first; a profile map is refused), and
+ * when |ground_z| or |a . q_s| or |b . q_s| of an instance exceeds 1e3.  Setting the draw puts every instance on the level field of the
+ * configured grid (heights 0 + (gz + 0), cfg.mu) located at the plant's current state, replacing a terrain or a profile, clears the
+ * contact impulses as hb_plant_set_terrain_field does, and restarts the rows and the log; with follow_map the controller's map becomes
+ * the zero map over the same grid.  A configuration in force is switched off before the new one's arrays are allocated and written:
+ * HB_ERR_ARG and HB_ERR_STATE keep it, HB_ERR_DEVICE leaves the draw off.  While the draw is in force hb_plant_set_terrain and every
+ * hb_plant_set_terrain_field / hb_plant_set_terrain_profile, the switch-off calls included, return HB_ERR_STATE,
+ * hb_plant_set_contact_model refuses a |ground_z| above 1e3 with HB_ERR_ARG, and hb_plant_get_terrain_field, hb_ground_get_field,
+ * hb_plant_field_eval and hb_plant_reset read the device records first (the host copies are stale).  cfg NULL, turning respawn or the
+ * episode off switch the draw off: field and map stay in force as last drawn, the host copies are refreshed, and respawn, if still on,
+ * keeps placing on the field.  Leaving model 1 switches draw and field off.  hb_plant_reset empties the log; records and rows stay.
+ * hb_plant_set_respawn with a field in force and hb_plant_set_terrain_field with a respawn in force stay refused: the draw is the one
+ * way to a respawn on a field.
+ * Out of scope: a draw for episode 0, a grid or a direction per episode, respawn on a field the host set, the instance-range / graph
+ * paths, smoothed or correlated roughness. */
+#define HB_FD_STREAM 0x46444431u /* third counter word; differs from HB_RS_STREAM, HB_SC_STREAM and HB_PD_STREAM */
+enum { HB_FD_FLAT = 1, HB_FD_ROUGH = 2, HB_FD_TILT = 4, HB_FD_TILT_ROUGH = 8 }; /* kinds */
+enum { HB_FD_KIND = 0, HB_FD_AMPLITUDE = 1, HB_FD_SLOPE_U = 2, HB_FD_SLOPE_W = 3, HB_FD_MUS = 4 /* [4] */, HB_FD_N = 8 }; /* row */
+#define HB_FD_LOG_W (5 + HB_FD_N) /* finished episode's index, cause, TICKS, progress, TILT_MAX, then its HB_FD_N parameters */
+#define HB_FD_LOG_MAX 1024
+typedef struct hb_field_draw_config {
+  uint64_t seed;
+  int32_t kinds;              /* OR of HB_FD_*, at least one */
+  int32_t mu_per_point;       /* 0: one coefficient for the four points; 1: one each */
+  double dir[2];              /* |dir| > 0, normalised as the terrain profile normalises it */
+  int32_t n_nodes[2];         /* (nu, nw), 2 .. HB_FIELD_MAX_NODES */
+  double spacing[2];          /* (du, dw) m, in [1e-3, 10] */
+  double centre[2];           /* grid-local (u, w) of the spawn point, inside the grid */
+  double calm;                /* m, >= 0: half-width of the square around the spawn point without bumps */
+  double amp_lo, amp_hi;      /* m, 0 <= lo <= hi: bump amplitude (a node moves by at most A) */
+  double slope_u_lo, slope_u_hi, slope_w_lo, slope_w_hi; /* signed, lo <= hi: dz/du, dz/dw of the tilt */
+  double mu_lo, mu_hi;        /* 0 <= lo <= hi */
+  int32_t follow_map;         /* 0 / 1: the controller's field map follows the drawn field */
+  int32_t log_capacity;       /* 0 .. HB_FD_LOG_MAX finished episodes kept per instance */
+  int32_t reserved[2];        /* 0 */
+} hb_field_draw_config;
+/* cfg NULL: off. */
+int32_t hb_plant_set_field_draw(hb_ctx* ctx, const hb_field_draw_config* cfg);
+/* row[batch][HB_FD_N]: the parameters every instance's current ground was drawn with.  Synchronises like hb_plant_get_episode.
+ * HB_ERR_STATE without a field draw in force. */
+int32_t hb_plant_get_field_draw(hb_ctx* ctx, double* row);
+/* count[batch] = rows logged per instance, log[batch][log_capacity][HB_FD_LOG_W] (rows behind count are zero); either may be NULL.
+ * Synchronises.  HB_ERR_STATE without a field draw in force. */
+int32_t hb_plant_get_field_draw_log(hb_ctx* ctx, int32_t* count, double* log);
 
 /* ---- sensors from the plant: what LeggedController::updateStateEstimation reads, computed on the device -----------
  * hb_plant_sense turns the plant's state into the sensor arrays of hb_estimator_update and leaves them on the device

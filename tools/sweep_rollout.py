@@ -27,6 +27,12 @@
                                                         controller blind; survival, tilt and slip by amplitude from one run(n) and one
                                                         read-back of the episode record.  --ground-map: the same rows once more with the
                                                         field as the controller's field map (hb_ground_set_field), next to the blind ones
+    python tools/sweep_rollout.py --random-rough 3000 --robots 256 --max-ticks 1000   repeated episodes on a height field composed on the device per episode:
+                                                        level, rough (bump amplitude 0 .. --rough-max), tilted (slopes up to 0.1) or both, a 32 x 32
+                                                        grid of 5 cm cells around the spawn point (hb_plant_set_field_draw); survival, progress
+                                                        and largest tilt by kind and amplitude bin, from one run(n) and one read-back of the
+                                                        draw's log.  --ground-map: the controller's field map follows every drawn field;
+                                                        --joint-model as everywhere
     python tools/sweep_rollout.py --readback            the two sweeps once more with the per-tick read-back loop the findings of items 17 - 20
                                                         were made with, for the wall time per tick of both
 
@@ -41,8 +47,8 @@ import numpy as np
 
 sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
 from hunter_bipedal_control_amd import abi, ingest  # noqa: E402
-from hunter_bipedal_control_amd.rollout import (ResidentLoop, curb_profile, episode_summary, payload_on_base, profile_draw_table,  # noqa: E402
-                                                respawn_summary, rough_field, scenario_table)
+from hunter_bipedal_control_amd.rollout import (ResidentLoop, curb_profile, episode_summary, field_draw_table, payload_on_base,  # noqa: E402
+                                                profile_draw_table, respawn_summary, rough_field, scenario_table)
 from hunter_bipedal_control_amd.solver import HunterSolver  # noqa: E402
 
 FRICTION = [0.7, 0.5, 0.4, 0.3, 0.2, 0.15, 0.1, 0.05]
@@ -247,6 +253,65 @@ def print_random_curbs(log, bins=3):
             row(name, "[%.3g, %.3g]" % (edges[b], edges[b + 1]), of & (which == b))
 
 
+# the grid of --rough (32 x 32 nodes of 5 cm, from 0.35 m behind the spawn point to 1.2 m ahead of it, centred across), bumps under the
+# feet of the start too (calm = 0), tilts of up to 0.1 either way
+RANDOM_ROUGH = dict(kinds=abi.HB_FD_ALL, dir=(1.0, 0.0), n_nodes=(32, 32), spacing=(ROUGH_CELL, ROUGH_CELL), centre=(0.35, 0.775), calm=0.0,
+                    amp_lo=0.0, slope_u_lo=-0.1, slope_u_hi=0.1, slope_w_lo=-0.1, slope_w_hi=0.1, mu_lo=0.7, mu_hi=0.7, seed=4)
+
+
+def run_random_rough(params, robots, ticks, max_ticks, amp_max, joint_model=None, ground_map=False):
+    """Repeated episodes on a newly composed height field each -> (log of the draw, respawn totals, wall seconds of the ticks, the largest
+    amplitude drawn).  amp_max is cut to what the draw's slope bound admits on this grid beside the tilt: (0.1 + 2 A / 0.05)^2 * 2 <= 2.9
+    gives A <= 0.0276 m (a seeded field of --rough is scaled down as a whole instead)."""
+    B = robots
+    amp_max = min(amp_max, 0.999 * (np.sqrt(2.9 / 2.0) - RANDOM_ROUGH["slope_u_hi"]) * ROUGH_CELL / 2.0)
+    s = HunterSolver(params, batch=B, max_nodes=108)
+    try:
+        horizon = 100 * params["config"]["dt"]
+        # (fall_height 0.2 as in run_curb: the fall test is measured along the normal of the facet under the base origin)
+        loop = ResidentLoop(s, params, ["trot"] * B, np.tile([0.2, 0.0, 0.0, 0.0], (B, 1)), contact_config=dict(fall_height=0.2), joint_model=joint_model,
+                            static_schedule_until=ticks * 0.002 + horizon + 1.5, episode=dict(slip_speed=0.05),
+                            respawn=dict(RANDOMIZE_RESPAWN, max_ticks=max_ticks),
+                            field_draw=dict(RANDOM_ROUGH, amp_hi=amp_max, log_capacity=min(abi.HB_FD_LOG_MAX, ticks // 8 + 1)),
+                            ground_map="draw" if ground_map else None)
+        s.sync()
+        t0 = time.perf_counter()
+        loop.run(ticks)
+        log = loop.field_draw_log()
+        return log, loop.respawn_totals(), time.perf_counter() - t0, amp_max
+    finally:
+        s.close()
+
+
+def print_random_rough(log, bins=4):
+    """Survival rate (episodes that ended by time-out), median progress along the direction, median of the largest tilt and mean ticks by
+    kind, and for the two rough kinds by amplitude bin, from the log alone."""
+    t = field_draw_table(log)
+    drawn = t["EPISODE"] > 0                       # (episode 0 ran on the level field of the start, not on a draw)
+    print(f"   {len(t['EPISODE'])} finished episodes logged, {int(drawn.sum())} of them on a drawn field")
+    survived = t["CAUSE"] == abi.HB_RS_TIMEOUT
+    heads = ("kind", "amplitude", "episodes", "survival", "progress med", "tiltmax med", "ticks")
+    print("   " + " ".join(f"{h:>16}" for h in heads))
+
+    def row(kind, label, m):
+        # (medians: a robot that is lost can leave very large values at its last finite tick)
+        cells = (kind, label, f"{int(m.sum())}") + ((f"{survived[m].mean():.3f}", f"{np.median(t['PROGRESS'][m]):.4f}", f"{np.median(t['TILT_MAX'][m]):.4f}",
+                                                     f"{t['TICKS'][m].mean():.1f}") if m.any() else ("-",) * 4)
+        print("   " + " ".join(f"{c:>16}" for c in cells))
+
+    row("flat", "0", drawn & (t["KIND"] == abi.HB_FD_FLAT))
+    row("tilt", "0", drawn & (t["KIND"] == abi.HB_FD_TILT))
+    for name, kind in (("rough", abi.HB_FD_ROUGH), ("tilt + rough", abi.HB_FD_TILT_ROUGH)):
+        of = drawn & (t["KIND"] == kind)
+        if not of.any():
+            row(name, "-", of)
+            continue
+        edges = np.linspace(t["AMPLITUDE"][of].min(), t["AMPLITUDE"][of].max(), bins + 1)
+        which = np.clip(np.searchsorted(edges, t["AMPLITUDE"], side="right") - 1, 0, bins - 1)
+        for b in range(bins):
+            row(name, "[%.3g, %.3g]" % (edges[b], edges[b + 1]), of & (which == b))
+
+
 def print_randomize(log, bins=4):
     """Survival rate (episodes that ended by time-out) and mean ticks, binned by mu, |grade| and payload mass, from the log alone."""
     t = scenario_table(log)
@@ -328,7 +393,8 @@ def main():
     ap.add_argument("--respawn", type=int, metavar="N_TICKS", help="the friction sweep as repeated episodes of at most N_TICKS ticks, from the respawn totals")
     ap.add_argument("--randomize", type=int, metavar="N_TICKS", help="N_TICKS ticks of repeated episodes with slope, friction, payload and a push drawn on the device per episode; one read-back")
     ap.add_argument("--random-curbs", type=int, metavar="N_TICKS", help="N_TICKS ticks of repeated episodes on level ground, a curb / step-down or stairs drawn on the device per episode; one read-back")
-    ap.add_argument("--robots", type=int, default=64, help="batch of --randomize / --random-curbs")
+    ap.add_argument("--random-rough", type=int, metavar="N_TICKS", help="N_TICKS ticks of repeated episodes on a level, rough, tilted or rough and tilted height field composed on the device per episode (bump amplitude up to --rough-max); one read-back")
+    ap.add_argument("--robots", type=int, default=64, help="batch of --randomize / --random-curbs / --random-rough / --rough")
     ap.add_argument("--max-ticks", type=int, default=400, help="time-out of an episode of --randomize / --random-curbs")
     ap.add_argument("--host-driven", action="store_true", help="--randomize with the host calling the setters per respawn round and uploading a wrench per tick")
     ap.add_argument("--curb", action="store_true", help="one curb / step-down height per robot (0, 1, 2, 3 cm down and up), trot across it; from the episode record alone")
@@ -353,6 +419,14 @@ def main():
               f"B = {args.robots}, {args.rough} ticks, run() and one read-back: {wall:.3f} s, {1e3 * wall / args.rough:.3f} ms per tick")
         print_rough(amp, rec)
     if args.rough:
+        return
+    if args.random_rough:
+        log, tot, wall, amp = run_random_rough(params, args.robots, args.random_rough, args.max_ticks, args.rough_max, joint_model=jm, ground_map=args.ground_map)
+        print(f"-- a height field composed per episode, {'controller on the field map that follows' if args.ground_map else 'controller blind'}, "
+              f"{'joint model' if args.joint_model else 'ideal joints'}, B = {args.robots}, {args.random_rough} ticks, episodes of at most {args.max_ticks} "
+              f"ticks, bump amplitude up to {amp:.4f} m, run() and one read-back: {wall:.3f} s, {1e3 * wall / args.random_rough:.3f} ms per tick")
+        print(f"   episodes {int(tot['EPISODES'].sum())}: fallen {int(tot['N_FALLEN'].sum())}, non-finite {int(tot['N_NONFINITE'].sum())}, timed out {int(tot['N_TIMEOUT'].sum())}")
+        print_random_rough(log)
         return
     if args.random_curbs:
         log, tot, wall = run_random_curbs(params, args.robots, args.random_curbs, args.max_ticks, joint_model=jm, ground_map=args.ground_map)
