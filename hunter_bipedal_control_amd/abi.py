@@ -465,6 +465,37 @@ def split_field_draw(row) -> dict:
     return {name: (row[..., at].copy() if n == 1 else row[..., at:at + n].copy()) for name, at, n in FIELD_DRAW_FIELDS}
 
 
+class HbHeightScanConfig(C.Structure):
+    """hb_height_scan_config (include/hunter_hip.h): the controller's field map perceived from the plant's ground, hb_plant_set_height_scan."""
+    _fields_ = [("n_nodes", C.c_int32 * 2), ("back", C.c_int32 * 2), ("dir", C.c_double * 2), ("spacing", C.c_double * 2), ("range", C.c_double),
+                ("noise", C.c_double), ("dropout", C.c_double), ("register_mode", C.c_int32), ("reserved", C.c_int32), ("seed", C.c_uint64),
+                ("instance_offset", C.c_uint32), ("pad", C.c_int32)]
+
+
+HB_HS_STREAM = 0x48535331
+
+
+def make_height_scan_config(**fields) -> HbHeightScanConfig:
+    """An ideal sensor: a 32 x 32 grid along x with 0.1 m spacing, the registration point in its middle cell (back None: (n - 1) // 2), no
+    range limit, no noise, no dropout, registered with the plant's position, seed 0; any field by name overrides (n_nodes, back, dir,
+    spacing: 2 values each)."""
+    d = dict(n_nodes=(HB_FIELD_MAX_NODES, HB_FIELD_MAX_NODES), back=None, dir=(1.0, 0.0), spacing=(0.1, 0.1), range=0.0, noise=0.0, dropout=0.0,
+             register_mode=0, reserved=0, seed=0, instance_offset=0, pad=0)
+    for k in fields:
+        if k not in d:
+            raise TypeError(f"make_height_scan_config: unknown field {k!r} (one of {sorted(d)})")
+    d.update(fields)
+    out = HbHeightScanConfig()
+    for k in ("range", "noise", "dropout"):
+        setattr(out, k, float(d[k]))
+    for k in ("register_mode", "reserved", "seed", "instance_offset", "pad"):
+        setattr(out, k, int(d[k]))
+    for j in (0, 1):
+        out.n_nodes[j], out.dir[j], out.spacing[j] = int(d["n_nodes"][j]), float(d["dir"][j]), float(d["spacing"][j])
+        out.back[j] = (out.n_nodes[j] - 1) // 2 if d["back"] is None else int(d["back"][j])
+    return out
+
+
 class HbJointGains(C.Structure):
     _fields_ = [(k, C.c_double) for k in ("kp_big_stance", "kp_big_swing", "kd_big", "kp_small_stance", "kp_small_swing", "kd_small",
                                           "kd_feet", "kp_position", "kd_position")]

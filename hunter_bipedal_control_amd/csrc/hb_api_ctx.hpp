@@ -157,6 +157,13 @@ struct hb_ctx {
   FieldDrawBatch field_draw{};
   hb_field_draw_config field_draw_cfg{};
   bool field_draw_on = false;
+  // height scan (hb_plant_set_height_scan): scan_on while a configuration is in force (gfield_on is then true as well, and gfield_hdr_host /
+  // gfield_z_host are stale: scan_refresh_host brings them up to date); scan_cfg holds the direction already normalised; scan_count =
+  // hb_plant_scan calls since the configuration was set (the noise counter); the arrays are allocated by the first call that gives one
+  ScanBatch scan{};
+  hb_height_scan_config scan_cfg{};
+  bool scan_on = false;
+  uint32_t scan_count = 0;
   // reference generation (allocated on the first hb_refgen_reset)
   RefgenBatch rg{};
   hb_refgen_config rg_cfg{};
@@ -478,7 +485,7 @@ static int32_t resident_write(hb_ctx* ctx, hipStream_t s, bool fence, F&& launch
 
 extern "C" {
 
-int32_t hb_version(void) { return 303; }
+int32_t hb_version(void) { return 304; }
 
 const char* hb_last_error(const hb_ctx* ctx) { return ctx ? ctx->err.c_str() : g_create_error.c_str(); }
 

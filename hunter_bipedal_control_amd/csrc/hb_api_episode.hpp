@@ -261,6 +261,7 @@ int32_t hb_plant_set_field_draw(hb_ctx* ctx, const hb_field_draw_config* cfg) {
   HB_FAIL_IF(cfg && ctx->scenario_on && (ctx->scenario_cfg.channels & (HB_SC_SLOPE | HB_SC_MU)), HB_ERR_STATE, "hb_plant_set_field_draw: the scenario in force draws the terrain (hb_plant_set_scenario with HB_SC_SLOPE or HB_SC_MU): turn it off first");
   HB_TRY(refuse_config(ctx, "hb_plant_set_field_draw", cfg ? field_draw_config_refusal(*cfg) : nullptr));
   HB_FAIL_IF(cfg && cfg->follow_map && ctx->ground_on, HB_ERR_STATE, "hb_plant_set_field_draw: follow_map while a profile map is in force (hb_ground_set_profile): the draw writes field maps, set the zero field map first (hb_ground_set_field)");
+  HB_FAIL_IF(cfg && cfg->follow_map && ctx->scan_on, HB_ERR_STATE, "hb_plant_set_field_draw: follow_map while a height scan is in force (hb_plant_set_height_scan): the scan writes the field map, turn it off first");
   HB_FAIL_IF(cfg && cfg->follow_map && !ctx->gfield_on, HB_ERR_STATE, "hb_plant_set_field_draw: follow_map without a field map in force (hb_ground_set_field): set the zero field map first");
   HB_FAIL_IF(cfg && !(std::fabs(ctx->contact_cfg.ground_z) <= FD_REACH), HB_ERR_STATE, "hb_plant_set_field_draw: |ground_z| of the contact model above 1e3: the heights are drawn around ground_z");
   HB_ENTER_DEVICE();

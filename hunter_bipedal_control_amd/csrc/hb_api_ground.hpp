@@ -19,6 +19,7 @@ int32_t hb_ground_set_profile(hb_ctx* ctx, const int32_t* n_knots, const double*
   const bool on = n_knots || dir || knots;
   HB_FAIL_IF(on && !(n_knots && dir && knots), HB_ERR_ARG, "hb_ground_set_profile: give n_knots, dir and knots, or none of them to switch the map off (the map in force is kept)");
   HB_FAIL_IF(on && ctx->field_draw_on && ctx->field_draw_cfg.follow_map, HB_ERR_STATE, "hb_ground_set_profile: the field draw in force writes the field map (hb_plant_set_field_draw, follow_map): turn it off first");
+  HB_FAIL_IF(ctx->scan_on, HB_ERR_STATE, "hb_ground_set_profile: the height scan in force writes the field map (hb_plant_set_height_scan): turn it off first");
   const size_t B = ctx->B;
   std::vector<double> rec(on ? B * Ground::size : 0), kn(on ? B * HB_PROFILE_MAX_KNOTS * 2 : 0);
   for (size_t i = 0; i < B && on; ++i) {
@@ -66,6 +67,7 @@ int32_t hb_ground_set_field(hb_ctx* ctx, const int32_t* n_nodes, const double* d
   const bool on = n_nodes || dir || origin || spacing || heights;
   HB_FAIL_IF(on && !(n_nodes && dir && origin && spacing && heights), HB_ERR_ARG, "hb_ground_set_field: give n_nodes, dir, origin, spacing and heights, or none of them to switch the map off (the map in force is kept)");
   HB_FAIL_IF(on && ctx->profile_draw_on && ctx->profile_draw_cfg.follow_map, HB_ERR_STATE, "hb_ground_set_field: the profile draw in force writes the profile map (hb_plant_set_profile_draw, follow_map): turn it off first");
+  HB_FAIL_IF(ctx->scan_on, HB_ERR_STATE, "hb_ground_set_field: the height scan in force writes the field map (hb_plant_set_height_scan): turn it off first");
   const size_t B = ctx->B;
   std::vector<double> hdr(on ? B * GroundField::size : 0), z(on ? B * GroundField::nz : 0);
   for (size_t i = 0; i < B && on; ++i) {
@@ -100,6 +102,11 @@ int32_t hb_ground_get_field(hb_ctx* ctx, int32_t* n_nodes, double* dir, double* 
     HB_ENTER_DEVICE();
     HB_HIP(hipStreamSynchronize(ctx->s_wbc));
     HB_TRY(field_draw_refresh_host(ctx));
+  }
+  if (ctx->scan_on) {   // likewise the map the device scans
+    HB_ENTER_DEVICE();
+    HB_HIP(hipStreamSynchronize(ctx->s_wbc));
+    HB_TRY(scan_refresh_host(ctx));
   }
   for (size_t i = 0; i < size_t(ctx->B); ++i) {
     const double* h = ctx->gfield_hdr_host.data() + i * GroundField::size;

@@ -340,6 +340,26 @@ static int32_t field_draw_off(hb_ctx* ctx) {
   return HB_OK;
 }
 
+// ---- height scan: what the plant and ground entries share with hb_plant_set_height_scan ---------------------------------------------------
+// The host images of the field map the device has been scanning, from the device.  The caller has drained ctx->s_wbc.
+static int32_t scan_refresh_host(hb_ctx* ctx) {
+  if (!(ctx->scan_on && ctx->gfield_on)) return HB_OK;
+  HB_TRY(pull(ctx, ctx->gfield_hdr_host.data(), ctx->gfield, ctx->gfield.hdr, whole(ctx)));
+  return pull(ctx, ctx->gfield_z_host.data(), ctx->gfield, ctx->gfield.z, whole(ctx));
+}
+// Scan off: the map stays in force as last written (the host images follow the device).  The caller has drained ctx->s_wbc.
+static int32_t scan_off(hb_ctx* ctx) {
+  if (!ctx->scan_on) return HB_OK;
+  HB_TRY(scan_refresh_host(ctx));
+  ctx->scan_on = false;
+  return HB_OK;
+}
+// every instance's map counts as cleared from here on (ScanBatch::episode_seen below zero), on s
+static int32_t scan_mark_cleared(hb_ctx* ctx, hipStream_t s) {
+  HB_HIP(hipMemsetAsync(ctx->scan.episode_seen, 0xFF, size_t(ctx->B) * sizeof(int), s));
+  return HB_OK;
+}
+
 // Installs the field records hdr[B][Field::stored] and heights z[B][Field::nz] as the ground in force: records to the device, host images,
 // the facets under the plant's present state, one ground at a time (the field replaces a terrain and a profile), no warm start from the
 // ground of before.  With a map (ghdr, gz) the field map of the controller follows.  The caller has drained ctx->s_wbc; the vectors are
@@ -398,6 +418,7 @@ int32_t hb_plant_reset(hb_ctx* ctx, const double* q0, const double* v0, double b
   if (ctx->field_on) HB_TRY(field_locate(ctx, q0, ctx->s_wbc));
   if (ctx->episode_on) HB_TRY(episode_start(ctx, ctx->s_wbc));   // the record restarts from the reset state
   if (ctx->respawn_on) HB_TRY(respawn_totals_start(ctx, ctx->s_wbc));   // ... and so do the totals of the respawn
+  if (ctx->scan_on) HB_TRY(scan_mark_cleared(ctx, ctx->s_wbc));         // the first scan of the reset plant starts from an empty map
   HB_HIP(hipStreamSynchronize(ctx->s_wbc));
   if (ctx->scenario_on) HB_TRY(scenario_start(ctx, false));   // the log is empty, nobody has a push; terrain, models and scen stay as last drawn
   if (ctx->profile_draw_on) HB_TRY(profile_draw_start(ctx, false));   // the log is empty; profile, map and rows stay as last drawn
@@ -534,6 +555,7 @@ int32_t hb_plant_set_contact_model(hb_ctx* ctx, const hb_contact_config* cfg) {
   if (!ground) HB_TRY(scenario_off(ctx));   // the scenario belongs to contact model 1 (and gives the wrench back)
   if (!ground) HB_TRY(profile_draw_off(ctx));   // ... and so does the profile draw
   if (!ground) HB_TRY(field_draw_off(ctx));     // ... and the field draw
+  if (!ground) HB_TRY(scan_off(ctx));           // ... and the height scan
   ctx->contact_cfg = ground ? *cfg : hb_contact_config{};
   if (!ground) ctx->terrain_on = false;   // the terrain belongs to contact model 1
   if (!ground) ctx->profile_on = false;   // ... and so does the terrain profile

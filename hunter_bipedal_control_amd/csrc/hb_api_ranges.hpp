@@ -252,6 +252,7 @@ int32_t hb_debug_graph_state(hb_ctx* ctx, int64_t* out2) {
 
 int32_t hb_set_chunks(hb_ctx* ctx, int32_t n_chunks) {
   HB_ENTER_ARGS(n_chunks < 1 || n_chunks > kMaxRanges);
+  HB_FAIL_IF(n_chunks > 1 && ctx->scan_on, HB_ERR_STATE, "hb_set_chunks: a height scan is in force (hb_plant_set_height_scan): the scan runs on the whole batch only, turn it off first");
   HB_TRY(hb_sync(ctx));
   ctx->n_chunks = n_chunks;
   ctx->graph_disabled = false;  // a new set of ranges gets a new chance to capture

@@ -170,6 +170,14 @@ inline PlantForm plant_form(int contact_mode, bool joints_on, bool terrain_on, b
   return {field_on ? G::Field : profile_on ? G::Profile : modelvar_on ? G::Varied : terrain_on ? G::Terrain : G::Level, joints_on, hybrid};
 }
 
+// Height scan (hb_plant_scan): which form of k_plant_scan a launch takes — the plant's ground the scan samples, by the order of plant_form
+// (a height field or a profile before a terrain, a terrain before the level ground).  The values are hb_scan.hpp's SCAN_*: the template
+// argument GROUND of its routines.  A model variation changes no ground: without a terrain the varied kernels step on the level record.
+enum class ScanGround { None = 0, Plane = 1, Profile = 2, Field = 3 };
+inline ScanGround scan_ground(bool terrain_on, bool profile_on, bool field_on) {
+  return field_on ? ScanGround::Field : profile_on ? ScanGround::Profile : terrain_on ? ScanGround::Plane : ScanGround::None;
+}
+
 // LQ approximation: trips of this many nodes per wavefront (k_lq_trip).  Longer trips fill the lanes of the value phase better (16 nodes:
 // all 64), shorter ones keep small batches spread over the chip and balance them finer: the longest trip that still gives every
 // wavefront slot of the chip (12 per CU) four trips of the CONCURRENT batch — 16 nodes from 2048 instances up, 8 at 1024, 4 at 512

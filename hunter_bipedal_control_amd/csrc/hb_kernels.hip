@@ -1533,6 +1533,38 @@ __global__ __launch_bounds__(64) void k_plant_field_draw(FieldDrawBatch fd, hb_f
     for (int k = cx.lane; k < GroundField::size; k += cx.nlanes) gf.hdr[size_t(GroundField::size) * i + k] = map_s[k];
 }
 
+// ---- height scan (hb_plant_scan, hb_scan.hpp): one wavefront per instance ------------------------------------------------------------------
+// The pose, the decision to skip and the decision to clear are read by every lane from the same words (wave-uniform).  The instance's 1024
+// old heights are staged in LDS (8 KB, consecutive lanes on consecutive words) ahead of a workgroup barrier, so the in-place update reads
+// every old height before it writes any and a node without a return finds the old height of its shifted index there.  Lane l then takes
+// blocks l + 64 m, m = 0 .. 3, of each channel that is on — 16 nodes, four consecutive ones per block — so a pass of the wavefront stores
+// one contiguous 2 KB run of heights, 32 B per lane, and 256 B of flags.  GROUND (hb_scan.hpp SCAN_*) is picked on the host (hb_forms.hpp
+// scan_ground): gnd is the plant's ground record with gstride doubles per instance (null / 0 for the level ground), fz the heights of its
+// field.  itot: RespawnBatch::itot, or null without a respawn configuration in force.
+template <int GROUND>
+__global__ __launch_bounds__(64) void k_plant_scan(ScanBatch sb, hb_height_scan_config K, unsigned count, const double* __restrict__ q,
+                                                   const double* __restrict__ rbd, const int* __restrict__ itot, const double* __restrict__ gnd,
+                                                   int gstride, const double* __restrict__ fz, GroundFieldBatch gf, double ground_z) {
+  const int i = blockIdx.x;
+  if (i >= sb.B) return;
+  const DeviceCtx cx;
+  __shared__ double old[GroundField::nz];
+  __shared__ int cnt[64];
+  ScanIo io;
+  io.q = q + 16 * size_t(i);
+  io.rbd = rbd + HB_NRBD * size_t(i);
+  io.itot = itot ? itot + HB_RS_NI * size_t(i) : nullptr;
+  io.gnd = gnd ? gnd + size_t(gstride) * i : nullptr;
+  io.fz = fz ? fz + size_t(Field::nz) * i : nullptr;
+  io.hdr = gf.hdr + size_t(GroundField::size) * i;
+  io.z = gf.z + size_t(GroundField::nz) * i;
+  io.k = sb.k + 2 * size_t(i);
+  io.episode_seen = sb.episode_seen + i;
+  io.n_returns = sb.n_returns + i;
+  io.returned = sb.returned + size_t(GroundField::nz) * i;
+  scan_instance<GROUND>(cx, K, K.instance_offset + uint32_t(i), count, ground_z, io, old, cnt);
+}
+
 // ---- profile draw at respawn (hb_plant_set_profile_draw, hb_profiledraw.hpp): one wavefront per instance, ahead of k_plant_respawn --------
 // Every lane reads k_plant_respawn's decision from the instance's still unchanged record (the same words: wave-uniform), and a wavefront
 // whose instance stays leaves after those loads.  A respawning wavefront appends the log row of the finished episode (all lanes, from the
@@ -1998,6 +2030,7 @@ __global__ void k_estimator_reset(int B, double* xhat, double* P, double* yaw_la
 #include "hb_api_refgen.hpp"
 #include "hb_api_plant.hpp"
 #include "hb_api_episode.hpp"
+#include "hb_api_scan.hpp"
 #include "hb_api_est.hpp"
 #include "hb_api_lcm.hpp"
 #include "hb_api_ranges.hpp"

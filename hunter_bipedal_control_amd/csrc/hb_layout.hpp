@@ -16,6 +16,7 @@
 #include "hb_ground.hpp"
 #include "hb_profiledraw.hpp"
 #include "hb_fielddraw.hpp"
+#include "hb_scan.hpp"
 
 namespace {
 using namespace hb;
@@ -380,6 +381,22 @@ constexpr void fields(GroundFieldBatch& g, size_t, F&& f) {
   HB_FIELD(g.hdr, GroundField::size); HB_FIELD(g.z, GroundField::nz);
 }
 
+// height scan (hb_plant_set_height_scan, hb_scan.hpp), allocated by the first call that gives a configuration: the lattice index of grid
+// node (0, 0) at the last scan (k), the episode index that scan saw (episode_seen; below zero: the map is cleared), the number of returns
+// (n_returns; -1: the last scan skipped the instance) and the return flag of every node in the pitch numbering (returned).  The scanned
+// map itself goes to GroundFieldBatch::hdr / z.
+struct ScanBatch {
+  int B;
+  int* k;
+  int* episode_seen;
+  int* n_returns;
+  unsigned char* returned;
+};
+template <class F>
+constexpr void fields(ScanBatch& c, size_t, F&& f) {
+  HB_FIELD(c.k, 2); HB_FIELD(c.episode_seen, 1); HB_FIELD(c.n_returns, 1); HB_FIELD(c.returned, GroundField::nz);
+}
+
 // GaitBatch (hb_gait.hpp): the schedule, the template, the rate limiter and the velocity history are slot-major
 template <class F>
 constexpr void fields(GaitBatch& g, size_t, F&& f) {
@@ -460,6 +477,7 @@ static_assert(sizeof(ActuatorBatch) == kPtr /*B*/ + n_fields<ActuatorBatch>() * 
 static_assert(sizeof(RefgenBatch) == kPtr /*B*/ + n_fields<RefgenBatch>() * kPtr + kPtr /*init_stance*/, "describe every array of RefgenBatch in fields()");
 static_assert(sizeof(GroundBatch) == kPtr /*B*/ + n_fields<GroundBatch>() * kPtr, "describe every array of GroundBatch in fields()");
 static_assert(sizeof(GroundFieldBatch) == kPtr /*B*/ + n_fields<GroundFieldBatch>() * kPtr, "describe every array of GroundFieldBatch in fields()");
+static_assert(sizeof(ScanBatch) == kPtr /*B*/ + n_fields<ScanBatch>() * kPtr, "describe every array of ScanBatch in fields()");
 static_assert(sizeof(GaitBatch) == 2 * sizeof(int) + n_fields<GaitBatch>() * kPtr, "describe every array of GaitBatch in fields()");
 static_assert(sizeof(EstBatch) == kPtr /*B*/ + (n_fields<EstBatch>() + 2 /*res_rbd, res_x0*/) * kPtr, "describe every array of EstBatch in fields()");
 static_assert(sizeof(TickUpload) == n_fields<TickUpload>() * kPtr, "describe every array of TickUpload in fields()");

@@ -251,7 +251,7 @@ class ResidentLoop:
                  t_gait_start: float = 0.3, joint_ik: bool = True, substeps: int = 4, static_schedule_until: float = 0.0,
                  device_gait: bool = False, use_estimator: bool = False, sensor_config=None, sensor_bias=None, contact_config=None,
                  joint_model=None, actuator: str = "held", terrain=None, episode=None, model_variation=None, respawn=None, scenario=None,
-                 ground_map=None, profile_draw=None, field_draw=None):
+                 ground_map=None, profile_draw=None, field_draw=None, height_scan=None):
         """static_schedule_until > 0: the mode schedules are uploaded once for [-1, static_schedule_until] (at most
         HB_MAX_EVENTS events) instead of a sliding window per MPC call — no per-call host work for large batches.
         device_gait: the device gait manager produces the windows; step() builds no per-instance list and uploads no schedule, and
@@ -277,7 +277,7 @@ class ResidentLoop:
         profile.  ground_map="plant" is refused beside a field (the profile map is one-dimensional: ground_map="field" hands the field over),
         and so is respawn=.
         ground_map: the ground the controller's side plans and filters on (hb_ground_set_profile, hb_ground_set_field) — None: the level
-        plane; "field": the plant field's heights above the level ground of the start, as a field map (needs terrain=dict(field=...));
+        plane; "scan": a field map perceived from the plant's ground on the device (height_scan= below); "field": the plant field's heights above the level ground of the start, as a field map (needs terrain=dict(field=...));
         dict(field=dict(dir=, origin=, spacing=, heights=), per instance as terrain's field): a field map of the caller's, beside any plant
         ground; "plant": the
         plant's terrain profile with the start offset taken out (the knots of terrain["profile"] as given when relative, less the height of
@@ -307,7 +307,23 @@ class ResidentLoop:
         Needs respawn= and contact_config=, excludes terrain= and profile_draw= (one draw owns the ground) and is set after the scenario;
         ground_map="draw" sets the zero field map over the draw's grid and follow_map, so the controller's map follows every drawn
         field.  field_draw() / field_draw_log() read the current parameters and the log of the finished episodes.  (A field of the
-        host's, terrain=dict(field=...), stays refused beside respawn=.)"""
+        host's, terrain=dict(field=...), stays refused beside respawn=.)
+        height_scan: with ground_map="scan" the controller's field map is PERCEIVED from the plant's ground on the device
+        (hb_plant_set_height_scan) — a dict of abi.make_height_scan_config fields ({} or None: the ideal 32 x 32 sensor) plus, optionally,
+        every= (default mpc_every): plant_scan() runs at the top of every tick that is a multiple of it, ahead of the sensors and the
+        estimator and behind a respawn of the tick before; an abi.HbHeightScanConfig is taken as it is (every = mpc_every).  The zero field
+        map over the scan grid goes in first.  Needs contact_config=; composes with terrain=dict(plane= | profile= | field=) and with
+        profile_draw= / field_draw= that do not follow (a draw with follow_map beside it is a ValueError: one writer of the map).
+        height_scan() reads origin index, return counts and return flags of the last scan."""
+        if height_scan is not None and not (isinstance(ground_map, str) and ground_map == "scan"):
+            raise ValueError('height_scan= belongs to ground_map="scan"')
+        if isinstance(ground_map, str) and ground_map == "scan":
+            if contact_config is None:
+                raise ValueError('ground_map="scan" scans the ground of the ground-contact plant: give contact_config= as well')
+            for draw in (profile_draw, field_draw):
+                follows = draw.get("follow_map", 0) if isinstance(draw, dict) else getattr(draw, "follow_map", 0)
+                if draw is not None and follows:
+                    raise ValueError('ground_map="scan" beside a draw with follow_map: the scan and the draw would both write the controller\'s map')
         if field_draw is not None and (respawn is None or contact_config is None):
             raise ValueError("the field is drawn at respawn, for the ground-contact plant: give respawn= and contact_config= as well")
         if field_draw is not None and (terrain is not None or profile_draw is not None):
@@ -404,15 +420,15 @@ class ResidentLoop:
                         n = plane / np.linalg.norm(plane, axis=1, keepdims=True)
                         plane = np.concatenate([n, plane_under_contact_points(solver, q0, n)[:, None]], axis=1)
                 solver.plant_set_terrain(plane, terrain.get("mu"))
-        if isinstance(ground_map, str) and ground_map == "draw":
-            pass   # (the zero map goes in with the draw, below)
+        if isinstance(ground_map, str) and ground_map in ("draw", "scan"):
+            pass   # (the zero map goes in with the draw / the scan, below)
         elif isinstance(ground_map, str) and ground_map == "field":   # the plant field's heights above the level ground of the start
             if terrain is None or terrain.get("field") is None or contact_config is None:
                 raise ValueError('ground_map="field" hands the plant\'s height field to the controller: give terrain=dict(field=...) as well')
             solver.ground_set_field(plant_field["dir"], plant_field["origin"], plant_field["spacing"], plant_field["heights"])
         elif isinstance(ground_map, str):
             if ground_map != "plant" or terrain is None or terrain.get("profile") is None:
-                raise ValueError('ground_map is None, "plant" (with terrain=dict(profile=...)), "field" (with terrain=dict(field=...)), "draw" (with profile_draw=), dict(dir=..., knots=...) or dict(field=dict(dir=, origin=, spacing=, heights=))')
+                raise ValueError('ground_map is None, "plant" (with terrain=dict(profile=...)), "field" (with terrain=dict(field=...)), "draw" (with profile_draw= or field_draw=), "scan", dict(dir=..., knots=...) or dict(field=dict(dir=, origin=, spacing=, heights=))')
             solver.ground_set_profile(plant_map["n_knots"], plant_map["dir"], plant_map["knots"])
         elif ground_map is not None and ground_map.get("field") is not None:   # a field map of the caller's
             fld = ground_map["field"]
@@ -464,6 +480,19 @@ class ResidentLoop:
                 solver.ground_set_field(np.tile(np.array(field_draw.dir[:]), (self.B, 1)), np.zeros((self.B, 2)),
                                         np.tile(np.array(field_draw.spacing[:]), (self.B, 1)), np.zeros((self.B, nu, nw)))
             solver.plant_set_field_draw(field_draw)
+        self.scan_every = 0
+        if isinstance(ground_map, str) and ground_map == "scan":
+            self.scan_every = int(mpc_every)
+            if height_scan is None or isinstance(height_scan, dict):
+                fields = dict(height_scan or {})
+                self.scan_every = int(fields.pop("every", mpc_every))
+                height_scan = abi.make_height_scan_config(**fields)
+            if self.scan_every < 1:
+                raise ValueError("height_scan: every >= 1")
+            nu, nw = height_scan.n_nodes[0], height_scan.n_nodes[1]
+            solver.ground_set_field(np.tile(np.array(height_scan.dir[:]), (self.B, 1)), np.zeros((self.B, 2)),
+                                    np.tile(np.array(height_scan.spacing[:]), (self.B, 1)), np.zeros((self.B, nu, nw)))
+            solver.plant_set_height_scan(height_scan)
         # resident observation of the initial state
         rbd = np.zeros((self.B, 32))
         rbd[:, 0:3], rbd[:, 3:6], rbd[:, 6:16] = q0[:, 3:6], q0[:, 0:3], q0[:, 6:]
@@ -499,6 +528,8 @@ class ResidentLoop:
         DeviceLoop keeps them) instead of staying on the device; the loop itself is the same.  check_refgen False: the status of the
         reference generation is not read back (run)."""
         s = self.s
+        if self.scan_every and self.tick % self.scan_every == 0:
+            s.plant_scan()
         if self.use_estimator:
             s.plant_sense()
             s.estimator_update_resident(self.dt, to_resident=True)
@@ -574,6 +605,12 @@ class ResidentLoop:
         if not self.has_field_draw:
             raise ValueError("ResidentLoop was built without field_draw=")
         return self.s.plant_get_field_draw()
+
+    def height_scan(self) -> dict:
+        """Origin index, return counts and return flags of the last scan (HunterSolver.plant_get_height_scan)."""
+        if not self.scan_every:
+            raise ValueError('ResidentLoop was built without ground_map="scan"')
+        return self.s.plant_get_height_scan()
 
     def field_draw_log(self) -> dict:
         """The log of the finished episodes (HunterSolver.plant_get_field_draw_log)."""

@@ -43,6 +43,7 @@ ABI_SYMBOLS = [
     "hb_plant_set_scenario", "hb_plant_get_scenario", "hb_plant_get_scenario_log",
     "hb_plant_set_profile_draw", "hb_plant_get_profile_draw", "hb_plant_get_profile_draw_log",
     "hb_plant_set_field_draw", "hb_plant_get_field_draw", "hb_plant_get_field_draw_log",
+    "hb_plant_set_height_scan", "hb_plant_scan", "hb_plant_get_height_scan",
     "hb_ground_set_profile", "hb_ground_get_profile", "hb_ground_set_field", "hb_ground_get_field", "hb_ground_eval",
 ]
 # include/hunter_lcm.h
@@ -596,6 +597,25 @@ class HunterSolver:
         count, log = np.zeros(self.B, dtype=np.int32), np.zeros((self.B, cap, abi.HB_FD_LOG_W))
         self._check(self.lib.hb_plant_get_field_draw_log(self.ctx, _p(count), _p(log) if cap else None), "hb_plant_get_field_draw_log")
         return dict(count=count, log=log)
+
+    # ---- height scan (hb_plant_set_height_scan) ----------------------------------------------------------------------------------------
+    def plant_set_height_scan(self, cfg: "abi.HbHeightScanConfig" = None):
+        """cfg None: off (the map last written stays in force); abi.make_height_scan_config(...): plant_scan() writes the controller's field
+        map from the plant's ground.  Needs contact model 1 and a field map in force (ground_set_field: the zero map over the scan grid)."""
+        self._check(self.lib.hb_plant_set_height_scan(self.ctx, None if cfg is None else C.byref(cfg)), "hb_plant_set_height_scan")
+
+    def plant_scan(self):
+        """One scan of every instance; enqueue-only."""
+        self._check(self.lib.hb_plant_scan(self.ctx), "hb_plant_scan")
+
+    def plant_get_height_scan(self):
+        """-> dict(cfg: the configuration in force (dir as stored), origin_index[B][2] int32, n_returns[B] int32 (-1: the last scan skipped
+        the instance), returned[B][32][32] uint8 (1: the node had a return)), as the last scan left them."""
+        cfg = abi.HbHeightScanConfig()
+        org, n = np.zeros((self.B, 2), dtype=np.int32), np.zeros(self.B, dtype=np.int32)
+        ret = np.zeros((self.B, abi.HB_FIELD_MAX_NODES, abi.HB_FIELD_MAX_NODES), dtype=np.uint8)
+        self._check(self.lib.hb_plant_get_height_scan(self.ctx, C.byref(cfg), _p(org), _p(n), _p(ret)), "hb_plant_get_height_scan")
+        return dict(cfg=cfg, origin_index=org, n_returns=n, returned=ret)
 
     # ---- sensors from the plant (hb_plant_sense) and the estimator on them ------------------------------------------------
     def plant_set_sensor_model(self, sensor_cfg: "abi.HbSensorConfig" = None, gyro_bias=None, accel_bias=None):

@@ -995,6 +995,83 @@ int32_t hb_plant_get_field_draw(hb_ctx* ctx, double* row);
  * Synchronises.  HB_ERR_STATE without a field draw in force. */
 int32_t hb_plant_get_field_draw_log(hb_ctx* ctx, int32_t* count, double* log);
 
+/* ---- height scan: the controller's field map perceived from the plant's ground ----------------------------------------------------------
+ * With a height scan in force, hb_plant_scan writes the controller's field map (hb_ground_set_field below) of every instance from the
+ * ground the plant stands on, as an elevation sensor would: a robot-centred grid of limited range, noisy and with holes, registered with
+ * the true or the estimated base position, that remembers what it saw once the ground is under the body.  One kernel (k_plant_scan, one
+ * wavefront per instance); nothing crosses the bus.  Off by default; without a scan every call enqueues exactly what it enqueues without
+ * this block, and the scan writes only the field map's arrays and its own.
+ *
+ * Notation for one scan of instance i.  Every line is an IEEE double operation of its own, in the order written, brackets first, nothing
+ * fused.  p = q[0:3] of the plant;  e = p in register mode 0, e = the position rbd[3:6] of the resident observation in register mode 1;
+ * a = the stored unit direction (dir / sqrt(dir_x dir_x + dir_y dir_y)), b = (-a_y, a_x);  (nu, nw) = n_nodes, (du, dw) = spacing;
+ * gz = ground_z of the contact model.
+ *   1. If any of p[0:3], e[0:3] is not finite, or |(a_x e_x + a_y e_y) / du| or |(b_x e_x + b_y e_y) / dw| is >= 2^30, the scan of this
+ *      instance is skipped: header, heights, origin_index and returned stay as they are, n_returns = -1, and no float-to-int conversion of
+ *      such a value is reached.
+ *   2. ku = int(floor((a_x e_x + a_y e_y) / du)) - back[0];  kw likewise with b, dw, back[1];  org = (double(ku) du, double(kw) dw).  The
+ *      map's header is that of hb_ground_set_field for n_nodes, a, org, spacing (csrc/hb_ground.hpp ground_field_compose).
+ *   3. Node (iu, iw), iu < nu, iw < nw:  um = org_u + double(iu) du,  wm = org_w + double(iw) dw;  map point
+ *      m = (a_x um + b_x wm, a_y um + b_y wm);  sample point s = m in mode 0,  s = (m - e_xy) + p_xy in mode 1.
+ *   4. Truth: z_s is the height over s of the plane the plant would put a contact point at s on.  With the stored plane (n, d) of the
+ *      segment of the terrain profile in force, of the instance's plane with a terrain in force, or n = e_z and d = gz otherwise:
+ *      z_s = ((d - n_x s_x) - n_y s_y) / n_z.  With a height field in force the facet under s (the cell and triangle rule, one routine
+ *      with the step) is read from the four stored heights of its cell, as hb_ground_eval reads a field map:
+ *      z_s = z00 + e1 f1 + e2 f2 with the operands of hb_ground_set_field's height, taken from the plant's header and heights.  No unit
+ *      normal lies between a stored height and the scanned one: a sample point on a node of the field returns that node's height bit for
+ *      bit (through the facet's record it would return it to an ulp or two).
+ *      h = z_s - gz in mode 0,  h = ((z_s - p_z) + e_z) - gz in mode 1.
+ *   5. The node has a return iff (range == 0 or (s_x - p_x)^2 + (s_y - p_y)^2 <= range^2) and (dropout == 0 or u_n >= dropout).
+ *   6. With a return the map stores 0 + (h + noise z_n); with noise == 0 the term is not added (0 + h): the ideal height bit for bit,
+ *      whatever dropout is.
+ *   7. Without a return the node keeps what the map held at that lattice node: the old height of node (iu + ku - ku_old, iw + kw - kw_old),
+ *      or 0 if that index lies outside the old nu x nw or the map is cleared.  The map is cleared by hb_plant_set_height_scan (which zeroes
+ *      the heights at once), by the first scan after hb_plant_reset, and, while a respawn configuration is in force, when
+ *      itot[HB_RS_I_EPISODE_INDEX] of the instance differs from the value its last scan saw (the scan keeps that value per instance; the
+ *      respawn kernels are not touched).  Nodes beyond (nu, nw) store 0.  The update is in place; all old heights of an instance are read
+ *      before any is written.
+ *   8. Philox4x32-10 and Box-Muller are those of hb_plant_sense, u = (word + 0.5) 2^-32:  key = (seed low 32, seed high 32);
+ *      counter = (instance_offset + i, scan_count low 32, HB_HS_STREAM, block), scan_count = the hb_plant_scan calls since the set call
+ *      (the first scan has 0).  Block k, k = 0 .. 255: the normals z_n of the nodes n = 4 k .. 4 k + 3 in the PITCH numbering
+ *      n = iu HB_FIELD_MAX_NODES + iw (words (0, 1) give the first two, (2, 3) the other two); block 256 + k: word m is the uniform
+ *      u_n of node 4 k + m.  A node's draw does not depend on (nu, nw); the blocks of a channel that is off (noise == 0, dropout == 0) are not
+ *      generated.  A shard with instance_offset = the global index of its instance 0 reproduces its slice.
+ *   9. Outputs per instance: origin_index = (ku, kw), n_returns, returned[n] (0 / 1, pitch numbering).
+ * The scan does not run the steepness check of the field setters: the map's reader (ground_field_height) needs no normal, so a noisy map
+ * of any steepness is valid.
+ *
+ * State.  hb_plant_set_height_scan returns HB_ERR_STATE before hb_plant_reset, outside contact model 1, without a FIELD map in force (set
+ * the zero field map over the scan grid first, as for follow_map), while a field draw or a profile draw with follow_map is in force (their
+ * set calls refuse a follow_map while a scan is in force), and with hb_set_chunks > 1 (hb_set_chunks refuses more than one while a scan is
+ * in force).  While a scan is in force hb_ground_set_field and hb_ground_set_profile are refused and hb_ground_get_field reads the device
+ * arrays first.  HB_ERR_ARG (the configuration in force is kept) for a field outside the ranges below or a non-finite one.  cfg NULL: off;
+ * the map last written stays in force.  hb_plant_scan runs on the stream of the plant, between the ordering points of a writer of the
+ * resident observation; it does not synchronise and invalidates no captured graph.  hb_plant_get_height_scan synchronises; every
+ * pointer may be NULL.
+ * Out of scope: yaw-aligned grids, attitude error in the registration, occlusion, the instance-range / graph paths. */
+#define HB_HS_STREAM 0x48535331u /* third counter word; differs from HB_RS_STREAM, HB_SC_STREAM, HB_PD_STREAM and HB_FD_STREAM */
+typedef struct hb_height_scan_config {
+  int32_t n_nodes[2];     /* (nu, nw), 2 .. HB_FIELD_MAX_NODES: the scan grid = the field map it writes */
+  int32_t back[2];        /* cells of the grid behind / right of the cell the registration point is in, 0 .. n - 2 */
+  double dir[2];          /* direction a of the grid, |dir| > 0, normalised as the terrain profile normalises it */
+  double spacing[2];      /* (du, dw) > 0 */
+  double range;           /* >= 0; 0: no limit.  A node farther than this, horizontally, from the TRUE base has no return */
+  double noise;           /* >= 0: standard deviation of the additive height noise per return, m */
+  double dropout;         /* 0 <= dropout < 1: probability that a return is lost */
+  int32_t register_mode;  /* 0: the map is registered with the plant's base position; 1: with the resident estimate (translation only) */
+  int32_t reserved;       /* 0 */
+  uint64_t seed;
+  uint32_t instance_offset;
+  int32_t pad;            /* 0 */
+} hb_height_scan_config;
+/* cfg NULL: off; the map last written stays in force. */
+int32_t hb_plant_set_height_scan(hb_ctx* ctx, const hb_height_scan_config* cfg);
+/* One scan of every instance, enqueue-only.  HB_ERR_STATE without a scan in force. */
+int32_t hb_plant_scan(hb_ctx* ctx);
+/* cfg: the configuration in force (dir as stored); origin_index[batch][2]; n_returns[batch]; returned[batch][32 * 32] in the pitch
+ * numbering, all as the last scan left them (zero before the first).  HB_ERR_STATE without a scan in force. */
+int32_t hb_plant_get_height_scan(hb_ctx* ctx, hb_height_scan_config* cfg, int32_t* origin_index, int32_t* n_returns, uint8_t* returned);
+
 /* ---- sensors from the plant: what LeggedController::updateStateEstimation reads, computed on the device -----------
  * hb_plant_sense turns the plant's state into the sensor arrays of hb_estimator_update and leaves them on the device
  * (plant-owned arrays [batch][4|3|3|10|10|10] and int [batch][4]); hb_estimator_update_resident /

@@ -561,6 +561,20 @@ class ReferenceManager {
                                    off ? nullptr : spacing.data(), off ? nullptr : heights.data()),
                "hb_ground_set_field");
   }
+  // The field map perceived from the plant's ground (hb_plant_set_height_scan; needs a field map in force: set the zero map over the scan
+  // grid with setGroundField first).  cfg nullptr: off, the map last written stays.  scanHeights(): one scan of every instance,
+  // enqueue-only.  getHeightScan: originIndex [batch][2], nReturns [batch], returned [batch][32 * 32] as the last scan left them.
+  void setHeightScan(const hb_height_scan_config* cfg) { ctx_.check(hb_plant_set_height_scan(ctx_.get(), cfg), "hb_plant_set_height_scan"); }
+  void scanHeights() { ctx_.check(hb_plant_scan(ctx_.get()), "hb_plant_scan"); }
+  hb_height_scan_config getHeightScan(std::vector<int32_t>& originIndex, std::vector<int32_t>& nReturns, std::vector<uint8_t>& returned) {
+    const size_t B = size_t(ctx_.batch());
+    hb_height_scan_config cfg{};
+    originIndex.assign(B * 2, 0);
+    nReturns.assign(B, 0);
+    returned.assign(B * HB_FIELD_MAX_NODES * HB_FIELD_MAX_NODES, 0);
+    ctx_.check(hb_plant_get_height_scan(ctx_.get(), &cfg, originIndex.data(), nReturns.data(), returned.data()), "hb_plant_get_height_scan");
+    return cfg;
+  }
   // initTime [batch], cmdVel [batch][4] = (vx, vy, vz, yaw rate); observation [batch][22] or nullptr = the resident one
   void preSolverRun(const vector_t& initTime, scalar_t timeHorizon, const vector_t& cmdVel, const vector_t* observation = nullptr) {
     const size_t B = size_t(ctx_.batch());

@@ -76,7 +76,27 @@ def make_loop(params, mu, pitch, ticks, static, joint_model, payload=None, respa
     return s, loop
 
 
-def run_curb(params, heights, at, ticks, joint_model=None, riser_slope=np.sqrt(3.0), ground_map=False):
+# the sensor of --scan: 32 x 32 nodes of 5 cm along the walk, the robot in the cell 0.35 m from the rear edge and in the middle across (the
+# window of --rough, carried along)
+SCAN_GRID = dict(n_nodes=(32, 32), back=(7, 15), dir=(1.0, 0.0), spacing=(0.05, 0.05))
+
+
+def map_args(handed, scan, how):
+    """ResidentLoop's ground_map / height_scan: the map perceived by the scan (scan: a dict of abi.make_height_scan_config fields), handed
+    over (`how`: "plant", "field" or "draw") or none."""
+    if scan is not None:
+        return dict(ground_map="scan", height_scan=dict(SCAN_GRID, **scan))
+    return dict(ground_map=how if handed else None)
+
+
+def map_label(handed, scan, told):
+    if scan is not None:
+        reg = "the estimate" if scan.get("register_mode") else "the plant's position"
+        return f"controller on the scanned map (noise {scan.get('noise', 0.0):g} m, range {scan.get('range', 0.0):g} m, dropout {scan.get('dropout', 0.0):g}, registered with {reg})"
+    return told if handed else "controller blind"
+
+
+def run_curb(params, heights, at, ticks, joint_model=None, riser_slope=np.sqrt(3.0), ground_map=False, scan=None):
     """One batch: instance i trots along +x across a curb (height > 0) or a step down (< 0) of heights[i] whose riser starts `at` ahead of the
     base origin of the start; ground_map: the controller is given the profile too -> (episode record, segment under the points and the base at the end, wall seconds of the ticks)."""
     B = len(heights)
@@ -86,7 +106,7 @@ def run_curb(params, heights, at, ticks, joint_model=None, riser_slope=np.sqrt(3
         # and over a riser of slope sqrt(3) (n_z = 0.5) the standing height of 0.62 m reads 0.31 m
         loop = ResidentLoop(s, params, ["trot"] * B, np.tile([0.2, 0.0, 0.0, 0.0], (B, 1)), contact_config=dict(fall_height=0.2), joint_model=joint_model,
                             terrain=dict(profile=dict(dir=np.tile([1.0, 0.0], (B, 1)), knots=[curb_profile(h, at, riser_slope) for h in heights]), relative=True),
-                            episode=dict(slip_speed=0.05), ground_map="plant" if ground_map else None)
+                            episode=dict(slip_speed=0.05), **map_args(ground_map, scan, "plant"))
         s.sync()
         t0 = time.perf_counter()
         loop.run(ticks)
@@ -100,7 +120,7 @@ def run_curb(params, heights, at, ticks, joint_model=None, riser_slope=np.sqrt(3
 ROUGH_STEPS, ROUGH_CELL = 8, 0.05
 
 
-def run_rough(params, robots, ticks, amp_max, joint_model=None, ground_map=False):
+def run_rough(params, robots, ticks, amp_max, joint_model=None, ground_map=False, scan=None):
     """One batch: instance i trots along +x over a rough field of its own (seed i) with bump amplitude amp_max * (i % 8) / 7, 32 x 32 nodes of
     5 cm, from 0.35 m behind the start to 1.2 m ahead of it; ground_map: the controller is given the field too (hb_ground_set_field)
     -> (amplitude per instance, episode record, wall seconds of the ticks)."""
@@ -114,7 +134,7 @@ def run_rough(params, robots, ticks, amp_max, joint_model=None, ground_map=False
         # (fall_height 0.2 as in run_curb: the fall test is measured along the normal of the facet under the base origin)
         loop = ResidentLoop(s, params, ["trot"] * B, np.tile([0.2, 0.0, 0.0, 0.0], (B, 1)), contact_config=dict(fall_height=0.2), joint_model=joint_model,
                             terrain=dict(field=fields, relative=True), static_schedule_until=ticks * 0.002 + horizon + 1.5, episode=dict(slip_speed=0.05),
-                            ground_map="field" if ground_map else None)
+                            **map_args(ground_map, scan, "field"))
         s.sync()
         t0 = time.perf_counter()
         loop.run(ticks)
@@ -205,7 +225,7 @@ RANDOM_CURBS = dict(kinds=abi.HB_PD_ALL, dir=(1.0, 0.0), height_lo=-0.03, height
                     steps_hi=4, run_lo=0.2, run_hi=0.3, mu_lo=0.7, mu_hi=0.7, seed=3)
 
 
-def run_random_curbs(params, robots, ticks, max_ticks, joint_model=None, ground_map=False):
+def run_random_curbs(params, robots, ticks, max_ticks, joint_model=None, ground_map=False, scan=None):
     """Repeated episodes on a newly drawn ground each -> (log of the draw, respawn totals, wall seconds of the ticks)."""
     B = robots
     s = HunterSolver(params, batch=B, max_nodes=108)
@@ -215,7 +235,7 @@ def run_random_curbs(params, robots, ticks, max_ticks, joint_model=None, ground_
         loop = ResidentLoop(s, params, ["trot"] * B, np.tile([0.2, 0.0, 0.0, 0.0], (B, 1)), contact_config=dict(fall_height=0.2), joint_model=joint_model,
                             static_schedule_until=ticks * 0.002 + horizon + 1.5, episode=dict(slip_speed=0.05),
                             respawn=dict(RANDOMIZE_RESPAWN, max_ticks=max_ticks),
-                            profile_draw=dict(RANDOM_CURBS, log_capacity=min(abi.HB_PD_LOG_MAX, ticks // 8 + 1)), ground_map="draw" if ground_map else None)
+                            profile_draw=dict(RANDOM_CURBS, log_capacity=min(abi.HB_PD_LOG_MAX, ticks // 8 + 1)), **map_args(ground_map, scan, "draw"))
         s.sync()
         t0 = time.perf_counter()
         loop.run(ticks)
@@ -259,7 +279,7 @@ RANDOM_ROUGH = dict(kinds=abi.HB_FD_ALL, dir=(1.0, 0.0), n_nodes=(32, 32), spaci
                     amp_lo=0.0, slope_u_lo=-0.1, slope_u_hi=0.1, slope_w_lo=-0.1, slope_w_hi=0.1, mu_lo=0.7, mu_hi=0.7, seed=4)
 
 
-def run_random_rough(params, robots, ticks, max_ticks, amp_max, joint_model=None, ground_map=False):
+def run_random_rough(params, robots, ticks, max_ticks, amp_max, joint_model=None, ground_map=False, scan=None):
     """Repeated episodes on a newly composed height field each -> (log of the draw, respawn totals, wall seconds of the ticks, the largest
     amplitude drawn).  amp_max is cut to what the draw's slope bound admits on this grid beside the tilt: (0.1 + 2 A / 0.05)^2 * 2 <= 2.9
     gives A <= 0.0276 m (a seeded field of --rough is scaled down as a whole instead)."""
@@ -273,7 +293,7 @@ def run_random_rough(params, robots, ticks, max_ticks, amp_max, joint_model=None
                             static_schedule_until=ticks * 0.002 + horizon + 1.5, episode=dict(slip_speed=0.05),
                             respawn=dict(RANDOMIZE_RESPAWN, max_ticks=max_ticks),
                             field_draw=dict(RANDOM_ROUGH, amp_hi=amp_max, log_capacity=min(abi.HB_FD_LOG_MAX, ticks // 8 + 1)),
-                            ground_map="draw" if ground_map else None)
+                            **map_args(ground_map, scan, "draw"))
         s.sync()
         t0 = time.perf_counter()
         loop.run(ticks)
@@ -404,33 +424,43 @@ def main():
     ap.add_argument("--rough", type=int, metavar="N_TICKS", help="N_TICKS ticks on a seeded rough height field per robot, bump amplitude 0 .. --rough-max over the batch (--robots); one read-back")
     ap.add_argument("--rough-max", type=float, default=0.035, help="largest bump amplitude of --rough, metres")
     ap.add_argument("--readback", action="store_true", help="also time the per-tick read-back loop on the two sweeps")
+    ap.add_argument("--scan", action="store_true", help="--random-rough / --random-curbs / --rough / --curb with the controller on a field map PERCEIVED from the plant's ground on the device (hb_plant_set_height_scan: 32 x 32 nodes of 5 cm carried with the robot), between blind and --ground-map")
+    ap.add_argument("--scan-noise", type=float, default=0.0, metavar="S", help="standard deviation of the height noise per return of --scan, metres")
+    ap.add_argument("--scan-range", type=float, default=0.0, metavar="R", help="range of --scan, metres from the base (0: no limit)")
+    ap.add_argument("--scan-dropout", type=float, default=0.0, metavar="P", help="probability that a return of --scan is lost")
+    ap.add_argument("--scan-register", action="store_true", help="--scan registered with the estimated base position instead of the plant's")
     args = ap.parse_args()
+    if args.scan and args.ground_map:
+        ap.error("--scan and --ground-map: one source of the controller's map at a time")
+    if args.scan and not (args.curb or args.rough or args.random_rough or args.random_curbs):
+        ap.error("--scan goes with --random-rough, --random-curbs, --rough or --curb")
+    scan = dict(noise=args.scan_noise, range=args.scan_range, dropout=args.scan_dropout, register_mode=1 if args.scan_register else 0) if args.scan else None
     params = ingest.load_packaged()
     jm = {} if args.joint_model else None
     if args.curb:
-        rec, seg, wall = run_curb(params, CURBS, args.curb_at, args.ticks, joint_model=jm, riser_slope=args.riser_slope, ground_map=args.ground_map)
-        print(f"-- curb sweep, {'controller on the ground map' if args.ground_map else 'controller blind'}, B = {len(CURBS)}, riser of slope {args.riser_slope:.3g} {args.curb_at} m ahead, {args.ticks} ticks, run(): {1e3 * wall / args.ticks:.3f} ms per tick")
+        rec, seg, wall = run_curb(params, CURBS, args.curb_at, args.ticks, joint_model=jm, riser_slope=args.riser_slope, ground_map=args.ground_map, scan=scan)
+        print(f"-- curb sweep, {map_label(args.ground_map, scan, 'controller on the ground map')}, B = {len(CURBS)}, riser of slope {args.riser_slope:.3g} {args.curb_at} m ahead, {args.ticks} ticks, run(): {1e3 * wall / args.ticks:.3f} ms per tick")
         table("height", CURBS, rec)
         print("   segment under the four contact points and the base at the end (0 before the riser, 1 on it, 2 beyond):", seg.tolist())
         return
     for mapped in ([False, True] if args.ground_map else [False]) if args.rough else []:   # (--ground-map: the same rows next to the blind ones)
-        amp, rec, wall = run_rough(params, args.robots, args.rough, args.rough_max, joint_model=jm, ground_map=mapped)
-        print(f"-- rough ground, controller {'on the field map' if mapped else 'blind'}, {'joint model' if args.joint_model else 'ideal joints'}, "
+        amp, rec, wall = run_rough(params, args.robots, args.rough, args.rough_max, joint_model=jm, ground_map=mapped, scan=scan)
+        print(f"-- rough ground, {map_label(mapped, scan, 'controller on the field map')}, {'joint model' if args.joint_model else 'ideal joints'}, "
               f"B = {args.robots}, {args.rough} ticks, run() and one read-back: {wall:.3f} s, {1e3 * wall / args.rough:.3f} ms per tick")
         print_rough(amp, rec)
     if args.rough:
         return
     if args.random_rough:
-        log, tot, wall, amp = run_random_rough(params, args.robots, args.random_rough, args.max_ticks, args.rough_max, joint_model=jm, ground_map=args.ground_map)
-        print(f"-- a height field composed per episode, {'controller on the field map that follows' if args.ground_map else 'controller blind'}, "
+        log, tot, wall, amp = run_random_rough(params, args.robots, args.random_rough, args.max_ticks, args.rough_max, joint_model=jm, ground_map=args.ground_map, scan=scan)
+        print(f"-- a height field composed per episode, {map_label(args.ground_map, scan, 'controller on the field map that follows')}, "
               f"{'joint model' if args.joint_model else 'ideal joints'}, B = {args.robots}, {args.random_rough} ticks, episodes of at most {args.max_ticks} "
               f"ticks, bump amplitude up to {amp:.4f} m, run() and one read-back: {wall:.3f} s, {1e3 * wall / args.random_rough:.3f} ms per tick")
         print(f"   episodes {int(tot['EPISODES'].sum())}: fallen {int(tot['N_FALLEN'].sum())}, non-finite {int(tot['N_NONFINITE'].sum())}, timed out {int(tot['N_TIMEOUT'].sum())}")
         print_random_rough(log)
         return
     if args.random_curbs:
-        log, tot, wall = run_random_curbs(params, args.robots, args.random_curbs, args.max_ticks, joint_model=jm, ground_map=args.ground_map)
-        print(f"-- a ground drawn per episode, {'controller on the map that follows' if args.ground_map else 'controller blind'}, "
+        log, tot, wall = run_random_curbs(params, args.robots, args.random_curbs, args.max_ticks, joint_model=jm, ground_map=args.ground_map, scan=scan)
+        print(f"-- a ground drawn per episode, {map_label(args.ground_map, scan, 'controller on the map that follows')}, "
               f"{'joint model' if args.joint_model else 'ideal joints'}, B = {args.robots}, {args.random_curbs} ticks, episodes of at most {args.max_ticks} "
               f"ticks, run() and one read-back: {wall:.3f} s, {1e3 * wall / args.random_curbs:.3f} ms per tick")
         print(f"   episodes {int(tot['EPISODES'].sum())}: fallen {int(tot['N_FALLEN'].sum())}, non-finite {int(tot['N_NONFINITE'].sum())}, timed out {int(tot['N_TIMEOUT'].sum())}")
