@@ -176,6 +176,7 @@ int32_t hb_tick_resident(hb_ctx* ctx, double dt_est, const double* quat, const d
   if (!ctx || !quat || !ang_vel_local || !lin_acc_local || !joint_pos || !joint_vel || !contact_flag || !t_now || !cmd_vel || !(dt_est > 0.0) ||
       !(horizon > 0.0))
     return HB_ERR_ARG;
+  HB_FAIL_IF(ctx->rg_ready && rg_horizon_over_knot_bound(ctx->rg_cfg, horizon), HB_ERR_ARG, RG_KNOT_BOUND_TEXT("hb_tick_resident"));
   HB_FAIL_IF(ctx->respawn_on, HB_ERR_STATE, "hb_tick_resident: a respawn configuration is in force (hb_plant_set_respawn): the instance-range / graph paths do not consume its pending flags; clear it first");
   if (ctx->n_chunks <= 1) {  // one stream: the four calls themselves (enqueue-only forms)
     HB_TRY(hb_set_resident_time(ctx, t_now));

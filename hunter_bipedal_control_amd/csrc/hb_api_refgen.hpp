@@ -1,6 +1,12 @@
 // Host side, part 4: reference generation (hb_refgen_*) and the device gait manager (hb_gait_*).
 #pragma once
 
+// message of the refusal of a horizon that needs more joint-reference knots than the knot arrays hold (hb_refgen.hpp
+// rg_horizon_over_knot_bound): RG_MAX_KNOTS - 2 = 22 knots, 0.15 s apart
+static_assert(RG_MAX_KNOTS - 2 == 22, "the bound named in RG_KNOT_BOUND_TEXT and in include/hunter_hip.h");
+#define RG_KNOT_BOUND_TEXT(fn) \
+  fn ": with joint_ik the horizon must stay below 3.3 s (22 joint-reference knots, one every 0.15 s); a longer one is refused, not resampled onto fewer knots"
+
 extern "C" {
 
 int32_t hb_refgen_reset(hb_ctx* ctx, const hb_refgen_config* cfg, const double* latest_stance) {
@@ -64,6 +70,7 @@ static void launch_refgen(const hb_ctx* ctx, const Batch& b, RefgenBatch r, int 
 int32_t hb_refgen_update(hb_ctx* ctx, const double* t0, double horizon, const double* x_now, const double* cmd_vel, int32_t* status) {
   HB_ENTER_ARGS(!t0 || !cmd_vel || !(horizon > 0.0));
   HB_FAIL_IF(!ctx->rg_ready, HB_ERR_STATE, "hb_refgen_update: call hb_refgen_reset first");
+  HB_FAIL_IF(rg_horizon_over_knot_bound(ctx->rg_cfg, horizon), HB_ERR_ARG, RG_KNOT_BOUND_TEXT("hb_refgen_update"));
   for (int v : ctx->rg_have_schedule)
     HB_FAIL_IF(!v && !ctx->gait_on, HB_ERR_STATE, "hb_refgen_update: an instance has no mode schedule (hb_refgen_set_schedule)");
   HB_ENTER_DEVICE();

@@ -144,6 +144,14 @@ HB_HD void rg_make_target(const RefgenConfig& K, double t0, double horizon, cons
 
 // ---- joint reference by inverse kinematics (InverseKinematics.cpp:20-231 as restated in refgen.py) -----------------
 constexpr int RG_MAX_KNOTS = 24;  // targets resampled every 0.15 s: timeHorizon 3.0 s -> 21 knots; the last two slots hold the 2-knot target
+constexpr double RG_KNOT_STEP = 0.15;
+// calculateJointRef resamples every 0.15 s without a bound: floor(((t0 + horizon) - t0) / 0.15) + 1 knots.  The knot arrays hold
+// RG_MAX_KNOTS - 2 of them, so with joint_ik a horizon of (RG_MAX_KNOTS - 2) * 0.15 = 3.3 s or more has no faithful tables here and the
+// entry points refuse it (hb_refgen_update, hb_tick_resident; the host emulator's emu_refgen).  The 1e-9 keeps the rounding of
+// (t0 + horizon) - t0 — below 5e-10 for t0 up to 2^21 s — from carrying an accepted horizon over the bound.
+HB_HD bool rg_horizon_over_knot_bound(const RefgenConfig& K, double horizon) {
+  return K.joint_ik != 0 && horizon >= (RG_MAX_KNOTS - 2) * RG_KNOT_STEP - 1e-9;
+}
 
 // Work arrays of the IK of one (instance, leg).  They are indexed by loop counters, so as thread-private arrays they sit in
 // scratch memory; the kernel gives every thread one of these in LDS instead.
@@ -817,7 +825,9 @@ HB_HD int refgen_plan(const DevModel& M, const RefgenConfig& K, int n_ev, const 
   // ---- target knots: the 2-knot command target, or its 0.15 s resampling with IK joint references (calculateJointRef)
   int nk = 2;
   if (K.joint_ik) {
-    const int n = int(floor((tf_h - t0) / 0.15)) + 1;
+    const int n = int(floor((tf_h - t0) / RG_KNOT_STEP)) + 1;
+    // (the clamp is an unreachable guard of the knot arrays: every entry point refuses the horizons that would need more knots,
+    // rg_horizon_over_knot_bound — clamped knots would be spread over the horizon, which is not what the reference computes)
     if (n > 2) nk = n > RG_MAX_KNOTS - 2 ? RG_MAX_KNOTS - 2 : n;
   }
   if (nk == 2) {

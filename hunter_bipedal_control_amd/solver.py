@@ -832,7 +832,9 @@ class HunterSolver:
                     "hb_refgen_set_schedule")
 
     def refgen_update(self, t0, horizon, x_now, cmd_vel, want_status=True):
-        """want_status=False: the enqueue-only form (no device synchronisation; status later through refgen_status())."""
+        """want_status=False: the enqueue-only form (no device synchronisation; status later through refgen_status()).
+        With joint_ik in the configuration the horizon must stay below 3.3 s (22 joint-reference knots, one every 0.15 s): a longer
+        one raises HunterHipError (HB_ERR_ARG), here and in tick_resident, instead of tables resampled onto fewer knots."""
         status = np.zeros(self.B, dtype=np.int32) if want_status else None
         x = None if x_now is None else _f64(x_now, (self.B, 22))
         self._check(self.lib.hb_refgen_update(self.ctx, _p(_f64(t0, (self.B,))), C.c_double(horizon), _p(x), _p(_f64(cmd_vel, (self.B, 4))),

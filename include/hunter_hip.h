@@ -1371,7 +1371,11 @@ int32_t hb_refgen_set_schedule(hb_ctx* ctx, int32_t inst_begin, int32_t inst_cou
  * status[batch] (may be NULL): 0 ok, 1 a swing phase runs out of the schedule, 2 grid longer than max_nodes.
  * With status == NULL the call is ENQUEUE-ONLY: the host arrays are copied into library-owned pinned staging (they are the
  * caller's again on return), no device synchronisation takes place, and the status words are read later with
- * hb_refgen_get_status — a driver that feeds a batch every tick can then run a few ticks ahead of the device. */
+ * hb_refgen_get_status — a driver that feeds a batch every tick can then run a few ticks ahead of the device.
+ * With joint_ik the joint reference has one knot every 0.15 s, floor(horizon / 0.15) + 1 of them, and the library holds 22: a horizon
+ * of 22 * 0.15 - 1e-9 = 3.3 s or more is HB_ERR_ARG (here and in hb_tick_resident; nothing is enqueued, the tables keep their
+ * contents) — the reference resamples without a bound, and tables on fewer knots would differ from its tables under status 0.
+ * Without joint_ik the horizon is bounded by max_nodes alone (status 2). */
 int32_t hb_refgen_update(hb_ctx* ctx, const double* t0, double horizon, const double* x_now, const double* cmd_vel,
                          int32_t* status);
 /* Status words of the last hb_refgen_update (synchronises). */

@@ -313,10 +313,12 @@ int emu_hoqp_generic(int n, int n_levels, const int* mA, const int* mD, const do
 }
 #include "../../hunter_bipedal_control_amd/csrc/hb_refgen.hpp"
 extern "C" {
-// device reference generation of one instance on the host
+// device reference generation of one instance on the host; -1 (HB_ERR_ARG) where hb_refgen_update refuses the horizon (the joint-reference
+// knot bound, rg_horizon_over_knot_bound), with nothing written
 int emu_refgen(const hb_model* m, const hb::RefgenConfig* k, int n_ev, const double* ev, const int* modes, double t0, double horizon,
                const double* x_now, const double* cmd_vel, double* latest_stance, int max_nodes, int* n_nodes, double* t, int* mode,
                double* xref, double* swing) {
+  if (rg_horizon_over_knot_bound(*k, horizon)) return HB_ERR_ARG;
   DevModel d = make_dev_model(*m);
   std::vector<double> phases(size_t(4) * (RG_MAX_EVENTS + 1) * RG_PHASE, 0.0);
   return refgen_instance(d, *k, n_ev, ev, modes, t0, horizon, x_now, cmd_vel, latest_stance, phases.data(), max_nodes, n_nodes, t, mode,
