@@ -496,6 +496,27 @@ def make_height_scan_config(**fields) -> HbHeightScanConfig:
     return out
 
 
+HB_FOOTHOLD_MAX_SHIFT = 8   # hb_ground_set_foothold: candidates to either side of the nominal foothold at most
+HB_NO_FOOTHOLD = -2 ** 31   # hb_ground_get_foothold_choice: the shift of a foot the pass planned no foothold for
+
+
+class HbFootholdConfig(C.Structure):
+    """hb_foothold_config (include/hunter_hip.h): the planner's foothold mode on the ground map, hb_ground_set_foothold."""
+    _fields_ = [("mode", C.c_int32), ("n_shift", C.c_int32), ("shift_step", C.c_double), ("flat_tol", C.c_double)]
+
+
+FOOTHOLD_MODES = {"point": 0, "sole": 1}
+
+
+def make_foothold_config(mode, n_shift=3, shift_step=0.02, flat_tol=0.005) -> HbFootholdConfig:
+    """mode (always given by the caller): 0 / "point" (per contact point) or 1 / "sole"; the other defaults are placeholders nobody has
+    measured."""
+    out = HbFootholdConfig()
+    out.mode = FOOTHOLD_MODES[mode] if isinstance(mode, str) else int(mode)
+    out.n_shift, out.shift_step, out.flat_tol = int(n_shift), float(shift_step), float(flat_tol)
+    return out
+
+
 class HbJointGains(C.Structure):
     _fields_ = [(k, C.c_double) for k in ("kp_big_stance", "kp_big_swing", "kd_big", "kp_small_stance", "kp_small_swing", "kd_small",
                                           "kd_feet", "kp_position", "kd_position")]

@@ -15,7 +15,7 @@ $HIPCC $HB_HIPCC_FLAGS -shared -Rpass-analysis=kernel-resource-usage -o $OUT hb_
 grep -E "error|warning:" "$LOG" | grep -v "Wcomment" >&2 || true
 python3 - "$LOG" "$ABLATE" <<'PY'
 import re, sys
-hot = ["k_lqE", "k_lq_tripE", "6k_gaitE", "8k_refgenE", "k_refgen_ikE", "k_refgen_nodesE", "k_estimatorE", "15k_refgen_groundE", "18k_estimator_groundE", "15k_refgen_gfieldE", "18k_estimator_gfieldE", "k_warm_shiftE", "k_ric_bwdE", "k_ric_bwd4E", "k_ric_fwdE", "k_ric_fwd_wE", "5k_wbcE", "10k_wbc_certE", "6k_hwbcE", "11k_hwbc_certE", "k_ls_evalE", "k_ls_tail_evalE", "k_ls_eval_nodeE", "k_ls_tail_eval_nodeE", "k_ls_tail_decideE", "k_policy_evalE", "k_mpc_cert_nodesE", "k_mpc_cert_sweepE", "15k_plant_contactE", "14k_plant_jointsE", "14k_plant_hybridE", "22k_plant_contact_hybridE", "21k_plant_joints_hybridE", "15k_plant_terrainE", "22k_plant_terrain_jointsE", "22k_plant_terrain_hybridE", "29k_plant_terrain_joints_hybridE", "14k_plant_variedE", "21k_plant_varied_jointsE", "21k_plant_varied_hybridE", "28k_plant_varied_joints_hybridE", "15k_plant_profileE", "22k_plant_profile_jointsE", "22k_plant_profile_hybridE", "29k_plant_profile_joints_hybridE", "13k_plant_fieldE", "20k_plant_field_jointsE", "20k_plant_field_hybridE", "27k_plant_field_joints_hybridE", "15k_plant_episodeE", "15k_plant_respawnE", "21k_plant_respawn_fieldE", "18k_plant_field_drawE", "12k_plant_scanI", "20k_plant_profile_drawE", "16k_plant_scenarioE", "12k_plant_pushE"]
+hot = ["k_lqE", "k_lq_tripE", "6k_gaitE", "8k_refgenE", "k_refgen_ikE", "k_refgen_nodesE", "k_estimatorE", "15k_refgen_groundE", "18k_estimator_groundE", "15k_refgen_gfieldE", "20k_refgen_ground_soleE", "20k_refgen_gfield_soleE", "18k_estimator_gfieldE", "k_warm_shiftE", "k_ric_bwdE", "k_ric_bwd4E", "k_ric_fwdE", "k_ric_fwd_wE", "5k_wbcE", "10k_wbc_certE", "6k_hwbcE", "11k_hwbc_certE", "k_ls_evalE", "k_ls_tail_evalE", "k_ls_eval_nodeE", "k_ls_tail_eval_nodeE", "k_ls_tail_decideE", "k_policy_evalE", "k_mpc_cert_nodesE", "k_mpc_cert_sweepE", "15k_plant_contactE", "14k_plant_jointsE", "14k_plant_hybridE", "22k_plant_contact_hybridE", "21k_plant_joints_hybridE", "15k_plant_terrainE", "22k_plant_terrain_jointsE", "22k_plant_terrain_hybridE", "29k_plant_terrain_joints_hybridE", "14k_plant_variedE", "21k_plant_varied_jointsE", "21k_plant_varied_hybridE", "28k_plant_varied_joints_hybridE", "15k_plant_profileE", "22k_plant_profile_jointsE", "22k_plant_profile_hybridE", "29k_plant_profile_joints_hybridE", "13k_plant_fieldE", "20k_plant_field_jointsE", "20k_plant_field_hybridE", "27k_plant_field_joints_hybridE", "15k_plant_episodeE", "15k_plant_respawnE", "21k_plant_respawn_fieldE", "18k_plant_field_drawE", "12k_plant_scanI", "20k_plant_profile_drawE", "16k_plant_scenarioE", "12k_plant_pushE"]
 # the two-lane line-search kernels must leave room for a second wavefront on the SIMD: VGPR + AGPR <= 256
 shared_simd = ["k_ls_evalE", "k_ls_tail_evalE"]
 txt = open(sys.argv[1]).read()

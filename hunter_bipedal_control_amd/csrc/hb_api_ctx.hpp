@@ -185,6 +185,11 @@ struct hb_ctx {
   GroundFieldBatch gfield{};
   std::vector<double> gfield_hdr_host, gfield_z_host;
   bool gfield_on = false;
+  // foothold configuration (hb_ground_set_foothold): foothold_cfg.mode 1 while the sole mode is on (the planner then runs in its sole forms
+  // whenever a map is in force, hb_forms.hpp use_sole_forms); sole: the choice read-back, allocated by the first call that switches the
+  // mode on.  Nothing resets the configuration but its own setter.
+  hb_foothold_config foothold_cfg{};
+  SoleBatch sole{};
   // state estimator (allocated on the first hb_estimator_reset)
   EstBatch est{};
   hb_estimator_config est_cfg{};
@@ -485,7 +490,7 @@ static int32_t resident_write(hb_ctx* ctx, hipStream_t s, bool fence, F&& launch
 
 extern "C" {
 
-int32_t hb_version(void) { return 304; }
+int32_t hb_version(void) { return 305; }
 
 const char* hb_last_error(const hb_ctx* ctx) { return ctx ? ctx->err.c_str() : g_create_error.c_str(); }
 

@@ -119,4 +119,50 @@ int32_t hb_ground_get_field(hb_ctx* ctx, int32_t* n_nodes, double* dir, double* 
   return HB_OK;
 }
 
+// The foothold configuration (include/hunter_hip.h above hb_ground_set_foothold): which forms of the planner launch_refgen takes while a
+// map is in force (hb_forms.hpp use_sole_forms).  On / off changes what a range enqueues: graph_epoch, as ground_map_select.
+int32_t hb_ground_set_foothold(hb_ctx* ctx, const hb_foothold_config* cfg) {
+  HB_ENTER_ARGS(false);
+  hb_foothold_config c{};
+  if (cfg && cfg->mode != 0) {
+    if (const char* why = foothold_refusal(*cfg)) {
+      ctx->err = std::string("hb_ground_set_foothold: ") + why + " (the configuration in force is kept)";
+      return HB_ERR_ARG;
+    }
+    c = *cfg;
+  }
+  HB_ENTER_DEVICE();
+  HB_TRY(hb_sync(ctx));   // (a pass in flight still runs on the configuration it was launched with)
+  if (c.mode == 1 && ctx->foothold_cfg.mode != 1) {
+    SoleBatch& sb = ctx->sole;
+    HB_TRY(ensure_fields(ctx, sb));
+    std::vector<int32_t> none(size_t(ctx->B) * 2, RG_NO_FOOTHOLD);
+    HB_TRY(push(ctx, none.data(), sb, sb.shift, whole(ctx)));
+    HB_TRY(zero_field(ctx, sb, sb.defect));
+    HB_TRY(zero_field(ctx, sb, sb.level));
+  }
+  if (c.mode != ctx->foothold_cfg.mode) ++ctx->graph_epoch;
+  ctx->foothold_cfg = c;
+  return HB_OK;
+}
+
+int32_t hb_ground_get_foothold(hb_ctx* ctx, hb_foothold_config* out) {
+  HB_ENTER_ARGS(!out);
+  *out = ctx->foothold_cfg;
+  return HB_OK;
+}
+
+int32_t hb_ground_get_foothold_choice(hb_ctx* ctx, int32_t i0, int32_t cnt, int32_t* shift, double* defect, int32_t* level) {
+  HB_ENTER_ARGS(!range_ok(ctx, i0, cnt, 1));
+  HB_FAIL_IF(ctx->foothold_cfg.mode != 1, HB_ERR_STATE, "hb_ground_get_foothold_choice: the sole mode is off (hb_ground_set_foothold)");
+  HB_ENTER_DEVICE();
+  HB_HIP(hipStreamSynchronize(ctx->s_mpc));
+  SoleBatch& sb = ctx->sole;
+  const Range r{i0, cnt};
+  HB_TRY(pull(ctx, shift, sb, sb.shift, r));
+  HB_TRY(pull(ctx, defect, sb, sb.defect, r));
+  HB_TRY(pull(ctx, level, sb, sb.level, r));
+  return HB_OK;
+}
+
 }  // extern "C"

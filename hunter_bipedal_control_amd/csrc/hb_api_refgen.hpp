@@ -54,7 +54,15 @@ static void launch_refgen(const hb_ctx* ctx, const Batch& b, RefgenBatch r, int 
     r.cmd = g.cmd;
   }
   const GroundForm gf = use_ground_forms(ctx->ground_on, ctx->gfield_on);
-  if (gf == GroundForm::Field)   // the planner on the field map of these instances (hb_ground_set_field)
+  if (use_sole_forms(gf, ctx->foothold_cfg.mode)) {   // the two points of a foot planned as one sole (hb_ground_set_foothold)
+    const SoleBatch sb = view(ctx->sole, ctx->Nmax, i0, b.B);
+    if (gf == GroundForm::Field)
+      hipLaunchKernelGGL(k_refgen_gfield_sole, dim3((4 * b.B + 63) / 64), dim3(64), 0, s, b, r, view(ctx->gfield, ctx->Nmax, i0, b.B), ctx->dmodel,
+                         ctx->rg_cfg, horizon, init_flag, ctx->foothold_cfg, sb);
+    else
+      hipLaunchKernelGGL(k_refgen_ground_sole, dim3((4 * b.B + 63) / 64), dim3(64), 0, s, b, r, view(ctx->ground, ctx->Nmax, i0, b.B), ctx->dmodel,
+                         ctx->rg_cfg, horizon, init_flag, ctx->foothold_cfg, sb);
+  } else if (gf == GroundForm::Field)   // the planner on the field map of these instances (hb_ground_set_field)
     hipLaunchKernelGGL(k_refgen_gfield, dim3((4 * b.B + 63) / 64), dim3(64), 0, s, b, r, view(ctx->gfield, ctx->Nmax, i0, b.B), ctx->dmodel, ctx->rg_cfg,
                        horizon, init_flag);
   else if (gf == GroundForm::Profile)   // the planner on the ground map of these instances (hb_ground_set_profile)

@@ -153,6 +153,11 @@ inline GroundForm use_ground_forms(bool map_in_force, bool field_map_in_force = 
   return field_map_in_force ? GroundForm::Field : map_in_force ? GroundForm::Profile : GroundForm::None;
 }
 
+// Planner only: the sole forms (k_refgen_ground_sole, k_refgen_gfield_sole) while a map is in force AND the foothold configuration asks for
+// soles (hb_ground_set_foothold, mode 1).  Without a map there is nothing to be consistent with: the base form runs whatever the mode, and
+// a context that never made the call (mode 0) launches what it always launched.  The filter has no sole form.
+inline bool use_sole_forms(GroundForm gf, int foothold_mode = 0) { return gf != GroundForm::None && foothold_mode == 1; }
+
 // Plant step: which of the twenty-two step kernels a launch takes (hb_api_plant.hpp plant_launch names them).  Contact mode 0 is the pinned
 // stub (k_plant / k_plant_hybrid), which knows neither joints nor ground; in contact model 1 a height field or a profile (one ground at a
 // time: the host never has both in force) goes before a model variation (the field and profile kernels take the variation by pointer), a

@@ -1781,9 +1781,13 @@ struct NoMap {};
 // ONE body for the three forms that follow; MAP (hb_forms.hpp) is the map the planner puts its points to, g the
 // maps of the instances of b (NoMap, hb_layout.hpp GroundBatch or GroundFieldBatch).  The batches and the config come by reference: by
 // value the inlined body was allocated and scheduled further from the kernels it replaces.
-template <int MAP, class G>
+// SOLE = 1: the sole forms (hb_ground_set_foothold) — F the configuration, sb the choice read-back of the instances of b.  The partner
+// point's stance x, y, which the init_stance block below or the planner's refresh may write in this launch, are ordered inside
+// refgen_plan (fence and wave barrier, as the staging below: the four lanes of an instance share a wavefront).
+template <int MAP, class G, int SOLE = 0>
 __device__ __forceinline__ void refgen_step(const Batch& b, const RefgenBatch& r, const G& g, const DevModel* __restrict__ M, const hb_refgen_config& K,
-                                            double horizon, const int* __restrict__ init_flag) {
+                                            double horizon, const int* __restrict__ init_flag, const hb_foothold_config* F = nullptr,
+                                            const SoleBatch* sb = nullptr) {
   const int gid = blockIdx.x * blockDim.x + threadIdx.x;
   const int i = gid >> 2, foot = gid & 3;
   if (i >= b.B) return;   // (a whole group of four leaves together)
@@ -1821,10 +1825,19 @@ __device__ __forceinline__ void refgen_step(const Batch& b, const RefgenBatch& r
     gz = g.z + size_t(i) * GroundField::nz;
   }
   const size_t N = b.Nmax;
-  const int st = refgen_plan<MAP>(*M, K, r.n_ev[i], r.ev + size_t(i) * HB_MAX_EVENTS, r.modes + size_t(i) * (HB_MAX_EVENTS + 1), r.t0[i], horizon,
-                                  x_now, r.cmd + size_t(i) * 4, stance, r.phases + size_t(i) * 4 * (HB_MAX_EVENTS + 1) * RG_PHASE, b.Nmax,
-                                  b.n_nodes + i, b.t + size_t(i) * (N + 1), r.n_knots + i, r.knot_t + size_t(i) * RG_MAX_KNOTS,
-                                  r.knot_x + size_t(i) * RG_MAX_KNOTS * HB_NX, foot, 4, gnd, gz);
+  int st;
+  if constexpr (SOLE) {
+    const RgSole sole{F, sb->shift + 2 * size_t(i), sb->defect + 2 * size_t(i), sb->level + 2 * size_t(i)};
+    st = refgen_plan<MAP, 1>(*M, K, r.n_ev[i], r.ev + size_t(i) * HB_MAX_EVENTS, r.modes + size_t(i) * (HB_MAX_EVENTS + 1), r.t0[i], horizon,
+                             x_now, r.cmd + size_t(i) * 4, stance, r.phases + size_t(i) * 4 * (HB_MAX_EVENTS + 1) * RG_PHASE, b.Nmax,
+                             b.n_nodes + i, b.t + size_t(i) * (N + 1), r.n_knots + i, r.knot_t + size_t(i) * RG_MAX_KNOTS,
+                             r.knot_x + size_t(i) * RG_MAX_KNOTS * HB_NX, foot, 4, gnd, gz, sole);
+  } else {
+    st = refgen_plan<MAP>(*M, K, r.n_ev[i], r.ev + size_t(i) * HB_MAX_EVENTS, r.modes + size_t(i) * (HB_MAX_EVENTS + 1), r.t0[i], horizon,
+                          x_now, r.cmd + size_t(i) * 4, stance, r.phases + size_t(i) * 4 * (HB_MAX_EVENTS + 1) * RG_PHASE, b.Nmax,
+                          b.n_nodes + i, b.t + size_t(i) * (N + 1), r.n_knots + i, r.knot_t + size_t(i) * RG_MAX_KNOTS,
+                          r.knot_x + size_t(i) * RG_MAX_KNOTS * HB_NX, foot, 4, gnd, gz);
+  }
   // status of the instance: 2 (grid too long, from the lane of foot 0) wins, else 1 if any foot reported a phase without its events
   int any = st == 1 ? 1 : 0;
   any |= __shfl_xor(any, 1, 64);
@@ -1866,6 +1879,15 @@ __global__ __launch_bounds__(64) void k_refgen_ground(Batch b, RefgenBatch r, Gr
 __global__ __launch_bounds__(64) void k_refgen_gfield(Batch b, RefgenBatch r, GroundFieldBatch g, const DevModel* __restrict__ M, hb_refgen_config K,
                                                       double horizon, const int* __restrict__ init_flag) {
   refgen_step<MAP_FIELD>(b, r, g, M, K, horizon, init_flag);
+}
+// the sole forms of the two (hb_ground_set_foothold, mode 1; launched only while a map is in force and the mode is on)
+__global__ __launch_bounds__(64) void k_refgen_ground_sole(Batch b, RefgenBatch r, GroundBatch g, const DevModel* __restrict__ M, hb_refgen_config K,
+                                                           double horizon, const int* __restrict__ init_flag, hb_foothold_config F, SoleBatch sb) {
+  refgen_step<MAP_PROFILE, GroundBatch, 1>(b, r, g, M, K, horizon, init_flag, &F, &sb);
+}
+__global__ __launch_bounds__(64) void k_refgen_gfield_sole(Batch b, RefgenBatch r, GroundFieldBatch g, const DevModel* __restrict__ M, hb_refgen_config K,
+                                                           double horizon, const int* __restrict__ init_flag, hb_foothold_config F, SoleBatch sb) {
+  refgen_step<MAP_FIELD, GroundFieldBatch, 1>(b, r, g, M, K, horizon, init_flag, &F, &sb);
 }
 // joint-reference IK: eight lanes per (instance, leg), eight pairs per wavefront (hb_refgen.hpp refgen_ik_group)
 __global__ __launch_bounds__(64) void k_refgen_ik(Batch b, RefgenBatch r, const DevModel* __restrict__ M, hb_refgen_config K, double horizon) {

@@ -381,6 +381,20 @@ constexpr void fields(GroundFieldBatch& g, size_t, F&& f) {
   HB_FIELD(g.hdr, GroundField::size); HB_FIELD(g.z, GroundField::nz);
 }
 
+// choice read-back of the planner's sole forms (hb_ground_set_foothold, hb_refgen.hpp RgSole), allocated by the first call that switches
+// the sole mode on: per (instance, foot) the candidate taken for the first foothold the last pass planned (shift; INT32_MIN: none), its
+// defect and whether the fallback levelled it.  Written by the lane of the foot's toe.
+struct SoleBatch {
+  int B;
+  int* shift;
+  double* defect;
+  int* level;
+};
+template <class F>
+constexpr void fields(SoleBatch& c, size_t, F&& f) {
+  HB_FIELD(c.shift, 2); HB_FIELD(c.defect, 2); HB_FIELD(c.level, 2);
+}
+
 // height scan (hb_plant_set_height_scan, hb_scan.hpp), allocated by the first call that gives a configuration: the lattice index of grid
 // node (0, 0) at the last scan (k), the episode index that scan saw (episode_seen; below zero: the map is cleared), the number of returns
 // (n_returns; -1: the last scan skipped the instance) and the return flag of every node in the pitch numbering (returned).  The scanned
@@ -477,6 +491,7 @@ static_assert(sizeof(ActuatorBatch) == kPtr /*B*/ + n_fields<ActuatorBatch>() * 
 static_assert(sizeof(RefgenBatch) == kPtr /*B*/ + n_fields<RefgenBatch>() * kPtr + kPtr /*init_stance*/, "describe every array of RefgenBatch in fields()");
 static_assert(sizeof(GroundBatch) == kPtr /*B*/ + n_fields<GroundBatch>() * kPtr, "describe every array of GroundBatch in fields()");
 static_assert(sizeof(GroundFieldBatch) == kPtr /*B*/ + n_fields<GroundFieldBatch>() * kPtr, "describe every array of GroundFieldBatch in fields()");
+static_assert(sizeof(SoleBatch) == kPtr /*B*/ + n_fields<SoleBatch>() * kPtr, "describe every array of SoleBatch in fields()");
 static_assert(sizeof(ScanBatch) == kPtr /*B*/ + n_fields<ScanBatch>() * kPtr, "describe every array of ScanBatch in fields()");
 static_assert(sizeof(GaitBatch) == 2 * sizeof(int) + n_fields<GaitBatch>() * kPtr, "describe every array of GaitBatch in fields()");
 static_assert(sizeof(EstBatch) == kPtr /*B*/ + (n_fields<EstBatch>() + 2 /*res_rbd, res_x0*/) * kPtr, "describe every array of EstBatch in fields()");

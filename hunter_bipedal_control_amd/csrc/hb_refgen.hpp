@@ -680,6 +680,57 @@ __device__ __forceinline__ void refgen_ik_group(const DevModel& M, const RefgenC
 }
 #endif
 
+// ---- sole mode (hb_ground_set_foothold; include/hunter_hip.h above it): the two contact points of a foot planned as one sole ----------
+// What the sole mode of refgen_plan takes besides the map: the configuration and the choice read-back of the instance ([2] each, written
+// by the caller that plans the toe of a foot).
+struct RgSole {
+  const hb_foothold_config* cfg = nullptr;
+  int* shift = nullptr;
+  double* defect = nullptr;
+  int* level = nullptr;
+};
+constexpr int RG_NO_FOOTHOLD = -2147483647 - 1;   // INT32_MIN: the pass planned no foothold for the foot
+// Host: the reason hb_ground_set_foothold refuses a configuration that asks for a mode other than 0, or null.
+inline const char* foothold_refusal(const hb_foothold_config& c) {
+  const double inf = __builtin_inf();
+  if (c.mode != 1) return "mode is 0 (per contact point) or 1 (per sole)";
+  if (c.n_shift < 0 || c.n_shift > HB_FOOTHOLD_MAX_SHIFT) return "n_shift outside 0 .. HB_FOOTHOLD_MAX_SHIFT";
+  if (c.n_shift > 0 && !(c.shift_step > 0.0 && c.shift_step < inf)) return "shift_step must be finite and > 0 when n_shift > 0";
+  if (!(c.flat_tol >= 0.0 && c.flat_tol < inf)) return "flat_tol must be finite and >= 0";
+  return nullptr;
+}
+struct RgSoleSample { double delta, top; };
+// max that keeps a NaN once it has one, and takes one when it meets one
+HB_HD double rg_max_nan(double m, double v) { return m != m ? m : (v <= m ? m : v); }
+// S(cT, cH): five samples from the heel (q = 0) to the toe (q = 4), their largest distance from the chord and the highest of them.  No
+// contraction, as ground_height.  The five evaluations do not depend on one another: the field form issues their loads together.
+template <int MAP>
+HB_HD RgSoleSample rg_sole_sample(const double* gnd, const double* gz, double tx, double ty, double hx, double hy) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  const double dx = tx - hx, dy = ty - hy;
+  const double h0 = map_height<MAP>(gnd, gz, hx + 0.0 * dx, hy + 0.0 * dy);
+  const double h1 = map_height<MAP>(gnd, gz, hx + 0.25 * dx, hy + 0.25 * dy);
+  const double h2 = map_height<MAP>(gnd, gz, hx + 0.5 * dx, hy + 0.5 * dy);
+  const double h3 = map_height<MAP>(gnd, gz, hx + 0.75 * dx, hy + 0.75 * dy);
+  const double h4 = map_height<MAP>(gnd, gz, hx + 1.0 * dx, hy + 1.0 * dy);
+  const double dh = h4 - h0;
+  RgSoleSample s;
+  s.delta = rg_max_nan(rg_max_nan(rg_max_nan(0.0, fabs(h1 - (h0 + 0.25 * dh))), fabs(h2 - (h0 + 0.5 * dh))), fabs(h3 - (h0 + 0.75 * dh)));
+  s.top = rg_max_nan(rg_max_nan(rg_max_nan(rg_max_nan(h0, h1), h2), h3), h4);
+  return s;
+}
+// candidate m of the search order 0, +1, -1, +2, -2, ...
+HB_HD int rg_sole_candidate(int m) { return (m & 1) ? (m + 1) / 2 : -(m / 2); }
+// One point of a sole moved to candidate k along e
+HB_HD double rg_sole_shift(double p, int k, double step, double e) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  return p + (double(k) * step) * e;
+}
+
 // Planner step of one instance: swing phases of the four feet and the shooting grid.  `phases` is
 // [4][RG_MAX_EVENTS + 1][RG_PHASE]; `latest_stance` [4][3] persists between calls
 // (SwingTrajectoryPlanner::latestStanceposition_).  Returns 0, or 1 if a swing phase has no take-off / touch-down time
@@ -692,11 +743,15 @@ __device__ __forceinline__ void refgen_ik_group(const DevModel& M, const RefgenC
 // thread-private copy would be indexed dynamically) the latest stance position and every foothold stand next_position_z above the map under their own x, y, the centrifugal
 // term takes the height of the body above the map, and the target knots follow it (rg_make_target).  Nothing else differs.
 // MAP_FIELD: the same on the field map (hb_ground_set_field): gnd its header, gz its heights (global memory).
-template <int MAP = MAP_NONE>
+// SOLE = 1 (with a map only): the sole mode, sole = its configuration and read-back.  Every caller evaluates the sole of its foot in the
+// same operation order as the caller of the partner point, so the two take identical decisions without talking to one another; the
+// partner's latest stance x, y are read from latest_stance behind the refresh (the device orders the two inside the wavefront).
+template <int MAP = MAP_NONE, int SOLE = 0>
 HB_HD int refgen_plan(const DevModel& M, const RefgenConfig& K, int n_ev, const double* ev, const int* modes, double t0, double horizon,
                       const double* x_now, const double* cmd_vel, double* latest_stance, double* phases, int max_nodes,
                       int* n_nodes_out, double* t_out, int* n_knots_out, double* knot_t, double* knot_x, int foot0 = 0, int foot_step = 1,
-                      const double* gnd = nullptr, const double* gz = nullptr) {
+                      const double* gnd = nullptr, const double* gz = nullptr, const RgSole& sole = RgSole{}) {
+  static_assert(!SOLE || MAP != MAP_NONE, "the sole mode acts on a map");
   const int n_ph = n_ev + 1;
   RgTarget T;
   rg_make_target<MAP>(K, t0, horizon, x_now, cmd_vel, knot_x + size_t(RG_MAX_KNOTS - 2) * HB_NX, knot_x + size_t(RG_MAX_KNOTS - 1) * HB_NX, T,
@@ -733,12 +788,28 @@ HB_HD int refgen_plan(const DevModel& M, const RefgenConfig& K, int n_ev, const 
       }
     }
   }
+  if constexpr (SOLE) {
+    // the partner point's x, y of this launch (the refresh above, the init_stance block of the kernel) are in place before they are read
+#if defined(__HIP_DEVICE_COMPILE__)
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+#endif
+  }
   // ---- swing planner update (SwingTrajectoryPlanner::update) ----------------------------------------------------------
   int status = 0;
   for (int j = foot0; j < HB_NC; j += foot_step) {
     double* ls = latest_stance + 3 * j;
     ls[2] = K.next_position_z;
     if constexpr (MAP != MAP_NONE) ls[2] = map_height<MAP>(gnd, gz, ls[0], ls[1]) + K.next_position_z;
+    [[maybe_unused]] bool first_foothold = true;
+    if constexpr (SOLE) {
+      // stance memory: the sole under the two points as they stand, not shifted; a sole that does not lie flat is levelled on its top
+      const double* lt = latest_stance + 3 * (j & 1);
+      const double* lh = latest_stance + 3 * ((j & 1) + 2);
+      const RgSoleSample s = rg_sole_sample<MAP>(gnd, gz, lt[0], lt[1], lh[0], lh[1]);
+      if (!(s.delta <= sole.cfg->flat_tol)) ls[2] = s.top + K.next_position_z;
+      if (j < 2) { sole.shift[j] = RG_NO_FOOTHOLD; sole.defect[j] = 0.0; sole.level[j] = 0; }
+    }
     double last[3] = {ls[0], ls[1], ls[2]}, nxt[3] = {ls[0], ls[1], ls[2]};
     int last_final = 0;
     double* phj = phases + size_t(j) * (RG_MAX_EVENTS + 1) * RG_PHASE;
@@ -774,6 +845,8 @@ HB_HD int refgen_plan(const DevModel& M, const RefgenConfig& K, int n_ev, const 
           const Vec3<double> ca = rot * Vec3<double>(cmd_vel[3], 0.0, 0.0);
           const Vec3<double> v(T.cur[0], T.cur[1], 0.0);  // targets.x[0][0:3]
           const Vec3<double> body(T.at(t0, 6), T.at(t0, 7), T.at(t0, 8));
+          // (the sole mode below restates body + p_sh + p_sym + p_cent for both points of the foot, term by term and in this association:
+          // a change here is a change there, or the sole mode stops being the per-point mode on a plane — the anchor tests hold the two together)
           const Vec3<double> p_sh = (tf - t0) * (0.5 * v + 0.5 * cl) + bias;
           const Vec3<double> p_sym = (t_mid - tf) * v + 0.03 * (v - cl);
           double above = body.z;   // height of the body above the ground under it
@@ -781,7 +854,39 @@ HB_HD int refgen_plan(const DevModel& M, const RefgenConfig& K, int n_ev, const 
           const Vec3<double> p_cent = (0.5 * sqrt(above / 9.81)) * cross(v, ca);
           const Vec3<double> pn = body + p_sh + p_sym + p_cent;
           nxt[0] = pn.x; nxt[1] = pn.y; nxt[2] = K.next_position_z;
-          if constexpr (MAP != MAP_NONE) nxt[2] = map_height<MAP>(gnd, gz, pn.x, pn.y) + K.next_position_z;
+          if constexpr (MAP != MAP_NONE && !SOLE) nxt[2] = map_height<MAP>(gnd, gz, pn.x, pn.y) + K.next_position_z;
+          if constexpr (SOLE) {
+            // the nominal footholds of the toe and the heel by ONE routine (the caller's own point included: both callers of a foot see
+            // the same two points), then the candidates along the sole's axis, nearest first
+            const hb_foothold_config& F = *sole.cfg;
+            const Vec3<double> p_lead = (tf - t0) * (0.5 * v + 0.5 * cl);
+            const Mat3<double> rot_mid = rg_rot_zyx(bm);
+            auto nominal = [&](int jj) {
+              return body + (p_lead + rot_mid * Vec3<double>(K.feet_bias[jj][0], K.feet_bias[jj][1], K.feet_bias[jj][2])) + p_sym + p_cent;
+            };
+            const Vec3<double> pT = nominal(j & 1), pH = nominal((j & 1) + 2);
+            const double dx = pT.x - pH.x, dy = pT.y - pH.y;
+            const double len = sqrt(dx * dx + dy * dy);
+            const bool can_shift = len > 0.0 && len <= 1.79769313486231570815e+308;
+            const double ex = can_shift ? dx / len : 0.0, ey = can_shift ? dy / len : 0.0;
+            const int n_cand = can_shift ? 2 * F.n_shift + 1 : 1;
+            int k_best = 0, levelled = 1;
+            RgSoleSample s_best{0.0, 0.0};
+            for (int m = 0; m < n_cand; ++m) {
+              const int k = rg_sole_candidate(m);
+              const RgSoleSample s = rg_sole_sample<MAP>(gnd, gz, rg_sole_shift(pT.x, k, F.shift_step, ex), rg_sole_shift(pT.y, k, F.shift_step, ey),
+                                                         rg_sole_shift(pH.x, k, F.shift_step, ex), rg_sole_shift(pH.y, k, F.shift_step, ey));
+              const bool accept = s.delta <= F.flat_tol;
+              if (m == 0 || accept || s.delta < s_best.delta || (s_best.delta != s_best.delta && s.delta == s.delta)) { k_best = k; s_best = s; }
+              if (accept) { levelled = 0; break; }
+            }
+            const Vec3<double>& own = (j >> 1) ? pH : pT;
+            nxt[0] = rg_sole_shift(own.x, k_best, F.shift_step, ex);
+            nxt[1] = rg_sole_shift(own.y, k_best, F.shift_step, ey);
+            nxt[2] = (levelled ? s_best.top : map_height<MAP>(gnd, gz, nxt[0], nxt[1])) + K.next_position_z;
+            if (j < 2 && first_foothold) { sole.shift[j] = k_best; sole.defect[j] = s_best.delta; sole.level[j] = levelled; }
+            first_foothold = false;
+          }
           last_final = f_idx;
         }
         ph[0] = ts; ph[1] = tf;

@@ -251,7 +251,7 @@ class ResidentLoop:
                  t_gait_start: float = 0.3, joint_ik: bool = True, substeps: int = 4, static_schedule_until: float = 0.0,
                  device_gait: bool = False, use_estimator: bool = False, sensor_config=None, sensor_bias=None, contact_config=None,
                  joint_model=None, actuator: str = "held", terrain=None, episode=None, model_variation=None, respawn=None, scenario=None,
-                 ground_map=None, profile_draw=None, field_draw=None, height_scan=None):
+                 ground_map=None, profile_draw=None, field_draw=None, height_scan=None, foothold=None):
         """static_schedule_until > 0: the mode schedules are uploaded once for [-1, static_schedule_until] (at most
         HB_MAX_EVENTS events) instead of a sliding window per MPC call — no per-call host work for large batches.
         device_gait: the device gait manager produces the windows; step() builds no per-instance list and uploads no schedule, and
@@ -314,7 +314,12 @@ class ResidentLoop:
         estimator and behind a respawn of the tick before; an abi.HbHeightScanConfig is taken as it is (every = mpc_every).  The zero field
         map over the scan grid goes in first.  Needs contact_config=; composes with terrain=dict(plane= | profile= | field=) and with
         profile_draw= / field_draw= that do not follow (a draw with follow_map beside it is a ValueError: one writer of the map).
-        height_scan() reads origin index, return counts and return flags of the last scan."""
+        height_scan() reads origin index, return counts and return flags of the last scan.
+        foothold: the planner's foothold mode on the map (hb_ground_set_foothold) — None: the call is not made (per contact point); a dict
+        of abi.make_foothold_config fields, e.g. dict(mode="sole", n_shift=3, shift_step=0.02, flat_tol=0.005): with mode "sole" the toe
+        and the heel of a foot are planned as one sole, shifted along its axis off an edge or levelled on it.  These defaults are
+        UNMEASURED placeholders: nobody has tuned n_shift, shift_step or flat_tol yet.  An abi.HbFootholdConfig is taken as it is.  Acts
+        while a map is in force (any ground_map=); foothold_choice() reads what the last planner pass decided."""
         if height_scan is not None and not (isinstance(ground_map, str) and ground_map == "scan"):
             raise ValueError('height_scan= belongs to ground_map="scan"')
         if isinstance(ground_map, str) and ground_map == "scan":
@@ -493,6 +498,9 @@ class ResidentLoop:
             solver.ground_set_field(np.tile(np.array(height_scan.dir[:]), (self.B, 1)), np.zeros((self.B, 2)),
                                     np.tile(np.array(height_scan.spacing[:]), (self.B, 1)), np.zeros((self.B, nu, nw)))
             solver.plant_set_height_scan(height_scan)
+        self.has_foothold = foothold is not None
+        if foothold is not None:
+            solver.ground_set_foothold(abi.make_foothold_config(**foothold) if isinstance(foothold, dict) else foothold)
         # resident observation of the initial state
         rbd = np.zeros((self.B, 32))
         rbd[:, 0:3], rbd[:, 3:6], rbd[:, 6:16] = q0[:, 3:6], q0[:, 0:3], q0[:, 6:]
@@ -567,6 +575,12 @@ class ResidentLoop:
         status = self.s.refgen_status()
         if status.max() != 0:
             raise RuntimeError(f"reference generation failed: {status}")
+
+    def foothold_choice(self) -> dict:
+        """What the last planner pass in sole mode decided per (instance, foot) (HunterSolver.ground_get_foothold_choice)."""
+        if not self.has_foothold:
+            raise ValueError("ResidentLoop was built without foothold=")
+        return self.s.ground_get_foothold_choice()
 
     def episode(self, want_trace: bool = False) -> dict:
         """The episode records of the run so far (HunterSolver.plant_episode)."""

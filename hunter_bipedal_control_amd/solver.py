@@ -45,6 +45,7 @@ ABI_SYMBOLS = [
     "hb_plant_set_field_draw", "hb_plant_get_field_draw", "hb_plant_get_field_draw_log",
     "hb_plant_set_height_scan", "hb_plant_scan", "hb_plant_get_height_scan",
     "hb_ground_set_profile", "hb_ground_get_profile", "hb_ground_set_field", "hb_ground_get_field", "hb_ground_eval",
+    "hb_ground_set_foothold", "hb_ground_get_foothold", "hb_ground_get_foothold_choice",
 ]
 # include/hunter_lcm.h
 LCM_SYMBOLS = ["hb_lcm_fingerprint", "hb_lcm_encoded_size", "hb_lcm_field_count", "hb_lcm_encode", "hb_lcm_decode", "hb_lcm_frame", "hb_lcm_unframe",
@@ -462,6 +463,29 @@ class HunterSolver:
         out = dict(n_nodes=np.zeros((self.B, 2), dtype=np.int32), dir=np.zeros((self.B, 2)), origin=np.zeros((self.B, 2)), spacing=np.zeros((self.B, 2)),
                    heights=np.zeros((self.B, N, N)))
         self._check(self.lib.hb_ground_get_field(self.ctx, *[_p(a) for a in out.values()]), "hb_ground_get_field")
+        return out
+
+    # ---- foothold mode on the ground map (hb_ground_set_foothold) ------------------------------------------------------------------
+    def ground_set_foothold(self, cfg=None, **fields):
+        """cfg: an abi.HbFootholdConfig, or None with fields of abi.make_foothold_config (mode="sole" or "point" must be among them; n_shift,
+        shift_step, flat_tol); no argument at all: off.  Mode 1 plans the toe and the heel of a foot as one sole on the map in force."""
+        if cfg is None and fields:
+            cfg = abi.make_foothold_config(**fields)
+        self._check(self.lib.hb_ground_set_foothold(self.ctx, None if cfg is None else C.byref(cfg)), "hb_ground_set_foothold")
+
+    def ground_get_foothold(self):
+        """-> dict(mode, n_shift, shift_step, flat_tol) of the configuration in force (all zero while off)."""
+        out = abi.HbFootholdConfig()
+        self._check(self.lib.hb_ground_get_foothold(self.ctx, C.byref(out)), "hb_ground_get_foothold")
+        return dict(mode=out.mode, n_shift=out.n_shift, shift_step=out.shift_step, flat_tol=out.flat_tol)
+
+    def ground_get_foothold_choice(self, inst_begin=0, inst_count=None):
+        """What the last planner pass in sole mode decided for the first foothold of every foot -> dict(shift[count][2] int32
+        (abi.HB_NO_FOOTHOLD: none planned), defect[count][2], level[count][2] int32)."""
+        cnt = self.B - inst_begin if inst_count is None else inst_count
+        out = dict(shift=np.zeros((cnt, 2), dtype=np.int32), defect=np.zeros((cnt, 2)), level=np.zeros((cnt, 2), dtype=np.int32))
+        self._check(self.lib.hb_ground_get_foothold_choice(self.ctx, C.c_int32(inst_begin), C.c_int32(cnt), *[_p(a) for a in out.values()]),
+                    "hb_ground_get_foothold_choice")
         return out
 
     def ground_eval(self, inst, xy):

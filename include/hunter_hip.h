@@ -1504,6 +1504,54 @@ int32_t hb_ground_set_field(hb_ctx* ctx, const int32_t* n_nodes /*[batch][2]*/, 
 /* The field map in force (any pointer may be NULL): n_nodes[batch][2], dir[batch][2] as stored, origin, spacing [batch][2],
  * heights[batch][HB_FIELD_MAX_NODES][HB_FIELD_MAX_NODES] (zero beyond (nu, nw)).  HB_ERR_STATE unless a field map is in force. */
 int32_t hb_ground_get_field(hb_ctx* ctx, int32_t* n_nodes, double* dir, double* origin, double* spacing, double* heights);
+/* ---- sole-consistent footholds on the ground map, with edge avoidance -------------------------------------------------------------------
+ * On a map the planner puts every contact point to the ground on its own (the operands above hb_ground_set_profile).  The toe and the
+ * heel of one rigid sole are two such points: with a riser or a bump between them they are planned at different heights, a pitch the
+ * ground does not have.  Mode 1 of this configuration (one per context, off by default) plans the two points of a foot as ONE sole.  It
+ * acts only while a map is in force, in forms of the planner of their own (k_refgen_ground_sole, k_refgen_gfield_sole: no other kernel
+ * changes), and differs from the per-point forms in exactly the two operands below; the centrifugal term, the two target knots, the
+ * filter's height rows, the cone and the end-effector rows stay as they are.
+ * Foot l in {0, 1} has the contact points T = l (contact f1, the toe) and H = l + 2 (f2, the heel); the two carry the same contact flag
+ * in every mode.  G is the height function of the map in force, npz = next_position_z.
+ * Sole sample  S(cT, cH) -> (delta, top)  of two points (x, y):  the five sample points  c_q = cH + (q / 4) (cT - cH), q = 0 .. 4, per
+ * coordinate (q / 4 exact, one difference, one product, one sum);  h_q = G(c_q);  the chord  ch_q = h_0 + (q / 4) (h_4 - h_0);  the defect
+ * delta = max over q = 1 .. 3 of |h_q - ch_q|;  top = max over q = 0 .. 4 of h_q.  Every operation is rounded on its own (no fused
+ * multiply-add).  A NaN among the h_q makes delta (and top) NaN, and a NaN delta is never accepted.
+ *   latest stance position of a foot in contact, after the x, y refresh of its points:  (delta, top) = S(ls_T.xy, ls_H.xy), not shifted;
+ *       delta <= flat_tol:  ls_P.z = G(ls_P.xy) + npz  for P = T, H (the per-point values);  otherwise both  ls_P.z = top + npz, a level
+ *       sole on its highest sample.  (The memory of a foot in the air keeps its x, y and is put to the map in the same way.)
+ *   foothold of a swing phase (calNextFootPos):  pT, pH = the nominal footholds of the two points by the per-point formula (they differ in
+ *       feet_bias only);  e = (pT - pH).xy / |(pT - pH).xy|  (length = sqrt(dx dx + dy dy); zero or non-finite: no shifting, n_shift taken
+ *       as 0);  candidate k moves both points by the same vector,  c_k(P) = P.xy + (k shift_step) e,  with  (delta_k, top_k) =
+ *       S(c_k(pT), c_k(pH));  the candidates are tried in the order  k = 0, +1, -1, +2, -2, .., +n_shift, -n_shift  and the first with
+ *       delta_k <= flat_tol is accepted:  P.xy = c_k(P),  P.z = G(c_k(P)) + npz  — on a single plane today's foothold bit for bit.  If
+ *       none is accepted, k* = the candidate of the smallest delta_k (the earliest in the order among equals; a NaN loses against any
+ *       number), both points move to c_k*(P) and both get  z = top_k* + npz  (levelled).  The shifted foothold is the take-off point of the
+ *       next swing phase, as footholds chain today.
+ * mode 0: per contact point; 1: per sole.  n_shift: candidates to either side of the nominal foothold.  shift_step [m].  flat_tol [m]. */
+#define HB_FOOTHOLD_MAX_SHIFT 8
+typedef struct hb_foothold_config {
+  int32_t mode;        /* 0: per contact point (the behaviour without this call); 1: per sole */
+  int32_t n_shift;     /* 0 .. HB_FOOTHOLD_MAX_SHIFT: candidates to either side of the nominal foothold */
+  double  shift_step;  /* [m], > 0 when n_shift > 0 */
+  double  flat_tol;    /* [m], >= 0 */
+} hb_foothold_config;
+/* cfg NULL or mode 0: off (the stored configuration becomes all zero).  HB_ERR_ARG for a mode outside {0, 1}, n_shift outside
+ * 0 .. HB_FOOTHOLD_MAX_SHIFT, a non-finite or non-positive shift_step with n_shift > 0, a negative or non-finite flat_tol; a refused
+ * call keeps the configuration in force.  Legal any time after hb_create, with or without a map in force (it takes effect while one
+ * is, with every producer of the map: the two setters, a draw with follow_map, the height scan); synchronises, takes effect from the next
+ * pass, and switching the mode on or off re-captures the range graphs.  The configuration survives hb_refgen_reset, hb_estimator_reset,
+ * hb_plant_reset and a respawn. */
+int32_t hb_ground_set_foothold(hb_ctx* ctx, const hb_foothold_config* cfg);
+/* The configuration in force (all zero while off). */
+int32_t hb_ground_get_foothold(hb_ctx* ctx, hb_foothold_config* out);
+/* What the last planner pass in sole mode decided, per (instance, foot l), for the FIRST foothold it planned for that foot (any pointer
+ * may be NULL; [count][2]): shift = the k taken, or INT32_MIN if the pass planned no foothold for the foot (defect 0, level 0 then);
+ * defect = delta_k of that candidate; level = 1 if the fallback levelled the pair, else 0.  Switching the mode on clears the read-back
+ * to "no foothold"; a pass that does not run in sole mode (no map in force) leaves it as it is.  Synchronises.  HB_ERR_STATE while the
+ * mode is off. */
+int32_t hb_ground_get_foothold_choice(hb_ctx* ctx, int32_t inst_begin, int32_t inst_count, int32_t* shift /*[count][2]*/,
+                                      double* defect /*[count][2]*/, int32_t* level /*[count][2]*/);
 /* Node tables back to the host (any pointer may be NULL); layouts as in hb_mpc_set_references. */
 int32_t hb_mpc_get_references(hb_ctx* ctx, int32_t inst_begin, int32_t inst_count, int32_t* n_nodes, double* t,
                               int32_t* mode, double* x_ref, double* swing_ref);

@@ -561,6 +561,22 @@ class ReferenceManager {
                                    off ? nullptr : spacing.data(), off ? nullptr : heights.data()),
                "hb_ground_set_field");
   }
+  // The planner's foothold mode on the map (hb_ground_set_foothold): cfg nullptr or mode 0: per contact point; mode 1: the toe and the heel of
+  // a foot as one sole.  Legal with or without a map in force.  getFootholdChoice: shift, defect, level [batch][2] of the last planner pass
+  // in sole mode (shift INT32_MIN: no foothold planned for the foot).
+  void setFootholdConfig(const hb_foothold_config* cfg) { ctx_.check(hb_ground_set_foothold(ctx_.get(), cfg), "hb_ground_set_foothold"); }
+  hb_foothold_config getFootholdConfig() {
+    hb_foothold_config cfg{};
+    ctx_.check(hb_ground_get_foothold(ctx_.get(), &cfg), "hb_ground_get_foothold");
+    return cfg;
+  }
+  void getFootholdChoice(std::vector<int32_t>& shift, vector_t& defect, std::vector<int32_t>& level) {
+    const size_t B = size_t(ctx_.batch());
+    shift.assign(B * 2, 0);
+    defect.assign(B * 2, 0.0);
+    level.assign(B * 2, 0);
+    ctx_.check(hb_ground_get_foothold_choice(ctx_.get(), 0, int32_t(B), shift.data(), defect.data(), level.data()), "hb_ground_get_foothold_choice");
+  }
   // The field map perceived from the plant's ground (hb_plant_set_height_scan; needs a field map in force: set the zero map over the scan
   // grid with setGroundField first).  cfg nullptr: off, the map last written stays.  scanHeights(): one scan of every instance,
   // enqueue-only.  getHeightScan: originIndex [batch][2], nReturns [batch], returned [batch][32 * 32] as the last scan left them.

@@ -81,12 +81,46 @@ def make_loop(params, mu, pitch, ticks, static, joint_model, payload=None, respa
 SCAN_GRID = dict(n_nodes=(32, 32), back=(7, 15), dir=(1.0, 0.0), spacing=(0.05, 0.05))
 
 
+# --sole: the foothold configuration every mapped run of this process hands to ResidentLoop (None: the call is not made), and what
+# run_ticks has read of the choice read-back since: planned first footholds, those accepted off the nominal place, those levelled
+SOLE = None
+SOLE_STATS = dict(planned=0, shifted=0, levelled=0)
+
+
 def map_args(handed, scan, how):
     """ResidentLoop's ground_map / height_scan: the map perceived by the scan (scan: a dict of abi.make_height_scan_config fields), handed
-    over (`how`: "plant", "field" or "draw") or none."""
+    over (`how`: "plant", "field" or "draw") or none; with --sole and a map, the foothold configuration as well."""
+    sole = dict(foothold=SOLE) if SOLE is not None and (scan is not None or handed) else {}
     if scan is not None:
-        return dict(ground_map="scan", height_scan=dict(SCAN_GRID, **scan))
-    return dict(ground_map=how if handed else None)
+        return dict(ground_map="scan", height_scan=dict(SCAN_GRID, **scan), **sole)
+    return dict(ground_map=how if handed else None, **sole)
+
+
+def run_ticks(loop, ticks):
+    """loop.run(ticks); in sole mode in pieces of one MPC period, the choice read-back sampled after each (the only read-back of the run
+    besides the planner's status)."""
+    if not getattr(loop, "has_foothold", False):
+        loop.run(ticks)
+        return
+    done = 0
+    while done < ticks:
+        n = min(loop.mpc_every, ticks - done)
+        loop.run(n)
+        done += n
+        c = loop.foothold_choice()
+        planned = c["shift"] != abi.HB_NO_FOOTHOLD
+        SOLE_STATS["planned"] += int(planned.sum())
+        SOLE_STATS["shifted"] += int((planned & (c["shift"] != 0) & (c["level"] == 0)).sum())
+        SOLE_STATS["levelled"] += int((planned & (c["level"] == 1)).sum())
+
+
+def print_sole_shares():
+    if SOLE is None or SOLE_STATS["planned"] == 0:   # (a blind run beside the mapped one has none)
+        return
+    n = SOLE_STATS["planned"]
+    print(f"   sole mode (n_shift {SOLE['n_shift']}, step {SOLE['shift_step']:g} m, tolerance {SOLE['flat_tol']:g} m): of {SOLE_STATS['planned']} first footholds "
+          f"sampled once per MPC call, accepted off the nominal place {SOLE_STATS['shifted'] / n:.3f}, levelled by the fallback {SOLE_STATS['levelled'] / n:.3f}")
+    SOLE_STATS.update(planned=0, shifted=0, levelled=0)
 
 
 def map_label(handed, scan, told):
@@ -109,7 +143,7 @@ def run_curb(params, heights, at, ticks, joint_model=None, riser_slope=np.sqrt(3
                             episode=dict(slip_speed=0.05), **map_args(ground_map, scan, "plant"))
         s.sync()
         t0 = time.perf_counter()
-        loop.run(ticks)
+        run_ticks(loop, ticks)
         rec = loop.episode()
         wall = time.perf_counter() - t0
         return rec, s.plant_get_terrain_profile()["segment"], wall
@@ -137,7 +171,7 @@ def run_rough(params, robots, ticks, amp_max, joint_model=None, ground_map=False
                             **map_args(ground_map, scan, "field"))
         s.sync()
         t0 = time.perf_counter()
-        loop.run(ticks)
+        run_ticks(loop, ticks)
         rec = loop.episode()
         return amp, rec, time.perf_counter() - t0
     finally:
@@ -238,7 +272,7 @@ def run_random_curbs(params, robots, ticks, max_ticks, joint_model=None, ground_
                             profile_draw=dict(RANDOM_CURBS, log_capacity=min(abi.HB_PD_LOG_MAX, ticks // 8 + 1)), **map_args(ground_map, scan, "draw"))
         s.sync()
         t0 = time.perf_counter()
-        loop.run(ticks)
+        run_ticks(loop, ticks)
         log = loop.profile_draw_log()
         return log, loop.respawn_totals(), time.perf_counter() - t0
     finally:
@@ -296,7 +330,7 @@ def run_random_rough(params, robots, ticks, max_ticks, amp_max, joint_model=None
                             **map_args(ground_map, scan, "draw"))
         s.sync()
         t0 = time.perf_counter()
-        loop.run(ticks)
+        run_ticks(loop, ticks)
         log = loop.field_draw_log()
         return log, loop.respawn_totals(), time.perf_counter() - t0, amp_max
     finally:
@@ -429,7 +463,16 @@ def main():
     ap.add_argument("--scan-range", type=float, default=0.0, metavar="R", help="range of --scan, metres from the base (0: no limit)")
     ap.add_argument("--scan-dropout", type=float, default=0.0, metavar="P", help="probability that a return of --scan is lost")
     ap.add_argument("--scan-register", action="store_true", help="--scan registered with the estimated base position instead of the plant's")
+    ap.add_argument("--sole", action="store_true", help="--ground-map / --scan with the toe and the heel of a foot planned as one sole (hb_ground_set_foothold); prints the shares of first footholds shifted and levelled from the choice read-back, sampled once per MPC call: every sample is a synchronising read-back, so the ms per tick printed for a --sole run includes the sampling and is not comparable with a run without --sole")
+    ap.add_argument("--sole-shift", type=int, default=3, metavar="N", help="candidates of --sole to either side of the nominal foothold (unmeasured default)")
+    ap.add_argument("--sole-step", type=float, default=0.02, metavar="S", help="distance between candidates of --sole, metres (unmeasured default)")
+    ap.add_argument("--sole-tol", type=float, default=0.005, metavar="T", help="largest defect of a sole --sole takes for flat, metres (unmeasured default)")
     args = ap.parse_args()
+    if args.sole and not (args.ground_map or args.scan):
+        ap.error("--sole acts on the controller's map: give --ground-map or --scan as well")
+    if args.sole:
+        global SOLE
+        SOLE = dict(mode="sole", n_shift=args.sole_shift, shift_step=args.sole_step, flat_tol=args.sole_tol)
     if args.scan and args.ground_map:
         ap.error("--scan and --ground-map: one source of the controller's map at a time")
     if args.scan and not (args.curb or args.rough or args.random_rough or args.random_curbs):
@@ -442,12 +485,14 @@ def main():
         print(f"-- curb sweep, {map_label(args.ground_map, scan, 'controller on the ground map')}, B = {len(CURBS)}, riser of slope {args.riser_slope:.3g} {args.curb_at} m ahead, {args.ticks} ticks, run(): {1e3 * wall / args.ticks:.3f} ms per tick")
         table("height", CURBS, rec)
         print("   segment under the four contact points and the base at the end (0 before the riser, 1 on it, 2 beyond):", seg.tolist())
+        print_sole_shares()
         return
     for mapped in ([False, True] if args.ground_map else [False]) if args.rough else []:   # (--ground-map: the same rows next to the blind ones)
         amp, rec, wall = run_rough(params, args.robots, args.rough, args.rough_max, joint_model=jm, ground_map=mapped, scan=scan)
         print(f"-- rough ground, {map_label(mapped, scan, 'controller on the field map')}, {'joint model' if args.joint_model else 'ideal joints'}, "
               f"B = {args.robots}, {args.rough} ticks, run() and one read-back: {wall:.3f} s, {1e3 * wall / args.rough:.3f} ms per tick")
         print_rough(amp, rec)
+        print_sole_shares()
     if args.rough:
         return
     if args.random_rough:
@@ -457,6 +502,7 @@ def main():
               f"ticks, bump amplitude up to {amp:.4f} m, run() and one read-back: {wall:.3f} s, {1e3 * wall / args.random_rough:.3f} ms per tick")
         print(f"   episodes {int(tot['EPISODES'].sum())}: fallen {int(tot['N_FALLEN'].sum())}, non-finite {int(tot['N_NONFINITE'].sum())}, timed out {int(tot['N_TIMEOUT'].sum())}")
         print_random_rough(log)
+        print_sole_shares()
         return
     if args.random_curbs:
         log, tot, wall = run_random_curbs(params, args.robots, args.random_curbs, args.max_ticks, joint_model=jm, ground_map=args.ground_map, scan=scan)
@@ -465,6 +511,7 @@ def main():
               f"ticks, run() and one read-back: {wall:.3f} s, {1e3 * wall / args.random_curbs:.3f} ms per tick")
         print(f"   episodes {int(tot['EPISODES'].sum())}: fallen {int(tot['N_FALLEN'].sum())}, non-finite {int(tot['N_NONFINITE'].sum())}, timed out {int(tot['N_TIMEOUT'].sum())}")
         print_random_curbs(log)
+        print_sole_shares()
         return
     if args.randomize:
         log, tot, wall = run_randomize(params, args.robots, args.randomize, args.max_ticks, joint_model=jm, host_driven=args.host_driven)
